@@ -15,6 +15,7 @@ with the path's one exchange step, the all_gather of the 64-byte commitments ove
 
     python bench.py --gpus 1 --steps 3 --warmup 1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR     (what the last timed step computed, as DIR/*.npy)
 """
 import argparse
 import json
@@ -28,6 +29,43 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s
+DUMP_BLIND_SEED = 20260015      # --dump-outputs: the blinding rows of the last timed step (the other steps draw theirs from the OS)
+DUMP_SAMPLE_SEED = 20260016     # --dump-outputs: which coefficient columns and rows are written
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _limbs_f64(a):
+    """field elements / points as u64 limbs (..., m) -> (..., 2 m) float64: every u64 split into its u32 halves, low half first,
+    each exact in a float64"""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    return a.view(np.uint32).reshape(a.shape[:-1] + (2 * a.shape[-1],)).astype(np.float64)
+
+
+def dump_outputs(out_dir, hp, commitments, api):
+    """What the last timed step handed its caller, as out_dir/<name>.npy (float64; exact u32 limbs where the values are field
+    elements or curve points): the commitments of every column (gathered over ranks), the k-means results, a seeded sample of the
+    coefficient columns lagrange_to_coeff wrote and the extended coset of this rank's last column (always in the coset buffer,
+    however many columns it holds at a time).  Call right after the timed steps: relayout() overwrites the columns."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    cent, ind = hp.results()
+    arrays = {"commitments": _limbs_f64(commitments), "centroids": api.dequantize(cent, hp.P),
+              "centroid_cells": _limbs_f64(cent), "assignment_cells": _limbs_f64(ind)}
+    if hp.my_cols:
+        B = 32
+        cols = np.sort(rng.choice(hp.my_cols, size=min(32, hp.my_cols), replace=False))
+        rows = np.sort(rng.choice(hp.rows, size=min(4096, hp.rows), replace=False))
+        arrays["coeff_sample"] = np.stack([_limbs_f64(hp.d_cols.download((hp.rows, 4), offset=int(c) * hp.rows * B)[rows]) for c in cols])
+        arrays["coeff_sample_columns"] = np.asarray(hp.global_columns(), dtype=np.float64)[cols]
+        arrays["coeff_sample_rows"] = rows.astype(np.float64)
+        # the step writes the cosets block by block into d_ext; the last block starts at `last`
+        blk = min(hp.ext_cols, hp.my_cols)
+        last = (hp.my_cols - 1) // blk * blk
+        arrays["ext_last_column"] = _limbs_f64(hp.d_ext.download((4 * hp.rows, 4), offset=(hp.my_cols - 1 - last) * 4 * hp.rows * B))
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs would write {total} bytes"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def pmc_traffic_per_launch(kernel):
@@ -367,7 +405,14 @@ def main():
     ap.add_argument("--small", action="store_true", help="reduced problem for quick functional checks (not a valid bench line)")
     ap.add_argument("--verify-gather", action="store_true",
                     help="after the timed steps rank 0 re-runs the job unsharded and checks the gathered commitments against it (tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy; that step's blinding rows are seeded, so the same "
+                         "arguments give the same outputs from run to run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -424,10 +469,10 @@ def main():
     if dist is not None:
         dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
 
-    def one_step(timings=None):
+    def one_step(timings=None, blind_seed=None):
         """one pass of the hot path; with N > 1 it ends with the path's one exchange step, the all_gather of the 64-byte
         commitments of every rank's column shard (every rank then holds what the transcript absorbs next)"""
-        com = hp.step(timings)
+        com = hp.step(timings, blind_seed=blind_seed)
         if dist is not None:
             com = gather_commitments(dist, com, hp.shards, dev)
         return com
@@ -440,8 +485,9 @@ def main():
     # region has drained (vdb_profile_begin_deferred): the kernels run and overlap exactly as they do unprofiled
     api.profile_begin(deferred=True)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        commitments = one_step(timings)
+    for i in range(args.steps):
+        seeded = args.dump_outputs is not None and i == args.steps - 1
+        commitments = one_step(timings, blind_seed=cfg.get("blind_seed", DUMP_BLIND_SEED) if seeded else None)
     barrier()
     elapsed = time.perf_counter() - t0
     prof = api.profile_end()
@@ -450,6 +496,8 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, hp, commitments, api)
 
     gather_ok = None
     if args.verify_gather and rank == 0:

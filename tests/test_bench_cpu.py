@@ -68,3 +68,22 @@ def test_every_kernel_of_the_library_has_a_source_hash():
     for kernel in ("k_ntt_pass", "k_msm_accum", "k_msm_sort", "k_dist_head", "k_dist_tail", "k_perm_eval", "k_gate_eval"):
         assert len(h[kernel]) == 64
     assert h["k_ntt_pass"] != h["k_msm_accum"]
+
+
+def test_steps_must_be_positive():
+    import subprocess
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert res.returncode != 0 and "--steps must be at least 1" in res.stderr
+
+
+def test_dumped_limbs_are_exact():
+    """--dump-outputs writes field elements and points as their u32 limbs in float64: nothing is rounded"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    a = np.random.default_rng(3).integers(0, 2**64, size=(5, 3, 4), dtype=np.uint64)
+    a[0, 0] = [2**64 - 1, 0, 1, 2**53 + 1]
+    f = bench._limbs_f64(a)
+    assert f.dtype == np.float64 and f.shape == (5, 3, 8)
+    back = f[..., 0::2].astype(np.uint64) | (f[..., 1::2].astype(np.uint64) << np.uint64(32))
+    assert np.array_equal(back, a)

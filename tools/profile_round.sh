@@ -3,7 +3,7 @@
 # usage on the GPU box: bash tools/profile_round.sh r02e   (then, back in the container: python profiles/summarize.py r02e)
 set -e
 TAG=${1:-rXX}
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 # the source these profiles are measured on (profiles/srchash.py): summarize.py writes it into the summary's header
 python3 $R/profiles/srchash.py $R > $R/gpurun_out/prof_${TAG}_srchash.json

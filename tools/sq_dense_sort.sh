@@ -1,7 +1,7 @@
 #!/bin/bash
 # SQ counters of the MSM kernels on uniformly random (dense) scalars: gpurun -- 'bash tools/sq_dense_sort.sh'
 set -e
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_WAIT_ANY --output-format csv -d $R/gpurun_out/sqd -o sq -- python3 $R/tools/msm_ntt_micro.py 1024 > $R/gpurun_out/sqd.log 2>&1
 python3 - <<PY

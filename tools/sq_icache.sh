@@ -1,7 +1,7 @@
 #!/bin/bash
 # instruction-cache requests / misses per kernel of one bench step (rocprofv3 SQC counters): gpurun -- 'bash tools/sq_icache.sh'
 set -e
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU --output-format csv -d $R/gpurun_out/sqi -o sq -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-proof > $R/gpurun_out/sqi.log 2>&1
 python3 - <<PY

@@ -1,7 +1,7 @@
 #!/bin/bash
 # VALU instruction count per kernel of one bench step (rocprofv3 SQ counters): gpurun -- 'bash tools/sq_valu.sh'
 set -e
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE --output-format csv -d $R/gpurun_out/sqv -o sq -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-proof > $R/gpurun_out/sqv.log 2>&1
 python3 - <<PY
