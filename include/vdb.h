@@ -34,6 +34,10 @@ extern "C" {
 typedef struct { uint64_t l[4]; } vdb_fr;
 typedef struct { uint64_t l[4]; } vdb_fq;
 typedef struct { vdb_fq x, y; } vdb_g1;
+/* G2 point on the twist y^2 = x^3 + 3 / (9 + u) over Fq2 = Fq[u] / (u^2 + 1), affine: x = x[0] + x[1] u, y = y[0] + y[1] u, each
+ * coordinate a Montgomery Fq like vdb_g1's (so a halo2curves G2Affine {x: Fq2 {c0, c1}, y: Fq2 {c0, c1}} crosses as is); the
+ * identity is all zero. */
+typedef struct { vdb_fq x[2], y[2]; } vdb_g2;
 typedef struct vdb_srs vdb_srs;
 
 enum {
@@ -550,6 +554,29 @@ int vdb_mock_check_dev(const vdb_fr *stream_dev, uint64_t n_cells, const uint8_t
  * the cell and row i of the instance column).  Sets out->instances_unequal / first_instance and leaves the other fields alone. */
 int vdb_mock_check_instances_dev(const vdb_fr *stream_dev, uint64_t n_cells, const int64_t *instance_cells_dev, const vdb_fr *instances_dev,
                                  uint64_t n_instances, vdb_mock_report *out);
+
+/* ---- b7 Verify: the Verify arm of the reference's scaffold (SnarkCmd::Verify, src/scaffold/mod.rs:298-320) — halo2's
+ *      read_snark + verify_proof over a proof this library wrote (halo2_vectordb_amd/verifier.py drives them). -------------- */
+/* Status byte per point of vdb_g1_decompress_dev. */
+enum { VDB_G1_OK = 0, VDB_G1_NONCANONICAL = 1 /* x >= q, or the spare top bit that is not the sign is set */,
+       VDB_G1_NOT_ON_CURVE = 2 /* x^3 + 3 has no square root */, VDB_G1_BAD_IDENTITY = 3 /* x = 0 with a flag bit set */ };
+/* Replaces the point reads of halo2's TranscriptRead::read_point (G1Affine::from_bytes) for a whole proof at once: n 32-byte
+ * compressed encodings (x little-endian; bit sign_bit of the last byte — 6 or 7, as vdb_transcript_set_sign_bit — says y is odd;
+ * the identity is the all-zero encoding) -> n Montgomery affine points in out_dev (the identity and every rejected point as
+ * (0, 0)) and one VDB_G1_* status per point in status_dev.  Device pointers; blocks until done. */
+int vdb_g1_decompress_dev(const uint8_t *enc_dev, size_t n, uint32_t sign_bit, vdb_g1 *out_dev, uint8_t *status_dev);
+/* Replaces the MSM of halo2's verify_proof (the verifier's MSMKZG::eval, best_multiexp over arbitrary bases):
+ * out_host = sum_i scalars[i] points[i] for n arbitrary affine points (identity allowed) and Montgomery scalars below r, both in
+ * HBM.  Variable-base Pippenger: no window tables are built, the bases are used once.  n = 0 gives the identity. */
+int vdb_msm_points_dev(const vdb_g1 *points_dev, const vdb_fr *scalars_dev, size_t n, vdb_g1 *out_host);
+/* Host arithmetic (no GPU needed, no vdb_init): replaces halo2's KZG verifier key side.
+ * [s] G2 for the EIP-197 generator of G2 — the SRS's [tau]_2 (ParamsKZG::s_g2) from the key's scalar s (Montgomery Fr). */
+int vdb_g2_mul_generator(const vdb_fr *s, vdb_g2 *out);
+/* *ok = 1 when prod_i e(a[i], b[i]) = 1 in GT (the optimal ate pairing, one final exponentiation for the product), else 0 —
+ * Bn256::multi_miller_loop(...).final_exponentiation() == Gt::identity() of halo2's KZG verification.  Identities contribute 1;
+ * n = 0 accepts.  VDB_ERR_ARG when a coordinate is not below q or a point is not on its curve (G2's subgroup is not checked:
+ * the verifier's G2 points are the generator and [tau]_2 from vdb_g2_mul_generator). */
+int vdb_pairing_check(const vdb_g1 *a, const vdb_g2 *b, size_t n, int *ok);
 
 /* ---- b6 Poseidon: replaces poseidon::PoseidonChip<F,3,2> value semantics (T=3, RATE=2, R_F=8,
  *      R_P=57 as examples/merkle.rs:15-18; call sites src/gadget/vectordb.rs:180-182, 213-215) --- */
