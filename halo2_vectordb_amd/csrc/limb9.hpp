@@ -110,6 +110,36 @@ HD L9 l9_mul_shoup(const L9& v, const L9& w, const L9& wq) {
   shoup_core29<M>(r.l, v.l, w.l, wq.l);
   return r;
 }
+// Shoup companions (host and device code: the stage tables and the kernel-argument constants are built on the host, the inter-pass
+// records on the device, all from these two functions).  The nine 29-bit limbs of a < 2^256:
+HD void limbs29(const u256& a, uint32_t out[9]) {
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+    const int bit = 29 * k, wd = bit >> 5, sh = bit & 31;
+    uint64_t v = (uint64_t)a.w[wd] >> sh;
+    if (sh && wd + 1 < 8) v |= (uint64_t)a.w[wd + 1 < 8 ? wd + 1 : 0] << (32 - sh);
+    out[k] = (uint32_t)v & 0x1fffffffu;
+  }
+}
+// out[0..8]: the limbs of w (canonical, below r); out[9..17]: those of w' = floor(w 2^261 / r), by 261 steps of long division (the
+// remainder starts at w < r and stays below 2 r < 2^255 before each conditional subtraction; bit b of w' is bit b % 29 of limb b / 29)
+HD void shoup_pair29(const u256& w, uint32_t out[18]) {
+  limbs29(w, out);
+  const u256 p = mod_p<Fr>();
+  u256 r = w;
+#pragma unroll
+  for (int k = 8; k >= 0; k--) {
+    uint32_t d = 0;
+    for (int j = 28; j >= 0; j--) {
+      u256 s, t;
+      u256_add(s, r, r);
+      const uint32_t borrow = u256_sub(t, s, p);
+      r = borrow ? s : t;
+      d |= (borrow ^ 1u) << j;
+    }
+    out[9 + k] = d;
+  }
+}
 // (a1 * b1 + a2 * b2) / 2^261 (+ less than p) with one reduction; limbs of a1 and a2 together below 6 * 2^29
 template <class M>
 HD L9 l9_mul2(const L9& a1, const L9& b1, const L9& a2, const L9& b2) {

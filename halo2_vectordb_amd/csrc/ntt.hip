@@ -20,6 +20,7 @@
 
 #include "common.hpp"
 #include "limb9.hpp"
+#include "shoup_tables.hpp"
 
 namespace vdb {
 
@@ -59,9 +60,37 @@ struct NttPass {
   const uint32_t* sh_tab;
   uint32_t sh_res_log, sh_ns;     // resolution and number of entries (m / 2 >> sh_res_log)
   int32_t sh_max_s;               // radix-4 steps starting at stage s <= sh_max_s find both their stages' twiddles in the table
+  // the SA instantiations (VDB_NTT_SHOUP_ALL): every product by a constant is a Shoup product.  No LDS table of Montgomery-form stage
+  // twiddles then; the first step's omega_4 comes from the Shoup table, the radix-2 stage's twiddles from sh2_tab in global memory
+  const uint32_t* sh2_tab;        // sh_tab's layout at full resolution (m / 2 entries): the radix-2 stage of an odd-size pass
+  const uint4* tw_rec;            // non-last pass: tw_inter's entries as (w, w') limbs, 80 B each (k_shoup_records)
+  uint32_t zsh[3][18];            // coset == 1, 2: the factors of residues 0, 1, 2 (1 or s; zeta; zeta^2 — times s), plain and quotient
 };
 
 __device__ __forceinline__ uint32_t bitrev_s(uint32_t x, uint32_t bits) { return bits ? (__brev(x) >> (32 - bits)) : 0u; }
+// nine limbs of a kernel-argument constant
+__device__ __forceinline__ L9 kconst(const uint32_t* k) {
+  L9 r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.l[i] = k[i];
+  return r;
+}
+// nine limbs from a global table of 18-word entries (NttPass::sh_tab's layout; 8-byte aligned)
+__device__ __forceinline__ void ld_pair18(const uint32_t* e, L9& w, L9& wq) {
+  const uint2* q = reinterpret_cast<const uint2*>(e);
+  uint32_t t[18];
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    const uint2 v = q[i];
+    t[2 * i] = v.x;
+    t[2 * i + 1] = v.y;
+  }
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    w.l[i] = t[i];
+    wq.l[i] = t[9 + i];
+  }
+}
 
 // limbs below 2^32, value below 2^259 -> canonical eight words without a multiplication and without a carry pass of its own:
 // subtract q r with q = floor(top / (r_8 + 1)), top = l_8 + (l_7 >> 29) — the value's true top limb or one less (what limbs 0..6
@@ -128,19 +157,27 @@ __device__ __forceinline__ void ntt_static_steps(F&& f) {
     ntt_static_steps<CS, (s + 1 < CS ? s + 2 : s + 1), step + 1>(f);
   }
 }
-constexpr uint32_t ntt_spec_sh_res_log(uint32_t cs) { return cs == 8 ? 0u : 2u; }   // what ntt_dev's LDS budget gives 256- / 512-point passes
-template <bool LAST, bool VS = false, uint32_t CS = 0, uint32_t CS0 = 0, uint32_t CREN = 0>
+// what ntt_dev's LDS budget gives 256- / 512-point passes: the 512-point passes' table at half resolution once the Montgomery-form table
+// is gone (SA), which then holds both twiddles of the step at stage 6 too
+constexpr uint32_t ntt_spec_sh_res_log(uint32_t cs, bool sa) { return cs == 8 ? 0u : (sa ? 1u : 2u); }
+// `SA` (specialised instantiations only): every product by a constant is a Shoup product (NttPass::sh_tab, sh2_tab, tw_rec, zsh).  A
+// Shoup product of v (limbs below 6.1 * 2^29, the bound every Montgomery operand here already keeps) is below (1 + v / 2^261 + 2^-23) r
+// with exactly normalised limbs (shoup_core29) — below 1.14 r for the v < 22 r of these passes, as a Montgomery product by a normalised
+// twiddle is (v r / 2^261 + r) — so every limb and value bound of the carry schedule, the 14 r offsets and the stores without a final
+// subtraction holds unchanged.
+template <bool LAST, bool VS = false, uint32_t CS = 0, uint32_t CS0 = 0, uint32_t CREN = 0, bool SA = false>
 __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(const u256* __restrict__ in, u256* __restrict__ out,
                                                          const u256* __restrict__ tw, const u256* __restrict__ tw_inter, NttPass p,
                                                          uint32_t tiles_per_col) {
   extern __shared__ uint4 smem[];
   constexpr bool SPEC = CS > 0;
+  static_assert(!SA || ((CS == 8 || CS == 9) && !VS), "SA: the 256- and 512-point instantiations, not the virtual-column one");
   const uint32_t S = SPEC ? CS : p.S, P_logG = SPEC ? 10u - CS : p.logG, P_s0 = SPEC ? CS0 : p.s0, P_ren_mask = SPEC ? CREN : p.ren_mask;
-  const uint32_t P_sh_res_log = SPEC ? ntt_spec_sh_res_log(CS) : p.sh_res_log, P_sh_ns = SPEC ? ((1u << (CS ? CS - 1 : 0)) >> ntt_spec_sh_res_log(CS)) : p.sh_ns;
-  const int32_t P_sh_max_s = SPEC ? (int32_t)CS - 2 - (int32_t)ntt_spec_sh_res_log(CS) : p.sh_max_s;
+  const uint32_t P_sh_res_log = SPEC ? ntt_spec_sh_res_log(CS, SA) : p.sh_res_log, P_sh_ns = SPEC ? ((1u << (CS ? CS - 1 : 0)) >> ntt_spec_sh_res_log(CS, SA)) : p.sh_ns;
+  const int32_t P_sh_max_s = SPEC ? (int32_t)CS - 2 - (int32_t)ntt_spec_sh_res_log(CS, SA) : p.sh_max_s;
   const bool P_shoup = SPEC ? true : p.sh_tab != nullptr, P_blk0 = SPEC ? true : p.blk0 != 0;
   const uint32_t m = 1u << S, G = 1u << P_logG, T = m * G;
-  const uint32_t row = m + 1, NE = G * row, NW = m / 2 ? m / 2 : 1;
+  const uint32_t row = m + 1, NE = G * row, NW = SA ? 0u : (m / 2 ? m / 2 : 1);
   L9Planes D, W;
   D.a = smem;
   D.b = D.a + NE;
@@ -207,7 +244,8 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(const u256* __restrict
   }
 
   // stage twiddles 32 * omega_m^e = tw[e * n/m], as limbs
-  for (uint32_t e = tid; e < m / 2; e += NTT_THREADS) lds_put(W, e, l9_split(ld256(tw + ((size_t)e << (p.log_n - S)))));
+  if (!SA)
+    for (uint32_t e = tid; e < m / 2; e += NTT_THREADS) lds_put(W, e, l9_split(ld256(tw + ((size_t)e << (p.log_n - S)))));
   for (uint32_t e = tid; e < NS; e += NTT_THREADS) {
     L9 ws, wq;
 #pragma unroll
@@ -242,6 +280,12 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(const u256* __restrict
       v = l9_split(from_src ? colsrc_fetch(csrc, idx, 1ull << p.log_n, p.n_blind) : ld256(cin + idx));
       if constexpr (VS) {
         v = l9_mul(v, l9_split(ld256(ctab + idx)));
+      } else if (SA && p.coset) {
+        // a loaded value is canonical: the product is below 1.01 r
+        const uint32_t r3 = (uint32_t)(idx % 3);
+        if (r3 == 1) v = l9_mul_shoup<Fr>(v, kconst(p.zsh[1]), kconst(p.zsh[1] + 9));
+        else if (r3 == 2) v = l9_mul_shoup<Fr>(v, kconst(p.zsh[2]), kconst(p.zsh[2] + 9));
+        else if (p.coset == 2) v = l9_mul_shoup<Fr>(v, kconst(p.zsh[0]), kconst(p.zsh[0] + 9));
       } else if (p.coset) {
         uint32_t r3 = (uint32_t)(idx % 3);
         if (r3 == 1) v = l9_mul(v, Z1);
@@ -257,10 +301,15 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(const u256* __restrict
   __syncthreads();
   // butterfly steps: two stages at a time on four elements held in registers (one LDS round trip and one barrier
   // per two stages), a single radix-2 stage at the end when the number of stages is odd
+  // SA, odd S: the radix-2 stage's (w, w') from global memory.  Its 2^(S-1) G butterflies are 2 per thread with the same block —
+  // b & (m / 2 - 1) == tid when m / 2 == NTT_THREADS — so one entry per thread, fetched at the start of the step before, whose
+  // butterflies hide the latency
+  L9 r2w, r2q;
   auto do_step = [&](auto s_c, auto step_c) {
     const uint32_t s = s_c, step = step_c;
     const uint32_t logh = S - 1 - s, h = 1u << logh;
     const bool ren = (P_ren_mask >> step) & 1;
+    if (SA && (S & 1) && s + 3 == S) ld_pair18(p.sh2_tab + 18 * bitrev_s(tid & ((m >> 1) - 1), S - 1), r2w, r2q);
     if (s + 1 < S) {
       const uint32_t h2 = h >> 1, lh1 = logh ? logh - 1 : 0;   // (logh >= 1 here; the guard keeps the dead instantiations of a compile-time schedule well formed)
       // (the body is instantiated per (first step, carry pass) combination: a run-time `if (ren)` inside one body makes the
@@ -297,7 +346,14 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(const u256* __restrict
             L9 a0 = l9_add(x0, x2), a2 = l9_sub(x0, x2, p.ckp);
             L9 a1 = l9_add(x1, x3), a3 = l9_sub(x1, x3, p.ckp);
             l9_carry(a1);  // a1 is subtracted below: its limbs must be below 2^29 again
-            const L9 t3 = l9_mul(a3, lds_get(W, m >> 2));
+            L9 t3;
+            if (SA) {
+              // omega_4 from the Shoup table (index m / 4 is a multiple of its resolution), which is in LDS before the first barrier
+              const uint32_t iq = (m >> 2) >> P_sh_res_log;
+              t3 = l9_mul_shoup<Fr>(a3, lds_get(WS, iq), lds_get(WQ, iq));
+            } else {
+              t3 = l9_mul(a3, lds_get(W, m >> 2));
+            }
             x0 = l9_add(a0, a1);
             x1 = l9_sub(a0, a1, p.ckp);
             x2 = l9_add(a2, t3);
@@ -381,7 +437,8 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(const u256* __restrict
           l9_renorm(u);
           l9_renorm(v);
         }
-        if (s) v = l9_mul(v, lds_get(W, bitrev_s(blk, s) << logh));
+        if (SA) v = l9_mul_shoup<Fr>(v, r2w, r2q);   // (s == S - 1 >= 8 here: blk == pj == tid, the entry fetched above)
+        else if (s) v = l9_mul(v, lds_get(W, bitrev_s(blk, s) << logh));
         lds_put(D, a0, l9_add(u, v));
         lds_put(D, a1, l9_sub(u, v, p.ckp));
       }
@@ -409,13 +466,23 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(const u256* __restrict
   // waits for their acknowledgement too (one in-order vmcnt), which would put a store round trip between elements
   constexpr uint32_t EPT = NTT_TILE / NTT_THREADS;
   u256 twv[EPT];
+  L9 trw[SA ? EPT : 1], trq[SA ? EPT : 1];   // SA: the records (w, w') instead, already in limbs
   if (!LAST) {
 #pragma unroll
     for (uint32_t it = 0; it < EPT; it++) {
       const uint32_t e = tid + it * NTT_THREADS;
       const uint32_t g = e & (G - 1), q = e >> P_logG;
       const uint64_t ex = ((uint64_t)q * ((uint64_t)i0 + g)) << (p.log_n - S - p.log_inner);
-      if (e < T) twv[it] = ld256(tw_inter + ex);
+      if (e < T) {
+        if constexpr (SA) {
+          const uint4* rp = p.tw_rec + 5 * ex;
+          const uint4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3], r4 = rp[4];
+          trw[it] = L9{{r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x}};
+          trq[it] = L9{{r2.y, r2.z, r2.w, r3.x, r3.y, r3.z, r3.w, r4.x, r4.y}};
+        } else {
+          twv[it] = ld256(tw_inter + ex);
+        }
+      }
     }
   }
 #pragma unroll
@@ -426,7 +493,8 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(const u256* __restrict
     L9 v = lds_get(D, g * row + bitrev_s(q, S));
     if (p.ren_out) l9_renorm(v);
     if (!LAST) {
-      v = l9_mul(v, l9_split(twv[it]));
+      if constexpr (SA) v = l9_mul_shoup<Fr>(v, trw[it], trq[it]);
+      else v = l9_mul(v, l9_split(twv[it]));
       // below 1.2 r and exactly normalised: stored without the final conditional subtraction (the next pass only needs
       // normalised limbs below 1.9 r)
       st256(cout + base + (uint64_t)q * jstride + g, l9_pack(v));
@@ -506,44 +574,13 @@ static const u256* get_twiddles(uint32_t log_n, const u256& omega, const u256& f
 
 // Shoup table of one pass size (see NttPass::sh_tab): entry j holds, for e = j << res_log, the plain residue of
 // omega_m^e = omega^(e n / m) and floor(that * 2^261 / r), nine 29-bit limbs each.  Built on the host (a few hundred entries, a
-// 261-step long division each), cached per device beside the twiddle tables.
-static void limbs29(const u256& a, uint32_t extra_top /* bits 256.. */, uint32_t out[9]) {
-  for (int k = 0; k < 9; k++) {
-    const int bit = 29 * k, wd = bit >> 5, sh = bit & 31;
-    uint64_t v = wd < 8 ? (uint64_t)a.w[wd] >> sh : 0;
-    if (sh && wd + 1 < 8) v |= (uint64_t)a.w[wd + 1] << (32 - sh);
-    if (wd + 1 == 8 && sh) v |= (uint64_t)extra_top << (32 - sh);
-    if (wd == 8) v = extra_top >> sh;
-    out[k] = (uint32_t)v & 0x1fffffffu;
-  }
-}
+// 261-step long division each: shoup_stage_entries), cached per device beside the twiddle tables.
 static const uint32_t* get_shoup_table(uint32_t log_n, const u256& omega, uint32_t S, uint32_t res_log, int* err) {
   Context& c = ctx();
   Context::TwKey key{log_n | (S << 8) | (res_log << 16) | 0x40000000u, omega};
   auto it = c.twiddles.find(key);
   if (it != c.twiddles.end()) return reinterpret_cast<const uint32_t*>(it->second);
-  const uint32_t m = 1u << S, ns = (m / 2) >> res_log;
-  std::vector<uint32_t> tab((size_t)ns * 18);
-  const u256 p = mod_p<Fr>();
-  const u256 step = mont_pow<Fr>(omega, u256_from_u64(((uint64_t)1 << (log_n - S)) << res_log));  // omega_m^(2^res_log)
-  u256 cur = mont_one<Fr>();
-  for (uint32_t j = 0; j < ns; j++) {
-    const u256 w = from_mont<Fr>(cur);
-    limbs29(w, 0, &tab[18 * (size_t)j]);
-    // q = floor(w 2^261 / p): r starts at w (< p) and takes 261 doubling steps; r stays below 2 p < 2^255 before each reduction
-    u256 r = w;
-    uint32_t q[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int b = 260; b >= 0; b--) {
-      u256 d;
-      u256_add(d, r, r);
-      u256 t;
-      const uint32_t borrow = u256_sub(t, d, p);
-      r = borrow ? d : t;
-      if (!borrow) q[b / 29] |= 1u << (b % 29);
-    }
-    for (int k = 0; k < 9; k++) tab[18 * (size_t)j + 9 + k] = q[k];
-    cur = fr_mul(cur, step);
-  }
+  const std::vector<uint32_t> tab = shoup_stage_entries(log_n, omega, S, res_log);
   uint32_t* d = nullptr;
   hipError_t e = hipMalloc(&d, tab.size() * sizeof(uint32_t));
   if (e != hipSuccess) {
@@ -553,6 +590,43 @@ static const uint32_t* get_shoup_table(uint32_t log_n, const u256& omega, uint32
   e = hipMemcpy(d, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     *err = hip_fail(e, "hipMemcpy(shoup table)", __FILE__, __LINE__);
+    (void)hipFree(d);
+    return nullptr;
+  }
+  c.twiddles[key] = reinterpret_cast<u256*>(d);
+  return d;
+}
+
+// The inter-pass records of a twiddle table (NttPass::tw_rec): entry e of `tw` as (c, c') limbs, 80 B (shoup_record_of_tw).  n long
+// divisions: built on the device, one lane per entry, once per (log_n, omega, table) and cached beside the table it mirrors.
+__global__ __launch_bounds__(256) void k_shoup_records(const u256* __restrict__ tw, uint64_t n, u256 inv32, uint4* __restrict__ rec) {
+  const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  uint32_t o[20];
+  shoup_record_of_tw(ld256(tw + e), inv32, o);
+#pragma unroll
+  for (int i = 0; i < 5; i++) rec[5 * e + i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
+}
+static const uint4* get_shoup_records(uint32_t log_n, const u256& omega, bool scaled, const u256* tw, int* err) {
+  Context& c = ctx();
+  Context::TwKey key{log_n | (scaled ? 0x80000000u : 0u) | 0x20000000u, omega};
+  auto it = c.twiddles.find(key);
+  if (it != c.twiddles.end()) return reinterpret_cast<const uint4*>(it->second);
+  const uint64_t n = 1ull << log_n;
+  uint4* d = nullptr;
+  hipError_t e = hipMalloc(&d, n * 5 * sizeof(uint4));
+  if (e != hipSuccess) {
+    *err = hip_fail(e, "hipMalloc(shoup records)", __FILE__, __LINE__);
+    return nullptr;
+  }
+  const u256 inv32 = mont_inv<Fr>(host_fr_from_u64(32));
+  {
+    VDB_PROF("k_shoup_records");
+    hipLaunchKernelGGL(k_shoup_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.stream, tw, n, inv32, d);
+  }
+  e = hipGetLastError();
+  if (e != hipSuccess) {
+    *err = hip_fail(e, "k_shoup_records", __FILE__, __LINE__);
     (void)hipFree(d);
     return nullptr;
   }
@@ -618,10 +692,13 @@ int ntt_dev(u256* data, u256* out_or_null, size_t n_cols, uint32_t log_n, const 
   z1 = fr_mul(z1, m32);
   z2 = fr_mul(z2, m32);
   u256 z0 = m32;
+  // SA: the same three factors without the 32, as Shoup constants (zsh)
+  u256 zc[3] = {mont_one<Fr>(), host_zeta(), fr_mul(host_zeta(), host_zeta())};
   if (in_scale) {  // the polynomial s p(X) on the coset: the scalar rides on the coset factors (one more product on a third of the inputs)
     z0 = fr_mul(z0, *in_scale);
     z1 = fr_mul(z1, *in_scale);
     z2 = fr_mul(z2, *in_scale);
+    for (int t = 0; t < 3; t++) zc[t] = fr_mul(zc[t], *in_scale);
   }
   static const bool shoup_on = !(getenv("VDB_NTT_SHOUP") && getenv("VDB_NTT_SHOUP")[0] == '0');
   // 14 r with limbs that dominate a normalised subtrahend (l9_sub)
@@ -738,9 +815,22 @@ int ntt_dev(u256* data, u256* out_or_null, size_t n_cols, uint32_t log_n, const 
       }
       uint32_t G = 1u << p.logG;
       uint32_t tiles = (uint32_t)(n / ((uint64_t)m * G));
-      size_t lds = (size_t)(G * (m + 1) + (m / 2 ? m / 2 : 1)) * (2 * sizeof(uint4) + sizeof(uint32_t));
+      // the instantiation with this pass's size, first stage, carry schedule and Shoup resolution as compile-time constants when there is
+      // one (the 256- and 512-point passes of the prover's transforms), the generic kernel otherwise (VDB_NTT_SPEC=0: always)
+      static const bool spec_on = !(getenv("VDB_NTT_SPEC") && getenv("VDB_NTT_SPEC")[0] == '0');
+      const bool vs = (l == 0 && vslots);
+      auto spec_shape = [&](uint32_t cs, uint32_t cs0, uint32_t cren) {
+        return spec_on && L > 1 && p.S == cs && p.s0 == cs0 && p.ren_mask == cren && p.logG == 10 - cs && p.blk0;
+      };
+      // SA instantiation (VDB_NTT_SHOUP_ALL=0: the Montgomery products of before, the same instantiations otherwise): a specialised,
+      // non-virtual pass, with the 80-B inter-pass records bounded to n <= 2^22 (335 MB)
+      static const bool shoup_all = !(getenv("VDB_NTT_SHOUP_ALL") && getenv("VDB_NTT_SHOUP_ALL")[0] == '0');
+      const bool sa = shoup_all && shoup_on && !vs && log_n <= 22 &&
+                      (spec_shape(8, 0, 4) || spec_shape(9, 0, 20) || (!last && spec_shape(9, 2, 4)));
+      // (SA holds no Montgomery-form stage twiddles in LDS)
+      size_t lds = (size_t)(G * (m + 1) + (sa ? 0 : (m / 2 ? m / 2 : 1))) * (2 * sizeof(uint4) + sizeof(uint32_t));
       // Shoup table in what is left of a third of the CU's LDS (three workgroups per CU stay resident): full resolution for the
-      // 256-point passes, a quarter for the 512-point ones; passes too small to have a general radix-4 step do without
+      // 256-point passes, a quarter for the 512-point ones (a half under SA); passes too small to have a general radix-4 step do without
       p.sh_tab = nullptr;
       p.sh_res_log = p.sh_ns = 0;
       p.sh_max_s = -1;
@@ -769,30 +859,45 @@ int ntt_dev(u256* data, u256* out_or_null, size_t n_cols, uint32_t log_n, const 
           raised = true;
         }
       }
-      // the instantiation with this pass's size, first stage, carry schedule and Shoup resolution as compile-time constants when there is
-      // one (the 256- and 512-point passes of the prover's transforms), the generic kernel otherwise (VDB_NTT_SPEC=0: always)
-      static const bool spec_on = !(getenv("VDB_NTT_SPEC") && getenv("VDB_NTT_SPEC")[0] == '0');
       const u256* twi = last ? tw : (l == 0 ? tw_scaled : tw);
-      const bool vs = (l == 0 && vslots);
-      auto spec = [&](uint32_t cs, uint32_t cs0, uint32_t cren) {
-        const uint32_t rl = ntt_spec_sh_res_log(cs);
-        return spec_on && L > 1 && p.S == cs && p.s0 == cs0 && p.ren_mask == cren && p.logG == 10 - cs && p.sh_tab && p.blk0 && p.sh_res_log == rl &&
-               p.sh_ns == ((1u << (cs - 1)) >> rl) && p.sh_max_s == (int32_t)cs - 2 - (int32_t)rl;
+      auto spec = [&](uint32_t cs, uint32_t cs0, uint32_t cren, bool sa_) {
+        const uint32_t rl = ntt_spec_sh_res_log(cs, sa_);
+        return spec_shape(cs, cs0, cren) && p.sh_tab && p.sh_res_log == rl && p.sh_ns == ((1u << (cs - 1)) >> rl) && p.sh_max_s == (int32_t)cs - 2 - (int32_t)rl;
       };
+      if (sa) {
+        if (!spec(p.S, p.s0, p.ren_mask, true)) {  // (cannot happen: the LDS plan above gives the SA resolution to these shapes)
+          set_error("ntt: SA plan does not match its instantiation");
+          return VDB_ERR_ARG;
+        }
+        if (S[l] & 1) {
+          p.sh2_tab = get_shoup_table(log_n, omega, S[l], 0, &err);
+          if (!p.sh2_tab) return err;
+        }
+        if (!last) {
+          p.tw_rec = get_shoup_records(log_n, omega, twi != tw, twi, &err);
+          if (!p.tw_rec) return err;
+        }
+        for (int t = 0; t < 3; t++) shoup_const_of_mont(zc[t], p.zsh[t]);
+      }
 #define NTT_LAUNCH(...) hipLaunchKernelGGL((k_ntt_pass<__VA_ARGS__>), grid, dim3(NTT_THREADS), lds, c.stream, src, out, tw, twi, p, tiles)
       {
         VDB_PROF("k_ntt_pass");
         if (last) {
           if (vs) NTT_LAUNCH(true, true);
-          else if (spec(8, 0, 4)) NTT_LAUNCH(true, false, 8, 0, 4);
-          else if (spec(9, 0, 20)) NTT_LAUNCH(true, false, 9, 0, 20);
+          else if (sa && p.S == 8) NTT_LAUNCH(true, false, 8, 0, 4, true);
+          else if (sa) NTT_LAUNCH(true, false, 9, 0, 20, true);
+          else if (spec(8, 0, 4, false)) NTT_LAUNCH(true, false, 8, 0, 4);
+          else if (spec(9, 0, 20, false)) NTT_LAUNCH(true, false, 9, 0, 20);
           else NTT_LAUNCH(true, false);
         } else {
-          if (vs && spec(8, 0, 4)) NTT_LAUNCH(false, true, 8, 0, 4);
+          if (vs && spec(8, 0, 4, false)) NTT_LAUNCH(false, true, 8, 0, 4);
           else if (vs) NTT_LAUNCH(false, true);
-          else if (spec(8, 0, 4)) NTT_LAUNCH(false, false, 8, 0, 4);
-          else if (spec(9, 2, 4)) NTT_LAUNCH(false, false, 9, 2, 4);
-          else if (spec(9, 0, 20)) NTT_LAUNCH(false, false, 9, 0, 20);
+          else if (sa && p.S == 8) NTT_LAUNCH(false, false, 8, 0, 4, true);
+          else if (sa && p.s0 == 2) NTT_LAUNCH(false, false, 9, 2, 4, true);
+          else if (sa) NTT_LAUNCH(false, false, 9, 0, 20, true);
+          else if (spec(8, 0, 4, false)) NTT_LAUNCH(false, false, 8, 0, 4);
+          else if (spec(9, 2, 4, false)) NTT_LAUNCH(false, false, 9, 2, 4);
+          else if (spec(9, 0, 20, false)) NTT_LAUNCH(false, false, 9, 0, 20);
           else NTT_LAUNCH(false, false);
         }
       }
