@@ -118,7 +118,8 @@ _SIGNATURES = {
     "vdb_coeff_to_extended": [_P, _P, _SZ, _U32, _U32], "vdb_coeff_to_extended_dev": [_P, _P, _SZ, _U32, _U32], "vdb_coeff_to_extended_scaled_dev": [_P, _P, _SZ, _U32, _U32, _P],
     "vdb_fr_root_of_unity": [_U32, _P], "vdb_profile_end": [_P, _SZ],
     "vdb_g1_decompress_dev": [_P, _SZ, _U32, _P, _P], "vdb_msm_points_dev": [_P, _P, _SZ, _P], "vdb_g2_mul_generator": [_P, _P],
-    "vdb_pairing_check": [_P, _P, _SZ, _P],
+    "vdb_pairing_check": [_P, _P, _SZ, _P], "vdb_g2_check": [_P, _SZ, _P],
+    "vdb_g1_check_dev": [_P, _SZ, _P, _P], "vdb_g1_lagrange_from_monomial_dev": [_U32, _P, _P], "vdb_srs_downsize": [_U32, _P, _P],
     "vdb_poseidon_hash_many": [_P, _SZ, _SZ, _P], "vdb_poseidon_merkle_root": [_P, _SZ, _SZ, _P], "vdb_poseidon_permute": [_P, _SZ],
 }
 

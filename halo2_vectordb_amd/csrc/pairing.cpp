@@ -380,4 +380,36 @@ int vdb_pairing_check(const vdb_g1* a, const vdb_g2* b, size_t n, int* ok) {
   return VDB_OK;
 }
 
+int vdb_g2_check(const vdb_g2* p, size_t n, int* ok) {
+  if (!ok || (n && !p)) {
+    vdb::set_error("null pointer");
+    return VDB_ERR_ARG;
+  }
+  *ok = 1;
+  for (size_t i = 0; i < n; i++) {
+    const vdb_g2& q = p[i];
+    if (!canonical_fq(q.x[0]) || !canonical_fq(q.x[1]) || !canonical_fq(q.y[0]) || !canonical_fq(q.y[1])) {
+      *ok = 0;
+      return VDB_OK;
+    }
+    const G2 pt = {F2{as_f(q.x[0]), as_f(q.x[1])}, F2{as_f(q.y[0]), as_f(q.y[1])}, false};
+    if (f2_is_zero(pt.x) && f2_is_zero(pt.y)) continue;   // the identity
+    if (!g2_on_curve(pt)) {
+      *ok = 0;
+      return VDB_OK;
+    }
+    // r P = O: the twist's group has order r times a large cofactor, so a point on it is in G2 only when this holds
+    G2 acc = {F2{fq_zero(), fq_zero()}, F2{fq_zero(), fq_zero()}, true};
+    for (int b = 253; b >= 0; b--) {
+      g2_step(acc, acc, nullptr, nullptr, nullptr);
+      if ((MR.p[b / 64] >> (b % 64)) & 1) g2_step(acc, pt, nullptr, nullptr, nullptr);
+    }
+    if (!acc.inf) {
+      *ok = 0;
+      return VDB_OK;
+    }
+  }
+  return VDB_OK;
+}
+
 }  // extern "C"

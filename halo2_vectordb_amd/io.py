@@ -156,6 +156,9 @@ def read_verifying_key(path):
         for key in ("delta", "tau", "vk_digest"):
             if key in meta:
                 meta[key] = int(meta[key])
+        for key in ("tau_g2", "g2"):          # G2 points of an SRS from a params file: 16 words each
+            if key in meta:
+                meta[key] = np.array([int(w) for w in meta[key]], dtype=np.uint64).reshape(16)
         meta["n_instances"] = int(meta["n_instances"])
         if "opened" in meta:
             meta["opened"] = {int(rot): list(names) for rot, names in meta["opened"].items()}

@@ -186,9 +186,12 @@ class KmeansHotPath:
     """kmeans::<K, I> over N x D vectors at 2^k rows: witness -> layout -> commit -> NTT, one GPU."""
 
     def __init__(self, n=256, dim=128, K=4, I=8, k=16, P=48, L=15, metric="euclidean", seed=20260004, tau=None,
-                 col_shard=(0, 1), vectors=None, blind_seed=None):
+                 col_shard=(0, 1), vectors=None, blind_seed=None, params=None):
         """`tau`: toxic-waste scalar of the "unsafe" SRS as a canonical integer; None = the scalar the reference's
         `gen_srs(k)` derives from its fixed ChaCha20 seed (srs.gen_srs_tau, src/scaffold/mod.rs:260).
+        `params`: an SRS whose scalar nobody knows instead — an srs.ParamsKZG (downsized to k on the device when its k is larger)
+        or the path of a halo2 params file (read at k), what gen_srs(k) loads from params/kzg_bn254_{k}.srs when that exists.
+        Not together with `tau`; `self.tau` stays None and `self.tau_g2` / `self.g2` carry the SRS's G2 side.
         `vectors`: the f64 rows the circuit assigns first (the `--input` file of the reference's examples,
         src/scaffold/mod.rs:64-77); None = the seeded SIFT-shaped synthetic rows of SURVEY 8(d).
         `blind_seed`: None = the blinding rows of every column are drawn afresh from the operating system's entropy for every
@@ -205,7 +208,11 @@ class KmeansHotPath:
         self.lib = api.init()
         self.rank, self.world = col_shard
         self.seed = seed
+        if params is not None and tau is not None:
+            raise ValueError("give the SRS as tau or as params, not both")
         self.tau = tau
+        self.params = params
+        self.tau_g2 = self.g2 = None
         self.factor_constants = True
         self.shard_witness = True   # generate only the witness cells this rank's columns hold (values are computed everywhere)
         self.balance_shards = True  # equalise estimated time per rank instead of column count
@@ -258,11 +265,18 @@ class KmeansHotPath:
         self.n_cols = self.n_adv_cols + self.n_lk_cols
         from_ints = lambda vals: np.array([[(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)] for v in vals], dtype=np.uint64)
         R = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
-        if self.tau is None:
-            from .srs import gen_srs_tau
-            self.tau = gen_srs_tau()
-        tau = from_ints([self.tau * (1 << 256) % R])[0]
-        g, gl = api.srs_setup_unsafe(self.k, tau)
+        if self.params is not None:
+            from .srs import ParamsKZG
+            params = self.params if isinstance(self.params, ParamsKZG) else ParamsKZG.read(self.params, self.k)
+            params = params.downsize(self.k)      # ValueError when the params hold fewer than 2^k points
+            g, gl = params.g, params.g_lagrange
+            self.g2, self.tau_g2 = params.g2, params.s_g2
+        else:
+            if self.tau is None:
+                from .srs import gen_srs_tau
+                self.tau = gen_srs_tau()
+            tau = from_ints([self.tau * (1 << 256) % R])[0]
+            g, gl = api.srs_setup_unsafe(self.k, tau)
         self.g_lagrange = gl
         self.g_monomial = g
         self.srs = api.Srs(self.k, None, gl, window_bits=self.msm_window_bits)
@@ -585,8 +599,9 @@ class MerkleHotPath(KmeansHotPath):
     column counts per rank are balanced already; a rank that holds a block of columns traces only the permutations whose
     cells fall into it (the sponge states and the tree's digests are computed by every rank, value only)."""
 
-    def __init__(self, n=1024, dim=128, k=15, P=32, seed=20260003, tau=None, col_shard=(0, 1), vectors=None, blind_seed=None):
-        super().__init__(n=n, dim=dim, K=1, I=1, k=k, P=P, L=8, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors, blind_seed=blind_seed)
+    def __init__(self, n=1024, dim=128, k=15, P=32, seed=20260003, tau=None, col_shard=(0, 1), vectors=None, blind_seed=None, params=None):
+        super().__init__(n=n, dim=dim, K=1, I=1, k=k, P=P, L=8, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors, blind_seed=blind_seed,
+                         params=params)
         self.balance_shards = False
         self.msm_window_bits = 14   # every scalar is a full-width Poseidon state: 19 windows instead of 24
 
@@ -631,10 +646,11 @@ class NearestHotPath(KmeansHotPath):
     chain (value-only walk), and stores the cells of its own block of columns only — the distance blocks, N-way parallel and nearly
     all of the cells, are skipped outside the rank's window."""
 
-    def __init__(self, n=64, dim=128, k=14, P=48, L=13, metric="euclidean", seed=20260002, tau=None, col_shard=(0, 1), vectors=None, blind_seed=None):
+    def __init__(self, n=64, dim=128, k=14, P=48, L=13, metric="euclidean", seed=20260002, tau=None, col_shard=(0, 1), vectors=None, blind_seed=None,
+                 params=None):
         """`vectors`: (n + 1, dim) f64 rows, the query first"""
         super().__init__(n=n, dim=dim, K=1, I=1, k=k, P=P, L=L, metric=metric, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors,
-                         blind_seed=blind_seed)
+                         blind_seed=blind_seed, params=params)
 
     def n_input_rows(self):
         return self.n + 1
@@ -740,10 +756,10 @@ class DistancesHotPath(KmeansHotPath):
     columns: nothing to shard the witness by)."""
 
     def __init__(self, dim=4, metrics=("euclidean", "manhattan", "cosine", "hamming"), k=13, P=48, L=12, seed=20260001, tau=None, col_shard=(0, 1), vectors=None,
-                 blind_seed=None, public=True):
+                 blind_seed=None, public=True, params=None):
         """`vectors`: (2, dim) f64 rows, a then b"""
         super().__init__(n=2, dim=dim, K=1, I=1, k=k, P=P, L=L, metric=metrics[0], seed=seed, tau=tau, col_shard=col_shard, vectors=vectors,
-                         blind_seed=blind_seed)
+                         blind_seed=blind_seed, params=params)
         self.metrics = tuple(metrics)
         for m in self.metrics:
             if m not in api.METRICS:
@@ -795,13 +811,14 @@ class FixedPointHotPath(DistancesHotPath):
     qexp2(x), qlog2(x) when x > 0, qsin(x), with x and every result public.  Stream: [x | the cells of each call in turn]
     (vdb_wit_fp_op_dev, one instance each).  `ops`: other FixedPointInstructions names instead of the example's."""
 
-    def __init__(self, x=1.128, ops=None, k=13, P=32, L=12, tau=None, blind_seed=None):
+    def __init__(self, x=1.128, ops=None, k=13, P=32, L=12, tau=None, blind_seed=None, params=None):
         self.x = float(x)
         self.ops = tuple(ops) if ops is not None else ("qexp2",) + (("qlog2",) if self.x > 0.0 else ()) + ("qsin",)
         for name in self.ops:
             if name not in api.FP_OPS:
                 raise ValueError("unknown FixedPointChip operation: " + str(name))
-        KmeansHotPath.__init__(self, n=1, dim=1, K=1, I=1, k=k, P=P, L=L, metric="euclidean", tau=tau, vectors=np.array([[self.x]]), blind_seed=blind_seed)
+        KmeansHotPath.__init__(self, n=1, dim=1, K=1, I=1, k=k, P=P, L=L, metric="euclidean", tau=tau, vectors=np.array([[self.x]]), blind_seed=blind_seed,
+                               params=params)
         self.metrics = ()
         self.public = True
         self.shard_witness = False

@@ -647,12 +647,18 @@ class ProverRounds:
         """What the Keygen arm writes beside the proving key (src/scaffold/mod.rs:276-281: data/{name}.vk) in this build's own
         container (upstream's is SerdeFormat::RawBytes of halo2's VerifyingKey: parity unpinned): the circuit's shape, the commitments
         of the fixed polynomials in FIXED order, the transcript digest made of them, the SRS scalar of the deterministic "unsafe"
-        setup the reference's gen_srs uses (a verifier derives [tau]_2 from it; a ceremony SRS would carry the G2 point instead), and
-        — when a proof's `opened` map is given — which polynomial is opened at which rotation.  io.read_verifying_key reads it."""
+        setup the reference's gen_srs uses (a verifier derives [tau]_2 from it) — or, for an SRS from a params file, whose scalar nobody
+        knows, its G2 points tau_g2 = [tau]_2 and g2 instead —, and — when a proof's `opened` map is given — which polynomial is opened
+        at which rotation.  io.read_verifying_key reads it."""
         from .io import write_verifying_key
         meta = dict(rows=self.rows, k=self.k, n_adv=self.n_adv, n_lk=self.n_lk, n_cols=self.n_cols, n_sets=self.n_sets, chunk_len=self.chunk_len,
-                    n_blind=N_BLIND, delta=str(_fr_to_int(self.delta)), n_instances=len(self.instance_cells), tau=str(self.hp.tau),
-                    vk_digest=str(_fr_to_int(self.vk_digest())))
+                    n_blind=N_BLIND, delta=str(_fr_to_int(self.delta)), n_instances=len(self.instance_cells))
+        if self.hp.tau is not None:
+            meta["tau"] = str(self.hp.tau)
+        else:
+            meta["tau_g2"] = [str(int(w)) for w in self.hp.tau_g2]
+            meta["g2"] = [str(int(w)) for w in self.hp.g2]
+        meta["vk_digest"] = str(_fr_to_int(self.vk_digest()))
         if opened is not None:
             meta["opened"] = {str(rot): list(names) for rot, names in opened.items()}
         write_verifying_key(path, meta, {name: self.fixed[name].commits for name in FIXED})

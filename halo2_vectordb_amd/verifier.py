@@ -74,9 +74,9 @@ def vk_digest(fixed):
 class VerifyingKey:
     """The circuit's shape (meta: rows, k, n_adv, n_lk, n_cols, n_sets, chunk_len, n_blind, delta, n_instances), which polynomial is
     opened at which rotation, the fixed commitments ({name: (m, 8) uint64} for FIXED), and [tau]_2 — from the SRS scalar tau of the
-    deterministic setup, or given as a vdb_g2 array."""
+    deterministic setup, or given as a vdb_g2 array — with the SRS's g2 (G2's generator unless given: a params file carries its own)."""
 
-    def __init__(self, meta, fixed, opened=None, tau=None, tau_g2=None):
+    def __init__(self, meta, fixed, opened=None, tau=None, tau_g2=None, g2=None):
         self.meta = {key: int(meta[key]) for key in ("rows", "k", "n_adv", "n_lk", "n_cols", "n_sets", "chunk_len", "n_blind", "delta", "n_instances")}
         self.fixed = {name: np.ascontiguousarray(fixed[name], dtype=np.uint64).reshape(-1, 8) for name in FIXED}
         self.opened = {int(rot): list(names) for rot, names in (opened or _default_opened(self.meta["n_lk"], self.meta["n_blind"])).items()}
@@ -85,6 +85,7 @@ class VerifyingKey:
                 raise ValueError("a verifying key needs [tau]_2 or the SRS scalar tau")
             tau_g2 = _g2_generator_times(int(tau))
         self.tau_g2 = np.ascontiguousarray(tau_g2, dtype=np.uint64).reshape(16)
+        self.g2 = _g2_one() if g2 is None else np.ascontiguousarray(g2, dtype=np.uint64).reshape(16)
         self._digest = None
 
     @classmethod
@@ -93,20 +94,38 @@ class VerifyingKey:
         from .rounds import N_BLIND, _fr_to_int
         meta = dict(rows=pr.rows, k=pr.k, n_adv=pr.n_adv, n_lk=pr.n_lk, n_cols=pr.n_cols, n_sets=pr.n_sets, chunk_len=pr.chunk_len, n_blind=N_BLIND,
                     delta=_fr_to_int(pr.delta), n_instances=len(pr.instance_cells))
-        return cls(meta, {name: pr.fixed[name].commits for name in FIXED}, opened, tau=pr.hp.tau)
+        fixed = {name: pr.fixed[name].commits for name in FIXED}
+        if pr.hp.tau is None:        # an SRS from a params file
+            return cls(meta, fixed, opened, tau_g2=pr.hp.tau_g2, g2=pr.hp.g2)
+        return cls(meta, fixed, opened, tau=pr.hp.tau)
 
     @classmethod
-    def read(cls, path, n_instances=None, tau=None):
+    def read(cls, path, n_instances=None, tau=None, params=None):
         """save_verifying_key's .npz (its stored digest is checked), or else halo2's RawBytes .vk (io.read_verifying_key_raw; the number
-        of public values and the SRS scalar come from the caller — the reference's gen_srs scalar by default).  ValueError when the
-        file is not a key of this circuit family."""
+        of public values and the SRS scalar come from the caller — the reference's gen_srs scalar by default).  `params`: the SRS's G2
+        side from a halo2 params file instead (its path, or an srs.ParamsKZG), for either kind of key; not together with `tau`.
+        ValueError when the file is not a key of this circuit family."""
         from . import io
+        g2 = tau_g2 = None
+        if params is not None:
+            if tau is not None:
+                raise ValueError("give the SRS as tau or as params, not both")
+            from .srs import ParamsKZG, read_params_g2
+            g2, tau_g2 = (params.g2, params.s_g2) if isinstance(params, ParamsKZG) else read_params_g2(params)
         if str(path).endswith(".npz"):
             meta, fixed = io.read_verifying_key(path)
-            vk = cls(meta, fixed, meta.get("opened"), tau=meta["tau"] if tau is None else tau)
+            if tau_g2 is None and tau is None and "tau_g2" in meta:      # a key made from a params file carries its G2 points
+                tau_g2, g2 = meta["tau_g2"], meta.get("g2")
+            if tau_g2 is not None:
+                vk = cls(meta, fixed, meta.get("opened"), tau_g2=tau_g2, g2=g2)
+            else:
+                vk = cls(meta, fixed, meta.get("opened"), tau=meta.get("tau") if tau is None else tau)
             if "vk_digest" in meta and _fr_int(vk.digest()) != meta["vk_digest"]:
                 raise ValueError("the key's digest is not the digest of its commitments")
             return vk
+        if tau_g2 is not None:
+            meta, fixed, _selectors = io.read_verifying_key_raw(path, n_instances=int(n_instances or 0))
+            return cls(meta, fixed, meta.pop("opened"), tau_g2=tau_g2, g2=g2)
         if tau is None:
             from .srs import gen_srs_tau
             tau = gen_srs_tau()
@@ -421,7 +440,7 @@ def _verify(proof, instances, vk, sign_bit, t):
     t["msm"] = time.perf_counter() - t0
     # ---- e(left, [1]_2) e(-W2, [tau]_2) = 1
     t0 = time.perf_counter()
-    ok = pairing_check(np.stack([left, _neg_point(W2)]), np.stack([_g2_one(), vk.tau_g2]))
+    ok = pairing_check(np.stack([left, _neg_point(W2)]), np.stack([vk.g2, vk.tau_g2]))
     t["pairing"] = time.perf_counter() - t0
     return ok
 
@@ -450,12 +469,13 @@ class Verifier:
         self.timings = {}
 
     @classmethod
-    def from_files(cls, snark_path, vk_path, tau=None, sign_bit=6):
+    def from_files(cls, snark_path, vk_path, tau=None, sign_bit=6, params=None):
         """snark_path: io.write_snark's file; vk_path: save_verifying_key's .npz or halo2's RawBytes .vk (then tau is the SRS scalar,
-        the reference's gen_srs scalar by default).  ValueError when either file is malformed."""
+        the reference's gen_srs scalar by default); params: a halo2 params file (or srs.ParamsKZG) whose g2 and [tau]_2 the pairing
+        uses instead.  ValueError when either file is malformed."""
         from .io import read_snark
         proof, instances = read_snark(snark_path)
-        return cls(proof, instances, VerifyingKey.read(vk_path, n_instances=len(instances), tau=tau), sign_bit)
+        return cls(proof, instances, VerifyingKey.read(vk_path, n_instances=len(instances), tau=tau, params=params), sign_bit)
 
     def verify(self):
         self.timings = {}

@@ -239,6 +239,20 @@ int vdb_srs_load_window(uint32_t k, const vdb_g1 *g, const vdb_g1 *g_lagrange, u
 /* "unsafe" trusted setup with a caller-supplied tau, the construction ParamsKZG::setup performs behind
  * gen_srs(k) (src/scaffold/mod.rs:260-261: "unsafe" message); tau is a Montgomery Fr.  Test/bench SRS. */
 int vdb_srs_setup_unsafe(uint32_t k, const vdb_fr *tau, vdb_g1 *g_out, vdb_g1 *g_lagrange_out);
+/* A params file instead of a known tau: what halo2-base's gen_srs(k) reads from params/kzg_bn254_{k}.srs when the file exists
+ * (src/scaffold/mod.rs:260), typically one ceremony file cut down with ParamsKZG::downsize(k).
+ * vdb_g1_check_dev replaces the point checks of halo2's SerdeFormat::RawBytes reader (ParamsKZG::read): both coordinates below q
+ * (as the raw Montgomery words) and y^2 = x^3 + 3, (0, 0) accepted as the identity.  *n_bad: the number of points that fail;
+ * *first_bad: the lowest index among them (n when none fails).  Blocks until done. */
+int vdb_g1_check_dev(const vdb_g1 *pts_dev, size_t n, uint64_t *n_bad, uint64_t *first_bad);
+/* Replaces halo2's g_to_lagrange (ParamsKZG::downsize: best_fft over G1 with omega^-1, times n^-1, batch_normalize):
+ * g_lagrange[i] = n^-1 sum_j omega^(-ij) g[j] for n = 2^k arbitrary affine points (identity allowed), omega =
+ * vdb_fr_root_of_unity(k); canonical affine out, identity (0, 0).  k = 1 .. 26; the two buffers may be the same.  Blocks until
+ * done (its work buffers, 2 x 128 B per point, are released before it returns). */
+int vdb_g1_lagrange_from_monomial_dev(uint32_t k, const vdb_g1 *g_dev, vdb_g1 *g_lagrange_dev);
+/* ParamsKZG::downsize(k) for a host caller: g_host holds at least 2^k monomial points (the first 2^k of a longer g are used),
+ * g_lagrange_out receives the 2^k Lagrange points.  g itself is the prefix of the longer one. */
+int vdb_srs_downsize(uint32_t k, const vdb_g1 *g_host, vdb_g1 *g_lagrange_out);
 void vdb_srs_free(vdb_srs *srs);
 /* out[c] = parts[0][c] + ... + parts[m-1][c] in G1 (host arrays, m x n and n affine points; the identity is (0, 0)): the
  * combine step of a point-sharded MSM — each GPU commits its slice of the rows of every column against the matching slice of
@@ -577,6 +591,10 @@ int vdb_g2_mul_generator(const vdb_fr *s, vdb_g2 *out);
  * n = 0 accepts.  VDB_ERR_ARG when a coordinate is not below q or a point is not on its curve (G2's subgroup is not checked:
  * the verifier's G2 points are the generator and [tau]_2 from vdb_g2_mul_generator). */
 int vdb_pairing_check(const vdb_g1 *a, const vdb_g2 *b, size_t n, int *ok);
+/* *ok = 1 when each of the n points is a G2 element: coordinates below q, on the twist (the all-zero identity included) and
+ * r P = O — what halo2's RawBytes reader checks of a params file's g2 and s_g2 (ParamsKZG::read), plus the subgroup.  Host
+ * arithmetic, no GPU needed. */
+int vdb_g2_check(const vdb_g2 *p, size_t n, int *ok);
 
 /* ---- b6 Poseidon: replaces poseidon::PoseidonChip<F,3,2> value semantics (T=3, RATE=2, R_F=8,
  *      R_P=57 as examples/merkle.rs:15-18; call sites src/gadget/vectordb.rs:180-182, 213-215) --- */
