@@ -11,6 +11,9 @@ import struct
 
 import numpy as np
 
+from . import protocol
+from .protocol import FIXED as VK_FIXED
+
 
 def read_fvecs(path, count=None, dim=None):
     """Returns an (n, d) float64 array (the reference widens f32 to f64 before quantizing).  `count` limits the number
@@ -131,9 +134,6 @@ def read_snark(path):
 
 
 # ---------------------------------------------------------------- verifying key file (the reference writes data/{name}.vk, src/scaffold/mod.rs:276-281)
-VK_FIXED = ("sel", "sigma", "cst", "table")
-
-
 def write_verifying_key(path, meta, fixed):
     """meta: JSON-serialisable description of the circuit's shape (rounds.ProverRounds.save_verifying_key); fixed[name]: (n, 8) uint64
     commitments.  An .npz without pickled objects (numpy appends the suffix when `path` lacks it; pass a name ending in .npz)."""
@@ -298,17 +298,10 @@ def read_verifying_key_raw(path, n_instances=0, tau=None):
     n_lk = n_perm - n_adv - 2
     if n_lk < 0:
         raise ValueError("verifying key: fewer permutation columns than gate columns")
-    chunk_len = 2 if n_lk else 1
-    from .rounds import N_BLIND, _fr_to_int
-    from . import api
-    meta = dict(rows=1 << k, k=k, n_adv=n_adv, n_lk=n_lk, n_cols=n_adv + n_lk, n_sets=-(-n_perm // chunk_len), chunk_len=chunk_len, n_blind=N_BLIND,
-                delta=_fr_to_int(api.fr_delta()), n_instances=int(n_instances))
+    meta = protocol.key_meta(k, n_adv, n_lk, int(n_instances))
     if tau is not None:
         meta["tau"] = int(tau)
-    names = {0: ["adv", "sel", "sigma", "cst", "table", "pa", "ps", "zp", "zl", "hf", "rand"], 1: ["advg", "zp", "zl"], 2: ["advg"], 3: ["advg"], -1: ["pa"], -N_BLIND: ["zp"]}
-    lookup_only = {"pa", "ps", "zl"}
-    meta["opened"] = {rot: [n for n in ns if n_lk or n not in lookup_only] for rot, ns in names.items()}
-    meta["opened"] = {rot: ns for rot, ns in meta["opened"].items() if ns}
+    meta["opened"] = protocol.opened(n_lk)
     fc = doc["fixed_commitments"]
     fixed = {"table": fc[0:1], "cst": fc[1:2], "sel": fc[2:], "sigma": doc["permutation_commitments"]}
     return meta, fixed, doc["selectors"]

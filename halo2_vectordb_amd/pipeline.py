@@ -17,13 +17,9 @@ import numpy as np
 
 from . import api
 from ._lib import check
+from .protocol import N_BLIND, constraint_degree
 
 MINIMUM_ROWS = 9   # MINIMUM_ROWS default, src/scaffold/mod.rs:383
-# Rows at the end of every column that the prover fills with random scalars: halo2's blinding_factors() + 1.  blinding_factors() =
-# max(3, advice queries per column) + 2 [UPSTREAM-RECALL]; halo2-base's vertical gate reads a column at four rotations, so 6 — which is
-# what the reference's own MINIMUM_ROWS = 9 = blinding_factors() + 3 says (src/scaffold/mod.rs:383) — and the last usable row, where
-# l_last sits and the running products end, is row 2^k - 7.  (Rounds 1-2 used 6.)
-N_BLIND = 7
 
 
 def sift_like_vectors(seed, n, dim, k_distinct=0):
@@ -82,9 +78,9 @@ def balanced_column_shards(var_adv, var_lk, world, msm_share=0.22):
 
 
 def set_cols(n_lk_cols):
-    """columns per product polynomial of the permutation argument, halo2's chunk_len = cs.degree() - 2 (rounds.constraint_degree: 4 for a
+    """columns per product polynomial of the permutation argument, halo2's chunk_len = cs.degree() - 2 (protocol.constraint_degree: 4 for a
     circuit with lookup columns, 3 without): block boundaries of a sharded job fall on sets"""
-    return 2 if n_lk_cols else 1
+    return constraint_degree(n_lk_cols) - 2
 
 
 SET_COLS = 2

@@ -26,53 +26,23 @@ import time
 
 import numpy as np
 
-from . import api
+from . import api, protocol
 from ._lib import check
-from .pipeline import N_BLIND
+from .protocol import DERIVED, FIXED, N_BLIND, R_MOD, constraint_degree
+from .protocol import fr_from_int as _fr_from_int, fr_to_int as _fr_to_int
 
 B = 32
-DERIVED = ("hf",)   # opened polynomials whose evaluation is not in the proof: the verifier computes it (h folded at x, from the quotient identity)
-FIXED = ("sel", "sigma", "cst", "table")     # the committed fixed polynomials, in the order the verifying key's digest absorbs their commitments
-# (the Lagrange selectors l_0, l_last, l_active = 1 - l_last - l_blind the quotient multiplies by are not polynomials of the key: halo2
-#  neither commits nor opens them, its verifier evaluates them at x from the domain — lagrange_evals below; the prover keeps their
-#  cosets as key material, self.fixed["lag"])
-# The constraint system's degree, halo2 ConstraintSystem::degree() [UPSTREAM-RECALL; SURVEY App. C.4 / C.5]: the maximum of the
-# permutation argument's required degree (3), the lookup arguments' (max(4, 2 + input degree + table degree) = 4: halo2-base's "lookup wo
-# selector" reads one lookup-advice column against the table column, both of degree 1) and the gates' (the vertical gate
-# q (a + b c - d): 3).  A circuit with lookup columns has degree 4; one without (merkle_commitment alone: the builder's auto-config
-# gives it no lookup-advice column, so RangeConfig creates no lookup argument) degree 3.  Everything below follows from it the way
-# halo2 derives it:
-#   chunk_len = degree - 2   columns per product polynomial of the permutation argument (permutation::Argument)
-#   n_h       = degree - 1   pieces of the quotient (quotient_poly_degree; extended domain 2^(k + ceil(log2(degree - 1))))
+# The quotient has n_h = degree - 1 pieces (protocol.constraint_degree).
 # halo2 evaluates the numerator on every point of the extended domain; the quotient has degree below n_h n, so its values on n_h of the
 # cosets of the 2^k-th roots of unity determine it, and the gates' share (degree 3: below 2 n) on two.  The rounds work coset by coset
 # ("slots", vdb_coeff_to_cosets_dev: arrays [column][slot][row]) on n_slots = n_h of them and never make the rest: with degree 4 a
 # quarter of every extended transform and of every evaluation kernel is not run, and the quotient that comes out is the same polynomial.
-def constraint_degree(n_lookup_columns):
-    return 4 if n_lookup_columns else 3
-
-
 GATE_SLOTS = 2               # cosets the gate terms are evaluated on (slots 0, 1 = the coset of 2 n points)
 BLOCK_COLS = 510 # fixed-polynomial cosets are produced this many columns at a time (a multiple of every chunk_len; 3.2 GB at 2^16 rows)
-R_MOD = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 
 
 def _sz(v):
     return ctypes.c_size_t(int(v))
-
-
-def _fr_from_int(v):
-    v = v % R_MOD * (1 << 256) % R_MOD
-    return np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
-
-
-_RINV = pow(1 << 256, -1, R_MOD)
-
-
-def _fr_to_int(a):
-    a = np.asarray(a, dtype=np.uint64).reshape(4)
-    v = sum(int(a[i]) << (64 * i) for i in range(4))
-    return v * _RINV % R_MOD
 
 
 class _View:
@@ -277,11 +247,7 @@ class ProverRounds:
         at keygen) — here the squeeze of a sponge of its own over every fixed commitment in FIXED order, computed once per key (the
         38 k points of the k = 16 cosine circuit would otherwise cost every proof 19 k permutations on the host)."""
         if self._vk_digest is None:
-            tr0 = api.Transcript()
-            for name in FIXED:
-                tr0.common_points(self.fixed[name].commits)
-            self._vk_digest = tr0.squeeze()
-            tr0.free()
+            self._vk_digest = protocol.vk_digest({name: self.fixed[name].commits for name in FIXED})
         return self._vk_digest
 
     def _fixed_poly(self, name, lag_buf, n_cols, keep_lag=True, keep_ext=True, ranges=None, n_total=None):
@@ -651,8 +617,8 @@ class ProverRounds:
         knows, its G2 points tau_g2 = [tau]_2 and g2 instead —, and — when a proof's `opened` map is given — which polynomial is opened
         at which rotation.  io.read_verifying_key reads it."""
         from .io import write_verifying_key
-        meta = dict(rows=self.rows, k=self.k, n_adv=self.n_adv, n_lk=self.n_lk, n_cols=self.n_cols, n_sets=self.n_sets, chunk_len=self.chunk_len,
-                    n_blind=N_BLIND, delta=str(_fr_to_int(self.delta)), n_instances=len(self.instance_cells))
+        meta = protocol.key_meta(self.k, self.n_adv, self.n_lk, len(self.instance_cells))
+        meta["delta"] = str(meta["delta"])
         if self.hp.tau is not None:
             meta["tau"] = str(self.hp.tau)
         else:
@@ -1304,20 +1270,12 @@ class ProverRounds:
             check(lib.vdb_poly_axpy_dev(d_hf.ptr, api._p(_fr_from_int(pow(xn, i, R_MOD))), d_h.at(i * rows * B), _sz(rows)))
         polys["hf"] = _Poly("hf", 1, coeff=d_hf, commits=stage("commit_h", lambda: self._commit(d_hf, 1, 0)), replicated=True)
 
-        # round 5 (x): evaluations.  Which polynomial is read at which rotation: the gate reads the advice at rows 0..3, the
-        # products one row ahead, the permuted input one row back, the chained product N_BLIND rows back.
+        # round 5 (x): evaluations, at the rotations protocol.opened states
         allp = {**polys, **fx}
-        opened = {0: ["adv", "sel", "sigma", "cst", "table", "pa", "ps", "zp", "zl", "hf", "rand"], 1: ["advg", "zp", "zl"], 2: ["advg"], 3: ["advg"], -1: ["pa"],
-                  -N_BLIND: ["zp"]}
-        opened = {rot: [name for name in names if allp[name].n_total] for rot, names in opened.items()}    # a circuit without lookups
-        opened = {rot: names for rot, names in opened.items() if names}                                   # opens nothing at w^-1 x
-        x_int = _fr_to_int(ch["x"])
-        w_int = _fr_to_int(api.root_of_unity(k))
-        evals, points = {}, {}
-
+        opened = protocol.opened(self.n_lk)
+        points = protocol.rotation_points(_fr_to_int(ch["x"]), k, opened)
+        evals = {}
         groups = [(rot, name) for rot, names in opened.items() for name in names]
-        for rot in opened:
-            points[rot] = x_int * pow(w_int, rot % rows, R_MOD) % R_MOD
 
         def evaluate():
             for rot, name in groups:
@@ -1439,49 +1397,13 @@ class ProverRounds:
         lib, rows = self.lib, self.rows
         comm, world, rank = self.comm, self.world, self.rank
         R = R_MOD
-        by_poly = {}
-        for rot, names in opened.items():
-            for name in names:
-                by_poly.setdefault(name, []).append(rot)
-        sets = []
-        for name, rots in by_poly.items():
-            key = tuple(sorted(rots))
-            for sset in sets:
-                if sset[0] == key:
-                    sset[1].append(name)
-                    break
-            else:
-                sets.append((key, [name]))
+        sets = protocol.rotation_sets(opened)
         squeeze("yo", "v")
         yo, v = _fr_to_int(ch["yo"]), _fr_to_int(ch["v"])
         m = len(sets)
         d_q = [api.DeviceBuffer(rows * B) for _ in sets]
         d_f, d_a, d_b = api.DeviceBuffer(rows * B), self.d_comb, self.d_quot
         ev_int = _Evals(evals)
-
-        def interpolate(pts, vals):          # coefficients (low first) of the polynomial through (pts, vals)
-            coeffs = [0] * len(pts)
-            for i, (xi, yi) in enumerate(zip(pts, vals)):
-                basis, denom = [1], 1
-                for j, xj in enumerate(pts):
-                    if j != i:
-                        basis = [(a - xj * b) % R for a, b in zip([0] + basis, basis + [0])]
-                        denom = denom * (xi - xj) % R
-                scale = yi * pow(denom, -1, R) % R
-                coeffs = [(c + scale * b) % R for c, b in zip(coeffs, basis)]
-            return coeffs
-
-        def at(coeffs, x):
-            acc = 0
-            for c in reversed(coeffs):
-                acc = (acc * x + c) % R
-            return acc
-
-        def vanish(rots, x):
-            acc = 1
-            for rot in rots:
-                acc = acc * (x - points[rot]) % R
-            return acc
 
         def combine(names, dest):
             """dest <- this rank's share of the set's polynomials combined with powers of yo: polynomial j of the M the set has in
@@ -1522,7 +1444,7 @@ class ProverRounds:
                         e = np.ascontiguousarray(evals[(name, rot)], dtype=np.uint64)
                         check(lib.vdb_fr_horner(api._p(e), _sz(e.shape[0]), p["yo"], api._p(acc)))
                     vals.append(_fr_to_int(acc))
-                r = interpolate([points[rot] for rot in rots], vals)
+                r = protocol.interpolate([points[rot] for rot in rots], vals)
                 r_polys.append(r)
                 # (q_S - r_S) / Z_S: the low coefficients on the host, one division per point on the device.  (r_S has fewer
                 # coefficients than Z_S has roots: it changes the remainders only, which is why a rank's share needs no r_S.)
@@ -1550,10 +1472,10 @@ class ProverRounds:
             check(lib.vdb_memset_dev(d_a.ptr, 0, _sz(rows * B)))
             const = 0
             for s_i, (rots, names) in enumerate(sets):
-                coef = pow(v, m - 1 - s_i, R) * vanish([rot for rot in all_rots if rot not in rots], u) % R
+                coef = pow(v, m - 1 - s_i, R) * protocol.vanishing([points[rot] for rot in all_rots if rot not in rots], u) % R
                 check(lib.vdb_poly_axpy_dev(d_a.ptr, api._p(_fr_from_int(coef)), d_q[s_i].ptr, _sz(rows)))
-                const = (const + coef * at(r_polys[s_i], u)) % R
-            check(lib.vdb_poly_axpy_dev(d_a.ptr, api._p(_fr_from_int(-vanish(all_rots, u))), d_f.ptr, _sz(rows)))
+                const = (const + coef * protocol.horner(r_polys[s_i], u)) % R
+            check(lib.vdb_poly_axpy_dev(d_a.ptr, api._p(_fr_from_int(-protocol.vanishing([points[rot] for rot in all_rots], u))), d_f.ptr, _sz(rows)))
             if rank == 0:                                     # the constant term belongs to one share
                 c0 = np.zeros((1, 4), dtype=np.uint64)
                 check(lib.vdb_memcpy_d2h(api._p(c0), d_a.ptr, _sz(32)))
@@ -1588,80 +1510,16 @@ class ProverRounds:
                 setattr(self, name, None)
 
 
-def instance_eval(instances, x, k):
-    """The instance polynomial at x from the public values alone (what a verifier does instead of reading an evaluation from the
-    proof): sum_i v_i L_i(x), L_i(x) = w^i (x^n - 1) / (n (x - w^i)) over the domain of 2^k rows.  Canonical integers."""
-    n = 1 << k
-    w = _fr_to_int(api.root_of_unity(k))
-    if not instances:
-        return 0
-    xn1 = (pow(x, n, R_MOD) - 1) % R_MOD
-    acc, wi = 0, 1
-    dens = []
-    for _ in instances:
-        dens.append((x - wi) % R_MOD)
-        wi = wi * w % R_MOD
-    # one inversion for all denominators
-    pref = [1]
-    for d in dens:
-        pref.append(pref[-1] * d % R_MOD)
-    inv = pow(pref[-1], -1, R_MOD)
-    wi_list = [pow(w, i, R_MOD) for i in range(len(instances))]
-    for i in range(len(instances) - 1, -1, -1):
-        di = inv * pref[i] % R_MOD
-        inv = inv * dens[i] % R_MOD
-        acc = (acc + int(instances[i]) * wi_list[i] % R_MOD * di) % R_MOD
-    return acc * xn1 % R_MOD * pow(n, -1, R_MOD) % R_MOD
-
-
-def lagrange_evals(x, k, usable):
-    """(l_0(x), l_last(x), l_active(x)) as a verifier computes them (halo2 EvaluationDomain::l_i_range): l_i(x) = w^i (x^n - 1) / (n (x - w^i));
-    l_last = l_usable, l_active = 1 - l_last - l_blind with l_blind the sum over the rows behind `usable`"""
-    R, n = R_MOD, 1 << k
-    w = _fr_to_int(api.root_of_unity(k))
-    zn = (pow(x, n, R) - 1) * pow(n, -1, R) % R
-    li = lambda i: pow(w, i, R) * zn % R * pow((x - pow(w, i, R)) % R, -1, R) % R
-    l_last = li(usable)
-    l_blind = sum(li(i) for i in range(usable + 1, n)) % R
-    return li(0), l_last, (1 - l_last - l_blind) % R
-
-
 def quotient_identity_holds(pr, challenges, evals, instances=None):
     """What a verifier checks first: the gate, permutation and lookup expressions recombined from the evaluations at x (and the
-    rotated points) equal h(x) (x^n - 1).  `pr`: the ProverRounds that produced them (for the circuit's shape); `challenges`,
-    `evals`: as returned by ProverRounds.prove.  Plain integer arithmetic on the host."""
-    R = R_MOD
-    b, g, yv, x = (_fr_to_int(challenges[name]) for name in ("beta", "gamma", "y", "x"))
-    delta, n, n_adv = _fr_to_int(pr.delta), pr.rows, pr.n_adv
-    ev = lambda name, rot=0: evals.get((name, rot), [])
-    acc = 0
-    a0, a1, a2, a3, q = ev("adv"), ev("advg", 1), ev("advg", 2), ev("advg", 3), ev("sel")
-    for c in range(n_adv):
-        acc = (acc * yv + q[c] * (a0[c] + a1[c] * a2[c] - a3[c])) % R
-    l0, ll, la = lagrange_evals(x, pr.k, pr.usable)
-    sg, z0, z1, zb = ev("sigma"), ev("zp"), ev("zp", 1), ev("zp", -N_BLIND)
-    # the permutation's columns: advice, lookup, the constants' fixed column, the instance column (evaluated from the public values)
-    pcols = list(a0) + list(ev("cst")) + [instance_eval(list(instances) if instances is not None else [], x, pr.k)]
-    n_cols, n_sets = len(pcols), len(z0)
-    acc = (acc * yv + l0 * (1 - z0[0])) % R
-    acc = (acc * yv + ll * (z0[-1] * z0[-1] - z0[-1])) % R
-    for i in range(1, n_sets):
-        acc = (acc * yv + l0 * (z0[i] - zb[i - 1])) % R
-    cur = b * x % R
-    for i in range(n_sets):
-        left, right = z1[i], z0[i]
-        for c in range(i * pr.chunk_len, min((i + 1) * pr.chunk_len, n_cols)):
-            left = left * (pcols[c] + b * sg[c] + g) % R
-            right = right * (pcols[c] + cur + g) % R
-            cur = cur * delta % R
-        acc = (acc * yv + la * (left - right)) % R
-    A, S, PA, PS, PAm, Z, Z1 = a0[n_adv:], ev("table")[0], ev("pa"), ev("ps"), ev("pa", -1), ev("zl"), ev("zl", 1)
-    for c in range(len(PA)):
-        acc = (acc * yv + l0 * (1 - Z[c])) % R
-        acc = (acc * yv + ll * (Z[c] * Z[c] - Z[c])) % R
-        acc = (acc * yv + la * (Z1[c] * (PA[c] + b) * (PS[c] + g) - Z[c] * (A[c] + b) * (S + g))) % R
-        acc = (acc * yv + l0 * (PA[c] - PS[c])) % R
-        acc = (acc * yv + la * (PA[c] - PS[c]) * (PA[c] - PAm[c])) % R
-    xn = pow(x, n, R)
-    hx = ev("hf")[0]                 # h folded at x: sum_i x^(n i) h_i(x), evaluated by the prover (a verifier computes it from this very identity)
-    return acc == hx * (xn - 1) % R and acc != 0
+    rotated points, protocol.quotient_numerator) equal h(x) (x^n - 1).  `pr`: the ProverRounds that produced them (for the circuit's
+    shape); `challenges`, `evals`: as returned by ProverRounds.prove.  False as well when the evaluations do not have the shape of
+    pr's circuit.  Plain integer arithmetic on the host."""
+    ch = {name: _fr_to_int(challenges[name]) for name in ("beta", "gamma", "y", "x")}
+    meta = protocol.key_meta(pr.k, pr.n_adv, pr.n_lk, len(pr.instance_cells))
+    try:
+        num = protocol.quotient_numerator(meta, ch, evals, list(instances) if instances is not None else [])
+    except ValueError:
+        return False
+    hx = evals[("hf", 0)][0]                 # h folded at x: sum_i x^(n i) h_i(x), evaluated by the prover (a verifier computes it from this very identity)
+    return num == hx * (pow(ch["x"], pr.rows, R_MOD) - 1) % R_MOD and num != 0

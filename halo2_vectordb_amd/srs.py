@@ -21,7 +21,7 @@ import struct
 
 import numpy as np
 
-R_MOD = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
+from .protocol import R_MOD, fr_from_int
 
 
 def _rotl(v, c):
@@ -77,8 +77,7 @@ def gen_srs_tau(seed=bytes(32)):
 
 def tau_mont_limbs(tau):
     """canonical integer -> Montgomery form as 4 x u64 (the layout vdb_srs_setup_unsafe takes)"""
-    v = tau * (1 << 256) % R_MOD
-    return np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+    return fr_from_int(tau)
 
 
 # ---------------------------------------------------------------- halo2's params file (ParamsKZG::{read, write}, SerdeFormat::RawBytes)

@@ -5,7 +5,7 @@ that ProverRounds.prove() wrote against its verifying key.
     ok = verify(proof, instances, vk)                       # True / False, never raises on malformed input
     ok = Verifier.from_files("kmeans.snark", "kmeans.snark.vk.npz").verify()
 
-The protocol is the one the prover runs (rounds.py), replayed from the proof bytes alone:
+The protocol is the one the prover runs (rounds.py; protocol.py states what the two share), replayed from the proof bytes alone:
   1. every compressed point of the proof decompressed in one device call (vdb_g1_decompress_dev);
   2. the Fiat–Shamir transcript replayed (api.Transcript): the key's digest, the public values, then the proof's points and
      evaluations in the order the prover wrote them, squeezing theta, beta, gamma, y, x, the SHPLONK challenges y', v, u;
@@ -22,53 +22,18 @@ import time
 
 import numpy as np
 
-from . import _lib, api
+from . import _lib, api, protocol
 from .api import DeviceBuffer, _p, _sz
+from .protocol import FIXED, R_MOD, fr_from_int, fr_from_ints, fr_to_int
 
-R_MOD = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 Q_MOD = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47
-_R_INV = pow(1 << 256, -1, R_MOD)
-FIXED = ("sel", "sigma", "cst", "table")
-
-
-def _fr_int(a):
-    """Montgomery limbs -> canonical integer"""
-    a = np.asarray(a, dtype=np.uint64).reshape(4)
-    return sum(int(a[i]) << (64 * i) for i in range(4)) * _R_INV % R_MOD
-
-
-def _fr_mont(values):
-    """canonical integers -> (n, 4) Montgomery limbs"""
-    raw = b"".join(((int(v) << 256) % R_MOD).to_bytes(32, "little") for v in values)
-    return np.frombuffer(raw, dtype="<u8").astype(np.uint64).reshape(-1, 4)
-
-
-def _default_opened(n_lk, n_blind):
-    """which polynomial ProverRounds opens at which rotation (rounds.py; what a key without that record describes)"""
-    names = {0: ["adv", "sel", "sigma", "cst", "table", "pa", "ps", "zp", "zl", "hf", "rand"], 1: ["advg", "zp", "zl"], 2: ["advg"], 3: ["advg"], -1: ["pa"],
-             -n_blind: ["zp"]}
-    lookup_only = {"pa", "ps", "zl"}
-    opened = {rot: [n for n in ns if n_lk or n not in lookup_only] for rot, ns in names.items()}
-    return {rot: ns for rot, ns in opened.items() if ns}
 
 
 def _g2_generator_times(s):
     """[s] G2 as a vdb_g2 (16 uint64: x0, x1, y0, y1, Montgomery)"""
     out = np.zeros(16, dtype=np.uint64)
-    api.check(_lib.load().vdb_g2_mul_generator(_p(_fr_mont([s % R_MOD])), _p(out)))
+    api.check(_lib.load().vdb_g2_mul_generator(_p(fr_from_int(s)), _p(out)))
     return out
-
-
-def vk_digest(fixed):
-    """the key's one scalar in the transcript (halo2's vk.transcript_repr): the squeeze of a sponge of its own over every fixed
-    commitment in FIXED order — ProverRounds.vk_digest's construction"""
-    tr = api.Transcript()
-    try:
-        for name in FIXED:
-            tr.common_points(fixed[name])
-        return tr.squeeze()
-    finally:
-        tr.free()
 
 
 class VerifyingKey:
@@ -79,7 +44,7 @@ class VerifyingKey:
     def __init__(self, meta, fixed, opened=None, tau=None, tau_g2=None, g2=None):
         self.meta = {key: int(meta[key]) for key in ("rows", "k", "n_adv", "n_lk", "n_cols", "n_sets", "chunk_len", "n_blind", "delta", "n_instances")}
         self.fixed = {name: np.ascontiguousarray(fixed[name], dtype=np.uint64).reshape(-1, 8) for name in FIXED}
-        self.opened = {int(rot): list(names) for rot, names in (opened or _default_opened(self.meta["n_lk"], self.meta["n_blind"])).items()}
+        self.opened = {int(rot): list(names) for rot, names in (opened or protocol.opened(self.meta["n_lk"], self.meta["n_blind"])).items()}
         if tau_g2 is None:
             if tau is None:
                 raise ValueError("a verifying key needs [tau]_2 or the SRS scalar tau")
@@ -91,9 +56,7 @@ class VerifyingKey:
     @classmethod
     def from_prover(cls, pr, opened=None):
         """the key of a ProverRounds after keygen (what save_verifying_key writes)"""
-        from .rounds import N_BLIND, _fr_to_int
-        meta = dict(rows=pr.rows, k=pr.k, n_adv=pr.n_adv, n_lk=pr.n_lk, n_cols=pr.n_cols, n_sets=pr.n_sets, chunk_len=pr.chunk_len, n_blind=N_BLIND,
-                    delta=_fr_to_int(pr.delta), n_instances=len(pr.instance_cells))
+        meta = protocol.key_meta(pr.k, pr.n_adv, pr.n_lk, len(pr.instance_cells))
         fixed = {name: pr.fixed[name].commits for name in FIXED}
         if pr.hp.tau is None:        # an SRS from a params file
             return cls(meta, fixed, opened, tau_g2=pr.hp.tau_g2, g2=pr.hp.g2)
@@ -120,7 +83,7 @@ class VerifyingKey:
                 vk = cls(meta, fixed, meta.get("opened"), tau_g2=tau_g2, g2=g2)
             else:
                 vk = cls(meta, fixed, meta.get("opened"), tau=meta.get("tau") if tau is None else tau)
-            if "vk_digest" in meta and _fr_int(vk.digest()) != meta["vk_digest"]:
+            if "vk_digest" in meta and fr_to_int(vk.digest()) != meta["vk_digest"]:
                 raise ValueError("the key's digest is not the digest of its commitments")
             return vk
         if tau_g2 is not None:
@@ -134,7 +97,7 @@ class VerifyingKey:
 
     def digest(self):
         if self._digest is None:
-            self._digest = vk_digest(self.fixed)
+            self._digest = protocol.vk_digest(self.fixed)
         return self._digest
 
 
@@ -205,86 +168,6 @@ def _neg_point(pt):
     return pt
 
 
-def _interpolate(pts, vals):
-    """coefficients (low first) of the polynomial through (pts[i], vals[i])"""
-    R = R_MOD
-    coeffs = [0] * len(pts)
-    for i, (xi, yi) in enumerate(zip(pts, vals)):
-        basis, denom = [1], 1
-        for j, xj in enumerate(pts):
-            if j != i:
-                basis = [(a - xj * b) % R for a, b in zip([0] + basis, basis + [0])]
-                denom = denom * (xi - xj) % R
-        scale = yi * pow(denom, -1, R) % R
-        coeffs = [(c + scale * b) % R for c, b in zip(coeffs, basis)]
-    return coeffs
-
-
-def _instance_at(instances, x, k, w):
-    """the instance column at x from the public values: sum_i v_i L_i(x), L_i(x) = w^i (x^n - 1) / (n (x - w^i))"""
-    R, n = R_MOD, 1 << k
-    acc, wi = 0, 1
-    for v in instances:
-        acc = (acc + v * wi * pow((x - wi) % R, -1, R)) % R
-        wi = wi * w % R
-    return acc * (pow(x, n, R) - 1) * pow(n, -1, R) % R
-
-
-def quotient_numerator(meta, ch, evals, instances):
-    """gates + permutation + lookup expressions recombined from the evaluations at x (the prover's quotient identity, rounds.py);
-    raises _Reject when the evaluations do not have the shape the key describes"""
-    R = R_MOD
-    b, g, yv, x = ch["beta"], ch["gamma"], ch["y"], ch["x"]
-    delta, n, n_adv, chunk, n_blind = meta["delta"], meta["rows"], meta["n_adv"], meta["chunk_len"], meta["n_blind"]
-    ev = lambda name, rot=0: evals.get((name, rot), [])
-    acc = 0
-    a0, a1, a2, a3, q = ev("adv"), ev("advg", 1), ev("advg", 2), ev("advg", 3), ev("sel")
-    if min(len(a0), len(a1), len(a2), len(a3), len(q)) < n_adv:
-        raise _Reject
-    for c in range(n_adv):
-        acc = (acc * yv + q[c] * (a0[c] + a1[c] * a2[c] - a3[c])) % R
-    w = _fr_int(api.root_of_unity(meta["k"]))
-    zn = (pow(x, n, R) - 1) * pow(n, -1, R) % R
-    l_at = lambda i: pow(w, i, R) * zn % R * pow((x - pow(w, i, R)) % R, -1, R) % R
-    usable = n - n_blind
-    if not 0 < usable < n:
-        raise _Reject
-    l0, ll = l_at(0), l_at(usable)
-    la = (1 - ll - sum(l_at(i) for i in range(usable + 1, n))) % R
-    sg, z0, z1, zb = ev("sigma"), ev("zp"), ev("zp", 1), ev("zp", -n_blind)
-    # the permutation's columns: advice, lookup, the constants' fixed column, the instance column (from the public values)
-    pcols = list(a0) + list(ev("cst")) + [_instance_at(instances, x, meta["k"], w)]
-    n_cols, n_sets = len(pcols), len(z0)
-    if n_cols != meta["n_cols"] + 2 or len(sg) != n_cols or n_sets == 0 or len(z1) < n_sets or len(zb) < n_sets - 1 or chunk < 1:
-        raise _Reject
-    if n_sets * chunk < n_cols or (n_sets - 1) * chunk >= n_cols:
-        raise _Reject
-    acc = (acc * yv + l0 * (1 - z0[0])) % R
-    acc = (acc * yv + ll * (z0[-1] * z0[-1] - z0[-1])) % R
-    for i in range(1, n_sets):
-        acc = (acc * yv + l0 * (z0[i] - zb[i - 1])) % R
-    cur = b * x % R
-    for i in range(n_sets):
-        left, right = z1[i], z0[i]
-        for c in range(i * chunk, min((i + 1) * chunk, n_cols)):
-            left = left * (pcols[c] + b * sg[c] + g) % R
-            right = right * (pcols[c] + cur + g) % R
-            cur = cur * delta % R
-        acc = (acc * yv + la * (left - right)) % R
-    A, PA, PS, PAm, Z, Z1 = a0[n_adv:], ev("pa"), ev("ps"), ev("pa", -1), ev("zl"), ev("zl", 1)
-    if A:
-        if not ev("table") or min(len(PA), len(PS), len(PAm), len(Z), len(Z1)) < len(A):
-            raise _Reject
-        S = ev("table")[0]
-    for c in range(len(A)):
-        acc = (acc * yv + l0 * (1 - Z[c])) % R
-        acc = (acc * yv + ll * (Z[c] * Z[c] - Z[c])) % R
-        acc = (acc * yv + la * (Z1[c] * (PA[c] + b) * (PS[c] + g) - Z[c] * (A[c] + b) * (S + g))) % R
-        acc = (acc * yv + l0 * (PA[c] - PS[c])) % R
-        acc = (acc * yv + la * (PA[c] - PS[c]) * (PA[c] - PAm[c])) % R
-    return acc
-
-
 def verify(proof, instances, vk, sign_bit=6, timings=None):
     """True when `proof` (the bytes ProverRounds.prove() writes) proves the statement `instances` (the public values, integers)
     under `vk` (a VerifyingKey); False for a wrong proof and for any malformed input — a short or long proof, a point off the
@@ -337,7 +220,7 @@ def _verify(proof, instances, vk, sign_bit, t):
             return out
         tr.common_scalar(vk.digest())
         if instances:
-            tr.common_scalars(_fr_mont(instances))
+            tr.common_scalars(fr_from_ints(instances))
         C = dict(vk.fixed)
         C["adv"] = points(counts["adv"])
         C["advg"] = C["adv"][: meta["n_adv"]]          # the gate columns, opened at rows 1..3 as a group of their own
@@ -351,7 +234,7 @@ def _verify(proof, instances, vk, sign_bit, t):
         C["h"] = points(meta["chunk_len"] + 1)          # the quotient's degree - 1 pieces
         ch["x"] = tr.squeeze()
         if n_evals:
-            tr.common_scalars(_fr_mont(evs))
+            tr.common_scalars(fr_from_ints(evs))
         evals, k = {}, 0
         for rot, names in opened.items():
             for name in names:
@@ -363,41 +246,22 @@ def _verify(proof, instances, vk, sign_bit, t):
         W2 = points(1)[0]
     finally:
         tr.free()
-    ch = {name: _fr_int(v) for name, v in ch.items()}
+    ch = {name: fr_to_int(v) for name, v in ch.items()}
     t["transcript"] = time.perf_counter() - t0
 
     # ---- h folded at x: its value is what the quotient identity demands; its commitment sum_i [x^(n i)] H_i joins the MSM below
     t0 = time.perf_counter()
     x, yo, v, u = ch["x"], ch["yo"], ch["v"], ch["u"]
     xn = pow(x, meta["rows"], R)
-    num = quotient_numerator(meta, ch, evals, instances)
+    num = protocol.quotient_numerator(meta, ch, evals, instances)
     evals[("hf", 0)] = [num * pow((xn - 1) % R, -1, R) % R]
     for name in ("adv", "advg", "sel", "sigma", "cst", "table", "pa", "ps", "zp", "zl", "rand"):
         if any(name in ns for ns in opened.values()) and len(C[name]) != counts[name]:
             raise _Reject
     # ---- SHPLONK: one set per distinct set of rotations
-    w = _fr_int(api.root_of_unity(meta["k"]))
-    at = {rot: x * pow(w, rot % meta["rows"], R) % R for rot in opened}
-    by_poly = {}
-    for rot, names in opened.items():
-        for name in names:
-            by_poly.setdefault(name, []).append(rot)
-    sets = []
-    for name, rots in by_poly.items():
-        key = tuple(sorted(rots))
-        for sset in sets:
-            if sset[0] == key:
-                sset[1].append(name)
-                break
-        else:
-            sets.append((key, [name]))
+    at = protocol.rotation_points(x, meta["k"], opened)
+    sets = protocol.rotation_sets(opened)
     all_rots = sorted({rot for rots, _ in sets for rot in rots})
-
-    def vanish(rots, z):
-        acc = 1
-        for rot in rots:
-            acc = acc * (z - at[rot]) % R
-        return acc
     m, scalars, bases, g_scalar = len(sets), [], [], 0
     for s_i, (rots, names) in enumerate(sets):
         vals = []
@@ -407,10 +271,8 @@ def _verify(proof, instances, vk, sign_bit, t):
                 for e in evals[(name, rot)]:
                     acc = (acc * yo + e) % R
             vals.append(acc)
-        r_u = 0
-        for c in reversed(_interpolate([at[rot] for rot in rots], vals)):
-            r_u = (r_u * u + c) % R
-        coef = pow(v, m - 1 - s_i, R) * vanish([rot for rot in all_rots if rot not in rots], u) % R
+        r_u = protocol.horner(protocol.interpolate([at[rot] for rot in rots], vals), u)
+        coef = pow(v, m - 1 - s_i, R) * protocol.vanishing([at[rot] for rot in all_rots if rot not in rots], u) % R
         n_commits = sum(1 if name == "hf" else len(C[name]) for name in names)
         powers, p = [0] * n_commits, coef
         for i in range(n_commits - 1, -1, -1):            # coef yo^(n_commits - 1 - i) for the i-th commitment of the set
@@ -431,9 +293,9 @@ def _verify(proof, instances, vk, sign_bit, t):
                 i += len(C[name])
         g_scalar = (g_scalar - coef * r_u) % R
     G1 = np.concatenate([_fq_mont(1), _fq_mont(2)])           # the generator (1, 2)
-    scalars += [g_scalar, (-vanish(all_rots, u)) % R, u]
+    scalars += [g_scalar, (-protocol.vanishing([at[rot] for rot in all_rots], u)) % R, u]
     bases += [G1.reshape(1, 8), W1.reshape(1, 8), W2.reshape(1, 8)]
-    sc = _fr_mont(scalars)
+    sc = fr_from_ints(scalars)
     t["algebra"] = time.perf_counter() - t0
     t0 = time.perf_counter()
     left = msm_points(np.concatenate(bases), sc)

@@ -32,7 +32,8 @@ def api():
 
 
 def test_c4_euclidean_hot_path_against_the_oracle(api, O):
-    from halo2_vectordb_amd.pipeline import KmeansHotPath, N_BLIND
+    from halo2_vectordb_amd.pipeline import KmeansHotPath
+    from halo2_vectordb_amd.protocol import N_BLIND
     hp = KmeansHotPath(seed=SEED, blind_seed=77, **CFG).setup()      # (fixed blinds: the commitments are recomputed on the CPU)
     try:
         # the numbers DESIGN.md section 5 and the bench line quote

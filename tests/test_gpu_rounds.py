@@ -169,10 +169,9 @@ def check_openings(O, v_int, commitments, evals, openings):
 
 
 def _meta(pr):
-    from halo2_vectordb_amd.rounds import N_BLIND
-    import halo2_vectordb_amd.rounds as rounds
+    from halo2_vectordb_amd.protocol import N_BLIND, fr_to_int
     return dict(rows=pr.rows, k=pr.k, n_adv=pr.n_adv, n_lk=pr.n_lk, n_cols=pr.n_cols, n_sets=pr.n_sets, chunk_len=pr.chunk_len, n_blind=N_BLIND,
-                delta=rounds._fr_to_int(pr.delta), n_instances=len(pr.instance_cells))
+                delta=fr_to_int(pr.delta), n_instances=len(pr.instance_cells))
 
 
 def test_round_outputs_have_the_expected_shape(circuit, proved):
@@ -683,7 +682,7 @@ def test_a_verifier_accepts_the_proof_bytes_and_rejects_tampered_ones(circuit, O
         assert not _verify(O, api, bytes(bad), vk)
     assert not _verify(O, api, proof[:-32], vk) and not _verify(O, api, proof + bytes(32), vk)
     # a verifying key that states another constraint degree than the circuit's (chunk_len = degree - 2 columns per product polynomial,
-    # degree - 1 quotient pieces; [UPSTREAM-RECALL] for halo2's value, rounds.constraint_degree): the proof is not a proof under it
+    # degree - 1 quotient pieces; [UPSTREAM-RECALL] for halo2's value, protocol.constraint_degree): the proof is not a proof under it
     for wrong in (1, 3):
         n_sets = -(-(vk["meta"]["n_cols"] + 2) // wrong)
         assert not _verify(O, api, proof, {**vk, "meta": {**vk["meta"], "chunk_len": wrong}})

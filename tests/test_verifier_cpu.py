@@ -107,8 +107,9 @@ def _oracle_stages(monkeypatch, O):
 
 def test_the_verifier_protocol_on_a_cpu_proof(monkeypatch, O):
     """C1 proved by the oracle's CPU prover: verifier.verify accepts it and rejects a flipped byte, another statement, a short and a
-    long proof, a missing public value, and a key that states another constraint degree"""
-    from halo2_vectordb_amd import verifier
+    long proof, a missing public value, and a key that states another constraint degree.  The protocol's opening table is what the
+    prover opened, and a key without that record (which falls back to the table) accepts and rejects the same"""
+    from halo2_vectordb_amd import protocol, verifier
     from oracle import prover as PV
     import test_oracle_prover_cpu as C1
     _oracle_stages(monkeypatch, O)
@@ -130,3 +131,7 @@ def test_the_verifier_protocol_on_a_cpu_proof(monkeypatch, O):
     wrong = verifier.VerifyingKey({**meta, "chunk_len": 1}, vk.fixed, out["opened"], tau_g2=vk.tau_g2)
     assert not verifier.verify(proof, inst, wrong)
     assert not verifier.verify(proof, inst, verifier.VerifyingKey(meta, vk.fixed, out["opened"], tau=C1.TAU + 1))
+    assert protocol.opened(cs.n_lk, protocol.N_BLIND) == out["opened"]
+    default = verifier.VerifyingKey(meta, vk.fixed, None, tau=C1.TAU)
+    assert default.opened == out["opened"]
+    assert verifier.verify(proof, inst, default) and not verifier.verify(bytes(bad), inst, default)
