@@ -13,7 +13,12 @@ flat stream.  Multi-GPU: columns are sharded over ranks (strong sc
 cheap value-only path of the whole circuit but emits only the cells of its own columns); every timed step ends
 with the path's one exchange step, the all_gather of the 64-byte commitments over RCCL.
 
+A plain run sets up, warms up, times the steps and prints the line: `roofline` then holds only what the HIP events of the timed
+steps give.  --full adds what takes runs of its own: the whole proof (`proof`), the field-product microbenchmark (`roofline.valu`),
+the CPU port on a sample and one small CPU proof (`cpu_baseline`); --no-proof / --no-cpu-baseline leave parts of it out.
+
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR     (what the last timed step computed, as DIR/*.npy)
 """
@@ -395,25 +400,31 @@ def whole_proof(api, rank=0, world=1, comm=None, small=False):
     return res
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-proof", action="store_true", help="skip the whole-proof measurement that follows the bench line's timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the whole proof, the field-product microbenchmark and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-proof", action="store_true", help="with --full: skip the whole-proof measurement")
     ap.add_argument("--small", action="store_true", help="reduced problem for quick functional checks (not a valid bench line)")
     ap.add_argument("--verify-gather", action="store_true",
                     help="after the timed steps rank 0 re-runs the job unsharded and checks the gathered commitments against it (tests)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write what the last timed step computed as DIR/<name>.npy; that step's blinding rows are seeded, so the same "
                          "arguments give the same outputs from run to run")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.warmup < 0:
         ap.error("--warmup must not be negative")
+    return args
 
+
+def main():
+    args = parse_args()
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -436,12 +447,12 @@ def main():
     from halo2_vectordb_amd.pipeline import KmeansHotPath
     api.init(local_rank % max(1, api.device_count()) if os.environ.get("VDB_DIST_BACKEND", "nccl") == "nccl" else 0)
 
-    # One GPU: the whole-proof measurement runs FIRST, on the card as a fresh process finds it — its setup + keygen time is then the
-    # time a deployment's keygen takes (6 s), not that of a keygen that follows 225 GB of frees (mapping fresh HBM costs this driver
+    # --full, one GPU: the whole-proof measurement runs FIRST, on the card as a fresh process finds it — its setup + keygen time is then
+    # the time a deployment's keygen takes (6 s), not that of a keygen that follows 225 GB of frees (mapping fresh HBM costs this driver
     # ~30 ms / GiB, and an allocation that follows large frees pays again: 11 s).  It stays outside the timed region either way; an
     # exception in it cannot cost the line.  With N > 1 it runs after the line's timed region, in a bounded worker (below).
     proof = None
-    if not args.no_proof and world == 1:
+    if args.full and not args.no_proof and world == 1:
         try:
             proof = whole_proof(api, small=args.small)
         except Exception as e:      # the bench line stands on its own
@@ -540,23 +551,24 @@ def main():
                     "algorithmic_bytes_per_launch": algo_bytes, "algorithmic_bytes_per_step": algo_step,
                     "avg_launch_ms": avg_ms, "launches_per_step": rec["launches"],
                     "timing": "HIP events around every launch of the timed steps, on the launch's own stream (deferred read-out)",
-                    "note": "integer-ALU bound (254-bit Montgomery products on v_mad_u64_u32); see valu",
+                    "note": "integer-ALU bound (254-bit Montgomery products on v_mad_u64_u32); see valu (--full)",
                     "kernels_ms_per_step": {k: round(v["ms"], 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])[:8]}}
-        try:
-            mul_rate = api.bench_fr_mul()
-            roofline["valu"] = {"fr_mul_per_s_microbench": mul_rate}
-            if name == "k_ntt_pass":
-                # field products the two transforms of one column need: butterflies with a non-trivial
-                # twiddle plus the inter-pass / coset / 1/n products, over all launches of the step
-                k, e = hp.k, 2
-                per_col = (n // 2) * (k - 1) + n + (2 * n) // 3 + (4 * n // 2) * (k + e - 2) + 4 * n
-                rate = per_col * hp.my_cols / (rec["ms"] * 1e-3)
-                roofline["valu"].update({"kernel_fr_mul_per_s": rate, "frac_of_microbench": rate / mul_rate,
-                                         "note": "products the NTT makes per second against the library's own field-product microbenchmark "
-                                                 "(vdb_bench_fr_mul, measured in this run): the bound that applies to this kernel"})
-        except Exception:
-            pass
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            try:
+                mul_rate = api.bench_fr_mul()
+                roofline["valu"] = {"fr_mul_per_s_microbench": mul_rate}
+                if name == "k_ntt_pass":
+                    # field products the two transforms of one column need: butterflies with a non-trivial
+                    # twiddle plus the inter-pass / coset / 1/n products, over all launches of the step
+                    k, e = hp.k, 2
+                    per_col = (n // 2) * (k - 1) + n + (2 * n) // 3 + (4 * n // 2) * (k + e - 2) + 4 * n
+                    rate = per_col * hp.my_cols / (rec["ms"] * 1e-3)
+                    roofline["valu"].update({"kernel_fr_mul_per_s": rate, "frac_of_microbench": rate / mul_rate,
+                                             "note": "products the NTT makes per second against the library's own field-product microbenchmark "
+                                                     "(vdb_bench_fr_mul, measured in this run): the bound that applies to this kernel"})
+            except Exception:
+                pass
+        if args.full and world == 1 and not args.no_cpu_baseline:
             hp.relayout()
             ns = min(hp.n_cols, 256)  # ~10-20 s of host work on the GPU box: 1 witness iteration + 3 x 256 columns of MSM / NTT
             idx = list(range(0, hp.n_cols, max(1, hp.n_cols // ns)))[:ns]
@@ -568,7 +580,7 @@ def main():
                 cpu["measured_small_proof"] = {"error": repr(e)[:300]}
 
     abandoned = False
-    if not args.no_proof and dist is not None:
+    if args.full and not args.no_proof and dist is not None:
         from halo2_vectordb_amd._lib import check as _check
         hp.free()
         _check(api.init().vdb_scratch_release())

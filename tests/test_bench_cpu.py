@@ -87,3 +87,11 @@ def test_dumped_limbs_are_exact():
     assert f.dtype == np.float64 and f.shape == (5, 3, 8)
     back = f[..., 0::2].astype(np.uint64) | (f[..., 1::2].astype(np.uint64) << np.uint64(32))
     assert np.array_equal(back, a)
+
+
+def test_full_is_off_by_default():
+    """a plain run measures the headline alone; --full asks for the rest (and --no-proof / --no-cpu-baseline narrow it)"""
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    assert bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    assert bench.parse_args(["--full", "--no-proof"]).full is True
