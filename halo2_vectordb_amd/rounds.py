@@ -18,6 +18,7 @@ with multiopen="gwc"); the order of the quotient's terms follows plonk/evaluatio
 unpinned).  What the tests hold it to instead is what a verifier checks: the quotient identity at a random point recombined
 from the returned evaluations, and every opening against its commitments in the exponent (tests/test_gpu_rounds.py).
 """
+import contextlib
 import ctypes
 from collections.abc import Mapping
 
@@ -28,6 +29,7 @@ import numpy as np
 
 from . import api, protocol
 from ._lib import check
+from .pipeline import MINIMUM_ROWS
 from .protocol import DERIVED, FIXED, N_BLIND, R_MOD, constraint_degree
 from .protocol import fr_from_int as _fr_from_int, fr_to_int as _fr_to_int
 
@@ -43,6 +45,17 @@ BLOCK_COLS = 510 # fixed-polynomial cosets are produced this many columns at a t
 
 def _sz(v):
     return ctypes.c_size_t(int(v))
+
+
+def _position(ranges, i):
+    """position of global index i in a buffer that holds the stretches `ranges` one after the other (this rank's sets in its
+    product buffers, its permutation columns in its sigma buffers)"""
+    off = 0
+    for lo, hi in ranges:
+        if lo <= i < hi:
+            return off + i - lo
+        off += hi - lo
+    raise KeyError(i)
 
 
 class _View:
@@ -104,6 +117,84 @@ class _Poly:
         self.lag = self.coeff = self.ext = None
 
 
+class _Proof:
+    """What one run of ProverRounds.prove carries from round to round: the transcript (None when the challenges are handed
+    in), the challenges `ch` and their pointers `p`, the host's transcript time `host`, the device `timings` (None: untimed),
+    the blinding seed, the polynomials made so far and the public values."""
+
+    def __init__(self, challenges, seed, timings):
+        self.tr = api.Transcript() if challenges is None else None
+        self.ch = {} if challenges is None else {name: np.ascontiguousarray(v, dtype=np.uint64) for name, v in challenges.items()}
+        self.p = {name: api._p(v) for name, v in self.ch.items()}
+        self.host = {"transcript": 0.0}
+        self.timings = timings
+        self._seed = seed
+        self.polys = {}
+        self.instances = []
+        self.resident = False           # every advice coset in the hot path's coset buffer (set by the advice round)
+
+    def seed(self, i):
+        """the blinding seed of slot i, None when the proof is not seeded.  Slots: 0 the advice columns (the hot path), 1 the
+        permuted inputs, 2 the permuted tables, 3 the permutation products, 4 the lookup products, 5 the random polynomial."""
+        return None if self._seed is None else [int(self._seed), i]
+
+    @contextlib.contextmanager
+    def host_transcript(self):
+        """wall-clock time of the host's transcript work inside, added to host["transcript"]"""
+        t0 = time.perf_counter()
+        yield
+        self.host["transcript"] += (time.perf_counter() - t0) * 1e3
+
+    @contextlib.contextmanager
+    def stage(self, name):
+        """device time of the work inside, added to timings[name] — only when timings were asked for: the timer waits for the
+        device, and an untimed proof lets the host's transcript work run beside whatever the device still has queued"""
+        if self.timings is None:
+            yield
+            return
+        api.timer_start()
+        yield
+        self.timings[name] = self.timings.get(name, 0.0) + api.timer_stop()
+
+    def squeeze(self, *names):
+        if self.tr is not None:
+            with self.host_transcript():
+                for name in names:
+                    self.ch[name] = self.tr.squeeze()
+                    self.p[name] = api._p(self.ch[name])
+
+    def write_points(self, points):
+        if self.tr is not None and len(points):
+            with self.host_transcript():
+                self.tr.write_points(np.stack([np.asarray(pt) for pt in points]) if isinstance(points, list) else points)
+
+    def power(self, name, e):
+        """challenge^e as a Montgomery element (a fold that skips e terms another rank holds multiplies by it)"""
+        return _fr_from_int(pow(_fr_to_int(self.ch[name]), int(e), R_MOD))
+
+
+class _Fold:
+    """position in a sum  sum_i t_i c^(N-1-i)  (c = challenge `challenge` of the proof `pf`, N = n_terms) that this rank folds
+    its own terms of, in increasing i, into `acc` (n_elems field elements): `skip_to(i, count)` before terms i .. i + count - 1
+    are folded in (acc <- acc c + t_i) multiplies the accumulator by c for every term in between that another rank holds;
+    `finish()` for the terms after its last.  On one rank nothing is ever skipped."""
+
+    def __init__(self, lib, pf, challenge, acc, n_elems, n_terms):
+        self.lib, self.pf, self.challenge, self.acc, self.n_elems, self.n_terms = lib, pf, challenge, acc, n_elems, n_terms
+        self.pos, self.live = 0, False
+
+    def skip_to(self, i, count):
+        if self.live and i > self.pos:
+            check(self.lib.vdb_poly_scale_dev(self.acc.ptr, api._p(self.pf.power(self.challenge, i - self.pos)), _sz(self.n_elems)))
+        assert i >= self.pos or not self.live, "terms are folded in increasing order"
+        self.pos, self.live = i + count, True
+
+    def finish(self):
+        if self.live and self.n_terms > self.pos:
+            check(self.lib.vdb_poly_scale_dev(self.acc.ptr, api._p(self.pf.power(self.challenge, self.n_terms - self.pos)), _sz(self.n_elems)))
+        self.pos = self.n_terms
+
+
 class ProverRounds:
     """`comm`: the exchange steps of a sharded proof (dist.Comm over torch.distributed: RCCL on a multi-GPU node, gloo in the
     tests) when the hot path `hp` holds one rank's column blocks (col_shard = (rank, world)); None for a proof on one GPU.
@@ -137,6 +228,7 @@ class ProverRounds:
         self.my_sets = sum(hi - lo for lo, hi in self.set_ranges)
         self.my_sig = sum(hi - lo for lo, hi in self.sig_ranges)
         self.adv_ranges = [(self.a_lo, self.a_hi), (self.n_adv + self.l_lo, self.n_adv + self.l_hi)]      # my columns among all advice + lookup columns
+        self.lk_ranges = [(self.l_lo, self.l_hi)]                               # my lookup columns among all lookup columns
         self.foreign = self.map.foreign_cols(self.rank)                        # columns of my sets that another rank holds
         self.stray = self.map.stray_cols(self.rank)                            # my columns that lie in another rank's set
         self.delta = api.fr_delta()
@@ -148,24 +240,6 @@ class ProverRounds:
         self.instance_cells = []
 
     # ------------------------------------------------------------------ local positions of global things
-    def _set_local(self, i):
-        """position of global set i in this rank's product buffers"""
-        off = 0
-        for lo, hi in self.set_ranges:
-            if lo <= i < hi:
-                return off + i - lo
-            off += hi - lo
-        raise KeyError(i)
-
-    def _sig_local(self, p):
-        """position of permutation column p in this rank's sigma buffers"""
-        off = 0
-        for lo, hi in self.sig_ranges:
-            if lo <= p < hi:
-                return off + p - lo
-            off += hi - lo
-        raise KeyError(p)
-
     def _col_local(self, p):
         """position of advice / lookup column p (permutation numbering) in the hot path's column buffer [my advice | my lookup]; None: not mine"""
         if self.a_lo <= p < self.a_hi:
@@ -228,17 +302,14 @@ class ProverRounds:
         if n_cols * cnt == 0:
             return
         if seed is None or ranges is None or n_total == n_cols:
-            d = api.DeviceBuffer(n_cols * cnt * B)
-            api.random_scalars_dev(d.ptr, n_cols * cnt, seed=seed)
-            check(self.lib.vdb_fill_rows_dev(buf.ptr, _sz(n_cols), _sz(self.rows), _sz(from_row), d.ptr))
-        else:
-            d = api.DeviceBuffer(n_total * cnt * B)
-            api.random_scalars_dev(d.ptr, n_total * cnt, seed=seed)
-            off = 0
-            for lo, hi in ranges:
-                if hi > lo:
-                    check(self.lib.vdb_fill_rows_dev(buf.at(off * self.rows * B), _sz(hi - lo), _sz(self.rows), _sz(from_row), d.at(lo * cnt * B)))
-                off += hi - lo
+            ranges, n_total = [(0, n_cols)], n_cols
+        d = api.DeviceBuffer(n_total * cnt * B)
+        api.random_scalars_dev(d.ptr, n_total * cnt, seed=seed)
+        off = 0
+        for lo, hi in ranges:
+            if hi > lo:
+                check(self.lib.vdb_fill_rows_dev(buf.at(off * self.rows * B), _sz(hi - lo), _sz(self.rows), _sz(from_row), d.at(lo * cnt * B)))
+            off += hi - lo
         api.sync()
         d.free()
 
@@ -369,7 +440,6 @@ class ProverRounds:
         # (vdb_permutation_mapping_dev: pointer jumping, one radix sort; copymap.mapping_from_copy_of is the host restatement
         # the tests compare it with).  A map without lookup sources leaves the lookup columns untied: only the tests' negative
         # cases want that.
-        from .pipeline import MINIMUM_ROWS
         d_parent = api.DeviceBuffer(hp.n_cells * 8)
         d_lsrc = None
         if on_dev:
@@ -568,10 +638,17 @@ class ProverRounds:
         blk = max(2 * CHUNK_LEN, min(self.block_cols, -(-max(self.my_sig, 1) // (2 * CHUNK_LEN)) * (2 * CHUNK_LEN)) // (2 * CHUNK_LEN) * (2 * CHUNK_LEN))
         self.blk_alloc = blk
         self.pool_der = api.DeviceBuffer(max(n_der, 1) * rows * B)
+        self.d_pa, self.d_ps, self.d_zp, self.d_zl = (_View(self.pool_der, lo * rows * B, m * rows * B) for lo, m in
+                                                      ((0, self.my_lk), (self.my_lk, self.my_lk), (2 * self.my_lk, self.my_sets), (2 * self.my_lk + self.my_sets, self.my_lk)))
         self.d_lklag = api.DeviceBuffer(max(self.my_lk, 1) * rows * B)
         # what a sharded proof receives from other ranks: the columns that complete the set spanning the advice / lookup junction
         # (Lagrange and coefficient form), one boundary product polynomial per requested set
         self.z_req = self.map.z_requests(self.rank)
+        self.foreign_slot = {c: i for i, c in enumerate(self.foreign)}          # positions in d_foreign_lag / d_foreign_coeff
+        self.z_slot = {i: j for j, i in enumerate(self.z_req)}                  # positions in d_zhalo
+        self.all_foreign = self.map.all_foreign_cols() if self.world > 1 else []     # what the ranks send each other
+        self.all_z = self.map.all_z_requests() if self.world > 1 else []
+        self.l_cosets = tuple(self.fixed["lag"].ext.at(i * self.ne * B) for i in range(3))     # l0, l_last, l_active
         self.d_foreign_lag = api.DeviceBuffer(max(len(self.foreign), 1) * rows * B)
         self.d_foreign_coeff = api.DeviceBuffer(max(len(self.foreign), 1) * rows * B)
         self.d_zhalo = api.DeviceBuffer(max(len(self.z_req), 1) * rows * B)
@@ -809,581 +886,510 @@ class ProverRounds:
         from the quotient identity, halo2's vanishing argument) -> then the multi-open: "gwc": v, one quotient per rotation
         point; "shplonk" (what the reference's gen_snark_shplonk runs, [UPSTREAM-RECALL] for the order of its challenges):
         yo, v; the quotient f of all rotation sets; u; the quotient of the linearisation polynomial.
+        Each round is a method of its own on the proof's state (_Proof), called below in that order.
         `instances`: the public values, one per public cell of keygen (Montgomery field elements); None = read from the witness
         this proof commits to (the honest prover's statement: circuit.instances(), src/scaffold/mod.rs:265).  They fill rows
         0 .. of the instance column, which the permutation argument ties to the public cells.
-        Returns dict(commitments, evals, openings, points, proof, instances): commitments[name] (n, 8); evals[(name, rotation)] list
-        of ints; openings: list of dict(rotation, point, polys=[names in combination order], eval, W).
+        Returns dict(commitments, evals, openings, points, proof, challenges, opened, instances): commitments[name] (n, 8); evals[(name,
+        rotation)] list of ints; openings: "gwc": list of dict(rotation, point, polys=[names in combination order], eval, W), or _shplonk's.
         `seed`: None = every blinding scalar of this proof (advice, lookup and product columns) comes fresh from the
         operating system's entropy, as in halo2's create_proof; an integer makes the proof reproducible (tests).
         Sharded (world > 1, SHPLONK only): every rank calls prove() with the same arguments; each works on its own columns and
         sets and all end with the same proof bytes (see the class docstring and shardmap.py)."""
-        hp, lib, rows, k, ne = self.hp, self.lib, self.rows, self.k, self.ne
-        CHUNK_LEN, N_H, N_SLOTS = self.chunk_len, self.n_h, self.n_slots
-        comm, world, rank = self.comm, self.world, self.rank
-        if world > 1 and multiopen != "shplonk":
+        if self.world > 1 and multiopen != "shplonk":
             raise ValueError("the sharded rounds open with SHPLONK")
-        seeds = iter([None] * 9 if seed is None else [[int(seed), i] for i in range(1, 10)])
-        tr = api.Transcript() if challenges is None else None
-        ch = {} if challenges is None else {name: np.ascontiguousarray(v, dtype=np.uint64) for name, v in challenges.items()}
-        p = {name: api._p(v) for name, v in ch.items()}
+        pf = _Proof(challenges, seed, timings)
+        self.host_ms = pf.host          # wall-clock ms the host spent in the sponge (read by the benches)
+        if pf.tr is not None:
+            pf.tr.common_scalar(self.vk_digest())
+        self._advice(pf, instances)
+        pf.omega = api.root_of_unity(self.k)        # (the products round's sigma columns of a key loaded from a file)
+        self._lookup_permuted(pf)
+        self._receive_foreign()
+        self._products(pf)
+        self._random_poly(pf)
+        self._receive_boundary_products()
+        self._quotient(pf)
+        self._fold_h(pf)
+        allp = {**pf.polys, **self.fixed}
+        opened = protocol.opened(self.n_lk)
+        points = protocol.rotation_points(_fr_to_int(pf.ch["x"]), self.k, opened)
+        evals = self._evaluations(pf, allp, opened, points)
+        if multiopen == "shplonk":
+            openings = self._shplonk(pf, allp, opened, points, evals)
+        else:
+            openings = self._open_gwc(pf, allp, opened, points)
+        proof = None
+        if pf.tr is not None:
+            proof = pf.tr.proof()
+            pf.tr.free()
+        api.sync()
+        return dict(commitments={name: q.commits for name, q in allp.items()}, evals=_Evals(evals), openings=openings, points=points,
+                    proof=proof, challenges={name: v.copy() for name, v in pf.ch.items()}, opened=opened,
+                    instances=[_fr_to_int(v) for v in pf.instances])
 
-        host = self.host_ms = {"transcript": 0.0}     # wall-clock ms the host spent in the sponge (read by the benches)
+    # ------------------------------------------------------------------ the permutation's columns, block by block
+    @property
+    def _blk(self):
+        """columns per block of the streamed stages: `block_cols` (a caller may lower it after keygen) within the blocks allocated"""
+        two = 2 * self.chunk_len
+        return max(two, min(self.block_cols, self.blk_alloc) // two * two)
 
-        def squeeze(*names):
-            if tr is not None:
-                t0 = time.perf_counter()
-                for name in names:
-                    ch[name] = tr.squeeze()
-                    p[name] = api._p(ch[name])
-                host["transcript"] += (time.perf_counter() - t0) * 1e3
+    def _runs(self, c0, nb):
+        """the permutation's columns c0 .. c0 + nb cut into stretches of one kind: (kind, first column, count) with kind
+        "adv" / "lk" (this rank's), "foreign" (another rank's, received), "cst", "inst" """
+        out = []
+        for c in range(c0, c0 + nb):
+            kind = ("cst" if c == self.n_cols else "inst" if c == self.n_cols + 1 else "adv" if self.a_lo <= c < self.a_hi else
+                    "lk" if self.l_lo <= c - self.n_adv < self.l_hi else "foreign")
+            if kind == "foreign" and c not in self.foreign_slot:
+                raise AssertionError("a column of this rank's sets that nobody sent")
+            if out and out[-1][0] == kind and kind not in ("cst", "inst") and (kind != "foreign" or self.foreign_slot[c] == self.foreign_slot[c - 1] + 1):
+                out[-1][2] += 1
+            else:
+                out.append([kind, c, 1])
+        return out
 
-        def write_points(points):
-            if tr is not None and len(points):
-                t0 = time.perf_counter()
-                tr.write_points(np.stack([np.asarray(pt) for pt in points]) if isinstance(points, list) else points)
-                host["transcript"] += (time.perf_counter() - t0) * 1e3
+    def _lagrange_block(self, c0, nb, dest):
+        """the permutation's columns c0 .. c0 + nb in Lagrange form: advice from the stream, lookup from their laid-out copy, constants, instances"""
+        hp, lib, rows = self.hp, self.lib, self.rows
+        for kind, c, m in self._runs(c0, nb):
+            to = dest.at((c - c0) * rows * B)
+            if kind == "adv":
+                check(lib.vdb_layout_columns_range_dev(hp.d_stream.ptr, ctypes.c_uint64(hp.n_cells), api._p(hp.bp), ctypes.c_uint64(len(hp.bp)), self.k,
+                                                       ctypes.c_uint64(c), ctypes.c_uint64(c + m), to, hp.d_blind.ptr, N_BLIND))
+            else:
+                src = (self.d_lklag.at((c - self.n_adv - self.l_lo) * rows * B) if kind == "lk" else self.d_foreign_lag.at(self.foreign_slot[c] * rows * B)
+                       if kind == "foreign" else self.fixed["cst"].lag.ptr if kind == "cst" else self.d_inst_lag.ptr)
+                check(lib.vdb_memcpy_d2d(to, src, _sz(m * rows * B)))
 
-        if tr is not None:
-            tr.common_scalar(self.vk_digest())
-        usable, n_adv, n_lk, n_cols, n_sets = self.usable, self.n_adv, self.n_lk, self.n_cols, self.n_sets
-        a_lo, a_hi, l_lo, l_hi, my_adv, my_lk, my_sets = self.a_lo, self.a_hi, self.l_lo, self.l_hi, self.my_adv, self.my_lk, self.my_sets
-        my_cols = my_adv + my_lk
-        lk_ranges = [(l_lo, l_hi)]
-        fx = self.fixed
-        T = {} if timings is None else timings
+    def _local_ext_index(self, c):
+        """position of permutation column c in the hot path's coset buffer [my advice | my lookup | constants | instance], None: not there"""
+        if c >= self.n_cols:
+            return self.my_adv + self.my_lk + c - self.n_cols
+        return self._col_local(c)
 
-        def stage(name, fn):
-            # device time per stage only when asked for: the timer waits for the device, and an untimed proof lets the host's
-            # transcript work run beside whatever the device still has queued
-            if timings is None:
-                return fn()
-            api.timer_start()
-            r = fn()
-            T[name] = T.get(name, 0.0) + api.timer_stop()
-            return r
+    def _adv_ext_block(self, pf, c0, nb):
+        """(pointer, first column) of a buffer that holds the cosets of the permutation's columns c0 .. c0 + nb"""
+        hp, ne = self.hp, self.ne
+        if pf.resident:
+            loc = [self._local_ext_index(c) for c in range(c0, c0 + nb)]
+            if None not in loc and loc == list(range(loc[0], loc[0] + nb)):
+                return hp.d_ext.ptr, c0 - loc[0]
+        for kind, c, m in self._runs(c0, nb):
+            to = self.d_ea.at((c - c0) * ne * B)
+            if kind in ("adv", "lk"):
+                if pf.resident:
+                    check(self.lib.vdb_memcpy_d2d(to, hp.d_ext.at(self._col_local(c) * ne * B), _sz(m * ne * B)))
+                else:
+                    self._ext_into(hp.d_cols.at(self._col_local(c) * self.rows * B), to, m)
+            elif kind == "foreign":
+                self._ext_into(self.d_foreign_coeff.at(self.foreign_slot[c] * self.rows * B), to, m)
+            else:
+                check(self.lib.vdb_memcpy_d2d(to, (self.fixed["cst"].ext if kind == "cst" else self.d_inst_ext).ptr, _sz(ne * B)))
+        return self.d_ea.ptr, c0
 
-        def power(name, e):
-            """challenge^e as a Montgomery element (a fold that skips e terms another rank holds multiplies by it)"""
-            return _fr_from_int(pow(_fr_to_int(ch[name]), int(e), R_MOD))
+    def _col_ptr(self, base, col0, c):
+        return ctypes.c_void_p(base.value + (c - col0) * self.ne * B)
 
-        class _Fold:
-            """position in a sum  sum_i t_i c^(N-1-i)  that this rank folds its own terms of, in increasing i: `skip_to(i)`
-            before term i is folded in (acc <- acc c + t_i) multiplies the accumulator by c for every term in between that
-            another rank holds; `finish()` for the terms after its last.  On one rank nothing is ever skipped."""
+    def _ext_into(self, coeff_ptr, dest_ptr, m):
+        check(self.lib.vdb_coeff_to_cosets_dev(coeff_ptr, dest_ptr, _sz(m), self.k, self.n_slots, None))
 
-            def __init__(self, acc, n_elems, challenge, n_terms):
-                self.acc, self.n_elems, self.challenge, self.n_terms, self.pos, self.live = acc, n_elems, challenge, n_terms, 0, False
+    def _z_coeff(self, i):
+        """coefficient form of product polynomial i: mine, or the copy its owner sent"""
+        if i in self.z_slot:
+            return self.d_zhalo.at(self.z_slot[i] * self.rows * B)
+        return self.d_zp.at(_position(self.set_ranges, i) * self.rows * B)
 
-            def skip_to(self, i, count):
-                if self.live and i > self.pos:
-                    check(lib.vdb_poly_scale_dev(self.acc.ptr, api._p(power(self.challenge, i - self.pos)), _sz(self.n_elems)))
-                assert i >= self.pos or not self.live, "terms are folded in increasing order"
-                self.pos, self.live = i + count, True
+    # ------------------------------------------------------------------ what the ranks of a sharded proof send each other
+    def _exchange(self, keys, held, dest, slot):
+        """Exchange the polynomials each rank owns: a host slab with one per entry of `keys`, filled from `held` ((position in keys,
+        device pointer) of the ones this rank holds), summed over the ranks; the entries this rank receives (`slot`: key -> position
+        in `dest`) are uploaded into dest.  `keys` is empty on one rank: nothing happens."""
+        if not keys:
+            return
+        slab = np.zeros((len(keys), self.rows, 4), dtype=np.uint64)
+        for j, ptr in held:
+            check(self.lib.vdb_memcpy_d2h(api._p(slab[j]), ptr, _sz(self.rows * B)))
+        slab = self.comm.sum_disjoint(slab)
+        for j, key in enumerate(keys):
+            if key in slot:
+                dest.upload(slab[j], offset=slot[key] * self.rows * B)
 
-            def finish(self):
-                if self.live and self.n_terms > self.pos:
-                    check(lib.vdb_poly_scale_dev(self.acc.ptr, api._p(power(self.challenge, self.n_terms - self.pos)), _sz(self.n_elems)))
-                self.pos = self.n_terms
+    def _held_foreign(self):
+        """(position, pointer) of the Lagrange form of each column of all_foreign this rank holds, laid out one at a time"""
+        tmp = api.DeviceBuffer(self.rows * B)
+        for i, c in enumerate(self.all_foreign):
+            if self._col_local(c) is not None:
+                self._lagrange_block(c, 1, tmp)
+                yield i, tmp.ptr
+        tmp.free()
 
-        # round 1: advice columns (the hot path of the bench: witness, commit, lagrange_to_coeff, coeff_to_extended)
-        resident = hp.ext_cols >= my_cols + 2      # every advice coset stays in HBM; otherwise they are recomputed block by block below
+    # ------------------------------------------------------------------ round 1: advice and instance columns
+    def _advice(self, pf, instances):
+        """the advice columns (the hot path of the bench: witness, commit, lagrange_to_coeff, coeff_to_extended), the instance
+        column made from the public values -> theta"""
+        hp, lib, rows, k, ne = self.hp, self.lib, self.rows, self.k, self.ne
+        my_cols = self.my_adv + self.my_lk
+        pf.resident = hp.ext_cols >= my_cols + 2      # every advice coset stays in HBM; otherwise they are recomputed block by block
         ni = len(self.instance_cells)
         given = None if instances is None else np.ascontiguousarray(np.stack([np.asarray(v, dtype=np.uint64) for v in instances]).reshape(-1, 4) if ni else np.zeros((0, 4), np.uint64))
         assert given is None or len(given) == ni, "one value per public cell"
         inst_host = np.zeros((max(ni, 1), 4), dtype=np.uint64)
-
-        def public_values():
-            # rows 0 .. ni - 1 of the instance column <- the public cells of the witness just generated (or the values of the
-            # statement handed in); the values are needed on the host before the advice commitments enter the transcript, so they
-            # are read here, behind the witness kernels only, and not behind the transforms queued next
-            if not ni:
-                return
-            if given is None:
-                if world == 1:
-                    check(lib.vdb_gather_fr_dev(hp.d_stream.ptr, self.d_inst_cells.ptr, _sz(ni), self.d_inst_lag.ptr))
-                else:
-                    # a rank writes only the cells of its own columns; the values every rank computes are the gadget's results
-                    ptr, cnt = hp.public_values_dev()
-                    if cnt != ni or self.instance_cells != self.public_cells:
-                        raise ValueError("a sharded proof exposes the circuit's default public cells")
-                    check(lib.vdb_memcpy_d2d(self.d_inst_lag.ptr, ptr, _sz(ni * B)))
-                check(lib.vdb_memcpy_d2h(api._p(inst_host), self.d_inst_lag.ptr, _sz(ni * B)))
-            else:
-                inst_host[:ni] = given
-                check(lib.vdb_memcpy_h2d(self.d_inst_lag.ptr, api._p(inst_host), _sz(ni * B)))
         # (the transforms of the advice columns are still running when step returns: the commitments are absorbed meanwhile)
-        adv_local = hp.step(timings, blind_seed=None if seed is None else [int(seed), 0], with_ext=False, sync=False, after_witness=public_values).copy()
-        if resident:        # the cosets of all my columns at once, into the hot path's coset buffer (three of the four it is sized for)
-            stage("ntt", lambda: check(lib.vdb_coeff_to_cosets_dev(hp.d_cols.ptr, hp.d_ext.ptr, _sz(my_cols), k, N_SLOTS, None)))
-        adv_commits = self._globalize(adv_local, self.adv_ranges, n_cols)
-        instances = [inst_host[i].copy() for i in range(ni)]
+        adv_local = hp.step(pf.timings, blind_seed=pf.seed(0), with_ext=False, sync=False, after_witness=lambda: self._public_values(inst_host, given)).copy()
+        if pf.resident:        # the cosets of all my columns at once, into the hot path's coset buffer (three of the four it is sized for)
+            with pf.stage("ntt"):
+                self._ext_into(hp.d_cols.ptr, hp.d_ext.ptr, my_cols)
+        adv_commits = self._globalize(adv_local, self.adv_ranges, self.n_cols)
+        pf.instances = [inst_host[i].copy() for i in range(ni)]
         # the instance polynomial in the forms the rounds read (one column: queued behind the advice transforms)
         check(lib.vdb_memcpy_d2d(self.d_inst_coeff.ptr, self.d_inst_lag.ptr, _sz(rows * B)))
         check(lib.vdb_lagrange_to_coeff_dev(self.d_inst_coeff.ptr, _sz(1), k))
-        check(lib.vdb_coeff_to_cosets_dev(self.d_inst_coeff.ptr, self.d_inst_ext.ptr, _sz(1), k, N_SLOTS, None))
-        if resident:
+        self._ext_into(self.d_inst_coeff.ptr, self.d_inst_ext.ptr, 1)
+        if pf.resident:
             check(lib.vdb_memcpy_d2d(hp.d_ext.at((my_cols + 1) * ne * B), self.d_inst_ext.ptr, _sz(ne * B)))
-        if tr is not None and ni:
-            t0 = time.perf_counter()
-            tr.common_scalars(inst_host[:ni])
-            host["transcript"] += (time.perf_counter() - t0) * 1e3
-        write_points(adv_commits)
-        squeeze("theta")
-        adv = _Poly("adv", my_cols, coeff=hp.d_cols, commits=adv_commits, ranges=self.adv_ranges, n_total=n_cols)
-        n_perm = self.n_perm
+        if pf.tr is not None and ni:
+            with pf.host_transcript():
+                pf.tr.common_scalars(inst_host[:ni])
+        pf.write_points(adv_commits)
+        pf.squeeze("theta")
+        pf.polys["adv"] = _Poly("adv", my_cols, coeff=hp.d_cols, commits=adv_commits, ranges=self.adv_ranges, n_total=self.n_cols)
         # the gate columns once more as a group of their own: only they are read at rows 1..3 (halo2 opens a column at the rotations
         # its queries name — the lookup columns only at the current row)
-        polys = {"adv": adv, "advg": _Poly("advg", my_adv, coeff=hp.d_cols, commits=adv_commits[:n_adv], ranges=[(a_lo, a_hi)], n_total=n_adv)}
-        # Everything below works on blocks of `blk` columns: the Lagrange forms, the sigma columns and every extended coset
-        # exist one block at a time (the advice cosets too, unless the hot path keeps them resident); what stays in HBM is the
-        # streams, the coefficient forms and the derived columns.
-        blk = max(2 * CHUNK_LEN, min(self.block_cols, self.blk_alloc) // (2 * CHUNK_LEN) * (2 * CHUNK_LEN))
-        d_lag_a, d_lag_s, d_ea, d_eb, d_ez, d_zf, d_zlast, d_lklag = self.d_lag_a, self.d_lag_s, self.d_ea, self.d_eb, self.d_ez, self.d_zf, self.d_zlast, self.d_lklag
-        omega = api.root_of_unity(k)
-        bp_p, n_bp = api._p(hp.bp), ctypes.c_uint64(len(hp.bp))
-        from .pipeline import MINIMUM_ROWS
-        lk_blind = hp.d_blind.at(hp.n_adv_cols * N_BLIND * B)
-        foreign_slot = {c: i for i, c in enumerate(self.foreign)}
+        pf.polys["advg"] = _Poly("advg", self.my_adv, coeff=hp.d_cols, commits=adv_commits[: self.n_adv], ranges=[(self.a_lo, self.a_hi)], n_total=self.n_adv)
 
-        def runs(c0, nb):
-            """the permutation's columns c0 .. c0 + nb cut into stretches of one kind: (kind, first column, count) with kind
-            "adv" / "lk" (this rank's), "foreign" (another rank's, received), "cst", "inst" """
-            out = []
-            for c in range(c0, c0 + nb):
-                kind = ("cst" if c == n_cols else "inst" if c == n_cols + 1 else "adv" if a_lo <= c < a_hi else
-                        "lk" if l_lo <= c - n_adv < l_hi else "foreign")
-                if kind == "foreign" and c not in foreign_slot:
-                    raise AssertionError("a column of this rank's sets that nobody sent")
-                if out and out[-1][0] == kind and kind not in ("cst", "inst") and (kind != "foreign" or foreign_slot[c] == foreign_slot[c - 1] + 1):
-                    out[-1][2] += 1
-                else:
-                    out.append([kind, c, 1])
-            return out
+    def _public_values(self, inst_host, given):
+        """rows 0 .. ni - 1 of the instance column <- the public cells of the witness just generated (or the values of the
+        statement handed in); the values are needed on the host before the advice commitments enter the transcript, so they
+        are read here, behind the witness kernels only, and not behind the transforms queued next"""
+        hp, lib, ni = self.hp, self.lib, len(self.instance_cells)
+        if not ni:
+            return
+        if given is None:
+            if self.world == 1:
+                check(lib.vdb_gather_fr_dev(hp.d_stream.ptr, self.d_inst_cells.ptr, _sz(ni), self.d_inst_lag.ptr))
+            else:
+                # a rank writes only the cells of its own columns; the values every rank computes are the gadget's results
+                ptr, cnt = hp.public_values_dev()
+                if cnt != ni or self.instance_cells != self.public_cells:
+                    raise ValueError("a sharded proof exposes the circuit's default public cells")
+                check(lib.vdb_memcpy_d2d(self.d_inst_lag.ptr, ptr, _sz(ni * B)))
+            check(lib.vdb_memcpy_d2h(api._p(inst_host), self.d_inst_lag.ptr, _sz(ni * B)))
+        else:
+            inst_host[:ni] = given
+            check(lib.vdb_memcpy_h2d(self.d_inst_lag.ptr, api._p(inst_host), _sz(ni * B)))
 
-        def lagrange_block(c0, nb, dest):
-            """the permutation's columns c0 .. c0 + nb in Lagrange form: advice from the stream, lookup from their laid-out copy, constants, instances"""
-            for kind, c, m in runs(c0, nb):
-                to = dest.at((c - c0) * rows * B)
-                if kind == "adv":
-                    check(lib.vdb_layout_columns_range_dev(hp.d_stream.ptr, ctypes.c_uint64(hp.n_cells), bp_p, n_bp, k, ctypes.c_uint64(c), ctypes.c_uint64(c + m),
-                                                           to, hp.d_blind.ptr, N_BLIND))
-                else:
-                    src = (d_lklag.at((c - n_adv - l_lo) * rows * B) if kind == "lk" else self.d_foreign_lag.at(foreign_slot[c] * rows * B) if kind == "foreign"
-                           else fx["cst"].lag.ptr if kind == "cst" else self.d_inst_lag.ptr)
-                    check(lib.vdb_memcpy_d2d(to, src, _sz(m * rows * B)))
-
-        def local_ext_index(c):
-            """position of permutation column c in the hot path's coset buffer [my advice | my lookup | constants | instance], None: not there"""
-            loc = self._col_local(c)
-            if loc is not None:
-                return loc
-            return my_cols + (c - n_cols) if c >= n_cols else None
-
-        def adv_ext_block(c0, nb):
-            """(pointer, first column) of a buffer that holds the cosets of the permutation's columns c0 .. c0 + nb"""
-            if resident:
-                loc = [local_ext_index(c) for c in range(c0, c0 + nb)]
-                if None not in loc and loc == list(range(loc[0], loc[0] + nb)):
-                    return hp.d_ext.ptr, c0 - loc[0]
-            for kind, c, m in runs(c0, nb):
-                to = d_ea.at((c - c0) * ne * B)
-                if kind in ("adv", "lk"):
-                    if resident:
-                        check(lib.vdb_memcpy_d2d(to, hp.d_ext.at(self._col_local(c) * ne * B), _sz(m * ne * B)))
-                    else:
-                        check(lib.vdb_coeff_to_cosets_dev(hp.d_cols.at(self._col_local(c) * rows * B), to, _sz(m), k, N_SLOTS, None))
-                elif kind == "foreign":
-                    check(lib.vdb_coeff_to_cosets_dev(self.d_foreign_coeff.at(foreign_slot[c] * rows * B), to, _sz(m), k, N_SLOTS, None))
-                else:
-                    check(lib.vdb_memcpy_d2d(to, (fx["cst"].ext if kind == "cst" else self.d_inst_ext).ptr, _sz(ne * B)))
-            return d_ea.ptr, c0
-
-        def col_ptr(base, col0, c):
-            return ctypes.c_void_p((base.value if hasattr(base, "value") else int(base)) + (c - col0) * ne * B)
-
-        # round 2: the lookup argument's permuted columns
-        counts = {"pa": my_lk, "ps": my_lk, "zp": my_sets, "zl": my_lk}
-        der, off = {}, 0
-        for name, m in counts.items():
-            der[name] = _View(self.pool_der, off * rows * B, m * rows * B)
-            off += m
-        d_pa, d_ps, d_zp, d_zl = der["pa"], der["ps"], der["zp"], der["zl"]
-
-        def permute():
+    # ------------------------------------------------------------------ round 2: the lookup argument's permuted columns
+    def _lookup_permuted(self, pf):
+        """the permuted input and table columns, blinded and committed -> beta, gamma"""
+        hp, lib, rows, my_lk, n_lk, lk_ranges = self.hp, self.lib, self.rows, self.my_lk, self.n_lk, self.lk_ranges
+        with pf.stage("lookup_permute"):
             if my_lk:
-                check(lib.vdb_layout_lookup_range_dev(hp.d_lookup.ptr, ctypes.c_uint64(hp.n_lookup), k, MINIMUM_ROWS, ctypes.c_uint64(l_lo), ctypes.c_uint64(l_hi),
-                                                      d_lklag.ptr, lk_blind, N_BLIND))
-            check(lib.vdb_lookup_permute_dev(d_lklag.ptr, fx["table"].lag.ptr, _sz(my_lk), _sz(rows), _sz(usable), hp.L, d_pa.ptr, d_ps.ptr))
-        stage("lookup_permute", permute)
-        self._blind(d_pa, my_lk, usable, next(seeds), lk_ranges, n_lk)
-        self._blind(d_ps, my_lk, usable, next(seeds), lk_ranges, n_lk)
-        pa_c = stage("commit_permuted", lambda: self._commit(d_pa, my_lk, 1, dense=False))
-        ps_c = stage("commit_permuted", lambda: self._commit(d_ps, my_lk, 1, dense=False))
-        if world > 1:
+                check(lib.vdb_layout_lookup_range_dev(hp.d_lookup.ptr, ctypes.c_uint64(hp.n_lookup), self.k, MINIMUM_ROWS, ctypes.c_uint64(self.l_lo), ctypes.c_uint64(self.l_hi),
+                                                      self.d_lklag.ptr, hp.d_blind.at(hp.n_adv_cols * N_BLIND * B), N_BLIND))
+            check(lib.vdb_lookup_permute_dev(self.d_lklag.ptr, self.fixed["table"].lag.ptr, _sz(my_lk), _sz(rows), _sz(self.usable), hp.L, self.d_pa.ptr, self.d_ps.ptr))
+        self._blind(self.d_pa, my_lk, self.usable, pf.seed(1), lk_ranges, n_lk)
+        self._blind(self.d_ps, my_lk, self.usable, pf.seed(2), lk_ranges, n_lk)
+        with pf.stage("commit_permuted"):
+            pa_c = self._commit(self.d_pa, my_lk, 1, dense=False)
+        with pf.stage("commit_permuted"):
+            ps_c = self._commit(self.d_ps, my_lk, 1, dense=False)
+        if self.world > 1:
             both = self._globalize(np.concatenate([pa_c, ps_c], axis=1), lk_ranges, n_lk)
             pa_c, ps_c = np.ascontiguousarray(both[:, :8]), np.ascontiguousarray(both[:, 8:])
-        polys["pa"] = _Poly("pa", my_lk, lag=d_pa, commits=pa_c, ranges=lk_ranges, n_total=n_lk)
-        polys["ps"] = _Poly("ps", my_lk, lag=d_ps, commits=ps_c, ranges=lk_ranges, n_total=n_lk)
-        if n_lk:
-            write_points(np.stack([polys["pa"].commits, polys["ps"].commits], axis=1).reshape(-1, 8))     # (pa_c, ps_c) per lookup column
-        squeeze("beta", "gamma")
+        pf.polys["pa"] = _Poly("pa", my_lk, lag=self.d_pa, commits=pa_c, ranges=lk_ranges, n_total=n_lk)
+        pf.polys["ps"] = _Poly("ps", my_lk, lag=self.d_ps, commits=ps_c, ranges=lk_ranges, n_total=n_lk)
+        pf.write_points(np.stack([pa_c, ps_c], axis=1).reshape(-1, 8))     # (pa_c, ps_c) per lookup column
+        pf.squeeze("beta", "gamma")
 
-        # the columns of my sets that another rank holds (the set that spans the advice / lookup junction): their holder sends the
-        # Lagrange form, blinding rows included; the coefficient form is made here
-        all_foreign = self.map.all_foreign_cols() if world > 1 else []
-        if all_foreign:
-            slab = np.zeros((len(all_foreign), rows, 4), dtype=np.uint64)
-            tmp = api.DeviceBuffer(rows * B)
-            for i, c in enumerate(all_foreign):
-                if self._col_local(c) is not None:
-                    lagrange_block(c, 1, tmp)
-                    slab[i] = tmp.download((rows, 4))
-            tmp.free()
-            slab = comm.sum_disjoint(slab)
-            for i, c in enumerate(all_foreign):
-                if c in foreign_slot:
-                    self.d_foreign_lag.upload(slab[i], offset=foreign_slot[c] * rows * B)
-            if self.foreign:
-                check(lib.vdb_memcpy_d2d(self.d_foreign_coeff.ptr, self.d_foreign_lag.ptr, _sz(len(self.foreign) * rows * B)))
-                check(lib.vdb_lagrange_to_coeff_dev(self.d_foreign_coeff.ptr, _sz(len(self.foreign)), k))
-            del slab
+    def _receive_foreign(self):
+        """the columns of my sets that another rank holds (the set that spans the advice / lookup junction): their holder sends the
+        Lagrange form, blinding rows included; the coefficient form is made here"""
+        self._exchange(self.all_foreign, self._held_foreign(), self.d_foreign_lag, self.foreign_slot)
+        if self.foreign:
+            check(self.lib.vdb_memcpy_d2d(self.d_foreign_coeff.ptr, self.d_foreign_lag.ptr, _sz(len(self.foreign) * self.rows * B)))
+            check(self.lib.vdb_lagrange_to_coeff_dev(self.d_foreign_coeff.ptr, _sz(len(self.foreign)), self.k))
 
-        # round 3 (beta, gamma): the running products of both arguments
-        def products():
+    # ------------------------------------------------------------------ round 3 (beta, gamma): the running products
+    def _products(self, pf):
+        """the running products of both arguments, blinded and committed, then turned (with the permuted columns) into
+        coefficient form.  The host absorbs one batch of commitments while the device works on the next thing that needs no
+        challenge: the lookup products' MSM beside the permutation products' commitments, the coefficient forms (needed by the
+        quotient, independent of y) beside the lookup products' commitments."""
+        lib, rows, k, usable, my_lk, my_sets, d_zp, blk = self.lib, self.rows, self.k, self.usable, self.my_lk, self.my_sets, self.d_zp, self._blk
+        with pf.stage("products"):
             for s_lo, s_hi in self.set_ranges:
                 p_lo, p_hi = self.map.range_cols((s_lo, s_hi))
                 for c0 in range(p_lo, p_hi, blk):
                     nb = min(blk, p_hi - c0)
-                    lagrange_block(c0, nb, d_lag_a)
+                    self._lagrange_block(c0, nb, self.d_lag_a)
                     if self.d_map32 is not None:
-                        check(lib.vdb_permutation_sigma_packed_dev(self.d_map32.at(c0 * rows * 4), _sz(nb), _sz(n_perm), k, api._p(self.delta), d_lag_s.ptr))
+                        check(lib.vdb_permutation_sigma_packed_dev(self.d_map32.at(c0 * rows * 4), _sz(nb), _sz(self.n_perm), k, api._p(self.delta), self.d_lag_s.ptr))
                     else:                                      # a key loaded from a file: back from the coefficient form
-                        check(lib.vdb_memcpy_d2d(d_lag_s.ptr, fx["sigma"].coeff.at(self._sig_local(c0) * rows * B), _sz(nb * rows * B)))
-                        check(lib.vdb_ntt_batch_dev(d_lag_s.ptr, _sz(nb), k, api._p(omega), 0))
-                    check(lib.vdb_permutation_product_range_dev(d_lag_a.ptr, d_lag_s.ptr, _sz(nb), _sz(c0), k, _sz(usable), _sz(CHUNK_LEN), p["beta"], p["gamma"],
-                                                                api._p(self.delta), d_zp.at(self._set_local(c0 // CHUNK_LEN) * rows * B)))
+                        check(lib.vdb_memcpy_d2d(self.d_lag_s.ptr, self.fixed["sigma"].coeff.at(_position(self.sig_ranges, c0) * rows * B), _sz(nb * rows * B)))
+                        check(lib.vdb_ntt_batch_dev(self.d_lag_s.ptr, _sz(nb), k, api._p(pf.omega), 0))
+                    check(lib.vdb_permutation_product_range_dev(self.d_lag_a.ptr, self.d_lag_s.ptr, _sz(nb), _sz(c0), k, _sz(usable), _sz(self.chunk_len), pf.p["beta"], pf.p["gamma"],
+                                                                api._p(self.delta), d_zp.at(_position(self.set_ranges, c0 // self.chunk_len) * rows * B)))
                 # the products of a range run on from set to set
-                check(lib.vdb_permutation_chain_dev(d_zp.at(self._set_local(s_lo) * rows * B), _sz(s_hi - s_lo), k, _sz(usable)))
-            if world > 1:
+                check(lib.vdb_permutation_chain_dev(d_zp.at(_position(self.set_ranges, s_lo) * rows * B), _sz(s_hi - s_lo), k, _sz(usable)))
+            if self.world > 1:
                 # ... and from range to range across the ranks: every range starts where the one before it ended.  One field
                 # element per range is exchanged (its last running product at the last usable row), every rank multiplies up the
                 # ranges before its own.
                 order = self.map.all_ranges()
                 ends = np.zeros((len(order), 4), dtype=np.uint64)
                 for i, (lo, hi, r) in enumerate(order):
-                    if r == rank:
-                        check(lib.vdb_memcpy_d2h(api._p(ends[i]), d_zp.at((self._set_local(hi - 1) * rows + usable) * B), _sz(B)))
-                ends = comm.sum_disjoint(ends)
+                    if r == self.rank:
+                        check(lib.vdb_memcpy_d2h(api._p(ends[i]), d_zp.at((_position(self.set_ranges, hi - 1) * rows + usable) * B), _sz(B)))
+                ends = self.comm.sum_disjoint(ends)
                 acc = 1
                 for i, (lo, hi, r) in enumerate(order):
-                    if r == rank and acc != 1:
-                        check(lib.vdb_poly_scale_dev(d_zp.at(self._set_local(lo) * rows * B), api._p(_fr_from_int(acc)), _sz((hi - lo) * rows)))
+                    if r == self.rank and acc != 1:
+                        check(lib.vdb_poly_scale_dev(d_zp.at(_position(self.set_ranges, lo) * rows * B), api._p(_fr_from_int(acc)), _sz((hi - lo) * rows)))
                     acc = acc * _fr_to_int(ends[i]) % R_MOD
-            check(lib.vdb_lookup_product_dev(d_lklag.ptr, fx["table"].lag.ptr, d_pa.ptr, d_ps.ptr, _sz(my_lk), _sz(rows), _sz(usable), p["beta"], p["gamma"],
-                                             d_zl.ptr))
-        stage("products", products)
-        self._blind(d_zp, my_sets, usable + 1, next(seeds), self.set_ranges, n_sets)
-        self._blind(d_zl, my_lk, usable + 1, next(seeds), lk_ranges, n_lk)
-        def derived_forms(names):
-            for name in names:
-                q = polys[name]
-                check(lib.vdb_lagrange_to_coeff_dev(q.lag.ptr, _sz(q.n_cols), k))      # in place: the Lagrange form is not needed again
-                q.coeff, q.lag = q.lag, None
-        # The host absorbs one batch of commitments while the device works on the next thing that needs no challenge: the lookup
-        # products' MSM beside the permutation products' commitments, the coefficient forms (needed by the quotient, independent of y)
-        # beside the lookup products' commitments.
-        zp_c = self._globalize(stage("commit_products", lambda: self._commit(d_zp, my_sets, 1)), self.set_ranges, n_sets)
-        polys["zp"] = _Poly("zp", my_sets, lag=d_zp, commits=zp_c, ranges=self.set_ranges, n_total=n_sets)
-        stage("commit_products", lambda: self._commit_begin(d_zl, my_lk, 1))
+            check(lib.vdb_lookup_product_dev(self.d_lklag.ptr, self.fixed["table"].lag.ptr, self.d_pa.ptr, self.d_ps.ptr, _sz(my_lk), _sz(rows), _sz(usable), pf.p["beta"], pf.p["gamma"],
+                                             self.d_zl.ptr))
+        self._blind(d_zp, my_sets, usable + 1, pf.seed(3), self.set_ranges, self.n_sets)
+        self._blind(self.d_zl, my_lk, usable + 1, pf.seed(4), self.lk_ranges, self.n_lk)
+        with pf.stage("commit_products"):
+            zp_c = self._commit(d_zp, my_sets, 1)
+        pf.polys["zp"] = _Poly("zp", my_sets, lag=d_zp, commits=self._globalize(zp_c, self.set_ranges, self.n_sets), ranges=self.set_ranges, n_total=self.n_sets)
+        with pf.stage("commit_products"):
+            self._commit_begin(self.d_zl, my_lk, 1)
         try:
-            write_points(polys["zp"].commits)
+            pf.write_points(pf.polys["zp"].commits)
         except Exception:
             lib.vdb_msm_batch_end(None, _sz(0))       # a deferred MSM must always be collected, or every later MSM is refused
             raise
-        zl_c = self._globalize(stage("commit_products", lambda: self._commit_end(my_lk)), lk_ranges, n_lk)
-        polys["zl"] = _Poly("zl", my_lk, lag=d_zl, commits=zl_c, ranges=lk_ranges, n_total=n_lk)
-        stage("derived_ntt", lambda: derived_forms(("pa", "ps", "zp", "zl")))
-        write_points(polys["zl"].commits)
-        # The vanishing argument's random polynomial (halo2 plonk/vanishing/prover.rs Argument::commit, [UPSTREAM-RECALL]): n uniform
-        # coefficients, committed before y is squeezed and opened at x beside the folded quotient — it blinds the one evaluation of h
-        # the multi-open reveals.  In a sharded proof rank 0 draws it and every rank receives the same coefficients.
-        d_rand = self.d_rand
-        if rank == 0:
-            api.random_scalars_dev(d_rand.ptr, rows, seed=next(seeds))
-        if world > 1:
-            rc = np.zeros((rows, 4), dtype=np.uint64)
-            if rank == 0:
-                check(lib.vdb_memcpy_d2h(api._p(rc), d_rand.ptr, _sz(rows * B)))
-            rc = comm.sum_disjoint(rc)
-            if rank != 0:
-                d_rand.upload(rc)
-        polys["rand"] = _Poly("rand", 1, coeff=d_rand, commits=stage("commit_h", lambda: self._commit(d_rand, 1, 0)), replicated=True)
-        write_points(polys["rand"].commits)
-        squeeze("y")
+        with pf.stage("commit_products"):
+            zl_c = self._commit_end(my_lk)
+        pf.polys["zl"] = _Poly("zl", my_lk, lag=self.d_zl, commits=self._globalize(zl_c, self.lk_ranges, self.n_lk), ranges=self.lk_ranges, n_total=self.n_lk)
+        with pf.stage("derived_ntt"):
+            for name in ("pa", "ps", "zp", "zl"):
+                q = pf.polys[name]
+                check(lib.vdb_lagrange_to_coeff_dev(q.lag.ptr, _sz(q.n_cols), k))      # in place: the Lagrange form is not needed again
+                q.coeff, q.lag = q.lag, None
+        pf.write_points(pf.polys["zl"].commits)
 
-        # the boundary products other ranks ask for, in coefficient form: the set before each of their ranges, and the first set
-        # for the rank that closes the chain
-        zp = polys["zp"]
-        z_slot = {i: j for j, i in enumerate(self.z_req)}
-        all_z = self.map.all_z_requests() if world > 1 else []
-        if all_z:
-            slab = np.zeros((len(all_z), rows, 4), dtype=np.uint64)
-            for j, i in enumerate(all_z):
-                if self.map.set_owner(i) == rank:
-                    check(lib.vdb_memcpy_d2h(api._p(slab[j]), zp.coeff.at(self._set_local(i) * rows * B), _sz(rows * B)))
-            slab = comm.sum_disjoint(slab)
-            for j, i in enumerate(all_z):
-                if i in z_slot:
-                    self.d_zhalo.upload(slab[j], offset=z_slot[i] * rows * B)
-            del slab
+    def _random_poly(self, pf):
+        """The vanishing argument's random polynomial (halo2 plonk/vanishing/prover.rs Argument::commit, [UPSTREAM-RECALL]): n uniform
+        coefficients, committed before y is squeezed and opened at x beside the folded quotient — it blinds the one evaluation of h
+        the multi-open reveals.  In a sharded proof rank 0 draws it and every rank receives the same coefficients.  -> y"""
+        if self.rank == 0:
+            api.random_scalars_dev(self.d_rand.ptr, self.rows, seed=pf.seed(5))
+        self._exchange([0] if self.world > 1 else [], [(0, self.d_rand.ptr)] if self.rank == 0 else [], self.d_rand, {} if self.rank == 0 else {0: 0})
+        with pf.stage("commit_h"):
+            rand_c = self._commit(self.d_rand, 1, 0)
+        pf.polys["rand"] = _Poly("rand", 1, coeff=self.d_rand, commits=rand_c, replicated=True)
+        pf.write_points(rand_c)
+        pf.squeeze("y")
 
-        def z_coeff(i):
-            """coefficient form of product polynomial i: mine, or the copy its owner sent"""
-            if i in z_slot:
-                return self.d_zhalo.at(z_slot[i] * rows * B)
-            return zp.coeff.at(self._set_local(i) * rows * B)
+    def _receive_boundary_products(self):
+        """the boundary products other ranks ask for, in coefficient form: the set before each of their ranges, the first set for the chain's closer"""
+        self._exchange(self.all_z, ((j, self._z_coeff(i)) for j, i in enumerate(self.all_z) if self.map.set_owner(i) == self.rank), self.d_zhalo, self.z_slot)
 
-        # round 4 (y): the quotient
-        d_h = self.d_h
-        l0, ll, la = (ctypes.c_void_p(fx["lag"].ext.ptr.value + i * ne * B) for i in range(3))
-
-        def to_ext(coeff_ptr, dest_ptr, m):
-            check(lib.vdb_coeff_to_cosets_dev(coeff_ptr, dest_ptr, _sz(m), k, N_SLOTS, None))
-
-        def quotient():
-            # The numerator is sum_i term_i y^(N-1-i) over the terms in halo2's order: gates (one per advice column),
-            # the permutation argument (two terms of the product columns alone, the chaining of the sets, one product term per set),
-            # the lookup argument (five per lookup column).  Each group is folded into an accumulator of its own (acc <- acc y +
-            # term, from zero) while ONE sweep over blocks of columns produces every coset once — the advice / lookup / constants
-            # cosets (unless resident), selectors, sigma, product and lookup-argument cosets — and the groups are joined at the end:
-            # h = ((Ag y^n2 + A2) y^n3 + A3) y^n4 + A4.  (The public inputs have no term of their own: the instance column is one
-            # of the permutation's columns.)
-            # Everything is evaluated coset by coset on N_SLOTS = 3 of the extended domain's four cosets (the quotient has degree below
-            # 3 n; 2 of 2 for a circuit of degree 3).  The gates have degree 3: their share of the quotient, Ag / (X^n - 1), has degree below 2 n, so Ag is evaluated on
-            # two of them (slots 0 and 1 of the advice cosets; the selector cosets are made for those two only), brought back to
-            # coefficients from there, and joined in coefficient form.
-            # Sharded: a rank folds the terms of its own columns and sets (the folds skip what other ranks hold: _Fold); every step
-            # after that — the joins, the division by X^n - 1, the way back to coefficients — is linear, so each rank ends with a
-            # share of h's coefficients and the shares are added (the one bulk exchange of the proof: 2^(k+2) x 32 B per rank).
-            ag, a2, a3, a4 = self.d_hg, self.d_h2, self.d_h3, self.d_h4
+    # ------------------------------------------------------------------ round 4 (y): the quotient
+    def _quotient(self, pf):
+        """h's pieces, committed -> x.  The numerator is sum_i term_i y^(N-1-i) over the terms in halo2's order: gates (one per advice column),
+        the permutation argument (two terms of the product columns alone, the chaining of the sets, one product term per set),
+        the lookup argument (five per lookup column).  Each group is folded into an accumulator of its own (acc <- acc y +
+        term, from zero) while ONE sweep over blocks of columns produces every coset once — the advice / lookup / constants
+        cosets (unless resident), selectors, sigma, product and lookup-argument cosets — and the groups are joined at the end:
+        h = ((Ag y^n2 + A2) y^n3 + A3) y^n4 + A4.  (The public inputs have no term of their own: the instance column is one
+        of the permutation's columns.)
+        Everything is evaluated coset by coset on N_SLOTS = 3 of the extended domain's four cosets (the quotient has degree below
+        3 n; 2 of 2 for a circuit of degree 3).  The gates have degree 3: their share of the quotient, Ag / (X^n - 1), has degree below 2 n, so Ag is evaluated on
+        two of them (slots 0 and 1 of the advice cosets; the selector cosets are made for those two only), brought back to
+        coefficients from there, and joined in coefficient form.
+        Sharded: a rank folds the terms of its own columns and sets (the folds skip what other ranks hold: _Fold); every step
+        after that — the joins, the division by X^n - 1, the way back to coefficients — is linear, so each rank ends with a
+        share of h's coefficients and the shares are added (the one bulk exchange of the proof: 2^(k+2) x 32 B per rank)."""
+        lib, rows, k, ne, n_adv, n_sets, blk = self.lib, self.rows, self.k, self.ne, self.n_adv, self.n_sets, self._blk
+        ag, a2, a3, a4 = self.d_hg, self.d_h2, self.d_h3, self.d_h4
+        n2, n3, n4 = 2 + (n_sets - 1), n_sets, 5 * self.n_lk
+        folds = (_Fold(lib, pf, "y", ag, GATE_SLOTS * rows, n_adv), _Fold(lib, pf, "y", a2, ne, n2), _Fold(lib, pf, "y", a3, ne, n3), _Fold(lib, pf, "y", a4, ne, n4))
+        perm_args = (_sz(self.n_perm), _sz(self.chunk_len), k, self.n_slots, _sz(self.usable), *self.l_cosets, pf.p["beta"], pf.p["gamma"], api._p(self.delta), pf.p["y"])
+        with pf.stage("quotient"):
             for a in (a2, a3, a4):
                 check(lib.vdb_memset_dev(a.ptr, 0, _sz(ne * B)))
             check(lib.vdb_memset_dev(ag.ptr, 0, _sz(GATE_SLOTS * rows * B)))
-            n2, n3, n4 = 2 + (n_sets - 1), n_sets, 5 * n_lk
-            f_g, f_2, f_3, f_4 = _Fold(ag, GATE_SLOTS * rows, "y", n_adv), _Fold(a2, ne, "y", n2), _Fold(a3, ne, "y", n3), _Fold(a4, ne, "y", n4)
-            perm_args = (_sz(n_perm), _sz(CHUNK_LEN), k, N_SLOTS, _sz(usable), l0, ll, la, p["beta"], p["gamma"], api._p(self.delta), p["y"])
             # l0 (1 - z_0), l_last (z_last^2 - z_last): the first two terms of group 2, folded in by the owner of the last set
-            if self.map.head_owner() == rank:
-                to_ext(z_coeff(0), d_zf.ptr, 1)
-                to_ext(z_coeff(n_sets - 1), d_zlast.ptr, 1)
-                f_2.skip_to(0, 2)
-                check(lib.vdb_permutation_eval_parts_cosets_dev(None, _sz(0), None, None, _sz(0), d_zf.ptr, d_zlast.ptr, *perm_args, a2.ptr, 1, _sz(0), _sz(0), _sz(0), _sz(0)))
-            third = blk // 3
-            sigma_scaled = os.environ.get("VDB_SIGMA_SCALED", "1") != "0"      # (0: the A/B baseline — sigma's own cosets, the product by beta per point)
-            fixed_resident = getattr(self, "fixed_cosets_resident", False)
-
-            def lookup_terms(base, col0, j_lo, j_hi):
-                """the lookup argument of my lookup columns j_lo .. j_hi, whose input cosets are in the block at `base`:
-                [permuted input | permuted table | product] cosets in thirds of one buffer"""
-                for j0 in range(j_lo, max(j_hi, j_lo), third):
-                    m = min(third, j_hi - j0)
-                    to_ext(polys["pa"].coeff.at((j0 - l_lo) * rows * B), d_eb.ptr, m)
-                    to_ext(polys["ps"].coeff.at((j0 - l_lo) * rows * B), d_eb.at(third * ne * B), m)
-                    to_ext(polys["zl"].coeff.at((j0 - l_lo) * rows * B), d_eb.at(2 * third * ne * B), m)
-                    f_4.skip_to(5 * j0, 5 * m)
-                    check(lib.vdb_lookup_eval_cosets_dev(col_ptr(base, col0, n_adv + j0), fx["table"].ext.ptr, d_eb.ptr, d_eb.at(third * ne * B), d_eb.at(2 * third * ne * B),
-                                                         _sz(m), k, N_SLOTS, l0, ll, la, p["beta"], p["gamma"], p["y"], a4.ptr))
+            if self.map.head_owner() == self.rank:
+                self._ext_into(self._z_coeff(0), self.d_zf.ptr, 1)
+                self._ext_into(self._z_coeff(n_sets - 1), self.d_zlast.ptr, 1)
+                folds[1].skip_to(0, 2)
+                check(lib.vdb_permutation_eval_parts_cosets_dev(None, _sz(0), None, None, _sz(0), self.d_zf.ptr, self.d_zlast.ptr, *perm_args, a2.ptr, 1, _sz(0), _sz(0), _sz(0), _sz(0)))
             # my lookup columns that complete another rank's set (the head of the lookup columns, at the advice / lookup junction):
             # their lookup argument is mine all the same, and comes first in the order of the terms
             stray_lk = sorted(c for c in self.stray if c >= n_adv)
             if stray_lk:
                 assert stray_lk == list(range(stray_lk[0], stray_lk[0] + len(stray_lk)))
-                base, col0 = adv_ext_block(stray_lk[0], len(stray_lk))
-                lookup_terms(base, col0, stray_lk[0] - n_adv, stray_lk[-1] + 1 - n_adv)
+                base, col0 = self._adv_ext_block(pf, stray_lk[0], len(stray_lk))
+                self._lookup_terms(pf, folds[3], base, col0, stray_lk[0] - n_adv, stray_lk[-1] + 1 - n_adv)
             assert all(c >= n_adv for c in self.stray), "an advice column outside its rank's sets"
             for s_lo, s_hi in self.set_ranges:
                 p_lo, p_hi = self.map.range_cols((s_lo, s_hi))
                 for c0 in range(p_lo, p_hi, blk):
-                    nb = min(blk, p_hi - c0)
-                    base, col0 = adv_ext_block(c0, nb)
-                    g0, g1 = max(c0, a_lo), min(c0 + nb, a_hi)
-                    if g0 < g1:                                            # gates of the block's advice columns
-                        if fixed_resident:
-                            sel_ptr = fx["sel"].ext.at((g0 - a_lo) * GATE_SLOTS * rows * B)
-                        else:
-                            check(lib.vdb_coeff_to_cosets_dev(fx["sel"].coeff.at((g0 - a_lo) * rows * B), d_eb.ptr, _sz(g1 - g0), k, GATE_SLOTS, None))
-                            sel_ptr = d_eb.ptr
-                        f_g.skip_to(g0, g1 - g0)
-                        check(lib.vdb_gate_eval_cosets_dev(col_ptr(base, col0, g0), N_SLOTS, sel_ptr, _sz(g1 - g0), k, GATE_SLOTS, p["y"], ag.ptr))
-                    # permutation: the block's sets with their sigma cosets and product cosets (one set more in front for the chaining)
-                    set_lo, set_hi = c0 // CHUNK_LEN, -(-(c0 + nb) // CHUNK_LEN)
-                    z0 = max(set_lo - 1, 0)
-                    # (the cosets of beta sigma: the scalar rides on the transform's coset factors, the evaluation skips a product per point)
-                    # resident sigma cosets (keygen): no transform, the evaluation multiplies by beta itself
-                    if fixed_resident:
-                        sig_ptr, sig_head = fx["sigma"].ext.at(self._sig_local(c0) * ne * B), 0
-                    elif sigma_scaled:
-                        check(lib.vdb_coeff_to_cosets_dev(fx["sigma"].coeff.at(self._sig_local(c0) * rows * B), d_eb.ptr, _sz(nb), k, N_SLOTS, p["beta"]))
-                        sig_ptr, sig_head = d_eb.ptr, 2
-                    else:
-                        to_ext(fx["sigma"].coeff.at(self._sig_local(c0) * rows * B), d_eb.ptr, nb)
-                        sig_ptr, sig_head = d_eb.ptr, 0
-                    if z0 < set_lo and (z0 in z_slot or z0 < s_lo):          # the set in front is another rank's (or another range's)
-                        to_ext(z_coeff(z0), d_ez.ptr, 1)
-                        to_ext(z_coeff(set_lo), d_ez.at(ne * B), set_hi - set_lo)
-                    else:
-                        to_ext(z_coeff(z0), d_ez.ptr, set_hi - z0)
-                    if max(set_lo, 1) < set_hi:
-                        f_2.skip_to(max(set_lo, 1) + 1, set_hi - max(set_lo, 1))
-                        check(lib.vdb_permutation_eval_parts_cosets_dev(None, _sz(0), None, d_ez.ptr, _sz(z0), None, None, *perm_args, a2.ptr, 0, _sz(max(set_lo, 1)), _sz(set_hi),
-                                                                 _sz(0), _sz(0)))
-                    f_3.skip_to(set_lo, set_hi - set_lo)
-                    check(lib.vdb_permutation_eval_parts_cosets_dev(base, _sz(col0), sig_ptr, d_ez.ptr, _sz(z0), None, None, *perm_args, a3.ptr, sig_head, _sz(0), _sz(0), _sz(set_lo),
-                                                             _sz(set_hi)))
-                    # lookup argument of the block's lookup columns that are mine
-                    j_lo, j_hi = max(c0 - n_adv, l_lo), min(c0 + nb - n_adv, l_hi)
-                    lookup_terms(base, col0, j_lo, j_hi)
-            for f in (f_g, f_2, f_3, f_4):
+                    self._quotient_block(pf, folds, perm_args, s_lo, c0, min(blk, p_hi - c0))
+            for f in folds:
                 f.finish()
             # join the groups that live on the 4 n points (acc_next += y^(terms of the next group) * acc), divide, back to coefficients
-            y_int = _fr_to_int(ch["y"])
+            y_int = _fr_to_int(pf.ch["y"])
             check(lib.vdb_poly_axpy_dev(a3.ptr, api._p(_fr_from_int(pow(y_int, n3, R_MOD))), a2.ptr, _sz(ne)))
             check(lib.vdb_poly_axpy_dev(a4.ptr, api._p(_fr_from_int(pow(y_int, n4, R_MOD))), a3.ptr, _sz(ne)))
             # (division by X^n - 1 — a constant per coset —, residues modulo X^n - g_t^n, the Vandermonde system in g_t^n: N_H pieces)
-            check(lib.vdb_cosets_to_coeff_dev(a4.ptr, d_h.ptr, k, N_SLOTS))
+            check(lib.vdb_cosets_to_coeff_dev(a4.ptr, self.d_h.ptr, k, self.n_slots))
             # the gates' share: the same from its two cosets, then h += y^(every later term) * (its 2 n coefficients)
             check(lib.vdb_cosets_to_coeff_dev(ag.ptr, a2.ptr, k, GATE_SLOTS))
-            check(lib.vdb_poly_axpy_dev(d_h.ptr, api._p(_fr_from_int(pow(y_int, n2 + n3 + n4, R_MOD))), a2.ptr, _sz(GATE_SLOTS * rows)))
-            comm.sum_field_dev(d_h.ptr, ne)                      # every rank's share of h (nothing to do on one rank)
-        stage("quotient", quotient)
-        n_h = N_H                                             # h(X) = sum_i X^(n i) h_i(X), degree below (degree - 1) n
-        polys["h"] = _Poly("h", n_h, coeff=d_h, commits=stage("commit_h", lambda: self._commit(d_h, n_h, 0)), replicated=True)
-        write_points(polys["h"].commits)
-        squeeze("x")
-        # h folded at x (halo2 vanishing::Constructed::evaluate): hf(X) = sum_i x^(n i) h_i(X), one polynomial of degree below n whose
-        # commitment the verifier forms from the pieces' and whose value at x it computes from the quotient identity — neither is sent
-        xn = pow(_fr_to_int(ch["x"]), rows, R_MOD)
-        d_hf = self.d_hf
-        check(lib.vdb_memcpy_d2d(d_hf.ptr, d_h.ptr, _sz(rows * B)))
-        for i in range(1, n_h):
-            check(lib.vdb_poly_axpy_dev(d_hf.ptr, api._p(_fr_from_int(pow(xn, i, R_MOD))), d_h.at(i * rows * B), _sz(rows)))
-        polys["hf"] = _Poly("hf", 1, coeff=d_hf, commits=stage("commit_h", lambda: self._commit(d_hf, 1, 0)), replicated=True)
+            check(lib.vdb_poly_axpy_dev(self.d_h.ptr, api._p(_fr_from_int(pow(y_int, n2 + n3 + n4, R_MOD))), a2.ptr, _sz(GATE_SLOTS * rows)))
+            self.comm.sum_field_dev(self.d_h.ptr, ne)                      # every rank's share of h (nothing to do on one rank)
+        with pf.stage("commit_h"):
+            h_c = self._commit(self.d_h, self.n_h, 0)      # h(X) = sum_i X^(n i) h_i(X), degree below (degree - 1) n
+        pf.polys["h"] = _Poly("h", self.n_h, coeff=self.d_h, commits=h_c, replicated=True)
+        pf.write_points(h_c)
+        pf.squeeze("x")
 
-        # round 5 (x): evaluations, at the rotations protocol.opened states
-        allp = {**polys, **fx}
-        opened = protocol.opened(self.n_lk)
-        points = protocol.rotation_points(_fr_to_int(ch["x"]), k, opened)
-        evals = {}
+    def _quotient_block(self, pf, folds, perm_args, s_lo, c0, nb):
+        """the quotient's terms of the permutation's columns c0 .. c0 + nb (in the range of sets from s_lo): gates, permutation, lookups"""
+        lib, rows, k, ne, fx, chunk, d_eb, d_ez = self.lib, self.rows, self.k, self.ne, self.fixed, self.chunk_len, self.d_eb, self.d_ez
+        f_g, f_2, f_3, f_4 = folds
+        base, col0 = self._adv_ext_block(pf, c0, nb)
+        g0, g1 = max(c0, self.a_lo), min(c0 + nb, self.a_hi)
+        if g0 < g1:                                            # gates of the block's advice columns
+            if self.fixed_cosets_resident:
+                sel_ptr = fx["sel"].ext.at((g0 - self.a_lo) * GATE_SLOTS * rows * B)
+            else:
+                check(lib.vdb_coeff_to_cosets_dev(fx["sel"].coeff.at((g0 - self.a_lo) * rows * B), d_eb.ptr, _sz(g1 - g0), k, GATE_SLOTS, None))
+                sel_ptr = d_eb.ptr
+            f_g.skip_to(g0, g1 - g0)
+            check(lib.vdb_gate_eval_cosets_dev(self._col_ptr(base, col0, g0), self.n_slots, sel_ptr, _sz(g1 - g0), k, GATE_SLOTS, pf.p["y"], self.d_hg.ptr))
+        # permutation: the block's sets with their sigma cosets and product cosets (one set more in front for the chaining)
+        set_lo, set_hi = c0 // chunk, -(-(c0 + nb) // chunk)
+        z0 = max(set_lo - 1, 0)
+        if self.fixed_cosets_resident:      # resident sigma cosets (keygen): no transform, the evaluation multiplies by beta itself
+            sig_ptr, sig_head = fx["sigma"].ext.at(_position(self.sig_ranges, c0) * ne * B), 0
+        else:                               # the cosets of beta sigma: the scalar rides on the transform's coset factors, the evaluation skips a product per point
+            check(lib.vdb_coeff_to_cosets_dev(fx["sigma"].coeff.at(_position(self.sig_ranges, c0) * rows * B), d_eb.ptr, _sz(nb), k, self.n_slots, pf.p["beta"]))
+            sig_ptr, sig_head = d_eb.ptr, 2
+        if z0 < set_lo and (z0 in self.z_slot or z0 < s_lo):          # the set in front is another rank's (or another range's)
+            self._ext_into(self._z_coeff(z0), d_ez.ptr, 1)
+            self._ext_into(self._z_coeff(set_lo), d_ez.at(ne * B), set_hi - set_lo)
+        else:
+            self._ext_into(self._z_coeff(z0), d_ez.ptr, set_hi - z0)
+        if max(set_lo, 1) < set_hi:
+            f_2.skip_to(max(set_lo, 1) + 1, set_hi - max(set_lo, 1))
+            check(lib.vdb_permutation_eval_parts_cosets_dev(None, _sz(0), None, d_ez.ptr, _sz(z0), None, None, *perm_args, self.d_h2.ptr, 0, _sz(max(set_lo, 1)), _sz(set_hi),
+                                                            _sz(0), _sz(0)))
+        f_3.skip_to(set_lo, set_hi - set_lo)
+        check(lib.vdb_permutation_eval_parts_cosets_dev(base, _sz(col0), sig_ptr, d_ez.ptr, _sz(z0), None, None, *perm_args, self.d_h3.ptr, sig_head, _sz(0), _sz(0), _sz(set_lo),
+                                                        _sz(set_hi)))
+        # lookup argument of the block's lookup columns that are mine
+        j_lo, j_hi = max(c0 - self.n_adv, self.l_lo), min(c0 + nb - self.n_adv, self.l_hi)
+        self._lookup_terms(pf, f_4, base, col0, j_lo, j_hi)
+
+    def _lookup_terms(self, pf, fold, base, col0, j_lo, j_hi):
+        """the lookup argument of my lookup columns j_lo .. j_hi, whose input cosets are in the block at `base`:
+        [permuted input | permuted table | product] cosets in thirds of one buffer"""
+        rows, ne, d_eb, polys, third = self.rows, self.ne, self.d_eb, pf.polys, self._blk // 3
+        for j0 in range(j_lo, max(j_hi, j_lo), third):
+            m = min(third, j_hi - j0)
+            for i, name in enumerate(("pa", "ps", "zl")):
+                self._ext_into(polys[name].coeff.at((j0 - self.l_lo) * rows * B), d_eb.at(i * third * ne * B), m)
+            fold.skip_to(5 * j0, 5 * m)
+            check(self.lib.vdb_lookup_eval_cosets_dev(self._col_ptr(base, col0, self.n_adv + j0), self.fixed["table"].ext.ptr, d_eb.ptr, d_eb.at(third * ne * B),
+                                                      d_eb.at(2 * third * ne * B), _sz(m), self.k, self.n_slots, *self.l_cosets, pf.p["beta"], pf.p["gamma"], pf.p["y"], self.d_h4.ptr))
+
+    def _fold_h(self, pf):
+        """h folded at x (halo2 vanishing::Constructed::evaluate): hf(X) = sum_i x^(n i) h_i(X), one polynomial of degree below n whose
+        commitment the verifier forms from the pieces' and whose value at x it computes from the quotient identity — neither is sent"""
+        lib, rows = self.lib, self.rows
+        xn = pow(_fr_to_int(pf.ch["x"]), rows, R_MOD)
+        check(lib.vdb_memcpy_d2d(self.d_hf.ptr, self.d_h.ptr, _sz(rows * B)))
+        for i in range(1, self.n_h):
+            check(lib.vdb_poly_axpy_dev(self.d_hf.ptr, api._p(_fr_from_int(pow(xn, i, R_MOD))), self.d_h.at(i * rows * B), _sz(rows)))
+        with pf.stage("commit_h"):
+            hf_c = self._commit(self.d_hf, 1, 0)
+        pf.polys["hf"] = _Poly("hf", 1, coeff=self.d_hf, commits=hf_c, replicated=True)
+
+    # ------------------------------------------------------------------ round 5 (x): evaluations, at the rotations protocol.opened states
+    def _evaluations(self, pf, allp, opened, points):
+        """every opened polynomial at its points, absorbed into the transcript -> evals[(name, rotation)] (Montgomery arrays)"""
         groups = [(rot, name) for rot, names in opened.items() for name in names]
-
-        def evaluate():
+        evals = {}
+        if self.world == 1 and pf.tr is not None and pf.timings is None:
+            # the device evaluates group i + 1 while the host absorbs the evaluations of group i (the sponge's host work — ~6 us per four
+            # values — is longer than the evaluation itself: only the first group's kernel is not hidden)
+            sizes = [allp[name].n_cols for _rot, name in groups]
+            offs = [sum(sizes[:i]) * B for i in range(len(groups))]
+            d_ev = api.DeviceBuffer(max(sum(sizes), 1) * B)
+            launches = [(allp[name], points[rot], d_ev.at(o)) for (rot, name), o in zip(groups, offs)]
+            try:
+                if groups:
+                    self._eval_into(*launches[0])
+                for i, (rot, name) in enumerate(groups):
+                    out = d_ev.download((sizes[i], 4), offset=offs[i])       # waits for group i's kernel only
+                    if i + 1 < len(groups):
+                        self._eval_into(*launches[i + 1])
+                    evals[(name, rot)] = out
+                    if name not in DERIVED:                  # computed by the verifier, not sent
+                        with pf.host_transcript():
+                            pf.tr.write_scalars(out)
+                            pf.tr.flush()
+            finally:
+                api.sync()
+                d_ev.free()
+            return evals
+        with pf.stage("evaluations"):
             for rot, name in groups:
                 q = allp[name]
                 out = np.zeros((q.n_cols, 4), dtype=np.uint64)
-                check(lib.vdb_eval_polys_dev(q.coeff.ptr, _sz(q.n_cols), _sz(rows), api._p(_fr_from_int(points[rot])), api._p(out)))
+                check(self.lib.vdb_eval_polys_dev(q.coeff.ptr, _sz(q.n_cols), _sz(self.rows), api._p(_fr_from_int(points[rot])), api._p(out)))
                 evals[(name, rot)] = out
-            if world > 1:
+            if self.world > 1:
                 # every rank evaluated its own polynomials: one exchange puts every group's evaluations in the global order
                 # (the polynomials every rank holds are not exchanged)
                 shared = [(rot, name) for rot, name in groups if not allp[name].replicated]
-                whole = np.zeros((sum(allp[name].n_total for _rot, name in shared), 4), dtype=np.uint64)
-                o = 0
-                for rot, name in shared:
-                    q, loc = allp[name], 0
-                    for lo, hi in q.ranges:
-                        whole[o + lo: o + hi] = evals[(name, rot)][loc: loc + hi - lo]
-                        loc += hi - lo
-                    o += q.n_total
-                whole = comm.sum_disjoint(whole)
+                ranges, o = [], 0
+                for _rot, name in shared:
+                    ranges += [(o + lo, o + hi) for lo, hi in allp[name].ranges]
+                    o += allp[name].n_total
+                whole = self._globalize(np.concatenate([evals[(name, rot)] for rot, name in shared]), ranges, o)
                 o = 0
                 for rot, name in shared:
                     evals[(name, rot)] = np.ascontiguousarray(whole[o: o + allp[name].n_total])
                     o += allp[name].n_total
-
-        def evaluate_and_absorb():
-            # the device evaluates group i + 1 while the host absorbs the evaluations of group i (the sponge's host work — ~6 us per four
-            # values — is longer than the evaluation itself: only the first group's kernel is not hidden)
-            total = sum(allp[name].n_cols for _rot, name in groups)
-            d_ev = api.DeviceBuffer(max(total, 1) * B)
-            offs, o = [], 0
-            for _rot, name in groups:
-                offs.append(o)
-                o += allp[name].n_cols * B
-
-            def launch(i):
-                rot, name = groups[i]
-                q = allp[name]
-                check(lib.vdb_eval_polys_dev_out(q.coeff.ptr, _sz(q.n_cols), _sz(rows), api._p(_fr_from_int(points[rot])), d_ev.at(offs[i])))
-            try:
-                if groups:
-                    launch(0)
-                for i, (rot, name) in enumerate(groups):
-                    out = d_ev.download((allp[name].n_cols, 4), offset=offs[i])       # waits for group i's kernel only
-                    if i + 1 < len(groups):
-                        launch(i + 1)
-                    evals[(name, rot)] = out
-                    if name in DERIVED:                  # computed by the verifier, not sent
-                        continue
-                    t0 = time.perf_counter()
-                    tr.write_scalars(out)
-                    tr.flush()
-                    host["transcript"] += (time.perf_counter() - t0) * 1e3
-            finally:
-                api.sync()
-                d_ev.free()
-
-        if world == 1 and tr is not None and timings is None and os.environ.get("VDB_EVAL_PIPELINE", "1") != "0":
-            evaluate_and_absorb()
-        else:
-            stage("evaluations", evaluate)
-            if tr is not None:
-                t0 = time.perf_counter()
+        if pf.tr is not None:
+            with pf.host_transcript():
                 for rot, name in groups:
-                    if name not in DERIVED:
-                        tr.write_scalars(evals[(name, rot)])
-                host["transcript"] += (time.perf_counter() - t0) * 1e3
-        d_comb, d_quot = self.d_comb, self.d_quot
-        if multiopen == "shplonk":
-            openings = self._shplonk(allp, opened, points, evals, p, ch, squeeze, write_points, stage, power)
-            proof = None
-            if tr is not None:
-                proof = tr.proof()
-                tr.free()
-            api.sync()
-            return dict(commitments={name: q.commits for name, q in allp.items()}, evals=openings.pop("evals_int"), openings=openings, points=points,
-                        proof=proof, challenges={name: v.copy() for name, v in ch.items()}, opened=opened,
-                        instances=[_fr_to_int(v) for v in instances])
-        squeeze("v")
+                    if name not in DERIVED:                  # computed by the verifier, not sent
+                        pf.tr.write_scalars(evals[(name, rot)])
+        return evals
 
-        # round 6 (v): one opening per rotation point: combine with powers of v, divide by (X - point), commit
+    def _eval_into(self, q, point, dest):
+        check(self.lib.vdb_eval_polys_dev_out(q.coeff.ptr, _sz(q.n_cols), _sz(self.rows), api._p(_fr_from_int(point)), dest))
+
+    # ------------------------------------------------------------------ round 6: the multi-open
+    def _open_gwc(self, pf, allp, opened, points):
+        """v -> one opening per rotation point: combine with powers of v, divide by (X - point), commit"""
+        lib, rows, d_comb, d_quot = self.lib, self.rows, self.d_comb, self.d_quot
+        pf.squeeze("v")
         openings = []
-
-        def open_all():
+        with pf.stage("openings"):
             for rot, names in opened.items():
                 check(lib.vdb_memset_dev(d_comb.ptr, 0, _sz(rows * B)))
                 for name in names:
                     q = allp[name]
-                    check(lib.vdb_poly_lincomb_dev(q.coeff.ptr, _sz(q.n_cols), _sz(rows), p["v"], d_comb.ptr))
-                ptm = _fr_from_int(points[rot])
+                    check(lib.vdb_poly_lincomb_dev(q.coeff.ptr, _sz(q.n_cols), _sz(rows), pf.p["v"], d_comb.ptr))
                 rem = np.zeros((1, 4), dtype=np.uint64)
-                check(lib.vdb_kate_div_dev(d_comb.ptr, _sz(1), _sz(rows), api._p(ptm), d_quot.ptr, api._p(rem)))
+                check(lib.vdb_kate_div_dev(d_comb.ptr, _sz(1), _sz(rows), api._p(_fr_from_int(points[rot])), d_quot.ptr, api._p(rem)))
                 W = self._commit(d_quot, 1, 0)[0]
                 openings.append(dict(rotation=rot, point=points[rot], polys=list(names), eval=rem[0].copy(), W=W))
-        stage("openings", open_all)
-        write_points([op["W"] for op in openings])
-        proof = None
-        if tr is not None:
-            proof = tr.proof()
-            tr.free()
-        api.sync()
-        commitments = {name: q.commits for name, q in allp.items()}
-        return dict(commitments=commitments, evals=_Evals(evals), openings=openings, points=points,
-                    proof=proof, challenges={name: v.copy() for name, v in ch.items()}, opened=opened,
-                        instances=[_fr_to_int(v) for v in instances])
+        pf.write_points([op["W"] for op in openings])
+        return openings
 
-    # ------------------------------------------------------------------ SHPLONK multi-open (halo2 poly/kzg/multiopen/shplonk)
-    def _shplonk(self, allp, opened, points, evals, p, ch, squeeze, write_points, stage, power):
+    # SHPLONK multi-open (halo2 poly/kzg/multiopen/shplonk)
+    def _shplonk(self, pf, allp, opened, points, evals):
         """Polynomials opened at the same set of points form a rotation set S.  With q_S = the set's polynomials combined with
         powers of yo, r_S the interpolant of q_S's values on S and Z_S the vanishing polynomial of S:
             f = sum_S v^(m-1-s) (q_S - r_S) / Z_S                          -> commitment W1, then u,
@@ -1394,49 +1400,19 @@ class ProverRounds:
         place in the whole set); the quotient of a division by Z_S — the remainder dropped — and L's division by X - u are
         linear, so every rank commits its share of f and of L / (X - u) and the shares are added as points (vdb_g1_sum: RCCL has no
         curve operator, two 64-byte points per rank are gathered)."""
-        lib, rows = self.lib, self.rows
-        comm, world, rank = self.comm, self.world, self.rank
-        R = R_MOD
+        lib, rows, p, R = self.lib, self.rows, pf.p, R_MOD
         sets = protocol.rotation_sets(opened)
-        squeeze("yo", "v")
-        yo, v = _fr_to_int(ch["yo"]), _fr_to_int(ch["v"])
+        pf.squeeze("yo", "v")
+        v = _fr_to_int(pf.ch["v"])
         m = len(sets)
         d_q = [api.DeviceBuffer(rows * B) for _ in sets]
         d_f, d_a, d_b = api.DeviceBuffer(rows * B), self.d_comb, self.d_quot
-        ev_int = _Evals(evals)
-
-        def combine(names, dest):
-            """dest <- this rank's share of the set's polynomials combined with powers of yo: polynomial j of the M the set has in
-            all enters with yo^(M - 1 - j).  Horner over the ones held here; a stretch another rank holds multiplies by yo^(its length)."""
-            check(lib.vdb_memset_dev(dest.ptr, 0, _sz(rows * B)))
-            pos, base, live = 0, 0, False
-            for name in names:
-                q = allp[name]
-                loc = 0
-                for lo, hi in (q.ranges if (not q.replicated or rank == 0) else []):
-                    if live and base + lo > pos:
-                        check(lib.vdb_poly_scale_dev(dest.ptr, api._p(power("yo", base + lo - pos)), _sz(rows)))
-                    check(lib.vdb_poly_lincomb_dev(q.coeff.at(loc * rows * B), _sz(hi - lo), _sz(rows), p["yo"], dest.ptr))
-                    pos, live, loc = base + hi, True, loc + hi - lo
-                base += q.n_total
-            if live and base > pos:
-                check(lib.vdb_poly_scale_dev(dest.ptr, api._p(power("yo", base - pos)), _sz(rows)))
-
-        def share(point):
-            """the sum over the ranks of their partial commitments"""
-            if world == 1:
-                return point
-            out = np.zeros((1, 8), dtype=np.uint64)
-            parts = np.ascontiguousarray(comm.gather_rows(np.asarray(point, dtype=np.uint64).reshape(1, 8)))
-            check(lib.vdb_g1_sum(api._p(parts), _sz(world), _sz(1), api._p(out)))
-            return out[0]
-
         r_polys, rems = [], []
-
-        def quotient_f():
+        # f, the quotient of all rotation sets
+        with pf.stage("openings"):
             check(lib.vdb_memset_dev(d_f.ptr, 0, _sz(rows * B)))
             for s_i, (rots, names) in enumerate(sets):
-                combine(names, d_q[s_i])
+                self._combine(pf, allp, names, d_q[s_i])
                 vals = []
                 for rot in rots:                                   # the set's evaluations at this point, combined with powers of yo (host, compiled)
                     acc = np.zeros(4, dtype=np.uint64)
@@ -1449,7 +1425,7 @@ class ProverRounds:
                 # (q_S - r_S) / Z_S: the low coefficients on the host, one division per point on the device.  (r_S has fewer
                 # coefficients than Z_S has roots: it changes the remainders only, which is why a rank's share needs no r_S.)
                 check(lib.vdb_memcpy_d2d(d_a.ptr, d_q[s_i].ptr, _sz(rows * B)))
-                if world == 1:
+                if self.world == 1:
                     low = np.zeros((len(r), 4), dtype=np.uint64)
                     check(lib.vdb_memcpy_d2h(api._p(low), d_a.ptr, _sz(low.nbytes)))
                     low = np.stack([_fr_from_int(_fr_to_int(low[i]) - r[i]) for i in range(len(r))])
@@ -1461,14 +1437,13 @@ class ProverRounds:
                     rems.append(_fr_to_int(rem[0]))
                     src, dst = dst, src
                 check(lib.vdb_poly_lincomb_dev(src.ptr, _sz(1), _sz(rows), p["v"], d_f.ptr))          # f = f v + (q_S - r_S) / Z_S
-            return share(self._commit(d_f, 1, 0)[0])
-        W1 = stage("openings", quotient_f)
-        write_points([W1])
-        squeeze("u")
-        u = _fr_to_int(ch["u"])
+            W1 = self._share(self._commit(d_f, 1, 0)[0])
+        pf.write_points([W1])
+        pf.squeeze("u")
+        u = _fr_to_int(pf.ch["u"])
         all_rots = sorted({rot for rots, _ in sets for rot in rots})
-
-        def linearisation():
+        # the linearisation polynomial L and its quotient by X - u
+        with pf.stage("openings"):
             check(lib.vdb_memset_dev(d_a.ptr, 0, _sz(rows * B)))
             const = 0
             for s_i, (rots, names) in enumerate(sets):
@@ -1476,7 +1451,7 @@ class ProverRounds:
                 check(lib.vdb_poly_axpy_dev(d_a.ptr, api._p(_fr_from_int(coef)), d_q[s_i].ptr, _sz(rows)))
                 const = (const + coef * protocol.horner(r_polys[s_i], u)) % R
             check(lib.vdb_poly_axpy_dev(d_a.ptr, api._p(_fr_from_int(-protocol.vanishing([points[rot] for rot in all_rots], u))), d_f.ptr, _sz(rows)))
-            if rank == 0:                                     # the constant term belongs to one share
+            if self.rank == 0:                                     # the constant term belongs to one share
                 c0 = np.zeros((1, 4), dtype=np.uint64)
                 check(lib.vdb_memcpy_d2h(api._p(c0), d_a.ptr, _sz(32)))
                 c0[0] = _fr_from_int(_fr_to_int(c0[0]) - const)
@@ -1484,12 +1459,36 @@ class ProverRounds:
             rem = np.zeros((1, 4), dtype=np.uint64)
             check(lib.vdb_kate_div_dev(d_a.ptr, _sz(1), _sz(rows), p["u"], d_b.ptr, api._p(rem)))
             rems.append(_fr_to_int(rem[0]))
-            return share(self._commit(d_b, 1, 0)[0])
-        W2 = stage("openings", linearisation)
-        write_points([W2])
+            W2 = self._share(self._commit(d_b, 1, 0)[0])
+        pf.write_points([W2])
         for b in d_q + [d_f]:
             b.free()
-        return dict(kind="shplonk", sets=[(list(rots), list(names)) for rots, names in sets], W1=W1, W2=W2, remainders=rems, evals_int=ev_int)
+        return dict(kind="shplonk", sets=[(list(rots), list(names)) for rots, names in sets], W1=W1, W2=W2, remainders=rems)
+
+    def _combine(self, pf, allp, names, dest):
+        """dest <- this rank's share of the set's polynomials combined with powers of yo: polynomial j of the M the set has in
+        all enters with yo^(M - 1 - j).  A fold over the ones held here (the replicated ones by rank 0)."""
+        rows = self.rows
+        check(self.lib.vdb_memset_dev(dest.ptr, 0, _sz(rows * B)))
+        fold = _Fold(self.lib, pf, "yo", dest, rows, sum(allp[name].n_total for name in names))
+        base = 0
+        for name in names:
+            q, loc = allp[name], 0
+            for lo, hi in (q.ranges if (not q.replicated or self.rank == 0) else []):
+                fold.skip_to(base + lo, hi - lo)
+                check(self.lib.vdb_poly_lincomb_dev(q.coeff.at(loc * rows * B), _sz(hi - lo), _sz(rows), pf.p["yo"], dest.ptr))
+                loc += hi - lo
+            base += q.n_total
+        fold.finish()
+
+    def _share(self, point):
+        """the sum over the ranks of their partial commitments"""
+        if self.world == 1:
+            return point
+        out = np.zeros((1, 8), dtype=np.uint64)
+        parts = np.ascontiguousarray(self.comm.gather_rows(np.asarray(point, dtype=np.uint64).reshape(1, 8)))
+        check(self.lib.vdb_g1_sum(api._p(parts), _sz(self.world), _sz(1), api._p(out)))
+        return out[0]
 
     def free(self):
         for q in self.fixed.values():
