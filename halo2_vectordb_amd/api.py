@@ -2,6 +2,7 @@
 marshals numpy buffers into one `vdb_*` call.  Field elements are uint64 arrays (..., 4):
 little-endian limbs, Montgomery form (halo2curves layout).  G1 points are (..., 8): x then y.
 """
+import contextlib
 import ctypes
 
 import numpy as np
@@ -323,6 +324,19 @@ def wit_fp_op(op, a, b=None, P=48, L=13, selectors=False):
     check(lib.vdb_wit_fp_op(FP_OPS[op], ctypes.c_uint32(P), ctypes.c_uint32(L), _p(a), _p(b) if b is not None else None, _sz(n), _p(stream), _p(lookup),
                             _p(sel) if selectors else None, _p(res)))
     return dict(stream=stream, lookup=lookup, **_split_flags(sel), result=res)
+
+
+@contextlib.contextmanager
+def wit_window(adv, lookup):
+    """Within the block the witness entry points store only the stream cells in [adv[0], adv[1]) and the lookup cells in
+    [lookup[0], lookup[1]) — a rank's window, positions counted from the stream pointers handed to each call; every value is still
+    computed (vdb_wit_set_window).  The full window is restored on the way out."""
+    lib = _lib.init()
+    check(lib.vdb_wit_set_window(ctypes.c_uint64(adv[0]), ctypes.c_uint64(adv[1]), ctypes.c_uint64(lookup[0]), ctypes.c_uint64(lookup[1])))
+    try:
+        yield
+    finally:
+        check(lib.vdb_wit_set_window(ctypes.c_uint64(0), ctypes.c_uint64(2**64 - 1), ctypes.c_uint64(0), ctypes.c_uint64(2**64 - 1)))
 
 
 def wit_nearest(metric, query, vectors, P=48, L=13, selectors=False):

@@ -22,6 +22,9 @@ import numpy as np
 
 R = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 SELF, CONST, EXT0 = -1, -2, -10
+# the FixedPointInstructions calls of one operand (Sym.fp_op; what pipeline.FixedPointHotPath proves)
+FP_UNARY_OPS = ("qexp2", "qlog2", "qsin", "qexp", "qlog", "qsqrt", "qabs", "is_neg", "neg", "signed_div_scale", "sign", "clip", "qcos", "qtan",
+                "qsinh", "qcosh", "qtanh")
 
 EXP2_COEF = [3.6240421303547230336183979205877e-11, 4.1284327467833130245549169910389e-10, 0.0000000071086385644026346316624185550542,
              0.00000010172297085296590958930245291448, 0.0000013215904023658396206789543841996, 0.000015252713316417140696221389106544,
@@ -420,9 +423,8 @@ class Sym:
 
     def fp_op(self, name, a):
         """one unary FixedPointInstructions call (the numbering of vdb_wit_fp_op names the same set)"""
-        return dict(qexp2=self.qexp2, qlog2=self.qlog2, qsin=self.qsin, qexp=self.qexp, qlog=self.qlog, qsqrt=self.qsqrt, qabs=self.qabs,
-                    is_neg=self.is_neg, neg=self.g_neg, signed_div_scale=self.signed_div_scale, sign=self.sign, clip=self.clip, qcos=self.qcos,
-                    qtan=self.qtan, qsinh=lambda x: self._sinh_cosh(x, False), qcosh=lambda x: self._sinh_cosh(x, True), qtanh=self.qtanh)[name](a)
+        named = dict(neg=self.g_neg, qsinh=lambda x: self._sinh_cosh(x, False), qcosh=lambda x: self._sinh_cosh(x, True))
+        return {op: named.get(op) or getattr(self, op) for op in FP_UNARY_OPS}[name](a)
 
     def inner_product(self, a, b):                           # :854-874
         res = self.g_add(C(0), C(0))

@@ -10,16 +10,19 @@ Mirrors what the reference's `Prove` arm does up to the committed / extended adv
 selectors recorded, from which the break points ("pinning") are derived.  Everything stays in HBM;
 only commitments (64 B per column) come back to the host.
 """
+import contextlib
 import ctypes
+import functools
 import math
 
 import numpy as np
 
 from . import api
 from ._lib import check
-from .protocol import N_BLIND, constraint_degree
+from .circuit_sym import FP_UNARY_OPS
+from .protocol import MINIMUM_ROWS, N_BLIND, constraint_degree, fr_from_int
 
-MINIMUM_ROWS = 9   # MINIMUM_ROWS default, src/scaffold/mod.rs:383
+B = 32      # bytes per field element
 
 
 def sift_like_vectors(seed, n, dim, k_distinct=0):
@@ -178,18 +181,33 @@ def allgather_partials(dist, local, device):
     return np.stack([g.cpu().numpy().view(np.uint64) for g in gathered])
 
 
-class KmeansHotPath:
-    """kmeans::<K, I> over N x D vectors at 2^k rows: witness -> layout -> commit -> NTT, one GPU."""
+def _end_to_end(codes, size):
+    """Independent gadget calls laid end to end in the stream: `size(code, byref cells, byref lookup cells)` is the calls' size entry
+    point.  -> ([(code, first cell, first lookup cell)] per call, cells of all, lookup cells of all)."""
+    parts = []
+    cells_total = lk_total = 0
+    for code in codes:
+        cells, lk = ctypes.c_uint64(), ctypes.c_uint64()
+        check(size(code, ctypes.byref(cells), ctypes.byref(lk)))
+        parts.append((code, cells_total, lk_total))
+        cells_total, lk_total = cells_total + cells.value, lk_total + lk.value
+    return parts, cells_total, lk_total
 
-    def __init__(self, n=256, dim=128, K=4, I=8, k=16, P=48, L=15, metric="euclidean", seed=20260004, tau=None,
-                 col_shard=(0, 1), vectors=None, blind_seed=None, params=None):
+
+class HotPath:
+    """The HBM-resident driver of one circuit on one GPU (or one rank's block of its columns): witness -> layout -> commit -> NTT.
+    Circuit neutral: a circuit class states its inputs and sizes (_input_vectors, n_input_rows, _circuit_size), its outputs
+    (_alloc_outputs, registered with _output), the gadget calls that emit its cells after the input rows (_emit), what it makes
+    public (public_values_dev), what it returns (results) and its constraint map (constraint_map)."""
+
+    def __init__(self, n, dim, k, P, L, seed=None, tau=None, col_shard=(0, 1), vectors=None, blind_seed=None, params=None):
         """`tau`: toxic-waste scalar of the "unsafe" SRS as a canonical integer; None = the scalar the reference's
         `gen_srs(k)` derives from its fixed ChaCha20 seed (srs.gen_srs_tau, src/scaffold/mod.rs:260).
         `params`: an SRS whose scalar nobody knows instead — an srs.ParamsKZG (downsized to k on the device when its k is larger)
         or the path of a halo2 params file (read at k), what gen_srs(k) loads from params/kzg_bn254_{k}.srs when that exists.
         Not together with `tau`; `self.tau` stays None and `self.tau_g2` / `self.g2` carry the SRS's G2 side.
         `vectors`: the f64 rows the circuit assigns first (the `--input` file of the reference's examples,
-        src/scaffold/mod.rs:64-77); None = the seeded SIFT-shaped synthetic rows of SURVEY 8(d).
+        src/scaffold/mod.rs:64-77); None = the circuit's seeded synthetic rows (SIFT-shaped).
         `blind_seed`: None = the blinding rows of every column are drawn afresh from the operating system's entropy for every
         proof (step), as halo2's create_proof does with its OsRng (reached from src/scaffold/mod.rs:296); an integer fixes
         them — a test hook for comparing commitments across runs, never for real proofs (two proofs that share blinds leak
@@ -197,9 +215,7 @@ class KmeansHotPath:
         self.blind_seed = blind_seed
         self._entropy = None
         self.given_vectors = None if vectors is None else np.ascontiguousarray(vectors, dtype=np.float64)
-        self.n, self.dim, self.K, self.I, self.k, self.P, self.L = n, dim, K, I, k, P, L
-        self.metric = api.METRICS[metric]
-        self.metric_name = metric
+        self.n, self.dim, self.k, self.P, self.L = n, dim, k, P, L
         self.rows = 1 << k
         self.lib = api.init()
         self.rank, self.world = col_shard
@@ -209,6 +225,7 @@ class KmeansHotPath:
         self.tau = tau
         self.params = params
         self.tau_g2 = self.g2 = None
+        self._outputs = []
         self.factor_constants = True
         self.shard_witness = True   # generate only the witness cells this rank's columns hold (values are computed everywhere)
         self.balance_shards = True  # equalise estimated time per rank instead of column count
@@ -222,24 +239,36 @@ class KmeansHotPath:
         """`pinning`: path of a configs/{name}.json written by an earlier keygen (io.write_pinning); when given, its break
         points are used as they are — the Prove arm of the reference (src/scaffold/mod.rs:285-287) — after checking that
         they describe this circuit; otherwise they are derived from the keygen-style run, like the Keygen arm."""
-        lib, n, dim, K, I = self.lib, self.n, self.dim, self.K, self.I
         # the MSMs of setup and keygen (constant points, fixed columns) work in a bounded work space: on a still empty card the default
         # (half of the free HBM) would map up to 96 GiB for a two-second MSM, and mapping fresh HBM costs ~30 ms / GiB; step() lifts it
         api.msm_scratch_cap(api.KEYGEN_SCRATCH_CAP)
-        self._cap_lifted = False
+        self._load_inputs()
+        d_sel = self._plan_layout(pinning)
+        self._load_srs()
+        self._partition_columns(d_sel)
+        self._column_sources()
+        self._factor_constants(d_sel)
+        self._size_cosets()
+        return self
+
+    def _load_inputs(self):
+        """The input rows on the device, the witness streams and the circuit's outputs."""
         vec, self.seed = self._input_vectors() if self.given_vectors is None else (self.given_vectors, self.seed)
         assert vec.shape == (self.n_input_rows(), self.dim), "input rows do not match the circuit's shape"
         self.vectors_f64 = vec
         self.qvec = api.quantize(vec, self.P)
         self.n_in, n_gadget_cells, self.n_lookup = self._circuit_size()
         self.n_cells = self.n_in + n_gadget_cells
-        B = 32
         self.d_vec = api.DeviceBuffer(self.qvec.nbytes)
         self.d_vec.upload(self.qvec)
         self.d_stream = api.DeviceBuffer(self.n_cells * B)
         self.d_lookup = api.DeviceBuffer(max(self.n_lookup, 1) * B)
         self._alloc_outputs()
-        # keygen-style run: record gate starts, derive break points (the reference pins them in configs/*.json)
+
+    def _plan_layout(self, pinning):
+        """Keygen-style run: record gate starts, derive the break points (the reference pins them in configs/*.json) and the column
+        counts.  -> the gate-start flags (device), which the later steps read and _factor_constants frees."""
+        lib = self.lib
         d_sel = api.DeviceBuffer(self.n_cells)
         check(lib.vdb_memset_dev(d_sel.ptr, 0, ctypes.c_size_t(self.n_cells)))
         self._witness(sel=d_sel)
@@ -256,11 +285,11 @@ class KmeansHotPath:
                 raise ValueError("pinning file does not describe this circuit (degree, lookup_bits or break points differ)")
             self.bp = bp
         self.n_adv_cols = len(self.bp) + 1
-        max_rows = self.rows - MINIMUM_ROWS
-        self.n_lk_cols = math.ceil(self.n_lookup / max_rows)
+        self.n_lk_cols = math.ceil(self.n_lookup / (self.rows - MINIMUM_ROWS))
         self.n_cols = self.n_adv_cols + self.n_lk_cols
-        from_ints = lambda vals: np.array([[(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)] for v in vals], dtype=np.uint64)
-        R = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
+        return d_sel
+
+    def _load_srs(self):
         if self.params is not None:
             from .srs import ParamsKZG
             params = self.params if isinstance(self.params, ParamsKZG) else ParamsKZG.read(self.params, self.k)
@@ -271,12 +300,15 @@ class KmeansHotPath:
             if self.tau is None:
                 from .srs import gen_srs_tau
                 self.tau = gen_srs_tau()
-            tau = from_ints([self.tau * (1 << 256) % R])[0]
-            g, gl = api.srs_setup_unsafe(self.k, tau)
+            g, gl = api.srs_setup_unsafe(self.k, fr_from_int(self.tau))
         self.g_lagrange = gl
         self.g_monomial = g
         self.srs = api.Srs(self.k, None, gl, window_bits=self.msm_window_bits)
-        # column sharding over ranks: a block of the advice columns and a block of the lookup columns each
+
+    def _partition_columns(self, d_sel):
+        """Column sharding over ranks: a block of the advice columns and a block of the lookup columns each, and the stretches of the
+        witness streams they hold (the rank window of _window)."""
+        lib = self.lib
         self.shards = column_shards(self.n_adv_cols, self.n_lk_cols, self.world)
         if self.world > 1 and self.balance_shards:
             # keygen-time statistics of the layout just produced (every rank computes the same numbers)
@@ -311,7 +343,12 @@ class KmeansHotPath:
             self.win_adv = (int(starts[self.a_lo]), s_hi)
         else:
             self.win_adv = (0, 0)
+        max_rows = self.rows - MINIMUM_ROWS
         self.win_lk = (self.l_lo * max_rows, min(self.l_hi * max_rows, self.n_lookup)) if self.my_lk else (0, 0)
+
+    def _column_sources(self):
+        """The blinding scalars, the column buffer and the descriptors of where each of my columns lies in the streams."""
+        lib = self.lib
         # N_BLIND blinding scalars per column, uniform in Fr: 64 bytes of entropy each, reduced on the device
         self.d_blind = api.DeviceBuffer(self.n_cols * N_BLIND * B)
         self.d_wide = api.DeviceBuffer(self.n_cols * N_BLIND * 64)
@@ -326,8 +363,11 @@ class KmeansHotPath:
             check(lib.vdb_colsrc_build_lookup_dev(self.d_lookup.ptr, ctypes.c_uint64(self.n_lookup), self.k, MINIMUM_ROWS, ctypes.c_uint64(self.l_lo),
                                                   ctypes.c_uint64(self.l_hi), self.d_blind.at(self.n_adv_cols * N_BLIND * B), N_BLIND,
                                                   self.d_src.at(self.my_adv * 24)))
-        # keygen-time factoring of the constant cells: column-layout mask of the QuantumCell::Constant cells and the
-        # per-column MSM of exactly those cells (data independent, so computed once like the rest of the proving key)
+
+    def _factor_constants(self, d_sel):
+        """Keygen-time factoring of the constant cells: column-layout mask of the QuantumCell::Constant cells and the per-column MSM of
+        exactly those cells (data independent, so computed once like the rest of the proving key).  Frees `d_sel`."""
+        lib = self.lib
         # (lookup columns hold no constants: their mask stays zero and their constant point is the identity).
         # Only this rank's advice columns, laid out in the column buffer the step overwrites anyway: no second buffer of the
         # columns' size (33.7 GiB at C4') is allocated and handed back.
@@ -353,12 +393,14 @@ class KmeansHotPath:
         self.const_cell_fraction = float(d_fmask.download((n_el,), dtype=np.uint8).mean()) if n_el <= (1 << 28) else None
         d_fmask.free()
         api.sync()
-        # The extended cosets, last: all of them when they fit beside everything above and leave the MSM its work space (C4:
-        # 68 GB), otherwise the largest block of columns that does — the cosets are then produced block after block into the
-        # same buffer (a circuit larger than HBM streams through: C4' cosine, 20.3 k columns = 170 GB of cosets; C5's Merkle).
-        # Two columns more than this rank holds: the prover rounds keep the cosets of the constants' fixed column and of the
-        # instance column behind the advice cosets, so that the permutation argument reads its columns from one contiguous
-        # block (rounds.py).
+
+    def _size_cosets(self):
+        """The extended cosets, last: all of them when they fit beside everything above and leave the MSM its work space (C4:
+        68 GB), otherwise the largest block of columns that does — the cosets are then produced block after block into the
+        same buffer (a circuit larger than HBM streams through: C4' cosine, 20.3 k columns = 170 GB of cosets; C5's Merkle).
+        Two columns more than this rank holds: the prover rounds keep the cosets of the constants' fixed column and of the
+        instance column behind the advice cosets, so that the permutation argument reads its columns from one contiguous
+        block (rounds.py)."""
         per_col = self.rows * 4 * B
         want = max(self.my_cols, 1) + 2
         if self.ext_block_cols is None:
@@ -369,7 +411,6 @@ class KmeansHotPath:
         else:
             self.ext_cols = min(want, int(self.ext_block_cols))
         self.d_ext = api.DeviceBuffer(self.ext_cols * per_col)
-        return self
 
     # ------------------------------------------------------------------ blinding
     def _draw_entropy(self, seed):
@@ -386,24 +427,71 @@ class KmeansHotPath:
         self.d_wide.upload(np.frombuffer(raw, dtype=np.uint8))
         check(self.lib.vdb_fr_from_wide_dev(self.d_wide.ptr, ctypes.c_size_t(self.n_cols * N_BLIND), self.d_blind.ptr))
 
-    # ------------------------------------------------------------------ what is specific to the k-means circuit
+    # ------------------------------------------------------------------ what a circuit states
     def _input_vectors(self):
         """(f64 rows that ctx.assign_witnesses puts at the head of the stream, seed actually used)"""
-        return sift_like_vectors(self.seed, self.n, self.dim, self.K)
+        raise NotImplementedError
 
     def n_input_rows(self):
         return self.n
 
     def _circuit_size(self):
-        """(cells of ctx.assign_witnesses(quantize_vector(v)) for every vector, cells the gadget emits, lookup cells)"""
-        cells, lk = ctypes.c_uint64(), ctypes.c_uint64()
-        check(self.lib.vdb_wit_kmeans_size(self.metric, self.P, self.L, self.n, self.dim, self.K, self.I, 0, ctypes.byref(cells), ctypes.byref(lk)))
-        return self.n * self.dim, cells.value, lk.value
+        """(cells of ctx.assign_witnesses(quantize_vector(v)) for every input row, cells the gadgets emit, lookup cells)"""
+        raise NotImplementedError
 
     def _alloc_outputs(self):
-        self.d_cent = api.DeviceBuffer(self.K * self.dim * 32)
-        self.d_ind = api.DeviceBuffer(self.n * self.K * 32)
+        """the circuit's output buffers, each made with _output"""
+        raise NotImplementedError
 
+    def _emit(self, sel):
+        """the circuit's gadget calls, their cells from n_in on (sel: gate-start flag bytes of the stream, or None)"""
+        raise NotImplementedError
+
+    def public_values_dev(self):
+        """(device pointer, count) of the values the reference's example of this circuit makes public, in make_public order.  Every
+        rank computes them (value-only walk), whichever rank's columns hold the cells."""
+        raise NotImplementedError
+
+    def results(self):
+        raise NotImplementedError
+
+    def constraint_map(self, d_flags, on_device=True):
+        """(the circuit's constraint map (circuit_sym.CopyMap over the stream cells), the cells its example makes public in make_public
+        order, the stream cell of its Merkle root or None).  d_flags: the flags of a keygen-style run (keygen_flags); on_device: let the
+        device place the map of a large circuit (circuit_dev.py) instead of the host."""
+        raise NotImplementedError
+
+    # ------------------------------------------------------------------ helpers of the circuits
+    def _output(self, nbytes):
+        """a device buffer for the circuit's outputs, freed by free()"""
+        buf = api.DeviceBuffer(nbytes)
+        self._outputs.append(buf)
+        return buf
+
+    @staticmethod
+    def _sel_at(sel, at):
+        """the flag bytes of a gadget call whose cells start `at` cells into the stream"""
+        return ctypes.c_void_p(sel.ptr.value + at) if sel is not None else None
+
+    def _window(self, sel, at, lookup=True):
+        """The rank window of a gadget call whose cells start `at` cells into the stream: a rank that shards the witness stores only
+        the cells its columns hold (the values are computed everywhere).  `lookup`: the call emits lookup cells (else the lookup
+        window is empty)."""
+        if not (sel is None and self.shard_witness and self.world > 1):
+            return contextlib.nullcontext()
+        return api.wit_window(adv=tuple(max(0, x - at) for x in self.win_adv), lookup=self.win_lk if lookup else (0, 0))
+
+    def _fetch(self, lo, hi):
+        """canonical integers of stream cells [lo, hi)"""
+        c = api.fr_to_canonical(self.d_stream.download((hi - lo, 4), offset=lo * B))
+        return [int(r[0]) | int(r[1]) << 64 | int(r[2]) << 128 | int(r[3]) << 192 for r in c]
+
+    @staticmethod
+    def _fetch_flags(d_flags, lo, hi):
+        """flag bytes of stream cells [lo, hi)"""
+        return d_flags.download((hi - lo,), dtype=np.uint8, offset=lo)
+
+    # ------------------------------------------------------------------ the pinning file, the input, the layout, the witness
     def write_pinning(self, path):
         """configs/{name}.json of the Keygen arm (src/scaffold/mod.rs:272)."""
         from .io import write_pinning
@@ -417,7 +505,7 @@ class KmeansHotPath:
 
     def _layout(self, dest=None):
         """My block of advice columns followed by my block of lookup columns, compact in d_cols (or `dest`)."""
-        lib, B = self.lib, 32
+        lib = self.lib
         d_cols = self.d_cols if dest is None else dest
         if self.my_adv:
             check(lib.vdb_layout_columns_range_dev(self.d_stream.ptr, ctypes.c_uint64(self.n_cells), api._p(self.bp), ctypes.c_uint64(len(self.bp)), self.k,
@@ -428,22 +516,10 @@ class KmeansHotPath:
                                                   self.d_blind.at(self.n_adv_cols * N_BLIND * B), N_BLIND))
 
     def _witness(self, sel=None):
-        lib = self.lib
-        # [assign_witnesses(vectors)] [kmeans cells]
+        """[assign_witnesses(input rows)] [the gadgets' cells]"""
         if self.n_in:
-            check(lib.vdb_memcpy_d2d(self.d_stream.ptr, self.d_vec.ptr, ctypes.c_size_t(self.n_in * 32)))
-        windowed = sel is None and self.shard_witness and self.world > 1
-        if windowed:
-            # window in the coordinates of the pointers handed to the call (the kmeans cells start n_in cells into the stream)
-            lo, hi = (max(0, x - self.n_in) for x in self.win_adv)
-            check(lib.vdb_wit_set_window(ctypes.c_uint64(lo), ctypes.c_uint64(hi), ctypes.c_uint64(self.win_lk[0]), ctypes.c_uint64(self.win_lk[1])))
-        try:
-            check(lib.vdb_wit_kmeans_dev(self.metric, self.P, self.L, self.d_vec.ptr, self.n, self.dim, self.K, self.I, 0, self.d_stream.at(self.n_in * 32),
-                                         self.d_lookup.ptr, ctypes.c_void_p(sel.ptr.value + self.n_in) if sel is not None else None, self.d_cent.ptr,
-                                         self.d_ind.ptr))
-        finally:
-            if windowed:
-                check(lib.vdb_wit_set_window(ctypes.c_uint64(0), ctypes.c_uint64(2**64 - 1), ctypes.c_uint64(0), ctypes.c_uint64(2**64 - 1)))
+            check(self.lib.vdb_memcpy_d2d(self.d_stream.ptr, self.d_vec.ptr, ctypes.c_size_t(self.n_in * B)))
+        self._emit(sel)
 
     # ------------------------------------------------------------------ one pass of the hot path
     def step(self, timings=None, blind_seed=None, with_ext=True, sync=True, after_witness=None):
@@ -452,10 +528,9 @@ class KmeansHotPath:
         still running on the library's stream (the caller absorbs the commitments into its transcript meanwhile; everything it
         queues next is ordered behind them).  `after_witness`: called once the witness kernels are queued and before the
         commitments are (the prover rounds read the public cells out of the stream there)."""
-        lib, B = self.lib, 32
-        if not getattr(self, "_cap_lifted", True):      # the prover's MSM takes the work space its default policy gives it
-            api.msm_scratch_cap(0)
-            self._cap_lifted = True
+        lib = self.lib
+        # the prover's MSM takes the work space its default policy gives it, whatever setup / keygen of any hot path bounded it to
+        api.msm_scratch_cap(0)
         self.refresh_blinds(blind_seed)
 
         def stage(name, fn):
@@ -560,7 +635,7 @@ class KmeansHotPath:
         """Lagrange-basis columns as laid out (call right after `layout`, i.e. use relayout()); global column numbers."""
         out = np.zeros((len(col_indices), self.rows, 4), dtype=np.uint64)
         for j, c in enumerate(col_indices):
-            out[j] = self.d_cols.download((self.rows, 4), offset=self.local_index(c) * self.rows * 32)
+            out[j] = self.d_cols.download((self.rows, 4), offset=self.local_index(c) * self.rows * B)
         return out
 
     def relayout(self):
@@ -569,59 +644,99 @@ class KmeansHotPath:
         self._layout()
         api.sync()
 
+    def free(self):
+        for name in ("d_vec", "d_stream", "d_lookup", "d_blind", "d_wide", "d_cols", "d_ext", "d_mask", "d_cpts", "d_src"):
+            b = getattr(self, name, None)
+            if b is not None:
+                b.free()
+        for b in self._outputs:
+            b.free()
+        self._outputs = []
+        if getattr(self, "srs", None) is not None:
+            self.srs.free()
+
+
+def _merkle_cells(hp):
+    """cells of merkle_commitment over the hot path's n vectors"""
+    cells = ctypes.c_uint64()
+    check(hp.lib.vdb_wit_merkle_size(hp.n, hp.dim, 0, ctypes.byref(cells)))
+    return cells.value
+
+
+def _merkle_trace(hp, d_vectors, at, sel):
+    """merkle_commitment over the n vectors at `d_vectors`, its cells `at` cells into the stream, the root into hp.d_root.  Windowed:
+    only the permutations whose cells fall into this rank's columns are traced; the digests are computed everywhere."""
+    with hp._window(sel, at, lookup=False):
+        check(hp.lib.vdb_wit_merkle_dev(d_vectors, hp.n, hp.dim, 0, hp.d_stream.at(at * B), hp._sel_at(sel, at), hp.d_root.ptr))
+
+
+class KmeansHotPath(HotPath):
+    """kmeans::<K, I> over N x D vectors at 2^k rows: witness -> layout -> commit -> NTT, one GPU."""
+
+    def __init__(self, n=256, dim=128, K=4, I=8, k=16, P=48, L=15, metric="euclidean", seed=20260004, tau=None,
+                 col_shard=(0, 1), vectors=None, blind_seed=None, params=None):
+        super().__init__(n, dim, k, P, L, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors, blind_seed=blind_seed, params=params)
+        self.K, self.I = K, I
+        self.metric = api.METRICS[metric]
+        self.metric_name = metric
+
+    def _input_vectors(self):
+        return sift_like_vectors(self.seed, self.n, self.dim, self.K)
+
+    def _circuit_size(self):
+        cells, lk = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self.lib.vdb_wit_kmeans_size(self.metric, self.P, self.L, self.n, self.dim, self.K, self.I, 0, ctypes.byref(cells), ctypes.byref(lk)))
+        return self.n * self.dim, cells.value, lk.value
+
+    def _alloc_outputs(self):
+        self.d_cent = self._output(self.K * self.dim * 32)
+        self.d_ind = self._output(self.n * self.K * 32)
+
+    def _emit(self, sel):
+        at = self.n_in
+        with self._window(sel, at):
+            check(self.lib.vdb_wit_kmeans_dev(self.metric, self.P, self.L, self.d_vec.ptr, self.n, self.dim, self.K, self.I, 0, self.d_stream.at(at * B),
+                                              self.d_lookup.ptr, self._sel_at(sel, at), self.d_cent.ptr, self.d_ind.ptr))
+
     def public_values_dev(self):
-        """(device pointer, count) of the values the reference's example of this circuit makes public, in make_public order
-        (examples/kmeans.rs:51-56: every centroid, word by word).  Every rank computes them (value-only walk), whichever rank's
-        columns hold the cells."""
-        return self.d_cent.ptr, self.K * self.dim
+        return self.d_cent.ptr, self.K * self.dim              # examples/kmeans.rs:51-56: every centroid, word by word
 
     def results(self):
         cent = self.d_cent.download((self.K, self.dim, 4))
         ind = self.d_ind.download((self.n, self.K, 4))
         return cent, ind
 
-    def free(self):
-        for name in ("d_vec", "d_stream", "d_lookup", "d_cent", "d_ind", "d_blind", "d_wide", "d_cols", "d_ext", "d_mask", "d_cpts", "d_src"):
-            b = getattr(self, name, None)
-            if b is not None:
-                b.free()
-        if getattr(self, "srs", None) is not None:
-            self.srs.free()
+    def constraint_map(self, d_flags, on_device=True):
+        # the unit blocks are traced on the host (a few thousand cells each); their hundreds of thousands of instances are placed
+        # by the device (circuit_dev.py): the map's 10^9-cell arrays never exist on the host
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        cm, (cent, _ind) = CS.build_kmeans(self.metric_name, self.n, self.dim, self.K, self.I, self.P, self.L, builder=DeviceBuilder if on_device else None)
+        return cm, np.asarray(cent).reshape(-1), None
 
 
-class MerkleHotPath(KmeansHotPath):
+class MerkleHotPath(HotPath):
     """merkle_commitment over N x D vectors (src/gadget/vectordb.rs:165-223; examples/merkle.rs) through the same hot
     path: Poseidon trace on the GPU -> commit -> NTT.  No lookup cells; every column is dense (Poseidon states), so equal
     column counts per rank are balanced already; a rank that holds a block of columns traces only the permutations whose
     cells fall into it (the sponge states and the tree's digests are computed by every rank, value only)."""
 
     def __init__(self, n=1024, dim=128, k=15, P=32, seed=20260003, tau=None, col_shard=(0, 1), vectors=None, blind_seed=None, params=None):
-        super().__init__(n=n, dim=dim, K=1, I=1, k=k, P=P, L=8, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors, blind_seed=blind_seed,
-                         params=params)
+        super().__init__(n, dim, k, P, 8, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors, blind_seed=blind_seed, params=params)
         self.balance_shards = False
         self.msm_window_bits = 14   # every scalar is a full-width Poseidon state: 19 windows instead of 24
 
+    def _input_vectors(self):
+        return sift_like_vectors(self.seed, self.n, self.dim)
+
     def _circuit_size(self):
-        cells = ctypes.c_uint64()
-        check(self.lib.vdb_wit_merkle_size(self.n, self.dim, 0, ctypes.byref(cells)))
-        return self.n * self.dim, cells.value, 0      # the vectors are assigned first (tests/vectordb/mod.rs:253-262 chip_merkle)
+        return self.n * self.dim, _merkle_cells(self), 0      # the vectors are assigned first (tests/vectordb/mod.rs:253-262 chip_merkle)
 
     def _alloc_outputs(self):
-        self.d_root = api.DeviceBuffer(32)
+        self.d_root = self._output(32)
 
-    def _witness(self, sel=None):
-        lib = self.lib
-        check(lib.vdb_memcpy_d2d(self.d_stream.ptr, self.d_vec.ptr, ctypes.c_size_t(self.n_in * 32)))
-        windowed = sel is None and self.shard_witness and self.world > 1
-        if windowed:   # only the permutations whose cells fall into this rank's columns are traced; the digests are computed everywhere
-            lo, hi = (max(0, x - self.n_in) for x in self.win_adv)       # in the coordinates of the pointer handed to the call
-            check(lib.vdb_wit_set_window(ctypes.c_uint64(lo), ctypes.c_uint64(hi), ctypes.c_uint64(0), ctypes.c_uint64(0)))
-        try:
-            check(lib.vdb_wit_merkle_dev(self.d_vec.ptr, self.n, self.dim, 0, self.d_stream.at(self.n_in * 32),
-                                         ctypes.c_void_p(sel.ptr.value + self.n_in) if sel is not None else None, self.d_root.ptr))
-        finally:
-            if windowed:
-                check(lib.vdb_wit_set_window(ctypes.c_uint64(0), ctypes.c_uint64(2**64 - 1), ctypes.c_uint64(0), ctypes.c_uint64(2**64 - 1)))
+    def _emit(self, sel):
+        _merkle_trace(self, self.d_vec.ptr, self.n_in, sel)
 
     def public_values_dev(self):
         return self.d_root.ptr, 1                  # examples/merkle.rs:47
@@ -629,14 +744,20 @@ class MerkleHotPath(KmeansHotPath):
     def results(self):
         return self.d_root.download((4,))
 
-    def free(self):
-        super().free()
-        if getattr(self, "d_root", None) is not None:
-            self.d_root.free()
-            self.d_root = None
+    def constraint_map(self, d_flags, on_device=True):
+        if on_device:
+            from .circuit_dev import DeviceBuilder, place_merkle
+            bld = DeviceBuilder(self.n_cells, 0)
+            root, end = place_merkle(bld, self.n, self.dim, self.n_in, 0, functools.partial(self._fetch_flags, d_flags), self._fetch)
+            assert end == self.n_cells
+            cm = bld.finish()
+        else:
+            from .copymap import merkle_circuit_map
+            cm, root = merkle_circuit_map(self.n, self.dim, d_flags.download((self.n_cells,), dtype=np.uint8), self._fetch)
+        return cm, [root], root                    # examples/merkle.rs:47 make_public.push(root)
 
 
-class NearestHotPath(KmeansHotPath):
+class NearestHotPath(HotPath):
     """nearest_vector(query, vectors) (src/gadget/vectordb.rs:122-163; tests/vectordb/mod.rs:220-247 assigns the query, then the
     vectors) through the same hot path.  Sharded: every rank computes the N distances' values and the short minimum
     chain (value-only walk), and stores the cells of its own block of columns only — the distance blocks, N-way parallel and nearly
@@ -645,8 +766,9 @@ class NearestHotPath(KmeansHotPath):
     def __init__(self, n=64, dim=128, k=14, P=48, L=13, metric="euclidean", seed=20260002, tau=None, col_shard=(0, 1), vectors=None, blind_seed=None,
                  params=None):
         """`vectors`: (n + 1, dim) f64 rows, the query first"""
-        super().__init__(n=n, dim=dim, K=1, I=1, k=k, P=P, L=L, metric=metric, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors,
-                         blind_seed=blind_seed, params=params)
+        super().__init__(n, dim, k, P, L, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors, blind_seed=blind_seed, params=params)
+        self.metric = api.METRICS[metric]
+        self.metric_name = metric
 
     def n_input_rows(self):
         return self.n + 1
@@ -662,23 +784,14 @@ class NearestHotPath(KmeansHotPath):
         return (self.n + 1) * self.dim, cells.value, lk.value
 
     def _alloc_outputs(self):
-        self.d_ind = api.DeviceBuffer(self.n * 32)
-        self.d_res = api.DeviceBuffer(self.dim * 32)
+        self.d_ind = self._output(self.n * 32)
+        self.d_res = self._output(self.dim * 32)
 
-    def _witness(self, sel=None):
-        lib = self.lib
-        check(lib.vdb_memcpy_d2d(self.d_stream.ptr, self.d_vec.ptr, ctypes.c_size_t(self.n_in * 32)))
-        windowed = sel is None and self.shard_witness and self.world > 1
-        if windowed:   # in the coordinates of the pointers handed to the call (the gadget's cells start n_in cells into the stream)
-            lo, hi = (max(0, x - self.n_in) for x in self.win_adv)
-            check(lib.vdb_wit_set_window(ctypes.c_uint64(lo), ctypes.c_uint64(hi), ctypes.c_uint64(self.win_lk[0]), ctypes.c_uint64(self.win_lk[1])))
-        try:
-            check(lib.vdb_wit_nearest_dev(self.metric, self.P, self.L, self.d_vec.ptr, self.d_vec.at(self.dim * 32), self.n, self.dim, self.d_stream.at(self.n_in * 32),
-                                          self.d_lookup.ptr, ctypes.c_void_p(sel.ptr.value + self.n_in) if sel is not None else None, self.d_ind.ptr,
-                                          self.d_res.ptr))
-        finally:
-            if windowed:
-                check(lib.vdb_wit_set_window(ctypes.c_uint64(0), ctypes.c_uint64(2**64 - 1), ctypes.c_uint64(0), ctypes.c_uint64(2**64 - 1)))
+    def _emit(self, sel):
+        at = self.n_in
+        with self._window(sel, at):
+            check(self.lib.vdb_wit_nearest_dev(self.metric, self.P, self.L, self.d_vec.ptr, self.d_vec.at(self.dim * 32), self.n, self.dim,
+                                               self.d_stream.at(at * B), self.d_lookup.ptr, self._sel_at(sel, at), self.d_ind.ptr, self.d_res.ptr))
 
     def public_values_dev(self):
         return self.d_res.ptr, self.dim            # examples/query.rs:58: the nearest vector
@@ -686,11 +799,11 @@ class NearestHotPath(KmeansHotPath):
     def results(self):
         return self.d_ind.download((self.n, 4)), self.d_res.download((self.dim, 4))
 
-    def free(self):
-        super().free()
-        if getattr(self, "d_res", None) is not None:
-            self.d_res.free()
-            self.d_res = None
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        cm, (_ind, res) = CS.build_nearest(self.metric_name, self.n, self.dim, self.P, self.L, builder=DeviceBuilder if on_device else None)
+        return cm, res, None                       # examples/query.rs:58 make_public.extend(result)
 
 
 class QueryHotPath(NearestHotPath):
@@ -702,30 +815,18 @@ class QueryHotPath(NearestHotPath):
 
     def _circuit_size(self):
         n_in, nv_cells, lk = super()._circuit_size()
-        mk = ctypes.c_uint64()
-        check(self.lib.vdb_wit_merkle_size(self.n, self.dim, 0, ctypes.byref(mk)))
-        self.nearest_cells, self.merkle_cells = nv_cells, mk.value
-        return n_in, nv_cells + mk.value, lk
+        self.nearest_cells, self.merkle_cells = nv_cells, _merkle_cells(self)
+        return n_in, nv_cells + self.merkle_cells, lk
 
     def _alloc_outputs(self):
         super()._alloc_outputs()
-        self.d_root = api.DeviceBuffer(32)
-        self.d_pub = api.DeviceBuffer((self.dim + 1) * 32)      # [result vector | root]: the public statement, in make_public order
+        self.d_root = self._output(32)
+        self.d_pub = self._output((self.dim + 1) * 32)      # [result vector | root]: the public statement, in make_public order
 
-    def _witness(self, sel=None):
+    def _emit(self, sel):
         lib = self.lib
-        super()._witness(sel)                                       # inputs + nearest_vector (windowed like NearestHotPath)
-        off = self.n_in + self.nearest_cells
-        windowed = sel is None and self.shard_witness and self.world > 1
-        if windowed:                                                 # in the coordinates of the Merkle trace's first cell
-            lo, hi = (max(0, x - off) for x in self.win_adv)
-            check(lib.vdb_wit_set_window(ctypes.c_uint64(lo), ctypes.c_uint64(hi), ctypes.c_uint64(0), ctypes.c_uint64(0)))
-        try:
-            check(lib.vdb_wit_merkle_dev(self.d_vec.at(self.dim * 32), self.n, self.dim, 0, self.d_stream.at(off * 32),
-                                         ctypes.c_void_p(sel.ptr.value + off) if sel is not None else None, self.d_root.ptr))
-        finally:
-            if windowed:
-                check(lib.vdb_wit_set_window(ctypes.c_uint64(0), ctypes.c_uint64(2**64 - 1), ctypes.c_uint64(0), ctypes.c_uint64(2**64 - 1)))
+        super()._emit(sel)                                          # nearest_vector (windowed like NearestHotPath)
+        _merkle_trace(self, self.d_vec.at(self.dim * 32), self.n_in + self.nearest_cells, sel)
         check(lib.vdb_memcpy_d2d(self.d_pub.ptr, self.d_res.ptr, ctypes.c_size_t(self.dim * 32)))
         check(lib.vdb_memcpy_d2d(self.d_pub.at(self.dim * 32), self.d_root.ptr, ctypes.c_size_t(32)))
 
@@ -736,15 +837,19 @@ class QueryHotPath(NearestHotPath):
         ind, res = super().results()
         return ind, res, self.d_root.download((4,))
 
-    def free(self):
-        super().free()
-        for name in ("d_root", "d_pub"):
-            if getattr(self, name, None) is not None:
-                getattr(self, name).free()
-                setattr(self, name, None)
+    def constraint_map(self, d_flags, on_device=True):
+        # nearest_vector, then merkle_commitment over the same assigned vectors, in one map (examples/query.rs)
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder, place_merkle
+        bld, (_ind, res), used = CS.build_nearest(self.metric_name, self.n, self.dim, self.P, self.L, builder=DeviceBuilder,
+                                                  extra_cells=self.merkle_cells, finish=False)
+        assert used == self.n_in + self.nearest_cells
+        root, end = place_merkle(bld, self.n, self.dim, used, self.dim, functools.partial(self._fetch_flags, d_flags), self._fetch)
+        assert end == self.n_cells
+        return bld.finish(), list(res) + [root], root      # examples/query.rs:58, :69: the result vector, then the root
 
 
-class DistancesHotPath(KmeansHotPath):
+class DistancesHotPath(HotPath):
     """The reference's two-vector circuits through the same hot path: examples/distances.rs:29-59 (assign a, assign b, then
     euclidean, manhattan, cosine and hamming distance of the same two vectors, each made public) and examples/euclid.rs:26-46 (ten Euclidean distances of one pair, nothing public:
     `metrics=("euclidean",) * 10, public=False`).  BASELINE configs[0] is this circuit with one Euclidean distance of two 4-dim
@@ -754,12 +859,11 @@ class DistancesHotPath(KmeansHotPath):
     def __init__(self, dim=4, metrics=("euclidean", "manhattan", "cosine", "hamming"), k=13, P=48, L=12, seed=20260001, tau=None, col_shard=(0, 1), vectors=None,
                  blind_seed=None, public=True, params=None):
         """`vectors`: (2, dim) f64 rows, a then b"""
-        super().__init__(n=2, dim=dim, K=1, I=1, k=k, P=P, L=L, metric=metrics[0], seed=seed, tau=tau, col_shard=col_shard, vectors=vectors,
-                         blind_seed=blind_seed, params=params)
-        self.metrics = tuple(metrics)
-        for m in self.metrics:
+        for m in metrics:
             if m not in api.METRICS:
                 raise ValueError("unknown distance: " + str(m))
+        super().__init__(2, dim, k, P, L, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors, blind_seed=blind_seed, params=params)
+        self.metrics = tuple(metrics)
         self.public = bool(public)
         self.shard_witness = False
 
@@ -767,26 +871,18 @@ class DistancesHotPath(KmeansHotPath):
         return sift_like_vectors(self.seed, 2, self.dim)
 
     def _circuit_size(self):
-        self.parts = []
-        cells_total = lk_total = 0
-        for m in self.metrics:
-            cells, lk = ctypes.c_uint64(), ctypes.c_uint64()
-            check(self.lib.vdb_wit_distance_size(api.METRICS[m], self.P, self.L, 1, self.dim, ctypes.byref(cells), ctypes.byref(lk)))
-            self.parts.append((api.METRICS[m], cells_total, lk_total))
-            cells_total, lk_total = cells_total + cells.value, lk_total + lk.value
-        return 2 * self.dim, cells_total, lk_total
+        self.parts, cells, lk = _end_to_end([api.METRICS[m] for m in self.metrics],
+                                            lambda code, cells, lk: self.lib.vdb_wit_distance_size(code, self.P, self.L, 1, self.dim, cells, lk))
+        return 2 * self.dim, cells, lk
 
     def _alloc_outputs(self):
-        self.d_res = api.DeviceBuffer(len(self.metrics) * 32)
+        self.d_res = self._output(len(self.metrics) * 32)
 
-    def _witness(self, sel=None):
-        lib = self.lib
-        check(lib.vdb_memcpy_d2d(self.d_stream.ptr, self.d_vec.ptr, ctypes.c_size_t(self.n_in * 32)))
+    def _emit(self, sel):
         for i, (metric, off, lk_off) in enumerate(self.parts):
             at = self.n_in + off
-            check(lib.vdb_wit_distance_dev(metric, self.P, self.L, self.d_vec.ptr, self.d_vec.at(self.dim * 32), 1, self.dim, self.d_stream.at(at * 32),
-                                           self.d_lookup.at(lk_off * 32), ctypes.c_void_p(sel.ptr.value + at) if sel is not None else None,
-                                           self.d_res.at(i * 32)))
+            check(self.lib.vdb_wit_distance_dev(metric, self.P, self.L, self.d_vec.ptr, self.d_vec.at(self.dim * 32), 1, self.dim, self.d_stream.at(at * B),
+                                                self.d_lookup.at(lk_off * B), self._sel_at(sel, at), self.d_res.at(i * 32)))
 
     def public_values_dev(self):
         return self.d_res.ptr, len(self.metrics) if self.public else 0      # examples/distances.rs:44-59: make_public.push(dist) after each
@@ -794,58 +890,53 @@ class DistancesHotPath(KmeansHotPath):
     def results(self):
         return self.d_res.download((len(self.metrics), 4))
 
-    def free(self):
-        super().free()
-        if getattr(self, "d_res", None) is not None:
-            self.d_res.free()
-            self.d_res = None
+    def constraint_map(self, d_flags, on_device=True):
+        # two vectors, a handful of distances: the whole trace on the host (examples/distances.rs, examples/euclid.rs)
+        from . import circuit_sym as CS
+        cm, outs = CS.trace_distances(self.metrics, self.dim, self.P, self.L)
+        return cm, outs if self.public else [], None      # examples/distances.rs:44-59 make_public.push(dist)
 
 
-
-class FixedPointHotPath(DistancesHotPath):
+class FixedPointHotPath(HotPath):
     """examples/fixed_point.rs:38-112 through the hot path: FixedPointChip<32> on ONE value — x = ctx.load_witness(quantization(x)), then
     qexp2(x), qlog2(x) when x > 0, qsin(x), with x and every result public.  Stream: [x | the cells of each call in turn]
-    (vdb_wit_fp_op_dev, one instance each).  `ops`: other FixedPointInstructions names instead of the example's."""
+    (vdb_wit_fp_op_dev, one instance each).  `ops`: other unary FixedPointInstructions names instead of the example's."""
 
     def __init__(self, x=1.128, ops=None, k=13, P=32, L=12, tau=None, blind_seed=None, params=None):
         self.x = float(x)
         self.ops = tuple(ops) if ops is not None else ("qexp2",) + (("qlog2",) if self.x > 0.0 else ()) + ("qsin",)
         for name in self.ops:
-            if name not in api.FP_OPS:
-                raise ValueError("unknown FixedPointChip operation: " + str(name))
-        KmeansHotPath.__init__(self, n=1, dim=1, K=1, I=1, k=k, P=P, L=L, metric="euclidean", tau=tau, vectors=np.array([[self.x]]), blind_seed=blind_seed,
-                               params=params)
-        self.metrics = ()
-        self.public = True
+            if name not in FP_UNARY_OPS:
+                raise ValueError("not a unary FixedPointChip operation: " + str(name))
+        super().__init__(1, 1, k, P, L, tau=tau, blind_seed=blind_seed, params=params)
         self.shard_witness = False
 
     def _input_vectors(self):
         return np.array([[self.x]], dtype=np.float64), None
 
     def _circuit_size(self):
-        self.parts = []
-        cells_total = lk_total = 0
-        for name in self.ops:
-            cells, lk = ctypes.c_uint64(), ctypes.c_uint64()
-            check(self.lib.vdb_wit_fp_op_size(api.FP_OPS[name], self.P, self.L, 1, ctypes.byref(cells), ctypes.byref(lk)))
-            self.parts.append((api.FP_OPS[name], cells_total, lk_total))
-            cells_total, lk_total = cells_total + cells.value, lk_total + lk.value
-        return 1, cells_total, lk_total
+        self.parts, cells, lk = _end_to_end([api.FP_OPS[name] for name in self.ops],
+                                            lambda code, cells, lk: self.lib.vdb_wit_fp_op_size(code, self.P, self.L, 1, cells, lk))
+        return 1, cells, lk
 
     def _alloc_outputs(self):
-        self.d_res = api.DeviceBuffer((1 + len(self.ops)) * 32)        # [x | results]: the public statement in make_public order
+        self.d_res = self._output((1 + len(self.ops)) * 32)        # [x | results]: the public statement in make_public order
 
-    def _witness(self, sel=None):
-        lib = self.lib
-        check(lib.vdb_memcpy_d2d(self.d_stream.ptr, self.d_vec.ptr, ctypes.c_size_t(32)))
-        check(lib.vdb_memcpy_d2d(self.d_res.ptr, self.d_vec.ptr, ctypes.c_size_t(32)))
+    def _emit(self, sel):
+        check(self.lib.vdb_memcpy_d2d(self.d_res.ptr, self.d_vec.ptr, ctypes.c_size_t(32)))
         for i, (op, off, lk_off) in enumerate(self.parts):
             at = 1 + off
-            check(lib.vdb_wit_fp_op_dev(op, self.P, self.L, self.d_vec.ptr, None, 1, self.d_stream.at(at * 32), self.d_lookup.at(lk_off * 32),
-                                        ctypes.c_void_p(sel.ptr.value + at) if sel is not None else None, self.d_res.at((1 + i) * 32)))
+            check(self.lib.vdb_wit_fp_op_dev(op, self.P, self.L, self.d_vec.ptr, None, 1, self.d_stream.at(at * B), self.d_lookup.at(lk_off * B),
+                                             self._sel_at(sel, at), self.d_res.at((1 + i) * 32)))
 
     def public_values_dev(self):
         return self.d_res.ptr, 1 + len(self.ops)           # examples/fixed_point.rs:64, :79, :94, :110: make_public.push after each
 
     def results(self):
         return self.d_res.download((1 + len(self.ops), 4))[1:]
+
+    def constraint_map(self, d_flags, on_device=True):
+        # one value, a handful of FixedPointChip calls (examples/fixed_point.rs): x and every result public
+        from . import circuit_sym as CS
+        cm, outs = CS.trace_fixed_point(self.ops, self.P, self.L)
+        return cm, outs, None

@@ -15,6 +15,7 @@ _R_INV = pow(1 << 256, -1, R_MOD)
 # what the reference's own MINIMUM_ROWS = 9 = blinding_factors() + 3 says (src/scaffold/mod.rs:383) — and the last usable row, where
 # l_last sits and the running products end, is row 2^k - 7.  (Rounds 1-2 used 6.)
 N_BLIND = 7
+MINIMUM_ROWS = 9    # rows at the end of every column that the layout leaves free (src/scaffold/mod.rs:383)
 FIXED = ("sel", "sigma", "cst", "table")     # the committed fixed polynomials, in the order the verifying key's digest absorbs their commitments
 DERIVED = ("hf",)   # opened polynomials whose evaluation is not in the proof: the verifier computes it (h folded at x, from the quotient identity)
 # (the Lagrange selectors l_0, l_last, l_active = 1 - l_last - l_blind the quotient multiplies by are not polynomials of the key: halo2

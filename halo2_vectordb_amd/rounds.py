@@ -29,8 +29,7 @@ import numpy as np
 
 from . import api, protocol
 from ._lib import check
-from .pipeline import MINIMUM_ROWS
-from .protocol import DERIVED, FIXED, N_BLIND, R_MOD, constraint_degree
+from .protocol import DERIVED, FIXED, MINIMUM_ROWS, N_BLIND, R_MOD, constraint_degree
 from .protocol import fr_from_int as _fr_from_int, fr_to_int as _fr_to_int
 
 B = 32
@@ -341,63 +340,11 @@ class ProverRounds:
 
     # ------------------------------------------------------------------ keygen side (untimed): the fixed polynomials
     def circuit_map(self, d_flags):
-        """The circuit's constraint map (circuit_sym.CopyMap) for the gadget this hot path runs: the symbolic trace of the
-        fixed-point gadgets, or of the Poseidon sponge for the Merkle circuit."""
-        from .pipeline import DistancesHotPath, FixedPointHotPath, MerkleHotPath, NearestHotPath, QueryHotPath
-        hp = self.hp
-        on_device = getattr(self, "map_on_device", True)
-        if isinstance(hp, FixedPointHotPath):
-            # one value, a handful of FixedPointChip calls (examples/fixed_point.rs): x and every result public
-            from . import circuit_sym as CS
-            cm, outs = CS.trace_fixed_point(hp.ops, hp.P, hp.L)
-            self.public_cells = [int(c) for c in outs]
-            return cm
-        if isinstance(hp, DistancesHotPath):
-            # two vectors, a handful of distances: the whole trace on the host (examples/distances.rs, examples/euclid.rs)
-            from . import circuit_sym as CS
-            cm, outs = CS.trace_distances(hp.metrics, hp.dim, hp.P, hp.L)
-            self.public_cells = [int(c) for c in outs] if hp.public else []      # examples/distances.rs:44-59 make_public.push(dist)
-            return cm
-
-        def fetch(lo, hi):
-            c = api.fr_to_canonical(hp.d_stream.download((hi - lo, 4), offset=lo * B))
-            return [int(r[0]) | int(r[1]) << 64 | int(r[2]) << 128 | int(r[3]) << 192 for r in c]
-
-        def fetch_flags(lo, hi):
-            return d_flags.download((hi - lo,), dtype=np.uint8, offset=lo)
-        if isinstance(hp, MerkleHotPath):
-            if on_device:
-                from .circuit_dev import DeviceBuilder, place_merkle
-                bld = DeviceBuilder(hp.n_cells, 0)
-                self.root_cell, end = place_merkle(bld, hp.n, hp.dim, hp.n_in, 0, fetch_flags, fetch)
-                assert end == hp.n_cells
-                cm = bld.finish()
-            else:
-                from .copymap import merkle_circuit_map
-                cm, self.root_cell = merkle_circuit_map(hp.n, hp.dim, d_flags.download((hp.n_cells,), dtype=np.uint8), fetch)
-            self.public_cells = [int(self.root_cell)]                               # examples/merkle.rs:47 make_public.push(root)
-            return cm
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        # the unit blocks are traced on the host (a few thousand cells each); their hundreds of thousands of instances are placed
-        # by the device (circuit_dev.py): the map's 10^9-cell arrays never exist on the host
-        builder = DeviceBuilder if on_device else None
-        if isinstance(hp, QueryHotPath):
-            # nearest_vector, then merkle_commitment over the same assigned vectors, in one map (examples/query.rs)
-            from .circuit_dev import place_merkle
-            bld, (_ind, res), used = CS.build_nearest(hp.metric_name, hp.n, hp.dim, hp.P, hp.L, builder=DeviceBuilder, extra_cells=hp.merkle_cells, finish=False)
-            assert used == hp.n_in + hp.nearest_cells
-            self.root_cell, end = place_merkle(bld, hp.n, hp.dim, used, hp.dim, fetch_flags, fetch)
-            assert end == hp.n_cells
-            cm = bld.finish()
-            self.public_cells = [int(c) for c in res] + [int(self.root_cell)]       # examples/query.rs:58, :69: the result vector, then the root
-            return cm
-        if isinstance(hp, NearestHotPath):
-            cm, (_ind, res) = CS.build_nearest(hp.metric_name, hp.n, hp.dim, hp.P, hp.L, builder=builder)
-            self.public_cells = [int(c) for c in res]                               # examples/query.rs:58 make_public.extend(result)
-        else:
-            cm, (cent, _ind) = CS.build_kmeans(hp.metric_name, hp.n, hp.dim, hp.K, hp.I, hp.P, hp.L, builder=builder)
-            self.public_cells = [int(c) for c in np.asarray(cent).reshape(-1)]      # examples/kmeans.rs:51-56: every centroid, word by word
+        """The circuit's constraint map (circuit_sym.CopyMap) for the gadget this hot path runs (hp.constraint_map); sets the cells its
+        example makes public and the Merkle root's cell (None for a circuit without one).  `map_on_device` = False: the host builds
+        the maps the device would place."""
+        cm, public, self.root_cell = self.hp.constraint_map(d_flags, getattr(self, "map_on_device", True))
+        self.public_cells = [int(c) for c in public]
         return cm
 
     def keygen(self, circuit=None, instance_cells=None, check=True):
@@ -410,9 +357,8 @@ class ProverRounds:
         `check`: run the device-side MockProver on the keygen witness with the whole map (vdb_mock_check_dev); the report is
         kept in self.keygen_report (a circuit the witness does not satisfy can still be set up — the proof will not verify)."""
         hp, lib, rows, k = self.hp, self.lib, self.rows, self.k
-        # the fixed columns' commitments work in the bounded MSM work space of setup (pipeline.setup); the first step() lifts the bound
+        # the fixed columns' commitments work in the bounded MSM work space of setup (pipeline.HotPath.setup); every step() lifts the bound
         api.msm_scratch_cap(api.KEYGEN_SCRATCH_CAP)
-        hp._cap_lifted = False
         # the derived columns (products, quotient, opening quotients) and the fixed sigma columns hold full-width scalars
         self.srs_m = api.Srs(k, hp.g_monomial, hp.g_lagrange, window_bits=14)
         self.srs_few = api.Srs(k, hp.g_monomial, None)     # a handful of columns: the bucket folding dominates, fewer buckets win

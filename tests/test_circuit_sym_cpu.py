@@ -168,6 +168,15 @@ def test_fixed_point_example_map_on_the_oracles_witness(O, x):
     assert [vals[o] for o in outs] == [to_ints(O, q)[0]] + [to_ints(O, r)[0] for r in res]
 
 
+def test_fixed_point_hot_path_refuses_binary_operations():
+    """FixedPointHotPath proves calls of one operand: a binary FixedPointInstructions name is refused up front, naming it, before the
+    library is touched"""
+    from halo2_vectordb_amd.pipeline import FixedPointHotPath
+    for name in ("qadd", "qdiv"):
+        with pytest.raises(ValueError, match=name):
+            FixedPointHotPath(ops=(name,))
+
+
 @pytest.mark.parametrize("name", ["neg", "qabs", "is_neg", "qsqrt", "qlog2", "qexp2", "qlog", "qexp", "sign", "clip", "qsin", "qcos", "qtan", "qsinh", "qcosh", "qtanh"])
 def test_every_unary_fixed_point_operation_map_on_the_oracles_witness(O, name):
     """the symbolic map of one FixedPointInstructions call on a loaded witness (what FixedPointHotPath(ops=...) proves), on the oracle's

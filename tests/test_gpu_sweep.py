@@ -1,6 +1,6 @@
 """A seeded sweep over shapes the fixed cases of tests/test_gpu_witness.py do not name: every gadget entry point at random sizes, all
 four distances, both precisions the reference's examples use, lookup widths 8 .. 15 — advice cells, lookup cells, gate flags and
-results against the oracle, bit for bit; then the same traces stored through random rank windows (vdb_wit_set_window): every cell
+results against the oracle, bit for bit; then the same traces stored through random rank windows (api.wit_window): every cell
 inside the window equal, every cell outside it untouched.  Where the oracle reports a domain error (the reference would panic: an
 empty cluster's division) the library must refuse with VDB_ERR_DOMAIN instead of returning cells."""
 import ctypes
@@ -104,11 +104,8 @@ def test_random_rank_windows_store_their_cells_and_nothing_else(api, O):
             d_vec.upload(qv)
             check(lib.vdb_memset_dev(d_adv.ptr, 0xA5, ctypes.c_size_t(adv.nbytes)))
             check(lib.vdb_memset_dev(d_lk.ptr, 0xA5, ctypes.c_size_t(max(lk.nbytes, 32))))
-            check(lib.vdb_wit_set_window(ctypes.c_uint64(lo), ctypes.c_uint64(hi), ctypes.c_uint64(llo), ctypes.c_uint64(lhi)))
-            try:
+            with api.wit_window(adv=(lo, hi), lookup=(llo, lhi)):
                 check(lib.vdb_wit_kmeans_dev(api.METRICS[metric], P, L, d_vec.ptr, n, dim, K, I, 0, d_adv.ptr, d_lk.ptr, None, d_cent.ptr, d_ind.ptr))
-            finally:
-                check(lib.vdb_wit_set_window(ctypes.c_uint64(0), ctypes.c_uint64(2 ** 64 - 1), ctypes.c_uint64(0), ctypes.c_uint64(2 ** 64 - 1)))
             g_adv, g_lk = d_adv.download(adv.shape), d_lk.download(lk.shape) if len(lk) else lk
             tag = f"case {case}: {metric} n={n} dim={dim} K={K} I={I} L={L} window [{lo}, {hi}) / [{llo}, {lhi})"
             assert np.array_equal(g_adv[lo:hi], adv[lo:hi]), tag
@@ -139,11 +136,8 @@ def _windowed(api, lib, check, adv, lk, window, run):
     try:
         check(lib.vdb_memset_dev(d_adv.ptr, POISON, ctypes.c_size_t(max(adv.nbytes, 32))))
         check(lib.vdb_memset_dev(d_lk.ptr, POISON, ctypes.c_size_t(max(lk.nbytes, 32))))
-        check(lib.vdb_wit_set_window(ctypes.c_uint64(lo), ctypes.c_uint64(hi), ctypes.c_uint64(llo), ctypes.c_uint64(lhi)))
-        try:
+        with api.wit_window(adv=(lo, hi), lookup=(llo, lhi)):
             run(d_adv, d_lk)
-        finally:
-            check(lib.vdb_wit_set_window(ctypes.c_uint64(0), ctypes.c_uint64(2 ** 64 - 1), ctypes.c_uint64(0), ctypes.c_uint64(2 ** 64 - 1)))
         return d_adv.download(adv.shape), (d_lk.download(lk.shape) if len(lk) else lk)
     finally:
         d_adv.free()
