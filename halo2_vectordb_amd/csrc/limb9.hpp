@@ -56,7 +56,8 @@ HD u256 l9_pack(const L9& L) {
   r.w[7] = (L.l[7] >> 21) | (L.l[8] << 8);
   return r;
 }
-// one parallel carry pass: limbs below 2^32 in, limbs below 2^29 + 8 out (top limb takes what is left)
+// one parallel carry pass: limbs below 2^32 in, limbs below 2^29 + 8 out (top limb takes what is left: it needs room for a carry
+// of at most 7, i.e. value below 2^264 - 7 * 2^232)
 HD void l9_renorm(L9& x) {
   uint32_t c[8];
 #pragma unroll
@@ -66,7 +67,8 @@ HD void l9_renorm(L9& x) {
 #pragma unroll
   for (int k = 1; k < 9; k++) x.l[k] += c[k - 1];
 }
-// full carry propagation: limbs 0..7 exactly below 2^29
+// full carry propagation: limbs 0..7 exactly below 2^29.  Every limb takes the carry of the one below before it gives its own:
+// limbs at most 2^32 - 8 in (a carry is then at most 7 and nothing wraps)
 HD void l9_carry(L9& x) {
 #pragma unroll
   for (int k = 0; k < 8; k++) {
@@ -81,8 +83,12 @@ HD L9 l9_add(const L9& a, const L9& b) {
   return r;
 }
 // a - t + K p, limb-wise.  `ckp` is K p written with limbs c[0] = v_0 + 2^29, c[k] = v_k + 2^29 - 1 (0 < k < 8),
-// c[8] = v_8 - 1 (l9_offset_limbs), which dominate the limbs of any t with limbs 0..7 below 2^29 and value below
-// (K - 1) p, so no limb ever goes negative.
+// c[8] = v_8 - 1 (l9_offset_limbs).  Exact — limb k is a_k + c_k - t_k as integers, for any a whose sums stay below 2^32 — when
+// t_k <= c_k for every k.  Limbs 0..7 of c are at least 2^29 - 1, so for a t with limbs 0..7 below 2^29 the condition is on the top
+// limb alone: t_8 <= c_8 = floor(K p / 2^232) - 1, which every value below (K - 2^-22) p meets (in particular every value below
+// (K - 1) p; the MSM subtracts values below 7.5 q from 8 q).  t_8 = c_8 + 1 wraps.  A t as l9_renorm leaves it (limbs up to
+// 2^29 + 7) is covered by the offsets whose limbs v_k are all at least 8 — 9 r, 14 r, 34 r, 8 q, 2 q, but not 2 r (v_0 = 2).
+// (tests/test_l9_cpu.py: test_sub_domain_edge, test_sub_renormalised_subtrahend)
 HD L9 l9_sub(const L9& a, const L9& t, const uint32_t (&ckp)[9]) {
   L9 r;
 #pragma unroll
@@ -187,6 +193,31 @@ inline double l9_offset_limbs(uint32_t K, uint32_t out[9]) {
   double cmax = 0;
   for (int k = 0; k < 8; k++) cmax = fmax(cmax, (double)out[k] / (double)(1u << 29));
   return cmax;
+}
+
+// limbs below 2^32, value below 2^259 -> canonical eight words without a multiplication and without a carry pass of its own:
+// subtract q r with q = floor(top / (r_8 + 1)), top = l_8 + (l_7 >> 29) — the value's true top limb or one less (what limbs 0..6
+// and the low 29 bits of l_7 carry into bit 232 is at most 1) — so q is never too large and, as an exact quotient, at most 1 too
+// small (both occur in tests/test_gpu_l9.py; MU's rounding may cost one more); the subtraction's 64-bit column accumulator
+// propagates every carry on the way, and two conditional subtractions (2 r, then r) finish anything below 4 r
+__device__ __forceinline__ u256 l9_canon_wide(L9 x) {
+  constexpr uint32_t MU = 2840127191u;  // floor(2^53 / (0x30644e + 1))
+  const uint32_t q = __umulhi((x.l[8] + (x.l[7] >> 29)) << 3, MU) >> 24;
+  // x + q (2^261 - r) mod 2^261
+  uint64_t acc = 0;
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+    const uint32_t nk = (k == 0 ? 0x20000000u : 0x1fffffffu) - FrParams::P29[k];  // limbs of 2^261 - r
+    acc += (uint64_t)x.l[k] + (uint64_t)q * nk;
+    x.l[k] = (uint32_t)acc & 0x1fffffffu;
+    acc >>= 29;
+  }
+  u256 v = l9_pack(x), t, p2, pp = mod_p<Fr>();
+  u256_add(p2, pp, pp);
+  uint32_t keep = u256_sub(t, v, p2);
+#pragma unroll
+  for (int i = 0; i < 8; i++) v.w[i] = keep ? v.w[i] : t.w[i];
+  return lazy_canon<Fr>(v);
 }
 
 }  // namespace vdb

@@ -92,29 +92,6 @@ __device__ __forceinline__ void ld_pair18(const uint32_t* e, L9& w, L9& wq) {
   }
 }
 
-// limbs below 2^32, value below 2^259 -> canonical eight words without a multiplication and without a carry pass of its own:
-// subtract q r with q = floor(top / (r_8 + 1)), top = l_8 + (l_7 >> 29) — the value's true top limb or one less (what limbs 0..6
-// and the low 29 bits of l_7 carry into bit 232 is at most 1) — so q is never too large and at most 3 too small; the subtraction's
-// 64-bit column accumulator propagates every carry on the way, and two conditional subtractions (2 r, then r) finish below 4 r
-__device__ __forceinline__ u256 l9_canon_wide(L9 x) {
-  constexpr uint32_t MU = 2840127191u;  // floor(2^53 / (0x30644e + 1))
-  const uint32_t q = __umulhi((x.l[8] + (x.l[7] >> 29)) << 3, MU) >> 24;
-  // x + q (2^261 - r) mod 2^261
-  uint64_t acc = 0;
-#pragma unroll
-  for (int k = 0; k < 9; k++) {
-    const uint32_t nk = (k == 0 ? 0x20000000u : 0x1fffffffu) - FrParams::P29[k];  // limbs of 2^261 - r
-    acc += (uint64_t)x.l[k] + (uint64_t)q * nk;
-    x.l[k] = (uint32_t)acc & 0x1fffffffu;
-    acc >>= 29;
-  }
-  u256 v = l9_pack(x), t, p2, pp = mod_p<Fr>();
-  u256_add(p2, pp, pp);
-  uint32_t keep = u256_sub(t, v, p2);
-#pragma unroll
-  for (int i = 0; i < 8; i++) v.w[i] = keep ? v.w[i] : t.w[i];
-  return lazy_canon<Fr>(v);
-}
 // products and the final conditional subtraction are over Fr in this file
 __device__ __forceinline__ L9 l9_mul(const L9& a, const L9& W) { return l9_mul<Fr>(a, W); }
 __device__ __forceinline__ u256 l9_canon(const L9& t) { return l9_canon<Fr>(t); }
@@ -343,6 +320,8 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(const u256* __restrict
           }
           if (FIRST) {
             // stage 0: every twiddle is 1.  stage 1: block 0 has twiddle 1, block 1 has omega_4.
+            // x2, x3 are subtracted as loaded: exactly normalised, because the carry bit is never set for the step that starts at stage 0
+            // (ntt_dev refuses such a schedule)
             L9 a0 = l9_add(x0, x2), a2 = l9_sub(x0, x2, p.ckp);
             L9 a1 = l9_add(x1, x3), a3 = l9_sub(x1, x3, p.ckp);
             l9_carry(a1);  // a1 is subtracted below: its limbs must be below 2^29 again
@@ -776,6 +755,14 @@ int ntt_dev(u256* data, u256* out_or_null, size_t n_cols, uint32_t log_n, const 
             }
             st += 1;
           }
+        }
+        // the step that starts at stage 0 subtracts its operands as loaded (k_ntt_pass, the FIRST branch and the radix-2 stage of a
+        // one-stage pass) and its limb bounds above assume exactly normalised input.  The loop above never puts a carry pass in front
+        // of it; keep it so.  (Limbs of 2^29 + 7 would still be inside l9_sub's domain for the 14 r offset, but not for every offset:
+        // tests/test_l9_cpu.py::test_sub_renormalised_subtrahend)
+        if (p.s0 == 0 && (p.ren_mask & 1u)) {
+          set_error("ntt: the carry schedule put a carry pass in front of the step at stage 0");
+          return VDB_ERR_ARG;
         }
         // the write-out multiplies (inter-pass twiddle, 1/n, zeta) unless it is a forward transform's last pass, whose reduction
         // carries on its own (l9_canon_wide): a carry pass only when the last step left limbs above what a product takes
