@@ -123,6 +123,7 @@ HD u256 u256_shr(const u256& a, unsigned s) {
   }
   return t;
 }
+// left shift by s in [0, 255], bits shifted beyond bit 255 are dropped
 HD u256 u256_shl(const u256& a, unsigned s) {
   u256 t = a;
   const unsigned ws = s >> 5, bs = s & 31;
@@ -156,7 +157,7 @@ HD u256 u256_shr_small(const u256& a, unsigned s) {
   o.w[7] = a.w[7] >> s;
   return o;
 }
-// keep the low `bits` bits
+// keep the low `bits` bits; any count is allowed, 256 and above keep the whole value
 HD u256 u256_low_bits(const u256& a, unsigned bits) {
   u256 o;
 #pragma unroll
@@ -175,7 +176,7 @@ HD unsigned u256_bits(const u256& a) {
   return r;
 }
 HD uint32_t u256_bit(const u256& a, unsigned i) { return (a.w[i >> 5] >> (i & 31)) & 1u; }
-// extract `len` (<= 32) bits starting at bit `pos`
+// extract `len` (<= 32, 0 gives 0) bits starting at bit `pos`; bits at 256 and above read as zero, so does any pos >= 256
 HD uint32_t u256_extract(const u256& a, unsigned pos, unsigned len) {
   if (pos >= 256) return 0u;
   u256 t = u256_shr(a, pos);

@@ -160,7 +160,8 @@ struct Gadgets {
 
   HD u256 zero() const { return u256_zero(); }
   // Montgomery form v * 2^256 mod r of a small integer (v < 2^24) WITHOUT a table: v c - q r with c = 2^256 mod r and
-  // q = floor(v mu / 2^32), mu = floor(c 2^32 / r) — never above floor(v c / r) and at most one below, so the difference is
+  // q = floor(v mu / 2^32), mu = floor(c 2^32 / r) — never above floor(v c / r) and at most one below (for 4,566 of the v < 2^24, the
+  // first of them 46,183: lookup widths up to 15 never take the subtraction), so the difference is
   // below 2 r and one conditional subtraction finishes.  ~45 vector instructions instead of a 32-byte gather whose index is
   // data dependent: in the gadget chains such a load queues behind every store issued before it (one in-order vmcnt), and
   // the range checks make dozens of them per qmul.
@@ -409,7 +410,8 @@ struct Gadgets {
   // shape that indexes no register array at run time.  The divisor is shifted left until its top bit is bit 255 (bn), the dividend by
   // the same amount (a 512-bit value hi : lo); hi < bn is the first partial remainder, and each of lo's eight words, from the top,
   // yields one 32-bit quotient digit: the estimate floor(top two words of the remainder / top word of bn) is at most 2 too large for a
-  // normalised divisor, which at most two add-backs correct.  Words that cannot produce a digit (remainder below the divisor's top
+  // normalised divisor, which at most two add-backs correct (where the remainder's top word equals the divisor's the estimate does not fit a
+  // word and is clamped to 2^32 - 1, which is then at most 1 too large).  Words that cannot produce a digit (remainder below the divisor's top
   // word) cost a shift.  The bit-serial loop this replaces took ~60 instructions for every BIT of the dividend — half of the
   // sequential chain of a distance's tail (qsqrt divides twice).
   HD static void divmod_u256(const u256& a, const u256& b, u256& q, u256& r) {

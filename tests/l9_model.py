@@ -365,9 +365,9 @@ def check_ec_output(want_pts, words, tag):
 
 # ---- case files ---------------------------------------------------------------------------------------------------------------------
 class Block:
-    def __init__(self, op, mod, cases):
+    def __init__(self, op, mod, cases, nin=NIN, names=NAMES):
         self.op, self.mod, self.cases = op, mod, cases
-        assert cases and all(len(w) == NIN[op] and all(0 <= x < U32 for x in w) for _, w in cases), NAMES[op]
+        assert cases and all(len(w) == nin[op] and all(0 <= x < U32 for x in w) for _, w in cases), names[op]
 
     def classes(self):
         c = {}
@@ -386,17 +386,18 @@ def write_cases(path, blocks):
                 f.write(struct.pack(f"<{len(w)}I", *w))
 
 
-def read_results(path, blocks):
-    """-> per block, one list of output words per case; asserts that the probe returned exactly one record per case"""
+def read_results(path, blocks, nout=NOUT, names=NAMES):
+    """-> per block, one list of output words per case; asserts that the probe returned exactly one record per case.  `nout` / `names`:
+    the result widths and op names of the probe that wrote the file (tests/u256_model.py shares the format)"""
     data = open(path, "rb").read()
     assert len(data) % 4 == 0
     words = struct.unpack(f"<{len(data) // 4}I", data)
     assert words[0] == MAGIC and words[1] == len(blocks)
     pos, res = 2, []
     for b in blocks:
-        assert words[pos: pos + 3] == (b.op, b.mod, len(b.cases)), NAMES[b.op]
+        assert words[pos: pos + 3] == (b.op, b.mod, len(b.cases)), names[b.op]
         pos += 3
-        n = NOUT[b.op]
+        n = nout[b.op]
         res.append([list(words[pos + i * n: pos + (i + 1) * n]) for i in range(len(b.cases))])
         pos += n * len(b.cases)
         assert len(res[-1]) == len(b.cases) and all(len(x) == n for x in res[-1])
@@ -763,17 +764,17 @@ def check_block(b, results):
 
 
 # ---- the probe -----------------------------------------------------------------------------------------------------------------------
-def compile_probe(dirname):
-    exe = os.path.join(str(dirname), "l9_probe")
-    subprocess.run([HIPCC, "-O2", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "-o", exe, os.path.join(ROOT, "tools", "l9_probe.hip")],
+def compile_probe(dirname, name="l9_probe"):
+    exe = os.path.join(str(dirname), name)
+    subprocess.run([HIPCC, "-O2", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "-o", exe, os.path.join(ROOT, "tools", name + ".hip")],
                    check=True, capture_output=True, text=True)
     return exe
 
 
-def run_probe(exe, mode, blocks, dirname, timeout):
+def run_probe(exe, mode, blocks, dirname, timeout, nout=NOUT, names=NAMES):
     """one child process; a non-zero or signal exit fails with the child's stderr; nothing is retried"""
     cases, out = os.path.join(str(dirname), f"cases{mode}.bin"), os.path.join(str(dirname), f"out{mode}.bin")
     write_cases(cases, blocks)
     r = subprocess.run([exe, mode, cases, out], capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, f"l9_probe {mode} exited with {r.returncode}:\n{r.stderr}"
-    return read_results(out, blocks)
+    assert r.returncode == 0, f"{os.path.basename(exe)} {mode} exited with {r.returncode}:\n{r.stderr}"
+    return read_results(out, blocks, nout, names)
