@@ -589,6 +589,16 @@ def trace_nearest(metric, n, dim, P, L):
     return _whole(s, (n + 1) * dim), (ind, res)
 
 
+def trace_nearest_batch(metric, q, n, dim, P, L):
+    """assign the q queries, assign the n database vectors, then nearest_vector(query, vectors) query after query over the same
+    assigned database cells (pipeline.BatchQueryHotPath before its merkle_commitment); -> the map, (indicators (q, n), results (q, dim))"""
+    s = Sym(P, L)
+    qs = [s.assign_witnesses(dim) for _ in range(q)]
+    vs = [s.assign_witnesses(dim) for _ in range(n)]
+    outs = [s.nearest_vector(metric, qq, vs) for qq in qs]
+    return _whole(s, (q + n) * dim), ([o[0] for o in outs], [o[1] for o in outs])
+
+
 def trace_kmeans(metric, n, dim, K, I, P, L):
     s = Sym(P, L)
     vs = [s.assign_witnesses(dim) for _ in range(n)]
@@ -698,6 +708,46 @@ def build_nearest(metric, n, dim, P, L, builder=None, extra_cells=0, finish=True
     sb = Block(s, [s.g_select_by_indicator([ext(k) for k in range(n)], [ext(n + k) for k in range(n)])])
     jd = np.arange(dim, dtype=np.int64)
     res = B.place(sb, sel0 + jd * (1 + 3 * n), np.zeros(dim, dtype=np.int64), np.concatenate([vec.T, np.broadcast_to(ind, (dim, n))], axis=1))[:, 0]
+    if not finish:
+        return B, (ind, res), total
+    return B.finish(), (ind, res)
+
+
+def build_nearest_batch(metric, q, n, dim, P, L, builder=None, extra_cells=0, finish=True):
+    """q x nearest_vector(query_i, vectors) after [queries | vectors] have been assigned, in the stream order of witness.hip
+    (wit_nearest_batch_dev): query i's block — n distances, n - 1 qmin, n is_equal, dim select_by_indicator — starts i blocks behind the
+    first, its lookup cells i runs behind.  Every query's distances copy the same database cells and that query's own; outputs
+    (indicators (q, n), results (q, dim)).  `builder`, `extra_cells`, `finish`: as for build_nearest."""
+    db = _distance_block(metric, dim, P, L)
+    s = Sym(P, L)
+    qm = Block(s, [s.qmin(ext(0), ext(1))])
+    s = Sym(P, L)
+    ie = Block(s, [s.g_is_equal(ext(0), ext(1))])
+    s = Sym(P, L)
+    sb = Block(s, [s.g_select_by_indicator([ext(k) for k in range(n)], [ext(n + k) for k in range(n)])])
+    n_in = (q + n) * dim
+    qmin_off = n * db.n
+    iseq_off = qmin_off + (n - 1) * qm.n
+    sel_off = iseq_off + 12 * n
+    per_q, per_q_l = sel_off + dim * (1 + 3 * n), n * db.n_lk + (n - 1) * qm.n_lk
+    total = n_in + q * per_q
+    B = (builder or _Builder)(total + extra_cells, q * per_q_l)
+    queries = np.arange(q * dim, dtype=np.int64).reshape(q, dim)
+    vec = q * dim + np.arange(n * dim, dtype=np.int64).reshape(n, dim)
+    qq, ii = np.repeat(np.arange(q, dtype=np.int64), n), np.tile(np.arange(n, dtype=np.int64), q)
+    base, lbase = n_in + qq * per_q, qq * per_q_l
+    d = B.place(db, base + ii * db.n, lbase + ii * db.n_lk, np.concatenate([vec[ii], queries[qq]], axis=1))[:, 0].reshape(q, n)
+    acc = np.empty((q, n), dtype=np.int64)
+    acc[:, 0] = d[:, 0]
+    if n > 1:
+        qj, j = np.repeat(np.arange(q, dtype=np.int64), n - 1), np.tile(np.arange(n - 1, dtype=np.int64), q)
+        bases = n_in + qj * per_q + qmin_off + j * qm.n
+        acc[:, 1:] = (bases + qm.outs[0]).reshape(q, n - 1)
+        B.place(qm, bases, qj * per_q_l + n * db.n_lk + j * qm.n_lk, np.stack([acc[:, :-1].reshape(-1), d[:, 1:].reshape(-1)], axis=1))
+    ind = B.place(ie, base + iseq_off + 12 * ii, np.zeros(q * n, dtype=np.int64), np.stack([acc[qq, n - 1], d.reshape(-1)], axis=1))[:, 0].reshape(q, n)
+    qd, jd = np.repeat(np.arange(q, dtype=np.int64), dim), np.tile(np.arange(dim, dtype=np.int64), q)
+    res = B.place(sb, n_in + qd * per_q + sel_off + jd * (1 + 3 * n), np.zeros(q * dim, dtype=np.int64),
+                  np.concatenate([vec.T[jd], ind[qd]], axis=1))[:, 0].reshape(q, dim)
     if not finish:
         return B, (ind, res), total
     return B.finish(), (ind, res)

@@ -681,6 +681,125 @@ __global__ __launch_bounds__(64) void k_nv_select(Streams st, const FpTables* __
   result[j] = s;
 }
 
+// ------------------------------------------------------------------ nearest_vector for a batch of queries over one database
+// (vectordb.rs:122-163 once per query, the calls end to end in the stream).  Query q's block starts q * (cells of one nearest_vector)
+// behind the first; its distances, prefix minima and indicators sit at [q * n, (q + 1) * n) of the value arrays.
+struct NvBatch {
+  uint64_t adv0, lk0;          // first cell / lookup cell of query 0's block
+  uint64_t per_q, per_q_l;     // cells / lookup cells of one nearest_vector
+  uint64_t qmin_off, qmin_loff, iseq_off, sel_off;   // where the closing stages start inside a block
+  uint32_t Q, n, D;
+};
+// qmin(m, x) as a value (vectordb.rs:141-145 folds it over the distances): is_neg(m - x) ? m : x
+__device__ __forceinline__ u256 nv_vmin(const Gadgets& g, const u256& m, const u256& x) {
+  return g.v_is_neg(from_mont<Fr>(fr_sub(m, x))) ? m : x;
+}
+__device__ __forceinline__ u256 wave_shfl_up(const u256& v, int off) {
+  u256 o;
+#pragma unroll
+  for (int k = 0; k < 8; k++) o.w[k] = __shfl_up(v.w[k], off, 64);
+  return o;
+}
+__device__ __forceinline__ u256 wave_bcast(const u256& v, int lane) {
+  u256 o;
+#pragma unroll
+  for (int k = 0; k < 8; k++) o.w[k] = __shfl(v.w[k], lane, 64);
+  return o;
+}
+// The prefix minima of every query's qmin chain: one wavefront per query, an inclusive scan over 64 distances at a time with the
+// running minimum carried from tile to tile.  Over values the range checks admit, v_is_neg(m - x) is a total order and the scan IS the
+// serial fold (ties: equal values, equal bits).  Over anything else (field elements no fixed-point value quantizes to) the relation
+// need not be transitive, so every lane checks the fold's own recurrence pm[i] == qmin(pm[i - 1], d[i]) on what the scan produced —
+// which, with pm[0] == d[0], characterises the serial walk — and a query that fails it is walked serially by lane 0.
+__global__ __launch_bounds__(64) void k_nvb_prefix_min(const FpTables* __restrict__ T, const u256* __restrict__ d, uint32_t n, u256* __restrict__ pm) {
+  const uint32_t q = blockIdx.x, lane = threadIdx.x;
+  const u256* dq = d + (size_t)q * n;
+  u256* pq = pm + (size_t)q * n;
+  WCtx c{};
+  Gadgets g(c);
+  u256 carry = u256_zero();
+  bool ok = true;
+  for (uint32_t c0 = 0; c0 < n; c0 += 64) {
+    const uint32_t i = c0 + lane;
+    const bool live = i < n;
+    const u256 x = dq[live ? i : n - 1];      // padding lanes repeat the last distance: a minimum does not change under it
+    u256 v = x;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const u256 o = wave_shfl_up(v, off);
+      if ((int)lane >= off) v = nv_vmin(g, o, v);
+    }
+    if (c0) v = nv_vmin(g, carry, v);
+    u256 prev = wave_shfl_up(v, 1);
+    if (lane == 0) prev = carry;
+    if (live) {
+      ok = ok && u256_eq(v, i == 0 ? x : nv_vmin(g, prev, x));
+      pq[i] = v;
+    }
+    carry = wave_bcast(v, 63);
+  }
+  if (!__all((int)ok) && lane == 0) {
+    u256 m = dq[0];
+    pq[0] = m;
+    for (uint32_t i = 1; i < n; i++) {
+      m = nv_vmin(g, m, dq[i]);
+      pq[i] = m;
+    }
+  }
+}
+// lanes = (query, link of its chain): qmin(pm[i - 1], d[i]), i = 1 .. n - 1
+__global__ __launch_bounds__(64) void k_nvb_qmin(Streams st, const FpTables* __restrict__ T, NvBatch nb, const u256* __restrict__ d,
+                                                 const u256* __restrict__ pm) {
+  const uint64_t t = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+  const uint32_t links = nb.n - 1;
+  if (t >= (uint64_t)nb.Q * links) return;
+  const uint32_t q = (uint32_t)(t / links), i = (uint32_t)(t % links) + 1;
+  WCtx c = make_ctx(st, T, nb.adv0 + q * nb.per_q + nb.qmin_off + (uint64_t)(i - 1) * T->sz.qmin[0],
+                    nb.lk0 + q * nb.per_q_l + nb.qmin_loff + (uint64_t)(i - 1) * T->sz.qmin[1]);
+  Gadgets g(c);
+  g.fp_qmin(pm[(size_t)q * nb.n + i - 1], d[(size_t)q * nb.n + i]);
+}
+// lanes = (query, vector): is_equal(min_q, d_i)
+__global__ __launch_bounds__(64) void k_nvb_is_equal(Streams st, const FpTables* __restrict__ T, NvBatch nb, const u256* __restrict__ d,
+                                                     const u256* __restrict__ pm, u256* __restrict__ ind) {
+  const uint64_t t = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+  if (t >= (uint64_t)nb.Q * nb.n) return;
+  const uint32_t q = (uint32_t)(t / nb.n), i = (uint32_t)(t % nb.n);
+  WCtx c = make_ctx(st, T, nb.adv0 + q * nb.per_q + nb.iseq_off + 12ull * i, 0);
+  Gadgets g(c);
+  ind[t] = g.g_is_equal(pm[(size_t)q * nb.n + nb.n - 1], d[t]);
+}
+// select_by_indicator per (query, dimension), the walk over the n vectors cut into `S` segments: lanes = (query, segment, dimension),
+// the dimension fastest so that a wavefront reads consecutive elements of one vector.  The running value at a segment's start is the
+// element of the last vector before it whose indicator is set (0 when there is none), found by walking the indicators backwards.
+__global__ __launch_bounds__(64) void k_nvb_select(Streams st, const FpTables* __restrict__ T, NvBatch nb, uint32_t S, const u256* __restrict__ vectors,
+                                                   const u256* __restrict__ ind, u256* __restrict__ result) {
+  const uint64_t t = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+  const uint32_t n = nb.n, D = nb.D;
+  if (t >= (uint64_t)nb.Q * S * D) return;
+  const uint32_t j = (uint32_t)(t % D), sg = (uint32_t)((t / D) % S), q = (uint32_t)(t / ((uint64_t)D * S));
+  const uint32_t i0 = (uint32_t)((uint64_t)n * sg / S), i1 = (uint32_t)((uint64_t)n * (sg + 1) / S);
+  const u256* indq = ind + (size_t)q * n;
+  const uint64_t base = nb.adv0 + q * nb.per_q + nb.sel_off + (uint64_t)j * (1 + 3ull * n);
+  u256 s = u256_zero();
+  for (uint32_t i = i0; i-- > 0;) {
+    if (!u256_is_zero(indq[i])) {
+      s = vectors[(size_t)i * D + j];
+      break;
+    }
+  }
+  WCtx c = make_ctx(st, T, base + (i0 ? 1 + 3ull * i0 : 0), 0);
+  if (i0 == 0) c.push(s, n > 0);
+  for (uint32_t i = i0; i < i1; i++) {
+    u256 a = vectors[(size_t)i * D + j], in = indq[i];
+    if (!u256_is_zero(in)) s = a;
+    c.push(a, false);
+    c.push(in, false);
+    c.push(s, i + 1 < n);
+  }
+  if (sg == S - 1) result[(size_t)q * D + j] = s;
+}
+
 // ------------------------------------------------------------------ kmeans (vectordb.rs:225-362)
 struct KmLayout {
   uint32_t N, D, K;
@@ -1257,6 +1376,70 @@ int wit_nearest_dev(FpEntry* fp, int metric, const u256* query, const u256* vect
   return inv_list_fixup(st);
 }
 
+// what one batch call may hold (include/vdb.h VDB_NEAREST_BATCH_MAX_*): the instance numbers of the distance kernels and the lane numbers
+// of the closing stages are 32-bit, the work space is 160 B per (query, vector), and the deferred-inversion counter is 32-bit (an
+// is_zero block of eight cells defers at most one inverse, so 2^34 cells stay far below its wrap)
+static int nv_batch_fits(size_t Q, size_t n, size_t dim, uint64_t per_q) {
+  if (Q > VDB_NEAREST_BATCH_MAX_INSTANCES || n > VDB_NEAREST_BATCH_MAX_INSTANCES / Q || dim > VDB_NEAREST_BATCH_MAX_INSTANCES / Q ||
+      per_q > VDB_NEAREST_BATCH_MAX_CELLS / Q) {
+    set_error("nearest_vector batch too large for one call: n_queries * n and n_queries * dim at most 2^24, cells at most 2^34 (include/vdb.h)");
+    return VDB_ERR_ARG;
+  }
+  return VDB_OK;
+}
+// segments of the select's walk over the n vectors: enough lanes to give every CU a few wavefronts, no segment below eight vectors
+static uint32_t nv_select_segments(size_t Q, size_t n, size_t dim) {
+  const uint64_t lanes = (uint64_t)Q * dim, want = (uint64_t)ctx().cu_count * 4 * 64;
+  uint64_t s = (want + lanes - 1) / lanes, cap = n / 8;
+  if (s > cap) s = cap;
+  return s < 1 ? 1u : (uint32_t)s;
+}
+// Q x nearest_vector(query_q, vectors), block q at adv_off + q * (cells of one): the distances of all queries in one run_distances
+// (instance t = q * n + i is distance(vector_i, query_q)), then one launch per closing stage — the launch count does not depend on Q
+int wit_nearest_batch_dev(FpEntry* fp, int metric, const u256* queries, const u256* vectors, size_t Q, size_t n, size_t dim, Streams st,
+                          uint64_t adv_off, uint64_t lk_off, u256* ind, u256* result) {
+  DistLayout dl;
+  NvLayout nl;
+  TRY(nv_layout(fp, metric, n, dim, &dl, &nl));
+  TRY(nv_batch_fits(Q, n, dim, nl.total));
+  TRY(inv_list_attach(st, Q * nl.total));
+  TRY(set_winv(st, fp->dev));
+  const size_t inst = Q * n;
+  InstMap im{adv_off, lk_off, (uint32_t)n, nl.total, nl.total_l, (uint32_t)n, (uint32_t)n};  // (vector_{t % n}, query_{t / n})
+  u256* mid = (u256*)scratch_get(0, (inst * 5 + 8) * sizeof(u256));
+  if (!mid) return VDB_ERR_OOM;
+  u256* dist = mid + 3 * inst;
+  u256* pm = dist + inst;
+  TRY(run_distances(st, fp, dl, im, (uint32_t)inst, vectors, queries, mid, dist));
+  const NvBatch nb{adv_off, lk_off, nl.total, nl.total_l, nl.dist, nl.dist_l, nl.dist + nl.qmin, nl.dist + nl.qmin + nl.iseq, (uint32_t)Q, (uint32_t)n,
+                   (uint32_t)dim};
+  hipStream_t s = ctx().stream;
+  {
+    VDB_PROF("k_nvb_prefix_min");
+    hipLaunchKernelGGL(k_nvb_prefix_min, dim3((unsigned)Q), dim3(64), 0, s, fp->dev, dist, (uint32_t)n, pm);
+  }
+  VDB_LAUNCH_CHECK();
+  if (n > 1) {
+    {
+      VDB_PROF("k_nvb_qmin");
+      hipLaunchKernelGGL(k_nvb_qmin, dim3((unsigned)((Q * (n - 1) + 63) / 64)), dim3(64), 0, s, st, fp->dev, nb, dist, pm);
+    }
+    VDB_LAUNCH_CHECK();
+  }
+  {
+    VDB_PROF("k_nvb_is_equal");
+    hipLaunchKernelGGL(k_nvb_is_equal, dim3((unsigned)((inst + 63) / 64)), dim3(64), 0, s, st, fp->dev, nb, dist, pm, ind);
+  }
+  VDB_LAUNCH_CHECK();
+  {
+    const uint32_t S = nv_select_segments(Q, n, dim);
+    VDB_PROF("k_nvb_select");
+    hipLaunchKernelGGL(k_nvb_select, dim3((unsigned)((Q * dim * S + 63) / 64)), dim3(64), 0, s, st, fp->dev, nb, S, vectors, ind, result);
+  }
+  VDB_LAUNCH_CHECK();
+  return inv_list_fixup(st);
+}
+
 static int km_layout(FpEntry* fp, int metric, size_t n, size_t dim, size_t K, DistLayout* dl, KmLayout* kl) {
   TRY(dist_layout(fp->host, metric, dim, dl));
   const Sizes& z = fp->host.sz;
@@ -1654,6 +1837,57 @@ int vdb_wit_nearest_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* query_
   // the cells, exit early outside it — while every rank computes every value (the N distances, the short minimum chain)
   Streams st{as_u256(stream_dev), selector_dev, as_u256(lookup_dev), derr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], g_win[2], g_win[3]};
   TRY(wit_nearest_dev(fp, metric, as_u256(query_dev), as_u256(vectors_dev), n, dim, st, 0, 0, as_u256(indicator_dev), as_u256(result_dev)));
+  return check_err_flag(derr);
+}
+
+// nearest_vector (vectordb.rs:122-163) for n_queries queries over one database, the calls end to end in the streams
+int vdb_wit_nearest_batch_size(int metric, uint32_t P, uint32_t L, size_t n_queries, size_t n, size_t dim, uint64_t* cells, uint64_t* lookups) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(n_queries > 0 && n > 0, "no query or empty database");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  DistLayout dl;
+  NvLayout nl;
+  TRY(nv_layout(fp, metric, n, dim, &dl, &nl));
+  TRY(nv_batch_fits(n_queries, n, dim, nl.total));
+  if (cells) *cells = n_queries * nl.total;
+  if (lookups) *lookups = n_queries * nl.total_l;
+  return VDB_OK;
+}
+int vdb_wit_nearest_batch(int metric, uint32_t P, uint32_t L, const vdb_fr* queries, const vdb_fr* vectors, size_t n_queries, size_t n, size_t dim,
+                          vdb_fr* stream_out, vdb_fr* lookup_out, uint8_t* selector_out, vdb_fr* indicators_out, vdb_fr* results_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(queries && vectors && n_queries > 0 && n > 0 && dim > 0, "null pointer or empty input");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  uint64_t cells, lookups;
+  TRY(vdb_wit_nearest_batch_size(metric, P, L, n_queries, n, dim, &cells, &lookups));
+  DevBuf dq, dv, dind, dres;
+  HostStreams hs;
+  TRY(upload(dq, queries, n_queries * dim * sizeof(u256)));
+  TRY(upload(dv, vectors, n * dim * sizeof(u256)));
+  TRY(dind.alloc(n_queries * n * sizeof(u256)));
+  TRY(dres.alloc(n_queries * dim * sizeof(u256)));
+  TRY(hs.init(cells, lookups, selector_out != nullptr));
+  TRY(wit_nearest_batch_dev(fp, metric, dq.as<u256>(), dv.as<u256>(), n_queries, n, dim, hs.st, 0, 0, dind.as<u256>(), dres.as<u256>()));
+  TRY(download(indicators_out, dind.p, n_queries * n * sizeof(u256)));
+  TRY(download(results_out, dres.p, n_queries * dim * sizeof(u256)));
+  return hs.finish(stream_out, lookup_out, selector_out, cells, lookups);
+}
+int vdb_wit_nearest_batch_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* queries_dev, const vdb_fr* vectors_dev, size_t n_queries, size_t n,
+                              size_t dim, vdb_fr* stream_dev, vdb_fr* lookup_dev, uint8_t* selector_dev, vdb_fr* indicators_dev, vdb_fr* results_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(queries_dev && vectors_dev && stream_dev && lookup_dev && indicators_dev && results_dev && n_queries > 0 && n > 0 && dim > 0,
+          "null pointer or empty input");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  int* derr = (int*)scratch_get(1, 64);
+  if (!derr) return VDB_ERR_OOM;
+  VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
+  // the rank window as in vdb_wit_nearest_dev: every rank computes every value, a rank stores the cells inside its window
+  Streams st{as_u256(stream_dev), selector_dev, as_u256(lookup_dev), derr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], g_win[2], g_win[3]};
+  TRY(wit_nearest_batch_dev(fp, metric, as_u256(queries_dev), as_u256(vectors_dev), n_queries, n, dim, st, 0, 0, as_u256(indicators_dev),
+                            as_u256(results_dev)));
   return check_err_flag(derr);
 }
 

@@ -849,6 +849,71 @@ class QueryHotPath(NearestHotPath):
         return bld.finish(), list(res) + [root], root      # examples/query.rs:58, :69: the result vector, then the root
 
 
+class BatchQueryHotPath(HotPath):
+    """A batch of queries against ONE committed database in one proof: the closure a user of the reference's chips writes for it —
+    assign the q queries, assign the n database vectors, nearest_vector(query, database) per query (src/gadget/vectordb.rs:122-163),
+    merkle_commitment(database) once (:165-223) — i.e. examples/query.rs:32-73 with its nearest_vector repeated, so that q queries pay
+    for the database commitment once.  Stream: [queries | vectors | nearest_vector of query 0 | ... | of query q - 1 |
+    merkle_commitment]; the lookup cells are the nearest_vector runs in query order; public, in make_public order: the q result
+    vectors, then the root (the queries stay private, as in the example).  With q = 1 the circuit is QueryHotPath's.  All q
+    nearest_vector blocks come from one call (vdb_wit_nearest_batch_dev: the launch count does not depend on q); sharded like
+    NearestHotPath — every rank computes every value, a rank stores the cells of its own columns."""
+
+    def __init__(self, q=8, n=64, dim=128, k=16, P=48, L=13, metric="euclidean", seed=20260002, tau=None, col_shard=(0, 1), vectors=None,
+                 blind_seed=None, params=None):
+        """`vectors`: (q + n, dim) f64 rows, the queries first"""
+        if q < 1:
+            raise ValueError("a batch holds at least one query")
+        super().__init__(n, dim, k, P, L, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors, blind_seed=blind_seed, params=params)
+        self.q = q
+        self.metric = api.METRICS[metric]
+        self.metric_name = metric
+
+    def n_input_rows(self):
+        return self.q + self.n
+
+    def _input_vectors(self):
+        # the database is QueryHotPath's for the same seed, and with q = 1 so is the query
+        vec, seed = sift_like_vectors(self.seed, self.n, self.dim)
+        queries, _ = sift_like_vectors(seed + 1000, self.q, self.dim)
+        return np.concatenate([queries, vec]), seed
+
+    def _circuit_size(self):
+        cells, lk = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self.lib.vdb_wit_nearest_batch_size(self.metric, self.P, self.L, self.q, self.n, self.dim, ctypes.byref(cells), ctypes.byref(lk)))
+        self.nearest_cells, self.merkle_cells = cells.value, _merkle_cells(self)
+        return (self.q + self.n) * self.dim, self.nearest_cells + self.merkle_cells, lk.value
+
+    def _alloc_outputs(self):
+        self.d_ind = self._output(self.q * self.n * 32)
+        self.d_root = self._output(32)
+        self.d_pub = self._output((self.q * self.dim + 1) * 32)     # [result vectors | root]: the public statement, in make_public order
+
+    def _emit(self, sel):
+        at, d_db = self.n_in, self.d_vec.at(self.q * self.dim * 32)
+        with self._window(sel, at):
+            check(self.lib.vdb_wit_nearest_batch_dev(self.metric, self.P, self.L, self.d_vec.ptr, d_db, self.q, self.n, self.dim, self.d_stream.at(at * B),
+                                                     self.d_lookup.ptr, self._sel_at(sel, at), self.d_ind.ptr, self.d_pub.ptr))
+        _merkle_trace(self, d_db, at + self.nearest_cells, sel)
+        check(self.lib.vdb_memcpy_d2d(self.d_pub.at(self.q * self.dim * 32), self.d_root.ptr, ctypes.c_size_t(32)))
+
+    def public_values_dev(self):
+        return self.d_pub.ptr, self.q * self.dim + 1     # make_public.extend(result) per query (examples/query.rs:58), then push(root) (:69)
+
+    def results(self):
+        return self.d_ind.download((self.q, self.n, 4)), self.d_pub.download((self.q, self.dim, 4)), self.d_root.download((4,))
+
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder, place_merkle
+        bld, (_ind, res), used = CS.build_nearest_batch(self.metric_name, self.q, self.n, self.dim, self.P, self.L, builder=DeviceBuilder,
+                                                        extra_cells=self.merkle_cells, finish=False)
+        assert used == self.n_in + self.nearest_cells
+        root, end = place_merkle(bld, self.n, self.dim, used, self.q * self.dim, functools.partial(self._fetch_flags, d_flags), self._fetch)
+        assert end == self.n_cells
+        return bld.finish(), [int(c) for c in np.asarray(res).reshape(-1)] + [root], root
+
+
 class DistancesHotPath(HotPath):
     """The reference's two-vector circuits through the same hot path: examples/distances.rs:29-59 (assign a, assign b, then
     euclidean, manhattan, cosine and hamming distance of the same two vectors, each made public) and examples/euclid.rs:26-46 (ten Euclidean distances of one pair, nothing public:

@@ -165,6 +165,25 @@ int vdb_wit_nearest(int metric, uint32_t precision_bits, uint32_t lookup_bits, c
  * a rank stores the cells of its own columns, every rank computes every value (the n distances, the short minimum chain) */
 int vdb_wit_nearest_dev(int metric, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *query_dev, const vdb_fr *vectors_dev, size_t n, size_t dim,
                         vdb_fr *stream_dev, vdb_fr *lookup_dev, uint8_t *selector_dev, vdb_fr *indicator_dev, vdb_fr *result_dev);
+/* nearest_vector for a batch of queries over ONE database (src/gadget/vectordb.rs:122-163 called once per query, query after query, as a
+ * closure over the reference's chips would): the stream holds n_queries blocks of vdb_wit_nearest's cells end to end, the lookup stream
+ * their lookup runs in query order; queries n_queries x dim, indicators_out n_queries x n raw 0/1 bits, results_out n_queries x dim.
+ * Bit-identical to n_queries calls of vdb_wit_nearest at the matching offsets, with a number of kernel launches that does not depend on
+ * n_queries.  The _dev form honours vdb_wit_set_window like vdb_wit_nearest_dev.
+ * Limits of one call (VDB_ERR_ARG beyond them, as for n_queries == 0): n_queries * n and n_queries * dim at most
+ * VDB_NEAREST_BATCH_MAX_INSTANCES (32-bit instance numbers; 160 B of work space per (query, vector)), n_queries * cells of one
+ * nearest_vector at most VDB_NEAREST_BATCH_MAX_CELLS.  The deferred-inversion list holds 16 M entries whatever the batch: beyond them
+ * inverse cells are computed in line — slower, the same stream.  VDB_ERR_OOM when the work space cannot be allocated. */
+#define VDB_NEAREST_BATCH_MAX_INSTANCES ((size_t)1 << 24)
+#define VDB_NEAREST_BATCH_MAX_CELLS ((uint64_t)1 << 34)
+int vdb_wit_nearest_batch_size(int metric, uint32_t precision_bits, uint32_t lookup_bits, size_t n_queries, size_t n, size_t dim, uint64_t *cells,
+                               uint64_t *lookups);
+int vdb_wit_nearest_batch(int metric, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *queries, const vdb_fr *vectors, size_t n_queries,
+                          size_t n, size_t dim, vdb_fr *stream_out, vdb_fr *lookup_out, uint8_t *selector_out, vdb_fr *indicators_out,
+                          vdb_fr *results_out);
+int vdb_wit_nearest_batch_dev(int metric, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *queries_dev, const vdb_fr *vectors_dev,
+                              size_t n_queries, size_t n, size_t dim, vdb_fr *stream_dev, vdb_fr *lookup_dev, uint8_t *selector_dev,
+                              vdb_fr *indicators_dev, vdb_fr *results_dev);
 /* VectorDBChip::kmeans::<K, I> (src/gadget/vectordb.rs:225-362): centroids K x dim, indicators n x K
  * (quantized 1.0 / 0).  zero_cached: Context::load_zero already called earlier in this context. */
 int vdb_wit_kmeans_size(int metric, uint32_t precision_bits, uint32_t lookup_bits, size_t n, size_t dim, size_t K, size_t I, int zero_cached,
