@@ -375,6 +375,28 @@ def wit_nearest_batch(metric, queries, vectors, P=48, L=13, selectors=False):
     return dict(stream=stream, lookup=lookup, **_split_flags(sel), indicators=ind, results=res)
 
 
+def wit_nearest_topk(metric, queries, vectors, topk, P=48, L=13, selectors=False):
+    """the `topk` nearest rows of the database `vectors` (n, dim, 4) for every row of `queries` (q, dim, 4), nearest first
+    (vdb_wit_nearest_topk: nearest_vector's closing stages once per round, a round's winners masked before the next; on a tie every
+    tied row is a winner of that round and its result is the last of them): dict(stream, lookup, selectors, indicators (q, topk, n, 4),
+    results (q, topk, dim, 4))"""
+    lib = _lib.init()
+    queries, vectors = _fr(queries), _fr(vectors)
+    q, n, dim = queries.shape[0], vectors.shape[0], vectors.shape[1]
+    assert queries.shape[1] == dim
+    cells, lk = _u64(), _u64()
+    check(lib.vdb_wit_nearest_topk_size(METRICS[metric], ctypes.c_uint32(P), ctypes.c_uint32(L), _sz(q), _sz(n), _sz(dim), _sz(topk), ctypes.byref(cells),
+                                        ctypes.byref(lk)))
+    stream = np.zeros((cells.value, 4), dtype=np.uint64)
+    lookup = np.zeros((lk.value, 4), dtype=np.uint64)
+    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
+    ind = np.zeros((q, topk, n, 4), dtype=np.uint64)
+    res = np.zeros((q, topk, dim, 4), dtype=np.uint64)
+    check(lib.vdb_wit_nearest_topk(METRICS[metric], ctypes.c_uint32(P), ctypes.c_uint32(L), _p(queries), _p(vectors), _sz(q), _sz(n), _sz(dim), _sz(topk),
+                                   _p(stream), _p(lookup), _p(sel) if selectors else None, _p(ind), _p(res)))
+    return dict(stream=stream, lookup=lookup, **_split_flags(sel), indicators=ind, results=res)
+
+
 def wit_kmeans(metric, vectors, K, I, P=48, L=13, zero_cached=False, selectors=False):
     lib = _lib.init()
     vectors = _fr(vectors)

@@ -462,6 +462,25 @@ class Sym:
         res = [self.g_select_by_indicator([v[j] for v in vectors], ind) for j in range(len(query))]
         return ind, res
 
+    def nearest_topk(self, metric, query, vectors, topk):
+        """the topk nearest vectors (include/vdb.h vdb_wit_nearest_topk): nearest_vector's distances, then per round its qmin chain,
+        is_equal and select_by_indicator over the entries the earlier rounds left, every winner replaced by Constant(M), M = 2^(2P) - 1,
+        through gate.select before the next round; -> (indicators per round, results per round)"""
+        assert 1 <= topk <= len(vectors)
+        cur = [self.distance(metric, v, query) for v in vectors]
+        big = C((1 << (2 * self.P)) - 1)
+        inds, ress = [], []
+        for r in range(topk):
+            m = cur[0]
+            for d in cur[1:]:
+                m = self.qmin(m, d)
+            ind = [self.g_is_equal(m, d) for d in cur]
+            ress.append([self.g_select_by_indicator([v[j] for v in vectors], ind) for j in range(len(query))])
+            inds.append(ind)
+            if r + 1 < topk:
+                cur = [self.g_select(big, d, i) for d, i in zip(cur, ind)]
+        return inds, ress
+
     def kmeans(self, metric, vectors, K, I):                 # :225-362, distance(c, v)
         one = self.load_constant(quantize(1.0, self.P))
         zero = self.load_constant(0)
@@ -596,6 +615,16 @@ def trace_nearest_batch(metric, q, n, dim, P, L):
     qs = [s.assign_witnesses(dim) for _ in range(q)]
     vs = [s.assign_witnesses(dim) for _ in range(n)]
     outs = [s.nearest_vector(metric, qq, vs) for qq in qs]
+    return _whole(s, (q + n) * dim), ([o[0] for o in outs], [o[1] for o in outs])
+
+
+def trace_nearest_topk(metric, q, n, dim, topk, P, L):
+    """assign the q queries, assign the n database vectors, then Sym.nearest_topk query after query over the same assigned database
+    cells (pipeline.TopKQueryHotPath before its merkle_commitment); -> the map, (indicators (q, topk, n), results (q, topk, dim))"""
+    s = Sym(P, L)
+    qs = [s.assign_witnesses(dim) for _ in range(q)]
+    vs = [s.assign_witnesses(dim) for _ in range(n)]
+    outs = [s.nearest_topk(metric, qq, vs, topk) for qq in qs]
     return _whole(s, (q + n) * dim), ([o[0] for o in outs], [o[1] for o in outs])
 
 
@@ -751,6 +780,63 @@ def build_nearest_batch(metric, q, n, dim, P, L, builder=None, extra_cells=0, fi
     if not finish:
         return B, (ind, res), total
     return B.finish(), (ind, res)
+
+
+def build_nearest_topk(metric, q, n, dim, topk, P, L, builder=None, extra_cells=0, finish=True):
+    """q x Sym.nearest_topk(query_i, vectors, topk) after [queries | vectors] have been assigned, in the stream order of witness.hip
+    (wit_nearest_topk_dev): query i's block is its n distances, then per round n - 1 qmin, n is_equal, dim select_by_indicator and —
+    before every round but the first — the n select(Constant(M), cur, ind) of the round before; the lookup cells are the distance runs,
+    then the qmin runs round by round.  M is a constant of the map (a fixed-column value), tied to the cell that holds it in every
+    select.  Outputs (indicators (q, topk, n), results (q, topk, dim)).  `builder`, `extra_cells`, `finish`: as for build_nearest."""
+    if not 1 <= topk <= n:
+        raise ValueError("topk must be at least 1 and at most n")
+    db = _distance_block(metric, dim, P, L)
+    s = Sym(P, L)
+    qm = Block(s, [s.qmin(ext(0), ext(1))])
+    s = Sym(P, L)
+    ie = Block(s, [s.g_is_equal(ext(0), ext(1))])
+    s = Sym(P, L)
+    sb = Block(s, [s.g_select_by_indicator([ext(k) for k in range(n)], [ext(n + k) for k in range(n)])])
+    s = Sym(P, L)
+    mk = Block(s, [s.g_select(C((1 << (2 * P)) - 1), ext(0), ext(1))])
+    n_in = (q + n) * dim
+    rounds_off, rounds_loff = n * db.n, n * db.n_lk
+    iseq_off = (n - 1) * qm.n
+    sel_off = iseq_off + ie.n * n
+    mask_off = sel_off + dim * sb.n
+    per_r, per_r_l = mask_off + mk.n * n, (n - 1) * qm.n_lk
+    per_q, per_q_l = rounds_off + topk * per_r - mk.n * n, rounds_loff + topk * per_r_l
+    total = n_in + q * per_q
+    B = (builder or _Builder)(total + extra_cells, q * per_q_l)
+    queries = np.arange(q * dim, dtype=np.int64).reshape(q, dim)
+    vec = q * dim + np.arange(n * dim, dtype=np.int64).reshape(n, dim)
+    qq, ii = np.repeat(np.arange(q, dtype=np.int64), n), np.tile(np.arange(n, dtype=np.int64), q)
+    base, lbase = n_in + qq * per_q, qq * per_q_l
+    cur = B.place(db, base + ii * db.n, lbase + ii * db.n_lk, np.concatenate([vec[ii], queries[qq]], axis=1))[:, 0].reshape(q, n)
+    qj, j = np.repeat(np.arange(q, dtype=np.int64), n - 1), np.tile(np.arange(n - 1, dtype=np.int64), q)
+    qd, jd = np.repeat(np.arange(q, dtype=np.int64), dim), np.tile(np.arange(dim, dtype=np.int64), q)
+    inds, ress = [], []
+    for r in range(topk):
+        rbase, rlbase = rounds_off + r * per_r, rounds_loff + r * per_r_l
+        acc = np.empty((q, n), dtype=np.int64)
+        acc[:, 0] = cur[:, 0]
+        if n > 1:
+            bases = n_in + qj * per_q + rbase + j * qm.n
+            acc[:, 1:] = (bases + qm.outs[0]).reshape(q, n - 1)
+            B.place(qm, bases, qj * per_q_l + rlbase + j * qm.n_lk, np.stack([acc[:, :-1].reshape(-1), cur[:, 1:].reshape(-1)], axis=1))
+        ind = B.place(ie, base + rbase + iseq_off + ie.n * ii, np.zeros(q * n, dtype=np.int64),
+                      np.stack([acc[qq, n - 1], cur.reshape(-1)], axis=1))[:, 0].reshape(q, n)
+        res = B.place(sb, n_in + qd * per_q + rbase + sel_off + jd * sb.n, np.zeros(q * dim, dtype=np.int64),
+                      np.concatenate([vec.T[jd], ind[qd]], axis=1))[:, 0].reshape(q, dim)
+        inds.append(ind)
+        ress.append(res)
+        if r + 1 < topk:
+            cur = B.place(mk, base + rbase + mask_off + mk.n * ii, np.zeros(q * n, dtype=np.int64),
+                          np.stack([cur.reshape(-1), ind.reshape(-1)], axis=1))[:, 0].reshape(q, n)
+    outs = (np.stack(inds, axis=1), np.stack(ress, axis=1))
+    if not finish:
+        return B, outs, total
+    return B.finish(), outs
 
 
 def build_kmeans(metric, n, dim, K, I, P, L, builder=None):

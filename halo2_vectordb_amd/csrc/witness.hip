@@ -800,6 +800,146 @@ __global__ __launch_bounds__(64) void k_nvb_select(Streams st, const FpTables* _
   if (sg == S - 1) result[(size_t)q * D + j] = s;
 }
 
+// ------------------------------------------------------------------ the t nearest vectors of every query (top-k over one database)
+// Per query: the n distances, then t rounds of [n - 1 qmin | n is_equal | D select_by_indicator | n select(Constant(M), cur_i, ind_i)],
+// the last round without its select(M, ..) blocks.  M = 2^(2P) - 1 takes a round's winners out of the next round's minimum.  Round r of
+// query q keeps its prefix minima at [(q * t + r) * n, + n) of `pm`; `rnd[q * n + i]` is the first round whose mask replaced entry i
+// (NV_UNMASKED: none), so that the entry a round works on is cur_r,i = rnd < r ? M : d_i.
+constexpr uint32_t NV_UNMASKED = 0xffffffffu;
+struct NvTopk {
+  uint64_t adv0, lk0;          // first cell / lookup cell of query 0's block
+  uint64_t per_q, per_q_l;     // cells / lookup cells of one query's block
+  uint64_t rounds_off, rounds_loff, per_r, per_r_l;   // where round 0 starts inside a block; cells / lookup cells of a round that masks
+  uint64_t iseq_off, sel_off, mask_off;               // where the stages after the qmin chain start inside a round
+  uint32_t Q, n, D, t;
+};
+__device__ __forceinline__ u256 nvt_mask_value(const FpTables* T) { return fr_sub(T->pow2[2 * T->P], mont_one<Fr>()); }
+__device__ __forceinline__ u256 nvt_cur(const u256* __restrict__ dq, const uint32_t* __restrict__ rq, uint32_t i, uint32_t r, const u256& M) {
+  return rq[i] < r ? M : dq[i];
+}
+// All t rounds of a query's values, one wavefront per query: per round the tiled scan of k_nvb_prefix_min over the entries the earlier
+// rounds left (with its check of the serial recurrence and the serial walk where it fails), the round's minimum to every lane, and the
+// entries whose bits equal it marked as masked from the next round on.  Lanes past the end of a tile hold M: a live lane only ever
+// reads lower lanes, and the carry is taken from a full tile.
+__global__ __launch_bounds__(64) void k_nvt_rounds(const FpTables* __restrict__ T, const u256* __restrict__ d, uint32_t n, uint32_t t,
+                                                   u256* __restrict__ pm, uint32_t* __restrict__ rnd) {
+  const uint32_t q = blockIdx.x, lane = threadIdx.x;
+  const u256* dq = d + (size_t)q * n;
+  uint32_t* rq = rnd + (size_t)q * n;
+  WCtx c{};
+  Gadgets g(c);
+  const u256 M = nvt_mask_value(T);
+  for (uint32_t i = lane; i < n; i += 64) rq[i] = NV_UNMASKED;
+  for (uint32_t r = 0; r < t; r++) {
+    u256* pq = pm + ((size_t)q * t + r) * n;
+    u256 carry = u256_zero();
+    bool ok = true;
+    for (uint32_t c0 = 0; c0 < n; c0 += 64) {
+      const uint32_t i = c0 + lane;
+      const bool live = i < n;
+      const u256 x = live ? nvt_cur(dq, rq, i, r, M) : M;
+      u256 v = x;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const u256 o = wave_shfl_up(v, off);
+        if ((int)lane >= off) v = nv_vmin(g, o, v);
+      }
+      if (c0) v = nv_vmin(g, carry, v);
+      u256 prev = wave_shfl_up(v, 1);
+      if (lane == 0) prev = carry;
+      if (live) {
+        ok = ok && u256_eq(v, i == 0 ? x : nv_vmin(g, prev, x));
+        pq[i] = v;
+      }
+      carry = wave_bcast(v, n - c0 < 64 ? (int)(n - c0 - 1) : 63);
+    }
+    u256 m = carry;
+    if (!__all((int)ok)) {
+      if (lane == 0) {
+        m = nvt_cur(dq, rq, 0, r, M);
+        pq[0] = m;
+        for (uint32_t i = 1; i < n; i++) {
+          m = nv_vmin(g, m, nvt_cur(dq, rq, i, r, M));
+          pq[i] = m;
+        }
+      }
+      m = wave_bcast(m, 0);
+    }
+    if (r + 1 < t) {
+      for (uint32_t i = lane; i < n; i += 64)
+        if (rq[i] == NV_UNMASKED && u256_eq(dq[i], m)) rq[i] = r;
+      __threadfence_block();   // lane 0's serial walk of a later round reads what the other lanes marked
+      __syncthreads();
+    }
+  }
+}
+// lanes = (query, round, link of the round's chain): qmin(pm[i - 1], cur_i), i = 1 .. n - 1
+__global__ __launch_bounds__(64) void k_nvt_qmin(Streams st, const FpTables* __restrict__ T, NvTopk nt, const u256* __restrict__ d,
+                                                 const u256* __restrict__ pm, const uint32_t* __restrict__ rnd) {
+  const uint64_t th = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+  const uint32_t links = nt.n - 1;
+  if (th >= (uint64_t)nt.Q * nt.t * links) return;
+  const uint32_t i = (uint32_t)(th % links) + 1, r = (uint32_t)((th / links) % nt.t), q = (uint32_t)(th / ((uint64_t)links * nt.t));
+  WCtx c = make_ctx(st, T, nt.adv0 + q * nt.per_q + nt.rounds_off + r * nt.per_r + (uint64_t)(i - 1) * T->sz.qmin[0],
+                    nt.lk0 + q * nt.per_q_l + nt.rounds_loff + r * nt.per_r_l + (uint64_t)(i - 1) * T->sz.qmin[1]);
+  Gadgets g(c);
+  const u256 M = nvt_mask_value(T);
+  g.fp_qmin(pm[((size_t)q * nt.t + r) * nt.n + i - 1], nvt_cur(d + (size_t)q * nt.n, rnd + (size_t)q * nt.n, i, r, M));
+}
+// lanes = (query, round, vector): is_equal(min_r, cur_i)
+__global__ __launch_bounds__(64) void k_nvt_is_equal(Streams st, const FpTables* __restrict__ T, NvTopk nt, const u256* __restrict__ d,
+                                                     const u256* __restrict__ pm, const uint32_t* __restrict__ rnd, u256* __restrict__ ind) {
+  const uint64_t th = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+  if (th >= (uint64_t)nt.Q * nt.t * nt.n) return;
+  const uint32_t i = (uint32_t)(th % nt.n), r = (uint32_t)((th / nt.n) % nt.t), q = (uint32_t)(th / ((uint64_t)nt.n * nt.t));
+  WCtx c = make_ctx(st, T, nt.adv0 + q * nt.per_q + nt.rounds_off + r * nt.per_r + nt.iseq_off + 12ull * i, 0);
+  Gadgets g(c);
+  const u256 M = nvt_mask_value(T);
+  ind[th] = g.g_is_equal(pm[((size_t)q * nt.t + r) * nt.n + nt.n - 1], nvt_cur(d + (size_t)q * nt.n, rnd + (size_t)q * nt.n, i, r, M));
+}
+// lanes = (query, round before the last, vector): select(Constant(M), cur_i, ind_i), the entry the next round works on
+__global__ __launch_bounds__(64) void k_nvt_mask(Streams st, const FpTables* __restrict__ T, NvTopk nt, const u256* __restrict__ d,
+                                                 const uint32_t* __restrict__ rnd, const u256* __restrict__ ind) {
+  const uint64_t th = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+  const uint32_t masking = nt.t - 1;
+  if (th >= (uint64_t)nt.Q * masking * nt.n) return;
+  const uint32_t i = (uint32_t)(th % nt.n), r = (uint32_t)((th / nt.n) % masking), q = (uint32_t)(th / ((uint64_t)nt.n * masking));
+  WCtx c = make_ctx(st, T, nt.adv0 + q * nt.per_q + nt.rounds_off + r * nt.per_r + nt.mask_off + 8ull * i, 0);
+  Gadgets g(c);
+  const u256 M = nvt_mask_value(T);
+  g.g_select(M, nvt_cur(d + (size_t)q * nt.n, rnd + (size_t)q * nt.n, i, r, M), ind[((size_t)q * nt.t + r) * nt.n + i]);
+}
+// select_by_indicator per (query, round, dimension), the walk cut into `S` segments as in k_nvb_select: lanes = (query, round, segment,
+// dimension), the dimension fastest
+__global__ __launch_bounds__(64) void k_nvt_select(Streams st, const FpTables* __restrict__ T, NvTopk nt, uint32_t S, const u256* __restrict__ vectors,
+                                                   const u256* __restrict__ ind, u256* __restrict__ result) {
+  const uint64_t th = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+  const uint32_t n = nt.n, D = nt.D;
+  if (th >= (uint64_t)nt.Q * nt.t * S * D) return;
+  const uint32_t j = (uint32_t)(th % D), sg = (uint32_t)((th / D) % S), qr = (uint32_t)(th / ((uint64_t)D * S));
+  const uint32_t q = qr / nt.t, r = qr % nt.t;
+  const uint32_t i0 = (uint32_t)((uint64_t)n * sg / S), i1 = (uint32_t)((uint64_t)n * (sg + 1) / S);
+  const u256* indq = ind + (size_t)qr * n;
+  const uint64_t base = nt.adv0 + q * nt.per_q + nt.rounds_off + r * nt.per_r + nt.sel_off + (uint64_t)j * (1 + 3ull * n);
+  u256 s = u256_zero();
+  for (uint32_t i = i0; i-- > 0;) {
+    if (!u256_is_zero(indq[i])) {
+      s = vectors[(size_t)i * D + j];
+      break;
+    }
+  }
+  WCtx c = make_ctx(st, T, base + (i0 ? 1 + 3ull * i0 : 0), 0);
+  if (i0 == 0) c.push(s, n > 0);
+  for (uint32_t i = i0; i < i1; i++) {
+    u256 a = vectors[(size_t)i * D + j], in = indq[i];
+    if (!u256_is_zero(in)) s = a;
+    c.push(a, false);
+    c.push(in, false);
+    c.push(s, i + 1 < n);
+  }
+  if (sg == S - 1) result[(size_t)qr * D + j] = s;
+}
+
 // ------------------------------------------------------------------ kmeans (vectordb.rs:225-362)
 struct KmLayout {
   uint32_t N, D, K;
@@ -1440,6 +1580,89 @@ int wit_nearest_batch_dev(FpEntry* fp, int metric, const u256* queries, const u2
   return inv_list_fixup(st);
 }
 
+// the block of one query with `topk` rounds (include/vdb.h vdb_wit_nearest_topk): NvLayout's stages, the closing ones once per round
+struct NvTopkLayout {
+  uint64_t per_r, mask, total, total_l;
+};
+static void nv_topk_layout(const NvLayout& nl, size_t n, size_t topk, NvTopkLayout* o) {
+  o->mask = 8ull * n;
+  o->per_r = nl.qmin + nl.iseq + nl.sel + o->mask;
+  o->total = nl.dist + topk * o->per_r - o->mask;     // the last round emits no select(M, ..)
+  o->total_l = nl.dist_l + topk * nl.qmin_l;
+}
+// what one top-k call may hold (include/vdb.h VDB_NEAREST_TOPK_MAX_*): lane numbers over (query, round, vector) and (query, round,
+// dimension) are 32-bit before the segments multiply them, the work space is 32 B per (query, round, vector) and 164 B per (query,
+// vector), and the deferred-inversion counter is 32-bit as in nv_batch_fits
+static int nv_topk_fits(size_t Q, size_t n, size_t dim, size_t topk, const NvLayout& nl) {
+  if (topk == 0 || topk > n) {
+    set_error("top-k: topk must be at least 1 and at most n");
+    return VDB_ERR_ARG;
+  }
+  const size_t cap = VDB_NEAREST_TOPK_MAX_INSTANCES;
+  const uint64_t round_cells = nl.qmin + nl.iseq + nl.sel + 8ull * n;
+  if (Q > cap || topk > cap / Q || n > cap / (Q * topk) || dim > cap / (Q * topk) || nl.dist > VDB_NEAREST_TOPK_MAX_CELLS / Q ||
+      round_cells > VDB_NEAREST_TOPK_MAX_CELLS / (Q * topk) || Q * (nl.dist + topk * round_cells - 8ull * n) > VDB_NEAREST_TOPK_MAX_CELLS) {
+    set_error("top-k query too large for one call: n_queries * topk * n and n_queries * topk * dim at most 2^24, cells at most 2^34 (include/vdb.h)");
+    return VDB_ERR_ARG;
+  }
+  return VDB_OK;
+}
+// Q x [n distances, then topk rounds of qmin chain / is_equal / select_by_indicator / mask], block q at adv_off + q * (cells of one):
+// one run_distances over Q x n instances, one value kernel that runs every round of every query, and one launch per emitting stage —
+// the launch count depends on neither Q nor topk
+int wit_nearest_topk_dev(FpEntry* fp, int metric, const u256* queries, const u256* vectors, size_t Q, size_t n, size_t dim, size_t topk, Streams st,
+                         uint64_t adv_off, uint64_t lk_off, u256* ind, u256* result) {
+  DistLayout dl;
+  NvLayout nl;
+  NvTopkLayout tl;
+  TRY(nv_layout(fp, metric, n, dim, &dl, &nl));
+  TRY(nv_topk_fits(Q, n, dim, topk, nl));
+  nv_topk_layout(nl, n, topk, &tl);
+  TRY(inv_list_attach(st, Q * tl.total));
+  TRY(set_winv(st, fp->dev));
+  const size_t inst = Q * n, rinst = inst * topk;
+  InstMap im{adv_off, lk_off, (uint32_t)n, tl.total, tl.total_l, (uint32_t)n, (uint32_t)n};  // (vector_{t % n}, query_{t / n})
+  u256* mid = (u256*)scratch_get(0, (inst * 4 + rinst + 8) * sizeof(u256) + inst * sizeof(uint32_t));
+  if (!mid) return VDB_ERR_OOM;
+  u256* dist = mid + 3 * inst;
+  u256* pm = dist + inst;
+  uint32_t* rnd = (uint32_t*)(pm + rinst + 8);
+  TRY(run_distances(st, fp, dl, im, (uint32_t)inst, vectors, queries, mid, dist));
+  const NvTopk nt{adv_off, lk_off, tl.total, tl.total_l, nl.dist, nl.dist_l, tl.per_r, nl.qmin_l, nl.qmin, nl.qmin + nl.iseq,
+                  nl.qmin + nl.iseq + nl.sel, (uint32_t)Q, (uint32_t)n, (uint32_t)dim, (uint32_t)topk};
+  hipStream_t s = ctx().stream;
+  {
+    VDB_PROF("k_nvt_rounds");
+    hipLaunchKernelGGL(k_nvt_rounds, dim3((unsigned)Q), dim3(64), 0, s, fp->dev, dist, (uint32_t)n, (uint32_t)topk, pm, rnd);
+  }
+  VDB_LAUNCH_CHECK();
+  if (n > 1) {
+    {
+      VDB_PROF("k_nvt_qmin");
+      hipLaunchKernelGGL(k_nvt_qmin, dim3((unsigned)((Q * topk * (n - 1) + 63) / 64)), dim3(64), 0, s, st, fp->dev, nt, dist, pm, rnd);
+    }
+    VDB_LAUNCH_CHECK();
+  }
+  {
+    VDB_PROF("k_nvt_is_equal");
+    hipLaunchKernelGGL(k_nvt_is_equal, dim3((unsigned)((rinst + 63) / 64)), dim3(64), 0, s, st, fp->dev, nt, dist, pm, rnd, ind);
+  }
+  VDB_LAUNCH_CHECK();
+  {
+    // launched for topk == 1 too (one wavefront that finds no lane of its own): the launch count of a call does not depend on topk
+    VDB_PROF("k_nvt_mask");
+    hipLaunchKernelGGL(k_nvt_mask, dim3((unsigned)((inst * (topk - 1) + 63) / 64 + (topk == 1))), dim3(64), 0, s, st, fp->dev, nt, dist, rnd, ind);
+  }
+  VDB_LAUNCH_CHECK();
+  {
+    const uint32_t S = nv_select_segments(Q * topk, n, dim);
+    VDB_PROF("k_nvt_select");
+    hipLaunchKernelGGL(k_nvt_select, dim3((unsigned)((Q * topk * dim * S + 63) / 64)), dim3(64), 0, s, st, fp->dev, nt, S, vectors, ind, result);
+  }
+  VDB_LAUNCH_CHECK();
+  return inv_list_fixup(st);
+}
+
 static int km_layout(FpEntry* fp, int metric, size_t n, size_t dim, size_t K, DistLayout* dl, KmLayout* kl) {
   TRY(dist_layout(fp->host, metric, dim, dl));
   const Sizes& z = fp->host.sz;
@@ -1888,6 +2111,62 @@ int vdb_wit_nearest_batch_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* 
   Streams st{as_u256(stream_dev), selector_dev, as_u256(lookup_dev), derr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], g_win[2], g_win[3]};
   TRY(wit_nearest_batch_dev(fp, metric, as_u256(queries_dev), as_u256(vectors_dev), n_queries, n, dim, st, 0, 0, as_u256(indicators_dev),
                             as_u256(results_dev)));
+  return check_err_flag(derr);
+}
+
+// the topk nearest vectors of every query (include/vdb.h): nearest_vector's distances, then its closing stages once per round
+int vdb_wit_nearest_topk_size(int metric, uint32_t P, uint32_t L, size_t n_queries, size_t n, size_t dim, size_t topk, uint64_t* cells,
+                              uint64_t* lookups) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(n_queries > 0 && n > 0, "no query or empty database");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  DistLayout dl;
+  NvLayout nl;
+  NvTopkLayout tl;
+  TRY(nv_layout(fp, metric, n, dim, &dl, &nl));
+  TRY(nv_topk_fits(n_queries, n, dim, topk, nl));
+  nv_topk_layout(nl, n, topk, &tl);
+  if (cells) *cells = n_queries * tl.total;
+  if (lookups) *lookups = n_queries * tl.total_l;
+  return VDB_OK;
+}
+int vdb_wit_nearest_topk(int metric, uint32_t P, uint32_t L, const vdb_fr* queries, const vdb_fr* vectors, size_t n_queries, size_t n, size_t dim,
+                         size_t topk, vdb_fr* stream_out, vdb_fr* lookup_out, uint8_t* selector_out, vdb_fr* indicators_out, vdb_fr* results_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(queries && vectors && n_queries > 0 && n > 0 && dim > 0, "null pointer or empty input");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  uint64_t cells, lookups;
+  TRY(vdb_wit_nearest_topk_size(metric, P, L, n_queries, n, dim, topk, &cells, &lookups));
+  DevBuf dq, dv, dind, dres;
+  HostStreams hs;
+  TRY(upload(dq, queries, n_queries * dim * sizeof(u256)));
+  TRY(upload(dv, vectors, n * dim * sizeof(u256)));
+  TRY(dind.alloc(n_queries * topk * n * sizeof(u256)));
+  TRY(dres.alloc(n_queries * topk * dim * sizeof(u256)));
+  TRY(hs.init(cells, lookups, selector_out != nullptr));
+  TRY(wit_nearest_topk_dev(fp, metric, dq.as<u256>(), dv.as<u256>(), n_queries, n, dim, topk, hs.st, 0, 0, dind.as<u256>(), dres.as<u256>()));
+  TRY(download(indicators_out, dind.p, n_queries * topk * n * sizeof(u256)));
+  TRY(download(results_out, dres.p, n_queries * topk * dim * sizeof(u256)));
+  return hs.finish(stream_out, lookup_out, selector_out, cells, lookups);
+}
+int vdb_wit_nearest_topk_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* queries_dev, const vdb_fr* vectors_dev, size_t n_queries, size_t n,
+                             size_t dim, size_t topk, vdb_fr* stream_dev, vdb_fr* lookup_dev, uint8_t* selector_dev, vdb_fr* indicators_dev,
+                             vdb_fr* results_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(queries_dev && vectors_dev && stream_dev && lookup_dev && indicators_dev && results_dev && n_queries > 0 && n > 0 && dim > 0,
+          "null pointer or empty input");
+  VDB_ARG(topk > 0 && topk <= n, "topk must be at least 1 and at most n");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  int* derr = (int*)scratch_get(1, 64);
+  if (!derr) return VDB_ERR_OOM;
+  VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
+  // the rank window as in vdb_wit_nearest_batch_dev: every rank computes every value, a rank stores the cells inside its window
+  Streams st{as_u256(stream_dev), selector_dev, as_u256(lookup_dev), derr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], g_win[2], g_win[3]};
+  TRY(wit_nearest_topk_dev(fp, metric, as_u256(queries_dev), as_u256(vectors_dev), n_queries, n, dim, topk, st, 0, 0, as_u256(indicators_dev),
+                           as_u256(results_dev)));
   return check_err_flag(derr);
 }
 

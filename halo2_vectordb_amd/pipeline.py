@@ -914,6 +914,75 @@ class BatchQueryHotPath(HotPath):
         return bld.finish(), [int(c) for c in np.asarray(res).reshape(-1)] + [root], root
 
 
+class TopKQueryHotPath(HotPath):
+    """Top-k queries against ONE committed database in one proof: assign the q queries, assign the n database vectors, per query the
+    `topk` rounds of include/vdb.h's vdb_wit_nearest_topk (nearest_vector's distances once, its qmin chain / is_equal /
+    select_by_indicator per round, the winners replaced by Constant(2^(2P) - 1) through gate.select before the next round), then
+    merkle_commitment(database) once.  The reference has no top-k gadget: this is the closure a user of its chips writes.  Stream:
+    [queries | vectors | block of query 0 | ... | merkle_commitment]; public, in make_public order: per query the topk result vectors,
+    nearest first, then the root.  With topk = 1 the circuit is BatchQueryHotPath's, with q = 1 too QueryHotPath's.  Ties are
+    nearest_vector's: every vector at the round's minimum distance gets its indicator set, the round's result is the last of them and
+    all of them leave together; when fewer than topk distinct distances exist, the later rounds set every indicator and return the
+    last vector.  All blocks come from one call whose launch count depends on neither q nor topk; sharded like NearestHotPath."""
+
+    def __init__(self, topk=10, q=1, n=64, dim=128, k=16, P=48, L=13, metric="euclidean", seed=20260002, tau=None, col_shard=(0, 1), vectors=None,
+                 blind_seed=None, params=None):
+        """`vectors`: (q + n, dim) f64 rows, the queries first"""
+        if q < 1:
+            raise ValueError("a batch holds at least one query")
+        if not 1 <= topk <= n:
+            raise ValueError("topk must be at least 1 and at most n")
+        super().__init__(n, dim, k, P, L, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors, blind_seed=blind_seed, params=params)
+        self.q, self.topk = q, topk
+        self.metric = api.METRICS[metric]
+        self.metric_name = metric
+
+    def n_input_rows(self):
+        return self.q + self.n
+
+    def _input_vectors(self):
+        # the database and the queries are BatchQueryHotPath's for the same seed
+        vec, seed = sift_like_vectors(self.seed, self.n, self.dim)
+        queries, _ = sift_like_vectors(seed + 1000, self.q, self.dim)
+        return np.concatenate([queries, vec]), seed
+
+    def _circuit_size(self):
+        cells, lk = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self.lib.vdb_wit_nearest_topk_size(self.metric, self.P, self.L, self.q, self.n, self.dim, self.topk, ctypes.byref(cells), ctypes.byref(lk)))
+        self.nearest_cells, self.merkle_cells = cells.value, _merkle_cells(self)
+        return (self.q + self.n) * self.dim, self.nearest_cells + self.merkle_cells, lk.value
+
+    def _alloc_outputs(self):
+        self.d_ind = self._output(self.q * self.topk * self.n * 32)
+        self.d_root = self._output(32)
+        self.d_pub = self._output((self.q * self.topk * self.dim + 1) * 32)     # [result vectors | root]: the public statement, in make_public order
+
+    def _emit(self, sel):
+        at, d_db = self.n_in, self.d_vec.at(self.q * self.dim * 32)
+        with self._window(sel, at):
+            check(self.lib.vdb_wit_nearest_topk_dev(self.metric, self.P, self.L, self.d_vec.ptr, d_db, self.q, self.n, self.dim, self.topk,
+                                                    self.d_stream.at(at * B), self.d_lookup.ptr, self._sel_at(sel, at), self.d_ind.ptr, self.d_pub.ptr))
+        _merkle_trace(self, d_db, at + self.nearest_cells, sel)
+        check(self.lib.vdb_memcpy_d2d(self.d_pub.at(self.q * self.topk * self.dim * 32), self.d_root.ptr, ctypes.c_size_t(32)))
+
+    def public_values_dev(self):
+        return self.d_pub.ptr, self.q * self.topk * self.dim + 1
+
+    def results(self):
+        return (self.d_ind.download((self.q, self.topk, self.n, 4)), self.d_pub.download((self.q, self.topk, self.dim, 4)),
+                self.d_root.download((4,)))
+
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder, place_merkle
+        bld, (_ind, res), used = CS.build_nearest_topk(self.metric_name, self.q, self.n, self.dim, self.topk, self.P, self.L, builder=DeviceBuilder,
+                                                       extra_cells=self.merkle_cells, finish=False)
+        assert used == self.n_in + self.nearest_cells
+        root, end = place_merkle(bld, self.n, self.dim, used, self.q * self.dim, functools.partial(self._fetch_flags, d_flags), self._fetch)
+        assert end == self.n_cells
+        return bld.finish(), [int(c) for c in np.asarray(res).reshape(-1)] + [root], root
+
+
 class DistancesHotPath(HotPath):
     """The reference's two-vector circuits through the same hot path: examples/distances.rs:29-59 (assign a, assign b, then
     euclidean, manhattan, cosine and hamming distance of the same two vectors, each made public) and examples/euclid.rs:26-46 (ten Euclidean distances of one pair, nothing public:

@@ -184,6 +184,34 @@ int vdb_wit_nearest_batch(int metric, uint32_t precision_bits, uint32_t lookup_b
 int vdb_wit_nearest_batch_dev(int metric, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *queries_dev, const vdb_fr *vectors_dev,
                               size_t n_queries, size_t n, size_t dim, vdb_fr *stream_dev, vdb_fr *lookup_dev, uint8_t *selector_dev,
                               vdb_fr *indicators_dev, vdb_fr *results_dev);
+/* The topk nearest vectors of every query over ONE database (top-k query).  The reference has no such gadget; the cells are those of the
+ * closure a user of its chips writes.  Per query, in query order: the n distance blocks of vdb_wit_nearest, then for round
+ * r = 0 .. topk - 1 over the entries cur (cur = the distances for r = 0):
+ *   min_r   = qmin folded over cur_0 .. cur_{n-1}                (n - 1 qmin blocks, with their lookup cells)
+ *   ind_r,i = gate.is_equal(min_r, cur_i)                        (12 cells each)
+ *   res_r,j = gate.select_by_indicator(v_.,j, ind_r,.)           (1 + 3 n cells each)
+ *   cur_i   = gate.select(Constant(M), cur_i, ind_r,i)           (8 cells each; not emitted after the last round)
+ * with M = 2^(2 precision_bits) - 1, the largest value of the chip's range.  Lookup stream: per query the n distance runs, then per round
+ * the n - 1 qmin runs.  indicators_out n_queries x topk x n raw 0/1 bits, results_out n_queries x topk x dim, nearest first.
+ * topk == 1 writes the bytes of vdb_wit_nearest_batch.  Ties behave as in nearest_vector: every entry that equals the round's minimum gets
+ * its indicator set, the round's result is the LAST of them, and all of them are masked in that round; once fewer distinct distances than
+ * rounds remain, a round runs on an all-M array, sets every indicator and returns the last vector.
+ * The number of kernel launches depends on neither n_queries nor topk.  The _dev form honours vdb_wit_set_window like
+ * vdb_wit_nearest_batch_dev.  Work space: 32 B per (query, round, vector) for the round's prefix minima, and per (query, vector) 160 B
+ * for the distances plus 4 B for the round that masked the entry.
+ * Limits of one call (VDB_ERR_ARG beyond them, as for topk == 0, topk > n and n_queries == 0, before anything is launched):
+ * n_queries * topk * n and n_queries * topk * dim at most VDB_NEAREST_TOPK_MAX_INSTANCES (32-bit lane numbers), all cells at most
+ * VDB_NEAREST_TOPK_MAX_CELLS.  VDB_ERR_OOM when the work space cannot be allocated. */
+#define VDB_NEAREST_TOPK_MAX_INSTANCES ((size_t)1 << 24)
+#define VDB_NEAREST_TOPK_MAX_CELLS ((uint64_t)1 << 34)
+int vdb_wit_nearest_topk_size(int metric, uint32_t precision_bits, uint32_t lookup_bits, size_t n_queries, size_t n, size_t dim, size_t topk,
+                              uint64_t *cells, uint64_t *lookups);
+int vdb_wit_nearest_topk(int metric, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *queries, const vdb_fr *vectors, size_t n_queries,
+                         size_t n, size_t dim, size_t topk, vdb_fr *stream_out, vdb_fr *lookup_out, uint8_t *selector_out, vdb_fr *indicators_out,
+                         vdb_fr *results_out);
+int vdb_wit_nearest_topk_dev(int metric, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *queries_dev, const vdb_fr *vectors_dev,
+                             size_t n_queries, size_t n, size_t dim, size_t topk, vdb_fr *stream_dev, vdb_fr *lookup_dev, uint8_t *selector_dev,
+                             vdb_fr *indicators_dev, vdb_fr *results_dev);
 /* VectorDBChip::kmeans::<K, I> (src/gadget/vectordb.rs:225-362): centroids K x dim, indicators n x K
  * (quantized 1.0 / 0).  zero_cached: Context::load_zero already called earlier in this context. */
 int vdb_wit_kmeans_size(int metric, uint32_t precision_bits, uint32_t lookup_bits, size_t n, size_t dim, size_t K, size_t I, int zero_cached,

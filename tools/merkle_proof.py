@@ -7,7 +7,8 @@ device) in the permutation argument, the root public, fresh blinds, Fiat-Shamir 
 vectors, result vector and root public; `--lookup-bits`, `--metric`): e.g. the in-cluster query of BASELINE C5's demo,
 `--circuit query --n 5000 --k 18 --lookup-bits 17 --block-cols 126 --ext-block-cols 64`.  With `--queries Q` (Q > 1) the query circuit
 holds Q queries against the one database — nearest_vector per query, one merkle_commitment, the Q result vectors and the root public
-(pipeline.BatchQueryHotPath)."""
+(pipeline.BatchQueryHotPath); with `--topk T` (T > 1) every query asks for its T nearest vectors, nearest first
+(pipeline.TopKQueryHotPath)."""
 import argparse
 import json
 import os
@@ -18,7 +19,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from halo2_vectordb_amd import api  # noqa: E402
-from halo2_vectordb_amd.pipeline import BatchQueryHotPath, MerkleHotPath, QueryHotPath  # noqa: E402
+from halo2_vectordb_amd.pipeline import BatchQueryHotPath, MerkleHotPath, QueryHotPath, TopKQueryHotPath  # noqa: E402
 from halo2_vectordb_amd.rounds import ProverRounds, quotient_identity_holds  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -33,6 +34,7 @@ ap.add_argument("--circuit", default="merkle", choices=["merkle", "query"])
 ap.add_argument("--lookup-bits", type=int, default=13)
 ap.add_argument("--metric", default="euclidean")
 ap.add_argument("--queries", type=int, default=1, help="--circuit query: queries proved against the one database in this proof")
+ap.add_argument("--topk", type=int, default=1, help="--circuit query: nearest vectors proved per query, nearest first")
 ap.add_argument("--out", default=None, help="write the proof (io.write_snark) and the verifying key beside it")
 args = ap.parse_args()
 
@@ -40,7 +42,11 @@ api.init(0)
 t0 = time.time()
 if args.queries < 1 or (args.queries > 1 and args.circuit != "query"):
     raise SystemExit("--queries needs --circuit query and at least one query")
-if args.circuit == "query" and args.queries > 1:
+if args.topk < 1 or (args.topk > 1 and args.circuit != "query"):
+    raise SystemExit("--topk needs --circuit query and at least one neighbour")
+if args.circuit == "query" and args.topk > 1:
+    hp = TopKQueryHotPath(topk=args.topk, q=args.queries, n=args.n, dim=args.dim, k=args.k, L=args.lookup_bits, metric=args.metric, seed=args.seed)
+elif args.circuit == "query" and args.queries > 1:
     hp = BatchQueryHotPath(q=args.queries, n=args.n, dim=args.dim, k=args.k, L=args.lookup_bits, metric=args.metric, seed=args.seed)
 elif args.circuit == "query":
     hp = QueryHotPath(n=args.n, dim=args.dim, k=args.k, L=args.lookup_bits, metric=args.metric, seed=args.seed)
@@ -73,7 +79,7 @@ if args.out:
     write_snark(args.out, out["proof"], out["instances"])
     pr.save_verifying_key(args.out + ".vk.npz", opened=out["opened"])
 what = f"merkle_commitment {args.n}x{args.dim} k={args.k}" if args.circuit == "merkle" else \
-    f"query circuit ({str(args.queries) + ' x ' if args.queries > 1 else ''}nearest_vector {args.metric} + merkle_commitment) over {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}"
+    f"query circuit ({str(args.queries) + ' x ' if args.queries > 1 else ''}{'top-' + str(args.topk) + ' ' if args.topk > 1 else ''}nearest_vector {args.metric} + merkle_commitment) over {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}"
 print(json.dumps({"workload": what + ": whole constraint map, public outputs in the instance column, transcript, fresh blinds, SHPLONK", "lookup_cells": hp.n_lookup,
                   "cells": hp.n_cells, "columns": hp.n_cols, "product_sets": pr.n_sets, "mock_report_on_keygen_witness": pr.keygen_report.as_dict(),
                   "setup_s": round(t1 - t0, 1), "keygen_s": round(t2 - t1, 1), "quotient_identity_at_x_holds": bool(ok),
