@@ -427,6 +427,50 @@ def wit_merkle(vectors, zero_cached=False, selectors=False):
     return dict(stream=stream, **_split_flags(sel), root=root)
 
 
+def merkle_levels(n):
+    """(lp, depth) of merkle_commitment's tree over n vectors: the padded leaf count and the number of levels above the leaves"""
+    lp = 1
+    while lp < n:
+        lp <<= 1
+    return lp, lp.bit_length() - 1
+
+
+def merkle_tree_build(vectors):
+    """the digests of every level of merkle_commitment's tree over `vectors` (n, dim, 4), as vdb_merkle_tree_build_dev leaves them on
+    the device: (2 lp, 4), the leaves first, the root at entry 2 lp - 2"""
+    lib = _lib.init()
+    vectors = _fr(vectors)
+    n, dim = vectors.shape[0], vectors.shape[1]
+    lp, _ = merkle_levels(n)
+    d_vec, d_lv = DeviceBuffer(vectors.nbytes), DeviceBuffer(2 * lp * 32)
+    try:
+        d_vec.upload(vectors)
+        check(lib.vdb_merkle_tree_build_dev(d_vec.ptr, _sz(n), _sz(dim), d_lv.ptr))
+        return d_lv.download((2 * lp, 4))
+    finally:
+        d_vec.free()
+        d_lv.free()
+
+
+def wit_merkle_update(levels, n, new_vectors, indices, selectors=False):
+    """a batch of Merkle path updates (vdb_wit_merkle_update) against the tree `levels` (merkle_tree_build's array over n vectors):
+    slot indices[j] takes new_vectors[j] (m, dim, 4), in order.  dict(stream, selectors, input_cells, public (3 m + 2, 4):
+    [old root | idx, old leaf, new leaf per update | new root], levels: the tree after the batch)"""
+    lib = _lib.init()
+    new_vectors = _fr(new_vectors)
+    levels = np.array(levels, dtype=np.uint64, copy=True)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64)
+    m, dim = new_vectors.shape[0], new_vectors.shape[1]
+    assert idx.shape == (m,) and levels.shape == (2 * merkle_levels(n)[0], 4)
+    cells, n_in = _u64(), _u64()
+    check(lib.vdb_wit_merkle_update_size(_sz(n), _sz(dim), _sz(m), ctypes.byref(cells), ctypes.byref(n_in)))
+    stream = np.zeros((cells.value, 4), dtype=np.uint64)
+    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
+    pub = np.zeros((3 * m + 2, 4), dtype=np.uint64)
+    check(lib.vdb_wit_merkle_update(_p(levels), _sz(n), _sz(dim), _p(new_vectors), _p(idx), _sz(m), _p(stream), _p(sel) if selectors else None, _p(pub)))
+    return dict(stream=stream, **_split_flags(sel), input_cells=n_in.value, public=pub, levels=levels)
+
+
 def layout_plan(selectors, k, minimum_rows=9):
     lib = _lib.init()
     selectors = np.ascontiguousarray(selectors, dtype=np.uint8)

@@ -82,6 +82,11 @@ class DeviceBuilder:
     def constant_cell(self, pos, value):
         self.d_const_idx.upload(np.array([self.const_index(value % R)], dtype=np.int64), offset=int(pos) * 8)
 
+    def tie(self, cell, src):
+        """ctx.constrain_equal(src, cell): `cell` (a placed block's fresh witness) copies the earlier cell `src`"""
+        assert src < cell
+        self.d_copy_of.upload(np.array([src], dtype=np.int64), offset=int(cell) * 8)
+
     def _template(self, blk):
         key = id(blk)
         if key not in self._blocks:

@@ -668,6 +668,11 @@ class _Builder:
     def constant_cell(self, pos, value):
         self.const_idx[pos] = self.const_index(value % R)
 
+    def tie(self, cell, src):
+        """ctx.constrain_equal(src, cell): `cell` (a placed block's fresh witness) copies the earlier cell `src`"""
+        assert src < cell
+        self.copy_of[cell] = src
+
     def place(self, blk, bases, lk_bases, ext_cells):
         """instances of `blk` at advice offsets `bases` (m,), lookup offsets `lk_bases` (m,), external inputs `ext_cells` (m, n_ext);
         returns the absolute cells of the block's outputs, (m, n_outs)"""
@@ -904,3 +909,231 @@ def build_kmeans(metric, n, dim, K, I, P, L, builder=None):
             new_cent[k] = B.place(qd, sums0 + (n - 1) * dim * 4 + j * qd.n, clb + j * qd.n_lk, np.stack([sum_cells, np.full(dim, size_cells[k])], axis=1))[:, 0]
         cent = new_cent
     return B.finish(), (cent, ind)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Merkle path updates (include/vdb.h vdb_wit_merkle_update; pipeline.UpdateHotPath)
+def merkle_update_layout(m, dim, depth):
+    """where the cells of a batch of m path updates lie: dict(nperm, n_ins, sizes, leaf_cells, node_cells, level_cells, ip_cells,
+    per_update, n_vec, old_leaf, bits, sibs, n_in, total) — the last five stream cells: [new vectors | old leaves | bits | siblings],
+    then update j's block at n_in + j * per_update: its leaf sponge, per level [assert_bit 4 | select lo 8 | select ro 8 | H old |
+    select ln 8 | select rn 8 | H new], the index inner product"""
+    from .copymap import perm_cells
+    if m < 1 or depth < 1 or dim < 1:
+        raise ValueError("a batch holds at least one update of a tree with at least two leaves")
+    nperm = (dim + 1) // 2 + (1 if dim % 2 == 0 else 0)
+    n_ins = [max(0, min(2, dim - 2 * p)) for p in range(nperm)]
+    sizes = [perm_cells(k) for k in n_ins]
+    node_cells = perm_cells(2) + perm_cells(0)
+    lay = dict(nperm=nperm, n_ins=n_ins, sizes=sizes, leaf_cells=sum(sizes), node_cells=node_cells, level_cells=36 + 2 * node_cells,
+               ip_cells=1 + 3 * (depth - 1), n_vec=m * dim, old_leaf=m * dim, bits=m * dim + m, sibs=m * dim + m + m * depth)
+    lay["per_update"] = lay["leaf_cells"] + depth * lay["level_cells"] + lay["ip_cells"]
+    lay["n_in"] = m * (dim + 1 + 2 * depth)
+    lay["total"] = lay["n_in"] + m * lay["per_update"]
+    return lay
+
+
+def merkle_update_instances(m, top_old0, idx, old_leaf, new_leaf, top_new_last):
+    """the public cells in make_public order: the old root, per update (idx, old leaf, new leaf), the new root"""
+    out = [int(top_old0)]
+    for j in range(m):
+        out += [int(idx[j]), int(old_leaf[j]), int(new_leaf[j])]
+    return out + [int(top_new_last)]
+
+
+def trace_merkle_update(m, dim, depth, fetch_flags, fetch_values):
+    """The closure of a batch of m path updates cell by cell (the ground truth of build_merkle_update): assign the four witness groups,
+    then per update the leaf sponge, the levels and the index, the top of the old path tied to the top of the update before.
+    fetch_flags(lo, hi) / fetch_values(lo, hi): flag bytes / canonical values of stream cells of a keygen-style run (one instance of
+    every kind of permutation is read: the Poseidon constants are fixed-column values).  -> (CopyMap, public cells)"""
+    from .copymap import perm_cells, permutation_template
+    lay = merkle_update_layout(m, dim, depth)
+    total = lay["total"]
+    copy_of, cidx, gate = list(range(total)), [-1] * total, [False] * total
+    consts, cmap, tmpl = [], {}, {}
+
+    def cid(v):
+        v %= R
+        if v not in cmap:
+            cmap[v] = len(consts)
+            consts.append(v)
+        return cmap[v]
+
+    def put(at, cells, gates):
+        """cells: ('c', earlier cell) | ('k', constant) | None (a new value)"""
+        for i, (x, g) in enumerate(zip(cells, gates)):
+            gate[at + i] = bool(g)
+            if x is None:
+                continue
+            if x[0] == "k":
+                cidx[at + i] = cid(x[1])
+            else:
+                copy_of[at + i] = x[1]
+        return at + len(cells)
+
+    def select(at, a, b, s):                                 # [a - b, 1, b, a, b, sel, a - b, out]
+        put(at, [None, ("k", 1), ("c", b), ("c", a), ("c", b), ("c", s), ("c", at), None], [1, 0, 0, 0, 1, 0, 0, 0])
+        return at + 7
+
+    def perm(at, n_in, state, msgs):
+        if n_in not in tmpl:
+            size = perm_cells(n_in)
+            flags = np.asarray(fetch_flags(at, at + size), dtype=np.uint8)
+            tmpl[n_in] = (permutation_template(flags, n_in), flags, fetch_values(at, at + size))
+        (src, fin), flags, vals = tmpl[n_in]
+        for i, s in enumerate(src.tolist()):
+            p = at + i
+            gate[p] = bool(flags[i] & 1)
+            if flags[i] & 2:
+                cidx[p] = cid(int(vals[i]))
+            elif s >= 0:
+                copy_of[p] = at + s
+            elif s <= -20:
+                copy_of[p] = msgs[-20 - s]
+            elif s <= -10:
+                if state is None:                            # the chip's initial state: capacity 2^64, then zeros
+                    cidx[p] = cid((1 << 64) if s == -10 else 0)
+                else:
+                    copy_of[p] = state[-10 - s]
+        return [at + f for f in fin]
+
+    def node(at, left, right):
+        st = perm(at, 2, None, [left, right])
+        return perm(at + perm_cells(2), 0, st, [])[1]
+
+    idx_cells, new_leaves, prev_top, top_old0 = [], [], None, None
+    for j in range(m):
+        at = lay["n_in"] + j * lay["per_update"]
+        state = None
+        for p in range(lay["nperm"]):
+            state = perm(at, lay["n_ins"][p], state, [j * dim + 2 * p + i for i in range(lay["n_ins"][p])])
+            at += lay["sizes"][p]
+        cur_old, cur_new = lay["old_leaf"] + j, state[1]
+        new_leaves.append(cur_new)
+        bits = [lay["bits"] + j * depth + l for l in range(depth)]
+        for l in range(depth):
+            b, sib = bits[l], lay["sibs"] + j * depth + l
+            put(at, [("k", 0), ("c", b), ("c", b), ("c", b)], [1, 0, 0, 0])
+            lo = select(at + 4, sib, cur_old, b)
+            ro = select(at + 12, cur_old, sib, b)
+            cur_old = node(at + 20, lo, ro)
+            at += 20 + lay["node_cells"]
+            ln = select(at, sib, cur_new, b)
+            rn = select(at + 8, cur_new, sib, b)
+            cur_new = node(at + 16, ln, rn)
+            at += 16 + lay["node_cells"]
+        cells, gates = [("c", bits[0])], [depth > 1]         # inner_product(bits, Constant(2^l)): 2^0 = 1, the sum starts with b_0 itself
+        for l in range(1, depth):
+            cells += [("c", bits[l]), ("k", 1 << l), None]
+            gates += [0, 0, l + 1 < depth]
+        at = put(at, cells, gates)
+        idx_cells.append(at - 1)
+        assert at == lay["n_in"] + (j + 1) * lay["per_update"]
+        if prev_top is None:
+            top_old0 = cur_old
+        else:
+            copy_of[cur_old] = prev_top                      # ctx.constrain_equal(cur_old, root_{j-1})
+        prev_top = cur_new
+    cm = CopyMap(np.asarray(copy_of, dtype=np.int64), np.asarray(cidx, dtype=np.int64), consts, np.zeros(total, dtype=bool), np.asarray(gate, dtype=bool),
+                 np.zeros(0, dtype=np.int64))
+    return cm, merkle_update_instances(m, top_old0, idx_cells, [lay["old_leaf"] + j for j in range(m)], new_leaves, prev_top)
+
+
+def _perm_block(flags, values, n_in, fresh, tied):
+    """one PoseidonChip::permutation as a unit block (external inputs 0..2: the sponge state, 3..4: the absorbed words): `fresh`: the
+    state is the chip's initial one (constants 2^64, 0, 0) instead of external cells; `tied`: the words copy external cells"""
+    from .copymap import T, permutation_template
+    src, fin = permutation_template(flags, n_in)
+    flags = np.asarray(flags, dtype=np.uint8)
+    b = Block.__new__(Block)
+    out = np.where(src >= 0, src, SELF).astype(np.int64)
+    consts, cmap, cidx = [], {}, np.full(src.size, -1, dtype=np.int64)
+
+    def cid(v):
+        if v not in cmap:
+            cmap[v] = len(consts)
+            consts.append(v)
+        return cmap[v]
+    for i in np.flatnonzero(flags & 2):
+        cidx[i] = cid(int(values[i]) % R)
+    for i in range(T):
+        cols = np.flatnonzero(src == -10 - i)
+        if fresh:
+            for c in cols:
+                cidx[c] = cid((1 << 64) if i == 0 else 0)
+        else:
+            out[cols] = EXT0 - i
+    if tied:
+        for i in range(2):
+            out[np.flatnonzero(src == -20 - i)] = EXT0 - (T + i)
+    b.src, b.gate, b.cidx, b.consts = out, (flags & 1).astype(bool), cidx, consts
+    b.asserted, b.lk = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    b.n, b.n_lk, b.outs = src.size, 0, np.asarray(fin, dtype=np.int64)
+    b.local, b.isext = b.src >= 0, b.src <= EXT0
+    b.ext_no = np.where(b.isext, EXT0 - b.src, 0)
+    b.lk_isext, b.lk_ext_no = np.zeros(0, dtype=bool), np.zeros(0, dtype=np.int64)
+    return b
+
+
+def build_merkle_update(m, dim, depth, fetch_flags, fetch_values, builder=None):
+    """trace_merkle_update's map assembled from unit blocks — one per kind of permutation, the bit with its two selects, the two selects
+    of the new path, the index inner product — each placed for all m updates at once, level after level (`builder`: as build_kmeans).
+    -> (CopyMap, public cells)"""
+    from .copymap import T, perm_cells
+    lay = merkle_update_layout(m, dim, depth)
+    B = (builder or _Builder)(lay["total"], 0)
+    j = np.arange(m, dtype=np.int64)
+    zeros = np.zeros(m, dtype=np.int64)
+    base = lay["n_in"] + j * lay["per_update"]
+    blocks = {}
+
+    def perm(bases, n_in, state, msgs):
+        fresh, tied = state is None, n_in > 0
+        key = (n_in, fresh)
+        if key not in blocks:
+            at, size = int(bases[0]), perm_cells(n_in)
+            blocks[key] = _perm_block(fetch_flags(at, at + size), fetch_values(at, at + size), n_in, fresh, tied)
+        e = np.zeros((m, T + 2), dtype=np.int64)
+        if not fresh:
+            for i in range(T):
+                e[:, i] = state[i]
+        for i in range(n_in):
+            e[:, T + i] = msgs[i]
+        outs = B.place(blocks[key], bases, zeros, e)
+        return [outs[:, i] for i in range(T)]
+
+    def node(bases, left, right):
+        return perm(bases + perm_cells(2), 0, perm(bases, 2, None, [left, right]), [])[1]
+
+    s = Sym(0, 0)
+    s.g_assert_bit(ext(0))
+    head = Block(s, [s.g_select(ext(1), ext(2), ext(0)), s.g_select(ext(2), ext(1), ext(0))])     # (bit, sibling, cur_old) -> lo, ro
+    s = Sym(0, 0)
+    tail = Block(s, [s.g_select(ext(1), ext(2), ext(0)), s.g_select(ext(2), ext(1), ext(0))])     # (bit, sibling, cur_new) -> ln, rn
+    s = Sym(0, 0)
+    acc = s.push(ext(0), depth > 1)
+    for l in range(1, depth):
+        s.push(ext(l))
+        s.push(C(1 << l))
+        acc = s.push(None, l + 1 < depth)
+    ip = Block(s, [acc])
+
+    state, off = None, 0
+    for p in range(lay["nperm"]):
+        state = perm(base + off, lay["n_ins"][p], state, [j * dim + 2 * p + i for i in range(lay["n_ins"][p])])
+        off += lay["sizes"][p]
+    new_leaf = state[1]
+    cur_old, cur_new = lay["old_leaf"] + j, new_leaf
+    bits = lay["bits"] + j[:, None] * depth + np.arange(depth, dtype=np.int64)[None, :]
+    for l in range(depth):
+        lb = base + lay["leaf_cells"] + l * lay["level_cells"]
+        sib = lay["sibs"] + j * depth + l
+        lr = B.place(head, lb, zeros, np.stack([bits[:, l], sib, cur_old], axis=1))
+        cur_old = node(lb + 20, lr[:, 0], lr[:, 1])
+        lb = lb + 20 + lay["node_cells"]
+        lr = B.place(tail, lb, zeros, np.stack([bits[:, l], sib, cur_new], axis=1))
+        cur_new = node(lb + 16, lr[:, 0], lr[:, 1])
+    idx = B.place(ip, base + lay["leaf_cells"] + depth * lay["level_cells"], zeros, bits)[:, 0]
+    for k in range(1, m):
+        B.tie(int(cur_old[k]), int(cur_new[k - 1]))          # ctx.constrain_equal(cur_old, root_{j-1})
+    return B.finish(), merkle_update_instances(m, cur_old[0], idx, lay["old_leaf"] + j, new_leaf, cur_new[m - 1])

@@ -81,10 +81,8 @@ class _Tracer:
         return [self.ip_const(st) for _ in range(T)]
 
 
-def permutation_template(flags, n_in):
-    """(src codes, final state offsets) of one PoseidonChip::permutation absorbing n_in message words; `flags`: the kernel's
-    flag bytes of one such permutation (bit 0 gate start, bit 1 constant)."""
-    t = _Tracer(flags)
+def _trace_permutation(t, n_in):
+    """one PoseidonChip::permutation absorbing n_in message words on tracer `t`; -> the final state's cells"""
     st = [-10 - i for i in range(T)]
     st[0] = t.sum([st[0], None], 0b10)
     for i in range(n_in):
@@ -106,7 +104,14 @@ def permutation_template(flags, n_in):
         st = nxt
     for _ in range(HALF - 1):
         st = t.dense([t.sbox(x) for x in st])
-    st = t.dense([t.sbox(x) for x in st])
+    return t.dense([t.sbox(x) for x in st])
+
+
+def permutation_template(flags, n_in):
+    """(src codes, final state offsets) of one PoseidonChip::permutation absorbing n_in message words; `flags`: the kernel's
+    flag bytes of one such permutation (bit 0 gate start, bit 1 constant)."""
+    t = _Tracer(flags)
+    st = _trace_permutation(t, n_in)
     n = len(t.src)
     if n != len(flags):
         raise ValueError(f"permutation template has {n} cells, the kernel emitted {len(flags)}")

@@ -1306,6 +1306,160 @@ __global__ __launch_bounds__(64) void k_mk_tree_trace(Streams stq, const FpTable
   c = trace_permutation(c, T, sp, st, in, j ? 0 : 2);
 }
 
+// ------------------------------------------------------------------ Merkle path updates (include/vdb.h vdb_wit_merkle_update)
+// A batch of m updates (idx_j, new vector_j) against the resident tree `levels` (k_mk_tree_trace's layout), applied in order.  Stream:
+// [new vectors | old leaves | bits | siblings] (the assigned witnesses), then per update its leaf sponge, per level
+// [assert_bit | select lo | select ro | H(lo, ro) | select ln | select rn | H(ln, rn)], and the index inner product.
+// Values: the m leaf hashes (k_mk_leaf_states), then level after level (k_mku_level, a thread per (update, old / new path)).  Which
+// earlier update of the batch last touched a node depends on the indices alone, so one kernel (k_mku_touchers) answers it for every
+// (update, level) before any hash is known: a backward scan over the batch's indices held in LDS.
+#define MKU_MAX_UPDATES 4096
+struct MkuLayout {
+  uint32_t m, D, depth, nperm;
+  uint64_t leaf_cells, level_cells, ip_cells, per_update, n_vec, n_in, total;
+};
+HD uint64_t mku_level_off(uint64_t lp, uint32_t l) { return 2 * (lp - (lp >> l)); }
+// per (level, update), arrays indexed [l * m + j]: sib_from = the latest earlier update whose path holds this one's sibling node at
+// level l (-1: the resident digest is still current), last = no later update touches this update's node at level l (its new-path
+// digest is the batch's final state of that node); prev_same[j] = the latest earlier update of the same slot (-1: none)
+__global__ __launch_bounds__(256) void k_mku_touchers(const uint32_t* __restrict__ idx, uint32_t m, uint32_t depth, int32_t* __restrict__ sib_from,
+                                                      int32_t* __restrict__ prev_same, uint8_t* __restrict__ last) {
+  __shared__ uint32_t sidx[MKU_MAX_UPDATES];
+  for (uint32_t i = threadIdx.x; i < m; i += 256) sidx[i] = idx[i];
+  __syncthreads();
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= m * depth) return;
+  const uint32_t j = t % m, l = t / m;
+  const uint32_t node = sidx[j] >> l;
+  int32_t from = -1;
+  for (int32_t i = (int32_t)j - 1; i >= 0; i--)
+    if ((sidx[i] >> l) == (node ^ 1u)) {
+      from = i;
+      break;
+    }
+  sib_from[t] = from;
+  if (l == 0) {
+    int32_t same = -1;
+    for (int32_t i = (int32_t)j - 1; i >= 0; i--)
+      if (sidx[i] == node) {
+        same = i;
+        break;
+      }
+    prev_same[j] = same;
+  }
+  uint8_t is_last = 1;
+  for (uint32_t i = j + 1; i < m; i++)
+    if ((sidx[i] >> l) == node) {
+      is_last = 0;
+      break;
+    }
+  last[t] = is_last;
+}
+// level l of both paths of every update: lane (j, side) hashes its path's digest with the sibling as it is at update j's turn.
+// path_old / path_new: [(depth + 1) * m], level-major; row 0 of path_new holds the new leaves already (k_mk_leaf_states).
+// wit: [old leaves m | bits m * depth | siblings m * depth], the assigned witnesses behind the new vectors.
+__global__ __launch_bounds__(64) void k_mku_level(const PoseidonSpec* __restrict__ sp, const u256* __restrict__ levels, uint64_t lp,
+                                                  const uint32_t* __restrict__ idx, uint32_t m, uint32_t depth, uint32_t l,
+                                                  const int32_t* __restrict__ sib_from, const int32_t* __restrict__ prev_same, u256* __restrict__ wit,
+                                                  u256* __restrict__ path_old, u256* __restrict__ path_new) {
+  const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= 2 * m) return;
+  const uint32_t j = t % m, side = t / m;
+  const uint32_t node = idx[j] >> l, bit = node & 1u;
+  const int32_t from = sib_from[(size_t)l * m + j];
+  const u256 sib = from >= 0 ? path_new[(size_t)l * m + from] : levels[mku_level_off(lp, l) + (node ^ 1u)];
+  u256 cur;
+  if (side) {
+    cur = path_new[(size_t)l * m + j];
+  } else if (l == 0) {
+    const int32_t ps = prev_same[j];
+    cur = ps >= 0 ? path_new[ps] : levels[node];
+    path_old[j] = cur;
+    wit[j] = cur;
+  } else {
+    cur = path_old[(size_t)l * m + j];
+  }
+  if (!side) {
+    wit[(size_t)m + (size_t)j * depth + l] = bit ? mont_one<Fr>() : u256_zero();
+    wit[(size_t)m + (size_t)m * depth + (size_t)j * depth + l] = sib;
+  }
+  u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
+  u256 in[PSD_RATE] = {bit ? sib : cur, bit ? cur : sib};
+  psd_permute_absorb(sp, st, in, 2);
+  psd_permute_absorb(sp, st, in, 0);
+  (side ? path_new : path_old)[(size_t)(l + 1) * m + j] = st[1];
+}
+// the batch's final state into the resident tree: every node's digest from the last update that touched it
+__global__ __launch_bounds__(64) void k_mku_writeback(u256* __restrict__ levels, uint64_t lp, const uint32_t* __restrict__ idx, uint32_t m, uint32_t depth,
+                                                      const uint8_t* __restrict__ last, const u256* __restrict__ path_new) {
+  const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= m * (depth + 1)) return;
+  const uint32_t j = t % m, l = t / m;
+  const bool is_last = l < depth ? last[t] != 0 : j + 1 == m;
+  if (is_last) levels[mku_level_off(lp, l) + (idx[j] >> l)] = path_new[t];
+}
+// ctx.assign_witnesses of the four input groups: plain cells, no gate
+__global__ __launch_bounds__(256) void k_mku_inputs(Streams st, uint64_t base, const u256* __restrict__ new_vectors, const u256* __restrict__ wit,
+                                                    uint64_t n_vec, uint64_t n_in) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_in) return;
+  const uint64_t p = base + i;
+  if (p < st.rlo || p >= st.rhi) return;
+  st.adv[p] = i < n_vec ? new_vectors[i] : wit[i - n_vec];
+  if (st.sel) st.sel[p] = 0;
+}
+// the cells of one level of one update in five parts (blockIdx.y): the bit and the four selects, then the two permutations of the
+// old path's hash and the two of the new path's — a lane per (update, level), a wavefront holding one part only
+__global__ __launch_bounds__(64) void k_mku_level_trace(Streams stq, const FpTables* __restrict__ T, const PoseidonSpec* __restrict__ sp, MkuLayout ml,
+                                                        uint64_t base, const uint32_t* __restrict__ idx, const u256* __restrict__ wit,
+                                                        const u256* __restrict__ path_old, const u256* __restrict__ path_new) {
+  const uint32_t t = blockIdx.x * 64 + threadIdx.x, part = blockIdx.y;
+  const uint32_t m = ml.m, depth = ml.depth;
+  if (t >= m * depth) return;
+  const uint32_t j = t / depth, l = t % depth;
+  const uint64_t H = perm_cells(2) + perm_cells(0);
+  const uint64_t lb = base + ml.n_in + (uint64_t)j * ml.per_update + ml.leaf_cells + (uint64_t)l * ml.level_cells;
+  const uint32_t bit = (idx[j] >> l) & 1u;
+  const u256* psib = wit + ((size_t)m + (size_t)m * depth + (size_t)j * depth + l);
+  WCtx c = make_ctx(stq, T, lb, 0);
+  if (part == 0) {
+    if (!stq.touches(lb, lb + 20, 0, 0) && !stq.touches(lb + 20 + H, lb + 36 + H, 0, 0)) return;
+    const u256 b = bit ? mont_one<Fr>() : u256_zero();
+    const u256 sib = *psib;
+    Gadgets g(c);
+    g.g_assert_bit(b);
+    for (int side = 0; side < 2; side++) {
+      const u256 cur = (side ? path_new : path_old)[(size_t)l * m + j];
+      g.g_select(sib, cur, b);
+      g.g_select(cur, sib, b);
+      c.pos = lb + 20 + H;
+    }
+    return;
+  }
+  const uint32_t side = (part - 1) >> 1, second = (part - 1) & 1u;
+  c.pos = lb + 20 + (side ? H + 16 : 0) + (second ? perm_cells(2) : 0);
+  if (!stq.touches(c.pos, c.pos + (second ? perm_cells(0) : perm_cells(2)), 0, 0)) return;
+  const u256* pcur = (side ? path_new : path_old) + ((size_t)l * m + j);
+  u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
+  u256 in[PSD_RATE] = {*(bit ? psib : pcur), *(bit ? pcur : psib)};
+  if (second) psd_permute_absorb(sp, st, in, 2);   // the padding-only permutation starts where the absorbing one ended
+  c = trace_permutation(c, T, sp, st, in, second ? 0 : 2);
+}
+// idx_j = gate.inner_product(bits, Constant(2^l)) per update, and the public values [old root | idx, old leaf, new leaf per update | new root]
+__global__ __launch_bounds__(64) void k_mku_index(Streams stq, const FpTables* __restrict__ T, MkuLayout ml, uint64_t base, const u256* __restrict__ wit,
+                                                  const u256* __restrict__ path_old, const u256* __restrict__ path_new, u256* __restrict__ pub) {
+  const uint32_t j = blockIdx.x * 64 + threadIdx.x;
+  const uint32_t m = ml.m, depth = ml.depth;
+  if (j >= m) return;
+  WCtx c = make_ctx(stq, T, base + ml.n_in + (uint64_t)j * ml.per_update + ml.leaf_cells + (uint64_t)depth * ml.level_cells, 0);
+  const u256 s = trace_ip_const(c, T, wit + (size_t)m + (size_t)j * depth, T->pow2, (int)depth);
+  pub[1 + 3 * (size_t)j] = s;
+  pub[2 + 3 * (size_t)j] = wit[j];
+  pub[3 + 3 * (size_t)j] = path_new[j];
+  if (j == 0) pub[0] = path_old[(size_t)depth * m];
+  if (j + 1 == m) pub[1 + 3 * (size_t)m] = path_new[(size_t)depth * m + j];
+}
+
 // ------------------------------------------------------------------ layout (halo2-base assign_threads_in)
 // break points from the gate-start bits: the row walk of GateThreadBuilder::assign_all.  A column that
 // starts at stream cell S breaks at the first row r in {M-3, M-2 (if that cell starts a gate), M-1}.
@@ -1837,6 +1991,139 @@ int wit_merkle_dev(const u256* vectors, size_t n, size_t dim, int zero_cached, S
   return VDB_OK;
 }
 
+// the digests of every level of merkle_commitment's tree, values only, in k_mk_tree_trace's layout (2 lp entries, the last unused)
+int merkle_tree_build_dev(const u256* vectors, size_t n, size_t dim, u256* levels) {
+  const PoseidonSpec* sp;
+  TRY(poseidon_spec_dev(&sp, nullptr));
+  MkLayout ml;
+  mk_layout(n, dim, 0, &ml);
+  hipStream_t s = ctx().stream;
+  u256* states = (u256*)scratch_get(0, (n * ml.nperm * PSD_T + 8) * sizeof(u256));
+  if (!states) return VDB_ERR_OOM;
+  const uint64_t lp = ml.n_leaves_pow2;
+  VDB_HIP(hipMemsetAsync(levels, 0, 2 * lp * sizeof(u256), s));
+  {
+    VDB_PROF("k_mk_leaf_states");
+    hipLaunchKernelGGL(k_mk_leaf_states, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, sp, vectors, (uint32_t)n, (uint32_t)dim, ml.nperm, states, levels);
+  }
+  VDB_LAUNCH_CHECK();
+  for (uint64_t lv = lp, off = 0; lv > 1; off += lv, lv /= 2) {
+    {
+      VDB_PROF("k_mk_level_values");
+      hipLaunchKernelGGL(k_mk_level_values, dim3((unsigned)((lv / 2 + 63) / 64)), dim3(64), 0, s, sp, levels + off, (uint32_t)(lv / 2), levels + off + lv);
+    }
+    VDB_LAUNCH_CHECK();
+  }
+  return VDB_OK;
+}
+
+// sizes of a batch of m path updates in a tree over n vectors; the limits of one call (include/vdb.h)
+static int mku_layout(size_t n, size_t dim, size_t m, MkuLayout* o, uint64_t* lp_out) {
+  VDB_ARG(n > 0 && dim > 0, "empty database");
+  VDB_ARG(m > 0, "a batch holds at least one update");
+  VDB_ARG(m <= MKU_MAX_UPDATES, "more than VDB_MERKLE_UPDATE_MAX_UPDATES updates in one call");
+  VDB_ARG(n <= ((size_t)1 << 30) && dim <= ((size_t)1 << 20), "tree deeper than 30 levels or vector longer than 2^20 words");
+  MkLayout ml;
+  mk_layout(n, dim, 0, &ml);
+  const uint64_t lp = ml.n_leaves_pow2;
+  uint32_t depth = 0;
+  while (((uint64_t)1 << depth) < lp) depth++;
+  VDB_ARG(depth >= 1, "a tree of one leaf has no path (depth 0)");
+  o->m = (uint32_t)m;
+  o->D = (uint32_t)dim;
+  o->depth = depth;
+  o->nperm = ml.nperm;
+  o->leaf_cells = ml.leaf_cells;
+  o->level_cells = 4 + 4 * 8 + 2 * (uint64_t)(perm_cells(2) + perm_cells(0));
+  o->ip_cells = 1 + 3 * (uint64_t)(depth - 1);
+  o->per_update = o->leaf_cells + depth * o->level_cells + o->ip_cells;
+  o->n_vec = (uint64_t)m * dim;
+  o->n_in = o->n_vec + (uint64_t)m * (1 + 2 * (uint64_t)depth);
+  o->total = o->n_in + (uint64_t)m * o->per_update;
+  VDB_ARG(o->total <= ((uint64_t)1 << 34) && (uint64_t)m * ml.nperm <= ((uint64_t)1 << 30), "more than VDB_MERKLE_UPDATE_MAX_CELLS cells in one call");
+  if (lp_out) *lp_out = lp;
+  return VDB_OK;
+}
+int wit_merkle_update_dev(u256* levels, size_t n, size_t dim, const u256* new_vectors, const uint64_t* indices, size_t m, Streams st, uint64_t adv_off,
+                          u256* pub) {
+  MkuLayout ml;
+  uint64_t lp;
+  TRY(mku_layout(n, dim, m, &ml, &lp));
+  static thread_local std::vector<uint32_t> hidx;  // pageable source: hipMemcpyAsync stages it before returning
+  hidx.resize(m);
+  for (size_t j = 0; j < m; j++) {
+    VDB_ARG(indices[j] < lp, "update index outside the padded tree (growing the tree is out of scope)");
+    hidx[j] = (uint32_t)indices[j];
+  }
+  FpEntry* fp;
+  TRY(get_fp(48, 13, &fp));  // only GateChip primitives are used: P and L are irrelevant
+  TRY(set_winv(st, fp->dev));
+  const PoseidonSpec* sp;
+  TRY(poseidon_spec_dev(&sp, nullptr));
+  hipStream_t s = ctx().stream;
+  const uint32_t depth = ml.depth;
+  const size_t n_states = m * ml.nperm * PSD_T, n_wit = m * (1 + 2 * (size_t)depth), n_path = m * ((size_t)depth + 1);
+  const size_t n_u256 = n_states + n_wit + 2 * n_path;
+  const size_t need = n_u256 * sizeof(u256) + (m * depth + 2 * m) * sizeof(uint32_t) + m * depth + 64;
+  u256* buf = (u256*)scratch_get(0, need);
+  if (!buf) return VDB_ERR_OOM;
+  u256* states = buf;
+  u256* wit = states + n_states;
+  u256* path_old = wit + n_wit;
+  u256* path_new = path_old + n_path;
+  int32_t* sib_from = (int32_t*)(path_new + n_path);
+  int32_t* prev_same = sib_from + m * depth;
+  uint32_t* didx = (uint32_t*)(prev_same + m);
+  uint8_t* last = (uint8_t*)(didx + m);
+  VDB_HIP(hipMemcpyAsync(didx, hidx.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  const uint32_t mu = (uint32_t)m;
+  {
+    VDB_PROF("k_mku_touchers");
+    hipLaunchKernelGGL(k_mku_touchers, dim3((unsigned)((m * depth + 255) / 256)), dim3(256), 0, s, didx, mu, depth, sib_from, prev_same, last);
+  }
+  VDB_LAUNCH_CHECK();
+  {
+    VDB_PROF("k_mk_leaf_states");
+    hipLaunchKernelGGL(k_mk_leaf_states, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s, sp, new_vectors, mu, (uint32_t)dim, ml.nperm, states, path_new);
+  }
+  VDB_LAUNCH_CHECK();
+  for (uint32_t l = 0; l < depth; l++) {
+    {
+      VDB_PROF("k_mku_level");
+      hipLaunchKernelGGL(k_mku_level, dim3((unsigned)((2 * m + 63) / 64)), dim3(64), 0, s, sp, levels, lp, didx, mu, depth, l, sib_from, prev_same, wit, path_old,
+                         path_new);
+    }
+    VDB_LAUNCH_CHECK();
+  }
+  {
+    VDB_PROF("k_mku_writeback");
+    hipLaunchKernelGGL(k_mku_writeback, dim3((unsigned)((n_path + 63) / 64)), dim3(64), 0, s, levels, lp, didx, mu, depth, last, path_new);
+  }
+  VDB_LAUNCH_CHECK();
+  {
+    VDB_PROF("k_mku_inputs");
+    hipLaunchKernelGGL(k_mku_inputs, dim3((unsigned)((ml.n_in + 255) / 256)), dim3(256), 0, s, st, adv_off, new_vectors, wit, ml.n_vec, ml.n_in);
+  }
+  VDB_LAUNCH_CHECK();
+  {
+    VDB_PROF("k_mk_leaf_trace");
+    hipLaunchKernelGGL(k_mk_leaf_trace, dim3((unsigned)((m * ml.nperm + 63) / 64)), dim3(64), 0, s, st, fp->dev, sp, new_vectors, mu, (uint32_t)dim, ml.nperm,
+                       adv_off + ml.n_in, ml.per_update, states);
+  }
+  VDB_LAUNCH_CHECK();
+  {
+    VDB_PROF("k_mku_level_trace");
+    hipLaunchKernelGGL(k_mku_level_trace, dim3((unsigned)((m * depth + 63) / 64), 5), dim3(64), 0, s, st, fp->dev, sp, ml, adv_off, didx, wit, path_old, path_new);
+  }
+  VDB_LAUNCH_CHECK();
+  {
+    VDB_PROF("k_mku_index");
+    hipLaunchKernelGGL(k_mku_index, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s, st, fp->dev, ml, adv_off, wit, path_old, path_new, pub);
+  }
+  VDB_LAUNCH_CHECK();
+  return VDB_OK;
+}
+
 }  // namespace vdb
 
 using namespace vdb;
@@ -2255,6 +2542,47 @@ int vdb_wit_merkle(const vdb_fr* vectors, size_t n, size_t dim, int zero_cached,
   TRY(wit_merkle_dev(dv.as<u256>(), n, dim, zero_cached, hs.st, 0, droot.as<u256>()));
   TRY(download(root_out, droot.p, sizeof(u256)));
   return hs.finish(stream_out, nullptr, selector_out, cells, 0);
+}
+
+// the resident tree and batches of path updates against it (include/vdb.h)
+int vdb_merkle_tree_build_dev(const vdb_fr* vectors_dev, size_t n, size_t dim, vdb_fr* levels_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(vectors_dev && levels_dev && n > 0 && dim > 0, "null pointer or empty database");
+  VDB_ARG(n <= ((size_t)1 << 30), "tree deeper than 30 levels");
+  return merkle_tree_build_dev(as_u256(vectors_dev), n, dim, as_u256(levels_dev));
+}
+int vdb_wit_merkle_update_size(size_t n, size_t dim, size_t m, uint64_t* cells, uint64_t* input_cells) {
+  MkuLayout ml;
+  TRY(mku_layout(n, dim, m, &ml, nullptr));
+  if (cells) *cells = ml.total;
+  if (input_cells) *input_cells = ml.n_in;
+  return VDB_OK;
+}
+int vdb_wit_merkle_update_dev(vdb_fr* levels_dev, size_t n, size_t dim, const vdb_fr* new_vectors_dev, const uint64_t* indices, size_t m, vdb_fr* stream_dev,
+                              uint8_t* selector_dev, vdb_fr* public_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(levels_dev && new_vectors_dev && indices && stream_dev && public_dev, "null pointer");
+  Streams st{as_u256(stream_dev), selector_dev, nullptr, nullptr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], 0, ~0ull};
+  return wit_merkle_update_dev(as_u256(levels_dev), n, dim, as_u256(new_vectors_dev), indices, m, st, 0, as_u256(public_dev));
+}
+int vdb_wit_merkle_update(vdb_fr* levels, size_t n, size_t dim, const vdb_fr* new_vectors, const uint64_t* indices, size_t m, vdb_fr* stream_out,
+                          uint8_t* selector_out, vdb_fr* public_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(levels && new_vectors && indices, "null pointer");
+  MkuLayout ml;
+  uint64_t lp;
+  TRY(mku_layout(n, dim, m, &ml, &lp));
+  for (size_t j = 0; j < m; j++) VDB_ARG(indices[j] < lp, "update index outside the padded tree (growing the tree is out of scope)");
+  DevBuf dl, dv, dpub;
+  HostStreams hs;
+  TRY(upload(dl, levels, 2 * lp * sizeof(u256)));
+  TRY(upload(dv, new_vectors, m * dim * sizeof(u256)));
+  TRY(dpub.alloc((3 * m + 2) * sizeof(u256)));
+  TRY(hs.init(ml.total, 0, selector_out != nullptr));
+  TRY(wit_merkle_update_dev(dl.as<u256>(), n, dim, dv.as<u256>(), indices, m, hs.st, 0, dpub.as<u256>()));
+  TRY(download(public_out, dpub.p, (3 * m + 2) * sizeof(u256)));
+  TRY(download(levels, dl.p, 2 * lp * sizeof(u256)));
+  return hs.finish(stream_out, nullptr, selector_out, ml.total, 0);
 }
 
 // ---- b4 layout ---------------------------------------------------------------------------------

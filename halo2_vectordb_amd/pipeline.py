@@ -757,6 +757,111 @@ class MerkleHotPath(HotPath):
         return cm, [root], root                    # examples/merkle.rs:47 make_public.push(root)
 
 
+class UpdateHotPath(HotPath):
+    """Inserts and replacements proved against the committed root: a batch of m Merkle path updates in one proof (include/vdb.h
+    vdb_wit_merkle_update).  The reference has no such gadget: this is the closure a user of its chips writes.  Assigned witnesses:
+    the m new vectors, per update the old leaf, the index bits and the siblings; then per update the leaf hash of the new vector, both
+    paths level by level (assert_bit, four selects, two node hashes), the index as inner_product(bits, 2^l), and the top of the old path
+    tied to the top of the update before.  Public: [old root | idx, old leaf, new leaf per update | new root]; an insert shows as old
+    leaf 0.  The tree stays on the device: `d_levels` holds it after the batch (`d_levels0` before it), and `levels=` starts a batch
+    from the tree another batch left.  No lookup cells; sharded like MerkleHotPath."""
+
+    def __init__(self, n=1024, dim=128, m=8, k=15, L=8, P=32, seed=20260005, tau=None, col_shard=(0, 1), vectors=None, updates=None, levels=None,
+                 blind_seed=None, params=None):
+        """`vectors`: the (n, dim) f64 database the tree is built from (None: seeded synthetic rows), or `levels`: a tree already on
+        the device or host (api.merkle_tree_build's layout; a DeviceBuffer or a (2 lp, 4) array).  `updates`: (indices, (m, dim) f64
+        rows), applied in order (None: m seeded replacements and, where the padding has room, inserts)"""
+        if m < 1:
+            raise ValueError("a batch holds at least one update")
+        self.lp, self.depth = api.merkle_levels(n)
+        if self.depth < 1:
+            raise ValueError("a tree of one leaf has no path")
+        super().__init__(n, dim, k, P, L, seed=seed, tau=tau, col_shard=col_shard, vectors=None, blind_seed=blind_seed, params=params)
+        self.m = m
+        self.database_f64 = None if vectors is None else np.ascontiguousarray(vectors, dtype=np.float64)
+        self.given_levels, self.given_updates = levels, updates
+        self.balance_shards = False
+        self.msm_window_bits = 14   # as MerkleHotPath: nearly every scalar is a full-width Poseidon state
+
+    def n_input_rows(self):
+        return self.m
+
+    def _input_vectors(self):
+        """the m new vectors (the rows ctx.assign_witnesses puts first) and self.indices"""
+        if self.given_updates is not None:
+            idx, rows = self.given_updates
+            rows = np.ascontiguousarray(rows, dtype=np.float64)
+        else:
+            rows, _ = sift_like_vectors(self.seed + 2000, self.m, self.dim)
+            rng = np.random.default_rng(self.seed)
+            idx = rng.integers(0, self.n, size=self.m)
+            free = min(self.lp - self.n, self.m // 2)
+            if free:
+                idx[self.m - free:] = self.n + np.arange(free)      # the batch ends with inserts into the padding
+        self.indices = np.ascontiguousarray(idx, dtype=np.uint64)
+        if self.indices.shape != (self.m,) or (self.indices >= self.lp).any():
+            raise ValueError("an update needs an index below the padded leaf count for every new vector")
+        return rows, self.seed
+
+    def _load_inputs(self):
+        super()._load_inputs()
+        self.d_levels0 = self._output(2 * self.lp * B)
+        self.d_levels = self._output(2 * self.lp * B)
+        if self.given_levels is not None:
+            lv = self.given_levels
+            if isinstance(lv, api.DeviceBuffer):
+                check(self.lib.vdb_memcpy_d2d(self.d_levels0.ptr, lv.ptr, ctypes.c_size_t(2 * self.lp * B)))
+            else:
+                lv = np.ascontiguousarray(lv, dtype=np.uint64)
+                assert lv.shape == (2 * self.lp, 4), "the tree does not belong to this shape"
+                self.d_levels0.upload(lv)
+        else:
+            if self.database_f64 is None:
+                self.database_f64, _ = sift_like_vectors(self.seed, self.n, self.dim)
+            assert self.database_f64.shape == (self.n, self.dim), "database rows do not match the circuit's shape"
+            qdb = api.quantize(self.database_f64, self.P)
+            d_db = api.DeviceBuffer(qdb.nbytes)
+            try:
+                d_db.upload(qdb)
+                check(self.lib.vdb_merkle_tree_build_dev(d_db.ptr, self.n, self.dim, self.d_levels0.ptr))
+                api.sync()
+            finally:
+                d_db.free()
+
+    def _circuit_size(self):
+        cells, n_in = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self.lib.vdb_wit_merkle_update_size(self.n, self.dim, self.m, ctypes.byref(cells), ctypes.byref(n_in)))
+        return n_in.value, cells.value - n_in.value, 0
+
+    def _alloc_outputs(self):
+        self.d_pub = self._output((3 * self.m + 2) * B)
+
+    def _witness(self, sel=None):
+        # the call writes the assigned witnesses too (old leaves and siblings come out of its value pass); every run starts from the
+        # tree before the batch, so that the keygen-style runs and the proof state the same update
+        check(self.lib.vdb_memcpy_d2d(self.d_levels.ptr, self.d_levels0.ptr, ctypes.c_size_t(2 * self.lp * B)))
+        with self._window(sel, 0, lookup=False):
+            check(self.lib.vdb_wit_merkle_update_dev(self.d_levels.ptr, self.n, self.dim, self.d_vec.ptr, api._p(self.indices), self.m, self.d_stream.ptr,
+                                                     self._sel_at(sel, 0), self.d_pub.ptr))
+
+    def public_values_dev(self):
+        return self.d_pub.ptr, 3 * self.m + 2
+
+    def results(self):
+        """(old root (4,), indices (m, 4), old leaves (m, 4), new leaves (m, 4), new root (4,))"""
+        pub = self.d_pub.download((3 * self.m + 2, 4))
+        per = pub[1:-1].reshape(self.m, 3, 4)
+        return pub[0], per[:, 0], per[:, 1], per[:, 2], pub[-1]
+
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        cm, pub = CS.build_merkle_update(self.m, self.dim, self.depth, functools.partial(self._fetch_flags, d_flags), self._fetch,
+                                         builder=DeviceBuilder if on_device else None)
+        assert cm.n_cells == self.n_cells
+        return cm, pub, None
+
+
 class NearestHotPath(HotPath):
     """nearest_vector(query, vectors) (src/gadget/vectordb.rs:122-163; tests/vectordb/mod.rs:220-247 assigns the query, then the
     vectors) through the same hot path.  Sharded: every rank computes the N distances' values and the short minimum

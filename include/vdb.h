@@ -230,6 +230,36 @@ int vdb_wit_kmeans_dev(int metric, uint32_t precision_bits, uint32_t lookup_bits
 int vdb_wit_merkle_size(size_t n, size_t dim, int zero_cached, uint64_t *cells);
 int vdb_wit_merkle(const vdb_fr *vectors, size_t n, size_t dim, int zero_cached, vdb_fr *stream_out, uint8_t *selector_out, vdb_fr *root_out);
 int vdb_wit_merkle_dev(const vdb_fr *vectors_dev, size_t n, size_t dim, int zero_cached, vdb_fr *stream_dev, uint8_t *selector_dev, vdb_fr *root_dev);
+/* The tree of merkle_commitment (src/gadget/vectordb.rs:165-223) kept on the device, values only: levels_dev receives the digests of every
+ * level one after the other — the lp = next_power_of_two(n) leaf digests (the padding leaves 0), then lp / 2 nodes, ..., the root at
+ * entry 2 lp - 2; 2 lp entries are written (the last is 0).  A service keeps this buffer between batches of updates and never rehashes
+ * the database. */
+int vdb_merkle_tree_build_dev(const vdb_fr *vectors_dev, size_t n, size_t dim, vdb_fr *levels_dev);
+/* Inserts and replacements proved against the committed root: a batch of m Merkle path updates (indices[j], new vector j), applied in
+ * order.  The reference has no such gadget; the cells are those of the closure a user of its chips writes.  depth = log2(lp) >= 1.
+ * Stream, from cell 0: the assigned witnesses — the m new vectors (m x dim), m old leaves, per update the depth index bits (least
+ * significant first), per update the depth siblings (leaf level first): input_cells of them — then per update j
+ *   new_leaf = poseidon.clear(); update(new_vector_j); squeeze()               (the leaf hash of merkle_commitment)
+ *   per level l: gate.assert_bit(b_l); lo = select(sib_l, cur_old, b_l); ro = select(cur_old, sib_l, b_l); cur_old = H(lo, ro);
+ *                ln = select(sib_l, cur_new, b_l); rn = select(cur_new, sib_l, b_l); cur_new = H(ln, rn)      (9,048 cells a level)
+ *   idx = gate.inner_product(bits, Constant(2^l))                              (1 + 3 (depth - 1) cells)
+ * with H the node hash of merkle_commitment.  The circuit ties cur_old at the top of update j to cur_new at the top of update j - 1
+ * (a copy constraint, no cells).  public 3 m + 2 values: [old root | idx_j, old_leaf_j, new_leaf_j per update | new root].
+ * An insert is an update of a padding slot (old leaf 0).  Updates of one batch see each other (repeated slots, sibling slots); the
+ * result is that of applying them one after the other.  levels (vdb_merkle_tree_build_dev's layout) is read and left in the state
+ * after the batch.  indices is a HOST array in both forms (it is checked before anything is launched).
+ * The number of kernel launches depends on depth, not on m.  The _dev form honours vdb_wit_set_window like vdb_wit_merkle_dev.
+ * Work space: 32 B x m x (3 (dim / 2 + 1) + 4 depth + 3) plus 5 B per (update, level).
+ * Limits of one call (VDB_ERR_ARG beyond them, as for m == 0, depth == 0 (n == 1) and an index >= lp, before anything is launched):
+ * m at most VDB_MERKLE_UPDATE_MAX_UPDATES (the batch's indices are scanned in LDS), depth at most 30, all cells at most
+ * VDB_MERKLE_UPDATE_MAX_CELLS.  Deleting a vector, growing the tree past lp and a stand-alone membership proof are not provided. */
+#define VDB_MERKLE_UPDATE_MAX_UPDATES ((size_t)4096)
+#define VDB_MERKLE_UPDATE_MAX_CELLS ((uint64_t)1 << 34)
+int vdb_wit_merkle_update_size(size_t n, size_t dim, size_t m, uint64_t *cells, uint64_t *input_cells);
+int vdb_wit_merkle_update(vdb_fr *levels, size_t n, size_t dim, const vdb_fr *new_vectors, const uint64_t *indices, size_t m, vdb_fr *stream_out,
+                          uint8_t *selector_out, vdb_fr *public_out);
+int vdb_wit_merkle_update_dev(vdb_fr *levels_dev, size_t n, size_t dim, const vdb_fr *new_vectors_dev, const uint64_t *indices, size_t m,
+                              vdb_fr *stream_dev, uint8_t *selector_dev, vdb_fr *public_dev);
 
 /* ---- b4 stream -> columns: replaces halo2-base GateThreadBuilder::assign_all (break points, keygen)
  *      and assign_threads_in (prover) as driven by RangeCircuitBuilder::prover(builder, break_points)

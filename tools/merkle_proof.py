@@ -8,7 +8,9 @@ vectors, result vector and root public; `--lookup-bits`, `--metric`): e.g. the i
 `--circuit query --n 5000 --k 18 --lookup-bits 17 --block-cols 126 --ext-block-cols 64`.  With `--queries Q` (Q > 1) the query circuit
 holds Q queries against the one database — nearest_vector per query, one merkle_commitment, the Q result vectors and the root public
 (pipeline.BatchQueryHotPath); with `--topk T` (T > 1) every query asks for its T nearest vectors, nearest first
-(pipeline.TopKQueryHotPath)."""
+(pipeline.TopKQueryHotPath).
+`--circuit update --updates M` proves M inserts / replacements against the committed root of the n x dim database instead
+(pipeline.UpdateHotPath: M Merkle path updates, [old root | idx, old leaf, new leaf per update | new root] public)."""
 import argparse
 import json
 import os
@@ -19,7 +21,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from halo2_vectordb_amd import api  # noqa: E402
-from halo2_vectordb_amd.pipeline import BatchQueryHotPath, MerkleHotPath, QueryHotPath, TopKQueryHotPath  # noqa: E402
+from halo2_vectordb_amd.pipeline import BatchQueryHotPath, MerkleHotPath, QueryHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
 from halo2_vectordb_amd.rounds import ProverRounds, quotient_identity_holds  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -30,11 +32,12 @@ ap.add_argument("--seed", type=int, default=20260003)
 ap.add_argument("--block-cols", type=int, default=510)
 ap.add_argument("--ext-block-cols", type=int, default=None)
 ap.add_argument("--proofs", type=int, default=2)
-ap.add_argument("--circuit", default="merkle", choices=["merkle", "query"])
+ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update"])
 ap.add_argument("--lookup-bits", type=int, default=13)
 ap.add_argument("--metric", default="euclidean")
 ap.add_argument("--queries", type=int, default=1, help="--circuit query: queries proved against the one database in this proof")
 ap.add_argument("--topk", type=int, default=1, help="--circuit query: nearest vectors proved per query, nearest first")
+ap.add_argument("--updates", type=int, default=8, help="--circuit update: inserts / replacements proved in this proof")
 ap.add_argument("--out", default=None, help="write the proof (io.write_snark) and the verifying key beside it")
 args = ap.parse_args()
 
@@ -48,6 +51,8 @@ if args.circuit == "query" and args.topk > 1:
     hp = TopKQueryHotPath(topk=args.topk, q=args.queries, n=args.n, dim=args.dim, k=args.k, L=args.lookup_bits, metric=args.metric, seed=args.seed)
 elif args.circuit == "query" and args.queries > 1:
     hp = BatchQueryHotPath(q=args.queries, n=args.n, dim=args.dim, k=args.k, L=args.lookup_bits, metric=args.metric, seed=args.seed)
+elif args.circuit == "update":
+    hp = UpdateHotPath(n=args.n, dim=args.dim, m=args.updates, k=args.k, seed=args.seed)
 elif args.circuit == "query":
     hp = QueryHotPath(n=args.n, dim=args.dim, k=args.k, L=args.lookup_bits, metric=args.metric, seed=args.seed)
 else:
@@ -72,13 +77,14 @@ wall, host_ms, out = best
 T = {}
 pr.prove(None, timings=T)
 ok = quotient_identity_holds(pr, out["challenges"], out["evals"], out["instances"])
-root = api.fr_to_canonical(np.asarray(hp.results()[-1] if args.circuit == "query" else hp.results()).reshape(1, 4))[0]
+root = api.fr_to_canonical(np.asarray(hp.results() if args.circuit == "merkle" else hp.results()[-1]).reshape(1, 4))[0]
 root_int = int(root[0]) | int(root[1]) << 64 | int(root[2]) << 128 | int(root[3]) << 192
 if args.out:
     from halo2_vectordb_amd.io import write_snark
     write_snark(args.out, out["proof"], out["instances"])
     pr.save_verifying_key(args.out + ".vk.npz", opened=out["opened"])
 what = f"merkle_commitment {args.n}x{args.dim} k={args.k}" if args.circuit == "merkle" else \
+    f"{args.updates} Merkle path updates against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "update" else \
     f"query circuit ({str(args.queries) + ' x ' if args.queries > 1 else ''}{'top-' + str(args.topk) + ' ' if args.topk > 1 else ''}nearest_vector {args.metric} + merkle_commitment) over {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}"
 print(json.dumps({"workload": what + ": whole constraint map, public outputs in the instance column, transcript, fresh blinds, SHPLONK", "lookup_cells": hp.n_lookup,
                   "cells": hp.n_cells, "columns": hp.n_cols, "product_sets": pr.n_sets, "mock_report_on_keygen_witness": pr.keygen_report.as_dict(),
