@@ -340,39 +340,19 @@ def wit_window(adv, lookup):
 
 
 def wit_nearest(metric, query, vectors, P=48, L=13, selectors=False):
-    lib = _lib.init()
-    query, vectors = _fr(query), _fr(vectors)
-    n, dim = vectors.shape[0], vectors.shape[1]
-    cells, lk = _u64(), _u64()
-    check(lib.vdb_wit_nearest_size(METRICS[metric], ctypes.c_uint32(P), ctypes.c_uint32(L), _sz(n), _sz(dim), ctypes.byref(cells), ctypes.byref(lk)))
-    stream = np.zeros((cells.value, 4), dtype=np.uint64)
-    lookup = np.zeros((lk.value, 4), dtype=np.uint64)
-    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
-    ind = np.zeros((n, 4), dtype=np.uint64)
-    res = np.zeros((dim, 4), dtype=np.uint64)
-    check(lib.vdb_wit_nearest(METRICS[metric], ctypes.c_uint32(P), ctypes.c_uint32(L), _p(query), _p(vectors), _sz(n), _sz(dim), _p(stream), _p(lookup),
-                              _p(sel) if selectors else None, _p(ind), _p(res)))
-    return dict(stream=stream, lookup=lookup, **_split_flags(sel), indicator=ind, result=res)
+    """nearest_vector(query (dim, 4), vectors (n, dim, 4)): wit_nearest_batch of the one query; dict(stream, lookup, selectors,
+    indicator (n, 4), result (dim, 4))"""
+    out = wit_nearest_batch(metric, _fr(query)[None], vectors, P, L, selectors)
+    out["indicator"], out["result"] = out.pop("indicators")[0], out.pop("results")[0]
+    return out
 
 
 def wit_nearest_batch(metric, queries, vectors, P=48, L=13, selectors=False):
     """nearest_vector of every row of `queries` (q, dim, 4) over the one database `vectors` (n, dim, 4), the calls end to end in the
-    streams (vdb_wit_nearest_batch): dict(stream, lookup, selectors, indicators (q, n, 4), results (q, dim, 4))"""
-    lib = _lib.init()
-    queries, vectors = _fr(queries), _fr(vectors)
-    q, n, dim = queries.shape[0], vectors.shape[0], vectors.shape[1]
-    assert queries.shape[1] == dim
-    cells, lk = _u64(), _u64()
-    check(lib.vdb_wit_nearest_batch_size(METRICS[metric], ctypes.c_uint32(P), ctypes.c_uint32(L), _sz(q), _sz(n), _sz(dim), ctypes.byref(cells),
-                                         ctypes.byref(lk)))
-    stream = np.zeros((cells.value, 4), dtype=np.uint64)
-    lookup = np.zeros((lk.value, 4), dtype=np.uint64)
-    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
-    ind = np.zeros((q, n, 4), dtype=np.uint64)
-    res = np.zeros((q, dim, 4), dtype=np.uint64)
-    check(lib.vdb_wit_nearest_batch(METRICS[metric], ctypes.c_uint32(P), ctypes.c_uint32(L), _p(queries), _p(vectors), _sz(q), _sz(n), _sz(dim),
-                                    _p(stream), _p(lookup), _p(sel) if selectors else None, _p(ind), _p(res)))
-    return dict(stream=stream, lookup=lookup, **_split_flags(sel), indicators=ind, results=res)
+    streams: wit_nearest_topk's one round; dict(stream, lookup, selectors, indicators (q, n, 4), results (q, dim, 4))"""
+    out = wit_nearest_topk(metric, queries, vectors, 1, P, L, selectors)
+    out["indicators"], out["results"] = out["indicators"][:, 0], out["results"][:, 0]
+    return out
 
 
 def wit_nearest_topk(metric, queries, vectors, topk, P=48, L=13, selectors=False):

@@ -710,89 +710,15 @@ def _distance_block(metric, dim, P, L):
     return Block(s, [out])
 
 
-def build_nearest(metric, n, dim, P, L, builder=None, extra_cells=0, finish=True):
-    """nearest_vector(query, vectors) after [query | vectors] have been assigned (tests/vectordb/mod.rs:220-247): the map the
-    whole-circuit trace gives, assembled from one distance block, one qmin block and the closing cells.  `extra_cells`: room for a
-    gadget that follows in the same stream (the query circuit's merkle_commitment); with finish=False the builder itself is returned,
-    (builder, outputs, cells used so far), for the caller to go on placing"""
-    db = _distance_block(metric, dim, P, L)
-    s = Sym(P, L)
-    qm = Block(s, [s.qmin(ext(0), ext(1))])
-    n_in = (n + 1) * dim
-    dist0, qmin0 = n_in, n_in + n * db.n
-    iseq0 = qmin0 + (n - 1) * qm.n
-    sel0 = iseq0 + 12 * n
-    total = sel0 + dim * (1 + 3 * n)
-    B = (builder or _Builder)(total + extra_cells, n * db.n_lk + (n - 1) * qm.n_lk)
-    query = np.arange(dim, dtype=np.int64)
-    vec = dim + np.arange(n * dim, dtype=np.int64).reshape(n, dim)
-    i = np.arange(n, dtype=np.int64)
-    d = B.place(db, dist0 + i * db.n, i * db.n_lk, np.concatenate([vec, np.broadcast_to(query, (n, dim))], axis=1))[:, 0]
-    acc = np.empty(n, dtype=np.int64)
-    acc[0] = d[0]
-    if n > 1:
-        j = np.arange(n - 1, dtype=np.int64)
-        outs = qmin0 + j * qm.n + qm.outs[0]
-        acc[1:] = outs
-        B.place(qm, qmin0 + j * qm.n, n * db.n_lk + j * qm.n_lk, np.stack([acc[:-1], d[1:]], axis=1))
-    s = Sym(P, L)
-    ie = Block(s, [s.g_is_equal(ext(0), ext(1))])
-    ind = B.place(ie, iseq0 + 12 * i, np.zeros(n, dtype=np.int64), np.stack([np.full(n, acc[-1]), d], axis=1))[:, 0]
-    s = Sym(P, L)
-    sb = Block(s, [s.g_select_by_indicator([ext(k) for k in range(n)], [ext(n + k) for k in range(n)])])
-    jd = np.arange(dim, dtype=np.int64)
-    res = B.place(sb, sel0 + jd * (1 + 3 * n), np.zeros(dim, dtype=np.int64), np.concatenate([vec.T, np.broadcast_to(ind, (dim, n))], axis=1))[:, 0]
-    if not finish:
-        return B, (ind, res), total
-    return B.finish(), (ind, res)
-
-
-def build_nearest_batch(metric, q, n, dim, P, L, builder=None, extra_cells=0, finish=True):
-    """q x nearest_vector(query_i, vectors) after [queries | vectors] have been assigned, in the stream order of witness.hip
-    (wit_nearest_batch_dev): query i's block — n distances, n - 1 qmin, n is_equal, dim select_by_indicator — starts i blocks behind the
-    first, its lookup cells i runs behind.  Every query's distances copy the same database cells and that query's own; outputs
-    (indicators (q, n), results (q, dim)).  `builder`, `extra_cells`, `finish`: as for build_nearest."""
-    db = _distance_block(metric, dim, P, L)
-    s = Sym(P, L)
-    qm = Block(s, [s.qmin(ext(0), ext(1))])
-    s = Sym(P, L)
-    ie = Block(s, [s.g_is_equal(ext(0), ext(1))])
-    s = Sym(P, L)
-    sb = Block(s, [s.g_select_by_indicator([ext(k) for k in range(n)], [ext(n + k) for k in range(n)])])
-    n_in = (q + n) * dim
-    qmin_off = n * db.n
-    iseq_off = qmin_off + (n - 1) * qm.n
-    sel_off = iseq_off + 12 * n
-    per_q, per_q_l = sel_off + dim * (1 + 3 * n), n * db.n_lk + (n - 1) * qm.n_lk
-    total = n_in + q * per_q
-    B = (builder or _Builder)(total + extra_cells, q * per_q_l)
-    queries = np.arange(q * dim, dtype=np.int64).reshape(q, dim)
-    vec = q * dim + np.arange(n * dim, dtype=np.int64).reshape(n, dim)
-    qq, ii = np.repeat(np.arange(q, dtype=np.int64), n), np.tile(np.arange(n, dtype=np.int64), q)
-    base, lbase = n_in + qq * per_q, qq * per_q_l
-    d = B.place(db, base + ii * db.n, lbase + ii * db.n_lk, np.concatenate([vec[ii], queries[qq]], axis=1))[:, 0].reshape(q, n)
-    acc = np.empty((q, n), dtype=np.int64)
-    acc[:, 0] = d[:, 0]
-    if n > 1:
-        qj, j = np.repeat(np.arange(q, dtype=np.int64), n - 1), np.tile(np.arange(n - 1, dtype=np.int64), q)
-        bases = n_in + qj * per_q + qmin_off + j * qm.n
-        acc[:, 1:] = (bases + qm.outs[0]).reshape(q, n - 1)
-        B.place(qm, bases, qj * per_q_l + n * db.n_lk + j * qm.n_lk, np.stack([acc[:, :-1].reshape(-1), d[:, 1:].reshape(-1)], axis=1))
-    ind = B.place(ie, base + iseq_off + 12 * ii, np.zeros(q * n, dtype=np.int64), np.stack([acc[qq, n - 1], d.reshape(-1)], axis=1))[:, 0].reshape(q, n)
-    qd, jd = np.repeat(np.arange(q, dtype=np.int64), dim), np.tile(np.arange(dim, dtype=np.int64), q)
-    res = B.place(sb, n_in + qd * per_q + sel_off + jd * (1 + 3 * n), np.zeros(q * dim, dtype=np.int64),
-                  np.concatenate([vec.T[jd], ind[qd]], axis=1))[:, 0].reshape(q, dim)
-    if not finish:
-        return B, (ind, res), total
-    return B.finish(), (ind, res)
-
-
 def build_nearest_topk(metric, q, n, dim, topk, P, L, builder=None, extra_cells=0, finish=True):
-    """q x Sym.nearest_topk(query_i, vectors, topk) after [queries | vectors] have been assigned, in the stream order of witness.hip
-    (wit_nearest_topk_dev): query i's block is its n distances, then per round n - 1 qmin, n is_equal, dim select_by_indicator and —
+    """q x Sym.nearest_topk(query_i, vectors, topk) after [queries | vectors] have been assigned (tests/vectordb/mod.rs:220-247 assigns
+    the query, then the vectors), in the stream order of witness.hip (wit_nearest_dev): the map the whole-circuit trace gives, assembled
+    from one block per gadget.  Query i's block is its n distances, then per round n - 1 qmin, n is_equal, dim select_by_indicator and —
     before every round but the first — the n select(Constant(M), cur, ind) of the round before; the lookup cells are the distance runs,
     then the qmin runs round by round.  M is a constant of the map (a fixed-column value), tied to the cell that holds it in every
-    select.  Outputs (indicators (q, topk, n), results (q, topk, dim)).  `builder`, `extra_cells`, `finish`: as for build_nearest."""
+    select.  Outputs (indicators (q, topk, n), results (q, topk, dim)).  `extra_cells`: room for a gadget that follows in the same stream
+    (the query circuits' merkle_commitment); with finish=False the builder itself is returned, (builder, outputs, cells used so far), for
+    the caller to go on placing."""
     if not 1 <= topk <= n:
         raise ValueError("topk must be at least 1 and at most n")
     db = _distance_block(metric, dim, P, L)
@@ -842,6 +768,22 @@ def build_nearest_topk(metric, q, n, dim, topk, P, L, builder=None, extra_cells=
     if not finish:
         return B, outs, total
     return B.finish(), outs
+
+
+def _squeeze(built, axes):
+    """a build_nearest_topk result with the axes of length one in `axes` taken out of its (indicators, results)"""
+    return (built[0], tuple(np.squeeze(o, axis=axes) for o in built[1])) + tuple(built[2:])
+
+
+def build_nearest_batch(metric, q, n, dim, P, L, builder=None, extra_cells=0, finish=True):
+    """q x nearest_vector(query_i, vectors): build_nearest_topk at topk = 1, which emits no select(M, ..) and names no constant M;
+    outputs (indicators (q, n), results (q, dim))"""
+    return _squeeze(build_nearest_topk(metric, q, n, dim, 1, P, L, builder=builder, extra_cells=extra_cells, finish=finish), 1)
+
+
+def build_nearest(metric, n, dim, P, L, builder=None, extra_cells=0, finish=True):
+    """nearest_vector(query, vectors): build_nearest_topk at q = topk = 1; outputs (indicators (n,), result (dim,))"""
+    return _squeeze(build_nearest_topk(metric, 1, n, dim, 1, P, L, builder=builder, extra_cells=extra_cells, finish=finish), (0, 1))
 
 
 def build_kmeans(metric, n, dim, K, I, P, L, builder=None):

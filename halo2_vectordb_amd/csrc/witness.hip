@@ -634,62 +634,22 @@ static int run_distances(const Streams& st, FpEntry* fp, const DistLayout& dl, c
   return VDB_OK;
 }
 
-// ------------------------------------------------------------------ nearest_vector (vectordb.rs:122-163)
-__global__ void k_nv_prefix_min(const FpTables* __restrict__ T, const u256* __restrict__ d, uint32_t n, u256* __restrict__ pm) {
-  if (blockIdx.x || threadIdx.x) return;
-  WCtx c{};
-  Gadgets g(c);
-  u256 m = d[0];
-  pm[0] = m;
-  for (uint32_t i = 1; i < n; i++) {
-    u256 x = d[i];
-    if (!g.v_is_neg(from_mont<Fr>(fr_sub(m, x)))) m = x;  // qmin(m, x) = is_neg(m - x) ? m : x
-    pm[i] = m;
-  }
-}
-__global__ __launch_bounds__(64) void k_nv_qmin(Streams st, const FpTables* __restrict__ T, uint64_t base, uint64_t lbase, const u256* __restrict__ d,
-                                                const u256* __restrict__ pm, uint32_t n) {
-  uint32_t i = blockIdx.x * 64 + threadIdx.x + 1;
-  if (i >= n) return;
-  WCtx c = make_ctx(st, T, base + (uint64_t)(i - 1) * T->sz.qmin[0], lbase + (uint64_t)(i - 1) * T->sz.qmin[1]);
-  Gadgets g(c);
-  g.fp_qmin(pm[i - 1], d[i]);
-}
-__global__ __launch_bounds__(64) void k_nv_is_equal(Streams st, const FpTables* __restrict__ T, uint64_t base, const u256* __restrict__ d,
-                                                    const u256* __restrict__ pm, uint32_t n, u256* __restrict__ ind) {
-  uint32_t i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= n) return;
-  WCtx c = make_ctx(st, T, base + 12ull * i, 0);
-  Gadgets g(c);
-  ind[i] = g.g_is_equal(pm[n - 1], d[i]);
-}
-// select_by_indicator per dimension: [0, a0, ind0, s0, a1, ind1, s1, ...]
-__global__ __launch_bounds__(64) void k_nv_select(Streams st, const FpTables* __restrict__ T, uint64_t base, const u256* __restrict__ vectors,
-                                                  const u256* __restrict__ ind, uint32_t n, uint32_t D, u256* __restrict__ result) {
-  uint32_t j = blockIdx.x * 64 + threadIdx.x;
-  if (j >= D) return;
-  WCtx c = make_ctx(st, T, base + (uint64_t)j * (1 + 3ull * n), 0);
-  u256 s = u256_zero();
-  c.push(s, n > 0);
-  for (uint32_t i = 0; i < n; i++) {
-    u256 a = vectors[(size_t)i * D + j], in = ind[i];
-    if (!u256_is_zero(in)) s = a;
-    c.push(a, false);
-    c.push(in, false);
-    c.push(s, i + 1 < n);
-  }
-  result[j] = s;
-}
-
-// ------------------------------------------------------------------ nearest_vector for a batch of queries over one database
-// (vectordb.rs:122-163 once per query, the calls end to end in the stream).  Query q's block starts q * (cells of one nearest_vector)
-// behind the first; its distances, prefix minima and indicators sit at [q * n, (q + 1) * n) of the value arrays.
-struct NvBatch {
+// ------------------------------------------------------------------ nearest_vector (vectordb.rs:122-163): the t nearest vectors of
+// every one of Q queries over one database, the queries' blocks end to end in the stream.  t = 1 is nearest_vector itself, once per query
+// (no select(M, ..) is emitted); Q = t = 1 is the reference's single call.
+// Per query: the n distances, then t rounds of [n - 1 qmin | n is_equal | D select_by_indicator | n select(Constant(M), cur_i, ind_i)],
+// the last round without its select(M, ..) blocks.  M = 2^(2P) - 1 takes a round's winners out of the next round's minimum.  Round r of
+// query q keeps its prefix minima at [(q * t + r) * n, + n) of `pm`; `rnd[q * n + i]` is the first round whose mask replaced entry i
+// (NV_UNMASKED: none), so that the entry a round works on is cur_r,i = rnd < r ? M : d_i.
+constexpr uint32_t NV_UNMASKED = 0xffffffffu;
+struct NvMap {
   uint64_t adv0, lk0;          // first cell / lookup cell of query 0's block
-  uint64_t per_q, per_q_l;     // cells / lookup cells of one nearest_vector
-  uint64_t qmin_off, qmin_loff, iseq_off, sel_off;   // where the closing stages start inside a block
-  uint32_t Q, n, D;
+  uint64_t per_q, per_q_l;     // cells / lookup cells of one query's block
+  uint64_t rounds_off, rounds_loff, per_r, per_r_l;   // where round 0 starts inside a block; cells / lookup cells of a round that masks
+  uint64_t iseq_off, sel_off, mask_off;               // where the stages after the qmin chain start inside a round
+  uint32_t Q, n, D, t;
 };
+__device__ __forceinline__ u256 nv_mask_value(const FpTables* T) { return fr_sub(T->pow2[2 * T->P], mont_one<Fr>()); }
 // qmin(m, x) as a value (vectordb.rs:141-145 folds it over the distances): is_neg(m - x) ? m : x
 __device__ __forceinline__ u256 nv_vmin(const Gadgets& g, const u256& m, const u256& x) {
   return g.v_is_neg(from_mont<Fr>(fr_sub(m, x))) ? m : x;
@@ -706,129 +666,25 @@ __device__ __forceinline__ u256 wave_bcast(const u256& v, int lane) {
   for (int k = 0; k < 8; k++) o.w[k] = __shfl(v.w[k], lane, 64);
   return o;
 }
-// The prefix minima of every query's qmin chain: one wavefront per query, an inclusive scan over 64 distances at a time with the
-// running minimum carried from tile to tile.  Over values the range checks admit, v_is_neg(m - x) is a total order and the scan IS the
-// serial fold (ties: equal values, equal bits).  Over anything else (field elements no fixed-point value quantizes to) the relation
-// need not be transitive, so every lane checks the fold's own recurrence pm[i] == qmin(pm[i - 1], d[i]) on what the scan produced —
-// which, with pm[0] == d[0], characterises the serial walk — and a query that fails it is walked serially by lane 0.
-__global__ __launch_bounds__(64) void k_nvb_prefix_min(const FpTables* __restrict__ T, const u256* __restrict__ d, uint32_t n, u256* __restrict__ pm) {
-  const uint32_t q = blockIdx.x, lane = threadIdx.x;
-  const u256* dq = d + (size_t)q * n;
-  u256* pq = pm + (size_t)q * n;
-  WCtx c{};
-  Gadgets g(c);
-  u256 carry = u256_zero();
-  bool ok = true;
-  for (uint32_t c0 = 0; c0 < n; c0 += 64) {
-    const uint32_t i = c0 + lane;
-    const bool live = i < n;
-    const u256 x = dq[live ? i : n - 1];      // padding lanes repeat the last distance: a minimum does not change under it
-    u256 v = x;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const u256 o = wave_shfl_up(v, off);
-      if ((int)lane >= off) v = nv_vmin(g, o, v);
-    }
-    if (c0) v = nv_vmin(g, carry, v);
-    u256 prev = wave_shfl_up(v, 1);
-    if (lane == 0) prev = carry;
-    if (live) {
-      ok = ok && u256_eq(v, i == 0 ? x : nv_vmin(g, prev, x));
-      pq[i] = v;
-    }
-    carry = wave_bcast(v, 63);
-  }
-  if (!__all((int)ok) && lane == 0) {
-    u256 m = dq[0];
-    pq[0] = m;
-    for (uint32_t i = 1; i < n; i++) {
-      m = nv_vmin(g, m, dq[i]);
-      pq[i] = m;
-    }
-  }
-}
-// lanes = (query, link of its chain): qmin(pm[i - 1], d[i]), i = 1 .. n - 1
-__global__ __launch_bounds__(64) void k_nvb_qmin(Streams st, const FpTables* __restrict__ T, NvBatch nb, const u256* __restrict__ d,
-                                                 const u256* __restrict__ pm) {
-  const uint64_t t = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-  const uint32_t links = nb.n - 1;
-  if (t >= (uint64_t)nb.Q * links) return;
-  const uint32_t q = (uint32_t)(t / links), i = (uint32_t)(t % links) + 1;
-  WCtx c = make_ctx(st, T, nb.adv0 + q * nb.per_q + nb.qmin_off + (uint64_t)(i - 1) * T->sz.qmin[0],
-                    nb.lk0 + q * nb.per_q_l + nb.qmin_loff + (uint64_t)(i - 1) * T->sz.qmin[1]);
-  Gadgets g(c);
-  g.fp_qmin(pm[(size_t)q * nb.n + i - 1], d[(size_t)q * nb.n + i]);
-}
-// lanes = (query, vector): is_equal(min_q, d_i)
-__global__ __launch_bounds__(64) void k_nvb_is_equal(Streams st, const FpTables* __restrict__ T, NvBatch nb, const u256* __restrict__ d,
-                                                     const u256* __restrict__ pm, u256* __restrict__ ind) {
-  const uint64_t t = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-  if (t >= (uint64_t)nb.Q * nb.n) return;
-  const uint32_t q = (uint32_t)(t / nb.n), i = (uint32_t)(t % nb.n);
-  WCtx c = make_ctx(st, T, nb.adv0 + q * nb.per_q + nb.iseq_off + 12ull * i, 0);
-  Gadgets g(c);
-  ind[t] = g.g_is_equal(pm[(size_t)q * nb.n + nb.n - 1], d[t]);
-}
-// select_by_indicator per (query, dimension), the walk over the n vectors cut into `S` segments: lanes = (query, segment, dimension),
-// the dimension fastest so that a wavefront reads consecutive elements of one vector.  The running value at a segment's start is the
-// element of the last vector before it whose indicator is set (0 when there is none), found by walking the indicators backwards.
-__global__ __launch_bounds__(64) void k_nvb_select(Streams st, const FpTables* __restrict__ T, NvBatch nb, uint32_t S, const u256* __restrict__ vectors,
-                                                   const u256* __restrict__ ind, u256* __restrict__ result) {
-  const uint64_t t = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-  const uint32_t n = nb.n, D = nb.D;
-  if (t >= (uint64_t)nb.Q * S * D) return;
-  const uint32_t j = (uint32_t)(t % D), sg = (uint32_t)((t / D) % S), q = (uint32_t)(t / ((uint64_t)D * S));
-  const uint32_t i0 = (uint32_t)((uint64_t)n * sg / S), i1 = (uint32_t)((uint64_t)n * (sg + 1) / S);
-  const u256* indq = ind + (size_t)q * n;
-  const uint64_t base = nb.adv0 + q * nb.per_q + nb.sel_off + (uint64_t)j * (1 + 3ull * n);
-  u256 s = u256_zero();
-  for (uint32_t i = i0; i-- > 0;) {
-    if (!u256_is_zero(indq[i])) {
-      s = vectors[(size_t)i * D + j];
-      break;
-    }
-  }
-  WCtx c = make_ctx(st, T, base + (i0 ? 1 + 3ull * i0 : 0), 0);
-  if (i0 == 0) c.push(s, n > 0);
-  for (uint32_t i = i0; i < i1; i++) {
-    u256 a = vectors[(size_t)i * D + j], in = indq[i];
-    if (!u256_is_zero(in)) s = a;
-    c.push(a, false);
-    c.push(in, false);
-    c.push(s, i + 1 < n);
-  }
-  if (sg == S - 1) result[(size_t)q * D + j] = s;
-}
-
-// ------------------------------------------------------------------ the t nearest vectors of every query (top-k over one database)
-// Per query: the n distances, then t rounds of [n - 1 qmin | n is_equal | D select_by_indicator | n select(Constant(M), cur_i, ind_i)],
-// the last round without its select(M, ..) blocks.  M = 2^(2P) - 1 takes a round's winners out of the next round's minimum.  Round r of
-// query q keeps its prefix minima at [(q * t + r) * n, + n) of `pm`; `rnd[q * n + i]` is the first round whose mask replaced entry i
-// (NV_UNMASKED: none), so that the entry a round works on is cur_r,i = rnd < r ? M : d_i.
-constexpr uint32_t NV_UNMASKED = 0xffffffffu;
-struct NvTopk {
-  uint64_t adv0, lk0;          // first cell / lookup cell of query 0's block
-  uint64_t per_q, per_q_l;     // cells / lookup cells of one query's block
-  uint64_t rounds_off, rounds_loff, per_r, per_r_l;   // where round 0 starts inside a block; cells / lookup cells of a round that masks
-  uint64_t iseq_off, sel_off, mask_off;               // where the stages after the qmin chain start inside a round
-  uint32_t Q, n, D, t;
-};
-__device__ __forceinline__ u256 nvt_mask_value(const FpTables* T) { return fr_sub(T->pow2[2 * T->P], mont_one<Fr>()); }
-__device__ __forceinline__ u256 nvt_cur(const u256* __restrict__ dq, const uint32_t* __restrict__ rq, uint32_t i, uint32_t r, const u256& M) {
+__device__ __forceinline__ u256 nv_cur(const u256* __restrict__ dq, const uint32_t* __restrict__ rq, uint32_t i, uint32_t r, const u256& M) {
   return rq[i] < r ? M : dq[i];
 }
-// All t rounds of a query's values, one wavefront per query: per round the tiled scan of k_nvb_prefix_min over the entries the earlier
-// rounds left (with its check of the serial recurrence and the serial walk where it fails), the round's minimum to every lane, and the
-// entries whose bits equal it marked as masked from the next round on.  Lanes past the end of a tile hold M: a live lane only ever
-// reads lower lanes, and the carry is taken from a full tile.
-__global__ __launch_bounds__(64) void k_nvt_rounds(const FpTables* __restrict__ T, const u256* __restrict__ d, uint32_t n, uint32_t t,
+// All t rounds of a query's values, one wavefront per query.  Per round: the prefix minima of the qmin chain over the entries the
+// earlier rounds left — an inclusive scan over 64 entries at a time, the running minimum carried from tile to tile — the round's
+// minimum to every lane, and the entries whose bits equal it marked as masked from the next round on.  Over values the range checks
+// admit, v_is_neg(m - x) is a total order and the scan IS the serial fold (ties: equal values, equal bits).  Over anything else (field
+// elements no fixed-point value quantizes to) the relation need not be transitive, so every lane checks the fold's own recurrence
+// pm[i] == qmin(pm[i - 1], cur_i) on what the scan produced — which, with pm[0] == cur_0, characterises the serial walk — and a round
+// that fails it is walked serially by lane 0.  Lanes past the end of a tile hold M: a live lane only ever reads lower lanes, and the
+// carry is taken from a full tile.
+__global__ __launch_bounds__(64) void k_nv_rounds(const FpTables* __restrict__ T, const u256* __restrict__ d, uint32_t n, uint32_t t,
                                                    u256* __restrict__ pm, uint32_t* __restrict__ rnd) {
   const uint32_t q = blockIdx.x, lane = threadIdx.x;
   const u256* dq = d + (size_t)q * n;
   uint32_t* rq = rnd + (size_t)q * n;
   WCtx c{};
   Gadgets g(c);
-  const u256 M = nvt_mask_value(T);
+  const u256 M = nv_mask_value(T);
   for (uint32_t i = lane; i < n; i += 64) rq[i] = NV_UNMASKED;
   for (uint32_t r = 0; r < t; r++) {
     u256* pq = pm + ((size_t)q * t + r) * n;
@@ -837,7 +693,7 @@ __global__ __launch_bounds__(64) void k_nvt_rounds(const FpTables* __restrict__ 
     for (uint32_t c0 = 0; c0 < n; c0 += 64) {
       const uint32_t i = c0 + lane;
       const bool live = i < n;
-      const u256 x = live ? nvt_cur(dq, rq, i, r, M) : M;
+      const u256 x = live ? nv_cur(dq, rq, i, r, M) : M;
       u256 v = x;
 #pragma unroll
       for (int off = 1; off < 64; off <<= 1) {
@@ -856,10 +712,10 @@ __global__ __launch_bounds__(64) void k_nvt_rounds(const FpTables* __restrict__ 
     u256 m = carry;
     if (!__all((int)ok)) {
       if (lane == 0) {
-        m = nvt_cur(dq, rq, 0, r, M);
+        m = nv_cur(dq, rq, 0, r, M);
         pq[0] = m;
         for (uint32_t i = 1; i < n; i++) {
-          m = nv_vmin(g, m, nvt_cur(dq, rq, i, r, M));
+          m = nv_vmin(g, m, nv_cur(dq, rq, i, r, M));
           pq[i] = m;
         }
       }
@@ -874,53 +730,55 @@ __global__ __launch_bounds__(64) void k_nvt_rounds(const FpTables* __restrict__ 
   }
 }
 // lanes = (query, round, link of the round's chain): qmin(pm[i - 1], cur_i), i = 1 .. n - 1
-__global__ __launch_bounds__(64) void k_nvt_qmin(Streams st, const FpTables* __restrict__ T, NvTopk nt, const u256* __restrict__ d,
+__global__ __launch_bounds__(64) void k_nv_qmin(Streams st, const FpTables* __restrict__ T, NvMap nm, const u256* __restrict__ d,
                                                  const u256* __restrict__ pm, const uint32_t* __restrict__ rnd) {
   const uint64_t th = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-  const uint32_t links = nt.n - 1;
-  if (th >= (uint64_t)nt.Q * nt.t * links) return;
-  const uint32_t i = (uint32_t)(th % links) + 1, r = (uint32_t)((th / links) % nt.t), q = (uint32_t)(th / ((uint64_t)links * nt.t));
-  WCtx c = make_ctx(st, T, nt.adv0 + q * nt.per_q + nt.rounds_off + r * nt.per_r + (uint64_t)(i - 1) * T->sz.qmin[0],
-                    nt.lk0 + q * nt.per_q_l + nt.rounds_loff + r * nt.per_r_l + (uint64_t)(i - 1) * T->sz.qmin[1]);
+  const uint32_t links = nm.n - 1;
+  if (th >= (uint64_t)nm.Q * nm.t * links) return;
+  const uint32_t i = (uint32_t)(th % links) + 1, r = (uint32_t)((th / links) % nm.t), q = (uint32_t)(th / ((uint64_t)links * nm.t));
+  WCtx c = make_ctx(st, T, nm.adv0 + q * nm.per_q + nm.rounds_off + r * nm.per_r + (uint64_t)(i - 1) * T->sz.qmin[0],
+                    nm.lk0 + q * nm.per_q_l + nm.rounds_loff + r * nm.per_r_l + (uint64_t)(i - 1) * T->sz.qmin[1]);
   Gadgets g(c);
-  const u256 M = nvt_mask_value(T);
-  g.fp_qmin(pm[((size_t)q * nt.t + r) * nt.n + i - 1], nvt_cur(d + (size_t)q * nt.n, rnd + (size_t)q * nt.n, i, r, M));
+  const u256 M = nv_mask_value(T);
+  g.fp_qmin(pm[((size_t)q * nm.t + r) * nm.n + i - 1], nv_cur(d + (size_t)q * nm.n, rnd + (size_t)q * nm.n, i, r, M));
 }
 // lanes = (query, round, vector): is_equal(min_r, cur_i)
-__global__ __launch_bounds__(64) void k_nvt_is_equal(Streams st, const FpTables* __restrict__ T, NvTopk nt, const u256* __restrict__ d,
+__global__ __launch_bounds__(64) void k_nv_is_equal(Streams st, const FpTables* __restrict__ T, NvMap nm, const u256* __restrict__ d,
                                                      const u256* __restrict__ pm, const uint32_t* __restrict__ rnd, u256* __restrict__ ind) {
   const uint64_t th = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-  if (th >= (uint64_t)nt.Q * nt.t * nt.n) return;
-  const uint32_t i = (uint32_t)(th % nt.n), r = (uint32_t)((th / nt.n) % nt.t), q = (uint32_t)(th / ((uint64_t)nt.n * nt.t));
-  WCtx c = make_ctx(st, T, nt.adv0 + q * nt.per_q + nt.rounds_off + r * nt.per_r + nt.iseq_off + 12ull * i, 0);
+  if (th >= (uint64_t)nm.Q * nm.t * nm.n) return;
+  const uint32_t i = (uint32_t)(th % nm.n), r = (uint32_t)((th / nm.n) % nm.t), q = (uint32_t)(th / ((uint64_t)nm.n * nm.t));
+  WCtx c = make_ctx(st, T, nm.adv0 + q * nm.per_q + nm.rounds_off + r * nm.per_r + nm.iseq_off + 12ull * i, 0);
   Gadgets g(c);
-  const u256 M = nvt_mask_value(T);
-  ind[th] = g.g_is_equal(pm[((size_t)q * nt.t + r) * nt.n + nt.n - 1], nvt_cur(d + (size_t)q * nt.n, rnd + (size_t)q * nt.n, i, r, M));
+  const u256 M = nv_mask_value(T);
+  ind[th] = g.g_is_equal(pm[((size_t)q * nm.t + r) * nm.n + nm.n - 1], nv_cur(d + (size_t)q * nm.n, rnd + (size_t)q * nm.n, i, r, M));
 }
 // lanes = (query, round before the last, vector): select(Constant(M), cur_i, ind_i), the entry the next round works on
-__global__ __launch_bounds__(64) void k_nvt_mask(Streams st, const FpTables* __restrict__ T, NvTopk nt, const u256* __restrict__ d,
+__global__ __launch_bounds__(64) void k_nv_mask(Streams st, const FpTables* __restrict__ T, NvMap nm, const u256* __restrict__ d,
                                                  const uint32_t* __restrict__ rnd, const u256* __restrict__ ind) {
   const uint64_t th = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-  const uint32_t masking = nt.t - 1;
-  if (th >= (uint64_t)nt.Q * masking * nt.n) return;
-  const uint32_t i = (uint32_t)(th % nt.n), r = (uint32_t)((th / nt.n) % masking), q = (uint32_t)(th / ((uint64_t)nt.n * masking));
-  WCtx c = make_ctx(st, T, nt.adv0 + q * nt.per_q + nt.rounds_off + r * nt.per_r + nt.mask_off + 8ull * i, 0);
+  const uint32_t masking = nm.t - 1;
+  if (th >= (uint64_t)nm.Q * masking * nm.n) return;
+  const uint32_t i = (uint32_t)(th % nm.n), r = (uint32_t)((th / nm.n) % masking), q = (uint32_t)(th / ((uint64_t)nm.n * masking));
+  WCtx c = make_ctx(st, T, nm.adv0 + q * nm.per_q + nm.rounds_off + r * nm.per_r + nm.mask_off + 8ull * i, 0);
   Gadgets g(c);
-  const u256 M = nvt_mask_value(T);
-  g.g_select(M, nvt_cur(d + (size_t)q * nt.n, rnd + (size_t)q * nt.n, i, r, M), ind[((size_t)q * nt.t + r) * nt.n + i]);
+  const u256 M = nv_mask_value(T);
+  g.g_select(M, nv_cur(d + (size_t)q * nm.n, rnd + (size_t)q * nm.n, i, r, M), ind[((size_t)q * nm.t + r) * nm.n + i]);
 }
-// select_by_indicator per (query, round, dimension), the walk cut into `S` segments as in k_nvb_select: lanes = (query, round, segment,
-// dimension), the dimension fastest
-__global__ __launch_bounds__(64) void k_nvt_select(Streams st, const FpTables* __restrict__ T, NvTopk nt, uint32_t S, const u256* __restrict__ vectors,
+// select_by_indicator per (query, round, dimension): [0, a0, ind0, s0, a1, ind1, s1, ...], the walk over the n vectors cut into `S`
+// segments: lanes = (query, round, segment, dimension), the dimension fastest so that a wavefront reads consecutive elements of one
+// vector.  The running value at a segment's start is the element of the last vector before it whose indicator is set (0 when there is
+// none), found by walking the indicators backwards.
+__global__ __launch_bounds__(64) void k_nv_select(Streams st, const FpTables* __restrict__ T, NvMap nm, uint32_t S, const u256* __restrict__ vectors,
                                                    const u256* __restrict__ ind, u256* __restrict__ result) {
   const uint64_t th = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-  const uint32_t n = nt.n, D = nt.D;
-  if (th >= (uint64_t)nt.Q * nt.t * S * D) return;
+  const uint32_t n = nm.n, D = nm.D;
+  if (th >= (uint64_t)nm.Q * nm.t * S * D) return;
   const uint32_t j = (uint32_t)(th % D), sg = (uint32_t)((th / D) % S), qr = (uint32_t)(th / ((uint64_t)D * S));
-  const uint32_t q = qr / nt.t, r = qr % nt.t;
+  const uint32_t q = qr / nm.t, r = qr % nm.t;
   const uint32_t i0 = (uint32_t)((uint64_t)n * sg / S), i1 = (uint32_t)((uint64_t)n * (sg + 1) / S);
   const u256* indq = ind + (size_t)qr * n;
-  const uint64_t base = nt.adv0 + q * nt.per_q + nt.rounds_off + r * nt.per_r + nt.sel_off + (uint64_t)j * (1 + 3ull * n);
+  const uint64_t base = nm.adv0 + q * nm.per_q + nm.rounds_off + r * nm.per_r + nm.sel_off + (uint64_t)j * (1 + 3ull * n);
   u256 s = u256_zero();
   for (uint32_t i = i0; i-- > 0;) {
     if (!u256_is_zero(indq[i])) {
@@ -1613,10 +1471,12 @@ int wit_fp_op_dev(FpEntry* fp, int op, const u256* a, const u256* b, size_t n, S
   return inv_list_fixup(st);
 }
 
+// the block of one query with `topk` rounds (include/vdb.h vdb_wit_nearest_topk): the distances, then per round the qmin chain, the
+// is_equal blocks, the select_by_indicator walks and the select(M, ..) blocks, which the last round does not emit
 struct NvLayout {
-  uint64_t dist, dist_l, qmin, qmin_l, iseq, sel, total, total_l;
+  uint64_t dist, dist_l, qmin, qmin_l, iseq, sel, mask, per_r, total, total_l;
 };
-static int nv_layout(FpEntry* fp, int metric, size_t n, size_t dim, DistLayout* dl, NvLayout* o) {
+static int nv_layout(FpEntry* fp, int metric, size_t n, size_t dim, size_t topk, DistLayout* dl, NvLayout* o) {
   TRY(dist_layout(fp->host, metric, dim, dl));
   o->dist = n * dl->total_cells;
   o->dist_l = n * dl->total_lk;
@@ -1624,194 +1484,92 @@ static int nv_layout(FpEntry* fp, int metric, size_t n, size_t dim, DistLayout* 
   o->qmin_l = (n - 1) * (uint64_t)fp->host.sz.qmin[1];
   o->iseq = 12ull * n;
   o->sel = dim * (1 + 3ull * n);
-  o->total = o->dist + o->qmin + o->iseq + o->sel;
-  o->total_l = o->dist_l + o->qmin_l;
-  return VDB_OK;
-}
-int wit_nearest_dev(FpEntry* fp, int metric, const u256* query, const u256* vectors, size_t n, size_t dim, Streams st, uint64_t adv_off,
-                    uint64_t lk_off, u256* ind, u256* result) {
-  DistLayout dl;
-  NvLayout nl;
-  TRY(nv_layout(fp, metric, n, dim, &dl, &nl));
-  TRY(inv_list_attach(st, nl.total));
-  TRY(set_winv(st, fp->dev));
-  InstMap im{adv_off, lk_off, 1, dl.total_cells, dl.total_lk, 0xffffffffu, 0xffffffffu};  // (vector_i, query)
-  u256* mid = (u256*)scratch_get(0, (n * 5 + 8) * sizeof(u256));
-  if (!mid) return VDB_ERR_OOM;
-  u256* dist = mid + 3 * n;
-  u256* pm = dist + n;
-  TRY(run_distances(st, fp, dl, im, (uint32_t)n, vectors, query, mid, dist));
-  hipStream_t s = ctx().stream;
-  {
-    VDB_PROF("k_nv_prefix_min");
-    hipLaunchKernelGGL(k_nv_prefix_min, dim3(1), dim3(1), 0, s, fp->dev, dist, (uint32_t)n, pm);
-  }
-  VDB_LAUNCH_CHECK();
-  if (n > 1) {
-    {
-      VDB_PROF("k_nv_qmin");
-      hipLaunchKernelGGL(k_nv_qmin, dim3((unsigned)((n - 1 + 63) / 64)), dim3(64), 0, s, st, fp->dev, adv_off + nl.dist, lk_off + nl.dist_l, dist, pm,
-                       (uint32_t)n);
-    }
-    VDB_LAUNCH_CHECK();
-  }
-  {
-    VDB_PROF("k_nv_is_equal");
-    hipLaunchKernelGGL(k_nv_is_equal, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, st, fp->dev, adv_off + nl.dist + nl.qmin, dist, pm, (uint32_t)n,
-                     ind);
-  }
-  VDB_LAUNCH_CHECK();
-  {
-    VDB_PROF("k_nv_select");
-    hipLaunchKernelGGL(k_nv_select, dim3((unsigned)((dim + 63) / 64)), dim3(64), 0, s, st, fp->dev, adv_off + nl.dist + nl.qmin + nl.iseq, vectors, ind,
-                     (uint32_t)n, (uint32_t)dim, result);
-  }
-  VDB_LAUNCH_CHECK();
-  return inv_list_fixup(st);
-}
-
-// what one batch call may hold (include/vdb.h VDB_NEAREST_BATCH_MAX_*): the instance numbers of the distance kernels and the lane numbers
-// of the closing stages are 32-bit, the work space is 160 B per (query, vector), and the deferred-inversion counter is 32-bit (an
-// is_zero block of eight cells defers at most one inverse, so 2^34 cells stay far below its wrap)
-static int nv_batch_fits(size_t Q, size_t n, size_t dim, uint64_t per_q) {
-  if (Q > VDB_NEAREST_BATCH_MAX_INSTANCES || n > VDB_NEAREST_BATCH_MAX_INSTANCES / Q || dim > VDB_NEAREST_BATCH_MAX_INSTANCES / Q ||
-      per_q > VDB_NEAREST_BATCH_MAX_CELLS / Q) {
-    set_error("nearest_vector batch too large for one call: n_queries * n and n_queries * dim at most 2^24, cells at most 2^34 (include/vdb.h)");
-    return VDB_ERR_ARG;
-  }
-  return VDB_OK;
-}
-// segments of the select's walk over the n vectors: enough lanes to give every CU a few wavefronts, no segment below eight vectors
-static uint32_t nv_select_segments(size_t Q, size_t n, size_t dim) {
-  const uint64_t lanes = (uint64_t)Q * dim, want = (uint64_t)ctx().cu_count * 4 * 64;
-  uint64_t s = (want + lanes - 1) / lanes, cap = n / 8;
-  if (s > cap) s = cap;
-  return s < 1 ? 1u : (uint32_t)s;
-}
-// Q x nearest_vector(query_q, vectors), block q at adv_off + q * (cells of one): the distances of all queries in one run_distances
-// (instance t = q * n + i is distance(vector_i, query_q)), then one launch per closing stage — the launch count does not depend on Q
-int wit_nearest_batch_dev(FpEntry* fp, int metric, const u256* queries, const u256* vectors, size_t Q, size_t n, size_t dim, Streams st,
-                          uint64_t adv_off, uint64_t lk_off, u256* ind, u256* result) {
-  DistLayout dl;
-  NvLayout nl;
-  TRY(nv_layout(fp, metric, n, dim, &dl, &nl));
-  TRY(nv_batch_fits(Q, n, dim, nl.total));
-  TRY(inv_list_attach(st, Q * nl.total));
-  TRY(set_winv(st, fp->dev));
-  const size_t inst = Q * n;
-  InstMap im{adv_off, lk_off, (uint32_t)n, nl.total, nl.total_l, (uint32_t)n, (uint32_t)n};  // (vector_{t % n}, query_{t / n})
-  u256* mid = (u256*)scratch_get(0, (inst * 5 + 8) * sizeof(u256));
-  if (!mid) return VDB_ERR_OOM;
-  u256* dist = mid + 3 * inst;
-  u256* pm = dist + inst;
-  TRY(run_distances(st, fp, dl, im, (uint32_t)inst, vectors, queries, mid, dist));
-  const NvBatch nb{adv_off, lk_off, nl.total, nl.total_l, nl.dist, nl.dist_l, nl.dist + nl.qmin, nl.dist + nl.qmin + nl.iseq, (uint32_t)Q, (uint32_t)n,
-                   (uint32_t)dim};
-  hipStream_t s = ctx().stream;
-  {
-    VDB_PROF("k_nvb_prefix_min");
-    hipLaunchKernelGGL(k_nvb_prefix_min, dim3((unsigned)Q), dim3(64), 0, s, fp->dev, dist, (uint32_t)n, pm);
-  }
-  VDB_LAUNCH_CHECK();
-  if (n > 1) {
-    {
-      VDB_PROF("k_nvb_qmin");
-      hipLaunchKernelGGL(k_nvb_qmin, dim3((unsigned)((Q * (n - 1) + 63) / 64)), dim3(64), 0, s, st, fp->dev, nb, dist, pm);
-    }
-    VDB_LAUNCH_CHECK();
-  }
-  {
-    VDB_PROF("k_nvb_is_equal");
-    hipLaunchKernelGGL(k_nvb_is_equal, dim3((unsigned)((inst + 63) / 64)), dim3(64), 0, s, st, fp->dev, nb, dist, pm, ind);
-  }
-  VDB_LAUNCH_CHECK();
-  {
-    const uint32_t S = nv_select_segments(Q, n, dim);
-    VDB_PROF("k_nvb_select");
-    hipLaunchKernelGGL(k_nvb_select, dim3((unsigned)((Q * dim * S + 63) / 64)), dim3(64), 0, s, st, fp->dev, nb, S, vectors, ind, result);
-  }
-  VDB_LAUNCH_CHECK();
-  return inv_list_fixup(st);
-}
-
-// the block of one query with `topk` rounds (include/vdb.h vdb_wit_nearest_topk): NvLayout's stages, the closing ones once per round
-struct NvTopkLayout {
-  uint64_t per_r, mask, total, total_l;
-};
-static void nv_topk_layout(const NvLayout& nl, size_t n, size_t topk, NvTopkLayout* o) {
   o->mask = 8ull * n;
-  o->per_r = nl.qmin + nl.iseq + nl.sel + o->mask;
-  o->total = nl.dist + topk * o->per_r - o->mask;     // the last round emits no select(M, ..)
-  o->total_l = nl.dist_l + topk * nl.qmin_l;
+  o->per_r = o->qmin + o->iseq + o->sel + o->mask;
+  o->total = o->dist + topk * o->per_r - o->mask;
+  o->total_l = o->dist_l + topk * o->qmin_l;
+  return VDB_OK;
 }
-// what one top-k call may hold (include/vdb.h VDB_NEAREST_TOPK_MAX_*): lane numbers over (query, round, vector) and (query, round,
-// dimension) are 32-bit before the segments multiply them, the work space is 32 B per (query, round, vector) and 164 B per (query,
-// vector), and the deferred-inversion counter is 32-bit as in nv_batch_fits
-static int nv_topk_fits(size_t Q, size_t n, size_t dim, size_t topk, const NvLayout& nl) {
+// what one call may hold (include/vdb.h VDB_NEAREST_TOPK_MAX_*): the instance numbers of the distance kernels are 32-bit, and so are
+// the lane numbers over (query, round, vector) and (query, round, dimension) before the segments multiply them; the work space is 32 B
+// per (query, round, vector) and 132 B per (query, vector); the deferred-inversion counter is 32-bit (an is_zero block of eight cells
+// defers at most one inverse, so 2^34 cells stay far below its wrap).
+// At topk = 1 this refuses exactly the calls whose n_queries * n or n_queries * dim exceed 2^24 or whose cells exceed 2^34, the limit
+// of the batch entry points: the last term is that cell limit, and the two before it follow from it — nl.dist is part of the cells,
+// and the round's 8 n select(M, ..) cells, which the last round does not emit, are at most nl.dist, because one distance block has
+// at least 8 cells (dist_layout: for dim >= 1 the smallest, Manhattan's, is 4 dim + dim qabs + 1, and the entry points that run ask
+// for dim >= 1).
+// The single-query entry points share the limit.  No call that could run is refused by it: 2^34 cells are 512 GiB of advice stream,
+// more than the card's 288 GB of memory, and n or dim above 2^24 with one distance block per vector passes 2^34 cells far earlier.
+static int nv_fits(size_t Q, size_t n, size_t dim, size_t topk, const NvLayout& nl) {
   if (topk == 0 || topk > n) {
     set_error("top-k: topk must be at least 1 and at most n");
     return VDB_ERR_ARG;
   }
   const size_t cap = VDB_NEAREST_TOPK_MAX_INSTANCES;
-  const uint64_t round_cells = nl.qmin + nl.iseq + nl.sel + 8ull * n;
   if (Q > cap || topk > cap / Q || n > cap / (Q * topk) || dim > cap / (Q * topk) || nl.dist > VDB_NEAREST_TOPK_MAX_CELLS / Q ||
-      round_cells > VDB_NEAREST_TOPK_MAX_CELLS / (Q * topk) || Q * (nl.dist + topk * round_cells - 8ull * n) > VDB_NEAREST_TOPK_MAX_CELLS) {
-    set_error("top-k query too large for one call: n_queries * topk * n and n_queries * topk * dim at most 2^24, cells at most 2^34 (include/vdb.h)");
+      nl.per_r > VDB_NEAREST_TOPK_MAX_CELLS / (Q * topk) || Q * nl.total > VDB_NEAREST_TOPK_MAX_CELLS) {
+    set_error("nearest_vector call too large: n_queries * topk * n and n_queries * topk * dim at most 2^24, cells at most 2^34 (include/vdb.h)");
     return VDB_ERR_ARG;
   }
   return VDB_OK;
 }
+// segments of the select's walk over the n vectors: enough lanes to give every CU a few wavefronts, no segment below eight vectors
+static uint32_t nv_select_segments(size_t QT, size_t n, size_t dim) {
+  const uint64_t lanes = (uint64_t)QT * dim, want = (uint64_t)ctx().cu_count * 4 * 64;
+  uint64_t s = (want + lanes - 1) / lanes, cap = n / 8;
+  if (s > cap) s = cap;
+  return s < 1 ? 1u : (uint32_t)s;
+}
 // Q x [n distances, then topk rounds of qmin chain / is_equal / select_by_indicator / mask], block q at adv_off + q * (cells of one):
-// one run_distances over Q x n instances, one value kernel that runs every round of every query, and one launch per emitting stage —
-// the launch count depends on neither Q nor topk
-int wit_nearest_topk_dev(FpEntry* fp, int metric, const u256* queries, const u256* vectors, size_t Q, size_t n, size_t dim, size_t topk, Streams st,
-                         uint64_t adv_off, uint64_t lk_off, u256* ind, u256* result) {
+// one run_distances over Q x n instances (instance t = q * n + i is distance(vector_i, query_q)), one value kernel that runs every
+// round of every query, and one launch per emitting stage — the launch count depends on neither Q nor topk
+int wit_nearest_dev(FpEntry* fp, int metric, const u256* queries, const u256* vectors, size_t Q, size_t n, size_t dim, size_t topk, Streams st,
+                    uint64_t adv_off, uint64_t lk_off, u256* ind, u256* result) {
   DistLayout dl;
   NvLayout nl;
-  NvTopkLayout tl;
-  TRY(nv_layout(fp, metric, n, dim, &dl, &nl));
-  TRY(nv_topk_fits(Q, n, dim, topk, nl));
-  nv_topk_layout(nl, n, topk, &tl);
-  TRY(inv_list_attach(st, Q * tl.total));
+  TRY(nv_layout(fp, metric, n, dim, topk, &dl, &nl));
+  TRY(nv_fits(Q, n, dim, topk, nl));
+  TRY(inv_list_attach(st, Q * nl.total));
   TRY(set_winv(st, fp->dev));
   const size_t inst = Q * n, rinst = inst * topk;
-  InstMap im{adv_off, lk_off, (uint32_t)n, tl.total, tl.total_l, (uint32_t)n, (uint32_t)n};  // (vector_{t % n}, query_{t / n})
+  InstMap im{adv_off, lk_off, (uint32_t)n, nl.total, nl.total_l, (uint32_t)n, (uint32_t)n};  // (vector_{t % n}, query_{t / n})
   u256* mid = (u256*)scratch_get(0, (inst * 4 + rinst + 8) * sizeof(u256) + inst * sizeof(uint32_t));
   if (!mid) return VDB_ERR_OOM;
   u256* dist = mid + 3 * inst;
   u256* pm = dist + inst;
   uint32_t* rnd = (uint32_t*)(pm + rinst + 8);
   TRY(run_distances(st, fp, dl, im, (uint32_t)inst, vectors, queries, mid, dist));
-  const NvTopk nt{adv_off, lk_off, tl.total, tl.total_l, nl.dist, nl.dist_l, tl.per_r, nl.qmin_l, nl.qmin, nl.qmin + nl.iseq,
-                  nl.qmin + nl.iseq + nl.sel, (uint32_t)Q, (uint32_t)n, (uint32_t)dim, (uint32_t)topk};
+  const NvMap nm{adv_off, lk_off, nl.total, nl.total_l, nl.dist, nl.dist_l, nl.per_r, nl.qmin_l, nl.qmin, nl.qmin + nl.iseq,
+                 nl.qmin + nl.iseq + nl.sel, (uint32_t)Q, (uint32_t)n, (uint32_t)dim, (uint32_t)topk};
   hipStream_t s = ctx().stream;
   {
-    VDB_PROF("k_nvt_rounds");
-    hipLaunchKernelGGL(k_nvt_rounds, dim3((unsigned)Q), dim3(64), 0, s, fp->dev, dist, (uint32_t)n, (uint32_t)topk, pm, rnd);
+    VDB_PROF("k_nv_rounds");
+    hipLaunchKernelGGL(k_nv_rounds, dim3((unsigned)Q), dim3(64), 0, s, fp->dev, dist, (uint32_t)n, (uint32_t)topk, pm, rnd);
   }
   VDB_LAUNCH_CHECK();
   if (n > 1) {
     {
-      VDB_PROF("k_nvt_qmin");
-      hipLaunchKernelGGL(k_nvt_qmin, dim3((unsigned)((Q * topk * (n - 1) + 63) / 64)), dim3(64), 0, s, st, fp->dev, nt, dist, pm, rnd);
+      VDB_PROF("k_nv_qmin");
+      hipLaunchKernelGGL(k_nv_qmin, dim3((unsigned)((Q * topk * (n - 1) + 63) / 64)), dim3(64), 0, s, st, fp->dev, nm, dist, pm, rnd);
     }
     VDB_LAUNCH_CHECK();
   }
   {
-    VDB_PROF("k_nvt_is_equal");
-    hipLaunchKernelGGL(k_nvt_is_equal, dim3((unsigned)((rinst + 63) / 64)), dim3(64), 0, s, st, fp->dev, nt, dist, pm, rnd, ind);
+    VDB_PROF("k_nv_is_equal");
+    hipLaunchKernelGGL(k_nv_is_equal, dim3((unsigned)((rinst + 63) / 64)), dim3(64), 0, s, st, fp->dev, nm, dist, pm, rnd, ind);
   }
   VDB_LAUNCH_CHECK();
   {
     // launched for topk == 1 too (one wavefront that finds no lane of its own): the launch count of a call does not depend on topk
-    VDB_PROF("k_nvt_mask");
-    hipLaunchKernelGGL(k_nvt_mask, dim3((unsigned)((inst * (topk - 1) + 63) / 64 + (topk == 1))), dim3(64), 0, s, st, fp->dev, nt, dist, rnd, ind);
+    VDB_PROF("k_nv_mask");
+    hipLaunchKernelGGL(k_nv_mask, dim3((unsigned)((inst * (topk - 1) + 63) / 64 + (topk == 1))), dim3(64), 0, s, st, fp->dev, nm, dist, rnd, ind);
   }
   VDB_LAUNCH_CHECK();
   {
     const uint32_t S = nv_select_segments(Q * topk, n, dim);
-    VDB_PROF("k_nvt_select");
-    hipLaunchKernelGGL(k_nvt_select, dim3((unsigned)((Q * topk * dim * S + 63) / 64)), dim3(64), 0, s, st, fp->dev, nt, S, vectors, ind, result);
+    VDB_PROF("k_nv_select");
+    hipLaunchKernelGGL(k_nv_select, dim3((unsigned)((Q * topk * dim * S + 63) / 64)), dim3(64), 0, s, st, fp->dev, nm, S, vectors, ind, result);
   }
   VDB_LAUNCH_CHECK();
   return inv_list_fixup(st);
@@ -2301,107 +2059,8 @@ int vdb_wit_fp_op_dev(int op, uint32_t P, uint32_t L, const vdb_fr* a_dev, const
   return check_err_flag(derr);
 }
 
-int vdb_wit_nearest_size(int metric, uint32_t P, uint32_t L, size_t n, size_t dim, uint64_t* cells, uint64_t* lookups) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(n > 0, "empty database");
-  FpEntry* fp;
-  TRY(get_fp(P, L, &fp));
-  DistLayout dl;
-  NvLayout nl;
-  TRY(nv_layout(fp, metric, n, dim, &dl, &nl));
-  if (cells) *cells = nl.total;
-  if (lookups) *lookups = nl.total_l;
-  return VDB_OK;
-}
-int vdb_wit_nearest(int metric, uint32_t P, uint32_t L, const vdb_fr* query, const vdb_fr* vectors, size_t n, size_t dim, vdb_fr* stream_out,
-                    vdb_fr* lookup_out, uint8_t* selector_out, vdb_fr* indicator_out, vdb_fr* result_out) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(query && vectors && n > 0 && dim > 0, "null pointer or empty input");
-  FpEntry* fp;
-  TRY(get_fp(P, L, &fp));
-  uint64_t cells, lookups;
-  TRY(vdb_wit_nearest_size(metric, P, L, n, dim, &cells, &lookups));
-  DevBuf dq, dv, dind, dres;
-  HostStreams hs;
-  TRY(upload(dq, query, dim * sizeof(u256)));
-  TRY(upload(dv, vectors, n * dim * sizeof(u256)));
-  TRY(dind.alloc(n * sizeof(u256)));
-  TRY(dres.alloc(dim * sizeof(u256)));
-  TRY(hs.init(cells, lookups, selector_out != nullptr));
-  TRY(wit_nearest_dev(fp, metric, dq.as<u256>(), dv.as<u256>(), n, dim, hs.st, 0, 0, dind.as<u256>(), dres.as<u256>()));
-  TRY(download(indicator_out, dind.p, n * sizeof(u256)));
-  TRY(download(result_out, dres.p, dim * sizeof(u256)));
-  return hs.finish(stream_out, lookup_out, selector_out, cells, lookups);
-}
-
-int vdb_wit_nearest_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* query_dev, const vdb_fr* vectors_dev, size_t n, size_t dim, vdb_fr* stream_dev,
-                        vdb_fr* lookup_dev, uint8_t* selector_dev, vdb_fr* indicator_dev, vdb_fr* result_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(query_dev && vectors_dev && stream_dev && lookup_dev && indicator_dev && result_dev && n > 0 && dim > 0, "null pointer or empty input");
-  FpEntry* fp;
-  TRY(get_fp(P, L, &fp));
-  int* derr = (int*)scratch_get(1, 64);
-  if (!derr) return VDB_ERR_OOM;
-  VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
-  // the rank window (vdb_wit_set_window): a rank stores the cells of its own columns — the distances, N-way parallel and nearly all of
-  // the cells, exit early outside it — while every rank computes every value (the N distances, the short minimum chain)
-  Streams st{as_u256(stream_dev), selector_dev, as_u256(lookup_dev), derr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], g_win[2], g_win[3]};
-  TRY(wit_nearest_dev(fp, metric, as_u256(query_dev), as_u256(vectors_dev), n, dim, st, 0, 0, as_u256(indicator_dev), as_u256(result_dev)));
-  return check_err_flag(derr);
-}
-
-// nearest_vector (vectordb.rs:122-163) for n_queries queries over one database, the calls end to end in the streams
-int vdb_wit_nearest_batch_size(int metric, uint32_t P, uint32_t L, size_t n_queries, size_t n, size_t dim, uint64_t* cells, uint64_t* lookups) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(n_queries > 0 && n > 0, "no query or empty database");
-  FpEntry* fp;
-  TRY(get_fp(P, L, &fp));
-  DistLayout dl;
-  NvLayout nl;
-  TRY(nv_layout(fp, metric, n, dim, &dl, &nl));
-  TRY(nv_batch_fits(n_queries, n, dim, nl.total));
-  if (cells) *cells = n_queries * nl.total;
-  if (lookups) *lookups = n_queries * nl.total_l;
-  return VDB_OK;
-}
-int vdb_wit_nearest_batch(int metric, uint32_t P, uint32_t L, const vdb_fr* queries, const vdb_fr* vectors, size_t n_queries, size_t n, size_t dim,
-                          vdb_fr* stream_out, vdb_fr* lookup_out, uint8_t* selector_out, vdb_fr* indicators_out, vdb_fr* results_out) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(queries && vectors && n_queries > 0 && n > 0 && dim > 0, "null pointer or empty input");
-  FpEntry* fp;
-  TRY(get_fp(P, L, &fp));
-  uint64_t cells, lookups;
-  TRY(vdb_wit_nearest_batch_size(metric, P, L, n_queries, n, dim, &cells, &lookups));
-  DevBuf dq, dv, dind, dres;
-  HostStreams hs;
-  TRY(upload(dq, queries, n_queries * dim * sizeof(u256)));
-  TRY(upload(dv, vectors, n * dim * sizeof(u256)));
-  TRY(dind.alloc(n_queries * n * sizeof(u256)));
-  TRY(dres.alloc(n_queries * dim * sizeof(u256)));
-  TRY(hs.init(cells, lookups, selector_out != nullptr));
-  TRY(wit_nearest_batch_dev(fp, metric, dq.as<u256>(), dv.as<u256>(), n_queries, n, dim, hs.st, 0, 0, dind.as<u256>(), dres.as<u256>()));
-  TRY(download(indicators_out, dind.p, n_queries * n * sizeof(u256)));
-  TRY(download(results_out, dres.p, n_queries * dim * sizeof(u256)));
-  return hs.finish(stream_out, lookup_out, selector_out, cells, lookups);
-}
-int vdb_wit_nearest_batch_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* queries_dev, const vdb_fr* vectors_dev, size_t n_queries, size_t n,
-                              size_t dim, vdb_fr* stream_dev, vdb_fr* lookup_dev, uint8_t* selector_dev, vdb_fr* indicators_dev, vdb_fr* results_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(queries_dev && vectors_dev && stream_dev && lookup_dev && indicators_dev && results_dev && n_queries > 0 && n > 0 && dim > 0,
-          "null pointer or empty input");
-  FpEntry* fp;
-  TRY(get_fp(P, L, &fp));
-  int* derr = (int*)scratch_get(1, 64);
-  if (!derr) return VDB_ERR_OOM;
-  VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
-  // the rank window as in vdb_wit_nearest_dev: every rank computes every value, a rank stores the cells inside its window
-  Streams st{as_u256(stream_dev), selector_dev, as_u256(lookup_dev), derr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], g_win[2], g_win[3]};
-  TRY(wit_nearest_batch_dev(fp, metric, as_u256(queries_dev), as_u256(vectors_dev), n_queries, n, dim, st, 0, 0, as_u256(indicators_dev),
-                            as_u256(results_dev)));
-  return check_err_flag(derr);
-}
-
-// the topk nearest vectors of every query (include/vdb.h): nearest_vector's distances, then its closing stages once per round
+// the topk nearest vectors of every one of n_queries queries (include/vdb.h): nearest_vector's distances, then its closing stages once per
+// round.  The batch entry points are these at topk = 1, the single-query ones at n_queries = 1 too.
 int vdb_wit_nearest_topk_size(int metric, uint32_t P, uint32_t L, size_t n_queries, size_t n, size_t dim, size_t topk, uint64_t* cells,
                               uint64_t* lookups) {
   VDB_REQUIRE_INIT();
@@ -2410,12 +2069,10 @@ int vdb_wit_nearest_topk_size(int metric, uint32_t P, uint32_t L, size_t n_queri
   TRY(get_fp(P, L, &fp));
   DistLayout dl;
   NvLayout nl;
-  NvTopkLayout tl;
-  TRY(nv_layout(fp, metric, n, dim, &dl, &nl));
-  TRY(nv_topk_fits(n_queries, n, dim, topk, nl));
-  nv_topk_layout(nl, n, topk, &tl);
-  if (cells) *cells = n_queries * tl.total;
-  if (lookups) *lookups = n_queries * tl.total_l;
+  TRY(nv_layout(fp, metric, n, dim, topk, &dl, &nl));
+  TRY(nv_fits(n_queries, n, dim, topk, nl));
+  if (cells) *cells = n_queries * nl.total;
+  if (lookups) *lookups = n_queries * nl.total_l;
   return VDB_OK;
 }
 int vdb_wit_nearest_topk(int metric, uint32_t P, uint32_t L, const vdb_fr* queries, const vdb_fr* vectors, size_t n_queries, size_t n, size_t dim,
@@ -2433,7 +2090,7 @@ int vdb_wit_nearest_topk(int metric, uint32_t P, uint32_t L, const vdb_fr* queri
   TRY(dind.alloc(n_queries * topk * n * sizeof(u256)));
   TRY(dres.alloc(n_queries * topk * dim * sizeof(u256)));
   TRY(hs.init(cells, lookups, selector_out != nullptr));
-  TRY(wit_nearest_topk_dev(fp, metric, dq.as<u256>(), dv.as<u256>(), n_queries, n, dim, topk, hs.st, 0, 0, dind.as<u256>(), dres.as<u256>()));
+  TRY(wit_nearest_dev(fp, metric, dq.as<u256>(), dv.as<u256>(), n_queries, n, dim, topk, hs.st, 0, 0, dind.as<u256>(), dres.as<u256>()));
   TRY(download(indicators_out, dind.p, n_queries * topk * n * sizeof(u256)));
   TRY(download(results_out, dres.p, n_queries * topk * dim * sizeof(u256)));
   return hs.finish(stream_out, lookup_out, selector_out, cells, lookups);
@@ -2450,11 +2107,39 @@ int vdb_wit_nearest_topk_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* q
   int* derr = (int*)scratch_get(1, 64);
   if (!derr) return VDB_ERR_OOM;
   VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
-  // the rank window as in vdb_wit_nearest_batch_dev: every rank computes every value, a rank stores the cells inside its window
+  // the rank window (vdb_wit_set_window): a rank stores the cells of its own columns — the distances, N-way parallel and nearly all of
+  // the cells, exit early outside it — while every rank computes every value (the distances, the short minimum chains)
   Streams st{as_u256(stream_dev), selector_dev, as_u256(lookup_dev), derr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], g_win[2], g_win[3]};
-  TRY(wit_nearest_topk_dev(fp, metric, as_u256(queries_dev), as_u256(vectors_dev), n_queries, n, dim, topk, st, 0, 0, as_u256(indicators_dev),
-                           as_u256(results_dev)));
+  TRY(wit_nearest_dev(fp, metric, as_u256(queries_dev), as_u256(vectors_dev), n_queries, n, dim, topk, st, 0, 0, as_u256(indicators_dev),
+                      as_u256(results_dev)));
   return check_err_flag(derr);
+}
+
+// nearest_vector (vectordb.rs:122-163) for n_queries queries over one database, the calls end to end in the streams
+int vdb_wit_nearest_batch_size(int metric, uint32_t P, uint32_t L, size_t n_queries, size_t n, size_t dim, uint64_t* cells, uint64_t* lookups) {
+  return vdb_wit_nearest_topk_size(metric, P, L, n_queries, n, dim, 1, cells, lookups);
+}
+int vdb_wit_nearest_batch(int metric, uint32_t P, uint32_t L, const vdb_fr* queries, const vdb_fr* vectors, size_t n_queries, size_t n, size_t dim,
+                          vdb_fr* stream_out, vdb_fr* lookup_out, uint8_t* selector_out, vdb_fr* indicators_out, vdb_fr* results_out) {
+  return vdb_wit_nearest_topk(metric, P, L, queries, vectors, n_queries, n, dim, 1, stream_out, lookup_out, selector_out, indicators_out, results_out);
+}
+int vdb_wit_nearest_batch_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* queries_dev, const vdb_fr* vectors_dev, size_t n_queries, size_t n,
+                              size_t dim, vdb_fr* stream_dev, vdb_fr* lookup_dev, uint8_t* selector_dev, vdb_fr* indicators_dev, vdb_fr* results_dev) {
+  return vdb_wit_nearest_topk_dev(metric, P, L, queries_dev, vectors_dev, n_queries, n, dim, 1, stream_dev, lookup_dev, selector_dev, indicators_dev,
+                                  results_dev);
+}
+
+// nearest_vector (vectordb.rs:122-163) for one query
+int vdb_wit_nearest_size(int metric, uint32_t P, uint32_t L, size_t n, size_t dim, uint64_t* cells, uint64_t* lookups) {
+  return vdb_wit_nearest_topk_size(metric, P, L, 1, n, dim, 1, cells, lookups);
+}
+int vdb_wit_nearest(int metric, uint32_t P, uint32_t L, const vdb_fr* query, const vdb_fr* vectors, size_t n, size_t dim, vdb_fr* stream_out,
+                    vdb_fr* lookup_out, uint8_t* selector_out, vdb_fr* indicator_out, vdb_fr* result_out) {
+  return vdb_wit_nearest_topk(metric, P, L, query, vectors, 1, n, dim, 1, stream_out, lookup_out, selector_out, indicator_out, result_out);
+}
+int vdb_wit_nearest_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* query_dev, const vdb_fr* vectors_dev, size_t n, size_t dim, vdb_fr* stream_dev,
+                        vdb_fr* lookup_dev, uint8_t* selector_dev, vdb_fr* indicator_dev, vdb_fr* result_dev) {
+  return vdb_wit_nearest_topk_dev(metric, P, L, query_dev, vectors_dev, 1, n, dim, 1, stream_dev, lookup_dev, selector_dev, indicator_dev, result_dev);
 }
 
 int vdb_wit_kmeans_size(int metric, uint32_t P, uint32_t L, size_t n, size_t dim, size_t K, size_t I, int zero_cached, uint64_t* cells,

@@ -862,173 +862,23 @@ class UpdateHotPath(HotPath):
         return cm, pub, None
 
 
-class NearestHotPath(HotPath):
-    """nearest_vector(query, vectors) (src/gadget/vectordb.rs:122-163; tests/vectordb/mod.rs:220-247 assigns the query, then the
-    vectors) through the same hot path.  Sharded: every rank computes the N distances' values and the short minimum
-    chain (value-only walk), and stores the cells of its own block of columns only — the distance blocks, N-way parallel and nearly
-    all of the cells, are skipped outside the rank's window."""
-
-    def __init__(self, n=64, dim=128, k=14, P=48, L=13, metric="euclidean", seed=20260002, tau=None, col_shard=(0, 1), vectors=None, blind_seed=None,
-                 params=None):
-        """`vectors`: (n + 1, dim) f64 rows, the query first"""
-        super().__init__(n, dim, k, P, L, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors, blind_seed=blind_seed, params=params)
-        self.metric = api.METRICS[metric]
-        self.metric_name = metric
-
-    def n_input_rows(self):
-        return self.n + 1
-
-    def _input_vectors(self):
-        vec, seed = sift_like_vectors(self.seed, self.n, self.dim)
-        query, _ = sift_like_vectors(seed + 1000, 1, self.dim)
-        return np.concatenate([query, vec]), seed
-
-    def _circuit_size(self):
-        cells, lk = ctypes.c_uint64(), ctypes.c_uint64()
-        check(self.lib.vdb_wit_nearest_size(self.metric, self.P, self.L, self.n, self.dim, ctypes.byref(cells), ctypes.byref(lk)))
-        return (self.n + 1) * self.dim, cells.value, lk.value
-
-    def _alloc_outputs(self):
-        self.d_ind = self._output(self.n * 32)
-        self.d_res = self._output(self.dim * 32)
-
-    def _emit(self, sel):
-        at = self.n_in
-        with self._window(sel, at):
-            check(self.lib.vdb_wit_nearest_dev(self.metric, self.P, self.L, self.d_vec.ptr, self.d_vec.at(self.dim * 32), self.n, self.dim,
-                                               self.d_stream.at(at * B), self.d_lookup.ptr, self._sel_at(sel, at), self.d_ind.ptr, self.d_res.ptr))
-
-    def public_values_dev(self):
-        return self.d_res.ptr, self.dim            # examples/query.rs:58: the nearest vector
-
-    def results(self):
-        return self.d_ind.download((self.n, 4)), self.d_res.download((self.dim, 4))
-
-    def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        cm, (_ind, res) = CS.build_nearest(self.metric_name, self.n, self.dim, self.P, self.L, builder=DeviceBuilder if on_device else None)
-        return cm, res, None                       # examples/query.rs:58 make_public.extend(result)
-
-
-class QueryHotPath(NearestHotPath):
-    """The reference's `query` circuit — "exhaustively find the similar vector & commit to the database" (examples/query.rs:32-73;
-    tests/vectordb/mod.rs:220-247 chip_nearest_vector): nearest_vector(query, database) and merkle_commitment(database) in ONE
-    circuit over the same assigned vectors, the result vector and the Merkle root public.  Stream: [query | vectors | nearest_vector's
-    cells | merkle_commitment's cells]; the lookup cells are nearest_vector's.  (PoseidonChip::new's three load_constant cells are
-    not emitted, as in MerkleHotPath: the sponge's initial state is pinned as constants of the circuit.)"""
-
-    def _circuit_size(self):
-        n_in, nv_cells, lk = super()._circuit_size()
-        self.nearest_cells, self.merkle_cells = nv_cells, _merkle_cells(self)
-        return n_in, nv_cells + self.merkle_cells, lk
-
-    def _alloc_outputs(self):
-        super()._alloc_outputs()
-        self.d_root = self._output(32)
-        self.d_pub = self._output((self.dim + 1) * 32)      # [result vector | root]: the public statement, in make_public order
-
-    def _emit(self, sel):
-        lib = self.lib
-        super()._emit(sel)                                          # nearest_vector (windowed like NearestHotPath)
-        _merkle_trace(self, self.d_vec.at(self.dim * 32), self.n_in + self.nearest_cells, sel)
-        check(lib.vdb_memcpy_d2d(self.d_pub.ptr, self.d_res.ptr, ctypes.c_size_t(self.dim * 32)))
-        check(lib.vdb_memcpy_d2d(self.d_pub.at(self.dim * 32), self.d_root.ptr, ctypes.c_size_t(32)))
-
-    def public_values_dev(self):
-        return self.d_pub.ptr, self.dim + 1          # examples/query.rs:58 make_public.extend(result), :69 make_public.push(root)
-
-    def results(self):
-        ind, res = super().results()
-        return ind, res, self.d_root.download((4,))
-
-    def constraint_map(self, d_flags, on_device=True):
-        # nearest_vector, then merkle_commitment over the same assigned vectors, in one map (examples/query.rs)
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder, place_merkle
-        bld, (_ind, res), used = CS.build_nearest(self.metric_name, self.n, self.dim, self.P, self.L, builder=DeviceBuilder,
-                                                  extra_cells=self.merkle_cells, finish=False)
-        assert used == self.n_in + self.nearest_cells
-        root, end = place_merkle(bld, self.n, self.dim, used, self.dim, functools.partial(self._fetch_flags, d_flags), self._fetch)
-        assert end == self.n_cells
-        return bld.finish(), list(res) + [root], root      # examples/query.rs:58, :69: the result vector, then the root
-
-
-class BatchQueryHotPath(HotPath):
-    """A batch of queries against ONE committed database in one proof: the closure a user of the reference's chips writes for it —
-    assign the q queries, assign the n database vectors, nearest_vector(query, database) per query (src/gadget/vectordb.rs:122-163),
-    merkle_commitment(database) once (:165-223) — i.e. examples/query.rs:32-73 with its nearest_vector repeated, so that q queries pay
-    for the database commitment once.  Stream: [queries | vectors | nearest_vector of query 0 | ... | of query q - 1 |
-    merkle_commitment]; the lookup cells are the nearest_vector runs in query order; public, in make_public order: the q result
-    vectors, then the root (the queries stay private, as in the example).  With q = 1 the circuit is QueryHotPath's.  All q
-    nearest_vector blocks come from one call (vdb_wit_nearest_batch_dev: the launch count does not depend on q); sharded like
-    NearestHotPath — every rank computes every value, a rank stores the cells of its own columns."""
-
-    def __init__(self, q=8, n=64, dim=128, k=16, P=48, L=13, metric="euclidean", seed=20260002, tau=None, col_shard=(0, 1), vectors=None,
-                 blind_seed=None, params=None):
-        """`vectors`: (q + n, dim) f64 rows, the queries first"""
-        if q < 1:
-            raise ValueError("a batch holds at least one query")
-        super().__init__(n, dim, k, P, L, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors, blind_seed=blind_seed, params=params)
-        self.q = q
-        self.metric = api.METRICS[metric]
-        self.metric_name = metric
-
-    def n_input_rows(self):
-        return self.q + self.n
-
-    def _input_vectors(self):
-        # the database is QueryHotPath's for the same seed, and with q = 1 so is the query
-        vec, seed = sift_like_vectors(self.seed, self.n, self.dim)
-        queries, _ = sift_like_vectors(seed + 1000, self.q, self.dim)
-        return np.concatenate([queries, vec]), seed
-
-    def _circuit_size(self):
-        cells, lk = ctypes.c_uint64(), ctypes.c_uint64()
-        check(self.lib.vdb_wit_nearest_batch_size(self.metric, self.P, self.L, self.q, self.n, self.dim, ctypes.byref(cells), ctypes.byref(lk)))
-        self.nearest_cells, self.merkle_cells = cells.value, _merkle_cells(self)
-        return (self.q + self.n) * self.dim, self.nearest_cells + self.merkle_cells, lk.value
-
-    def _alloc_outputs(self):
-        self.d_ind = self._output(self.q * self.n * 32)
-        self.d_root = self._output(32)
-        self.d_pub = self._output((self.q * self.dim + 1) * 32)     # [result vectors | root]: the public statement, in make_public order
-
-    def _emit(self, sel):
-        at, d_db = self.n_in, self.d_vec.at(self.q * self.dim * 32)
-        with self._window(sel, at):
-            check(self.lib.vdb_wit_nearest_batch_dev(self.metric, self.P, self.L, self.d_vec.ptr, d_db, self.q, self.n, self.dim, self.d_stream.at(at * B),
-                                                     self.d_lookup.ptr, self._sel_at(sel, at), self.d_ind.ptr, self.d_pub.ptr))
-        _merkle_trace(self, d_db, at + self.nearest_cells, sel)
-        check(self.lib.vdb_memcpy_d2d(self.d_pub.at(self.q * self.dim * 32), self.d_root.ptr, ctypes.c_size_t(32)))
-
-    def public_values_dev(self):
-        return self.d_pub.ptr, self.q * self.dim + 1     # make_public.extend(result) per query (examples/query.rs:58), then push(root) (:69)
-
-    def results(self):
-        return self.d_ind.download((self.q, self.n, 4)), self.d_pub.download((self.q, self.dim, 4)), self.d_root.download((4,))
-
-    def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder, place_merkle
-        bld, (_ind, res), used = CS.build_nearest_batch(self.metric_name, self.q, self.n, self.dim, self.P, self.L, builder=DeviceBuilder,
-                                                        extra_cells=self.merkle_cells, finish=False)
-        assert used == self.n_in + self.nearest_cells
-        root, end = place_merkle(bld, self.n, self.dim, used, self.q * self.dim, functools.partial(self._fetch_flags, d_flags), self._fetch)
-        assert end == self.n_cells
-        return bld.finish(), [int(c) for c in np.asarray(res).reshape(-1)] + [root], root
-
-
 class TopKQueryHotPath(HotPath):
     """Top-k queries against ONE committed database in one proof: assign the q queries, assign the n database vectors, per query the
     `topk` rounds of include/vdb.h's vdb_wit_nearest_topk (nearest_vector's distances once, its qmin chain / is_equal /
     select_by_indicator per round, the winners replaced by Constant(2^(2P) - 1) through gate.select before the next round), then
     merkle_commitment(database) once.  The reference has no top-k gadget: this is the closure a user of its chips writes.  Stream:
-    [queries | vectors | block of query 0 | ... | merkle_commitment]; public, in make_public order: per query the topk result vectors,
-    nearest first, then the root.  With topk = 1 the circuit is BatchQueryHotPath's, with q = 1 too QueryHotPath's.  Ties are
+    [queries | vectors | block of query 0 | ... | merkle_commitment]; the lookup cells are the queries' blocks in query order; public,
+    in make_public order: per query the topk result vectors, nearest first, then the root (the queries stay private).  With topk = 1
+    the circuit is BatchQueryHotPath's, with q = 1 too QueryHotPath's: those classes are this one at these values.  Ties are
     nearest_vector's: every vector at the round's minimum distance gets its indicator set, the round's result is the last of them and
     all of them leave together; when fewer than topk distinct distances exist, the later rounds set every indicator and return the
-    last vector.  All blocks come from one call whose launch count depends on neither q nor topk; sharded like NearestHotPath."""
+    last vector.  (PoseidonChip::new's three load_constant cells are not emitted, as in MerkleHotPath: the sponge's initial state is
+    pinned as constants of the circuit.)  All blocks come from one call whose launch count depends on neither q nor topk.  Sharded
+    (SURVEY §8e): every rank computes the distances' values and the short minimum chains (value-only walk), and stores the cells of
+    its own block of columns only — the distance blocks, N-way parallel and nearly all of the cells, are skipped outside the rank's
+    window."""
+
+    commit = True        # merkle_commitment(database) follows in the same circuit, its root public (NearestHotPath: not)
 
     def __init__(self, topk=10, q=1, n=64, dim=128, k=16, P=48, L=13, metric="euclidean", seed=20260002, tau=None, col_shard=(0, 1), vectors=None,
                  blind_seed=None, params=None):
@@ -1039,6 +889,7 @@ class TopKQueryHotPath(HotPath):
             raise ValueError("topk must be at least 1 and at most n")
         super().__init__(n, dim, k, P, L, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors, blind_seed=blind_seed, params=params)
         self.q, self.topk = q, topk
+        self.n_results = q * topk * dim            # cells of the result vectors
         self.metric = api.METRICS[metric]
         self.metric_name = metric
 
@@ -1046,7 +897,6 @@ class TopKQueryHotPath(HotPath):
         return self.q + self.n
 
     def _input_vectors(self):
-        # the database and the queries are BatchQueryHotPath's for the same seed
         vec, seed = sift_like_vectors(self.seed, self.n, self.dim)
         queries, _ = sift_like_vectors(seed + 1000, self.q, self.dim)
         return np.concatenate([queries, vec]), seed
@@ -1054,38 +904,87 @@ class TopKQueryHotPath(HotPath):
     def _circuit_size(self):
         cells, lk = ctypes.c_uint64(), ctypes.c_uint64()
         check(self.lib.vdb_wit_nearest_topk_size(self.metric, self.P, self.L, self.q, self.n, self.dim, self.topk, ctypes.byref(cells), ctypes.byref(lk)))
-        self.nearest_cells, self.merkle_cells = cells.value, _merkle_cells(self)
+        self.nearest_cells, self.merkle_cells = cells.value, _merkle_cells(self) if self.commit else 0
         return (self.q + self.n) * self.dim, self.nearest_cells + self.merkle_cells, lk.value
 
     def _alloc_outputs(self):
         self.d_ind = self._output(self.q * self.topk * self.n * 32)
-        self.d_root = self._output(32)
-        self.d_pub = self._output((self.q * self.topk * self.dim + 1) * 32)     # [result vectors | root]: the public statement, in make_public order
+        # [result vectors | root]: the public statement, in make_public order (examples/query.rs:58 make_public.extend(result), :69 push(root))
+        self.d_pub = self.d_res = self._output((self.n_results + self.commit) * 32)
+        if self.commit:
+            self.d_root = self._output(32)
 
     def _emit(self, sel):
         at, d_db = self.n_in, self.d_vec.at(self.q * self.dim * 32)
         with self._window(sel, at):
             check(self.lib.vdb_wit_nearest_topk_dev(self.metric, self.P, self.L, self.d_vec.ptr, d_db, self.q, self.n, self.dim, self.topk,
                                                     self.d_stream.at(at * B), self.d_lookup.ptr, self._sel_at(sel, at), self.d_ind.ptr, self.d_pub.ptr))
-        _merkle_trace(self, d_db, at + self.nearest_cells, sel)
-        check(self.lib.vdb_memcpy_d2d(self.d_pub.at(self.q * self.topk * self.dim * 32), self.d_root.ptr, ctypes.c_size_t(32)))
+        if self.commit:
+            _merkle_trace(self, d_db, at + self.nearest_cells, sel)
+            check(self.lib.vdb_memcpy_d2d(self.d_pub.at(self.n_results * 32), self.d_root.ptr, ctypes.c_size_t(32)))
 
     def public_values_dev(self):
-        return self.d_pub.ptr, self.q * self.topk * self.dim + 1
+        return self.d_pub.ptr, self.n_results + self.commit
+
+    def _result_axes(self):
+        return self.q, self.topk
 
     def results(self):
-        return (self.d_ind.download((self.q, self.topk, self.n, 4)), self.d_pub.download((self.q, self.topk, self.dim, 4)),
-                self.d_root.download((4,)))
+        axes = self._result_axes()
+        out = self.d_ind.download(axes + (self.n, 4)), self.d_pub.download(axes + (self.dim, 4))
+        return out + (self.d_root.download((4,)),) if self.commit else out
 
     def constraint_map(self, d_flags, on_device=True):
+        # the queries' blocks, then merkle_commitment over the same assigned vectors, in one map (examples/query.rs)
         from . import circuit_sym as CS
         from .circuit_dev import DeviceBuilder, place_merkle
-        bld, (_ind, res), used = CS.build_nearest_topk(self.metric_name, self.q, self.n, self.dim, self.topk, self.P, self.L, builder=DeviceBuilder,
+        bld, (_ind, res), used = CS.build_nearest_topk(self.metric_name, self.q, self.n, self.dim, self.topk, self.P, self.L,
+                                                       builder=DeviceBuilder if on_device or self.commit else None,
                                                        extra_cells=self.merkle_cells, finish=False)
         assert used == self.n_in + self.nearest_cells
-        root, end = place_merkle(bld, self.n, self.dim, used, self.q * self.dim, functools.partial(self._fetch_flags, d_flags), self._fetch)
-        assert end == self.n_cells
-        return bld.finish(), [int(c) for c in np.asarray(res).reshape(-1)] + [root], root
+        public, root = [int(c) for c in np.asarray(res).reshape(-1)], None
+        if self.commit:
+            root, end = place_merkle(bld, self.n, self.dim, used, self.q * self.dim, functools.partial(self._fetch_flags, d_flags), self._fetch)
+            assert end == self.n_cells
+            public.append(root)
+        return bld.finish(), public, root
+
+
+class BatchQueryHotPath(TopKQueryHotPath):
+    """A batch of queries against ONE committed database in one proof: the closure a user of the reference's chips writes for it —
+    assign the q queries, assign the n database vectors, nearest_vector(query, database) per query (src/gadget/vectordb.rs:122-163),
+    merkle_commitment(database) once (:165-223) — i.e. examples/query.rs:32-73 with its nearest_vector repeated, so that q queries pay
+    for the database commitment once.  TopKQueryHotPath at topk = 1, its results without the round axis."""
+
+    def __init__(self, q=8, n=64, dim=128, k=16, P=48, L=13, metric="euclidean", seed=20260002, tau=None, col_shard=(0, 1), vectors=None,
+                 blind_seed=None, params=None):
+        """`vectors`: (q + n, dim) f64 rows, the queries first"""
+        super().__init__(1, q, n, dim, k, P, L, metric, seed, tau, col_shard, vectors, blind_seed, params)
+
+    def _result_axes(self):
+        return (self.q,)
+
+
+class QueryHotPath(TopKQueryHotPath):
+    """The reference's `query` circuit — "exhaustively find the similar vector & commit to the database" (examples/query.rs:32-73;
+    tests/vectordb/mod.rs:220-247 chip_nearest_vector): nearest_vector(query, database) and merkle_commitment(database) in ONE
+    circuit over the same assigned vectors, the result vector and the Merkle root public.  TopKQueryHotPath at q = topk = 1, its
+    results without the query and round axes."""
+
+    def __init__(self, n=64, dim=128, k=14, P=48, L=13, metric="euclidean", seed=20260002, tau=None, col_shard=(0, 1), vectors=None, blind_seed=None,
+                 params=None):
+        """`vectors`: (n + 1, dim) f64 rows, the query first"""
+        super().__init__(1, 1, n, dim, k, P, L, metric, seed, tau, col_shard, vectors, blind_seed, params)
+
+    def _result_axes(self):
+        return ()
+
+
+class NearestHotPath(QueryHotPath):
+    """nearest_vector(query, vectors) alone (src/gadget/vectordb.rs:122-163; tests/vectordb/mod.rs:220-247 assigns the query, then the
+    vectors): QueryHotPath without the commitment, the result vector public (examples/query.rs:58)."""
+
+    commit = False
 
 
 class DistancesHotPath(HotPath):

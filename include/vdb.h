@@ -157,7 +157,9 @@ int vdb_wit_fp_op(int op, uint32_t precision_bits, uint32_t lookup_bits, const v
                   vdb_fr *lookup_out, uint8_t *selector_out, vdb_fr *result_out);
 int vdb_wit_fp_op_dev(int op, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *a_dev, const vdb_fr *b_dev, size_t n, vdb_fr *stream_dev,
                       vdb_fr *lookup_dev, uint8_t *selector_dev, vdb_fr *result_dev);
-/* VectorDBChip::nearest_vector (src/gadget/vectordb.rs:122-163): indicator_out n raw 0/1 field bits */
+/* VectorDBChip::nearest_vector (src/gadget/vectordb.rs:122-163): indicator_out n raw 0/1 field bits.  vdb_wit_nearest_batch with one
+ * query, and so within its limits of one call: n and dim at most 2^24, the cells at most 2^34.  No call that could run is refused by
+ * them: 2^34 cells are 512 GiB of stream, more than the card holds. */
 int vdb_wit_nearest_size(int metric, uint32_t precision_bits, uint32_t lookup_bits, size_t n, size_t dim, uint64_t *cells, uint64_t *lookups);
 int vdb_wit_nearest(int metric, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *query, const vdb_fr *vectors, size_t n, size_t dim,
                     vdb_fr *stream_out, vdb_fr *lookup_out, uint8_t *selector_out, vdb_fr *indicator_out, vdb_fr *result_out);
@@ -171,8 +173,9 @@ int vdb_wit_nearest_dev(int metric, uint32_t precision_bits, uint32_t lookup_bit
  * Bit-identical to n_queries calls of vdb_wit_nearest at the matching offsets, with a number of kernel launches that does not depend on
  * n_queries.  The _dev form honours vdb_wit_set_window like vdb_wit_nearest_dev.
  * Limits of one call (VDB_ERR_ARG beyond them, as for n_queries == 0): n_queries * n and n_queries * dim at most
- * VDB_NEAREST_BATCH_MAX_INSTANCES (32-bit instance numbers; 160 B of work space per (query, vector)), n_queries * cells of one
- * nearest_vector at most VDB_NEAREST_BATCH_MAX_CELLS.  The deferred-inversion list holds 16 M entries whatever the batch: beyond them
+ * VDB_NEAREST_BATCH_MAX_INSTANCES (32-bit instance numbers; 164 B of work space per (query, vector)), n_queries * cells of one
+ * nearest_vector at most VDB_NEAREST_BATCH_MAX_CELLS: vdb_wit_nearest_topk's limits at topk == 1, which refuse exactly these calls (the
+ * constants are the TOPK ones).  The deferred-inversion list holds 16 M entries whatever the batch: beyond them
  * inverse cells are computed in line — slower, the same stream.  VDB_ERR_OOM when the work space cannot be allocated. */
 #define VDB_NEAREST_BATCH_MAX_INSTANCES ((size_t)1 << 24)
 #define VDB_NEAREST_BATCH_MAX_CELLS ((uint64_t)1 << 34)
@@ -193,12 +196,12 @@ int vdb_wit_nearest_batch_dev(int metric, uint32_t precision_bits, uint32_t look
  *   cur_i   = gate.select(Constant(M), cur_i, ind_r,i)           (8 cells each; not emitted after the last round)
  * with M = 2^(2 precision_bits) - 1, the largest value of the chip's range.  Lookup stream: per query the n distance runs, then per round
  * the n - 1 qmin runs.  indicators_out n_queries x topk x n raw 0/1 bits, results_out n_queries x topk x dim, nearest first.
- * topk == 1 writes the bytes of vdb_wit_nearest_batch.  Ties behave as in nearest_vector: every entry that equals the round's minimum gets
+ * topk == 1 is vdb_wit_nearest_batch, which forwards here.  Ties behave as in nearest_vector: every entry that equals the round's minimum gets
  * its indicator set, the round's result is the LAST of them, and all of them are masked in that round; once fewer distinct distances than
  * rounds remain, a round runs on an all-M array, sets every indicator and returns the last vector.
  * The number of kernel launches depends on neither n_queries nor topk.  The _dev form honours vdb_wit_set_window like
- * vdb_wit_nearest_batch_dev.  Work space: 32 B per (query, round, vector) for the round's prefix minima, and per (query, vector) 160 B
- * for the distances plus 4 B for the round that masked the entry.
+ * vdb_wit_nearest_batch_dev.  Work space: 32 B per (query, round, vector) for the round's prefix minima, and per (query, vector) 128 B
+ * for the distances plus 4 B for the round that masked the entry: 164 B per (query, vector) at topk == 1.
  * Limits of one call (VDB_ERR_ARG beyond them, as for topk == 0, topk > n and n_queries == 0, before anything is launched):
  * n_queries * topk * n and n_queries * topk * dim at most VDB_NEAREST_TOPK_MAX_INSTANCES (32-bit lane numbers), all cells at most
  * VDB_NEAREST_TOPK_MAX_CELLS.  VDB_ERR_OOM when the work space cannot be allocated. */

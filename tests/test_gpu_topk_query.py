@@ -215,12 +215,13 @@ def test_arguments_and_limits_are_refused_and_nothing_is_written(api, O):
 
 
 def test_launch_count_depends_on_neither_queries_nor_rounds(api, O):
+    """the top-k entry point over (q, t), and the single-query and batch entry points, which are the same path at t = 1"""
     from halo2_vectordb_amd._lib import check
     lib = api.init()
     rng = np.random.default_rng(3)
     n, dim = 64, 8
     counts = {}
-    for q, topk in ((1, 1), (1, 10), (8, 10), (1, 64)):
+    for entry, q, topk in (("topk", 1, 1), ("topk", 1, 10), ("topk", 8, 10), ("topk", 1, 64), ("single", 1, 1), ("batch", 8, 1)):
         qv = O.quantize(rng.uniform(0.25, 3.0, size=(q + n, dim)), 48)
         cells, lk = ctypes.c_uint64(), ctypes.c_uint64()
         check(lib.vdb_wit_nearest_topk_size(0, 48, 13, q, n, dim, topk, ctypes.byref(cells), ctypes.byref(lk)))
@@ -229,22 +230,24 @@ def test_launch_count_depends_on_neither_queries_nor_rounds(api, O):
             d_q, d_db = _dev(api, up, qv[:q]), _dev(api, up, qv[q:])
             bufs = [api.DeviceBuffer(x) for x in (cells.value * 32, lk.value * 32, q * topk * n * 32, q * topk * dim * 32)]
             up += bufs
-            run = lambda: check(lib.vdb_wit_nearest_topk_dev(0, 48, 13, d_q.ptr, d_db.ptr, q, n, dim, topk, bufs[0].ptr, bufs[1].ptr, None, bufs[2].ptr,
-                                                             bufs[3].ptr))
+            out = (bufs[0].ptr, bufs[1].ptr, None, bufs[2].ptr, bufs[3].ptr)
+            run = dict(topk=lambda: check(lib.vdb_wit_nearest_topk_dev(0, 48, 13, d_q.ptr, d_db.ptr, q, n, dim, topk, *out)),
+                       single=lambda: check(lib.vdb_wit_nearest_dev(0, 48, 13, d_q.ptr, d_db.ptr, n, dim, *out)),
+                       batch=lambda: check(lib.vdb_wit_nearest_batch_dev(0, 48, 13, d_q.ptr, d_db.ptr, q, n, dim, *out)))[entry]
             run()
             api.sync()
             api.profile_begin(deferred=True)
             run()
             api.sync()
             prof = api.profile_end()
-            counts[(q, topk)] = {name: int(v["launches"]) for name, v in prof.items()}
+            counts[(entry, q, topk)] = {name: int(v["launches"]) for name, v in prof.items()}
         finally:
             for b in up:
                 b.free()
-    first = counts[(1, 1)]
+    first = counts[("topk", 1, 1)]
     assert all(c == first for c in counts.values()), counts
-    assert {name: first[name] for name in first if name.startswith("k_nvt_")} == dict(k_nvt_rounds=1, k_nvt_qmin=1, k_nvt_is_equal=1, k_nvt_mask=1,
-                                                                                      k_nvt_select=1), first
+    assert {name: first[name] for name in first if name.startswith("k_nv_")} == dict(k_nv_rounds=1, k_nv_qmin=1, k_nv_is_equal=1, k_nv_mask=1,
+                                                                                     k_nv_select=1), first
 
 
 def test_rank_windows_store_their_cells_and_nothing_else(api, O):

@@ -4,8 +4,8 @@ Method of tools/batch_query_probe.py: HIP events, warm, five alternating repeats
 counts from the library's own event profiler in a pass of their own.  Euclidean, 64 x 128, P = 48, L = 13, k = 14:
 
 1. cells — vdb_wit_nearest_topk_size for t = 1 and 10 beside vdb_wit_nearest_size;
-2. witness — vdb_wit_nearest_topk_dev for (q, t) in {(1, 1), (1, 10), (8, 10), (1, 64)}; at t = 1 in alternation with
-   vdb_wit_nearest_batch_dev on the same buffers (same bytes checked);
+2. witness — vdb_wit_nearest_topk_dev for (q, t) in {(1, 1), (1, 10), (8, 10), (1, 64)} (the batch entry point is this call at
+   t = 1: tools/batch_query_probe.py times it);
 3. whole proof — TopKQueryHotPath(topk = 10) against QueryHotPath in one process, alternating, both verified: ms, proof bytes,
    column counts, prover stages.
 
@@ -69,44 +69,23 @@ def witness_probe(api, q, t):
     def topk():
         check(lib.vdb_wit_nearest_topk_dev(m, P, L, d_q.ptr, d_db.ptr, q, N, DIM, t, d_adv.ptr, d_lk.ptr, None, d_ind.ptr, d_res.ptr))
 
-    def batch():
-        check(lib.vdb_wit_nearest_batch_dev(m, P, L, d_q.ptr, d_db.ptr, q, N, DIM, d_adv.ptr, d_lk.ptr, None, d_ind.ptr, d_res.ptr))
-
     def timed(fn):
         api.sync()
         api.timer_start()
         fn()
         return api.timer_stop()
 
-    ways = dict(topk=topk, **(dict(batch=batch) if t == 1 else {}))
     try:
-        outs = {}
-        for name, fn in ways.items():                                      # warm; at t = 1 the two ways must leave the same bytes
-            fn()
-            api.sync()
-            outs[name] = (d_adv.download((cells, 4)), d_lk.download((lks, 4)), d_res.download((q * t * DIM, 4)))
-        same = all(np.array_equal(a, b) for a, b in zip(outs["topk"], outs["batch"])) if t == 1 else None
-        del outs
-        times = {name: [] for name in ways}
-        for _ in range(REPEATS):                                           # alternating
-            for name, fn in ways.items():
-                times[name].append(timed(fn))
-        kernels = {}
-        for name, fn in ways.items():                                      # per-kernel times and launch counts, a pass of its own
-            api.sync()
-            api.profile_begin(deferred=True)
-            fn()
-            api.sync()
-            kernels[name] = api.profile_end()
-        rep = dict(q=q, topk=t, cells=cells, lookup_cells=lks, topk_ms=stats(times["topk"]), kernels_ms=kernels,
-                   launches=int(sum(v["launches"] for v in kernels["topk"].values())),
-                   stream_write_GBps=(cells + lks) * 32 / (float(np.median(times["topk"])) * 1e-3) / 1e9)
-        if t == 1:
-            b = stats(times["batch"])
-            spread = max(b["spread"], rep["topk_ms"]["spread"])
-            rep.update(batch_ms=b, same_bytes=bool(same), spread_ms=spread, batch_launches=int(sum(v["launches"] for v in kernels["batch"].values())),
-                       topk_not_slower_than_batch_beyond_spread=bool(rep["topk_ms"]["median"] <= b["median"] + spread))
-        return rep
+        topk()                                                             # warm
+        times = [timed(topk) for _ in range(REPEATS)]
+        api.sync()                                                         # per-kernel times and launch counts, a pass of its own
+        api.profile_begin(deferred=True)
+        topk()
+        api.sync()
+        kernels = api.profile_end()
+        return dict(q=q, topk=t, cells=cells, lookup_cells=lks, topk_ms=stats(times), kernels_ms=dict(topk=kernels),
+                    launches=int(sum(v["launches"] for v in kernels.values())),
+                    stream_write_GBps=(cells + lks) * 32 / (float(np.median(times)) * 1e-3) / 1e9)
     finally:
         for x in bufs:
             x.free()
@@ -171,9 +150,8 @@ def main():
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1)
     brief = dict(cells=doc["cells"], launches_equal=doc["launches_equal_in_every_row"],
-                 witness=[dict(q=w["q"], topk=w["topk"], ms=w["topk_ms"]["median"], spread=w["topk_ms"]["spread"], launches=w["launches"],
-                               **({"batch_ms": w["batch_ms"]["median"], "same_bytes": w["same_bytes"], "not_slower": w["topk_not_slower_than_batch_beyond_spread"]}
-                                  if w["topk"] == 1 else {})) for w in doc["witness"]])
+                 witness=[dict(q=w["q"], topk=w["topk"], ms=w["topk_ms"]["median"], spread=w["topk_ms"]["spread"], launches=w["launches"])
+                          for w in doc["witness"]])
     if "proof" in doc:
         pf = doc["proof"]
         brief["proof"] = {name: dict(ms=pf[name]["proof_ms"]["median"], spread=pf[name]["proof_ms"]["spread"], bytes=pf[name]["proof_bytes"],
