@@ -20,6 +20,8 @@ import math
 
 import numpy as np
 
+from .copymap import T, perm_cells, permutation_template
+
 R = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 SELF, CONST, EXT0 = -1, -2, -10
 # the FixedPointInstructions calls of one operand (Sym.fp_op; what pipeline.FixedPointHotPath proves)
@@ -637,26 +639,10 @@ def trace_kmeans(metric, n, dim, K, I, P, L):
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # BASELINE-sized circuits: traced unit blocks, instantiated with numpy
-class Block:
-    """a traced unit with `n_ext` external inputs and `outs` (block cells handed to later blocks)"""
+class ConstPool:
+    """the distinct fixed-column values of a map or of a block, numbered by first use"""
 
-    def __init__(self, sym, outs):
-        self.src, self.gate, self.cidx, self.consts, self.asserted, self.lk = sym.arrays()
-        self.n, self.n_lk, self.outs = len(self.src), len(self.lk), np.asarray(outs, dtype=np.int64)
-        self.local = self.src >= 0
-        self.isext = self.src <= EXT0
-        self.ext_no = np.where(self.isext, EXT0 - self.src, 0)
-        self.lk_isext = self.lk <= EXT0
-        self.lk_ext_no = np.where(self.lk_isext, EXT0 - self.lk, 0)
-
-
-class _Builder:
-    def __init__(self, n_cells, n_lookup):
-        self.copy_of = np.arange(n_cells, dtype=np.int64)
-        self.const_idx = np.full(n_cells, -1, dtype=np.int64)
-        self.asserted = np.zeros(n_cells, dtype=bool)
-        self.gate = np.zeros(n_cells, dtype=bool)
-        self.lookup_src = np.full(n_lookup, -1, dtype=np.int64)
+    def __init__(self):
         self.consts, self._cmap = [], {}
 
     def const_index(self, v):
@@ -664,6 +650,35 @@ class _Builder:
             self._cmap[v] = len(self.consts)
             self.consts.append(v)
         return self._cmap[v]
+
+
+class Block:
+    """a traced unit with `n_ext` external inputs and `outs` (block cells handed to later blocks)"""
+
+    def __init__(self, sym, outs):
+        """`sym`: the Sym that traced the unit, or what its arrays() would return (from_arrays)"""
+        self.src, self.gate, self.cidx, self.consts, self.asserted, self.lk = sym.arrays() if isinstance(sym, Sym) else sym
+        self.n, self.n_lk, self.outs = len(self.src), len(self.lk), np.asarray(outs, dtype=np.int64)
+        self.local = self.src >= 0
+        self.isext = self.src <= EXT0
+        self.ext_no = np.where(self.isext, EXT0 - self.src, 0)
+        self.lk_isext = self.lk <= EXT0
+        self.lk_ext_no = np.where(self.lk_isext, EXT0 - self.lk, 0)
+
+    @classmethod
+    def from_arrays(cls, src, gate, cidx, consts, asserted, lk, outs):
+        """a unit that no Sym traced (the Poseidon permutation, whose template copymap.py holds)"""
+        return cls((src, gate, cidx, consts, asserted, lk), outs)
+
+
+class _Builder(ConstPool):
+    def __init__(self, n_cells, n_lookup):
+        super().__init__()
+        self.copy_of = np.arange(n_cells, dtype=np.int64)
+        self.const_idx = np.full(n_cells, -1, dtype=np.int64)
+        self.asserted = np.zeros(n_cells, dtype=bool)
+        self.gate = np.zeros(n_cells, dtype=bool)
+        self.lookup_src = np.full(n_lookup, -1, dtype=np.int64)
 
     def constant_cell(self, pos, value):
         self.const_idx[pos] = self.const_index(value % R)
@@ -854,21 +869,122 @@ def build_kmeans(metric, n, dim, K, I, P, L, builder=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# merkle_commitment (src/gadget/vectordb.rs:165-223 through PoseidonChip<F, 3, 2>): copymap.py's permutation template as a unit block
+def merkle_leaf_layout(dim):
+    """the sponge of one leaf of `dim` words and one tree node: dict(nperm, n_ins: words each of the leaf's permutations absorbs,
+    sizes: their cells, leaf_cells, node_cells: absorb [left, right], then the padding-only permutation)"""
+    nperm = (dim + 1) // 2 + (1 if dim % 2 == 0 else 0)
+    n_ins = [max(0, min(2, dim - 2 * p)) for p in range(nperm)]
+    sizes = [perm_cells(k) for k in n_ins]
+    return dict(nperm=nperm, n_ins=n_ins, sizes=sizes, leaf_cells=sum(sizes), node_cells=perm_cells(2) + perm_cells(0))
+
+
+def _perm_block(flags, values, n_in, fresh, tied):
+    """one PoseidonChip::permutation as a unit block (external inputs 0..2: the sponge state, 3..4: the absorbed words): `fresh`: the
+    state is the chip's initial one (constants 2^64, 0, 0, though the kernels do not flag them) instead of external cells; `tied`: the
+    words copy external cells.  `flags` / `values`: the kernel's flag bytes / the canonical values of one such permutation."""
+    flags = np.asarray(flags, dtype=np.uint8)
+    src, fin = permutation_template(flags, n_in)
+    out = np.where(src >= 0, src, SELF).astype(np.int64)
+    pool, cidx = ConstPool(), np.full(src.size, -1, dtype=np.int64)
+    for i in np.flatnonzero(flags & 2):
+        cidx[i] = pool.const_index(int(values[i]) % R)
+    for i in range(T):
+        cols = np.flatnonzero(src == -10 - i)
+        if fresh:
+            for c in cols:
+                cidx[c] = pool.const_index((1 << 64) if i == 0 else 0)
+        else:
+            out[cols] = ext(i)
+    if tied:
+        for i in range(2):
+            out[np.flatnonzero(src == -20 - i)] = ext(T + i)
+    none = np.zeros(0, dtype=np.int64)
+    return Block.from_arrays(out, (flags & 1).astype(bool), cidx, pool.consts, none, none, fin)
+
+
+def _perm_placer(B, fetch_flags, fetch_values):
+    """perm(bases, n_in, state, msgs): permutations absorbing n_in words placed into builder `B` at the stream cells `bases`; `state`:
+    the T cell arrays of the state they go on from (None: the chip's initial state), `msgs`: the n_in cell arrays of the words (None:
+    free cells); -> the T cell arrays of the final state.  One block per kind (n_in, fresh, tied), made from the flags and values of
+    the first instance placed."""
+    blocks = {}
+
+    def perm(bases, n_in, state, msgs):
+        fresh, tied = state is None, n_in > 0 and msgs is not None
+        key = (n_in, fresh, tied)
+        if key not in blocks:
+            at, size = int(bases[0]), perm_cells(n_in)
+            blocks[key] = _perm_block(fetch_flags(at, at + size), fetch_values(at, at + size), n_in, fresh, tied)
+        e = np.zeros((bases.size, T + 2), dtype=np.int64)
+        if not fresh:
+            for i in range(T):
+                e[:, i] = state[i]
+        if tied:
+            for i in range(n_in):
+                e[:, T + i] = msgs[i]
+        outs = B.place(blocks[key], bases, np.zeros(bases.size, dtype=np.int64), e)
+        return [outs[:, i] for i in range(T)]
+    return perm
+
+
+def place_merkle(B, n, dim, base, vec_base, fetch_flags, fetch_values):
+    """merkle_commitment over n vectors of `dim` words whose trace starts at stream cell `base`, placed into builder `B` in the cell
+    order of witness.hip: the leaves' sponges, the load_zero cell of the padding, the tree.  `vec_base`: stream cell of word 0 of
+    vector 0 (the assigned vectors the leaves absorb; None: free words).  fetch_flags(lo, hi) / fetch_values(lo, hi): the kernel's
+    flag bytes / the canonical values of stream cells [lo, hi) of a keygen-style run (one instance of each kind of permutation is
+    read).  -> (stream cell of the root, first cell after the trace)"""
+    lay = merkle_leaf_layout(dim)
+    perm = _perm_placer(B, fetch_flags, fetch_values)
+    v = np.arange(n, dtype=np.int64)
+    state, at = None, base + v * lay["leaf_cells"]
+    for p, n_in in enumerate(lay["n_ins"]):
+        state = perm(at, n_in, state, None if vec_base is None else [vec_base + v * dim + 2 * p + i for i in range(n_in)])
+        at = at + lay["sizes"][p]
+    lp, pos = 1 << (n - 1).bit_length(), base + n * lay["leaf_cells"]
+    digest = np.full(lp, pos, dtype=np.int64)                # the padding leaves: the zero cell that follows the leaves
+    digest[:n] = state[1]
+    if lp > n:
+        B.constant_cell(pos, 0)                              # ctx.load_zero()
+        pos += 1
+    while digest.size > 1:
+        bases = pos + np.arange(digest.size // 2, dtype=np.int64) * lay["node_cells"]
+        digest = perm(bases + perm_cells(2), 0, perm(bases, 2, None, [digest[0::2], digest[1::2]]), [])[1]
+        pos += bases.size * lay["node_cells"]
+    return int(digest[0]), pos
+
+
+def build_merkle(n, dim, fetch_flags, fetch_values, builder=None):
+    """the stand-alone Merkle circuit (examples/merkle.rs; pipeline.MerkleHotPath): the n * dim vector words assigned first
+    (ctx.assign_witnesses, as the reference's chip_merkle does), then merkle_commitment over them (`builder`, fetch_flags,
+    fetch_values: as build_merkle_update).  Constant cells are the cells the kernels flag, the zero cell of the padding and the
+    sponge's initial state at the start of every leaf and tree node.  -> (CopyMap, root cell)"""
+    n_in = n * dim
+    if n < 1 or dim < 1:
+        raise ValueError("a commitment is over at least one vector of at least one word")
+    if np.asarray(fetch_flags(0, n_in)).any():
+        raise ValueError("the assigned vector words carry no gate or constant flag")
+    lay, lp = merkle_leaf_layout(dim), 1 << (n - 1).bit_length()
+    total = n_in + n * lay["leaf_cells"] + (lp > n) + (lp - 1) * lay["node_cells"]
+    B = (builder or _Builder)(total, 0)
+    root, end = place_merkle(B, n, dim, n_in, 0, fetch_flags, fetch_values)
+    if end != total:
+        raise ValueError("the trace does not end where the circuit does")
+    return B.finish(), root
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # Merkle path updates (include/vdb.h vdb_wit_merkle_update; pipeline.UpdateHotPath)
 def merkle_update_layout(m, dim, depth):
     """where the cells of a batch of m path updates lie: dict(nperm, n_ins, sizes, leaf_cells, node_cells, level_cells, ip_cells,
     per_update, n_vec, old_leaf, bits, sibs, n_in, total) — the last five stream cells: [new vectors | old leaves | bits | siblings],
     then update j's block at n_in + j * per_update: its leaf sponge, per level [assert_bit 4 | select lo 8 | select ro 8 | H old |
     select ln 8 | select rn 8 | H new], the index inner product"""
-    from .copymap import perm_cells
     if m < 1 or depth < 1 or dim < 1:
         raise ValueError("a batch holds at least one update of a tree with at least two leaves")
-    nperm = (dim + 1) // 2 + (1 if dim % 2 == 0 else 0)
-    n_ins = [max(0, min(2, dim - 2 * p)) for p in range(nperm)]
-    sizes = [perm_cells(k) for k in n_ins]
-    node_cells = perm_cells(2) + perm_cells(0)
-    lay = dict(nperm=nperm, n_ins=n_ins, sizes=sizes, leaf_cells=sum(sizes), node_cells=node_cells, level_cells=36 + 2 * node_cells,
-               ip_cells=1 + 3 * (depth - 1), n_vec=m * dim, old_leaf=m * dim, bits=m * dim + m, sibs=m * dim + m + m * depth)
+    lay = merkle_leaf_layout(dim)
+    lay.update(level_cells=36 + 2 * lay["node_cells"], ip_cells=1 + 3 * (depth - 1), n_vec=m * dim, old_leaf=m * dim, bits=m * dim + m,
+               sibs=m * dim + m + m * depth)
     lay["per_update"] = lay["leaf_cells"] + depth * lay["level_cells"] + lay["ip_cells"]
     lay["n_in"] = m * (dim + 1 + 2 * depth)
     lay["total"] = lay["n_in"] + m * lay["per_update"]
@@ -888,7 +1004,6 @@ def trace_merkle_update(m, dim, depth, fetch_flags, fetch_values):
     then per update the leaf sponge, the levels and the index, the top of the old path tied to the top of the update before.
     fetch_flags(lo, hi) / fetch_values(lo, hi): flag bytes / canonical values of stream cells of a keygen-style run (one instance of
     every kind of permutation is read: the Poseidon constants are fixed-column values).  -> (CopyMap, public cells)"""
-    from .copymap import perm_cells, permutation_template
     lay = merkle_update_layout(m, dim, depth)
     total = lay["total"]
     copy_of, cidx, gate = list(range(total)), [-1] * total, [False] * total
@@ -981,68 +1096,16 @@ def trace_merkle_update(m, dim, depth, fetch_flags, fetch_values):
     return cm, merkle_update_instances(m, top_old0, idx_cells, [lay["old_leaf"] + j for j in range(m)], new_leaves, prev_top)
 
 
-def _perm_block(flags, values, n_in, fresh, tied):
-    """one PoseidonChip::permutation as a unit block (external inputs 0..2: the sponge state, 3..4: the absorbed words): `fresh`: the
-    state is the chip's initial one (constants 2^64, 0, 0) instead of external cells; `tied`: the words copy external cells"""
-    from .copymap import T, permutation_template
-    src, fin = permutation_template(flags, n_in)
-    flags = np.asarray(flags, dtype=np.uint8)
-    b = Block.__new__(Block)
-    out = np.where(src >= 0, src, SELF).astype(np.int64)
-    consts, cmap, cidx = [], {}, np.full(src.size, -1, dtype=np.int64)
-
-    def cid(v):
-        if v not in cmap:
-            cmap[v] = len(consts)
-            consts.append(v)
-        return cmap[v]
-    for i in np.flatnonzero(flags & 2):
-        cidx[i] = cid(int(values[i]) % R)
-    for i in range(T):
-        cols = np.flatnonzero(src == -10 - i)
-        if fresh:
-            for c in cols:
-                cidx[c] = cid((1 << 64) if i == 0 else 0)
-        else:
-            out[cols] = EXT0 - i
-    if tied:
-        for i in range(2):
-            out[np.flatnonzero(src == -20 - i)] = EXT0 - (T + i)
-    b.src, b.gate, b.cidx, b.consts = out, (flags & 1).astype(bool), cidx, consts
-    b.asserted, b.lk = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
-    b.n, b.n_lk, b.outs = src.size, 0, np.asarray(fin, dtype=np.int64)
-    b.local, b.isext = b.src >= 0, b.src <= EXT0
-    b.ext_no = np.where(b.isext, EXT0 - b.src, 0)
-    b.lk_isext, b.lk_ext_no = np.zeros(0, dtype=bool), np.zeros(0, dtype=np.int64)
-    return b
-
-
 def build_merkle_update(m, dim, depth, fetch_flags, fetch_values, builder=None):
     """trace_merkle_update's map assembled from unit blocks — one per kind of permutation, the bit with its two selects, the two selects
     of the new path, the index inner product — each placed for all m updates at once, level after level (`builder`: as build_kmeans).
     -> (CopyMap, public cells)"""
-    from .copymap import T, perm_cells
     lay = merkle_update_layout(m, dim, depth)
     B = (builder or _Builder)(lay["total"], 0)
     j = np.arange(m, dtype=np.int64)
     zeros = np.zeros(m, dtype=np.int64)
     base = lay["n_in"] + j * lay["per_update"]
-    blocks = {}
-
-    def perm(bases, n_in, state, msgs):
-        fresh, tied = state is None, n_in > 0
-        key = (n_in, fresh)
-        if key not in blocks:
-            at, size = int(bases[0]), perm_cells(n_in)
-            blocks[key] = _perm_block(fetch_flags(at, at + size), fetch_values(at, at + size), n_in, fresh, tied)
-        e = np.zeros((m, T + 2), dtype=np.int64)
-        if not fresh:
-            for i in range(T):
-                e[:, i] = state[i]
-        for i in range(n_in):
-            e[:, T + i] = msgs[i]
-        outs = B.place(blocks[key], bases, zeros, e)
-        return [outs[:, i] for i in range(T)]
+    perm = _perm_placer(B, fetch_flags, fetch_values)
 
     def node(bases, left, right):
         return perm(bases + perm_cells(2), 0, perm(bases, 2, None, [left, right]), [])[1]

@@ -1,18 +1,15 @@
-"""The Merkle circuit's own copy constraints (what keygen feeds the permutation argument beyond the cells
-the column layout duplicates): for every cell of the Poseidon trace that `merkle_commitment` emits
-(/root/reference/src/gadget/vectordb.rs:165-223 through PoseidonChip<F, 3, 2>), the earlier cell it is a copy of.
+"""The Poseidon permutation's cell template and the tests' host restatements of the permutation argument's inputs.
 
-The trace is data independent, so the map is built symbolically on the host from the cell templates of the halo2-base
-primitives the permutation is made of — GateChip::sum, inner_product with constants, mul, mul_add — in exactly the order
-halo2_vectordb_amd/csrc/witness.hip (trace_permutation) emits them, and instantiated per permutation with numpy.  The
-builder consumes the gate / constant flag bytes of one real permutation (a keygen-style run) both to resolve the one
-structural choice that depends on the spec's constants (inner_product starts with the first operand itself when its
-constant is one) and as a check: every gate-start bit and every constant bit of the template must equal the kernel's.
-tests/test_gpu_rounds.py additionally checks the map against witness values: every cell equals the cell it copies.
-
-The leaves' message words are copies of the vector cells assigned at the head of the stream (ctx.assign_witnesses before
-the gadget runs, as the reference's chip_merkle does).  Constant cells are not part of the map: they are pinned by
-the constants gate of the rounds (rounds.py) instead of being tied to a fixed column.  [UPSTREAM-RECALL] for the primitives' cell templates, as for the kernels themselves."""
+`permutation_template` is one PoseidonChip<F, 3, 2>::permutation as `merkle_commitment` emits it
+(src/gadget/vectordb.rs:165-223): for every cell, the earlier cell of the permutation, the state word or the absorbed
+word it copies.  It is traced symbolically from the cell templates of the halo2-base primitives the permutation is made of —
+GateChip::sum, inner_product with constants, mul, mul_add — in exactly the order halo2_vectordb_amd/csrc/witness.hip
+(trace_permutation) emits them.  The tracer consumes the gate / constant flag bytes of one real permutation (a keygen-style run) both
+to resolve the one structural choice that depends on the spec's constants (inner_product starts with the first operand itself when
+its constant is one) and as a check: every gate-start bit and every constant bit of the template must equal the kernel's.
+The block builders turn the template into a unit block and place it along the leaves and the tree (place_merkle, build_merkle,
+build_merkle_update).  `lookup_sources` and `mapping_from_copy_of` restate on the host what keygen does on the device.
+[UPSTREAM-RECALL] for the primitives' cell templates, as for the kernels themselves."""
 import numpy as np
 
 T, RATE, R_F, R_P = 3, 2, 8, 57
@@ -127,89 +124,6 @@ def perm_cells(n_in):
     return {2: 18, 1: 15, 0: 12}[n_in] + 2238
 
 
-def merkle_copy_map(n, dim, flags, vectors_assigned=True, placements=None):
-    """copy_of[i] = stream offset of the cell that cell i copies (i itself for new cells and constants) for merkle_commitment
-    over n vectors of `dim` words; `flags`: the flag bytes of a keygen-style run of the same circuit (vdb_wit_merkle_dev with a
-    selector buffer).  With `vectors_assigned` the stream starts with the n * dim assigned vector words
-    (ctx.assign_witnesses, as the reference's chip_merkle does) and every message word a leaf absorbs is a copy of its
-    cell; without, the message words are free cells.  Also returns the stream offset of the root cell and the offsets of the
-    cells that hold the sponge's initial state (every leaf and every tree node starts from [2^64, 0, 0]; the kernels emit them
-    as ordinary cells, the circuit must pin them like constants)."""
-    flags = np.asarray(flags, dtype=np.uint8)
-    n_in = n * dim if vectors_assigned else 0
-    if n_in:
-        if flags[:n_in].any():
-            raise ValueError("the assigned vector words carry no gate or constant flag")
-        inner = [] if placements is not None else None
-        gadget, root, init = merkle_copy_map(n, dim, flags[n_in:], vectors_assigned=None, placements=inner)
-        if placements is not None:
-            placements.extend((k, bases + n_in, states) for k, bases, states in inner)
-        return np.concatenate([np.arange(n_in, dtype=np.int64), gadget + n_in]), root + n_in, init + n_in
-    nperm = (dim + 1) // 2 + (1 if dim % 2 == 0 else 0)
-    n_ins = [max(0, min(2, dim - 2 * p)) for p in range(nperm)]
-    sizes = [perm_cells(k) for k in n_ins]
-    leaf_cells = sum(sizes)
-    lp = 1
-    while lp < n:
-        lp <<= 1
-    zero_cell = 1 if lp > n else 0
-    node_cells = perm_cells(2) + perm_cells(0)
-    total = n * leaf_cells + zero_cell + (lp - 1) * node_cells
-    if total != flags.size:
-        raise ValueError("flags do not belong to this circuit")
-    copy_of = np.arange(total, dtype=np.int64)
-    templates = {}
-    init_cells = []          # cells that hold the sponge's initial state [2^64, 0, 0]: constants of the circuit, though not flagged
-
-    def template(n_in, at):
-        if n_in not in templates:
-            templates[n_in] = permutation_template(flags[at: at + perm_cells(n_in)], n_in)
-        return templates[n_in]
-
-    def place(bases, n_in, state_src, msg_src):
-        """instantiate the template at every offset in `bases`; state_src / msg_src: per input, array of source offsets (or
-        None: a free / constant-initialised cell)"""
-        src, fin = template(n_in, int(bases[0]))
-        if placements is not None:      # (message words absorbed, instance offsets, which of the T state inputs start from the chip's initial state)
-            placements.append((n_in, bases.copy(), [st is None for st in state_src]))
-        idx = bases[:, None] + np.arange(src.size)[None, :]
-        val = np.where(src[None, :] >= 0, bases[:, None] + np.maximum(src, 0)[None, :], idx)
-        for i in range(T):
-            cols = np.flatnonzero(src == -10 - i)
-            if state_src[i] is not None and cols.size:
-                val[:, cols] = state_src[i][:, None]
-            elif cols.size:
-                init_cells.append(idx[:, cols].reshape(-1))
-        for i in range(n_in):
-            cols = np.flatnonzero(src == -20 - i)
-            if msg_src[i] is not None and cols.size:
-                val[:, cols] = msg_src[i][:, None]
-        copy_of[idx.reshape(-1)] = val.reshape(-1)
-        return [bases + f for f in fin]
-
-    # leaves: the sponge state runs through the leaf's permutations; the first starts from the chip's initial state
-    leaf_base = np.arange(n, dtype=np.int64) * leaf_cells
-    state, off = [None] * T, 0
-    for p in range(nperm):
-        # (vectors_assigned is None in the inner call of the assigned-vectors case: the words sit n * dim cells before the gadget)
-        msg = [np.arange(n, dtype=np.int64) * dim + 2 * p + i - n * dim for i in range(n_ins[p])] if vectors_assigned is None else [None] * n_ins[p]
-        state = place(leaf_base + off, n_ins[p], state, msg)
-        off += sizes[p]
-    digest = np.full(lp, n * leaf_cells, dtype=np.int64)        # padding leaves: the load_zero cell after the leaves
-    digest[:n] = state[1]
-    # tree levels: absorb [left, right], then the padding-only permutation
-    pos, width = n * leaf_cells + zero_cell, lp
-    while width > 1:
-        half = width // 2
-        bases = pos + np.arange(half, dtype=np.int64) * node_cells
-        st1 = place(bases, 2, [None] * T, [digest[0:width:2], digest[1:width:2]])
-        st2 = place(bases + perm_cells(2), 0, st1, [])
-        digest = st2[1]
-        pos += half * node_cells
-        width = half
-    return copy_of, int(digest[0]), np.sort(np.concatenate(init_cells))
-
-
 def lookup_sources(flags, n_lookup):
     """For every cell of the lookup stream (cells_to_lookup: copies of advice cells, laid out in the lookup columns) the
     stream offset of the advice cell it copies, from a keygen-style run's flag bytes: the kernels mark those cells with bit 2
@@ -294,48 +208,3 @@ def mapping_from_copy_of(copy_of, break_points, n_cols, rows, lookup_src=None, l
     mapping = (np.arange(total_cols, dtype=np.uint64)[:, None] << np.uint64(32)) | np.arange(rows, dtype=np.uint64)[None, :]
     mapping[pc, prw] = (pc[nxt_idx].astype(np.uint64) << np.uint64(32)) | prw[nxt_idx].astype(np.uint64)
     return mapping
-
-
-def merkle_circuit_map(n, dim, flags, fetch, vectors_assigned=True):
-    """The Merkle circuit's whole constraint map as a circuit_sym.CopyMap, plus the root cell: merkle_copy_map's copies, the
-    lookup-free gate flags, and every constant cell with the fixed-column value it is tied to — the cells the kernels flag
-    (bit 1: Poseidon round constants, matrix entries, the ones and zeros of the gate templates), the zero cell of the padding,
-    and the sponge's initial state [2^64, 0, 0] at the start of every leaf and tree node, which the kernels emit as ordinary
-    cells.  Constants are data independent and repeat with the permutation template, so their values are read from ONE instance
-    of each template through `fetch(lo, hi)` -> canonical integers of stream cells [lo, hi) of a keygen-style run."""
-    from .circuit_sym import CopyMap
-    flags = np.asarray(flags, dtype=np.uint8)
-    placements = []
-    copy_of, root, _init = merkle_copy_map(n, dim, flags, vectors_assigned, placements)
-    const_idx = np.full(flags.size, -1, dtype=np.int64)
-    consts, cmap = [], {}
-
-    def cid(v):
-        if v not in cmap:
-            cmap[v] = len(consts)
-            consts.append(v)
-        return cmap[v]
-
-    first = {}
-    for n_in, bases, fresh_state in placements:
-        size = perm_cells(n_in)
-        if n_in not in first:
-            b0 = int(bases[0])
-            src, _ = permutation_template(flags[b0: b0 + size], n_in)
-            vals = fetch(b0, b0 + size)
-            cst = np.flatnonzero(flags[b0: b0 + size] & 2)
-            first[n_in] = (src, cst, np.asarray([cid(int(vals[i])) for i in cst], dtype=np.int64))
-        src, cst, ids = first[n_in]
-        const_idx[(bases[:, None] + cst[None, :]).reshape(-1)] = np.broadcast_to(ids[None, :], (bases.size, cst.size)).reshape(-1)
-        for i, fresh in enumerate(fresh_state):            # state word i starts from the chip's initial state: capacity 2^64, then zeros
-            cols = np.flatnonzero(src == -10 - i)
-            if fresh and cols.size:
-                const_idx[(bases[:, None] + cols[None, :]).reshape(-1)] = cid((1 << 64) if i == 0 else 0)
-    # flagged cells outside the permutations (the padding's load_zero cell)
-    rest = np.flatnonzero(((flags & 2) != 0) & (const_idx < 0))
-    for i in rest:
-        const_idx[i] = cid(int(fetch(int(i), int(i) + 1)[0]))
-    tied = const_idx >= 0
-    if (copy_of[tied] != np.flatnonzero(tied)).any():
-        raise ValueError("a constant cell of the Merkle circuit copies another cell")
-    return CopyMap(copy_of, const_idx, consts, np.zeros(flags.size, dtype=bool), (flags & 1).astype(bool), np.zeros(0, dtype=np.int64)), root

@@ -745,15 +745,10 @@ class MerkleHotPath(HotPath):
         return self.d_root.download((4,))
 
     def constraint_map(self, d_flags, on_device=True):
-        if on_device:
-            from .circuit_dev import DeviceBuilder, place_merkle
-            bld = DeviceBuilder(self.n_cells, 0)
-            root, end = place_merkle(bld, self.n, self.dim, self.n_in, 0, functools.partial(self._fetch_flags, d_flags), self._fetch)
-            assert end == self.n_cells
-            cm = bld.finish()
-        else:
-            from .copymap import merkle_circuit_map
-            cm, root = merkle_circuit_map(self.n, self.dim, d_flags.download((self.n_cells,), dtype=np.uint8), self._fetch)
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        cm, root = CS.build_merkle(self.n, self.dim, functools.partial(self._fetch_flags, d_flags), self._fetch, builder=DeviceBuilder if on_device else None)
+        assert cm.n_cells == self.n_cells
         return cm, [root], root                    # examples/merkle.rs:47 make_public.push(root)
 
 
@@ -937,14 +932,13 @@ class TopKQueryHotPath(HotPath):
     def constraint_map(self, d_flags, on_device=True):
         # the queries' blocks, then merkle_commitment over the same assigned vectors, in one map (examples/query.rs)
         from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder, place_merkle
+        from .circuit_dev import DeviceBuilder
         bld, (_ind, res), used = CS.build_nearest_topk(self.metric_name, self.q, self.n, self.dim, self.topk, self.P, self.L,
-                                                       builder=DeviceBuilder if on_device or self.commit else None,
-                                                       extra_cells=self.merkle_cells, finish=False)
+                                                       builder=DeviceBuilder if on_device else None, extra_cells=self.merkle_cells, finish=False)
         assert used == self.n_in + self.nearest_cells
         public, root = [int(c) for c in np.asarray(res).reshape(-1)], None
         if self.commit:
-            root, end = place_merkle(bld, self.n, self.dim, used, self.q * self.dim, functools.partial(self._fetch_flags, d_flags), self._fetch)
+            root, end = CS.place_merkle(bld, self.n, self.dim, used, self.q * self.dim, functools.partial(self._fetch_flags, d_flags), self._fetch)
             assert end == self.n_cells
             public.append(root)
         return bld.finish(), public, root

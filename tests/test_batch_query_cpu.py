@@ -66,7 +66,7 @@ def test_a_batch_of_one_is_the_single_query_circuit(metric, n, dim):
 
 
 def test_builder_contract_leaves_room_for_the_commitment():
-    """builder= / extra_cells= / finish= as for build_nearest: the builder comes back with the cells used, so that place_merkle can follow"""
+    """builder= / extra_cells= / finish= as for build_nearest: the builder comes back with the cells used, so that circuit_sym.place_merkle can follow"""
     metric, q, n, dim = SHAPES[0]
     whole, _ = CS.build_nearest_batch(metric, q, n, dim, P, L)
     B, (ind, res), used = CS.build_nearest_batch(metric, q, n, dim, P, L, builder=CS._Builder, extra_cells=77, finish=False)

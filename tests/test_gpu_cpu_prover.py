@@ -102,15 +102,15 @@ def test_cosine_kmeans_resident_and_streamed(api, O):
 
 
 def test_merkle_circuit_degree_three(api, O):
-    from halo2_vectordb_amd.copymap import merkle_circuit_map
+    from halo2_vectordb_amd.circuit_sym import build_merkle
     from halo2_vectordb_amd.pipeline import MerkleHotPath
     from halo2_vectordb_amd.rounds import ProverRounds
     from oracle import prover as PV
     n, dim, k = 6, 5, 11
     hp = MerkleHotPath(n=n, dim=dim, k=k, tau=TAU).setup()
     pr = ProverRounds(hp)
-    pr.map_on_device = False          # the host's construction of the map (copymap.merkle_circuit_map), the one the CPU side is given below:
-    pr.keygen()                       # the device's placement numbers the constants in another order — another, equally valid, fixed column
+    pr.map_on_device = False          # the host's construction of the map (circuit_sym.build_merkle on the numpy builder), the one the CPU
+    pr.keygen()                       # side is given below
     try:
         qv = O.quantize(hp.vectors_f64, hp.P)
         c = O.Ctx(store=True, keygen=True, plan_k=k)
@@ -124,7 +124,7 @@ def test_merkle_circuit_degree_three(api, O):
         d_flags.free()
         assert np.array_equal(flags & 1, c.selectors())
         ints = O.fr_to_ints(stream)
-        cm, root_cell = merkle_circuit_map(n, dim, flags, lambda lo, hi: ints[lo:hi])
+        cm, root_cell = build_merkle(n, dim, lambda lo, hi: flags[lo:hi], lambda lo, hi: ints[lo:hi])
         assert np.array_equal(stream[root_cell], root)
         cs = PV.Circuit(k, hp.L, c.break_points(), c.selectors(), 0, cm.copy_of, cm.const_idx, cm.consts, None, [int(root_cell)])
         assert (cs.degree, cs.chunk_len, cs.n_h) == (3, 1, 2) and pr.degree == 3

@@ -87,8 +87,9 @@ def test_query_proof_states_the_result_and_the_root(api, O):
 
 @pytest.mark.parametrize("n,dim", [(6, 5), (5, 4), (8, 3)])
 def test_merkle_map_built_on_the_device_is_the_host_built_map(api, O, n, dim):
-    """circuit_dev.place_merkle (the Poseidon trace's copy constraints placed by vdb_copymap_place_dev) against
-    copymap.merkle_circuit_map (numpy): same copies, constants, gate flags, root cell — odd and even word counts, padded trees"""
+    """circuit_sym.build_merkle placed by circuit_dev.DeviceBuilder (vdb_copymap_place_dev) against the same walk placed by the numpy
+    builder: same copies, constants in the same order, gate flags, root cell — odd and even word counts, padded trees
+    (tests/test_merkle_map_cpu.py holds the walk itself against the oracle's closure)"""
     from halo2_vectordb_amd.pipeline import MerkleHotPath
     from halo2_vectordb_amd.rounds import ProverRounds
     hp = MerkleHotPath(n=n, dim=dim, k=11, tau=TAU).setup()
@@ -106,7 +107,8 @@ def test_merkle_map_built_on_the_device_is_the_host_built_map(api, O, n, dim):
         d, h = maps[True], maps[False]
         assert d[4] == h[4] and d[5] == h[5]
         assert np.array_equal(d[0], h[0]) and np.array_equal(d[2], h[2])
-        # the constants may be numbered differently: compare the values the cells are tied to
+        # both builders number the constants by first use along one walk; the values the cells are tied to, besides
+        assert np.array_equal(d[1], h[1]) and d[3] == h[3]
         val = lambda m: np.where(m[1] >= 0, np.asarray(m[3] + [0], dtype=object)[np.maximum(m[1], -1)], -1)
         assert np.array_equal(val(d), val(h))
     finally:
