@@ -157,6 +157,15 @@ struct ProfScope {
 };
 #define VDB_PROF(name) vdb::ProfScope _prof_scope_(name)
 #define VDB_PROF_ON(name, stream) vdb::ProfScope _prof_scope_(name, stream)
+// One kernel on the main stream, no dynamic LDS, timed under the kernel's own name; returns from the enclosing function on a launch error
+#define VDB_LAUNCH(kernel, grid, block, ...)                                           \
+  do {                                                                                 \
+    {                                                                                  \
+      VDB_PROF(#kernel);                                                               \
+      hipLaunchKernelGGL(kernel, grid, block, 0, vdb::ctx().stream, __VA_ARGS__);      \
+    }                                                                                  \
+    VDB_LAUNCH_CHECK();                                                                \
+  } while (0)
 
 // Fr domain constants computed on the host with the same field code
 u256 host_root_of_unity(uint32_t k);  // ROOT_OF_UNITY^(2^(28-k)), Montgomery

@@ -263,12 +263,7 @@ extern "C" int vdb_copymap_finish_dev(const int64_t* copy_of_dev, const int64_t*
   unsigned long long* d = (unsigned long long*)scratch_get(5, 64);
   if (!d) return VDB_ERR_OOM;
   VDB_HIP(hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), cx.stream));
-  {
-    VDB_PROF("k_map_finish");
-    hipLaunchKernelGGL(k_map_finish, dim3((unsigned)(cx.cu_count * 16)), dim3(256), 0, cx.stream, copy_of_dev, const_idx_dev, n_cells, lookup_src_dev, n_lookup,
-                       parent_dev, d);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_map_finish, dim3((unsigned)(cx.cu_count * 16)), dim3(256), copy_of_dev, const_idx_dev, n_cells, lookup_src_dev, n_lookup, parent_dev, d);
   unsigned long long h[2];
   VDB_HIP(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, cx.stream));
   VDB_HIP(hipStreamSynchronize(cx.stream));
@@ -331,11 +326,7 @@ extern "C" int vdb_permutation_mapping_ws_dev(int64_t* parent_dev, uint64_t n_ce
   // 1. roots
   for (int it = 0; it < 64; it++) {
     VDB_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), cx.stream));
-    {
-      VDB_PROF("k_pm_jump");
-      hipLaunchKernelGGL(k_pm_jump, dim3(grid), dim3(256), 0, cx.stream, parent_dev, n_cells, d_flag);
-    }
-    VDB_LAUNCH_CHECK();
+    VDB_LAUNCH(k_pm_jump, dim3(grid), dim3(256), parent_dev, n_cells, d_flag);
     int changed = 0;
     VDB_HIP(hipMemcpyAsync(&changed, d_flag, sizeof(int), hipMemcpyDeviceToHost, cx.stream));
     VDB_HIP(hipStreamSynchronize(cx.stream));
@@ -411,11 +402,7 @@ extern "C" int vdb_permutation_mapping_ws_dev(int64_t* parent_dev, uint64_t n_ce
   // 4. cycles
   const uint64_t n_grid = (n_cols + 2) * rows;  // [advice | lookup | constants | instance]
   hipLaunchKernelGGL(k_pm_identity, dim3((unsigned)((n_grid + 255) / 256)), dim3(256), 0, cx.stream, mapping_dev, n_cols + 2, rows);
-  {
-    VDB_PROF("k_pm_link");
-    hipLaunchKernelGGL(k_pm_link, dim3(grid), dim3(256), 0, cx.stream, keys2, vals2, total, rows, mapping_dev);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_pm_link, dim3(grid), dim3(256), keys2, vals2, total, rows, mapping_dev);
   VDB_HIP(hipStreamSynchronize(cx.stream));
   return VDB_OK;
 }

@@ -127,12 +127,8 @@ extern "C" int vdb_mock_check_instances_dev(const vdb_fr* stream_dev, uint64_t n
   unsigned long long h[2] = {0ull, ~0ull};
   VDB_HIP(hipMemcpyAsync(d, h, sizeof(h), hipMemcpyHostToDevice, c.stream));
   VDB_HIP(hipStreamSynchronize(c.stream));  // `h` is on the stack
-  {
-    VDB_PROF("k_mock_instances");
-    hipLaunchKernelGGL(k_mock_instances, dim3((unsigned)((n_instances + 255) / 256)), dim3(256), 0, c.stream, as_u256(stream_dev), n_cells, instance_cells_dev,
-                       as_u256(instances_dev), n_instances, d);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_mock_instances, dim3((unsigned)((n_instances + 255) / 256)), dim3(256), as_u256(stream_dev), n_cells, instance_cells_dev,
+             as_u256(instances_dev), n_instances, d);
   VDB_HIP(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, c.stream));
   VDB_HIP(hipStreamSynchronize(c.stream));
   out->instances_unequal = h[0], out->first_instance = h[1];

@@ -662,28 +662,18 @@ int vdb_grand_product_dev(const vdb_fr* num_dev, const vdb_fr* den_dev, size_t n
   VDB_REQUIRE_INIT();
   VDB_ARG(num_dev && den_dev && z_dev && n >= 1, "bad argument");
   if (n_cols == 0) return VDB_OK;
-  {
-    VDB_PROF("k_grand_product");
-    hipLaunchKernelGGL(k_grand_product, dim3((unsigned)n_cols), dim3(GP_THREADS), 0, ctx().stream, as_u256(num_dev), as_u256(den_dev), as_u256(z_dev),
-                     (uint64_t)n, (uint64_t)n);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_grand_product, dim3((unsigned)n_cols), dim3(GP_THREADS), as_u256(num_dev), as_u256(den_dev), as_u256(z_dev), (uint64_t)n, (uint64_t)n);
   return VDB_OK;
 }
 
 // queues the evaluation kernel: out_dev receives n_cols values
 static int eval_polys_launch(const vdb_fr* coeff_dev, size_t n_cols, size_t n, const vdb_fr* x, u256* dout) {
-  Context& cx = ctx();
   u256 xv;
   memcpy(&xv, x, 32);
   u256 y = xv;
   for (int i = 0; i < 8; i++) y = fr_mul(y, y);  // x^256
   y = fr_mul(y, host_fr_from_u64(32));             // pre-scaled for the nine-limb product
-  {
-    VDB_PROF("k_eval_polys");
-    hipLaunchKernelGGL(k_eval_polys, dim3((unsigned)n_cols), dim3(EV_THREADS), 0, cx.stream, as_u256(coeff_dev), (uint64_t)n, xv, y, dout);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_eval_polys, dim3((unsigned)n_cols), dim3(EV_THREADS), as_u256(coeff_dev), (uint64_t)n, xv, y, dout);
   return VDB_OK;
 }
 int vdb_eval_polys_dev(const vdb_fr* coeff_dev, size_t n_cols, size_t n, const vdb_fr* x, vdb_fr* out_host) {
@@ -765,22 +755,14 @@ int vdb_divide_by_vanishing_dev(vdb_fr* h_ext_dev, uint32_t k, uint32_t ext_k) {
   if (!dt) return VDB_ERR_OOM;
   VDB_HIP(hipMemcpyAsync(dt, t.data(), period * sizeof(u256), hipMemcpyHostToDevice, cx.stream));
   const uint64_t ne = 1ull << (k + ext_k);
-  {
-    VDB_PROF("k_mul_periodic");
-    hipLaunchKernelGGL(k_mul_periodic, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, cx.stream, as_u256(h_ext_dev), ne, dt, period - 1);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_mul_periodic, dim3((unsigned)((ne + 255) / 256)), dim3(256), as_u256(h_ext_dev), ne, dt, period - 1);
   VDB_HIP(hipStreamSynchronize(cx.stream));  // t is a host vector
   return VDB_OK;
 }
 // z columns of `n` entries from the terms in scratch: z[0 .. usable] is the running product, the rest zero
 static int product_columns(const u256* num, const u256* den, size_t n_z, size_t n, size_t usable_rows, u256* z) {
   Context& cx = ctx();
-  {
-    VDB_PROF("k_grand_product");
-    hipLaunchKernelGGL(k_grand_product, dim3((unsigned)n_z), dim3(GP_THREADS), 0, cx.stream, num, den, z, (uint64_t)usable_rows + 1, (uint64_t)n);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_grand_product, dim3((unsigned)n_z), dim3(GP_THREADS), num, den, z, (uint64_t)usable_rows + 1, (uint64_t)n);
   if (usable_rows + 1 < n) {
     hipLaunchKernelGGL(k_zero_tail, dim3((unsigned)((n - usable_rows - 1 + 255) / 256), (unsigned)n_z), dim3(256), 0, cx.stream, z, (uint64_t)n,
                        (uint64_t)usable_rows + 1, (uint64_t)n);
@@ -813,12 +795,7 @@ int vdb_permutation_sigma_dev(const uint64_t* mapping_dev, size_t n_cols, uint32
   VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), cx.stream));
   hipLaunchKernelGGL(k_beta_omega_powers, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cx.stream, host_root_of_unity(k), mont_one<Fr>(), n, wpow);
   hipLaunchKernelGGL(k_beta_omega_powers, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, cx.stream, dv, mont_one<Fr>(), (uint64_t)n_cols, dpow);
-  {
-    VDB_PROF("k_perm_sigma");
-    hipLaunchKernelGGL(k_perm_sigma, dim3((unsigned)((n_cols * n + 255) / 256)), dim3(256), 0, cx.stream, mapping_dev, (uint64_t)n_cols, n, wpow, dpow,
-                       as_u256(sigma_dev), derr);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_perm_sigma, dim3((unsigned)((n_cols * n + 255) / 256)), dim3(256), mapping_dev, (uint64_t)n_cols, n, wpow, dpow, as_u256(sigma_dev), derr);
   int herr = 0;
   VDB_HIP(hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, cx.stream));
   VDB_HIP(hipStreamSynchronize(cx.stream));
@@ -1129,12 +1106,8 @@ static int lookup_eval(const vdb_fr* input_ext_dev, const vdb_fr* table_ext_dev,
   memcpy(&beta_m, beta, 32);
   memcpy(&gamma_m, gamma, 32);
   const uint64_t ne = 1ull << q.log_ne;
-  {
-    VDB_PROF("k_lookup_eval");
-    hipLaunchKernelGGL(k_lookup_eval, dim3((unsigned)((ne + 255) / 256), n_slots ? n_slots : 1), dim3(256), 0, ctx().stream, as_u256(input_ext_dev), as_u256(table_ext_dev),
-                       as_u256(perm_input_ext_dev), as_u256(perm_table_ext_dev), as_u256(z_ext_dev), (uint64_t)n_cols, q, beta_m, gamma_m, as_u256(acc_dev));
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_lookup_eval, dim3((unsigned)((ne + 255) / 256), n_slots ? n_slots : 1), dim3(256), as_u256(input_ext_dev), as_u256(table_ext_dev),
+             as_u256(perm_input_ext_dev), as_u256(perm_table_ext_dev), as_u256(z_ext_dev), (uint64_t)n_cols, q, beta_m, gamma_m, as_u256(acc_dev));
   return VDB_OK;
 }
 
@@ -1153,11 +1126,7 @@ int vdb_gather_fr_dev(const vdb_fr* src_dev, const int64_t* idx_dev, size_t n, v
   VDB_REQUIRE_INIT();
   VDB_ARG(n == 0 || (src_dev && idx_dev && out_dev), "bad argument");
   if (n == 0) return VDB_OK;
-  {
-    VDB_PROF("k_gather_fr");
-    hipLaunchKernelGGL(k_gather_fr, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx().stream, as_u256(src_dev), idx_dev, (uint64_t)n, as_u256(out_dev));
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_gather_fr, dim3((unsigned)((n + 255) / 256)), dim3(256), as_u256(src_dev), idx_dev, (uint64_t)n, as_u256(out_dev));
   return VDB_OK;
 }
 int vdb_poly_axpy_dev(vdb_fr* acc_dev, const vdb_fr* a, const vdb_fr* x_dev, size_t n) {
@@ -1196,11 +1165,7 @@ int vdb_kate_div_dev(const vdb_fr* coeff_dev, size_t n_cols, size_t n, const vdb
     drem = (u256*)scratch_get(5, n_cols * sizeof(u256));
     if (!drem) return VDB_ERR_OOM;
   }
-  {
-    VDB_PROF("k_kate_div");
-    hipLaunchKernelGGL(k_kate_div, dim3((unsigned)n_cols), dim3(KD_THREADS), 0, cx.stream, as_u256(coeff_dev), (uint64_t)n, xv, xe, as_u256(quot_dev), drem);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_kate_div, dim3((unsigned)n_cols), dim3(KD_THREADS), as_u256(coeff_dev), (uint64_t)n, xv, xe, as_u256(quot_dev), drem);
   if (rem_host) {
     VDB_HIP(hipMemcpyAsync(rem_host, drem, n_cols * sizeof(u256), hipMemcpyDeviceToHost, cx.stream));
     VDB_HIP(hipStreamSynchronize(cx.stream));
@@ -1214,12 +1179,8 @@ int vdb_poly_lincomb_dev(const vdb_fr* polys_dev, size_t n_cols, size_t n, const
   if (n_cols == 0 || n == 0) return VDB_OK;
   u256 vv;
   memcpy(&vv, v, 32);
-  {
-    VDB_PROF("k_poly_lincomb");
-    hipLaunchKernelGGL(k_poly_lincomb, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx().stream, as_u256(polys_dev), (uint64_t)n_cols, (uint64_t)n,
-                       fr_mul(vv, host_fr_from_u64(32)), as_u256(acc_dev));
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_poly_lincomb, dim3((unsigned)((n + 255) / 256)), dim3(256), as_u256(polys_dev), (uint64_t)n_cols, (uint64_t)n, fr_mul(vv, host_fr_from_u64(32)),
+             as_u256(acc_dev));
   return VDB_OK;
 }
 
@@ -1250,11 +1211,7 @@ int vdb_lookup_permute_dev(const vdb_fr* input_dev, const vdb_fr* table_dev, siz
                      in_hist, derr);
   }
   VDB_LAUNCH_CHECK();
-  {
-    VDB_PROF("k_lp_scan");
-    hipLaunchKernelGGL(k_lp_scan, dim3((unsigned)n_cols), dim3(LP_THREADS), 0, cx.stream, in_hist, tab_hist, bins, off, dist, lpre, totals, derr);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_lp_scan, dim3((unsigned)n_cols), dim3(LP_THREADS), in_hist, tab_hist, bins, off, dist, lpre, totals, derr);
   int h = 0;
   VDB_HIP(hipMemcpyAsync(&h, derr, sizeof(int), hipMemcpyDeviceToHost, cx.stream));
   VDB_HIP(hipStreamSynchronize(cx.stream));
@@ -1263,12 +1220,8 @@ int vdb_lookup_permute_dev(const vdb_fr* input_dev, const vdb_fr* table_dev, siz
     return VDB_ERR_DOMAIN;
   }
   const unsigned gr = (unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-  {
-    VDB_PROF("k_lp_rows");
-    hipLaunchKernelGGL(k_lp_rows, dim3(gr, (unsigned)n_cols), dim3(256), 0, cx.stream, in_hist, tab_hist, off, dist, lpre, totals, bins, (uint64_t)usable_rows,
-                     (uint64_t)n, as_u256(permuted_input_dev), as_u256(permuted_table_dev));
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_lp_rows, dim3(gr, (unsigned)n_cols), dim3(256), in_hist, tab_hist, off, dist, lpre, totals, bins, (uint64_t)usable_rows, (uint64_t)n,
+             as_u256(permuted_input_dev), as_u256(permuted_table_dev));
   return VDB_OK;
 }
 

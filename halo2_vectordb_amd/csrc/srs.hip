@@ -123,29 +123,15 @@ int lagrange_from_monomial(uint32_t k, const Affine* g, Affine* out) {
   }
   const u256 omega_inv = mont_inv<Fr>(host_root_of_unity(k));
   const unsigned blocks = (unsigned)((half + DFT_BLOCK - 1) / DFT_BLOCK);
-  {
-    VDB_PROF("k_g1_dft_twiddles");
-    hipLaunchKernelGGL(k_g1_dft_twiddles, dim3((unsigned)((half + 255) / 256)), dim3(256), 0, cx.stream, omega_inv, (size_t)half, tw);
-  }
-  VDB_LAUNCH_CHECK();
-  {
-    VDB_PROF("k_g1_dft_first");
-    hipLaunchKernelGGL(k_g1_dft_first, dim3(blocks), dim3(DFT_BLOCK), 0, cx.stream, g, half, buf[0]);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_g1_dft_twiddles, dim3((unsigned)((half + 255) / 256)), dim3(256), omega_inv, (size_t)half, tw);
+  VDB_LAUNCH(k_g1_dft_first, dim3(blocks), dim3(DFT_BLOCK), g, half, buf[0]);
   int cur = 0;
   for (uint32_t s = 1; s < k; s++) {
-    VDB_PROF("k_g1_dft_stage");
-    hipLaunchKernelGGL(k_g1_dft_stage, dim3(blocks), dim3(DFT_BLOCK), 0, cx.stream, buf[cur], buf[cur ^ 1], tw, half, s, k - 1 - s);
-    VDB_LAUNCH_CHECK();
+    VDB_LAUNCH(k_g1_dft_stage, dim3(blocks), dim3(DFT_BLOCK), buf[cur], buf[cur ^ 1], tw, half, s, k - 1 - s);
     cur ^= 1;
   }
   const u256 n_inv = from_mont<Fr>(mont_inv<Fr>(host_fr_from_u64(n)));
-  {
-    VDB_PROF("k_g1_dft_finish");
-    hipLaunchKernelGGL(k_g1_dft_finish, dim3((unsigned)((n + DFT_BLOCK - 1) / DFT_BLOCK)), dim3(DFT_BLOCK), 0, cx.stream, buf[cur], n, n_inv, out);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_g1_dft_finish, dim3((unsigned)((n + DFT_BLOCK - 1) / DFT_BLOCK)), dim3(DFT_BLOCK), buf[cur], n, n_inv, out);
   VDB_HIP(hipStreamSynchronize(cx.stream));
   return VDB_OK;
 }
@@ -167,11 +153,7 @@ int vdb_g1_check_dev(const vdb_g1* pts_dev, size_t n, uint64_t* n_bad, uint64_t*
   if (!counters) return VDB_ERR_OOM;
   VDB_HIP(hipMemsetAsync(counters, 0, sizeof(unsigned long long), cx.stream));
   VDB_HIP(hipMemsetAsync(counters + 1, 0xff, sizeof(unsigned long long), cx.stream));
-  {
-    VDB_PROF("k_g1_check");
-    hipLaunchKernelGGL(k_g1_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cx.stream, reinterpret_cast<const Affine*>(pts_dev), n, counters);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_g1_check, dim3((unsigned)((n + 255) / 256)), dim3(256), reinterpret_cast<const Affine*>(pts_dev), n, counters);
   unsigned long long res[2];
   VDB_HIP(hipMemcpyAsync(res, counters, sizeof(res), hipMemcpyDeviceToHost, cx.stream));
   VDB_HIP(hipStreamSynchronize(cx.stream));

@@ -200,12 +200,7 @@ int vdb_g1_decompress_dev(const uint8_t* enc_dev, size_t n, uint32_t sign_bit, v
   if (n == 0) return VDB_OK;
   VDB_ARG(enc_dev && out_dev && status_dev, "null pointer");
   Context& cx = ctx();
-  {
-    VDB_PROF("k_g1_decompress");
-    hipLaunchKernelGGL(k_g1_decompress, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cx.stream, enc_dev, n, sign_bit,
-                       reinterpret_cast<Affine*>(out_dev), status_dev);
-    VDB_LAUNCH_CHECK();
-  }
+  VDB_LAUNCH(k_g1_decompress, dim3((unsigned)((n + 255) / 256)), dim3(256), enc_dev, n, sign_bit, reinterpret_cast<Affine*>(out_dev), status_dev);
   VDB_HIP(hipStreamSynchronize(cx.stream));
   return VDB_OK;
 }

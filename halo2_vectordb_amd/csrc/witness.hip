@@ -149,11 +149,7 @@ static int get_fp(uint32_t P, uint32_t L, FpEntry** out) {
   }
   compute_sizes(T);
   VDB_HIP(hipMalloc(&e->limb_tab, ((size_t)1 << L) * sizeof(u256)));
-  {
-    VDB_PROF("k_limb_table");
-    hipLaunchKernelGGL(k_limb_table, dim3((unsigned)(((1u << L) + 255) / 256)), dim3(256), 0, ctx().stream, e->limb_tab, 1u << L);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_limb_table, dim3((unsigned)(((1u << L) + 255) / 256)), dim3(256), e->limb_tab, 1u << L);
   T.limb_tab = e->limb_tab;
   VDB_HIP(hipMalloc(&e->dev, sizeof(FpTables)));
   VDB_HIP(hipMemcpyAsync(e->dev, &T, sizeof(FpTables), hipMemcpyHostToDevice, ctx().stream));
@@ -460,6 +456,18 @@ __device__ __forceinline__ u256 wave_sum_fr(u256 v) {
   }
   return v;
 }
+__device__ __forceinline__ u256 wave_shfl_up(const u256& v, int off) {
+  u256 o;
+#pragma unroll
+  for (int k = 0; k < 8; k++) o.w[k] = __shfl_up(v.w[k], off, 64);
+  return o;
+}
+__device__ __forceinline__ u256 wave_bcast(const u256& v, int lane) {
+  u256 o;
+#pragma unroll
+  for (int k = 0; k < 8; k++) o.w[k] = __shfl(v.w[k], lane, 64);
+  return o;
+}
 __global__ __launch_bounds__(64) void k_dist_values(const FpTables* __restrict__ T, DistLayout dl, InstMap im, const u256* __restrict__ A,
                                                     const u256* __restrict__ Bv, u256* __restrict__ mid, u256* __restrict__ result) {
   const uint32_t t = blockIdx.x, lane = threadIdx.x, D = dl.D;
@@ -574,11 +582,7 @@ static int inv_list_attach(Streams& st, uint64_t cells) {
 }
 static int inv_list_fixup(const Streams& st) {
   if (!st.inv_cnt) return VDB_OK;
-  {
-    VDB_PROF("k_inv_fixup");
-    hipLaunchKernelGGL(k_inv_fixup, dim3((unsigned)(ctx().cu_count * 8)), dim3(64), 0, ctx().stream, st.adv, st.inv_pos, st.inv_val, st.inv_cnt, st.inv_cap);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_inv_fixup, dim3((unsigned)(ctx().cu_count * 8)), dim3(64), st.adv, st.inv_pos, st.inv_val, st.inv_cnt, st.inv_cap);
   return VDB_OK;
 }
 
@@ -587,10 +591,6 @@ static uint32_t tail_segments(uint32_t n_inst) {
   uint32_t s = 4096 / (groups ? groups : 1);
   if (s < 1) s = 1;
   if (s > 64) s = 64;
-  if (const char* e = getenv("VDB_TAIL_SEGMENTS")) {
-    int v = atoi(e);
-    if (v >= 1 && v <= 1024) s = (uint32_t)v;
-  }
   return s;
 }
 
@@ -599,38 +599,17 @@ static int run_distances(const Streams& st, FpEntry* fp, const DistLayout& dl, c
                          const u256* Bv, u256* mid, u256* result) {
   if (n_inst == 0) return VDB_OK;
   // a rank that stores only a window of the streams first computes every distance's value with the value-only kernels; the emitting
-  // kernels then leave at once wherever none of their cells lie in the window (VDB_WIT_VALUES=0: the walk of rounds 1-3, every rank
-  // running every head and the last tail segment in value-only mode)
-  static const bool values_on = !(getenv("VDB_WIT_VALUES") && getenv("VDB_WIT_VALUES")[0] == '0');
+  // kernels then leave at once wherever none of their cells lie in the window (with selectors requested, every rank runs every head and
+  // the last tail segment in value-only mode instead)
   const bool windowed = !(st.rlo == 0 && st.rhi == ~0ull && st.rllo == 0 && st.rlhi == ~0ull);
-  const int have_values = (windowed && values_on && st.sel == nullptr) ? 1 : 0;
+  const int have_values = (windowed && st.sel == nullptr) ? 1 : 0;
   if (have_values) {
-    {
-      VDB_PROF("k_dist_values");
-      hipLaunchKernelGGL(k_dist_values, dim3(n_inst), dim3(64), 0, ctx().stream, fp->dev, dl, im, A, Bv, mid, result);
-    }
-    VDB_LAUNCH_CHECK();
-    if (dl.tail_cells) {
-      {
-        VDB_PROF("k_dist_tail_values");
-        hipLaunchKernelGGL(k_dist_tail_values, dim3((n_inst + 63) / 64), dim3(64), 0, ctx().stream, st, fp->dev, dl, n_inst, mid, result);
-      }
-      VDB_LAUNCH_CHECK();
-    }
+    VDB_LAUNCH(k_dist_values, dim3(n_inst), dim3(64), fp->dev, dl, im, A, Bv, mid, result);
+    if (dl.tail_cells) VDB_LAUNCH(k_dist_tail_values, dim3((n_inst + 63) / 64), dim3(64), st, fp->dev, dl, n_inst, mid, result);
   }
-  {
-    VDB_PROF("k_dist_head");
-    hipLaunchKernelGGL(k_dist_head, dim3(n_inst), dim3(HEAD_TB), 0, ctx().stream, st, fp->dev, dl, im, A, Bv, mid, result, have_values);
-  }
-  VDB_LAUNCH_CHECK();
-  if (dl.tail_cells) {
-    {
-      VDB_PROF("k_dist_tail");
-      hipLaunchKernelGGL(k_dist_tail, dim3((n_inst + 63) / 64, tail_segments(n_inst)), dim3(64), 0, ctx().stream, st, fp->dev, dl, im, n_inst,
-                       mid, result, have_values);
-    }
-    VDB_LAUNCH_CHECK();
-  }
+  VDB_LAUNCH(k_dist_head, dim3(n_inst), dim3(HEAD_TB), st, fp->dev, dl, im, A, Bv, mid, result, have_values);
+  if (dl.tail_cells)
+    VDB_LAUNCH(k_dist_tail, dim3((n_inst + 63) / 64, tail_segments(n_inst)), dim3(64), st, fp->dev, dl, im, n_inst, mid, result, have_values);
   return VDB_OK;
 }
 
@@ -653,18 +632,6 @@ __device__ __forceinline__ u256 nv_mask_value(const FpTables* T) { return fr_sub
 // qmin(m, x) as a value (vectordb.rs:141-145 folds it over the distances): is_neg(m - x) ? m : x
 __device__ __forceinline__ u256 nv_vmin(const Gadgets& g, const u256& m, const u256& x) {
   return g.v_is_neg(from_mont<Fr>(fr_sub(m, x))) ? m : x;
-}
-__device__ __forceinline__ u256 wave_shfl_up(const u256& v, int off) {
-  u256 o;
-#pragma unroll
-  for (int k = 0; k < 8; k++) o.w[k] = __shfl_up(v.w[k], off, 64);
-  return o;
-}
-__device__ __forceinline__ u256 wave_bcast(const u256& v, int lane) {
-  u256 o;
-#pragma unroll
-  for (int k = 0; k < 8; k++) o.w[k] = __shfl(v.w[k], lane, 64);
-  return o;
 }
 __device__ __forceinline__ u256 nv_cur(const u256* __restrict__ dq, const uint32_t* __restrict__ rq, uint32_t i, uint32_t r, const u256& M) {
   return rq[i] < r ? M : dq[i];
@@ -829,18 +796,6 @@ __global__ __launch_bounds__(64) void k_km_assign(Streams st, const FpTables* __
   }
 }
 #define KM_PF 8
-__device__ __forceinline__ u256 shfl_up_u256(const u256& v, int delta) {
-  u256 r;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.w[i] = (uint32_t)__shfl_up((int)v.w[i], delta, 64);
-  return r;
-}
-__device__ __forceinline__ u256 shfl_u256w(const u256& v, int src) {
-  u256 r;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.w[i] = (uint32_t)__shfl((int)v.w[i], src, 64);
-  return r;
-}
 // One wavefront folds one chain s_v = s_{v-1} + x_v (s_0 = x_0) and emits the qadd cells of steps v = 1 .. N-1 at
 // base + (v - 1) * stride: ORDER 0 = [s_{v-1}, x_v, 1, s_v], ORDER 1 = [x_v, s_{v-1}, 1, s_v].  The chain is
 // sequential in the reference; here lane l owns the contiguous steps [l * per, (l + 1) * per): lane totals (loads
@@ -862,10 +817,10 @@ __device__ __forceinline__ u256 chain_fold_wave(WCtx& c, uint64_t base, uint64_t
   }
   u256 inc = tot;  // inclusive scan over lanes
   for (int o = 1; o < 64; o <<= 1) {
-    u256 t = shfl_up_u256(inc, o);
+    u256 t = wave_shfl_up(inc, o);
     if ((int)lane >= o) inc = fr_add(inc, t);
   }
-  const u256 total = shfl_u256w(inc, 63);
+  const u256 total = wave_bcast(inc, 63);
   u256 run = fr_sub(inc, tot);  // exclusive prefix = s_{lo-1}
   // the lane's cells: steps max(lo, 1) .. hi-1
   const uint32_t first = lo ? lo : 1;
@@ -1104,26 +1059,6 @@ __global__ __launch_bounds__(64) void k_mk_leaf_trace(Streams stq, const FpTable
   u256 in[PSD_RATE] = {cnt > 0 ? msg[off] : u256_zero(), cnt > 1 ? msg[off + 1] : u256_zero()};
   c = trace_permutation(c, T, sp, st, in, cnt);
 }
-// one thread per tree node: two permutations (absorb [l, r], then padding only)
-__global__ __launch_bounds__(64) void k_mk_node(Streams stq, const FpTables* __restrict__ T, const PoseidonSpec* __restrict__ sp, const u256* __restrict__ in_lv,
-                                                uint32_t n_out, uint64_t base, u256* __restrict__ out_lv) {
-  uint32_t t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= n_out) return;
-  const uint64_t p0 = base + (uint64_t)t * (perm_cells(2) + perm_cells(0));
-  u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
-  u256 in[PSD_RATE] = {in_lv[2 * t], in_lv[2 * t + 1]};
-  if (!stq.touches(p0, p0 + perm_cells(2) + perm_cells(0), 0, 0)) {  // outside the rank's window: the digest only
-    psd_permute_absorb(sp, st, in, 2);
-    psd_permute_absorb(sp, st, in, 0);
-    out_lv[t] = st[1];
-    return;
-  }
-  WCtx c = make_ctx(stq, T, p0, 0);
-  c = trace_permutation(c, T, sp, st, in, 2);
-  c = trace_permutation(c, T, sp, st, in, 0);
-  out_lv[t] = st[1];
-}
-
 // The tree without a launch per level's TRACE: the digests of every level first (value only: two permutations of latency per level,
 // k_mk_level_values), then every node's two permutations traced in ONE launch — a thread per (node, permutation), the padding-only
 // permutation starting from the state its thread recomputes.  (One thread per node tracing 4.5 k cells level after level cost ten
@@ -1433,13 +1368,12 @@ static int check_err_flag(int* derr) {
 }
 
 // ---- device-level drivers -------------------------------------------------------------------
-int wit_distance_dev(FpEntry* fp, int metric, const u256* a, const u256* b, size_t n_pairs, size_t dim, Streams st, uint64_t adv_off,
-                     uint64_t lk_off, u256* result) {
+int wit_distance_dev(FpEntry* fp, int metric, const u256* a, const u256* b, size_t n_pairs, size_t dim, Streams st, u256* result) {
   DistLayout dl;
   TRY(dist_layout(fp->host, metric, dim, &dl));
   TRY(inv_list_attach(st, n_pairs * dl.total_cells));
   TRY(set_winv(st, fp->dev));
-  InstMap im{adv_off, lk_off, 1, dl.total_cells, dl.total_lk, 0xffffffffu, 1};
+  InstMap im{0, 0, 1, dl.total_cells, dl.total_lk, 0xffffffffu, 1};
   u256* mid = (u256*)scratch_get(0, n_pairs * 3 * sizeof(u256) + 64);
   if (!mid) return VDB_ERR_OOM;
   TRY(run_distances(st, fp, dl, im, (uint32_t)n_pairs, a, b, mid, result));
@@ -1457,17 +1391,12 @@ __global__ __launch_bounds__(64) void k_fp_op(Streams st, const FpTables* __rest
   result[i] = r;
   if (c.err) atomicOr(st.err, c.err);
 }
-int wit_fp_op_dev(FpEntry* fp, int op, const u256* a, const u256* b, size_t n, Streams st, uint64_t adv_off, uint64_t lk_off, u256* result) {
+int wit_fp_op_dev(FpEntry* fp, int op, const u256* a, const u256* b, size_t n, Streams st, u256* result) {
   uint32_t sz[2];
   fp_op_size(fp->host, op, sz);
   TRY(inv_list_attach(st, n * (uint64_t)sz[0]));
   TRY(set_winv(st, fp->dev));
-  {
-    VDB_PROF("k_fp_op");
-    hipLaunchKernelGGL(k_fp_op, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx().stream, st, fp->dev, op, a, b, (uint32_t)n, sz[0], sz[1], adv_off, lk_off,
-                       result);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_fp_op, dim3((unsigned)((n + 63) / 64)), dim3(64), st, fp->dev, op, a, b, (uint32_t)n, sz[0], sz[1], 0, 0, result);
   return inv_list_fixup(st);
 }
 
@@ -1521,11 +1450,11 @@ static uint32_t nv_select_segments(size_t QT, size_t n, size_t dim) {
   if (s > cap) s = cap;
   return s < 1 ? 1u : (uint32_t)s;
 }
-// Q x [n distances, then topk rounds of qmin chain / is_equal / select_by_indicator / mask], block q at adv_off + q * (cells of one):
+// Q x [n distances, then topk rounds of qmin chain / is_equal / select_by_indicator / mask], block q at q * (cells of one):
 // one run_distances over Q x n instances (instance t = q * n + i is distance(vector_i, query_q)), one value kernel that runs every
 // round of every query, and one launch per emitting stage — the launch count depends on neither Q nor topk
 int wit_nearest_dev(FpEntry* fp, int metric, const u256* queries, const u256* vectors, size_t Q, size_t n, size_t dim, size_t topk, Streams st,
-                    uint64_t adv_off, uint64_t lk_off, u256* ind, u256* result) {
+                    u256* ind, u256* result) {
   DistLayout dl;
   NvLayout nl;
   TRY(nv_layout(fp, metric, n, dim, topk, &dl, &nl));
@@ -1533,45 +1462,22 @@ int wit_nearest_dev(FpEntry* fp, int metric, const u256* queries, const u256* ve
   TRY(inv_list_attach(st, Q * nl.total));
   TRY(set_winv(st, fp->dev));
   const size_t inst = Q * n, rinst = inst * topk;
-  InstMap im{adv_off, lk_off, (uint32_t)n, nl.total, nl.total_l, (uint32_t)n, (uint32_t)n};  // (vector_{t % n}, query_{t / n})
+  InstMap im{0, 0, (uint32_t)n, nl.total, nl.total_l, (uint32_t)n, (uint32_t)n};  // (vector_{t % n}, query_{t / n})
   u256* mid = (u256*)scratch_get(0, (inst * 4 + rinst + 8) * sizeof(u256) + inst * sizeof(uint32_t));
   if (!mid) return VDB_ERR_OOM;
   u256* dist = mid + 3 * inst;
   u256* pm = dist + inst;
   uint32_t* rnd = (uint32_t*)(pm + rinst + 8);
   TRY(run_distances(st, fp, dl, im, (uint32_t)inst, vectors, queries, mid, dist));
-  const NvMap nm{adv_off, lk_off, nl.total, nl.total_l, nl.dist, nl.dist_l, nl.per_r, nl.qmin_l, nl.qmin, nl.qmin + nl.iseq,
+  const NvMap nm{0, 0, nl.total, nl.total_l, nl.dist, nl.dist_l, nl.per_r, nl.qmin_l, nl.qmin, nl.qmin + nl.iseq,
                  nl.qmin + nl.iseq + nl.sel, (uint32_t)Q, (uint32_t)n, (uint32_t)dim, (uint32_t)topk};
-  hipStream_t s = ctx().stream;
-  {
-    VDB_PROF("k_nv_rounds");
-    hipLaunchKernelGGL(k_nv_rounds, dim3((unsigned)Q), dim3(64), 0, s, fp->dev, dist, (uint32_t)n, (uint32_t)topk, pm, rnd);
-  }
-  VDB_LAUNCH_CHECK();
-  if (n > 1) {
-    {
-      VDB_PROF("k_nv_qmin");
-      hipLaunchKernelGGL(k_nv_qmin, dim3((unsigned)((Q * topk * (n - 1) + 63) / 64)), dim3(64), 0, s, st, fp->dev, nm, dist, pm, rnd);
-    }
-    VDB_LAUNCH_CHECK();
-  }
-  {
-    VDB_PROF("k_nv_is_equal");
-    hipLaunchKernelGGL(k_nv_is_equal, dim3((unsigned)((rinst + 63) / 64)), dim3(64), 0, s, st, fp->dev, nm, dist, pm, rnd, ind);
-  }
-  VDB_LAUNCH_CHECK();
-  {
-    // launched for topk == 1 too (one wavefront that finds no lane of its own): the launch count of a call does not depend on topk
-    VDB_PROF("k_nv_mask");
-    hipLaunchKernelGGL(k_nv_mask, dim3((unsigned)((inst * (topk - 1) + 63) / 64 + (topk == 1))), dim3(64), 0, s, st, fp->dev, nm, dist, rnd, ind);
-  }
-  VDB_LAUNCH_CHECK();
-  {
-    const uint32_t S = nv_select_segments(Q * topk, n, dim);
-    VDB_PROF("k_nv_select");
-    hipLaunchKernelGGL(k_nv_select, dim3((unsigned)((Q * topk * dim * S + 63) / 64)), dim3(64), 0, s, st, fp->dev, nm, S, vectors, ind, result);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_nv_rounds, dim3((unsigned)Q), dim3(64), fp->dev, dist, (uint32_t)n, (uint32_t)topk, pm, rnd);
+  if (n > 1) VDB_LAUNCH(k_nv_qmin, dim3((unsigned)((Q * topk * (n - 1) + 63) / 64)), dim3(64), st, fp->dev, nm, dist, pm, rnd);
+  VDB_LAUNCH(k_nv_is_equal, dim3((unsigned)((rinst + 63) / 64)), dim3(64), st, fp->dev, nm, dist, pm, rnd, ind);
+  // launched for topk == 1 too (one wavefront that finds no lane of its own): the launch count of a call does not depend on topk
+  VDB_LAUNCH(k_nv_mask, dim3((unsigned)((inst * (topk - 1) + 63) / 64 + (topk == 1))), dim3(64), st, fp->dev, nm, dist, rnd, ind);
+  const uint32_t S = nv_select_segments(Q * topk, n, dim);
+  VDB_LAUNCH(k_nv_select, dim3((unsigned)((Q * topk * dim * S + 63) / 64)), dim3(64), st, fp->dev, nm, S, vectors, ind, result);
   return inv_list_fixup(st);
 }
 
@@ -1593,7 +1499,7 @@ static int km_layout(FpEntry* fp, int metric, size_t n, size_t dim, size_t K, Di
   return VDB_OK;
 }
 int wit_kmeans_dev(FpEntry* fp, int metric, const u256* vectors, size_t n, size_t dim, size_t K, size_t I, int zero_cached, Streams st,
-                   uint64_t adv_off, uint64_t lk_off, u256* cent_out, u256* ind_out) {
+                   u256* cent_out, u256* ind_out) {
   DistLayout dl;
   KmLayout kl;
   TRY(km_layout(fp, metric, n, dim, K, &dl, &kl));
@@ -1610,44 +1516,20 @@ int wit_kmeans_dev(FpEntry* fp, int metric, const u256* vectors, size_t n, size_
   u256* sizes = sums + K * dim;
   u256* filt = sizes + K;
   // preamble: load_constant(quantization(1.0)); load_zero()
-  {
-    VDB_PROF("k_push_cells");
-    hipLaunchKernelGGL(k_push_cells, dim3(1), dim3(1), 0, s, st, adv_off, fp->host.c_one_q, u256_zero(), zero_cached ? 1u : 2u);
-  }
-  VDB_LAUNCH_CHECK();
-  uint64_t pos = adv_off + (zero_cached ? 1 : 2), lpos = lk_off;
+  VDB_LAUNCH(k_push_cells, dim3(1), dim3(1), st, 0, fp->host.c_one_q, u256_zero(), zero_cached ? 1u : 2u);
+  uint64_t pos = zero_cached ? 1 : 2, lpos = 0;
   VDB_HIP(hipMemcpyAsync(cent, vectors, K * dim * sizeof(u256), hipMemcpyDeviceToDevice, s));
   u256 scale_inv = mont_inv<Fr>(fp->host.scale);
   for (size_t it = 0; it < I; it++) {
     InstMap im{pos, lpos, (uint32_t)K, kl.per_vec, kl.per_vec_l, (uint32_t)K, (uint32_t)K};  // distance(centroid_k, vector_v)
     TRY(run_distances(st, fp, dl, im, (uint32_t)(n * K), cent, vectors, mid, dist));
-    {
-      VDB_PROF("k_km_assign");
-      hipLaunchKernelGGL(k_km_assign, dim3((unsigned)((n + 63) / 64), (unsigned)(2 * K)), dim3(64), 0, s, st, fp->dev, kl, dl, pos, lpos, dist, ind_out);
-    }
-    VDB_LAUNCH_CHECK();
-    {
-      VDB_PROF("k_km_sizes");
-      hipLaunchKernelGGL(k_km_sizes, dim3((unsigned)K), dim3(64), 0, s, st, fp->dev, kl, pos + kl.assign, ind_out, sizes);
-    }
-    VDB_LAUNCH_CHECK();
+    VDB_LAUNCH(k_km_assign, dim3((unsigned)((n + 63) / 64), (unsigned)(2 * K)), dim3(64), st, fp->dev, kl, dl, pos, lpos, dist, ind_out);
+    VDB_LAUNCH(k_km_sizes, dim3((unsigned)K), dim3(64), st, fp->dev, kl, pos + kl.assign, ind_out, sizes);
     uint64_t cb = pos + kl.assign + kl.sizes, clb = lpos + kl.assign_l;
-    {
-      VDB_PROF("k_km_filter");
-      hipLaunchKernelGGL(k_km_filter, dim3((unsigned)((K * n * ((dim + KM_PF - 1) / KM_PF) + 63) / 64)), dim3(64), 0, s, st, fp->dev, kl, cb, vectors,
-                         ind_out, scale_inv, filt);
-    }
-    VDB_LAUNCH_CHECK();
-    {
-      VDB_PROF("k_km_sum");
-      hipLaunchKernelGGL(k_km_sum, dim3((unsigned)(K * dim)), dim3(64), 0, s, st, fp->dev, kl, cb, filt, sums);
-    }
-    VDB_LAUNCH_CHECK();
-    {
-      VDB_PROF("k_km_div");
-      hipLaunchKernelGGL(k_km_div, dim3((unsigned)((K * dim + 63) / 64), 8), dim3(64), 0, s, st, fp->dev, kl, cb, clb, sums, sizes, cent);
-    }
-    VDB_LAUNCH_CHECK();
+    VDB_LAUNCH(k_km_filter, dim3((unsigned)((K * n * ((dim + KM_PF - 1) / KM_PF) + 63) / 64)), dim3(64), st, fp->dev, kl, cb, vectors, ind_out, scale_inv,
+               filt);
+    VDB_LAUNCH(k_km_sum, dim3((unsigned)(K * dim)), dim3(64), st, fp->dev, kl, cb, filt, sums);
+    VDB_LAUNCH(k_km_div, dim3((unsigned)((K * dim + 63) / 64), 8), dim3(64), st, fp->dev, kl, cb, clb, sums, sizes, cent);
     pos += kl.iter;
     lpos += kl.iter_l;
   }
@@ -1673,7 +1555,22 @@ static void mk_layout(size_t n, size_t dim, int zero_cached, MkLayout* o) {
   o->zero_cell = (lp > n && !zero_cached) ? 1 : 0;
   o->total = o->leaves + o->zero_cell + (lp - 1) * (uint64_t)(perm_cells(2) + perm_cells(0));
 }
-int wit_merkle_dev(const u256* vectors, size_t n, size_t dim, int zero_cached, Streams st, uint64_t adv_off, u256* root_out) {
+// The digests of every level of merkle_commitment's tree, values only, into `levels` in k_mk_tree_trace's layout: the lp padded leaf
+// digests, then the levels one after the other (lp + lp / 2 + ... + 1 of the 2 lp entries, the last unused); the root is at *root_off.
+// `states` receives the sponge state before every permutation of every leaf (n * nperm * PSD_T entries).
+static int mk_tree_values(const PoseidonSpec* sp, const u256* vectors, size_t n, size_t dim, const MkLayout& ml, u256* states, u256* levels,
+                          uint64_t* root_off) {
+  const uint64_t lp = ml.n_leaves_pow2;
+  VDB_HIP(hipMemsetAsync(levels, 0, 2 * lp * sizeof(u256), ctx().stream));
+  VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((n + 63) / 64)), dim3(64), sp, vectors, (uint32_t)n, (uint32_t)dim, ml.nperm, states, levels);
+  uint64_t off = 0;
+  for (uint64_t lv = lp; lv > 1; off += lv, lv /= 2)
+    VDB_LAUNCH(k_mk_level_values, dim3((unsigned)((lv / 2 + 63) / 64)), dim3(64), sp, levels + off, (uint32_t)(lv / 2), levels + off + lv);
+  *root_off = off;
+  return VDB_OK;
+}
+int wit_merkle_dev(const u256* vectors, size_t n, size_t dim, int zero_cached, Streams st, u256* root_out) {
+  VDB_ARG(n <= ((size_t)1 << 30), "tree deeper than 30 levels");
   FpEntry* fp;
   TRY(get_fp(48, 13, &fp));  // only GateChip primitives are used: P and L are irrelevant
   TRY(set_winv(st, fp->dev));
@@ -1681,98 +1578,32 @@ int wit_merkle_dev(const u256* vectors, size_t n, size_t dim, int zero_cached, S
   TRY(poseidon_spec_dev(&sp, nullptr));
   MkLayout ml;
   mk_layout(n, dim, zero_cached, &ml);
-  hipStream_t s = ctx().stream;
-  size_t need = (n * ml.nperm * PSD_T + 2 * ml.n_leaves_pow2 + 8) * sizeof(u256);
-  u256* buf = (u256*)scratch_get(0, need);
-  if (!buf) return VDB_ERR_OOM;
-  u256* states = buf;
-  u256* lva = states + n * ml.nperm * PSD_T;
-  u256* lvb = lva + ml.n_leaves_pow2;
-  VDB_HIP(hipMemsetAsync(lva, 0, ml.n_leaves_pow2 * sizeof(u256), s));
-  {
-    VDB_PROF("k_mk_leaf_states");
-    hipLaunchKernelGGL(k_mk_leaf_states, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, sp, vectors, (uint32_t)n, (uint32_t)dim, ml.nperm, states, lva);
-  }
-  VDB_LAUNCH_CHECK();
-  {
-    VDB_PROF("k_mk_leaf_trace");
-    hipLaunchKernelGGL(k_mk_leaf_trace, dim3((unsigned)((n * ml.nperm + 63) / 64)), dim3(64), 0, s, st, fp->dev, sp, vectors, (uint32_t)n, (uint32_t)dim,
-                     ml.nperm, adv_off, ml.leaf_cells, states);
-  }
-  VDB_LAUNCH_CHECK();
-  uint64_t pos = adv_off + ml.leaves;
-  if (ml.zero_cell) {
-    {
-      VDB_PROF("k_push_cells");
-      hipLaunchKernelGGL(k_push_cells, dim3(1), dim3(1), 0, s, st, pos, u256_zero(), u256_zero(), 1u);
-    }
-    VDB_LAUNCH_CHECK();
-    pos += 1;
-  }
-  // the tree: every level's digests (lva holds the levels one after the other: lp + lp / 2 + ... + 1 < 2 lp entries = lva | lvb), then one
-  // launch that traces all lp - 1 nodes (VDB_MK_TREE=0: a launch per level, each thread tracing its node's two permutations)
-  static const bool tree_on = !(getenv("VDB_MK_TREE") && getenv("VDB_MK_TREE")[0] == '0');
   const uint64_t lp = ml.n_leaves_pow2;
-  if (tree_on && lp > 1 && lp <= (1u << 30)) {
-    uint64_t lv = lp, off = 0;
-    while (lv > 1) {
-      const uint64_t no = lv / 2;
-      {
-        VDB_PROF("k_mk_level_values");
-        hipLaunchKernelGGL(k_mk_level_values, dim3((unsigned)((no + 63) / 64)), dim3(64), 0, s, sp, lva + off, (uint32_t)no, lva + off + lv);
-      }
-      VDB_LAUNCH_CHECK();
-      off += lv;
-      lv = no;
-    }
-    {
-      VDB_PROF("k_mk_tree_trace");
-      hipLaunchKernelGGL(k_mk_tree_trace, dim3((unsigned)((2 * (lp - 1) + 63) / 64)), dim3(64), 0, s, st, fp->dev, sp, lva, (uint32_t)lp, pos);
-    }
-    VDB_LAUNCH_CHECK();
-    VDB_HIP(hipMemcpyAsync(root_out, lva + off, sizeof(u256), hipMemcpyDeviceToDevice, s));
-    return VDB_OK;
-  }
-  uint64_t lv = ml.n_leaves_pow2;
-  while (lv > 1) {
-    uint64_t no = lv / 2;
-    {
-      VDB_PROF("k_mk_node");
-      hipLaunchKernelGGL(k_mk_node, dim3((unsigned)((no + 63) / 64)), dim3(64), 0, s, st, fp->dev, sp, lva, (uint32_t)no, pos, lvb);
-    }
-    VDB_LAUNCH_CHECK();
-    pos += no * (uint64_t)(perm_cells(2) + perm_cells(0));
-    std::swap(lva, lvb);
-    lv = no;
-  }
-  VDB_HIP(hipMemcpyAsync(root_out, lva, sizeof(u256), hipMemcpyDeviceToDevice, s));
+  u256* states = (u256*)scratch_get(0, (n * ml.nperm * PSD_T + 2 * lp + 8) * sizeof(u256));
+  if (!states) return VDB_ERR_OOM;
+  u256* levels = states + n * ml.nperm * PSD_T;
+  uint64_t root_off;
+  TRY(mk_tree_values(sp, vectors, n, dim, ml, states, levels, &root_off));
+  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((n * ml.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, vectors, (uint32_t)n, (uint32_t)dim, ml.nperm, 0,
+             ml.leaf_cells, states);
+  if (ml.zero_cell) VDB_LAUNCH(k_push_cells, dim3(1), dim3(1), st, ml.leaves, u256_zero(), u256_zero(), 1u);
+  // every node's two permutations in one launch (a tree of one leaf has no node: its root is the leaf digest)
+  if (lp > 1)
+    VDB_LAUNCH(k_mk_tree_trace, dim3((unsigned)((2 * (lp - 1) + 63) / 64)), dim3(64), st, fp->dev, sp, levels, (uint32_t)lp, ml.leaves + ml.zero_cell);
+  VDB_HIP(hipMemcpyAsync(root_out, levels + root_off, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
   return VDB_OK;
 }
 
-// the digests of every level of merkle_commitment's tree, values only, in k_mk_tree_trace's layout (2 lp entries, the last unused)
+// the resident tree of the path updates: mk_tree_values into the caller's buffer
 int merkle_tree_build_dev(const u256* vectors, size_t n, size_t dim, u256* levels) {
   const PoseidonSpec* sp;
   TRY(poseidon_spec_dev(&sp, nullptr));
   MkLayout ml;
   mk_layout(n, dim, 0, &ml);
-  hipStream_t s = ctx().stream;
   u256* states = (u256*)scratch_get(0, (n * ml.nperm * PSD_T + 8) * sizeof(u256));
   if (!states) return VDB_ERR_OOM;
-  const uint64_t lp = ml.n_leaves_pow2;
-  VDB_HIP(hipMemsetAsync(levels, 0, 2 * lp * sizeof(u256), s));
-  {
-    VDB_PROF("k_mk_leaf_states");
-    hipLaunchKernelGGL(k_mk_leaf_states, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, sp, vectors, (uint32_t)n, (uint32_t)dim, ml.nperm, states, levels);
-  }
-  VDB_LAUNCH_CHECK();
-  for (uint64_t lv = lp, off = 0; lv > 1; off += lv, lv /= 2) {
-    {
-      VDB_PROF("k_mk_level_values");
-      hipLaunchKernelGGL(k_mk_level_values, dim3((unsigned)((lv / 2 + 63) / 64)), dim3(64), 0, s, sp, levels + off, (uint32_t)(lv / 2), levels + off + lv);
-    }
-    VDB_LAUNCH_CHECK();
-  }
-  return VDB_OK;
+  uint64_t root_off;
+  return mk_tree_values(sp, vectors, n, dim, ml, states, levels, &root_off);
 }
 
 // sizes of a batch of m path updates in a tree over n vectors; the limits of one call (include/vdb.h)
@@ -1802,8 +1633,7 @@ static int mku_layout(size_t n, size_t dim, size_t m, MkuLayout* o, uint64_t* lp
   if (lp_out) *lp_out = lp;
   return VDB_OK;
 }
-int wit_merkle_update_dev(u256* levels, size_t n, size_t dim, const u256* new_vectors, const uint64_t* indices, size_t m, Streams st, uint64_t adv_off,
-                          u256* pub) {
+int wit_merkle_update_dev(u256* levels, size_t n, size_t dim, const u256* new_vectors, const uint64_t* indices, size_t m, Streams st, u256* pub) {
   MkuLayout ml;
   uint64_t lp;
   TRY(mku_layout(n, dim, m, &ml, &lp));
@@ -1835,50 +1665,16 @@ int wit_merkle_update_dev(u256* levels, size_t n, size_t dim, const u256* new_ve
   uint8_t* last = (uint8_t*)(didx + m);
   VDB_HIP(hipMemcpyAsync(didx, hidx.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
   const uint32_t mu = (uint32_t)m;
-  {
-    VDB_PROF("k_mku_touchers");
-    hipLaunchKernelGGL(k_mku_touchers, dim3((unsigned)((m * depth + 255) / 256)), dim3(256), 0, s, didx, mu, depth, sib_from, prev_same, last);
-  }
-  VDB_LAUNCH_CHECK();
-  {
-    VDB_PROF("k_mk_leaf_states");
-    hipLaunchKernelGGL(k_mk_leaf_states, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s, sp, new_vectors, mu, (uint32_t)dim, ml.nperm, states, path_new);
-  }
-  VDB_LAUNCH_CHECK();
-  for (uint32_t l = 0; l < depth; l++) {
-    {
-      VDB_PROF("k_mku_level");
-      hipLaunchKernelGGL(k_mku_level, dim3((unsigned)((2 * m + 63) / 64)), dim3(64), 0, s, sp, levels, lp, didx, mu, depth, l, sib_from, prev_same, wit, path_old,
-                         path_new);
-    }
-    VDB_LAUNCH_CHECK();
-  }
-  {
-    VDB_PROF("k_mku_writeback");
-    hipLaunchKernelGGL(k_mku_writeback, dim3((unsigned)((n_path + 63) / 64)), dim3(64), 0, s, levels, lp, didx, mu, depth, last, path_new);
-  }
-  VDB_LAUNCH_CHECK();
-  {
-    VDB_PROF("k_mku_inputs");
-    hipLaunchKernelGGL(k_mku_inputs, dim3((unsigned)((ml.n_in + 255) / 256)), dim3(256), 0, s, st, adv_off, new_vectors, wit, ml.n_vec, ml.n_in);
-  }
-  VDB_LAUNCH_CHECK();
-  {
-    VDB_PROF("k_mk_leaf_trace");
-    hipLaunchKernelGGL(k_mk_leaf_trace, dim3((unsigned)((m * ml.nperm + 63) / 64)), dim3(64), 0, s, st, fp->dev, sp, new_vectors, mu, (uint32_t)dim, ml.nperm,
-                       adv_off + ml.n_in, ml.per_update, states);
-  }
-  VDB_LAUNCH_CHECK();
-  {
-    VDB_PROF("k_mku_level_trace");
-    hipLaunchKernelGGL(k_mku_level_trace, dim3((unsigned)((m * depth + 63) / 64), 5), dim3(64), 0, s, st, fp->dev, sp, ml, adv_off, didx, wit, path_old, path_new);
-  }
-  VDB_LAUNCH_CHECK();
-  {
-    VDB_PROF("k_mku_index");
-    hipLaunchKernelGGL(k_mku_index, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s, st, fp->dev, ml, adv_off, wit, path_old, path_new, pub);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_mku_touchers, dim3((unsigned)((m * depth + 255) / 256)), dim3(256), didx, mu, depth, sib_from, prev_same, last);
+  VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((m + 63) / 64)), dim3(64), sp, new_vectors, mu, (uint32_t)dim, ml.nperm, states, path_new);
+  for (uint32_t l = 0; l < depth; l++)
+    VDB_LAUNCH(k_mku_level, dim3((unsigned)((2 * m + 63) / 64)), dim3(64), sp, levels, lp, didx, mu, depth, l, sib_from, prev_same, wit, path_old, path_new);
+  VDB_LAUNCH(k_mku_writeback, dim3((unsigned)((n_path + 63) / 64)), dim3(64), levels, lp, didx, mu, depth, last, path_new);
+  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)((ml.n_in + 255) / 256)), dim3(256), st, 0, new_vectors, wit, ml.n_vec, ml.n_in);
+  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((m * ml.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, new_vectors, mu, (uint32_t)dim, ml.nperm,
+             ml.n_in, ml.per_update, states);
+  VDB_LAUNCH(k_mku_level_trace, dim3((unsigned)((m * depth + 63) / 64), 5), dim3(64), st, fp->dev, sp, ml, 0, didx, wit, path_old, path_new);
+  VDB_LAUNCH(k_mku_index, dim3((unsigned)((m + 63) / 64)), dim3(64), st, fp->dev, ml, 0, wit, path_old, path_new, pub);
   return VDB_OK;
 }
 
@@ -1948,6 +1744,23 @@ struct HostStreams {
     return check_err_flag(st.err);
   }
 };
+// the streams of a *_dev entry point: the caller's device buffers under the current rank window (vdb_wit_set_window)
+struct DevStreams {
+  Streams st;
+  // with the error word (distance, fp_op, nearest, kmeans)
+  int init(vdb_fr* stream_dev, uint8_t* selector_dev, vdb_fr* lookup_dev) {
+    int* derr = (int*)scratch_get(1, 64);
+    if (!derr) return VDB_ERR_OOM;
+    VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
+    st = Streams{as_u256(stream_dev), selector_dev, as_u256(lookup_dev), derr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], g_win[2], g_win[3]};
+    return VDB_OK;
+  }
+  // without error word and lookups (merkle, merkle_update: GateChip primitives only)
+  void init(vdb_fr* stream_dev, uint8_t* selector_dev) {
+    st = Streams{as_u256(stream_dev), selector_dev, nullptr, nullptr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], 0, ~0ull};
+  }
+  int finish() { return st.err ? check_err_flag(st.err) : VDB_OK; }
+};
 
 extern "C" {
 
@@ -1994,7 +1807,7 @@ int vdb_wit_distance(int metric, uint32_t P, uint32_t L, const vdb_fr* a, const 
   TRY(upload(db, b, n_pairs * dim * sizeof(u256)));
   TRY(dres.alloc(n_pairs * sizeof(u256)));
   TRY(hs.init(cells, lookups, selector_out != nullptr));
-  TRY(wit_distance_dev(fp, metric, da.as<u256>(), db.as<u256>(), n_pairs, dim, hs.st, 0, 0, dres.as<u256>()));
+  TRY(wit_distance_dev(fp, metric, da.as<u256>(), db.as<u256>(), n_pairs, dim, hs.st, dres.as<u256>()));
   TRY(download(result_out, dres.p, n_pairs * sizeof(u256)));
   return hs.finish(stream_out, lookup_out, selector_out, cells, lookups);
 }
@@ -2005,12 +1818,10 @@ int vdb_wit_distance_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* a_dev
   VDB_ARG(a_dev && b_dev && stream_dev && lookup_dev && result_dev && n_pairs > 0 && dim > 0, "null pointer or empty input");
   FpEntry* fp;
   TRY(get_fp(P, L, &fp));
-  int* derr = (int*)scratch_get(1, 64);
-  if (!derr) return VDB_ERR_OOM;
-  VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
-  Streams st{as_u256(stream_dev), selector_dev, as_u256(lookup_dev), derr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], g_win[2], g_win[3]};
-  TRY(wit_distance_dev(fp, metric, as_u256(a_dev), as_u256(b_dev), n_pairs, dim, st, 0, 0, as_u256(result_dev)));
-  return check_err_flag(derr);
+  DevStreams ds;
+  TRY(ds.init(stream_dev, selector_dev, lookup_dev));
+  TRY(wit_distance_dev(fp, metric, as_u256(a_dev), as_u256(b_dev), n_pairs, dim, ds.st, as_u256(result_dev)));
+  return ds.finish();
 }
 
 int vdb_wit_fp_op_size(int op, uint32_t P, uint32_t L, size_t n, uint64_t* cells, uint64_t* lookups) {
@@ -2040,7 +1851,7 @@ int vdb_wit_fp_op(int op, uint32_t P, uint32_t L, const vdb_fr* a, const vdb_fr*
   if (b) TRY(upload(db, b, n * sizeof(u256)));
   TRY(dres.alloc(n * sizeof(u256)));
   TRY(hs.init(cells, lookups, selector_out != nullptr));
-  TRY(wit_fp_op_dev(fp, op, da.as<u256>(), b ? db.as<u256>() : nullptr, n, hs.st, 0, 0, dres.as<u256>()));
+  TRY(wit_fp_op_dev(fp, op, da.as<u256>(), b ? db.as<u256>() : nullptr, n, hs.st, dres.as<u256>()));
   TRY(download(result_out, dres.p, n * sizeof(u256)));
   return hs.finish(stream_out, lookup_out, selector_out, cells, lookups);
 }
@@ -2051,12 +1862,10 @@ int vdb_wit_fp_op_dev(int op, uint32_t P, uint32_t L, const vdb_fr* a_dev, const
   VDB_ARG(a_dev && stream_dev && lookup_dev && result_dev && n > 0 && n <= 0xffffffffull, "null pointer or empty input");
   FpEntry* fp;
   TRY(get_fp(P, L, &fp));
-  int* derr = (int*)scratch_get(1, 64);
-  if (!derr) return VDB_ERR_OOM;
-  VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
-  Streams st{as_u256(stream_dev), selector_dev, as_u256(lookup_dev), derr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], g_win[2], g_win[3]};
-  TRY(wit_fp_op_dev(fp, op, as_u256(a_dev), as_u256(b_dev), n, st, 0, 0, as_u256(result_dev)));
-  return check_err_flag(derr);
+  DevStreams ds;
+  TRY(ds.init(stream_dev, selector_dev, lookup_dev));
+  TRY(wit_fp_op_dev(fp, op, as_u256(a_dev), as_u256(b_dev), n, ds.st, as_u256(result_dev)));
+  return ds.finish();
 }
 
 // the topk nearest vectors of every one of n_queries queries (include/vdb.h): nearest_vector's distances, then its closing stages once per
@@ -2090,7 +1899,7 @@ int vdb_wit_nearest_topk(int metric, uint32_t P, uint32_t L, const vdb_fr* queri
   TRY(dind.alloc(n_queries * topk * n * sizeof(u256)));
   TRY(dres.alloc(n_queries * topk * dim * sizeof(u256)));
   TRY(hs.init(cells, lookups, selector_out != nullptr));
-  TRY(wit_nearest_dev(fp, metric, dq.as<u256>(), dv.as<u256>(), n_queries, n, dim, topk, hs.st, 0, 0, dind.as<u256>(), dres.as<u256>()));
+  TRY(wit_nearest_dev(fp, metric, dq.as<u256>(), dv.as<u256>(), n_queries, n, dim, topk, hs.st, dind.as<u256>(), dres.as<u256>()));
   TRY(download(indicators_out, dind.p, n_queries * topk * n * sizeof(u256)));
   TRY(download(results_out, dres.p, n_queries * topk * dim * sizeof(u256)));
   return hs.finish(stream_out, lookup_out, selector_out, cells, lookups);
@@ -2104,15 +1913,13 @@ int vdb_wit_nearest_topk_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* q
   VDB_ARG(topk > 0 && topk <= n, "topk must be at least 1 and at most n");
   FpEntry* fp;
   TRY(get_fp(P, L, &fp));
-  int* derr = (int*)scratch_get(1, 64);
-  if (!derr) return VDB_ERR_OOM;
-  VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
   // the rank window (vdb_wit_set_window): a rank stores the cells of its own columns — the distances, N-way parallel and nearly all of
   // the cells, exit early outside it — while every rank computes every value (the distances, the short minimum chains)
-  Streams st{as_u256(stream_dev), selector_dev, as_u256(lookup_dev), derr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], g_win[2], g_win[3]};
-  TRY(wit_nearest_dev(fp, metric, as_u256(queries_dev), as_u256(vectors_dev), n_queries, n, dim, topk, st, 0, 0, as_u256(indicators_dev),
+  DevStreams ds;
+  TRY(ds.init(stream_dev, selector_dev, lookup_dev));
+  TRY(wit_nearest_dev(fp, metric, as_u256(queries_dev), as_u256(vectors_dev), n_queries, n, dim, topk, ds.st, as_u256(indicators_dev),
                       as_u256(results_dev)));
-  return check_err_flag(derr);
+  return ds.finish();
 }
 
 // nearest_vector (vectordb.rs:122-163) for n_queries queries over one database, the calls end to end in the streams
@@ -2174,12 +1981,10 @@ int vdb_wit_kmeans_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* vectors
   TRY(vdb_wit_kmeans_size(metric, P, L, n, dim, K, I, zero_cached, &cells, &lookups));
   FpEntry* fp;
   TRY(get_fp(P, L, &fp));
-  int* derr = (int*)scratch_get(1, 64);
-  if (!derr) return VDB_ERR_OOM;
-  VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
-  Streams st{as_u256(stream_dev), selector_dev, as_u256(lookup_dev), derr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], g_win[2], g_win[3]};
-  TRY(wit_kmeans_dev(fp, metric, as_u256(vectors_dev), n, dim, K, I, zero_cached, st, 0, 0, as_u256(centroids_dev), as_u256(indicators_dev)));
-  return check_err_flag(derr);
+  DevStreams ds;
+  TRY(ds.init(stream_dev, selector_dev, lookup_dev));
+  TRY(wit_kmeans_dev(fp, metric, as_u256(vectors_dev), n, dim, K, I, zero_cached, ds.st, as_u256(centroids_dev), as_u256(indicators_dev)));
+  return ds.finish();
 }
 int vdb_wit_kmeans(int metric, uint32_t P, uint32_t L, const vdb_fr* vectors, size_t n, size_t dim, size_t K, size_t I, int zero_cached,
                    vdb_fr* stream_out, vdb_fr* lookup_out, uint8_t* selector_out, vdb_fr* centroids_out, vdb_fr* indicators_out) {
@@ -2195,7 +2000,7 @@ int vdb_wit_kmeans(int metric, uint32_t P, uint32_t L, const vdb_fr* vectors, si
   TRY(dc.alloc(K * dim * sizeof(u256)));
   TRY(di.alloc(n * K * sizeof(u256)));
   TRY(hs.init(cells, lookups, selector_out != nullptr));
-  TRY(wit_kmeans_dev(fp, metric, dv.as<u256>(), n, dim, K, I, zero_cached, hs.st, 0, 0, dc.as<u256>(), di.as<u256>()));
+  TRY(wit_kmeans_dev(fp, metric, dv.as<u256>(), n, dim, K, I, zero_cached, hs.st, dc.as<u256>(), di.as<u256>()));
   TRY(download(centroids_out, dc.p, K * dim * sizeof(u256)));
   TRY(download(indicators_out, di.p, n * K * sizeof(u256)));
   return hs.finish(stream_out, lookup_out, selector_out, cells, lookups);
@@ -2211,8 +2016,10 @@ int vdb_wit_merkle_size(size_t n, size_t dim, int zero_cached, uint64_t* cells) 
 int vdb_wit_merkle_dev(const vdb_fr* vectors_dev, size_t n, size_t dim, int zero_cached, vdb_fr* stream_dev, uint8_t* selector_dev, vdb_fr* root_dev) {
   VDB_REQUIRE_INIT();
   VDB_ARG(vectors_dev && stream_dev && root_dev && n > 0, "null pointer");
-  Streams st{as_u256(stream_dev), selector_dev, nullptr, nullptr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], 0, ~0ull};
-  return wit_merkle_dev(as_u256(vectors_dev), n, dim, zero_cached, st, 0, as_u256(root_dev));
+  DevStreams ds;
+  ds.init(stream_dev, selector_dev);
+  TRY(wit_merkle_dev(as_u256(vectors_dev), n, dim, zero_cached, ds.st, as_u256(root_dev)));
+  return ds.finish();
 }
 int vdb_wit_merkle(const vdb_fr* vectors, size_t n, size_t dim, int zero_cached, vdb_fr* stream_out, uint8_t* selector_out, vdb_fr* root_out) {
   VDB_REQUIRE_INIT();
@@ -2224,7 +2031,7 @@ int vdb_wit_merkle(const vdb_fr* vectors, size_t n, size_t dim, int zero_cached,
   TRY(upload(dv, vectors, n * dim * sizeof(u256)));
   TRY(droot.alloc(sizeof(u256)));
   TRY(hs.init(cells, 0, selector_out != nullptr));
-  TRY(wit_merkle_dev(dv.as<u256>(), n, dim, zero_cached, hs.st, 0, droot.as<u256>()));
+  TRY(wit_merkle_dev(dv.as<u256>(), n, dim, zero_cached, hs.st, droot.as<u256>()));
   TRY(download(root_out, droot.p, sizeof(u256)));
   return hs.finish(stream_out, nullptr, selector_out, cells, 0);
 }
@@ -2247,8 +2054,10 @@ int vdb_wit_merkle_update_dev(vdb_fr* levels_dev, size_t n, size_t dim, const vd
                               uint8_t* selector_dev, vdb_fr* public_dev) {
   VDB_REQUIRE_INIT();
   VDB_ARG(levels_dev && new_vectors_dev && indices && stream_dev && public_dev, "null pointer");
-  Streams st{as_u256(stream_dev), selector_dev, nullptr, nullptr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], 0, ~0ull};
-  return wit_merkle_update_dev(as_u256(levels_dev), n, dim, as_u256(new_vectors_dev), indices, m, st, 0, as_u256(public_dev));
+  DevStreams ds;
+  ds.init(stream_dev, selector_dev);
+  TRY(wit_merkle_update_dev(as_u256(levels_dev), n, dim, as_u256(new_vectors_dev), indices, m, ds.st, as_u256(public_dev)));
+  return ds.finish();
 }
 int vdb_wit_merkle_update(vdb_fr* levels, size_t n, size_t dim, const vdb_fr* new_vectors, const uint64_t* indices, size_t m, vdb_fr* stream_out,
                           uint8_t* selector_out, vdb_fr* public_out) {
@@ -2264,7 +2073,7 @@ int vdb_wit_merkle_update(vdb_fr* levels, size_t n, size_t dim, const vdb_fr* ne
   TRY(upload(dv, new_vectors, m * dim * sizeof(u256)));
   TRY(dpub.alloc((3 * m + 2) * sizeof(u256)));
   TRY(hs.init(ml.total, 0, selector_out != nullptr));
-  TRY(wit_merkle_update_dev(dl.as<u256>(), n, dim, dv.as<u256>(), indices, m, hs.st, 0, dpub.as<u256>()));
+  TRY(wit_merkle_update_dev(dl.as<u256>(), n, dim, dv.as<u256>(), indices, m, hs.st, dpub.as<u256>()));
   TRY(download(public_out, dpub.p, (3 * m + 2) * sizeof(u256)));
   TRY(download(levels, dl.p, 2 * lp * sizeof(u256)));
   return hs.finish(stream_out, nullptr, selector_out, ml.total, 0);
@@ -2279,11 +2088,7 @@ int vdb_layout_plan_dev(const uint8_t* selector_dev, uint64_t n_cells, uint32_t 
   uint64_t est = n_cells / (max_rows - 3) + 2;
   uint64_t* d = (uint64_t*)scratch_get(1, (est + 1) * sizeof(uint64_t));
   if (!d) return VDB_ERR_OOM;
-  {
-    VDB_PROF("k_layout_plan");
-    hipLaunchKernelGGL(k_layout_plan, dim3(1), dim3(1), 0, ctx().stream, selector_dev, n_cells, max_rows, d + 1, est, d);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_layout_plan, dim3(1), dim3(1), selector_dev, n_cells, max_rows, d + 1, est, d);
   uint64_t nbp = 0;
   VDB_HIP(hipMemcpyAsync(&nbp, d, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx().stream));
   VDB_HIP(hipStreamSynchronize(ctx().stream));
@@ -2321,12 +2126,8 @@ int vdb_layout_columns_range_dev(const vdb_fr* stream_dev, uint64_t n_cells, con
   uint64_t *dbp, *dst;
   TRY(upload_break_points(break_points, n_bp, &dbp, &dst));
   uint64_t total = (col_hi - col_lo) * rows;
-  {
-    VDB_PROF("k_layout_columns");
-    hipLaunchKernelGGL(k_layout_columns, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx().stream, as_u256(stream_dev), n_cells, dst, dbp, n_bp, k,
-                     as_u256(cols_dev), blind_dev ? as_u256(blind_dev) : nullptr, n_blind, col_lo, col_hi);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_layout_columns, dim3((unsigned)((total + 255) / 256)), dim3(256), as_u256(stream_dev), n_cells, dst, dbp, n_bp, k, as_u256(cols_dev),
+             blind_dev ? as_u256(blind_dev) : nullptr, n_blind, col_lo, col_hi);
   VDB_HIP(hipStreamSynchronize(ctx().stream));  // break_points is a host buffer the caller may free
   return VDB_OK;
 }
@@ -2381,12 +2182,8 @@ int vdb_layout_lookup_range_dev(const vdb_fr* lookup_dev, uint64_t n_cells, uint
   const uint64_t n_cols = col_hi - col_lo;
   if (n_cols == 0) return VDB_OK;
   uint64_t total = n_cols << k;
-  {
-    VDB_PROF("k_layout_lookup");
-    hipLaunchKernelGGL(k_layout_lookup, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx().stream, as_u256(lookup_dev), n_cells, max_rows, k, n_cols,
-                     as_u256(cols_dev), blind_dev ? as_u256(blind_dev) : nullptr, n_blind, col_lo);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_layout_lookup, dim3((unsigned)((total + 255) / 256)), dim3(256), as_u256(lookup_dev), n_cells, max_rows, k, n_cols, as_u256(cols_dev),
+             blind_dev ? as_u256(blind_dev) : nullptr, n_blind, col_lo);
   return VDB_OK;
 }
 int vdb_layout_const_mask_dev(const uint8_t* flags_dev, uint64_t n_cells, const uint64_t* break_points, uint64_t n_bp, uint32_t k, uint8_t* mask_dev) {
@@ -2396,11 +2193,7 @@ int vdb_layout_const_mask_dev(const uint8_t* flags_dev, uint64_t n_cells, const 
   uint64_t *dbp, *dst;
   TRY(upload_break_points(break_points, n_bp, &dbp, &dst));
   uint64_t total = (n_bp + 1) * rows;
-  {
-    VDB_PROF("k_layout_const_mask");
-    hipLaunchKernelGGL(k_layout_const_mask, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx().stream, flags_dev, n_cells, dst, dbp, n_bp, k, mask_dev);
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_layout_const_mask, dim3((unsigned)((total + 255) / 256)), dim3(256), flags_dev, n_cells, dst, dbp, n_bp, k, mask_dev);
   VDB_HIP(hipStreamSynchronize(ctx().stream));
   return VDB_OK;
 }
@@ -2411,12 +2204,7 @@ int vdb_layout_selectors_dev(const uint8_t* flags_dev, uint64_t n_cells, const u
   uint64_t *dbp, *dst;
   TRY(upload_break_points(break_points, n_bp, &dbp, &dst));
   uint64_t total = (n_bp + 1) * rows;
-  {
-    VDB_PROF("k_layout_selectors");
-    hipLaunchKernelGGL(k_layout_selectors, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx().stream, flags_dev, n_cells, dst, dbp, n_bp, k,
-                     as_u256(q_dev));
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_layout_selectors, dim3((unsigned)((total + 255) / 256)), dim3(256), flags_dev, n_cells, dst, dbp, n_bp, k, as_u256(q_dev));
   VDB_HIP(hipStreamSynchronize(ctx().stream));
   return VDB_OK;
 }
@@ -2424,11 +2212,7 @@ int vdb_mask_select_dev(const vdb_fr* in_dev, const uint8_t* mask_dev, uint64_t 
   VDB_REQUIRE_INIT();
   VDB_ARG(in_dev && mask_dev && out_dev, "null pointer");
   if (n == 0) return VDB_OK;
-  {
-    VDB_PROF("k_mask_select");
-    hipLaunchKernelGGL(k_mask_select, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx().stream, as_u256(in_dev), mask_dev, n, keep_const, as_u256(out_dev));
-  }
-  VDB_LAUNCH_CHECK();
+  VDB_LAUNCH(k_mask_select, dim3((unsigned)((n + 255) / 256)), dim3(256), as_u256(in_dev), mask_dev, n, keep_const, as_u256(out_dev));
   return VDB_OK;
 }
 int vdb_layout_columns(const vdb_fr* stream, uint64_t n_cells, const uint64_t* break_points, uint64_t n_bp, const vdb_fr* lookup, uint64_t n_lookup,

@@ -229,7 +229,8 @@ int vdb_wit_set_window(uint64_t adv_lo, uint64_t adv_hi, uint64_t lookup_lo, uin
 int vdb_wit_kmeans_dev(int metric, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *vectors_dev, size_t n, size_t dim, size_t K, size_t I,
                        int zero_cached, vdb_fr *stream_dev, vdb_fr *lookup_dev, uint8_t *selector_dev, vdb_fr *centroids_dev, vdb_fr *indicators_dev);
 /* VectorDBChip::merkle_commitment with PoseidonChip<F,3,2>(R_F=8, R_P=57) (src/gadget/vectordb.rs:165-223):
- * the permutation trace cells; no lookups */
+ * the permutation trace cells; no lookups.  n at most 2^30 (a tree of at most 30 levels), like vdb_merkle_tree_build_dev:
+ * VDB_ERR_ARG above */
 int vdb_wit_merkle_size(size_t n, size_t dim, int zero_cached, uint64_t *cells);
 int vdb_wit_merkle(const vdb_fr *vectors, size_t n, size_t dim, int zero_cached, vdb_fr *stream_out, uint8_t *selector_out, vdb_fr *root_out);
 int vdb_wit_merkle_dev(const vdb_fr *vectors_dev, size_t n, size_t dim, int zero_cached, vdb_fr *stream_dev, uint8_t *selector_dev, vdb_fr *root_dev);

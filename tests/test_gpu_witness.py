@@ -1,5 +1,7 @@
 """GPU parity of the witness-stream generators (C ABI vdb_wit_*, vdb_layout_*) against the CPU oracle:
 advice stream, lookup stream, gate-start bits and results must be bit-identical on the same inputs."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -134,6 +136,48 @@ def test_merkle_trace(api, O, n, dim):
     assert np.array_equal(got["root"], root)
     assert np.array_equal(got["root"], api.poseidon_merkle_root(v))
     assert_streams(got, c)
+
+
+@pytest.mark.parametrize("n,dim", [(5, 3), (2, 4)])
+def test_merkle_trace_windowed(api, O, n, dim):
+    """vdb_wit_merkle_dev under a rank window (api.wit_window): two runs that store [0, cut) and [cut, cells) into zero-filled
+    buffers give the full stream between them and the root each, for a cut inside the leaf section, at the zero cell (5 vectors: 8
+    padded leaves; 2 vectors have none) and inside the padding-only permutation of the last node.  dim 3 ends a leaf on a one-input
+    permutation, dim 4 on a padding-only one."""
+    lib = api._lib.init()
+    perm = {2: 2238 + 18, 1: 2238 + 15, 0: 2238 + 12}   # cells of a permutation that absorbs 2, 1, 0 inputs
+    v = O.quantize(np.random.default_rng(950 + n).random((n, dim)), 32)
+    c = O.Ctx(store=True, keygen=True)
+    root = c.merkle_commitment(v)
+    want = c.advice()
+    cells = want.shape[0]
+    lp, _ = api.merkle_levels(n)
+    leaves = n * sum(perm[min(2, max(0, dim - 2 * p))] for p in range(dim // 2 + 1))
+    assert cells == leaves + (lp > n) + (lp - 1) * (perm[2] + perm[0])
+    d_vec, d_stream, d_root = api.DeviceBuffer(v.nbytes), api.DeviceBuffer(cells * 32), api.DeviceBuffer(32)
+    d_vec.upload(v)
+
+    def run():
+        d_stream.upload(np.zeros((cells, 4), dtype=np.uint64))
+        d_root.upload(np.zeros(4, dtype=np.uint64))
+        api.check(lib.vdb_wit_merkle_dev(d_vec.ptr, ctypes.c_size_t(n), ctypes.c_size_t(dim), 0, d_stream.ptr, None, d_root.ptr))
+        return d_stream.download((cells, 4)), d_root.download(4)
+
+    try:
+        full, full_root = run()
+        cuts = [leaves // n + perm[2] // 2] + ([leaves] if lp > n else []) + [cells - perm[0] // 2]
+        for cut in cuts:
+            with api.wit_window((0, cut), (0, 2**64 - 1)):
+                first, root_first = run()
+            with api.wit_window((cut, cells), (0, 2**64 - 1)):
+                second, root_second = run()
+            assert np.array_equal(root_first, root) and np.array_equal(root_second, root), cut
+            assert np.concatenate([first[:cut], second[cut:]]).tobytes() == full.tobytes(), cut
+    finally:
+        for d in (d_vec, d_stream, d_root):
+            d.free()
+    assert np.array_equal(full_root, root)
+    assert full.tobytes() == want.tobytes()
 
 
 def test_layout_plan_and_columns(api, O):
