@@ -451,6 +451,30 @@ def wit_merkle_update(levels, n, new_vectors, indices, selectors=False):
     return dict(stream=stream, **_split_flags(sel), input_cells=n_in.value, public=pub, levels=levels)
 
 
+def wit_merkle_open(levels, n, indices, vectors=None, selectors=False):
+    """m openings (vdb_wit_merkle_open) of the tree `levels` (merkle_tree_build's array over n vectors, or what a batch of updates left):
+    slot indices[j] is read.  `vectors` (m, dim, 4): the vectors read (vector mode); None: leaf mode, any slot of the padded tree.
+    dict(stream, selectors, input_cells, public: [root | idx, leaf per read | in vector mode the vectors word by word])"""
+    lib = _lib.init()
+    levels = np.ascontiguousarray(levels, dtype=np.uint64)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64)
+    m = idx.shape[0]
+    assert idx.shape == (m,) and levels.shape == (2 * merkle_levels(n)[0], 4)
+    dim = 1                                                   # leaf mode reads no vector: the word count only has to be a valid one
+    if vectors is not None:
+        vectors = _fr(vectors)
+        assert vectors.shape[0] == m
+        dim = vectors.shape[1]
+    cells, n_in = _u64(), _u64()
+    check(lib.vdb_wit_merkle_open_size(_sz(n), _sz(dim), _sz(m), int(vectors is not None), ctypes.byref(cells), ctypes.byref(n_in)))
+    stream = np.zeros((cells.value, 4), dtype=np.uint64)
+    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
+    pub = np.zeros((1 + 2 * m + (m * dim if vectors is not None else 0), 4), dtype=np.uint64)
+    check(lib.vdb_wit_merkle_open(_p(levels), _sz(n), _sz(dim), _p(vectors) if vectors is not None else None, _p(idx), _sz(m), _p(stream),
+                                  _p(sel) if selectors else None, _p(pub)))
+    return dict(stream=stream, **_split_flags(sel), input_cells=n_in.value, public=pub)
+
+
 def layout_plan(selectors, k, minimum_rows=9):
     lib = _lib.init()
     selectors = np.ascontiguousarray(selectors, dtype=np.uint8)

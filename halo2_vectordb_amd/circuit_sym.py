@@ -999,101 +999,123 @@ def merkle_update_instances(m, top_old0, idx, old_leaf, new_leaf, top_new_last):
     return out + [int(top_new_last)]
 
 
+class _CellTrace:
+    """the cell-by-cell tracer of the Merkle path circuits (trace_merkle_update, trace_merkle_open): the GateChip templates they use,
+    written straight into copy_of / const_idx / gate.  fetch_flags / fetch_values: as trace_merkle_update."""
+
+    def __init__(self, total, fetch_flags, fetch_values):
+        self.total, self.fetch_flags, self.fetch_values = total, fetch_flags, fetch_values
+        self.copy_of, self.cidx, self.gate = list(range(total)), [-1] * total, [False] * total
+        self.consts, self.cmap, self.tmpl = [], {}, {}
+
+    def cid(self, v):
+        v %= R
+        if v not in self.cmap:
+            self.cmap[v] = len(self.consts)
+            self.consts.append(v)
+        return self.cmap[v]
+
+    def put(self, at, cells, gates):
+        """cells: ('c', earlier cell) | ('k', constant) | None (a new value)"""
+        for i, (x, g) in enumerate(zip(cells, gates)):
+            self.gate[at + i] = bool(g)
+            if x is None:
+                continue
+            if x[0] == "k":
+                self.cidx[at + i] = self.cid(x[1])
+            else:
+                self.copy_of[at + i] = x[1]
+        return at + len(cells)
+
+    def assert_bit(self, at, b):                             # [0, b, b, b]
+        return self.put(at, [("k", 0), ("c", b), ("c", b), ("c", b)], [1, 0, 0, 0])
+
+    def select(self, at, a, b, s):                           # [a - b, 1, b, a, b, sel, a - b, out]
+        self.put(at, [None, ("k", 1), ("c", b), ("c", a), ("c", b), ("c", s), ("c", at), None], [1, 0, 0, 0, 1, 0, 0, 0])
+        return at + 7
+
+    def perm(self, at, n_in, state, msgs):
+        if n_in not in self.tmpl:
+            size = perm_cells(n_in)
+            flags = np.asarray(self.fetch_flags(at, at + size), dtype=np.uint8)
+            self.tmpl[n_in] = (permutation_template(flags, n_in), flags, self.fetch_values(at, at + size))
+        (src, fin), flags, vals = self.tmpl[n_in]
+        for i, s in enumerate(src.tolist()):
+            p = at + i
+            self.gate[p] = bool(flags[i] & 1)
+            if flags[i] & 2:
+                self.cidx[p] = self.cid(int(vals[i]))
+            elif s >= 0:
+                self.copy_of[p] = at + s
+            elif s <= -20:
+                self.copy_of[p] = msgs[-20 - s]
+            elif s <= -10:
+                if state is None:                            # the chip's initial state: capacity 2^64, then zeros
+                    self.cidx[p] = self.cid((1 << 64) if s == -10 else 0)
+                else:
+                    self.copy_of[p] = state[-10 - s]
+        return [at + f for f in fin]
+
+    def node(self, at, left, right):
+        st = self.perm(at, 2, None, [left, right])
+        return self.perm(at + perm_cells(2), 0, st, [])[1]
+
+    def leaf(self, at, lay, word0):
+        """the sponge of one leaf over the assigned words word0, word0 + 1, ... -> (the squeeze cell, the first cell after it)"""
+        state = None
+        for p in range(lay["nperm"]):
+            state = self.perm(at, lay["n_ins"][p], state, [word0 + 2 * p + i for i in range(lay["n_ins"][p])])
+            at += lay["sizes"][p]
+        return state[1], at
+
+    def index(self, at, bits):
+        """inner_product(bits, Constant(2^l)): 2^0 = 1, the sum starts with b_0 itself -> (the sum's cell, the first cell after it)"""
+        depth = len(bits)
+        cells, gates = [("c", bits[0])], [depth > 1]
+        for l in range(1, depth):
+            cells += [("c", bits[l]), ("k", 1 << l), None]
+            gates += [0, 0, l + 1 < depth]
+        at = self.put(at, cells, gates)
+        return at - 1, at
+
+    def finish(self):
+        return CopyMap(np.asarray(self.copy_of, dtype=np.int64), np.asarray(self.cidx, dtype=np.int64), self.consts, np.zeros(self.total, dtype=bool),
+                       np.asarray(self.gate, dtype=bool), np.zeros(0, dtype=np.int64))
+
+
 def trace_merkle_update(m, dim, depth, fetch_flags, fetch_values):
     """The closure of a batch of m path updates cell by cell (the ground truth of build_merkle_update): assign the four witness groups,
     then per update the leaf sponge, the levels and the index, the top of the old path tied to the top of the update before.
     fetch_flags(lo, hi) / fetch_values(lo, hi): flag bytes / canonical values of stream cells of a keygen-style run (one instance of
     every kind of permutation is read: the Poseidon constants are fixed-column values).  -> (CopyMap, public cells)"""
     lay = merkle_update_layout(m, dim, depth)
-    total = lay["total"]
-    copy_of, cidx, gate = list(range(total)), [-1] * total, [False] * total
-    consts, cmap, tmpl = [], {}, {}
-
-    def cid(v):
-        v %= R
-        if v not in cmap:
-            cmap[v] = len(consts)
-            consts.append(v)
-        return cmap[v]
-
-    def put(at, cells, gates):
-        """cells: ('c', earlier cell) | ('k', constant) | None (a new value)"""
-        for i, (x, g) in enumerate(zip(cells, gates)):
-            gate[at + i] = bool(g)
-            if x is None:
-                continue
-            if x[0] == "k":
-                cidx[at + i] = cid(x[1])
-            else:
-                copy_of[at + i] = x[1]
-        return at + len(cells)
-
-    def select(at, a, b, s):                                 # [a - b, 1, b, a, b, sel, a - b, out]
-        put(at, [None, ("k", 1), ("c", b), ("c", a), ("c", b), ("c", s), ("c", at), None], [1, 0, 0, 0, 1, 0, 0, 0])
-        return at + 7
-
-    def perm(at, n_in, state, msgs):
-        if n_in not in tmpl:
-            size = perm_cells(n_in)
-            flags = np.asarray(fetch_flags(at, at + size), dtype=np.uint8)
-            tmpl[n_in] = (permutation_template(flags, n_in), flags, fetch_values(at, at + size))
-        (src, fin), flags, vals = tmpl[n_in]
-        for i, s in enumerate(src.tolist()):
-            p = at + i
-            gate[p] = bool(flags[i] & 1)
-            if flags[i] & 2:
-                cidx[p] = cid(int(vals[i]))
-            elif s >= 0:
-                copy_of[p] = at + s
-            elif s <= -20:
-                copy_of[p] = msgs[-20 - s]
-            elif s <= -10:
-                if state is None:                            # the chip's initial state: capacity 2^64, then zeros
-                    cidx[p] = cid((1 << 64) if s == -10 else 0)
-                else:
-                    copy_of[p] = state[-10 - s]
-        return [at + f for f in fin]
-
-    def node(at, left, right):
-        st = perm(at, 2, None, [left, right])
-        return perm(at + perm_cells(2), 0, st, [])[1]
-
+    t = _CellTrace(lay["total"], fetch_flags, fetch_values)
     idx_cells, new_leaves, prev_top, top_old0 = [], [], None, None
     for j in range(m):
-        at = lay["n_in"] + j * lay["per_update"]
-        state = None
-        for p in range(lay["nperm"]):
-            state = perm(at, lay["n_ins"][p], state, [j * dim + 2 * p + i for i in range(lay["n_ins"][p])])
-            at += lay["sizes"][p]
-        cur_old, cur_new = lay["old_leaf"] + j, state[1]
+        cur_new, at = t.leaf(lay["n_in"] + j * lay["per_update"], lay, j * dim)
+        cur_old = lay["old_leaf"] + j
         new_leaves.append(cur_new)
         bits = [lay["bits"] + j * depth + l for l in range(depth)]
         for l in range(depth):
             b, sib = bits[l], lay["sibs"] + j * depth + l
-            put(at, [("k", 0), ("c", b), ("c", b), ("c", b)], [1, 0, 0, 0])
-            lo = select(at + 4, sib, cur_old, b)
-            ro = select(at + 12, cur_old, sib, b)
-            cur_old = node(at + 20, lo, ro)
+            t.assert_bit(at, b)
+            lo = t.select(at + 4, sib, cur_old, b)
+            ro = t.select(at + 12, cur_old, sib, b)
+            cur_old = t.node(at + 20, lo, ro)
             at += 20 + lay["node_cells"]
-            ln = select(at, sib, cur_new, b)
-            rn = select(at + 8, cur_new, sib, b)
-            cur_new = node(at + 16, ln, rn)
+            ln = t.select(at, sib, cur_new, b)
+            rn = t.select(at + 8, cur_new, sib, b)
+            cur_new = t.node(at + 16, ln, rn)
             at += 16 + lay["node_cells"]
-        cells, gates = [("c", bits[0])], [depth > 1]         # inner_product(bits, Constant(2^l)): 2^0 = 1, the sum starts with b_0 itself
-        for l in range(1, depth):
-            cells += [("c", bits[l]), ("k", 1 << l), None]
-            gates += [0, 0, l + 1 < depth]
-        at = put(at, cells, gates)
-        idx_cells.append(at - 1)
+        idx_cell, at = t.index(at, bits)
+        idx_cells.append(idx_cell)
         assert at == lay["n_in"] + (j + 1) * lay["per_update"]
         if prev_top is None:
             top_old0 = cur_old
         else:
-            copy_of[cur_old] = prev_top                      # ctx.constrain_equal(cur_old, root_{j-1})
+            t.copy_of[cur_old] = prev_top                    # ctx.constrain_equal(cur_old, root_{j-1})
         prev_top = cur_new
-    cm = CopyMap(np.asarray(copy_of, dtype=np.int64), np.asarray(cidx, dtype=np.int64), consts, np.zeros(total, dtype=bool), np.asarray(gate, dtype=bool),
-                 np.zeros(0, dtype=np.int64))
-    return cm, merkle_update_instances(m, top_old0, idx_cells, [lay["old_leaf"] + j for j in range(m)], new_leaves, prev_top)
+    return t.finish(), merkle_update_instances(m, top_old0, idx_cells, [lay["old_leaf"] + j for j in range(m)], new_leaves, prev_top)
 
 
 def build_merkle_update(m, dim, depth, fetch_flags, fetch_values, builder=None):
@@ -1142,3 +1164,102 @@ def build_merkle_update(m, dim, depth, fetch_flags, fetch_values, builder=None):
     for k in range(1, m):
         B.tie(int(cur_old[k]), int(cur_new[k - 1]))          # ctx.constrain_equal(cur_old, root_{j-1})
     return B.finish(), merkle_update_instances(m, cur_old[0], idx, lay["old_leaf"] + j, new_leaf, cur_new[m - 1])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Merkle openings (include/vdb.h vdb_wit_merkle_open; pipeline.ReadHotPath)
+def merkle_open_layout(m, dim, depth, with_vectors):
+    """where the cells of m openings lie: dict(nperm, n_ins, sizes, leaf_cells, node_cells, level_cells, ip_cells, per_read, n_lead,
+    bits, sibs, n_in, total) — stream cells [vectors m * dim (vector mode) or leaves m (leaf mode) | bits | siblings], then read j's
+    block at n_in + j * per_read: its leaf sponge (vector mode only), per level [assert_bit 4 | select lo 8 | select ro 8 | H], the
+    index inner product"""
+    if m < 1 or depth < 1 or dim < 1:
+        raise ValueError("a call opens at least one slot of a tree with at least two leaves")
+    lay = merkle_leaf_layout(dim)
+    if not with_vectors:
+        lay.update(nperm=0, n_ins=[], sizes=[], leaf_cells=0)
+    n_lead = m * dim if with_vectors else m
+    lay.update(level_cells=20 + lay["node_cells"], ip_cells=1 + 3 * (depth - 1), n_lead=n_lead, bits=n_lead, sibs=n_lead + m * depth,
+               n_in=n_lead + 2 * m * depth)
+    lay["per_read"] = lay["leaf_cells"] + depth * lay["level_cells"] + lay["ip_cells"]
+    lay["total"] = lay["n_in"] + m * lay["per_read"]
+    return lay
+
+
+def merkle_open_instances(m, top0, idx, leaf, vector_cells=()):
+    """the public cells in make_public order: the root (the top of read 0), per read (idx, leaf), then in vector mode the m vectors word
+    by word"""
+    out = [int(top0)]
+    for j in range(m):
+        out += [int(idx[j]), int(leaf[j])]
+    return out + [int(c) for c in vector_cells]
+
+
+def trace_merkle_open(m, dim, depth, with_vectors, fetch_flags, fetch_values):
+    """The closure of m openings cell by cell (the ground truth of build_merkle_open): assign the three witness groups, then per read the
+    leaf sponge (vector mode), the levels and the index, the top of every read after the first tied to the top of read 0.
+    fetch_flags / fetch_values: as trace_merkle_update.  -> (CopyMap, public cells)"""
+    lay = merkle_open_layout(m, dim, depth, with_vectors)
+    t = _CellTrace(lay["total"], fetch_flags, fetch_values)
+    idx_cells, leaves, top0 = [], [], None
+    for j in range(m):
+        at = lay["n_in"] + j * lay["per_read"]
+        cur, at = t.leaf(at, lay, j * dim) if with_vectors else (j, at)      # the squeeze cell, or the assigned leaf
+        leaves.append(cur)
+        bits = [lay["bits"] + j * depth + l for l in range(depth)]
+        for l in range(depth):
+            b, sib = bits[l], lay["sibs"] + j * depth + l
+            t.assert_bit(at, b)
+            lo = t.select(at + 4, sib, cur, b)
+            ro = t.select(at + 12, cur, sib, b)
+            cur = t.node(at + 20, lo, ro)
+            at += lay["level_cells"]
+        idx_cell, at = t.index(at, bits)
+        idx_cells.append(idx_cell)
+        assert at == lay["n_in"] + (j + 1) * lay["per_read"]
+        if top0 is None:
+            top0 = cur
+        else:
+            t.copy_of[cur] = top0                            # ctx.constrain_equal(cur, root)
+    return t.finish(), merkle_open_instances(m, top0, idx_cells, leaves, range(m * dim) if with_vectors else ())
+
+
+def build_merkle_open(m, dim, depth, with_vectors, fetch_flags, fetch_values, builder=None):
+    """trace_merkle_open's map assembled from unit blocks — one per kind of permutation, the bit with its two selects, the index inner
+    product — each placed for all m reads at once, level after level (`builder`: as build_kmeans).  -> (CopyMap, public cells)"""
+    lay = merkle_open_layout(m, dim, depth, with_vectors)
+    B = (builder or _Builder)(lay["total"], 0)
+    j = np.arange(m, dtype=np.int64)
+    zeros = np.zeros(m, dtype=np.int64)
+    base = lay["n_in"] + j * lay["per_read"]
+    perm = _perm_placer(B, fetch_flags, fetch_values)
+
+    s = Sym(0, 0)
+    s.g_assert_bit(ext(0))
+    head = Block(s, [s.g_select(ext(1), ext(2), ext(0)), s.g_select(ext(2), ext(1), ext(0))])     # (bit, sibling, cur) -> lo, ro
+    s = Sym(0, 0)
+    acc = s.push(ext(0), depth > 1)
+    for l in range(1, depth):
+        s.push(ext(l))
+        s.push(C(1 << l))
+        acc = s.push(None, l + 1 < depth)
+    ip = Block(s, [acc])
+
+    if with_vectors:
+        state, off = None, 0
+        for p in range(lay["nperm"]):
+            state = perm(base + off, lay["n_ins"][p], state, [j * dim + 2 * p + i for i in range(lay["n_ins"][p])])
+            off += lay["sizes"][p]
+        leaf = state[1]
+    else:
+        leaf = j
+    cur = leaf
+    bits = lay["bits"] + j[:, None] * depth + np.arange(depth, dtype=np.int64)[None, :]
+    for l in range(depth):
+        lb = base + lay["leaf_cells"] + l * lay["level_cells"]
+        lr = B.place(head, lb, zeros, np.stack([bits[:, l], lay["sibs"] + j * depth + l, cur], axis=1))
+        cur = perm(lb + 20 + perm_cells(2), 0, perm(lb + 20, 2, None, [lr[:, 0], lr[:, 1]]), [])[1]
+    idx = B.place(ip, base + lay["leaf_cells"] + depth * lay["level_cells"], zeros, bits)[:, 0]
+    for k in range(1, m):
+        B.tie(int(cur[k]), int(cur[0]))                      # ctx.constrain_equal(cur, root)
+    return B.finish(), merkle_open_instances(m, cur[0], idx, leaf, range(m * dim) if with_vectors else ())

@@ -1253,6 +1253,86 @@ __global__ __launch_bounds__(64) void k_mku_index(Streams stq, const FpTables* _
   if (j + 1 == m) pub[1 + 3 * (size_t)m] = path_new[(size_t)depth * m + j];
 }
 
+// ------------------------------------------------------------------ Merkle openings (include/vdb.h vdb_wit_merkle_open)
+// m reads of slots idx_j of the resident tree `levels`, independent of each other; `levels` is only read.  Stream:
+// [vectors m * D (vector mode) or leaves m (leaf mode) | bits | siblings] (the assigned witnesses), then per read its leaf sponge
+// (vector mode only), per level [assert_bit | select lo | select ro | H(lo, ro)], and the index inner product.  No value pass hashes a
+// path node: the digest of read j at level l and its sibling are levels[mku_level_off(lp, l) + (idx_j >> l)] and its neighbour.
+struct MkoLayout {
+  uint32_t m, D, depth, nperm, with_vectors;
+  uint64_t leaf_cells, level_cells, ip_cells, per_read, n_lead, n_in, total;
+};
+// ctx.assign_witnesses of the three input groups: plain cells, no gate, a lane per cell
+__global__ __launch_bounds__(256) void k_mko_inputs(Streams st, uint64_t base, MkoLayout ml, uint64_t lp, const u256* __restrict__ vectors,
+                                                    const u256* __restrict__ levels, const uint32_t* __restrict__ idx) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= ml.n_in) return;
+  const uint64_t p = base + i;
+  if (p < st.rlo || p >= st.rhi) return;
+  u256 v;
+  if (i < ml.n_lead) {
+    v = ml.with_vectors ? vectors[i] : levels[idx[i]];
+  } else {
+    const uint64_t n_bits = (uint64_t)ml.m * ml.depth;
+    uint64_t t = i - ml.n_lead;
+    const bool sibling = t >= n_bits;
+    if (sibling) t -= n_bits;
+    const uint32_t l = (uint32_t)(t % ml.depth), node = idx[t / ml.depth] >> l;
+    v = sibling ? levels[mku_level_off(lp, l) + (node ^ 1u)] : ((node & 1u) ? mont_one<Fr>() : u256_zero());
+  }
+  st.adv[p] = v;
+  if (st.sel) st.sel[p] = 0;
+}
+// the cells of one level of one read in three parts (blockIdx.y): the bit and the two selects, then the absorbing and the padding-only
+// permutation of H(lo, ro) — a lane per (read, level), a wavefront holding one part only
+__global__ __launch_bounds__(64) void k_mko_level_trace(Streams stq, const FpTables* __restrict__ T, const PoseidonSpec* __restrict__ sp, MkoLayout ml,
+                                                        uint64_t base, uint64_t lp, const uint32_t* __restrict__ idx, const u256* __restrict__ levels) {
+  const uint32_t t = blockIdx.x * 64 + threadIdx.x, part = blockIdx.y;
+  const uint32_t depth = ml.depth;
+  if (t >= ml.m * depth) return;
+  const uint32_t j = t / depth, l = t % depth;
+  const uint64_t lb = base + ml.n_in + (uint64_t)j * ml.per_read + ml.leaf_cells + (uint64_t)l * ml.level_cells;
+  const uint32_t node = idx[j] >> l, bit = node & 1u;
+  const u256* pcur = levels + mku_level_off(lp, l) + node;
+  const u256* psib = levels + mku_level_off(lp, l) + (node ^ 1u);
+  WCtx c = make_ctx(stq, T, lb, 0);
+  if (part == 0) {
+    if (!stq.touches(lb, lb + 20, 0, 0)) return;
+    const u256 b = bit ? mont_one<Fr>() : u256_zero();
+    const u256 cur = *pcur, sib = *psib;
+    Gadgets g(c);
+    g.g_assert_bit(b);
+    g.g_select(sib, cur, b);
+    g.g_select(cur, sib, b);
+    return;
+  }
+  const uint32_t second = part - 1;
+  c.pos = lb + 20 + (second ? perm_cells(2) : 0);
+  if (!stq.touches(c.pos, c.pos + (second ? perm_cells(0) : perm_cells(2)), 0, 0)) return;
+  u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
+  u256 in[PSD_RATE] = {*(bit ? psib : pcur), *(bit ? pcur : psib)};
+  if (second) psd_permute_absorb(sp, st, in, 2);   // the padding-only permutation starts where the absorbing one ended
+  c = trace_permutation(c, T, sp, st, in, second ? 0 : 2);
+}
+// idx_j = gate.inner_product(bits, Constant(2^l)) per read, and the public values [root | idx, leaf per read | the vectors word by word]
+// (vleaf: the sponges' digests, k_mk_leaf_states; null in leaf mode, where the leaf is the assigned one)
+__global__ __launch_bounds__(64) void k_mko_index(Streams stq, const FpTables* __restrict__ T, MkoLayout ml, uint64_t base, uint64_t lp,
+                                                  const uint32_t* __restrict__ idx, const u256* __restrict__ levels, const u256* __restrict__ vectors,
+                                                  const u256* __restrict__ vleaf, u256* __restrict__ pub) {
+  const uint32_t j = blockIdx.x * 64 + threadIdx.x;
+  const uint32_t m = ml.m, depth = ml.depth;
+  if (j >= m) return;
+  const uint32_t slot = idx[j];
+  u256 bits[30];
+  for (uint32_t l = 0; l < depth; l++) bits[l] = ((slot >> l) & 1u) ? mont_one<Fr>() : u256_zero();
+  WCtx c = make_ctx(stq, T, base + ml.n_in + (uint64_t)j * ml.per_read + ml.leaf_cells + (uint64_t)depth * ml.level_cells, 0);
+  pub[1 + 2 * (size_t)j] = trace_ip_const(c, T, bits, T->pow2, (int)depth);
+  pub[2 + 2 * (size_t)j] = vleaf ? vleaf[j] : levels[slot];
+  if (j == 0) pub[0] = levels[mku_level_off(lp, depth)];
+  if (ml.with_vectors)
+    for (uint32_t w = 0; w < ml.D; w++) pub[1 + 2 * (size_t)m + (size_t)j * ml.D + w] = vectors[(size_t)j * ml.D + w];
+}
+
 // ------------------------------------------------------------------ layout (halo2-base assign_threads_in)
 // break points from the gate-start bits: the row walk of GateThreadBuilder::assign_all.  A column that
 // starts at stream cell S breaks at the first row r in {M-3, M-2 (if that cell starts a gate), M-1}.
@@ -1678,6 +1758,74 @@ int wit_merkle_update_dev(u256* levels, size_t n, size_t dim, const u256* new_ve
   return VDB_OK;
 }
 
+// sizes of m openings in a tree over n vectors; the limits of one call (include/vdb.h).  No cap on m beyond the cell count: nothing
+// is scanned in LDS.
+static int mko_layout(size_t n, size_t dim, size_t m, int with_vectors, MkoLayout* o, uint64_t* lp_out) {
+  VDB_ARG(n > 0 && dim > 0, "empty database");
+  VDB_ARG(m > 0, "a call opens at least one slot");
+  VDB_ARG(n <= ((size_t)1 << 30) && dim <= ((size_t)1 << 20), "tree deeper than 30 levels or vector longer than 2^20 words");
+  MkLayout ml;
+  mk_layout(n, dim, 0, &ml);
+  const uint64_t lp = ml.n_leaves_pow2;
+  uint32_t depth = 0;
+  while (((uint64_t)1 << depth) < lp) depth++;
+  VDB_ARG(depth >= 1, "a tree of one leaf has no path (depth 0)");
+  VDB_ARG(m < ((size_t)1 << 31) && (uint64_t)m * depth < ((uint64_t)1 << 31), "2^31 or more (read, level) pairs in one call");
+  o->m = (uint32_t)m;
+  o->D = (uint32_t)dim;
+  o->depth = depth;
+  o->with_vectors = with_vectors ? 1u : 0u;
+  o->nperm = with_vectors ? ml.nperm : 0;
+  o->leaf_cells = with_vectors ? ml.leaf_cells : 0;
+  o->level_cells = 4 + 2 * 8 + (uint64_t)(perm_cells(2) + perm_cells(0));
+  o->ip_cells = 1 + 3 * (uint64_t)(depth - 1);
+  o->per_read = o->leaf_cells + depth * o->level_cells + o->ip_cells;
+  o->n_lead = with_vectors ? (uint64_t)m * dim : (uint64_t)m;
+  o->n_in = o->n_lead + 2 * (uint64_t)m * depth;
+  o->total = o->n_in + (uint64_t)m * o->per_read;
+  VDB_ARG(o->total <= ((uint64_t)1 << 34), "more than VDB_MERKLE_OPEN_MAX_CELLS cells in one call");
+  if (lp_out) *lp_out = lp;
+  return VDB_OK;
+}
+// every opened slot lies in the padded tree, and in vector mode holds a vector
+static int mko_check_indices(const uint64_t* indices, size_t m, uint64_t lp, size_t n, int with_vectors) {
+  for (size_t j = 0; j < m; j++) {
+    VDB_ARG(indices[j] < lp, "opened slot outside the padded tree");
+    VDB_ARG(!with_vectors || indices[j] < n, "opened slot holds no vector (open it in leaf mode: its leaf is 0)");
+  }
+  return VDB_OK;
+}
+int wit_merkle_open_dev(const u256* levels, size_t n, size_t dim, const u256* vectors, const uint64_t* indices, size_t m, Streams st, u256* pub) {
+  MkoLayout ml;
+  uint64_t lp;
+  TRY(mko_layout(n, dim, m, vectors != nullptr, &ml, &lp));
+  TRY(mko_check_indices(indices, m, lp, n, vectors != nullptr));
+  static thread_local std::vector<uint32_t> hidx;  // pageable source: hipMemcpyAsync stages it before returning
+  hidx.resize(m);
+  for (size_t j = 0; j < m; j++) hidx[j] = (uint32_t)indices[j];
+  FpEntry* fp;
+  TRY(get_fp(48, 13, &fp));  // only GateChip primitives are used: P and L are irrelevant
+  TRY(set_winv(st, fp->dev));
+  const PoseidonSpec* sp;
+  TRY(poseidon_spec_dev(&sp, nullptr));
+  const size_t n_states = m * ml.nperm * PSD_T, n_leaf = vectors ? m : 0;
+  u256* states = (u256*)scratch_get(0, (n_states + n_leaf) * sizeof(u256) + m * sizeof(uint32_t) + 64);
+  if (!states) return VDB_ERR_OOM;
+  u256* vleaf = vectors ? states + n_states : nullptr;
+  uint32_t* didx = (uint32_t*)(states + n_states + n_leaf);
+  VDB_HIP(hipMemcpyAsync(didx, hidx.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx().stream));
+  const uint32_t mu = (uint32_t)m, depth = ml.depth;
+  VDB_LAUNCH(k_mko_inputs, dim3((unsigned)((ml.n_in + 255) / 256)), dim3(256), st, 0, ml, lp, vectors, levels, didx);
+  if (vectors) {
+    VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((m + 63) / 64)), dim3(64), sp, vectors, mu, (uint32_t)dim, ml.nperm, states, vleaf);
+    VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((m * ml.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, vectors, mu, (uint32_t)dim, ml.nperm, ml.n_in,
+               ml.per_read, states);
+  }
+  VDB_LAUNCH(k_mko_level_trace, dim3((unsigned)(((uint64_t)m * depth + 63) / 64), 3), dim3(64), st, fp->dev, sp, ml, 0, lp, didx, levels);
+  VDB_LAUNCH(k_mko_index, dim3((unsigned)((m + 63) / 64)), dim3(64), st, fp->dev, ml, 0, lp, didx, levels, vectors, vleaf, pub);
+  return VDB_OK;
+}
+
 }  // namespace vdb
 
 using namespace vdb;
@@ -2076,6 +2224,43 @@ int vdb_wit_merkle_update(vdb_fr* levels, size_t n, size_t dim, const vdb_fr* ne
   TRY(wit_merkle_update_dev(dl.as<u256>(), n, dim, dv.as<u256>(), indices, m, hs.st, dpub.as<u256>()));
   TRY(download(public_out, dpub.p, (3 * m + 2) * sizeof(u256)));
   TRY(download(levels, dl.p, 2 * lp * sizeof(u256)));
+  return hs.finish(stream_out, nullptr, selector_out, ml.total, 0);
+}
+
+// openings of the resident tree (include/vdb.h)
+int vdb_wit_merkle_open_size(size_t n, size_t dim, size_t m, int with_vectors, uint64_t* cells, uint64_t* input_cells) {
+  MkoLayout ml;
+  TRY(mko_layout(n, dim, m, with_vectors, &ml, nullptr));
+  if (cells) *cells = ml.total;
+  if (input_cells) *input_cells = ml.n_in;
+  return VDB_OK;
+}
+int vdb_wit_merkle_open_dev(const vdb_fr* levels_dev, size_t n, size_t dim, const vdb_fr* vectors_dev, const uint64_t* indices, size_t m, vdb_fr* stream_dev,
+                            uint8_t* selector_dev, vdb_fr* public_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(levels_dev && indices && stream_dev && public_dev, "null pointer");
+  DevStreams ds;
+  ds.init(stream_dev, selector_dev);
+  TRY(wit_merkle_open_dev(as_u256(levels_dev), n, dim, vectors_dev ? as_u256(vectors_dev) : nullptr, indices, m, ds.st, as_u256(public_dev)));
+  return ds.finish();
+}
+int vdb_wit_merkle_open(const vdb_fr* levels, size_t n, size_t dim, const vdb_fr* vectors, const uint64_t* indices, size_t m, vdb_fr* stream_out,
+                        uint8_t* selector_out, vdb_fr* public_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(levels && indices, "null pointer");
+  MkoLayout ml;
+  uint64_t lp;
+  TRY(mko_layout(n, dim, m, vectors != nullptr, &ml, &lp));
+  TRY(mko_check_indices(indices, m, lp, n, vectors != nullptr));
+  const size_t n_pub = 1 + 2 * m + (vectors ? m * dim : 0);
+  DevBuf dl, dv, dpub;
+  HostStreams hs;
+  TRY(upload(dl, levels, 2 * lp * sizeof(u256)));
+  if (vectors) TRY(upload(dv, vectors, m * dim * sizeof(u256)));
+  TRY(dpub.alloc(n_pub * sizeof(u256)));
+  TRY(hs.init(ml.total, 0, selector_out != nullptr));
+  TRY(wit_merkle_open_dev(dl.as<u256>(), n, dim, vectors ? dv.as<u256>() : nullptr, indices, m, hs.st, dpub.as<u256>()));
+  TRY(download(public_out, dpub.p, n_pub * sizeof(u256)));
   return hs.finish(stream_out, nullptr, selector_out, ml.total, 0);
 }
 

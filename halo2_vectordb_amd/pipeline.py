@@ -857,6 +857,112 @@ class UpdateHotPath(HotPath):
         return cm, pub, None
 
 
+class ReadHotPath(HotPath):
+    """Reads proved against the committed root: m openings of the resident tree in one proof (include/vdb.h vdb_wit_merkle_open).  The
+    reference has no such gadget: this is the closure a user of its chips writes.  reveal="vector": the m vectors read are assigned,
+    hashed (merkle_commitment's leaf hash) and public, "slot i holds vector v"; reveal="leaf": the leaf digest is assigned and
+    public, and a padding slot shows leaf 0, "slot i is empty".  Then per read the path level by level (assert_bit, two selects, one
+    node hash), the index as inner_product(bits, 2^l), and the top of every read tied to the top of read 0.  Public: [root | idx, leaf
+    per read | the vectors word by word (vector mode)].  Reads do not see each other and leave the tree (`d_levels`) as it is.  No
+    lookup cells; sharded like MerkleHotPath."""
+
+    def __init__(self, n=1024, dim=128, m=8, k=15, L=8, P=32, seed=20260006, tau=None, col_shard=(0, 1), vectors=None, levels=None, reads=None,
+                 reveal="vector", blind_seed=None, params=None):
+        """`vectors`: the current (n, dim) f64 database (None: seeded synthetic rows, when the tree is built here too); `levels`: the
+        tree as it stands (api.merkle_tree_build's layout: a DeviceBuffer, for instance an UpdateHotPath's d_levels, or a (2 lp, 4)
+        array; None: built from `vectors`).  `reads`: the m slots (None: m seeded slots, in leaf mode the last one a padding slot where
+        the tree has one)"""
+        if m < 1:
+            raise ValueError("a call opens at least one slot")
+        if reveal not in ("vector", "leaf"):
+            raise ValueError("reveal is 'vector' or 'leaf'")
+        self.lp, self.depth = api.merkle_levels(n)
+        if self.depth < 1:
+            raise ValueError("a tree of one leaf has no path")
+        super().__init__(n, dim, k, P, L, seed=seed, tau=tau, col_shard=col_shard, vectors=None, blind_seed=blind_seed, params=params)
+        self.m, self.with_vectors = m, reveal == "vector"
+        self.database_f64 = None if vectors is None else np.ascontiguousarray(vectors, dtype=np.float64)
+        if self.database_f64 is None and (levels is None or self.with_vectors):
+            if levels is not None:
+                raise ValueError("a read that reveals vectors needs the database the tree was built from")
+            self.database_f64, _ = sift_like_vectors(self.seed, self.n, self.dim)
+        if self.database_f64 is not None and self.database_f64.shape != (self.n, self.dim):
+            raise ValueError("database rows do not match the circuit's shape")
+        self.given_levels, self.given_reads = levels, reads
+        self.balance_shards = False
+        self.msm_window_bits = 14   # as MerkleHotPath: nearly every scalar is a full-width Poseidon state
+
+    def n_input_rows(self):
+        return self.m if self.with_vectors else 0
+
+    def _input_vectors(self):
+        """the m rows read, gathered from the database (vector mode; none in leaf mode), and self.indices"""
+        if self.given_reads is not None:
+            idx = np.asarray(self.given_reads)
+        else:
+            idx = np.random.default_rng(self.seed).integers(0, self.n, size=self.m)
+            if not self.with_vectors and self.lp > self.n:
+                idx[-1] = self.n                                  # "this slot is empty"
+        self.indices = np.ascontiguousarray(idx, dtype=np.uint64)
+        if self.indices.shape != (self.m,) or (self.indices >= (self.n if self.with_vectors else self.lp)).any():
+            raise ValueError("a read needs a slot that holds a vector (vector mode) or lies in the padded tree (leaf mode)")
+        rows = self.database_f64[self.indices.astype(np.int64)] if self.with_vectors else np.zeros((0, self.dim))
+        return rows, self.seed
+
+    def _load_inputs(self):
+        super()._load_inputs()
+        self.d_levels = self._output(2 * self.lp * B)
+        lv = self.given_levels
+        if isinstance(lv, api.DeviceBuffer):
+            check(self.lib.vdb_memcpy_d2d(self.d_levels.ptr, lv.ptr, ctypes.c_size_t(2 * self.lp * B)))
+        elif lv is not None:
+            lv = np.ascontiguousarray(lv, dtype=np.uint64)
+            assert lv.shape == (2 * self.lp, 4), "the tree does not belong to this shape"
+            self.d_levels.upload(lv)
+        else:
+            qdb = api.quantize(self.database_f64, self.P)
+            d_db = api.DeviceBuffer(qdb.nbytes)
+            try:
+                d_db.upload(qdb)
+                check(self.lib.vdb_merkle_tree_build_dev(d_db.ptr, self.n, self.dim, self.d_levels.ptr))
+                api.sync()
+            finally:
+                d_db.free()
+
+    def _circuit_size(self):
+        cells, n_in = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self.lib.vdb_wit_merkle_open_size(self.n, self.dim, self.m, int(self.with_vectors), ctypes.byref(cells), ctypes.byref(n_in)))
+        return n_in.value, cells.value - n_in.value, 0
+
+    def _alloc_outputs(self):
+        self.n_pub = 1 + 2 * self.m + (self.m * self.dim if self.with_vectors else 0)
+        self.d_pub = self._output(self.n_pub * B)
+
+    def _witness(self, sel=None):
+        # the call writes the assigned witnesses too (bits from the indices, siblings and leaves out of the tree)
+        with self._window(sel, 0, lookup=False):
+            check(self.lib.vdb_wit_merkle_open_dev(self.d_levels.ptr, self.n, self.dim, self.d_vec.ptr if self.with_vectors else None, api._p(self.indices),
+                                                   self.m, self.d_stream.ptr, self._sel_at(sel, 0), self.d_pub.ptr))
+
+    def public_values_dev(self):
+        return self.d_pub.ptr, self.n_pub
+
+    def results(self):
+        """(root (4,), indices (m, 4), leaves (m, 4)[, vectors (m, dim, 4) in vector mode])"""
+        pub = self.d_pub.download((self.n_pub, 4))
+        per = pub[1:1 + 2 * self.m].reshape(self.m, 2, 4)
+        out = (pub[0], per[:, 0], per[:, 1])
+        return out + (pub[1 + 2 * self.m:].reshape(self.m, self.dim, 4),) if self.with_vectors else out
+
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        cm, pub = CS.build_merkle_open(self.m, self.dim, self.depth, self.with_vectors, functools.partial(self._fetch_flags, d_flags), self._fetch,
+                                       builder=DeviceBuilder if on_device else None)
+        assert cm.n_cells == self.n_cells
+        return cm, pub, None
+
+
 class TopKQueryHotPath(HotPath):
     """Top-k queries against ONE committed database in one proof: assign the q queries, assign the n database vectors, per query the
     `topk` rounds of include/vdb.h's vdb_wit_nearest_topk (nearest_vector's distances once, its qmin chain / is_equal /

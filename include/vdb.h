@@ -256,7 +256,7 @@ int vdb_merkle_tree_build_dev(const vdb_fr *vectors_dev, size_t n, size_t dim, v
  * Work space: 32 B x m x (3 (dim / 2 + 1) + 4 depth + 3) plus 5 B per (update, level).
  * Limits of one call (VDB_ERR_ARG beyond them, as for m == 0, depth == 0 (n == 1) and an index >= lp, before anything is launched):
  * m at most VDB_MERKLE_UPDATE_MAX_UPDATES (the batch's indices are scanned in LDS), depth at most 30, all cells at most
- * VDB_MERKLE_UPDATE_MAX_CELLS.  Deleting a vector, growing the tree past lp and a stand-alone membership proof are not provided. */
+ * VDB_MERKLE_UPDATE_MAX_CELLS.  Deleting a vector and growing the tree past lp are not provided (a read is vdb_wit_merkle_open). */
 #define VDB_MERKLE_UPDATE_MAX_UPDATES ((size_t)4096)
 #define VDB_MERKLE_UPDATE_MAX_CELLS ((uint64_t)1 << 34)
 int vdb_wit_merkle_update_size(size_t n, size_t dim, size_t m, uint64_t *cells, uint64_t *input_cells);
@@ -264,6 +264,37 @@ int vdb_wit_merkle_update(vdb_fr *levels, size_t n, size_t dim, const vdb_fr *ne
                           uint8_t *selector_out, vdb_fr *public_out);
 int vdb_wit_merkle_update_dev(vdb_fr *levels_dev, size_t n, size_t dim, const vdb_fr *new_vectors_dev, const uint64_t *indices, size_t m,
                               vdb_fr *stream_dev, uint8_t *selector_dev, vdb_fr *public_dev);
+/* Reads proved against the committed root: m openings of slots indices[j] of the tree `levels` (vdb_merkle_tree_build_dev's layout, or
+ * what a batch of updates left), "slot i of the database with this root holds vector v" or "slot i is empty".  The reference has no such
+ * gadget; the cells are those of the closure a user of its chips writes.  depth = log2(lp) >= 1.  Repeats are allowed; reads do not
+ * see each other; levels is only read.
+ * Vector mode (vectors: the m vectors read, m x dim).  Stream, from cell 0: the assigned witnesses — the m vectors, per read the depth
+ * index bits (least significant first), per read the depth siblings (leaf level first): input_cells of them — then per read j
+ *   leaf = poseidon.clear(); update(vector_j); squeeze()                       (the leaf hash of merkle_commitment)
+ *   cur = leaf; per level l: gate.assert_bit(b_l); lo = select(sib_l, cur, b_l); ro = select(cur, sib_l, b_l); cur = H(lo, ro)
+ *                                                                              (4 + 8 + 8 + 4,506 = 4,526 cells a level)
+ *   idx = gate.inner_product(bits, Constant(2^l))                              (1 + 3 (depth - 1) cells)
+ * with H the node hash of merkle_commitment.  The circuit ties the top of read j >= 1 to the top of read 0 (a copy constraint, no
+ * cells).  public 1 + 2 m + m dim values: [root | idx_j, leaf_j per read | vector_0 ... vector_{m-1}, dim words each].  A slot >= n
+ * holds no vector and is refused.
+ * Leaf mode (vectors NULL): the leaf digest is itself an assigned witness and public; stream [leaves m | bits | siblings], then per read
+ * the levels and the index, no leaf sponge.  public 1 + 2 m values: [root | idx_j, leaf_j per read].  Any slot < lp may be opened; a
+ * padding slot shows leaf 0: "this slot is empty".
+ * Every digest of a path and every sibling is read from levels; nothing compares the vectors with the tree.  If a vector is not the one
+ * committed at its slot, or levels is stale, the call still writes a stream, and that stream breaks a copy constraint (the sponge's
+ * squeeze cell, or a node hash's output, differs from the `cur` cells that copy it): the Mock stage reports it and no proof verifies.
+ * indices is a HOST array in both forms.  The number of kernel launches depends on neither m nor depth (five in vector mode, three in
+ * leaf mode).  The _dev form honours vdb_wit_set_window like vdb_wit_merkle_dev.
+ * Work space: vector mode 32 B x m x (3 (dim / 2 + 1) + 1) plus 4 B per read; leaf mode 4 B per read.
+ * VDB_ERR_ARG, before anything is launched and before any buffer is touched: m == 0, depth == 0 (n == 1), n == 0 or dim == 0, n > 2^30
+ * or dim > 2^20, an index >= lp, an index >= n in vector mode, m x depth >= 2^31, more than VDB_MERKLE_OPEN_MAX_CELLS cells.  There is
+ * no cap on m itself: nothing is scanned in LDS. */
+#define VDB_MERKLE_OPEN_MAX_CELLS ((uint64_t)1 << 34)
+int vdb_wit_merkle_open_size(size_t n, size_t dim, size_t m, int with_vectors, uint64_t *cells, uint64_t *input_cells);
+int vdb_wit_merkle_open(const vdb_fr *levels, size_t n, size_t dim, const vdb_fr *vectors /* m x dim, NULL: leaf mode */, const uint64_t *indices,
+                        size_t m, vdb_fr *stream_out, uint8_t *selector_out, vdb_fr *public_out);
+int vdb_wit_merkle_open_dev(const vdb_fr *levels_dev, size_t n, size_t dim, const vdb_fr *vectors_dev /* m x dim, NULL: leaf mode */,
+                            const uint64_t *indices /* host */, size_t m, vdb_fr *stream_dev, uint8_t *selector_dev, vdb_fr *public_dev);
 
 /* ---- b4 stream -> columns: replaces halo2-base GateThreadBuilder::assign_all (break points, keygen)
  *      and assign_threads_in (prover) as driven by RangeCircuitBuilder::prover(builder, break_points)

@@ -10,7 +10,10 @@ holds Q queries against the one database — nearest_vector per query, one merkl
 (pipeline.BatchQueryHotPath); with `--topk T` (T > 1) every query asks for its T nearest vectors, nearest first
 (pipeline.TopKQueryHotPath).
 `--circuit update --updates M` proves M inserts / replacements against the committed root of the n x dim database instead
-(pipeline.UpdateHotPath: M Merkle path updates, [old root | idx, old leaf, new leaf per update | new root] public)."""
+(pipeline.UpdateHotPath: M Merkle path updates, [old root | idx, old leaf, new leaf per update | new root] public).
+`--circuit read --reads M` proves M reads of the committed n x dim database (pipeline.ReadHotPath: M Merkle openings, [root | idx, leaf
+per read | the vectors read] public; `--leaf-only`: the leaf digests instead of the vectors, a padding slot showing leaf 0), and has
+the verifier check the proof."""
 import argparse
 import json
 import os
@@ -21,7 +24,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from halo2_vectordb_amd import api  # noqa: E402
-from halo2_vectordb_amd.pipeline import BatchQueryHotPath, MerkleHotPath, QueryHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
+from halo2_vectordb_amd.pipeline import BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
 from halo2_vectordb_amd.rounds import ProverRounds, quotient_identity_holds  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -32,12 +35,14 @@ ap.add_argument("--seed", type=int, default=20260003)
 ap.add_argument("--block-cols", type=int, default=510)
 ap.add_argument("--ext-block-cols", type=int, default=None)
 ap.add_argument("--proofs", type=int, default=2)
-ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update"])
+ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read"])
 ap.add_argument("--lookup-bits", type=int, default=13)
 ap.add_argument("--metric", default="euclidean")
 ap.add_argument("--queries", type=int, default=1, help="--circuit query: queries proved against the one database in this proof")
 ap.add_argument("--topk", type=int, default=1, help="--circuit query: nearest vectors proved per query, nearest first")
 ap.add_argument("--updates", type=int, default=8, help="--circuit update: inserts / replacements proved in this proof")
+ap.add_argument("--reads", type=int, default=8, help="--circuit read: slots opened in this proof")
+ap.add_argument("--leaf-only", action="store_true", help="--circuit read: reveal the leaf digests, not the vectors")
 ap.add_argument("--out", default=None, help="write the proof (io.write_snark) and the verifying key beside it")
 args = ap.parse_args()
 
@@ -53,6 +58,8 @@ elif args.circuit == "query" and args.queries > 1:
     hp = BatchQueryHotPath(q=args.queries, n=args.n, dim=args.dim, k=args.k, L=args.lookup_bits, metric=args.metric, seed=args.seed)
 elif args.circuit == "update":
     hp = UpdateHotPath(n=args.n, dim=args.dim, m=args.updates, k=args.k, seed=args.seed)
+elif args.circuit == "read":
+    hp = ReadHotPath(n=args.n, dim=args.dim, m=args.reads, k=args.k, seed=args.seed, reveal="leaf" if args.leaf_only else "vector")
 elif args.circuit == "query":
     hp = QueryHotPath(n=args.n, dim=args.dim, k=args.k, L=args.lookup_bits, metric=args.metric, seed=args.seed)
 else:
@@ -77,19 +84,25 @@ wall, host_ms, out = best
 T = {}
 pr.prove(None, timings=T)
 ok = quotient_identity_holds(pr, out["challenges"], out["evals"], out["instances"])
-root = api.fr_to_canonical(np.asarray(hp.results() if args.circuit == "merkle" else hp.results()[-1]).reshape(1, 4))[0]
+root_at = 0 if args.circuit == "read" else -1                # a read states the root first, the other circuits last
+root = api.fr_to_canonical(np.asarray(hp.results() if args.circuit == "merkle" else hp.results()[root_at]).reshape(1, 4))[0]
 root_int = int(root[0]) | int(root[1]) << 64 | int(root[2]) << 128 | int(root[3]) << 192
 if args.out:
     from halo2_vectordb_amd.io import write_snark
     write_snark(args.out, out["proof"], out["instances"])
     pr.save_verifying_key(args.out + ".vk.npz", opened=out["opened"])
+accepted = {}
+if args.circuit == "read":
+    from halo2_vectordb_amd import verifier
+    accepted = {"proof_accepted": bool(verifier.verify(out["proof"], out["instances"], verifier.VerifyingKey.from_prover(pr, out["opened"])))}
 what = f"merkle_commitment {args.n}x{args.dim} k={args.k}" if args.circuit == "merkle" else \
     f"{args.updates} Merkle path updates against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "update" else \
+    f"{args.reads} Merkle openings ({'leaves' if args.leaf_only else 'vectors'} public) against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "read" else \
     f"query circuit ({str(args.queries) + ' x ' if args.queries > 1 else ''}{'top-' + str(args.topk) + ' ' if args.topk > 1 else ''}nearest_vector {args.metric} + merkle_commitment) over {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}"
 print(json.dumps({"workload": what + ": whole constraint map, public outputs in the instance column, transcript, fresh blinds, SHPLONK", "lookup_cells": hp.n_lookup,
                   "cells": hp.n_cells, "columns": hp.n_cols, "product_sets": pr.n_sets, "mock_report_on_keygen_witness": pr.keygen_report.as_dict(),
                   "setup_s": round(t1 - t0, 1), "keygen_s": round(t2 - t1, 1), "quotient_identity_at_x_holds": bool(ok),
-                  "public_root_is_the_hash_only_kernels_root": out["instances"][-1] == root_int, "n_instances": len(out["instances"]), "proof_bytes": len(out["proof"]), "proof_wall_ms": round(wall, 1),
+                  "public_root_is_the_hash_only_kernels_root": out["instances"][root_at] == root_int, **accepted, "n_instances": len(out["instances"]), "proof_bytes": len(out["proof"]), "proof_wall_ms": round(wall, 1),
                   "constraints_per_s": round(hp.n_cells / (wall * 1e-3)), "host_transcript_ms": round(host_ms["transcript"], 1),
                   "device_ms": {k: round(v, 2) for k, v in T.items()}, "device_ms_total": round(sum(T.values()), 1),
                   "block_cols": args.block_cols, "ext_cols_held": hp.ext_cols}))

@@ -7,7 +7,7 @@ must not depend on the number of ranks (tests/test_gpu_sharded.py).
         tools/sharded_prove.py --circuit kmeans --out /tmp/p2.bin
 
 Circuits: "kmeans" (a small cosine k-means), "nearest" (small), "c2" (BASELINE configs[1]: nearest_vector over 64 x 128, k = 14),
-"merkle" (small, no lookup columns), "distances" (examples/distances.rs, small), "query" (small: nearest_vector and merkle_commitment in one circuit), "batch_query" (small: three queries against one database, nearest_vector per query and one merkle_commitment), "topk_query" (small: two queries, the three nearest vectors of each, one merkle_commitment), "merkle_update" (small: four inserts / replacements proved against the root of six vectors), "mid" (cosine k-means over 128 x 64 vectors, K = 4, I = 4, at 2^16 rows).  Rank 0 writes the proof bytes to --out and prints one JSON line; every rank checks that its
+"merkle" (small, no lookup columns), "distances" (examples/distances.rs, small), "query" (small: nearest_vector and merkle_commitment in one circuit), "batch_query" (small: three queries against one database, nearest_vector per query and one merkle_commitment), "topk_query" (small: two queries, the three nearest vectors of each, one merkle_commitment), "merkle_update" (small: four inserts / replacements proved against the root of six vectors), "merkle_read" (small: four reads, one slot twice, of six vectors, the vectors public), "mid" (cosine k-means over 128 x 64 vectors, K = 4, I = 4, at 2^16 rows).  Rank 0 writes the proof bytes to --out and prints one JSON line; every rank checks that its
 own transcript ended with the same bytes (sha256 exchanged)."""
 import argparse
 import hashlib
@@ -78,6 +78,9 @@ def main():
         from halo2_vectordb_amd.pipeline import UpdateHotPath
         rows = np.random.default_rng(5).integers(0, 219, size=(4, 4)).astype(np.float64)
         hp = UpdateHotPath(n=6, dim=4, m=4, k=12, tau=TAU, col_shard=shard, updates=([2, 6, 2, 7], rows))
+    elif args.circuit == "merkle_read":    # four reads of six vectors, slot 2 twice, the vectors public: 1 + 2 m + m dim public values
+        from halo2_vectordb_amd.pipeline import ReadHotPath
+        hp = ReadHotPath(n=6, dim=4, m=4, k=12, tau=TAU, col_shard=shard, reads=[2, 5, 2, 0])
     elif args.circuit == "c2":
         hp = NearestHotPath(n=64, dim=128, k=14, L=13, tau=TAU, col_shard=shard)
     elif args.circuit == "mid":      # a k = 16 cosine k-means of a few thousand columns: per-rank work and exchange overheads at a real row count
