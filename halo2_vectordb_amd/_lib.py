@@ -69,6 +69,9 @@ _SIGNATURES = {
     "vdb_wit_merkle_dev": [_P, _SZ, _SZ, _I, _P, _P, _P],
     "vdb_merkle_tree_build_dev": [_P, _SZ, _SZ, _P], "vdb_wit_merkle_update_size": [_SZ, _SZ, _SZ, _P, _P],
     "vdb_wit_merkle_update": [_P, _SZ, _SZ, _P, _P, _SZ, _P, _P, _P], "vdb_wit_merkle_update_dev": [_P, _SZ, _SZ, _P, _P, _SZ, _P, _P, _P],
+    "vdb_merkle_tree_grow_dev": [_P, _SZ, _U32, _P], "vdb_wit_merkle_update_ops_size": [_SZ, _SZ, _SZ, _P, _U32, _P, _P],
+    "vdb_wit_merkle_update_ops": [_P, _SZ, _SZ, _U32, _P, _P, _P, _SZ, _P, _P, _P],
+    "vdb_wit_merkle_update_ops_dev": [_P, _SZ, _SZ, _U32, _P, _P, _P, _SZ, _P, _P, _P],
     "vdb_wit_merkle_open_size": [_SZ, _SZ, _SZ, _I, _P, _P],
     "vdb_wit_merkle_open": [_P, _SZ, _SZ, _P, _P, _SZ, _P, _P, _P], "vdb_wit_merkle_open_dev": [_P, _SZ, _SZ, _P, _P, _SZ, _P, _P, _P],
     "vdb_wit_nearest_batch_size": [_I, _U32, _U32, _SZ, _SZ, _SZ, _P, _P],

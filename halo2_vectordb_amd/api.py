@@ -432,22 +432,43 @@ def merkle_tree_build(vectors):
         d_lv.free()
 
 
-def wit_merkle_update(levels, n, new_vectors, indices, selectors=False):
-    """a batch of Merkle path updates (vdb_wit_merkle_update) against the tree `levels` (merkle_tree_build's array over n vectors):
-    slot indices[j] takes new_vectors[j] (m, dim, 4), in order.  dict(stream, selectors, input_cells, public (3 m + 2, 4):
-    [old root | idx, old leaf, new leaf per update | new root], levels: the tree after the batch)"""
+def merkle_tree_grow(levels, n, grow):
+    """the tree `levels` (merkle_tree_build's array over n vectors) with its padded leaf count doubled `grow` times, the new slots
+    empty (vdb_merkle_tree_grow_dev): (2 lp 2^grow, 4) in the same layout"""
+    lib = _lib.init()
+    levels = np.ascontiguousarray(levels, dtype=np.uint64)
+    lp, _ = merkle_levels(n)
+    assert levels.shape == (2 * lp, 4) and grow >= 0
+    d_lv, d_out = DeviceBuffer(levels.nbytes), DeviceBuffer(2 * (lp << grow) * 32)
+    try:
+        d_lv.upload(levels)
+        check(lib.vdb_merkle_tree_grow_dev(d_lv.ptr, _sz(n), int(grow), d_out.ptr))
+        return d_out.download((2 * (lp << grow), 4))
+    finally:
+        d_lv.free()
+        d_out.free()
+
+
+def wit_merkle_update(levels, n, new_vectors, indices, selectors=False, kinds=None, grow=0):
+    """a batch of Merkle path updates (vdb_wit_merkle_update_ops) against the tree `levels` (merkle_tree_build's array over n vectors,
+    after merkle_tree_grow when grow > 0): slot indices[j] takes the next row of new_vectors (w, dim, 4), or is emptied where
+    kinds[j] = 1 (None: all writes), in order.  dict(stream, selectors, input_cells, public (3 m + 2, 4): [old root | idx, old leaf,
+    new leaf per update | new root], levels: the tree after the batch)"""
     lib = _lib.init()
     new_vectors = _fr(new_vectors)
     levels = np.array(levels, dtype=np.uint64, copy=True)
     idx = np.ascontiguousarray(indices, dtype=np.uint64)
-    m, dim = new_vectors.shape[0], new_vectors.shape[1]
-    assert idx.shape == (m,) and levels.shape == (2 * merkle_levels(n)[0], 4)
+    m, dim = idx.shape[0], new_vectors.shape[1]
+    kinds = np.zeros(m, dtype=np.uint8) if kinds is None else np.ascontiguousarray(kinds, dtype=np.uint8)
+    assert idx.shape == (m,) and kinds.shape == (m,) and levels.shape == (2 * (merkle_levels(n)[0] << grow), 4)
+    assert new_vectors.shape[0] == int((kinds == 0).sum()), "one new vector per write"
     cells, n_in = _u64(), _u64()
-    check(lib.vdb_wit_merkle_update_size(_sz(n), _sz(dim), _sz(m), ctypes.byref(cells), ctypes.byref(n_in)))
+    check(lib.vdb_wit_merkle_update_ops_size(_sz(n), _sz(dim), _sz(m), _p(kinds), int(grow), ctypes.byref(cells), ctypes.byref(n_in)))
     stream = np.zeros((cells.value, 4), dtype=np.uint64)
     sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
     pub = np.zeros((3 * m + 2, 4), dtype=np.uint64)
-    check(lib.vdb_wit_merkle_update(_p(levels), _sz(n), _sz(dim), _p(new_vectors), _p(idx), _sz(m), _p(stream), _p(sel) if selectors else None, _p(pub)))
+    check(lib.vdb_wit_merkle_update_ops(_p(levels), _sz(n), _sz(dim), int(grow), _p(new_vectors) if new_vectors.shape[0] else None, _p(idx), _p(kinds),
+                                        _sz(m), _p(stream), _p(sel) if selectors else None, _p(pub)))
     return dict(stream=stream, **_split_flags(sel), input_cells=n_in.value, public=pub, levels=levels)
 
 

@@ -975,19 +975,40 @@ def build_merkle(n, dim, fetch_flags, fetch_values, builder=None):
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # Merkle path updates (include/vdb.h vdb_wit_merkle_update; pipeline.UpdateHotPath)
-def merkle_update_layout(m, dim, depth):
+def merkle_update_layout(m, dim, depth, kinds=None, grow=0):
     """where the cells of a batch of m path updates lie: dict(nperm, n_ins, sizes, leaf_cells, node_cells, level_cells, ip_cells,
     per_update, n_vec, old_leaf, bits, sibs, n_in, total) — the last five stream cells: [new vectors | old leaves | bits | siblings],
     then update j's block at n_in + j * per_update: its leaf sponge, per level [assert_bit 4 | select lo 8 | select ro 8 | H old |
-    select ln 8 | select rn 8 | H new], the index inner product"""
+    select ln 8 | select rn 8 | H new], the index inner product.
+    kinds[j] = 1 makes update j a delete (one load_constant(0) cell in place of the sponge; only the w writes have a new vector) and
+    `grow` doublings of the tree before the batch put R_0 behind the siblings and the growth block [Z_0 | depth - 1 hashes Z_{l+1} =
+    H(Z_l, Z_l) | grow hashes R_{i+1} = H(R_i, Z_{d+i})] behind the assigned witnesses (`depth` is the grown one, d = depth - grow).
+    Further keys: kinds, grow, w, write_no (per update: its row among the new vectors, -1 for a delete), r0 and z0 (cells; None when
+    grow = 0), grow_cells, block and levels_at (per update: its first cell, the first cell of its level 0); per_update is the size of
+    a write's block."""
+    kinds = [0] * m if kinds is None else [int(k) for k in kinds]
     if m < 1 or depth < 1 or dim < 1:
         raise ValueError("a batch holds at least one update of a tree with at least two leaves")
+    if len(kinds) != m or not set(kinds) <= {0, 1} or grow < 0 or grow > depth:
+        raise ValueError("one kind (0 write, 1 delete) per update, and no more doublings than the grown tree has levels")
     lay = merkle_leaf_layout(dim)
-    lay.update(level_cells=36 + 2 * lay["node_cells"], ip_cells=1 + 3 * (depth - 1), n_vec=m * dim, old_leaf=m * dim, bits=m * dim + m,
-               sibs=m * dim + m + m * depth)
+    w = kinds.count(0)
+    lay.update(level_cells=36 + 2 * lay["node_cells"], ip_cells=1 + 3 * (depth - 1), n_vec=w * dim, old_leaf=w * dim, bits=w * dim + m,
+               sibs=w * dim + m + m * depth, kinds=kinds, grow=grow, w=w)
     lay["per_update"] = lay["leaf_cells"] + depth * lay["level_cells"] + lay["ip_cells"]
-    lay["n_in"] = m * (dim + 1 + 2 * depth)
-    lay["total"] = lay["n_in"] + m * lay["per_update"]
+    lay["n_in"] = w * dim + m * (1 + 2 * depth) + (1 if grow else 0)
+    lay["r0"], lay["z0"] = (lay["n_in"] - 1, lay["n_in"]) if grow else (None, None)
+    lay["grow_cells"] = 1 + (depth - 1 + grow) * lay["node_cells"] if grow else 0
+    at, wn = lay["n_in"] + lay["grow_cells"], 0
+    lay["block"], lay["levels_at"], lay["write_no"] = [], [], []
+    for k in kinds:
+        lay["block"].append(at)
+        at += 1 if k else lay["leaf_cells"]
+        lay["levels_at"].append(at)
+        lay["write_no"].append(-1 if k else wn)
+        wn += 1 - k
+        at += depth * lay["level_cells"] + lay["ip_cells"]
+    lay["total"] = at
     return lay
 
 
@@ -1083,16 +1104,32 @@ class _CellTrace:
                        np.asarray(self.gate, dtype=bool), np.zeros(0, dtype=np.int64))
 
 
-def trace_merkle_update(m, dim, depth, fetch_flags, fetch_values):
-    """The closure of a batch of m path updates cell by cell (the ground truth of build_merkle_update): assign the four witness groups,
-    then per update the leaf sponge, the levels and the index, the top of the old path tied to the top of the update before.
+def trace_merkle_update(m, dim, depth, fetch_flags, fetch_values, kinds=None, grow=0):
+    """The closure of a batch of m path updates cell by cell (the ground truth of build_merkle_update): assign the witness groups, the
+    growth block when the tree was grown, then per update the leaf sponge (a write) or the constant 0 (a delete), the levels and the
+    index, the top of the old path tied to the top of the update before — that of update 0 to R_grow when the tree was grown.
     fetch_flags(lo, hi) / fetch_values(lo, hi): flag bytes / canonical values of stream cells of a keygen-style run (one instance of
     every kind of permutation is read: the Poseidon constants are fixed-column values).  -> (CopyMap, public cells)"""
-    lay = merkle_update_layout(m, dim, depth)
+    lay = merkle_update_layout(m, dim, depth, kinds, grow)
     t = _CellTrace(lay["total"], fetch_flags, fetch_values)
     idx_cells, new_leaves, prev_top, top_old0 = [], [], None, None
+    if grow:
+        at = t.put(lay["z0"], [("k", 0)], [0])                # Z_0 = ctx.load_constant(0)
+        z, prev_top = [lay["z0"]], lay["r0"]
+        for l in range(depth - 1):
+            z.append(t.node(at, z[l], z[l]))
+            at += lay["node_cells"]
+        for i in range(grow):
+            prev_top = t.node(at, prev_top, z[depth - grow + i])
+            at += lay["node_cells"]
+        assert at == lay["block"][0]
     for j in range(m):
-        cur_new, at = t.leaf(lay["n_in"] + j * lay["per_update"], lay, j * dim)
+        if lay["kinds"][j]:
+            cur_new = lay["block"][j]
+            at = t.put(cur_new, [("k", 0)], [0])             # new_leaf = ctx.load_constant(0)
+        else:
+            cur_new, at = t.leaf(lay["block"][j], lay, lay["write_no"][j] * dim)
+        assert at == lay["levels_at"][j]
         cur_old = lay["old_leaf"] + j
         new_leaves.append(cur_new)
         bits = [lay["bits"] + j * depth + l for l in range(depth)]
@@ -1109,28 +1146,42 @@ def trace_merkle_update(m, dim, depth, fetch_flags, fetch_values):
             at += 16 + lay["node_cells"]
         idx_cell, at = t.index(at, bits)
         idx_cells.append(idx_cell)
-        assert at == lay["n_in"] + (j + 1) * lay["per_update"]
-        if prev_top is None:
-            top_old0 = cur_old
-        else:
-            t.copy_of[cur_old] = prev_top                    # ctx.constrain_equal(cur_old, root_{j-1})
+        assert at == (lay["block"][j + 1] if j + 1 < m else lay["total"])
+        if j == 0:
+            top_old0 = lay["r0"] if grow else cur_old
+        if prev_top is not None:
+            t.copy_of[cur_old] = prev_top                    # ctx.constrain_equal(cur_old, root_{j-1}) (update 0: R_grow)
         prev_top = cur_new
     return t.finish(), merkle_update_instances(m, top_old0, idx_cells, [lay["old_leaf"] + j for j in range(m)], new_leaves, prev_top)
 
 
-def build_merkle_update(m, dim, depth, fetch_flags, fetch_values, builder=None):
+def build_merkle_update(m, dim, depth, fetch_flags, fetch_values, builder=None, kinds=None, grow=0):
     """trace_merkle_update's map assembled from unit blocks — one per kind of permutation, the bit with its two selects, the two selects
-    of the new path, the index inner product — each placed for all m updates at once, level after level (`builder`: as build_kmeans).
+    of the new path, the index inner product — each placed for all m updates at once, level after level (`builder`: as build_kmeans);
+    the growth block's hashes one after the other, the constants (Z_0, each delete's 0) as fixed-column cells.
     -> (CopyMap, public cells)"""
-    lay = merkle_update_layout(m, dim, depth)
+    lay = merkle_update_layout(m, dim, depth, kinds, grow)
     B = (builder or _Builder)(lay["total"], 0)
     j = np.arange(m, dtype=np.int64)
     zeros = np.zeros(m, dtype=np.int64)
-    base = lay["n_in"] + j * lay["per_update"]
+    base = np.asarray(lay["block"], dtype=np.int64)
+    levels_at = np.asarray(lay["levels_at"], dtype=np.int64)
     perm = _perm_placer(B, fetch_flags, fetch_values)
 
     def node(bases, left, right):
         return perm(bases + perm_cells(2), 0, perm(bases, 2, None, [left, right]), [])[1]
+
+    top = None
+    if grow:
+        B.constant_cell(lay["z0"], 0)                        # Z_0 = ctx.load_constant(0)
+        one = lambda c: np.asarray([c], dtype=np.int64)
+        z, top, at = [one(lay["z0"])], one(lay["r0"]), lay["z0"] + 1
+        for l in range(depth - 1):
+            z.append(node(one(at), z[l], z[l]))
+            at += lay["node_cells"]
+        for i in range(grow):
+            top = node(one(at), top, z[depth - grow + i])
+            at += lay["node_cells"]
 
     s = Sym(0, 0)
     s.g_assert_bit(ext(0))
@@ -1145,25 +1196,33 @@ def build_merkle_update(m, dim, depth, fetch_flags, fetch_values, builder=None):
         acc = s.push(None, l + 1 < depth)
     ip = Block(s, [acc])
 
-    state, off = None, 0
-    for p in range(lay["nperm"]):
-        state = perm(base + off, lay["n_ins"][p], state, [j * dim + 2 * p + i for i in range(lay["n_ins"][p])])
-        off += lay["sizes"][p]
-    new_leaf = state[1]
+    is_write = np.asarray(lay["kinds"], dtype=np.int64) == 0
+    new_leaf = base.copy()                                   # a delete: its block starts with new_leaf = ctx.load_constant(0)
+    for c in base[~is_write]:
+        B.constant_cell(int(c), 0)
+    if lay["w"]:
+        wbase, word0 = base[is_write], np.arange(lay["w"], dtype=np.int64) * dim
+        state, off = None, 0
+        for p in range(lay["nperm"]):
+            state = perm(wbase + off, lay["n_ins"][p], state, [word0 + 2 * p + i for i in range(lay["n_ins"][p])])
+            off += lay["sizes"][p]
+        new_leaf[is_write] = state[1]
     cur_old, cur_new = lay["old_leaf"] + j, new_leaf
     bits = lay["bits"] + j[:, None] * depth + np.arange(depth, dtype=np.int64)[None, :]
     for l in range(depth):
-        lb = base + lay["leaf_cells"] + l * lay["level_cells"]
+        lb = levels_at + l * lay["level_cells"]
         sib = lay["sibs"] + j * depth + l
         lr = B.place(head, lb, zeros, np.stack([bits[:, l], sib, cur_old], axis=1))
         cur_old = node(lb + 20, lr[:, 0], lr[:, 1])
         lb = lb + 20 + lay["node_cells"]
         lr = B.place(tail, lb, zeros, np.stack([bits[:, l], sib, cur_new], axis=1))
         cur_new = node(lb + 16, lr[:, 0], lr[:, 1])
-    idx = B.place(ip, base + lay["leaf_cells"] + depth * lay["level_cells"], zeros, bits)[:, 0]
+    idx = B.place(ip, levels_at + depth * lay["level_cells"], zeros, bits)[:, 0]
+    if grow:
+        B.tie(int(cur_old[0]), int(top[0]))                  # ctx.constrain_equal(cur_old, R_grow)
     for k in range(1, m):
         B.tie(int(cur_old[k]), int(cur_new[k - 1]))          # ctx.constrain_equal(cur_old, root_{j-1})
-    return B.finish(), merkle_update_instances(m, cur_old[0], idx, lay["old_leaf"] + j, new_leaf, cur_new[m - 1])
+    return B.finish(), merkle_update_instances(m, lay["r0"] if grow else cur_old[0], idx, lay["old_leaf"] + j, new_leaf, cur_new[m - 1])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -49,6 +49,7 @@ struct Context {
   // device-resident caches owned by other translation units; released through their hooks in vdb_shutdown
   std::map<uint64_t, void*> fp_tables;   // witness.hip: FixedPointChip tables keyed by (P, L)
   void* poseidon_spec = nullptr;          // poseidon.hip: device copy of the Poseidon spec
+  void* poseidon_empty = nullptr;         // poseidon.hip: digests of the empty subtrees of every height (poseidon_empty_subtrees_dev)
   bool ntt_lds_raised = false;            // ntt.hip: hipFuncAttributeMaxDynamicSharedMemorySize raised on this device
   uint64_t win[4] = {0, ~0ull, 0, ~0ull}; // witness.hip: rank window of the *_dev witness entry points (vdb_wit_set_window)
 };

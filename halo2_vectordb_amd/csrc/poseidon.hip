@@ -233,6 +233,8 @@ static std::once_flag g_spec_once;
 void poseidon_release(Context& c) {
   if (c.poseidon_spec) (void)hipFree(c.poseidon_spec);
   c.poseidon_spec = nullptr;
+  if (c.poseidon_empty) (void)hipFree(c.poseidon_empty);
+  c.poseidon_empty = nullptr;
 }
 // the host copy is built once per process, the device copy once per bound device (Context::poseidon_spec)
 int poseidon_spec_dev(const PoseidonSpec** dev_out, const PoseidonSpec** host_out) {
@@ -269,6 +271,32 @@ __global__ __launch_bounds__(256) void k_poseidon_permute(const PoseidonSpec* __
   for (int i = 0; i < PSD_RATE; i++) zero[i] = u256_zero();
   psd_permute_absorb(sp, st, zero, PSD_RATE);  // absorbing RATE zeros adds only the round-0 constants
   for (int i = 0; i < PSD_T; i++) st256(states + t * PSD_T + i, st[i]);
+}
+
+// the chain of empty-subtree digests: PSD_EMPTY_LEVELS - 1 dependent hashes, one lane, once per device
+__global__ void k_poseidon_empty_subtrees(const PoseidonSpec* __restrict__ sp, u256* __restrict__ z, uint32_t n) {
+  if (blockIdx.x || threadIdx.x) return;
+  u256 cur = u256_zero();
+  st256(z, cur);
+  for (uint32_t l = 1; l < n; l++) {
+    u256 in[PSD_RATE] = {cur, cur};
+    cur = psd_hash(sp, in, 2, 1);
+    st256(z + l, cur);
+  }
+}
+int poseidon_empty_subtrees_dev(const u256** dev_out) {
+  Context& c = ctx();
+  if (!c.poseidon_empty) {
+    const PoseidonSpec* sp;
+    int rc = poseidon_spec_dev(&sp, nullptr);
+    if (rc) return rc;
+    void* z = nullptr;
+    VDB_HIP(hipMalloc(&z, PSD_EMPTY_LEVELS * sizeof(u256)));
+    VDB_LAUNCH(k_poseidon_empty_subtrees, dim3(1), dim3(1), sp, static_cast<u256*>(z), (uint32_t)PSD_EMPTY_LEVELS);
+    c.poseidon_empty = z;  // stream ordered: every later kernel of this context reads the finished table
+  }
+  *dev_out = static_cast<const u256*>(c.poseidon_empty);
+  return VDB_OK;
 }
 
 // device-level merkle root over already-resident leaves buffer (size: next pow2), result in lv[0]

@@ -46,6 +46,10 @@ void poseidon_plain_params(int t, int r_f, int r_p, std::vector<u256>& rc, std::
 void poseidon_build_spec(PoseidonSpec* out);
 // device-resident copy (created on first use)
 int poseidon_spec_dev(const PoseidonSpec** dev_out, const PoseidonSpec** host_out);
+// Z_l, l = 0 .. PSD_EMPTY_LEVELS - 1: the digest of a subtree of height l whose leaves are all the padding leaf 0 (Z_0 = 0,
+// Z_{l+1} = H(Z_l, Z_l)); data independent, hashed once per bound device and kept there beside the spec
+constexpr int PSD_EMPTY_LEVELS = 31;
+int poseidon_empty_subtrees_dev(const u256** dev_out);
 
 __device__ __forceinline__ u256 psd_pow5(const u256& x) {
   u256 x2 = fr_mul(x, x);

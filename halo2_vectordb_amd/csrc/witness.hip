@@ -1017,9 +1017,10 @@ __device__ __noinline__ WCtx trace_permutation(WCtx c, const FpTables* T, const 
 }
 HD uint32_t perm_cells(int n_in) { return (n_in == 2 ? 18u : (n_in == 1 ? 15u : 12u)) + 2238u; }
 
-// sponge states before every permutation of every leaf (value only)
+// sponge states before every permutation of every leaf (value only); leaf v's digest goes to leaves[leaf_at[v]] (null: leaves[v])
 __global__ __launch_bounds__(64) void k_mk_leaf_states(const PoseidonSpec* __restrict__ sp, const u256* __restrict__ vectors, uint32_t n, uint32_t D,
-                                                       uint32_t nperm, u256* __restrict__ states /* n * nperm * 3 */, u256* __restrict__ leaves) {
+                                                       uint32_t nperm, u256* __restrict__ states /* n * nperm * 3 */, u256* __restrict__ leaves,
+                                                       const uint32_t* __restrict__ leaf_at) {
   uint32_t v = blockIdx.x * 64 + threadIdx.x;
   if (v >= n) return;
   u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
@@ -1032,19 +1033,19 @@ __global__ __launch_bounds__(64) void k_mk_leaf_states(const PoseidonSpec* __res
     psd_permute_absorb(sp, st, in, cnt);
     off += (uint32_t)cnt;
   }
-  leaves[v] = st[1];
+  leaves[leaf_at ? leaf_at[v] : v] = st[1];
 }
-// one thread per leaf permutation: the trace cells
+// one thread per leaf permutation: the trace cells; leaf v's sponge starts at base + v * leaf_cells, or at base + starts[v] where given
 __global__ __launch_bounds__(64) void k_mk_leaf_trace(Streams stq, const FpTables* __restrict__ T, const PoseidonSpec* __restrict__ sp,
                                                       const u256* __restrict__ vectors, uint32_t n, uint32_t D, uint32_t nperm, uint64_t base,
-                                                      uint64_t leaf_cells, const u256* __restrict__ states) {
+                                                      uint64_t leaf_cells, const u256* __restrict__ states, const uint64_t* __restrict__ starts) {
   uint32_t id = blockIdx.x * 64 + threadIdx.x;
   if (id >= n * nperm) return;
   uint32_t v = id / nperm, p = id % nperm;
   uint32_t off = 2 * p;
   int cnt = off < D ? (int)(D - off < 2 ? D - off : 2) : 0;
   // permutations 0..p-1 of a leaf are full (2 inputs) except possibly the one before the padding-only one
-  uint64_t pos = base + (uint64_t)v * leaf_cells;
+  uint64_t pos = base + (starts ? starts[v] : (uint64_t)v * leaf_cells);
   for (uint32_t q = 0; q < p; q++) {
     uint32_t o = 2 * q;
     pos += perm_cells(o < D ? (int)(D - o < 2 ? D - o : 2) : 0);
@@ -1106,17 +1107,24 @@ __global__ __launch_bounds__(64) void k_mk_tree_trace(Streams stq, const FpTable
 // Values: the m leaf hashes (k_mk_leaf_states), then level after level (k_mku_level, a thread per (update, old / new path)).  Which
 // earlier update of the batch last touched a node depends on the indices alone, so one kernel (k_mku_touchers) answers it for every
 // (update, level) before any hash is known: a backward scan over the batch's indices held in LDS.
+// An update is a write or a delete (kinds): a delete's new leaf is one load_constant(0) cell in place of the sponge, so the blocks of
+// a batch differ in size and the kernels take where update j's levels start from an array (level_at, host prefix sums).  The tree may
+// have been doubled `grow` times before the batch (vdb_merkle_tree_grow_dev): then the assigned witnesses end with R_0, the root before
+// the growth, and a growth block follows them: [Z_0 = load_constant(0) | Z_{l+1} = H(Z_l, Z_l), l < depth - 1 | R_{i+1} = H(R_i, Z_{d+i}),
+// i < grow] (k_mku_grow_trace), d the depth before the growth.  A plain batch is all writes and grow = 0.
 #define MKU_MAX_UPDATES 4096
 struct MkuLayout {
-  uint32_t m, D, depth, nperm;
-  uint64_t leaf_cells, level_cells, ip_cells, per_update, n_vec, n_in, total;
+  uint32_t m, w, D, depth, d0, grow, nperm;  // w: the writes among the m updates; depth = d0 + grow
+  uint64_t leaf_cells, level_cells, ip_cells, n_vec, n_wit, n_in, grow_cells, total;  // n_in = n_vec + n_wit (+ 1: R_0 when grow)
 };
 HD uint64_t mku_level_off(uint64_t lp, uint32_t l) { return 2 * (lp - (lp >> l)); }
 // per (level, update), arrays indexed [l * m + j]: sib_from = the latest earlier update whose path holds this one's sibling node at
 // level l (-1: the resident digest is still current), last = no later update touches this update's node at level l (its new-path
-// digest is the batch's final state of that node); prev_same[j] = the latest earlier update of the same slot (-1: none)
+// digest is the batch's final state of that node); prev_same[j] = the latest earlier update of the same slot (-1: none).
+// write_no[j]: which of the new vectors update j writes, -1 for a delete, whose new leaf 0 goes into row 0 of path_new here
 __global__ __launch_bounds__(256) void k_mku_touchers(const uint32_t* __restrict__ idx, uint32_t m, uint32_t depth, int32_t* __restrict__ sib_from,
-                                                      int32_t* __restrict__ prev_same, uint8_t* __restrict__ last) {
+                                                      int32_t* __restrict__ prev_same, uint8_t* __restrict__ last, const int32_t* __restrict__ write_no,
+                                                      u256* __restrict__ path_new) {
   __shared__ uint32_t sidx[MKU_MAX_UPDATES];
   for (uint32_t i = threadIdx.x; i < m; i += 256) sidx[i] = idx[i];
   __syncthreads();
@@ -1139,6 +1147,7 @@ __global__ __launch_bounds__(256) void k_mku_touchers(const uint32_t* __restrict
         break;
       }
     prev_same[j] = same;
+    if (write_no[j] < 0) path_new[j] = u256_zero();
   }
   uint8_t is_last = 1;
   for (uint32_t i = j + 1; i < m; i++)
@@ -1191,7 +1200,7 @@ __global__ __launch_bounds__(64) void k_mku_writeback(u256* __restrict__ levels,
   const bool is_last = l < depth ? last[t] != 0 : j + 1 == m;
   if (is_last) levels[mku_level_off(lp, l) + (idx[j] >> l)] = path_new[t];
 }
-// ctx.assign_witnesses of the four input groups: plain cells, no gate
+// ctx.assign_witnesses of the four input groups: plain cells, no gate (R_0 behind them is k_mku_grow_trace's)
 __global__ __launch_bounds__(256) void k_mku_inputs(Streams st, uint64_t base, const u256* __restrict__ new_vectors, const u256* __restrict__ wit,
                                                     uint64_t n_vec, uint64_t n_in) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1204,14 +1213,15 @@ __global__ __launch_bounds__(256) void k_mku_inputs(Streams st, uint64_t base, c
 // the cells of one level of one update in five parts (blockIdx.y): the bit and the four selects, then the two permutations of the
 // old path's hash and the two of the new path's — a lane per (update, level), a wavefront holding one part only
 __global__ __launch_bounds__(64) void k_mku_level_trace(Streams stq, const FpTables* __restrict__ T, const PoseidonSpec* __restrict__ sp, MkuLayout ml,
-                                                        uint64_t base, const uint32_t* __restrict__ idx, const u256* __restrict__ wit,
-                                                        const u256* __restrict__ path_old, const u256* __restrict__ path_new) {
+                                                        uint64_t base, const uint64_t* __restrict__ level_at, const uint32_t* __restrict__ idx,
+                                                        const u256* __restrict__ wit, const u256* __restrict__ path_old,
+                                                        const u256* __restrict__ path_new) {
   const uint32_t t = blockIdx.x * 64 + threadIdx.x, part = blockIdx.y;
   const uint32_t m = ml.m, depth = ml.depth;
   if (t >= m * depth) return;
   const uint32_t j = t / depth, l = t % depth;
   const uint64_t H = perm_cells(2) + perm_cells(0);
-  const uint64_t lb = base + ml.n_in + (uint64_t)j * ml.per_update + ml.leaf_cells + (uint64_t)l * ml.level_cells;
+  const uint64_t lb = base + level_at[j] + (uint64_t)l * ml.level_cells;
   const uint32_t bit = (idx[j] >> l) & 1u;
   const u256* psib = wit + ((size_t)m + (size_t)m * depth + (size_t)j * depth + l);
   WCtx c = make_ctx(stq, T, lb, 0);
@@ -1238,19 +1248,69 @@ __global__ __launch_bounds__(64) void k_mku_level_trace(Streams stq, const FpTab
   if (second) psd_permute_absorb(sp, st, in, 2);   // the padding-only permutation starts where the absorbing one ended
   c = trace_permutation(c, T, sp, st, in, second ? 0 : 2);
 }
-// idx_j = gate.inner_product(bits, Constant(2^l)) per update, and the public values [old root | idx, old leaf, new leaf per update | new root]
-__global__ __launch_bounds__(64) void k_mku_index(Streams stq, const FpTables* __restrict__ T, MkuLayout ml, uint64_t base, const u256* __restrict__ wit,
+// idx_j = gate.inner_product(bits, Constant(2^l)) per update, a delete's load_constant(0) cell in front of its levels, and the public
+// values [old root | idx, old leaf, new leaf per update | new root] (the old root of a grown tree is R_0: k_mku_grow_trace's)
+__global__ __launch_bounds__(64) void k_mku_index(Streams stq, const FpTables* __restrict__ T, MkuLayout ml, uint64_t base,
+                                                  const uint64_t* __restrict__ level_at, const int32_t* __restrict__ write_no, const u256* __restrict__ wit,
                                                   const u256* __restrict__ path_old, const u256* __restrict__ path_new, u256* __restrict__ pub) {
   const uint32_t j = blockIdx.x * 64 + threadIdx.x;
   const uint32_t m = ml.m, depth = ml.depth;
   if (j >= m) return;
-  WCtx c = make_ctx(stq, T, base + ml.n_in + (uint64_t)j * ml.per_update + ml.leaf_cells + (uint64_t)depth * ml.level_cells, 0);
+  WCtx c = make_ctx(stq, T, base + level_at[j] - 1, 0);
+  if (write_no[j] < 0) c.push(u256_zero(), false, true);
+  c.pos = base + level_at[j] + (uint64_t)depth * ml.level_cells;
   const u256 s = trace_ip_const(c, T, wit + (size_t)m + (size_t)j * depth, T->pow2, (int)depth);
   pub[1 + 3 * (size_t)j] = s;
   pub[2 + 3 * (size_t)j] = wit[j];
   pub[3 + 3 * (size_t)j] = path_new[j];
-  if (j == 0) pub[0] = path_old[(size_t)depth * m];
+  if (j == 0 && !ml.grow) pub[0] = path_old[(size_t)depth * m];
   if (j + 1 == m) pub[1 + 3 * (size_t)m] = path_new[(size_t)depth * m + j];
+}
+// The growth block of a batch against a tree doubled ml.grow times, and what belongs to it: the assigned R_0 in front of it and the
+// public old root.  A lane per permutation of its depth - 1 + grow node hashes; every input is resident: Z_l in `empty`
+// (poseidon_empty_subtrees_dev), R_i at entry 0 of level d0 + i of `levels` as long as k_mku_writeback has not run.
+__global__ __launch_bounds__(64) void k_mku_grow_trace(Streams stq, const FpTables* __restrict__ T, const PoseidonSpec* __restrict__ sp, MkuLayout ml,
+                                                       uint64_t base, uint64_t lp, const u256* __restrict__ levels, const u256* __restrict__ empty,
+                                                       u256* __restrict__ pub) {
+  const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+  const uint32_t n_z = ml.depth - 1, n_hash = n_z + ml.grow;
+  if (t >= 2 * n_hash) return;
+  const uint64_t gb = base + ml.n_in;
+  if (t == 0) {
+    const u256 r0 = levels[mku_level_off(lp, ml.d0)];
+    pub[0] = r0;
+    WCtx c = make_ctx(stq, T, gb - 1, 0);
+    c.push(r0, false);
+    c.push(u256_zero(), false, true);
+  }
+  const uint32_t h = t >> 1, second = t & 1u;
+  const uint64_t p0 = gb + 1 + (uint64_t)h * (perm_cells(2) + perm_cells(0)) + (second ? perm_cells(2) : 0);
+  if (!stq.touches(p0, p0 + (second ? perm_cells(0) : perm_cells(2)), 0, 0)) return;
+  const uint32_t lz = h < n_z ? h : ml.d0 + (h - n_z);
+  u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
+  u256 in[PSD_RATE] = {h < n_z ? empty[lz] : levels[mku_level_off(lp, lz)], empty[lz]};
+  if (second) psd_permute_absorb(sp, st, in, 2);   // the padding-only permutation starts where the absorbing one ended
+  WCtx c = make_ctx(stq, T, p0, 0);
+  c = trace_permutation(c, T, sp, st, in, second ? 0 : 2);
+}
+
+// ------------------------------------------------------------------ growing the resident tree (include/vdb.h vdb_merkle_tree_grow_dev)
+// The tree over lp leaves (depth d) laid out again as the tree over lp << grow leaves whose new slots are empty, a lane per entry:
+// level l < d keeps its lp >> l digests and continues with Z_l; level d + i holds R_i at entry 0 (R_0: the old root; R_{i+1} =
+// H(R_i, Z_{d+i}): k_mk_level_values on one node, `grow` launches after this one, which leaves 0 there) and Z_{d+i} behind it.
+__global__ __launch_bounds__(256) void k_mk_tree_grow(const u256* __restrict__ old_lv, uint64_t lp, uint32_t d, uint32_t grow,
+                                                      const u256* __restrict__ empty, u256* __restrict__ out) {
+  const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x, glp = lp << grow;
+  if (e >= 2 * glp) return;
+  uint32_t l = 0;
+  while (l < d + grow && e >= mku_level_off(glp, l + 1)) l++;
+  const uint64_t i = e - mku_level_off(glp, l);
+  u256 v;
+  if (i >= (glp >> l)) v = u256_zero();                   // the unused last entry
+  else if (l < d) v = i < (lp >> l) ? old_lv[mku_level_off(lp, l) + i] : empty[l];
+  else if (i) v = empty[l];
+  else v = l == d ? old_lv[mku_level_off(lp, d)] : u256_zero();
+  out[e] = v;
 }
 
 // ------------------------------------------------------------------ Merkle openings (include/vdb.h vdb_wit_merkle_open)
@@ -1642,7 +1702,7 @@ static int mk_tree_values(const PoseidonSpec* sp, const u256* vectors, size_t n,
                           uint64_t* root_off) {
   const uint64_t lp = ml.n_leaves_pow2;
   VDB_HIP(hipMemsetAsync(levels, 0, 2 * lp * sizeof(u256), ctx().stream));
-  VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((n + 63) / 64)), dim3(64), sp, vectors, (uint32_t)n, (uint32_t)dim, ml.nperm, states, levels);
+  VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((n + 63) / 64)), dim3(64), sp, vectors, (uint32_t)n, (uint32_t)dim, ml.nperm, states, levels, nullptr);
   uint64_t off = 0;
   for (uint64_t lv = lp; lv > 1; off += lv, lv /= 2)
     VDB_LAUNCH(k_mk_level_values, dim3((unsigned)((lv / 2 + 63) / 64)), dim3(64), sp, levels + off, (uint32_t)(lv / 2), levels + off + lv);
@@ -1665,7 +1725,7 @@ int wit_merkle_dev(const u256* vectors, size_t n, size_t dim, int zero_cached, S
   uint64_t root_off;
   TRY(mk_tree_values(sp, vectors, n, dim, ml, states, levels, &root_off));
   VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((n * ml.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, vectors, (uint32_t)n, (uint32_t)dim, ml.nperm, 0,
-             ml.leaf_cells, states);
+             ml.leaf_cells, states, nullptr);
   if (ml.zero_cell) VDB_LAUNCH(k_push_cells, dim3(1), dim3(1), st, ml.leaves, u256_zero(), u256_zero(), 1u);
   // every node's two permutations in one launch (a tree of one leaf has no node: its root is the leaf digest)
   if (lp > 1)
@@ -1686,75 +1746,149 @@ int merkle_tree_build_dev(const u256* vectors, size_t n, size_t dim, u256* level
   return mk_tree_values(sp, vectors, n, dim, ml, states, levels, &root_off);
 }
 
-// sizes of a batch of m path updates in a tree over n vectors; the limits of one call (include/vdb.h)
-static int mku_layout(size_t n, size_t dim, size_t m, MkuLayout* o, uint64_t* lp_out) {
+// the tree of vdb_merkle_tree_build_dev with its padded leaf count doubled `grow` times, the new slots empty, into `grown`
+int merkle_tree_grow_dev(const u256* levels, size_t n, unsigned grow, u256* grown) {
+  VDB_ARG(n > 0 && n <= ((size_t)1 << 30), "empty database or tree deeper than 30 levels");
+  uint64_t lp = 1;
+  uint32_t d = 0;
+  while (lp < n) lp <<= 1, d++;
+  VDB_ARG(d + (uint64_t)grow <= 30, "grown tree deeper than 30 levels");
+  const PoseidonSpec* sp;
+  TRY(poseidon_spec_dev(&sp, nullptr));
+  const u256* empty;
+  TRY(poseidon_empty_subtrees_dev(&empty));
+  const uint64_t glp = lp << grow;
+  VDB_LAUNCH(k_mk_tree_grow, dim3((unsigned)((2 * glp + 255) / 256)), dim3(256), levels, lp, d, (uint32_t)grow, empty, grown);
+  for (uint32_t i = 0; i < grow; i++)
+    VDB_LAUNCH(k_mk_level_values, dim3(1), dim3(64), sp, grown + mku_level_off(glp, d + i), 1u, grown + mku_level_off(glp, d + i + 1));
+  return VDB_OK;
+}
+
+// sizes of a batch of m path updates (kinds: 0 write, 1 delete; null: all writes) in a tree over n vectors grown `grow` times; the
+// limits of one call (include/vdb.h).  level_at (m; null: not wanted): where the levels of update j start in the stream, behind its
+// leaf sponge or its zero cell; write_no (m): the row of new_vectors update j writes, -1 for a delete.
+static int mku_layout(size_t n, size_t dim, size_t m, const uint8_t* kinds, unsigned grow, MkuLayout* o, uint64_t* lp_out, uint64_t* level_at,
+                      int32_t* write_no) {
   VDB_ARG(n > 0 && dim > 0, "empty database");
   VDB_ARG(m > 0, "a batch holds at least one update");
   VDB_ARG(m <= MKU_MAX_UPDATES, "more than VDB_MERKLE_UPDATE_MAX_UPDATES updates in one call");
   VDB_ARG(n <= ((size_t)1 << 30) && dim <= ((size_t)1 << 20), "tree deeper than 30 levels or vector longer than 2^20 words");
   MkLayout ml;
   mk_layout(n, dim, 0, &ml);
-  const uint64_t lp = ml.n_leaves_pow2;
-  uint32_t depth = 0;
-  while (((uint64_t)1 << depth) < lp) depth++;
+  uint32_t d0 = 0;
+  while (((uint64_t)1 << d0) < ml.n_leaves_pow2) d0++;
+  VDB_ARG(d0 + (uint64_t)grow <= 30, "grown tree deeper than 30 levels");
+  const uint32_t depth = d0 + (uint32_t)grow;
   VDB_ARG(depth >= 1, "a tree of one leaf has no path (depth 0)");
+  size_t w = 0;
+  for (size_t j = 0; j < m; j++) {
+    VDB_ARG(!kinds || kinds[j] <= 1, "an update is a write (0) or a delete (1)");
+    w += !kinds || kinds[j] == 0;
+  }
+  const uint64_t H = perm_cells(2) + perm_cells(0);
   o->m = (uint32_t)m;
+  o->w = (uint32_t)w;
   o->D = (uint32_t)dim;
   o->depth = depth;
+  o->d0 = d0;
+  o->grow = (uint32_t)grow;
   o->nperm = ml.nperm;
   o->leaf_cells = ml.leaf_cells;
-  o->level_cells = 4 + 4 * 8 + 2 * (uint64_t)(perm_cells(2) + perm_cells(0));
+  o->level_cells = 4 + 4 * 8 + 2 * H;
   o->ip_cells = 1 + 3 * (uint64_t)(depth - 1);
-  o->per_update = o->leaf_cells + depth * o->level_cells + o->ip_cells;
-  o->n_vec = (uint64_t)m * dim;
-  o->n_in = o->n_vec + (uint64_t)m * (1 + 2 * (uint64_t)depth);
-  o->total = o->n_in + (uint64_t)m * o->per_update;
+  o->n_vec = (uint64_t)w * dim;
+  o->n_wit = (uint64_t)m * (1 + 2 * (uint64_t)depth);
+  o->n_in = o->n_vec + o->n_wit + (grow ? 1 : 0);
+  o->grow_cells = grow ? 1 + (uint64_t)(depth - 1 + grow) * H : 0;
+  uint64_t at = o->n_in + o->grow_cells;
+  int32_t wn = 0;
+  for (size_t j = 0; j < m; j++) {
+    const bool del = kinds && kinds[j];
+    at += del ? 1 : o->leaf_cells;
+    if (level_at) level_at[j] = at;
+    if (write_no) write_no[j] = del ? -1 : wn++;
+    at += depth * o->level_cells + o->ip_cells;
+  }
+  o->total = at;
   VDB_ARG(o->total <= ((uint64_t)1 << 34) && (uint64_t)m * ml.nperm <= ((uint64_t)1 << 30), "more than VDB_MERKLE_UPDATE_MAX_CELLS cells in one call");
-  if (lp_out) *lp_out = lp;
+  if (lp_out) *lp_out = ml.n_leaves_pow2 << grow;
   return VDB_OK;
 }
-int wit_merkle_update_dev(u256* levels, size_t n, size_t dim, const u256* new_vectors, const uint64_t* indices, size_t m, Streams st, u256* pub) {
+// `levels`: the tree at depth d + grow (merkle_tree_grow_dev's when grow > 0), left in the state after the batch; new_vectors: the rows of
+// the writes in update order
+int wit_merkle_update_dev(u256* levels, size_t n, size_t dim, unsigned grow, const u256* new_vectors, const uint64_t* indices, const uint8_t* kinds,
+                          size_t m, Streams st, u256* pub) {
+  static thread_local std::vector<uint64_t> h_level_at;
+  static thread_local std::vector<int32_t> h_write_no;
+  static thread_local std::vector<uint64_t> hbuf;  // pageable source: hipMemcpyAsync stages it before returning
+  VDB_ARG(m > 0 && m <= MKU_MAX_UPDATES, "a batch holds 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES updates");
+  h_level_at.resize(m);
+  h_write_no.resize(m);
   MkuLayout ml;
   uint64_t lp;
-  TRY(mku_layout(n, dim, m, &ml, &lp));
-  static thread_local std::vector<uint32_t> hidx;  // pageable source: hipMemcpyAsync stages it before returning
-  hidx.resize(m);
+  TRY(mku_layout(n, dim, m, kinds, grow, &ml, &lp, h_level_at.data(), h_write_no.data()));
+  VDB_ARG(new_vectors || ml.w == 0, "null pointer: a write needs its new vector");
+  // one upload: [level_at m | leaf_at w: where the sponge of write v starts | idx m | write_no m | write_of w: the update of write v]
+  const size_t w = ml.w;
+  const size_t n_tab = (m + w) * sizeof(uint64_t) + (2 * m + w) * sizeof(uint32_t);
+  hbuf.resize(n_tab / sizeof(uint64_t) + 1);
+  uint64_t* p_level_at = hbuf.data();
+  uint64_t* p_leaf_at = p_level_at + m;
+  uint32_t* p_idx = (uint32_t*)(p_leaf_at + w);
+  int32_t* p_write_no = (int32_t*)(p_idx + m);
+  uint32_t* p_write_of = (uint32_t*)(p_write_no + m);
   for (size_t j = 0; j < m; j++) {
-    VDB_ARG(indices[j] < lp, "update index outside the padded tree (growing the tree is out of scope)");
-    hidx[j] = (uint32_t)indices[j];
+    VDB_ARG(indices[j] < lp, "update index outside the padded tree (grow it first: vdb_merkle_tree_grow_dev)");
+    p_level_at[j] = h_level_at[j];
+    p_idx[j] = (uint32_t)indices[j];
+    p_write_no[j] = h_write_no[j];
+    if (h_write_no[j] >= 0) {
+      p_leaf_at[h_write_no[j]] = h_level_at[j] - ml.leaf_cells;
+      p_write_of[h_write_no[j]] = (uint32_t)j;
+    }
   }
   FpEntry* fp;
   TRY(get_fp(48, 13, &fp));  // only GateChip primitives are used: P and L are irrelevant
   TRY(set_winv(st, fp->dev));
   const PoseidonSpec* sp;
   TRY(poseidon_spec_dev(&sp, nullptr));
+  const u256* empty = nullptr;
+  if (grow) TRY(poseidon_empty_subtrees_dev(&empty));
   hipStream_t s = ctx().stream;
   const uint32_t depth = ml.depth;
-  const size_t n_states = m * ml.nperm * PSD_T, n_wit = m * (1 + 2 * (size_t)depth), n_path = m * ((size_t)depth + 1);
+  const size_t n_states = w * ml.nperm * PSD_T, n_wit = ml.n_wit, n_path = m * ((size_t)depth + 1);
   const size_t n_u256 = n_states + n_wit + 2 * n_path;
-  const size_t need = n_u256 * sizeof(u256) + (m * depth + 2 * m) * sizeof(uint32_t) + m * depth + 64;
+  const size_t need = n_u256 * sizeof(u256) + n_tab + (m * depth + m) * sizeof(uint32_t) + m * depth + 64;
   u256* buf = (u256*)scratch_get(0, need);
   if (!buf) return VDB_ERR_OOM;
   u256* states = buf;
   u256* wit = states + n_states;
   u256* path_old = wit + n_wit;
   u256* path_new = path_old + n_path;
-  int32_t* sib_from = (int32_t*)(path_new + n_path);
+  uint64_t* level_at = (uint64_t*)(path_new + n_path);
+  uint64_t* leaf_at = level_at + m;
+  uint32_t* didx = (uint32_t*)(leaf_at + w);
+  int32_t* write_no = (int32_t*)(didx + m);
+  uint32_t* write_of = (uint32_t*)(write_no + m);
+  int32_t* sib_from = (int32_t*)(write_of + w);
   int32_t* prev_same = sib_from + m * depth;
-  uint32_t* didx = (uint32_t*)(prev_same + m);
-  uint8_t* last = (uint8_t*)(didx + m);
-  VDB_HIP(hipMemcpyAsync(didx, hidx.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  const uint32_t mu = (uint32_t)m;
-  VDB_LAUNCH(k_mku_touchers, dim3((unsigned)((m * depth + 255) / 256)), dim3(256), didx, mu, depth, sib_from, prev_same, last);
-  VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((m + 63) / 64)), dim3(64), sp, new_vectors, mu, (uint32_t)dim, ml.nperm, states, path_new);
+  uint8_t* last = (uint8_t*)(prev_same + m);
+  VDB_HIP(hipMemcpyAsync(level_at, hbuf.data(), n_tab, hipMemcpyHostToDevice, s));
+  const uint32_t mu = (uint32_t)m, wu = (uint32_t)w;
+  // grids of at least one block: the launches of a call do not depend on how many of its updates are writes
+  VDB_LAUNCH(k_mku_touchers, dim3((unsigned)((m * depth + 255) / 256)), dim3(256), didx, mu, depth, sib_from, prev_same, last, write_no, path_new);
+  VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((w + 63) / 64 + (w == 0))), dim3(64), sp, new_vectors, wu, (uint32_t)dim, ml.nperm, states, path_new,
+             write_of);
   for (uint32_t l = 0; l < depth; l++)
     VDB_LAUNCH(k_mku_level, dim3((unsigned)((2 * m + 63) / 64)), dim3(64), sp, levels, lp, didx, mu, depth, l, sib_from, prev_same, wit, path_old, path_new);
+  if (grow)  // R_i and the public old root, read before the write-back replaces them
+    VDB_LAUNCH(k_mku_grow_trace, dim3((unsigned)((2 * (depth - 1 + grow) + 63) / 64)), dim3(64), st, fp->dev, sp, ml, 0, lp, levels, empty, pub);
   VDB_LAUNCH(k_mku_writeback, dim3((unsigned)((n_path + 63) / 64)), dim3(64), levels, lp, didx, mu, depth, last, path_new);
-  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)((ml.n_in + 255) / 256)), dim3(256), st, 0, new_vectors, wit, ml.n_vec, ml.n_in);
-  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((m * ml.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, new_vectors, mu, (uint32_t)dim, ml.nperm,
-             ml.n_in, ml.per_update, states);
-  VDB_LAUNCH(k_mku_level_trace, dim3((unsigned)((m * depth + 63) / 64), 5), dim3(64), st, fp->dev, sp, ml, 0, didx, wit, path_old, path_new);
-  VDB_LAUNCH(k_mku_index, dim3((unsigned)((m + 63) / 64)), dim3(64), st, fp->dev, ml, 0, wit, path_old, path_new, pub);
+  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)((ml.n_vec + n_wit + 255) / 256)), dim3(256), st, 0, new_vectors, wit, ml.n_vec, ml.n_vec + n_wit);
+  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((w * ml.nperm + 63) / 64 + (w == 0))), dim3(64), st, fp->dev, sp, new_vectors, wu, (uint32_t)dim, ml.nperm, 0,
+             ml.leaf_cells, states, leaf_at);
+  VDB_LAUNCH(k_mku_level_trace, dim3((unsigned)((m * depth + 63) / 64), 5), dim3(64), st, fp->dev, sp, ml, 0, level_at, didx, wit, path_old, path_new);
+  VDB_LAUNCH(k_mku_index, dim3((unsigned)((m + 63) / 64)), dim3(64), st, fp->dev, ml, 0, level_at, write_no, wit, path_old, path_new, pub);
   return VDB_OK;
 }
 
@@ -1817,9 +1951,9 @@ int wit_merkle_open_dev(const u256* levels, size_t n, size_t dim, const u256* ve
   const uint32_t mu = (uint32_t)m, depth = ml.depth;
   VDB_LAUNCH(k_mko_inputs, dim3((unsigned)((ml.n_in + 255) / 256)), dim3(256), st, 0, ml, lp, vectors, levels, didx);
   if (vectors) {
-    VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((m + 63) / 64)), dim3(64), sp, vectors, mu, (uint32_t)dim, ml.nperm, states, vleaf);
+    VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((m + 63) / 64)), dim3(64), sp, vectors, mu, (uint32_t)dim, ml.nperm, states, vleaf, nullptr);
     VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((m * ml.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, vectors, mu, (uint32_t)dim, ml.nperm, ml.n_in,
-               ml.per_read, states);
+               ml.per_read, states, nullptr);
   }
   VDB_LAUNCH(k_mko_level_trace, dim3((unsigned)(((uint64_t)m * depth + 63) / 64), 3), dim3(64), st, fp->dev, sp, ml, 0, lp, didx, levels);
   VDB_LAUNCH(k_mko_index, dim3((unsigned)((m + 63) / 64)), dim3(64), st, fp->dev, ml, 0, lp, didx, levels, vectors, vleaf, pub);
@@ -2191,40 +2325,59 @@ int vdb_merkle_tree_build_dev(const vdb_fr* vectors_dev, size_t n, size_t dim, v
   VDB_ARG(n <= ((size_t)1 << 30), "tree deeper than 30 levels");
   return merkle_tree_build_dev(as_u256(vectors_dev), n, dim, as_u256(levels_dev));
 }
-int vdb_wit_merkle_update_size(size_t n, size_t dim, size_t m, uint64_t* cells, uint64_t* input_cells) {
+int vdb_merkle_tree_grow_dev(const vdb_fr* levels_dev, size_t n, unsigned grow, vdb_fr* grown_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(levels_dev && grown_dev, "null pointer");
+  return merkle_tree_grow_dev(as_u256(levels_dev), n, grow, as_u256(grown_dev));
+}
+int vdb_wit_merkle_update_ops_size(size_t n, size_t dim, size_t m, const uint8_t* kinds, unsigned grow, uint64_t* cells, uint64_t* input_cells) {
   MkuLayout ml;
-  TRY(mku_layout(n, dim, m, &ml, nullptr));
+  TRY(mku_layout(n, dim, m, kinds, grow, &ml, nullptr, nullptr, nullptr));
   if (cells) *cells = ml.total;
   if (input_cells) *input_cells = ml.n_in;
   return VDB_OK;
 }
-int vdb_wit_merkle_update_dev(vdb_fr* levels_dev, size_t n, size_t dim, const vdb_fr* new_vectors_dev, const uint64_t* indices, size_t m, vdb_fr* stream_dev,
-                              uint8_t* selector_dev, vdb_fr* public_dev) {
+int vdb_wit_merkle_update_ops_dev(vdb_fr* levels_dev, size_t n, size_t dim, unsigned grow, const vdb_fr* new_vectors_dev, const uint64_t* indices,
+                                  const uint8_t* kinds, size_t m, vdb_fr* stream_dev, uint8_t* selector_dev, vdb_fr* public_dev) {
   VDB_REQUIRE_INIT();
-  VDB_ARG(levels_dev && new_vectors_dev && indices && stream_dev && public_dev, "null pointer");
+  VDB_ARG(levels_dev && indices && stream_dev && public_dev, "null pointer");
   DevStreams ds;
   ds.init(stream_dev, selector_dev);
-  TRY(wit_merkle_update_dev(as_u256(levels_dev), n, dim, as_u256(new_vectors_dev), indices, m, ds.st, as_u256(public_dev)));
+  TRY(wit_merkle_update_dev(as_u256(levels_dev), n, dim, grow, new_vectors_dev ? as_u256(new_vectors_dev) : nullptr, indices, kinds, m, ds.st,
+                            as_u256(public_dev)));
   return ds.finish();
 }
-int vdb_wit_merkle_update(vdb_fr* levels, size_t n, size_t dim, const vdb_fr* new_vectors, const uint64_t* indices, size_t m, vdb_fr* stream_out,
-                          uint8_t* selector_out, vdb_fr* public_out) {
+int vdb_wit_merkle_update_ops(vdb_fr* levels, size_t n, size_t dim, unsigned grow, const vdb_fr* new_vectors, const uint64_t* indices, const uint8_t* kinds,
+                              size_t m, vdb_fr* stream_out, uint8_t* selector_out, vdb_fr* public_out) {
   VDB_REQUIRE_INIT();
-  VDB_ARG(levels && new_vectors && indices, "null pointer");
+  VDB_ARG(levels && indices, "null pointer");
   MkuLayout ml;
   uint64_t lp;
-  TRY(mku_layout(n, dim, m, &ml, &lp));
-  for (size_t j = 0; j < m; j++) VDB_ARG(indices[j] < lp, "update index outside the padded tree (growing the tree is out of scope)");
+  TRY(mku_layout(n, dim, m, kinds, grow, &ml, &lp, nullptr, nullptr));
+  VDB_ARG(new_vectors || ml.w == 0, "null pointer");
+  for (size_t j = 0; j < m; j++) VDB_ARG(indices[j] < lp, "update index outside the padded tree (grow it first: vdb_merkle_tree_grow_dev)");
   DevBuf dl, dv, dpub;
   HostStreams hs;
   TRY(upload(dl, levels, 2 * lp * sizeof(u256)));
-  TRY(upload(dv, new_vectors, m * dim * sizeof(u256)));
+  if (ml.w) TRY(upload(dv, new_vectors, ml.n_vec * sizeof(u256)));
   TRY(dpub.alloc((3 * m + 2) * sizeof(u256)));
   TRY(hs.init(ml.total, 0, selector_out != nullptr));
-  TRY(wit_merkle_update_dev(dl.as<u256>(), n, dim, dv.as<u256>(), indices, m, hs.st, dpub.as<u256>()));
+  TRY(wit_merkle_update_dev(dl.as<u256>(), n, dim, grow, ml.w ? dv.as<u256>() : nullptr, indices, kinds, m, hs.st, dpub.as<u256>()));
   TRY(download(public_out, dpub.p, (3 * m + 2) * sizeof(u256)));
   TRY(download(levels, dl.p, 2 * lp * sizeof(u256)));
   return hs.finish(stream_out, nullptr, selector_out, ml.total, 0);
+}
+// a plain batch: every update a write, the tree not grown
+int vdb_wit_merkle_update_size(size_t n, size_t dim, size_t m, uint64_t* cells, uint64_t* input_cells) {
+  return vdb_wit_merkle_update_ops_size(n, dim, m, nullptr, 0, cells, input_cells);
+}
+int vdb_wit_merkle_update_dev(vdb_fr* levels_dev, size_t n, size_t dim, const vdb_fr* new_vectors_dev, const uint64_t* indices, size_t m, vdb_fr* stream_dev,
+                              uint8_t* selector_dev, vdb_fr* public_dev) {
+  return vdb_wit_merkle_update_ops_dev(levels_dev, n, dim, 0, new_vectors_dev, indices, nullptr, m, stream_dev, selector_dev, public_dev);
+}
+int vdb_wit_merkle_update(vdb_fr* levels, size_t n, size_t dim, const vdb_fr* new_vectors, const uint64_t* indices, size_t m, vdb_fr* stream_out,
+                          uint8_t* selector_out, vdb_fr* public_out) {
+  return vdb_wit_merkle_update_ops(levels, n, dim, 0, new_vectors, indices, nullptr, m, stream_out, selector_out, public_out);
 }
 
 // openings of the resident tree (include/vdb.h)

@@ -759,18 +759,29 @@ class UpdateHotPath(HotPath):
     paths level by level (assert_bit, four selects, two node hashes), the index as inner_product(bits, 2^l), and the top of the old path
     tied to the top of the update before.  Public: [old root | idx, old leaf, new leaf per update | new root]; an insert shows as old
     leaf 0.  The tree stays on the device: `d_levels` holds it after the batch (`d_levels0` before it), and `levels=` starts a batch
-    from the tree another batch left.  No lookup cells; sharded like MerkleHotPath."""
+    from the tree another batch left.  No lookup cells; sharded like MerkleHotPath.
+    `kinds` makes updates deletes (the new leaf is the constant 0) and `grow` doubles the padded leaf count that many times before the
+    first update (include/vdb.h vdb_wit_merkle_update_ops, vdb_merkle_tree_grow_dev): both are circuit shape, the public values keep
+    their form — the old root is the root before the growth, a delete shows new leaf 0."""
 
     def __init__(self, n=1024, dim=128, m=8, k=15, L=8, P=32, seed=20260005, tau=None, col_shard=(0, 1), vectors=None, updates=None, levels=None,
-                 blind_seed=None, params=None):
+                 blind_seed=None, params=None, kinds=None, grow=0):
         """`vectors`: the (n, dim) f64 database the tree is built from (None: seeded synthetic rows), or `levels`: a tree already on
-        the device or host (api.merkle_tree_build's layout; a DeviceBuffer or a (2 lp, 4) array).  `updates`: (indices, (m, dim) f64
-        rows), applied in order (None: m seeded replacements and, where the padding has room, inserts)"""
+        the device or host (api.merkle_tree_build's layout over n vectors, not yet grown; a DeviceBuffer or a (2 lp, 4) array).
+        `updates`: (indices, (w, dim) f64 rows of the writes), applied in order (None: m seeded replacements and, where the padding has
+        room, inserts).  `kinds`: per update 0 (write) or 1 (delete), None: all writes.  `lp` and `depth` are the grown tree's."""
         if m < 1:
             raise ValueError("a batch holds at least one update")
-        self.lp, self.depth = api.merkle_levels(n)
+        self.kinds = np.zeros(m, dtype=np.uint8) if kinds is None else np.ascontiguousarray(kinds, dtype=np.uint8)
+        if self.kinds.shape != (m,) or (self.kinds > 1).any() or grow < 0:
+            raise ValueError("one kind (0 write, 1 delete) per update and a non-negative number of doublings")
+        self.grow, self.w = int(grow), int((self.kinds == 0).sum())
+        self.lp0, depth0 = api.merkle_levels(n)
+        self.lp, self.depth = self.lp0 << self.grow, depth0 + self.grow
         if self.depth < 1:
             raise ValueError("a tree of one leaf has no path")
+        if self.depth > 30:
+            raise ValueError("a tree of at most 30 levels")
         super().__init__(n, dim, k, P, L, seed=seed, tau=tau, col_shard=col_shard, vectors=None, blind_seed=blind_seed, params=params)
         self.m = m
         self.database_f64 = None if vectors is None else np.ascontiguousarray(vectors, dtype=np.float64)
@@ -779,15 +790,16 @@ class UpdateHotPath(HotPath):
         self.msm_window_bits = 14   # as MerkleHotPath: nearly every scalar is a full-width Poseidon state
 
     def n_input_rows(self):
-        return self.m
+        return self.w
 
     def _input_vectors(self):
-        """the m new vectors (the rows ctx.assign_witnesses puts first) and self.indices"""
+        """the new vectors of the writes (the rows ctx.assign_witnesses puts first) and self.indices"""
         if self.given_updates is not None:
             idx, rows = self.given_updates
-            rows = np.ascontiguousarray(rows, dtype=np.float64)
+            rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, self.dim)
         else:
             rows, _ = sift_like_vectors(self.seed + 2000, self.m, self.dim)
+            rows = rows[: self.w]
             rng = np.random.default_rng(self.seed)
             idx = rng.integers(0, self.n, size=self.m)
             free = min(self.lp - self.n, self.m // 2)
@@ -802,14 +814,16 @@ class UpdateHotPath(HotPath):
         super()._load_inputs()
         self.d_levels0 = self._output(2 * self.lp * B)
         self.d_levels = self._output(2 * self.lp * B)
+        # the tree before the growth: straight into d_levels0 when it is not grown, else into d_levels, which every run overwrites
+        d_small = self.d_levels if self.grow else self.d_levels0
         if self.given_levels is not None:
             lv = self.given_levels
             if isinstance(lv, api.DeviceBuffer):
-                check(self.lib.vdb_memcpy_d2d(self.d_levels0.ptr, lv.ptr, ctypes.c_size_t(2 * self.lp * B)))
+                check(self.lib.vdb_memcpy_d2d(d_small.ptr, lv.ptr, ctypes.c_size_t(2 * self.lp0 * B)))
             else:
                 lv = np.ascontiguousarray(lv, dtype=np.uint64)
-                assert lv.shape == (2 * self.lp, 4), "the tree does not belong to this shape"
-                self.d_levels0.upload(lv)
+                assert lv.shape == (2 * self.lp0, 4), "the tree does not belong to this shape"
+                d_small.upload(lv)
         else:
             if self.database_f64 is None:
                 self.database_f64, _ = sift_like_vectors(self.seed, self.n, self.dim)
@@ -818,14 +832,17 @@ class UpdateHotPath(HotPath):
             d_db = api.DeviceBuffer(qdb.nbytes)
             try:
                 d_db.upload(qdb)
-                check(self.lib.vdb_merkle_tree_build_dev(d_db.ptr, self.n, self.dim, self.d_levels0.ptr))
+                check(self.lib.vdb_merkle_tree_build_dev(d_db.ptr, self.n, self.dim, d_small.ptr))
                 api.sync()
             finally:
                 d_db.free()
+        if self.grow:
+            check(self.lib.vdb_merkle_tree_grow_dev(d_small.ptr, self.n, self.grow, self.d_levels0.ptr))
+            api.sync()
 
     def _circuit_size(self):
         cells, n_in = ctypes.c_uint64(), ctypes.c_uint64()
-        check(self.lib.vdb_wit_merkle_update_size(self.n, self.dim, self.m, ctypes.byref(cells), ctypes.byref(n_in)))
+        check(self.lib.vdb_wit_merkle_update_ops_size(self.n, self.dim, self.m, api._p(self.kinds), self.grow, ctypes.byref(cells), ctypes.byref(n_in)))
         return n_in.value, cells.value - n_in.value, 0
 
     def _alloc_outputs(self):
@@ -836,8 +853,9 @@ class UpdateHotPath(HotPath):
         # tree before the batch, so that the keygen-style runs and the proof state the same update
         check(self.lib.vdb_memcpy_d2d(self.d_levels.ptr, self.d_levels0.ptr, ctypes.c_size_t(2 * self.lp * B)))
         with self._window(sel, 0, lookup=False):
-            check(self.lib.vdb_wit_merkle_update_dev(self.d_levels.ptr, self.n, self.dim, self.d_vec.ptr, api._p(self.indices), self.m, self.d_stream.ptr,
-                                                     self._sel_at(sel, 0), self.d_pub.ptr))
+            check(self.lib.vdb_wit_merkle_update_ops_dev(self.d_levels.ptr, self.n, self.dim, self.grow, self.d_vec.ptr if self.w else None,
+                                                         api._p(self.indices), api._p(self.kinds), self.m, self.d_stream.ptr, self._sel_at(sel, 0),
+                                                         self.d_pub.ptr))
 
     def public_values_dev(self):
         return self.d_pub.ptr, 3 * self.m + 2
@@ -852,7 +870,7 @@ class UpdateHotPath(HotPath):
         from . import circuit_sym as CS
         from .circuit_dev import DeviceBuilder
         cm, pub = CS.build_merkle_update(self.m, self.dim, self.depth, functools.partial(self._fetch_flags, d_flags), self._fetch,
-                                         builder=DeviceBuilder if on_device else None)
+                                         builder=DeviceBuilder if on_device else None, kinds=self.kinds.tolist(), grow=self.grow)
         assert cm.n_cells == self.n_cells
         return cm, pub, None
 

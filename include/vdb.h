@@ -256,7 +256,8 @@ int vdb_merkle_tree_build_dev(const vdb_fr *vectors_dev, size_t n, size_t dim, v
  * Work space: 32 B x m x (3 (dim / 2 + 1) + 4 depth + 3) plus 5 B per (update, level).
  * Limits of one call (VDB_ERR_ARG beyond them, as for m == 0, depth == 0 (n == 1) and an index >= lp, before anything is launched):
  * m at most VDB_MERKLE_UPDATE_MAX_UPDATES (the batch's indices are scanned in LDS), depth at most 30, all cells at most
- * VDB_MERKLE_UPDATE_MAX_CELLS.  Deleting a vector and growing the tree past lp are not provided (a read is vdb_wit_merkle_open). */
+ * VDB_MERKLE_UPDATE_MAX_CELLS.  These three calls are the vdb_wit_merkle_update_ops calls below with every update a write and the
+ * tree not grown (kinds == NULL, grow == 0): one kernel family.  A read is vdb_wit_merkle_open. */
 #define VDB_MERKLE_UPDATE_MAX_UPDATES ((size_t)4096)
 #define VDB_MERKLE_UPDATE_MAX_CELLS ((uint64_t)1 << 34)
 int vdb_wit_merkle_update_size(size_t n, size_t dim, size_t m, uint64_t *cells, uint64_t *input_cells);
@@ -264,6 +265,31 @@ int vdb_wit_merkle_update(vdb_fr *levels, size_t n, size_t dim, const vdb_fr *ne
                           uint8_t *selector_out, vdb_fr *public_out);
 int vdb_wit_merkle_update_dev(vdb_fr *levels_dev, size_t n, size_t dim, const vdb_fr *new_vectors_dev, const uint64_t *indices, size_t m,
                               vdb_fr *stream_dev, uint8_t *selector_dev, vdb_fr *public_dev);
+/* Growing the resident tree: the tree `levels_dev` over n vectors (lp padded leaves, depth d) laid out again with lp << grow leaves, the
+ * new slots empty, into grown_dev: 2 (lp << grow) entries in the same layout.  Level l < d keeps its digests and continues with Z_l,
+ * level d + i holds R_i at entry 0 and Z_{d+i} behind it, the last entry is 0; Z_0 = 0, Z_{l+1} = H(Z_l, Z_l) (the digest of an empty
+ * subtree of height l: data independent, hashed once per device and kept there), R_0 the old root, R_{i+1} = H(R_i, Z_{d+i}).
+ * levels_dev is only read.  d + grow at most 30 (VDB_ERR_ARG above); 1 + grow launches. */
+int vdb_merkle_tree_grow_dev(const vdb_fr *levels_dev, size_t n, unsigned grow, vdb_fr *grown_dev);
+/* Writes, deletes and growth proved against the committed root: the update circuit above with, per update, kinds[j] (0: a write, 1: a
+ * delete; a HOST array of m bytes, NULL: all writes) and the padded leaf count doubled `grow` times before the first update.
+ * d = log2(lp), depth = d + grow >= 1 (d == 0 is allowed when grow >= 1), w = the number of writes.  Stream: the assigned witnesses
+ * [new vectors w x dim (the writes, in update order) | old leaves m | bits m x depth | siblings m x depth], when grow >= 1 followed by
+ * R_0, the root before the growth (input_cells counts it); then, when grow >= 1, the growth block
+ *   Z_0 = ctx.load_constant(0); Z_{l+1} = H(Z_l, Z_l), l = 0 .. depth - 2; R_{i+1} = H(R_i, Z_{d+i}), i = 0 .. grow - 1
+ * ((depth - 1 + grow) x 4,506 + 1 cells; no digest is a constant of the circuit); then per update its block as above, a delete
+ * emitting the one cell ctx.load_constant(0) in place of the leaf sponge: that cell is its new_leaf.  cur_old at the top of update 0
+ * is tied to R_grow.  public, 3 m + 2 values as above: the old root is R_0, a delete shows new_leaf 0; grow and kinds are circuit shape
+ * (the verifying key's).  Deleting an empty slot is legal.  `levels` is the tree at depth d + grow (vdb_merkle_tree_grow_dev's when
+ * grow >= 1) and is left in the state after the batch; new_vectors holds the w rows of the writes (may be NULL when w == 0).
+ * The number of launches depends on depth and on grow > 0, never on m, w or the kinds.  The _dev form honours vdb_wit_set_window.
+ * VDB_ERR_ARG before anything is launched: a kind other than 0 or 1, d + grow > 30, d + grow == 0, an index >= lp << grow, and the
+ * limits on m and on the cell count above. */
+int vdb_wit_merkle_update_ops_size(size_t n, size_t dim, size_t m, const uint8_t *kinds, unsigned grow, uint64_t *cells, uint64_t *input_cells);
+int vdb_wit_merkle_update_ops(vdb_fr *levels, size_t n, size_t dim, unsigned grow, const vdb_fr *new_vectors, const uint64_t *indices,
+                              const uint8_t *kinds, size_t m, vdb_fr *stream_out, uint8_t *selector_out, vdb_fr *public_out);
+int vdb_wit_merkle_update_ops_dev(vdb_fr *levels_dev, size_t n, size_t dim, unsigned grow, const vdb_fr *new_vectors_dev, const uint64_t *indices,
+                                  const uint8_t *kinds, size_t m, vdb_fr *stream_dev, uint8_t *selector_dev, vdb_fr *public_dev);
 /* Reads proved against the committed root: m openings of slots indices[j] of the tree `levels` (vdb_merkle_tree_build_dev's layout, or
  * what a batch of updates left), "slot i of the database with this root holds vector v" or "slot i is empty".  The reference has no such
  * gadget; the cells are those of the closure a user of its chips writes.  depth = log2(lp) >= 1.  Repeats are allowed; reads do not

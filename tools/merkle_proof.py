@@ -10,7 +10,9 @@ holds Q queries against the one database — nearest_vector per query, one merkl
 (pipeline.BatchQueryHotPath); with `--topk T` (T > 1) every query asks for its T nearest vectors, nearest first
 (pipeline.TopKQueryHotPath).
 `--circuit update --updates M` proves M inserts / replacements against the committed root of the n x dim database instead
-(pipeline.UpdateHotPath: M Merkle path updates, [old root | idx, old leaf, new leaf per update | new root] public).
+(pipeline.UpdateHotPath: M Merkle path updates, [old root | idx, old leaf, new leaf per update | new root] public); `--deletes K` makes
+the last K of them deletes (new leaf 0), `--grow G` doubles the padded leaf count G times before the first update (the old root stays
+the root before the growth).
 `--circuit read --reads M` proves M reads of the committed n x dim database (pipeline.ReadHotPath: M Merkle openings, [root | idx, leaf
 per read | the vectors read] public; `--leaf-only`: the leaf digests instead of the vectors, a padding slot showing leaf 0), and has
 the verifier check the proof."""
@@ -41,6 +43,8 @@ ap.add_argument("--metric", default="euclidean")
 ap.add_argument("--queries", type=int, default=1, help="--circuit query: queries proved against the one database in this proof")
 ap.add_argument("--topk", type=int, default=1, help="--circuit query: nearest vectors proved per query, nearest first")
 ap.add_argument("--updates", type=int, default=8, help="--circuit update: inserts / replacements proved in this proof")
+ap.add_argument("--deletes", type=int, default=0, help="--circuit update: the last K updates empty their slot instead of writing it")
+ap.add_argument("--grow", type=int, default=0, help="--circuit update: doublings of the padded leaf count before the first update")
 ap.add_argument("--reads", type=int, default=8, help="--circuit read: slots opened in this proof")
 ap.add_argument("--leaf-only", action="store_true", help="--circuit read: reveal the leaf digests, not the vectors")
 ap.add_argument("--out", default=None, help="write the proof (io.write_snark) and the verifying key beside it")
@@ -50,6 +54,8 @@ api.init(0)
 t0 = time.time()
 if args.queries < 1 or (args.queries > 1 and args.circuit != "query"):
     raise SystemExit("--queries needs --circuit query and at least one query")
+if (args.deletes or args.grow) and args.circuit != "update":
+    raise SystemExit("--deletes and --grow need --circuit update")
 if args.topk < 1 or (args.topk > 1 and args.circuit != "query"):
     raise SystemExit("--topk needs --circuit query and at least one neighbour")
 if args.circuit == "query" and args.topk > 1:
@@ -57,7 +63,10 @@ if args.circuit == "query" and args.topk > 1:
 elif args.circuit == "query" and args.queries > 1:
     hp = BatchQueryHotPath(q=args.queries, n=args.n, dim=args.dim, k=args.k, L=args.lookup_bits, metric=args.metric, seed=args.seed)
 elif args.circuit == "update":
-    hp = UpdateHotPath(n=args.n, dim=args.dim, m=args.updates, k=args.k, seed=args.seed)
+    if not 0 <= args.deletes <= args.updates or args.grow < 0:
+        raise SystemExit("--deletes is between 0 and --updates, --grow is not negative")
+    kinds = [0] * (args.updates - args.deletes) + [1] * args.deletes
+    hp = UpdateHotPath(n=args.n, dim=args.dim, m=args.updates, k=args.k, seed=args.seed, kinds=kinds, grow=args.grow)
 elif args.circuit == "read":
     hp = ReadHotPath(n=args.n, dim=args.dim, m=args.reads, k=args.k, seed=args.seed, reveal="leaf" if args.leaf_only else "vector")
 elif args.circuit == "query":
@@ -96,7 +105,7 @@ if args.circuit == "read":
     from halo2_vectordb_amd import verifier
     accepted = {"proof_accepted": bool(verifier.verify(out["proof"], out["instances"], verifier.VerifyingKey.from_prover(pr, out["opened"])))}
 what = f"merkle_commitment {args.n}x{args.dim} k={args.k}" if args.circuit == "merkle" else \
-    f"{args.updates} Merkle path updates against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "update" else \
+    f"{args.updates} Merkle path updates ({args.deletes} deletes, tree grown {args.grow} times) against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "update" else \
     f"{args.reads} Merkle openings ({'leaves' if args.leaf_only else 'vectors'} public) against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "read" else \
     f"query circuit ({str(args.queries) + ' x ' if args.queries > 1 else ''}{'top-' + str(args.topk) + ' ' if args.topk > 1 else ''}nearest_vector {args.metric} + merkle_commitment) over {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}"
 print(json.dumps({"workload": what + ": whole constraint map, public outputs in the instance column, transcript, fresh blinds, SHPLONK", "lookup_cells": hp.n_lookup,

@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--seed", type=int, default=41)
     ap.add_argument("--block-cols", type=int, default=510)
     ap.add_argument("--ext-block-cols", type=int, default=None, help="hold this many coset columns (forces the streamed rounds)")
+    ap.add_argument("--deletes", type=int, default=0, help="merkle_update: the last K of the four updates empty their slot")
+    ap.add_argument("--grow", type=int, default=0, help="merkle_update: doublings of the padded leaf count before the first update")
     ap.add_argument("--timed", type=int, default=0, help="also time this many proofs with fresh blinds")
     ap.add_argument("--save-key", default=None, help="after keygen every rank writes its share of the proving key to <path>.rank<r>of<w>.npz")
     ap.add_argument("--load-key", default=None, help="no keygen: every rank reads its share of the proving key from <path>.rank<r>of<w>.npz")
@@ -77,7 +79,8 @@ def main():
     elif args.circuit == "merkle_update":    # a replacement, an insert into the padding, the same slot again, its sibling: 3 m + 2 public values
         from halo2_vectordb_amd.pipeline import UpdateHotPath
         rows = np.random.default_rng(5).integers(0, 219, size=(4, 4)).astype(np.float64)
-        hp = UpdateHotPath(n=6, dim=4, m=4, k=12, tau=TAU, col_shard=shard, updates=([2, 6, 2, 7], rows))
+        kinds = [0] * (4 - args.deletes) + [1] * args.deletes
+        hp = UpdateHotPath(n=6, dim=4, m=4, k=12, tau=TAU, col_shard=shard, updates=([2, 6, 2, 7], rows[: 4 - args.deletes]), kinds=kinds, grow=args.grow)
     elif args.circuit == "merkle_read":    # four reads of six vectors, slot 2 twice, the vectors public: 1 + 2 m + m dim public values
         from halo2_vectordb_amd.pipeline import ReadHotPath
         hp = ReadHotPath(n=6, dim=4, m=4, k=12, tau=TAU, col_shard=shard, reads=[2, 5, 2, 0])
