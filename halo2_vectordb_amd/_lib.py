@@ -74,6 +74,10 @@ _SIGNATURES = {
     "vdb_wit_merkle_update_ops_dev": [_P, _SZ, _SZ, _U32, _P, _P, _P, _SZ, _P, _P, _P],
     "vdb_wit_merkle_open_size": [_SZ, _SZ, _SZ, _I, _P, _P],
     "vdb_wit_merkle_open": [_P, _SZ, _SZ, _P, _P, _SZ, _P, _P, _P], "vdb_wit_merkle_open_dev": [_P, _SZ, _SZ, _P, _P, _SZ, _P, _P, _P],
+    "vdb_ann_index_forest_size": [_P, _SZ, _SZ, _P, _P], "vdb_ann_index_build_dev": [_P, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],
+    "vdb_wit_ann_query_size": [_I, _U32, _U32, _SZ, _SZ, _SZ, _P, _P, _P],
+    "vdb_wit_ann_query": [_I, _U32, _U32, _P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _P],
+    "vdb_wit_ann_query_dev": [_I, _U32, _U32, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _P],
     "vdb_wit_nearest_batch_size": [_I, _U32, _U32, _SZ, _SZ, _SZ, _P, _P],
     "vdb_wit_nearest_batch": [_I, _U32, _U32, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],
     "vdb_wit_nearest_batch_dev": [_I, _U32, _U32, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],

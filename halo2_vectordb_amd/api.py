@@ -472,6 +472,62 @@ def wit_merkle_update(levels, n, new_vectors, indices, selectors=False, kinds=No
     return dict(stream=stream, **_split_flags(sel), input_cells=n_in.value, public=pub, levels=levels)
 
 
+def ann_forest_layout(cluster_ids, K):
+    """(digests of the forest of vdb_ann_index_build_dev, the K + 2 digest offsets at which its segments start): segment c < K is the tree
+    of cluster c, segment K the centroids' tree (vdb_ann_index_forest_size; VdbError on an id >= K, an empty cluster or K = 0)"""
+    lib = _lib.init()
+    ids = np.ascontiguousarray(cluster_ids, dtype=np.uint32)
+    digests, seg = _u64(), np.zeros(int(K) + 2, dtype=np.uint64)
+    check(lib.vdb_ann_index_forest_size(_p(ids), _sz(ids.size), _sz(K), ctypes.byref(digests), _p(seg)))
+    return digests.value, seg
+
+
+def ann_index_build(vectors, cluster_ids, centroids):
+    """the index of approximate-nearest-neighbour queries (vdb_ann_index_build_dev) over `vectors` (n, dim, 4), their cluster ids (n,) and
+    `centroids` (K, dim, 4), downloaded: dict(grouped (n, dim, 4), slots (n,), offsets (K + 1,), forest (digests, 4), segments (K + 2,),
+    roots (K + 2, 4): [centroids' root | cluster roots | index root])"""
+    lib = _lib.init()
+    vectors, centroids = _fr(vectors), _fr(centroids)
+    n, dim, K = vectors.shape[0], vectors.shape[1], centroids.shape[0]
+    ids = np.ascontiguousarray(cluster_ids, dtype=np.uint32)
+    assert ids.shape == (n,) and centroids.shape[1] == dim
+    digests, seg = ann_forest_layout(ids, K)
+    bufs = [DeviceBuffer(vectors.nbytes), DeviceBuffer(centroids.nbytes), DeviceBuffer(vectors.nbytes), DeviceBuffer(n * 4), DeviceBuffer((K + 1) * 8),
+            DeviceBuffer(digests * 32), DeviceBuffer((K + 2) * 32)]
+    try:
+        bufs[0].upload(vectors)
+        bufs[1].upload(centroids)
+        check(lib.vdb_ann_index_build_dev(bufs[0].ptr, _p(ids), bufs[1].ptr, _sz(n), _sz(K), _sz(dim), bufs[2].ptr, bufs[3].ptr, bufs[4].ptr, bufs[5].ptr,
+                                          bufs[6].ptr))
+        return dict(grouped=bufs[2].download((n, dim, 4)), slots=bufs[3].download((n,), dtype=np.uint32), offsets=bufs[4].download((K + 1,), dtype=np.uint64),
+                    forest=bufs[5].download((digests, 4)), segments=seg, roots=bufs[6].download((K + 2, 4)))
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def wit_ann_query(metric, query, centroids, members, cluster_roots, P=48, L=13, selectors=False):
+    """the circuit of one approximate-nearest-neighbour query (vdb_wit_ann_query) on query (dim, 4), centroids (K, dim, 4), the members of
+    the cluster searched (n_c, dim, 4) and the K cluster roots (K, 4): dict(stream, lookup, selectors, n_in, centroid_indicator (K, 4),
+    member_indicator (n_c, 4), result (dim, 4), index_root (4,), public (dim + 1, 4))"""
+    lib = _lib.init()
+    query, centroids, members, cluster_roots = _fr(query), _fr(centroids), _fr(members), _fr(cluster_roots)
+    K, dim, n_c = centroids.shape[0], centroids.shape[1], members.shape[0]
+    assert query.shape == (dim, 4) and members.shape[1] == dim and cluster_roots.shape == (K, 4)
+    cells, lk, n_in = _u64(), _u64(), _u64()
+    m = METRICS[metric]
+    check(lib.vdb_wit_ann_query_size(m, ctypes.c_uint32(P), ctypes.c_uint32(L), _sz(K), _sz(n_c), _sz(dim), ctypes.byref(cells), ctypes.byref(lk),
+                                     ctypes.byref(n_in)))
+    stream = np.zeros((cells.value, 4), dtype=np.uint64)
+    lookup = np.zeros((lk.value, 4), dtype=np.uint64)
+    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
+    ind_c, ind_m, pub = np.zeros((K, 4), dtype=np.uint64), np.zeros((n_c, 4), dtype=np.uint64), np.zeros((dim + 1, 4), dtype=np.uint64)
+    check(lib.vdb_wit_ann_query(m, ctypes.c_uint32(P), ctypes.c_uint32(L), _p(query), _p(centroids), _p(members), _p(cluster_roots), _sz(K), _sz(n_c),
+                                _sz(dim), _p(stream), _p(lookup), _p(sel) if selectors else None, _p(ind_c), _p(ind_m), _p(pub)))
+    return dict(stream=stream, lookup=lookup, **_split_flags(sel), n_in=n_in.value, centroid_indicator=ind_c, member_indicator=ind_m, result=pub[:dim],
+                index_root=pub[dim], public=pub)
+
+
 def wit_merkle_open(levels, n, indices, vectors=None, selectors=False):
     """m openings (vdb_wit_merkle_open) of the tree `levels` (merkle_tree_build's array over n vectors, or what a batch of updates left):
     slot indices[j] is read.  `vectors` (m, dim, 4): the vectors read (vector mode); None: leaf mode, any slot of the padded tree.
@@ -881,6 +937,18 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+class DeviceView(DeviceBuffer):
+    """`nbytes` of another DeviceBuffer's allocation from `offset` on: taken wherever a DeviceBuffer is read, owns nothing (free() is a
+    no-op; the view is valid as long as its owner's allocation)"""
+
+    def __init__(self, owner, offset, nbytes):
+        assert 0 <= int(offset) and int(offset) + int(nbytes) <= owner.nbytes
+        self.L, self.owner, self.nbytes, self.ptr = owner.L, owner, int(nbytes), owner.at(offset)
+
+    def free(self):
+        self.ptr = None
 
 
 def mem_info():

@@ -725,61 +725,83 @@ def _distance_block(metric, dim, P, L):
     return Block(s, [out])
 
 
-def build_nearest_topk(metric, q, n, dim, topk, P, L, builder=None, extra_cells=0, finish=True):
-    """q x Sym.nearest_topk(query_i, vectors, topk) after [queries | vectors] have been assigned (tests/vectordb/mod.rs:220-247 assigns
-    the query, then the vectors), in the stream order of witness.hip (wit_nearest_dev): the map the whole-circuit trace gives, assembled
-    from one block per gadget.  Query i's block is its n distances, then per round n - 1 qmin, n is_equal, dim select_by_indicator and —
-    before every round but the first — the n select(Constant(M), cur, ind) of the round before; the lookup cells are the distance runs,
-    then the qmin runs round by round.  M is a constant of the map (a fixed-column value), tied to the cell that holds it in every
-    select.  Outputs (indicators (q, topk, n), results (q, topk, dim)).  `extra_cells`: room for a gadget that follows in the same stream
-    (the query circuits' merkle_commitment); with finish=False the builder itself is returned, (builder, outputs, cells used so far), for
-    the caller to go on placing."""
+def nearest_units(metric, n, dim, topk, P, L):
+    """the unit blocks of Sym.nearest_topk over n vectors of `dim` words and where its stages lie: dict(db, qm, ie, sb, mk: the blocks of
+    one distance, qmin, is_equal, select_by_indicator over n cells, select(Constant(M), ..); rounds_off / rounds_loff: where round 0 starts
+    in a query's block; iseq_off, sel_off, mask_off: the stages of a round after its qmin chain; per_r / per_r_l, per_q / per_q_l: cells
+    and lookup cells of a round that masks and of a query's block)"""
     if not 1 <= topk <= n:
         raise ValueError("topk must be at least 1 and at most n")
-    db = _distance_block(metric, dim, P, L)
+    u = dict(n=n, dim=dim, topk=topk, db=_distance_block(metric, dim, P, L))
     s = Sym(P, L)
-    qm = Block(s, [s.qmin(ext(0), ext(1))])
+    u["qm"] = Block(s, [s.qmin(ext(0), ext(1))])
     s = Sym(P, L)
-    ie = Block(s, [s.g_is_equal(ext(0), ext(1))])
+    u["ie"] = Block(s, [s.g_is_equal(ext(0), ext(1))])
     s = Sym(P, L)
-    sb = Block(s, [s.g_select_by_indicator([ext(k) for k in range(n)], [ext(n + k) for k in range(n)])])
+    u["sb"] = Block(s, [s.g_select_by_indicator([ext(k) for k in range(n)], [ext(n + k) for k in range(n)])])
     s = Sym(P, L)
-    mk = Block(s, [s.g_select(C((1 << (2 * P)) - 1), ext(0), ext(1))])
-    n_in = (q + n) * dim
-    rounds_off, rounds_loff = n * db.n, n * db.n_lk
-    iseq_off = (n - 1) * qm.n
-    sel_off = iseq_off + ie.n * n
-    mask_off = sel_off + dim * sb.n
-    per_r, per_r_l = mask_off + mk.n * n, (n - 1) * qm.n_lk
-    per_q, per_q_l = rounds_off + topk * per_r - mk.n * n, rounds_loff + topk * per_r_l
-    total = n_in + q * per_q
-    B = (builder or _Builder)(total + extra_cells, q * per_q_l)
-    queries = np.arange(q * dim, dtype=np.int64).reshape(q, dim)
-    vec = q * dim + np.arange(n * dim, dtype=np.int64).reshape(n, dim)
+    u["mk"] = Block(s, [s.g_select(C((1 << (2 * P)) - 1), ext(0), ext(1))])
+    u["rounds_off"], u["rounds_loff"] = n * u["db"].n, n * u["db"].n_lk
+    u["iseq_off"] = (n - 1) * u["qm"].n
+    u["sel_off"] = u["iseq_off"] + u["ie"].n * n
+    u["mask_off"] = u["sel_off"] + dim * u["sb"].n
+    u["per_r"], u["per_r_l"] = u["mask_off"] + u["mk"].n * n, (n - 1) * u["qm"].n_lk
+    u["per_q"], u["per_q_l"] = u["rounds_off"] + topk * u["per_r"] - u["mk"].n * n, u["rounds_loff"] + topk * u["per_r_l"]
+    return u
+
+
+def place_nearest(B, u, queries, vec, base, lbase):
+    """q x Sym.nearest_topk(query_i, vectors, topk) placed into builder `B`: `u`: nearest_units of the shape; `queries` (q, dim) / `vec`
+    (n, dim): the stream cells of the queries' and the vectors' words; query i's block starts at stream cell base + i per_q, its lookup cells
+    at lbase + i per_q_l, in the stream order of witness.hip (nv_emit).  -> (indicators (q, topk, n), results (q, topk, dim))"""
+    n, dim, topk = u["n"], u["dim"], u["topk"]
+    db, qm, ie, sb, mk = u["db"], u["qm"], u["ie"], u["sb"], u["mk"]
+    per_q, per_q_l, per_r, per_r_l = u["per_q"], u["per_q_l"], u["per_r"], u["per_r_l"]
+    iseq_off, sel_off, mask_off = u["iseq_off"], u["sel_off"], u["mask_off"]
+    queries, vec = np.asarray(queries, dtype=np.int64).reshape(-1, dim), np.asarray(vec, dtype=np.int64).reshape(n, dim)
+    q = queries.shape[0]
     qq, ii = np.repeat(np.arange(q, dtype=np.int64), n), np.tile(np.arange(n, dtype=np.int64), q)
-    base, lbase = n_in + qq * per_q, qq * per_q_l
-    cur = B.place(db, base + ii * db.n, lbase + ii * db.n_lk, np.concatenate([vec[ii], queries[qq]], axis=1))[:, 0].reshape(q, n)
+    bq, lbq = base + qq * per_q, lbase + qq * per_q_l
+    cur = B.place(db, bq + ii * db.n, lbq + ii * db.n_lk, np.concatenate([vec[ii], queries[qq]], axis=1))[:, 0].reshape(q, n)
     qj, j = np.repeat(np.arange(q, dtype=np.int64), n - 1), np.tile(np.arange(n - 1, dtype=np.int64), q)
     qd, jd = np.repeat(np.arange(q, dtype=np.int64), dim), np.tile(np.arange(dim, dtype=np.int64), q)
     inds, ress = [], []
     for r in range(topk):
-        rbase, rlbase = rounds_off + r * per_r, rounds_loff + r * per_r_l
+        rbase, rlbase = u["rounds_off"] + r * per_r, u["rounds_loff"] + r * per_r_l
         acc = np.empty((q, n), dtype=np.int64)
         acc[:, 0] = cur[:, 0]
         if n > 1:
-            bases = n_in + qj * per_q + rbase + j * qm.n
+            bases = base + qj * per_q + rbase + j * qm.n
             acc[:, 1:] = (bases + qm.outs[0]).reshape(q, n - 1)
-            B.place(qm, bases, qj * per_q_l + rlbase + j * qm.n_lk, np.stack([acc[:, :-1].reshape(-1), cur[:, 1:].reshape(-1)], axis=1))
-        ind = B.place(ie, base + rbase + iseq_off + ie.n * ii, np.zeros(q * n, dtype=np.int64),
+            B.place(qm, bases, lbase + qj * per_q_l + rlbase + j * qm.n_lk, np.stack([acc[:, :-1].reshape(-1), cur[:, 1:].reshape(-1)], axis=1))
+        ind = B.place(ie, bq + rbase + iseq_off + ie.n * ii, np.zeros(q * n, dtype=np.int64),
                       np.stack([acc[qq, n - 1], cur.reshape(-1)], axis=1))[:, 0].reshape(q, n)
-        res = B.place(sb, n_in + qd * per_q + rbase + sel_off + jd * sb.n, np.zeros(q * dim, dtype=np.int64),
+        res = B.place(sb, base + qd * per_q + rbase + sel_off + jd * sb.n, np.zeros(q * dim, dtype=np.int64),
                       np.concatenate([vec.T[jd], ind[qd]], axis=1))[:, 0].reshape(q, dim)
         inds.append(ind)
         ress.append(res)
         if r + 1 < topk:
-            cur = B.place(mk, base + rbase + mask_off + mk.n * ii, np.zeros(q * n, dtype=np.int64),
+            cur = B.place(mk, bq + rbase + mask_off + mk.n * ii, np.zeros(q * n, dtype=np.int64),
                           np.stack([cur.reshape(-1), ind.reshape(-1)], axis=1))[:, 0].reshape(q, n)
-    outs = (np.stack(inds, axis=1), np.stack(ress, axis=1))
+    return np.stack(inds, axis=1), np.stack(ress, axis=1)
+
+
+def build_nearest_topk(metric, q, n, dim, topk, P, L, builder=None, extra_cells=0, finish=True):
+    """q x Sym.nearest_topk(query_i, vectors, topk) after [queries | vectors] have been assigned (tests/vectordb/mod.rs:220-247 assigns
+    the query, then the vectors), in the stream order of witness.hip (wit_nearest_dev): the map the whole-circuit trace gives, assembled
+    from one block per gadget (place_nearest).  Query i's block is its n distances, then per round n - 1 qmin, n is_equal, dim
+    select_by_indicator and — before every round but the first — the n select(Constant(M), cur, ind) of the round before; the lookup cells
+    are the distance runs, then the qmin runs round by round.  M is a constant of the map (a fixed-column value), tied to the cell that
+    holds it in every select.  Outputs (indicators (q, topk, n), results (q, topk, dim)).  `extra_cells`: room for a gadget that follows
+    in the same stream (the query circuits' merkle_commitment); with finish=False the builder itself is returned, (builder, outputs, cells
+    used so far), for the caller to go on placing."""
+    u = nearest_units(metric, n, dim, topk, P, L)
+    n_in = (q + n) * dim
+    total = n_in + q * u["per_q"]
+    B = (builder or _Builder)(total + extra_cells, q * u["per_q_l"])
+    queries = np.arange(q * dim, dtype=np.int64).reshape(q, dim)
+    vec = q * dim + np.arange(n * dim, dtype=np.int64).reshape(n, dim)
+    outs = place_nearest(B, u, queries, vec, n_in, 0)
     if not finish:
         return B, outs, total
     return B.finish(), outs
@@ -928,12 +950,13 @@ def _perm_placer(B, fetch_flags, fetch_values):
     return perm
 
 
-def place_merkle(B, n, dim, base, vec_base, fetch_flags, fetch_values):
+def place_merkle(B, n, dim, base, vec_base, fetch_flags, fetch_values, zero_cell=None):
     """merkle_commitment over n vectors of `dim` words whose trace starts at stream cell `base`, placed into builder `B` in the cell
     order of witness.hip: the leaves' sponges, the load_zero cell of the padding, the tree.  `vec_base`: stream cell of word 0 of
     vector 0 (the assigned vectors the leaves absorb; None: free words).  fetch_flags(lo, hi) / fetch_values(lo, hi): the kernel's
     flag bytes / the canonical values of stream cells [lo, hi) of a keygen-style run (one instance of each kind of permutation is
-    read).  -> (stream cell of the root, first cell after the trace)"""
+    read).  `zero_cell`: the cell an earlier ctx.load_zero() of the same circuit made (Context::load_zero caches it): the padding then
+    copies that cell and the trace has none of its own.  -> (stream cell of the root, first cell after the trace)"""
     lay = merkle_leaf_layout(dim)
     perm = _perm_placer(B, fetch_flags, fetch_values)
     v = np.arange(n, dtype=np.int64)
@@ -942,9 +965,9 @@ def place_merkle(B, n, dim, base, vec_base, fetch_flags, fetch_values):
         state = perm(at, n_in, state, None if vec_base is None else [vec_base + v * dim + 2 * p + i for i in range(n_in)])
         at = at + lay["sizes"][p]
     lp, pos = 1 << (n - 1).bit_length(), base + n * lay["leaf_cells"]
-    digest = np.full(lp, pos, dtype=np.int64)                # the padding leaves: the zero cell that follows the leaves
+    digest = np.full(lp, pos if zero_cell is None else zero_cell, dtype=np.int64)   # the padding leaves: the zero cell that follows the leaves
     digest[:n] = state[1]
-    if lp > n:
+    if lp > n and zero_cell is None:
         B.constant_cell(pos, 0)                              # ctx.load_zero()
         pos += 1
     while digest.size > 1:
@@ -971,6 +994,78 @@ def build_merkle(n, dim, fetch_flags, fetch_values, builder=None):
     if end != total:
         raise ValueError("the trace does not end where the circuit does")
     return B.finish(), root
+
+
+def merkle_cells(n, dim, zero_cached=False):
+    """cells of merkle_commitment over n vectors of `dim` words (vdb_wit_merkle_size)"""
+    lay, lp = merkle_leaf_layout(dim), 1 << (n - 1).bit_length()
+    return n * lay["leaf_cells"] + (1 if lp > n and not zero_cached else 0) + (lp - 1) * lay["node_cells"]
+
+
+def place_sponge(B, base, words, fetch_flags, fetch_values):
+    """poseidon.clear(); update(words); squeeze() over the stream cells `words` — merkle_commitment's leaf hash of one vector — placed
+    into builder `B` from stream cell `base` on.  -> (stream cell of the digest, first cell after the trace)"""
+    lay = merkle_leaf_layout(len(words))
+    perm = _perm_placer(B, fetch_flags, fetch_values)
+    state, at = None, np.asarray([base], dtype=np.int64)
+    for p, n_in in enumerate(lay["n_ins"]):
+        state = perm(at, n_in, state, [np.asarray([words[2 * p + i]], dtype=np.int64) for i in range(n_in)])
+        at = at + lay["sizes"][p]
+    return int(state[1][0]), int(at[0])
+
+
+def ann_query_layout(metric, K, n_c, dim, P, L):
+    """where the blocks of the approximate-nearest-neighbour query circuit start (include/vdb.h vdb_wit_ann_query): dict(query, centroids,
+    members, roots: the assigned inputs; n_in; nearest_c, merkle_c, nearest_m, merkle_m, select, sponge: the blocks; total; lk_m: the
+    first lookup cell of the second search; total_l; units_c, units_m: nearest_units of the two searches; zero_c: the centroids' padding
+    loads the zero cell)"""
+    uc, um = nearest_units(metric, K, dim, 1, P, L), nearest_units(metric, n_c, dim, 1, P, L)
+    zero_c = (1 << (K - 1).bit_length()) > K
+    lay = dict(query=0, centroids=dim, members=dim + K * dim, roots=dim + K * dim + n_c * dim, units_c=uc, units_m=um, zero_c=zero_c)
+    lay["n_in"] = lay["nearest_c"] = lay["roots"] + K
+    lay["merkle_c"] = lay["nearest_c"] + uc["per_q"]
+    lay["nearest_m"] = lay["merkle_c"] + merkle_cells(K, dim)
+    lay["merkle_m"] = lay["nearest_m"] + um["per_q"]
+    lay["select"] = lay["merkle_m"] + merkle_cells(n_c, dim, zero_c)
+    lay["sponge"] = lay["select"] + 1 + 3 * K
+    lay["total"] = lay["sponge"] + merkle_leaf_layout(K + 1)["leaf_cells"]
+    lay["lk_m"], lay["total_l"] = uc["per_q_l"], uc["per_q_l"] + um["per_q_l"]
+    return lay
+
+
+def build_ann_query(metric, K, n_c, dim, P, L, fetch_flags, fetch_values, builder=None):
+    """The approximate-nearest-neighbour query against a committed index in one circuit (pipeline.AnnQueryHotPath): [query | centroids |
+    members | cluster roots] assigned, then nearest_vector(query, centroids), merkle_commitment(centroids), nearest_vector(query, members),
+    merkle_commitment(members), select_by_indicator(cluster roots, centroid indicator), whose output is TIED to the members' root — the
+    cluster searched is the winning centroid's — and the sponge over [centroids' root | cluster roots].  fetch_flags / fetch_values: as
+    place_merkle.  -> (CopyMap, public cells: the dim result cells then the index root, dict(centroid_indicator, member_indicator, result,
+    centroids_root, members_root, selected, index_root, layout))"""
+    if K < 1 or n_c < 1 or dim < 1:
+        raise ValueError("at least one centroid, one member and one word")
+    lay = ann_query_layout(metric, K, n_c, dim, P, L)
+    if np.asarray(fetch_flags(0, lay["n_in"])).any():
+        raise ValueError("the assigned inputs carry no gate or constant flag")
+    B = (builder or _Builder)(lay["total"], lay["total_l"])
+    query = np.arange(dim, dtype=np.int64).reshape(1, dim)
+    cent = lay["centroids"] + np.arange(K * dim, dtype=np.int64).reshape(K, dim)
+    mem = lay["members"] + np.arange(n_c * dim, dtype=np.int64).reshape(n_c, dim)
+    roots = lay["roots"] + np.arange(K, dtype=np.int64)
+    ind_c, _ = place_nearest(B, lay["units_c"], query, cent, lay["nearest_c"], 0)
+    croot, end = place_merkle(B, K, dim, lay["merkle_c"], lay["centroids"], fetch_flags, fetch_values)
+    assert end == lay["nearest_m"]
+    ind_m, res = place_nearest(B, lay["units_m"], query, mem, lay["nearest_m"], lay["lk_m"])
+    zero = lay["merkle_c"] + K * merkle_leaf_layout(dim)["leaf_cells"] if lay["zero_c"] else None
+    mroot, end = place_merkle(B, n_c, dim, lay["merkle_m"], lay["members"], fetch_flags, fetch_values, zero_cell=zero)
+    assert end == lay["select"]
+    ind_c, ind_m, res = ind_c.reshape(K), ind_m.reshape(n_c), res.reshape(dim)
+    sel = int(B.place(lay["units_c"]["sb"], [lay["select"]], [0], np.concatenate([roots, ind_c])[None, :])[0, 0])
+    B.tie(sel, mroot)                                        # constrain_equal(sel, mroot)
+    index_root, end = place_sponge(B, lay["sponge"], [croot] + [int(c) for c in roots], fetch_flags, fetch_values)
+    if end != lay["total"]:
+        raise ValueError("the trace does not end where the circuit does")
+    public = [int(c) for c in res] + [index_root]
+    return B.finish(), public, dict(centroid_indicator=ind_c, member_indicator=ind_m, result=res, centroids_root=croot, members_root=mroot, selected=sel,
+                                    index_root=index_root, layout=lay)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -5,7 +5,10 @@
 // run as independent threads; long sequential gadgets are cut into position windows, one window per
 // wavefront of 64 instances.  The stream is written once (32 B per cell: the HBM-write roofline of
 // this stage) and read once by the layout kernel.
+#include <algorithm>
 #include <cmath>
+#include <cstring>
+#include <vector>
 
 #include "common.hpp"
 #include "gadgets.hpp"
@@ -911,7 +914,7 @@ __global__ __launch_bounds__(64) void k_km_div(Streams st, const FpTables* __res
   }
 }
 __global__ void k_push_cells(Streams st, uint64_t pos, u256 a, u256 b, uint32_t n) {
-  if (blockIdx.x || threadIdx.x) return;
+  if (blockIdx.x || threadIdx.x || n == 0) return;
   // load_constant / load_zero cells: data-independent; stored by the rank whose window holds them, like every other cell
   if (pos >= st.rlo && pos < st.rhi) {
     st.adv[pos] = a;
@@ -1593,6 +1596,31 @@ static uint32_t nv_select_segments(size_t QT, size_t n, size_t dim) {
 // Q x [n distances, then topk rounds of qmin chain / is_equal / select_by_indicator / mask], block q at q * (cells of one):
 // one run_distances over Q x n instances (instance t = q * n + i is distance(vector_i, query_q)), one value kernel that runs every
 // round of every query, and one launch per emitting stage — the launch count depends on neither Q nor topk
+// (the blocks alone, Q of them from stream cell `base` / lookup cell `lbase` on: the caller has attached the inversion list and published
+//  the call's context.  `fixed_launches`: the qmin chain is launched at n = 1 too, where it has no lane, so that a caller's launch count
+//  does not depend on n)
+static int nv_emit(FpEntry* fp, const DistLayout& dl, const NvLayout& nl, const u256* queries, const u256* vectors, size_t Q, size_t n, size_t dim,
+                   size_t topk, const Streams& st, uint64_t base, uint64_t lbase, bool fixed_launches, u256* ind, u256* result) {
+  const size_t inst = Q * n, rinst = inst * topk;
+  InstMap im{base, lbase, (uint32_t)n, nl.total, nl.total_l, (uint32_t)n, (uint32_t)n};  // (vector_{t % n}, query_{t / n})
+  u256* mid = (u256*)scratch_get(0, (inst * 4 + rinst + 8) * sizeof(u256) + inst * sizeof(uint32_t));
+  if (!mid) return VDB_ERR_OOM;
+  u256* dist = mid + 3 * inst;
+  u256* pm = dist + inst;
+  uint32_t* rnd = (uint32_t*)(pm + rinst + 8);
+  TRY(run_distances(st, fp, dl, im, (uint32_t)inst, vectors, queries, mid, dist));
+  const NvMap nm{base, lbase, nl.total, nl.total_l, nl.dist, nl.dist_l, nl.per_r, nl.qmin_l, nl.qmin, nl.qmin + nl.iseq,
+                 nl.qmin + nl.iseq + nl.sel, (uint32_t)Q, (uint32_t)n, (uint32_t)dim, (uint32_t)topk};
+  VDB_LAUNCH(k_nv_rounds, dim3((unsigned)Q), dim3(64), fp->dev, dist, (uint32_t)n, (uint32_t)topk, pm, rnd);
+  if (n > 1 || fixed_launches)
+    VDB_LAUNCH(k_nv_qmin, dim3((unsigned)((Q * topk * (n - 1) + 63) / 64 + (n == 1))), dim3(64), st, fp->dev, nm, dist, pm, rnd);
+  VDB_LAUNCH(k_nv_is_equal, dim3((unsigned)((rinst + 63) / 64)), dim3(64), st, fp->dev, nm, dist, pm, rnd, ind);
+  // launched for topk == 1 too (one wavefront that finds no lane of its own): the launch count of a call does not depend on topk
+  VDB_LAUNCH(k_nv_mask, dim3((unsigned)((inst * (topk - 1) + 63) / 64 + (topk == 1))), dim3(64), st, fp->dev, nm, dist, rnd, ind);
+  const uint32_t S = nv_select_segments(Q * topk, n, dim);
+  VDB_LAUNCH(k_nv_select, dim3((unsigned)((Q * topk * dim * S + 63) / 64)), dim3(64), st, fp->dev, nm, S, vectors, ind, result);
+  return VDB_OK;
+}
 int wit_nearest_dev(FpEntry* fp, int metric, const u256* queries, const u256* vectors, size_t Q, size_t n, size_t dim, size_t topk, Streams st,
                     u256* ind, u256* result) {
   DistLayout dl;
@@ -1601,23 +1629,7 @@ int wit_nearest_dev(FpEntry* fp, int metric, const u256* queries, const u256* ve
   TRY(nv_fits(Q, n, dim, topk, nl));
   TRY(inv_list_attach(st, Q * nl.total));
   TRY(set_winv(st, fp->dev));
-  const size_t inst = Q * n, rinst = inst * topk;
-  InstMap im{0, 0, (uint32_t)n, nl.total, nl.total_l, (uint32_t)n, (uint32_t)n};  // (vector_{t % n}, query_{t / n})
-  u256* mid = (u256*)scratch_get(0, (inst * 4 + rinst + 8) * sizeof(u256) + inst * sizeof(uint32_t));
-  if (!mid) return VDB_ERR_OOM;
-  u256* dist = mid + 3 * inst;
-  u256* pm = dist + inst;
-  uint32_t* rnd = (uint32_t*)(pm + rinst + 8);
-  TRY(run_distances(st, fp, dl, im, (uint32_t)inst, vectors, queries, mid, dist));
-  const NvMap nm{0, 0, nl.total, nl.total_l, nl.dist, nl.dist_l, nl.per_r, nl.qmin_l, nl.qmin, nl.qmin + nl.iseq,
-                 nl.qmin + nl.iseq + nl.sel, (uint32_t)Q, (uint32_t)n, (uint32_t)dim, (uint32_t)topk};
-  VDB_LAUNCH(k_nv_rounds, dim3((unsigned)Q), dim3(64), fp->dev, dist, (uint32_t)n, (uint32_t)topk, pm, rnd);
-  if (n > 1) VDB_LAUNCH(k_nv_qmin, dim3((unsigned)((Q * topk * (n - 1) + 63) / 64)), dim3(64), st, fp->dev, nm, dist, pm, rnd);
-  VDB_LAUNCH(k_nv_is_equal, dim3((unsigned)((rinst + 63) / 64)), dim3(64), st, fp->dev, nm, dist, pm, rnd, ind);
-  // launched for topk == 1 too (one wavefront that finds no lane of its own): the launch count of a call does not depend on topk
-  VDB_LAUNCH(k_nv_mask, dim3((unsigned)((inst * (topk - 1) + 63) / 64 + (topk == 1))), dim3(64), st, fp->dev, nm, dist, rnd, ind);
-  const uint32_t S = nv_select_segments(Q * topk, n, dim);
-  VDB_LAUNCH(k_nv_select, dim3((unsigned)((Q * topk * dim * S + 63) / 64)), dim3(64), st, fp->dev, nm, S, vectors, ind, result);
+  TRY(nv_emit(fp, dl, nl, queries, vectors, Q, n, dim, topk, st, 0, 0, false, ind, result));
   return inv_list_fixup(st);
 }
 
@@ -1709,6 +1721,33 @@ static int mk_tree_values(const PoseidonSpec* sp, const u256* vectors, size_t n,
   *root_off = off;
   return VDB_OK;
 }
+// merkle_commitment's cells from stream cell `base` on (the caller has published the call's context).  `resident`: the tree's digests
+// where they already lie on the device (vdb_merkle_tree_build_dev's layout, only read) — then only the leaves' sponge states are computed,
+// and the launch count does not depend on n (the zero cell and the tree trace are launched where they have nothing to store, too);
+// null: the digests are computed here, a launch per level
+static int mk_emit(FpEntry* fp, const PoseidonSpec* sp, const u256* vectors, size_t n, size_t dim, const MkLayout& ml, const Streams& st, uint64_t base,
+                   const u256* resident, u256* root_out) {
+  const uint64_t lp = ml.n_leaves_pow2;
+  u256* states = (u256*)scratch_get(0, (n * ml.nperm * PSD_T + 2 * lp + 8) * sizeof(u256));
+  if (!states) return VDB_ERR_OOM;
+  u256* levels = states + n * ml.nperm * PSD_T;
+  uint64_t root_off = 2 * lp - 2;
+  if (resident)  // (the leaf digests the kernel writes beside the states are the resident ones again)
+    VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((n + 63) / 64)), dim3(64), sp, vectors, (uint32_t)n, (uint32_t)dim, ml.nperm, states, levels, nullptr);
+  else
+    TRY(mk_tree_values(sp, vectors, n, dim, ml, states, levels, &root_off));
+  const u256* lv = resident ? resident : levels;
+  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((n * ml.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, vectors, (uint32_t)n, (uint32_t)dim, ml.nperm, base,
+             ml.leaf_cells, states, nullptr);
+  if (ml.zero_cell || resident)
+    VDB_LAUNCH(k_push_cells, dim3(1), dim3(1), st, base + ml.leaves, u256_zero(), u256_zero(), ml.zero_cell ? 1u : 0u);
+  // every node's two permutations in one launch (a tree of one leaf has no node: its root is the leaf digest)
+  if (lp > 1 || resident)
+    VDB_LAUNCH(k_mk_tree_trace, dim3((unsigned)((2 * (lp - 1) + 63) / 64 + (lp == 1))), dim3(64), st, fp->dev, sp, lv, (uint32_t)lp,
+               base + ml.leaves + ml.zero_cell);
+  if (root_out) VDB_HIP(hipMemcpyAsync(root_out, lv + root_off, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
+  return VDB_OK;
+}
 int wit_merkle_dev(const u256* vectors, size_t n, size_t dim, int zero_cached, Streams st, u256* root_out) {
   VDB_ARG(n <= ((size_t)1 << 30), "tree deeper than 30 levels");
   FpEntry* fp;
@@ -1718,20 +1757,7 @@ int wit_merkle_dev(const u256* vectors, size_t n, size_t dim, int zero_cached, S
   TRY(poseidon_spec_dev(&sp, nullptr));
   MkLayout ml;
   mk_layout(n, dim, zero_cached, &ml);
-  const uint64_t lp = ml.n_leaves_pow2;
-  u256* states = (u256*)scratch_get(0, (n * ml.nperm * PSD_T + 2 * lp + 8) * sizeof(u256));
-  if (!states) return VDB_ERR_OOM;
-  u256* levels = states + n * ml.nperm * PSD_T;
-  uint64_t root_off;
-  TRY(mk_tree_values(sp, vectors, n, dim, ml, states, levels, &root_off));
-  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((n * ml.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, vectors, (uint32_t)n, (uint32_t)dim, ml.nperm, 0,
-             ml.leaf_cells, states, nullptr);
-  if (ml.zero_cell) VDB_LAUNCH(k_push_cells, dim3(1), dim3(1), st, ml.leaves, u256_zero(), u256_zero(), 1u);
-  // every node's two permutations in one launch (a tree of one leaf has no node: its root is the leaf digest)
-  if (lp > 1)
-    VDB_LAUNCH(k_mk_tree_trace, dim3((unsigned)((2 * (lp - 1) + 63) / 64)), dim3(64), st, fp->dev, sp, levels, (uint32_t)lp, ml.leaves + ml.zero_cell);
-  VDB_HIP(hipMemcpyAsync(root_out, levels + root_off, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
-  return VDB_OK;
+  return mk_emit(fp, sp, vectors, n, dim, ml, st, 0, nullptr, root_out);
 }
 
 // the resident tree of the path updates: mk_tree_values into the caller's buffer
@@ -1958,6 +1984,233 @@ int wit_merkle_open_dev(const u256* levels, size_t n, size_t dim, const u256* ve
   VDB_LAUNCH(k_mko_level_trace, dim3((unsigned)(((uint64_t)m * depth + 63) / 64), 3), dim3(64), st, fp->dev, sp, ml, 0, lp, didx, levels);
   VDB_LAUNCH(k_mko_index, dim3((unsigned)((m + 63) / 64)), dim3(64), st, fp->dev, ml, 0, lp, didx, levels, vectors, vleaf, pub);
   return VDB_OK;
+}
+
+// ------------------------------------------------------------------ the index of an approximate-nearest-neighbour query (include/vdb.h
+// vdb_ann_index_build_dev, vdb_wit_ann_query).  The index commits to K centroids and to the database grouped by cluster:
+// index_root = sponge over [merkle_commitment(centroids), merkle_commitment(members(0)), ..., merkle_commitment(members(K - 1))].
+// The K + 1 trees lie one after the other in a forest, segment s = 2 lp_s digests in mk_tree_values' layout (segment K: the centroids'),
+// and are hashed level by level by ONE launch per level over all segments.
+struct AnnForest {
+  std::vector<uint64_t> seg_off;   // K + 2: where segment s starts in the forest, in digests
+  std::vector<uint32_t> seg_lp;    // K + 1
+  std::vector<uint32_t> prefix;    // depth x (K + 2): nodes of level l + 1 in the segments before s
+  uint32_t depth = 0;
+};
+static int ann_forest_plan(const uint32_t* ids, size_t n, size_t K, AnnForest* f) {
+  VDB_ARG(ids && n > 0 && K > 0, "null pointer, empty database or K = 0");
+  VDB_ARG(n <= VDB_ANN_MAX_VECTORS && K <= VDB_ANN_MAX_CLUSTERS, "index too large: n at most 2^24, K at most 4096 (include/vdb.h)");
+  std::vector<uint64_t> cnt(K, 0);
+  for (size_t i = 0; i < n; i++) {
+    VDB_ARG(ids[i] < K, "cluster id >= K");
+    cnt[ids[i]]++;
+  }
+  f->seg_off.assign(K + 2, 0);
+  f->seg_lp.assign(K + 1, 1);
+  f->depth = 0;
+  for (size_t s = 0; s <= K; s++) {
+    const uint64_t m = s < K ? cnt[s] : K;
+    VDB_ARG(m > 0, "empty cluster: merkle_commitment is undefined over zero vectors");
+    uint64_t lp = 1;
+    uint32_t d = 0;
+    while (lp < m) lp <<= 1, d++;
+    f->seg_lp[s] = (uint32_t)lp;
+    f->seg_off[s + 1] = f->seg_off[s] + 2 * lp;
+    if (d > f->depth) f->depth = d;
+  }
+  f->prefix.assign((size_t)f->depth * (K + 2), 0);
+  for (uint32_t l = 0; l < f->depth; l++)
+    for (size_t s = 0; s <= K; s++) f->prefix[(size_t)l * (K + 2) + s + 1] = f->prefix[(size_t)l * (K + 2) + s] + (f->seg_lp[s] >> (l + 1));
+  return VDB_OK;
+}
+// Stable grouping of the rows by cluster id, one wavefront: 64 rows at a time, a row's rank = the rows of its cluster in the tiles before
+// (counts in LDS) + the lower lanes of its tile with the same id.  Then the K + 1 offsets (a serial prefix sum by lane 0), and per row
+// its place among the grouped rows, the database slot that place holds and where its leaf digest goes in the forest.
+__global__ __launch_bounds__(64) void k_ann_group(const uint32_t* __restrict__ ids, uint32_t n, uint32_t K, const uint64_t* __restrict__ seg_off,
+                                                   uint64_t* __restrict__ offsets, uint32_t* __restrict__ rank, uint32_t* __restrict__ slots,
+                                                   uint32_t* __restrict__ leaf_at) {
+  __shared__ uint32_t cnt[VDB_ANN_MAX_CLUSTERS];
+  const uint32_t lane = threadIdx.x;
+  for (uint32_t c = lane; c < K; c += 64) cnt[c] = 0;
+  __syncthreads();
+  for (uint32_t c0 = 0; c0 < n; c0 += 64) {
+    const uint32_t i = c0 + lane;
+    const bool live = i < n;
+    const uint32_t id = live ? ids[i] : 0xffffffffu;
+    uint32_t lower = 0, r = 0;
+    bool last = true;
+    for (int l = 0; l < 64; l++) {
+      const uint32_t o = (uint32_t)__shfl((int)id, l);
+      if (o == id) {
+        if (l < (int)lane) lower++;
+        if (l > (int)lane) last = false;
+      }
+    }
+    if (live) {
+      r = cnt[id] + lower;
+      rank[i] = r;
+    }
+    __syncthreads();
+    if (live && last) cnt[id] = r + 1;
+    __syncthreads();
+  }
+  if (lane == 0) {
+    uint32_t acc = 0;
+    for (uint32_t c = 0; c < K; c++) {
+      const uint32_t m = cnt[c];
+      offsets[c] = acc;
+      cnt[c] = acc;
+      acc += m;
+    }
+    offsets[K] = acc;
+  }
+  __syncthreads();
+  for (uint32_t i = lane; i < n; i += 64) {
+    const uint32_t id = ids[i], r = rank[i], pos = cnt[id] + r;
+    slots[pos] = i;
+    leaf_at[pos] = (uint32_t)seg_off[id] + r;
+  }
+}
+// the rows in grouped order, a lane per word
+__global__ __launch_bounds__(256) void k_ann_gather(const u256* __restrict__ db, const uint32_t* __restrict__ slots, uint64_t n, uint32_t D,
+                                                    u256* __restrict__ grouped) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= n * D) return;
+  grouped[t] = db[(uint64_t)slots[t / D] * D + t % D];
+}
+// level l + 1 of every tree of the forest from its level l: a lane per (segment, node), the segment found in the prefix sums of the
+// level's node counts (a segment shallower than the level has no node and no lane)
+__global__ __launch_bounds__(64) void k_ann_forest_level(const PoseidonSpec* __restrict__ sp, u256* __restrict__ forest, const uint64_t* __restrict__ seg_off,
+                                                          const uint32_t* __restrict__ seg_lp, const uint32_t* __restrict__ prefix, uint32_t n_seg,
+                                                          uint32_t l) {
+  const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= prefix[n_seg]) return;
+  uint32_t lo = 0, hi = n_seg;   // the last segment s with prefix[s] <= t (segments without a node share their successor's prefix)
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (prefix[mid] <= t) lo = mid; else hi = mid;
+  }
+  const uint32_t node = t - prefix[lo];
+  const uint64_t lp = seg_lp[lo];
+  const u256* in_lv = forest + seg_off[lo] + mku_level_off(lp, l);
+  u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
+  u256 in[PSD_RATE] = {in_lv[2 * node], in_lv[2 * node + 1]};
+  psd_permute_absorb(sp, st, in, 2);
+  psd_permute_absorb(sp, st, in, 0);
+  forest[seg_off[lo] + mku_level_off(lp, l + 1) + node] = st[1];
+}
+// [centroids' root | the K cluster roots]: the words the index root is the sponge of
+__global__ __launch_bounds__(64) void k_ann_roots(const u256* __restrict__ forest, const uint64_t* __restrict__ seg_off, const uint32_t* __restrict__ seg_lp,
+                                                   uint32_t K, u256* __restrict__ roots) {
+  const uint32_t s = blockIdx.x * 64 + threadIdx.x;
+  if (s > K) return;
+  roots[s == K ? 0 : 1 + s] = forest[seg_off[s] + 2 * (uint64_t)seg_lp[s] - 2];
+}
+
+int ann_index_build_dev(const u256* db, const uint32_t* ids, const u256* centroids, size_t n, size_t K, size_t dim, u256* grouped, uint32_t* slots,
+                        uint64_t* offsets, u256* forest, u256* roots) {
+  static thread_local AnnForest f;   // (pageable source of an asynchronous upload: it outlives the call)
+  TRY(ann_forest_plan(ids, n, K, &f));
+  const PoseidonSpec* sp;
+  TRY(poseidon_spec_dev(&sp, nullptr));
+  hipStream_t s = ctx().stream;
+  const size_t n_seg = K + 1, n_pre = (size_t)f.depth * (K + 2);
+  // work space: [seg_off | seg_lp, prefix, ids, rank, leaf_at] and the sponge states of the larger of the two leaf launches
+  uint8_t* w = (uint8_t*)scratch_get(7, (K + 2) * 8 + (n_seg + n_pre + 3 * n + 16) * 4);
+  if (!w) return VDB_ERR_OOM;
+  uint64_t* d_off = (uint64_t*)w;
+  uint32_t* d_lp = (uint32_t*)(d_off + K + 2);
+  uint32_t *d_pre = d_lp + n_seg, *d_ids = d_pre + n_pre, *d_rank = d_ids + n, *d_at = d_rank + n;
+  MkLayout ml, mw;
+  mk_layout(n, dim, 0, &ml);
+  mk_layout(1, K + 1, 0, &mw);
+  const size_t n_states = std::max((n > K ? n : K) * (size_t)ml.nperm, (size_t)mw.nperm) * PSD_T;
+  u256* states = (u256*)scratch_get(0, (n_states + 8) * sizeof(u256));
+  if (!states) return VDB_ERR_OOM;
+  VDB_HIP(hipMemcpyAsync(d_off, f.seg_off.data(), (K + 2) * 8, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(d_lp, f.seg_lp.data(), n_seg * 4, hipMemcpyHostToDevice, s));
+  if (n_pre) VDB_HIP(hipMemcpyAsync(d_pre, f.prefix.data(), n_pre * 4, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(d_ids, ids, n * 4, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemsetAsync(forest, 0, f.seg_off[K + 1] * sizeof(u256), s));
+  VDB_LAUNCH(k_ann_group, dim3(1), dim3(64), d_ids, (uint32_t)n, (uint32_t)K, d_off, offsets, d_rank, slots, d_at);
+  VDB_LAUNCH(k_ann_gather, dim3((unsigned)((n * dim + 255) / 256)), dim3(256), db, slots, (uint64_t)n, (uint32_t)dim, grouped);
+  // the leaf of a row does not depend on its cluster: one launch over the grouped rows, one over the centroids
+  VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((n + 63) / 64)), dim3(64), sp, grouped, (uint32_t)n, (uint32_t)dim, ml.nperm, states, forest, d_at);
+  VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((K + 63) / 64)), dim3(64), sp, centroids, (uint32_t)K, (uint32_t)dim, ml.nperm, states,
+             forest + f.seg_off[K], nullptr);
+  for (uint32_t l = 0; l < f.depth; l++)
+    VDB_LAUNCH(k_ann_forest_level, dim3((unsigned)((f.prefix[(size_t)l * (K + 2) + n_seg] + 63) / 64)), dim3(64), sp, forest, d_off, d_lp,
+               d_pre + (size_t)l * (K + 2), (uint32_t)n_seg, l);
+  VDB_LAUNCH(k_ann_roots, dim3((unsigned)(K / 64 + 1)), dim3(64), forest, d_off, d_lp, (uint32_t)K, roots);
+  VDB_LAUNCH(k_mk_leaf_states, dim3(1), dim3(64), sp, roots, 1u, (uint32_t)(K + 1), mw.nperm, states, roots + K + 1, nullptr);
+  // (the host arrays are read when the copies are enqueued on this runtime; the synchronisation makes that no assumption here, where
+  //  the next call of this thread rewrites them)
+  VDB_HIP(hipStreamSynchronize(s));
+  return VDB_OK;
+}
+
+// the circuit of one query (include/vdb.h vdb_wit_ann_query): where its blocks start
+struct AnnLayout {
+  DistLayout dl;
+  NvLayout nc, nm;
+  MkLayout mc, mm, mw;
+  uint64_t n_in, b_nc, b_mc, b_nm, b_mm, b_sel, b_root, total, l_nm, total_l;
+};
+static int ann_layout(FpEntry* fp, int metric, size_t K, size_t n_c, size_t dim, AnnLayout* o) {
+  VDB_ARG(K > 0 && n_c > 0 && dim > 0, "K = 0, empty cluster or dim = 0");
+  VDB_ARG(K <= VDB_ANN_MAX_CLUSTERS && n_c <= VDB_ANN_MAX_VECTORS && dim <= ((size_t)1 << 20), "query too large (include/vdb.h)");
+  TRY(nv_layout(fp, metric, K, dim, 1, &o->dl, &o->nc));
+  TRY(nv_fits(1, K, dim, 1, o->nc));
+  TRY(nv_layout(fp, metric, n_c, dim, 1, &o->dl, &o->nm));
+  TRY(nv_fits(1, n_c, dim, 1, o->nm));
+  mk_layout(K, dim, 0, &o->mc);
+  mk_layout(n_c, dim, (int)o->mc.zero_cell, &o->mm);   // Context::load_zero caches its cell: the centroids' padding has loaded it
+  mk_layout(1, K + 1, 1, &o->mw);
+  o->n_in = dim + K * dim + n_c * dim + K;
+  o->b_nc = o->n_in;
+  o->b_mc = o->b_nc + o->nc.total;
+  o->b_nm = o->b_mc + o->mc.total;
+  o->b_mm = o->b_nm + o->nm.total;
+  o->b_sel = o->b_mm + o->mm.total;
+  o->b_root = o->b_sel + 1 + 3 * K;
+  o->total = o->b_root + o->mw.total;
+  o->l_nm = o->nc.total_l;
+  o->total_l = o->nc.total_l + o->nm.total_l;
+  VDB_ARG(o->total <= VDB_NEAREST_TOPK_MAX_CELLS, "query circuit above 2^34 cells");
+  return VDB_OK;
+}
+// [query | centroids | members | cluster roots] assigned, then nearest_vector(query, centroids), merkle_commitment(centroids),
+// nearest_vector(query, members), merkle_commitment(members), select_by_indicator(cluster roots, centroid indicator) — which the map ties
+// to the members' root — and the sponge over [centroids' root | cluster roots].  levels_c / levels_m: the two trees where they are
+// resident (forest segments), or null.  pub: the dim result words, then the index root.
+int wit_ann_query_dev(FpEntry* fp, int metric, const u256* query, const u256* centroids, const u256* members, const u256* cluster_roots,
+                      const u256* levels_c, const u256* levels_m, size_t K, size_t n_c, size_t dim, Streams st, u256* ind_c, u256* ind_m, u256* pub) {
+  AnnLayout a;
+  TRY(ann_layout(fp, metric, K, n_c, dim, &a));
+  const PoseidonSpec* sp;
+  TRY(poseidon_spec_dev(&sp, nullptr));
+  // work space of the call: [centroids' root | cluster roots] (the sponge's words), the selected root, the first search's result
+  u256* words = (u256*)scratch_get(7, (K + 1 + 1 + dim + 8 + (size_t)a.mw.nperm * PSD_T) * sizeof(u256));
+  if (!words) return VDB_ERR_OOM;
+  u256 *picked = words + K + 1, *res_c = picked + 1, *wstates = res_c + dim;
+  TRY(inv_list_attach(st, a.total));
+  TRY(set_winv(st, fp->dev));
+  hipStream_t s = ctx().stream;
+  const bool resident = levels_c && levels_m;
+  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)((dim + K * dim + 255) / 256)), dim3(256), st, 0, query, centroids, (uint64_t)dim, (uint64_t)(dim + K * dim));
+  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)((n_c * dim + K + 255) / 256)), dim3(256), st, dim + K * dim, members, cluster_roots, (uint64_t)(n_c * dim),
+             (uint64_t)(n_c * dim + K));
+  TRY(nv_emit(fp, a.dl, a.nc, query, centroids, 1, K, dim, 1, st, a.b_nc, 0, true, ind_c, res_c));
+  TRY(mk_emit(fp, sp, centroids, K, dim, a.mc, st, a.b_mc, resident ? levels_c : nullptr, words));
+  TRY(nv_emit(fp, a.dl, a.nm, query, members, 1, n_c, dim, 1, st, a.b_nm, a.l_nm, true, ind_m, pub));
+  TRY(mk_emit(fp, sp, members, n_c, dim, a.mm, st, a.b_mm, resident ? levels_m : nullptr, nullptr));
+  VDB_HIP(hipMemcpyAsync(words + 1, cluster_roots, K * sizeof(u256), hipMemcpyDeviceToDevice, s));
+  const NvMap sm{a.b_sel, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, (uint32_t)K, 1u, 1u};
+  VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), st, fp->dev, sm, 1u, cluster_roots, ind_c, picked);
+  VDB_LAUNCH(k_mk_leaf_states, dim3(1), dim3(64), sp, words, 1u, (uint32_t)(K + 1), a.mw.nperm, wstates, pub + dim, nullptr);
+  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((a.mw.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, words, 1u, (uint32_t)(K + 1), a.mw.nperm, a.b_root,
+             a.mw.leaf_cells, wstates, nullptr);
+  return inv_list_fixup(st);
 }
 
 }  // namespace vdb
@@ -2415,6 +2668,79 @@ int vdb_wit_merkle_open(const vdb_fr* levels, size_t n, size_t dim, const vdb_fr
   TRY(wit_merkle_open_dev(dl.as<u256>(), n, dim, vectors ? dv.as<u256>() : nullptr, indices, m, hs.st, dpub.as<u256>()));
   TRY(download(public_out, dpub.p, n_pub * sizeof(u256)));
   return hs.finish(stream_out, nullptr, selector_out, ml.total, 0);
+}
+
+// the index of approximate-nearest-neighbour queries and the circuit of one query (include/vdb.h)
+int vdb_ann_index_forest_size(const uint32_t* cluster_ids, size_t n, size_t K, uint64_t* digests, uint64_t* segment_offsets) {
+  AnnForest f;
+  TRY(ann_forest_plan(cluster_ids, n, K, &f));
+  if (digests) *digests = f.seg_off[K + 1];
+  if (segment_offsets) memcpy(segment_offsets, f.seg_off.data(), (K + 2) * sizeof(uint64_t));
+  return VDB_OK;
+}
+int vdb_ann_index_build_dev(const vdb_fr* vectors_dev, const uint32_t* cluster_ids, const vdb_fr* centroids_dev, size_t n, size_t K, size_t dim,
+                            vdb_fr* grouped_dev, uint32_t* slots_dev, uint64_t* offsets_dev, vdb_fr* forest_dev, vdb_fr* roots_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(vectors_dev && cluster_ids && centroids_dev && grouped_dev && slots_dev && offsets_dev && forest_dev && roots_dev && dim > 0 &&
+              dim <= ((size_t)1 << 20),
+          "null pointer or dim outside [1, 2^20]");
+  return ann_index_build_dev(as_u256(vectors_dev), cluster_ids, as_u256(centroids_dev), n, K, dim, as_u256(grouped_dev), slots_dev, offsets_dev,
+                             as_u256(forest_dev), as_u256(roots_dev));
+}
+int vdb_wit_ann_query_size(int metric, uint32_t P, uint32_t L, size_t K, size_t n_c, size_t dim, uint64_t* cells, uint64_t* lookups, uint64_t* input_cells) {
+  VDB_REQUIRE_INIT();
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  AnnLayout a;
+  TRY(ann_layout(fp, metric, K, n_c, dim, &a));
+  if (cells) *cells = a.total;
+  if (lookups) *lookups = a.total_l;
+  if (input_cells) *input_cells = a.n_in;
+  return VDB_OK;
+}
+int vdb_wit_ann_query_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* query_dev, const vdb_fr* centroids_dev, const vdb_fr* members_dev,
+                          const vdb_fr* cluster_roots_dev, const vdb_fr* centroid_levels_dev, const vdb_fr* member_levels_dev, size_t K, size_t n_c,
+                          size_t dim, vdb_fr* stream_dev, vdb_fr* lookup_dev, uint8_t* selector_dev, vdb_fr* centroid_indicator_dev,
+                          vdb_fr* member_indicator_dev, vdb_fr* public_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(query_dev && centroids_dev && members_dev && cluster_roots_dev && stream_dev && lookup_dev && centroid_indicator_dev && member_indicator_dev &&
+              public_dev,
+          "null pointer");
+  VDB_ARG(!centroid_levels_dev == !member_levels_dev, "the two resident trees are given together or not at all");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  DevStreams ds;
+  TRY(ds.init(stream_dev, selector_dev, lookup_dev));
+  TRY(wit_ann_query_dev(fp, metric, as_u256(query_dev), as_u256(centroids_dev), as_u256(members_dev), as_u256(cluster_roots_dev),
+                        centroid_levels_dev ? as_u256(centroid_levels_dev) : nullptr, member_levels_dev ? as_u256(member_levels_dev) : nullptr, K, n_c, dim,
+                        ds.st, as_u256(centroid_indicator_dev), as_u256(member_indicator_dev), as_u256(public_dev)));
+  return ds.finish();
+}
+int vdb_wit_ann_query(int metric, uint32_t P, uint32_t L, const vdb_fr* query, const vdb_fr* centroids, const vdb_fr* members, const vdb_fr* cluster_roots,
+                      size_t K, size_t n_c, size_t dim, vdb_fr* stream_out, vdb_fr* lookup_out, uint8_t* selector_out, vdb_fr* centroid_indicator_out,
+                      vdb_fr* member_indicator_out, vdb_fr* public_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(query && centroids && members && cluster_roots, "null pointer");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  AnnLayout a;
+  TRY(ann_layout(fp, metric, K, n_c, dim, &a));
+  DevBuf dq, dc, dm, dr, dic, dim_, dpub;
+  HostStreams hs;
+  TRY(upload(dq, query, dim * sizeof(u256)));
+  TRY(upload(dc, centroids, K * dim * sizeof(u256)));
+  TRY(upload(dm, members, n_c * dim * sizeof(u256)));
+  TRY(upload(dr, cluster_roots, K * sizeof(u256)));
+  TRY(dic.alloc(K * sizeof(u256)));
+  TRY(dim_.alloc(n_c * sizeof(u256)));
+  TRY(dpub.alloc((dim + 1) * sizeof(u256)));
+  TRY(hs.init(a.total, a.total_l, selector_out != nullptr));
+  TRY(wit_ann_query_dev(fp, metric, dq.as<u256>(), dc.as<u256>(), dm.as<u256>(), dr.as<u256>(), nullptr, nullptr, K, n_c, dim, hs.st, dic.as<u256>(),
+                        dim_.as<u256>(), dpub.as<u256>()));
+  TRY(download(centroid_indicator_out, dic.p, K * sizeof(u256)));
+  TRY(download(member_indicator_out, dim_.p, n_c * sizeof(u256)));
+  TRY(download(public_out, dpub.p, (dim + 1) * sizeof(u256)));
+  return hs.finish(stream_out, lookup_out, selector_out, a.total, a.total_l);
 }
 
 // ---- b4 layout ---------------------------------------------------------------------------------

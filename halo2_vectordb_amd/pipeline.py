@@ -1196,3 +1196,146 @@ class FixedPointHotPath(HotPath):
         from . import circuit_sym as CS
         cm, outs = CS.trace_fixed_point(self.ops, self.P, self.L)
         return cm, outs, None
+
+
+class AnnIndex:
+    """The committed index of approximate-nearest-neighbour queries, resident on the device (include/vdb.h vdb_ann_index_build_dev): the
+    rows grouped by cluster, the forest of the K cluster trees and the centroids' tree, and the K + 2 root digests.  `vectors`: (n, dim)
+    f64; `cluster_ids`: (n,) integers, or KmeansHotPath.results()'s (n, K, 4) indicators; `centroids`: (K, dim) f64, or the (K, dim, 4)
+    quantized centroids KmeansHotPath.results() returns."""
+
+    def __init__(self, n, dim, K, vectors, cluster_ids, centroids, P=48, L=13, metric="euclidean"):
+        self.lib = api.init()
+        self.n, self.dim, self.K, self.P, self.L, self.metric_name = n, dim, K, P, L, metric
+        ids = np.asarray(cluster_ids)
+        if ids.ndim == 3:
+            ids = np.argmax(ids.any(axis=2), axis=1)
+        self.cluster_ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        cent = np.asarray(centroids)
+        self.qcent = np.ascontiguousarray(cent, dtype=np.uint64) if cent.ndim == 3 else api.quantize(np.ascontiguousarray(cent, dtype=np.float64), P)
+        self.qvec = api.quantize(np.ascontiguousarray(vectors, dtype=np.float64), P)
+        if self.qvec.shape != (n, dim, 4) or self.qcent.shape != (K, dim, 4) or self.cluster_ids.shape != (n,):
+            raise ValueError("vectors, cluster ids and centroids do not match (n, dim, K)")
+        self.n_digests, self.segments = api.ann_forest_layout(self.cluster_ids, K)     # refuses an empty cluster, an id >= K, K = 0
+        self.sizes = np.bincount(self.cluster_ids, minlength=K).astype(np.int64)
+        self.offsets = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
+        self._bufs = []
+        self.d_vec, self.d_cent = self._buf(self.qvec.nbytes), self._buf(self.qcent.nbytes)
+        self.d_grouped, self.d_slots, self.d_offsets = self._buf(self.qvec.nbytes), self._buf(n * 4), self._buf((K + 1) * 8)
+        self.d_forest, self.d_roots = self._buf(self.n_digests * B), self._buf((K + 2) * B)
+        self.d_vec.upload(self.qvec)
+        self.d_cent.upload(self.qcent)
+        check(self.lib.vdb_ann_index_build_dev(self.d_vec.ptr, api._p(self.cluster_ids), self.d_cent.ptr, n, K, dim, self.d_grouped.ptr, self.d_slots.ptr,
+                                               self.d_offsets.ptr, self.d_forest.ptr, self.d_roots.ptr))
+
+    def _buf(self, nbytes):
+        b = api.DeviceBuffer(max(int(nbytes), 32))
+        self._bufs.append(b)
+        return b
+
+    def roots(self):
+        """(K + 2, 4): [centroids' root | cluster roots | index root]"""
+        return self.d_roots.download((self.K + 2, 4))
+
+    def levels_ptr(self, c):
+        """device pointer of segment c of the forest (c = K: the centroids' tree)"""
+        return self.d_forest.at(int(self.segments[c]) * B)
+
+    def levels(self, c):
+        """cluster c's tree as a `levels=` of ReadHotPath / UpdateHotPath over its sizes[c] members: a view of the 2 lp_c digests of
+        segment c where the forest holds them (the hot path copies them device to device); .download((2 lp_c, 4)) brings them to the host"""
+        lo, hi = int(self.segments[c]), int(self.segments[c + 1])
+        return api.DeviceView(self.d_forest, lo * B, (hi - lo) * B)
+
+    def members_ptr(self, c):
+        return self.d_grouped.at(int(self.offsets[c]) * self.dim * B)
+
+    def members(self, c):
+        return self.d_grouped.download((int(self.sizes[c]), self.dim, 4), offset=int(self.offsets[c]) * self.dim * B)
+
+    def probe(self, query):
+        """the id of the centroid nearest to `query` ((dim,) f64): nearest_vector's indicator (the last centroid at the minimum)"""
+        q = api.quantize(np.ascontiguousarray(query, dtype=np.float64).reshape(1, self.dim), self.P)[0]
+        ind = api.wit_nearest(self.metric_name, q, self.qcent, self.P, self.L)["indicator"]
+        return int(np.flatnonzero(ind.any(axis=1))[-1])
+
+    def free(self):
+        for b in self._bufs:
+            b.free()
+        self._bufs = []
+
+
+class AnnQueryHotPath(HotPath):
+    """An approximate-nearest-neighbour query against a committed AnnIndex in ONE proof (include/vdb.h vdb_wit_ann_query): assign the
+    query, the centroids, the members of the cluster searched and the K cluster roots; nearest_vector(query, centroids),
+    merkle_commitment(centroids), nearest_vector(query, members), merkle_commitment(members), select_by_indicator(cluster roots,
+    centroid indicator) tied to the members' root, and the sponge over [centroids' root | cluster roots].  The reference runs the two
+    searches in two circuits and compares roots outside them (tests/demo/mod.rs:52 "FIXME: these should be done in the same circuit"):
+    this is that one circuit.  Public: the result vector, then the index root.  The circuit's shape depends on (K, n_c, dim, metric):
+    one proving key per cluster size.  `cluster`: the cluster searched (None: index.probe(query)); a cluster other than the winning
+    centroid's breaks the copy constraint.  `cluster_roots` / `centroids`: quantized overrides of what the index holds (tests of the
+    binding); with them the two trees are hashed by the call instead of read from the forest."""
+
+    def __init__(self, index, query, cluster=None, k=13, P=48, L=12, metric="euclidean", tau=None, col_shard=(0, 1), blind_seed=None, params=None,
+                 cluster_roots=None, centroids=None):
+        query = np.ascontiguousarray(query, dtype=np.float64).reshape(1, index.dim)
+        self.index, self.K = index, index.K
+        self.cluster = index.probe(query[0]) if cluster is None else int(cluster)
+        super().__init__(int(index.sizes[self.cluster]), index.dim, k, P, L, seed=None, tau=tau, col_shard=col_shard, vectors=query, blind_seed=blind_seed,
+                         params=params)
+        self.metric, self.metric_name = api.METRICS[metric], metric
+        self.given_roots, self.given_cent = cluster_roots, centroids
+
+    def n_input_rows(self):
+        return 1
+
+    def _load_inputs(self):
+        super()._load_inputs()
+        ix, self.resident = self.index, self.given_roots is None and self.given_cent is None
+        self.p_cent, self.p_roots = ix.d_cent.ptr, ix.d_roots.at(B)
+        if self.given_roots is not None:
+            r = np.ascontiguousarray(self.given_roots, dtype=np.uint64)
+            assert r.shape == (self.K, 4)
+            d = self._output(r.nbytes)
+            d.upload(r)
+            self.p_roots = d.ptr
+        if self.given_cent is not None:
+            c = np.ascontiguousarray(self.given_cent, dtype=np.uint64)
+            assert c.shape == (self.K, self.dim, 4)
+            d = self._output(c.nbytes)
+            d.upload(c)
+            self.p_cent = d.ptr
+
+    def _circuit_size(self):
+        cells, lk, n_in = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(self.lib.vdb_wit_ann_query_size(self.metric, self.P, self.L, self.K, self.n, self.dim, ctypes.byref(cells), ctypes.byref(lk), ctypes.byref(n_in)))
+        return n_in.value, cells.value - n_in.value, lk.value
+
+    def _alloc_outputs(self):
+        self.d_ind_c, self.d_ind_m = self._output(self.K * B), self._output(self.n * B)
+        self.d_pub = self._output((self.dim + 1) * B)
+
+    def _witness(self, sel=None):
+        # the call writes the assigned witnesses too (centroids, members and roots where the index holds them)
+        ix = self.index
+        with self._window(sel, 0):
+            check(self.lib.vdb_wit_ann_query_dev(self.metric, self.P, self.L, self.d_vec.ptr, self.p_cent, ix.members_ptr(self.cluster), self.p_roots,
+                                                 ix.levels_ptr(self.K) if self.resident else None, ix.levels_ptr(self.cluster) if self.resident else None,
+                                                 self.K, self.n, self.dim, self.d_stream.ptr, self.d_lookup.ptr, self._sel_at(sel, 0), self.d_ind_c.ptr,
+                                                 self.d_ind_m.ptr, self.d_pub.ptr))
+
+    def public_values_dev(self):
+        return self.d_pub.ptr, self.dim + 1
+
+    def results(self):
+        """(centroid indicator (K, 4), member indicator (n_c, 4), result (dim, 4), index root (4,))"""
+        pub = self.d_pub.download((self.dim + 1, 4))
+        return self.d_ind_c.download((self.K, 4)), self.d_ind_m.download((self.n, 4)), pub[:self.dim], pub[self.dim]
+
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        cm, public, _ = CS.build_ann_query(self.metric_name, self.K, self.n, self.dim, self.P, self.L, functools.partial(self._fetch_flags, d_flags),
+                                           self._fetch, builder=DeviceBuilder if on_device else None)
+        assert cm.n_cells == self.n_cells
+        return cm, public, None

@@ -322,6 +322,59 @@ int vdb_wit_merkle_open(const vdb_fr *levels, size_t n, size_t dim, const vdb_fr
 int vdb_wit_merkle_open_dev(const vdb_fr *levels_dev, size_t n, size_t dim, const vdb_fr *vectors_dev /* m x dim, NULL: leaf mode */,
                             const uint64_t *indices /* host */, size_t m, vdb_fr *stream_dev, uint8_t *selector_dev, vdb_fr *public_dev);
 
+/* The index of approximate-nearest-neighbour queries and the circuit of one query.  The reference's demo (tests/demo/mod.rs:38-91) finds
+ * the nearest centroid, then the nearest vector of that centroid's cluster, in two circuits whose roots it compares outside any proof;
+ * this is the closure that does both in one circuit, bound to one public index root.
+ * members(c): the database vectors whose cluster id is c, in database order (select_cluster).  The index commitment:
+ *   centroids_root = merkle_commitment(centroids);  cluster_root_c = merkle_commitment(members(c))
+ *   index_root     = poseidon.clear(); update([centroids_root, cluster_root_0 .. cluster_root_{K-1}]); squeeze()
+ * i.e. the leaf hash merkle_commitment computes for one vector of K + 1 words.
+ * vdb_ann_index_build_dev (values only, everything left on the device): grouped_dev n x dim: the rows grouped by cluster, stable in
+ * database order; slots_dev n x uint32: the database slot of every grouped row; offsets_dev (K + 1) x uint64: cluster c's rows are
+ * [offsets[c], offsets[c + 1]) of the grouped rows; forest_dev: K + 1 segments, segment s at digest segment_offsets[s] holding the
+ * 2 lp_s digests of a tree in vdb_merkle_tree_build_dev's layout (leaves, zero padding, root at 2 lp_s - 2), lp_s the power of two >=
+ * the segment's leaf count — segment c < K is cluster c's tree, a valid levels_dev of vdb_wit_merkle_open_dev and
+ * vdb_wit_merkle_update_dev over |members(c)| vectors, segment K the centroids' tree; roots_dev K + 2 digests:
+ * [centroids_root | cluster_root_0 .. cluster_root_{K-1} | index_root].  vdb_ann_index_forest_size gives the digests of the forest and
+ * (segment_offsets, K + 2 entries, may be NULL) where its segments start.  cluster_ids is a HOST array in both calls.
+ * Launches: one grouping kernel (offsets and ranks for all clusters at once), one gather, two leaf launches (rows, centroids), one
+ * segmented level launch per level of the deepest tree over all K + 1 trees, one for the roots and one for the sponge: 6 + max depth,
+ * whatever K.  VDB_ERR_ARG before anything is launched: K == 0, n == 0, an id >= K, an empty cluster, n > VDB_ANN_MAX_VECTORS (32-bit
+ * forest offsets and row numbers), K > VDB_ANN_MAX_CLUSTERS (the grouping kernel counts the clusters in 16 KiB of LDS).
+ * Cost: the grouping kernel is a single wavefront that walks the n rows 64 at a time (a 64-step shuffle loop and two barriers a tile)
+ * and writes every row's place itself: n / 64 serial tiles on one compute unit, 262,144 of them at n = VDB_ANN_MAX_VECTORS.
+ *
+ * vdb_wit_ann_query: assigned, from cell 0: the query (dim), the centroids (K x dim), the members of the cluster searched (n_c x dim),
+ * the K cluster roots: input_cells of them.  Then
+ *   ind_c, _  = nearest_vector(query, centroids)            croot = merkle_commitment(centroids)
+ *   _, result = nearest_vector(query, members)              mroot = merkle_commitment(members)
+ *   sel       = gate.select_by_indicator(cluster_roots, ind_c)                  (1 + 3 K cells)
+ *   index_root = the sponge over [croot, cluster_roots ..]
+ * and the circuit ties sel to mroot (a copy constraint, no cell): the cluster searched is the one whose centroid won.  Lookup cells:
+ * the two nearest blocks', in block order.  public dim + 1 values: the result words, then index_root; the query, the winning cluster
+ * and its size stay private.  The shape depends on (K, n_c, dim, metric): one proving key per cluster size.  Ties are nearest_vector's.
+ * Members of another cluster than the winner's still give a stream; it breaks the sel = mroot copy.
+ * centroid_levels_dev / member_levels_dev: the two trees where they are resident (forest segments K and c), only read — then the launch
+ * count depends on neither K nor n_c; both NULL: the digests are computed by the call, a launch per level; one of them alone:
+ * VDB_ERR_ARG.  The caller answers for member_levels_dev being the tree of members_dev (and centroid_levels_dev that of
+ * centroids_dev): nothing checks it, and a stale tree gives a stream that fails only at Mock or verify time.  The _dev form honours
+ * vdb_wit_set_window.  VDB_ERR_ARG before anything is launched: K == 0, n_c == 0, dim == 0, the limits above, dim > 2^20, more than
+ * 2^34 cells, and the limits of vdb_wit_nearest_topk for each of the two searches. */
+#define VDB_ANN_MAX_VECTORS ((size_t)1 << 24)
+#define VDB_ANN_MAX_CLUSTERS 4096
+int vdb_ann_index_forest_size(const uint32_t *cluster_ids /* host */, size_t n, size_t K, uint64_t *digests, uint64_t *segment_offsets);
+int vdb_ann_index_build_dev(const vdb_fr *vectors_dev, const uint32_t *cluster_ids /* host */, const vdb_fr *centroids_dev, size_t n, size_t K,
+                            size_t dim, vdb_fr *grouped_dev, uint32_t *slots_dev, uint64_t *offsets_dev, vdb_fr *forest_dev, vdb_fr *roots_dev);
+int vdb_wit_ann_query_size(int metric, uint32_t precision_bits, uint32_t lookup_bits, size_t K, size_t n_c, size_t dim, uint64_t *cells,
+                           uint64_t *lookups, uint64_t *input_cells);
+int vdb_wit_ann_query(int metric, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *query, const vdb_fr *centroids, const vdb_fr *members,
+                      const vdb_fr *cluster_roots, size_t K, size_t n_c, size_t dim, vdb_fr *stream_out, vdb_fr *lookup_out, uint8_t *selector_out,
+                      vdb_fr *centroid_indicator_out, vdb_fr *member_indicator_out, vdb_fr *public_out);
+int vdb_wit_ann_query_dev(int metric, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *query_dev, const vdb_fr *centroids_dev,
+                          const vdb_fr *members_dev, const vdb_fr *cluster_roots_dev, const vdb_fr *centroid_levels_dev, const vdb_fr *member_levels_dev,
+                          size_t K, size_t n_c, size_t dim, vdb_fr *stream_dev, vdb_fr *lookup_dev, uint8_t *selector_dev,
+                          vdb_fr *centroid_indicator_dev, vdb_fr *member_indicator_dev, vdb_fr *public_dev);
+
 /* ---- b4 stream -> columns: replaces halo2-base GateThreadBuilder::assign_all (break points, keygen)
  *      and assign_threads_in (prover) as driven by RangeCircuitBuilder::prover(builder, break_points)
  *      (src/scaffold/mod.rs:393-396).  Columns are 2^k rows; the cell on a break row is duplicated at

@@ -15,7 +15,11 @@ the last K of them deletes (new leaf 0), `--grow G` doubles the padded leaf coun
 the root before the growth).
 `--circuit read --reads M` proves M reads of the committed n x dim database (pipeline.ReadHotPath: M Merkle openings, [root | idx, leaf
 per read | the vectors read] public; `--leaf-only`: the leaf digests instead of the vectors, a padding slot showing leaf 0), and has
-the verifier check the proof."""
+the verifier check the proof.
+`--circuit ann --K C` proves one approximate-nearest-neighbour query against a committed index of the n x dim database
+(pipeline.AnnIndex, AnnQueryHotPath: the first C vectors are the centroids, every vector belongs to its nearest one; nearest_vector over
+the centroids and over the winning cluster, both commitments, the selected cluster root tied to the members' root, [result | index_root]
+public), and has the verifier check the proof.  The circuit's size follows the cluster searched, not n."""
 import argparse
 import json
 import os
@@ -26,7 +30,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from halo2_vectordb_amd import api  # noqa: E402
-from halo2_vectordb_amd.pipeline import BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
+from halo2_vectordb_amd.pipeline import AnnIndex, AnnQueryHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
 from halo2_vectordb_amd.rounds import ProverRounds, quotient_identity_holds  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -37,7 +41,7 @@ ap.add_argument("--seed", type=int, default=20260003)
 ap.add_argument("--block-cols", type=int, default=510)
 ap.add_argument("--ext-block-cols", type=int, default=None)
 ap.add_argument("--proofs", type=int, default=2)
-ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read"])
+ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read", "ann"])
 ap.add_argument("--lookup-bits", type=int, default=13)
 ap.add_argument("--metric", default="euclidean")
 ap.add_argument("--queries", type=int, default=1, help="--circuit query: queries proved against the one database in this proof")
@@ -47,6 +51,7 @@ ap.add_argument("--deletes", type=int, default=0, help="--circuit update: the la
 ap.add_argument("--grow", type=int, default=0, help="--circuit update: doublings of the padded leaf count before the first update")
 ap.add_argument("--reads", type=int, default=8, help="--circuit read: slots opened in this proof")
 ap.add_argument("--leaf-only", action="store_true", help="--circuit read: reveal the leaf digests, not the vectors")
+ap.add_argument("--K", type=int, default=32, help="--circuit ann: clusters of the index")
 ap.add_argument("--out", default=None, help="write the proof (io.write_snark) and the verifying key beside it")
 args = ap.parse_args()
 
@@ -67,6 +72,16 @@ elif args.circuit == "update":
         raise SystemExit("--deletes is between 0 and --updates, --grow is not negative")
     kinds = [0] * (args.updates - args.deletes) + [1] * args.deletes
     hp = UpdateHotPath(n=args.n, dim=args.dim, m=args.updates, k=args.k, seed=args.seed, kinds=kinds, grow=args.grow)
+elif args.circuit == "ann":
+    from halo2_vectordb_amd.pipeline import sift_like_vectors
+    if not 1 <= args.K <= args.n:
+        raise SystemExit("--K is between 1 and --n")
+    db, seed = sift_like_vectors(args.seed, args.n, args.dim)
+    query = sift_like_vectors(seed + 1000, 1, args.dim)[0][0]
+    ids = np.argmin(((db[:, None, :] - db[None, :args.K, :]) ** 2).sum(axis=2), axis=1)
+    ids[:args.K] = np.arange(args.K)                           # (a duplicate of an earlier centroid still keeps its own cluster)
+    index = AnnIndex(args.n, args.dim, args.K, db, ids, db[:args.K], L=args.lookup_bits, metric=args.metric)
+    hp = AnnQueryHotPath(index, query, k=args.k, L=args.lookup_bits, metric=args.metric)
 elif args.circuit == "read":
     hp = ReadHotPath(n=args.n, dim=args.dim, m=args.reads, k=args.k, seed=args.seed, reveal="leaf" if args.leaf_only else "vector")
 elif args.circuit == "query":
@@ -101,12 +116,13 @@ if args.out:
     write_snark(args.out, out["proof"], out["instances"])
     pr.save_verifying_key(args.out + ".vk.npz", opened=out["opened"])
 accepted = {}
-if args.circuit == "read":
+if args.circuit in ("read", "ann"):
     from halo2_vectordb_amd import verifier
     accepted = {"proof_accepted": bool(verifier.verify(out["proof"], out["instances"], verifier.VerifyingKey.from_prover(pr, out["opened"])))}
 what = f"merkle_commitment {args.n}x{args.dim} k={args.k}" if args.circuit == "merkle" else \
     f"{args.updates} Merkle path updates ({args.deletes} deletes, tree grown {args.grow} times) against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "update" else \
     f"{args.reads} Merkle openings ({'leaves' if args.leaf_only else 'vectors'} public) against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "read" else \
+    f"ann query (K={args.K}, cluster {hp.cluster} of {hp.n} vectors, {args.metric}) against the index of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann" else \
     f"query circuit ({str(args.queries) + ' x ' if args.queries > 1 else ''}{'top-' + str(args.topk) + ' ' if args.topk > 1 else ''}nearest_vector {args.metric} + merkle_commitment) over {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}"
 print(json.dumps({"workload": what + ": whole constraint map, public outputs in the instance column, transcript, fresh blinds, SHPLONK", "lookup_cells": hp.n_lookup,
                   "cells": hp.n_cells, "columns": hp.n_cols, "product_sets": pr.n_sets, "mock_report_on_keygen_witness": pr.keygen_report.as_dict(),
@@ -117,3 +133,5 @@ print(json.dumps({"workload": what + ": whole constraint map, public outputs in 
                   "block_cols": args.block_cols, "ext_cols_held": hp.ext_cols}))
 pr.free()
 hp.free()
+if args.circuit == "ann":
+    index.free()
