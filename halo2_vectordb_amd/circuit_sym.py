@@ -950,6 +950,21 @@ def _perm_placer(B, fetch_flags, fetch_values):
     return perm
 
 
+def _node(perm, bases, left, right):
+    """a tree node's hash placed at `bases`: the permutation absorbing [left, right], then the padding-only one -> the digest cells"""
+    return perm(bases + perm_cells(2), 0, perm(bases, 2, None, [left, right]), [])[1]
+
+
+def _place_leaf_sponge(perm, bases, lay, words):
+    """the sponge of a leaf (lay: merkle_leaf_layout of its word count) placed at `bases`; words[k]: the cells its word k copies, one per
+    base (words None: free words) -> (the squeeze cells, the first cell after each sponge)"""
+    state, at = None, bases
+    for p, n_in in enumerate(lay["n_ins"]):
+        state = perm(at, n_in, state, None if words is None else [words[2 * p + i] for i in range(n_in)])
+        at = at + lay["sizes"][p]
+    return state[1], at
+
+
 def place_merkle(B, n, dim, base, vec_base, fetch_flags, fetch_values, zero_cell=None):
     """merkle_commitment over n vectors of `dim` words whose trace starts at stream cell `base`, placed into builder `B` in the cell
     order of witness.hip: the leaves' sponges, the load_zero cell of the padding, the tree.  `vec_base`: stream cell of word 0 of
@@ -960,19 +975,16 @@ def place_merkle(B, n, dim, base, vec_base, fetch_flags, fetch_values, zero_cell
     lay = merkle_leaf_layout(dim)
     perm = _perm_placer(B, fetch_flags, fetch_values)
     v = np.arange(n, dtype=np.int64)
-    state, at = None, base + v * lay["leaf_cells"]
-    for p, n_in in enumerate(lay["n_ins"]):
-        state = perm(at, n_in, state, None if vec_base is None else [vec_base + v * dim + 2 * p + i for i in range(n_in)])
-        at = at + lay["sizes"][p]
+    leaves, _ = _place_leaf_sponge(perm, base + v * lay["leaf_cells"], lay, None if vec_base is None else [vec_base + v * dim + k for k in range(dim)])
     lp, pos = 1 << (n - 1).bit_length(), base + n * lay["leaf_cells"]
     digest = np.full(lp, pos if zero_cell is None else zero_cell, dtype=np.int64)   # the padding leaves: the zero cell that follows the leaves
-    digest[:n] = state[1]
+    digest[:n] = leaves
     if lp > n and zero_cell is None:
         B.constant_cell(pos, 0)                              # ctx.load_zero()
         pos += 1
     while digest.size > 1:
         bases = pos + np.arange(digest.size // 2, dtype=np.int64) * lay["node_cells"]
-        digest = perm(bases + perm_cells(2), 0, perm(bases, 2, None, [digest[0::2], digest[1::2]]), [])[1]
+        digest = _node(perm, bases, digest[0::2], digest[1::2])
         pos += bases.size * lay["node_cells"]
     return int(digest[0]), pos
 
@@ -1005,13 +1017,9 @@ def merkle_cells(n, dim, zero_cached=False):
 def place_sponge(B, base, words, fetch_flags, fetch_values):
     """poseidon.clear(); update(words); squeeze() over the stream cells `words` — merkle_commitment's leaf hash of one vector — placed
     into builder `B` from stream cell `base` on.  -> (stream cell of the digest, first cell after the trace)"""
-    lay = merkle_leaf_layout(len(words))
-    perm = _perm_placer(B, fetch_flags, fetch_values)
-    state, at = None, np.asarray([base], dtype=np.int64)
-    for p, n_in in enumerate(lay["n_ins"]):
-        state = perm(at, n_in, state, [np.asarray([words[2 * p + i]], dtype=np.int64) for i in range(n_in)])
-        at = at + lay["sizes"][p]
-    return int(state[1][0]), int(at[0])
+    one = lambda c: np.asarray([c], dtype=np.int64)
+    digest, end = _place_leaf_sponge(_perm_placer(B, fetch_flags, fetch_values), one(base), merkle_leaf_layout(len(words)), [one(w) for w in words])
+    return int(digest[0]), int(end[0])
 
 
 def ann_query_layout(metric, K, n_c, dim, P, L):
@@ -1069,6 +1077,50 @@ def build_ann_query(metric, K, n_c, dim, P, L, fetch_flags, fetch_values, builde
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# The Merkle path that updates and openings share: per level [assert_bit 4 | select 8 | select 8 | H] for the first running digest and
+# [select 8 | select 8 | H] for a second one (an update's new path), then the index inner product over the bits
+def _path_layout(dim, depth, sides):
+    """merkle_leaf_layout(dim) with level_cells for `sides` running digests and ip_cells"""
+    lay = merkle_leaf_layout(dim)
+    lay.update(level_cells=20 + lay["node_cells"] + (sides - 1) * (16 + lay["node_cells"]), ip_cells=1 + 3 * (depth - 1))
+    return lay
+
+
+def _path_units(depth):
+    """the unit blocks of a path: head (bit, sibling, cur) -> lo, ro behind assert_bit(bit); tail: the same two selects alone;
+    ip (bits) -> inner_product(bits, Constant(2^l))"""
+    s = Sym(0, 0)
+    s.g_assert_bit(ext(0))
+    head = Block(s, [s.g_select(ext(1), ext(2), ext(0)), s.g_select(ext(2), ext(1), ext(0))])
+    s = Sym(0, 0)
+    tail = Block(s, [s.g_select(ext(1), ext(2), ext(0)), s.g_select(ext(2), ext(1), ext(0))])
+    s = Sym(0, 0)
+    acc = s.push(ext(0), depth > 1)
+    for l in range(1, depth):
+        s.push(ext(l))
+        s.push(C(1 << l))
+        acc = s.push(None, l + 1 < depth)
+    return head, tail, Block(s, [acc])
+
+
+def _place_path(B, perm, lay, levels_at, bits, sibs, curs):
+    """the levels and the index of the paths of all instances at once, level after level: levels_at: the first cell of each instance's
+    level 0, bits / sibs: its (instance, level) cells, curs: the one or two arrays of leaf cells the running digests start from
+    -> (the tops of the running digests, the index cells)"""
+    depth = bits.shape[1]
+    head, tail, ip = _path_units(depth)
+    zeros, curs = np.zeros(levels_at.size, dtype=np.int64), list(curs)
+    for l in range(depth):
+        at = levels_at + l * lay["level_cells"]
+        for k, cur in enumerate(curs):
+            lr = B.place(tail if k else head, at, zeros, np.stack([bits[:, l], sibs[:, l], cur], axis=1))
+            at = at + (16 if k else 20)
+            curs[k] = _node(perm, at, lr[:, 0], lr[:, 1])
+            at = at + lay["node_cells"]
+    return curs, B.place(ip, levels_at + depth * lay["level_cells"], zeros, bits)[:, 0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # Merkle path updates (include/vdb.h vdb_wit_merkle_update; pipeline.UpdateHotPath)
 def merkle_update_layout(m, dim, depth, kinds=None, grow=0):
     """where the cells of a batch of m path updates lie: dict(nperm, n_ins, sizes, leaf_cells, node_cells, level_cells, ip_cells,
@@ -1086,10 +1138,9 @@ def merkle_update_layout(m, dim, depth, kinds=None, grow=0):
         raise ValueError("a batch holds at least one update of a tree with at least two leaves")
     if len(kinds) != m or not set(kinds) <= {0, 1} or grow < 0 or grow > depth:
         raise ValueError("one kind (0 write, 1 delete) per update, and no more doublings than the grown tree has levels")
-    lay = merkle_leaf_layout(dim)
+    lay = _path_layout(dim, depth, 2)
     w = kinds.count(0)
-    lay.update(level_cells=36 + 2 * lay["node_cells"], ip_cells=1 + 3 * (depth - 1), n_vec=w * dim, old_leaf=w * dim, bits=w * dim + m,
-               sibs=w * dim + m + m * depth, kinds=kinds, grow=grow, w=w)
+    lay.update(n_vec=w * dim, old_leaf=w * dim, bits=w * dim + m, sibs=w * dim + m + m * depth, kinds=kinds, grow=grow, w=w)
     lay["per_update"] = lay["leaf_cells"] + depth * lay["level_cells"] + lay["ip_cells"]
     lay["n_in"] = w * dim + m * (1 + 2 * depth) + (1 if grow else 0)
     lay["r0"], lay["z0"] = (lay["n_in"] - 1, lay["n_in"]) if grow else (None, None)
@@ -1184,6 +1235,20 @@ class _CellTrace:
             at += lay["sizes"][p]
         return state[1], at
 
+    def path(self, at, curs, bits, sibs):
+        """the levels of a path from cell `at` on, for the one or two running digests that start at the cells `curs` (an update: its old
+        and its new path), and the index behind them -> (the tops of the running digests, the index cell, the first cell after it)"""
+        curs = list(curs)
+        for b, sib in zip(bits, sibs):
+            at = self.assert_bit(at, b)
+            for k, cur in enumerate(curs):
+                lo = self.select(at, sib, cur, b)
+                ro = self.select(at + 8, cur, sib, b)
+                curs[k] = self.node(at + 16, lo, ro)
+                at += 16 + perm_cells(2) + perm_cells(0)
+        idx_cell, at = self.index(at, bits)
+        return curs, idx_cell, at
+
     def index(self, at, bits):
         """inner_product(bits, Constant(2^l)): 2^0 = 1, the sum starts with b_0 itself -> (the sum's cell, the first cell after it)"""
         depth = len(bits)
@@ -1227,19 +1292,8 @@ def trace_merkle_update(m, dim, depth, fetch_flags, fetch_values, kinds=None, gr
         assert at == lay["levels_at"][j]
         cur_old = lay["old_leaf"] + j
         new_leaves.append(cur_new)
-        bits = [lay["bits"] + j * depth + l for l in range(depth)]
-        for l in range(depth):
-            b, sib = bits[l], lay["sibs"] + j * depth + l
-            t.assert_bit(at, b)
-            lo = t.select(at + 4, sib, cur_old, b)
-            ro = t.select(at + 12, cur_old, sib, b)
-            cur_old = t.node(at + 20, lo, ro)
-            at += 20 + lay["node_cells"]
-            ln = t.select(at, sib, cur_new, b)
-            rn = t.select(at + 8, cur_new, sib, b)
-            cur_new = t.node(at + 16, ln, rn)
-            at += 16 + lay["node_cells"]
-        idx_cell, at = t.index(at, bits)
+        (cur_old, cur_new), idx_cell, at = t.path(at, [cur_old, cur_new], range(lay["bits"] + j * depth, lay["bits"] + (j + 1) * depth),
+                                                  range(lay["sibs"] + j * depth, lay["sibs"] + (j + 1) * depth))
         idx_cells.append(idx_cell)
         assert at == (lay["block"][j + 1] if j + 1 < m else lay["total"])
         if j == 0:
@@ -1258,61 +1312,30 @@ def build_merkle_update(m, dim, depth, fetch_flags, fetch_values, builder=None, 
     lay = merkle_update_layout(m, dim, depth, kinds, grow)
     B = (builder or _Builder)(lay["total"], 0)
     j = np.arange(m, dtype=np.int64)
-    zeros = np.zeros(m, dtype=np.int64)
     base = np.asarray(lay["block"], dtype=np.int64)
-    levels_at = np.asarray(lay["levels_at"], dtype=np.int64)
     perm = _perm_placer(B, fetch_flags, fetch_values)
-
-    def node(bases, left, right):
-        return perm(bases + perm_cells(2), 0, perm(bases, 2, None, [left, right]), [])[1]
-
     top = None
     if grow:
         B.constant_cell(lay["z0"], 0)                        # Z_0 = ctx.load_constant(0)
         one = lambda c: np.asarray([c], dtype=np.int64)
         z, top, at = [one(lay["z0"])], one(lay["r0"]), lay["z0"] + 1
         for l in range(depth - 1):
-            z.append(node(one(at), z[l], z[l]))
+            z.append(_node(perm, one(at), z[l], z[l]))
             at += lay["node_cells"]
         for i in range(grow):
-            top = node(one(at), top, z[depth - grow + i])
+            top = _node(perm, one(at), top, z[depth - grow + i])
             at += lay["node_cells"]
-
-    s = Sym(0, 0)
-    s.g_assert_bit(ext(0))
-    head = Block(s, [s.g_select(ext(1), ext(2), ext(0)), s.g_select(ext(2), ext(1), ext(0))])     # (bit, sibling, cur_old) -> lo, ro
-    s = Sym(0, 0)
-    tail = Block(s, [s.g_select(ext(1), ext(2), ext(0)), s.g_select(ext(2), ext(1), ext(0))])     # (bit, sibling, cur_new) -> ln, rn
-    s = Sym(0, 0)
-    acc = s.push(ext(0), depth > 1)
-    for l in range(1, depth):
-        s.push(ext(l))
-        s.push(C(1 << l))
-        acc = s.push(None, l + 1 < depth)
-    ip = Block(s, [acc])
 
     is_write = np.asarray(lay["kinds"], dtype=np.int64) == 0
     new_leaf = base.copy()                                   # a delete: its block starts with new_leaf = ctx.load_constant(0)
     for c in base[~is_write]:
         B.constant_cell(int(c), 0)
     if lay["w"]:
-        wbase, word0 = base[is_write], np.arange(lay["w"], dtype=np.int64) * dim
-        state, off = None, 0
-        for p in range(lay["nperm"]):
-            state = perm(wbase + off, lay["n_ins"][p], state, [word0 + 2 * p + i for i in range(lay["n_ins"][p])])
-            off += lay["sizes"][p]
-        new_leaf[is_write] = state[1]
-    cur_old, cur_new = lay["old_leaf"] + j, new_leaf
-    bits = lay["bits"] + j[:, None] * depth + np.arange(depth, dtype=np.int64)[None, :]
-    for l in range(depth):
-        lb = levels_at + l * lay["level_cells"]
-        sib = lay["sibs"] + j * depth + l
-        lr = B.place(head, lb, zeros, np.stack([bits[:, l], sib, cur_old], axis=1))
-        cur_old = node(lb + 20, lr[:, 0], lr[:, 1])
-        lb = lb + 20 + lay["node_cells"]
-        lr = B.place(tail, lb, zeros, np.stack([bits[:, l], sib, cur_new], axis=1))
-        cur_new = node(lb + 16, lr[:, 0], lr[:, 1])
-    idx = B.place(ip, levels_at + depth * lay["level_cells"], zeros, bits)[:, 0]
+        word0 = np.arange(lay["w"], dtype=np.int64) * dim
+        new_leaf[is_write], _ = _place_leaf_sponge(perm, base[is_write], lay, [word0 + k for k in range(dim)])
+    path = j[:, None] * depth + np.arange(depth, dtype=np.int64)[None, :]
+    (cur_old, cur_new), idx = _place_path(B, perm, lay, np.asarray(lay["levels_at"], dtype=np.int64), lay["bits"] + path, lay["sibs"] + path,
+                                          [lay["old_leaf"] + j, new_leaf])
     if grow:
         B.tie(int(cur_old[0]), int(top[0]))                  # ctx.constrain_equal(cur_old, R_grow)
     for k in range(1, m):
@@ -1329,12 +1352,11 @@ def merkle_open_layout(m, dim, depth, with_vectors):
     index inner product"""
     if m < 1 or depth < 1 or dim < 1:
         raise ValueError("a call opens at least one slot of a tree with at least two leaves")
-    lay = merkle_leaf_layout(dim)
+    lay = _path_layout(dim, depth, 1)
     if not with_vectors:
         lay.update(nperm=0, n_ins=[], sizes=[], leaf_cells=0)
     n_lead = m * dim if with_vectors else m
-    lay.update(level_cells=20 + lay["node_cells"], ip_cells=1 + 3 * (depth - 1), n_lead=n_lead, bits=n_lead, sibs=n_lead + m * depth,
-               n_in=n_lead + 2 * m * depth)
+    lay.update(n_lead=n_lead, bits=n_lead, sibs=n_lead + m * depth, n_in=n_lead + 2 * m * depth)
     lay["per_read"] = lay["leaf_cells"] + depth * lay["level_cells"] + lay["ip_cells"]
     lay["total"] = lay["n_in"] + m * lay["per_read"]
     return lay
@@ -1360,15 +1382,8 @@ def trace_merkle_open(m, dim, depth, with_vectors, fetch_flags, fetch_values):
         at = lay["n_in"] + j * lay["per_read"]
         cur, at = t.leaf(at, lay, j * dim) if with_vectors else (j, at)      # the squeeze cell, or the assigned leaf
         leaves.append(cur)
-        bits = [lay["bits"] + j * depth + l for l in range(depth)]
-        for l in range(depth):
-            b, sib = bits[l], lay["sibs"] + j * depth + l
-            t.assert_bit(at, b)
-            lo = t.select(at + 4, sib, cur, b)
-            ro = t.select(at + 12, cur, sib, b)
-            cur = t.node(at + 20, lo, ro)
-            at += lay["level_cells"]
-        idx_cell, at = t.index(at, bits)
+        (cur,), idx_cell, at = t.path(at, [cur], range(lay["bits"] + j * depth, lay["bits"] + (j + 1) * depth),
+                                      range(lay["sibs"] + j * depth, lay["sibs"] + (j + 1) * depth))
         idx_cells.append(idx_cell)
         assert at == lay["n_in"] + (j + 1) * lay["per_read"]
         if top0 is None:
@@ -1384,36 +1399,11 @@ def build_merkle_open(m, dim, depth, with_vectors, fetch_flags, fetch_values, bu
     lay = merkle_open_layout(m, dim, depth, with_vectors)
     B = (builder or _Builder)(lay["total"], 0)
     j = np.arange(m, dtype=np.int64)
-    zeros = np.zeros(m, dtype=np.int64)
     base = lay["n_in"] + j * lay["per_read"]
     perm = _perm_placer(B, fetch_flags, fetch_values)
-
-    s = Sym(0, 0)
-    s.g_assert_bit(ext(0))
-    head = Block(s, [s.g_select(ext(1), ext(2), ext(0)), s.g_select(ext(2), ext(1), ext(0))])     # (bit, sibling, cur) -> lo, ro
-    s = Sym(0, 0)
-    acc = s.push(ext(0), depth > 1)
-    for l in range(1, depth):
-        s.push(ext(l))
-        s.push(C(1 << l))
-        acc = s.push(None, l + 1 < depth)
-    ip = Block(s, [acc])
-
-    if with_vectors:
-        state, off = None, 0
-        for p in range(lay["nperm"]):
-            state = perm(base + off, lay["n_ins"][p], state, [j * dim + 2 * p + i for i in range(lay["n_ins"][p])])
-            off += lay["sizes"][p]
-        leaf = state[1]
-    else:
-        leaf = j
-    cur = leaf
-    bits = lay["bits"] + j[:, None] * depth + np.arange(depth, dtype=np.int64)[None, :]
-    for l in range(depth):
-        lb = base + lay["leaf_cells"] + l * lay["level_cells"]
-        lr = B.place(head, lb, zeros, np.stack([bits[:, l], lay["sibs"] + j * depth + l, cur], axis=1))
-        cur = perm(lb + 20 + perm_cells(2), 0, perm(lb + 20, 2, None, [lr[:, 0], lr[:, 1]]), [])[1]
-    idx = B.place(ip, base + lay["leaf_cells"] + depth * lay["level_cells"], zeros, bits)[:, 0]
+    leaf = _place_leaf_sponge(perm, base, lay, [j * dim + k for k in range(dim)])[0] if with_vectors else j
+    path = j[:, None] * depth + np.arange(depth, dtype=np.int64)[None, :]
+    (cur,), idx = _place_path(B, perm, lay, base + lay["leaf_cells"], lay["bits"] + path, lay["sibs"] + path, [leaf])
     for k in range(1, m):
         B.tie(int(cur[k]), int(cur[0]))                      # ctx.constrain_equal(cur, root)
     return B.finish(), merkle_open_instances(m, cur[0], idx, leaf, range(m * dim) if with_vectors else ())

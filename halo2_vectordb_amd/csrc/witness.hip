@@ -940,14 +940,15 @@ __device__ u256 trace_sum(WCtx& c, const FpTables* T, const u256* v, int n, unsi
   }
   return s;
 }
-__device__ u256 trace_ip_const(WCtx& c, const FpTables* T, const u256* a, const u256* row, int n) {  // inner_product(a, constants)
+template <class A>   // inner_product(a, constants), operand i = a(i)
+__device__ __forceinline__ u256 trace_ip_const_of(WCtx& c, A&& a, const u256* row, int n) {
   u256 s;
   int i0, ng;
   if (u256_eq(row[0], mont_one<Fr>())) {
-    s = a[0];
+    s = a(0);
     i0 = 1;
     ng = n - 1;
-    c.push(a[0], ng > 0);
+    c.push(s, ng > 0);
   } else {
     s = u256_zero();
     i0 = 0;
@@ -956,12 +957,16 @@ __device__ u256 trace_ip_const(WCtx& c, const FpTables* T, const u256* a, const 
   }
   int gi = 1;
   for (int i = i0; i < n; i++, gi++) {
-    s = fr_add(s, fr_mul(a[i], row[i]));
-    c.push(a[i], false);
+    const u256 ai = a(i);
+    s = fr_add(s, fr_mul(ai, row[i]));
+    c.push(ai, false);
     c.push(row[i], false, true);  // Constant(matrix entry)
     c.push(s, gi < ng);
   }
   return s;
+}
+__device__ u256 trace_ip_const(WCtx& c, const FpTables* T, const u256* a, const u256* row, int n) {
+  return trace_ip_const_of(c, [a](int i) { return a[i]; }, row, n);
 }
 __device__ void trace_sbox(Gadgets& g, u256& x, const u256& cst) {
   u256 x2 = g.g_mul(x, x);
@@ -1018,7 +1023,55 @@ __device__ __noinline__ WCtx trace_permutation(WCtx c, const FpTables* T, const 
   trace_dense(c, T, st, sp->mds);
   return c;
 }
-HD uint32_t perm_cells(int n_in) { return (n_in == 2 ? 18u : (n_in == 1 ? 15u : 12u)) + 2238u; }
+HD constexpr uint32_t perm_cells(int n_in) { return (n_in == 2 ? 18u : (n_in == 1 ? 15u : 12u)) + 2238u; }
+// a tree node's hash: the permutation absorbing [left, right], then the padding-only one.  A level of a Merkle path: [assert_bit 4 |
+// select 8 | select 8 | node] for the first running digest, [select 8 | select 8 | node] for a second one (the updates' new path)
+constexpr uint32_t NODE_CELLS = perm_cells(2) + perm_cells(0), PATH_HEAD_CELLS = 4 + 2 * 8, PATH_TAIL_CELLS = 2 * 8;
+HD constexpr uint64_t path_level_cells(int sides) { return PATH_HEAD_CELLS + NODE_CELLS + (uint64_t)(sides - 1) * (PATH_TAIL_CELLS + NODE_CELLS); }
+// words that permutation p of the sponge over a leaf of D words absorbs
+HD int leaf_absorbs(size_t D, uint32_t p) { return 2 * (size_t)p < D ? (int)(D - 2 * (size_t)p < 2 ? D - 2 * (size_t)p : 2) : 0; }
+// One permutation of the node hash H(left, right) whose cells start at p0: the absorbing one, or (`second`) the padding-only one behind
+// it, which starts from the state its lane recomputes.  A rank that holds a block of columns emits only the permutations whose cells
+// fall into its stretch of the stream.
+__device__ __forceinline__ void trace_node_half(const Streams& stq, const FpTables* T, const PoseidonSpec* __restrict__ sp, uint64_t p0,
+                                                const u256* left, const u256* right, uint32_t second) {
+  if (second) p0 += perm_cells(2);
+  if (!stq.touches(p0, p0 + (second ? perm_cells(0) : perm_cells(2)), 0, 0)) return;
+  u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
+  u256 in[PSD_RATE] = {*left, *right};
+  if (second) psd_permute_absorb(sp, st, in, 2);   // the padding-only permutation starts where the absorbing one ended
+  WCtx c = make_ctx(stq, T, p0, 0);
+  c = trace_permutation(c, T, sp, st, in, second ? 0 : 2);
+}
+// One part of the level of a Merkle path whose cells start at lb, for SIDES running digests (*cur0, and *cur1 of the updates' new path)
+// against one sibling: part 0 = the bit and every side's two selects, part 1 + 2 * side + second = one permutation of that side's hash
+template <int SIDES>
+__device__ __forceinline__ void trace_path_level(const Streams& stq, const FpTables* T, const PoseidonSpec* __restrict__ sp, uint64_t lb, uint32_t bit,
+                                                 const u256* psib, const u256* cur0, const u256* cur1, uint32_t part) {
+  constexpr uint64_t tail_at = PATH_HEAD_CELLS + NODE_CELLS;
+  if (part == 0) {
+    if (!stq.touches(lb, lb + PATH_HEAD_CELLS, 0, 0) && !(SIDES == 2 && stq.touches(lb + tail_at, lb + tail_at + PATH_TAIL_CELLS, 0, 0))) return;
+    const u256 b = bit ? mont_one<Fr>() : u256_zero();
+    const u256 sib = *psib;
+    WCtx c = make_ctx(stq, T, lb, 0);
+    Gadgets g(c);
+    g.g_assert_bit(b);
+    for (int side = 0; side < SIDES; side++) {
+      const u256 cur = *(side ? cur1 : cur0);
+      g.g_select(sib, cur, b);
+      g.g_select(cur, sib, b);
+      c.pos = lb + tail_at;
+    }
+    return;
+  }
+  const uint32_t side = SIDES == 2 ? (part - 1) >> 1 : 0, second = (part - 1) & 1u;
+  const u256* pcur = side ? cur1 : cur0;
+  trace_node_half(stq, T, sp, lb + (side ? tail_at + PATH_TAIL_CELLS : PATH_HEAD_CELLS), bit ? psib : pcur, bit ? pcur : psib, second);
+}
+// idx = gate.inner_product(bits of `slot`, Constant(2^l)), l < depth, traced from c on
+__device__ u256 trace_path_index(WCtx& c, const FpTables* T, uint32_t slot, uint32_t depth) {
+  return trace_ip_const_of(c, [slot](int l) { return ((slot >> l) & 1u) ? mont_one<Fr>() : u256_zero(); }, T->pow2, (int)depth);
+}
 
 // sponge states before every permutation of every leaf (value only); leaf v's digest goes to leaves[leaf_at[v]] (null: leaves[v])
 __global__ __launch_bounds__(64) void k_mk_leaf_states(const PoseidonSpec* __restrict__ sp, const u256* __restrict__ vectors, uint32_t n, uint32_t D,
@@ -1028,13 +1081,11 @@ __global__ __launch_bounds__(64) void k_mk_leaf_states(const PoseidonSpec* __res
   if (v >= n) return;
   u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
   const u256* msg = vectors + (size_t)v * D;
-  uint32_t off = 0;
   for (uint32_t p = 0; p < nperm; p++) {
     for (int i = 0; i < PSD_T; i++) states[((size_t)v * nperm + p) * PSD_T + i] = st[i];
-    int cnt = off < D ? (int)(D - off < 2 ? D - off : 2) : 0;
-    u256 in[PSD_RATE] = {cnt > 0 ? msg[off] : u256_zero(), cnt > 1 ? msg[off + 1] : u256_zero()};
+    const int cnt = leaf_absorbs(D, p);
+    u256 in[PSD_RATE] = {cnt > 0 ? msg[2 * p] : u256_zero(), cnt > 1 ? msg[2 * p + 1] : u256_zero()};
     psd_permute_absorb(sp, st, in, cnt);
-    off += (uint32_t)cnt;
   }
   leaves[leaf_at ? leaf_at[v] : v] = st[1];
 }
@@ -1045,14 +1096,11 @@ __global__ __launch_bounds__(64) void k_mk_leaf_trace(Streams stq, const FpTable
   uint32_t id = blockIdx.x * 64 + threadIdx.x;
   if (id >= n * nperm) return;
   uint32_t v = id / nperm, p = id % nperm;
-  uint32_t off = 2 * p;
-  int cnt = off < D ? (int)(D - off < 2 ? D - off : 2) : 0;
+  const uint32_t off = 2 * p;
+  const int cnt = leaf_absorbs(D, p);
   // permutations 0..p-1 of a leaf are full (2 inputs) except possibly the one before the padding-only one
   uint64_t pos = base + (starts ? starts[v] : (uint64_t)v * leaf_cells);
-  for (uint32_t q = 0; q < p; q++) {
-    uint32_t o = 2 * q;
-    pos += perm_cells(o < D ? (int)(D - o < 2 ? D - o : 2) : 0);
-  }
+  for (uint32_t q = 0; q < p; q++) pos += perm_cells(leaf_absorbs(D, q));
   // a rank that holds a block of columns emits only the permutations whose cells fall into its stretch of the stream
   // (the sponge states they start from were computed by k_mk_leaf_states)
   if (!stq.touches(pos, pos + perm_cells(cnt), 0, 0)) return;
@@ -1078,7 +1126,7 @@ __global__ __launch_bounds__(64) void k_mk_level_values(const PoseidonSpec* __re
   out_lv[t] = st[1];
 }
 // levels: level 0 = the lp (padded) leaf digests, level l at offset lp (2 - 2^(1-l)) ... i.e. one after the other; node g of the
-// tree (level-major numbering, g < lp - 1) has its cells at base + g * (perm_cells(2) + perm_cells(0))
+// tree (level-major numbering, g < lp - 1) has its cells at base + g * NODE_CELLS
 __global__ __launch_bounds__(64) void k_mk_tree_trace(Streams stq, const FpTables* __restrict__ T, const PoseidonSpec* __restrict__ sp,
                                                       const u256* __restrict__ levels, uint32_t lp, uint64_t base) {
   const uint32_t id = blockIdx.x * 64 + threadIdx.x;
@@ -1092,15 +1140,8 @@ __global__ __launch_bounds__(64) void k_mk_tree_trace(Streams stq, const FpTable
     in_sz = sz;
     sz >>= 1;
   }
-  const uint32_t t = g - first;
-  const uint64_t p0 = base + (uint64_t)g * (perm_cells(2) + perm_cells(0)) + (j ? perm_cells(2) : 0);
-  const uint32_t cells = j ? perm_cells(0) : perm_cells(2);
-  if (!stq.touches(p0, p0 + cells, 0, 0)) return;
-  u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
-  u256 in[PSD_RATE] = {levels[in_off + 2 * t], levels[in_off + 2 * t + 1]};
-  if (j) psd_permute_absorb(sp, st, in, 2);   // the padding-only permutation starts where the absorbing one ended
-  WCtx c = make_ctx(stq, T, p0, 0);
-  c = trace_permutation(c, T, sp, st, in, j ? 0 : 2);
+  const u256* in = levels + in_off + 2 * (g - first);
+  trace_node_half(stq, T, sp, base + (uint64_t)g * NODE_CELLS, in, in + 1, j);
 }
 
 // ------------------------------------------------------------------ Merkle path updates (include/vdb.h vdb_wit_merkle_update)
@@ -1116,9 +1157,14 @@ __global__ __launch_bounds__(64) void k_mk_tree_trace(Streams stq, const FpTable
 // the growth, and a growth block follows them: [Z_0 = load_constant(0) | Z_{l+1} = H(Z_l, Z_l), l < depth - 1 | R_{i+1} = H(R_i, Z_{d+i}),
 // i < grow] (k_mku_grow_trace), d the depth before the growth.  A plain batch is all writes and grow = 0.
 #define MKU_MAX_UPDATES 4096
-struct MkuLayout {
-  uint32_t m, w, D, depth, d0, grow, nperm;  // w: the writes among the m updates; depth = d0 + grow
-  uint64_t leaf_cells, level_cells, ip_cells, n_vec, n_wit, n_in, grow_cells, total;  // n_in = n_vec + n_wit (+ 1: R_0 when grow)
+// what the stream of a path circuit is made of, for updates and reads alike (path_layout): the leaf sponge, a level, the index
+struct PathLayout {
+  uint32_t D, depth, nperm;
+  uint64_t leaf_cells, level_cells, ip_cells;
+};
+struct MkuLayout : PathLayout {
+  uint32_t m, w, d0, grow;  // w: the writes among the m updates; depth = d0 + grow
+  uint64_t n_vec, n_wit, n_in, grow_cells, total;  // n_in = n_vec + n_wit (+ 1: R_0 when grow)
 };
 HD uint64_t mku_level_off(uint64_t lp, uint32_t l) { return 2 * (lp - (lp >> l)); }
 // per (level, update), arrays indexed [l * m + j]: sib_from = the latest earlier update whose path holds this one's sibling node at
@@ -1223,47 +1269,23 @@ __global__ __launch_bounds__(64) void k_mku_level_trace(Streams stq, const FpTab
   const uint32_t m = ml.m, depth = ml.depth;
   if (t >= m * depth) return;
   const uint32_t j = t / depth, l = t % depth;
-  const uint64_t H = perm_cells(2) + perm_cells(0);
   const uint64_t lb = base + level_at[j] + (uint64_t)l * ml.level_cells;
-  const uint32_t bit = (idx[j] >> l) & 1u;
-  const u256* psib = wit + ((size_t)m + (size_t)m * depth + (size_t)j * depth + l);
-  WCtx c = make_ctx(stq, T, lb, 0);
-  if (part == 0) {
-    if (!stq.touches(lb, lb + 20, 0, 0) && !stq.touches(lb + 20 + H, lb + 36 + H, 0, 0)) return;
-    const u256 b = bit ? mont_one<Fr>() : u256_zero();
-    const u256 sib = *psib;
-    Gadgets g(c);
-    g.g_assert_bit(b);
-    for (int side = 0; side < 2; side++) {
-      const u256 cur = (side ? path_new : path_old)[(size_t)l * m + j];
-      g.g_select(sib, cur, b);
-      g.g_select(cur, sib, b);
-      c.pos = lb + 20 + H;
-    }
-    return;
-  }
-  const uint32_t side = (part - 1) >> 1, second = (part - 1) & 1u;
-  c.pos = lb + 20 + (side ? H + 16 : 0) + (second ? perm_cells(2) : 0);
-  if (!stq.touches(c.pos, c.pos + (second ? perm_cells(0) : perm_cells(2)), 0, 0)) return;
-  const u256* pcur = (side ? path_new : path_old) + ((size_t)l * m + j);
-  u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
-  u256 in[PSD_RATE] = {*(bit ? psib : pcur), *(bit ? pcur : psib)};
-  if (second) psd_permute_absorb(sp, st, in, 2);   // the padding-only permutation starts where the absorbing one ended
-  c = trace_permutation(c, T, sp, st, in, second ? 0 : 2);
+  trace_path_level<2>(stq, T, sp, lb, (idx[j] >> l) & 1u, wit + ((size_t)m + (size_t)m * depth + (size_t)j * depth + l), path_old + ((size_t)l * m + j),
+                      path_new + ((size_t)l * m + j), part);
 }
 // idx_j = gate.inner_product(bits, Constant(2^l)) per update, a delete's load_constant(0) cell in front of its levels, and the public
 // values [old root | idx, old leaf, new leaf per update | new root] (the old root of a grown tree is R_0: k_mku_grow_trace's)
 __global__ __launch_bounds__(64) void k_mku_index(Streams stq, const FpTables* __restrict__ T, MkuLayout ml, uint64_t base,
-                                                  const uint64_t* __restrict__ level_at, const int32_t* __restrict__ write_no, const u256* __restrict__ wit,
-                                                  const u256* __restrict__ path_old, const u256* __restrict__ path_new, u256* __restrict__ pub) {
+                                                  const uint64_t* __restrict__ level_at, const uint32_t* __restrict__ idx,
+                                                  const int32_t* __restrict__ write_no, const u256* __restrict__ wit, const u256* __restrict__ path_old,
+                                                  const u256* __restrict__ path_new, u256* __restrict__ pub) {
   const uint32_t j = blockIdx.x * 64 + threadIdx.x;
   const uint32_t m = ml.m, depth = ml.depth;
   if (j >= m) return;
   WCtx c = make_ctx(stq, T, base + level_at[j] - 1, 0);
   if (write_no[j] < 0) c.push(u256_zero(), false, true);
   c.pos = base + level_at[j] + (uint64_t)depth * ml.level_cells;
-  const u256 s = trace_ip_const(c, T, wit + (size_t)m + (size_t)j * depth, T->pow2, (int)depth);
-  pub[1 + 3 * (size_t)j] = s;
+  pub[1 + 3 * (size_t)j] = trace_path_index(c, T, idx[j], depth);   // (the assigned bits are those of idx_j: k_mku_level)
   pub[2 + 3 * (size_t)j] = wit[j];
   pub[3 + 3 * (size_t)j] = path_new[j];
   if (j == 0 && !ml.grow) pub[0] = path_old[(size_t)depth * m];
@@ -1287,14 +1309,8 @@ __global__ __launch_bounds__(64) void k_mku_grow_trace(Streams stq, const FpTabl
     c.push(u256_zero(), false, true);
   }
   const uint32_t h = t >> 1, second = t & 1u;
-  const uint64_t p0 = gb + 1 + (uint64_t)h * (perm_cells(2) + perm_cells(0)) + (second ? perm_cells(2) : 0);
-  if (!stq.touches(p0, p0 + (second ? perm_cells(0) : perm_cells(2)), 0, 0)) return;
   const uint32_t lz = h < n_z ? h : ml.d0 + (h - n_z);
-  u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
-  u256 in[PSD_RATE] = {h < n_z ? empty[lz] : levels[mku_level_off(lp, lz)], empty[lz]};
-  if (second) psd_permute_absorb(sp, st, in, 2);   // the padding-only permutation starts where the absorbing one ended
-  WCtx c = make_ctx(stq, T, p0, 0);
-  c = trace_permutation(c, T, sp, st, in, second ? 0 : 2);
+  trace_node_half(stq, T, sp, gb + 1 + (uint64_t)h * NODE_CELLS, h < n_z ? empty + lz : levels + mku_level_off(lp, lz), empty + lz, second);
 }
 
 // ------------------------------------------------------------------ growing the resident tree (include/vdb.h vdb_merkle_tree_grow_dev)
@@ -1321,9 +1337,9 @@ __global__ __launch_bounds__(256) void k_mk_tree_grow(const u256* __restrict__ o
 // [vectors m * D (vector mode) or leaves m (leaf mode) | bits | siblings] (the assigned witnesses), then per read its leaf sponge
 // (vector mode only), per level [assert_bit | select lo | select ro | H(lo, ro)], and the index inner product.  No value pass hashes a
 // path node: the digest of read j at level l and its sibling are levels[mku_level_off(lp, l) + (idx_j >> l)] and its neighbour.
-struct MkoLayout {
-  uint32_t m, D, depth, nperm, with_vectors;
-  uint64_t leaf_cells, level_cells, ip_cells, per_read, n_lead, n_in, total;
+struct MkoLayout : PathLayout {
+  uint32_t m, with_vectors;
+  uint64_t per_read, n_lead, n_in, total;
 };
 // ctx.assign_witnesses of the three input groups: plain cells, no gate, a lane per cell
 __global__ __launch_bounds__(256) void k_mko_inputs(Streams st, uint64_t base, MkoLayout ml, uint64_t lp, const u256* __restrict__ vectors,
@@ -1355,27 +1371,8 @@ __global__ __launch_bounds__(64) void k_mko_level_trace(Streams stq, const FpTab
   if (t >= ml.m * depth) return;
   const uint32_t j = t / depth, l = t % depth;
   const uint64_t lb = base + ml.n_in + (uint64_t)j * ml.per_read + ml.leaf_cells + (uint64_t)l * ml.level_cells;
-  const uint32_t node = idx[j] >> l, bit = node & 1u;
-  const u256* pcur = levels + mku_level_off(lp, l) + node;
-  const u256* psib = levels + mku_level_off(lp, l) + (node ^ 1u);
-  WCtx c = make_ctx(stq, T, lb, 0);
-  if (part == 0) {
-    if (!stq.touches(lb, lb + 20, 0, 0)) return;
-    const u256 b = bit ? mont_one<Fr>() : u256_zero();
-    const u256 cur = *pcur, sib = *psib;
-    Gadgets g(c);
-    g.g_assert_bit(b);
-    g.g_select(sib, cur, b);
-    g.g_select(cur, sib, b);
-    return;
-  }
-  const uint32_t second = part - 1;
-  c.pos = lb + 20 + (second ? perm_cells(2) : 0);
-  if (!stq.touches(c.pos, c.pos + (second ? perm_cells(0) : perm_cells(2)), 0, 0)) return;
-  u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
-  u256 in[PSD_RATE] = {*(bit ? psib : pcur), *(bit ? pcur : psib)};
-  if (second) psd_permute_absorb(sp, st, in, 2);   // the padding-only permutation starts where the absorbing one ended
-  c = trace_permutation(c, T, sp, st, in, second ? 0 : 2);
+  const uint32_t node = idx[j] >> l;
+  trace_path_level<1>(stq, T, sp, lb, node & 1u, levels + mku_level_off(lp, l) + (node ^ 1u), levels + mku_level_off(lp, l) + node, nullptr, part);
 }
 // idx_j = gate.inner_product(bits, Constant(2^l)) per read, and the public values [root | idx, leaf per read | the vectors word by word]
 // (vleaf: the sponges' digests, k_mk_leaf_states; null in leaf mode, where the leaf is the assigned one)
@@ -1386,10 +1383,8 @@ __global__ __launch_bounds__(64) void k_mko_index(Streams stq, const FpTables* _
   const uint32_t m = ml.m, depth = ml.depth;
   if (j >= m) return;
   const uint32_t slot = idx[j];
-  u256 bits[30];
-  for (uint32_t l = 0; l < depth; l++) bits[l] = ((slot >> l) & 1u) ? mont_one<Fr>() : u256_zero();
   WCtx c = make_ctx(stq, T, base + ml.n_in + (uint64_t)j * ml.per_read + ml.leaf_cells + (uint64_t)depth * ml.level_cells, 0);
-  pub[1 + 2 * (size_t)j] = trace_ip_const(c, T, bits, T->pow2, (int)depth);
+  pub[1 + 2 * (size_t)j] = trace_path_index(c, T, slot, depth);
   pub[2 + 2 * (size_t)j] = vleaf ? vleaf[j] : levels[slot];
   if (j == 0) pub[0] = levels[mku_level_off(lp, depth)];
   if (ml.with_vectors)
@@ -1689,23 +1684,23 @@ int wit_kmeans_dev(FpEntry* fp, int metric, const u256* vectors, size_t n, size_
   return inv_list_fixup(st);
 }
 
+// the tree over n leaves: its padded leaf count and its depth
+static void tree_shape(uint64_t n, uint64_t* lp, uint32_t* depth) {
+  for (*lp = 1, *depth = 0; *lp < n; *lp <<= 1) ++*depth;
+}
 struct MkLayout {
-  uint32_t nperm;
+  uint32_t nperm, depth;
   uint64_t leaf_cells, leaves, n_leaves_pow2, zero_cell, total;
 };
 static void mk_layout(size_t n, size_t dim, int zero_cached, MkLayout* o) {
   o->nperm = (uint32_t)((dim + 1) / 2 + (dim % 2 == 0 ? 1 : 0));
   o->leaf_cells = 0;
-  for (uint32_t p = 0; p < o->nperm; p++) {
-    size_t off = 2 * (size_t)p;
-    o->leaf_cells += perm_cells(off < dim ? (int)(dim - off < 2 ? dim - off : 2) : 0);
-  }
+  for (uint32_t p = 0; p < o->nperm; p++) o->leaf_cells += perm_cells(leaf_absorbs(dim, p));
   o->leaves = n * o->leaf_cells;
-  uint64_t lp = 1;
-  while (lp < n) lp <<= 1;
-  o->n_leaves_pow2 = lp;
+  tree_shape(n, &o->n_leaves_pow2, &o->depth);
+  const uint64_t lp = o->n_leaves_pow2;
   o->zero_cell = (lp > n && !zero_cached) ? 1 : 0;
-  o->total = o->leaves + o->zero_cell + (lp - 1) * (uint64_t)(perm_cells(2) + perm_cells(0));
+  o->total = o->leaves + o->zero_cell + (lp - 1) * (uint64_t)NODE_CELLS;
 }
 // The digests of every level of merkle_commitment's tree, values only, into `levels` in k_mk_tree_trace's layout: the lp padded leaf
 // digests, then the levels one after the other (lp + lp / 2 + ... + 1 of the 2 lp entries, the last unused); the root is at *root_off.
@@ -1748,13 +1743,17 @@ static int mk_emit(FpEntry* fp, const PoseidonSpec* sp, const u256* vectors, siz
   if (root_out) VDB_HIP(hipMemcpyAsync(root_out, lv + root_off, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
   return VDB_OK;
 }
+// what a Poseidon-only witness call starts with: the gate tables, the call's context published, the permutation's constants
+static int mk_begin(const Streams& st, FpEntry** fp, const PoseidonSpec** sp) {
+  TRY(get_fp(48, 13, fp));  // only GateChip primitives are used: P and L are irrelevant
+  TRY(set_winv(st, (*fp)->dev));
+  return poseidon_spec_dev(sp, nullptr);
+}
 int wit_merkle_dev(const u256* vectors, size_t n, size_t dim, int zero_cached, Streams st, u256* root_out) {
   VDB_ARG(n <= ((size_t)1 << 30), "tree deeper than 30 levels");
   FpEntry* fp;
-  TRY(get_fp(48, 13, &fp));  // only GateChip primitives are used: P and L are irrelevant
-  TRY(set_winv(st, fp->dev));
   const PoseidonSpec* sp;
-  TRY(poseidon_spec_dev(&sp, nullptr));
+  TRY(mk_begin(st, &fp, &sp));
   MkLayout ml;
   mk_layout(n, dim, zero_cached, &ml);
   return mk_emit(fp, sp, vectors, n, dim, ml, st, 0, nullptr, root_out);
@@ -1775,9 +1774,9 @@ int merkle_tree_build_dev(const u256* vectors, size_t n, size_t dim, u256* level
 // the tree of vdb_merkle_tree_build_dev with its padded leaf count doubled `grow` times, the new slots empty, into `grown`
 int merkle_tree_grow_dev(const u256* levels, size_t n, unsigned grow, u256* grown) {
   VDB_ARG(n > 0 && n <= ((size_t)1 << 30), "empty database or tree deeper than 30 levels");
-  uint64_t lp = 1;
-  uint32_t d = 0;
-  while (lp < n) lp <<= 1, d++;
+  uint64_t lp;
+  uint32_t d;
+  tree_shape(n, &lp, &d);
   VDB_ARG(d + (uint64_t)grow <= 30, "grown tree deeper than 30 levels");
   const PoseidonSpec* sp;
   TRY(poseidon_spec_dev(&sp, nullptr));
@@ -1790,42 +1789,47 @@ int merkle_tree_grow_dev(const u256* levels, size_t n, unsigned grow, u256* grow
   return VDB_OK;
 }
 
+// The part of a path circuit's layout that updates (sides = 2: an old and a new running digest per level) and reads (sides = 1) share,
+// with the limits both have (include/vdb.h): a tree over n vectors of `dim` words, doubled `grow` times; *lp: its padded leaf count
+static int path_layout(size_t n, size_t dim, unsigned grow, int sides, PathLayout* o, uint64_t* lp) {
+  VDB_ARG(n > 0 && dim > 0, "empty database");
+  VDB_ARG(n <= ((size_t)1 << 30) && dim <= ((size_t)1 << 20), "tree deeper than 30 levels or vector longer than 2^20 words");
+  MkLayout ml;
+  mk_layout(n, dim, 0, &ml);
+  VDB_ARG(ml.depth + (uint64_t)grow <= 30, "grown tree deeper than 30 levels");
+  o->D = (uint32_t)dim;
+  o->depth = ml.depth + (uint32_t)grow;
+  VDB_ARG(o->depth >= 1, "a tree of one leaf has no path (depth 0)");
+  o->nperm = ml.nperm;
+  o->leaf_cells = ml.leaf_cells;
+  o->level_cells = path_level_cells(sides);
+  o->ip_cells = 1 + 3 * (uint64_t)(o->depth - 1);
+  *lp = ml.n_leaves_pow2 << grow;
+  return VDB_OK;
+}
 // sizes of a batch of m path updates (kinds: 0 write, 1 delete; null: all writes) in a tree over n vectors grown `grow` times; the
 // limits of one call (include/vdb.h).  level_at (m; null: not wanted): where the levels of update j start in the stream, behind its
 // leaf sponge or its zero cell; write_no (m): the row of new_vectors update j writes, -1 for a delete.
 static int mku_layout(size_t n, size_t dim, size_t m, const uint8_t* kinds, unsigned grow, MkuLayout* o, uint64_t* lp_out, uint64_t* level_at,
                       int32_t* write_no) {
-  VDB_ARG(n > 0 && dim > 0, "empty database");
+  uint64_t lp;
+  TRY(path_layout(n, dim, grow, 2, o, &lp));
   VDB_ARG(m > 0, "a batch holds at least one update");
   VDB_ARG(m <= MKU_MAX_UPDATES, "more than VDB_MERKLE_UPDATE_MAX_UPDATES updates in one call");
-  VDB_ARG(n <= ((size_t)1 << 30) && dim <= ((size_t)1 << 20), "tree deeper than 30 levels or vector longer than 2^20 words");
-  MkLayout ml;
-  mk_layout(n, dim, 0, &ml);
-  uint32_t d0 = 0;
-  while (((uint64_t)1 << d0) < ml.n_leaves_pow2) d0++;
-  VDB_ARG(d0 + (uint64_t)grow <= 30, "grown tree deeper than 30 levels");
-  const uint32_t depth = d0 + (uint32_t)grow;
-  VDB_ARG(depth >= 1, "a tree of one leaf has no path (depth 0)");
+  const uint32_t depth = o->depth;
   size_t w = 0;
   for (size_t j = 0; j < m; j++) {
     VDB_ARG(!kinds || kinds[j] <= 1, "an update is a write (0) or a delete (1)");
     w += !kinds || kinds[j] == 0;
   }
-  const uint64_t H = perm_cells(2) + perm_cells(0);
   o->m = (uint32_t)m;
   o->w = (uint32_t)w;
-  o->D = (uint32_t)dim;
-  o->depth = depth;
-  o->d0 = d0;
+  o->d0 = depth - (uint32_t)grow;
   o->grow = (uint32_t)grow;
-  o->nperm = ml.nperm;
-  o->leaf_cells = ml.leaf_cells;
-  o->level_cells = 4 + 4 * 8 + 2 * H;
-  o->ip_cells = 1 + 3 * (uint64_t)(depth - 1);
   o->n_vec = (uint64_t)w * dim;
   o->n_wit = (uint64_t)m * (1 + 2 * (uint64_t)depth);
   o->n_in = o->n_vec + o->n_wit + (grow ? 1 : 0);
-  o->grow_cells = grow ? 1 + (uint64_t)(depth - 1 + grow) * H : 0;
+  o->grow_cells = grow ? 1 + (uint64_t)(depth - 1 + grow) * NODE_CELLS : 0;
   uint64_t at = o->n_in + o->grow_cells;
   int32_t wn = 0;
   for (size_t j = 0; j < m; j++) {
@@ -1836,8 +1840,8 @@ static int mku_layout(size_t n, size_t dim, size_t m, const uint8_t* kinds, unsi
     at += depth * o->level_cells + o->ip_cells;
   }
   o->total = at;
-  VDB_ARG(o->total <= ((uint64_t)1 << 34) && (uint64_t)m * ml.nperm <= ((uint64_t)1 << 30), "more than VDB_MERKLE_UPDATE_MAX_CELLS cells in one call");
-  if (lp_out) *lp_out = ml.n_leaves_pow2 << grow;
+  VDB_ARG(o->total <= ((uint64_t)1 << 34) && (uint64_t)m * o->nperm <= ((uint64_t)1 << 30), "more than VDB_MERKLE_UPDATE_MAX_CELLS cells in one call");
+  if (lp_out) *lp_out = lp;
   return VDB_OK;
 }
 // `levels`: the tree at depth d + grow (merkle_tree_grow_dev's when grow > 0), left in the state after the batch; new_vectors: the rows of
@@ -1874,10 +1878,8 @@ int wit_merkle_update_dev(u256* levels, size_t n, size_t dim, unsigned grow, con
     }
   }
   FpEntry* fp;
-  TRY(get_fp(48, 13, &fp));  // only GateChip primitives are used: P and L are irrelevant
-  TRY(set_winv(st, fp->dev));
   const PoseidonSpec* sp;
-  TRY(poseidon_spec_dev(&sp, nullptr));
+  TRY(mk_begin(st, &fp, &sp));
   const u256* empty = nullptr;
   if (grow) TRY(poseidon_empty_subtrees_dev(&empty));
   hipStream_t s = ctx().stream;
@@ -1914,31 +1916,21 @@ int wit_merkle_update_dev(u256* levels, size_t n, size_t dim, unsigned grow, con
   VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((w * ml.nperm + 63) / 64 + (w == 0))), dim3(64), st, fp->dev, sp, new_vectors, wu, (uint32_t)dim, ml.nperm, 0,
              ml.leaf_cells, states, leaf_at);
   VDB_LAUNCH(k_mku_level_trace, dim3((unsigned)((m * depth + 63) / 64), 5), dim3(64), st, fp->dev, sp, ml, 0, level_at, didx, wit, path_old, path_new);
-  VDB_LAUNCH(k_mku_index, dim3((unsigned)((m + 63) / 64)), dim3(64), st, fp->dev, ml, 0, level_at, write_no, wit, path_old, path_new, pub);
+  VDB_LAUNCH(k_mku_index, dim3((unsigned)((m + 63) / 64)), dim3(64), st, fp->dev, ml, 0, level_at, didx, write_no, wit, path_old, path_new, pub);
   return VDB_OK;
 }
 
 // sizes of m openings in a tree over n vectors; the limits of one call (include/vdb.h).  No cap on m beyond the cell count: nothing
 // is scanned in LDS.
 static int mko_layout(size_t n, size_t dim, size_t m, int with_vectors, MkoLayout* o, uint64_t* lp_out) {
-  VDB_ARG(n > 0 && dim > 0, "empty database");
+  uint64_t lp;
+  TRY(path_layout(n, dim, 0, 1, o, &lp));
   VDB_ARG(m > 0, "a call opens at least one slot");
-  VDB_ARG(n <= ((size_t)1 << 30) && dim <= ((size_t)1 << 20), "tree deeper than 30 levels or vector longer than 2^20 words");
-  MkLayout ml;
-  mk_layout(n, dim, 0, &ml);
-  const uint64_t lp = ml.n_leaves_pow2;
-  uint32_t depth = 0;
-  while (((uint64_t)1 << depth) < lp) depth++;
-  VDB_ARG(depth >= 1, "a tree of one leaf has no path (depth 0)");
+  const uint32_t depth = o->depth;
   VDB_ARG(m < ((size_t)1 << 31) && (uint64_t)m * depth < ((uint64_t)1 << 31), "2^31 or more (read, level) pairs in one call");
   o->m = (uint32_t)m;
-  o->D = (uint32_t)dim;
-  o->depth = depth;
   o->with_vectors = with_vectors ? 1u : 0u;
-  o->nperm = with_vectors ? ml.nperm : 0;
-  o->leaf_cells = with_vectors ? ml.leaf_cells : 0;
-  o->level_cells = 4 + 2 * 8 + (uint64_t)(perm_cells(2) + perm_cells(0));
-  o->ip_cells = 1 + 3 * (uint64_t)(depth - 1);
+  if (!with_vectors) o->nperm = 0, o->leaf_cells = 0;   // leaf mode: the leaf is assigned, no sponge
   o->per_read = o->leaf_cells + depth * o->level_cells + o->ip_cells;
   o->n_lead = with_vectors ? (uint64_t)m * dim : (uint64_t)m;
   o->n_in = o->n_lead + 2 * (uint64_t)m * depth;
@@ -1964,10 +1956,8 @@ int wit_merkle_open_dev(const u256* levels, size_t n, size_t dim, const u256* ve
   hidx.resize(m);
   for (size_t j = 0; j < m; j++) hidx[j] = (uint32_t)indices[j];
   FpEntry* fp;
-  TRY(get_fp(48, 13, &fp));  // only GateChip primitives are used: P and L are irrelevant
-  TRY(set_winv(st, fp->dev));
   const PoseidonSpec* sp;
-  TRY(poseidon_spec_dev(&sp, nullptr));
+  TRY(mk_begin(st, &fp, &sp));
   const size_t n_states = m * ml.nperm * PSD_T, n_leaf = vectors ? m : 0;
   u256* states = (u256*)scratch_get(0, (n_states + n_leaf) * sizeof(u256) + m * sizeof(uint32_t) + 64);
   if (!states) return VDB_ERR_OOM;
@@ -2011,9 +2001,9 @@ static int ann_forest_plan(const uint32_t* ids, size_t n, size_t K, AnnForest* f
   for (size_t s = 0; s <= K; s++) {
     const uint64_t m = s < K ? cnt[s] : K;
     VDB_ARG(m > 0, "empty cluster: merkle_commitment is undefined over zero vectors");
-    uint64_t lp = 1;
-    uint32_t d = 0;
-    while (lp < m) lp <<= 1, d++;
+    uint64_t lp;
+    uint32_t d;
+    tree_shape(m, &lp, &d);
     f->seg_lp[s] = (uint32_t)lp;
     f->seg_off[s + 1] = f->seg_off[s] + 2 * lp;
     if (d > f->depth) f->depth = d;

@@ -715,16 +715,43 @@ class KmeansHotPath(HotPath):
         return cm, np.asarray(cent).reshape(-1), None
 
 
-class MerkleHotPath(HotPath):
+class PoseidonHotPath(HotPath):
+    """What the circuits made of Poseidon permutations alone share (the commitment, path updates, openings): no lookup cells, and every
+    column is dense (Poseidon states), so equal column counts per rank are balanced already."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.balance_shards = False
+        self.msm_window_bits = 14   # nearly every scalar is a full-width Poseidon state: 19 windows instead of 24
+
+    def _load_tree(self, d_out, lp, levels):
+        """The resident tree over the n database vectors (api.merkle_tree_build's layout, 2 lp digests) into d_out: `levels` a
+        DeviceBuffer (copied), a (2 lp, 4) array (uploaded), or None: built from self.database_f64."""
+        if isinstance(levels, api.DeviceBuffer):
+            check(self.lib.vdb_memcpy_d2d(d_out.ptr, levels.ptr, ctypes.c_size_t(2 * lp * B)))
+        elif levels is not None:
+            levels = np.ascontiguousarray(levels, dtype=np.uint64)
+            assert levels.shape == (2 * lp, 4), "the tree does not belong to this shape"
+            d_out.upload(levels)
+        else:
+            assert self.database_f64.shape == (self.n, self.dim), "database rows do not match the circuit's shape"
+            qdb = api.quantize(self.database_f64, self.P)
+            d_db = api.DeviceBuffer(qdb.nbytes)
+            try:
+                d_db.upload(qdb)
+                check(self.lib.vdb_merkle_tree_build_dev(d_db.ptr, self.n, self.dim, d_out.ptr))
+                api.sync()
+            finally:
+                d_db.free()
+
+
+class MerkleHotPath(PoseidonHotPath):
     """merkle_commitment over N x D vectors (src/gadget/vectordb.rs:165-223; examples/merkle.rs) through the same hot
-    path: Poseidon trace on the GPU -> commit -> NTT.  No lookup cells; every column is dense (Poseidon states), so equal
-    column counts per rank are balanced already; a rank that holds a block of columns traces only the permutations whose
+    path: Poseidon trace on the GPU -> commit -> NTT.  A rank that holds a block of columns traces only the permutations whose
     cells fall into it (the sponge states and the tree's digests are computed by every rank, value only)."""
 
     def __init__(self, n=1024, dim=128, k=15, P=32, seed=20260003, tau=None, col_shard=(0, 1), vectors=None, blind_seed=None, params=None):
         super().__init__(n, dim, k, P, 8, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors, blind_seed=blind_seed, params=params)
-        self.balance_shards = False
-        self.msm_window_bits = 14   # every scalar is a full-width Poseidon state: 19 windows instead of 24
 
     def _input_vectors(self):
         return sift_like_vectors(self.seed, self.n, self.dim)
@@ -752,7 +779,7 @@ class MerkleHotPath(HotPath):
         return cm, [root], root                    # examples/merkle.rs:47 make_public.push(root)
 
 
-class UpdateHotPath(HotPath):
+class UpdateHotPath(PoseidonHotPath):
     """Inserts and replacements proved against the committed root: a batch of m Merkle path updates in one proof (include/vdb.h
     vdb_wit_merkle_update).  The reference has no such gadget: this is the closure a user of its chips writes.  Assigned witnesses:
     the m new vectors, per update the old leaf, the index bits and the siblings; then per update the leaf hash of the new vector, both
@@ -786,8 +813,6 @@ class UpdateHotPath(HotPath):
         self.m = m
         self.database_f64 = None if vectors is None else np.ascontiguousarray(vectors, dtype=np.float64)
         self.given_levels, self.given_updates = levels, updates
-        self.balance_shards = False
-        self.msm_window_bits = 14   # as MerkleHotPath: nearly every scalar is a full-width Poseidon state
 
     def n_input_rows(self):
         return self.w
@@ -816,26 +841,9 @@ class UpdateHotPath(HotPath):
         self.d_levels = self._output(2 * self.lp * B)
         # the tree before the growth: straight into d_levels0 when it is not grown, else into d_levels, which every run overwrites
         d_small = self.d_levels if self.grow else self.d_levels0
-        if self.given_levels is not None:
-            lv = self.given_levels
-            if isinstance(lv, api.DeviceBuffer):
-                check(self.lib.vdb_memcpy_d2d(d_small.ptr, lv.ptr, ctypes.c_size_t(2 * self.lp0 * B)))
-            else:
-                lv = np.ascontiguousarray(lv, dtype=np.uint64)
-                assert lv.shape == (2 * self.lp0, 4), "the tree does not belong to this shape"
-                d_small.upload(lv)
-        else:
-            if self.database_f64 is None:
-                self.database_f64, _ = sift_like_vectors(self.seed, self.n, self.dim)
-            assert self.database_f64.shape == (self.n, self.dim), "database rows do not match the circuit's shape"
-            qdb = api.quantize(self.database_f64, self.P)
-            d_db = api.DeviceBuffer(qdb.nbytes)
-            try:
-                d_db.upload(qdb)
-                check(self.lib.vdb_merkle_tree_build_dev(d_db.ptr, self.n, self.dim, d_small.ptr))
-                api.sync()
-            finally:
-                d_db.free()
+        if self.given_levels is None and self.database_f64 is None:
+            self.database_f64, _ = sift_like_vectors(self.seed, self.n, self.dim)
+        self._load_tree(d_small, self.lp0, self.given_levels)
         if self.grow:
             check(self.lib.vdb_merkle_tree_grow_dev(d_small.ptr, self.n, self.grow, self.d_levels0.ptr))
             api.sync()
@@ -875,7 +883,7 @@ class UpdateHotPath(HotPath):
         return cm, pub, None
 
 
-class ReadHotPath(HotPath):
+class ReadHotPath(PoseidonHotPath):
     """Reads proved against the committed root: m openings of the resident tree in one proof (include/vdb.h vdb_wit_merkle_open).  The
     reference has no such gadget: this is the closure a user of its chips writes.  reveal="vector": the m vectors read are assigned,
     hashed (merkle_commitment's leaf hash) and public, "slot i holds vector v"; reveal="leaf": the leaf digest is assigned and
@@ -907,8 +915,6 @@ class ReadHotPath(HotPath):
         if self.database_f64 is not None and self.database_f64.shape != (self.n, self.dim):
             raise ValueError("database rows do not match the circuit's shape")
         self.given_levels, self.given_reads = levels, reads
-        self.balance_shards = False
-        self.msm_window_bits = 14   # as MerkleHotPath: nearly every scalar is a full-width Poseidon state
 
     def n_input_rows(self):
         return self.m if self.with_vectors else 0
@@ -930,22 +936,7 @@ class ReadHotPath(HotPath):
     def _load_inputs(self):
         super()._load_inputs()
         self.d_levels = self._output(2 * self.lp * B)
-        lv = self.given_levels
-        if isinstance(lv, api.DeviceBuffer):
-            check(self.lib.vdb_memcpy_d2d(self.d_levels.ptr, lv.ptr, ctypes.c_size_t(2 * self.lp * B)))
-        elif lv is not None:
-            lv = np.ascontiguousarray(lv, dtype=np.uint64)
-            assert lv.shape == (2 * self.lp, 4), "the tree does not belong to this shape"
-            self.d_levels.upload(lv)
-        else:
-            qdb = api.quantize(self.database_f64, self.P)
-            d_db = api.DeviceBuffer(qdb.nbytes)
-            try:
-                d_db.upload(qdb)
-                check(self.lib.vdb_merkle_tree_build_dev(d_db.ptr, self.n, self.dim, self.d_levels.ptr))
-                api.sync()
-            finally:
-                d_db.free()
+        self._load_tree(self.d_levels, self.lp, self.given_levels)
 
     def _circuit_size(self):
         cells, n_in = ctypes.c_uint64(), ctypes.c_uint64()

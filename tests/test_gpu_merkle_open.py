@@ -139,8 +139,9 @@ def test_two_windowed_calls_write_the_bytes_of_one(api, O, with_vectors):
     lk = np.zeros((0, 4), dtype=np.uint64)
     lay = CS.merkle_open_layout(len(idx), dim, 3, with_vectors)
     level1 = lay["n_in"] + lay["per_read"] + lay["leaf_cells"] + lay["level_cells"]        # read 1, level 1
-    # inside the inputs, inside a leaf sponge (vector mode), inside a level's select block, inside its second permutation, two from the end
-    cuts = [lay["n_in"] - 3, level1 + 9, level1 + 20 + 2256 + 1000, cells - 2] + ([lay["n_in"] + 2256 + 7] if with_vectors else [])
+    # inside the inputs, inside a leaf sponge (vector mode), inside a level's select block, between the two permutations of its hash, inside
+    # the second one, two from the end
+    cuts = [lay["n_in"] - 3, level1 + 9, level1 + 20 + CS.perm_cells(2), level1 + 20 + 2256 + 1000, cells - 2] + ([lay["n_in"] + 2256 + 7] if with_vectors else [])
     up = []
     try:
         d_lv, d_pub = _dev(api, up, levels), _dev(api, up, np.zeros_like(pub))

@@ -142,6 +142,7 @@ def test_reference_shaped_inputs(api, O):
 
 
 def test_two_windowed_calls_write_the_bytes_of_one(api, O):
+    from halo2_vectordb_amd import circuit_sym as CS
     from halo2_vectordb_amd._lib import check
     lib = api.init()
     n, dim, idx = 6, 5, [4, 5, 6, 4, 1]
@@ -151,11 +152,16 @@ def test_two_windowed_calls_write_the_bytes_of_one(api, O):
     cells = want.shape[0]
     lk = np.zeros((0, 4), dtype=np.uint64)
     lay_in = _size(api, n, dim, len(idx))[1]
+    lay = CS.merkle_update_layout(len(idx), dim, 3)
+    level1 = lay["levels_at"][1] + lay["level_cells"]                  # update 1, level 1
+    # ... and inside a level's first select block, between the two permutations of its old hash, inside its second select block
+    in_level = (level1 + 7, level1 + 20 + CS.perm_cells(2), level1 + 20 + lay["node_cells"] + 5)
+    assert lay["n_in"] == lay_in and lay["total"] == cells
     up = []
     try:
         d_new, d_pub = _dev(api, up, new), _dev(api, up, np.zeros_like(pub))
         uidx = np.ascontiguousarray(idx, dtype=np.uint64)
-        for cut in (lay_in - 3, lay_in + 2256 + 7, cells // 2, cells - 2):
+        for cut in (lay_in - 3, lay_in + 2256 + 7, cells // 2, cells - 2) + in_level:
             halves = []
             for window in ((0, cut, 0, 0), (cut, cells, 0, 0)):
                 d_lv = _dev(api, up, levels0)                       # every call starts from the tree before the batch
