@@ -784,7 +784,14 @@ int msm_batch_dev(const vdb_srs* srs, int basis, const u256* scalars_dev, size_t
   l9k.to_rp = to_mont<Fq>(u256_from_u64(1024));
   for (size_t c0 = 0; c0 < n_cols; c0 += nb) {
     size_t nc = n_cols - c0 < nb ? n_cols - c0 : nb;
-    VDB_HIP(hipMemsetAsync(counters, 0, 4 * sizeof(uint32_t), cx.stream));
+    // counters[1], the overflow flag, is read once after the last batch: cleared before the first batch only, so that an overflow
+    // in any batch (whose k_msm_reduce leaves its points unwritten) still fails the call; the other three words are per batch
+    if (c0 == 0) {
+      VDB_HIP(hipMemsetAsync(counters, 0, 4 * sizeof(uint32_t), cx.stream));
+    } else {
+      VDB_HIP(hipMemsetAsync(counters, 0, sizeof(uint32_t), cx.stream));
+      VDB_HIP(hipMemsetAsync(counters + 2, 0, 2 * sizeof(uint32_t), cx.stream));
+    }
     {
       VDB_PROF("k_msm_sort");
       hipLaunchKernelGGL(k_msm_sort, dim3((unsigned)nc), dim3(MSM_SORT_THREADS), lds, cx.stream, scalars_dev ? scalars_dev + c0 * n : nullptr, srcs ? srcs + c0 : nullptr,
@@ -1042,6 +1049,8 @@ int vdb_msm_batch_masked_dev_begin(const vdb_srs* srs, int basis, const vdb_fr* 
   VDB_ARG(n <= srs->n && n > 0, "n exceeds the loaded SRS size");
   VDB_ARG((skip_mask_dev == nullptr) == (const_points_dev == nullptr), "mask and constant points go together");
   if (n_cols == 0) return VDB_OK;
+  // refused before the output buffer is touched: a wider second batch would re-allocate it under the batch that is still open
+  VDB_ARG(!ctx().msm_pending, "msm: a deferred batch has not been collected (vdb_msm_batch_end)");
   Affine* dout = (Affine*)deferred_out(n_cols * sizeof(Affine));
   if (!dout) return VDB_ERR_OOM;
   ctx().msm_out = dout;
@@ -1058,6 +1067,8 @@ int vdb_msm_batch_src_dev_begin(const vdb_srs* srs, int basis, const vdb_colsrc*
   VDB_ARG(n <= srs->n && n > 0 && n_blind <= n, "n exceeds the loaded SRS size");
   VDB_ARG((skip_mask_dev == nullptr) == (const_points_dev == nullptr), "mask and constant points go together");
   if (n_cols == 0) return VDB_OK;
+  // refused before the output buffer is touched: a wider second batch would re-allocate it under the batch that is still open
+  VDB_ARG(!ctx().msm_pending, "msm: a deferred batch has not been collected (vdb_msm_batch_end)");
   Affine* dout = (Affine*)deferred_out(n_cols * sizeof(Affine));
   if (!dout) return VDB_ERR_OOM;
   ctx().msm_out = dout;

@@ -2797,6 +2797,8 @@ int vdb_colsrc_build_dev(const vdb_fr* stream_dev, uint64_t n_cells, const uint6
     const uint64_t len = c < n_bp ? break_points[c] + 1 : n_cells - start;
     VDB_ARG(start <= n_cells && len <= rows && start + len <= n_cells, "break points do not match the stream length");
     if (c >= col_lo) {
+      // colsrc_fetch (and k_layout_columns) read a row below len from the stream before they look at the blinding rows
+      VDB_ARG(!blind_dev || len + n_blind <= rows, "a column's cells reach into its blinding rows");
       h[c - col_lo].src = stream_dev + start;
       h[c - col_lo].len = len;
       h[c - col_lo].blind = blind_dev ? blind_dev + c * n_blind : nullptr;
@@ -2817,6 +2819,7 @@ int vdb_colsrc_build_lookup_dev(const vdb_fr* lookup_dev, uint64_t n_cells, uint
     const uint64_t start = c * max_rows;
     h[c - col_lo].src = lookup_dev + (start < n_cells ? start : 0);
     h[c - col_lo].len = start < n_cells ? (n_cells - start < max_rows ? n_cells - start : max_rows) : 0;
+    VDB_ARG(!blind_dev || h[c - col_lo].len + n_blind <= (1ull << k), "a column's cells reach into its blinding rows");
     h[c - col_lo].blind = blind_dev ? blind_dev + c * n_blind : nullptr;
   }
   if (!h.empty()) VDB_HIP(hipMemcpyAsync(out_dev, h.data(), h.size() * sizeof(vdb_colsrc), hipMemcpyHostToDevice, ctx().stream));

@@ -397,7 +397,11 @@ int vdb_layout_lookup_dev(const vdb_fr *lookup_dev, uint64_t n_cells, uint32_t k
  * what vdb_layout_columns[_range]_dev / vdb_layout_lookup[_range]_dev would have written.  The commitment MSM
  * (vdb_msm_batch_src_dev_begin) and the first pass of lagrange_to_coeff (vdb_lagrange_to_coeff_src_dev, which writes the
  * coefficient columns) read through it, so the 64 B / cell of the layout copy disappear from the prover's step.  The
- * descriptors are data independent: build them once per circuit.  out_dev: (col_hi - col_lo) descriptors in device memory. */
+ * descriptors are data independent: build them once per circuit.  out_dev: (col_hi - col_lo) descriptors in device memory.
+ * The cells and the blinding rows of a column do not overlap: both readers take a row below len from the stream before they look
+ * at the blinding rows, so with blind_dev given the builders refuse a column with len + n_blind > 2^k (VDB_ERR_ARG, nothing is
+ * written) — a layout planned with minimum_rows >= n_blind never has one.  Without blind_dev a column may be 2^k cells long.
+ * A caller that writes descriptors itself keeps len + n_blind <= n where blind is set. */
 typedef struct {
   const vdb_fr *src;
   uint64_t len;
@@ -471,7 +475,8 @@ int vdb_msm_batch_dev(const vdb_srs *srs, int basis, const vdb_fr *scalars_dev, 
  * stream, so work queued next (vdb_lagrange_to_coeff_dev / vdb_coeff_to_extended_dev on the same columns: the scalars
  * are no longer read) overlaps it.  _end waits FOR THE MSM ONLY and copies the n_cols commitments out: what was queued on the
  * library's stream after _begin may still be running when it returns (the caller feeds the commitments to its transcript
- * while the transforms run; vdb_sync() or any blocking call joins).  One deferred MSM at a time. */
+ * while the transforms run; vdb_sync() or any blocking call joins).  One deferred MSM at a time: while one is open every other
+ * MSM (a second _begin, vdb_msm_batch[_masked]_dev) returns VDB_ERR_ARG and leaves the open one as it is; _end(NULL, 0) drops it. */
 int vdb_msm_batch_masked_dev_begin(const vdb_srs *srs, int basis, const vdb_fr *scalars_dev, size_t n_cols, size_t n, const uint8_t *skip_mask_dev,
                                    const vdb_g1 *const_points_dev);
 /* same for columns described by vdb_colsrc (n rows each, the last n_blind of them blinding rows) */
