@@ -57,6 +57,13 @@ def _position(ranges, i):
     raise KeyError(i)
 
 
+def _consts_table(consts):
+    """a circuit's distinct constants (Python integers) as Montgomery field elements, (n, 4): the fixed column's first rows"""
+    if not len(consts):
+        return np.zeros((0, 4), dtype=np.uint64)
+    return api.fr_from_canonical(np.array([[(int(v) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)] for v in consts], dtype=np.uint64))
+
+
 class _View:
     """a stretch of a pooled device allocation (same surface as api.DeviceBuffer; freeing it is a no-op)"""
 
@@ -200,7 +207,11 @@ class ProverRounds:
     Every rank runs the same rounds on its own columns and its own sets of the permutation argument (shardmap.ShardMap) and
     keeps a transcript of its own: commitments and evaluations are exchanged in the global order before they are absorbed, so
     every rank derives the same challenges and ends with the same proof bytes — the bytes a single GPU writes with the same
-    blinding scalars."""
+    blinding scalars.
+    Three switches, set on the object before keygen():
+    `map_on_device` (True): the device places the constraint map; False = the host builds the maps the device would place.
+    `keep_circuit` (False): keep the device's constraint map of a circuit of 2^28 cells or more, which keygen otherwise releases.
+    `keep_mapping` (False): keep the permutation's 64-bit mapping in `d_map` after keygen (the tests compare it with the host's)."""
 
     def __init__(self, hp, block_cols=BLOCK_COLS, comm=None):
         from .dist import LocalComm
@@ -233,9 +244,12 @@ class ProverRounds:
         self.delta = api.fr_delta()
         self.fixed = {}
         self._vk_digest = None
-        self.d_map32 = None
-        self.d_inst_cells = None
-        self.public_cells = []          # the circuit's default public cells (circuit_map); a key loaded from a file brings its own
+        self.map_on_device, self.keep_circuit, self.keep_mapping = True, False, False
+        self.circuit = None             # the constraint map of the last keygen
+        # d_key: the key's big buffer [sigma columns of my sets | selectors of my advice columns]; d_map / d_map32: the permutation's
+        # mapping in 64 bits per cell (only under keep_mapping) and packed in 32
+        self.d_key = self.d_map = self.d_map32 = self.d_inst_cells = None
+        self.public_cells = []        # the circuit's default public cells (circuit_map); a key loaded from a file brings its own
         self.instance_cells = []
 
     # ------------------------------------------------------------------ local positions of global things
@@ -343,7 +357,7 @@ class ProverRounds:
         """The circuit's constraint map (circuit_sym.CopyMap) for the gadget this hot path runs (hp.constraint_map); sets the cells its
         example makes public and the Merkle root's cell (None for a circuit without one).  `map_on_device` = False: the host builds
         the maps the device would place."""
-        cm, public, self.root_cell = self.hp.constraint_map(d_flags, getattr(self, "map_on_device", True))
+        cm, public, self.root_cell = self.hp.constraint_map(d_flags, self.map_on_device)
         self.public_cells = [int(c) for c in public]
         return cm
 
@@ -356,15 +370,31 @@ class ProverRounds:
         exposes (circuit_map: centroids / result vector / root) when the map is the gadget's own, nothing for a map handed in.
         `check`: run the device-side MockProver on the keygen witness with the whole map (vdb_mock_check_dev); the report is
         kept in self.keygen_report (a circuit the witness does not satisfy can still be set up — the proof will not verify)."""
-        hp, lib, rows, k = self.hp, self.lib, self.rows, self.k
         # the fixed columns' commitments work in the bounded MSM work space of setup (pipeline.HotPath.setup); every step() lifts the bound
         api.msm_scratch_cap(api.KEYGEN_SCRATCH_CAP)
+        self._commit_srs()
+        d_flags = self.hp.keygen_flags()        # gate selectors from a flag-recording witness run
+        cm = self._keygen_circuit(circuit, instance_cells, d_flags)
+        if check:
+            self.keygen_report = self.mock_check(d_flags)
+        d_map = self._build_mapping(cm, *self._permutation_parents(cm))
+        self._sigma_columns(d_map)
+        self._selector_columns(d_flags)
+        self._small_fixed()
+        api.sync()
+        return self._alloc_working_set()
+
+    def _commit_srs(self):
+        """the SRS handles of the commitments the hot path's own does not serve"""
         # the derived columns (products, quotient, opening quotients) and the fixed sigma columns hold full-width scalars
+        hp, k = self.hp, self.k
         self.srs_m = api.Srs(k, hp.g_monomial, hp.g_lagrange, window_bits=14)
         self.srs_few = api.Srs(k, hp.g_monomial, None)     # a handful of columns: the bucket folding dominates, fewer buckets win
-        # gate selectors from a flag-recording witness run
-        d_flags = hp.keygen_flags()
-        from ._lib import check as _chk     # (`check` is this method's flag)
+
+    def _keygen_circuit(self, circuit, instance_cells, d_flags):
+        """the constraint map and the public cells of this keygen (the arguments, or the gadget's own), checked against the hot
+        path's circuit; sets self.circuit, self.instance_cells, self.consts"""
+        hp = self.hp
         self.public_cells = []
         cm = circuit if circuit is not None else self.circuit_map(d_flags)
         if instance_cells is None:
@@ -372,133 +402,162 @@ class ProverRounds:
         self.instance_cells = [int(c) for c in instance_cells]
         if len(self.instance_cells) > self.usable or any(not 0 <= c < hp.n_cells for c in self.instance_cells):
             raise ValueError("public cells outside the stream, or more of them than usable rows of the instance column")
-        on_dev = hasattr(cm, "d_copy_of")
-        n_src = cm.n_lookup if on_dev else (None if cm.lookup_src is None else len(cm.lookup_src))
+        n_src = cm.n_lookup if hasattr(cm, "d_copy_of") else (None if cm.lookup_src is None else len(cm.lookup_src))
         if cm.n_cells != hp.n_cells or (n_src is not None and n_src != hp.n_lookup):
             raise ValueError("the constraint map does not describe this circuit (cell counts differ)")
         self.circuit = cm
         self.consts = [int(v) for v in cm.consts]
         if len(self.consts) > self.usable:
             raise ValueError("more distinct constants than usable rows of the fixed column")
-        if check:
-            self.keygen_report = self.mock_check(d_flags)
-        # sigma columns over [advice | lookup | constants | instance]: the cycles of the copy classes, built on the device
-        # (vdb_permutation_mapping_dev: pointer jumping, one radix sort; copymap.mapping_from_copy_of is the host restatement
-        # the tests compare it with).  A map without lookup sources leaves the lookup columns untied: only the tests' negative
-        # cases want that.
+        return cm
+
+    def _permutation_parents(self, cm):
+        """The copy forest the permutation is built from: (d_parent, lsrc_ptr, d_lsrc, tie_lookups) — every cell's parent (a cell
+        tied to a constant points at the constant's slot behind the cells), the lookup cells' sources (d_lsrc: the upload of a
+        host map's, which the caller frees; None for the device's map, which owns them) and whether the lookup columns are tied
+        at all.  A map without lookup sources leaves them untied: only the tests' negative cases want that."""
+        hp, lib = self.hp, self.lib
         d_parent = api.DeviceBuffer(hp.n_cells * 8)
-        d_lsrc = None
-        if on_dev:
+        if hasattr(cm, "d_copy_of"):
             bad, nosrc = ctypes.c_uint64(), ctypes.c_uint64()
-            _chk(lib.vdb_copymap_finish_dev(cm.d_copy_of.ptr, cm.d_const_idx.ptr, ctypes.c_uint64(hp.n_cells), cm.d_lookup_src.ptr, ctypes.c_uint64(hp.n_lookup),
-                                            d_parent.ptr, ctypes.byref(bad), ctypes.byref(nosrc)))
+            check(lib.vdb_copymap_finish_dev(cm.d_copy_of.ptr, cm.d_const_idx.ptr, ctypes.c_uint64(hp.n_cells), cm.d_lookup_src.ptr, ctypes.c_uint64(hp.n_lookup),
+                                             d_parent.ptr, ctypes.byref(bad), ctypes.byref(nosrc)))
             if bad.value:
                 raise ValueError("a cell tied to a constant must be the root of its copies")
-            tie_lookups = bool(hp.n_lookup)
-            lsrc_ptr = cm.d_lookup_src.ptr
-        else:
-            parent = cm.copy_of.astype(np.int64, copy=True)
-            tied = cm.const_idx >= 0
-            if (parent[tied] != np.flatnonzero(tied)).any():
-                raise ValueError("a cell tied to a constant must be the root of its copies")
-            parent[tied] = hp.n_cells + cm.const_idx[tied]
-            d_parent.upload(parent)
-            del parent
-            tie_lookups = bool(hp.n_lookup) and cm.lookup_src is not None
-            if tie_lookups:
-                d_lsrc = api.DeviceBuffer(hp.n_lookup * 8)
-                d_lsrc.upload(np.ascontiguousarray(cm.lookup_src, dtype=np.int64))
-            lsrc_ptr = d_lsrc.ptr if tie_lookups else None
+            return d_parent, cm.d_lookup_src.ptr, None, bool(hp.n_lookup)
+        parent = cm.copy_of.astype(np.int64, copy=True)
+        tied = cm.const_idx >= 0
+        if (parent[tied] != np.flatnonzero(tied)).any():
+            raise ValueError("a cell tied to a constant must be the root of its copies")
+        parent[tied] = hp.n_cells + cm.const_idx[tied]
+        d_parent.upload(parent)
+        del parent
+        tie_lookups = bool(hp.n_lookup) and cm.lookup_src is not None
+        d_lsrc = None
+        if tie_lookups:
+            d_lsrc = api.DeviceBuffer(hp.n_lookup * 8)
+            d_lsrc.upload(np.ascontiguousarray(cm.lookup_src, dtype=np.int64))
+        return d_parent, d_lsrc.ptr if tie_lookups else None, d_lsrc, tie_lookups
+
+    def _build_mapping(self, cm, d_parent, lsrc_ptr, d_lsrc, tie_lookups):
+        """The permutation over [advice | lookup | constants | instance]: the cycles of the copy classes, built on the device
+        (vdb_permutation_mapping_dev: pointer jumping, one radix sort; copymap.mapping_from_copy_of is the host restatement the
+        tests compare it with).  Allocates the key's buffer d_key, frees the parents, releases a large device map, and leaves the
+        mapping packed in self.d_map32.  Returns the 64-bit mapping d_map, which the sigma columns are made from."""
+        hp, lib, rows, k = self.hp, self.lib, self.rows, self.k
         d_map = api.DeviceBuffer(self.n_perm * rows * 8)
         bp64 = np.ascontiguousarray(hp.bp, dtype=np.uint64)
         self._upload_instance_cells()
         # The key's two big buffers — the sigma columns of my sets, the selectors of my advice columns — are ONE allocation, made
         # before the permutation is built and lent to it for its sort records (51 GiB at C4'): HBM that is mapped once and never handed
         # back (mapping or clearing HBM costs this driver ~30 ms / GiB, vdb_alloc_stats).
-        if getattr(self, "d_key", None) is not None:
+        if self.d_key is not None:
             self.d_key.free()
         self.d_key = api.DeviceBuffer(max(self.my_sig + self.my_adv, 1) * rows * B)
-        _chk(lib.vdb_permutation_mapping_ws_dev(d_parent.ptr, ctypes.c_uint64(hp.n_cells), ctypes.c_uint64(len(self.consts)), api._p(bp64), ctypes.c_uint64(len(bp64)), k,
-                                                lsrc_ptr if tie_lookups else None, ctypes.c_uint64(hp.n_lookup if tie_lookups else 0),
-                                                ctypes.c_uint64(rows - MINIMUM_ROWS), ctypes.c_uint64(self.n_cols),
-                                                self.d_inst_cells.ptr, ctypes.c_uint64(len(self.instance_cells)), d_map.ptr,
-                                                self.d_key.ptr, _sz(self.d_key.nbytes)))
+        check(lib.vdb_permutation_mapping_ws_dev(d_parent.ptr, ctypes.c_uint64(hp.n_cells), ctypes.c_uint64(len(self.consts)), api._p(bp64), ctypes.c_uint64(len(bp64)), k,
+                                                 lsrc_ptr if tie_lookups else None, ctypes.c_uint64(hp.n_lookup if tie_lookups else 0),
+                                                 ctypes.c_uint64(rows - MINIMUM_ROWS), ctypes.c_uint64(self.n_cols),
+                                                 self.d_inst_cells.ptr, ctypes.c_uint64(len(self.instance_cells)), d_map.ptr,
+                                                 self.d_key.ptr, _sz(self.d_key.nbytes)))
         d_parent.free()
         if d_lsrc is not None:
             d_lsrc.free()
-        if on_dev and hp.n_cells >= (1 << 28) and not getattr(self, "keep_circuit", False):
+        if hasattr(cm, "d_copy_of") and hp.n_cells >= (1 << 28) and not self.keep_circuit:
             cm.free()                    # tens of GB at BASELINE sizes: the proof needs the room; small circuits keep their map (tests, mock_check)
-        self._d_map_for_tests = d_map if getattr(self, "keep_mapping", False) else None
+        self.d_map = d_map if self.keep_mapping else None
         # the mapping stays with the key in 32 bits per cell when column and row fit: the product round makes the sigma columns'
         # Lagrange form from it (one product per cell) instead of transforming their coefficient form back
         self.d_map32 = None
-        if (self.n_perm - 1).bit_length() + k <= 32 and (getattr(self, "keep_packed_mapping", True) or self.world > 1):
+        if (self.n_perm - 1).bit_length() + k <= 32:
             self.d_map32 = api.DeviceBuffer(self.n_perm * rows * 4)
-            _chk(lib.vdb_permutation_mapping_pack_dev(d_map.ptr, _sz(self.n_perm), k, self.d_map32.ptr))
+            check(lib.vdb_permutation_mapping_pack_dev(d_map.ptr, _sz(self.n_perm), k, self.d_map32.ptr))
             api.sync()
         if self.world > 1 and self.d_map32 is None:
             raise ValueError("a sharded key keeps the packed mapping: column and row of a cell must fit 32 bits")
-        # sigma columns: every rank builds the cycles of the whole circuit (the copy classes cross all columns) and keeps the
-        # columns of its own sets
+        return d_map
+
+    def _sigma_columns(self, d_map):
+        """the sigma columns of my sets, into the front of d_key: every rank builds the cycles of the whole circuit (the copy
+        classes cross all columns) and keeps the columns of its own sets; frees d_map unless keep_mapping holds it"""
+        lib, rows, k = self.lib, self.rows, self.k
         d_sigma = _View(self.d_key, 0, self.my_sig * rows * B)
         off = 0
         for lo, hi in self.sig_ranges:
-            _chk(lib.vdb_permutation_sigma_dev(d_map.at(lo * rows * 8), _sz(hi - lo), k, api._p(self.delta), d_sigma.at(off * rows * B))
-                 if self.world == 1 else
-                 lib.vdb_permutation_sigma_packed_dev(self.d_map32.at(lo * rows * 4), _sz(hi - lo), _sz(self.n_perm), k, api._p(self.delta), d_sigma.at(off * rows * B)))
+            check(lib.vdb_permutation_sigma_dev(d_map.at(lo * rows * 8), _sz(hi - lo), k, api._p(self.delta), d_sigma.at(off * rows * B))
+                  if self.world == 1 else
+                  lib.vdb_permutation_sigma_packed_dev(self.d_map32.at(lo * rows * 4), _sz(hi - lo), _sz(self.n_perm), k, api._p(self.delta), d_sigma.at(off * rows * B)))
             off += hi - lo
-        if self._d_map_for_tests is None:
+        if self.d_map is None:
             d_map.free()
         self._fixed_poly("sigma", d_sigma, self.my_sig, keep_lag=False, keep_ext=False, ranges=self.sig_ranges, n_total=self.n_perm)
-        # gate selectors (after the permutation's work space is gone: both are tens of GB at BASELINE sizes), of my advice columns
+
+    def _selector_columns(self, d_flags):
+        """the gate selectors of my advice columns, behind the sigma columns in d_key (after the permutation's work space is
+        gone: both are tens of GB at BASELINE sizes); frees d_flags"""
+        hp, lib, rows = self.hp, self.lib, self.rows
         d_mine = _View(self.d_key, self.my_sig * rows * B, self.my_adv * rows * B)
-        if self.my_adv == self.n_adv:
-            d_q = d_mine
-            _chk(lib.vdb_layout_selectors_dev(d_flags.ptr, ctypes.c_uint64(hp.n_cells), api._p(hp.bp), ctypes.c_uint64(len(hp.bp)), k, d_q.ptr))
-            d_flags.free()
-        else:       # a rank of a sharded run lays out every column's selectors and keeps its own
-            d_q = api.DeviceBuffer(self.n_adv * rows * B)
-            _chk(lib.vdb_layout_selectors_dev(d_flags.ptr, ctypes.c_uint64(hp.n_cells), api._p(hp.bp), ctypes.c_uint64(len(hp.bp)), k, d_q.ptr))
-            d_flags.free()
-            _chk(lib.vdb_memcpy_d2d(d_mine.ptr, d_q.at(self.a_lo * rows * B), _sz(self.my_adv * rows * B)))
+        # a rank of a sharded run lays out every column's selectors and keeps its own
+        d_all = d_mine if self.my_adv == self.n_adv else api.DeviceBuffer(self.n_adv * rows * B)
+        check(lib.vdb_layout_selectors_dev(d_flags.ptr, ctypes.c_uint64(hp.n_cells), api._p(hp.bp), ctypes.c_uint64(len(hp.bp)), self.k, d_all.ptr))
+        d_flags.free()
+        if d_all is not d_mine:
+            check(lib.vdb_memcpy_d2d(d_mine.ptr, d_all.at(self.a_lo * rows * B), _sz(self.my_adv * rows * B)))
             api.sync()
-            d_q.free()
-            d_q = d_mine
-        self._fixed_poly("sel", d_q, self.my_adv, keep_lag=False, keep_ext=False, ranges=[(self.a_lo, self.a_hi)], n_total=self.n_adv)
+            d_all.free()
+        self._fixed_poly("sel", d_mine, self.my_adv, keep_lag=False, keep_ext=False, ranges=[(self.a_lo, self.a_hi)], n_total=self.n_adv)
+
+    def _small_fixed(self):
+        """the three small fixed polynomials every rank holds whole: the constants' column, the range table, the Lagrange selectors"""
+        hp, rows = self.hp, self.rows
         # the constants' fixed column: constant r at row r (halo2-base assigns the distinct constants of a circuit to fixed cells
         # and ties every Constant advice cell to its fixed cell through the permutation)
         cst = np.zeros((rows, 4), dtype=np.uint64)
-        if self.consts:
-            cst[: len(self.consts)] = api.fr_from_canonical(np.array([[(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)] for v in self.consts], dtype=np.uint64))
+        cst[: len(self.consts)] = _consts_table(self.consts)
         d_cst = api.DeviceBuffer(rows * B)
         d_cst.upload(cst)
         self._fixed_poly("cst", d_cst, 1)
-        # its coset sits behind the advice cosets, the instance column's behind it (the permutation term of the quotient reads one
-        # contiguous block of columns)
-        if hp.ext_cols >= self.my_adv + self.my_lk + 2:
-            _chk(lib.vdb_memcpy_d2d(hp.d_ext.at((self.my_adv + self.my_lk) * self.ne * B), self.fixed["cst"].ext.ptr, _sz(self.ne * B)))
-        # range table 0 .. 2^L - 1, zero below; Lagrange selectors l0, l_last, l_active
+        self._place_cst_coset()
+        # range table 0 .. 2^L - 1, zero below
         tab = np.arange(rows, dtype=np.uint64)
         tab[tab >= (1 << hp.L)] = 0
         d_tab = api.DeviceBuffer(rows * B)
         d_tab.upload(api.fr_from_canonical(np.stack([tab, np.zeros_like(tab), np.zeros_like(tab), np.zeros_like(tab)], axis=1)))
         self._fixed_poly("table", d_tab, 1)
-        lag = np.zeros((3, rows, 4), dtype=np.uint64)
-        one = _fr_from_int(1)
-        lag[0, 0], lag[1, self.usable], lag[2, : self.usable] = one, one, one
+        lag = self._lagrange_selectors()
         d_l = api.DeviceBuffer(lag.nbytes)
         d_l.upload(lag)
         self._fixed_poly("lag", d_l, 3)
-        api.sync()
-        return self._alloc_working_set()
+
+    def _lagrange_selectors(self):
+        """l0, l_last, l_active in Lagrange form (3, rows, 4): one at row 0, at the first unusable row, on every usable row"""
+        lag = np.zeros((3, self.rows, 4), dtype=np.uint64)
+        one = _fr_from_int(1)
+        lag[0, 0], lag[1, self.usable], lag[2, : self.usable] = one, one, one
+        return lag
+
+    def _place_cst_coset(self):
+        """the constants' coset sits behind the advice cosets, the instance column's behind it (the permutation term of the quotient
+        reads one contiguous block of columns)"""
+        hp = self.hp
+        if hp.ext_cols >= self.my_adv + self.my_lk + 2:
+            check(self.lib.vdb_memcpy_d2d(hp.d_ext.at((self.my_adv + self.my_lk) * self.ne * B), self.fixed["cst"].ext.ptr, _sz(self.ne * B)))
 
     def _upload_instance_cells(self):
         cells = np.asarray(self.instance_cells, dtype=np.int64)
-        if getattr(self, "d_inst_cells", None) is not None:      # a second keygen / key load on the same object
+        if self.d_inst_cells is not None:      # a second keygen / key load on the same object
             self.d_inst_cells.free()
         self.d_inst_cells = api.DeviceBuffer(max(cells.nbytes, 32))
         if cells.nbytes:
             self.d_inst_cells.upload(cells)
+
+    def _instance_values(self, instances):
+        """`instances` (canonical integers, one per public cell of keygen) as Montgomery field elements, (max(n, 1), 4)"""
+        if len(instances) != len(self.instance_cells):
+            raise ValueError("one value per public cell")
+        vals = np.zeros((max(len(instances), 1), 4), dtype=np.uint64)
+        if len(instances):
+            vals[: len(instances)] = np.stack([_fr_from_int(int(v)) for v in instances])
+        return vals
 
     def mock_check(self, d_flags=None, instances=None):
         """The Mock stage on the witness in HBM with this circuit's whole constraint map (vdb_mock_check_dev): gate rows, the
@@ -534,17 +593,12 @@ class ProverRounds:
                 d_lsrc = dev(cm.lookup_src, np.int64) if hp.n_lookup and cm.lookup_src is not None else None
                 d_cidx = dev(cm.const_idx, np.int64)
             tab = np.zeros((max(len(cm.consts), 1), 4), dtype=np.uint64)
-            if len(cm.consts):
-                tab[: len(cm.consts)] = api.fr_from_canonical(np.array([[(int(v) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)] for v in cm.consts], dtype=np.uint64))
+            tab[: len(cm.consts)] = _consts_table(cm.consts)
             d_tab = dev(tab, np.uint64)
             rep = api.mock_check_dev(hp.d_stream.ptr, hp.n_cells, d_flags.ptr, hp.d_lookup.ptr, hp.n_lookup, hp.L, d_copy.ptr,
                                      None if d_lsrc is None else d_lsrc.ptr, None, d_cidx.ptr, d_tab.ptr, len(cm.consts))
             if instances is not None:
-                if len(instances) != len(self.instance_cells):
-                    raise ValueError("one value per public cell")
-                vals = np.zeros((max(len(instances), 1), 4), dtype=np.uint64)
-                if len(instances):
-                    vals[: len(instances)] = np.stack([_fr_from_int(int(v)) for v in instances])
+                vals = self._instance_values(instances)
                 api.mock_check_instances_dev(rep, hp.d_stream.ptr, hp.n_cells, dev(self.instance_cells, np.int64).ptr, dev(vals, np.uint64).ptr, len(instances))
             return rep
         finally:
@@ -557,12 +611,10 @@ class ProverRounds:
         """The `instances` argument of MockProver::run alone, on the witness in HBM (vdb_mock_check_instances_dev): public cell i of
         keygen must hold instances[i] (canonical integers).  Needs no constraint map, so it also serves after keygen released the
         map of a BASELINE-size circuit.  api.MockReport with only the instance fields filled."""
-        if len(instances) != len(self.instance_cells):
-            raise ValueError("one value per public cell")
+        vals = self._instance_values(instances)
         rep = api.MockReport()
         if not len(instances):
             return rep
-        vals = np.stack([_fr_from_int(int(v)) for v in instances])
         d_vals = api.DeviceBuffer(vals.nbytes)
         try:
             d_vals.upload(vals)
@@ -612,10 +664,15 @@ class ProverRounds:
         check(lib.vdb_memset_dev(self.d_inst_lag.ptr, 0, _sz(rows * B)))
         self._vk_digest = None
         self.vk_digest()            # part of the key, made here so that no proof pays for it
-        # The cosets of the fixed polynomials that every proof would otherwise transform again — the sigma columns (n_slots cosets
-        # each) and the selectors (two) — stay in HBM when they fit beside everything above with room to spare for the MSM's work space:
-        # halo2's ProvingKey holds them too (fixed_cosets, permutation cosets).  They fit on a rank of a multi-GPU job and for circuits
-        # up to a few thousand columns; BASELINE C4' on one card (20,969 columns: 126 + 36 GB) streams them block by block as before.
+        self._keep_fixed_cosets()
+        return self
+
+    def _keep_fixed_cosets(self):
+        """The cosets of the fixed polynomials that every proof would otherwise transform again — the sigma columns (n_slots cosets
+        each) and the selectors (two) — stay in HBM when they fit beside the working set with room to spare for the MSM's work space:
+        halo2's ProvingKey holds them too (fixed_cosets, permutation cosets).  They fit on a rank of a multi-GPU job and for circuits
+        up to a few thousand columns; BASELINE C4' on one card (20,969 columns: 126 + 36 GB) streams them block by block as before."""
+        lib, rows = self.lib, self.rows
         self.fixed_cosets_resident = False
         need = (self.my_sig * self.ne + self.my_adv * GATE_SLOTS * rows) * B
         free, _total = api.mem_info()
@@ -629,7 +686,6 @@ class ProverRounds:
             check(lib.vdb_coeff_to_cosets_dev(sel.coeff.ptr, sel.ext.ptr, _sz(self.my_adv), self.k, GATE_SLOTS, None))
             api.sync()
             self.fixed_cosets_resident = True
-        return self
 
     # ------------------------------------------------------------------ the proving key on disk
     def save_verifying_key(self, path, opened=None):
@@ -691,9 +747,8 @@ class ProverRounds:
     def _install_key(self, doc):
         """doc[name + "_coeff"], doc[name + "_commits"] for every fixed polynomial, doc["instance_cells"]: the key's polynomials go
         to the device in the forms the rounds read"""
-        hp, lib, rows, k = self.hp, self.lib, self.rows, self.k
-        self.srs_m = api.Srs(k, hp.g_monomial, hp.g_lagrange, window_bits=14)
-        self.srs_few = api.Srs(k, hp.g_monomial, None)
+        lib, rows, k = self.lib, self.rows, self.k
+        self._commit_srs()
         omega = api.root_of_unity(k)
         # (name, polynomials held here, their place in the whole set, size of the whole set, Lagrange form kept, cosets kept)
         plan = (("sel", self.my_adv, [(self.a_lo, self.a_hi)], self.n_adv, False, False), ("sigma", self.my_sig, self.sig_ranges, self.n_perm, False, False),
@@ -717,8 +772,7 @@ class ProverRounds:
         if int(doc["instance_cells_are_the_default"][0]):
             self.public_cells = list(self.instance_cells)
         self._upload_instance_cells()
-        if hp.ext_cols >= self.my_adv + self.my_lk + 2:
-            check(lib.vdb_memcpy_d2d(hp.d_ext.at((self.my_adv + self.my_lk) * self.ne * B), self.fixed["cst"].ext.ptr, _sz(self.ne * B)))
+        self._place_cst_coset()
         api.sync()
         return self._alloc_working_set()
 
@@ -799,10 +853,7 @@ class ProverRounds:
             read_polys_raw(f, self.n_perm, ne, keep=False)
             if f.read(1):
                 raise ValueError("proving key: bytes after the permutation's cosets")
-        lag = np.zeros((3, rows, 4), dtype=np.uint64)
-        one = _fr_from_int(1)
-        lag[0, 0], lag[1, self.usable], lag[2, : self.usable] = one, one, one
-        lag_coeff = api.lagrange_to_coeff(lag)
+        lag_coeff = api.lagrange_to_coeff(self._lagrange_selectors())
         if not np.array_equal(api.coeff_to_extended(lag_coeff, self.raw_ext_k), lag_ext):
             raise ValueError("proving key: l_0, l_last, l_active_row are not this circuit's (another number of blinding rows?)")
         sel_bits = np.any(api.ntt_batch(fixed[2:], api.root_of_unity(self.k)) != 0, axis=2) if self.n_adv else np.zeros((0, rows), dtype=bool)
@@ -1442,12 +1493,12 @@ class ProverRounds:
         self.fixed = {}
         self._vk_digest = None
         for name in ("pool_der", "d_lklag", "d_lag_a", "d_lag_s", "d_ea", "d_eb", "d_ez", "d_zf", "d_zlast", "d_h", "d_h2", "d_h3", "d_h4", "d_hg", "d_comb", "d_quot", "d_map32", "d_inst_lag", "d_inst_coeff", "d_inst_ext", "d_inst_cells",
-                     "d_foreign_lag", "d_foreign_coeff", "d_zhalo", "d_rand", "d_hf", "d_key"):
+                     "d_foreign_lag", "d_foreign_coeff", "d_zhalo", "d_rand", "d_hf", "d_key", "d_map"):
             b = getattr(self, name, None)
             if b is not None:
                 b.free()
                 setattr(self, name, None)
-        if hasattr(getattr(self, "circuit", None), "free"):
+        if hasattr(self.circuit, "free"):
             self.circuit.free()
         for name in ("srs_m", "srs_few"):
             if getattr(self, name, None) is not None:

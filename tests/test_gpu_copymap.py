@@ -226,7 +226,7 @@ def test_device_permutation_mapping_has_the_cycles_of_the_host_construction(api,
     pr.keygen()
     try:
         cm, rows, n_perm = pr.circuit, pr.rows, pr.n_perm
-        dev = pr._d_map_for_tests.download((n_perm, rows), dtype=np.uint64)
+        dev = pr.d_map.download((n_perm, rows), dtype=np.uint64)
         host = mapping_from_copy_of(cm.copy_of, hp.bp, pr.n_cols, rows, cm.lookup_src, rows - MINIMUM_ROWS, const_idx=cm.const_idx, n_consts=len(cm.consts),
                                     instance_cells=pr.instance_cells)
         assert len(pr.instance_cells) == 2 * 3 and dev.shape == host.shape
@@ -250,7 +250,7 @@ def test_device_permutation_mapping_has_the_cycles_of_the_host_construction(api,
             assert lab[(pr.n_cols + 1) * rows + i] == lab[col * rows + cell - int(starts[col])]
         assert (classes(dev) != np.arange(n_perm * rows)).mean() > 0.3
     finally:
-        pr._d_map_for_tests.free()
+        pr.d_map.free()
         pr.free()
         hp.free()
 

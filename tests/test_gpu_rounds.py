@@ -534,6 +534,59 @@ def test_key_files_in_upstreams_layout(circuit, O, tmp_path):
         ProverRounds(hp).load_proving_key_raw(pk_path)
 
 
+def test_a_second_keygen_or_key_load_on_one_object(tmp_path):
+    """One ProverRounds object set up twice — keygen() twice, keygen() then load_proving_key() of the file it saved — holds the key
+    of a fresh object that ran keygen once (same digest, same proof bytes with the same blinding seed) and gives every buffer of both
+    set-ups back with free(); the permutation's 64-bit mapping stays in d_map only under keep_mapping.  DistancesHotPath at its
+    defaults: the smallest circuit with lookups and constants."""
+    from halo2_vectordb_amd import api
+    from halo2_vectordb_amd.pipeline import DistancesHotPath
+    from halo2_vectordb_amd.rounds import ProverRounds
+    api.init(0)
+    # hipMalloc hands out device memory in fragments of 2 MiB at the most: free memory that comes back to within one of them is
+    # free memory that came back (a buffer left behind is at least a column of 2^13 rows x 32 bytes, and the key's are many columns)
+    GRANULE, SEED = 2 << 20, 41
+    hp = DistancesHotPath().setup()
+    try:
+        fresh = ProverRounds(hp).keygen()
+        try:
+            want_digest, want = fresh.vk_digest().copy(), fresh.prove(seed=SEED)["proof"]
+        finally:
+            fresh.free()
+        assert len(want) > 0
+        api.sync()
+        before = api.mem_info()[0]           # (the library's grow-only work space has its size by now)
+
+        def same_key_and_all_memory_back(pr):
+            try:
+                assert np.array_equal(pr.vk_digest(), want_digest)
+                assert pr.prove(seed=SEED)["proof"] == want
+            finally:
+                pr.free()
+            assert pr.d_map is None and pr.d_key is None and pr.d_inst_cells is None
+            api.sync()
+            after = api.mem_info()[0]
+            print("free memory before / after (bytes):", before, after)
+            assert abs(after - before) <= GRANULE, (before, after)
+
+        pr = ProverRounds(hp).keygen()
+        assert pr.d_map is None
+        pr.keep_mapping = True
+        pr.keygen()
+        assert pr.d_map is not None and pr.d_map.ptr.value and pr.d_map.nbytes == pr.n_perm * pr.rows * 8
+        mapping = pr.d_map.download((pr.n_perm, pr.rows), dtype=np.uint64)      # live: (column << 32 | row) of every cell's successor
+        assert int((mapping >> np.uint64(32)).max()) < pr.n_perm and int((mapping & np.uint64(0xFFFFFFFF)).max()) < pr.rows
+        same_key_and_all_memory_back(pr)
+
+        pr = ProverRounds(hp).keygen()
+        path = tmp_path / "distances.pk.npz"
+        pr.save_proving_key(path)
+        pr.load_proving_key(path)
+        same_key_and_all_memory_back(pr)
+    finally:
+        hp.free()
+
+
 def _verify(O, api, proof, vk):
     """A verifier for the proofs ProverRounds.prove(None) writes (SHPLONK): knows the proof bytes and a verifying key — the
     circuit's shape, the fixed commitments, [tau] H — and nothing else.  Replays the transcript, checks the quotient identity
