@@ -130,6 +130,19 @@ HD void xyzz_add(XYZZ& acc, const XYZZ& b) {
   acc.zz = fq_mul(fq_mul(acc.zz, b.zz), pp);
   acc.zzz = fq_mul(fq_mul(acc.zzz, b.zzz), ppp);
 }
+HD XYZZ xyzz_neg(XYZZ p) {
+  p.y = fq_neg(p.y);
+  return p;
+}
+// [s] p for a canonical scalar s (double-and-add from the top bit)
+HD XYZZ xyzz_mul(const XYZZ& p, const u256& s) {
+  XYZZ acc = xyzz_identity();
+  for (int b = (int)u256_bits(s) - 1; b >= 0; b--) {
+    acc = xyzz_double(acc);
+    if (u256_bit(s, (unsigned)b)) xyzz_add(acc, p);
+  }
+  return acc;
+}
 // canonical affine (identity -> (0,0)); one Fermat inversion
 HD Affine xyzz_to_affine(const XYZZ& p) {
   Affine a;

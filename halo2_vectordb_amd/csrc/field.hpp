@@ -421,6 +421,8 @@ HD void mont_sqr_core29(uint32_t out[9], const uint32_t A[9]) {
 // column can absorb all 18 partial products (18 * 2^58 < 2^64) with no carry logic at all: every step is
 // one multiply-add into a 64-bit accumulator.  Nine radix-2^29 reduction steps divide by 2^261; feeding
 // a * 2^5 (a free change of limb offsets) makes the result a * b * 2^-256, i.e. the usual R.
+// The first operand may be ANY 256-bit value (k_from_wide feeds to_mont raw halves): a * 2^5 < 2^261 still splits into nine limbs
+// below 2^29 and the core returns less than (2^261 p + 2^261 p) / 2^261 = 2 p, which the one subtraction below makes canonical.  b < p.
 template <class M>
 HD u256 mont_mul(const u256& a, const u256& b) {
   constexpr uint32_t MASK = 0x1fffffffu;

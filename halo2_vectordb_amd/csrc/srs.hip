@@ -21,21 +21,6 @@ namespace {
 constexpr unsigned DFT_BLOCK = 128;
 constexpr uint32_t MAX_K = 26;
 
-__device__ __forceinline__ XYZZ xyzz_neg(XYZZ p) {
-  p.y = fq_neg(p.y);
-  return p;
-}
-
-// [s] p for a canonical scalar s (double-and-add from the top bit)
-__device__ XYZZ xyzz_mul(const XYZZ& p, const u256& s) {
-  XYZZ acc = xyzz_identity();
-  for (int b = (int)u256_bits(s) - 1; b >= 0; b--) {
-    acc = xyzz_double(acc);
-    if (u256_bit(s, (unsigned)b)) xyzz_add(acc, p);
-  }
-  return acc;
-}
-
 __global__ __launch_bounds__(256) void k_g1_check(const Affine* __restrict__ pts, size_t n, unsigned long long* __restrict__ counters) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

@@ -377,22 +377,23 @@ class Block:
         return c
 
 
-def write_cases(path, blocks):
+def write_cases(path, blocks, magic=MAGIC):
     with open(path, "wb") as f:
-        f.write(struct.pack("<2I", MAGIC, len(blocks)))
+        f.write(struct.pack("<2I", magic, len(blocks)))
         for b in blocks:
             f.write(struct.pack("<3I", b.op, b.mod, len(b.cases)))
             for _, w in b.cases:
                 f.write(struct.pack(f"<{len(w)}I", *w))
 
 
-def read_results(path, blocks, nout=NOUT, names=NAMES):
-    """-> per block, one list of output words per case; asserts that the probe returned exactly one record per case.  `nout` / `names`:
-    the result widths and op names of the probe that wrote the file (tests/u256_model.py shares the format)"""
+def read_results(path, blocks, nout=NOUT, names=NAMES, magic=MAGIC):
+    """-> per block, one list of output words per case; asserts that the probe returned exactly one record per case.  `nout` / `names` /
+    `magic`: the result widths, op names and file magic of the probe that wrote the file (tests/u256_model.py and tests/ec_model.py share
+    the format)"""
     data = open(path, "rb").read()
     assert len(data) % 4 == 0
     words = struct.unpack(f"<{len(data) // 4}I", data)
-    assert words[0] == MAGIC and words[1] == len(blocks)
+    assert words[0] == magic and words[1] == len(blocks)
     pos, res = 2, []
     for b in blocks:
         assert words[pos: pos + 3] == (b.op, b.mod, len(b.cases)), names[b.op]
@@ -771,10 +772,10 @@ def compile_probe(dirname, name="l9_probe"):
     return exe
 
 
-def run_probe(exe, mode, blocks, dirname, timeout, nout=NOUT, names=NAMES):
+def run_probe(exe, mode, blocks, dirname, timeout, nout=NOUT, names=NAMES, magic=MAGIC):
     """one child process; a non-zero or signal exit fails with the child's stderr; nothing is retried"""
     cases, out = os.path.join(str(dirname), f"cases{mode}.bin"), os.path.join(str(dirname), f"out{mode}.bin")
-    write_cases(cases, blocks)
+    write_cases(cases, blocks, magic)
     r = subprocess.run([exe, mode, cases, out], capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, f"{os.path.basename(exe)} {mode} exited with {r.returncode}:\n{r.stderr}"
-    return read_results(out, blocks, nout, names)
+    return read_results(out, blocks, nout, names, magic)

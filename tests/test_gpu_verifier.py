@@ -122,6 +122,113 @@ def test_msm_points_in_the_exceptional_cases(api, O, n):
     assert np.array_equal(verifier.msm_points(pts, scalars), _msm_want(O, scalars, pts))
 
 
+# ---- vdb_msm_points_dev at every window width ----------------------------------------------------------------------------------------
+# The expected sum never forms a bucket: the points come from a pool of 8 curve points (and the identity) with random signs, so
+#   sum_i s_i P_i = sum_j (sum_{i: P_i = +-pool_j} +-s_i mod r) pool_j
+# is eight scalar multiplications over Python integers (the chord-and-tangent law of tests/l9_model.py).
+R_MOD = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
+WIDTHS = list(range(4, 14))
+SEG = 32                     # k_vmsm_segment's run of buckets
+
+
+def _width_n(c):
+    """the point count that makes vdb_msm_points_dev pick the window width c (vmsm_window: 4 below 256, then floor(log2 n) - 3, at most 13)"""
+    n = 255 if c == 4 else 1 << (c + 3)
+    lg = n.bit_length() - 1
+    assert min(lg - 3 if lg > 7 else 4, 13) == c
+    return n
+
+
+def _mont_rows(vals, mod, per_row):
+    """integers -> Montgomery form, `per_row` field elements per row of uint64 limbs"""
+    raw = b"".join((v * (1 << 256) % mod).to_bytes(32, "little") for v in vals)
+    return np.frombuffer(raw, dtype=np.uint64).reshape(-1, 4 * per_row).copy()
+
+
+def _point_row(pt):
+    return np.zeros(8, dtype=np.uint64) if pt is None else _mont_rows(pt, Q_MOD, 2)[0]
+
+
+def _structured_scalars(c):
+    """(tag, canonical scalar) for width c: W = ceil(254 / c) windows, the top one holding 254 - (W - 1) c bits"""
+    W = -(-254 // c)
+    top = 254 - (W - 1) * c
+    assert 0 < top < c and W * c > 254
+    out = [("all-ones", ((1 << 254) - 1) % R_MOD), ("all-ones", R_MOD - 1)]
+    for name, w in (("first", 0), ("last-full", W - 2), ("top", W - 1)):
+        width = top if w == W - 1 else c
+        for d in (1, (1 << c) - 1, SEG - 1, SEG, SEG + 1):
+            if d < 1 << width and d << (w * c) < R_MOD:
+                out.append((f"digit-{name}", d << (w * c)))
+    fill = ((1 << top) - 1) << ((W - 1) * c)               # every bit of the top window; reduced when it is not below r
+    out.append(("top-fill", fill % R_MOD))
+    out.append(("top-max", (R_MOD - 1) >> ((W - 1) * c) << ((W - 1) * c)))        # the largest top digit a canonical scalar has
+    for w in range(W - 1):
+        if (w * c) % 32 + c > 32:                            # the digit's bits lie in two 32-bit limbs
+            out += [("straddle", d << (w * c)) for d in ((1 << c) - 1, 1 | 1 << (c - 1))]
+    assert all(0 < s < R_MOD for _, s in out)
+    have = {t for t, _ in out}
+    assert {"all-ones", "digit-first", "digit-last-full", "digit-top", "top-fill", "top-max"} <= have, (c, have)
+    assert ("straddle" in have) == (32 % c != 0)            # c-bit windows tile the 32-bit limbs exactly when c divides 32
+    return out
+
+
+@pytest.fixture(scope="module")
+def msm_pool():
+    import random
+
+    import l9_model as L
+    rng = random.Random(254)
+    pool = [(1, 2)] + [L.ec_point(rng) for _ in range(7)]
+    assert len({p[0] for p in pool}) == 8
+    rows = np.stack([_point_row(p) for p in pool] + [_point_row(L.ec_neg(p)) for p in pool] + [_point_row(None)])
+    return L, pool, rows
+
+
+@pytest.mark.parametrize("c", WIDTHS)
+def test_msm_points_at_every_window_width(api, msm_pool, c):
+    """n = 255 (c = 4) and n = 2^(c + 3): structured scalars — every digit all-ones; one non-zero digit 1, 2^c - 1, 31, 32, 33 in the
+    first, the last full and the top window; the top window filled; digits that straddle a 32-bit limb — then zero scalars on points,
+    scalars on the identity, and random ones.  The pool is small, so every bucket that is hit holds repeated and opposite points"""
+    from halo2_vectordb_amd import verifier
+    L, pool, rows = msm_pool
+    n = _width_n(c)
+    rng = np.random.default_rng(7000 + c)
+    structured = _structured_scalars(c)
+    k = len(structured)
+    assert k + 64 <= n
+    which = rng.integers(0, 9, size=n)                     # 8: the identity
+    which[:k] = np.arange(k) % 8                           # the structured scalars sit on points
+    neg = rng.integers(0, 2, size=n)
+    scalars = [s for _, s in structured] + [int.from_bytes(rng.bytes(32), "little") % R_MOD for _ in range(n - k)]
+    zeros = [i for i in range(k, k + 32) if which[i] != 8][:8]
+    for i in zeros:
+        scalars[i] = 0
+    assert zeros and any(which[i] == 8 and scalars[i] for i in range(n))
+    coef = [0] * 8
+    for j, s, sg in zip(which, scalars, neg):
+        if j != 8:
+            coef[j] = (coef[j] - s if sg else coef[j] + s) % R_MOD
+    want = None
+    for cj, p in zip(coef, pool):
+        want = L.ec_add(want, L.ec_mul(cj, p))
+    idx = np.where(which == 8, 16, which + 8 * neg)
+    got = verifier.msm_points(rows[idx], _mont_rows(scalars, R_MOD, 1))
+    print("cases:", n, "structured:", k)
+    assert np.array_equal(got, _point_row(want))
+
+
+@pytest.mark.parametrize("c", WIDTHS)
+def test_msm_points_one_bucket_of_n_equal_points(api, msm_pool, c):
+    """every point the same, every scalar 1: n P through one bucket of n equal additions (the first doubles)"""
+    from halo2_vectordb_amd import verifier
+    L, pool, rows = msm_pool
+    n = _width_n(c)
+    got = verifier.msm_points(np.tile(rows[c % 8], (n, 1)), np.tile(_mont_rows([1], R_MOD, 1)[0], (n, 1)))
+    print("cases:", n)
+    assert np.array_equal(got, _point_row(L.ec_mul(n, pool[c % 8])))
+
+
 def _yardstick_vk(pr, out):
     from oracle import pairing as PR
     return dict(meta=_meta(pr), opened=out["opened"], fixed={name: pr.fixed[name].commits for name in FIXED}, tau_h=PR.pt_mul(PR.G2, TAU),
