@@ -78,6 +78,11 @@ _SIGNATURES = {
     "vdb_wit_ann_query_size": [_I, _U32, _U32, _SZ, _SZ, _SZ, _P, _P, _P],
     "vdb_wit_ann_query": [_I, _U32, _U32, _P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _P],
     "vdb_wit_ann_query_dev": [_I, _U32, _U32, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _P],
+    "vdb_wit_ann_update_size": [_SZ, _SZ, _SZ, _SZ, _U32, _P, _P, _P],
+    "vdb_wit_ann_update": [_P, _P, _SZ, _SZ, _SZ, _SZ, _U32, _P, _P, _SZ, _P, _P, _P],
+    "vdb_wit_ann_update_dev": [_P, _P, _SZ, _SZ, _SZ, _SZ, _U32, _P, _P, _SZ, _P, _P, _P],
+    "vdb_ann_index_apply_size": [_P, _SZ, _SZ, _U32, _P, _SZ, _P, _P, _P],
+    "vdb_ann_index_apply_dev": [_P, _P, _P, _P, _P, _SZ, _SZ, _SZ, _U32, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P],
     "vdb_wit_nearest_batch_size": [_I, _U32, _U32, _SZ, _SZ, _SZ, _P, _P],
     "vdb_wit_nearest_batch": [_I, _U32, _U32, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],
     "vdb_wit_nearest_batch_dev": [_I, _U32, _U32, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],

@@ -528,6 +528,67 @@ def wit_ann_query(metric, query, centroids, members, cluster_roots, P=48, L=13, 
                 index_root=pub[dim], public=pub)
 
 
+def wit_ann_update(levels, roots, cluster, n_c, new_vectors, indices, grow=0, selectors=False):
+    """m writes into cluster `cluster` of a committed index (vdb_wit_ann_update), the streams alone: `levels` cluster c's tree over its
+    n_c members (merkle_tree_build's array, after merkle_tree_grow when grow > 0), `roots` (K + 1, 4): [centroids' root | cluster roots],
+    new_vectors (m, dim, 4), indices (m,): slots of the cluster, each below the fill at its turn or equal to it (an append).
+    dict(stream, selectors, flags, input_cells, update_base, public (3 m + 3, 4): [index_root_old | c | idx, old leaf, new leaf per write |
+    index_root_new], levels: the cluster's tree after the batch)"""
+    lib = _lib.init()
+    new_vectors, roots = _fr(new_vectors), _fr(roots)
+    levels = np.array(levels, dtype=np.uint64, copy=True)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64)
+    m, dim, K = idx.shape[0], new_vectors.shape[1], roots.shape[0] - 1
+    assert idx.shape == (m,) and new_vectors.shape[0] == m and levels.shape == (2 * (merkle_levels(n_c)[0] << grow), 4)
+    cells, n_in, ub = _u64(), _u64(), _u64()
+    check(lib.vdb_wit_ann_update_size(_sz(K), _sz(n_c), _sz(dim), _sz(m), int(grow), ctypes.byref(cells), ctypes.byref(n_in), ctypes.byref(ub)))
+    stream = np.zeros((cells.value, 4), dtype=np.uint64)
+    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
+    pub = np.zeros((3 * m + 3, 4), dtype=np.uint64)
+    check(lib.vdb_wit_ann_update(_p(levels), _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(dim), int(grow), _p(new_vectors), _p(idx), _sz(m), _p(stream),
+                                 _p(sel) if selectors else None, _p(pub)))
+    return dict(stream=stream, **_split_flags(sel), input_cells=n_in.value, update_base=ub.value, public=pub, levels=levels)
+
+
+def ann_index_apply_layout(sizes, cluster, grow, indices):
+    """(appends, digests of the forest after the batch, its K + 2 segment offsets) of vdb_ann_index_apply_dev (vdb_ann_index_apply_size;
+    VdbError on a write above the fill, or a `grow` that is not the smallest that fits the appends)"""
+    lib = _lib.init()
+    sizes, idx = np.ascontiguousarray(sizes, dtype=np.uint64), np.ascontiguousarray(indices, dtype=np.uint64)
+    K = sizes.shape[0]
+    appends, digests, seg = _u64(), _u64(), np.zeros(K + 2, dtype=np.uint64)
+    check(lib.vdb_ann_index_apply_size(_p(sizes), _sz(K), _sz(cluster), int(grow), _p(idx), _sz(idx.shape[0]), ctypes.byref(appends), ctypes.byref(digests),
+                                       _p(seg)))
+    return appends.value, digests.value, seg
+
+
+def ann_index_apply(index, cluster, grow, updated_levels, new_vectors, indices, db_slots):
+    """the index after a batch of writes into one cluster (vdb_ann_index_apply_dev), host arrays in and out: `index` an ann_index_build
+    dict, updated_levels the cluster's tree the witness call left, db_slots one database slot per append -> a dict of the same form"""
+    lib = _lib.init()
+    new_vectors, updated = _fr(new_vectors), _fr(updated_levels)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64)
+    slots_new = np.ascontiguousarray(db_slots, dtype=np.uint32)
+    sizes = np.diff(np.asarray(index["offsets"], dtype=np.uint64)).astype(np.uint64)
+    K, dim, n = sizes.shape[0], new_vectors.shape[1], index["grouped"].shape[0]
+    appends, digests, seg = ann_index_apply_layout(sizes, cluster, grow, idx)
+    assert slots_new.shape == (appends,) and idx.shape == (new_vectors.shape[0],)
+    n2 = n + appends
+    src = [index["grouped"], np.ascontiguousarray(index["slots"], dtype=np.uint32), index["forest"], index["roots"], updated, new_vectors]
+    ins = [DeviceBuffer(max(a.nbytes, 32)) for a in src]
+    outs = [DeviceBuffer(max(b, 32)) for b in (n2 * dim * 32, n2 * 4, (K + 1) * 8, digests * 32, (K + 2) * 32)]
+    try:
+        for b, a in zip(ins, src):
+            b.upload(np.ascontiguousarray(a))
+        check(lib.vdb_ann_index_apply_dev(ins[0].ptr, ins[1].ptr, ins[2].ptr, ins[3].ptr, _p(sizes), _sz(K), _sz(dim), _sz(cluster), int(grow), ins[4].ptr,
+                                          ins[5].ptr, _p(idx), _p(slots_new) if appends else None, _sz(idx.shape[0]), *[o.ptr for o in outs]))
+        return dict(grouped=outs[0].download((n2, dim, 4)), slots=outs[1].download((n2,), dtype=np.uint32), offsets=outs[2].download((K + 1,), dtype=np.uint64),
+                    forest=outs[3].download((digests, 4)), segments=seg, roots=outs[4].download((K + 2, 4)))
+    finally:
+        for b in ins + outs:
+            b.free()
+
+
 def wit_merkle_open(levels, n, indices, vectors=None, selectors=False):
     """m openings (vdb_wit_merkle_open) of the tree `levels` (merkle_tree_build's array over n vectors, or what a batch of updates left):
     slot indices[j] is read.  `vectors` (m, dim, 4): the vectors read (vector mode); None: leaf mode, any slot of the padded tree.

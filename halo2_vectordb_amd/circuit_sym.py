@@ -1227,13 +1227,19 @@ class _CellTrace:
         st = self.perm(at, 2, None, [left, right])
         return self.perm(at + perm_cells(2), 0, st, [])[1]
 
-    def leaf(self, at, lay, word0):
-        """the sponge of one leaf over the assigned words word0, word0 + 1, ... -> (the squeeze cell, the first cell after it)"""
+    def leaf(self, at, lay, word0, words=None):
+        """the sponge of one leaf over the assigned words word0, word0 + 1, ... (or over the cells `words`) -> (the squeeze cell, the
+        first cell after it)"""
         state = None
         for p in range(lay["nperm"]):
-            state = self.perm(at, lay["n_ins"][p], state, [word0 + 2 * p + i for i in range(lay["n_ins"][p])])
+            k = [2 * p + i for i in range(lay["n_ins"][p])]
+            state = self.perm(at, lay["n_ins"][p], state, [word0 + i for i in k] if words is None else [words[i] for i in k])
             at += lay["sizes"][p]
         return state[1], at
+
+    def is_zero(self, at, a):                                # [z, a, inv, 1, 0, a, z, 0] -> the second z (ctx.get(-2))
+        self.put(at, [None, ("c", a), None, ("k", 1), ("k", 0), ("c", a), ("c", at), ("k", 0)], [1, 0, 0, 0, 1, 0, 0, 0])
+        return at + 6
 
     def path(self, at, curs, bits, sibs):
         """the levels of a path from cell `at` on, for the one or two running digests that start at the cells `curs` (an update: its old
@@ -1264,6 +1270,42 @@ class _CellTrace:
                        np.asarray(self.gate, dtype=bool), np.zeros(0, dtype=np.int64))
 
 
+def _trace_update_block(t, lay, base):
+    """the cells of a batch of updates (lay: merkle_update_layout) traced into `t` from stream cell `base` on -> the public cells"""
+    m, grow = len(lay["kinds"]), lay["grow"]
+    dim, depth = lay["n_vec"] // max(lay["w"], 1), (lay["sibs"] - lay["bits"]) // m
+    idx_cells, new_leaves, prev_top, top_old0 = [], [], None, None
+    if grow:
+        at = t.put(base + lay["z0"], [("k", 0)], [0])         # Z_0 = ctx.load_constant(0)
+        z, prev_top = [base + lay["z0"]], base + lay["r0"]
+        for l in range(depth - 1):
+            z.append(t.node(at, z[l], z[l]))
+            at += lay["node_cells"]
+        for i in range(grow):
+            prev_top = t.node(at, prev_top, z[depth - grow + i])
+            at += lay["node_cells"]
+        assert at == base + lay["block"][0]
+    for j in range(m):
+        if lay["kinds"][j]:
+            cur_new = base + lay["block"][j]
+            at = t.put(cur_new, [("k", 0)], [0])             # new_leaf = ctx.load_constant(0)
+        else:
+            cur_new, at = t.leaf(base + lay["block"][j], lay, base + lay["write_no"][j] * dim)
+        assert at == base + lay["levels_at"][j]
+        cur_old = base + lay["old_leaf"] + j
+        new_leaves.append(cur_new)
+        (cur_old, cur_new), idx_cell, at = t.path(at, [cur_old, cur_new], range(base + lay["bits"] + j * depth, base + lay["bits"] + (j + 1) * depth),
+                                                  range(base + lay["sibs"] + j * depth, base + lay["sibs"] + (j + 1) * depth))
+        idx_cells.append(idx_cell)
+        assert at == base + (lay["block"][j + 1] if j + 1 < m else lay["total"])
+        if j == 0:
+            top_old0 = base + lay["r0"] if grow else cur_old
+        if prev_top is not None:
+            t.copy_of[cur_old] = prev_top                    # ctx.constrain_equal(cur_old, root_{j-1}) (update 0: R_grow)
+        prev_top = cur_new
+    return merkle_update_instances(m, top_old0, idx_cells, [base + lay["old_leaf"] + j for j in range(m)], new_leaves, prev_top)
+
+
 def trace_merkle_update(m, dim, depth, fetch_flags, fetch_values, kinds=None, grow=0):
     """The closure of a batch of m path updates cell by cell (the ground truth of build_merkle_update): assign the witness groups, the
     growth block when the tree was grown, then per update the leaf sponge (a write) or the constant 0 (a delete), the levels and the
@@ -1272,53 +1314,24 @@ def trace_merkle_update(m, dim, depth, fetch_flags, fetch_values, kinds=None, gr
     every kind of permutation is read: the Poseidon constants are fixed-column values).  -> (CopyMap, public cells)"""
     lay = merkle_update_layout(m, dim, depth, kinds, grow)
     t = _CellTrace(lay["total"], fetch_flags, fetch_values)
-    idx_cells, new_leaves, prev_top, top_old0 = [], [], None, None
-    if grow:
-        at = t.put(lay["z0"], [("k", 0)], [0])                # Z_0 = ctx.load_constant(0)
-        z, prev_top = [lay["z0"]], lay["r0"]
-        for l in range(depth - 1):
-            z.append(t.node(at, z[l], z[l]))
-            at += lay["node_cells"]
-        for i in range(grow):
-            prev_top = t.node(at, prev_top, z[depth - grow + i])
-            at += lay["node_cells"]
-        assert at == lay["block"][0]
-    for j in range(m):
-        if lay["kinds"][j]:
-            cur_new = lay["block"][j]
-            at = t.put(cur_new, [("k", 0)], [0])             # new_leaf = ctx.load_constant(0)
-        else:
-            cur_new, at = t.leaf(lay["block"][j], lay, lay["write_no"][j] * dim)
-        assert at == lay["levels_at"][j]
-        cur_old = lay["old_leaf"] + j
-        new_leaves.append(cur_new)
-        (cur_old, cur_new), idx_cell, at = t.path(at, [cur_old, cur_new], range(lay["bits"] + j * depth, lay["bits"] + (j + 1) * depth),
-                                                  range(lay["sibs"] + j * depth, lay["sibs"] + (j + 1) * depth))
-        idx_cells.append(idx_cell)
-        assert at == (lay["block"][j + 1] if j + 1 < m else lay["total"])
-        if j == 0:
-            top_old0 = lay["r0"] if grow else cur_old
-        if prev_top is not None:
-            t.copy_of[cur_old] = prev_top                    # ctx.constrain_equal(cur_old, root_{j-1}) (update 0: R_grow)
-        prev_top = cur_new
-    return t.finish(), merkle_update_instances(m, top_old0, idx_cells, [lay["old_leaf"] + j for j in range(m)], new_leaves, prev_top)
+    public = _trace_update_block(t, lay, 0)
+    return t.finish(), public
 
 
-def build_merkle_update(m, dim, depth, fetch_flags, fetch_values, builder=None, kinds=None, grow=0):
-    """trace_merkle_update's map assembled from unit blocks — one per kind of permutation, the bit with its two selects, the two selects
-    of the new path, the index inner product — each placed for all m updates at once, level after level (`builder`: as build_kmeans);
-    the growth block's hashes one after the other, the constants (Z_0, each delete's 0) as fixed-column cells.
-    -> (CopyMap, public cells)"""
+def place_merkle_update(B, m, dim, depth, fetch_flags, fetch_values, base=0, kinds=None, grow=0):
+    """trace_merkle_update's cells placed into builder `B` from stream cell `base` on, from unit blocks — one per kind of permutation,
+    the bit with its two selects, the two selects of the new path, the index inner product — each placed for all m updates at once, level
+    after level; the growth block's hashes one after the other, the constants (Z_0, each delete's 0) as fixed-column cells.
+    -> the public cells [old root | idx, old leaf, new leaf per update | new root]"""
     lay = merkle_update_layout(m, dim, depth, kinds, grow)
-    B = (builder or _Builder)(lay["total"], 0)
     j = np.arange(m, dtype=np.int64)
-    base = np.asarray(lay["block"], dtype=np.int64)
+    blocks = base + np.asarray(lay["block"], dtype=np.int64)
     perm = _perm_placer(B, fetch_flags, fetch_values)
     top = None
     if grow:
-        B.constant_cell(lay["z0"], 0)                        # Z_0 = ctx.load_constant(0)
+        B.constant_cell(base + lay["z0"], 0)                 # Z_0 = ctx.load_constant(0)
         one = lambda c: np.asarray([c], dtype=np.int64)
-        z, top, at = [one(lay["z0"])], one(lay["r0"]), lay["z0"] + 1
+        z, top, at = [one(base + lay["z0"])], one(base + lay["r0"]), base + lay["z0"] + 1
         for l in range(depth - 1):
             z.append(_node(perm, one(at), z[l], z[l]))
             at += lay["node_cells"]
@@ -1327,20 +1340,129 @@ def build_merkle_update(m, dim, depth, fetch_flags, fetch_values, builder=None, 
             at += lay["node_cells"]
 
     is_write = np.asarray(lay["kinds"], dtype=np.int64) == 0
-    new_leaf = base.copy()                                   # a delete: its block starts with new_leaf = ctx.load_constant(0)
-    for c in base[~is_write]:
+    new_leaf = blocks.copy()                                 # a delete: its block starts with new_leaf = ctx.load_constant(0)
+    for c in blocks[~is_write]:
         B.constant_cell(int(c), 0)
     if lay["w"]:
-        word0 = np.arange(lay["w"], dtype=np.int64) * dim
-        new_leaf[is_write], _ = _place_leaf_sponge(perm, base[is_write], lay, [word0 + k for k in range(dim)])
-    path = j[:, None] * depth + np.arange(depth, dtype=np.int64)[None, :]
-    (cur_old, cur_new), idx = _place_path(B, perm, lay, np.asarray(lay["levels_at"], dtype=np.int64), lay["bits"] + path, lay["sibs"] + path,
-                                          [lay["old_leaf"] + j, new_leaf])
+        word0 = base + np.arange(lay["w"], dtype=np.int64) * dim
+        new_leaf[is_write], _ = _place_leaf_sponge(perm, blocks[is_write], lay, [word0 + k for k in range(dim)])
+    path = base + j[:, None] * depth + np.arange(depth, dtype=np.int64)[None, :]
+    (cur_old, cur_new), idx = _place_path(B, perm, lay, base + np.asarray(lay["levels_at"], dtype=np.int64), lay["bits"] + path, lay["sibs"] + path,
+                                          [base + lay["old_leaf"] + j, new_leaf])
     if grow:
         B.tie(int(cur_old[0]), int(top[0]))                  # ctx.constrain_equal(cur_old, R_grow)
     for k in range(1, m):
         B.tie(int(cur_old[k]), int(cur_new[k - 1]))          # ctx.constrain_equal(cur_old, root_{j-1})
-    return B.finish(), merkle_update_instances(m, lay["r0"] if grow else cur_old[0], idx, lay["old_leaf"] + j, new_leaf, cur_new[m - 1])
+    return merkle_update_instances(m, base + lay["r0"] if grow else cur_old[0], idx, base + lay["old_leaf"] + j, new_leaf, cur_new[m - 1])
+
+
+def build_merkle_update(m, dim, depth, fetch_flags, fetch_values, builder=None, kinds=None, grow=0):
+    """trace_merkle_update's map assembled by place_merkle_update at stream cell 0 (`builder`: as build_kmeans).
+    -> (CopyMap, public cells)"""
+    lay = merkle_update_layout(m, dim, depth, kinds, grow)
+    B = (builder or _Builder)(lay["total"], 0)
+    public = place_merkle_update(B, m, dim, depth, fetch_flags, fetch_values, 0, kinds, grow)
+    return B.finish(), public
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Inserts and replacements against the index root (include/vdb.h vdb_wit_ann_update; pipeline.AnnUpdateHotPath)
+def ann_update_layout(K, m, dim, depth, grow=0):
+    """where the blocks of the index update circuit start: dict(c, centroids_root, roots: the assigned header; n_in; indicator, select,
+    sponge_old, update, new_roots, sponge_new: the blocks; total; update_layout: merkle_update_layout of block E (relative to `update`);
+    sponge: merkle_leaf_layout(K + 1))"""
+    if K < 1:
+        raise ValueError("an index has at least one cluster")
+    upd, sp = merkle_update_layout(m, dim, depth, None, grow), merkle_leaf_layout(K + 1)
+    lay = dict(c=0, centroids_root=1, roots=2, n_in=K + 2, indicator=K + 2, update_layout=upd, sponge=sp)
+    lay["select"] = lay["indicator"] + 8 + 12 * (K - 1)
+    lay["sponge_old"] = lay["select"] + 1 + 3 * K
+    lay["update"] = lay["sponge_old"] + sp["leaf_cells"]
+    lay["new_roots"] = lay["update"] + upd["total"]
+    lay["sponge_new"] = lay["new_roots"] + 8 * K
+    lay["total"] = lay["sponge_new"] + sp["leaf_cells"]
+    return lay
+
+
+def _indicator_at(lay, j):
+    return lay["indicator"] + (8 + 12 * (j - 1) if j else 0)
+
+
+def ann_update_instances(index_root_old, c, update_public, index_root_new):
+    """the public cells in make_public order: [index_root_old | c | idx, old leaf, new leaf per write | index_root_new] (the update
+    block's own old and new roots are not public)"""
+    return [int(index_root_old), int(c)] + [int(x) for x in update_public[1:-1]] + [int(index_root_new)]
+
+
+def trace_ann_update(K, m, dim, depth, fetch_flags, fetch_values, grow=0):
+    """The closure of m writes into one cluster of a committed index cell by cell (the ground truth of build_ann_update): the header
+    [c | centroids_root | cluster roots] assigned, idx_to_indicator(c, K) as select_from_idx unrolls it, select_by_indicator(cluster
+    roots, indicators) -> picked, the sponge over the header's roots, the update block (trace_merkle_update's cells), whose old root is
+    tied to picked, out_j = select(new cluster root, cluster_root_j, indicator_j) and the sponge over [centroids_root | out_j].
+    -> (CopyMap, public cells, dict(indicators, picked, old_root, new_root, outs, index_root_old, index_root_new, layout))"""
+    lay = ann_update_layout(K, m, dim, depth, grow)
+    t = _CellTrace(lay["total"], fetch_flags, fetch_values)
+    c, roots = lay["c"], [lay["roots"] + j for j in range(K)]
+    inds = [t.is_zero(lay["indicator"], c)]
+    for j in range(1, K):
+        at = _indicator_at(lay, j)
+        t.put(at, [None, ("k", j), ("k", 1), ("c", c)], [1, 0, 0, 0])      # is_equal(c, Constant(j)) = sub [d, j, 1, c] + is_zero(d)
+        inds.append(t.is_zero(at + 4, at))
+    cells, gates = [("k", 0)], [1]
+    for j in range(K):
+        cells += [("c", roots[j]), ("c", inds[j]), None]
+        gates += [0, 0, j + 1 < K]
+    picked = t.put(lay["select"], cells, gates) - 1
+    root_old, at = t.leaf(lay["sponge_old"], lay["sponge"], None, [lay["centroids_root"]] + roots)
+    assert at == lay["update"]
+    upub = _trace_update_block(t, lay["update_layout"], lay["update"])
+    t.copy_of[upub[0]] = picked                              # ctx.constrain_equal(picked, the update block's old root)
+    outs = [t.select(lay["new_roots"] + 8 * j, upub[-1], roots[j], inds[j]) for j in range(K)]
+    root_new, at = t.leaf(lay["sponge_new"], lay["sponge"], None, [lay["centroids_root"]] + outs)
+    assert at == lay["total"]
+    info = dict(indicators=inds, picked=picked, old_root=upub[0], new_root=upub[-1], outs=outs, index_root_old=root_old, index_root_new=root_new, layout=lay)
+    return t.finish(), ann_update_instances(root_old, c, upub, root_new), info
+
+
+def build_ann_update(K, m, dim, depth, fetch_flags, fetch_values, builder=None, grow=0):
+    """trace_ann_update's map assembled from unit blocks: is_equal(c, Constant(j)) placed for all j >= 1 at once (its constant j set per
+    instance), select_by_indicator over K cells, the two sponges (place_sponge), the update block (place_merkle_update at its base) and
+    the K selects placed at once (`builder`: as build_kmeans).  -> as trace_ann_update"""
+    lay = ann_update_layout(K, m, dim, depth, grow)
+    if np.asarray(fetch_flags(0, lay["n_in"])).any():
+        raise ValueError("the assigned header carries no gate or constant flag")
+    B = (builder or _Builder)(lay["total"], 0)
+    c, roots = lay["c"], lay["roots"] + np.arange(K, dtype=np.int64)
+    s = Sym(0, 0)
+    iz = Block(s, [s.g_is_zero(ext(0))])
+    inds = [int(B.place(iz, [lay["indicator"]], [0], [[c]])[0, 0])]
+    if K > 1:
+        s = Sym(0, 0)
+        d = s.push(None, True)                               # is_equal(c, Constant(j)) = sub [d, j, 1, c] + is_zero(d)
+        s.push(None); s.push(C(1)); s.push(ext(0))
+        ie = Block(s, [s.g_is_zero(d)])
+        at = np.asarray([_indicator_at(lay, j) for j in range(1, K)], dtype=np.int64)
+        inds += [int(x) for x in B.place(ie, at, np.zeros(K - 1, dtype=np.int64), np.full((K - 1, 1), c, dtype=np.int64))[:, 0]]
+        for j in range(1, K):
+            B.constant_cell(int(at[j - 1]) + 1, j)
+    inds = np.asarray(inds, dtype=np.int64)
+    s = Sym(0, 0)
+    sb = Block(s, [s.g_select_by_indicator([ext(i) for i in range(K)], [ext(K + i) for i in range(K)])])
+    picked = int(B.place(sb, [lay["select"]], [0], np.concatenate([roots, inds])[None, :])[0, 0])
+    root_old, end = place_sponge(B, lay["sponge_old"], [lay["centroids_root"]] + [int(r) for r in roots], fetch_flags, fetch_values)
+    assert end == lay["update"]
+    upub = place_merkle_update(B, m, dim, depth, fetch_flags, fetch_values, lay["update"], None, grow)
+    B.tie(upub[0], picked)                                   # ctx.constrain_equal(picked, the update block's old root)
+    s = Sym(0, 0)
+    sl = Block(s, [s.g_select(ext(0), ext(1), ext(2))])
+    outs = B.place(sl, lay["new_roots"] + 8 * np.arange(K, dtype=np.int64), np.zeros(K, dtype=np.int64),
+                   np.stack([np.full(K, upub[-1], dtype=np.int64), roots, inds], axis=1))[:, 0]
+    root_new, end = place_sponge(B, lay["sponge_new"], [lay["centroids_root"]] + [int(o) for o in outs], fetch_flags, fetch_values)
+    if end != lay["total"]:
+        raise ValueError("the trace does not end where the circuit does")
+    info = dict(indicators=[int(i) for i in inds], picked=picked, old_root=upub[0], new_root=upub[-1], outs=[int(o) for o in outs], index_root_old=root_old,
+                index_root_new=root_new, layout=lay)
+    return B.finish(), ann_update_instances(root_old, c, upub, root_new), info
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 
+#include "ann_update_host.hpp"
 #include "common.hpp"
 #include "gadgets.hpp"
 #include "poseidon.hpp"
@@ -1684,10 +1685,7 @@ int wit_kmeans_dev(FpEntry* fp, int metric, const u256* vectors, size_t n, size_
   return inv_list_fixup(st);
 }
 
-// the tree over n leaves: its padded leaf count and its depth
-static void tree_shape(uint64_t n, uint64_t* lp, uint32_t* depth) {
-  for (*lp = 1, *depth = 0; *lp < n; *lp <<= 1) ++*depth;
-}
+// (tree_shape, the padded leaf count and the depth of the tree over n leaves: ann_update_host.hpp)
 struct MkLayout {
   uint32_t nperm, depth;
   uint64_t leaf_cells, leaves, n_leaves_pow2, zero_cell, total;
@@ -1844,42 +1842,51 @@ static int mku_layout(size_t n, size_t dim, size_t m, const uint8_t* kinds, unsi
   if (lp_out) *lp_out = lp;
   return VDB_OK;
 }
-// `levels`: the tree at depth d + grow (merkle_tree_grow_dev's when grow > 0), left in the state after the batch; new_vectors: the rows of
-// the writes in update order
-int wit_merkle_update_dev(u256* levels, size_t n, size_t dim, unsigned grow, const u256* new_vectors, const uint64_t* indices, const uint8_t* kinds,
-                          size_t m, Streams st, u256* pub) {
-  static thread_local std::vector<uint64_t> h_level_at;
-  static thread_local std::vector<int32_t> h_write_no;
-  static thread_local std::vector<uint64_t> hbuf;  // pageable source: hipMemcpyAsync stages it before returning
-  VDB_ARG(m > 0 && m <= MKU_MAX_UPDATES, "a batch holds 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES updates");
-  h_level_at.resize(m);
-  h_write_no.resize(m);
+// What a batch of updates is on the host before anything is launched (mku_plan): its layout and, in one array that a single upload
+// takes to the device, [level_at m | leaf_at w: where the sponge of write v starts | idx m | write_no m | write_of w: the update of write v]
+struct MkuPlan {
   MkuLayout ml;
   uint64_t lp;
-  TRY(mku_layout(n, dim, m, kinds, grow, &ml, &lp, h_level_at.data(), h_write_no.data()));
+  size_t n_tab;
+  std::vector<uint64_t> level_at, tab;   // (tab: the pageable source of the upload; hipMemcpyAsync stages it before returning)
+  std::vector<int32_t> write_no;
+};
+static int mku_plan(size_t n, size_t dim, unsigned grow, const u256* new_vectors, const uint64_t* indices, const uint8_t* kinds, size_t m, MkuPlan* p) {
+  VDB_ARG(m > 0 && m <= MKU_MAX_UPDATES, "a batch holds 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES updates");
+  p->level_at.resize(m);
+  p->write_no.resize(m);
+  MkuLayout& ml = p->ml;
+  TRY(mku_layout(n, dim, m, kinds, grow, &ml, &p->lp, p->level_at.data(), p->write_no.data()));
   VDB_ARG(new_vectors || ml.w == 0, "null pointer: a write needs its new vector");
-  // one upload: [level_at m | leaf_at w: where the sponge of write v starts | idx m | write_no m | write_of w: the update of write v]
   const size_t w = ml.w;
-  const size_t n_tab = (m + w) * sizeof(uint64_t) + (2 * m + w) * sizeof(uint32_t);
-  hbuf.resize(n_tab / sizeof(uint64_t) + 1);
-  uint64_t* p_level_at = hbuf.data();
+  p->n_tab = (m + w) * sizeof(uint64_t) + (2 * m + w) * sizeof(uint32_t);
+  p->tab.resize(p->n_tab / sizeof(uint64_t) + 1);
+  uint64_t* p_level_at = p->tab.data();
   uint64_t* p_leaf_at = p_level_at + m;
   uint32_t* p_idx = (uint32_t*)(p_leaf_at + w);
   int32_t* p_write_no = (int32_t*)(p_idx + m);
   uint32_t* p_write_of = (uint32_t*)(p_write_no + m);
   for (size_t j = 0; j < m; j++) {
-    VDB_ARG(indices[j] < lp, "update index outside the padded tree (grow it first: vdb_merkle_tree_grow_dev)");
-    p_level_at[j] = h_level_at[j];
+    VDB_ARG(indices[j] < p->lp, "update index outside the padded tree (grow it first: vdb_merkle_tree_grow_dev)");
+    p_level_at[j] = p->level_at[j];
     p_idx[j] = (uint32_t)indices[j];
-    p_write_no[j] = h_write_no[j];
-    if (h_write_no[j] >= 0) {
-      p_leaf_at[h_write_no[j]] = h_level_at[j] - ml.leaf_cells;
-      p_write_of[h_write_no[j]] = (uint32_t)j;
+    p_write_no[j] = p->write_no[j];
+    if (p->write_no[j] >= 0) {
+      p_leaf_at[p->write_no[j]] = p->level_at[j] - ml.leaf_cells;
+      p_write_of[p->write_no[j]] = (uint32_t)j;
     }
   }
-  FpEntry* fp;
-  const PoseidonSpec* sp;
-  TRY(mk_begin(st, &fp, &sp));
+  return VDB_OK;
+}
+// The cells of a planned batch from stream cell `base` on, and its 3 m + 2 public values into `pub` (the caller has published the call's
+// context: mk_begin).  `levels`: the tree at depth d + grow (merkle_tree_grow_dev's when grow > 0), left in the state after the batch;
+// new_vectors: the rows of the writes in update order
+static int mku_emit(FpEntry* fp, const PoseidonSpec* sp, const MkuPlan& pl, u256* levels, size_t dim, const u256* new_vectors, const Streams& st,
+                    uint64_t base, u256* pub) {
+  const MkuLayout& ml = pl.ml;
+  const uint64_t lp = pl.lp;
+  const size_t m = ml.m, w = ml.w, n_tab = pl.n_tab;
+  const unsigned grow = ml.grow;
   const u256* empty = nullptr;
   if (grow) TRY(poseidon_empty_subtrees_dev(&empty));
   hipStream_t s = ctx().stream;
@@ -1901,7 +1908,7 @@ int wit_merkle_update_dev(u256* levels, size_t n, size_t dim, unsigned grow, con
   int32_t* sib_from = (int32_t*)(write_of + w);
   int32_t* prev_same = sib_from + m * depth;
   uint8_t* last = (uint8_t*)(prev_same + m);
-  VDB_HIP(hipMemcpyAsync(level_at, hbuf.data(), n_tab, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(level_at, pl.tab.data(), n_tab, hipMemcpyHostToDevice, s));
   const uint32_t mu = (uint32_t)m, wu = (uint32_t)w;
   // grids of at least one block: the launches of a call do not depend on how many of its updates are writes
   VDB_LAUNCH(k_mku_touchers, dim3((unsigned)((m * depth + 255) / 256)), dim3(256), didx, mu, depth, sib_from, prev_same, last, write_no, path_new);
@@ -1910,14 +1917,24 @@ int wit_merkle_update_dev(u256* levels, size_t n, size_t dim, unsigned grow, con
   for (uint32_t l = 0; l < depth; l++)
     VDB_LAUNCH(k_mku_level, dim3((unsigned)((2 * m + 63) / 64)), dim3(64), sp, levels, lp, didx, mu, depth, l, sib_from, prev_same, wit, path_old, path_new);
   if (grow)  // R_i and the public old root, read before the write-back replaces them
-    VDB_LAUNCH(k_mku_grow_trace, dim3((unsigned)((2 * (depth - 1 + grow) + 63) / 64)), dim3(64), st, fp->dev, sp, ml, 0, lp, levels, empty, pub);
+    VDB_LAUNCH(k_mku_grow_trace, dim3((unsigned)((2 * (depth - 1 + grow) + 63) / 64)), dim3(64), st, fp->dev, sp, ml, base, lp, levels, empty, pub);
   VDB_LAUNCH(k_mku_writeback, dim3((unsigned)((n_path + 63) / 64)), dim3(64), levels, lp, didx, mu, depth, last, path_new);
-  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)((ml.n_vec + n_wit + 255) / 256)), dim3(256), st, 0, new_vectors, wit, ml.n_vec, ml.n_vec + n_wit);
-  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((w * ml.nperm + 63) / 64 + (w == 0))), dim3(64), st, fp->dev, sp, new_vectors, wu, (uint32_t)dim, ml.nperm, 0,
+  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)((ml.n_vec + n_wit + 255) / 256)), dim3(256), st, base, new_vectors, wit, ml.n_vec, ml.n_vec + n_wit);
+  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((w * ml.nperm + 63) / 64 + (w == 0))), dim3(64), st, fp->dev, sp, new_vectors, wu, (uint32_t)dim, ml.nperm, base,
              ml.leaf_cells, states, leaf_at);
-  VDB_LAUNCH(k_mku_level_trace, dim3((unsigned)((m * depth + 63) / 64), 5), dim3(64), st, fp->dev, sp, ml, 0, level_at, didx, wit, path_old, path_new);
-  VDB_LAUNCH(k_mku_index, dim3((unsigned)((m + 63) / 64)), dim3(64), st, fp->dev, ml, 0, level_at, didx, write_no, wit, path_old, path_new, pub);
+  VDB_LAUNCH(k_mku_level_trace, dim3((unsigned)((m * depth + 63) / 64), 5), dim3(64), st, fp->dev, sp, ml, base, level_at, didx, wit, path_old, path_new);
+  VDB_LAUNCH(k_mku_index, dim3((unsigned)((m + 63) / 64)), dim3(64), st, fp->dev, ml, base, level_at, didx, write_no, wit, path_old, path_new, pub);
   return VDB_OK;
+}
+// vdb_wit_merkle_update_ops: the batch alone, at stream cell 0
+int wit_merkle_update_dev(u256* levels, size_t n, size_t dim, unsigned grow, const u256* new_vectors, const uint64_t* indices, const uint8_t* kinds,
+                          size_t m, Streams st, u256* pub) {
+  static thread_local MkuPlan pl;
+  TRY(mku_plan(n, dim, grow, new_vectors, indices, kinds, m, &pl));
+  FpEntry* fp;
+  const PoseidonSpec* sp;
+  TRY(mk_begin(st, &fp, &sp));
+  return mku_emit(fp, sp, pl, levels, dim, new_vectors, st, 0, pub);
 }
 
 // sizes of m openings in a tree over n vectors; the limits of one call (include/vdb.h).  No cap on m beyond the cell count: nothing
@@ -2201,6 +2218,230 @@ int wit_ann_query_dev(FpEntry* fp, int metric, const u256* query, const u256* ce
   VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((a.mw.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, words, 1u, (uint32_t)(K + 1), a.mw.nperm, a.b_root,
              a.mw.leaf_cells, wstates, nullptr);
   return inv_list_fixup(st);
+}
+
+// ------------------------------------------------------------------ inserts and replacements against the index root (include/vdb.h
+// vdb_wit_ann_update, vdb_ann_index_apply_dev).  m writes into cluster c move index_root_old to index_root_new in one circuit:
+// A [c | centroids_root | cluster roots] assigned, B idx_to_indicator(c, K), C select_by_indicator(cluster roots, indicators) -> picked,
+// D the sponge over the header's roots, E the update block of the cluster's tree (mku_emit at its base), F out_j = select(new cluster
+// root, cluster_root_j, indicator_j), G the sponge over [centroids_root | out_j].  The map ties picked to E's old root.
+struct AnnuLayout {
+  MkLayout mw;
+  AnnuBlocks b;
+};
+// work space of the call, in u256: [c | words_old K + 1] (the header as it is assigned) | ind K | picked | words_new K + 1 |
+// index_root_old, index_root_new | the update block's public values 3 m + 2 | the sponge states of D and of G
+struct AnnuWork {
+  u256 *hdr, *ind, *picked, *words_new, *iroot, *upub, *st_old, *st_new;
+};
+// the header: lane i < K + 2 assigns cell i and keeps the value for the blocks that read it
+__global__ __launch_bounds__(256) void k_annu_header(Streams st, uint64_t base, uint32_t c, const u256* __restrict__ roots, uint32_t K,
+                                                     u256* __restrict__ hdr) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= K + 2) return;
+  const u256 v = i ? roots[i - 1] : Gadgets::mont_small(c);
+  hdr[i] = v;
+  const uint64_t p = base + i;
+  if (p < st.rlo || p >= st.rhi) return;
+  st.adv[p] = v;
+  if (st.sel) st.sel[p] = 0;
+}
+// idx_to_indicator(c, K) as g_select_from_idx unrolls it, a lane per j: indicator 0 is is_zero(c) (8 cells), indicator j >= 1 is
+// is_equal(c, Constant(j)) (12 cells); the inverse of c - j comes from the small-inverse table or goes through the inverse list
+__global__ __launch_bounds__(64) void k_annu_indicator(Streams st, const FpTables* __restrict__ T, uint64_t base, uint32_t c, uint32_t K,
+                                                       u256* __restrict__ ind) {
+  const uint32_t j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= K) return;
+  ind[j] = j == c ? mont_one<Fr>() : u256_zero();
+  WCtx cx = make_ctx(st, T, base + annu_indicator_off(j), 0);
+  Gadgets g(cx);
+  if (cx.skip(j ? 12 : 8)) return;
+  const int64_t diff = (int64_t)c - (int64_t)j;
+  const u256 idx = Gadgets::mont_small(c);
+  if (j == 0) {
+    g.g_is_zero_inv(idx, g.signed_small_inv(idx, diff));
+  } else {
+    const u256 cj = Gadgets::mont_small(j), d = fr_sub(idx, cj);
+    cx.push(d, true); cx.push(cj, false, true); cx.push(mont_one<Fr>(), false, true); cx.push(idx, false);
+    g.g_is_zero_inv(d, g.signed_small_inv(d, diff));
+  }
+}
+// out_j = select(new cluster root, cluster_root_j, indicator_j), a lane per j; out_j is word 1 + j of the new sponge (word 0: the
+// centroids' root, lane 0's)
+__global__ __launch_bounds__(64) void k_annu_new_roots(Streams st, const FpTables* __restrict__ T, uint64_t base, uint32_t K,
+                                                       const u256* __restrict__ new_root, const u256* __restrict__ words_old,
+                                                       const u256* __restrict__ ind, u256* __restrict__ words_new) {
+  const uint32_t j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= K) return;
+  if (j == 0) words_new[0] = words_old[0];
+  WCtx cx = make_ctx(st, T, base + 8ull * j, 0);
+  Gadgets g(cx);
+  words_new[1 + j] = g.g_select(*new_root, words_old[1 + j], ind[j]);
+}
+// [index_root_old | c | idx_j, old_leaf_j, new_leaf_j per write | index_root_new] from the update block's own public values
+__global__ __launch_bounds__(256) void k_annu_public(const u256* __restrict__ upub, const u256* __restrict__ hdr, const u256* __restrict__ iroot,
+                                                     uint32_t m, u256* __restrict__ pub) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 3 * m + 3) return;
+  pub[i] = i == 0 ? iroot[0] : i == 1 ? hdr[0] : i == 3 * m + 2 ? iroot[1] : upub[i - 1];
+}
+static int annu_layout(size_t K, size_t cluster, size_t n_c, size_t dim, size_t m, unsigned grow, AnnuLayout* o, MkuLayout* ml) {
+  VDB_ARG(K > 0 && K <= VDB_ANN_MAX_CLUSTERS, "K = 0 or K above VDB_ANN_MAX_CLUSTERS");
+  VDB_ARG(cluster < K, "cluster >= K");
+  VDB_ARG(n_c <= VDB_ANN_MAX_VECTORS, "cluster larger than VDB_ANN_MAX_VECTORS");
+  TRY(mku_layout(n_c, dim, m, nullptr, grow, ml, nullptr, nullptr, nullptr));
+  mk_layout(1, K + 1, 1, &o->mw);
+  o->b = annu_blocks(K, o->mw.total, ml->total);
+  VDB_ARG(o->b.total <= ((uint64_t)1 << 34), "more than VDB_MERKLE_UPDATE_MAX_CELLS cells in one call");
+  return VDB_OK;
+}
+// roots: [centroids_root | the K cluster roots] of the index before the batch; levels: cluster c's tree at depth d + grow, left in the
+// state after the batch; pub: 3 m + 3
+int wit_ann_update_dev(u256* levels, const u256* roots, size_t K, size_t cluster, size_t n_c, size_t dim, unsigned grow, const u256* new_vectors,
+                       const uint64_t* indices, size_t m, Streams st, u256* pub) {
+  static thread_local MkuPlan pl;
+  AnnuLayout a;
+  MkuLayout ml0;
+  TRY(annu_layout(K, cluster, n_c, dim, m, grow, &a, &ml0));
+  TRY(mku_plan(n_c, dim, grow, new_vectors, indices, nullptr, m, &pl));
+  VDB_ARG(annu_track_fill(indices, m, n_c, pl.lp, nullptr, nullptr) == 0, "a write above the cluster's fill at its turn: the members of a cluster stay dense (append at the fill, or replace below it)");
+  const size_t n_st = (size_t)a.mw.nperm * PSD_T;
+  u256* w = (u256*)scratch_get(7, (2 * (K + 2) + K + 1 + 2 + 3 * m + 2 + 2 * n_st + 8) * sizeof(u256));
+  if (!w) return VDB_ERR_OOM;
+  AnnuWork k;
+  k.hdr = w;
+  k.ind = k.hdr + K + 2;
+  k.picked = k.ind + K;
+  k.words_new = k.picked + 1;
+  k.iroot = k.words_new + K + 1;
+  k.upub = k.iroot + 2;
+  k.st_old = k.upub + 3 * m + 2;
+  k.st_new = k.st_old + n_st;
+  TRY(inv_list_attach(st, a.b.total));
+  FpEntry* fp;
+  const PoseidonSpec* sp;
+  TRY(mk_begin(st, &fp, &sp));
+  const uint32_t Ku = (uint32_t)K, cu = (uint32_t)cluster, nperm = a.mw.nperm;
+  const u256* words_old = k.hdr + 1;
+  VDB_LAUNCH(k_annu_header, dim3((unsigned)((K + 2 + 255) / 256)), dim3(256), st, 0, cu, roots, Ku, k.hdr);
+  VDB_LAUNCH(k_annu_indicator, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, a.b.b_ind, cu, Ku, k.ind);
+  const NvMap sm{a.b.b_sel, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, Ku, 1u, 1u};
+  VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), st, fp->dev, sm, 1u, words_old + 1, k.ind, k.picked);
+  VDB_LAUNCH(k_mk_leaf_states, dim3(1), dim3(64), sp, words_old, 1u, Ku + 1, nperm, k.st_old, k.iroot, nullptr);
+  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((nperm + 63) / 64)), dim3(64), st, fp->dev, sp, words_old, 1u, Ku + 1, nperm, a.b.b_old, a.mw.leaf_cells,
+             k.st_old, nullptr);
+  TRY(mku_emit(fp, sp, pl, levels, dim, new_vectors, st, a.b.b_upd, k.upub));
+  VDB_LAUNCH(k_annu_new_roots, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, a.b.b_new, Ku, k.upub + 3 * m + 1, words_old, k.ind, k.words_new);
+  VDB_LAUNCH(k_mk_leaf_states, dim3(1), dim3(64), sp, k.words_new, 1u, Ku + 1, nperm, k.st_new, k.iroot + 1, nullptr);
+  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((nperm + 63) / 64)), dim3(64), st, fp->dev, sp, k.words_new, 1u, Ku + 1, nperm, a.b.b_root, a.mw.leaf_cells,
+             k.st_new, nullptr);
+  VDB_LAUNCH(k_annu_public, dim3((unsigned)((3 * m + 3 + 255) / 256)), dim3(256), k.upub, k.hdr, k.iroot, (uint32_t)m, pub);
+  return inv_list_fixup(st);
+}
+
+// The next index from the old one, the updated tree of cluster c and the batch (values only; the old buffers are only read).
+// One lane per word of the new grouped rows, then per new slot entry: rows up to the end of cluster c's old rows stay where they are,
+// the appended rows follow them, later rows move by the number of appends; inside cluster c the last write of the batch to a slot wins
+__global__ __launch_bounds__(256) void k_ann_rows_apply(const u256* __restrict__ grouped, const uint32_t* __restrict__ slots,
+                                                        const u256* __restrict__ new_vectors, const uint32_t* __restrict__ idx, uint32_t m,
+                                                        const uint32_t* __restrict__ db_slots, uint64_t off_c, uint64_t end_c, uint64_t appends,
+                                                        uint64_t n_new, uint32_t D, u256* __restrict__ grouped_out, uint32_t* __restrict__ slots_out) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x, n_words = n_new * D;
+  if (t >= n_words + n_new) return;
+  const bool is_slot = t >= n_words;
+  const uint64_t r = is_slot ? t - n_words : t / D;
+  if (is_slot) {
+    slots_out[r] = r < end_c ? slots[r] : r < end_c + appends ? db_slots[r - end_c] : slots[r - appends];
+    return;
+  }
+  const uint32_t wd = (uint32_t)(t % D);
+  if (r < off_c || r >= end_c + appends) {
+    grouped_out[t] = grouped[(r < off_c ? r : r - appends) * D + wd];
+    return;
+  }
+  const uint32_t s = (uint32_t)(r - off_c);
+  int32_t from = -1;
+  for (int32_t j = (int32_t)m - 1; j >= 0; j--)
+    if (idx[j] == s) {
+      from = j;
+      break;
+    }
+  // (an appended slot always has a write: the host's fill tracking)
+  grouped_out[t] = from >= 0 ? new_vectors[(uint64_t)from * D + wd] : grouped[r * D + wd];
+}
+// one lane per digest of the new forest: its segment by bisection in the new segment offsets; segment c comes from the updated tree,
+// every other one from where the old forest holds it (the segments behind c lie `delta` digests earlier there)
+__global__ __launch_bounds__(256) void k_ann_forest_move(const u256* __restrict__ forest, const u256* __restrict__ updated,
+                                                         const uint64_t* __restrict__ seg_off, uint32_t n_seg, uint32_t c, uint64_t delta,
+                                                         u256* __restrict__ forest_out) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= seg_off[n_seg]) return;
+  uint32_t lo = 0, hi = n_seg;   // the segment s with seg_off[s] <= t < seg_off[s + 1] (no segment is empty)
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (seg_off[mid] <= t) lo = mid; else hi = mid;
+  }
+  forest_out[t] = lo == c ? updated[t - seg_off[lo]] : forest[lo < c ? t : t - delta];
+}
+// the K + 1 words of the index root: the old ones, word 1 + c the updated tree's root
+__global__ __launch_bounds__(64) void k_ann_roots_apply(const u256* __restrict__ roots, const u256* __restrict__ updated, uint64_t glp, uint32_t K,
+                                                        uint32_t c, u256* __restrict__ roots_out) {
+  const uint32_t s = blockIdx.x * 64 + threadIdx.x;
+  if (s > K) return;
+  roots_out[s] = s == 1 + c ? updated[2 * glp - 2] : roots[s];
+}
+// what the two apply entry points share: the batch against cluster c's fill and the offsets after it (VDB_ERR_ARG, nothing launched)
+static int ann_apply_plan(const uint64_t* sizes, size_t K, size_t dim, size_t cluster, unsigned grow, const uint64_t* indices, size_t m,
+                          AnnuApplyPlan* p) {
+  VDB_ARG(sizes && indices, "null pointer");
+  VDB_ARG(K > 0 && K <= VDB_ANN_MAX_CLUSTERS && cluster < K, "K = 0, K above VDB_ANN_MAX_CLUSTERS or cluster >= K");
+  VDB_ARG(dim > 0 && dim <= ((size_t)1 << 20), "dim outside [1, 2^20]");
+  VDB_ARG(m > 0 && m <= MKU_MAX_UPDATES, "a batch holds 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES updates");
+  VDB_ARG(grow <= 30 && sizes[cluster] > 0 && sizes[cluster] <= VDB_ANN_MAX_VECTORS, "empty cluster, cluster too large or more than 30 doublings");
+  uint64_t lp, appends = 0;
+  uint32_t d;
+  tree_shape(sizes[cluster], &lp, &d);
+  VDB_ARG(annu_track_fill(indices, m, sizes[cluster], lp << grow, &appends, nullptr) == 0,
+          "a write above the cluster's fill at its turn or outside the grown tree");
+  const int rc = annu_apply_plan(sizes, K, cluster, grow, appends, p);
+  VDB_ARG(rc != 1, "empty cluster");
+  VDB_ARG(rc == 0, "the grown tree is not the tree over the cluster's new size: grow is the smallest number of doublings that fits the appends");
+  VDB_ARG(p->n_new <= VDB_ANN_MAX_VECTORS, "index too large: n at most VDB_ANN_MAX_VECTORS");
+  return VDB_OK;
+}
+int ann_index_apply_dev(const u256* grouped, const uint32_t* slots, const u256* forest, const u256* roots, const uint64_t* sizes, size_t K, size_t dim,
+                        size_t cluster, unsigned grow, const u256* updated, const u256* new_vectors, const uint64_t* indices, const uint32_t* db_slots,
+                        size_t m, u256* grouped_out, uint32_t* slots_out, uint64_t* offsets_out, u256* forest_out, u256* roots_out) {
+  static thread_local AnnuApplyPlan p;            // (pageable sources of asynchronous uploads: they outlive the call)
+  static thread_local std::vector<uint32_t> tab;  // [idx m | db_slots appends]
+  TRY(ann_apply_plan(sizes, K, dim, cluster, grow, indices, m, &p));
+  VDB_ARG(db_slots || p.appends == 0, "null pointer: an append needs its database slot");
+  const PoseidonSpec* sp;
+  TRY(poseidon_spec_dev(&sp, nullptr));
+  hipStream_t s = ctx().stream;
+  MkLayout mw;
+  mk_layout(1, K + 1, 0, &mw);
+  tab.resize(m + p.appends + 1);
+  for (size_t j = 0; j < m; j++) tab[j] = (uint32_t)indices[j];
+  for (size_t i = 0; i < p.appends; i++) tab[m + i] = db_slots[i];
+  uint8_t* w = (uint8_t*)scratch_get(7, (K + 2) * 8 + (m + p.appends + 16) * 4);
+  if (!w) return VDB_ERR_OOM;
+  uint64_t* d_off = (uint64_t*)w;
+  uint32_t* d_idx = (uint32_t*)(d_off + K + 2);
+  u256* states = (u256*)scratch_get(0, ((size_t)mw.nperm * PSD_T + 8) * sizeof(u256));
+  if (!states) return VDB_ERR_OOM;
+  VDB_HIP(hipMemcpyAsync(d_off, p.seg_off.data(), (K + 2) * 8, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(d_idx, tab.data(), (m + p.appends) * 4, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(offsets_out, p.offsets.data(), (K + 1) * 8, hipMemcpyHostToDevice, s));
+  const uint64_t lanes = p.n_new * dim + p.n_new;
+  VDB_LAUNCH(k_ann_rows_apply, dim3((unsigned)((lanes + 255) / 256)), dim3(256), grouped, slots, new_vectors, d_idx, (uint32_t)m, d_idx + m, p.off_c,
+             p.end_c, p.appends, p.n_new, (uint32_t)dim, grouped_out, slots_out);
+  VDB_LAUNCH(k_ann_forest_move, dim3((unsigned)((p.seg_off[K + 1] + 255) / 256)), dim3(256), forest, updated, d_off, (uint32_t)(K + 1), (uint32_t)cluster,
+             p.delta, forest_out);
+  VDB_LAUNCH(k_ann_roots_apply, dim3((unsigned)(K / 64 + 1)), dim3(64), roots, updated, p.glp_c, (uint32_t)K, (uint32_t)cluster, roots_out);
+  VDB_LAUNCH(k_mk_leaf_states, dim3(1), dim3(64), sp, roots_out, 1u, (uint32_t)(K + 1), mw.nperm, states, roots_out + K + 1, nullptr);
+  VDB_HIP(hipStreamSynchronize(s));
+  return VDB_OK;
 }
 
 }  // namespace vdb
@@ -2731,6 +2972,73 @@ int vdb_wit_ann_query(int metric, uint32_t P, uint32_t L, const vdb_fr* query, c
   TRY(download(member_indicator_out, dim_.p, n_c * sizeof(u256)));
   TRY(download(public_out, dpub.p, (dim + 1) * sizeof(u256)));
   return hs.finish(stream_out, lookup_out, selector_out, a.total, a.total_l);
+}
+
+// inserts and replacements against the index root, and the index after them (include/vdb.h)
+int vdb_wit_ann_update_size(size_t K, size_t n_c, size_t dim, size_t m, unsigned grow, uint64_t* cells, uint64_t* input_cells, uint64_t* update_base) {
+  AnnuLayout a;
+  MkuLayout ml;
+  TRY(annu_layout(K, 0, n_c, dim, m, grow, &a, &ml));
+  if (cells) *cells = a.b.total;
+  if (input_cells) *input_cells = a.b.n_in;
+  if (update_base) *update_base = a.b.b_upd;
+  return VDB_OK;
+}
+int vdb_wit_ann_update_dev(vdb_fr* levels_dev, const vdb_fr* roots_dev, size_t K, size_t cluster, size_t n_c, size_t dim, unsigned grow,
+                           const vdb_fr* new_vectors_dev, const uint64_t* indices, size_t m, vdb_fr* stream_dev, uint8_t* selector_dev,
+                           vdb_fr* public_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(levels_dev && roots_dev && new_vectors_dev && indices && stream_dev && public_dev, "null pointer");
+  DevStreams ds;
+  ds.init(stream_dev, selector_dev);
+  TRY(wit_ann_update_dev(as_u256(levels_dev), as_u256(roots_dev), K, cluster, n_c, dim, grow, as_u256(new_vectors_dev), indices, m, ds.st,
+                         as_u256(public_dev)));
+  return ds.finish();
+}
+int vdb_wit_ann_update(vdb_fr* levels, const vdb_fr* roots, size_t K, size_t cluster, size_t n_c, size_t dim, unsigned grow, const vdb_fr* new_vectors,
+                       const uint64_t* indices, size_t m, vdb_fr* stream_out, uint8_t* selector_out, vdb_fr* public_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(levels && roots && new_vectors && indices, "null pointer");
+  AnnuLayout a;
+  MkuLayout ml;
+  TRY(annu_layout(K, cluster, n_c, dim, m, grow, &a, &ml));
+  uint64_t lp;
+  uint32_t d;
+  tree_shape(n_c, &lp, &d);
+  lp <<= grow;
+  VDB_ARG(annu_track_fill(indices, m, n_c, lp, nullptr, nullptr) == 0, "a write above the cluster's fill at its turn or outside the grown tree");
+  DevBuf dl, dr, dv, dpub;
+  HostStreams hs;
+  TRY(upload(dl, levels, 2 * lp * sizeof(u256)));
+  TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
+  TRY(upload(dv, new_vectors, ml.n_vec * sizeof(u256)));
+  TRY(dpub.alloc((3 * m + 3) * sizeof(u256)));
+  TRY(hs.init(a.b.total, 0, selector_out != nullptr));
+  TRY(wit_ann_update_dev(dl.as<u256>(), dr.as<u256>(), K, cluster, n_c, dim, grow, dv.as<u256>(), indices, m, hs.st, dpub.as<u256>()));
+  TRY(download(public_out, dpub.p, (3 * m + 3) * sizeof(u256)));
+  TRY(download(levels, dl.p, 2 * lp * sizeof(u256)));
+  return hs.finish(stream_out, nullptr, selector_out, a.b.total, 0);
+}
+int vdb_ann_index_apply_size(const uint64_t* cluster_sizes, size_t K, size_t cluster, unsigned grow, const uint64_t* indices, size_t m, uint64_t* appends,
+                             uint64_t* digests, uint64_t* segment_offsets) {
+  AnnuApplyPlan p;
+  TRY(ann_apply_plan(cluster_sizes, K, 1, cluster, grow, indices, m, &p));
+  if (appends) *appends = p.appends;
+  if (digests) *digests = p.seg_off[K + 1];
+  if (segment_offsets) memcpy(segment_offsets, p.seg_off.data(), (K + 2) * sizeof(uint64_t));
+  return VDB_OK;
+}
+int vdb_ann_index_apply_dev(const vdb_fr* grouped_dev, const uint32_t* slots_dev, const vdb_fr* forest_dev, const vdb_fr* roots_dev,
+                            const uint64_t* cluster_sizes, size_t K, size_t dim, size_t cluster, unsigned grow, const vdb_fr* updated_levels_dev,
+                            const vdb_fr* new_vectors_dev, const uint64_t* indices, const uint32_t* db_slots, size_t m, vdb_fr* grouped_out_dev,
+                            uint32_t* slots_out_dev, uint64_t* offsets_out_dev, vdb_fr* forest_out_dev, vdb_fr* roots_out_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(grouped_dev && slots_dev && forest_dev && roots_dev && updated_levels_dev && new_vectors_dev && grouped_out_dev && slots_out_dev &&
+              offsets_out_dev && forest_out_dev && roots_out_dev,
+          "null pointer");
+  return ann_index_apply_dev(as_u256(grouped_dev), slots_dev, as_u256(forest_dev), as_u256(roots_dev), cluster_sizes, K, dim, cluster, grow,
+                             as_u256(updated_levels_dev), as_u256(new_vectors_dev), indices, db_slots, m, as_u256(grouped_out_dev), slots_out_dev,
+                             offsets_out_dev, as_u256(forest_out_dev), as_u256(roots_out_dev));
 }
 
 // ---- b4 layout ---------------------------------------------------------------------------------

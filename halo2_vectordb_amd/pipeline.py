@@ -1219,6 +1219,56 @@ class AnnIndex:
         check(self.lib.vdb_ann_index_build_dev(self.d_vec.ptr, api._p(self.cluster_ids), self.d_cent.ptr, n, K, dim, self.d_grouped.ptr, self.d_slots.ptr,
                                                self.d_offsets.ptr, self.d_forest.ptr, self.d_roots.ptr))
 
+    @classmethod
+    def from_resident(cls, dim, K, sizes, n_digests, segments, qcent, qvec, cluster_ids, P=48, L=13, metric="euclidean"):
+        """an index over buffers that are filled on the device (vdb_ann_index_apply_dev) instead of built here: the host-side shape
+        (`sizes` of the K clusters, the forest's `n_digests` and `segments`), the quantized centroids and database, and fresh device
+        buffers of that shape, which the caller fills; d_vec is not kept resident"""
+        ix = cls.__new__(cls)
+        ix.lib = api.init()
+        ix.sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+        ix.n, ix.dim, ix.K, ix.P, ix.L, ix.metric_name = int(ix.sizes.sum()), dim, K, P, L, metric
+        ix.cluster_ids, ix.qcent, ix.qvec = np.ascontiguousarray(cluster_ids, dtype=np.uint32), qcent, qvec
+        ix.n_digests, ix.segments = int(n_digests), np.ascontiguousarray(segments, dtype=np.uint64)
+        ix.offsets = np.concatenate([[0], np.cumsum(ix.sizes)]).astype(np.int64)
+        ix._bufs = []
+        ix.d_vec, ix.d_cent = None, ix._buf(qcent.nbytes)
+        ix.d_grouped, ix.d_slots, ix.d_offsets = ix._buf(ix.n * dim * B), ix._buf(ix.n * 4), ix._buf((K + 1) * 8)
+        ix.d_forest, ix.d_roots = ix._buf(ix.n_digests * B), ix._buf((K + 2) * B)
+        ix.d_cent.upload(qcent)
+        return ix
+
+    def updated(self, hp, db_slots=None):
+        """the index after the batch of AnnUpdateHotPath `hp` (its witness has run: hp.d_levels holds the cluster's tree after the
+        batch), as a new AnnIndex on buffers of its own (vdb_ann_index_apply_dev); this index stays valid.  `db_slots`: the database slot
+        of every append, in append order (None: n, n + 1, ..., which keeps the members in database order).  Queries, reads and further
+        updates run on the result unchanged."""
+        c, m, app = hp.cluster, hp.m, hp.appends
+        db_slots = np.arange(self.n, self.n + app, dtype=np.uint32) if db_slots is None else np.ascontiguousarray(db_slots, dtype=np.uint32)
+        if db_slots.shape != (app,):
+            raise ValueError("one database slot per append")
+        sizes64 = np.ascontiguousarray(self.sizes, dtype=np.uint64)
+        _, digests, seg = api.ann_index_apply_layout(sizes64, c, hp.grow, hp.indices)
+        # the host's view of the database: replaced rows where the cluster's slots say, appended rows at db_slots
+        old_slots = self.d_slots.download((int(self.sizes[c]),), dtype=np.uint32, offset=int(self.offsets[c]) * 4)
+        place = np.concatenate([old_slots, db_slots]).astype(np.int64)
+        n2 = max(self.n, int(place.max()) + 1)
+        qvec, ids = np.zeros((n2, self.dim, 4), dtype=np.uint64), np.zeros(n2, dtype=np.uint32)
+        qvec[:self.n], ids[:self.n] = self.qvec, self.cluster_ids
+        for j in range(m):
+            qvec[place[int(hp.indices[j])]], ids[place[int(hp.indices[j])]] = hp.qvec[j], c
+        sizes = self.sizes.copy()
+        sizes[c] += app
+        ix = AnnIndex.from_resident(self.dim, self.K, sizes, digests, seg, self.qcent, qvec, ids, P=self.P, L=self.L, metric=self.metric_name)
+        try:
+            check(self.lib.vdb_ann_index_apply_dev(self.d_grouped.ptr, self.d_slots.ptr, self.d_forest.ptr, self.d_roots.ptr, api._p(sizes64), self.K, self.dim,
+                                                   c, hp.grow, hp.d_levels.ptr, hp.d_vec.ptr, api._p(hp.indices), api._p(db_slots) if app else None, m,
+                                                   ix.d_grouped.ptr, ix.d_slots.ptr, ix.d_offsets.ptr, ix.d_forest.ptr, ix.d_roots.ptr))
+        except Exception:
+            ix.free()
+            raise
+        return ix
+
     def _buf(self, nbytes):
         b = api.DeviceBuffer(max(int(nbytes), 32))
         self._bufs.append(b)
@@ -1330,3 +1380,92 @@ class AnnQueryHotPath(HotPath):
                                            self._fetch, builder=DeviceBuilder if on_device else None)
         assert cm.n_cells == self.n_cells
         return cm, public, None
+
+
+class AnnUpdateHotPath(PoseidonHotPath):
+    """Inserts and replacements proved against the committed index root: m writes into ONE cluster c of an AnnIndex in one proof (include/vdb.h
+    vdb_wit_ann_update).  Assigned: [c | centroids' root | cluster roots]; then idx_to_indicator(c, K), select_by_indicator(cluster roots,
+    indicators) tied to the old root of the update block, the sponge over the roots (index_root_old), UpdateHotPath's whole circuit on the
+    cluster's tree, out_j = select(new cluster root, cluster_root_j, indicator_j) and the sponge over [centroids' root | out_j]
+    (index_root_new).  Public: [index_root_old | c | idx, old leaf, new leaf per write | index_root_new].  Writes only, and the members stay
+    dense: slot s of the cluster is below its fill (a replacement) or equal to it (an append).  Cluster assignment is NOT proved: the caller
+    chooses c (index.probe(v) is its tool).  K, m, grow and the depth are circuit shape, c is not.  `d_levels` holds the cluster's tree
+    after the batch; AnnIndex.updated(hp) gives the next index."""
+
+    def __init__(self, index, cluster, updates, grow=0, k=15, L=8, tau=None, col_shard=(0, 1), blind_seed=None, params=None, levels=None):
+        """`updates`: (slots in the cluster (m,), (m, dim) f64 rows), applied in order.  `grow`: doublings of the cluster's tree before the
+        first write; None: the smallest number that fits the appends.  `levels`: a tree to use in place of the index's segment c (a test of
+        the binding: another cluster's tree breaks the picked copy)."""
+        idx, rows = updates
+        self.indices = np.ascontiguousarray(idx, dtype=np.uint64)
+        m = self.indices.shape[0]
+        if m < 1:
+            raise ValueError("a batch holds at least one write")
+        self.index, self.K, self.cluster = index, index.K, int(cluster)
+        if not 0 <= self.cluster < self.K:
+            raise ValueError("cluster outside the index")
+        n_c = int(index.sizes[self.cluster])
+        fill = n_c
+        for s in self.indices.tolist():
+            if s > fill:
+                raise ValueError("a write above the cluster's fill: the members of a cluster stay dense")
+            fill += s == fill
+        self.appends = fill - n_c
+        self.lp0, depth0 = api.merkle_levels(n_c)
+        if grow is None:
+            grow = 0
+            while (self.lp0 << grow) < fill:
+                grow += 1
+        self.grow = int(grow)
+        self.lp, self.depth = self.lp0 << self.grow, depth0 + self.grow
+        if self.depth < 1:
+            raise ValueError("a tree of one leaf has no path: grow it")
+        super().__init__(n_c, index.dim, k, index.P, L, seed=None, tau=tau, col_shard=col_shard,
+                         vectors=np.ascontiguousarray(rows, dtype=np.float64).reshape(m, index.dim), blind_seed=blind_seed, params=params)
+        self.m, self.given_levels = m, levels
+
+    def n_input_rows(self):
+        return self.m
+
+    def _load_inputs(self):
+        super()._load_inputs()
+        self.d_levels0 = self._output(2 * self.lp * B)
+        self.d_levels = self._output(2 * self.lp * B)
+        d_small = self.d_levels if self.grow else self.d_levels0
+        self._load_tree(d_small, self.lp0, self.index.levels(self.cluster) if self.given_levels is None else self.given_levels)
+        if self.grow:
+            check(self.lib.vdb_merkle_tree_grow_dev(d_small.ptr, self.n, self.grow, self.d_levels0.ptr))
+            api.sync()
+
+    def _circuit_size(self):
+        cells, n_in, ub = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(self.lib.vdb_wit_ann_update_size(self.K, self.n, self.dim, self.m, self.grow, ctypes.byref(cells), ctypes.byref(n_in), ctypes.byref(ub)))
+        self.update_base = ub.value
+        return n_in.value, cells.value - n_in.value, 0
+
+    def _alloc_outputs(self):
+        self.d_pub = self._output((3 * self.m + 3) * B)
+
+    def _witness(self, sel=None):
+        # the call writes the assigned header too; every run starts from the cluster's tree before the batch
+        check(self.lib.vdb_memcpy_d2d(self.d_levels.ptr, self.d_levels0.ptr, ctypes.c_size_t(2 * self.lp * B)))
+        with self._window(sel, 0, lookup=False):
+            check(self.lib.vdb_wit_ann_update_dev(self.d_levels.ptr, self.index.d_roots.ptr, self.K, self.cluster, self.n, self.dim, self.grow,
+                                                  self.d_vec.ptr, api._p(self.indices), self.m, self.d_stream.ptr, self._sel_at(sel, 0), self.d_pub.ptr))
+
+    def public_values_dev(self):
+        return self.d_pub.ptr, 3 * self.m + 3
+
+    def results(self):
+        """(index_root_old (4,), c (4,), indices (m, 4), old leaves (m, 4), new leaves (m, 4), index_root_new (4,))"""
+        pub = self.d_pub.download((3 * self.m + 3, 4))
+        per = pub[2:-1].reshape(self.m, 3, 4)
+        return pub[0], pub[1], per[:, 0], per[:, 1], per[:, 2], pub[-1]
+
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        cm, pub, _ = CS.build_ann_update(self.K, self.m, self.dim, self.depth, functools.partial(self._fetch_flags, d_flags), self._fetch,
+                                         builder=DeviceBuilder if on_device else None, grow=self.grow)
+        assert cm.n_cells == self.n_cells
+        return cm, pub, None

@@ -375,6 +375,60 @@ int vdb_wit_ann_query_dev(int metric, uint32_t precision_bits, uint32_t lookup_b
                           size_t K, size_t n_c, size_t dim, vdb_fr *stream_dev, vdb_fr *lookup_dev, uint8_t *selector_dev,
                           vdb_fr *centroid_indicator_dev, vdb_fr *member_indicator_dev, vdb_fr *public_dev);
 
+/* Inserts and replacements proved against the committed index root: m writes into ONE cluster c of an index of K clusters move
+ * index_root_old to index_root_new in one circuit.  The reference has no such gadget; the cells are those of the closure a user of its
+ * chips writes.  n_c = |members(c)| before the batch, lp the power of two >= n_c, depth = log2(lp) + grow >= 1; the cluster's tree may
+ * be doubled `grow` times before the first write, as in vdb_wit_merkle_update_ops.  Stream, from cell 0:
+ *   A  [c | centroids_root | cluster_root_0 .. cluster_root_{K-1}] assigned                      (K + 2 cells: input_cells)
+ *   B  ind = gate.idx_to_indicator(c, K): ind_0 = is_zero(c) (8 cells), ind_j = is_equal(c, Constant(j)) (12 cells), j >= 1
+ *   C  picked = gate.select_by_indicator(cluster roots, ind)                                     (1 + 3 K cells)
+ *   D  index_root_old = poseidon.clear(); update([centroids_root, cluster roots ..]); squeeze()  (the sponge of vdb_wit_ann_query)
+ *   E  the whole stream of vdb_wit_merkle_update_ops(levels, n_c, dim, grow, new_vectors, indices, kinds = NULL), its assigned
+ *      witnesses included, from cell update_base on
+ *   F  out_j = gate.select(new cluster root, cluster_root_j, ind_j), j = 0 .. K - 1              (8 K cells)
+ *   G  index_root_new = the sponge over [centroids_root, out_0 .. out_{K-1}]
+ * Copies (no cell): every idx operand of B is c; C's operands are the header's roots and B's outputs; D's words are the header's; picked
+ * is tied to the old root block E exposes (R_0 when grow >= 1, else cur_old at the top of update 0); F's a is E's final root, its b and
+ * sel the header's roots and B's outputs; G's words are centroids_root and F's outputs.
+ * public, 3 m + 3 values: [index_root_old | c | idx_j, old_leaf_j, new_leaf_j per write | index_root_new].  E's own old and new roots
+ * stay private.  K, m, grow and the depth are circuit shape; c is not: one proving key serves every cluster of the same depth.
+ * Writes only, and the members stay dense: the query circuit hashes merkle_commitment(members(c)) over n_c dense rows, so a hole would
+ * make the cluster unqueryable.  Write j is accepted when indices[j] is below the fill at its turn (a replacement) or equal to it (an
+ * append: the fill rises by one); the fill starts at n_c; writes of a batch see each other.  There is no delete.
+ * Cluster assignment is NOT proved: nothing in the circuit shows that c is the cluster whose centroid is nearest to a new vector (the
+ * index build does not prove its cluster ids either).  The caller chooses c; nearest_vector over the centroids is its tool.
+ * roots: the K + 1 digests [centroids_root | cluster roots] (the head of vdb_ann_index_build_dev's roots_dev).  levels: cluster c's tree
+ * at depth d + grow (forest segment c, copied, and grown by vdb_merkle_tree_grow_dev when grow >= 1), left in the state after the batch.
+ * indices is a HOST array.  If levels is not the tree whose root is cluster_root_c the call still writes a stream; it breaks the picked
+ * copy.  The number of launches depends on the depth and on grow > 0, never on K, m, c or n_c.  The _dev form honours
+ * vdb_wit_set_window.  VDB_ERR_ARG before anything is launched: K == 0, K > VDB_ANN_MAX_CLUSTERS, c >= K, an index above the fill at
+ * its turn or >= lp << grow, and every limit of vdb_wit_merkle_update_ops (m, depth, cells).
+ *
+ * vdb_ann_index_apply_dev (values only, functional): the index after the batch into caller-provided buffers, from the old index's
+ * buffers (only read: the old index stays valid), updated_levels_dev (the 2 (lp_c << grow) digests the witness call left), the batch
+ * and db_slots (HOST, one database slot per append, in append order: n, n + 1, ... keeps "members in database order").  cluster_sizes:
+ * HOST, the K sizes before the batch.  Rows of clusters <= c stay, the appended rows follow cluster c's, later rows move by the number
+ * of appends; the last write of the batch to a slot wins; the forest is moved segment by segment (segment c from the updated tree); the
+ * K + 1 roots are copied, root c replaced, and the index root hashed again: four launches whatever the shape.  The result equals,
+ * entry for entry, vdb_ann_index_build_dev over the updated database and ids — so `grow` must be the smallest number of doublings
+ * that fits the appends (lp_c << grow == the power of two >= n_c + appends), VDB_ERR_ARG otherwise, as for the refusals above.
+ * vdb_ann_index_apply_size: the number of appends, the digests of the new forest and its K + 2 segment offsets (each may be NULL).
+ * Output sizes: grouped (n + appends) x dim, slots n + appends, offsets K + 1, forest `digests`, roots K + 2. */
+int vdb_wit_ann_update_size(size_t K, size_t n_c, size_t dim, size_t m, unsigned grow, uint64_t *cells, uint64_t *input_cells,
+                            uint64_t *update_base);
+int vdb_wit_ann_update(vdb_fr *levels, const vdb_fr *roots, size_t K, size_t cluster, size_t n_c, size_t dim, unsigned grow,
+                       const vdb_fr *new_vectors, const uint64_t *indices, size_t m, vdb_fr *stream_out, uint8_t *selector_out, vdb_fr *public_out);
+int vdb_wit_ann_update_dev(vdb_fr *levels_dev, const vdb_fr *roots_dev, size_t K, size_t cluster, size_t n_c, size_t dim, unsigned grow,
+                           const vdb_fr *new_vectors_dev, const uint64_t *indices /* host */, size_t m, vdb_fr *stream_dev, uint8_t *selector_dev,
+                           vdb_fr *public_dev);
+int vdb_ann_index_apply_size(const uint64_t *cluster_sizes /* host */, size_t K, size_t cluster, unsigned grow, const uint64_t *indices /* host */,
+                             size_t m, uint64_t *appends, uint64_t *digests, uint64_t *segment_offsets);
+int vdb_ann_index_apply_dev(const vdb_fr *grouped_dev, const uint32_t *slots_dev, const vdb_fr *forest_dev, const vdb_fr *roots_dev,
+                            const uint64_t *cluster_sizes /* host */, size_t K, size_t dim, size_t cluster, unsigned grow,
+                            const vdb_fr *updated_levels_dev, const vdb_fr *new_vectors_dev, const uint64_t *indices /* host */,
+                            const uint32_t *db_slots /* host */, size_t m, vdb_fr *grouped_out_dev, uint32_t *slots_out_dev,
+                            uint64_t *offsets_out_dev, vdb_fr *forest_out_dev, vdb_fr *roots_out_dev);
+
 /* ---- b4 stream -> columns: replaces halo2-base GateThreadBuilder::assign_all (break points, keygen)
  *      and assign_threads_in (prover) as driven by RangeCircuitBuilder::prover(builder, break_points)
  *      (src/scaffold/mod.rs:393-396).  Columns are 2^k rows; the cell on a break row is duplicated at

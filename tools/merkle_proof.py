@@ -19,7 +19,11 @@ the verifier check the proof.
 `--circuit ann --K C` proves one approximate-nearest-neighbour query against a committed index of the n x dim database
 (pipeline.AnnIndex, AnnQueryHotPath: the first C vectors are the centroids, every vector belongs to its nearest one; nearest_vector over
 the centroids and over the winning cluster, both commitments, the selected cluster root tied to the members' root, [result | index_root]
-public), and has the verifier check the proof.  The circuit's size follows the cluster searched, not n."""
+public), and has the verifier check the proof.  The circuit's size follows the cluster searched, not n.
+`--circuit ann-update --K C --updates M [--grow G]` proves M writes into one cluster of that index against its root
+(pipeline.AnnUpdateHotPath: the first write replaces member 0 of the largest cluster, the others append to it; [index_root_old | c | idx, old
+leaf, new leaf per write | index_root_new] public; `--grow` defaults to the smallest number of doublings that fits the appends), has the
+verifier check the proof and applies the batch to the resident index (AnnIndex.updated), whose root must be the public index_root_new."""
 import argparse
 import json
 import os
@@ -30,7 +34,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from halo2_vectordb_amd import api  # noqa: E402
-from halo2_vectordb_amd.pipeline import AnnIndex, AnnQueryHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
+from halo2_vectordb_amd.pipeline import AnnIndex, AnnQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
 from halo2_vectordb_amd.rounds import ProverRounds, quotient_identity_holds  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -41,14 +45,14 @@ ap.add_argument("--seed", type=int, default=20260003)
 ap.add_argument("--block-cols", type=int, default=510)
 ap.add_argument("--ext-block-cols", type=int, default=None)
 ap.add_argument("--proofs", type=int, default=2)
-ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read", "ann"])
+ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read", "ann", "ann-update"])
 ap.add_argument("--lookup-bits", type=int, default=13)
 ap.add_argument("--metric", default="euclidean")
 ap.add_argument("--queries", type=int, default=1, help="--circuit query: queries proved against the one database in this proof")
 ap.add_argument("--topk", type=int, default=1, help="--circuit query: nearest vectors proved per query, nearest first")
 ap.add_argument("--updates", type=int, default=8, help="--circuit update: inserts / replacements proved in this proof")
 ap.add_argument("--deletes", type=int, default=0, help="--circuit update: the last K updates empty their slot instead of writing it")
-ap.add_argument("--grow", type=int, default=0, help="--circuit update: doublings of the padded leaf count before the first update")
+ap.add_argument("--grow", type=int, default=None, help="--circuit update / ann-update: doublings of the padded leaf count before the first update")
 ap.add_argument("--reads", type=int, default=8, help="--circuit read: slots opened in this proof")
 ap.add_argument("--leaf-only", action="store_true", help="--circuit read: reveal the leaf digests, not the vectors")
 ap.add_argument("--K", type=int, default=32, help="--circuit ann: clusters of the index")
@@ -59,8 +63,9 @@ api.init(0)
 t0 = time.time()
 if args.queries < 1 or (args.queries > 1 and args.circuit != "query"):
     raise SystemExit("--queries needs --circuit query and at least one query")
-if (args.deletes or args.grow) and args.circuit != "update":
-    raise SystemExit("--deletes and --grow need --circuit update")
+if args.deletes and args.circuit != "update" or args.grow is not None and args.circuit not in ("update", "ann-update"):
+    raise SystemExit("--deletes needs --circuit update, --grow --circuit update or ann-update")
+ann_grow, args.grow = args.grow, args.grow or 0
 if args.topk < 1 or (args.topk > 1 and args.circuit != "query"):
     raise SystemExit("--topk needs --circuit query and at least one neighbour")
 if args.circuit == "query" and args.topk > 1:
@@ -72,7 +77,7 @@ elif args.circuit == "update":
         raise SystemExit("--deletes is between 0 and --updates, --grow is not negative")
     kinds = [0] * (args.updates - args.deletes) + [1] * args.deletes
     hp = UpdateHotPath(n=args.n, dim=args.dim, m=args.updates, k=args.k, seed=args.seed, kinds=kinds, grow=args.grow)
-elif args.circuit == "ann":
+elif args.circuit in ("ann", "ann-update"):
     from halo2_vectordb_amd.pipeline import sift_like_vectors
     if not 1 <= args.K <= args.n:
         raise SystemExit("--K is between 1 and --n")
@@ -81,7 +86,12 @@ elif args.circuit == "ann":
     ids = np.argmin(((db[:, None, :] - db[None, :args.K, :]) ** 2).sum(axis=2), axis=1)
     ids[:args.K] = np.arange(args.K)                           # (a duplicate of an earlier centroid still keeps its own cluster)
     index = AnnIndex(args.n, args.dim, args.K, db, ids, db[:args.K], L=args.lookup_bits, metric=args.metric)
-    hp = AnnQueryHotPath(index, query, k=args.k, L=args.lookup_bits, metric=args.metric)
+    if args.circuit == "ann":
+        hp = AnnQueryHotPath(index, query, k=args.k, L=args.lookup_bits, metric=args.metric)
+    else:
+        c = int(np.argmax(index.sizes))
+        slots = [0] + [int(index.sizes[c]) + i for i in range(args.updates - 1)]
+        hp = AnnUpdateHotPath(index, c, (slots, sift_like_vectors(seed + 2000, args.updates, args.dim)[0]), grow=ann_grow, k=args.k)
 elif args.circuit == "read":
     hp = ReadHotPath(n=args.n, dim=args.dim, m=args.reads, k=args.k, seed=args.seed, reveal="leaf" if args.leaf_only else "vector")
 elif args.circuit == "query":
@@ -116,13 +126,18 @@ if args.out:
     write_snark(args.out, out["proof"], out["instances"])
     pr.save_verifying_key(args.out + ".vk.npz", opened=out["opened"])
 accepted = {}
-if args.circuit in ("read", "ann"):
+if args.circuit in ("read", "ann", "ann-update"):
     from halo2_vectordb_amd import verifier
     accepted = {"proof_accepted": bool(verifier.verify(out["proof"], out["instances"], verifier.VerifyingKey.from_prover(pr, out["opened"])))}
+if args.circuit == "ann-update":
+    index2 = index.updated(hp)
+    accepted["applied_index_root_is_the_public_new_root"] = bool(np.array_equal(index2.roots()[-1], hp.results()[-1]))
+    index2.free()
 what = f"merkle_commitment {args.n}x{args.dim} k={args.k}" if args.circuit == "merkle" else \
     f"{args.updates} Merkle path updates ({args.deletes} deletes, tree grown {args.grow} times) against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "update" else \
     f"{args.reads} Merkle openings ({'leaves' if args.leaf_only else 'vectors'} public) against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "read" else \
     f"ann query (K={args.K}, cluster {hp.cluster} of {hp.n} vectors, {args.metric}) against the index of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann" else \
+    f"{args.updates} writes into cluster {hp.cluster} ({hp.n} members, tree grown {hp.grow} times) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-update" else \
     f"query circuit ({str(args.queries) + ' x ' if args.queries > 1 else ''}{'top-' + str(args.topk) + ' ' if args.topk > 1 else ''}nearest_vector {args.metric} + merkle_commitment) over {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}"
 print(json.dumps({"workload": what + ": whole constraint map, public outputs in the instance column, transcript, fresh blinds, SHPLONK", "lookup_cells": hp.n_lookup,
                   "cells": hp.n_cells, "columns": hp.n_cols, "product_sets": pr.n_sets, "mock_report_on_keygen_witness": pr.keygen_report.as_dict(),
@@ -133,5 +148,5 @@ print(json.dumps({"workload": what + ": whole constraint map, public outputs in 
                   "block_cols": args.block_cols, "ext_cols_held": hp.ext_cols}))
 pr.free()
 hp.free()
-if args.circuit == "ann":
+if args.circuit in ("ann", "ann-update"):
     index.free()
