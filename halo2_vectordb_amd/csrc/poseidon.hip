@@ -1,6 +1,7 @@
 // Poseidon: host-side parameter generation (Grain LFSR + optimized schedule) and the hash-only
-// device kernels behind vdb_poseidon_* (SURVEY §8 b6).  The trace-emitting variant used for witness
-// generation lives in witness.hip and shares poseidon.hpp.
+// device kernels behind vdb_poseidon_hash_many and vdb_poseidon_permute.  The Merkle tree over
+// the permutation (vdb_poseidon_merkle_root among its callers) is built in resident.hip, the trace-emitting
+// variant used for witness generation lives in witness.hip; all share poseidon.hpp.
 #include "poseidon.hpp"
 
 #include "common.hpp"
@@ -256,13 +257,6 @@ __global__ __launch_bounds__(256) void k_poseidon_hash_many(const PoseidonSpec* 
   if (t >= n_msgs) return;
   st256(out + t, psd_hash(sp, in + t * msg_len, msg_len, 1));
 }
-// one Merkle level: out[i] = H(in[2i], in[2i+1])
-__global__ __launch_bounds__(256) void k_poseidon_level(const PoseidonSpec* __restrict__ sp, const u256* __restrict__ in,
-                                                       size_t n_out, u256* __restrict__ out) {
-  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n_out) return;
-  st256(out + t, psd_hash(sp, in + 2 * t, 2, 1));
-}
 __global__ __launch_bounds__(256) void k_poseidon_permute(const PoseidonSpec* __restrict__ sp, u256* __restrict__ states, size_t n) {
   size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
@@ -299,27 +293,6 @@ int poseidon_empty_subtrees_dev(const u256** dev_out) {
   return VDB_OK;
 }
 
-// device-level merkle root over already-resident leaves buffer (size: next pow2), result in lv[0]
-int poseidon_merkle_dev(const u256* vectors_dev, size_t n, size_t dim, u256* lv /* leaves pow2 */, u256* tmp) {
-  Context& c = ctx();
-  const PoseidonSpec* sp;
-  int rc = poseidon_spec_dev(&sp, nullptr);
-  if (rc) return rc;
-  size_t leaves = 1;
-  while (leaves < n) leaves <<= 1;
-  VDB_HIP(hipMemsetAsync(lv, 0, leaves * sizeof(u256), c.stream));
-  VDB_LAUNCH(k_poseidon_hash_many, dim3((unsigned)((n + 255) / 256)), dim3(256), sp, vectors_dev, n, dim, lv);
-  u256 *a = lv, *b = tmp;
-  while (leaves > 1) {
-    size_t no = leaves / 2;
-    VDB_LAUNCH(k_poseidon_level, dim3((unsigned)((no + 255) / 256)), dim3(256), sp, a, no, b);
-    std::swap(a, b);
-    leaves = no;
-  }
-  if (a != lv) VDB_HIP(hipMemcpyAsync(lv, a, sizeof(u256), hipMemcpyDeviceToDevice, c.stream));
-  return VDB_OK;
-}
-
 }  // namespace vdb
 
 using namespace vdb;
@@ -341,24 +314,6 @@ int vdb_poseidon_hash_many(const vdb_fr* inputs, size_t n_msgs, size_t msg_len, 
   if (in_bytes) VDB_HIP(hipMemcpyAsync(din, inputs, in_bytes, hipMemcpyHostToDevice, c.stream));
   VDB_LAUNCH(k_poseidon_hash_many, dim3((unsigned)((n_msgs + 255) / 256)), dim3(256), sp, din, n_msgs, msg_len, dout);
   VDB_HIP(hipMemcpyAsync(digests, dout, n_msgs * sizeof(u256), hipMemcpyDeviceToHost, c.stream));
-  VDB_HIP(hipStreamSynchronize(c.stream));
-  return VDB_OK;
-}
-
-int vdb_poseidon_merkle_root(const vdb_fr* vectors, size_t n, size_t dim, vdb_fr* root) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(vectors && root && n > 0, "null pointer or empty database");
-  Context& c = ctx();
-  size_t leaves = 1;
-  while (leaves < n) leaves <<= 1;
-  u256* din = (u256*)scratch_get(0, n * dim * sizeof(u256) + 32);
-  u256* lv = (u256*)scratch_get(1, leaves * sizeof(u256));
-  u256* tmp = (u256*)scratch_get(2, leaves * sizeof(u256));
-  if (!din || !lv || !tmp) return VDB_ERR_OOM;
-  VDB_HIP(hipMemcpyAsync(din, vectors, n * dim * sizeof(u256), hipMemcpyHostToDevice, c.stream));
-  int rc = poseidon_merkle_dev(din, n, dim, lv, tmp);
-  if (rc) return rc;
-  VDB_HIP(hipMemcpyAsync(root, lv, sizeof(u256), hipMemcpyDeviceToHost, c.stream));
   VDB_HIP(hipStreamSynchronize(c.stream));
   return VDB_OK;
 }

@@ -1,10 +1,18 @@
-// Witness generation (b5), stream->column layout (b4) and fixed-point staging (a2/a3/a18) on gfx950.
+// Witness generation (b5) and fixed-point staging (a2/a3/a18) on gfx950: every kernel that emits cells of a witness stream, with
+// its layout and its driver.
+//   * fixed-point staging and the FixedPointChip tables (vdb_fp_*, get_fp, witness_release);
+//   * the call's context: Streams, set_winv (which publishes g_winv of gadgets.hpp before a call's launches) and make_ctx.  Every
+//     kernel of this file may read that context, and only kernels of this file can: the value-only code of the committed tree and
+//     index (resident.hip) and the layout stage (layout.hip) do not include gadgets.hpp;
+//   * the circuits: distances, FixedPointChip operations, nearest_vector / top-k, kmeans, merkle_commitment, Merkle path updates
+//     (with their value pass, which produces the assigned witnesses), Merkle openings, the ANN query and the ANN update;
+//   * HostStreams / DevStreams and the vdb_wit_*, vdb_fp_* and vdb_wit_set_window entry points.
 //
 // Every kernel writes cells of the flat advice stream at statically known offsets (gadgets.hpp), so
 // independent gadget instances — distance evaluations, Poseidon permutations, per-dimension folds —
 // run as independent threads; long sequential gadgets are cut into position windows, one window per
 // wavefront of 64 instances.  The stream is written once (32 B per cell: the HBM-write roofline of
-// this stage) and read once by the layout kernel.
+// this stage) and read once by the layout kernel (layout.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -13,11 +21,11 @@
 #include "ann_update_host.hpp"
 #include "common.hpp"
 #include "gadgets.hpp"
+#include "hostglue.hpp"
 #include "poseidon.hpp"
+#include "resident.hpp"
 
 namespace vdb {
-
-int poseidon_merkle_dev(const u256* vectors_dev, size_t n, size_t dim, u256* lv, u256* tmp);
 
 // ------------------------------------------------------------------ fixed-point staging (host)
 // fixed_point.rs:104-119: round(|x| * 2^P) as u128 (saturating), negative -> r - q
@@ -1029,8 +1037,6 @@ HD constexpr uint32_t perm_cells(int n_in) { return (n_in == 2 ? 18u : (n_in == 
 // select 8 | select 8 | node] for the first running digest, [select 8 | select 8 | node] for a second one (the updates' new path)
 constexpr uint32_t NODE_CELLS = perm_cells(2) + perm_cells(0), PATH_HEAD_CELLS = 4 + 2 * 8, PATH_TAIL_CELLS = 2 * 8;
 HD constexpr uint64_t path_level_cells(int sides) { return PATH_HEAD_CELLS + NODE_CELLS + (uint64_t)(sides - 1) * (PATH_TAIL_CELLS + NODE_CELLS); }
-// words that permutation p of the sponge over a leaf of D words absorbs
-HD int leaf_absorbs(size_t D, uint32_t p) { return 2 * (size_t)p < D ? (int)(D - 2 * (size_t)p < 2 ? D - 2 * (size_t)p : 2) : 0; }
 // One permutation of the node hash H(left, right) whose cells start at p0: the absorbing one, or (`second`) the padding-only one behind
 // it, which starts from the state its lane recomputes.  A rank that holds a block of columns emits only the permutations whose cells
 // fall into its stretch of the stream.
@@ -1074,22 +1080,6 @@ __device__ u256 trace_path_index(WCtx& c, const FpTables* T, uint32_t slot, uint
   return trace_ip_const_of(c, [slot](int l) { return ((slot >> l) & 1u) ? mont_one<Fr>() : u256_zero(); }, T->pow2, (int)depth);
 }
 
-// sponge states before every permutation of every leaf (value only); leaf v's digest goes to leaves[leaf_at[v]] (null: leaves[v])
-__global__ __launch_bounds__(64) void k_mk_leaf_states(const PoseidonSpec* __restrict__ sp, const u256* __restrict__ vectors, uint32_t n, uint32_t D,
-                                                       uint32_t nperm, u256* __restrict__ states /* n * nperm * 3 */, u256* __restrict__ leaves,
-                                                       const uint32_t* __restrict__ leaf_at) {
-  uint32_t v = blockIdx.x * 64 + threadIdx.x;
-  if (v >= n) return;
-  u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
-  const u256* msg = vectors + (size_t)v * D;
-  for (uint32_t p = 0; p < nperm; p++) {
-    for (int i = 0; i < PSD_T; i++) states[((size_t)v * nperm + p) * PSD_T + i] = st[i];
-    const int cnt = leaf_absorbs(D, p);
-    u256 in[PSD_RATE] = {cnt > 0 ? msg[2 * p] : u256_zero(), cnt > 1 ? msg[2 * p + 1] : u256_zero()};
-    psd_permute_absorb(sp, st, in, cnt);
-  }
-  leaves[leaf_at ? leaf_at[v] : v] = st[1];
-}
 // one thread per leaf permutation: the trace cells; leaf v's sponge starts at base + v * leaf_cells, or at base + starts[v] where given
 __global__ __launch_bounds__(64) void k_mk_leaf_trace(Streams stq, const FpTables* __restrict__ T, const PoseidonSpec* __restrict__ sp,
                                                       const u256* __restrict__ vectors, uint32_t n, uint32_t D, uint32_t nperm, uint64_t base,
@@ -1113,19 +1103,9 @@ __global__ __launch_bounds__(64) void k_mk_leaf_trace(Streams stq, const FpTable
   c = trace_permutation(c, T, sp, st, in, cnt);
 }
 // The tree without a launch per level's TRACE: the digests of every level first (value only: two permutations of latency per level,
-// k_mk_level_values), then every node's two permutations traced in ONE launch — a thread per (node, permutation), the padding-only
+// k_mk_level_values of resident.hip), then every node's two permutations traced in ONE launch — a thread per (node, permutation), the padding-only
 // permutation starting from the state its thread recomputes.  (One thread per node tracing 4.5 k cells level after level cost ten
 // launches of 2.1 ms each whatever the level's size: 21 of C3's 49 ms of witness.)
-__global__ __launch_bounds__(64) void k_mk_level_values(const PoseidonSpec* __restrict__ sp, const u256* __restrict__ in_lv, uint32_t n_out,
-                                                        u256* __restrict__ out_lv) {
-  uint32_t t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= n_out) return;
-  u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
-  u256 in[PSD_RATE] = {in_lv[2 * t], in_lv[2 * t + 1]};
-  psd_permute_absorb(sp, st, in, 2);
-  psd_permute_absorb(sp, st, in, 0);
-  out_lv[t] = st[1];
-}
 // levels: level 0 = the lp (padded) leaf digests, level l at offset lp (2 - 2^(1-l)) ... i.e. one after the other; node g of the
 // tree (level-major numbering, g < lp - 1) has its cells at base + g * NODE_CELLS
 __global__ __launch_bounds__(64) void k_mk_tree_trace(Streams stq, const FpTables* __restrict__ T, const PoseidonSpec* __restrict__ sp,
@@ -1157,7 +1137,6 @@ __global__ __launch_bounds__(64) void k_mk_tree_trace(Streams stq, const FpTable
 // have been doubled `grow` times before the batch (vdb_merkle_tree_grow_dev): then the assigned witnesses end with R_0, the root before
 // the growth, and a growth block follows them: [Z_0 = load_constant(0) | Z_{l+1} = H(Z_l, Z_l), l < depth - 1 | R_{i+1} = H(R_i, Z_{d+i}),
 // i < grow] (k_mku_grow_trace), d the depth before the growth.  A plain batch is all writes and grow = 0.
-#define MKU_MAX_UPDATES 4096
 // what the stream of a path circuit is made of, for updates and reads alike (path_layout): the leaf sponge, a level, the index
 struct PathLayout {
   uint32_t D, depth, nperm;
@@ -1167,7 +1146,6 @@ struct MkuLayout : PathLayout {
   uint32_t m, w, d0, grow;  // w: the writes among the m updates; depth = d0 + grow
   uint64_t n_vec, n_wit, n_in, grow_cells, total;  // n_in = n_vec + n_wit (+ 1: R_0 when grow)
 };
-HD uint64_t mku_level_off(uint64_t lp, uint32_t l) { return 2 * (lp - (lp >> l)); }
 // per (level, update), arrays indexed [l * m + j]: sib_from = the latest earlier update whose path holds this one's sibling node at
 // level l (-1: the resident digest is still current), last = no later update touches this update's node at level l (its new-path
 // digest is the batch's final state of that node); prev_same[j] = the latest earlier update of the same slot (-1: none).
@@ -1314,25 +1292,6 @@ __global__ __launch_bounds__(64) void k_mku_grow_trace(Streams stq, const FpTabl
   trace_node_half(stq, T, sp, gb + 1 + (uint64_t)h * NODE_CELLS, h < n_z ? empty + lz : levels + mku_level_off(lp, lz), empty + lz, second);
 }
 
-// ------------------------------------------------------------------ growing the resident tree (include/vdb.h vdb_merkle_tree_grow_dev)
-// The tree over lp leaves (depth d) laid out again as the tree over lp << grow leaves whose new slots are empty, a lane per entry:
-// level l < d keeps its lp >> l digests and continues with Z_l; level d + i holds R_i at entry 0 (R_0: the old root; R_{i+1} =
-// H(R_i, Z_{d+i}): k_mk_level_values on one node, `grow` launches after this one, which leaves 0 there) and Z_{d+i} behind it.
-__global__ __launch_bounds__(256) void k_mk_tree_grow(const u256* __restrict__ old_lv, uint64_t lp, uint32_t d, uint32_t grow,
-                                                      const u256* __restrict__ empty, u256* __restrict__ out) {
-  const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x, glp = lp << grow;
-  if (e >= 2 * glp) return;
-  uint32_t l = 0;
-  while (l < d + grow && e >= mku_level_off(glp, l + 1)) l++;
-  const uint64_t i = e - mku_level_off(glp, l);
-  u256 v;
-  if (i >= (glp >> l)) v = u256_zero();                   // the unused last entry
-  else if (l < d) v = i < (lp >> l) ? old_lv[mku_level_off(lp, l) + i] : empty[l];
-  else if (i) v = empty[l];
-  else v = l == d ? old_lv[mku_level_off(lp, d)] : u256_zero();
-  out[e] = v;
-}
-
 // ------------------------------------------------------------------ Merkle openings (include/vdb.h vdb_wit_merkle_open)
 // m reads of slots idx_j of the resident tree `levels`, independent of each other; `levels` is only read.  Stream:
 // [vectors m * D (vector mode) or leaves m (leaf mode) | bits | siblings] (the assigned witnesses), then per read its leaf sponge
@@ -1390,120 +1349,6 @@ __global__ __launch_bounds__(64) void k_mko_index(Streams stq, const FpTables* _
   if (j == 0) pub[0] = levels[mku_level_off(lp, depth)];
   if (ml.with_vectors)
     for (uint32_t w = 0; w < ml.D; w++) pub[1 + 2 * (size_t)m + (size_t)j * ml.D + w] = vectors[(size_t)j * ml.D + w];
-}
-
-// ------------------------------------------------------------------ layout (halo2-base assign_threads_in)
-// break points from the gate-start bits: the row walk of GateThreadBuilder::assign_all.  A column that
-// starts at stream cell S breaks at the first row r in {M-3, M-2 (if that cell starts a gate), M-1}.
-__global__ void k_layout_plan(const uint8_t* __restrict__ sel, uint64_t n_cells, uint64_t max_rows, uint64_t* __restrict__ bp, uint64_t cap,
-                              uint64_t* __restrict__ n_bp) {
-  if (blockIdx.x || threadIdx.x) return;
-  uint64_t S = 0, cnt = 0;
-  const uint64_t M = max_rows;
-  for (;;) {
-    uint64_t r;
-    if (M >= 3 && S + M - 3 < n_cells && (sel[S + M - 3] & 1)) r = M - 3;
-    else if (M >= 2 && S + M - 2 < n_cells && (sel[S + M - 2] & 1)) r = M - 2;
-    else r = M - 1;
-    if (S + r >= n_cells) break;
-    if (cnt < cap) bp[cnt] = r;
-    cnt++;
-    S += r;
-  }
-  *n_bp = cnt;
-}
-__global__ __launch_bounds__(256) void k_layout_columns(const u256* __restrict__ stream, uint64_t n_cells, const uint64_t* __restrict__ starts,
-                                                        const uint64_t* __restrict__ bp, uint64_t n_bp, uint32_t k, u256* __restrict__ cols,
-                                                        const u256* __restrict__ blind, uint32_t n_blind, uint64_t col_lo, uint64_t col_hi) {
-  const uint64_t rows = 1ull << k;
-  uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  uint64_t total = (col_hi - col_lo) * rows;
-  if (idx >= total) return;
-  uint64_t col = col_lo + (idx >> k), row = idx & (rows - 1);
-  uint64_t start = starts[col];
-  uint64_t len = col < n_bp ? bp[col] + 1 : n_cells - start;  // cells held by this column
-  u256 v = u256_zero();
-  if (row < len) v = ld256(stream + start + row);
-  else if (blind && row >= rows - n_blind) v = ld256(blind + col * n_blind + (row - (rows - n_blind)));
-  st256(cols + idx, v);
-}
-__global__ __launch_bounds__(256) void k_layout_lookup(const u256* __restrict__ lk, uint64_t n_cells, uint64_t max_rows, uint32_t k, uint64_t n_cols,
-                                                       u256* __restrict__ cols, const u256* __restrict__ blind, uint32_t n_blind, uint64_t col_lo) {
-  const uint64_t rows = 1ull << k;
-  uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n_cols * rows) return;
-  uint64_t col = col_lo + (idx >> k), row = idx & (rows - 1);
-  uint64_t src = col * max_rows + row;
-  u256 v = u256_zero();
-  if (row < max_rows && src < n_cells) v = ld256(lk + src);
-  else if (blind && row >= rows - n_blind) v = ld256(blind + col * n_blind + (row - (rows - n_blind)));
-  st256(cols + idx, v);
-}
-
-// column-layout image of the constant-cell flags (bit 1 of the keygen flag byte): mask[col][row] = 1 when the cell
-// laid out there is a data-independent constant
-__global__ __launch_bounds__(256) void k_layout_const_mask(const uint8_t* __restrict__ flags, uint64_t n_cells, const uint64_t* __restrict__ starts,
-                                                           const uint64_t* __restrict__ bp, uint64_t n_bp, uint32_t k, uint8_t* __restrict__ mask) {
-  const uint64_t rows = 1ull << k;
-  uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (n_bp + 1) * rows) return;
-  uint64_t col = idx >> k, row = idx & (rows - 1);
-  uint64_t start = starts[col];
-  uint64_t len = col < n_bp ? bp[col] + 1 : n_cells - start;
-  mask[idx] = row < len ? (flags[start + row] >> 1) & 1 : 0;
-}
-// column-layout image of the gate selectors as field elements: q[col][row] = 1 where a gate starts (bit 0 of the flag byte)
-__global__ __launch_bounds__(256) void k_layout_selectors(const uint8_t* __restrict__ flags, uint64_t n_cells, const uint64_t* __restrict__ starts,
-                                                          const uint64_t* __restrict__ bp, uint64_t n_bp, uint32_t k, u256* __restrict__ q) {
-  const uint64_t rows = 1ull << k;
-  uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (n_bp + 1) * rows) return;
-  uint64_t col = idx >> k, row = idx & (rows - 1);
-  uint64_t start = starts[col];
-  uint64_t len = col < n_bp ? bp[col] + 1 : n_cells - start;
-  // the last cell of a column that is not the last one is the cell the next column starts with again (break points sit on
-  // gate boundaries: it closes a gate here and opens one there), so its selector is enabled in the next column only
-  const uint64_t sel_len = col < n_bp ? len - 1 : len;
-  st256(q + idx, (row < sel_len && (flags[start + row] & 1)) ? mont_one<Fr>() : u256_zero());
-}
-// scalars' = mask ? v : 0 (constant part) or mask ? 0 : v (variable part)
-__global__ __launch_bounds__(256) void k_mask_select(const u256* __restrict__ in, const uint8_t* __restrict__ mask, uint64_t n, int keep_const,
-                                                     u256* __restrict__ out) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  bool m = mask[i] != 0;
-  st256(out + i, (m == (keep_const != 0)) ? ld256(in + i) : u256_zero());
-}
-
-// ------------------------------------------------------------------ helpers for the host-pointer ABI
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
-    return VDB_OK;
-  }
-  template <class U>
-  U* as() { return (U*)p; }
-};
-#define TRY(x)             \
-  do {                     \
-    int _rc = (x);         \
-    if (_rc) return _rc;   \
-  } while (0)
-
-static int check_err_flag(int* derr) {
-  int h = 0;
-  VDB_HIP(hipMemcpyAsync(&h, derr, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
-  VDB_HIP(hipStreamSynchronize(ctx().stream));
-  if (h) {
-    set_error("data-dependent failure the reference turns into a panic (division by zero / index out of range)");
-    return VDB_ERR_DOMAIN;
-  }
-  return VDB_OK;
 }
 
 // ---- device-level drivers -------------------------------------------------------------------
@@ -1685,34 +1530,18 @@ int wit_kmeans_dev(FpEntry* fp, int metric, const u256* vectors, size_t n, size_
   return inv_list_fixup(st);
 }
 
-// (tree_shape, the padded leaf count and the depth of the tree over n leaves: ann_update_host.hpp)
-struct MkLayout {
-  uint32_t nperm, depth;
-  uint64_t leaf_cells, leaves, n_leaves_pow2, zero_cell, total;
+// merkle_commitment over n vectors of `dim` words: the tree's shape (MkShape, resident.hpp) and the cells of its trace
+struct MkLayout : MkShape {
+  uint64_t leaf_cells, leaves, zero_cell, total;
 };
 static void mk_layout(size_t n, size_t dim, int zero_cached, MkLayout* o) {
-  o->nperm = (uint32_t)((dim + 1) / 2 + (dim % 2 == 0 ? 1 : 0));
+  mk_shape(n, dim, o);
   o->leaf_cells = 0;
   for (uint32_t p = 0; p < o->nperm; p++) o->leaf_cells += perm_cells(leaf_absorbs(dim, p));
   o->leaves = n * o->leaf_cells;
-  tree_shape(n, &o->n_leaves_pow2, &o->depth);
   const uint64_t lp = o->n_leaves_pow2;
   o->zero_cell = (lp > n && !zero_cached) ? 1 : 0;
   o->total = o->leaves + o->zero_cell + (lp - 1) * (uint64_t)NODE_CELLS;
-}
-// The digests of every level of merkle_commitment's tree, values only, into `levels` in k_mk_tree_trace's layout: the lp padded leaf
-// digests, then the levels one after the other (lp + lp / 2 + ... + 1 of the 2 lp entries, the last unused); the root is at *root_off.
-// `states` receives the sponge state before every permutation of every leaf (n * nperm * PSD_T entries).
-static int mk_tree_values(const PoseidonSpec* sp, const u256* vectors, size_t n, size_t dim, const MkLayout& ml, u256* states, u256* levels,
-                          uint64_t* root_off) {
-  const uint64_t lp = ml.n_leaves_pow2;
-  VDB_HIP(hipMemsetAsync(levels, 0, 2 * lp * sizeof(u256), ctx().stream));
-  VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((n + 63) / 64)), dim3(64), sp, vectors, (uint32_t)n, (uint32_t)dim, ml.nperm, states, levels, nullptr);
-  uint64_t off = 0;
-  for (uint64_t lv = lp; lv > 1; off += lv, lv /= 2)
-    VDB_LAUNCH(k_mk_level_values, dim3((unsigned)((lv / 2 + 63) / 64)), dim3(64), sp, levels + off, (uint32_t)(lv / 2), levels + off + lv);
-  *root_off = off;
-  return VDB_OK;
 }
 // merkle_commitment's cells from stream cell `base` on (the caller has published the call's context).  `resident`: the tree's digests
 // where they already lie on the device (vdb_merkle_tree_build_dev's layout, only read) — then only the leaves' sponge states are computed,
@@ -1726,7 +1555,7 @@ static int mk_emit(FpEntry* fp, const PoseidonSpec* sp, const u256* vectors, siz
   u256* levels = states + n * ml.nperm * PSD_T;
   uint64_t root_off = 2 * lp - 2;
   if (resident)  // (the leaf digests the kernel writes beside the states are the resident ones again)
-    VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((n + 63) / 64)), dim3(64), sp, vectors, (uint32_t)n, (uint32_t)dim, ml.nperm, states, levels, nullptr);
+    TRY(mk_leaf_states(sp, vectors, (uint32_t)n, (uint32_t)dim, ml.nperm, states, levels, nullptr));
   else
     TRY(mk_tree_values(sp, vectors, n, dim, ml, states, levels, &root_off));
   const u256* lv = resident ? resident : levels;
@@ -1755,36 +1584,6 @@ int wit_merkle_dev(const u256* vectors, size_t n, size_t dim, int zero_cached, S
   MkLayout ml;
   mk_layout(n, dim, zero_cached, &ml);
   return mk_emit(fp, sp, vectors, n, dim, ml, st, 0, nullptr, root_out);
-}
-
-// the resident tree of the path updates: mk_tree_values into the caller's buffer
-int merkle_tree_build_dev(const u256* vectors, size_t n, size_t dim, u256* levels) {
-  const PoseidonSpec* sp;
-  TRY(poseidon_spec_dev(&sp, nullptr));
-  MkLayout ml;
-  mk_layout(n, dim, 0, &ml);
-  u256* states = (u256*)scratch_get(0, (n * ml.nperm * PSD_T + 8) * sizeof(u256));
-  if (!states) return VDB_ERR_OOM;
-  uint64_t root_off;
-  return mk_tree_values(sp, vectors, n, dim, ml, states, levels, &root_off);
-}
-
-// the tree of vdb_merkle_tree_build_dev with its padded leaf count doubled `grow` times, the new slots empty, into `grown`
-int merkle_tree_grow_dev(const u256* levels, size_t n, unsigned grow, u256* grown) {
-  VDB_ARG(n > 0 && n <= ((size_t)1 << 30), "empty database or tree deeper than 30 levels");
-  uint64_t lp;
-  uint32_t d;
-  tree_shape(n, &lp, &d);
-  VDB_ARG(d + (uint64_t)grow <= 30, "grown tree deeper than 30 levels");
-  const PoseidonSpec* sp;
-  TRY(poseidon_spec_dev(&sp, nullptr));
-  const u256* empty;
-  TRY(poseidon_empty_subtrees_dev(&empty));
-  const uint64_t glp = lp << grow;
-  VDB_LAUNCH(k_mk_tree_grow, dim3((unsigned)((2 * glp + 255) / 256)), dim3(256), levels, lp, d, (uint32_t)grow, empty, grown);
-  for (uint32_t i = 0; i < grow; i++)
-    VDB_LAUNCH(k_mk_level_values, dim3(1), dim3(64), sp, grown + mku_level_off(glp, d + i), 1u, grown + mku_level_off(glp, d + i + 1));
-  return VDB_OK;
 }
 
 // The part of a path circuit's layout that updates (sides = 2: an old and a new running digest per level) and reads (sides = 1) share,
@@ -1912,8 +1711,7 @@ static int mku_emit(FpEntry* fp, const PoseidonSpec* sp, const MkuPlan& pl, u256
   const uint32_t mu = (uint32_t)m, wu = (uint32_t)w;
   // grids of at least one block: the launches of a call do not depend on how many of its updates are writes
   VDB_LAUNCH(k_mku_touchers, dim3((unsigned)((m * depth + 255) / 256)), dim3(256), didx, mu, depth, sib_from, prev_same, last, write_no, path_new);
-  VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((w + 63) / 64 + (w == 0))), dim3(64), sp, new_vectors, wu, (uint32_t)dim, ml.nperm, states, path_new,
-             write_of);
+  TRY(mk_leaf_states(sp, new_vectors, wu, (uint32_t)dim, ml.nperm, states, path_new, write_of));
   for (uint32_t l = 0; l < depth; l++)
     VDB_LAUNCH(k_mku_level, dim3((unsigned)((2 * m + 63) / 64)), dim3(64), sp, levels, lp, didx, mu, depth, l, sib_from, prev_same, wit, path_old, path_new);
   if (grow)  // R_i and the public old root, read before the write-back replaces them
@@ -1984,7 +1782,7 @@ int wit_merkle_open_dev(const u256* levels, size_t n, size_t dim, const u256* ve
   const uint32_t mu = (uint32_t)m, depth = ml.depth;
   VDB_LAUNCH(k_mko_inputs, dim3((unsigned)((ml.n_in + 255) / 256)), dim3(256), st, 0, ml, lp, vectors, levels, didx);
   if (vectors) {
-    VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((m + 63) / 64)), dim3(64), sp, vectors, mu, (uint32_t)dim, ml.nperm, states, vleaf, nullptr);
+    TRY(mk_leaf_states(sp, vectors, mu, (uint32_t)dim, ml.nperm, states, vleaf, nullptr));
     VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((m * ml.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, vectors, mu, (uint32_t)dim, ml.nperm, ml.n_in,
                ml.per_read, states, nullptr);
   }
@@ -1993,169 +1791,8 @@ int wit_merkle_open_dev(const u256* levels, size_t n, size_t dim, const u256* ve
   return VDB_OK;
 }
 
-// ------------------------------------------------------------------ the index of an approximate-nearest-neighbour query (include/vdb.h
-// vdb_ann_index_build_dev, vdb_wit_ann_query).  The index commits to K centroids and to the database grouped by cluster:
-// index_root = sponge over [merkle_commitment(centroids), merkle_commitment(members(0)), ..., merkle_commitment(members(K - 1))].
-// The K + 1 trees lie one after the other in a forest, segment s = 2 lp_s digests in mk_tree_values' layout (segment K: the centroids'),
-// and are hashed level by level by ONE launch per level over all segments.
-struct AnnForest {
-  std::vector<uint64_t> seg_off;   // K + 2: where segment s starts in the forest, in digests
-  std::vector<uint32_t> seg_lp;    // K + 1
-  std::vector<uint32_t> prefix;    // depth x (K + 2): nodes of level l + 1 in the segments before s
-  uint32_t depth = 0;
-};
-static int ann_forest_plan(const uint32_t* ids, size_t n, size_t K, AnnForest* f) {
-  VDB_ARG(ids && n > 0 && K > 0, "null pointer, empty database or K = 0");
-  VDB_ARG(n <= VDB_ANN_MAX_VECTORS && K <= VDB_ANN_MAX_CLUSTERS, "index too large: n at most 2^24, K at most 4096 (include/vdb.h)");
-  std::vector<uint64_t> cnt(K, 0);
-  for (size_t i = 0; i < n; i++) {
-    VDB_ARG(ids[i] < K, "cluster id >= K");
-    cnt[ids[i]]++;
-  }
-  f->seg_off.assign(K + 2, 0);
-  f->seg_lp.assign(K + 1, 1);
-  f->depth = 0;
-  for (size_t s = 0; s <= K; s++) {
-    const uint64_t m = s < K ? cnt[s] : K;
-    VDB_ARG(m > 0, "empty cluster: merkle_commitment is undefined over zero vectors");
-    uint64_t lp;
-    uint32_t d;
-    tree_shape(m, &lp, &d);
-    f->seg_lp[s] = (uint32_t)lp;
-    f->seg_off[s + 1] = f->seg_off[s] + 2 * lp;
-    if (d > f->depth) f->depth = d;
-  }
-  f->prefix.assign((size_t)f->depth * (K + 2), 0);
-  for (uint32_t l = 0; l < f->depth; l++)
-    for (size_t s = 0; s <= K; s++) f->prefix[(size_t)l * (K + 2) + s + 1] = f->prefix[(size_t)l * (K + 2) + s] + (f->seg_lp[s] >> (l + 1));
-  return VDB_OK;
-}
-// Stable grouping of the rows by cluster id, one wavefront: 64 rows at a time, a row's rank = the rows of its cluster in the tiles before
-// (counts in LDS) + the lower lanes of its tile with the same id.  Then the K + 1 offsets (a serial prefix sum by lane 0), and per row
-// its place among the grouped rows, the database slot that place holds and where its leaf digest goes in the forest.
-__global__ __launch_bounds__(64) void k_ann_group(const uint32_t* __restrict__ ids, uint32_t n, uint32_t K, const uint64_t* __restrict__ seg_off,
-                                                   uint64_t* __restrict__ offsets, uint32_t* __restrict__ rank, uint32_t* __restrict__ slots,
-                                                   uint32_t* __restrict__ leaf_at) {
-  __shared__ uint32_t cnt[VDB_ANN_MAX_CLUSTERS];
-  const uint32_t lane = threadIdx.x;
-  for (uint32_t c = lane; c < K; c += 64) cnt[c] = 0;
-  __syncthreads();
-  for (uint32_t c0 = 0; c0 < n; c0 += 64) {
-    const uint32_t i = c0 + lane;
-    const bool live = i < n;
-    const uint32_t id = live ? ids[i] : 0xffffffffu;
-    uint32_t lower = 0, r = 0;
-    bool last = true;
-    for (int l = 0; l < 64; l++) {
-      const uint32_t o = (uint32_t)__shfl((int)id, l);
-      if (o == id) {
-        if (l < (int)lane) lower++;
-        if (l > (int)lane) last = false;
-      }
-    }
-    if (live) {
-      r = cnt[id] + lower;
-      rank[i] = r;
-    }
-    __syncthreads();
-    if (live && last) cnt[id] = r + 1;
-    __syncthreads();
-  }
-  if (lane == 0) {
-    uint32_t acc = 0;
-    for (uint32_t c = 0; c < K; c++) {
-      const uint32_t m = cnt[c];
-      offsets[c] = acc;
-      cnt[c] = acc;
-      acc += m;
-    }
-    offsets[K] = acc;
-  }
-  __syncthreads();
-  for (uint32_t i = lane; i < n; i += 64) {
-    const uint32_t id = ids[i], r = rank[i], pos = cnt[id] + r;
-    slots[pos] = i;
-    leaf_at[pos] = (uint32_t)seg_off[id] + r;
-  }
-}
-// the rows in grouped order, a lane per word
-__global__ __launch_bounds__(256) void k_ann_gather(const u256* __restrict__ db, const uint32_t* __restrict__ slots, uint64_t n, uint32_t D,
-                                                    u256* __restrict__ grouped) {
-  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= n * D) return;
-  grouped[t] = db[(uint64_t)slots[t / D] * D + t % D];
-}
-// level l + 1 of every tree of the forest from its level l: a lane per (segment, node), the segment found in the prefix sums of the
-// level's node counts (a segment shallower than the level has no node and no lane)
-__global__ __launch_bounds__(64) void k_ann_forest_level(const PoseidonSpec* __restrict__ sp, u256* __restrict__ forest, const uint64_t* __restrict__ seg_off,
-                                                          const uint32_t* __restrict__ seg_lp, const uint32_t* __restrict__ prefix, uint32_t n_seg,
-                                                          uint32_t l) {
-  const uint32_t t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= prefix[n_seg]) return;
-  uint32_t lo = 0, hi = n_seg;   // the last segment s with prefix[s] <= t (segments without a node share their successor's prefix)
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) / 2;
-    if (prefix[mid] <= t) lo = mid; else hi = mid;
-  }
-  const uint32_t node = t - prefix[lo];
-  const uint64_t lp = seg_lp[lo];
-  const u256* in_lv = forest + seg_off[lo] + mku_level_off(lp, l);
-  u256 st[PSD_T] = {sp->cap, u256_zero(), u256_zero()};
-  u256 in[PSD_RATE] = {in_lv[2 * node], in_lv[2 * node + 1]};
-  psd_permute_absorb(sp, st, in, 2);
-  psd_permute_absorb(sp, st, in, 0);
-  forest[seg_off[lo] + mku_level_off(lp, l + 1) + node] = st[1];
-}
-// [centroids' root | the K cluster roots]: the words the index root is the sponge of
-__global__ __launch_bounds__(64) void k_ann_roots(const u256* __restrict__ forest, const uint64_t* __restrict__ seg_off, const uint32_t* __restrict__ seg_lp,
-                                                   uint32_t K, u256* __restrict__ roots) {
-  const uint32_t s = blockIdx.x * 64 + threadIdx.x;
-  if (s > K) return;
-  roots[s == K ? 0 : 1 + s] = forest[seg_off[s] + 2 * (uint64_t)seg_lp[s] - 2];
-}
-
-int ann_index_build_dev(const u256* db, const uint32_t* ids, const u256* centroids, size_t n, size_t K, size_t dim, u256* grouped, uint32_t* slots,
-                        uint64_t* offsets, u256* forest, u256* roots) {
-  static thread_local AnnForest f;   // (pageable source of an asynchronous upload: it outlives the call)
-  TRY(ann_forest_plan(ids, n, K, &f));
-  const PoseidonSpec* sp;
-  TRY(poseidon_spec_dev(&sp, nullptr));
-  hipStream_t s = ctx().stream;
-  const size_t n_seg = K + 1, n_pre = (size_t)f.depth * (K + 2);
-  // work space: [seg_off | seg_lp, prefix, ids, rank, leaf_at] and the sponge states of the larger of the two leaf launches
-  uint8_t* w = (uint8_t*)scratch_get(7, (K + 2) * 8 + (n_seg + n_pre + 3 * n + 16) * 4);
-  if (!w) return VDB_ERR_OOM;
-  uint64_t* d_off = (uint64_t*)w;
-  uint32_t* d_lp = (uint32_t*)(d_off + K + 2);
-  uint32_t *d_pre = d_lp + n_seg, *d_ids = d_pre + n_pre, *d_rank = d_ids + n, *d_at = d_rank + n;
-  MkLayout ml, mw;
-  mk_layout(n, dim, 0, &ml);
-  mk_layout(1, K + 1, 0, &mw);
-  const size_t n_states = std::max((n > K ? n : K) * (size_t)ml.nperm, (size_t)mw.nperm) * PSD_T;
-  u256* states = (u256*)scratch_get(0, (n_states + 8) * sizeof(u256));
-  if (!states) return VDB_ERR_OOM;
-  VDB_HIP(hipMemcpyAsync(d_off, f.seg_off.data(), (K + 2) * 8, hipMemcpyHostToDevice, s));
-  VDB_HIP(hipMemcpyAsync(d_lp, f.seg_lp.data(), n_seg * 4, hipMemcpyHostToDevice, s));
-  if (n_pre) VDB_HIP(hipMemcpyAsync(d_pre, f.prefix.data(), n_pre * 4, hipMemcpyHostToDevice, s));
-  VDB_HIP(hipMemcpyAsync(d_ids, ids, n * 4, hipMemcpyHostToDevice, s));
-  VDB_HIP(hipMemsetAsync(forest, 0, f.seg_off[K + 1] * sizeof(u256), s));
-  VDB_LAUNCH(k_ann_group, dim3(1), dim3(64), d_ids, (uint32_t)n, (uint32_t)K, d_off, offsets, d_rank, slots, d_at);
-  VDB_LAUNCH(k_ann_gather, dim3((unsigned)((n * dim + 255) / 256)), dim3(256), db, slots, (uint64_t)n, (uint32_t)dim, grouped);
-  // the leaf of a row does not depend on its cluster: one launch over the grouped rows, one over the centroids
-  VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((n + 63) / 64)), dim3(64), sp, grouped, (uint32_t)n, (uint32_t)dim, ml.nperm, states, forest, d_at);
-  VDB_LAUNCH(k_mk_leaf_states, dim3((unsigned)((K + 63) / 64)), dim3(64), sp, centroids, (uint32_t)K, (uint32_t)dim, ml.nperm, states,
-             forest + f.seg_off[K], nullptr);
-  for (uint32_t l = 0; l < f.depth; l++)
-    VDB_LAUNCH(k_ann_forest_level, dim3((unsigned)((f.prefix[(size_t)l * (K + 2) + n_seg] + 63) / 64)), dim3(64), sp, forest, d_off, d_lp,
-               d_pre + (size_t)l * (K + 2), (uint32_t)n_seg, l);
-  VDB_LAUNCH(k_ann_roots, dim3((unsigned)(K / 64 + 1)), dim3(64), forest, d_off, d_lp, (uint32_t)K, roots);
-  VDB_LAUNCH(k_mk_leaf_states, dim3(1), dim3(64), sp, roots, 1u, (uint32_t)(K + 1), mw.nperm, states, roots + K + 1, nullptr);
-  // (the host arrays are read when the copies are enqueued on this runtime; the synchronisation makes that no assumption here, where
-  //  the next call of this thread rewrites them)
-  VDB_HIP(hipStreamSynchronize(s));
-  return VDB_OK;
-}
-
+// ------------------------------------------------------------------ an approximate-nearest-neighbour query against the committed index
+// (include/vdb.h vdb_wit_ann_query; the index itself, its forest of K + 1 trees and their roots: resident.hip)
 // the circuit of one query (include/vdb.h vdb_wit_ann_query): where its blocks start
 struct AnnLayout {
   DistLayout dl;
@@ -2214,7 +1851,7 @@ int wit_ann_query_dev(FpEntry* fp, int metric, const u256* query, const u256* ce
   VDB_HIP(hipMemcpyAsync(words + 1, cluster_roots, K * sizeof(u256), hipMemcpyDeviceToDevice, s));
   const NvMap sm{a.b_sel, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, (uint32_t)K, 1u, 1u};
   VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), st, fp->dev, sm, 1u, cluster_roots, ind_c, picked);
-  VDB_LAUNCH(k_mk_leaf_states, dim3(1), dim3(64), sp, words, 1u, (uint32_t)(K + 1), a.mw.nperm, wstates, pub + dim, nullptr);
+  TRY(mk_leaf_states(sp, words, 1u, (uint32_t)(K + 1), a.mw.nperm, wstates, pub + dim, nullptr));
   VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((a.mw.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, words, 1u, (uint32_t)(K + 1), a.mw.nperm, a.b_root,
              a.mw.leaf_cells, wstates, nullptr);
   return inv_list_fixup(st);
@@ -2327,121 +1964,16 @@ int wit_ann_update_dev(u256* levels, const u256* roots, size_t K, size_t cluster
   VDB_LAUNCH(k_annu_indicator, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, a.b.b_ind, cu, Ku, k.ind);
   const NvMap sm{a.b.b_sel, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, Ku, 1u, 1u};
   VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), st, fp->dev, sm, 1u, words_old + 1, k.ind, k.picked);
-  VDB_LAUNCH(k_mk_leaf_states, dim3(1), dim3(64), sp, words_old, 1u, Ku + 1, nperm, k.st_old, k.iroot, nullptr);
+  TRY(mk_leaf_states(sp, words_old, 1u, Ku + 1, nperm, k.st_old, k.iroot, nullptr));
   VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((nperm + 63) / 64)), dim3(64), st, fp->dev, sp, words_old, 1u, Ku + 1, nperm, a.b.b_old, a.mw.leaf_cells,
              k.st_old, nullptr);
   TRY(mku_emit(fp, sp, pl, levels, dim, new_vectors, st, a.b.b_upd, k.upub));
   VDB_LAUNCH(k_annu_new_roots, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, a.b.b_new, Ku, k.upub + 3 * m + 1, words_old, k.ind, k.words_new);
-  VDB_LAUNCH(k_mk_leaf_states, dim3(1), dim3(64), sp, k.words_new, 1u, Ku + 1, nperm, k.st_new, k.iroot + 1, nullptr);
+  TRY(mk_leaf_states(sp, k.words_new, 1u, Ku + 1, nperm, k.st_new, k.iroot + 1, nullptr));
   VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((nperm + 63) / 64)), dim3(64), st, fp->dev, sp, k.words_new, 1u, Ku + 1, nperm, a.b.b_root, a.mw.leaf_cells,
              k.st_new, nullptr);
   VDB_LAUNCH(k_annu_public, dim3((unsigned)((3 * m + 3 + 255) / 256)), dim3(256), k.upub, k.hdr, k.iroot, (uint32_t)m, pub);
   return inv_list_fixup(st);
-}
-
-// The next index from the old one, the updated tree of cluster c and the batch (values only; the old buffers are only read).
-// One lane per word of the new grouped rows, then per new slot entry: rows up to the end of cluster c's old rows stay where they are,
-// the appended rows follow them, later rows move by the number of appends; inside cluster c the last write of the batch to a slot wins
-__global__ __launch_bounds__(256) void k_ann_rows_apply(const u256* __restrict__ grouped, const uint32_t* __restrict__ slots,
-                                                        const u256* __restrict__ new_vectors, const uint32_t* __restrict__ idx, uint32_t m,
-                                                        const uint32_t* __restrict__ db_slots, uint64_t off_c, uint64_t end_c, uint64_t appends,
-                                                        uint64_t n_new, uint32_t D, u256* __restrict__ grouped_out, uint32_t* __restrict__ slots_out) {
-  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x, n_words = n_new * D;
-  if (t >= n_words + n_new) return;
-  const bool is_slot = t >= n_words;
-  const uint64_t r = is_slot ? t - n_words : t / D;
-  if (is_slot) {
-    slots_out[r] = r < end_c ? slots[r] : r < end_c + appends ? db_slots[r - end_c] : slots[r - appends];
-    return;
-  }
-  const uint32_t wd = (uint32_t)(t % D);
-  if (r < off_c || r >= end_c + appends) {
-    grouped_out[t] = grouped[(r < off_c ? r : r - appends) * D + wd];
-    return;
-  }
-  const uint32_t s = (uint32_t)(r - off_c);
-  int32_t from = -1;
-  for (int32_t j = (int32_t)m - 1; j >= 0; j--)
-    if (idx[j] == s) {
-      from = j;
-      break;
-    }
-  // (an appended slot always has a write: the host's fill tracking)
-  grouped_out[t] = from >= 0 ? new_vectors[(uint64_t)from * D + wd] : grouped[r * D + wd];
-}
-// one lane per digest of the new forest: its segment by bisection in the new segment offsets; segment c comes from the updated tree,
-// every other one from where the old forest holds it (the segments behind c lie `delta` digests earlier there)
-__global__ __launch_bounds__(256) void k_ann_forest_move(const u256* __restrict__ forest, const u256* __restrict__ updated,
-                                                         const uint64_t* __restrict__ seg_off, uint32_t n_seg, uint32_t c, uint64_t delta,
-                                                         u256* __restrict__ forest_out) {
-  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= seg_off[n_seg]) return;
-  uint32_t lo = 0, hi = n_seg;   // the segment s with seg_off[s] <= t < seg_off[s + 1] (no segment is empty)
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) / 2;
-    if (seg_off[mid] <= t) lo = mid; else hi = mid;
-  }
-  forest_out[t] = lo == c ? updated[t - seg_off[lo]] : forest[lo < c ? t : t - delta];
-}
-// the K + 1 words of the index root: the old ones, word 1 + c the updated tree's root
-__global__ __launch_bounds__(64) void k_ann_roots_apply(const u256* __restrict__ roots, const u256* __restrict__ updated, uint64_t glp, uint32_t K,
-                                                        uint32_t c, u256* __restrict__ roots_out) {
-  const uint32_t s = blockIdx.x * 64 + threadIdx.x;
-  if (s > K) return;
-  roots_out[s] = s == 1 + c ? updated[2 * glp - 2] : roots[s];
-}
-// what the two apply entry points share: the batch against cluster c's fill and the offsets after it (VDB_ERR_ARG, nothing launched)
-static int ann_apply_plan(const uint64_t* sizes, size_t K, size_t dim, size_t cluster, unsigned grow, const uint64_t* indices, size_t m,
-                          AnnuApplyPlan* p) {
-  VDB_ARG(sizes && indices, "null pointer");
-  VDB_ARG(K > 0 && K <= VDB_ANN_MAX_CLUSTERS && cluster < K, "K = 0, K above VDB_ANN_MAX_CLUSTERS or cluster >= K");
-  VDB_ARG(dim > 0 && dim <= ((size_t)1 << 20), "dim outside [1, 2^20]");
-  VDB_ARG(m > 0 && m <= MKU_MAX_UPDATES, "a batch holds 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES updates");
-  VDB_ARG(grow <= 30 && sizes[cluster] > 0 && sizes[cluster] <= VDB_ANN_MAX_VECTORS, "empty cluster, cluster too large or more than 30 doublings");
-  uint64_t lp, appends = 0;
-  uint32_t d;
-  tree_shape(sizes[cluster], &lp, &d);
-  VDB_ARG(annu_track_fill(indices, m, sizes[cluster], lp << grow, &appends, nullptr) == 0,
-          "a write above the cluster's fill at its turn or outside the grown tree");
-  const int rc = annu_apply_plan(sizes, K, cluster, grow, appends, p);
-  VDB_ARG(rc != 1, "empty cluster");
-  VDB_ARG(rc == 0, "the grown tree is not the tree over the cluster's new size: grow is the smallest number of doublings that fits the appends");
-  VDB_ARG(p->n_new <= VDB_ANN_MAX_VECTORS, "index too large: n at most VDB_ANN_MAX_VECTORS");
-  return VDB_OK;
-}
-int ann_index_apply_dev(const u256* grouped, const uint32_t* slots, const u256* forest, const u256* roots, const uint64_t* sizes, size_t K, size_t dim,
-                        size_t cluster, unsigned grow, const u256* updated, const u256* new_vectors, const uint64_t* indices, const uint32_t* db_slots,
-                        size_t m, u256* grouped_out, uint32_t* slots_out, uint64_t* offsets_out, u256* forest_out, u256* roots_out) {
-  static thread_local AnnuApplyPlan p;            // (pageable sources of asynchronous uploads: they outlive the call)
-  static thread_local std::vector<uint32_t> tab;  // [idx m | db_slots appends]
-  TRY(ann_apply_plan(sizes, K, dim, cluster, grow, indices, m, &p));
-  VDB_ARG(db_slots || p.appends == 0, "null pointer: an append needs its database slot");
-  const PoseidonSpec* sp;
-  TRY(poseidon_spec_dev(&sp, nullptr));
-  hipStream_t s = ctx().stream;
-  MkLayout mw;
-  mk_layout(1, K + 1, 0, &mw);
-  tab.resize(m + p.appends + 1);
-  for (size_t j = 0; j < m; j++) tab[j] = (uint32_t)indices[j];
-  for (size_t i = 0; i < p.appends; i++) tab[m + i] = db_slots[i];
-  uint8_t* w = (uint8_t*)scratch_get(7, (K + 2) * 8 + (m + p.appends + 16) * 4);
-  if (!w) return VDB_ERR_OOM;
-  uint64_t* d_off = (uint64_t*)w;
-  uint32_t* d_idx = (uint32_t*)(d_off + K + 2);
-  u256* states = (u256*)scratch_get(0, ((size_t)mw.nperm * PSD_T + 8) * sizeof(u256));
-  if (!states) return VDB_ERR_OOM;
-  VDB_HIP(hipMemcpyAsync(d_off, p.seg_off.data(), (K + 2) * 8, hipMemcpyHostToDevice, s));
-  VDB_HIP(hipMemcpyAsync(d_idx, tab.data(), (m + p.appends) * 4, hipMemcpyHostToDevice, s));
-  VDB_HIP(hipMemcpyAsync(offsets_out, p.offsets.data(), (K + 1) * 8, hipMemcpyHostToDevice, s));
-  const uint64_t lanes = p.n_new * dim + p.n_new;
-  VDB_LAUNCH(k_ann_rows_apply, dim3((unsigned)((lanes + 255) / 256)), dim3(256), grouped, slots, new_vectors, d_idx, (uint32_t)m, d_idx + m, p.off_c,
-             p.end_c, p.appends, p.n_new, (uint32_t)dim, grouped_out, slots_out);
-  VDB_LAUNCH(k_ann_forest_move, dim3((unsigned)((p.seg_off[K + 1] + 255) / 256)), dim3(256), forest, updated, d_off, (uint32_t)(K + 1), (uint32_t)cluster,
-             p.delta, forest_out);
-  VDB_LAUNCH(k_ann_roots_apply, dim3((unsigned)(K / 64 + 1)), dim3(64), roots, updated, p.glp_c, (uint32_t)K, (uint32_t)cluster, roots_out);
-  VDB_LAUNCH(k_mk_leaf_states, dim3(1), dim3(64), sp, roots_out, 1u, (uint32_t)(K + 1), mw.nperm, states, roots_out + K + 1, nullptr);
-  VDB_HIP(hipStreamSynchronize(s));
-  return VDB_OK;
 }
 
 }  // namespace vdb
@@ -2451,35 +1983,6 @@ using namespace vdb;
 // rank window applied by the *_dev witness entry points (vdb_wit_set_window); full range by default; per device context
 #define g_win (vdb::ctx().win)
 
-// break points and their prefix sums (column c starts at stream cell starts[c]) -> device scratch slot 1
-static int upload_break_points(const uint64_t* break_points, uint64_t n_bp, uint64_t** dbp, uint64_t** dstarts) {
-  static thread_local std::vector<uint64_t> h;  // pageable source: hipMemcpyAsync stages it before returning
-  h.resize(2 * n_bp + 2);
-  uint64_t acc = 0;
-  h[n_bp] = 0;
-  for (uint64_t i = 0; i < n_bp; i++) {
-    h[i] = break_points[i];
-    acc += break_points[i];
-    h[n_bp + 1 + i] = acc;
-  }
-  uint64_t* d = (uint64_t*)scratch_get(1, (2 * n_bp + 2) * sizeof(uint64_t));
-  if (!d) return VDB_ERR_OOM;
-  VDB_HIP(hipMemcpyAsync(d, h.data(), (2 * n_bp + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx().stream));
-  *dbp = d;
-  *dstarts = d + n_bp;
-  return VDB_OK;
-}
-
-// upload helper for the host-pointer entry points
-static int upload(DevBuf& d, const void* src, size_t bytes) {
-  TRY(d.alloc(bytes));
-  if (bytes) VDB_HIP(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, ctx().stream));
-  return VDB_OK;
-}
-static int download(void* dst, const void* src, size_t bytes) {
-  if (dst && bytes) VDB_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx().stream));
-  return VDB_OK;
-}
 struct HostStreams {
   DevBuf adv, sel, lk, err;
   Streams st;
@@ -2802,18 +2305,7 @@ int vdb_wit_merkle(const vdb_fr* vectors, size_t n, size_t dim, int zero_cached,
   return hs.finish(stream_out, nullptr, selector_out, cells, 0);
 }
 
-// the resident tree and batches of path updates against it (include/vdb.h)
-int vdb_merkle_tree_build_dev(const vdb_fr* vectors_dev, size_t n, size_t dim, vdb_fr* levels_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(vectors_dev && levels_dev && n > 0 && dim > 0, "null pointer or empty database");
-  VDB_ARG(n <= ((size_t)1 << 30), "tree deeper than 30 levels");
-  return merkle_tree_build_dev(as_u256(vectors_dev), n, dim, as_u256(levels_dev));
-}
-int vdb_merkle_tree_grow_dev(const vdb_fr* levels_dev, size_t n, unsigned grow, vdb_fr* grown_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(levels_dev && grown_dev, "null pointer");
-  return merkle_tree_grow_dev(as_u256(levels_dev), n, grow, as_u256(grown_dev));
-}
+// batches of path updates against the resident tree (include/vdb.h; the tree itself: resident.hip)
 int vdb_wit_merkle_update_ops_size(size_t n, size_t dim, size_t m, const uint8_t* kinds, unsigned grow, uint64_t* cells, uint64_t* input_cells) {
   MkuLayout ml;
   TRY(mku_layout(n, dim, m, kinds, grow, &ml, nullptr, nullptr, nullptr));
@@ -2901,23 +2393,7 @@ int vdb_wit_merkle_open(const vdb_fr* levels, size_t n, size_t dim, const vdb_fr
   return hs.finish(stream_out, nullptr, selector_out, ml.total, 0);
 }
 
-// the index of approximate-nearest-neighbour queries and the circuit of one query (include/vdb.h)
-int vdb_ann_index_forest_size(const uint32_t* cluster_ids, size_t n, size_t K, uint64_t* digests, uint64_t* segment_offsets) {
-  AnnForest f;
-  TRY(ann_forest_plan(cluster_ids, n, K, &f));
-  if (digests) *digests = f.seg_off[K + 1];
-  if (segment_offsets) memcpy(segment_offsets, f.seg_off.data(), (K + 2) * sizeof(uint64_t));
-  return VDB_OK;
-}
-int vdb_ann_index_build_dev(const vdb_fr* vectors_dev, const uint32_t* cluster_ids, const vdb_fr* centroids_dev, size_t n, size_t K, size_t dim,
-                            vdb_fr* grouped_dev, uint32_t* slots_dev, uint64_t* offsets_dev, vdb_fr* forest_dev, vdb_fr* roots_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(vectors_dev && cluster_ids && centroids_dev && grouped_dev && slots_dev && offsets_dev && forest_dev && roots_dev && dim > 0 &&
-              dim <= ((size_t)1 << 20),
-          "null pointer or dim outside [1, 2^20]");
-  return ann_index_build_dev(as_u256(vectors_dev), cluster_ids, as_u256(centroids_dev), n, K, dim, as_u256(grouped_dev), slots_dev, offsets_dev,
-                             as_u256(forest_dev), as_u256(roots_dev));
-}
+// the circuit of one approximate-nearest-neighbour query (include/vdb.h)
 int vdb_wit_ann_query_size(int metric, uint32_t P, uint32_t L, size_t K, size_t n_c, size_t dim, uint64_t* cells, uint64_t* lookups, uint64_t* input_cells) {
   VDB_REQUIRE_INIT();
   FpEntry* fp;
@@ -3018,186 +2494,6 @@ int vdb_wit_ann_update(vdb_fr* levels, const vdb_fr* roots, size_t K, size_t clu
   TRY(download(public_out, dpub.p, (3 * m + 3) * sizeof(u256)));
   TRY(download(levels, dl.p, 2 * lp * sizeof(u256)));
   return hs.finish(stream_out, nullptr, selector_out, a.b.total, 0);
-}
-int vdb_ann_index_apply_size(const uint64_t* cluster_sizes, size_t K, size_t cluster, unsigned grow, const uint64_t* indices, size_t m, uint64_t* appends,
-                             uint64_t* digests, uint64_t* segment_offsets) {
-  AnnuApplyPlan p;
-  TRY(ann_apply_plan(cluster_sizes, K, 1, cluster, grow, indices, m, &p));
-  if (appends) *appends = p.appends;
-  if (digests) *digests = p.seg_off[K + 1];
-  if (segment_offsets) memcpy(segment_offsets, p.seg_off.data(), (K + 2) * sizeof(uint64_t));
-  return VDB_OK;
-}
-int vdb_ann_index_apply_dev(const vdb_fr* grouped_dev, const uint32_t* slots_dev, const vdb_fr* forest_dev, const vdb_fr* roots_dev,
-                            const uint64_t* cluster_sizes, size_t K, size_t dim, size_t cluster, unsigned grow, const vdb_fr* updated_levels_dev,
-                            const vdb_fr* new_vectors_dev, const uint64_t* indices, const uint32_t* db_slots, size_t m, vdb_fr* grouped_out_dev,
-                            uint32_t* slots_out_dev, uint64_t* offsets_out_dev, vdb_fr* forest_out_dev, vdb_fr* roots_out_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(grouped_dev && slots_dev && forest_dev && roots_dev && updated_levels_dev && new_vectors_dev && grouped_out_dev && slots_out_dev &&
-              offsets_out_dev && forest_out_dev && roots_out_dev,
-          "null pointer");
-  return ann_index_apply_dev(as_u256(grouped_dev), slots_dev, as_u256(forest_dev), as_u256(roots_dev), cluster_sizes, K, dim, cluster, grow,
-                             as_u256(updated_levels_dev), as_u256(new_vectors_dev), indices, db_slots, m, as_u256(grouped_out_dev), slots_out_dev,
-                             offsets_out_dev, as_u256(forest_out_dev), as_u256(roots_out_dev));
-}
-
-// ---- b4 layout ---------------------------------------------------------------------------------
-int vdb_layout_plan_dev(const uint8_t* selector_dev, uint64_t n_cells, uint32_t k, uint32_t minimum_rows, uint64_t* break_points_out, uint64_t cap,
-                        uint64_t* n_break_points) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(selector_dev && n_break_points && k >= 3 && k <= 28 && ((uint64_t)1 << k) > minimum_rows + 4, "bad argument");
-  uint64_t max_rows = ((uint64_t)1 << k) - minimum_rows;
-  uint64_t est = n_cells / (max_rows - 3) + 2;
-  uint64_t* d = (uint64_t*)scratch_get(1, (est + 1) * sizeof(uint64_t));
-  if (!d) return VDB_ERR_OOM;
-  VDB_LAUNCH(k_layout_plan, dim3(1), dim3(1), selector_dev, n_cells, max_rows, d + 1, est, d);
-  uint64_t nbp = 0;
-  VDB_HIP(hipMemcpyAsync(&nbp, d, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx().stream));
-  VDB_HIP(hipStreamSynchronize(ctx().stream));
-  *n_break_points = nbp;
-  if (break_points_out) {
-    VDB_ARG(cap >= nbp, "break point buffer too small");
-    VDB_HIP(hipMemcpy(break_points_out, d + 1, nbp * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  }
-  return VDB_OK;
-}
-int vdb_layout_plan(const uint8_t* selector, uint64_t n_cells, uint32_t k, uint32_t minimum_rows, uint64_t* break_points_out, uint64_t cap,
-                    uint64_t* n_break_points) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(selector, "null pointer");
-  DevBuf ds;
-  TRY(upload(ds, selector, n_cells));
-  return vdb_layout_plan_dev(ds.as<uint8_t>(), n_cells, k, minimum_rows, break_points_out, cap, n_break_points);
-}
-int vdb_layout_columns_dev(const vdb_fr* stream_dev, uint64_t n_cells, const uint64_t* break_points, uint64_t n_bp, uint32_t k, vdb_fr* cols_dev,
-                           const vdb_fr* blind_dev, uint32_t n_blind) {
-  return vdb_layout_columns_range_dev(stream_dev, n_cells, break_points, n_bp, k, 0, n_bp + 1, cols_dev, blind_dev, n_blind);
-}
-int vdb_layout_columns_range_dev(const vdb_fr* stream_dev, uint64_t n_cells, const uint64_t* break_points, uint64_t n_bp, uint32_t k, uint64_t col_lo,
-                                 uint64_t col_hi, vdb_fr* cols_dev, const vdb_fr* blind_dev, uint32_t n_blind) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(stream_dev && cols_dev && (break_points || n_bp == 0) && k <= 28 && col_lo <= col_hi && col_hi <= n_bp + 1, "bad argument");
-  if (col_lo == col_hi) return VDB_OK;
-  const uint64_t rows = 1ull << k;
-  uint64_t sum = 0;
-  for (uint64_t i = 0; i < n_bp; i++) {
-    VDB_ARG(break_points[i] < rows, "break point beyond the column height");
-    sum += break_points[i];
-  }
-  VDB_ARG(sum <= n_cells && n_cells - sum <= rows, "break points do not match the stream length");
-  uint64_t *dbp, *dst;
-  TRY(upload_break_points(break_points, n_bp, &dbp, &dst));
-  uint64_t total = (col_hi - col_lo) * rows;
-  VDB_LAUNCH(k_layout_columns, dim3((unsigned)((total + 255) / 256)), dim3(256), as_u256(stream_dev), n_cells, dst, dbp, n_bp, k, as_u256(cols_dev),
-             blind_dev ? as_u256(blind_dev) : nullptr, n_blind, col_lo, col_hi);
-  VDB_HIP(hipStreamSynchronize(ctx().stream));  // break_points is a host buffer the caller may free
-  return VDB_OK;
-}
-int vdb_colsrc_build_dev(const vdb_fr* stream_dev, uint64_t n_cells, const uint64_t* break_points, uint64_t n_bp, uint32_t k, uint64_t col_lo,
-                         uint64_t col_hi, const vdb_fr* blind_dev, uint32_t n_blind, vdb_colsrc* out_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(stream_dev && out_dev && (break_points || n_bp == 0) && k <= 28 && col_lo <= col_hi && col_hi <= n_bp + 1, "bad argument");
-  const uint64_t rows = 1ull << k;
-  std::vector<vdb_colsrc> h(col_hi - col_lo);
-  uint64_t start = 0;
-  for (uint64_t c = 0; c < col_hi; c++) {
-    if (c < n_bp) VDB_ARG(break_points[c] < rows, "break point beyond the column height");
-    const uint64_t len = c < n_bp ? break_points[c] + 1 : n_cells - start;
-    VDB_ARG(start <= n_cells && len <= rows && start + len <= n_cells, "break points do not match the stream length");
-    if (c >= col_lo) {
-      // colsrc_fetch (and k_layout_columns) read a row below len from the stream before they look at the blinding rows
-      VDB_ARG(!blind_dev || len + n_blind <= rows, "a column's cells reach into its blinding rows");
-      h[c - col_lo].src = stream_dev + start;
-      h[c - col_lo].len = len;
-      h[c - col_lo].blind = blind_dev ? blind_dev + c * n_blind : nullptr;
-    }
-    if (c < n_bp) start += break_points[c];
-  }
-  if (!h.empty()) VDB_HIP(hipMemcpyAsync(out_dev, h.data(), h.size() * sizeof(vdb_colsrc), hipMemcpyHostToDevice, ctx().stream));
-  VDB_HIP(hipStreamSynchronize(ctx().stream));
-  return VDB_OK;
-}
-int vdb_colsrc_build_lookup_dev(const vdb_fr* lookup_dev, uint64_t n_cells, uint32_t k, uint32_t minimum_rows, uint64_t col_lo, uint64_t col_hi,
-                                const vdb_fr* blind_dev, uint32_t n_blind, vdb_colsrc* out_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(out_dev && (lookup_dev || n_cells == 0) && k <= 28 && col_lo <= col_hi && minimum_rows < (1u << k), "bad argument");
-  const uint64_t max_rows = (1ull << k) - minimum_rows;
-  std::vector<vdb_colsrc> h(col_hi - col_lo);
-  for (uint64_t c = col_lo; c < col_hi; c++) {
-    const uint64_t start = c * max_rows;
-    h[c - col_lo].src = lookup_dev + (start < n_cells ? start : 0);
-    h[c - col_lo].len = start < n_cells ? (n_cells - start < max_rows ? n_cells - start : max_rows) : 0;
-    VDB_ARG(!blind_dev || h[c - col_lo].len + n_blind <= (1ull << k), "a column's cells reach into its blinding rows");
-    h[c - col_lo].blind = blind_dev ? blind_dev + c * n_blind : nullptr;
-  }
-  if (!h.empty()) VDB_HIP(hipMemcpyAsync(out_dev, h.data(), h.size() * sizeof(vdb_colsrc), hipMemcpyHostToDevice, ctx().stream));
-  VDB_HIP(hipStreamSynchronize(ctx().stream));
-  return VDB_OK;
-}
-int vdb_layout_lookup_dev(const vdb_fr* lookup_dev, uint64_t n_cells, uint32_t k, uint32_t minimum_rows, vdb_fr* cols_dev, uint64_t n_cols,
-                          const vdb_fr* blind_dev, uint32_t n_blind) {
-  VDB_ARG(n_cols * ((((uint64_t)1 << k)) - minimum_rows) >= n_cells, "not enough lookup columns");
-  return vdb_layout_lookup_range_dev(lookup_dev, n_cells, k, minimum_rows, 0, n_cols, cols_dev, blind_dev, n_blind);
-}
-int vdb_layout_lookup_range_dev(const vdb_fr* lookup_dev, uint64_t n_cells, uint32_t k, uint32_t minimum_rows, uint64_t col_lo, uint64_t col_hi,
-                                vdb_fr* cols_dev, const vdb_fr* blind_dev, uint32_t n_blind) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(cols_dev && (lookup_dev || n_cells == 0) && k <= 28 && col_lo <= col_hi, "bad argument");
-  uint64_t max_rows = ((uint64_t)1 << k) - minimum_rows;
-  const uint64_t n_cols = col_hi - col_lo;
-  if (n_cols == 0) return VDB_OK;
-  uint64_t total = n_cols << k;
-  VDB_LAUNCH(k_layout_lookup, dim3((unsigned)((total + 255) / 256)), dim3(256), as_u256(lookup_dev), n_cells, max_rows, k, n_cols, as_u256(cols_dev),
-             blind_dev ? as_u256(blind_dev) : nullptr, n_blind, col_lo);
-  return VDB_OK;
-}
-int vdb_layout_const_mask_dev(const uint8_t* flags_dev, uint64_t n_cells, const uint64_t* break_points, uint64_t n_bp, uint32_t k, uint8_t* mask_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(flags_dev && mask_dev && (break_points || n_bp == 0) && k <= 28, "bad argument");
-  const uint64_t rows = 1ull << k;
-  uint64_t *dbp, *dst;
-  TRY(upload_break_points(break_points, n_bp, &dbp, &dst));
-  uint64_t total = (n_bp + 1) * rows;
-  VDB_LAUNCH(k_layout_const_mask, dim3((unsigned)((total + 255) / 256)), dim3(256), flags_dev, n_cells, dst, dbp, n_bp, k, mask_dev);
-  VDB_HIP(hipStreamSynchronize(ctx().stream));
-  return VDB_OK;
-}
-int vdb_layout_selectors_dev(const uint8_t* flags_dev, uint64_t n_cells, const uint64_t* break_points, uint64_t n_bp, uint32_t k, vdb_fr* q_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(flags_dev && q_dev && (break_points || n_bp == 0) && k <= 28, "bad argument");
-  const uint64_t rows = 1ull << k;
-  uint64_t *dbp, *dst;
-  TRY(upload_break_points(break_points, n_bp, &dbp, &dst));
-  uint64_t total = (n_bp + 1) * rows;
-  VDB_LAUNCH(k_layout_selectors, dim3((unsigned)((total + 255) / 256)), dim3(256), flags_dev, n_cells, dst, dbp, n_bp, k, as_u256(q_dev));
-  VDB_HIP(hipStreamSynchronize(ctx().stream));
-  return VDB_OK;
-}
-int vdb_mask_select_dev(const vdb_fr* in_dev, const uint8_t* mask_dev, uint64_t n, int keep_const, vdb_fr* out_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(in_dev && mask_dev && out_dev, "null pointer");
-  if (n == 0) return VDB_OK;
-  VDB_LAUNCH(k_mask_select, dim3((unsigned)((n + 255) / 256)), dim3(256), as_u256(in_dev), mask_dev, n, keep_const, as_u256(out_dev));
-  return VDB_OK;
-}
-int vdb_layout_columns(const vdb_fr* stream, uint64_t n_cells, const uint64_t* break_points, uint64_t n_bp, const vdb_fr* lookup, uint64_t n_lookup,
-                       uint32_t k, uint32_t minimum_rows, vdb_fr* advice_cols_out, vdb_fr* lookup_cols_out, uint64_t n_lookup_cols) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(stream && advice_cols_out, "null pointer");
-  const uint64_t rows = 1ull << k;
-  DevBuf ds, dc, dl, dlc;
-  TRY(upload(ds, stream, n_cells * sizeof(u256)));
-  TRY(dc.alloc((n_bp + 1) * rows * sizeof(u256)));
-  TRY(vdb_layout_columns_dev(ds.as<vdb_fr>(), n_cells, break_points, n_bp, k, dc.as<vdb_fr>(), nullptr, 0));
-  TRY(download(advice_cols_out, dc.p, (n_bp + 1) * rows * sizeof(u256)));
-  if (lookup_cols_out && n_lookup_cols) {
-    TRY(upload(dl, lookup, n_lookup * sizeof(u256)));
-    TRY(dlc.alloc(n_lookup_cols * rows * sizeof(u256)));
-    TRY(vdb_layout_lookup_dev(dl.as<vdb_fr>(), n_lookup, k, minimum_rows, dlc.as<vdb_fr>(), n_lookup_cols, nullptr, 0));
-    TRY(download(lookup_cols_out, dlc.p, n_lookup_cols * rows * sizeof(u256)));
-  }
-  VDB_HIP(hipStreamSynchronize(ctx().stream));
-  return VDB_OK;
 }
 
 }  // extern "C"

@@ -206,3 +206,34 @@ def test_poseidon_sweep_of_message_lengths_and_tree_sizes(api, O):
         dim = int(rng.integers(1, 12))
         v = O.random_fr(rng, n * dim).reshape(n, dim, 4)
         assert np.array_equal(api.poseidon_merkle_root(v), O.poseidon_merkle_root(v)), (n, dim)
+
+
+def test_merkle_root_comes_from_the_resident_tree_builder(api, O):
+    """vdb_poseidon_merkle_root runs the builder of the resident tree.  Where one builder can differ from another — a tree of one leaf
+    (its root is the leaf digest), padding leaves, odd and even vector widths (the even ones end in the padding-only permutation) — the
+    root is the oracle's and is entry 2 lp - 2 of vdb_merkle_tree_build_dev's levels (entry 0 when n = 1).  The call works in scratch
+    slots 0 and 1 only: it goes through while a deferred MSM holds slot 2, and that MSM still returns the commitment of its column"""
+    rng = np.random.default_rng(8128)
+    for n in (1, 2, 3, 5, 8):
+        for dim in (1, 2, 3, 4):
+            v = O.random_fr(rng, n * dim).reshape(n, dim, 4)
+            root, levels = api.poseidon_merkle_root(v), api.merkle_tree_build(v)
+            lp, _ = api.merkle_levels(n)
+            assert np.array_equal(root, O.poseidon_merkle_root(v)), (n, dim)
+            assert np.array_equal(root, levels[2 * lp - 2 if n > 1 else 0]), (n, dim)
+    k, lib = 9, api.init()
+    g, gl = O.srs_from_tau(k, 0x9E3779B9)
+    col = O.random_fr(rng, 1 << k).reshape(1, 1 << k, 4)
+    srs, d_col = api.Srs(k, g, gl), api.DeviceBuffer(col.nbytes)
+    point = np.zeros((1, 8), dtype=np.uint64)
+    try:
+        d_col.upload(col)
+        api.check(lib.vdb_msm_batch_masked_dev_begin(srs.h, 1, d_col.ptr, 1, 1 << k, None, None))
+        between = api.poseidon_merkle_root(v)
+        api.check(lib.vdb_msm_batch_end(api._p(point), 1))
+    finally:
+        lib.vdb_msm_batch_end(None, 0)
+        d_col.free()
+        srs.free()
+    assert np.array_equal(between, root)
+    assert np.array_equal(point, O.msm_batch(col, gl, threads=4))
