@@ -589,6 +589,67 @@ def ann_index_apply(index, cluster, grow, updated_levels, new_vectors, indices, 
             b.free()
 
 
+def wit_ann_delete(levels, roots, cluster, n_c, dim, slots, selectors=False):
+    """m deletes from cluster `cluster` of a committed index (vdb_wit_ann_delete), the streams alone: `levels` cluster c's tree over its
+    n_c members (merkle_tree_build's array), `roots` (K + 1, 4): [centroids' root | cluster roots], slots (m,): slot j is below the fill
+    at its turn (n_c - j); the last member moves into it.  dict(stream, selectors, flags, input_cells, update_base, shrink_base, shrink,
+    public (4 m + 3, 4): [index_root_old | c | slot, removed leaf, last, moved leaf per delete | index_root_new], levels: the cluster's
+    tree after the batch, at its old size)"""
+    lib = _lib.init()
+    roots = _fr(roots)
+    levels = np.array(levels, dtype=np.uint64, copy=True)
+    idx = np.ascontiguousarray(slots, dtype=np.uint64)
+    m, K = idx.shape[0], roots.shape[0] - 1
+    assert idx.shape == (m,) and levels.shape == (2 * merkle_levels(n_c)[0], 4)
+    cells, n_in, ub, sb, s = _u64(), _u64(), _u64(), _u64(), ctypes.c_uint()
+    check(lib.vdb_wit_ann_delete_size(_sz(K), _sz(n_c), _sz(dim), _sz(m), ctypes.byref(cells), ctypes.byref(n_in), ctypes.byref(ub), ctypes.byref(sb),
+                                      ctypes.byref(s)))
+    stream = np.zeros((cells.value, 4), dtype=np.uint64)
+    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
+    pub = np.zeros((4 * m + 3, 4), dtype=np.uint64)
+    check(lib.vdb_wit_ann_delete(_p(levels), _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(dim), _p(idx), _sz(m), _p(stream),
+                                 _p(sel) if selectors else None, _p(pub)))
+    return dict(stream=stream, **_split_flags(sel), input_cells=n_in.value, update_base=ub.value, shrink_base=sb.value, shrink=s.value, public=pub,
+                levels=levels)
+
+
+def ann_index_remove_layout(sizes, cluster, slots):
+    """(halvings of the cluster's tree, digests of the forest after the batch, its K + 2 segment offsets) of vdb_ann_index_remove_dev
+    (vdb_ann_index_remove_size; VdbError on a slot at or above the fill at its turn, or a batch that would empty the cluster)"""
+    lib = _lib.init()
+    sizes, idx = np.ascontiguousarray(sizes, dtype=np.uint64), np.ascontiguousarray(slots, dtype=np.uint64)
+    K = sizes.shape[0]
+    s, digests, seg = ctypes.c_uint(), _u64(), np.zeros(K + 2, dtype=np.uint64)
+    check(lib.vdb_ann_index_remove_size(_p(sizes), _sz(K), _sz(cluster), _p(idx), _sz(idx.shape[0]), ctypes.byref(s), ctypes.byref(digests), _p(seg)))
+    return s.value, digests.value, seg
+
+
+def ann_index_remove(index, cluster, updated_levels, slots):
+    """the index after a batch of deletes from one cluster (vdb_ann_index_remove_dev), host arrays in and out: `index` an ann_index_build
+    dict, updated_levels the cluster's tree the witness call left (at its old size) -> a dict of the same form over the compacted
+    database: its slots are 0 .. n - m - 1"""
+    lib = _lib.init()
+    updated = _fr(updated_levels)
+    idx = np.ascontiguousarray(slots, dtype=np.uint64)
+    sizes = np.diff(np.asarray(index["offsets"], dtype=np.uint64)).astype(np.uint64)
+    K, dim, n, m = sizes.shape[0], index["grouped"].shape[1], index["grouped"].shape[0], idx.shape[0]
+    _, digests, seg = ann_index_remove_layout(sizes, cluster, idx)
+    n2 = n - m
+    src = [index["grouped"], index["forest"], index["roots"], updated]
+    ins = [DeviceBuffer(max(a.nbytes, 32)) for a in src]
+    outs = [DeviceBuffer(max(b, 32)) for b in (n2 * dim * 32, n2 * 4, (K + 1) * 8, digests * 32, (K + 2) * 32)]
+    try:
+        for b, a in zip(ins, src):
+            b.upload(np.ascontiguousarray(a))
+        check(lib.vdb_ann_index_remove_dev(ins[0].ptr, ins[1].ptr, ins[2].ptr, _p(sizes), _sz(K), _sz(dim), _sz(cluster), ins[3].ptr, _p(idx), _sz(m),
+                                           *[o.ptr for o in outs]))
+        return dict(grouped=outs[0].download((n2, dim, 4)), slots=outs[1].download((n2,), dtype=np.uint32), offsets=outs[2].download((K + 1,), dtype=np.uint64),
+                    forest=outs[3].download((digests, 4)), segments=seg, roots=outs[4].download((K + 2, 4)))
+    finally:
+        for b in ins + outs:
+            b.free()
+
+
 def wit_merkle_open(levels, n, indices, vectors=None, selectors=False):
     """m openings (vdb_wit_merkle_open) of the tree `levels` (merkle_tree_build's array over n vectors, or what a batch of updates left):
     slot indices[j] is read.  `vectors` (m, dim, 4): the vectors read (vector mode); None: leaf mode, any slot of the padded tree.

@@ -1122,7 +1122,7 @@ def _place_path(B, perm, lay, levels_at, bits, sibs, curs):
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # Merkle path updates (include/vdb.h vdb_wit_merkle_update; pipeline.UpdateHotPath)
-def merkle_update_layout(m, dim, depth, kinds=None, grow=0):
+def merkle_update_layout(m, dim, depth, kinds=None, grow=0, carried=False):
     """where the cells of a batch of m path updates lie: dict(nperm, n_ins, sizes, leaf_cells, node_cells, level_cells, ip_cells,
     per_update, n_vec, old_leaf, bits, sibs, n_in, total) — the last five stream cells: [new vectors | old leaves | bits | siblings],
     then update j's block at n_in + j * per_update: its leaf sponge, per level [assert_bit 4 | select lo 8 | select ro 8 | H old |
@@ -1132,11 +1132,12 @@ def merkle_update_layout(m, dim, depth, kinds=None, grow=0):
     H(Z_l, Z_l) | grow hashes R_{i+1} = H(R_i, Z_{d+i})] behind the assigned witnesses (`depth` is the grown one, d = depth - grow).
     Further keys: kinds, grow, w, write_no (per update: its row among the new vectors, -1 for a delete), r0 and z0 (cells; None when
     grow = 0), grow_cells, block and levels_at (per update: its first cell, the first cell of its level 0); per_update is the size of
-    a write's block."""
+    a write's block.  `carried` admits kind 2 (the index delete's move, ann_delete_layout): a carried leaf, ONE unflagged witness cell
+    where a delete has its constant 0."""
     kinds = [0] * m if kinds is None else [int(k) for k in kinds]
     if m < 1 or depth < 1 or dim < 1:
         raise ValueError("a batch holds at least one update of a tree with at least two leaves")
-    if len(kinds) != m or not set(kinds) <= {0, 1} or grow < 0 or grow > depth:
+    if len(kinds) != m or not set(kinds) <= ({0, 1, 2} if carried else {0, 1}) or grow < 0 or grow > depth:
         raise ValueError("one kind (0 write, 1 delete) per update, and no more doublings than the grown tree has levels")
     lay = _path_layout(dim, depth, 2)
     w = kinds.count(0)
@@ -1152,7 +1153,7 @@ def merkle_update_layout(m, dim, depth, kinds=None, grow=0):
         at += 1 if k else lay["leaf_cells"]
         lay["levels_at"].append(at)
         lay["write_no"].append(-1 if k else wn)
-        wn += 1 - k
+        wn += k == 0
         at += depth * lay["level_cells"] + lay["ip_cells"]
     lay["total"] = at
     return lay
@@ -1287,8 +1288,8 @@ def _trace_update_block(t, lay, base):
         assert at == base + lay["block"][0]
     for j in range(m):
         if lay["kinds"][j]:
-            cur_new = base + lay["block"][j]
-            at = t.put(cur_new, [("k", 0)], [0])             # new_leaf = ctx.load_constant(0)
+            cur_new = base + lay["block"][j]                 # new_leaf = ctx.load_constant(0), or the carried leaf: ctx.load_witness
+            at = t.put(cur_new, [("k", 0) if lay["kinds"][j] == 1 else None], [0])
         else:
             cur_new, at = t.leaf(base + lay["block"][j], lay, base + lay["write_no"][j] * dim)
         assert at == base + lay["levels_at"][j]
@@ -1318,12 +1319,13 @@ def trace_merkle_update(m, dim, depth, fetch_flags, fetch_values, kinds=None, gr
     return t.finish(), public
 
 
-def place_merkle_update(B, m, dim, depth, fetch_flags, fetch_values, base=0, kinds=None, grow=0):
+def place_merkle_update(B, m, dim, depth, fetch_flags, fetch_values, base=0, kinds=None, grow=0, carried=False):
     """trace_merkle_update's cells placed into builder `B` from stream cell `base` on, from unit blocks — one per kind of permutation,
     the bit with its two selects, the two selects of the new path, the index inner product — each placed for all m updates at once, level
     after level; the growth block's hashes one after the other, the constants (Z_0, each delete's 0) as fixed-column cells.
+    A carried leaf (kind 2, `carried`) is one unflagged witness cell: nothing is placed for it.
     -> the public cells [old root | idx, old leaf, new leaf per update | new root]"""
-    lay = merkle_update_layout(m, dim, depth, kinds, grow)
+    lay = merkle_update_layout(m, dim, depth, kinds, grow, carried)
     j = np.arange(m, dtype=np.int64)
     blocks = base + np.asarray(lay["block"], dtype=np.int64)
     perm = _perm_placer(B, fetch_flags, fetch_values)
@@ -1341,7 +1343,7 @@ def place_merkle_update(B, m, dim, depth, fetch_flags, fetch_values, base=0, kin
 
     is_write = np.asarray(lay["kinds"], dtype=np.int64) == 0
     new_leaf = blocks.copy()                                 # a delete: its block starts with new_leaf = ctx.load_constant(0)
-    for c in blocks[~is_write]:
+    for c in blocks[np.asarray(lay["kinds"], dtype=np.int64) == 1]:
         B.constant_cell(int(c), 0)
     if lay["w"]:
         word0 = base + np.arange(lay["w"], dtype=np.int64) * dim
@@ -1463,6 +1465,163 @@ def build_ann_update(K, m, dim, depth, fetch_flags, fetch_values, builder=None, 
     info = dict(indicators=[int(i) for i in inds], picked=picked, old_root=upub[0], new_root=upub[-1], outs=[int(o) for o in outs], index_root_old=root_old,
                 index_root_new=root_new, layout=lay)
     return B.finish(), ann_update_instances(root_old, c, upub, root_new), info
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Deletes against the index root (include/vdb.h vdb_wit_ann_delete; pipeline.AnnDeleteHotPath)
+def ann_delete_shrink(n_c, m):
+    """(depth of the cluster's tree over n_c members, the halvings s after m deletes: lp >> s is the power of two >= n_c - m)"""
+    if not 1 <= m < n_c:
+        raise ValueError("a batch holds at least one delete and leaves at least one member")
+    depth = (n_c - 1).bit_length()
+    return depth, depth - (n_c - m - 1).bit_length()
+
+
+def ann_delete_layout(K, m, dim, depth, shrink=0):
+    """where the blocks of the index delete circuit start: ann_update_layout's keys (update_layout: merkle_update_layout of block E' over
+    the 2 m path updates [carried, delete] * m) and `shrink`: the first cell of block S [S_0 | Z_0 | Z hashes depth - 1 | S hashes s]
+    between E' and F, shrink_cells (0 when the tree keeps its size), s"""
+    if K < 1:
+        raise ValueError("an index has at least one cluster")
+    if m < 1 or not 0 <= shrink <= depth:
+        raise ValueError("at least one delete, and no more halvings than the tree has levels")
+    upd, sp = merkle_update_layout(2 * m, dim, depth, [2, 1] * m, 0, carried=True), merkle_leaf_layout(K + 1)
+    lay = dict(c=0, centroids_root=1, roots=2, n_in=K + 2, indicator=K + 2, update_layout=upd, sponge=sp, s=shrink)
+    lay["select"] = lay["indicator"] + 8 + 12 * (K - 1)
+    lay["sponge_old"] = lay["select"] + 1 + 3 * K
+    lay["update"] = lay["sponge_old"] + sp["leaf_cells"]
+    lay["shrink"] = lay["update"] + upd["total"]
+    lay["shrink_cells"] = 2 + (depth - 1 + shrink) * upd["node_cells"] if shrink else 0
+    lay["new_roots"] = lay["shrink"] + lay["shrink_cells"]
+    lay["sponge_new"] = lay["new_roots"] + 8 * K
+    lay["total"] = lay["sponge_new"] + sp["leaf_cells"]
+    return lay
+
+
+def ann_delete_instances(index_root_old, c, update_public, index_root_new):
+    """the public cells in make_public order: [index_root_old | c | slot, removed leaf, last, moved leaf per delete | index_root_new] from
+    the update block's [old root | idx, old leaf, new leaf per path update | new root]: delete j is updates 2 j and 2 j + 1"""
+    u, out = update_public, [int(index_root_old), int(c)]
+    for j in range((len(u) - 2) // 6):
+        out += [int(u[1 + 6 * j]), int(u[2 + 6 * j]), int(u[4 + 6 * j]), int(u[3 + 6 * j])]
+    return out + [int(index_root_new)]
+
+
+def _delete_info(lay, m, upub, s0, top):
+    """what both forms report about E' and S: carried (the carried-leaf cell of each delete), moved_old (the old-leaf cell it is tied
+    to), s0, shrink_top (S_s), z0"""
+    u, base = lay["update_layout"], lay["update"]
+    return dict(carried=[base + u["block"][2 * j] for j in range(m)], moved_old=[base + u["old_leaf"] + 2 * j + 1 for j in range(m)], s0=s0, shrink_top=top,
+                z0=lay["shrink"] + 1 if lay["s"] else None, old_root=upub[0], new_root=upub[-1])
+
+
+def trace_ann_delete(K, m, dim, depth, fetch_flags, fetch_values, shrink=0):
+    """The closure of m deletes from one cluster of a committed index cell by cell (the ground truth of build_ann_delete): blocks A - D
+    of trace_ann_update, the update block over 2 m path updates (a carried leaf into slot_j, then the last slot emptied), the carried
+    cell tied to the old leaf of the update behind it, block S when the tree halves (its top tied to the update block's final root), F
+    over the new cluster root (S_0, or the final root when nothing shrinks) and G.
+    -> (CopyMap, public cells, dict(indicators, picked, old_root, new_root, outs, index_root_old, index_root_new, carried, moved_old, s0,
+    shrink_top, z0, layout))"""
+    lay = ann_delete_layout(K, m, dim, depth, shrink)
+    t = _CellTrace(lay["total"], fetch_flags, fetch_values)
+    c, roots = lay["c"], [lay["roots"] + j for j in range(K)]
+    inds = [t.is_zero(lay["indicator"], c)]
+    for j in range(1, K):
+        at = _indicator_at(lay, j)
+        t.put(at, [None, ("k", j), ("k", 1), ("c", c)], [1, 0, 0, 0])
+        inds.append(t.is_zero(at + 4, at))
+    cells, gates = [("k", 0)], [1]
+    for j in range(K):
+        cells += [("c", roots[j]), ("c", inds[j]), None]
+        gates += [0, 0, j + 1 < K]
+    picked = t.put(lay["select"], cells, gates) - 1
+    root_old, at = t.leaf(lay["sponge_old"], lay["sponge"], None, [lay["centroids_root"]] + roots)
+    assert at == lay["update"]
+    upub = _trace_update_block(t, lay["update_layout"], lay["update"])
+    t.copy_of[upub[0]] = picked                              # ctx.constrain_equal(picked, the update block's old root)
+    s0, top = None, None
+    info = _delete_info(lay, m, upub, None, None)
+    for a, b in zip(info["carried"], info["moved_old"]):
+        t.copy_of[a] = b                                     # the move: what left the last slot is what arrived
+    new_root = upub[-1]
+    if shrink:
+        s0 = top = lay["shrink"]                             # S_0 = ctx.load_witness, Z_0 = ctx.load_constant(0)
+        at = t.put(s0 + 1, [("k", 0)], [0])
+        z = [s0 + 1]
+        for l in range(depth - 1):
+            z.append(t.node(at, z[l], z[l]))
+            at += lay["update_layout"]["node_cells"]
+        for i in range(shrink):
+            top = t.node(at, top, z[depth - shrink + i])
+            at += lay["update_layout"]["node_cells"]
+        assert at == lay["new_roots"]
+        t.copy_of[top] = upub[-1]                            # ctx.constrain_equal(S_s, the update block's final root)
+        new_root = s0
+    outs = [t.select(lay["new_roots"] + 8 * j, new_root, roots[j], inds[j]) for j in range(K)]
+    root_new, at = t.leaf(lay["sponge_new"], lay["sponge"], None, [lay["centroids_root"]] + outs)
+    assert at == lay["total"]
+    info = dict(_delete_info(lay, m, upub, s0, top), indicators=inds, picked=picked, outs=outs, index_root_old=root_old, index_root_new=root_new, layout=lay)
+    return t.finish(), ann_delete_instances(root_old, c, upub, root_new), info
+
+
+def build_ann_delete(K, m, dim, depth, fetch_flags, fetch_values, builder=None, shrink=0):
+    """trace_ann_delete's map assembled from unit blocks, as build_ann_update: the update block is place_merkle_update at its base with
+    the carried kind, block S's hashes are placed one after the other (`builder`: as build_kmeans).  -> as trace_ann_delete"""
+    lay = ann_delete_layout(K, m, dim, depth, shrink)
+    if np.asarray(fetch_flags(0, lay["n_in"])).any():
+        raise ValueError("the assigned header carries no gate or constant flag")
+    B = (builder or _Builder)(lay["total"], 0)
+    c, roots = lay["c"], lay["roots"] + np.arange(K, dtype=np.int64)
+    s = Sym(0, 0)
+    iz = Block(s, [s.g_is_zero(ext(0))])
+    inds = [int(B.place(iz, [lay["indicator"]], [0], [[c]])[0, 0])]
+    if K > 1:
+        s = Sym(0, 0)
+        d = s.push(None, True)
+        s.push(None); s.push(C(1)); s.push(ext(0))
+        ie = Block(s, [s.g_is_zero(d)])
+        at = np.asarray([_indicator_at(lay, j) for j in range(1, K)], dtype=np.int64)
+        inds += [int(x) for x in B.place(ie, at, np.zeros(K - 1, dtype=np.int64), np.full((K - 1, 1), c, dtype=np.int64))[:, 0]]
+        for j in range(1, K):
+            B.constant_cell(int(at[j - 1]) + 1, j)
+    inds = np.asarray(inds, dtype=np.int64)
+    s = Sym(0, 0)
+    sb = Block(s, [s.g_select_by_indicator([ext(i) for i in range(K)], [ext(K + i) for i in range(K)])])
+    picked = int(B.place(sb, [lay["select"]], [0], np.concatenate([roots, inds])[None, :])[0, 0])
+    root_old, end = place_sponge(B, lay["sponge_old"], [lay["centroids_root"]] + [int(r) for r in roots], fetch_flags, fetch_values)
+    assert end == lay["update"]
+    upub = place_merkle_update(B, 2 * m, dim, depth, fetch_flags, fetch_values, lay["update"], [2, 1] * m, 0, carried=True)
+    B.tie(upub[0], picked)                                   # ctx.constrain_equal(picked, the update block's old root)
+    info = _delete_info(lay, m, upub, None, None)
+    for a, b in zip(info["carried"], info["moved_old"]):
+        B.tie(a, b)                                          # the move: what left the last slot is what arrived
+    s0, top, new_root = None, None, upub[-1]
+    if shrink:
+        one = lambda x: np.asarray([x], dtype=np.int64)
+        perm = _perm_placer(B, fetch_flags, fetch_values)
+        s0 = lay["shrink"]
+        B.constant_cell(s0 + 1, 0)                           # Z_0 = ctx.load_constant(0)
+        z, top, at = [one(s0 + 1)], one(s0), s0 + 2
+        for l in range(depth - 1):
+            z.append(_node(perm, one(at), z[l], z[l]))
+            at += lay["update_layout"]["node_cells"]
+        for i in range(shrink):
+            top = _node(perm, one(at), top, z[depth - shrink + i])
+            at += lay["update_layout"]["node_cells"]
+        assert at == lay["new_roots"]
+        top = int(top[0])
+        B.tie(top, upub[-1])                                 # ctx.constrain_equal(S_s, the update block's final root)
+        new_root = s0
+    s = Sym(0, 0)
+    sl = Block(s, [s.g_select(ext(0), ext(1), ext(2))])
+    outs = B.place(sl, lay["new_roots"] + 8 * np.arange(K, dtype=np.int64), np.zeros(K, dtype=np.int64),
+                   np.stack([np.full(K, new_root, dtype=np.int64), roots, inds], axis=1))[:, 0]
+    root_new, end = place_sponge(B, lay["sponge_new"], [lay["centroids_root"]] + [int(o) for o in outs], fetch_flags, fetch_values)
+    if end != lay["total"]:
+        raise ValueError("the trace does not end where the circuit does")
+    info = dict(_delete_info(lay, m, upub, s0, top), indicators=[int(i) for i in inds], picked=picked, outs=[int(o) for o in outs], index_root_old=root_old,
+                index_root_new=root_new, layout=lay)
+    return B.finish(), ann_delete_instances(root_old, c, upub, root_new), info
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -90,4 +90,107 @@ static inline int annu_apply_plan(const uint64_t* sizes, size_t K, size_t c, uns
   return 0;
 }
 
+// ------------------------------------------------------------------ deletes (include/vdb.h vdb_wit_ann_delete, vdb_ann_index_remove_dev)
+// A delete of slot i moves the last member into i and empties the last slot, so the members stay dense: delete j of a batch is two
+// path updates, 2 j at slot_j with the CARRIED leaf (the one at fill - 1 at that turn) and 2 j + 1 at fill - 1, a plain delete.  In a
+// delete-only batch every leaf of the cluster is an original leaf or 0, so where a leaf came from is tracked without a value:
+// origin[p] = the slot that held, before the batch, what position p holds now.  Only positions a delete wrote differ from p itself
+// (at most m of them): they are kept as a short list, latest first wins.
+struct AnndPlan {
+  std::vector<uint64_t> indices;      // 2 m: the path updates' slots
+  std::vector<uint8_t> kinds;         // 2 m: 2 (carried), 1 (delete), alternating
+  std::vector<uint32_t> carry_src;    // 2 m: for update 2 j the slot whose leaf, as the tree stood before the batch, it carries
+  std::vector<uint64_t> move_pos, move_src;   // the surviving positions p < n_c - m whose member is not the original one: p, origin[p]
+  uint64_t lp, lp_new;                // padded leaf counts before and after: lp_new = lp >> shrink is the power of two >= n_c - m
+  uint32_t depth, shrink;
+};
+// -> 0; 1: m == 0 or 2 m above max_updates; 2: m >= n_c (an emptied cluster is refused, as the build refuses one);
+// 3: slots[*bad] is at or above the fill at its turn
+static inline int annd_expand(const uint64_t* slots, size_t m, uint64_t n_c, size_t max_updates, AnndPlan* p, size_t* bad) {
+  if (m == 0 || m > max_updates / 2) return 1;
+  if (m >= n_c) return 2;
+  tree_shape(n_c, &p->lp, &p->depth);
+  uint32_t d_new;
+  tree_shape(n_c - m, &p->lp_new, &d_new);
+  p->shrink = p->depth - d_new;
+  p->indices.assign(2 * m, 0);
+  p->kinds.assign(2 * m, 1);
+  p->carry_src.assign(2 * m, 0);
+  std::vector<uint64_t> w_pos, w_src;   // the writes so far, in order: position, origin
+  auto origin = [&](uint64_t pos) {
+    for (size_t i = w_pos.size(); i-- > 0;)
+      if (w_pos[i] == pos) return w_src[i];
+    return pos;
+  };
+  for (size_t j = 0; j < m; j++) {
+    const uint64_t fill = n_c - j, last = fill - 1;
+    if (slots[j] >= fill) {
+      if (bad) *bad = j;
+      return 3;
+    }
+    const uint64_t src = origin(last);
+    p->indices[2 * j] = slots[j];
+    p->kinds[2 * j] = 2;
+    p->carry_src[2 * j] = (uint32_t)src;
+    p->indices[2 * j + 1] = last;
+    w_pos.push_back(slots[j]);
+    w_src.push_back(src);
+  }
+  p->move_pos.clear();
+  p->move_src.clear();
+  for (size_t i = w_pos.size(); i-- > 0;) {
+    const uint64_t pos = w_pos[i];
+    if (pos >= n_c - m || w_src[i] == pos) continue;
+    bool later = false;
+    for (size_t k = i + 1; k < w_pos.size() && !later; k++) later = w_pos[k] == pos;
+    if (later) continue;
+    p->move_pos.push_back(pos);
+    p->move_src.push_back(w_src[i]);
+  }
+  return 0;
+}
+// cells of block S, the proof that the dropped half is empty: [S_0 | Z_0 | Z_{l+1} = H(Z_l, Z_l), l < d - 1 | S_{i+1} = H(S_i, Z_{d-s+i}),
+// i < s]; nothing when the tree keeps its size
+static inline uint64_t annd_shrink_cells(uint32_t depth, uint32_t shrink, uint64_t node_cells) {
+  return shrink ? 2 + (uint64_t)(depth - 1 + shrink) * node_cells : 0;
+}
+// the blocks of the delete circuit: annu_blocks with block S between the update block E' and F (b_shr; b_new is F, as there)
+struct AnndBlocks {
+  AnnuBlocks b;
+  uint64_t b_shr;
+};
+static inline AnndBlocks annd_blocks(uint64_t K, uint64_t sponge_cells, uint64_t update_cells, uint64_t shrink_cells) {
+  AnndBlocks o;
+  o.b = annu_blocks(K, sponge_cells, update_cells + shrink_cells);
+  o.b_shr = o.b.b_upd + update_cells;
+  return o;
+}
+// The index after m deletes from cluster c: the K + 1 row offsets and the K + 2 segment offsets of the forest, cluster c's tree cut
+// to lp_new leaves.  delta: digests by which the segments behind c move down.  -> 0; 1: an empty cluster
+struct AnndRemovePlan {
+  std::vector<uint64_t> offsets, seg_off;
+  uint64_t n_new, off_c, keep_c, delta;   // keep_c = n_c - m, the rows of cluster c that stay
+};
+static inline int annd_remove_plan(const uint64_t* sizes, size_t K, size_t c, uint64_t m, uint64_t lp, uint64_t lp_new, AnndRemovePlan* p) {
+  p->offsets.assign(K + 1, 0);
+  p->seg_off.assign(K + 2, 0);
+  for (size_t s = 0; s <= K; s++) {
+    const uint64_t old_sz = s < K ? sizes[s] : K;
+    if (old_sz == 0) return 1;
+    uint64_t l;
+    uint32_t d;
+    tree_shape(old_sz, &l, &d);
+    if (s == c) {
+      l = lp_new;
+      p->off_c = p->offsets[s];
+      p->keep_c = old_sz - m;
+    }
+    if (s < K) p->offsets[s + 1] = p->offsets[s] + (s == c ? old_sz - m : old_sz);
+    p->seg_off[s + 1] = p->seg_off[s] + 2 * l;
+  }
+  p->n_new = p->offsets[K];
+  p->delta = 2 * (lp - lp_new);
+  return 0;
+}
+
 }  // namespace vdb

@@ -378,6 +378,112 @@ int ann_index_apply_dev(const u256* grouped, const uint32_t* slots, const u256* 
   return VDB_OK;
 }
 
+// ------------------------------------------------------------------ the index after a batch of deletes (include/vdb.h
+// vdb_ann_index_remove_dev; the batch's circuit is witness.hip's).  Values only; the old buffers are only read.
+// A removal compacts the database: the result is the fresh build over its own grouped rows taken as the database, so every grouped
+// row's slot is its own place.  One lane per word of the new grouped rows, then per slot entry: rows in front of cluster c stay, its
+// surviving position p holds the original member origin[p] (p itself unless the move table says otherwise: at most m entries, scanned
+// per lane), later rows move down by m
+__global__ __launch_bounds__(256) void k_ann_rows_remove(const u256* __restrict__ grouped, const uint32_t* __restrict__ move_pos,
+                                                         const uint32_t* __restrict__ move_src, uint32_t n_move, uint64_t off_c, uint64_t keep_c,
+                                                         uint64_t m, uint64_t n_new, uint32_t D, u256* __restrict__ grouped_out,
+                                                         uint32_t* __restrict__ slots_out) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x, n_words = n_new * D;
+  if (t >= n_words + n_new) return;
+  if (t >= n_words) {
+    slots_out[t - n_words] = (uint32_t)(t - n_words);
+    return;
+  }
+  const uint64_t r = t / D;
+  const uint32_t wd = (uint32_t)(t % D);
+  uint64_t from = r < off_c + keep_c ? r : r + m;
+  if (r >= off_c && r < off_c + keep_c) {
+    const uint32_t p = (uint32_t)(r - off_c);
+    for (uint32_t i = 0; i < n_move; i++)
+      if (move_pos[i] == p) {
+        from = off_c + move_src[i];
+        break;
+      }
+  }
+  grouped_out[t] = grouped[from * D + wd];
+}
+// one lane per digest of the new forest: its segment by bisection in the new segment offsets; segment c is the updated tree cut to
+// lp_new leaves (level l of the cut tree is the prefix of level l of the old one, the unused last entry 0), every other segment comes
+// from where the old forest holds it (the segments behind c lie `delta` digests later there)
+__global__ __launch_bounds__(256) void k_ann_forest_cut(const u256* __restrict__ forest, const u256* __restrict__ updated, const uint64_t* __restrict__ seg_off,
+                                                        uint32_t n_seg, uint32_t c, uint64_t lp, uint64_t lp_new, uint64_t delta,
+                                                        u256* __restrict__ forest_out) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= seg_off[n_seg]) return;
+  uint32_t lo = 0, hi = n_seg;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (seg_off[mid] <= t) lo = mid; else hi = mid;
+  }
+  if (lo != c) {
+    forest_out[t] = forest[lo < c ? t : t + delta];
+    return;
+  }
+  uint64_t e = t - seg_off[lo], width = lp_new;
+  uint32_t l = 0;
+  while (width && e >= width) {
+    e -= width;
+    width >>= 1;
+    l++;
+  }
+  forest_out[t] = width ? updated[mku_level_off(lp, l) + e] : u256_zero();
+}
+// what the two remove entry points share: the batch against cluster c's fill and the offsets after it (VDB_ERR_ARG, nothing launched)
+static int ann_remove_plan(const uint64_t* sizes, size_t K, size_t dim, size_t cluster, const uint64_t* slots, size_t m, AnndPlan* dp, AnndRemovePlan* p) {
+  VDB_ARG(sizes && slots, "null pointer");
+  VDB_ARG(K > 0 && K <= VDB_ANN_MAX_CLUSTERS && cluster < K, "K = 0, K above VDB_ANN_MAX_CLUSTERS or cluster >= K");
+  VDB_ARG(dim > 0 && dim <= ((size_t)1 << 20), "dim outside [1, 2^20]");
+  VDB_ARG(sizes[cluster] <= VDB_ANN_MAX_VECTORS, "cluster too large");
+  const int rc = annd_expand(slots, m, sizes[cluster], MKU_MAX_UPDATES, dp, nullptr);
+  VDB_ARG(rc != 1, "a batch holds 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES / 2 deletes");
+  VDB_ARG(rc != 2, "the batch would empty the cluster");
+  VDB_ARG(rc == 0, "a slot at or above the cluster's fill at its turn");
+  VDB_ARG(annd_remove_plan(sizes, K, cluster, m, dp->lp, dp->lp_new, p) == 0, "empty cluster");
+  VDB_ARG(p->n_new + m <= VDB_ANN_MAX_VECTORS, "index too large: n at most VDB_ANN_MAX_VECTORS");
+  return VDB_OK;
+}
+int ann_index_remove_dev(const u256* grouped, const u256* forest, const u256* roots, const uint64_t* sizes, size_t K, size_t dim, size_t cluster,
+                         const u256* updated, const uint64_t* slots, size_t m, u256* grouped_out, uint32_t* slots_out, uint64_t* offsets_out,
+                         u256* forest_out, u256* roots_out) {
+  static thread_local AnndPlan dp;                // (pageable sources of asynchronous uploads: they outlive the call)
+  static thread_local AnndRemovePlan p;
+  static thread_local std::vector<uint32_t> tab;  // [move_pos | move_src]
+  TRY(ann_remove_plan(sizes, K, dim, cluster, slots, m, &dp, &p));
+  const PoseidonSpec* sp;
+  TRY(poseidon_spec_dev(&sp, nullptr));
+  hipStream_t s = ctx().stream;
+  MkShape mw;
+  mk_shape(1, K + 1, &mw);
+  const size_t n_move = dp.move_pos.size();
+  tab.resize(2 * n_move + 1);
+  for (size_t i = 0; i < n_move; i++) tab[i] = (uint32_t)dp.move_pos[i], tab[n_move + i] = (uint32_t)dp.move_src[i];
+  uint8_t* w = (uint8_t*)scratch_get(7, (K + 2) * 8 + (2 * n_move + 16) * 4);
+  if (!w) return VDB_ERR_OOM;
+  uint64_t* d_off = (uint64_t*)w;
+  uint32_t* d_move = (uint32_t*)(d_off + K + 2);
+  u256* states = (u256*)scratch_get(0, ((size_t)mw.nperm * PSD_T + 8) * sizeof(u256));
+  if (!states) return VDB_ERR_OOM;
+  VDB_HIP(hipMemcpyAsync(d_off, p.seg_off.data(), (K + 2) * 8, hipMemcpyHostToDevice, s));
+  if (n_move) VDB_HIP(hipMemcpyAsync(d_move, tab.data(), 2 * n_move * 4, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(offsets_out, p.offsets.data(), (K + 1) * 8, hipMemcpyHostToDevice, s));
+  const uint64_t lanes = p.n_new * dim + p.n_new;
+  VDB_LAUNCH(k_ann_rows_remove, dim3((unsigned)((lanes + 255) / 256)), dim3(256), grouped, d_move, d_move + n_move, (uint32_t)n_move, p.off_c, p.keep_c,
+             (uint64_t)m, p.n_new, (uint32_t)dim, grouped_out, slots_out);
+  VDB_LAUNCH(k_ann_forest_cut, dim3((unsigned)((p.seg_off[K + 1] + 255) / 256)), dim3(256), forest, updated, d_off, (uint32_t)(K + 1), (uint32_t)cluster,
+             dp.lp, dp.lp_new, p.delta, forest_out);
+  // the cut tree's root lies where level d - s of the old layout starts: k_ann_roots_apply reads it as the root of a one-leaf tree there
+  VDB_LAUNCH(k_ann_roots_apply, dim3((unsigned)(K / 64 + 1)), dim3(64), roots, updated + mku_level_off(dp.lp, dp.depth - dp.shrink), (uint64_t)1, (uint32_t)K,
+             (uint32_t)cluster, roots_out);
+  TRY(mk_leaf_states(sp, roots_out, 1u, (uint32_t)(K + 1), mw.nperm, states, roots_out + K + 1, nullptr));
+  VDB_HIP(hipStreamSynchronize(s));
+  return VDB_OK;
+}
+
 }  // namespace vdb
 
 using namespace vdb;
@@ -456,6 +562,27 @@ int vdb_ann_index_apply_dev(const vdb_fr* grouped_dev, const uint32_t* slots_dev
   return ann_index_apply_dev(as_u256(grouped_dev), slots_dev, as_u256(forest_dev), as_u256(roots_dev), cluster_sizes, K, dim, cluster, grow,
                              as_u256(updated_levels_dev), as_u256(new_vectors_dev), indices, db_slots, m, as_u256(grouped_out_dev), slots_out_dev,
                              offsets_out_dev, as_u256(forest_out_dev), as_u256(roots_out_dev));
+}
+
+int vdb_ann_index_remove_size(const uint64_t* cluster_sizes, size_t K, size_t cluster, const uint64_t* slots, size_t m, unsigned* shrink, uint64_t* digests,
+                              uint64_t* segment_offsets) {
+  AnndPlan dp;
+  AnndRemovePlan p;
+  TRY(ann_remove_plan(cluster_sizes, K, 1, cluster, slots, m, &dp, &p));
+  if (shrink) *shrink = dp.shrink;
+  if (digests) *digests = p.seg_off[K + 1];
+  if (segment_offsets) memcpy(segment_offsets, p.seg_off.data(), (K + 2) * sizeof(uint64_t));
+  return VDB_OK;
+}
+int vdb_ann_index_remove_dev(const vdb_fr* grouped_dev, const vdb_fr* forest_dev, const vdb_fr* roots_dev, const uint64_t* cluster_sizes, size_t K, size_t dim,
+                             size_t cluster, const vdb_fr* updated_levels_dev, const uint64_t* slots, size_t m, vdb_fr* grouped_out_dev,
+                             uint32_t* slots_out_dev, uint64_t* offsets_out_dev, vdb_fr* forest_out_dev, vdb_fr* roots_out_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(grouped_dev && forest_dev && roots_dev && updated_levels_dev && grouped_out_dev && slots_out_dev && offsets_out_dev && forest_out_dev &&
+              roots_out_dev,
+          "null pointer");
+  return ann_index_remove_dev(as_u256(grouped_dev), as_u256(forest_dev), as_u256(roots_dev), cluster_sizes, K, dim, cluster, as_u256(updated_levels_dev),
+                              slots, m, as_u256(grouped_out_dev), slots_out_dev, offsets_out_dev, as_u256(forest_out_dev), as_u256(roots_out_dev));
 }
 
 }  // extern "C"

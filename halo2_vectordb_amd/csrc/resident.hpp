@@ -39,5 +39,8 @@ int ann_index_build_dev(const u256* db, const uint32_t* ids, const u256* centroi
 int ann_index_apply_dev(const u256* grouped, const uint32_t* slots, const u256* forest, const u256* roots, const uint64_t* sizes, size_t K, size_t dim,
                         size_t cluster, unsigned grow, const u256* updated, const u256* new_vectors, const uint64_t* indices, const uint32_t* db_slots,
                         size_t m, u256* grouped_out, uint32_t* slots_out, uint64_t* offsets_out, u256* forest_out, u256* roots_out);
+int ann_index_remove_dev(const u256* grouped, const u256* forest, const u256* roots, const uint64_t* sizes, size_t K, size_t dim, size_t cluster,
+                         const u256* updated, const uint64_t* slots, size_t m, u256* grouped_out, uint32_t* slots_out, uint64_t* offsets_out,
+                         u256* forest_out, u256* roots_out);
 
 }  // namespace vdb

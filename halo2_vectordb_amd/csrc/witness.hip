@@ -1149,10 +1149,11 @@ struct MkuLayout : PathLayout {
 // per (level, update), arrays indexed [l * m + j]: sib_from = the latest earlier update whose path holds this one's sibling node at
 // level l (-1: the resident digest is still current), last = no later update touches this update's node at level l (its new-path
 // digest is the batch's final state of that node); prev_same[j] = the latest earlier update of the same slot (-1: none).
-// write_no[j]: which of the new vectors update j writes, -1 for a delete, whose new leaf 0 goes into row 0 of path_new here
+// write_no[j]: which of the new vectors update j writes, -1 for a delete, whose new leaf 0 goes into row 0 of path_new here, and
+// -2 - s for a carried leaf (the index delete's move, mku_plan): the digest slot s of `levels` holds before the batch
 __global__ __launch_bounds__(256) void k_mku_touchers(const uint32_t* __restrict__ idx, uint32_t m, uint32_t depth, int32_t* __restrict__ sib_from,
                                                       int32_t* __restrict__ prev_same, uint8_t* __restrict__ last, const int32_t* __restrict__ write_no,
-                                                      u256* __restrict__ path_new) {
+                                                      const u256* __restrict__ levels, u256* __restrict__ path_new) {
   __shared__ uint32_t sidx[MKU_MAX_UPDATES];
   for (uint32_t i = threadIdx.x; i < m; i += 256) sidx[i] = idx[i];
   __syncthreads();
@@ -1175,7 +1176,8 @@ __global__ __launch_bounds__(256) void k_mku_touchers(const uint32_t* __restrict
         break;
       }
     prev_same[j] = same;
-    if (write_no[j] < 0) path_new[j] = u256_zero();
+    const int32_t wn = write_no[j];
+    if (wn < 0) path_new[j] = wn == -1 ? u256_zero() : levels[-2 - wn];
   }
   uint8_t is_last = 1;
   for (uint32_t i = j + 1; i < m; i++)
@@ -1252,7 +1254,8 @@ __global__ __launch_bounds__(64) void k_mku_level_trace(Streams stq, const FpTab
   trace_path_level<2>(stq, T, sp, lb, (idx[j] >> l) & 1u, wit + ((size_t)m + (size_t)m * depth + (size_t)j * depth + l), path_old + ((size_t)l * m + j),
                       path_new + ((size_t)l * m + j), part);
 }
-// idx_j = gate.inner_product(bits, Constant(2^l)) per update, a delete's load_constant(0) cell in front of its levels, and the public
+// idx_j = gate.inner_product(bits, Constant(2^l)) per update, a delete's load_constant(0) cell (a carried leaf's load_witness cell) in
+// front of its levels, and the public
 // values [old root | idx, old leaf, new leaf per update | new root] (the old root of a grown tree is R_0: k_mku_grow_trace's)
 __global__ __launch_bounds__(64) void k_mku_index(Streams stq, const FpTables* __restrict__ T, MkuLayout ml, uint64_t base,
                                                   const uint64_t* __restrict__ level_at, const uint32_t* __restrict__ idx,
@@ -1262,7 +1265,7 @@ __global__ __launch_bounds__(64) void k_mku_index(Streams stq, const FpTables* _
   const uint32_t m = ml.m, depth = ml.depth;
   if (j >= m) return;
   WCtx c = make_ctx(stq, T, base + level_at[j] - 1, 0);
-  if (write_no[j] < 0) c.push(u256_zero(), false, true);
+  if (write_no[j] < 0) c.push(path_new[j], false, write_no[j] == -1);
   c.pos = base + level_at[j] + (uint64_t)depth * ml.level_cells;
   pub[1 + 3 * (size_t)j] = trace_path_index(c, T, idx[j], depth);   // (the assigned bits are those of idx_j: k_mku_level)
   pub[2 + 3 * (size_t)j] = wit[j];
@@ -1607,8 +1610,9 @@ static int path_layout(size_t n, size_t dim, unsigned grow, int sides, PathLayou
 // sizes of a batch of m path updates (kinds: 0 write, 1 delete; null: all writes) in a tree over n vectors grown `grow` times; the
 // limits of one call (include/vdb.h).  level_at (m; null: not wanted): where the levels of update j start in the stream, behind its
 // leaf sponge or its zero cell; write_no (m): the row of new_vectors update j writes, -1 for a delete.
+// `carried` admits kind 2, a carried leaf: one load_witness cell where a delete has its zero (write_no -2; the index delete's alone)
 static int mku_layout(size_t n, size_t dim, size_t m, const uint8_t* kinds, unsigned grow, MkuLayout* o, uint64_t* lp_out, uint64_t* level_at,
-                      int32_t* write_no) {
+                      int32_t* write_no, bool carried = false) {
   uint64_t lp;
   TRY(path_layout(n, dim, grow, 2, o, &lp));
   VDB_ARG(m > 0, "a batch holds at least one update");
@@ -1616,7 +1620,7 @@ static int mku_layout(size_t n, size_t dim, size_t m, const uint8_t* kinds, unsi
   const uint32_t depth = o->depth;
   size_t w = 0;
   for (size_t j = 0; j < m; j++) {
-    VDB_ARG(!kinds || kinds[j] <= 1, "an update is a write (0) or a delete (1)");
+    VDB_ARG(!kinds || kinds[j] <= (carried ? 2 : 1), "an update is a write (0) or a delete (1)");
     w += !kinds || kinds[j] == 0;
   }
   o->m = (uint32_t)m;
@@ -1633,7 +1637,7 @@ static int mku_layout(size_t n, size_t dim, size_t m, const uint8_t* kinds, unsi
     const bool del = kinds && kinds[j];
     at += del ? 1 : o->leaf_cells;
     if (level_at) level_at[j] = at;
-    if (write_no) write_no[j] = del ? -1 : wn++;
+    if (write_no) write_no[j] = del ? -(int32_t)kinds[j] : wn++;
     at += depth * o->level_cells + o->ip_cells;
   }
   o->total = at;
@@ -1650,12 +1654,14 @@ struct MkuPlan {
   std::vector<uint64_t> level_at, tab;   // (tab: the pageable source of the upload; hipMemcpyAsync stages it before returning)
   std::vector<int32_t> write_no;
 };
-static int mku_plan(size_t n, size_t dim, unsigned grow, const u256* new_vectors, const uint64_t* indices, const uint8_t* kinds, size_t m, MkuPlan* p) {
+// carry_src (null: no kind 2 is admitted): for an update of kind 2 the slot whose resident digest is its new leaf
+static int mku_plan(size_t n, size_t dim, unsigned grow, const u256* new_vectors, const uint64_t* indices, const uint8_t* kinds, size_t m, MkuPlan* p,
+                    const uint32_t* carry_src = nullptr) {
   VDB_ARG(m > 0 && m <= MKU_MAX_UPDATES, "a batch holds 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES updates");
   p->level_at.resize(m);
   p->write_no.resize(m);
   MkuLayout& ml = p->ml;
-  TRY(mku_layout(n, dim, m, kinds, grow, &ml, &p->lp, p->level_at.data(), p->write_no.data()));
+  TRY(mku_layout(n, dim, m, kinds, grow, &ml, &p->lp, p->level_at.data(), p->write_no.data(), carry_src != nullptr));
   VDB_ARG(new_vectors || ml.w == 0, "null pointer: a write needs its new vector");
   const size_t w = ml.w;
   p->n_tab = (m + w) * sizeof(uint64_t) + (2 * m + w) * sizeof(uint32_t);
@@ -1669,6 +1675,10 @@ static int mku_plan(size_t n, size_t dim, unsigned grow, const u256* new_vectors
     VDB_ARG(indices[j] < p->lp, "update index outside the padded tree (grow it first: vdb_merkle_tree_grow_dev)");
     p_level_at[j] = p->level_at[j];
     p_idx[j] = (uint32_t)indices[j];
+    if (p->write_no[j] == -2) {
+      VDB_ARG(carry_src[j] < p->lp, "carried leaf outside the padded tree");
+      p->write_no[j] = -2 - (int32_t)carry_src[j];
+    }
     p_write_no[j] = p->write_no[j];
     if (p->write_no[j] >= 0) {
       p_leaf_at[p->write_no[j]] = p->level_at[j] - ml.leaf_cells;
@@ -1710,7 +1720,7 @@ static int mku_emit(FpEntry* fp, const PoseidonSpec* sp, const MkuPlan& pl, u256
   VDB_HIP(hipMemcpyAsync(level_at, pl.tab.data(), n_tab, hipMemcpyHostToDevice, s));
   const uint32_t mu = (uint32_t)m, wu = (uint32_t)w;
   // grids of at least one block: the launches of a call do not depend on how many of its updates are writes
-  VDB_LAUNCH(k_mku_touchers, dim3((unsigned)((m * depth + 255) / 256)), dim3(256), didx, mu, depth, sib_from, prev_same, last, write_no, path_new);
+  VDB_LAUNCH(k_mku_touchers, dim3((unsigned)((m * depth + 255) / 256)), dim3(256), didx, mu, depth, sib_from, prev_same, last, write_no, levels, path_new);
   TRY(mk_leaf_states(sp, new_vectors, wu, (uint32_t)dim, ml.nperm, states, path_new, write_of));
   for (uint32_t l = 0; l < depth; l++)
     VDB_LAUNCH(k_mku_level, dim3((unsigned)((2 * m + 63) / 64)), dim3(64), sp, levels, lp, didx, mu, depth, l, sib_from, prev_same, wit, path_old, path_new);
@@ -1973,6 +1983,124 @@ int wit_ann_update_dev(u256* levels, const u256* roots, size_t K, size_t cluster
   VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((nperm + 63) / 64)), dim3(64), st, fp->dev, sp, k.words_new, 1u, Ku + 1, nperm, a.b.b_root, a.mw.leaf_cells,
              k.st_new, nullptr);
   VDB_LAUNCH(k_annu_public, dim3((unsigned)((3 * m + 3 + 255) / 256)), dim3(256), k.upub, k.hdr, k.iroot, (uint32_t)m, pub);
+  return inv_list_fixup(st);
+}
+
+// ------------------------------------------------------------------ deletes against the index root (include/vdb.h vdb_wit_ann_delete,
+// vdb_ann_index_remove_dev).  m deletes from cluster c: blocks A - D, F, G as above; E' is the update block over 2 m path updates (delete
+// j: the last member's leaf carried into slot_j, then the last slot emptied: annd_expand), and when the cluster's tree halves s >= 1
+// times block S between E' and F proves that the dropped half is empty: [S_0 assigned | Z_0 = load_constant(0) | Z_{l+1} = H(Z_l, Z_l),
+// l < d - 1 | S_{i+1} = H(S_i, Z_{d-s+i}), i < s].  The map ties S_s to E's final root; F's `a` copies S_0, the root of the halved tree.
+struct AnndLayout {
+  MkLayout mw;
+  AnndBlocks b;
+  uint32_t depth, shrink;
+};
+// Block S, a lane per permutation of its d - 1 + s node hashes, in the form of k_mku_grow_trace; every input is resident: Z_l in `empty`,
+// S_i at entry 0 of level d - s + i of `levels` once k_mku_writeback has run.  Lane 0 also assigns S_0 and keeps it for block F.
+__global__ __launch_bounds__(64) void k_annd_shrink_trace(Streams stq, const FpTables* __restrict__ T, const PoseidonSpec* __restrict__ sp, uint64_t base,
+                                                          uint32_t depth, uint32_t shrink, uint64_t lp, const u256* __restrict__ levels,
+                                                          const u256* __restrict__ empty, u256* __restrict__ s0) {
+  const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+  const uint32_t n_z = depth - 1, n_hash = n_z + shrink, d1 = depth - shrink;
+  if (t >= 2 * n_hash) return;
+  if (t == 0) {
+    const u256 v = levels[mku_level_off(lp, d1)];
+    *s0 = v;
+    WCtx c = make_ctx(stq, T, base, 0);
+    c.push(v, false);
+    c.push(u256_zero(), false, true);
+  }
+  const uint32_t h = t >> 1, second = t & 1u;
+  const uint32_t lz = h < n_z ? h : d1 + (h - n_z);
+  trace_node_half(stq, T, sp, base + 2 + (uint64_t)h * NODE_CELLS, h < n_z ? empty + lz : levels + mku_level_off(lp, lz), empty + lz, second);
+}
+// [index_root_old | c | slot_j, removed_leaf_j, last_j, moved_leaf_j per delete | index_root_new] from the update block's public values
+// [old root | idx, old leaf, new leaf per path update | new root]: delete j is updates 2 j (the move) and 2 j + 1 (the emptied slot)
+__global__ __launch_bounds__(256) void k_annd_public(const u256* __restrict__ upub, const u256* __restrict__ hdr, const u256* __restrict__ iroot,
+                                                     uint32_t m, u256* __restrict__ pub) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 4 * m + 3) return;
+  if (i < 2 || i == 4 * m + 2) {
+    pub[i] = i == 0 ? iroot[0] : i == 1 ? hdr[0] : iroot[1];
+    return;
+  }
+  const uint32_t j = (i - 2) >> 2, k = (i - 2) & 3u;
+  pub[i] = upub[1 + 6 * (size_t)j + (k == 0 ? 0 : k == 1 ? 1 : k == 2 ? 3 : 2)];
+}
+// the host side of a delete batch, before anything is launched: the expansion to 2 m path updates and every refusal
+static int annd_layout(size_t K, size_t cluster, size_t n_c, size_t dim, const uint64_t* slots, size_t m, AnndLayout* o, MkuLayout* ml, AnndPlan* dp) {
+  VDB_ARG(K > 0 && K <= VDB_ANN_MAX_CLUSTERS, "K = 0 or K above VDB_ANN_MAX_CLUSTERS");
+  VDB_ARG(cluster < K, "cluster >= K");
+  VDB_ARG(n_c <= VDB_ANN_MAX_VECTORS, "cluster larger than VDB_ANN_MAX_VECTORS");
+  VDB_ARG(m > 0 && m <= MKU_MAX_UPDATES / 2, "a batch holds 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES / 2 deletes (two path updates each)");
+  VDB_ARG(m < n_c, "the batch would empty the cluster");
+  static thread_local std::vector<uint64_t> none;
+  if (!slots) {   // the size call: the shape does not depend on the slots
+    none.assign(m, 0);
+    slots = none.data();
+  }
+  const int rc = annd_expand(slots, m, n_c, MKU_MAX_UPDATES, dp, nullptr);
+  VDB_ARG(rc != 3, "a slot at or above the cluster's fill at its turn (every delete lowers the fill by one)");
+  VDB_ARG(rc == 0, "a batch holds at least one delete and leaves at least one member");
+  TRY(mku_layout(n_c, dim, 2 * m, dp->kinds.data(), 0, ml, nullptr, nullptr, nullptr, true));
+  mk_layout(1, K + 1, 1, &o->mw);
+  o->depth = dp->depth;
+  o->shrink = dp->shrink;
+  o->b = annd_blocks(K, o->mw.total, ml->total, annd_shrink_cells(dp->depth, dp->shrink, NODE_CELLS));
+  VDB_ARG(o->b.b.total <= ((uint64_t)1 << 34), "more than VDB_MERKLE_UPDATE_MAX_CELLS cells in one call");
+  return VDB_OK;
+}
+// roots: [centroids_root | the K cluster roots] of the index before the batch; levels: cluster c's tree over its n_c members, left in
+// the state after the batch (at its old size: vdb_ann_index_remove_dev cuts it); pub: 4 m + 3
+int wit_ann_delete_dev(u256* levels, const u256* roots, size_t K, size_t cluster, size_t n_c, size_t dim, const uint64_t* slots, size_t m, Streams st,
+                       u256* pub) {
+  static thread_local MkuPlan pl;
+  static thread_local AnndPlan dp;
+  AnndLayout a;
+  MkuLayout ml0;
+  VDB_ARG(slots, "null pointer");
+  TRY(annd_layout(K, cluster, n_c, dim, slots, m, &a, &ml0, &dp));
+  TRY(mku_plan(n_c, dim, 0, nullptr, dp.indices.data(), dp.kinds.data(), 2 * m, &pl, dp.carry_src.data()));
+  const u256* empty = nullptr;
+  if (a.shrink) TRY(poseidon_empty_subtrees_dev(&empty));
+  const AnnuBlocks& b = a.b.b;
+  const size_t n_st = (size_t)a.mw.nperm * PSD_T, n_up = 6 * m + 2;
+  u256* w = (u256*)scratch_get(7, (2 * (K + 2) + K + 1 + 2 + n_up + 1 + 2 * n_st + 8) * sizeof(u256));
+  if (!w) return VDB_ERR_OOM;
+  AnnuWork k;
+  k.hdr = w;
+  k.ind = k.hdr + K + 2;
+  k.picked = k.ind + K;
+  k.words_new = k.picked + 1;
+  k.iroot = k.words_new + K + 1;
+  k.upub = k.iroot + 2;
+  u256* s0 = k.upub + n_up;
+  k.st_old = s0 + 1;
+  k.st_new = k.st_old + n_st;
+  TRY(inv_list_attach(st, b.total));
+  FpEntry* fp;
+  const PoseidonSpec* sp;
+  TRY(mk_begin(st, &fp, &sp));
+  const uint32_t Ku = (uint32_t)K, cu = (uint32_t)cluster, nperm = a.mw.nperm;
+  const u256* words_old = k.hdr + 1;
+  VDB_LAUNCH(k_annu_header, dim3((unsigned)((K + 2 + 255) / 256)), dim3(256), st, 0, cu, roots, Ku, k.hdr);
+  VDB_LAUNCH(k_annu_indicator, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, b.b_ind, cu, Ku, k.ind);
+  const NvMap sm{b.b_sel, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, Ku, 1u, 1u};
+  VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), st, fp->dev, sm, 1u, words_old + 1, k.ind, k.picked);
+  TRY(mk_leaf_states(sp, words_old, 1u, Ku + 1, nperm, k.st_old, k.iroot, nullptr));
+  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((nperm + 63) / 64)), dim3(64), st, fp->dev, sp, words_old, 1u, Ku + 1, nperm, b.b_old, a.mw.leaf_cells,
+             k.st_old, nullptr);
+  TRY(mku_emit(fp, sp, pl, levels, dim, nullptr, st, b.b_upd, k.upub));
+  if (a.shrink)  // S_i are the halved tree's top digests as the write-back left them
+    VDB_LAUNCH(k_annd_shrink_trace, dim3((unsigned)((2 * (a.depth - 1 + a.shrink) + 63) / 64)), dim3(64), st, fp->dev, sp, a.b.b_shr, a.depth, a.shrink, pl.lp,
+               levels, empty, s0);
+  VDB_LAUNCH(k_annu_new_roots, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, b.b_new, Ku, a.shrink ? s0 : k.upub + n_up - 1, words_old, k.ind,
+             k.words_new);
+  TRY(mk_leaf_states(sp, k.words_new, 1u, Ku + 1, nperm, k.st_new, k.iroot + 1, nullptr));
+  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((nperm + 63) / 64)), dim3(64), st, fp->dev, sp, k.words_new, 1u, Ku + 1, nperm, b.b_root, a.mw.leaf_cells,
+             k.st_new, nullptr);
+  VDB_LAUNCH(k_annd_public, dim3((unsigned)((4 * m + 3 + 255) / 256)), dim3(256), k.upub, k.hdr, k.iroot, (uint32_t)m, pub);
   return inv_list_fixup(st);
 }
 
@@ -2494,6 +2622,49 @@ int vdb_wit_ann_update(vdb_fr* levels, const vdb_fr* roots, size_t K, size_t clu
   TRY(download(public_out, dpub.p, (3 * m + 3) * sizeof(u256)));
   TRY(download(levels, dl.p, 2 * lp * sizeof(u256)));
   return hs.finish(stream_out, nullptr, selector_out, a.b.total, 0);
+}
+
+// deletes against the index root (include/vdb.h); the index after them: resident.hip
+int vdb_wit_ann_delete_size(size_t K, size_t n_c, size_t dim, size_t m, uint64_t* cells, uint64_t* input_cells, uint64_t* update_base, uint64_t* shrink_base,
+                            unsigned* shrink) {
+  AnndLayout a;
+  MkuLayout ml;
+  AnndPlan dp;
+  TRY(annd_layout(K, 0, n_c, dim, nullptr, m, &a, &ml, &dp));
+  if (cells) *cells = a.b.b.total;
+  if (input_cells) *input_cells = a.b.b.n_in;
+  if (update_base) *update_base = a.b.b.b_upd;
+  if (shrink_base) *shrink_base = a.b.b_shr;
+  if (shrink) *shrink = a.shrink;
+  return VDB_OK;
+}
+int vdb_wit_ann_delete_dev(vdb_fr* levels_dev, const vdb_fr* roots_dev, size_t K, size_t cluster, size_t n_c, size_t dim, const uint64_t* slots, size_t m,
+                           vdb_fr* stream_dev, uint8_t* selector_dev, vdb_fr* public_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(levels_dev && roots_dev && slots && stream_dev && public_dev, "null pointer");
+  DevStreams ds;
+  ds.init(stream_dev, selector_dev);
+  TRY(wit_ann_delete_dev(as_u256(levels_dev), as_u256(roots_dev), K, cluster, n_c, dim, slots, m, ds.st, as_u256(public_dev)));
+  return ds.finish();
+}
+int vdb_wit_ann_delete(vdb_fr* levels, const vdb_fr* roots, size_t K, size_t cluster, size_t n_c, size_t dim, const uint64_t* slots, size_t m,
+                       vdb_fr* stream_out, uint8_t* selector_out, vdb_fr* public_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(levels && roots && slots, "null pointer");
+  AnndLayout a;
+  MkuLayout ml;
+  AnndPlan dp;
+  TRY(annd_layout(K, cluster, n_c, dim, slots, m, &a, &ml, &dp));
+  DevBuf dl, dr, dpub;
+  HostStreams hs;
+  TRY(upload(dl, levels, 2 * dp.lp * sizeof(u256)));
+  TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
+  TRY(dpub.alloc((4 * m + 3) * sizeof(u256)));
+  TRY(hs.init(a.b.b.total, 0, selector_out != nullptr));
+  TRY(wit_ann_delete_dev(dl.as<u256>(), dr.as<u256>(), K, cluster, n_c, dim, slots, m, hs.st, dpub.as<u256>()));
+  TRY(download(public_out, dpub.p, (4 * m + 3) * sizeof(u256)));
+  TRY(download(levels, dl.p, 2 * dp.lp * sizeof(u256)));
+  return hs.finish(stream_out, nullptr, selector_out, a.b.b.total, 0);
 }
 
 }  // extern "C"

@@ -1269,6 +1269,32 @@ class AnnIndex:
             raise
         return ix
 
+    def removed(self, hp):
+        """the index after the batch of AnnDeleteHotPath `hp` (its witness has run: hp.d_levels holds the cluster's tree after the
+        batch), as a new AnnIndex on buffers of its own (vdb_ann_index_remove_dev); this index stays valid.  A removal compacts the
+        database: the result's host view (qvec, cluster_ids) is its own grouped rows in order, database slot = grouped place.  Queries,
+        reads, updates and further deletes run on the result unchanged."""
+        c, m = hp.cluster, hp.m
+        sizes64 = np.ascontiguousarray(self.sizes, dtype=np.uint64)
+        _, digests, seg = api.ann_index_remove_layout(sizes64, c, hp.slots)
+        sizes = self.sizes.copy()
+        sizes[c] -= m
+        # the host's view: the grouped rows before the batch, cluster c's rearranged as the batch leaves them (hp.origin)
+        old_slots = self.d_slots.download((self.n,), dtype=np.uint32).astype(np.int64)
+        lo = int(self.offsets[c])
+        keep = np.concatenate([np.arange(lo), lo + np.asarray(hp.origin, dtype=np.int64), np.arange(lo + int(self.sizes[c]), self.n)]).astype(np.int64)
+        qvec = np.ascontiguousarray(self.qvec[old_slots[keep]])
+        ids = np.repeat(np.arange(self.K, dtype=np.uint32), sizes)
+        ix = AnnIndex.from_resident(self.dim, self.K, sizes, digests, seg, self.qcent, qvec, ids, P=self.P, L=self.L, metric=self.metric_name)
+        try:
+            check(self.lib.vdb_ann_index_remove_dev(self.d_grouped.ptr, self.d_forest.ptr, self.d_roots.ptr, api._p(sizes64), self.K, self.dim, c,
+                                                    hp.d_levels.ptr, api._p(hp.slots), m, ix.d_grouped.ptr, ix.d_slots.ptr, ix.d_offsets.ptr,
+                                                    ix.d_forest.ptr, ix.d_roots.ptr))
+        except Exception:
+            ix.free()
+            raise
+        return ix
+
     def _buf(self, nbytes):
         b = api.DeviceBuffer(max(int(nbytes), 32))
         self._bufs.append(b)
@@ -1467,5 +1493,81 @@ class AnnUpdateHotPath(PoseidonHotPath):
         from .circuit_dev import DeviceBuilder
         cm, pub, _ = CS.build_ann_update(self.K, self.m, self.dim, self.depth, functools.partial(self._fetch_flags, d_flags), self._fetch,
                                          builder=DeviceBuilder if on_device else None, grow=self.grow)
+        assert cm.n_cells == self.n_cells
+        return cm, pub, None
+
+
+class AnnDeleteHotPath(PoseidonHotPath):
+    """Deletes proved against the committed index root: m deletes from ONE cluster c of an AnnIndex in one proof (include/vdb.h
+    vdb_wit_ann_delete).  The members stay dense by swap-with-last: delete j moves the member at last_j = fill - 1 into slot_j and empties
+    the last slot, two path updates of the cluster's tree (a carried leaf, then a delete); when the cluster drops to a power of two the
+    tree halves, and the circuit proves that the dropped half is empty (block S).  Blocks A - D, F, G are AnnUpdateHotPath's.  Public:
+    [index_root_old | c | slot, removed leaf, last, moved leaf per delete | index_root_new]; a verifier who tracks n_c checks
+    last_j = n_c - 1 - j.  No input rows.  K, m, the depth and the halvings `s` are circuit shape, c and the slots are not.  `d_levels`
+    holds the cluster's tree after the batch at its old size; AnnIndex.removed(hp) gives the next index (which cuts it).  `origin[p]`:
+    the slot that held, before the batch, the member at surviving position p."""
+
+    def __init__(self, index, cluster, slots, k=15, L=8, tau=None, col_shard=(0, 1), blind_seed=None, params=None, levels=None):
+        """`slots`: (m,) slots of the cluster, each below the fill at its turn (n_c - j); repeats are legal.  `levels`: a tree to use in
+        place of the index's segment c (tests of the binding)."""
+        self.slots = np.ascontiguousarray(slots, dtype=np.uint64)
+        m = self.slots.shape[0]
+        self.index, self.K, self.cluster = index, index.K, int(cluster)
+        if not 0 <= self.cluster < self.K:
+            raise ValueError("cluster outside the index")
+        n_c = int(index.sizes[self.cluster])
+        if m < 1 or m >= n_c:
+            raise ValueError("a batch holds at least one delete and leaves at least one member")
+        origin = list(range(n_c))
+        for j, s in enumerate(self.slots.tolist()):
+            if s >= n_c - j:
+                raise ValueError("a slot at or above the cluster's fill at its turn")
+            origin[s] = origin[n_c - j - 1]
+        self.origin = origin[:n_c - m]
+        self.lp, self.depth = api.merkle_levels(n_c)
+        super().__init__(n_c, index.dim, k, index.P, L, seed=None, tau=tau, col_shard=col_shard, vectors=np.zeros((0, index.dim)), blind_seed=blind_seed,
+                         params=params)
+        self.m, self.given_levels = m, levels
+
+    def n_input_rows(self):
+        return 0
+
+    def _load_inputs(self):
+        super()._load_inputs()
+        self.d_levels0 = self._output(2 * self.lp * B)
+        self.d_levels = self._output(2 * self.lp * B)
+        self._load_tree(self.d_levels0, self.lp, self.index.levels(self.cluster) if self.given_levels is None else self.given_levels)
+
+    def _circuit_size(self):
+        cells, n_in, ub, sb, s = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint()
+        check(self.lib.vdb_wit_ann_delete_size(self.K, self.n, self.dim, self.m, ctypes.byref(cells), ctypes.byref(n_in), ctypes.byref(ub), ctypes.byref(sb),
+                                               ctypes.byref(s)))
+        self.update_base, self.shrink_base, self.shrink = ub.value, sb.value, s.value
+        return n_in.value, cells.value - n_in.value, 0
+
+    def _alloc_outputs(self):
+        self.d_pub = self._output((4 * self.m + 3) * B)
+
+    def _witness(self, sel=None):
+        # the call writes the assigned header too; every run starts from the cluster's tree before the batch
+        check(self.lib.vdb_memcpy_d2d(self.d_levels.ptr, self.d_levels0.ptr, ctypes.c_size_t(2 * self.lp * B)))
+        with self._window(sel, 0, lookup=False):
+            check(self.lib.vdb_wit_ann_delete_dev(self.d_levels.ptr, self.index.d_roots.ptr, self.K, self.cluster, self.n, self.dim, api._p(self.slots),
+                                                  self.m, self.d_stream.ptr, self._sel_at(sel, 0), self.d_pub.ptr))
+
+    def public_values_dev(self):
+        return self.d_pub.ptr, 4 * self.m + 3
+
+    def results(self):
+        """(index_root_old (4,), c (4,), slots (m, 4), removed leaves (m, 4), last (m, 4), moved leaves (m, 4), index_root_new (4,))"""
+        pub = self.d_pub.download((4 * self.m + 3, 4))
+        per = pub[2:-1].reshape(self.m, 4, 4)
+        return pub[0], pub[1], per[:, 0], per[:, 1], per[:, 2], per[:, 3], pub[-1]
+
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        cm, pub, _ = CS.build_ann_delete(self.K, self.m, self.dim, self.depth, functools.partial(self._fetch_flags, d_flags), self._fetch,
+                                         builder=DeviceBuilder if on_device else None, shrink=self.shrink)
         assert cm.n_cells == self.n_cells
         return cm, pub, None

@@ -394,7 +394,8 @@ int vdb_wit_ann_query_dev(int metric, uint32_t precision_bits, uint32_t lookup_b
  * stay private.  K, m, grow and the depth are circuit shape; c is not: one proving key serves every cluster of the same depth.
  * Writes only, and the members stay dense: the query circuit hashes merkle_commitment(members(c)) over n_c dense rows, so a hole would
  * make the cluster unqueryable.  Write j is accepted when indices[j] is below the fill at its turn (a replacement) or equal to it (an
- * append: the fill rises by one); the fill starts at n_c; writes of a batch see each other.  There is no delete.
+ * append: the fill rises by one); the fill starts at n_c; writes of a batch see each other.  Deletes are a batch of their own:
+ * vdb_wit_ann_delete below (chain the two calls to mix them).
  * Cluster assignment is NOT proved: nothing in the circuit shows that c is the cluster whose centroid is nearest to a new vector (the
  * index build does not prove its cluster ids either).  The caller chooses c; nearest_vector over the centroids is its tool.
  * roots: the K + 1 digests [centroids_root | cluster roots] (the head of vdb_ann_index_build_dev's roots_dev).  levels: cluster c's tree
@@ -428,6 +429,52 @@ int vdb_ann_index_apply_dev(const vdb_fr *grouped_dev, const uint32_t *slots_dev
                             const vdb_fr *updated_levels_dev, const vdb_fr *new_vectors_dev, const uint64_t *indices /* host */,
                             const uint32_t *db_slots /* host */, size_t m, vdb_fr *grouped_out_dev, uint32_t *slots_out_dev,
                             uint64_t *offsets_out_dev, vdb_fr *forest_out_dev, vdb_fr *roots_out_dev);
+
+/* Deletes against the index root: m deletes from ONE cluster c move index_root_old to index_root_new in one circuit.  The members stay
+ * dense by swap-with-last: delete j of slot_j moves the member at last_j = fill - 1 (the fill at its turn: n_c - j) into slot_j and
+ * empties slot last_j.  slot_j == last_j is legal (the leaf is carried onto itself, then deleted) and so are repeats: deleting slot 0
+ * twice removes the vector the first delete moved there.  n_c - m >= 1: an emptied cluster is refused, as the build refuses one.
+ * With lp the power of two >= n_c, d = log2(lp) and s the number of halvings with lp >> s == the power of two >= n_c - m (computed
+ * by the call, returned by _size; nothing has to be prepared for a shrink), the stream is, from cell 0:
+ *   A - D  exactly those of vdb_wit_ann_update
+ *   E'     the update block of vdb_wit_merkle_update_ops (grow = 0) over 2 m path updates, from cell update_base on: update 2 j at
+ *          slot_j, whose new leaf is CARRIED — one ctx.load_witness(digest) cell where a delete has its load_constant(0), the digest being
+ *          the leaf at last_j at that turn — and update 2 j + 1 at last_j, a delete.  (The carried kind is internal to this call:
+ *          vdb_wit_merkle_update_ops keeps refusing a kind above 1.)
+ *   S      only when s >= 1, from cell shrink_base on: S_0 assigned, Z_0 = load_constant(0), Z_{l+1} = H(Z_l, Z_l) for l = 0 .. d - 2,
+ *          S_{i+1} = H(S_i, Z_{d-s+i}) for i = 0 .. s - 1: 2 + (d - 1 + s) * 4506 cells
+ *   F, G   those of vdb_wit_ann_update; F's a copies the new cluster root: S_0 when s >= 1, else E''s final root
+ * Copies (no cell), beyond those of vdb_wit_ann_update: picked <-> cur_old at the top of update 0; the carried-leaf cell of update 2 j
+ * <-> the assigned old-leaf cell of update 2 j + 1 (what left the last slot is what arrived); S_s <-> E''s final root, so the removed
+ * half is PROVED empty: were it not, the hashes would disagree with the tree and the copy would break.
+ * public, 4 m + 3 values: [index_root_old | c | slot_j, removed_leaf_j, last_j, moved_leaf_j per delete | index_root_new].  The fill is
+ * not committed (nothing in vdb_wit_ann_update commits it either): a verifier who tracks n_c checks last_j == n_c - 1 - j on the public
+ * values.  The shape depends on (K, d, m, s, dim) only, never on which slots are deleted; the launches depend on d and on s > 0.
+ * levels: cluster c's tree over its n_c members (forest segment c, copied), left in the state after the batch AT ITS OLD SIZE:
+ * vdb_ann_index_remove_dev cuts it.  slots is a HOST array.  The _dev form honours vdb_wit_set_window.
+ * VDB_ERR_ARG before anything is launched: m == 0, 2 m > VDB_MERKLE_UPDATE_MAX_UPDATES, m >= n_c, a slot >= the fill at its turn,
+ * c >= K, K == 0, K > VDB_ANN_MAX_CLUSTERS, the cell limit.  _size takes no slots; each of its outputs may be NULL.
+ *
+ * vdb_ann_index_remove_dev (values only, functional; the old buffers are only read): the index after the batch.  Cluster c's
+ * surviving position p < n_c - m holds the original member origin[p] the batch leaves there, rows of later clusters move down by m,
+ * forest segment c is the updated tree cut to lp >> s leaves, later segments move, root c is replaced and the index root hashed again:
+ * four launches whatever the shape.  A REMOVAL COMPACTS THE DATABASE: database slots are renumbered so that the result equals, entry
+ * for entry (grouped rows, slots 0 .. n - m - 1, offsets, forest, roots), vdb_ann_index_build_dev over the database whose rows are the
+ * result's own grouped rows in order, with nondecreasing cluster ids.  A caller that keeps outside references to database slots maps
+ * them through the old slots array before the call.  vdb_ann_index_remove_size: s, the digests of the new forest and its K + 2 segment
+ * offsets (each may be NULL).  Output sizes: grouped (n - m) x dim, slots n - m, offsets K + 1, forest `digests`, roots K + 2. */
+int vdb_wit_ann_delete_size(size_t K, size_t n_c, size_t dim, size_t m, uint64_t *cells, uint64_t *input_cells, uint64_t *update_base,
+                            uint64_t *shrink_base, unsigned *shrink);
+int vdb_wit_ann_delete(vdb_fr *levels, const vdb_fr *roots, size_t K, size_t cluster, size_t n_c, size_t dim, const uint64_t *slots, size_t m,
+                       vdb_fr *stream_out, uint8_t *selector_out, vdb_fr *public_out);
+int vdb_wit_ann_delete_dev(vdb_fr *levels_dev, const vdb_fr *roots_dev, size_t K, size_t cluster, size_t n_c, size_t dim,
+                           const uint64_t *slots /* host */, size_t m, vdb_fr *stream_dev, uint8_t *selector_dev, vdb_fr *public_dev);
+int vdb_ann_index_remove_size(const uint64_t *cluster_sizes /* host */, size_t K, size_t cluster, const uint64_t *slots /* host */, size_t m,
+                              unsigned *shrink, uint64_t *digests, uint64_t *segment_offsets);
+int vdb_ann_index_remove_dev(const vdb_fr *grouped_dev, const vdb_fr *forest_dev, const vdb_fr *roots_dev,
+                             const uint64_t *cluster_sizes /* host */, size_t K, size_t dim, size_t cluster, const vdb_fr *updated_levels_dev,
+                             const uint64_t *slots /* host */, size_t m, vdb_fr *grouped_out_dev, uint32_t *slots_out_dev,
+                             uint64_t *offsets_out_dev, vdb_fr *forest_out_dev, vdb_fr *roots_out_dev);
 
 /* ---- b4 stream -> columns: replaces halo2-base GateThreadBuilder::assign_all (break points, keygen)
  *      and assign_threads_in (prover) as driven by RangeCircuitBuilder::prover(builder, break_points)

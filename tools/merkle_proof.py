@@ -23,7 +23,12 @@ public), and has the verifier check the proof.  The circuit's size follows the c
 `--circuit ann-update --K C --updates M [--grow G]` proves M writes into one cluster of that index against its root
 (pipeline.AnnUpdateHotPath: the first write replaces member 0 of the largest cluster, the others append to it; [index_root_old | c | idx, old
 leaf, new leaf per write | index_root_new] public; `--grow` defaults to the smallest number of doublings that fits the appends), has the
-verifier check the proof and applies the batch to the resident index (AnnIndex.updated), whose root must be the public index_root_new."""
+verifier check the proof and applies the batch to the resident index (AnnIndex.updated), whose root must be the public index_root_new.
+`--circuit ann-delete --K C --deletes M` proves M deletes from the largest cluster of that index (pipeline.AnnDeleteHotPath: slot 0 again and
+again, so every delete but the first removes the member the one before moved there; the last member moves into the slot and the cluster's
+tree halves when the fill drops to a power of two; [index_root_old | c | slot, removed leaf, last, moved leaf per delete | index_root_new]
+public), has the verifier check the proof and removes the batch from the resident index (AnnIndex.removed), whose root must be the
+public index_root_new."""
 import argparse
 import json
 import os
@@ -34,7 +39,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from halo2_vectordb_amd import api  # noqa: E402
-from halo2_vectordb_amd.pipeline import AnnIndex, AnnQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
+from halo2_vectordb_amd.pipeline import AnnDeleteHotPath, AnnIndex, AnnQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
 from halo2_vectordb_amd.rounds import ProverRounds, quotient_identity_holds  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -45,13 +50,13 @@ ap.add_argument("--seed", type=int, default=20260003)
 ap.add_argument("--block-cols", type=int, default=510)
 ap.add_argument("--ext-block-cols", type=int, default=None)
 ap.add_argument("--proofs", type=int, default=2)
-ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read", "ann", "ann-update"])
+ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read", "ann", "ann-update", "ann-delete"])
 ap.add_argument("--lookup-bits", type=int, default=13)
 ap.add_argument("--metric", default="euclidean")
 ap.add_argument("--queries", type=int, default=1, help="--circuit query: queries proved against the one database in this proof")
 ap.add_argument("--topk", type=int, default=1, help="--circuit query: nearest vectors proved per query, nearest first")
 ap.add_argument("--updates", type=int, default=8, help="--circuit update: inserts / replacements proved in this proof")
-ap.add_argument("--deletes", type=int, default=0, help="--circuit update: the last K updates empty their slot instead of writing it")
+ap.add_argument("--deletes", type=int, default=0, help="--circuit update: the last K updates empty their slot instead of writing it; --circuit ann-delete: deletes proved")
 ap.add_argument("--grow", type=int, default=None, help="--circuit update / ann-update: doublings of the padded leaf count before the first update")
 ap.add_argument("--reads", type=int, default=8, help="--circuit read: slots opened in this proof")
 ap.add_argument("--leaf-only", action="store_true", help="--circuit read: reveal the leaf digests, not the vectors")
@@ -63,8 +68,8 @@ api.init(0)
 t0 = time.time()
 if args.queries < 1 or (args.queries > 1 and args.circuit != "query"):
     raise SystemExit("--queries needs --circuit query and at least one query")
-if args.deletes and args.circuit != "update" or args.grow is not None and args.circuit not in ("update", "ann-update"):
-    raise SystemExit("--deletes needs --circuit update, --grow --circuit update or ann-update")
+if args.deletes and args.circuit not in ("update", "ann-delete") or args.grow is not None and args.circuit not in ("update", "ann-update"):
+    raise SystemExit("--deletes needs --circuit update or ann-delete, --grow --circuit update or ann-update")
 ann_grow, args.grow = args.grow, args.grow or 0
 if args.topk < 1 or (args.topk > 1 and args.circuit != "query"):
     raise SystemExit("--topk needs --circuit query and at least one neighbour")
@@ -77,7 +82,7 @@ elif args.circuit == "update":
         raise SystemExit("--deletes is between 0 and --updates, --grow is not negative")
     kinds = [0] * (args.updates - args.deletes) + [1] * args.deletes
     hp = UpdateHotPath(n=args.n, dim=args.dim, m=args.updates, k=args.k, seed=args.seed, kinds=kinds, grow=args.grow)
-elif args.circuit in ("ann", "ann-update"):
+elif args.circuit in ("ann", "ann-update", "ann-delete"):
     from halo2_vectordb_amd.pipeline import sift_like_vectors
     if not 1 <= args.K <= args.n:
         raise SystemExit("--K is between 1 and --n")
@@ -88,6 +93,11 @@ elif args.circuit in ("ann", "ann-update"):
     index = AnnIndex(args.n, args.dim, args.K, db, ids, db[:args.K], L=args.lookup_bits, metric=args.metric)
     if args.circuit == "ann":
         hp = AnnQueryHotPath(index, query, k=args.k, L=args.lookup_bits, metric=args.metric)
+    elif args.circuit == "ann-delete":
+        c = int(np.argmax(index.sizes))
+        if not 1 <= args.deletes < int(index.sizes[c]):
+            raise SystemExit("--deletes is at least 1 and leaves the largest cluster a member")
+        hp = AnnDeleteHotPath(index, c, [0] * args.deletes, k=args.k)
     else:
         c = int(np.argmax(index.sizes))
         slots = [0] + [int(index.sizes[c]) + i for i in range(args.updates - 1)]
@@ -126,18 +136,23 @@ if args.out:
     write_snark(args.out, out["proof"], out["instances"])
     pr.save_verifying_key(args.out + ".vk.npz", opened=out["opened"])
 accepted = {}
-if args.circuit in ("read", "ann", "ann-update"):
+if args.circuit in ("read", "ann", "ann-update", "ann-delete"):
     from halo2_vectordb_amd import verifier
     accepted = {"proof_accepted": bool(verifier.verify(out["proof"], out["instances"], verifier.VerifyingKey.from_prover(pr, out["opened"])))}
 if args.circuit == "ann-update":
     index2 = index.updated(hp)
     accepted["applied_index_root_is_the_public_new_root"] = bool(np.array_equal(index2.roots()[-1], hp.results()[-1]))
     index2.free()
+if args.circuit == "ann-delete":
+    index2 = index.removed(hp)
+    accepted["removed_index_root_is_the_public_new_root"] = bool(np.array_equal(index2.roots()[-1], hp.results()[-1]))
+    index2.free()
 what = f"merkle_commitment {args.n}x{args.dim} k={args.k}" if args.circuit == "merkle" else \
     f"{args.updates} Merkle path updates ({args.deletes} deletes, tree grown {args.grow} times) against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "update" else \
     f"{args.reads} Merkle openings ({'leaves' if args.leaf_only else 'vectors'} public) against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "read" else \
     f"ann query (K={args.K}, cluster {hp.cluster} of {hp.n} vectors, {args.metric}) against the index of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann" else \
     f"{args.updates} writes into cluster {hp.cluster} ({hp.n} members, tree grown {hp.grow} times) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-update" else \
+    f"{args.deletes} deletes from cluster {hp.cluster} ({hp.n} members, tree halved {hp.shrink} times) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-delete" else \
     f"query circuit ({str(args.queries) + ' x ' if args.queries > 1 else ''}{'top-' + str(args.topk) + ' ' if args.topk > 1 else ''}nearest_vector {args.metric} + merkle_commitment) over {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}"
 print(json.dumps({"workload": what + ": whole constraint map, public outputs in the instance column, transcript, fresh blinds, SHPLONK", "lookup_cells": hp.n_lookup,
                   "cells": hp.n_cells, "columns": hp.n_cols, "product_sets": pr.n_sets, "mock_report_on_keygen_witness": pr.keygen_report.as_dict(),
@@ -148,5 +163,5 @@ print(json.dumps({"workload": what + ": whole constraint map, public outputs in 
                   "block_cols": args.block_cols, "ext_cols_held": hp.ext_cols}))
 pr.free()
 hp.free()
-if args.circuit in ("ann", "ann-update"):
+if args.circuit in ("ann", "ann-update", "ann-delete"):
     index.free()
