@@ -528,6 +528,15 @@ def wit_ann_query(metric, query, centroids, members, cluster_roots, P=48, L=13, 
                 index_root=pub[dim], public=pub)
 
 
+def _wit_ann_batch(levels, cells, n_pub, selectors, call, **sizes):
+    """the buffers of a host-array call against the index root and its dict: call(levels, stream, selectors or None, public) -> its code"""
+    levels = np.array(levels, dtype=np.uint64, copy=True)
+    stream, pub = np.zeros((cells, 4), dtype=np.uint64), np.zeros((n_pub, 4), dtype=np.uint64)
+    sel = np.zeros(cells, dtype=np.uint8) if selectors else None
+    check(call(_p(levels), _p(stream), _p(sel) if selectors else None, _p(pub)))
+    return dict(stream=stream, **_split_flags(sel), **sizes, public=pub, levels=levels)
+
+
 def wit_ann_update(levels, roots, cluster, n_c, new_vectors, indices, grow=0, selectors=False):
     """m writes into cluster `cluster` of a committed index (vdb_wit_ann_update), the streams alone: `levels` cluster c's tree over its
     n_c members (merkle_tree_build's array, after merkle_tree_grow when grow > 0), `roots` (K + 1, 4): [centroids' root | cluster roots],
@@ -536,18 +545,14 @@ def wit_ann_update(levels, roots, cluster, n_c, new_vectors, indices, grow=0, se
     index_root_new], levels: the cluster's tree after the batch)"""
     lib = _lib.init()
     new_vectors, roots = _fr(new_vectors), _fr(roots)
-    levels = np.array(levels, dtype=np.uint64, copy=True)
     idx = np.ascontiguousarray(indices, dtype=np.uint64)
     m, dim, K = idx.shape[0], new_vectors.shape[1], roots.shape[0] - 1
-    assert idx.shape == (m,) and new_vectors.shape[0] == m and levels.shape == (2 * (merkle_levels(n_c)[0] << grow), 4)
+    assert idx.shape == (m,) and new_vectors.shape[0] == m and np.shape(levels) == (2 * (merkle_levels(n_c)[0] << grow), 4)
     cells, n_in, ub = _u64(), _u64(), _u64()
     check(lib.vdb_wit_ann_update_size(_sz(K), _sz(n_c), _sz(dim), _sz(m), int(grow), ctypes.byref(cells), ctypes.byref(n_in), ctypes.byref(ub)))
-    stream = np.zeros((cells.value, 4), dtype=np.uint64)
-    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
-    pub = np.zeros((3 * m + 3, 4), dtype=np.uint64)
-    check(lib.vdb_wit_ann_update(_p(levels), _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(dim), int(grow), _p(new_vectors), _p(idx), _sz(m), _p(stream),
-                                 _p(sel) if selectors else None, _p(pub)))
-    return dict(stream=stream, **_split_flags(sel), input_cells=n_in.value, update_base=ub.value, public=pub, levels=levels)
+    call = lambda lv, st, sl, pb: lib.vdb_wit_ann_update(lv, _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(dim), int(grow), _p(new_vectors), _p(idx),
+                                                         _sz(m), st, sl, pb)
+    return _wit_ann_batch(levels, cells.value, 3 * m + 3, selectors, call, input_cells=n_in.value, update_base=ub.value)
 
 
 def ann_index_apply_layout(sizes, cluster, grow, indices):
@@ -597,20 +602,14 @@ def wit_ann_delete(levels, roots, cluster, n_c, dim, slots, selectors=False):
     tree after the batch, at its old size)"""
     lib = _lib.init()
     roots = _fr(roots)
-    levels = np.array(levels, dtype=np.uint64, copy=True)
     idx = np.ascontiguousarray(slots, dtype=np.uint64)
     m, K = idx.shape[0], roots.shape[0] - 1
-    assert idx.shape == (m,) and levels.shape == (2 * merkle_levels(n_c)[0], 4)
+    assert idx.shape == (m,) and np.shape(levels) == (2 * merkle_levels(n_c)[0], 4)
     cells, n_in, ub, sb, s = _u64(), _u64(), _u64(), _u64(), ctypes.c_uint()
     check(lib.vdb_wit_ann_delete_size(_sz(K), _sz(n_c), _sz(dim), _sz(m), ctypes.byref(cells), ctypes.byref(n_in), ctypes.byref(ub), ctypes.byref(sb),
                                       ctypes.byref(s)))
-    stream = np.zeros((cells.value, 4), dtype=np.uint64)
-    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
-    pub = np.zeros((4 * m + 3, 4), dtype=np.uint64)
-    check(lib.vdb_wit_ann_delete(_p(levels), _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(dim), _p(idx), _sz(m), _p(stream),
-                                 _p(sel) if selectors else None, _p(pub)))
-    return dict(stream=stream, **_split_flags(sel), input_cells=n_in.value, update_base=ub.value, shrink_base=sb.value, shrink=s.value, public=pub,
-                levels=levels)
+    call = lambda lv, st, sl, pb: lib.vdb_wit_ann_delete(lv, _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(dim), _p(idx), _sz(m), st, sl, pb)
+    return _wit_ann_batch(levels, cells.value, 4 * m + 3, selectors, call, input_cells=n_in.value, update_base=ub.value, shrink_base=sb.value, shrink=s.value)
 
 
 def ann_index_remove_layout(sizes, cluster, slots):

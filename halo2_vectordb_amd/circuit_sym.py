@@ -1369,21 +1369,27 @@ def build_merkle_update(m, dim, depth, fetch_flags, fetch_values, builder=None, 
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # Inserts and replacements against the index root (include/vdb.h vdb_wit_ann_update; pipeline.AnnUpdateHotPath)
-def ann_update_layout(K, m, dim, depth, grow=0):
-    """where the blocks of the index update circuit start: dict(c, centroids_root, roots: the assigned header; n_in; indicator, select,
-    sponge_old, update, new_roots, sponge_new: the blocks; total; update_layout: merkle_update_layout of block E (relative to `update`);
-    sponge: merkle_leaf_layout(K + 1))"""
+def _ann_frame_layout(K, sp, inner_cells):
+    """The frame of a circuit against the index root (the update's and the delete's) around `inner_cells` cells of its own: dict(c,
+    centroids_root, roots: the assigned header A; n_in; indicator B, select C, sponge_old D, update: the inner block, new_roots F,
+    sponge_new G: the blocks; total; sponge: sp = merkle_leaf_layout(K + 1))"""
     if K < 1:
         raise ValueError("an index has at least one cluster")
-    upd, sp = merkle_update_layout(m, dim, depth, None, grow), merkle_leaf_layout(K + 1)
-    lay = dict(c=0, centroids_root=1, roots=2, n_in=K + 2, indicator=K + 2, update_layout=upd, sponge=sp)
+    lay = dict(c=0, centroids_root=1, roots=2, n_in=K + 2, indicator=K + 2, sponge=sp)
     lay["select"] = lay["indicator"] + 8 + 12 * (K - 1)
     lay["sponge_old"] = lay["select"] + 1 + 3 * K
     lay["update"] = lay["sponge_old"] + sp["leaf_cells"]
-    lay["new_roots"] = lay["update"] + upd["total"]
+    lay["new_roots"] = lay["update"] + inner_cells
     lay["sponge_new"] = lay["new_roots"] + 8 * K
     lay["total"] = lay["sponge_new"] + sp["leaf_cells"]
     return lay
+
+
+def ann_update_layout(K, m, dim, depth, grow=0):
+    """where the blocks of the index update circuit start: _ann_frame_layout's keys and update_layout: merkle_update_layout of block E
+    (relative to `update`)"""
+    upd = merkle_update_layout(m, dim, depth, None, grow)
+    return dict(_ann_frame_layout(K, merkle_leaf_layout(K + 1), upd["total"]), update_layout=upd)
 
 
 def _indicator_at(lay, j):
@@ -1396,14 +1402,10 @@ def ann_update_instances(index_root_old, c, update_public, index_root_new):
     return [int(index_root_old), int(c)] + [int(x) for x in update_public[1:-1]] + [int(index_root_new)]
 
 
-def trace_ann_update(K, m, dim, depth, fetch_flags, fetch_values, grow=0):
-    """The closure of m writes into one cluster of a committed index cell by cell (the ground truth of build_ann_update): the header
-    [c | centroids_root | cluster roots] assigned, idx_to_indicator(c, K) as select_from_idx unrolls it, select_by_indicator(cluster
-    roots, indicators) -> picked, the sponge over the header's roots, the update block (trace_merkle_update's cells), whose old root is
-    tied to picked, out_j = select(new cluster root, cluster_root_j, indicator_j) and the sponge over [centroids_root | out_j].
-    -> (CopyMap, public cells, dict(indicators, picked, old_root, new_root, outs, index_root_old, index_root_new, layout))"""
-    lay = ann_update_layout(K, m, dim, depth, grow)
-    t = _CellTrace(lay["total"], fetch_flags, fetch_values)
+def _trace_ann_head(t, lay):
+    """blocks A - D of the frame on a _CellTrace: the header assigned, idx_to_indicator(c, K) as select_from_idx unrolls it,
+    select_by_indicator(cluster roots, indicators) -> picked, the sponge over the header's roots.  -> (inds, picked, root_old)"""
+    K = lay["n_in"] - 2
     c, roots = lay["c"], [lay["roots"] + j for j in range(K)]
     inds = [t.is_zero(lay["indicator"], c)]
     for j in range(1, K):
@@ -1417,23 +1419,41 @@ def trace_ann_update(K, m, dim, depth, fetch_flags, fetch_values, grow=0):
     picked = t.put(lay["select"], cells, gates) - 1
     root_old, at = t.leaf(lay["sponge_old"], lay["sponge"], None, [lay["centroids_root"]] + roots)
     assert at == lay["update"]
-    upub = _trace_update_block(t, lay["update_layout"], lay["update"])
-    t.copy_of[upub[0]] = picked                              # ctx.constrain_equal(picked, the update block's old root)
-    outs = [t.select(lay["new_roots"] + 8 * j, upub[-1], roots[j], inds[j]) for j in range(K)]
+    return inds, picked, root_old
+
+
+def _trace_ann_tail(t, lay, inds, new_root):
+    """blocks F and G: out_j = select(new_root, cluster_root_j, indicator_j), the sponge over [centroids_root | out_j].
+    -> (outs, root_new)"""
+    outs = [t.select(lay["new_roots"] + 8 * j, new_root, lay["roots"] + j, inds[j]) for j in range(len(inds))]
     root_new, at = t.leaf(lay["sponge_new"], lay["sponge"], None, [lay["centroids_root"]] + outs)
     assert at == lay["total"]
-    info = dict(indicators=inds, picked=picked, old_root=upub[0], new_root=upub[-1], outs=outs, index_root_old=root_old, index_root_new=root_new, layout=lay)
-    return t.finish(), ann_update_instances(root_old, c, upub, root_new), info
+    return outs, root_new
 
 
-def build_ann_update(K, m, dim, depth, fetch_flags, fetch_values, builder=None, grow=0):
-    """trace_ann_update's map assembled from unit blocks: is_equal(c, Constant(j)) placed for all j >= 1 at once (its constant j set per
-    instance), select_by_indicator over K cells, the two sponges (place_sponge), the update block (place_merkle_update at its base) and
-    the K selects placed at once (`builder`: as build_kmeans).  -> as trace_ann_update"""
+def trace_ann_update(K, m, dim, depth, fetch_flags, fetch_values, grow=0):
+    """The closure of m writes into one cluster of a committed index cell by cell (the ground truth of build_ann_update): the header
+    [c | centroids_root | cluster roots] assigned, idx_to_indicator(c, K) as select_from_idx unrolls it, select_by_indicator(cluster
+    roots, indicators) -> picked, the sponge over the header's roots, the update block (trace_merkle_update's cells), whose old root is
+    tied to picked, out_j = select(new cluster root, cluster_root_j, indicator_j) and the sponge over [centroids_root | out_j].
+    -> (CopyMap, public cells, dict(indicators, picked, old_root, new_root, outs, index_root_old, index_root_new, layout))"""
     lay = ann_update_layout(K, m, dim, depth, grow)
+    t = _CellTrace(lay["total"], fetch_flags, fetch_values)
+    inds, picked, root_old = _trace_ann_head(t, lay)
+    upub = _trace_update_block(t, lay["update_layout"], lay["update"])
+    t.copy_of[upub[0]] = picked                              # ctx.constrain_equal(picked, the update block's old root)
+    outs, root_new = _trace_ann_tail(t, lay, inds, upub[-1])
+    info = dict(indicators=inds, picked=picked, old_root=upub[0], new_root=upub[-1], outs=outs, index_root_old=root_old, index_root_new=root_new, layout=lay)
+    return t.finish(), ann_update_instances(root_old, lay["c"], upub, root_new), info
+
+
+def _build_ann_head(lay, fetch_flags, fetch_values, builder):
+    """blocks A - D of the frame from unit blocks on a new builder: is_equal(c, Constant(j)) placed for all j >= 1 at once (its
+    constant j set per instance), select_by_indicator over K cells, the sponge (place_sponge).  -> (B, inds, picked, root_old)"""
     if np.asarray(fetch_flags(0, lay["n_in"])).any():
         raise ValueError("the assigned header carries no gate or constant flag")
     B = (builder or _Builder)(lay["total"], 0)
+    K = lay["n_in"] - 2
     c, roots = lay["c"], lay["roots"] + np.arange(K, dtype=np.int64)
     s = Sym(0, 0)
     iz = Block(s, [s.g_is_zero(ext(0))])
@@ -1453,18 +1473,34 @@ def build_ann_update(K, m, dim, depth, fetch_flags, fetch_values, builder=None, 
     picked = int(B.place(sb, [lay["select"]], [0], np.concatenate([roots, inds])[None, :])[0, 0])
     root_old, end = place_sponge(B, lay["sponge_old"], [lay["centroids_root"]] + [int(r) for r in roots], fetch_flags, fetch_values)
     assert end == lay["update"]
-    upub = place_merkle_update(B, m, dim, depth, fetch_flags, fetch_values, lay["update"], None, grow)
-    B.tie(upub[0], picked)                                   # ctx.constrain_equal(picked, the update block's old root)
+    return B, inds, picked, root_old
+
+
+def _build_ann_tail(B, lay, inds, new_root, fetch_flags, fetch_values):
+    """blocks F and G: the K selects placed at once, the sponge over [centroids_root | out_j].  -> (outs, root_new)"""
+    K = len(inds)
     s = Sym(0, 0)
     sl = Block(s, [s.g_select(ext(0), ext(1), ext(2))])
     outs = B.place(sl, lay["new_roots"] + 8 * np.arange(K, dtype=np.int64), np.zeros(K, dtype=np.int64),
-                   np.stack([np.full(K, upub[-1], dtype=np.int64), roots, inds], axis=1))[:, 0]
+                   np.stack([np.full(K, new_root, dtype=np.int64), lay["roots"] + np.arange(K, dtype=np.int64), inds], axis=1))[:, 0]
     root_new, end = place_sponge(B, lay["sponge_new"], [lay["centroids_root"]] + [int(o) for o in outs], fetch_flags, fetch_values)
     if end != lay["total"]:
         raise ValueError("the trace does not end where the circuit does")
-    info = dict(indicators=[int(i) for i in inds], picked=picked, old_root=upub[0], new_root=upub[-1], outs=[int(o) for o in outs], index_root_old=root_old,
+    return [int(o) for o in outs], root_new
+
+
+def build_ann_update(K, m, dim, depth, fetch_flags, fetch_values, builder=None, grow=0):
+    """trace_ann_update's map assembled from unit blocks: is_equal(c, Constant(j)) placed for all j >= 1 at once (its constant j set per
+    instance), select_by_indicator over K cells, the two sponges (place_sponge), the update block (place_merkle_update at its base) and
+    the K selects placed at once (`builder`: as build_kmeans).  -> as trace_ann_update"""
+    lay = ann_update_layout(K, m, dim, depth, grow)
+    B, inds, picked, root_old = _build_ann_head(lay, fetch_flags, fetch_values, builder)
+    upub = place_merkle_update(B, m, dim, depth, fetch_flags, fetch_values, lay["update"], None, grow)
+    B.tie(upub[0], picked)                                   # ctx.constrain_equal(picked, the update block's old root)
+    outs, root_new = _build_ann_tail(B, lay, inds, upub[-1], fetch_flags, fetch_values)
+    info = dict(indicators=[int(i) for i in inds], picked=picked, old_root=upub[0], new_root=upub[-1], outs=outs, index_root_old=root_old,
                 index_root_new=root_new, layout=lay)
-    return B.finish(), ann_update_instances(root_old, c, upub, root_new), info
+    return B.finish(), ann_update_instances(root_old, lay["c"], upub, root_new), info
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -1478,24 +1514,15 @@ def ann_delete_shrink(n_c, m):
 
 
 def ann_delete_layout(K, m, dim, depth, shrink=0):
-    """where the blocks of the index delete circuit start: ann_update_layout's keys (update_layout: merkle_update_layout of block E' over
-    the 2 m path updates [carried, delete] * m) and `shrink`: the first cell of block S [S_0 | Z_0 | Z hashes depth - 1 | S hashes s]
+    """where the blocks of the index delete circuit start: _ann_frame_layout's keys, update_layout (merkle_update_layout of block E' over
+    the 2 m path updates [carried, delete] * m), `shrink`: the first cell of block S [S_0 | Z_0 | Z hashes depth - 1 | S hashes s]
     between E' and F, shrink_cells (0 when the tree keeps its size), s"""
-    if K < 1:
-        raise ValueError("an index has at least one cluster")
     if m < 1 or not 0 <= shrink <= depth:
         raise ValueError("at least one delete, and no more halvings than the tree has levels")
-    upd, sp = merkle_update_layout(2 * m, dim, depth, [2, 1] * m, 0, carried=True), merkle_leaf_layout(K + 1)
-    lay = dict(c=0, centroids_root=1, roots=2, n_in=K + 2, indicator=K + 2, update_layout=upd, sponge=sp, s=shrink)
-    lay["select"] = lay["indicator"] + 8 + 12 * (K - 1)
-    lay["sponge_old"] = lay["select"] + 1 + 3 * K
-    lay["update"] = lay["sponge_old"] + sp["leaf_cells"]
-    lay["shrink"] = lay["update"] + upd["total"]
-    lay["shrink_cells"] = 2 + (depth - 1 + shrink) * upd["node_cells"] if shrink else 0
-    lay["new_roots"] = lay["shrink"] + lay["shrink_cells"]
-    lay["sponge_new"] = lay["new_roots"] + 8 * K
-    lay["total"] = lay["sponge_new"] + sp["leaf_cells"]
-    return lay
+    upd = merkle_update_layout(2 * m, dim, depth, [2, 1] * m, 0, carried=True)
+    cells = 2 + (depth - 1 + shrink) * upd["node_cells"] if shrink else 0
+    lay = _ann_frame_layout(K, merkle_leaf_layout(K + 1), upd["total"] + cells)
+    return dict(lay, update_layout=upd, shrink=lay["update"] + upd["total"], shrink_cells=cells, s=shrink)
 
 
 def ann_delete_instances(index_root_old, c, update_public, index_root_new):
@@ -1517,26 +1544,14 @@ def _delete_info(lay, m, upub, s0, top):
 
 def trace_ann_delete(K, m, dim, depth, fetch_flags, fetch_values, shrink=0):
     """The closure of m deletes from one cluster of a committed index cell by cell (the ground truth of build_ann_delete): blocks A - D
-    of trace_ann_update, the update block over 2 m path updates (a carried leaf into slot_j, then the last slot emptied), the carried
+    (_trace_ann_head), the update block over 2 m path updates (a carried leaf into slot_j, then the last slot emptied), the carried
     cell tied to the old leaf of the update behind it, block S when the tree halves (its top tied to the update block's final root), F
     over the new cluster root (S_0, or the final root when nothing shrinks) and G.
     -> (CopyMap, public cells, dict(indicators, picked, old_root, new_root, outs, index_root_old, index_root_new, carried, moved_old, s0,
     shrink_top, z0, layout))"""
     lay = ann_delete_layout(K, m, dim, depth, shrink)
     t = _CellTrace(lay["total"], fetch_flags, fetch_values)
-    c, roots = lay["c"], [lay["roots"] + j for j in range(K)]
-    inds = [t.is_zero(lay["indicator"], c)]
-    for j in range(1, K):
-        at = _indicator_at(lay, j)
-        t.put(at, [None, ("k", j), ("k", 1), ("c", c)], [1, 0, 0, 0])
-        inds.append(t.is_zero(at + 4, at))
-    cells, gates = [("k", 0)], [1]
-    for j in range(K):
-        cells += [("c", roots[j]), ("c", inds[j]), None]
-        gates += [0, 0, j + 1 < K]
-    picked = t.put(lay["select"], cells, gates) - 1
-    root_old, at = t.leaf(lay["sponge_old"], lay["sponge"], None, [lay["centroids_root"]] + roots)
-    assert at == lay["update"]
+    inds, picked, root_old = _trace_ann_head(t, lay)
     upub = _trace_update_block(t, lay["update_layout"], lay["update"])
     t.copy_of[upub[0]] = picked                              # ctx.constrain_equal(picked, the update block's old root)
     s0, top = None, None
@@ -1557,39 +1572,16 @@ def trace_ann_delete(K, m, dim, depth, fetch_flags, fetch_values, shrink=0):
         assert at == lay["new_roots"]
         t.copy_of[top] = upub[-1]                            # ctx.constrain_equal(S_s, the update block's final root)
         new_root = s0
-    outs = [t.select(lay["new_roots"] + 8 * j, new_root, roots[j], inds[j]) for j in range(K)]
-    root_new, at = t.leaf(lay["sponge_new"], lay["sponge"], None, [lay["centroids_root"]] + outs)
-    assert at == lay["total"]
+    outs, root_new = _trace_ann_tail(t, lay, inds, new_root)
     info = dict(_delete_info(lay, m, upub, s0, top), indicators=inds, picked=picked, outs=outs, index_root_old=root_old, index_root_new=root_new, layout=lay)
-    return t.finish(), ann_delete_instances(root_old, c, upub, root_new), info
+    return t.finish(), ann_delete_instances(root_old, lay["c"], upub, root_new), info
 
 
 def build_ann_delete(K, m, dim, depth, fetch_flags, fetch_values, builder=None, shrink=0):
     """trace_ann_delete's map assembled from unit blocks, as build_ann_update: the update block is place_merkle_update at its base with
     the carried kind, block S's hashes are placed one after the other (`builder`: as build_kmeans).  -> as trace_ann_delete"""
     lay = ann_delete_layout(K, m, dim, depth, shrink)
-    if np.asarray(fetch_flags(0, lay["n_in"])).any():
-        raise ValueError("the assigned header carries no gate or constant flag")
-    B = (builder or _Builder)(lay["total"], 0)
-    c, roots = lay["c"], lay["roots"] + np.arange(K, dtype=np.int64)
-    s = Sym(0, 0)
-    iz = Block(s, [s.g_is_zero(ext(0))])
-    inds = [int(B.place(iz, [lay["indicator"]], [0], [[c]])[0, 0])]
-    if K > 1:
-        s = Sym(0, 0)
-        d = s.push(None, True)
-        s.push(None); s.push(C(1)); s.push(ext(0))
-        ie = Block(s, [s.g_is_zero(d)])
-        at = np.asarray([_indicator_at(lay, j) for j in range(1, K)], dtype=np.int64)
-        inds += [int(x) for x in B.place(ie, at, np.zeros(K - 1, dtype=np.int64), np.full((K - 1, 1), c, dtype=np.int64))[:, 0]]
-        for j in range(1, K):
-            B.constant_cell(int(at[j - 1]) + 1, j)
-    inds = np.asarray(inds, dtype=np.int64)
-    s = Sym(0, 0)
-    sb = Block(s, [s.g_select_by_indicator([ext(i) for i in range(K)], [ext(K + i) for i in range(K)])])
-    picked = int(B.place(sb, [lay["select"]], [0], np.concatenate([roots, inds])[None, :])[0, 0])
-    root_old, end = place_sponge(B, lay["sponge_old"], [lay["centroids_root"]] + [int(r) for r in roots], fetch_flags, fetch_values)
-    assert end == lay["update"]
+    B, inds, picked, root_old = _build_ann_head(lay, fetch_flags, fetch_values, builder)
     upub = place_merkle_update(B, 2 * m, dim, depth, fetch_flags, fetch_values, lay["update"], [2, 1] * m, 0, carried=True)
     B.tie(upub[0], picked)                                   # ctx.constrain_equal(picked, the update block's old root)
     info = _delete_info(lay, m, upub, None, None)
@@ -1612,16 +1604,10 @@ def build_ann_delete(K, m, dim, depth, fetch_flags, fetch_values, builder=None, 
         top = int(top[0])
         B.tie(top, upub[-1])                                 # ctx.constrain_equal(S_s, the update block's final root)
         new_root = s0
-    s = Sym(0, 0)
-    sl = Block(s, [s.g_select(ext(0), ext(1), ext(2))])
-    outs = B.place(sl, lay["new_roots"] + 8 * np.arange(K, dtype=np.int64), np.zeros(K, dtype=np.int64),
-                   np.stack([np.full(K, new_root, dtype=np.int64), roots, inds], axis=1))[:, 0]
-    root_new, end = place_sponge(B, lay["sponge_new"], [lay["centroids_root"]] + [int(o) for o in outs], fetch_flags, fetch_values)
-    if end != lay["total"]:
-        raise ValueError("the trace does not end where the circuit does")
-    info = dict(_delete_info(lay, m, upub, s0, top), indicators=[int(i) for i in inds], picked=picked, outs=[int(o) for o in outs], index_root_old=root_old,
+    outs, root_new = _build_ann_tail(B, lay, inds, new_root, fetch_flags, fetch_values)
+    info = dict(_delete_info(lay, m, upub, s0, top), indicators=[int(i) for i in inds], picked=picked, outs=outs, index_root_old=root_old,
                 index_root_new=root_new, layout=lay)
-    return B.finish(), ann_delete_instances(root_old, c, upub, root_new), info
+    return B.finish(), ann_delete_instances(root_old, lay["c"], upub, root_new), info
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -19,19 +19,21 @@ static inline void tree_shape(uint64_t n, uint64_t* lp, uint32_t* depth) {
   for (*lp = 1, *depth = 0; *lp < n; *lp <<= 1) ++*depth;
 }
 
-// first stream cell of every block of the update circuit over K clusters: A the header [c | centroids_root | cluster roots],
-// B the indicators, C select_by_indicator, D the old sponge, E the update block, F the K selects, G the new sponge
+// first stream cell of every block of a circuit against the index root over K clusters (the update's and the delete's): A the header
+// [c | centroids_root | cluster roots], B the indicators, C select_by_indicator, D the old sponge, E the update block, S the delete's
+// proof that the dropped half is empty (b_shr; no cells in the update and when the tree keeps its size), F the K selects, G the new sponge
 struct AnnuBlocks {
-  uint64_t n_in, b_ind, b_sel, b_old, b_upd, b_new, b_root, total;
+  uint64_t n_in, b_ind, b_sel, b_old, b_upd, b_shr, b_new, b_root, total;
 };
-static inline AnnuBlocks annu_blocks(uint64_t K, uint64_t sponge_cells, uint64_t update_cells) {
+static inline AnnuBlocks annu_blocks(uint64_t K, uint64_t sponge_cells, uint64_t update_cells, uint64_t shrink_cells = 0) {
   AnnuBlocks o;
   o.n_in = K + 2;
   o.b_ind = o.n_in;
   o.b_sel = o.b_ind + 8 + 12 * (K - 1);
   o.b_old = o.b_sel + 1 + 3 * K;
   o.b_upd = o.b_old + sponge_cells;
-  o.b_new = o.b_upd + update_cells;
+  o.b_shr = o.b_upd + update_cells;
+  o.b_new = o.b_shr + shrink_cells;
   o.b_root = o.b_new + 8 * K;
   o.total = o.b_root + sponge_cells;
   return o;
@@ -153,17 +155,6 @@ static inline int annd_expand(const uint64_t* slots, size_t m, uint64_t n_c, siz
 // i < s]; nothing when the tree keeps its size
 static inline uint64_t annd_shrink_cells(uint32_t depth, uint32_t shrink, uint64_t node_cells) {
   return shrink ? 2 + (uint64_t)(depth - 1 + shrink) * node_cells : 0;
-}
-// the blocks of the delete circuit: annu_blocks with block S between the update block E' and F (b_shr; b_new is F, as there)
-struct AnndBlocks {
-  AnnuBlocks b;
-  uint64_t b_shr;
-};
-static inline AnndBlocks annd_blocks(uint64_t K, uint64_t sponge_cells, uint64_t update_cells, uint64_t shrink_cells) {
-  AnndBlocks o;
-  o.b = annu_blocks(K, sponge_cells, update_cells + shrink_cells);
-  o.b_shr = o.b.b_upd + update_cells;
-  return o;
 }
 // The index after m deletes from cluster c: the K + 1 row offsets and the K + 2 segment offsets of the forest, cluster c's tree cut
 // to lp_new leaves.  delta: digests by which the segments behind c move down.  -> 0; 1: an empty cluster

@@ -1871,15 +1871,11 @@ int wit_ann_query_dev(FpEntry* fp, int metric, const u256* query, const u256* ce
 // vdb_wit_ann_update, vdb_ann_index_apply_dev).  m writes into cluster c move index_root_old to index_root_new in one circuit:
 // A [c | centroids_root | cluster roots] assigned, B idx_to_indicator(c, K), C select_by_indicator(cluster roots, indicators) -> picked,
 // D the sponge over the header's roots, E the update block of the cluster's tree (mku_emit at its base), F out_j = select(new cluster
-// root, cluster_root_j, indicator_j), G the sponge over [centroids_root | out_j].  The map ties picked to E's old root.
+// root, cluster_root_j, indicator_j), G the sponge over [centroids_root | out_j].  The map ties picked to E's old root.  A - D, F and G
+// are the frame of every batch against the index root (AnnFrame: the delete below puts its own blocks into the same frame).
 struct AnnuLayout {
   MkLayout mw;
   AnnuBlocks b;
-};
-// work space of the call, in u256: [c | words_old K + 1] (the header as it is assigned) | ind K | picked | words_new K + 1 |
-// index_root_old, index_root_new | the update block's public values 3 m + 2 | the sponge states of D and of G
-struct AnnuWork {
-  u256 *hdr, *ind, *picked, *words_new, *iroot, *upub, *st_old, *st_new;
 };
 // the header: lane i < K + 2 assigns cell i and keeps the value for the blocks that read it
 __global__ __launch_bounds__(256) void k_annu_header(Streams st, uint64_t base, uint32_t c, const u256* __restrict__ roots, uint32_t K,
@@ -1932,16 +1928,69 @@ __global__ __launch_bounds__(256) void k_annu_public(const u256* __restrict__ up
   if (i >= 3 * m + 3) return;
   pub[i] = i == 0 ? iroot[0] : i == 1 ? hdr[0] : i == 3 * m + 2 ? iroot[1] : upub[i - 1];
 }
-static int annu_layout(size_t K, size_t cluster, size_t n_c, size_t dim, size_t m, unsigned grow, AnnuLayout* o, MkuLayout* ml) {
+// The refusals and the blocks every circuit against the index root shares.  inner(&shrink_cells) lays out the circuit's own blocks
+// into *ml, with its own refusals, which come between the frame's: after the arguments', before the cell limit.
+template <class Inner>
+static int ann_frame_layout(size_t K, size_t cluster, size_t n_c, AnnuLayout* o, MkuLayout* ml, Inner inner) {
   VDB_ARG(K > 0 && K <= VDB_ANN_MAX_CLUSTERS, "K = 0 or K above VDB_ANN_MAX_CLUSTERS");
   VDB_ARG(cluster < K, "cluster >= K");
   VDB_ARG(n_c <= VDB_ANN_MAX_VECTORS, "cluster larger than VDB_ANN_MAX_VECTORS");
-  TRY(mku_layout(n_c, dim, m, nullptr, grow, ml, nullptr, nullptr, nullptr));
+  uint64_t shrink_cells = 0;
+  TRY(inner(&shrink_cells));
   mk_layout(1, K + 1, 1, &o->mw);
-  o->b = annu_blocks(K, o->mw.total, ml->total);
+  o->b = annu_blocks(K, o->mw.total, ml->total, shrink_cells);
   VDB_ARG(o->b.total <= ((uint64_t)1 << 34), "more than VDB_MERKLE_UPDATE_MAX_CELLS cells in one call");
   return VDB_OK;
 }
+static int annu_layout(size_t K, size_t cluster, size_t n_c, size_t dim, size_t m, unsigned grow, AnnuLayout* o, MkuLayout* ml) {
+  return ann_frame_layout(K, cluster, n_c, o, ml, [&](uint64_t*) { return mku_layout(n_c, dim, m, nullptr, grow, ml, nullptr, nullptr, nullptr); });
+}
+// The frame of one call: its work space in scratch slot 7, in u256: [c | words_old K + 1] (the header as it is assigned) | ind K |
+// picked | words_new K + 1 | index_root_old, index_root_new | the inner block's public values n_upub | n_extra for the caller | the
+// sponge states of D and of G.  open() attaches the inverse list to the streams and emits A - D; the caller emits its own blocks
+// through `st`, then close() emits F and G over the new cluster root.
+struct AnnFrame {
+  Streams st;
+  FpEntry* fp;
+  const PoseidonSpec* sp;
+  const AnnuLayout* a;
+  uint32_t K;
+  u256 *hdr, *ind, *picked, *words_new, *iroot, *upub, *extra, *st_old, *st_new;
+  int open(Streams streams, const u256* roots, size_t K_, size_t cluster, const AnnuLayout& lay, size_t n_upub, size_t n_extra) {
+    st = streams, a = &lay, K = (uint32_t)K_;
+    const size_t n_st = (size_t)lay.mw.nperm * PSD_T;
+    hdr = (u256*)scratch_get(7, (2 * (K_ + 2) + K_ + 1 + 2 + n_upub + n_extra + 2 * n_st + 8) * sizeof(u256));
+    if (!hdr) return VDB_ERR_OOM;
+    ind = hdr + K_ + 2;
+    picked = ind + K_;
+    words_new = picked + 1;
+    iroot = words_new + K_ + 1;
+    upub = iroot + 2;
+    extra = upub + n_upub;
+    st_old = extra + n_extra;
+    st_new = st_old + n_st;
+    TRY(inv_list_attach(st, lay.b.total));
+    TRY(mk_begin(st, &fp, &sp));
+    const uint32_t cu = (uint32_t)cluster;
+    VDB_LAUNCH(k_annu_header, dim3((unsigned)((K_ + 2 + 255) / 256)), dim3(256), st, 0, cu, roots, K, hdr);
+    VDB_LAUNCH(k_annu_indicator, dim3((unsigned)((K_ + 63) / 64)), dim3(64), st, fp->dev, lay.b.b_ind, cu, K, ind);
+    const NvMap sm{lay.b.b_sel, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, K, 1u, 1u};
+    VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), st, fp->dev, sm, 1u, hdr + 2, ind, picked);
+    return sponge(hdr + 1, lay.b.b_old, st_old, iroot);
+  }
+  int close(const u256* new_root) {
+    VDB_LAUNCH(k_annu_new_roots, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, a->b.b_new, K, new_root, hdr + 1, ind, words_new);
+    return sponge(words_new, a->b.b_root, st_new, iroot + 1);
+  }
+  // blocks D and G: the sponge over K + 1 words at `base`, its digest to *root
+  int sponge(const u256* words, uint64_t base, u256* states, u256* root) {
+    const uint32_t nperm = a->mw.nperm;
+    TRY(mk_leaf_states(sp, words, 1u, K + 1, nperm, states, root, nullptr));
+    VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((nperm + 63) / 64)), dim3(64), st, fp->dev, sp, words, 1u, K + 1, nperm, base, a->mw.leaf_cells, states,
+               nullptr);
+    return VDB_OK;
+  }
+};
 // roots: [centroids_root | the K cluster roots] of the index before the batch; levels: cluster c's tree at depth d + grow, left in the
 // state after the batch; pub: 3 m + 3
 int wit_ann_update_dev(u256* levels, const u256* roots, size_t K, size_t cluster, size_t n_c, size_t dim, unsigned grow, const u256* new_vectors,
@@ -1952,38 +2001,12 @@ int wit_ann_update_dev(u256* levels, const u256* roots, size_t K, size_t cluster
   TRY(annu_layout(K, cluster, n_c, dim, m, grow, &a, &ml0));
   TRY(mku_plan(n_c, dim, grow, new_vectors, indices, nullptr, m, &pl));
   VDB_ARG(annu_track_fill(indices, m, n_c, pl.lp, nullptr, nullptr) == 0, "a write above the cluster's fill at its turn: the members of a cluster stay dense (append at the fill, or replace below it)");
-  const size_t n_st = (size_t)a.mw.nperm * PSD_T;
-  u256* w = (u256*)scratch_get(7, (2 * (K + 2) + K + 1 + 2 + 3 * m + 2 + 2 * n_st + 8) * sizeof(u256));
-  if (!w) return VDB_ERR_OOM;
-  AnnuWork k;
-  k.hdr = w;
-  k.ind = k.hdr + K + 2;
-  k.picked = k.ind + K;
-  k.words_new = k.picked + 1;
-  k.iroot = k.words_new + K + 1;
-  k.upub = k.iroot + 2;
-  k.st_old = k.upub + 3 * m + 2;
-  k.st_new = k.st_old + n_st;
-  TRY(inv_list_attach(st, a.b.total));
-  FpEntry* fp;
-  const PoseidonSpec* sp;
-  TRY(mk_begin(st, &fp, &sp));
-  const uint32_t Ku = (uint32_t)K, cu = (uint32_t)cluster, nperm = a.mw.nperm;
-  const u256* words_old = k.hdr + 1;
-  VDB_LAUNCH(k_annu_header, dim3((unsigned)((K + 2 + 255) / 256)), dim3(256), st, 0, cu, roots, Ku, k.hdr);
-  VDB_LAUNCH(k_annu_indicator, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, a.b.b_ind, cu, Ku, k.ind);
-  const NvMap sm{a.b.b_sel, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, Ku, 1u, 1u};
-  VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), st, fp->dev, sm, 1u, words_old + 1, k.ind, k.picked);
-  TRY(mk_leaf_states(sp, words_old, 1u, Ku + 1, nperm, k.st_old, k.iroot, nullptr));
-  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((nperm + 63) / 64)), dim3(64), st, fp->dev, sp, words_old, 1u, Ku + 1, nperm, a.b.b_old, a.mw.leaf_cells,
-             k.st_old, nullptr);
-  TRY(mku_emit(fp, sp, pl, levels, dim, new_vectors, st, a.b.b_upd, k.upub));
-  VDB_LAUNCH(k_annu_new_roots, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, a.b.b_new, Ku, k.upub + 3 * m + 1, words_old, k.ind, k.words_new);
-  TRY(mk_leaf_states(sp, k.words_new, 1u, Ku + 1, nperm, k.st_new, k.iroot + 1, nullptr));
-  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((nperm + 63) / 64)), dim3(64), st, fp->dev, sp, k.words_new, 1u, Ku + 1, nperm, a.b.b_root, a.mw.leaf_cells,
-             k.st_new, nullptr);
-  VDB_LAUNCH(k_annu_public, dim3((unsigned)((3 * m + 3 + 255) / 256)), dim3(256), k.upub, k.hdr, k.iroot, (uint32_t)m, pub);
-  return inv_list_fixup(st);
+  AnnFrame f;
+  TRY(f.open(st, roots, K, cluster, a, 3 * m + 2, 0));
+  TRY(mku_emit(f.fp, f.sp, pl, levels, dim, new_vectors, f.st, a.b.b_upd, f.upub));
+  TRY(f.close(f.upub + 3 * m + 1));
+  VDB_LAUNCH(k_annu_public, dim3((unsigned)((3 * m + 3 + 255) / 256)), dim3(256), f.upub, f.hdr, f.iroot, (uint32_t)m, pub);
+  return inv_list_fixup(f.st);
 }
 
 // ------------------------------------------------------------------ deletes against the index root (include/vdb.h vdb_wit_ann_delete,
@@ -1991,11 +2014,7 @@ int wit_ann_update_dev(u256* levels, const u256* roots, size_t K, size_t cluster
 // j: the last member's leaf carried into slot_j, then the last slot emptied: annd_expand), and when the cluster's tree halves s >= 1
 // times block S between E' and F proves that the dropped half is empty: [S_0 assigned | Z_0 = load_constant(0) | Z_{l+1} = H(Z_l, Z_l),
 // l < d - 1 | S_{i+1} = H(S_i, Z_{d-s+i}), i < s].  The map ties S_s to E's final root; F's `a` copies S_0, the root of the halved tree.
-struct AnndLayout {
-  MkLayout mw;
-  AnndBlocks b;
-  uint32_t depth, shrink;
-};
+
 // Block S, a lane per permutation of its d - 1 + s node hashes, in the form of k_mku_grow_trace; every input is resident: Z_l in `empty`,
 // S_i at entry 0 of level d - s + i of `levels` once k_mku_writeback has run.  Lane 0 also assigns S_0 and keeps it for block F.
 __global__ __launch_bounds__(64) void k_annd_shrink_trace(Streams stq, const FpTables* __restrict__ T, const PoseidonSpec* __restrict__ sp, uint64_t base,
@@ -2029,27 +2048,21 @@ __global__ __launch_bounds__(256) void k_annd_public(const u256* __restrict__ up
   pub[i] = upub[1 + 6 * (size_t)j + (k == 0 ? 0 : k == 1 ? 1 : k == 2 ? 3 : 2)];
 }
 // the host side of a delete batch, before anything is launched: the expansion to 2 m path updates and every refusal
-static int annd_layout(size_t K, size_t cluster, size_t n_c, size_t dim, const uint64_t* slots, size_t m, AnndLayout* o, MkuLayout* ml, AnndPlan* dp) {
-  VDB_ARG(K > 0 && K <= VDB_ANN_MAX_CLUSTERS, "K = 0 or K above VDB_ANN_MAX_CLUSTERS");
-  VDB_ARG(cluster < K, "cluster >= K");
-  VDB_ARG(n_c <= VDB_ANN_MAX_VECTORS, "cluster larger than VDB_ANN_MAX_VECTORS");
-  VDB_ARG(m > 0 && m <= MKU_MAX_UPDATES / 2, "a batch holds 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES / 2 deletes (two path updates each)");
-  VDB_ARG(m < n_c, "the batch would empty the cluster");
-  static thread_local std::vector<uint64_t> none;
-  if (!slots) {   // the size call: the shape does not depend on the slots
-    none.assign(m, 0);
-    slots = none.data();
-  }
-  const int rc = annd_expand(slots, m, n_c, MKU_MAX_UPDATES, dp, nullptr);
-  VDB_ARG(rc != 3, "a slot at or above the cluster's fill at its turn (every delete lowers the fill by one)");
-  VDB_ARG(rc == 0, "a batch holds at least one delete and leaves at least one member");
-  TRY(mku_layout(n_c, dim, 2 * m, dp->kinds.data(), 0, ml, nullptr, nullptr, nullptr, true));
-  mk_layout(1, K + 1, 1, &o->mw);
-  o->depth = dp->depth;
-  o->shrink = dp->shrink;
-  o->b = annd_blocks(K, o->mw.total, ml->total, annd_shrink_cells(dp->depth, dp->shrink, NODE_CELLS));
-  VDB_ARG(o->b.b.total <= ((uint64_t)1 << 34), "more than VDB_MERKLE_UPDATE_MAX_CELLS cells in one call");
-  return VDB_OK;
+static int annd_layout(size_t K, size_t cluster, size_t n_c, size_t dim, const uint64_t* slots, size_t m, AnnuLayout* o, MkuLayout* ml, AnndPlan* dp) {
+  return ann_frame_layout(K, cluster, n_c, o, ml, [&](uint64_t* shrink_cells) -> int {
+    VDB_ARG(m > 0 && m <= MKU_MAX_UPDATES / 2, "a batch holds 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES / 2 deletes (two path updates each)");
+    VDB_ARG(m < n_c, "the batch would empty the cluster");
+    static thread_local std::vector<uint64_t> none;
+    if (!slots) {   // the size call: the shape does not depend on the slots
+      none.assign(m, 0);
+      slots = none.data();
+    }
+    const int rc = annd_expand(slots, m, n_c, MKU_MAX_UPDATES, dp, nullptr);
+    VDB_ARG(rc != 3, "a slot at or above the cluster's fill at its turn (every delete lowers the fill by one)");
+    VDB_ARG(rc == 0, "a batch holds at least one delete and leaves at least one member");
+    *shrink_cells = annd_shrink_cells(dp->depth, dp->shrink, NODE_CELLS);
+    return mku_layout(n_c, dim, 2 * m, dp->kinds.data(), 0, ml, nullptr, nullptr, nullptr, true);
+  });
 }
 // roots: [centroids_root | the K cluster roots] of the index before the batch; levels: cluster c's tree over its n_c members, left in
 // the state after the batch (at its old size: vdb_ann_index_remove_dev cuts it); pub: 4 m + 3
@@ -2057,51 +2070,24 @@ int wit_ann_delete_dev(u256* levels, const u256* roots, size_t K, size_t cluster
                        u256* pub) {
   static thread_local MkuPlan pl;
   static thread_local AnndPlan dp;
-  AnndLayout a;
+  AnnuLayout a;
   MkuLayout ml0;
   VDB_ARG(slots, "null pointer");
   TRY(annd_layout(K, cluster, n_c, dim, slots, m, &a, &ml0, &dp));
   TRY(mku_plan(n_c, dim, 0, nullptr, dp.indices.data(), dp.kinds.data(), 2 * m, &pl, dp.carry_src.data()));
   const u256* empty = nullptr;
-  if (a.shrink) TRY(poseidon_empty_subtrees_dev(&empty));
-  const AnnuBlocks& b = a.b.b;
-  const size_t n_st = (size_t)a.mw.nperm * PSD_T, n_up = 6 * m + 2;
-  u256* w = (u256*)scratch_get(7, (2 * (K + 2) + K + 1 + 2 + n_up + 1 + 2 * n_st + 8) * sizeof(u256));
-  if (!w) return VDB_ERR_OOM;
-  AnnuWork k;
-  k.hdr = w;
-  k.ind = k.hdr + K + 2;
-  k.picked = k.ind + K;
-  k.words_new = k.picked + 1;
-  k.iroot = k.words_new + K + 1;
-  k.upub = k.iroot + 2;
-  u256* s0 = k.upub + n_up;
-  k.st_old = s0 + 1;
-  k.st_new = k.st_old + n_st;
-  TRY(inv_list_attach(st, b.total));
-  FpEntry* fp;
-  const PoseidonSpec* sp;
-  TRY(mk_begin(st, &fp, &sp));
-  const uint32_t Ku = (uint32_t)K, cu = (uint32_t)cluster, nperm = a.mw.nperm;
-  const u256* words_old = k.hdr + 1;
-  VDB_LAUNCH(k_annu_header, dim3((unsigned)((K + 2 + 255) / 256)), dim3(256), st, 0, cu, roots, Ku, k.hdr);
-  VDB_LAUNCH(k_annu_indicator, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, b.b_ind, cu, Ku, k.ind);
-  const NvMap sm{b.b_sel, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, Ku, 1u, 1u};
-  VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), st, fp->dev, sm, 1u, words_old + 1, k.ind, k.picked);
-  TRY(mk_leaf_states(sp, words_old, 1u, Ku + 1, nperm, k.st_old, k.iroot, nullptr));
-  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((nperm + 63) / 64)), dim3(64), st, fp->dev, sp, words_old, 1u, Ku + 1, nperm, b.b_old, a.mw.leaf_cells,
-             k.st_old, nullptr);
-  TRY(mku_emit(fp, sp, pl, levels, dim, nullptr, st, b.b_upd, k.upub));
-  if (a.shrink)  // S_i are the halved tree's top digests as the write-back left them
-    VDB_LAUNCH(k_annd_shrink_trace, dim3((unsigned)((2 * (a.depth - 1 + a.shrink) + 63) / 64)), dim3(64), st, fp->dev, sp, a.b.b_shr, a.depth, a.shrink, pl.lp,
-               levels, empty, s0);
-  VDB_LAUNCH(k_annu_new_roots, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, b.b_new, Ku, a.shrink ? s0 : k.upub + n_up - 1, words_old, k.ind,
-             k.words_new);
-  TRY(mk_leaf_states(sp, k.words_new, 1u, Ku + 1, nperm, k.st_new, k.iroot + 1, nullptr));
-  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((nperm + 63) / 64)), dim3(64), st, fp->dev, sp, k.words_new, 1u, Ku + 1, nperm, b.b_root, a.mw.leaf_cells,
-             k.st_new, nullptr);
-  VDB_LAUNCH(k_annd_public, dim3((unsigned)((4 * m + 3 + 255) / 256)), dim3(256), k.upub, k.hdr, k.iroot, (uint32_t)m, pub);
-  return inv_list_fixup(st);
+  if (dp.shrink) TRY(poseidon_empty_subtrees_dev(&empty));
+  const size_t n_up = 6 * m + 2;
+  AnnFrame f;
+  TRY(f.open(st, roots, K, cluster, a, n_up, 1));
+  u256* s0 = f.extra;
+  TRY(mku_emit(f.fp, f.sp, pl, levels, dim, nullptr, f.st, a.b.b_upd, f.upub));
+  if (dp.shrink)  // S_i are the halved tree's top digests as the write-back left them
+    VDB_LAUNCH(k_annd_shrink_trace, dim3((unsigned)((2 * (dp.depth - 1 + dp.shrink) + 63) / 64)), dim3(64), f.st, f.fp->dev, f.sp, a.b.b_shr, dp.depth, dp.shrink,
+               pl.lp, levels, empty, s0);
+  TRY(f.close(dp.shrink ? s0 : f.upub + n_up - 1));
+  VDB_LAUNCH(k_annd_public, dim3((unsigned)((4 * m + 3 + 255) / 256)), dim3(256), f.upub, f.hdr, f.iroot, (uint32_t)m, pub);
+  return inv_list_fixup(f.st);
 }
 
 }  // namespace vdb
@@ -2158,6 +2144,23 @@ struct DevStreams {
   }
   int finish() { return st.err ? check_err_flag(st.err) : VDB_OK; }
 };
+
+// What the host-array entry points of the two circuits against the index root share: the cluster's 2 lp levels and the K + 1 roots go
+// up, run(levels, roots, streams, public) emits the circuit, the public row and the levels as the batch left them come back.
+template <class Run>
+static int ann_batch_host(vdb_fr* levels, uint64_t lp, const vdb_fr* roots, size_t K, uint64_t cells, size_t n_pub, vdb_fr* stream_out, uint8_t* selector_out,
+                          vdb_fr* public_out, Run run) {
+  DevBuf dl, dr, dpub;
+  HostStreams hs;
+  TRY(upload(dl, levels, 2 * lp * sizeof(u256)));
+  TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
+  TRY(dpub.alloc(n_pub * sizeof(u256)));
+  TRY(hs.init(cells, 0, selector_out != nullptr));
+  TRY(run(dl.as<u256>(), dr.as<u256>(), hs.st, dpub.as<u256>()));
+  TRY(download(public_out, dpub.p, n_pub * sizeof(u256)));
+  TRY(download(levels, dl.p, 2 * lp * sizeof(u256)));
+  return hs.finish(stream_out, nullptr, selector_out, cells, 0);
+}
 
 extern "C" {
 
@@ -2611,31 +2614,25 @@ int vdb_wit_ann_update(vdb_fr* levels, const vdb_fr* roots, size_t K, size_t clu
   tree_shape(n_c, &lp, &d);
   lp <<= grow;
   VDB_ARG(annu_track_fill(indices, m, n_c, lp, nullptr, nullptr) == 0, "a write above the cluster's fill at its turn or outside the grown tree");
-  DevBuf dl, dr, dv, dpub;
-  HostStreams hs;
-  TRY(upload(dl, levels, 2 * lp * sizeof(u256)));
-  TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
+  DevBuf dv;
   TRY(upload(dv, new_vectors, ml.n_vec * sizeof(u256)));
-  TRY(dpub.alloc((3 * m + 3) * sizeof(u256)));
-  TRY(hs.init(a.b.total, 0, selector_out != nullptr));
-  TRY(wit_ann_update_dev(dl.as<u256>(), dr.as<u256>(), K, cluster, n_c, dim, grow, dv.as<u256>(), indices, m, hs.st, dpub.as<u256>()));
-  TRY(download(public_out, dpub.p, (3 * m + 3) * sizeof(u256)));
-  TRY(download(levels, dl.p, 2 * lp * sizeof(u256)));
-  return hs.finish(stream_out, nullptr, selector_out, a.b.total, 0);
+  return ann_batch_host(levels, lp, roots, K, a.b.total, 3 * m + 3, stream_out, selector_out, public_out, [&](u256* dl, const u256* dr, Streams st, u256* dpub) {
+    return wit_ann_update_dev(dl, dr, K, cluster, n_c, dim, grow, dv.as<u256>(), indices, m, st, dpub);
+  });
 }
 
 // deletes against the index root (include/vdb.h); the index after them: resident.hip
 int vdb_wit_ann_delete_size(size_t K, size_t n_c, size_t dim, size_t m, uint64_t* cells, uint64_t* input_cells, uint64_t* update_base, uint64_t* shrink_base,
                             unsigned* shrink) {
-  AnndLayout a;
+  AnnuLayout a;
   MkuLayout ml;
   AnndPlan dp;
   TRY(annd_layout(K, 0, n_c, dim, nullptr, m, &a, &ml, &dp));
-  if (cells) *cells = a.b.b.total;
-  if (input_cells) *input_cells = a.b.b.n_in;
-  if (update_base) *update_base = a.b.b.b_upd;
+  if (cells) *cells = a.b.total;
+  if (input_cells) *input_cells = a.b.n_in;
+  if (update_base) *update_base = a.b.b_upd;
   if (shrink_base) *shrink_base = a.b.b_shr;
-  if (shrink) *shrink = a.shrink;
+  if (shrink) *shrink = dp.shrink;
   return VDB_OK;
 }
 int vdb_wit_ann_delete_dev(vdb_fr* levels_dev, const vdb_fr* roots_dev, size_t K, size_t cluster, size_t n_c, size_t dim, const uint64_t* slots, size_t m,
@@ -2651,20 +2648,13 @@ int vdb_wit_ann_delete(vdb_fr* levels, const vdb_fr* roots, size_t K, size_t clu
                        vdb_fr* stream_out, uint8_t* selector_out, vdb_fr* public_out) {
   VDB_REQUIRE_INIT();
   VDB_ARG(levels && roots && slots, "null pointer");
-  AnndLayout a;
+  AnnuLayout a;
   MkuLayout ml;
   AnndPlan dp;
   TRY(annd_layout(K, cluster, n_c, dim, slots, m, &a, &ml, &dp));
-  DevBuf dl, dr, dpub;
-  HostStreams hs;
-  TRY(upload(dl, levels, 2 * dp.lp * sizeof(u256)));
-  TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
-  TRY(dpub.alloc((4 * m + 3) * sizeof(u256)));
-  TRY(hs.init(a.b.b.total, 0, selector_out != nullptr));
-  TRY(wit_ann_delete_dev(dl.as<u256>(), dr.as<u256>(), K, cluster, n_c, dim, slots, m, hs.st, dpub.as<u256>()));
-  TRY(download(public_out, dpub.p, (4 * m + 3) * sizeof(u256)));
-  TRY(download(levels, dl.p, 2 * dp.lp * sizeof(u256)));
-  return hs.finish(stream_out, nullptr, selector_out, a.b.b.total, 0);
+  return ann_batch_host(levels, dp.lp, roots, K, a.b.total, 4 * m + 3, stream_out, selector_out, public_out, [&](u256* dl, const u256* dr, Streams st, u256* dpub) {
+    return wit_ann_delete_dev(dl, dr, K, cluster, n_c, dim, slots, m, st, dpub);
+  });
 }
 
 }  // extern "C"

@@ -1408,7 +1408,49 @@ class AnnQueryHotPath(HotPath):
         return cm, public, None
 
 
-class AnnUpdateHotPath(PoseidonHotPath):
+class _AnnBatchHotPath(PoseidonHotPath):
+    """What the proofs of a batch against the committed index root share (AnnUpdateHotPath, AnnDeleteHotPath): the cluster c of an
+    AnnIndex, its tree before the batch (`d_levels0`) and the copy every witness run works on (`d_levels`), the public row `d_pub` of
+    `n_public` values, the map.  A subclass sets lp, depth, m, n_public and given_levels, and gives _circuit_size, _call(sel): the
+    library's witness call on these buffers -> its return code, and _builder(CS): (circuit_sym's build function, its own keywords)."""
+
+    def _cluster_size(self, index, cluster):
+        """binds the hot path to cluster c of the index -> n_c"""
+        self.index, self.K, self.cluster = index, index.K, int(cluster)
+        if not 0 <= self.cluster < self.K:
+            raise ValueError("cluster outside the index")
+        return int(index.sizes[self.cluster])
+
+    def _load_inputs(self, grow=0):
+        super()._load_inputs()
+        self.d_levels0 = self._output(2 * self.lp * B)
+        self.d_levels = self._output(2 * self.lp * B)
+        d_given = self.d_levels if grow else self.d_levels0      # a tree that has yet to be grown into d_levels0 waits in d_levels
+        self._load_tree(d_given, self.lp >> grow, self.index.levels(self.cluster) if self.given_levels is None else self.given_levels)
+
+    def _alloc_outputs(self):
+        self.d_pub = self._output(self.n_public * B)
+
+    def _witness(self, sel=None):
+        # the call writes the assigned header too; every run starts from the cluster's tree before the batch
+        check(self.lib.vdb_memcpy_d2d(self.d_levels.ptr, self.d_levels0.ptr, ctypes.c_size_t(2 * self.lp * B)))
+        with self._window(sel, 0, lookup=False):
+            check(self._call(self._sel_at(sel, 0)))
+
+    def public_values_dev(self):
+        return self.d_pub.ptr, self.n_public
+
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        build, kw = self._builder(CS)
+        cm, pub, _ = build(self.K, self.m, self.dim, self.depth, functools.partial(self._fetch_flags, d_flags), self._fetch,
+                           builder=DeviceBuilder if on_device else None, **kw)
+        assert cm.n_cells == self.n_cells
+        return cm, pub, None
+
+
+class AnnUpdateHotPath(_AnnBatchHotPath):
     """Inserts and replacements proved against the committed index root: m writes into ONE cluster c of an AnnIndex in one proof (include/vdb.h
     vdb_wit_ann_update).  Assigned: [c | centroids' root | cluster roots]; then idx_to_indicator(c, K), select_by_indicator(cluster roots,
     indicators) tied to the old root of the update block, the sponge over the roots (index_root_old), UpdateHotPath's whole circuit on the
@@ -1427,10 +1469,7 @@ class AnnUpdateHotPath(PoseidonHotPath):
         m = self.indices.shape[0]
         if m < 1:
             raise ValueError("a batch holds at least one write")
-        self.index, self.K, self.cluster = index, index.K, int(cluster)
-        if not 0 <= self.cluster < self.K:
-            raise ValueError("cluster outside the index")
-        n_c = int(index.sizes[self.cluster])
+        n_c = self._cluster_size(index, cluster)
         fill = n_c
         for s in self.indices.tolist():
             if s > fill:
@@ -1448,19 +1487,15 @@ class AnnUpdateHotPath(PoseidonHotPath):
             raise ValueError("a tree of one leaf has no path: grow it")
         super().__init__(n_c, index.dim, k, index.P, L, seed=None, tau=tau, col_shard=col_shard,
                          vectors=np.ascontiguousarray(rows, dtype=np.float64).reshape(m, index.dim), blind_seed=blind_seed, params=params)
-        self.m, self.given_levels = m, levels
+        self.m, self.n_public, self.given_levels = m, 3 * m + 3, levels
 
     def n_input_rows(self):
         return self.m
 
     def _load_inputs(self):
-        super()._load_inputs()
-        self.d_levels0 = self._output(2 * self.lp * B)
-        self.d_levels = self._output(2 * self.lp * B)
-        d_small = self.d_levels if self.grow else self.d_levels0
-        self._load_tree(d_small, self.lp0, self.index.levels(self.cluster) if self.given_levels is None else self.given_levels)
+        super()._load_inputs(self.grow)
         if self.grow:
-            check(self.lib.vdb_merkle_tree_grow_dev(d_small.ptr, self.n, self.grow, self.d_levels0.ptr))
+            check(self.lib.vdb_merkle_tree_grow_dev(self.d_levels.ptr, self.n, self.grow, self.d_levels0.ptr))
             api.sync()
 
     def _circuit_size(self):
@@ -1469,18 +1504,9 @@ class AnnUpdateHotPath(PoseidonHotPath):
         self.update_base = ub.value
         return n_in.value, cells.value - n_in.value, 0
 
-    def _alloc_outputs(self):
-        self.d_pub = self._output((3 * self.m + 3) * B)
-
-    def _witness(self, sel=None):
-        # the call writes the assigned header too; every run starts from the cluster's tree before the batch
-        check(self.lib.vdb_memcpy_d2d(self.d_levels.ptr, self.d_levels0.ptr, ctypes.c_size_t(2 * self.lp * B)))
-        with self._window(sel, 0, lookup=False):
-            check(self.lib.vdb_wit_ann_update_dev(self.d_levels.ptr, self.index.d_roots.ptr, self.K, self.cluster, self.n, self.dim, self.grow,
-                                                  self.d_vec.ptr, api._p(self.indices), self.m, self.d_stream.ptr, self._sel_at(sel, 0), self.d_pub.ptr))
-
-    def public_values_dev(self):
-        return self.d_pub.ptr, 3 * self.m + 3
+    def _call(self, sel):
+        return self.lib.vdb_wit_ann_update_dev(self.d_levels.ptr, self.index.d_roots.ptr, self.K, self.cluster, self.n, self.dim, self.grow, self.d_vec.ptr,
+                                               api._p(self.indices), self.m, self.d_stream.ptr, sel, self.d_pub.ptr)
 
     def results(self):
         """(index_root_old (4,), c (4,), indices (m, 4), old leaves (m, 4), new leaves (m, 4), index_root_new (4,))"""
@@ -1488,16 +1514,11 @@ class AnnUpdateHotPath(PoseidonHotPath):
         per = pub[2:-1].reshape(self.m, 3, 4)
         return pub[0], pub[1], per[:, 0], per[:, 1], per[:, 2], pub[-1]
 
-    def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        cm, pub, _ = CS.build_ann_update(self.K, self.m, self.dim, self.depth, functools.partial(self._fetch_flags, d_flags), self._fetch,
-                                         builder=DeviceBuilder if on_device else None, grow=self.grow)
-        assert cm.n_cells == self.n_cells
-        return cm, pub, None
+    def _builder(self, CS):
+        return CS.build_ann_update, dict(grow=self.grow)
 
 
-class AnnDeleteHotPath(PoseidonHotPath):
+class AnnDeleteHotPath(_AnnBatchHotPath):
     """Deletes proved against the committed index root: m deletes from ONE cluster c of an AnnIndex in one proof (include/vdb.h
     vdb_wit_ann_delete).  The members stay dense by swap-with-last: delete j moves the member at last_j = fill - 1 into slot_j and empties
     the last slot, two path updates of the cluster's tree (a carried leaf, then a delete); when the cluster drops to a power of two the
@@ -1512,10 +1533,7 @@ class AnnDeleteHotPath(PoseidonHotPath):
         place of the index's segment c (tests of the binding)."""
         self.slots = np.ascontiguousarray(slots, dtype=np.uint64)
         m = self.slots.shape[0]
-        self.index, self.K, self.cluster = index, index.K, int(cluster)
-        if not 0 <= self.cluster < self.K:
-            raise ValueError("cluster outside the index")
-        n_c = int(index.sizes[self.cluster])
+        n_c = self._cluster_size(index, cluster)
         if m < 1 or m >= n_c:
             raise ValueError("a batch holds at least one delete and leaves at least one member")
         origin = list(range(n_c))
@@ -1527,16 +1545,10 @@ class AnnDeleteHotPath(PoseidonHotPath):
         self.lp, self.depth = api.merkle_levels(n_c)
         super().__init__(n_c, index.dim, k, index.P, L, seed=None, tau=tau, col_shard=col_shard, vectors=np.zeros((0, index.dim)), blind_seed=blind_seed,
                          params=params)
-        self.m, self.given_levels = m, levels
+        self.m, self.n_public, self.given_levels = m, 4 * m + 3, levels
 
     def n_input_rows(self):
         return 0
-
-    def _load_inputs(self):
-        super()._load_inputs()
-        self.d_levels0 = self._output(2 * self.lp * B)
-        self.d_levels = self._output(2 * self.lp * B)
-        self._load_tree(self.d_levels0, self.lp, self.index.levels(self.cluster) if self.given_levels is None else self.given_levels)
 
     def _circuit_size(self):
         cells, n_in, ub, sb, s = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint()
@@ -1545,18 +1557,9 @@ class AnnDeleteHotPath(PoseidonHotPath):
         self.update_base, self.shrink_base, self.shrink = ub.value, sb.value, s.value
         return n_in.value, cells.value - n_in.value, 0
 
-    def _alloc_outputs(self):
-        self.d_pub = self._output((4 * self.m + 3) * B)
-
-    def _witness(self, sel=None):
-        # the call writes the assigned header too; every run starts from the cluster's tree before the batch
-        check(self.lib.vdb_memcpy_d2d(self.d_levels.ptr, self.d_levels0.ptr, ctypes.c_size_t(2 * self.lp * B)))
-        with self._window(sel, 0, lookup=False):
-            check(self.lib.vdb_wit_ann_delete_dev(self.d_levels.ptr, self.index.d_roots.ptr, self.K, self.cluster, self.n, self.dim, api._p(self.slots),
-                                                  self.m, self.d_stream.ptr, self._sel_at(sel, 0), self.d_pub.ptr))
-
-    def public_values_dev(self):
-        return self.d_pub.ptr, 4 * self.m + 3
+    def _call(self, sel):
+        return self.lib.vdb_wit_ann_delete_dev(self.d_levels.ptr, self.index.d_roots.ptr, self.K, self.cluster, self.n, self.dim, api._p(self.slots), self.m,
+                                               self.d_stream.ptr, sel, self.d_pub.ptr)
 
     def results(self):
         """(index_root_old (4,), c (4,), slots (m, 4), removed leaves (m, 4), last (m, 4), moved leaves (m, 4), index_root_new (4,))"""
@@ -1564,10 +1567,5 @@ class AnnDeleteHotPath(PoseidonHotPath):
         per = pub[2:-1].reshape(self.m, 4, 4)
         return pub[0], pub[1], per[:, 0], per[:, 1], per[:, 2], per[:, 3], pub[-1]
 
-    def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        cm, pub, _ = CS.build_ann_delete(self.K, self.m, self.dim, self.depth, functools.partial(self._fetch_flags, d_flags), self._fetch,
-                                         builder=DeviceBuilder if on_device else None, shrink=self.shrink)
-        assert cm.n_cells == self.n_cells
-        return cm, pub, None
+    def _builder(self, CS):
+        return CS.build_ann_delete, dict(shrink=self.shrink)

@@ -121,6 +121,45 @@ def test_traced_and_built_maps_agree_and_only_the_zero_operands_inverse_is_free(
         assert AM.violations(AM.recount(bm, alt, np.asarray([], dtype=object), 8, [int(x) for x in bpub], inst)) >= 1, cell
 
 
+@pytest.mark.parametrize("K", [1, 3])
+@pytest.mark.parametrize("shrink", [0, 1])
+def test_update_and_delete_share_one_frame(O, K, shrink):
+    """Blocks A - D and F - G of the two circuits are the same cells: the layouts agree up to the inner block and, behind it, after
+    subtracting its cells; so do the maps' entries, F - G translated by the same amount.  The one operand of each select of F that
+    copies the new cluster root is the circuit's own, and is excluded."""
+    import ann_update_model as AU
+    depth, k = 3, 1
+    sizes = ((6, 2, 3), (5, 2, 3))[shrink][:K]               # 6 -> 5 keeps the tree's size, 5 -> 4 halves it
+    md, db, ids, cent, ix, tree = case(O, sizes, 0, [1], seed=9)
+    assert md["s"] == shrink and len(tree) - 1 == depth
+    mu = AU.update_model(O, ix["roots"][:K + 1], 0, MU.build_tree(O, AN.select_cluster(db, ids, 0)[0]), [1], database(O, 1, DIM, 11), 0)
+    lu, ld = CS.ann_update_layout(K, k, DIM, depth, 0), CS.ann_delete_layout(K, k, DIM, depth, shrink)
+    head = ("c", "centroids_root", "roots", "n_in", "indicator", "select", "sponge_old", "update", "sponge")
+    assert all(lu[x] == ld[x] for x in head)
+    inner_u, inner_d = lu["update_layout"]["total"], ld["update_layout"]["total"] + ld["shrink_cells"]
+    assert ld["shrink_cells"] == (2 + depth * 4506 if shrink else 0) and inner_d > inner_u
+    assert all(lu[x] - inner_u == ld[x] - inner_d for x in ("new_roots", "sponge_new", "total"))
+    n_head, n_tail = lu["update"], lu["total"] - lu["new_roots"]
+    a_operand = 8 * np.arange(K) + 3                         # select: [a - b, 1, b, a, b, sel, a - b, out]
+    keep = np.setdiff1d(np.arange(n_tail), a_operand)
+    fu, fd = fetchers(mu), fetchers(md)
+    for form_u, form_d in ((CS.trace_ann_update, CS.trace_ann_delete), (CS.build_ann_update, CS.build_ann_delete)):
+        (cu, _, iu), (cd, _, idl) = form_u(K, k, DIM, depth, fu[0], fu[1], grow=0), form_d(K, k, DIM, depth, fd[0], fd[1], shrink=shrink)
+        entries = []
+        for cm, lay, info in ((cu, lu, iu), (cd, ld, idl)):
+            cells = np.concatenate([np.arange(n_head), lay["new_roots"] + np.arange(n_tail)])
+            src = cm.copy_of[cells]
+            new_root = info["s0"] if shrink and cm is cd else info["new_root"]
+            assert np.all(src[n_head + a_operand] == new_root), "F's `a` copies the new cluster root"
+            inner = (src >= lay["update"]) & (src < lay["new_roots"])
+            assert np.flatnonzero(inner).tolist() == (n_head + a_operand).tolist(), "nothing else of the frame reads the inner block"
+            src = np.where(src >= lay["new_roots"], src - lay["new_roots"] + n_head, src)       # into the frame's own numbering
+            const = np.where(cm.const_idx[cells] >= 0, np.asarray(cm.consts + [0], dtype=object)[cm.const_idx[cells]], -1)
+            entries.append([x[np.concatenate([np.arange(n_head), n_head + keep])] for x in (src, const, cm.asserted[cells], cm.gate[cells])])
+        for x, y, name in zip(entries[0], entries[1], ("copy_of", "const", "asserted", "gate")):
+            assert np.array_equal(x, y), (form_u.__name__, name)
+
+
 def test_plain_update_maps_refuse_the_carried_kind():
     with pytest.raises(ValueError):
         CS.merkle_update_layout(2, DIM, 2, kinds=[2, 1])

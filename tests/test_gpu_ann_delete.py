@@ -134,9 +134,11 @@ def test_two_windowed_calls_write_the_bytes_of_one(api, O):
     try:
         d_roots, d_pub = _dev(api, up, s["ix"]["roots"][:K + 1]), _dev(api, up, np.zeros_like(pub))
         # in front of and behind a carried cell of E', inside its inputs and a level; in S: between S_0 and Z_0, inside a Z hash, inside an
-        # S hash; between S and F
+        # S hash; between S and F; the frame the call shares with the update: inside the header, inside an indicator block, between C and
+        # D, inside F, near the end
         for cut in (r["update"] + u["carried"][1], r["update"] + u["carried"][2] + 1, r["update"] + u["n_in"] - 2, r["update"] + u["regions"][2]["levels"][1] + 25,
-                    r["shrink"] + 1, r["shrink"] + 2 + 4506 + 31, r["new_roots"] - 4506 - 7, r["new_roots"]):
+                    r["shrink"] + 1, r["shrink"] + 2 + 4506 + 31, r["new_roots"] - 4506 - 7, r["new_roots"],
+                    2, r["indicator"] + 8 + 5, r["sponge_old"], r["new_roots"] + 11, cells - 3):
             halves = []
             for window in ((0, cut, 0, 0), (cut, cells, 0, 0)):
                 d_lv = _dev(api, up, s["before"])                   # every call starts from the tree before the batch

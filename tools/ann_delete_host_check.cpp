@@ -78,9 +78,9 @@ int main() {
     // the blocks
     const uint64_t K = 1 + rng() % 5, sc = annd_shrink_cells(p.depth, p.shrink, 4506);
     CHECK(sc == (p.shrink ? 2 + (uint64_t)(p.depth - 1 + p.shrink) * 4506 : 0));
-    const AnndBlocks b = annd_blocks(K, 1000, 77, sc);
+    const AnnuBlocks b = annu_blocks(K, 1000, 77, sc);
     const AnnuBlocks u = annu_blocks(K, 1000, 77);
-    CHECK(b.b.b_upd == u.b_upd && b.b_shr == u.b_upd + 77 && b.b.b_new == b.b_shr + sc && b.b.total == u.total + sc && b.b.b_root - b.b.b_new == 8 * K);
+    CHECK(b.b_upd == u.b_upd && b.b_shr == u.b_upd + 77 && b.b_new == b.b_shr + sc && b.total == u.total + sc && b.b_root - b.b_new == 8 * K);
     // the index after the batch
     const size_t c = rng() % K;
     std::vector<uint64_t> sizes(K);

@@ -37,7 +37,7 @@ int main() {
     const AnnuBlocks b = annu_blocks(K, 1000, 77);
     CHECK(b.n_in == K + 2 && b.b_ind == K + 2);
     CHECK(b.b_sel - b.b_ind == 8 + 12 * (K - 1));
-    CHECK(b.b_old - b.b_sel == 1 + 3 * K && b.b_upd - b.b_old == 1000 && b.b_new - b.b_upd == 77);
+    CHECK(b.b_old - b.b_sel == 1 + 3 * K && b.b_upd - b.b_old == 1000 && b.b_new - b.b_upd == 77 && b.b_shr == b.b_new);
     CHECK(b.b_root - b.b_new == 8 * K && b.total - b.b_root == 1000);
     uint64_t at = 0;
     for (uint64_t j = 0; j < K; j++) {
