@@ -377,6 +377,21 @@ def wit_nearest_topk(metric, queries, vectors, topk, P=48, L=13, selectors=False
     return dict(stream=stream, lookup=lookup, **_split_flags(sel), indicators=ind, results=res)
 
 
+def nearest_values(metric, queries, vectors, P=48, L=13):
+    """nearest_vector's answer for every row of `queries` (q, dim, 4) over `vectors` (n, dim, 4) as values alone (vdb_nearest_values: no
+    stream is emitted): (idx (q,) uint32, dist (q, 4)), dist the minimum of the circuit's fixed-point distance(vector_i, query) bit for
+    bit, idx the last i at it"""
+    lib = _lib.init()
+    queries, vectors = _fr(queries), _fr(vectors)
+    q, n, dim = queries.shape[0], vectors.shape[0], vectors.shape[1]
+    assert queries.ndim == 3 and vectors.ndim == 3 and queries.shape[1] == dim
+    idx = np.zeros(q, dtype=np.uint32)
+    dist = np.zeros((q, 4), dtype=np.uint64)
+    check(lib.vdb_nearest_values(ctypes.c_uint32(P), ctypes.c_uint32(L), METRICS[metric], _p(queries), _p(vectors), _sz(q), _sz(n), _sz(dim), _p(idx),
+                                 _p(dist)))
+    return idx, dist
+
+
 def wit_kmeans(metric, vectors, K, I, P=48, L=13, zero_cached=False, selectors=False):
     lib = _lib.init()
     vectors = _fr(vectors)

@@ -708,6 +708,45 @@ __global__ __launch_bounds__(64) void k_nv_rounds(const FpTables* __restrict__ T
     }
   }
 }
+// The minimum of a query's n distances and the LAST entry that holds it, as values alone (vdb_nearest_values_dev), one wavefront per
+// query.  `a before b` is qmin's own test, v_is_neg(a - b): the signed fixed-point order, not the order of the 256 raw bits (a negative
+// value is a field element near the modulus).  A lane folds entries lane, lane + 64, ... in rising order and moves to a later entry
+// unless its own comes strictly before it, so a tie leaves the later index; the 64 (value, index) pairs then meet in a butterfly that
+// keeps the earlier value and, between two values neither of which comes before the other, the larger index — both partners of an
+// exchange decide alike.  Lanes past the end start from entry 0, a real entry with the lowest index: it can never displace a winner.
+// Over values the range checks admit this is the serial fold's minimum (see k_nv_rounds on what lies outside them), and the index is
+// the last set indicator of nearest_vector's is_equal(min, d_i).
+__global__ __launch_bounds__(64) void k_nv_argmin(const u256* __restrict__ d, uint32_t n, uint32_t* __restrict__ idx_out, u256* __restrict__ dist_out) {
+  const uint32_t q = blockIdx.x, lane = threadIdx.x;
+  const u256* dq = d + (size_t)q * n;
+  WCtx c{};
+  Gadgets g(c);
+  uint32_t bi = lane < n ? lane : 0;
+  u256 best = dq[bi];
+  for (uint32_t i = lane + 64; i < n; i += 64) {
+    const u256 x = dq[i];
+    if (!g.v_is_neg(from_mont<Fr>(fr_sub(best, x)))) {
+      best = x;
+      bi = i;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    u256 o;
+#pragma unroll
+    for (int k = 0; k < 8; k++) o.w[k] = __shfl_xor(best.w[k], off, 64);
+    const uint32_t oi = __shfl_xor(bi, off, 64);
+    const bool o_first = g.v_is_neg(from_mont<Fr>(fr_sub(o, best))), b_first = g.v_is_neg(from_mont<Fr>(fr_sub(best, o)));
+    if (o_first || (!b_first && oi > bi)) {
+      best = o;
+      bi = oi;
+    }
+  }
+  if (lane == 0) {
+    idx_out[q] = bi;
+    if (dist_out) dist_out[q] = best;
+  }
+}
 // lanes = (query, round, link of the round's chain): qmin(pm[i - 1], cur_i), i = 1 .. n - 1
 __global__ __launch_bounds__(64) void k_nv_qmin(Streams st, const FpTables* __restrict__ T, NvMap nm, const u256* __restrict__ d,
                                                  const u256* __restrict__ pm, const uint32_t* __restrict__ rnd) {
@@ -1475,6 +1514,28 @@ int wit_nearest_dev(FpEntry* fp, int metric, const u256* queries, const u256* ve
   TRY(set_winv(st, fp->dev));
   TRY(nv_emit(fp, dl, nl, queries, vectors, Q, n, dim, topk, st, 0, 0, false, ind, result));
   return inv_list_fixup(st);
+}
+// nearest_vector's distances and their minimum as values alone (include/vdb.h vdb_nearest_values_dev): the distance generators run as
+// a rank runs them whose window holds no cell — k_dist_values and k_dist_tail_values compute, the emitting kernels leave at once — so the
+// arithmetic is stated where the circuit's is and no stream is attached; then one wavefront per query takes the minimum.  Instance
+// t = q * n + i is distance(vector_i, query_q), as in nv_emit.  The launch count depends on neither Q nor n.
+int nearest_values_dev(FpEntry* fp, int metric, const u256* queries, const u256* vectors, size_t Q, size_t n, size_t dim, int* err, uint32_t* idx,
+                       u256* dist_out) {
+  DistLayout dl;
+  NvLayout nl;
+  TRY(nv_layout(fp, metric, n, dim, 1, &dl, &nl));
+  TRY(nv_fits(Q, n, dim, 1, nl));
+  Streams st{nullptr, nullptr, nullptr, err, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};   // the empty rank window
+  TRY(inv_list_attach(st, 0));   // (an is_zero block outside every window defers nothing and inverts nothing)
+  TRY(set_winv(st, fp->dev));
+  const size_t inst = Q * n;
+  u256* mid = (u256*)scratch_get(0, inst * 4 * sizeof(u256));
+  if (!mid) return VDB_ERR_OOM;
+  u256* dist = mid + 3 * inst;
+  InstMap im{0, 0, (uint32_t)n, nl.total, nl.total_l, (uint32_t)n, (uint32_t)n};  // (vector_{t % n}, query_{t / n})
+  TRY(run_distances(st, fp, dl, im, (uint32_t)inst, vectors, queries, mid, dist));
+  VDB_LAUNCH(k_nv_argmin, dim3((unsigned)Q), dim3(64), dist, (uint32_t)n, idx, dist_out);
+  return VDB_OK;
 }
 
 static int km_layout(FpEntry* fp, int metric, size_t n, size_t dim, size_t K, DistLayout* dl, KmLayout* kl) {
@@ -2320,6 +2381,41 @@ int vdb_wit_nearest_topk_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* q
   TRY(wit_nearest_dev(fp, metric, as_u256(queries_dev), as_u256(vectors_dev), n_queries, n, dim, topk, ds.st, as_u256(indicators_dev),
                       as_u256(results_dev)));
   return ds.finish();
+}
+
+// the minimum distance of every query and the last vector at it, values only (include/vdb.h): no stream, no window
+int vdb_nearest_values_dev(uint32_t P, uint32_t L, int metric, const vdb_fr* queries_dev, const vdb_fr* vectors_dev, size_t n_queries, size_t n, size_t dim,
+                           uint32_t* idx_out_dev, vdb_fr* dist_out_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(queries_dev && vectors_dev && idx_out_dev && n_queries > 0 && n > 0 && dim > 0, "null pointer or empty input");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  int* derr = (int*)scratch_get(1, 64);
+  if (!derr) return VDB_ERR_OOM;
+  VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
+  TRY(nearest_values_dev(fp, metric, as_u256(queries_dev), as_u256(vectors_dev), n_queries, n, dim, derr, idx_out_dev, as_u256(dist_out_dev)));
+  return check_err_flag(derr);
+}
+int vdb_nearest_values(uint32_t P, uint32_t L, int metric, const vdb_fr* queries, const vdb_fr* vectors, size_t n_queries, size_t n, size_t dim,
+                       uint32_t* idx_out, vdb_fr* dist_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(queries && vectors && idx_out && n_queries > 0 && n > 0 && dim > 0, "null pointer or empty input");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  DistLayout dl;
+  NvLayout nl;
+  TRY(nv_layout(fp, metric, n, dim, 1, &dl, &nl));
+  TRY(nv_fits(n_queries, n, dim, 1, nl));   // before anything is uploaded
+  DevBuf dq, dv, didx, ddist;
+  TRY(upload(dq, queries, n_queries * dim * sizeof(u256)));
+  TRY(upload(dv, vectors, n * dim * sizeof(u256)));
+  TRY(didx.alloc(n_queries * sizeof(uint32_t)));
+  TRY(ddist.alloc(n_queries * sizeof(u256)));
+  TRY(vdb_nearest_values_dev(P, L, metric, dq.as<vdb_fr>(), dv.as<vdb_fr>(), n_queries, n, dim, didx.as<uint32_t>(), ddist.as<vdb_fr>()));
+  TRY(download(idx_out, didx.p, n_queries * sizeof(uint32_t)));
+  TRY(download(dist_out, ddist.p, n_queries * sizeof(u256)));
+  VDB_HIP(hipStreamSynchronize(ctx().stream));
+  return VDB_OK;
 }
 
 // nearest_vector (vectordb.rs:122-163) for n_queries queries over one database, the calls end to end in the streams

@@ -1326,6 +1326,25 @@ class AnnIndex:
         ind = api.wit_nearest(self.metric_name, q, self.qcent, self.P, self.L)["indicator"]
         return int(np.flatnonzero(ind.any(axis=1))[-1])
 
+    def assign(self, rows, distances=False):
+        """the cluster of every row of `rows` ((m, dim) f64): probe's answer for each — the last centroid at the minimum of the
+        circuit's fixed-point distance — in one values-only call against the resident centroids (vdb_nearest_values_dev: nothing is
+        emitted, the centroids are not uploaded).  (m,) int64; with `distances` also the (m, 4) minimum distances."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, self.dim)
+        m = rows.shape[0]
+        if m == 0:
+            return (np.zeros(0, dtype=np.int64), np.zeros((0, 4), dtype=np.uint64)) if distances else np.zeros(0, dtype=np.int64)
+        d_rows, d_idx, d_dist = api.DeviceBuffer(m * self.dim * B), api.DeviceBuffer(m * 4), api.DeviceBuffer(m * B)
+        try:
+            d_rows.upload(api.quantize(rows, self.P))
+            check(self.lib.vdb_nearest_values_dev(self.P, self.L, api.METRICS[self.metric_name], d_rows.ptr, self.d_cent.ptr, m, self.K, self.dim,
+                                                  d_idx.ptr, d_dist.ptr))
+            idx = d_idx.download((m,), dtype=np.uint32).astype(np.int64)
+            return (idx, d_dist.download((m, 4))) if distances else idx
+        finally:
+            for b in (d_rows, d_idx, d_dist):
+                b.free()
+
     def free(self):
         for b in self._bufs:
             b.free()

@@ -215,6 +215,19 @@ int vdb_wit_nearest_topk(int metric, uint32_t precision_bits, uint32_t lookup_bi
 int vdb_wit_nearest_topk_dev(int metric, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *queries_dev, const vdb_fr *vectors_dev,
                              size_t n_queries, size_t n, size_t dim, size_t topk, vdb_fr *stream_dev, vdb_fr *lookup_dev, uint8_t *selector_dev,
                              vdb_fr *indicators_dev, vdb_fr *results_dev);
+/* nearest_vector's answer as VALUES alone: for every query q the minimum over i of the circuit's fixed-point
+ * distance(vector_i, query_q) (src/gadget/vectordb.rs:138's argument order), bit for bit what vdb_wit_nearest_batch's qmin chain ends
+ * in, and the LAST i at that minimum, the index of nearest_vector's last set indicator.  No stream is written or attached: the distance
+ * generators run on their value-only path (those of a rank whose window holds no cell), then one wavefront per query takes the
+ * minimum in qmin's order, the signed fixed-point one.  Routing for a circuit that proves the choice (which cluster a written vector
+ * belongs to) has to use this arithmetic: a near-tie that f64 resolves differently is a different answer.
+ * idx_out n_queries x uint32; dist_out n_queries values, may be NULL.  The number of kernel launches depends on neither n_queries nor
+ * n.  Work space: 128 B per (query, vector).  vdb_wit_set_window does not apply.  VDB_ERR_ARG before anything is launched: n_queries,
+ * n or dim == 0, and vdb_wit_nearest_topk's limits at topk == 1; VDB_ERR_DOMAIN as for the witness call (cosine of a zero vector). */
+int vdb_nearest_values_dev(uint32_t precision_bits, uint32_t lookup_bits, int metric, const vdb_fr *queries_dev, const vdb_fr *vectors_dev,
+                           size_t n_queries, size_t n, size_t dim, uint32_t *idx_out_dev, vdb_fr *dist_out_dev);
+int vdb_nearest_values(uint32_t precision_bits, uint32_t lookup_bits, int metric, const vdb_fr *queries, const vdb_fr *vectors, size_t n_queries,
+                       size_t n, size_t dim, uint32_t *idx_out, vdb_fr *dist_out);
 /* VectorDBChip::kmeans::<K, I> (src/gadget/vectordb.rs:225-362): centroids K x dim, indicators n x K
  * (quantized 1.0 / 0).  zero_cached: Context::load_zero already called earlier in this context. */
 int vdb_wit_kmeans_size(int metric, uint32_t precision_bits, uint32_t lookup_bits, size_t n, size_t dim, size_t K, size_t I, int zero_cached,
