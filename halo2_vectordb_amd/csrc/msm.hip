@@ -17,9 +17,10 @@
 //    With wide windows (thousands of buckets, dense scalars) the scatter goes in two phases: entries to the 256 runs of coarse bins
 //    here, k_msm_scatter2 orders each bin in place through LDS — four-byte stores to 8,192 open runs per column do not merge in L2.
 //  * k_msm_accum: one thread per range (every lane does exactly LCAP mixed additions), XYZZ accumulator in VGPRs.
-//  * k_msm_combine: segmented tree reduction of the partials of every bucket.
+//  * k_msm_combine: segmented tree reduction of the partials of every bucket, in the accumulator's nine-limb form.
 //  * k_msm_reduce: one wavefront per column; each lane folds its slice of buckets with the running-sum
-//    trick, lanes are combined with wavefront shuffles, lane 0 normalises to affine.
+//    trick, lanes are combined with wavefront shuffles (nine-limb form throughout: ec_l9.hpp).
+//  * k_msm_normalise: one lane per column brings the column's sum to canonical affine (the inversion).
 // Roofline: algorithmic HBM traffic is 32 B per scalar (+ bases once); the kernels are bound by 32-bit
 // integer multiply-add throughput (v_mad_u64_u32), see DESIGN.md.
 #include "common.hpp"
@@ -41,8 +42,8 @@ namespace vdb {
 
 #define MSM_SORT_THREADS 1024
 // Range length (entries one thread of k_msm_accum adds up) is chosen per batch: long ranges mean fewer segments, i.e.
-// less work for k_msm_partials / k_msm_combine (256: 4 ms of combine on the k = 16 kmeans workload against 20 ms at
-// 32), short ranges keep small jobs parallel (a single 2^16 column has only ~130 k entries).
+// less work for k_msm_combine (256: 4 ms of combine on the k = 16 kmeans workload against 20 ms at 32, measured on the
+// eight-word folding), short ranges keep small jobs parallel (a single 2^16 column has only ~130 k entries).
 #define MSM_LCAP_MIN 32
 #define MSM_LCAP_MAX 256
 
@@ -476,9 +477,12 @@ __global__ __launch_bounds__(MSM_SCATTER2_THREADS) void k_msm_scatter2(uint32_t*
   }
 }
 
-// A segment's partial sum leaves k_msm_accum as raw limbs (36 words; zz = 0 encodes the identity): the conversion to
-// the standard form costs four products, and inside the accumulation loop a flush by ANY lane of a wavefront makes the
-// whole wavefront walk the flush code, so it has to be cheap.  k_msm_partials converts all segments afterwards.
+// A segment's partial sum leaves k_msm_accum as raw limbs (36 words; zz = 0 encodes the identity): inside the accumulation
+// loop a flush by ANY lane of a wavefront makes the whole wavefront walk the flush code, so it has to be cheap.  The bucket
+// folding works on these records as they are (xyzz_add_l9 takes and leaves the accumulator's form): k_msm_combine folds them
+// in place, k_msm_reduce reads them and leaves one such record per column, and only k_msm_normalise converts — one column's
+// sum, not every segment (a conversion kernel used to bring all segments to eight-word XYZZ: four products and a canonical
+// form each, which the folding then split into limbs again).
 #define MSM_RAW_WORDS 36
 __device__ __forceinline__ void flush_l9(uint4* dst, const AccL9& acc, bool ident) {
   const uint32_t z = ident ? 0u : 0xffffffffu;
@@ -492,38 +496,24 @@ __device__ __forceinline__ void flush_l9(uint4* dst, const AccL9& acc, bool iden
   dst[7] = make_uint4(acc.zzz.l[4], acc.zzz.l[5], acc.zzz.l[6], acc.zzz.l[7]);
   dst[8] = make_uint4(acc.x.l[8], acc.y.l[8], acc.zz.l[8] & z, acc.zzz.l[8]);
 }
-__global__ __launch_bounds__(256) void k_msm_partials(const uint4* __restrict__ raw, XYZZ* __restrict__ partials, const uint32_t* __restrict__ counters,
-                                                      uint32_t seg_cap, u256 to_std) {
-  if (counters[1]) return;
-  const uint32_t total = counters[0] < seg_cap ? counters[0] : seg_cap;
-  const uint32_t stride = gridDim.x * blockDim.x;
-  const L9 ts = l9_split(to_std);
-  for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-    const uint4* src = raw + (size_t)t * (MSM_RAW_WORDS / 4);
-    uint4 w[9];
+__device__ __forceinline__ void raw_l9_low8(L9& c, const uint4& a, const uint4& b) {
+  c.l[0] = a.x; c.l[1] = a.y; c.l[2] = a.z; c.l[3] = a.w;
+  c.l[4] = b.x; c.l[5] = b.y; c.l[6] = b.z; c.l[7] = b.w;
+}
+// the record back into registers (the identity carries no meaningful limbs besides its zero zz: a lazy zz of a point is never zero)
+__device__ __forceinline__ void ld_raw_l9(const uint4* src, AccL9& acc, bool& ident) {
+  uint4 w[9];
 #pragma unroll
-    for (int i = 0; i < 9; i++) w[i] = src[i];
-    L9 c[4];
+  for (int i = 0; i < 9; i++) w[i] = src[i];
+  raw_l9_low8(acc.x, w[0], w[1]);
+  raw_l9_low8(acc.y, w[2], w[3]);
+  raw_l9_low8(acc.zz, w[4], w[5]);
+  raw_l9_low8(acc.zzz, w[6], w[7]);
+  acc.x.l[8] = w[8].x; acc.y.l[8] = w[8].y; acc.zz.l[8] = w[8].z; acc.zzz.l[8] = w[8].w;
+  uint32_t zz_any = 0;
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
-      c[j].l[0] = w[2 * j].x; c[j].l[1] = w[2 * j].y; c[j].l[2] = w[2 * j].z; c[j].l[3] = w[2 * j].w;
-      c[j].l[4] = w[2 * j + 1].x; c[j].l[5] = w[2 * j + 1].y; c[j].l[6] = w[2 * j + 1].z; c[j].l[7] = w[2 * j + 1].w;
-    }
-    c[0].l[8] = w[8].x; c[1].l[8] = w[8].y; c[2].l[8] = w[8].z; c[3].l[8] = w[8].w;
-    uint32_t zz_any = 0;
-#pragma unroll
-    for (int k = 0; k < 9; k++) zz_any |= c[2].l[k];
-    XYZZ a;
-    if (!zz_any) {
-      a = xyzz_identity();
-    } else {
-      a.x = l9_canon<Fq>(l9_mul<Fq>(c[0], ts));
-      a.y = l9_canon<Fq>(l9_mul<Fq>(c[1], ts));
-      a.zz = l9_canon<Fq>(l9_mul<Fq>(c[2], ts));
-      a.zzz = l9_canon<Fq>(l9_mul<Fq>(c[3], ts));
-    }
-    st_xyzz(partials + t, a);
-  }
+  for (int k = 0; k < 9; k++) zz_any |= acc.zz.l[k];
+  ident = zz_any == 0;
 }
 
 // One thread per range: exactly `lcap` mixed additions per lane (full lane utilisation); the accumulator is
@@ -586,8 +576,8 @@ __global__ __launch_bounds__(256) void k_msm_accum(const Affine* __restrict__ ta
 // its first segment slot.  This is what removes the witness-column skew from the reduce kernel.
 // (Measured alternatives: radix-8 in-place folding — 2x slower, one active lane in eight; one thread per bucket — 8x
 // slower, serial tails of the heavy buckets.)
-__global__ __launch_bounds__(256) void k_msm_combine(XYZZ* __restrict__ partials, const MsmSegInfo* __restrict__ seginfo, const uint32_t* __restrict__ counters,
-                                                     uint32_t pass, uint32_t task_cap) {
+__global__ __launch_bounds__(256) void k_msm_combine(uint4* __restrict__ raw, const MsmSegInfo* __restrict__ seginfo, const uint32_t* __restrict__ counters,
+                                                     uint32_t pass, uint32_t task_cap, MsmL9Consts K) {
   if (counters[1]) return;
   if ((1u << pass) >= counters[2]) return;  // every bucket is already folded to one partial
   const uint32_t total = counters[0] < task_cap ? counters[0] : task_cap;
@@ -596,72 +586,114 @@ __global__ __launch_bounds__(256) void k_msm_combine(XYZZ* __restrict__ partials
     const MsmSegInfo si = seginfo[t];
     const uint32_t len = (si.len + (1u << pass) - 1) >> pass, half = (len + 1) >> 1;
     if (len <= 1 || si.idx + half >= len) continue;
-    XYZZ a = ld_xyzz(partials + t), b = ld_xyzz(partials + t + half);
-    xyzz_add(a, b);
-    st_xyzz(partials + t, a);
+    AccL9 a, b;
+    bool a_id, b_id;
+    ld_raw_l9(raw + (size_t)t * (MSM_RAW_WORDS / 4), a, a_id);
+    ld_raw_l9(raw + (size_t)(t + half) * (MSM_RAW_WORDS / 4), b, b_id);
+    xyzz_add_l9(a, a_id, b, b_id, K);
+    flush_l9(raw + (size_t)t * (MSM_RAW_WORDS / 4), a, a_id);
   }
 }
 
-__device__ __forceinline__ u256 shfl_u256(const u256& v, int src) {
-  u256 r;
+__device__ __forceinline__ L9 shfl_l9(const L9& v, int src) {
+  L9 r;
 #pragma unroll
-  for (int i = 0; i < 8; i++) r.w[i] = (uint32_t)__shfl((int)v.w[i], src, 64);
+  for (int i = 0; i < 9; i++) r.l[i] = (uint32_t)__shfl((int)v.l[i], src, 64);
   return r;
 }
-__device__ __forceinline__ XYZZ shfl_xyzz(const XYZZ& p, int src) {
-  XYZZ r;
-  r.x = shfl_u256(p.x, src);
-  r.y = shfl_u256(p.y, src);
-  r.zz = shfl_u256(p.zz, src);
-  r.zzz = shfl_u256(p.zzz, src);
+__device__ __forceinline__ AccL9 shfl_acc_l9(const AccL9& p, int src) {
+  AccL9 r;
+  r.x = shfl_l9(p.x, src);
+  r.y = shfl_l9(p.y, src);
+  r.zz = shfl_l9(p.zz, src);
+  r.zzz = shfl_l9(p.zzz, src);
+  return r;
+}
+__device__ __forceinline__ AccL9 acc_l9_zero() {
+  AccL9 r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.x.l[i] = r.y.l[i] = r.zz.l[i] = r.zzz.l[i] = 0;
   return r;
 }
 
-// One wavefront per column: result = sum_b b * B_b with B_b = sum of the partials of bucket b.
-__global__ __launch_bounds__(64) void k_msm_reduce(const XYZZ* __restrict__ partials, const uint32_t* __restrict__ task_off, uint32_t c,
-                                                   const uint32_t* __restrict__ counters, const Affine* __restrict__ add_points, Affine* __restrict__ out) {
+// One wavefront per column: result = sum_b b * B_b with B_b = sum of the partials of bucket b.  Everything stays in the
+// accumulator's nine-limb form (xyzz_add_l9); the column's sum leaves as one raw record, k_msm_normalise makes it affine.
+__global__ __launch_bounds__(64) void k_msm_reduce(const uint4* __restrict__ raw, const uint32_t* __restrict__ task_off, uint32_t c,
+                                                   const uint32_t* __restrict__ counters, const Affine* __restrict__ add_points, uint4* __restrict__ sums,
+                                                   MsmL9Consts K) {
   if (counters[1]) return;
   const uint32_t B = 1u << (c - 1);
   const uint32_t col = blockIdx.x, lane = threadIdx.x;
   const uint32_t log_per = c - 1 >= 6 ? c - 7 : 0, per = 1u << log_per;
   const uint32_t* toff = task_off + (size_t)col * (B + 1);
-  XYZZ running = xyzz_identity(), total = xyzz_identity();
+  AccL9 running = acc_l9_zero(), total = acc_l9_zero();
+  bool run_id = true, tot_id = true;
   const uint32_t lo = lane * per;  // bucket indices [lo, lo+per) <-> bucket ids lo+1 .. lo+per
   if (lo < B) {
     for (int b = (int)(lo + per) - 1; b >= (int)lo; b--) {
       uint32_t t0 = toff[b], t1 = toff[b + 1];
       if (t1 > t0) {  // bucket sum was folded into its first slot by k_msm_combine
-        XYZZ p = ld_xyzz(partials + t0);
-        xyzz_add(running, p);
+        AccL9 p;
+        bool p_id;
+        ld_raw_l9(raw + (size_t)t0 * (MSM_RAW_WORDS / 4), p, p_id);
+        xyzz_add_l9(running, run_id, p, p_id, K);
       }
-      xyzz_add(total, running);
+      xyzz_add_l9(total, tot_id, running, run_id, K);  // (a doubling whenever total still equals running: one bucket so far)
     }
   }
   // total_L = sum (b - lo) * B_b over the lane's ids; running_L = sum B_b.
-  // result = sum_L total_L + per * sum_L L * running_L
-  // suffix scan of running over lanes: suf_L = sum_{L' >= L} running_L'
-  XYZZ suf = running;
+  // result = sum_L total_L + per * sum_L L * running_L = sum_L (total_L + per * [L >= 1] suf_L)
+  // suffix scan of running over lanes: suf_L = sum_{L' >= L} running_L', and sum_{L >= 1} suf_L = sum_L L * running_L
   for (int o = 1; o < 64; o <<= 1) {
-    XYZZ other = shfl_xyzz(suf, (int)lane + o < 64 ? (int)lane + o : (int)lane);
-    if ((int)lane + o < 64) xyzz_add(suf, other);
+    const int src = (int)lane + o < 64 ? (int)lane + o : (int)lane;
+    const AccL9 other = shfl_acc_l9(running, src);
+    const bool other_id = __shfl((int)run_id, src, 64) != 0;
+    if ((int)lane + o < 64) xyzz_add_l9(running, run_id, other, other_id, K);
   }
-  // sum_{L>=1} suf_L = sum_L L * running_L
-  XYZZ t2 = lane >= 1 ? suf : xyzz_identity();
-  XYZZ t1 = total;
+  // every lane scales its own suffix sum (all lanes double together) and folds it into its total: one accumulator, not two, goes
+  // through the tree
+  if (lane == 0) run_id = true;
+  for (uint32_t d = 0; d < log_per; d++) xyzz_dbl_l9(running, run_id, K);
+  xyzz_add_l9(total, tot_id, running, run_id, K);
   for (int o = 32; o >= 1; o >>= 1) {
-    XYZZ a = shfl_xyzz(t1, (int)lane + o < 64 ? (int)lane + o : (int)lane);
-    XYZZ b = shfl_xyzz(t2, (int)lane + o < 64 ? (int)lane + o : (int)lane);
-    if ((int)lane < o) {
-      xyzz_add(t1, a);
-      xyzz_add(t2, b);
-    }
+    const int src = (int)lane + o < 64 ? (int)lane + o : (int)lane;
+    const AccL9 other = shfl_acc_l9(total, src);
+    const bool other_id = __shfl((int)tot_id, src, 64) != 0;
+    if ((int)lane < o) xyzz_add_l9(total, tot_id, other, other_id, K);
   }
   if (lane == 0) {
-    for (uint32_t d = 0; d < log_per; d++) t2 = xyzz_double(t2);
-    xyzz_add(t1, t2);
-    if (add_points) xyzz_add_mixed(t1, ld_affine(add_points + col), false);  // + precomputed constant-cell part
-    st_affine(out + col, xyzz_to_affine(t1));
+    if (add_points) {  // + precomputed constant-cell part: a canonical affine point in standard form, times 32 for the accumulator's R'
+      Affine ap = ld_affine(add_points + col);
+      if (!affine_is_identity(ap)) {
+        ap.x = fq_mul(ap.x, K.one_rp);
+        ap.y = fq_mul(ap.y, K.one_rp);
+        madd_l9(total, tot_id, ap, false, K);
+      }
+    }
+    flush_l9(sums + (size_t)col * (MSM_RAW_WORDS / 4), total, tot_id);
   }
+}
+
+// One LANE per column: the column's sum out of the accumulator's form (four products by 2^256: R' -> R, canonical) and to the canonical
+// affine point, identity (0, 0).  The Fermat inversion — some 380 dependent products — runs in 64 columns per wavefront here; at the end of
+// k_msm_reduce it held a whole wavefront and its registers for one lane's chain.
+__global__ __launch_bounds__(64) void k_msm_normalise(const uint4* __restrict__ sums, uint32_t n_cols, const uint32_t* __restrict__ counters, u256 to_std,
+                                                      Affine* __restrict__ out) {
+  if (counters[1]) return;
+  const uint32_t col = blockIdx.x * blockDim.x + threadIdx.x;
+  if (col >= n_cols) return;
+  AccL9 a;
+  bool ident;
+  ld_raw_l9(sums + (size_t)col * (MSM_RAW_WORDS / 4), a, ident);
+  XYZZ p = xyzz_identity();
+  if (!ident) {
+    const L9 ts = l9_split(to_std);
+    p.x = l9_canon<Fq>(l9_mul<Fq>(a.x, ts));
+    p.y = l9_canon<Fq>(l9_mul<Fq>(a.y, ts));
+    p.zz = l9_canon<Fq>(l9_mul<Fq>(a.zz, ts));
+    p.zzz = l9_canon<Fq>(l9_mul<Fq>(a.zzz, ts));
+  }
+  st_affine(out + col, xyzz_to_affine(p));
 }
 
 
@@ -710,9 +742,13 @@ static uint32_t pick_window(uint32_t k) {
 }
 
 // device-level batched MSM: scalars_dev = n_cols x n (contiguous), out_dev = n_cols affine points
-// `defer_tail`: the bucket folding of the LAST batch (k_msm_combine, k_msm_reduce: short latency-bound launches that
-// leave most of the chip idle) goes to the context's auxiliary stream and the function returns without waiting;
-// msm_collect() joins.  The scalars are no longer read at that point, so the caller may overwrite them (NTT in place).
+// `defer_tail`: the bucket folding of the LAST batch (k_msm_combine, k_msm_reduce, k_msm_normalise) goes to the context's
+// auxiliary stream and the function returns without waiting; msm_collect() joins.  The scalars are no longer read at that
+// point, so the caller may overwrite them (NTT in place).  The folding is not free there: it fills the chip's issue slots
+// and registers like any other kernel, and the transform launches that run beside it take longer by most of what it costs
+// alone (profiles/NOTES.md, "bucket folding beside the transforms": the first two launches of lagrange_to_coeff, 2.3 and
+// 2.1 ms alone, took 4.9 and 6.5 ms beside the eight-word folding and its 213-register k_msm_reduce, 5.1 and 3.4 ms beside
+// this one).  What it saves is the dependency: the transforms need not wait for the commitments.
 int msm_batch_dev(const vdb_srs* srs, int basis, const u256* scalars_dev, size_t n_cols, size_t n, Affine* out_dev, const uint8_t* skip_mask = nullptr,
                   const Affine* add_points = nullptr, bool defer_tail = false, const ColSrc* srcs = nullptr, uint32_t n_blind = 0) {
   Context& cx = ctx();
@@ -730,7 +766,7 @@ int msm_batch_dev(const vdb_srs* srs, int basis, const u256* scalars_dev, size_t
   const size_t range_cap_col = (ent_cap + lcap - 1) / lcap;  // worst case: every digit non-zero
   const size_t seg_cap_col = B + range_cap_col;
   // large batches keep thousands of independent column reductions in flight
-  size_t per_col = ent_cap * 4 + range_cap_col * sizeof(MsmRange) + seg_cap_col * (sizeof(MsmSegInfo) + sizeof(XYZZ) + MSM_RAW_WORDS * 4) + 2 * (B + 1) * 4 +
+  size_t per_col = ent_cap * 4 + range_cap_col * sizeof(MsmRange) + seg_cap_col * (sizeof(MsmSegInfo) + MSM_RAW_WORDS * 4) + MSM_RAW_WORDS * 4 + 2 * (B + 1) * 4 +
                    n * 12;
   // two-phase scatter of the sort: bins of 2^fine_bits buckets; the table index and the fine bucket number share an entry's 31 bits
   static const bool two_phase_on = !(getenv("VDB_MSM_TWO_PHASE") && getenv("VDB_MSM_TWO_PHASE")[0] == '0');
@@ -765,9 +801,9 @@ int msm_batch_dev(const vdb_srs* srs, int basis, const u256* scalars_dev, size_t
   uint8_t* buf = (uint8_t*)scratch_get(2, nb * per_col + 512);
   if (!buf) return VDB_ERR_OOM;
   uint32_t* entries = (uint32_t*)buf;
-  XYZZ* partials = (XYZZ*)(buf + nb * ent_cap * 4);
-  uint4* raw = (uint4*)((uint8_t*)partials + nb * seg_cap_col * sizeof(XYZZ));
-  MsmRange* ranges = (MsmRange*)((uint8_t*)raw + nb * seg_cap_col * MSM_RAW_WORDS * 4);
+  uint4* raw = (uint4*)(buf + nb * ent_cap * 4);                                 // one record per segment, folded in place
+  uint4* sums = (uint4*)((uint8_t*)raw + nb * seg_cap_col * MSM_RAW_WORDS * 4);  // one record per column: what k_msm_reduce leaves
+  MsmRange* ranges = (MsmRange*)((uint8_t*)sums + nb * MSM_RAW_WORDS * 4);
   MsmSegInfo* seginfo = (MsmSegInfo*)((uint8_t*)ranges + nb * range_cap_col * sizeof(MsmRange));
   uint32_t* seg_off = (uint32_t*)((uint8_t*)seginfo + nb * seg_cap_col * sizeof(MsmSegInfo));
   uint32_t* bucket_off = seg_off + nb * (B + 1);
@@ -813,11 +849,6 @@ int msm_batch_dev(const vdb_srs* srs, int basis, const u256* scalars_dev, size_t
                        seg_off, counters, raw, seginfo, range_cap, l9k);
     }
     VDB_LAUNCH_CHECK();
-    {
-      VDB_PROF("k_msm_partials");
-      hipLaunchKernelGGL(k_msm_partials, dim3((unsigned)(cx.cu_count * 8)), dim3(256), 0, cx.stream, raw, partials, counters, seg_cap, l9k.to_std);
-    }
-    VDB_LAUNCH_CHECK();
     hipStream_t ts = cx.stream;
     if (defer_tail && c0 + nc == n_cols) {
       VDB_HIP(hipEventRecord(cx.ev_tail, cx.stream));
@@ -830,13 +861,18 @@ int msm_batch_dev(const vdb_srs* srs, int basis, const u256* scalars_dev, size_t
       while ((1u << passes) < max_nt) passes++;
       for (uint32_t ps = 0; ps < passes; ps++) {
         VDB_PROF_ON("k_msm_combine", ts);
-        hipLaunchKernelGGL(k_msm_combine, dim3((unsigned)(cx.cu_count * 8)), dim3(256), 0, ts, partials, seginfo, counters, ps, seg_cap);
+        hipLaunchKernelGGL(k_msm_combine, dim3((unsigned)(cx.cu_count * 8)), dim3(256), 0, ts, raw, seginfo, counters, ps, seg_cap, l9k);
       }
       VDB_LAUNCH_CHECK();
     }
     {
       VDB_PROF_ON("k_msm_reduce", ts);
-      hipLaunchKernelGGL(k_msm_reduce, dim3((unsigned)nc), dim3(64), 0, ts, partials, seg_off, c, counters, add_points ? add_points + c0 : nullptr, out_dev + c0);
+      hipLaunchKernelGGL(k_msm_reduce, dim3((unsigned)nc), dim3(64), 0, ts, raw, seg_off, c, counters, add_points ? add_points + c0 : nullptr, sums, l9k);
+    }
+    VDB_LAUNCH_CHECK();
+    {
+      VDB_PROF_ON("k_msm_normalise", ts);
+      hipLaunchKernelGGL(k_msm_normalise, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, ts, sums, (uint32_t)nc, counters, l9k.to_std, out_dev + c0);
     }
     VDB_LAUNCH_CHECK();
   }
