@@ -543,6 +543,27 @@ def wit_ann_query(metric, query, centroids, members, cluster_roots, P=48, L=13, 
                 index_root=pub[dim], public=pub)
 
 
+def wit_ann_audit(metric, centroids, members, roots, cluster, P=48, L=13, selectors=False):
+    """the audit of one cluster's routing (vdb_wit_ann_audit) on centroids (K, dim, 4), the members of cluster `cluster` (n_c, dim, 4) and
+    roots (K + 1, 4): [centroids' root | cluster roots]: dict(stream, lookup, selectors, flags, n_in, routed (n_c,) uint8: member i's own
+    centroid attains the minimum, public (2, 4): [index_root | c])"""
+    lib = _lib.init()
+    centroids, members, roots = _fr(centroids), _fr(members), _fr(roots)
+    K, dim, n_c = centroids.shape[0], centroids.shape[1], members.shape[0]
+    assert members.shape[1] == dim and roots.shape == (K + 1, 4)
+    cells, lk, n_in = _u64(), _u64(), _u64()
+    m = METRICS[metric]
+    check(lib.vdb_wit_ann_audit_size(m, ctypes.c_uint32(P), ctypes.c_uint32(L), _sz(K), _sz(n_c), _sz(dim), ctypes.byref(cells), ctypes.byref(lk),
+                                     ctypes.byref(n_in)))
+    stream = np.zeros((cells.value, 4), dtype=np.uint64)
+    lookup = np.zeros((lk.value, 4), dtype=np.uint64)
+    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
+    routed, pub = np.zeros(n_c, dtype=np.uint8), np.zeros((2, 4), dtype=np.uint64)
+    check(lib.vdb_wit_ann_audit(m, ctypes.c_uint32(P), ctypes.c_uint32(L), _p(centroids), _p(members), _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(dim),
+                                _p(stream), _p(lookup), _p(sel) if selectors else None, _p(routed), _p(pub)))
+    return dict(stream=stream, lookup=lookup, **_split_flags(sel), n_in=n_in.value, routed=routed, public=pub)
+
+
 def _wit_ann_batch(levels, cells, n_pub, selectors, call, **sizes):
     """the buffers of a host-array call against the index root and its dict: call(levels, stream, selectors or None, public) -> its code"""
     levels = np.array(levels, dtype=np.uint64, copy=True)

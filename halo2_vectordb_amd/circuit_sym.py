@@ -1452,7 +1452,7 @@ def _build_ann_head(lay, fetch_flags, fetch_values, builder):
     constant j set per instance), select_by_indicator over K cells, the sponge (place_sponge).  -> (B, inds, picked, root_old)"""
     if np.asarray(fetch_flags(0, lay["n_in"])).any():
         raise ValueError("the assigned header carries no gate or constant flag")
-    B = (builder or _Builder)(lay["total"], 0)
+    B = (builder or _Builder)(lay["total"], lay.get("total_l", 0))
     K = lay["n_in"] - 2
     c, roots = lay["c"], lay["roots"] + np.arange(K, dtype=np.int64)
     s = Sym(0, 0)
@@ -1608,6 +1608,95 @@ def build_ann_delete(K, m, dim, depth, fetch_flags, fetch_values, builder=None, 
     info = dict(_delete_info(lay, m, upub, s0, top), indicators=[int(i) for i in inds], picked=picked, outs=outs, index_root_old=root_old,
                 index_root_new=root_new, layout=lay)
     return B.finish(), ann_delete_instances(root_old, lay["c"], upub, root_new), info
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The audit of one cluster's routing (include/vdb.h vdb_wit_ann_audit; pipeline.AnnAuditHotPath)
+def ann_audit_layout(metric, K, n_c, dim, P, L):
+    """where the blocks of the audit circuit start: the head's keys of _ann_frame_layout (c, centroids_root, roots, n_in, indicator, select,
+    sponge_old, sponge) and centroids, members: the assigned block I (`update`: its first cell, where the head ends); routed: block R,
+    per_member / per_member_l: cells and lookup cells of one member's sub-block, chain_off, pick_off: where its qmin chain and its
+    select_by_indicator start; merkle_c, merkle_m; total, total_l; units: nearest_units over the K centroids; zero_c: the centroids'
+    padding loads the zero cell"""
+    if n_c < 1 or dim < 1:
+        raise ValueError("at least one member and one word")
+    head = _ann_frame_layout(K, merkle_leaf_layout(K + 1), 0)
+    lay = {k: head[k] for k in ("c", "centroids_root", "roots", "n_in", "indicator", "sponge", "select", "sponge_old", "update")}
+    u = nearest_units(metric, K, dim, 1, P, L)
+    zero_c = (1 << (K - 1).bit_length()) > K
+    lay.update(units=u, zero_c=zero_c, centroids=lay["update"], members=lay["update"] + K * dim)
+    lay["routed"] = lay["members"] + n_c * dim
+    lay["chain_off"] = K * u["db"].n
+    lay["pick_off"] = lay["chain_off"] + (K - 1) * u["qm"].n
+    lay["per_member"] = lay["pick_off"] + u["sb"].n
+    lay["per_member_l"] = K * u["db"].n_lk + (K - 1) * u["qm"].n_lk
+    lay["merkle_c"] = lay["routed"] + n_c * lay["per_member"]
+    lay["merkle_m"] = lay["merkle_c"] + merkle_cells(K, dim)
+    lay["total"] = lay["merkle_m"] + merkle_cells(n_c, dim, zero_c)
+    lay["total_l"] = n_c * lay["per_member_l"]
+    return lay
+
+
+def place_routed(B, u, members, centroids, ind, base, lbase):
+    """The routed block placed into builder `B` from the unit blocks of `u` = nearest_units over the K centroids: per member i, at
+    base + i per_member, the K distance(centroid_j, member_i) (the centroid in the vector role, as nearest_vector has it), the K - 1 qmin
+    of the chain and select_by_indicator(d_i0 .., `ind`); member i's lookup cells from lbase + i per_member_l on.  `members` (n_c, dim) /
+    `centroids` (K, dim) / `ind` (K,): stream cells.  -> (own (n_c,), m (n_c,)): the selection's outputs and the chains' minima (d_i0 at
+    K = 1); the caller ties them."""
+    K, dim = u["n"], u["dim"]
+    db, qm, sb = u["db"], u["qm"], u["sb"]
+    members, centroids = np.asarray(members, dtype=np.int64).reshape(-1, dim), np.asarray(centroids, dtype=np.int64).reshape(K, dim)
+    ind = np.asarray(ind, dtype=np.int64).reshape(K)
+    n_c = members.shape[0]
+    chain_off, chain_loff = K * db.n, K * db.n_lk
+    pick_off = chain_off + (K - 1) * qm.n
+    per, per_l = pick_off + sb.n, chain_loff + (K - 1) * qm.n_lk
+    ii, jj = np.repeat(np.arange(n_c, dtype=np.int64), K), np.tile(np.arange(K, dtype=np.int64), n_c)
+    d = B.place(db, base + ii * per + jj * db.n, lbase + ii * per_l + jj * db.n_lk, np.concatenate([centroids[jj], members[ii]], axis=1))[:, 0].reshape(n_c, K)
+    acc = np.empty((n_c, K), dtype=np.int64)
+    acc[:, 0] = d[:, 0]
+    if K > 1:
+        il, l = np.repeat(np.arange(n_c, dtype=np.int64), K - 1), np.tile(np.arange(K - 1, dtype=np.int64), n_c)
+        bases = base + il * per + chain_off + l * qm.n
+        acc[:, 1:] = (bases + qm.outs[0]).reshape(n_c, K - 1)
+        B.place(qm, bases, lbase + il * per_l + chain_loff + l * qm.n_lk, np.stack([acc[:, :-1].reshape(-1), d[:, 1:].reshape(-1)], axis=1))
+    own = B.place(sb, base + np.arange(n_c, dtype=np.int64) * per + pick_off, np.zeros(n_c, dtype=np.int64),
+                  np.concatenate([d, np.broadcast_to(ind[None, :], (n_c, K))], axis=1))[:, 0]
+    return own, acc[:, K - 1].copy()
+
+
+def ann_audit_instances(index_root, c):
+    """the public cells in make_public order: [index_root | c]"""
+    return [int(index_root), int(c)]
+
+
+def build_ann_audit(metric, K, n_c, dim, P, L, fetch_flags, fetch_values, builder=None):
+    """The audit of one cluster's routing in one circuit (pipeline.AnnAuditHotPath): the frame's head (_build_ann_head: the header
+    [c | centroids_root | cluster roots], idx_to_indicator(c, K), select_by_indicator(cluster roots, ind) -> picked, the sponge ->
+    index_root), [centroids | members] assigned, the routed block (place_routed) with every own_i TIED to m_i — centroid c attains the
+    minimum of member i's K distances — then merkle_commitment(centroids), tied to the header's centroids_root, and
+    merkle_commitment(members), tied to picked.  fetch_flags / fetch_values: as place_merkle; `builder`: as build_kmeans.
+    -> (CopyMap, public cells [index_root, c], dict(indicators, picked, own, m, centroids_root, members_root, index_root, layout))"""
+    lay = ann_audit_layout(metric, K, n_c, dim, P, L)
+    B, inds, picked, index_root = _build_ann_head(lay, fetch_flags, fetch_values, builder)
+    if np.asarray(fetch_flags(lay["centroids"], lay["routed"])).any():
+        raise ValueError("the assigned centroids and members carry no gate or constant flag")
+    cent = lay["centroids"] + np.arange(K * dim, dtype=np.int64).reshape(K, dim)
+    mem = lay["members"] + np.arange(n_c * dim, dtype=np.int64).reshape(n_c, dim)
+    own, m = place_routed(B, lay["units"], mem, cent, inds, lay["routed"], 0)
+    for o, x in zip(own.tolist(), m.tolist()):
+        B.tie(o, x)                                          # ctx.constrain_equal(m_i, own_i)
+    croot, end = place_merkle(B, K, dim, lay["merkle_c"], lay["centroids"], fetch_flags, fetch_values)
+    assert end == lay["merkle_m"]
+    B.tie(croot, lay["centroids_root"])                      # ctx.constrain_equal(centroids_root, croot)
+    zero = lay["merkle_c"] + K * merkle_leaf_layout(dim)["leaf_cells"] if lay["zero_c"] else None
+    mroot, end = place_merkle(B, n_c, dim, lay["merkle_m"], lay["members"], fetch_flags, fetch_values, zero_cell=zero)
+    if end != lay["total"]:
+        raise ValueError("the trace does not end where the circuit does")
+    B.tie(mroot, picked)                                     # ctx.constrain_equal(picked, mroot)
+    info = dict(indicators=[int(i) for i in inds], picked=picked, own=[int(o) for o in own], m=[int(x) for x in m], centroids_root=croot,
+                members_root=mroot, index_root=index_root, layout=lay)
+    return B.finish(), ann_audit_instances(index_root, lay["c"]), info
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -41,6 +41,36 @@ static inline AnnuBlocks annu_blocks(uint64_t K, uint64_t sponge_cells, uint64_t
 // where lane j's indicator starts inside block B: is_zero (8 cells) for j = 0, then is_equal (12 cells) each
 ANNU_HD static inline uint64_t annu_indicator_off(uint64_t j) { return j ? 8 + 12 * (j - 1) : 0; }
 
+// ------------------------------------------------------------------ the audit of one cluster's routing (include/vdb.h vdb_wit_ann_audit)
+// first stream cell of every block: A - D the frame's head as above (b_ind, b_sel, b_old), I the assigned [centroids K x dim | members
+// n_c x dim], R the routed block, one sub-block of per_member cells per member: K distances, the K - 1 qmin of the chain, then
+// select_by_indicator over the K distances (1 + 3 K cells, at pick_off inside the sub-block); MC and MM the two merkle_commitments.
+// Lookup cells are R's alone, per_member_l per member: the distance runs, then the qmin runs.
+struct AnnaBlocks {
+  uint64_t n_in, b_ind, b_sel, b_old, b_in, b_r, b_mc, b_mm, total;
+  uint64_t per_member, per_member_l, chain_off, chain_loff, pick_off, total_l;
+};
+static inline AnnaBlocks anna_blocks(uint64_t K, uint64_t n_c, uint64_t dim, uint64_t sponge_cells, uint64_t dist_cells, uint64_t dist_lk,
+                                     uint64_t qmin_cells, uint64_t qmin_lk, uint64_t mc_cells, uint64_t mm_cells) {
+  AnnaBlocks o;
+  o.n_in = K + 2;
+  o.b_ind = o.n_in;
+  o.b_sel = o.b_ind + 8 + 12 * (K - 1);
+  o.b_old = o.b_sel + 1 + 3 * K;
+  o.b_in = o.b_old + sponge_cells;
+  o.b_r = o.b_in + (K + n_c) * dim;
+  o.chain_off = K * dist_cells;
+  o.chain_loff = K * dist_lk;
+  o.pick_off = o.chain_off + (K - 1) * qmin_cells;
+  o.per_member = o.pick_off + 1 + 3 * K;
+  o.per_member_l = o.chain_loff + (K - 1) * qmin_lk;
+  o.b_mc = o.b_r + n_c * o.per_member;
+  o.b_mm = o.b_mc + mc_cells;
+  o.total = o.b_mm + mm_cells;
+  o.total_l = n_c * o.per_member_l;
+  return o;
+}
+
 // The members of a cluster stay dense: write j goes to a slot below the fill at its turn (a replacement) or exactly at it (an append,
 // which raises the fill by one).  n_c: the fill before the batch, glp: the padded leaf count of the grown tree.
 // -> 0 and *appends; 1: indices[*bad] lies above the fill at its turn; 2: it lies outside the grown tree

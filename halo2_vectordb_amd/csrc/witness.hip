@@ -2151,6 +2151,89 @@ int wit_ann_delete_dev(u256* levels, const u256* roots, size_t K, size_t cluster
   return inv_list_fixup(f.st);
 }
 
+// ------------------------------------------------------------------ the audit of one cluster's routing (include/vdb.h vdb_wit_ann_audit):
+// every member committed under cluster_root_c is at least as close to centroid c as to any other committed centroid.  Blocks A - D are
+// the frame's head; I [centroids | members] assigned; R per member i the K distance(centroid_j, member_i), the qmin chain -> m_i and
+// select_by_indicator(d_i0 .., ind) -> own_i, which the map ties to m_i; MC, MM the two merkle_commitments, whose roots the map ties to
+// the header's centroids_root and to picked.  Nothing after the head is the frame's: close() is not called.
+struct AnnaLayout {
+  AnnuLayout fr;     // what AnnFrame::open reads: b_ind, b_sel, b_old, total, mw
+  DistLayout dl;
+  MkLayout mc, mm;
+  AnnaBlocks b;
+};
+// select_by_indicator([d_i0 .. d_i,K-1], ind) per member, lanes = (member i, j), j fastest.  ind is one-hot at c, so the running value
+// is known without a walk: s_j = j >= c ? d_ic : 0, and lane (i, j) pushes [d_ij, ind_j, s_j] at 1 + 3 j of member i's block, lane
+// (i, 0) the leading 0 as well (k_nv_select's cells and flags for the same gadget).  Lane (i, 0) also states whether member i is routed:
+// d_ic is the chain's minimum.
+__global__ __launch_bounds__(64) void k_anna_pick(Streams st, const FpTables* __restrict__ T, uint64_t base, uint64_t per_member, uint32_t c, uint32_t K,
+                                                  uint32_t n_c, const u256* __restrict__ dist, const u256* __restrict__ pm,
+                                                  uint8_t* __restrict__ routed) {
+  const uint64_t th = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+  if (th >= (uint64_t)n_c * K) return;
+  const uint32_t j = (uint32_t)(th % K), i = (uint32_t)(th / K);
+  const u256* di = dist + (size_t)i * K;
+  const u256 own = di[c];
+  if (j == 0) routed[i] = u256_eq(own, pm[(size_t)i * K + K - 1]) ? 1 : 0;
+  WCtx cx = make_ctx(st, T, base + (uint64_t)i * per_member + (j ? 1 + 3ull * j : 0), 0);
+  if (j == 0) cx.push(u256_zero(), true);
+  cx.push(di[j], false);
+  cx.push(j == c ? mont_one<Fr>() : u256_zero(), false);
+  cx.push(j >= c ? own : u256_zero(), j + 1 < K);
+}
+// the refusals, in the frame's order, and where the blocks start
+static int anna_layout(FpEntry* fp, int metric, size_t K, size_t cluster, size_t n_c, size_t dim, AnnaLayout* o) {
+  MkuLayout none{};
+  TRY(ann_frame_layout(K, cluster, n_c, &o->fr, &none, [&](uint64_t*) -> int {
+    VDB_ARG(n_c > 0 && dim > 0 && dim <= ((size_t)1 << 20), "empty cluster, dim = 0 or dim above 2^20");
+    const size_t cap = VDB_NEAREST_TOPK_MAX_INSTANCES;
+    VDB_ARG(K <= cap / n_c && dim <= cap / n_c, "audit too large: n_c * K and n_c * dim at most VDB_NEAREST_TOPK_MAX_INSTANCES");
+    return dist_layout(fp->host, metric, dim, &o->dl);
+  }));
+  mk_layout(K, dim, 0, &o->mc);
+  mk_layout(n_c, dim, (int)o->mc.zero_cell, &o->mm);   // Context::load_zero caches its cell: the centroids' padding has loaded it
+  o->b = anna_blocks(K, n_c, dim, o->fr.mw.total, o->dl.total_cells, o->dl.total_lk, fp->host.sz.qmin[0], fp->host.sz.qmin[1], o->mc.total, o->mm.total);
+  VDB_ARG(o->b.total <= VDB_NEAREST_TOPK_MAX_CELLS, "audit circuit above 2^34 cells");
+  o->fr.b.n_in = o->b.n_in;
+  o->fr.b.b_ind = o->b.b_ind;
+  o->fr.b.b_sel = o->b.b_sel;
+  o->fr.b.b_old = o->b.b_old;
+  o->fr.b.total = o->b.total;
+  return VDB_OK;
+}
+// roots: [centroids_root | the K cluster roots]; levels_c / levels_m: the two trees where they are resident (forest segments K and c),
+// or both null; routed: n_c bytes; pub: [index_root | c].  Scratch slot 0 holds the distances and the prefix minima until k_anna_pick
+// has read them, and mk_emit asks for the slot again: every launch of R is enqueued before the first mk_emit (the stream orders them).
+int wit_ann_audit_dev(FpEntry* fp, int metric, const u256* centroids, const u256* members, const u256* roots, const u256* levels_c, const u256* levels_m,
+                      size_t K, size_t cluster, size_t n_c, size_t dim, Streams st, uint8_t* routed, u256* pub) {
+  AnnaLayout a;
+  TRY(anna_layout(fp, metric, K, cluster, n_c, dim, &a));
+  const AnnaBlocks& b = a.b;
+  const size_t inst = n_c * K;
+  u256* mid = (u256*)scratch_get(0, (inst * 5 + 8) * sizeof(u256) + inst * sizeof(uint32_t));
+  if (!mid) return VDB_ERR_OOM;
+  u256 *dist = mid + 3 * inst, *pm = dist + inst;
+  uint32_t* rnd = (uint32_t*)(pm + inst + 8);
+  AnnFrame f;
+  TRY(f.open(st, roots, K, cluster, a.fr, 0, 0));
+  TRY(set_winv(f.st, fp->dev));   // the head's gadgets are GateChip's alone; R's read the tables of (P, L)
+  const bool resident = levels_c && levels_m;
+  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)(((K + n_c) * dim + 255) / 256)), dim3(256), f.st, b.b_in, centroids, members, (uint64_t)(K * dim),
+             (uint64_t)((K + n_c) * dim));
+  const InstMap im{b.b_r, 0, (uint32_t)K, b.per_member, b.per_member_l, (uint32_t)K, (uint32_t)K};   // t = i K + j: (centroid_j, member_i)
+  TRY(run_distances(f.st, fp, a.dl, im, (uint32_t)inst, centroids, members, mid, dist));
+  VDB_LAUNCH(k_nv_rounds, dim3((unsigned)n_c), dim3(64), fp->dev, dist, (uint32_t)K, 1u, pm, rnd);
+  const NvMap nm{b.b_r, 0, b.per_member, b.per_member_l, b.chain_off, b.chain_loff, 0, 0, 0, 0, 0, (uint32_t)n_c, (uint32_t)K, (uint32_t)dim, 1u};
+  VDB_LAUNCH(k_nv_qmin, dim3((unsigned)((n_c * (K - 1) + 63) / 64 + (K == 1))), dim3(64), f.st, fp->dev, nm, dist, pm, rnd);
+  VDB_LAUNCH(k_anna_pick, dim3((unsigned)((inst + 63) / 64)), dim3(64), f.st, fp->dev, b.b_r + b.pick_off, b.per_member, (uint32_t)cluster, (uint32_t)K,
+             (uint32_t)n_c, dist, pm, routed);
+  TRY(mk_emit(fp, f.sp, centroids, K, dim, a.mc, f.st, b.b_mc, resident ? levels_c : nullptr, nullptr));
+  TRY(mk_emit(fp, f.sp, members, n_c, dim, a.mm, f.st, b.b_mm, resident ? levels_m : nullptr, nullptr));
+  VDB_HIP(hipMemcpyAsync(pub, f.iroot, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
+  VDB_HIP(hipMemcpyAsync(pub + 1, f.hdr, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
+  return inv_list_fixup(f.st);
+}
+
 }  // namespace vdb
 
 using namespace vdb;
@@ -2751,6 +2834,56 @@ int vdb_wit_ann_delete(vdb_fr* levels, const vdb_fr* roots, size_t K, size_t clu
   return ann_batch_host(levels, dp.lp, roots, K, a.b.total, 4 * m + 3, stream_out, selector_out, public_out, [&](u256* dl, const u256* dr, Streams st, u256* dpub) {
     return wit_ann_delete_dev(dl, dr, K, cluster, n_c, dim, slots, m, st, dpub);
   });
+}
+
+// the audit of one cluster's routing (include/vdb.h)
+int vdb_wit_ann_audit_size(int metric, uint32_t P, uint32_t L, size_t K, size_t n_c, size_t dim, uint64_t* cells, uint64_t* lookups, uint64_t* input_cells) {
+  VDB_REQUIRE_INIT();
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  AnnaLayout a;
+  TRY(anna_layout(fp, metric, K, 0, n_c, dim, &a));
+  if (cells) *cells = a.b.total;
+  if (lookups) *lookups = a.b.total_l;
+  if (input_cells) *input_cells = a.b.n_in;
+  return VDB_OK;
+}
+int vdb_wit_ann_audit_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* centroids_dev, const vdb_fr* members_dev, const vdb_fr* roots_dev,
+                          const vdb_fr* centroid_levels_dev, const vdb_fr* member_levels_dev, size_t K, size_t cluster, size_t n_c, size_t dim,
+                          vdb_fr* stream_dev, vdb_fr* lookup_dev, uint8_t* selector_dev, uint8_t* routed_dev, vdb_fr* public_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(centroids_dev && members_dev && roots_dev && stream_dev && lookup_dev && routed_dev && public_dev, "null pointer");
+  VDB_ARG(!centroid_levels_dev == !member_levels_dev, "the two resident trees are given together or not at all");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  DevStreams ds;
+  TRY(ds.init(stream_dev, selector_dev, lookup_dev));
+  TRY(wit_ann_audit_dev(fp, metric, as_u256(centroids_dev), as_u256(members_dev), as_u256(roots_dev),
+                        centroid_levels_dev ? as_u256(centroid_levels_dev) : nullptr, member_levels_dev ? as_u256(member_levels_dev) : nullptr, K, cluster,
+                        n_c, dim, ds.st, routed_dev, as_u256(public_dev)));
+  return ds.finish();
+}
+int vdb_wit_ann_audit(int metric, uint32_t P, uint32_t L, const vdb_fr* centroids, const vdb_fr* members, const vdb_fr* roots, size_t K, size_t cluster,
+                      size_t n_c, size_t dim, vdb_fr* stream_out, vdb_fr* lookup_out, uint8_t* selector_out, uint8_t* routed_out, vdb_fr* public_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(centroids && members && roots && routed_out && public_out, "null pointer");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  AnnaLayout a;
+  TRY(anna_layout(fp, metric, K, cluster, n_c, dim, &a));
+  DevBuf dc, dm, dr, drt, dpub;
+  HostStreams hs;
+  TRY(upload(dc, centroids, K * dim * sizeof(u256)));
+  TRY(upload(dm, members, n_c * dim * sizeof(u256)));
+  TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
+  TRY(drt.alloc(n_c));
+  TRY(dpub.alloc(2 * sizeof(u256)));
+  TRY(hs.init(a.b.total, a.b.total_l, selector_out != nullptr));
+  TRY(wit_ann_audit_dev(fp, metric, dc.as<u256>(), dm.as<u256>(), dr.as<u256>(), nullptr, nullptr, K, cluster, n_c, dim, hs.st, drt.as<uint8_t>(),
+                        dpub.as<u256>()));
+  TRY(download(routed_out, drt.p, n_c));
+  TRY(download(public_out, dpub.p, 2 * sizeof(u256)));
+  return hs.finish(stream_out, lookup_out, selector_out, a.b.total, a.b.total_l);
 }
 
 }  // extern "C"

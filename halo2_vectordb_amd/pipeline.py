@@ -1588,3 +1588,75 @@ class AnnDeleteHotPath(_AnnBatchHotPath):
 
     def _builder(self, CS):
         return CS.build_ann_delete, dict(shrink=self.shrink)
+
+
+class AnnAuditHotPath(HotPath):
+    """The routing of ONE cluster c of a committed AnnIndex proved in one proof (include/vdb.h vdb_wit_ann_audit): every member committed
+    under cluster_root_c is at least as close to centroid c as to any other committed centroid, in the circuit's fixed-point distance.
+    Assigned: the header [c | centroids' root | cluster roots]; then idx_to_indicator(c, K), select_by_indicator(cluster roots, indicators)
+    -> picked, the sponge over the roots (index_root), [centroids | members] assigned, per member its K distances, their qmin chain and
+    select_by_indicator(distances, indicators) tied to the chain's minimum, merkle_commitment(centroids) tied to the header's centroids'
+    root and merkle_commitment(members) tied to picked.  Public: [index_root | c].  It covers the build's cluster ids and the writes after
+    them: audit cluster c of index.updated(hp) after a batch into c; K proofs cover an index.  Not proved: that centroids are means, that
+    the database is complete.  A member equidistant from two centroids is accepted under either.  The shape depends on (K, n_c, dim,
+    metric): one proving key per cluster size.  A misrouted member still gives a witness; results()[2] flags it and its copy fails in
+    the Mock report.  `centroids` / `members`: quantized overrides of what the index holds (tests of the binding); with them the two
+    trees are hashed by the call instead of read from the forest."""
+
+    def __init__(self, index, cluster, k=13, P=48, L=12, metric="euclidean", tau=None, col_shard=(0, 1), blind_seed=None, params=None, centroids=None,
+                 members=None):
+        self.index, self.K, self.cluster = index, index.K, int(cluster)
+        if not 0 <= self.cluster < self.K:
+            raise ValueError("cluster outside the index")
+        super().__init__(int(index.sizes[self.cluster]), index.dim, k, P, L, seed=None, tau=tau, col_shard=col_shard, vectors=np.zeros((0, index.dim)),
+                         blind_seed=blind_seed, params=params)
+        self.metric, self.metric_name = api.METRICS[metric], metric
+        self.given_cent, self.given_members = centroids, members
+
+    def n_input_rows(self):
+        return 0
+
+    def _load_inputs(self):
+        super()._load_inputs()
+        ix, self.resident = self.index, self.given_cent is None and self.given_members is None
+        self.p_cent, self.p_members = ix.d_cent.ptr, ix.members_ptr(self.cluster)
+        for given, shape, name in ((self.given_cent, (self.K, self.dim, 4), "p_cent"), (self.given_members, (self.n, self.dim, 4), "p_members")):
+            if given is not None:
+                a = np.ascontiguousarray(given, dtype=np.uint64)
+                assert a.shape == shape
+                d = self._output(a.nbytes)
+                d.upload(a)
+                setattr(self, name, d.ptr)
+
+    def _circuit_size(self):
+        cells, lk, n_in = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(self.lib.vdb_wit_ann_audit_size(self.metric, self.P, self.L, self.K, self.n, self.dim, ctypes.byref(cells), ctypes.byref(lk), ctypes.byref(n_in)))
+        return n_in.value, cells.value - n_in.value, lk.value
+
+    def _alloc_outputs(self):
+        self.d_routed, self.d_pub = self._output(max(self.n, 32)), self._output(2 * B)
+
+    def _witness(self, sel=None):
+        # the call writes the assigned header, centroids and members too
+        ix = self.index
+        with self._window(sel, 0):
+            check(self.lib.vdb_wit_ann_audit_dev(self.metric, self.P, self.L, self.p_cent, self.p_members, ix.d_roots.ptr,
+                                                 ix.levels_ptr(self.K) if self.resident else None, ix.levels_ptr(self.cluster) if self.resident else None,
+                                                 self.K, self.cluster, self.n, self.dim, self.d_stream.ptr, self.d_lookup.ptr, self._sel_at(sel, 0),
+                                                 self.d_routed.ptr, self.d_pub.ptr))
+
+    def public_values_dev(self):
+        return self.d_pub.ptr, 2
+
+    def results(self):
+        """(index_root (4,), c (4,), routed (n_c,) uint8: member i's own centroid attains the minimum of its K distances)"""
+        pub = self.d_pub.download((2, 4))
+        return pub[0], pub[1], self.d_routed.download((self.n,), dtype=np.uint8)
+
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        cm, public, _ = CS.build_ann_audit(self.metric_name, self.K, self.n, self.dim, self.P, self.L, functools.partial(self._fetch_flags, d_flags),
+                                           self._fetch, builder=DeviceBuilder if on_device else None)
+        assert cm.n_cells == self.n_cells
+        return cm, public, None

@@ -489,6 +489,48 @@ int vdb_ann_index_remove_dev(const vdb_fr *grouped_dev, const vdb_fr *forest_dev
                              const uint64_t *slots /* host */, size_t m, vdb_fr *grouped_out_dev, uint32_t *slots_out_dev,
                              uint64_t *offsets_out_dev, vdb_fr *forest_out_dev, vdb_fr *roots_out_dev);
 
+/* The audit of one cluster's routing: in the index with root index_root, every member committed under cluster_root_c is at least as
+ * close to centroid c as to any other committed centroid, in the circuit's fixed-point distance for `metric`.  It covers the build's
+ * cluster ids and the writes after them alike (audit cluster c of the index a batch into c leaves); K such proofs cover an index.  It
+ * does not prove that centroids are means or that the database is complete.  The reference has no such gadget; the cells are those of
+ * the closure a user of its chips writes.  Stream, from cell 0:
+ *   A - D  exactly those of vdb_wit_ann_update: the header [c | centroids_root | cluster roots] (K + 2 cells: input_cells),
+ *          ind = idx_to_indicator(c, K), picked = select_by_indicator(cluster roots, ind), index_root = the sponge over the roots
+ *   I      [centroids K x dim | members n_c x dim] assigned
+ *   R      per member i, at R + i * per_member: d_ij = distance(centroid_j, member_i), j = 0 .. K - 1 (the centroid in the vector role,
+ *          the member in the query role: nearest_vector's argument order, so the values are vdb_nearest_values' bit for bit); the
+ *          K - 1 qmin of the chain -> m_i; own_i = gate.select_by_indicator([d_i0 .. d_i,K-1], ind)      (1 + 3 K cells)
+ *   MC     croot = merkle_commitment(centroids)
+ *   MM     mroot = merkle_commitment(members), its padding copying MC's zero cell where MC's padding has loaded one
+ * Copies (no cell): R's distance operands copy I and its ind cells B's outputs; own_i is tied to m_i (to d_i0 at K == 1, where there
+ * is no chain); croot is tied to the header's centroids_root and mroot to picked.  Lookup cells are R's alone, member i's from
+ * i * per_member_l on: the distance runs, then the qmin runs.  public, 2 values: [index_root | c].
+ * Ties: the statement is "centroid c attains the minimum", not nearest_vector's indicator is_equal(min, d_j), whose select_by_indicator
+ * is only satisfiable when it is one-hot: a member equidistant from two centroids is accepted under either, so an honest index with a
+ * tie stays provable.  Without ties this is vdb_nearest_values' rule (the last index at the minimum).
+ * A misrouted member still gives a stream: the call succeeds, routed[i] = 0 for that member (1 for every member whose own centroid
+ * attains the minimum) and only its own_i = m_i copy fails at Mock or verify time.  The shape depends on (K, n_c, dim, metric): one
+ * proving key per cluster size; c is a witness.
+ * roots: the K + 1 digests [centroids_root | cluster roots].  centroid_levels_dev / member_levels_dev: the two trees where they are
+ * resident (forest segments K and c), only read — then the launch count depends on neither K nor n_c; both NULL: the digests are
+ * computed by the call, a launch per level; one alone: VDB_ERR_ARG.  The caller answers for the trees being those of the rows given,
+ * as in vdb_wit_ann_query.  Launches: the head's four emitters and its sponge, one assignment kernel, the distance generators over
+ * n_c * K instances, one kernel for the prefix minima, one for the qmin chains (launched at K == 1 too, where it has no lane), one for the
+ * picks, the two trees' traces and the inverse fix-up: 20 with resident trees under Euclidean, whatever K, c and n_c.  A member EQUAL to
+ * a centroid has distance 0, where the reference's qsqrt(0) violates its own asserted constants (Euclidean): such a stream fails Mock.
+ * The _dev form honours vdb_wit_set_window.  VDB_ERR_ARG before anything is launched: K == 0,
+ * K > VDB_ANN_MAX_CLUSTERS, cluster >= K, n_c > VDB_ANN_MAX_VECTORS, n_c == 0, dim == 0, dim > 2^20, n_c * K or n_c * dim above
+ * VDB_NEAREST_TOPK_MAX_INSTANCES, more than 2^34 cells.  _size takes no cluster; each of its outputs may be NULL. */
+int vdb_wit_ann_audit_size(int metric, uint32_t precision_bits, uint32_t lookup_bits, size_t K, size_t n_c, size_t dim, uint64_t *cells,
+                           uint64_t *lookups, uint64_t *input_cells);
+int vdb_wit_ann_audit(int metric, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *centroids, const vdb_fr *members,
+                      const vdb_fr *roots, size_t K, size_t cluster, size_t n_c, size_t dim, vdb_fr *stream_out, vdb_fr *lookup_out,
+                      uint8_t *selector_out, uint8_t *routed_out, vdb_fr *public_out);
+int vdb_wit_ann_audit_dev(int metric, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *centroids_dev, const vdb_fr *members_dev,
+                          const vdb_fr *roots_dev, const vdb_fr *centroid_levels_dev, const vdb_fr *member_levels_dev, size_t K, size_t cluster,
+                          size_t n_c, size_t dim, vdb_fr *stream_dev, vdb_fr *lookup_dev, uint8_t *selector_dev, uint8_t *routed_dev,
+                          vdb_fr *public_dev);
+
 /* ---- b4 stream -> columns: replaces halo2-base GateThreadBuilder::assign_all (break points, keygen)
  *      and assign_threads_in (prover) as driven by RangeCircuitBuilder::prover(builder, break_points)
  *      (src/scaffold/mod.rs:393-396).  Columns are 2^k rows; the cell on a break row is duplicated at

@@ -28,7 +28,10 @@ verifier check the proof and applies the batch to the resident index (AnnIndex.u
 again, so every delete but the first removes the member the one before moved there; the last member moves into the slot and the cluster's
 tree halves when the fill drops to a power of two; [index_root_old | c | slot, removed leaf, last, moved leaf per delete | index_root_new]
 public), has the verifier check the proof and removes the batch from the resident index (AnnIndex.removed), whose root must be the
-public index_root_new."""
+public index_root_new.
+`--circuit ann-audit --K C [--cluster c]` proves the routing of one cluster of that index (pipeline.AnnAuditHotPath: the database is routed
+with AnnIndex.assign, the circuit's own fixed-point rule; every member of cluster c — default: the largest — is at least as close to
+centroid c as to any other centroid; [index_root | c] public) and has the verifier check the proof.  Exit status 0 when it is accepted."""
 import argparse
 import json
 import os
@@ -39,7 +42,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from halo2_vectordb_amd import api  # noqa: E402
-from halo2_vectordb_amd.pipeline import AnnDeleteHotPath, AnnIndex, AnnQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
+from halo2_vectordb_amd.pipeline import AnnAuditHotPath, AnnDeleteHotPath, AnnIndex, AnnQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
 from halo2_vectordb_amd.rounds import ProverRounds, quotient_identity_holds  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -50,7 +53,7 @@ ap.add_argument("--seed", type=int, default=20260003)
 ap.add_argument("--block-cols", type=int, default=510)
 ap.add_argument("--ext-block-cols", type=int, default=None)
 ap.add_argument("--proofs", type=int, default=2)
-ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read", "ann", "ann-update", "ann-delete"])
+ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read", "ann", "ann-update", "ann-delete", "ann-audit"])
 ap.add_argument("--lookup-bits", type=int, default=13)
 ap.add_argument("--metric", default="euclidean")
 ap.add_argument("--queries", type=int, default=1, help="--circuit query: queries proved against the one database in this proof")
@@ -61,6 +64,7 @@ ap.add_argument("--grow", type=int, default=None, help="--circuit update / ann-u
 ap.add_argument("--reads", type=int, default=8, help="--circuit read: slots opened in this proof")
 ap.add_argument("--leaf-only", action="store_true", help="--circuit read: reveal the leaf digests, not the vectors")
 ap.add_argument("--K", type=int, default=32, help="--circuit ann: clusters of the index")
+ap.add_argument("--cluster", type=int, default=None, help="--circuit ann-audit: the cluster audited (default: the largest)")
 ap.add_argument("--out", default=None, help="write the proof (io.write_snark) and the verifying key beside it")
 args = ap.parse_args()
 
@@ -82,7 +86,7 @@ elif args.circuit == "update":
         raise SystemExit("--deletes is between 0 and --updates, --grow is not negative")
     kinds = [0] * (args.updates - args.deletes) + [1] * args.deletes
     hp = UpdateHotPath(n=args.n, dim=args.dim, m=args.updates, k=args.k, seed=args.seed, kinds=kinds, grow=args.grow)
-elif args.circuit in ("ann", "ann-update", "ann-delete"):
+elif args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit"):
     from halo2_vectordb_amd.pipeline import sift_like_vectors
     if not 1 <= args.K <= args.n:
         raise SystemExit("--K is between 1 and --n")
@@ -91,7 +95,20 @@ elif args.circuit in ("ann", "ann-update", "ann-delete"):
     ids = np.argmin(((db[:, None, :] - db[None, :args.K, :]) ** 2).sum(axis=2), axis=1)
     ids[:args.K] = np.arange(args.K)                           # (a duplicate of an earlier centroid still keeps its own cluster)
     index = AnnIndex(args.n, args.dim, args.K, db, ids, db[:args.K], L=args.lookup_bits, metric=args.metric)
-    if args.circuit == "ann":
+    if args.circuit == "ann-audit":
+        # the clusters the audit can prove are the circuit's own: every row goes where AnnIndex.assign sends it.  The centroids are the
+        # first K vectors moved by one in their first word: a member EQUAL to a centroid has distance 0, and the reference's qsqrt(0)
+        # violates its own asserted constants, as a query equal to a vector does in the query circuits
+        cent = db[:args.K].copy()
+        cent[:, 0] += np.where(cent[:, 0] < 218, 1.0, -1.0)
+        index.free()
+        index = AnnIndex(args.n, args.dim, args.K, db, ids, cent, L=args.lookup_bits, metric=args.metric)
+        routed = index.assign(db)
+        index.free()
+        index = AnnIndex(args.n, args.dim, args.K, db, routed, cent, L=args.lookup_bits, metric=args.metric)
+        c = int(np.argmax(index.sizes)) if args.cluster is None else args.cluster
+        hp = AnnAuditHotPath(index, c, k=args.k, L=args.lookup_bits, metric=args.metric)
+    elif args.circuit == "ann":
         hp = AnnQueryHotPath(index, query, k=args.k, L=args.lookup_bits, metric=args.metric)
     elif args.circuit == "ann-delete":
         c = int(np.argmax(index.sizes))
@@ -128,7 +145,7 @@ wall, host_ms, out = best
 T = {}
 pr.prove(None, timings=T)
 ok = quotient_identity_holds(pr, out["challenges"], out["evals"], out["instances"])
-root_at = 0 if args.circuit == "read" else -1                # a read states the root first, the other circuits last
+root_at = 0 if args.circuit in ("read", "ann-audit") else -1  # a read and an audit state the root first, the other circuits last
 root = api.fr_to_canonical(np.asarray(hp.results() if args.circuit == "merkle" else hp.results()[root_at]).reshape(1, 4))[0]
 root_int = int(root[0]) | int(root[1]) << 64 | int(root[2]) << 128 | int(root[3]) << 192
 if args.out:
@@ -136,13 +153,15 @@ if args.out:
     write_snark(args.out, out["proof"], out["instances"])
     pr.save_verifying_key(args.out + ".vk.npz", opened=out["opened"])
 accepted = {}
-if args.circuit in ("read", "ann", "ann-update", "ann-delete"):
+if args.circuit in ("read", "ann", "ann-update", "ann-delete", "ann-audit"):
     from halo2_vectordb_amd import verifier
     accepted = {"proof_accepted": bool(verifier.verify(out["proof"], out["instances"], verifier.VerifyingKey.from_prover(pr, out["opened"])))}
 if args.circuit == "ann-update":
     index2 = index.updated(hp)
     accepted["applied_index_root_is_the_public_new_root"] = bool(np.array_equal(index2.roots()[-1], hp.results()[-1]))
     index2.free()
+if args.circuit == "ann-audit":
+    accepted["members_routed"] = int(hp.results()[2].sum())
 if args.circuit == "ann-delete":
     index2 = index.removed(hp)
     accepted["removed_index_root_is_the_public_new_root"] = bool(np.array_equal(index2.roots()[-1], hp.results()[-1]))
@@ -152,6 +171,7 @@ what = f"merkle_commitment {args.n}x{args.dim} k={args.k}" if args.circuit == "m
     f"{args.reads} Merkle openings ({'leaves' if args.leaf_only else 'vectors'} public) against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "read" else \
     f"ann query (K={args.K}, cluster {hp.cluster} of {hp.n} vectors, {args.metric}) against the index of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann" else \
     f"{args.updates} writes into cluster {hp.cluster} ({hp.n} members, tree grown {hp.grow} times) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-update" else \
+    f"routing audit of cluster {hp.cluster} ({hp.n} members, {args.metric}) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann-audit" else \
     f"{args.deletes} deletes from cluster {hp.cluster} ({hp.n} members, tree halved {hp.shrink} times) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-delete" else \
     f"query circuit ({str(args.queries) + ' x ' if args.queries > 1 else ''}{'top-' + str(args.topk) + ' ' if args.topk > 1 else ''}nearest_vector {args.metric} + merkle_commitment) over {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}"
 print(json.dumps({"workload": what + ": whole constraint map, public outputs in the instance column, transcript, fresh blinds, SHPLONK", "lookup_cells": hp.n_lookup,
@@ -163,5 +183,7 @@ print(json.dumps({"workload": what + ": whole constraint map, public outputs in 
                   "block_cols": args.block_cols, "ext_cols_held": hp.ext_cols}))
 pr.free()
 hp.free()
-if args.circuit in ("ann", "ann-update", "ann-delete"):
+if args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit"):
     index.free()
+if args.circuit == "ann-audit" and not accepted["proof_accepted"]:
+    sys.exit(1)
