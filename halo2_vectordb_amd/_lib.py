@@ -91,6 +91,11 @@ _SIGNATURES = {
     "vdb_wit_ann_audit_size": [_I, _U32, _U32, _SZ, _SZ, _SZ, _P, _P, _P],
     "vdb_wit_ann_audit": [_I, _U32, _U32, _P, _P, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],
     "vdb_wit_ann_audit_dev": [_I, _U32, _U32, _P, _P, _P, _P, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],
+    "vdb_wit_ann_mean_size": [_U32, _U32, _SZ, _SZ, _SZ, _P, _P, _P],
+    "vdb_wit_ann_mean": [_U32, _U32, _P, _P, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],
+    "vdb_wit_ann_mean_dev": [_U32, _U32, _P, _P, _P, _P, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],
+    "vdb_ann_cluster_means_dev": [_U32, _U32, _P, _P, _SZ, _SZ, _SZ, _P],
+    "vdb_ann_cluster_means": [_U32, _U32, _P, _P, _SZ, _SZ, _SZ, _P],
     "vdb_wit_nearest_batch_size": [_I, _U32, _U32, _SZ, _SZ, _SZ, _P, _P],
     "vdb_wit_nearest_batch": [_I, _U32, _U32, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],
     "vdb_wit_nearest_batch_dev": [_I, _U32, _U32, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],

@@ -564,6 +564,39 @@ def wit_ann_audit(metric, centroids, members, roots, cluster, P=48, L=13, select
     return dict(stream=stream, lookup=lookup, **_split_flags(sel), n_in=n_in.value, routed=routed, public=pub)
 
 
+def wit_ann_mean(centroids, members, roots, cluster, P=48, L=13, selectors=False):
+    """the mean audit of one cluster (vdb_wit_ann_mean) on centroids (K, dim, 4), the members of cluster `cluster` (n_c, dim, 4) and roots
+    (K + 1, 4): [centroids' root | cluster roots]: dict(stream, lookup, selectors, flags, n_in, mean_ok (dim,) uint8: word j of centroid
+    `cluster` is qdiv(sum of the members' words j, quantization(n_c)), public (2, 4): [index_root | c])"""
+    lib = _lib.init()
+    centroids, members, roots = _fr(centroids), _fr(members), _fr(roots)
+    K, dim, n_c = centroids.shape[0], centroids.shape[1], members.shape[0]
+    assert members.shape[1] == dim and roots.shape == (K + 1, 4)
+    cells, lk, n_in = _u64(), _u64(), _u64()
+    check(lib.vdb_wit_ann_mean_size(ctypes.c_uint32(P), ctypes.c_uint32(L), _sz(K), _sz(n_c), _sz(dim), ctypes.byref(cells), ctypes.byref(lk),
+                                    ctypes.byref(n_in)))
+    stream = np.zeros((cells.value, 4), dtype=np.uint64)
+    lookup = np.zeros((lk.value, 4), dtype=np.uint64)
+    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
+    ok, pub = np.zeros(dim, dtype=np.uint8), np.zeros((2, 4), dtype=np.uint64)
+    check(lib.vdb_wit_ann_mean(ctypes.c_uint32(P), ctypes.c_uint32(L), _p(centroids), _p(members), _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(dim),
+                               _p(stream), _p(lookup), _p(sel) if selectors else None, _p(ok), _p(pub)))
+    return dict(stream=stream, lookup=lookup, **_split_flags(sel), n_in=n_in.value, mean_ok=ok, public=pub)
+
+
+def ann_cluster_means(grouped, offsets, P=48, L=13):
+    """the means of all K clusters of grouped rows (n, dim, 4), cluster k the rows [offsets[k], offsets[k + 1]) (vdb_ann_cluster_means: values
+    only): (K, dim, 4), means[k][j] = qdiv(sum of the cluster's words j, quantization(n_k)) bit for bit as vdb_wit_ann_mean constrains it"""
+    lib = _lib.init()
+    grouped = _fr(grouped)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    assert grouped.ndim == 3 and offsets.ndim == 1 and offsets.size >= 1
+    n, dim, K = grouped.shape[0], grouped.shape[1], offsets.size - 1
+    means = np.zeros((K, dim, 4), dtype=np.uint64)
+    check(lib.vdb_ann_cluster_means(ctypes.c_uint32(P), ctypes.c_uint32(L), _p(grouped), _p(offsets), _sz(n), _sz(K), _sz(dim), _p(means)))
+    return means
+
+
 def _wit_ann_batch(levels, cells, n_pub, selectors, call, **sizes):
     """the buffers of a host-array call against the index root and its dict: call(levels, stream, selectors or None, public) -> its code"""
     levels = np.array(levels, dtype=np.uint64, copy=True)

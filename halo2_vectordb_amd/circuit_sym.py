@@ -1700,6 +1700,105 @@ def build_ann_audit(metric, K, n_c, dim, P, L, fetch_flags, fetch_values, builde
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# The mean audit of one cluster (include/vdb.h vdb_wit_ann_mean; pipeline.AnnMeanHotPath)
+def mean_units(K, P, L):
+    """the unit blocks of the mean audit: dict(sb: select_by_indicator over K cells, add: qadd, qd: qdiv)"""
+    s = Sym(P, L)
+    u = dict(sb=Block(s, [s.g_select_by_indicator([ext(k) for k in range(K)], [ext(K + k) for k in range(K)])]))
+    s = Sym(P, L)
+    u["add"] = Block(s, [s.g_add(ext(0), ext(1))])
+    s = Sym(P, L)
+    u["qd"] = Block(s, [s.qdiv(ext(0), ext(1))])
+    return u
+
+
+def ann_mean_layout(K, n_c, dim, P, L):
+    """where the blocks of the mean audit circuit start: the head's keys of _ann_frame_layout (c, centroids_root, roots, n_in, indicator,
+    select, sponge_old, sponge) and centroids, members: the assigned block I (`update`: its first cell, where the head ends); own: block
+    S (dim select_by_indicator over K cells); len: the constant quantization(n_c), block M's first cell; chain: the qadd cells; div: the
+    dim qdiv blocks; merkle_c, merkle_m; total, total_l; units: mean_units; zero_c: the centroids' padding loads the zero cell"""
+    if n_c < 1 or dim < 1:
+        raise ValueError("at least one member and one word")
+    if n_c >= 1 << P:
+        raise ValueError("quantization(n_c) must stay below qdiv's divisor bound 2^(2P)")
+    head = _ann_frame_layout(K, merkle_leaf_layout(K + 1), 0)
+    lay = {k: head[k] for k in ("c", "centroids_root", "roots", "n_in", "indicator", "sponge", "select", "sponge_old", "update")}
+    u = mean_units(K, P, L)
+    zero_c = (1 << (K - 1).bit_length()) > K
+    lay.update(units=u, zero_c=zero_c, centroids=lay["update"], members=lay["update"] + K * dim)
+    lay["own"] = lay["members"] + n_c * dim
+    lay["len"] = lay["own"] + dim * u["sb"].n
+    lay["chain"] = lay["len"] + 1
+    lay["div"] = lay["chain"] + (n_c - 1) * dim * u["add"].n
+    lay["merkle_c"] = lay["div"] + dim * u["qd"].n
+    lay["merkle_m"] = lay["merkle_c"] + merkle_cells(K, dim)
+    lay["total"] = lay["merkle_m"] + merkle_cells(n_c, dim, zero_c)
+    lay["total_l"] = dim * u["qd"].n_lk
+    return lay
+
+
+def place_mean(B, u, members, centroids, ind, n_c_quantized, own_base, len_cell, lbase):
+    """Blocks S and M placed into builder `B` from the unit blocks of `u` = mean_units: per word j select_by_indicator(centroids[:, j],
+    `ind`) at own_base + j sb.n; the constant `n_c_quantized` at `len_cell`; from len_cell + 1 on the qadd(member_i[j], running sum) of
+    members i = 1 .. n_c - 1, member-major (kmeans' order and stride), then per word qdiv(sum_j, len), its lookup cells from lbase +
+    j qd.n_lk on.  `members` (n_c, dim) / `centroids` (K, dim) / `ind` (K,): stream cells.  -> (own (dim,), mean (dim,)): the selection's
+    outputs and the quotients; the caller ties them."""
+    sb, add, qd = u["sb"], u["add"], u["qd"]
+    members, centroids = np.asarray(members, dtype=np.int64), np.asarray(centroids, dtype=np.int64)
+    (n_c, dim), K = members.shape, centroids.shape[0]
+    ind = np.asarray(ind, dtype=np.int64).reshape(K)
+    j = np.arange(dim, dtype=np.int64)
+    own = B.place(sb, own_base + j * sb.n, np.zeros(dim, dtype=np.int64), np.concatenate([centroids.T, np.broadcast_to(ind[None, :], (dim, K))], axis=1))[:, 0]
+    B.constant_cell(len_cell, n_c_quantized)                 # ctx.load_constant(quantization(n_c))
+    chain = len_cell + 1
+    sum_cells = members[0].copy()
+    if n_c > 1:
+        vv, jj = np.repeat(np.arange(1, n_c, dtype=np.int64), dim), np.tile(j, n_c - 1)
+        bases = chain + (vv - 1) * add.n * dim + add.n * jj
+        outs = bases + add.outs[0]
+        prev = np.where(vv == 1, members[0][jj], outs - add.n * dim)
+        B.place(add, bases, np.zeros_like(bases), np.stack([members[vv, jj], prev], axis=1))    # qadd(member's word, running sum)
+        sum_cells = outs.reshape(n_c - 1, dim)[-1]
+    div = chain + (n_c - 1) * dim * add.n
+    mean = B.place(qd, div + j * qd.n, lbase + j * qd.n_lk, np.stack([sum_cells, np.full(dim, len_cell)], axis=1))[:, 0]
+    return own, mean
+
+
+def ann_mean_instances(index_root, c):
+    """the public cells in make_public order: [index_root | c]"""
+    return [int(index_root), int(c)]
+
+
+def build_ann_mean(K, n_c, dim, P, L, fetch_flags, fetch_values, builder=None):
+    """The mean audit of one cluster in one circuit (pipeline.AnnMeanHotPath): the frame's head (_build_ann_head: the header
+    [c | centroids_root | cluster roots], idx_to_indicator(c, K), select_by_indicator(cluster roots, ind) -> picked, the sponge ->
+    index_root), [centroids | members] assigned, blocks S and M (place_mean) with every quotient mean_j TIED to own_j — word j of centroid
+    c is the mean of the members' words j — then merkle_commitment(centroids), tied to the header's centroids_root, and
+    merkle_commitment(members), tied to picked.  fetch_flags / fetch_values: as place_merkle; `builder`: as build_kmeans.
+    -> (CopyMap, public cells [index_root, c], dict(indicators, picked, own, mean, len, centroids_root, members_root, index_root, layout))"""
+    lay = ann_mean_layout(K, n_c, dim, P, L)
+    B, inds, picked, index_root = _build_ann_head(lay, fetch_flags, fetch_values, builder)
+    if np.asarray(fetch_flags(lay["centroids"], lay["own"])).any():
+        raise ValueError("the assigned centroids and members carry no gate or constant flag")
+    cent = lay["centroids"] + np.arange(K * dim, dtype=np.int64).reshape(K, dim)
+    mem = lay["members"] + np.arange(n_c * dim, dtype=np.int64).reshape(n_c, dim)
+    own, mean = place_mean(B, lay["units"], mem, cent, inds, n_c << P, lay["own"], lay["len"], 0)
+    for o, x in zip(own.tolist(), mean.tolist()):
+        B.tie(x, o)                                          # ctx.constrain_equal(own_j, mean_j)
+    croot, end = place_merkle(B, K, dim, lay["merkle_c"], lay["centroids"], fetch_flags, fetch_values)
+    assert end == lay["merkle_m"]
+    B.tie(croot, lay["centroids_root"])                      # ctx.constrain_equal(centroids_root, croot)
+    zero = lay["merkle_c"] + K * merkle_leaf_layout(dim)["leaf_cells"] if lay["zero_c"] else None
+    mroot, end = place_merkle(B, n_c, dim, lay["merkle_m"], lay["members"], fetch_flags, fetch_values, zero_cell=zero)
+    if end != lay["total"]:
+        raise ValueError("the trace does not end where the circuit does")
+    B.tie(mroot, picked)                                     # ctx.constrain_equal(picked, mroot)
+    info = dict(indicators=[int(i) for i in inds], picked=picked, own=[int(o) for o in own], mean=[int(x) for x in mean], len=lay["len"],
+                centroids_root=croot, members_root=mroot, index_root=index_root, layout=lay)
+    return B.finish(), ann_mean_instances(index_root, lay["c"]), info
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # Merkle openings (include/vdb.h vdb_wit_merkle_open; pipeline.ReadHotPath)
 def merkle_open_layout(m, dim, depth, with_vectors):
     """where the cells of m openings lie: dict(nperm, n_ins, sizes, leaf_cells, node_cells, level_cells, ip_cells, per_read, n_lead,

@@ -71,6 +71,33 @@ static inline AnnaBlocks anna_blocks(uint64_t K, uint64_t n_c, uint64_t dim, uin
   return o;
 }
 
+// ------------------------------------------------------------------ the mean audit of one cluster (include/vdb.h vdb_wit_ann_mean)
+// first stream cell of every block: A - D the frame's head as above (b_ind, b_sel, b_old), I the assigned [centroids K x dim | members
+// n_c x dim], S select_by_indicator(centroids, ind) word by word (1 + 3 K cells each) -> own, M: the constant len = quantization(n_c) at
+// b_m, the qadd chain from b_chain on (4 cells per member after the first and word, member-major), the dim qdiv blocks from b_div on; MC
+// and MM the two merkle_commitments.  Lookup cells are the qdiv blocks' alone, word j's from j * qdiv_lk on.
+struct AnnmBlocks {
+  uint64_t n_in, b_ind, b_sel, b_old, b_in, b_s, b_m, b_chain, b_div, b_mc, b_mm, total, total_l;
+};
+static inline AnnmBlocks annm_blocks(uint64_t K, uint64_t n_c, uint64_t dim, uint64_t sponge_cells, uint64_t qdiv_cells, uint64_t qdiv_lk,
+                                     uint64_t mc_cells, uint64_t mm_cells) {
+  AnnmBlocks o;
+  o.n_in = K + 2;
+  o.b_ind = o.n_in;
+  o.b_sel = o.b_ind + 8 + 12 * (K - 1);
+  o.b_old = o.b_sel + 1 + 3 * K;
+  o.b_in = o.b_old + sponge_cells;
+  o.b_s = o.b_in + (K + n_c) * dim;
+  o.b_m = o.b_s + dim * (1 + 3 * K);
+  o.b_chain = o.b_m + 1;
+  o.b_div = o.b_chain + (n_c - 1) * dim * 4;
+  o.b_mc = o.b_div + dim * qdiv_cells;
+  o.b_mm = o.b_mc + mc_cells;
+  o.total = o.b_mm + mm_cells;
+  o.total_l = dim * qdiv_lk;
+  return o;
+}
+
 // The members of a cluster stay dense: write j goes to a slot below the fill at its turn (a replacement) or exactly at it (an append,
 // which raises the fill by one).  n_c: the fill before the batch, glp: the padded leaf count of the grown tree.
 // -> 0 and *appends; 1: indices[*bad] lies above the fill at its turn; 2: it lies outside the grown tree

@@ -940,26 +940,78 @@ __global__ __launch_bounds__(64) void k_km_sum(Streams st, const FpTables* __res
   const u256 tot = chain_fold_wave<1>(c, base, 4ull * kl.D, kl.N, [&](uint32_t v) { return filt[((size_t)k * kl.N + v) * kl.D + j]; });
   if (threadIdx.x == 0) sums[id] = tot;
 }
-__global__ __launch_bounds__(64) void k_km_div(Streams st, const FpTables* __restrict__ T, KmLayout kl, uint64_t cbase0, uint64_t clbase0,
-                                               const u256* __restrict__ sums, const u256* __restrict__ sizes, u256* __restrict__ cent) {
-  uint32_t id = blockIdx.x * 64 + threadIdx.x;
-  const bool live = id < kl.K * kl.D;
-  if (!live) id = kl.K * kl.D - 1;
-  uint32_t k = id / kl.D, j = id % kl.D;
+// One lane's qdiv(a(), b()) at (base, lbase), its cell range cut into gridDim.y slices (blockIdx.y's is emitted); every slice but the last
+// leaves at once where no lane of the wavefront touches the rank window.  The last slice hands the quotient to done(r) and reports err.
+// A lane past the end (`live` false) runs a real lane's operands with an empty window.  The body of k_km_div and k_annm_div.
+template <class A, class B, class Done>
+__device__ __forceinline__ void qdiv_sliced(const Streams& st, const FpTables* __restrict__ T, uint64_t base, uint64_t lbase, bool live, A&& a, B&& b,
+                                            Done&& done) {
   const uint32_t S = gridDim.y, s = blockIdx.y;
-  const uint64_t base = cbase0 + (uint64_t)k * kl.per_cluster + (uint64_t)kl.N * (8 + 8ull * kl.D) + (uint64_t)(kl.N - 1) * kl.D * 4 + (uint64_t)j * T->sz.qdiv[0];
-  const uint64_t lbase = clbase0 + (uint64_t)k * kl.per_cluster_l + (uint64_t)j * T->sz.qdiv[1];
   if (s != S - 1 && !__any((int)(live && st.touches(base, base + T->sz.qdiv[0], lbase, lbase + T->sz.qdiv[1])))) return;
   WCtx c = make_ctx(st, T, base, lbase);
   c.lo = base + (uint64_t)T->sz.qdiv[0] * s / S;
   c.hi = base + (uint64_t)T->sz.qdiv[0] * (s + 1) / S;
   if (!live) c.lo = c.hi = base;
   Gadgets g(c);
-  u256 r = g.fp_qdiv(sums[id], sizes[k]);
+  u256 r = g.fp_qdiv(a(), b());
   if (live && s == S - 1) {
-    cent[id] = r;
+    done(r);
     if (c.err) atomicOr(st.err, c.err);
   }
+}
+__global__ __launch_bounds__(64) void k_km_div(Streams st, const FpTables* __restrict__ T, KmLayout kl, uint64_t cbase0, uint64_t clbase0,
+                                               const u256* __restrict__ sums, const u256* __restrict__ sizes, u256* __restrict__ cent) {
+  uint32_t id = blockIdx.x * 64 + threadIdx.x;
+  const bool live = id < kl.K * kl.D;
+  if (!live) id = kl.K * kl.D - 1;
+  uint32_t k = id / kl.D, j = id % kl.D;
+  const uint64_t base = cbase0 + (uint64_t)k * kl.per_cluster + (uint64_t)kl.N * (8 + 8ull * kl.D) + (uint64_t)(kl.N - 1) * kl.D * 4 + (uint64_t)j * T->sz.qdiv[0];
+  const uint64_t lbase = clbase0 + (uint64_t)k * kl.per_cluster_l + (uint64_t)j * T->sz.qdiv[1];
+  qdiv_sliced(st, T, base, lbase, live, [&] { return sums[id]; }, [&] { return sizes[k]; }, [&](const u256& r) { cent[id] = r; });
+}
+// The mean audit's block M (include/vdb.h vdb_wit_ann_mean), addressed without an indicator or a filter: one wavefront per word j folds
+// s_ij = member_i[j] + s_{i-1,j} over the n_c members, the qadd cells [x_ij, s_{i-1,j}, 1, s_ij] at chain + 4 ((i - 1) dim + j)
+// (k_km_sum's order and stride); then per word qdiv(s_j, len) at div + j qdiv[0], and mean_ok[j]: the quotient's bits are own_j's.
+__global__ __launch_bounds__(64) void k_annm_sum(Streams st, const FpTables* __restrict__ T, uint64_t chain, uint32_t n_c, uint32_t dim,
+                                                 const u256* __restrict__ members, u256* __restrict__ sums) {
+  const uint32_t j = blockIdx.x;
+  WCtx c = make_ctx(st, T, 0, 0);
+  const u256 tot = chain_fold_wave<1>(c, chain + 4ull * j, 4ull * dim, n_c, [&](uint32_t v) { return members[(size_t)v * dim + j]; });
+  if (threadIdx.x == 0) sums[j] = tot;
+}
+__global__ __launch_bounds__(64) void k_annm_div(Streams st, const FpTables* __restrict__ T, uint64_t div, uint32_t dim, const u256* __restrict__ sums,
+                                                 u256 len, const u256* __restrict__ own, uint8_t* __restrict__ mean_ok) {
+  uint32_t j = blockIdx.x * 64 + threadIdx.x;
+  const bool live = j < dim;
+  if (!live) j = dim - 1;
+  qdiv_sliced(st, T, div + (uint64_t)j * T->sz.qdiv[0], (uint64_t)j * T->sz.qdiv[1], live, [&] { return sums[j]; }, [&] { return len; },
+              [&](const u256& r) { mean_ok[j] = u256_eq(r, own[j]) ? 1 : 0; });
+}
+// The means of all K clusters of a resident index as values alone (include/vdb.h vdb_ann_cluster_means_dev): per cluster k and word j
+// qdiv(sum_i member_i[j], quantization(n_k)), the k-means tail's arithmetic with no filter in front.  fr_add is exact and associative, so
+// the serial walk gives the bits of the circuit's qadd chain; the quotient is the value form fp_qdiv takes under an empty window.  Grid
+// (ceil(dim / 64), K), one wavefront per block: lane l owns word 64 blockIdx.x + l, a member row is read as one contiguous run, KM_PF
+// loads are issued ahead of their adds as in chain_fold_wave.  The host has checked the offsets (rising, the last one the row count).
+__global__ __launch_bounds__(64) void k_ann_means(const u256* __restrict__ grouped, const uint64_t* __restrict__ offsets, uint32_t dim, int* __restrict__ err,
+                                                  u256* __restrict__ means) {
+  const uint32_t k = blockIdx.y, j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= dim) return;
+  const uint64_t lo = offsets[k], hi = offsets[k + 1];
+  u256 tot = u256_zero();
+  for (uint64_t v0 = lo; v0 < hi; v0 += KM_PF) {
+    u256 xv[KM_PF];
+#pragma unroll
+    for (uint32_t q = 0; q < KM_PF; q++) xv[q] = grouped[(size_t)(v0 + q < hi ? v0 + q : hi - 1) * dim + j];
+#pragma unroll
+    for (uint32_t q = 0; q < KM_PF; q++)
+      if (v0 + q < hi) tot = fr_add(tot, xv[q]);
+  }
+  WCtx c{};
+  Gadgets g(c);
+  const u256 len = fr_mul(to_mont<Fr>(u256_from_u64(hi - lo)), g.T.scale);   // quantization(n_k) = n_k 2^P
+  int e = 0;
+  means[(size_t)k * dim + j] = g.v_qdiv(tot, len, e);
+  if (e) atomicOr(err, e);
 }
 __global__ void k_push_cells(Streams st, uint64_t pos, u256 a, u256 b, uint32_t n) {
   if (blockIdx.x || threadIdx.x || n == 0) return;
@@ -2234,6 +2286,81 @@ int wit_ann_audit_dev(FpEntry* fp, int metric, const u256* centroids, const u256
   return inv_list_fixup(f.st);
 }
 
+// ------------------------------------------------------------------ the mean audit of one cluster (include/vdb.h vdb_wit_ann_mean):
+// word for word, centroid c is qdiv(sum of the members committed under cluster_root_c, quantization(n_c)).  Blocks A - D are the frame's
+// head; I [centroids | members] assigned; S select_by_indicator(centroids, ind) -> own (k_nv_select over the K centroids, a lane per
+// word); M the constant len, the qadd chains and the dim qdiv, whose outputs the map ties to own; MC, MM the two merkle_commitments,
+// whose roots the map ties to the header's centroids_root and to picked.  Nothing after the head is the frame's: close() is not called.
+struct AnnmLayout {
+  AnnuLayout fr;     // what AnnFrame::open reads: b_ind, b_sel, b_old, total, mw
+  MkLayout mc, mm;
+  AnnmBlocks b;
+};
+// the refusals, in the frame's order, and where the blocks start
+static int annm_layout(FpEntry* fp, size_t K, size_t cluster, size_t n_c, size_t dim, AnnmLayout* o) {
+  MkuLayout none{};
+  TRY(ann_frame_layout(K, cluster, n_c, &o->fr, &none, [&](uint64_t*) -> int {
+    VDB_ARG(n_c > 0 && dim > 0 && dim <= ((size_t)1 << 20), "empty cluster, dim = 0 or dim above 2^20");
+    const size_t cap = VDB_NEAREST_TOPK_MAX_INSTANCES;
+    VDB_ARG(K <= cap / dim && n_c <= cap / dim, "mean audit too large: K * dim and n_c * dim at most VDB_NEAREST_TOPK_MAX_INSTANCES");
+    // qdiv's divisor is asserted below 2^(2P) (r_div_mod_var(ar, ba, 4P, 2P, ..) in fp_qdiv_emit__body): quantization(n_c) = n_c 2^P
+    VDB_ARG(fp->host.P >= 63 || n_c < ((uint64_t)1 << fp->host.P), "n_c not below 2^P: quantization(n_c) would not pass qdiv's divisor bound 2^(2P)");
+    return VDB_OK;
+  }));
+  mk_layout(K, dim, 0, &o->mc);
+  mk_layout(n_c, dim, (int)o->mc.zero_cell, &o->mm);   // Context::load_zero caches its cell: the centroids' padding has loaded it
+  o->b = annm_blocks(K, n_c, dim, o->fr.mw.total, fp->host.sz.qdiv[0], fp->host.sz.qdiv[1], o->mc.total, o->mm.total);
+  VDB_ARG(o->b.total <= VDB_NEAREST_TOPK_MAX_CELLS, "mean audit circuit above 2^34 cells");
+  o->fr.b.n_in = o->b.n_in;
+  o->fr.b.b_ind = o->b.b_ind;
+  o->fr.b.b_sel = o->b.b_sel;
+  o->fr.b.b_old = o->b.b_old;
+  o->fr.b.total = o->b.total;
+  return VDB_OK;
+}
+// roots: [centroids_root | the K cluster roots]; levels_c / levels_m: the two trees where they are resident (forest segments K and c),
+// or both null; mean_ok: dim bytes; pub: [index_root | c].  own and the chain totals live in the frame's work space (scratch slot 7),
+// not in slot 0, which mk_emit asks for: S and M are still enqueued before the first mk_emit, the order the audit documents.
+int wit_ann_mean_dev(FpEntry* fp, const u256* centroids, const u256* members, const u256* roots, const u256* levels_c, const u256* levels_m, size_t K,
+                     size_t cluster, size_t n_c, size_t dim, Streams st, uint8_t* mean_ok, u256* pub) {
+  AnnmLayout a;
+  TRY(annm_layout(fp, K, cluster, n_c, dim, &a));
+  const AnnmBlocks& b = a.b;
+  AnnFrame f;
+  TRY(f.open(st, roots, K, cluster, a.fr, 0, 2 * dim));
+  TRY(set_winv(f.st, fp->dev));   // the head's gadgets are GateChip's alone; M's qdiv reads the tables of (P, L)
+  u256 *own = f.extra, *sums = own + dim;
+  const bool resident = levels_c && levels_m;
+  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)(((K + n_c) * dim + 255) / 256)), dim3(256), f.st, b.b_in, centroids, members, (uint64_t)(K * dim),
+             (uint64_t)((K + n_c) * dim));
+  const NvMap sm{b.b_s, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, (uint32_t)K, (uint32_t)dim, 1u};
+  VDB_LAUNCH(k_nv_select, dim3((unsigned)((dim + 63) / 64)), dim3(64), f.st, fp->dev, sm, 1u, centroids, f.ind, own);
+  const u256 len = fr_mul(to_mont<Fr>(u256_from_u64(n_c)), fp->host.scale);   // load_constant(quantization(n_c))
+  VDB_LAUNCH(k_push_cells, dim3(1), dim3(1), f.st, b.b_m, len, len, 1u);
+  VDB_LAUNCH(k_annm_sum, dim3((unsigned)dim), dim3(64), f.st, fp->dev, b.b_chain, (uint32_t)n_c, (uint32_t)dim, members, sums);
+  VDB_LAUNCH(k_annm_div, dim3((unsigned)((dim + 63) / 64), 8), dim3(64), f.st, fp->dev, b.b_div, (uint32_t)dim, sums, len, own, mean_ok);
+  TRY(mk_emit(fp, f.sp, centroids, K, dim, a.mc, f.st, b.b_mc, resident ? levels_c : nullptr, nullptr));
+  TRY(mk_emit(fp, f.sp, members, n_c, dim, a.mm, f.st, b.b_mm, resident ? levels_m : nullptr, nullptr));
+  VDB_HIP(hipMemcpyAsync(pub, f.iroot, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
+  VDB_HIP(hipMemcpyAsync(pub + 1, f.hdr, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
+  return inv_list_fixup(f.st);
+}
+
+// the means of all K clusters as values alone (include/vdb.h vdb_ann_cluster_means_dev); `offsets`: the host's copy, already checked
+static int ann_means_dev(FpEntry* fp, const u256* grouped, const uint64_t* offsets_dev, size_t K, size_t dim, int* err, u256* means) {
+  Streams st{nullptr, nullptr, nullptr, err, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};   // the empty rank window: no stream is attached
+  TRY(set_winv(st, fp->dev));
+  VDB_LAUNCH(k_ann_means, dim3((unsigned)((dim + 63) / 64), (unsigned)K), dim3(64), grouped, offsets_dev, (uint32_t)dim, err, means);
+  return VDB_OK;
+}
+// K > 0, dim > 0, offsets rising from 0 to n with no empty cluster: what the kernel's reads rest on
+static int ann_means_check(const uint64_t* offsets, size_t n, size_t K, size_t dim) {
+  VDB_ARG(K > 0 && K <= VDB_ANN_MAX_CLUSTERS && dim > 0 && dim <= ((size_t)1 << 20), "K = 0, K above VDB_ANN_MAX_CLUSTERS, dim = 0 or dim above 2^20");
+  VDB_ARG(n <= VDB_ANN_MAX_VECTORS && offsets[0] == 0 && offsets[K] == n, "offsets do not run from 0 to n, or n above VDB_ANN_MAX_VECTORS");
+  for (size_t k = 0; k < K; k++) VDB_ARG(offsets[k] < offsets[k + 1] && offsets[k + 1] <= n, "an empty cluster, or offsets that do not rise");
+  return VDB_OK;
+}
+
 }  // namespace vdb
 
 using namespace vdb;
@@ -2884,6 +3011,93 @@ int vdb_wit_ann_audit(int metric, uint32_t P, uint32_t L, const vdb_fr* centroid
   TRY(download(routed_out, drt.p, n_c));
   TRY(download(public_out, dpub.p, 2 * sizeof(u256)));
   return hs.finish(stream_out, lookup_out, selector_out, a.b.total, a.b.total_l);
+}
+
+// the mean audit of one cluster (include/vdb.h)
+int vdb_wit_ann_mean_size(uint32_t P, uint32_t L, size_t K, size_t n_c, size_t dim, uint64_t* cells, uint64_t* lookups, uint64_t* input_cells) {
+  VDB_REQUIRE_INIT();
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  AnnmLayout a;
+  TRY(annm_layout(fp, K, 0, n_c, dim, &a));
+  if (cells) *cells = a.b.total;
+  if (lookups) *lookups = a.b.total_l;
+  if (input_cells) *input_cells = a.b.n_in;
+  return VDB_OK;
+}
+int vdb_wit_ann_mean_dev(uint32_t P, uint32_t L, const vdb_fr* centroids_dev, const vdb_fr* members_dev, const vdb_fr* roots_dev,
+                         const vdb_fr* centroid_levels_dev, const vdb_fr* member_levels_dev, size_t K, size_t cluster, size_t n_c, size_t dim,
+                         vdb_fr* stream_dev, vdb_fr* lookup_dev, uint8_t* selector_dev, uint8_t* mean_ok_dev, vdb_fr* public_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(centroids_dev && members_dev && roots_dev && stream_dev && lookup_dev && mean_ok_dev && public_dev, "null pointer");
+  VDB_ARG(!centroid_levels_dev == !member_levels_dev, "the two resident trees are given together or not at all");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  DevStreams ds;
+  TRY(ds.init(stream_dev, selector_dev, lookup_dev));
+  TRY(wit_ann_mean_dev(fp, as_u256(centroids_dev), as_u256(members_dev), as_u256(roots_dev), centroid_levels_dev ? as_u256(centroid_levels_dev) : nullptr,
+                       member_levels_dev ? as_u256(member_levels_dev) : nullptr, K, cluster, n_c, dim, ds.st, mean_ok_dev, as_u256(public_dev)));
+  return ds.finish();
+}
+int vdb_wit_ann_mean(uint32_t P, uint32_t L, const vdb_fr* centroids, const vdb_fr* members, const vdb_fr* roots, size_t K, size_t cluster, size_t n_c,
+                     size_t dim, vdb_fr* stream_out, vdb_fr* lookup_out, uint8_t* selector_out, uint8_t* mean_ok_out, vdb_fr* public_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(centroids && members && roots && mean_ok_out && public_out, "null pointer");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  AnnmLayout a;
+  TRY(annm_layout(fp, K, cluster, n_c, dim, &a));
+  DevBuf dc, dm, dr, dok, dpub;
+  HostStreams hs;
+  TRY(upload(dc, centroids, K * dim * sizeof(u256)));
+  TRY(upload(dm, members, n_c * dim * sizeof(u256)));
+  TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
+  TRY(dok.alloc(dim));
+  TRY(dpub.alloc(2 * sizeof(u256)));
+  TRY(hs.init(a.b.total, a.b.total_l, selector_out != nullptr));
+  TRY(wit_ann_mean_dev(fp, dc.as<u256>(), dm.as<u256>(), dr.as<u256>(), nullptr, nullptr, K, cluster, n_c, dim, hs.st, dok.as<uint8_t>(), dpub.as<u256>()));
+  TRY(download(mean_ok_out, dok.p, dim));
+  TRY(download(public_out, dpub.p, 2 * sizeof(u256)));
+  return hs.finish(stream_out, lookup_out, selector_out, a.b.total, a.b.total_l);
+}
+
+// the means of all K clusters of a resident index, values only (include/vdb.h): no stream, no window
+int vdb_ann_cluster_means_dev(uint32_t P, uint32_t L, const vdb_fr* grouped_dev, const uint64_t* offsets_dev, size_t n, size_t K, size_t dim,
+                              vdb_fr* means_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(grouped_dev && offsets_dev && means_dev, "null pointer");
+  VDB_ARG(K > 0 && K <= VDB_ANN_MAX_CLUSTERS, "K = 0 or K above VDB_ANN_MAX_CLUSTERS");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  std::vector<uint64_t> off(K + 1);   // the kernel's reads rest on the offsets: they are checked on the host before it is launched
+  TRY(download(off.data(), offsets_dev, (K + 1) * sizeof(uint64_t)));
+  VDB_HIP(hipStreamSynchronize(ctx().stream));
+  TRY(ann_means_check(off.data(), n, K, dim));
+  int* derr = (int*)scratch_get(1, 64);
+  if (!derr) return VDB_ERR_OOM;
+  VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
+  TRY(ann_means_dev(fp, as_u256(grouped_dev), offsets_dev, K, dim, derr, as_u256(means_dev)));
+  return check_err_flag(derr);
+}
+int vdb_ann_cluster_means(uint32_t P, uint32_t L, const vdb_fr* grouped, const uint64_t* offsets, size_t n, size_t K, size_t dim, vdb_fr* means_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(grouped && offsets && means_out, "null pointer");
+  VDB_ARG(K > 0 && K <= VDB_ANN_MAX_CLUSTERS, "K = 0 or K above VDB_ANN_MAX_CLUSTERS");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  TRY(ann_means_check(offsets, n, K, dim));   // before anything is uploaded
+  DevBuf dg, doff, dmeans;
+  TRY(upload(dg, grouped, n * dim * sizeof(u256)));
+  TRY(upload(doff, offsets, (K + 1) * sizeof(uint64_t)));
+  TRY(dmeans.alloc(K * dim * sizeof(u256)));
+  int* derr = (int*)scratch_get(1, 64);
+  if (!derr) return VDB_ERR_OOM;
+  VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
+  TRY(ann_means_dev(fp, dg.as<u256>(), doff.as<uint64_t>(), K, dim, derr, dmeans.as<u256>()));
+  TRY(check_err_flag(derr));
+  TRY(download(means_out, dmeans.p, K * dim * sizeof(u256)));
+  VDB_HIP(hipStreamSynchronize(ctx().stream));
+  return VDB_OK;
 }
 
 }  // extern "C"

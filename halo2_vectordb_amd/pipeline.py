@@ -1192,7 +1192,7 @@ class FixedPointHotPath(HotPath):
 class AnnIndex:
     """The committed index of approximate-nearest-neighbour queries, resident on the device (include/vdb.h vdb_ann_index_build_dev): the
     rows grouped by cluster, the forest of the K cluster trees and the centroids' tree, and the K + 2 root digests.  `vectors`: (n, dim)
-    f64; `cluster_ids`: (n,) integers, or KmeansHotPath.results()'s (n, K, 4) indicators; `centroids`: (K, dim) f64, or the (K, dim, 4)
+    f64, or the (n, dim, 4) quantized rows; `cluster_ids`: (n,) integers, or KmeansHotPath.results()'s (n, K, 4) indicators; `centroids`: (K, dim) f64, or the (K, dim, 4)
     quantized centroids KmeansHotPath.results() returns."""
 
     def __init__(self, n, dim, K, vectors, cluster_ids, centroids, P=48, L=13, metric="euclidean"):
@@ -1204,7 +1204,8 @@ class AnnIndex:
         self.cluster_ids = np.ascontiguousarray(ids, dtype=np.uint32)
         cent = np.asarray(centroids)
         self.qcent = np.ascontiguousarray(cent, dtype=np.uint64) if cent.ndim == 3 else api.quantize(np.ascontiguousarray(cent, dtype=np.float64), P)
-        self.qvec = api.quantize(np.ascontiguousarray(vectors, dtype=np.float64), P)
+        vec = np.asarray(vectors)
+        self.qvec = np.ascontiguousarray(vec, dtype=np.uint64) if vec.ndim == 3 else api.quantize(np.ascontiguousarray(vec, dtype=np.float64), P)
         if self.qvec.shape != (n, dim, 4) or self.qcent.shape != (K, dim, 4) or self.cluster_ids.shape != (n,):
             raise ValueError("vectors, cluster ids and centroids do not match (n, dim, K)")
         self.n_digests, self.segments = api.ann_forest_layout(self.cluster_ids, K)     # refuses an empty cluster, an id >= K, K = 0
@@ -1344,6 +1345,26 @@ class AnnIndex:
         finally:
             for b in (d_rows, d_idx, d_dist):
                 b.free()
+
+    def means(self):
+        """(K, dim, 4): the mean of every cluster's members in the circuit's fixed-point arithmetic, qdiv(sum of the members' words,
+        quantization(n_k)), in one values-only call over the resident grouped rows (vdb_ann_cluster_means_dev: nothing is emitted or
+        uploaded) — bit for bit the centroid AnnMeanHotPath accepts for the cluster"""
+        d = api.DeviceBuffer(self.K * self.dim * B)
+        try:
+            check(self.lib.vdb_ann_cluster_means_dev(self.P, self.L, self.d_grouped.ptr, self.d_offsets.ptr, self.n, self.K, self.dim, d.ptr))
+            return d.download((self.K, self.dim, 4))
+        finally:
+            d.free()
+
+    def recentred(self):
+        """a new AnnIndex over the same rows and cluster ids whose centroids are means(): built from scratch by the index build, on
+        buffers of its own; this index stays valid.  After writes and deletes have moved the members, the mean audit of every cluster
+        of the result is clean.  NOT proved: that the result's root descends from this index's — nothing links the two roots; a
+        verifier of a recentred index checks its K mean audits (and K routing audits) against the new root alone."""
+        if self.qvec.shape[0] != self.n:
+            raise ValueError("the database has slots no cluster holds: recentre an index whose rows are dense")
+        return AnnIndex(self.n, self.dim, self.K, self.qvec, self.cluster_ids, self.means(), P=self.P, L=self.L, metric=self.metric_name)
 
     def free(self):
         for b in self._bufs:
@@ -1597,8 +1618,8 @@ class AnnAuditHotPath(HotPath):
     -> picked, the sponge over the roots (index_root), [centroids | members] assigned, per member its K distances, their qmin chain and
     select_by_indicator(distances, indicators) tied to the chain's minimum, merkle_commitment(centroids) tied to the header's centroids'
     root and merkle_commitment(members) tied to picked.  Public: [index_root | c].  It covers the build's cluster ids and the writes after
-    them: audit cluster c of index.updated(hp) after a batch into c; K proofs cover an index.  Not proved: that centroids are means, that
-    the database is complete.  A member equidistant from two centroids is accepted under either.  The shape depends on (K, n_c, dim,
+    them: audit cluster c of index.updated(hp) after a batch into c; K proofs cover an index.  That centroids are means is
+    proved per cluster by a proof of its own (AnnMeanHotPath).  Not proved: that the database is complete.  A member equidistant from two centroids is accepted under either.  The shape depends on (K, n_c, dim,
     metric): one proving key per cluster size.  A misrouted member still gives a witness; results()[2] flags it and its copy fails in
     the Mock report.  `centroids` / `members`: quantized overrides of what the index holds (tests of the binding); with them the two
     trees are hashed by the call instead of read from the forest."""
@@ -1618,6 +1639,10 @@ class AnnAuditHotPath(HotPath):
 
     def _load_inputs(self):
         super()._load_inputs()
+        self._cluster_inputs()
+
+    def _cluster_inputs(self):
+        """where the call reads the centroids and the cluster's members: the resident index, or the overrides given (AnnMeanHotPath's too)"""
         ix, self.resident = self.index, self.given_cent is None and self.given_members is None
         self.p_cent, self.p_members = ix.d_cent.ptr, ix.members_ptr(self.cluster)
         for given, shape, name in ((self.given_cent, (self.K, self.dim, 4), "p_cent"), (self.given_members, (self.n, self.dim, 4), "p_members")):
@@ -1658,5 +1683,70 @@ class AnnAuditHotPath(HotPath):
         from .circuit_dev import DeviceBuilder
         cm, public, _ = CS.build_ann_audit(self.metric_name, self.K, self.n, self.dim, self.P, self.L, functools.partial(self._fetch_flags, d_flags),
                                            self._fetch, builder=DeviceBuilder if on_device else None)
+        assert cm.n_cells == self.n_cells
+        return cm, public, None
+
+
+class AnnMeanHotPath(HotPath):
+    """That centroid c of a committed AnnIndex is the mean of its cluster, proved in one proof (include/vdb.h vdb_wit_ann_mean): word for
+    word, centroid c equals qdiv(sum of the members committed under cluster_root_c, quantization(n_c)) in the circuit's fixed-point
+    arithmetic.  Assigned: the header [c | centroids' root | cluster roots]; then idx_to_indicator(c, K), select_by_indicator(cluster
+    roots, indicators) -> picked, the sponge over the roots (index_root), [centroids | members] assigned, select_by_indicator(centroids,
+    indicators) -> own word by word, the constant quantization(n_c), the qadd chain over the members and one qdiv per word tied to own,
+    merkle_commitment(centroids) tied to the header's centroids' root and merkle_commitment(members) tied to picked.  Public:
+    [index_root | c].  K mean proofs and K routing audits (AnnAuditHotPath) state that the index is a fixed point of one Lloyd step over
+    the committed members.  Not proved: that the database is complete; that a recentred index (AnnIndex.recentred) descends from its
+    predecessor.  The shape depends on (K, n_c, dim): one proving key per cluster size.  A centroid that is not the mean still gives a
+    witness; results()[2] flags the words that differ and their copies fail in the Mock report.  `centroids` / `members`: quantized
+    overrides of what the index holds (tests of the binding); with them the two trees are hashed by the call instead of read from the
+    forest."""
+
+    def __init__(self, index, cluster, k=13, P=48, L=12, tau=None, col_shard=(0, 1), blind_seed=None, params=None, centroids=None, members=None):
+        self.index, self.K, self.cluster = index, index.K, int(cluster)
+        if not 0 <= self.cluster < self.K:
+            raise ValueError("cluster outside the index")
+        super().__init__(int(index.sizes[self.cluster]), index.dim, k, P, L, seed=None, tau=tau, col_shard=col_shard, vectors=np.zeros((0, index.dim)),
+                         blind_seed=blind_seed, params=params)
+        self.given_cent, self.given_members = centroids, members
+
+    def n_input_rows(self):
+        return 0
+
+    _cluster_inputs = AnnAuditHotPath._cluster_inputs
+
+    def _load_inputs(self):
+        super()._load_inputs()
+        self._cluster_inputs()
+
+    def _circuit_size(self):
+        cells, lk, n_in = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(self.lib.vdb_wit_ann_mean_size(self.P, self.L, self.K, self.n, self.dim, ctypes.byref(cells), ctypes.byref(lk), ctypes.byref(n_in)))
+        return n_in.value, cells.value - n_in.value, lk.value
+
+    def _alloc_outputs(self):
+        self.d_ok, self.d_pub = self._output(max(self.dim, 32)), self._output(2 * B)
+
+    def _witness(self, sel=None):
+        # the call writes the assigned header, centroids and members too
+        ix = self.index
+        with self._window(sel, 0):
+            check(self.lib.vdb_wit_ann_mean_dev(self.P, self.L, self.p_cent, self.p_members, ix.d_roots.ptr,
+                                                ix.levels_ptr(self.K) if self.resident else None, ix.levels_ptr(self.cluster) if self.resident else None,
+                                                self.K, self.cluster, self.n, self.dim, self.d_stream.ptr, self.d_lookup.ptr, self._sel_at(sel, 0),
+                                                self.d_ok.ptr, self.d_pub.ptr))
+
+    def public_values_dev(self):
+        return self.d_pub.ptr, 2
+
+    def results(self):
+        """(index_root (4,), c (4,), mean_ok (dim,) uint8: word j of centroid c is the mean of the members' words j)"""
+        pub = self.d_pub.download((2, 4))
+        return pub[0], pub[1], self.d_ok.download((self.dim,), dtype=np.uint8)
+
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        cm, public, _ = CS.build_ann_mean(self.K, self.n, self.dim, self.P, self.L, functools.partial(self._fetch_flags, d_flags), self._fetch,
+                                          builder=DeviceBuilder if on_device else None)
         assert cm.n_cells == self.n_cells
         return cm, public, None

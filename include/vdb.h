@@ -492,7 +492,8 @@ int vdb_ann_index_remove_dev(const vdb_fr *grouped_dev, const vdb_fr *forest_dev
 /* The audit of one cluster's routing: in the index with root index_root, every member committed under cluster_root_c is at least as
  * close to centroid c as to any other committed centroid, in the circuit's fixed-point distance for `metric`.  It covers the build's
  * cluster ids and the writes after them alike (audit cluster c of the index a batch into c leaves); K such proofs cover an index.  It
- * does not prove that centroids are means or that the database is complete.  The reference has no such gadget; the cells are those of
+ * does not prove that centroids are means (vdb_wit_ann_mean below does, per cluster and by a proof of its own) or that the database is
+ * complete.  The reference has no such gadget; the cells are those of
  * the closure a user of its chips writes.  Stream, from cell 0:
  *   A - D  exactly those of vdb_wit_ann_update: the header [c | centroids_root | cluster roots] (K + 2 cells: input_cells),
  *          ind = idx_to_indicator(c, K), picked = select_by_indicator(cluster roots, ind), index_root = the sponge over the roots
@@ -530,6 +531,60 @@ int vdb_wit_ann_audit_dev(int metric, uint32_t precision_bits, uint32_t lookup_b
                           const vdb_fr *roots_dev, const vdb_fr *centroid_levels_dev, const vdb_fr *member_levels_dev, size_t K, size_t cluster,
                           size_t n_c, size_t dim, vdb_fr *stream_dev, vdb_fr *lookup_dev, uint8_t *selector_dev, uint8_t *routed_dev,
                           vdb_fr *public_dev);
+
+/* The mean audit of one cluster: in the index with root index_root, word for word, centroid c equals
+ * qdiv(sum of the members committed under cluster_root_c, quantization(n_c)) in the circuit's fixed-point arithmetic.  K such proofs and
+ * K routing audits (vdb_wit_ann_audit) together state that the index is a fixed point of one Lloyd step over the committed members.  Not
+ * proved: that the database is complete, that a recentred index (new centroids, new root) descends from its predecessor.  The reference
+ * leaves this gadget commented out (src/gadget/vectordb.rs, mean_merkle: a qadd chain over the vectors, qdiv by
+ * load_constant(quantization(len)), bound to a Merkle root); the cells are those of that closure.  Stream, from cell 0:
+ *   A - D  exactly those of vdb_wit_ann_update: the header [c | centroids_root | cluster roots] (K + 2 cells: input_cells),
+ *          ind = idx_to_indicator(c, K), picked = select_by_indicator(cluster roots, ind), index_root = the sponge over the roots
+ *   I      [centroids K x dim | members n_c x dim] assigned
+ *   S      own_j = gate.select_by_indicator([centroid_0[j] .. centroid_K-1[j]], ind), j = 0 .. dim - 1          (1 + 3 K cells each)
+ *   M      len = load_constant(quantization(n_c)) (one cell, constant flag); for members i = 1 .. n_c - 1 and words j the qadd
+ *          [member_i[j], s_i-1,j, 1, s_ij] at M + 1 + 4 ((i - 1) dim + j), s_0j = member_0[j] (kmeans' argument order); then per word
+ *          mean_j = qdiv(s_n_c-1,j, len)                                                                        (qdiv's cells each)
+ *   MC     croot = merkle_commitment(centroids)
+ *   MM     mroot = merkle_commitment(members), its padding copying MC's zero cell where MC's padding has loaded one
+ * Copies (no cell): the chain's operands copy I (at n_c == 1 there is no chain and qdiv's first operand copies the member's cell), every
+ * qdiv divisor copies len, S's indicator cells copy B's outputs; mean_j is tied to own_j; croot is tied to the header's centroids_root and
+ * mroot to picked.  Lookup cells are the qdiv blocks' alone, word j's from j * (qdiv's lookup cells) on.  public, 2 values:
+ * [index_root | c].
+ * A centroid that is not the mean still gives a stream: the call succeeds, mean_ok[j] = 0 for the words that differ (1 for the others)
+ * and only their mean_j = own_j copies fail at Mock or verify time.  The shape depends on (K, n_c, dim): n_c enters as a constant, so there
+ * is one proving key per cluster size; c is a witness.
+ * Known cost: MC hashes all K centroids to bind one.  A Merkle opening of slot c of the centroids' tree, its index tied to c, would cost
+ * about one leaf and depth levels instead.
+ * roots, centroid_levels_dev / member_levels_dev: as in vdb_wit_ann_audit (both resident: the launch count depends on neither K nor n_c;
+ * both NULL: the digests are computed by the call; one alone: VDB_ERR_ARG).  Launches: the head's four emitters and its sponge, one
+ * assignment kernel, one selection, one constant, one kernel for the chains (launched at n_c == 1 too, where it emits nothing), one for
+ * the quotients, the two trees' traces and the inverse fix-up.  The _dev form honours vdb_wit_set_window; mean_ok and public are whole
+ * in every window.  VDB_ERR_ARG before anything is launched: K == 0, K > VDB_ANN_MAX_CLUSTERS, cluster >= K,
+ * n_c > VDB_ANN_MAX_VECTORS, n_c == 0, dim == 0, dim > 2^20, K * dim or n_c * dim above VDB_NEAREST_TOPK_MAX_INSTANCES,
+ * n_c >= 2^precision_bits (qdiv asserts its divisor below 2^(2 precision_bits), and quantization(n_c) = n_c 2^precision_bits; with
+ * precision_bits >= 32 and VDB_ANN_MAX_VECTORS = 2^24 the two limits before it already imply this one), more than 2^34 cells.  _size takes no cluster; each of its outputs may be NULL. */
+int vdb_wit_ann_mean_size(uint32_t precision_bits, uint32_t lookup_bits, size_t K, size_t n_c, size_t dim, uint64_t *cells, uint64_t *lookups,
+                          uint64_t *input_cells);
+int vdb_wit_ann_mean(uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *centroids, const vdb_fr *members, const vdb_fr *roots, size_t K,
+                     size_t cluster, size_t n_c, size_t dim, vdb_fr *stream_out, vdb_fr *lookup_out, uint8_t *selector_out, uint8_t *mean_ok_out,
+                     vdb_fr *public_out);
+int vdb_wit_ann_mean_dev(uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *centroids_dev, const vdb_fr *members_dev,
+                         const vdb_fr *roots_dev, const vdb_fr *centroid_levels_dev, const vdb_fr *member_levels_dev, size_t K, size_t cluster,
+                         size_t n_c, size_t dim, vdb_fr *stream_dev, vdb_fr *lookup_dev, uint8_t *selector_dev, uint8_t *mean_ok_dev,
+                         vdb_fr *public_dev);
+
+/* The means of all K clusters of an index as vdb_ann_index_build_dev leaves it, values only: means[k][j] =
+ * qdiv(sum_i member_i[j], quantization(n_k)) over the rows [offsets[k], offsets[k + 1]) of the grouped rows, bit for bit what
+ * vdb_wit_ann_mean constrains (the sum is exact in the field, so its order does not matter; the quotient is qdiv's value).  A server
+ * recomputes centroids that have drifted after writes and deletes with it, without proving a k-means.  grouped: n x dim; offsets:
+ * K + 1 x uint64; means: K x dim.  One launch whatever K and the cluster sizes; the _dev form reads the K + 1 offsets back first and
+ * checks them on the host.  VDB_ERR_ARG before anything is launched: K == 0, K > VDB_ANN_MAX_CLUSTERS, dim == 0, dim > 2^20,
+ * n > VDB_ANN_MAX_VECTORS, offsets that do not rise from 0 to n, an empty cluster.  VDB_ERR_DOMAIN: a quotient qdiv's value form flags. */
+int vdb_ann_cluster_means_dev(uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *grouped_dev, const uint64_t *offsets_dev, size_t n,
+                              size_t K, size_t dim, vdb_fr *means_dev);
+int vdb_ann_cluster_means(uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *grouped, const uint64_t *offsets, size_t n, size_t K,
+                          size_t dim, vdb_fr *means_out);
 
 /* ---- b4 stream -> columns: replaces halo2-base GateThreadBuilder::assign_all (break points, keygen)
  *      and assign_threads_in (prover) as driven by RangeCircuitBuilder::prover(builder, break_points)
