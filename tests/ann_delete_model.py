@@ -15,6 +15,7 @@ import numpy as np
 import ann_model as AN
 import merkle_update_model as MU
 import topk_model as TM
+from ann_update_model import window_ints
 from merkle_update_model import ZERO, _hash_ctx, assert_bit, inner_product_const
 from topk_model import select, to_ints, to_limbs
 
@@ -153,9 +154,10 @@ def fill_of(tree):
     return n
 
 
-def delete_model(O, roots, c, tree, slots, plan_k=None):
+def delete_model(O, roots, c, tree, slots, plan_k=None, block_flags=True):
     """The closure on `roots` (K + 1, 4) = [centroids' root | cluster roots] and the cluster's `tree` (lists per level; updated in place,
-    kept at its old size).  -> dict(advice, selectors, flags, break_points, n_in, public (4 m + 3, 4),
+    kept at its old size).  block_flags=False leaves the flag bytes of blocks E' and S at their gate bits and reads the integers of the
+    two sponges alone (ann_update_model.update_model).  -> dict(advice, selectors, flags, break_points, n_in, public (4 m + 3, 4),
     regions, update: path_ops_model's dict, indicators, picked, outs, s, s0, shrink_top, index_root_old, index_root_new,
     new_cluster_root, cut_tree: the tree cut to lp >> s)"""
     K, m = roots.shape[0] - 1, len(slots)
@@ -220,13 +222,15 @@ def delete_model(O, roots, c, tree, slots, plan_k=None):
     s.ctx(ctx)
     advice, sel = np.concatenate(s.adv), np.concatenate(s.sel) & 1
     assert advice.shape[0] == sel.shape[0] == s.n
-    flags, vals = sel.copy(), TM.to_ints(advice)
+    flags = sel.copy()
+    vals = TM.to_ints(advice) if block_flags else window_ints(advice, [(reg["sponge_old"], reg["update"]), (reg["sponge_new"], s.n)])
     flags[cst] |= 2
     assert AN._mark_constants(flags, vals, reg["sponge_old"], K + 1) == reg["update"]
     assert AN._mark_constants(flags, vals, reg["sponge_new"], K + 1) == s.n
-    from test_merkle_ops_cpu import kernel_like_flags
-    flags[reg["update"]:reg["shrink"]] = kernel_like_flags(u)
-    if sh:                                                       # block S's hashes: the constants of their permutations, as the update block's
+    if block_flags:
+        from test_merkle_ops_cpu import kernel_like_flags
+        flags[reg["update"]:reg["shrink"]] = kernel_like_flags(u)
+    if sh and block_flags:                                       # block S's hashes: the constants of their permutations, as the update block's
         hashes = dict(advice=advice[reg["shrink"]:reg["new_roots"]], selectors=sel[reg["shrink"]:reg["new_roots"]], constants=[1],
                       perms=[(2 + h * 4506 + k * (18 + 2238), 2 - 2 * k) for h in range(depth - 1 + sh) for k in range(2)])
         flags[reg["shrink"]:reg["new_roots"]] = kernel_like_flags(hashes)

@@ -50,9 +50,25 @@ def updated_database(db, ids, c, indices, new_vectors):
     return db, ids
 
 
-def update_model(O, roots, c, tree, indices, new_vectors, grow=0, plan_k=None):
+class window_ints:
+    """vals[i] for the cells of a few stretches [lo, hi) of a stream as canonical Python integers, the cells outside them left alone:
+    what _mark_constants reads of a sponge without the whole stream being converted"""
+
+    def __init__(self, advice, stretches):
+        self.parts = [(lo, TM.to_ints(advice[lo:hi])) for lo, hi in stretches]
+
+    def __getitem__(self, i):
+        for lo, v in self.parts:
+            if lo <= i < lo + len(v):
+                return v[i - lo]
+        raise IndexError(i)
+
+
+def update_model(O, roots, c, tree, indices, new_vectors, grow=0, plan_k=None, block_flags=True):
     """The closure on `roots` (K + 1, 4) = [centroids' root | cluster roots] and the cluster's `tree` (lists per level, already grown;
-    updated in place).  -> dict(advice, selectors, flags (the kernels' flag bytes: gate bit, constant bit), break_points, n_in, public
+    updated in place).  block_flags=False leaves the update block's flag bytes at their gate bits (the pass that reads the constant
+    bits off every cell's integer takes most of the time of a long batch; the caller then holds that block's flags to something else)
+    and reads the integers of the two sponges alone.  -> dict(advice, selectors, flags (the kernels' flag bytes: gate bit, constant bit), break_points, n_in, public
     (3 m + 3, 4), regions: first cell of each block, update: ops_model's dict, indicators, picked, outs, index_root_old, index_root_new)"""
     K, m = roots.shape[0] - 1, len(indices)
     assert 0 <= c < K
@@ -99,12 +115,14 @@ def update_model(O, roots, c, tree, indices, new_vectors, grow=0, plan_k=None):
     s.ctx(ctx)
     advice, sel = np.concatenate(s.adv), np.concatenate(s.sel) & 1
     assert advice.shape[0] == sel.shape[0] == s.n
-    flags, vals = sel.copy(), TM.to_ints(advice)
+    flags = sel.copy()
+    vals = TM.to_ints(advice) if block_flags else window_ints(advice, [(reg["sponge_old"], reg["update"]), (reg["sponge_new"], s.n)])
     flags[cst] |= 2
     assert AN._mark_constants(flags, vals, reg["sponge_old"], K + 1) == reg["update"]
     assert AN._mark_constants(flags, vals, reg["sponge_new"], K + 1) == s.n
-    from test_merkle_ops_cpu import kernel_like_flags
-    flags[reg["update"]:reg["new_roots"]] = kernel_like_flags(u)
+    if block_flags:
+        from test_merkle_ops_cpu import kernel_like_flags
+        flags[reg["update"]:reg["new_roots"]] = kernel_like_flags(u)
     public = np.concatenate([root_old[None], TM.to_limbs([c]), u["public"][1:-1], root_new[None]])
     return dict(advice=advice, selectors=sel, flags=flags, break_points=TM.row_walk(sel, plan_k) if plan_k is not None else None, n_in=K + 2,
                 public=public, regions=reg, update=u, indicators=ind, picked=picked, outs=outs, index_root_old=root_old, index_root_new=root_new,

@@ -58,6 +58,24 @@ def build_tree(O, db):
     return levels
 
 
+def walk_values(O, levels, indices, new_vectors):
+    """The batch as values alone, for batches far beyond what update_model can trace cell by cell: the updates applied one after the
+    other on the tree `levels` (build_tree's lists; updated in place), every digest from O.poseidon_hash_many, no cell.
+    -> the 3 m + 2 public values [old root | idx, old leaf, new leaf per update | new root]"""
+    m, depth = new_vectors.shape[0], len(levels) - 1
+    assert depth >= 1 and m == len(indices) >= 1
+    new_leaves = O.poseidon_hash_many(np.ascontiguousarray(new_vectors))
+    pub = [levels[depth][0].copy()]
+    for j in range(m):
+        idx = int(indices[j])
+        pub += [to_limbs([idx])[0], levels[0][idx].copy(), new_leaves[j].copy()]
+        levels[0][idx] = new_leaves[j].copy()
+        for l in range(depth):
+            node = (idx >> l) & ~1
+            levels[l + 1][node >> 1] = O.poseidon_hash_many(np.stack([levels[l][node], levels[l][node + 1]])[None])[0]
+    return np.stack(pub + [levels[depth][0].copy()])
+
+
 def flat_levels(levels):
     """the device layout: the levels one after the other, 2 lp entries, the last zero"""
     return np.stack([x for lv in levels for x in lv] + [ZERO])
