@@ -543,25 +543,31 @@ def wit_ann_query(metric, query, centroids, members, cluster_roots, P=48, L=13, 
                 index_root=pub[dim], public=pub)
 
 
+def _wit_ann_cluster(size, call, metric, centroids, members, roots, cluster, P, L, selectors, flag, per_member):
+    """the buffers of a host-array audit of one cluster and its dict: `size` / `call` the library's two entry points, which take the metric
+    (where the audit has one: `metric` not None), P and L ahead of what the audits share; `flag`: the key of the flag bytes, one per member
+    or one per word"""
+    centroids, members, roots = _fr(centroids), _fr(members), _fr(roots)
+    K, dim, n_c = centroids.shape[0], centroids.shape[1], members.shape[0]
+    assert members.shape[1] == dim and roots.shape == (K + 1, 4)
+    cells, lk, n_in = _u64(), _u64(), _u64()
+    ahead = ([] if metric is None else [METRICS[metric]]) + [ctypes.c_uint32(P), ctypes.c_uint32(L)]
+    check(size(*ahead, _sz(K), _sz(n_c), _sz(dim), ctypes.byref(cells), ctypes.byref(lk), ctypes.byref(n_in)))
+    stream = np.zeros((cells.value, 4), dtype=np.uint64)
+    lookup = np.zeros((lk.value, 4), dtype=np.uint64)
+    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
+    flags, pub = np.zeros(n_c if per_member else dim, dtype=np.uint8), np.zeros((2, 4), dtype=np.uint64)
+    check(call(*ahead, _p(centroids), _p(members), _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(dim), _p(stream), _p(lookup),
+               _p(sel) if selectors else None, _p(flags), _p(pub)))
+    return dict(stream=stream, lookup=lookup, **_split_flags(sel), n_in=n_in.value, **{flag: flags}, public=pub)
+
+
 def wit_ann_audit(metric, centroids, members, roots, cluster, P=48, L=13, selectors=False):
     """the audit of one cluster's routing (vdb_wit_ann_audit) on centroids (K, dim, 4), the members of cluster `cluster` (n_c, dim, 4) and
     roots (K + 1, 4): [centroids' root | cluster roots]: dict(stream, lookup, selectors, flags, n_in, routed (n_c,) uint8: member i's own
     centroid attains the minimum, public (2, 4): [index_root | c])"""
     lib = _lib.init()
-    centroids, members, roots = _fr(centroids), _fr(members), _fr(roots)
-    K, dim, n_c = centroids.shape[0], centroids.shape[1], members.shape[0]
-    assert members.shape[1] == dim and roots.shape == (K + 1, 4)
-    cells, lk, n_in = _u64(), _u64(), _u64()
-    m = METRICS[metric]
-    check(lib.vdb_wit_ann_audit_size(m, ctypes.c_uint32(P), ctypes.c_uint32(L), _sz(K), _sz(n_c), _sz(dim), ctypes.byref(cells), ctypes.byref(lk),
-                                     ctypes.byref(n_in)))
-    stream = np.zeros((cells.value, 4), dtype=np.uint64)
-    lookup = np.zeros((lk.value, 4), dtype=np.uint64)
-    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
-    routed, pub = np.zeros(n_c, dtype=np.uint8), np.zeros((2, 4), dtype=np.uint64)
-    check(lib.vdb_wit_ann_audit(m, ctypes.c_uint32(P), ctypes.c_uint32(L), _p(centroids), _p(members), _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(dim),
-                                _p(stream), _p(lookup), _p(sel) if selectors else None, _p(routed), _p(pub)))
-    return dict(stream=stream, lookup=lookup, **_split_flags(sel), n_in=n_in.value, routed=routed, public=pub)
+    return _wit_ann_cluster(lib.vdb_wit_ann_audit_size, lib.vdb_wit_ann_audit, metric, centroids, members, roots, cluster, P, L, selectors, "routed", True)
 
 
 def wit_ann_mean(centroids, members, roots, cluster, P=48, L=13, selectors=False):
@@ -569,19 +575,7 @@ def wit_ann_mean(centroids, members, roots, cluster, P=48, L=13, selectors=False
     (K + 1, 4): [centroids' root | cluster roots]: dict(stream, lookup, selectors, flags, n_in, mean_ok (dim,) uint8: word j of centroid
     `cluster` is qdiv(sum of the members' words j, quantization(n_c)), public (2, 4): [index_root | c])"""
     lib = _lib.init()
-    centroids, members, roots = _fr(centroids), _fr(members), _fr(roots)
-    K, dim, n_c = centroids.shape[0], centroids.shape[1], members.shape[0]
-    assert members.shape[1] == dim and roots.shape == (K + 1, 4)
-    cells, lk, n_in = _u64(), _u64(), _u64()
-    check(lib.vdb_wit_ann_mean_size(ctypes.c_uint32(P), ctypes.c_uint32(L), _sz(K), _sz(n_c), _sz(dim), ctypes.byref(cells), ctypes.byref(lk),
-                                    ctypes.byref(n_in)))
-    stream = np.zeros((cells.value, 4), dtype=np.uint64)
-    lookup = np.zeros((lk.value, 4), dtype=np.uint64)
-    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
-    ok, pub = np.zeros(dim, dtype=np.uint8), np.zeros((2, 4), dtype=np.uint64)
-    check(lib.vdb_wit_ann_mean(ctypes.c_uint32(P), ctypes.c_uint32(L), _p(centroids), _p(members), _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(dim),
-                               _p(stream), _p(lookup), _p(sel) if selectors else None, _p(ok), _p(pub)))
-    return dict(stream=stream, lookup=lookup, **_split_flags(sel), n_in=n_in.value, mean_ok=ok, public=pub)
+    return _wit_ann_cluster(lib.vdb_wit_ann_mean_size, lib.vdb_wit_ann_mean, None, centroids, members, roots, cluster, P, L, selectors, "mean_ok", False)
 
 
 def ann_cluster_means(grouped, offsets, P=48, L=13):

@@ -1611,30 +1611,77 @@ def build_ann_delete(K, m, dim, depth, fetch_flags, fetch_values, builder=None, 
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# The audit of one cluster's routing (include/vdb.h vdb_wit_ann_audit; pipeline.AnnAuditHotPath)
-def ann_audit_layout(metric, K, n_c, dim, P, L):
-    """where the blocks of the audit circuit start: the head's keys of _ann_frame_layout (c, centroids_root, roots, n_in, indicator, select,
-    sponge_old, sponge) and centroids, members: the assigned block I (`update`: its first cell, where the head ends); routed: block R,
-    per_member / per_member_l: cells and lookup cells of one member's sub-block, chain_off, pick_off: where its qmin chain and its
-    select_by_indicator start; merkle_c, merkle_m; total, total_l; units: nearest_units over the K centroids; zero_c: the centroids'
-    padding loads the zero cell"""
-    if n_c < 1 or dim < 1:
-        raise ValueError("at least one member and one word")
+# The cluster frame of the routing audit and the mean audit below, one circuit around a block of their own: A - D the frame's head, I
+# [centroids | members] assigned, the own block, MC and MM the two merkle_commitments; public [index_root | c]
+def _ann_cluster_layout(K, n_c, dim):
+    """the head's keys of _ann_frame_layout (c, centroids_root, roots, n_in, indicator, select, sponge_old, sponge; `update`: where the head
+    ends) and centroids, members: the assigned block I, the own block behind it; zero_c: the centroids' padding loads the zero cell"""
     head = _ann_frame_layout(K, merkle_leaf_layout(K + 1), 0)
     lay = {k: head[k] for k in ("c", "centroids_root", "roots", "n_in", "indicator", "sponge", "select", "sponge_old", "update")}
-    u = nearest_units(metric, K, dim, 1, P, L)
-    zero_c = (1 << (K - 1).bit_length()) > K
-    lay.update(units=u, zero_c=zero_c, centroids=lay["update"], members=lay["update"] + K * dim)
+    lay.update(zero_c=(1 << (K - 1).bit_length()) > K, centroids=lay["update"], members=lay["update"] + K * dim)
+    return lay
+
+
+def _ann_cluster_close(lay, K, n_c, dim, own_end):
+    """the two trees behind the audit's own block, which ends at `own_end`: merkle_c, merkle_m, total"""
+    lay["merkle_c"] = own_end
+    lay["merkle_m"] = lay["merkle_c"] + merkle_cells(K, dim)
+    lay["total"] = lay["merkle_m"] + merkle_cells(n_c, dim, lay["zero_c"])
+    return lay
+
+
+def ann_audit_instances(index_root, c):
+    """the public cells in make_public order: [index_root | c]"""
+    return [int(index_root), int(c)]
+
+
+ann_mean_instances = ann_audit_instances
+
+
+def _build_ann_cluster(lay, K, n_c, dim, fetch_flags, fetch_values, builder, place_own):
+    """The circuit of `lay` (an audit's layout over _ann_cluster_layout) in one map: the frame's head (_build_ann_head: the header
+    [c | centroids_root | cluster roots], idx_to_indicator(c, K), select_by_indicator(cluster roots, ind) -> picked, the sponge ->
+    index_root), [centroids | members] assigned, place_own(B, members (n_c, dim), centroids (K, dim), indicators) -> (pairs, its info
+    keys): the audit's own block, tied as B.tie(a, b) for every pair; merkle_commitment(centroids), tied to the header's centroids_root,
+    and merkle_commitment(members), tied to picked.  -> (CopyMap, public cells [index_root, c], dict(indicators, picked, the own keys,
+    centroids_root, members_root, index_root, layout))"""
+    B, inds, picked, index_root = _build_ann_head(lay, fetch_flags, fetch_values, builder)
+    if np.asarray(fetch_flags(lay["centroids"], lay["members"] + n_c * dim)).any():
+        raise ValueError("the assigned centroids and members carry no gate or constant flag")
+    cent = lay["centroids"] + np.arange(K * dim, dtype=np.int64).reshape(K, dim)
+    mem = lay["members"] + np.arange(n_c * dim, dtype=np.int64).reshape(n_c, dim)
+    pairs, own_info = place_own(B, mem, cent, inds)
+    for a, b in pairs:
+        B.tie(a, b)
+    croot, end = place_merkle(B, K, dim, lay["merkle_c"], lay["centroids"], fetch_flags, fetch_values)
+    assert end == lay["merkle_m"]
+    B.tie(croot, lay["centroids_root"])                      # ctx.constrain_equal(centroids_root, croot)
+    zero = lay["merkle_c"] + K * merkle_leaf_layout(dim)["leaf_cells"] if lay["zero_c"] else None
+    mroot, end = place_merkle(B, n_c, dim, lay["merkle_m"], lay["members"], fetch_flags, fetch_values, zero_cell=zero)
+    if end != lay["total"]:
+        raise ValueError("the trace does not end where the circuit does")
+    B.tie(mroot, picked)                                     # ctx.constrain_equal(picked, mroot)
+    info = dict(indicators=[int(i) for i in inds], picked=picked, **own_info, centroids_root=croot, members_root=mroot, index_root=index_root, layout=lay)
+    return B.finish(), ann_audit_instances(index_root, lay["c"]), info
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The audit of one cluster's routing (include/vdb.h vdb_wit_ann_audit; pipeline.AnnAuditHotPath)
+def ann_audit_layout(metric, K, n_c, dim, P, L):
+    """where the blocks of the audit circuit start: _ann_cluster_layout's keys; routed: block R, per_member / per_member_l: cells and
+    lookup cells of one member's sub-block, chain_off, pick_off: where its qmin chain and its select_by_indicator start; merkle_c,
+    merkle_m; total, total_l; units: nearest_units over the K centroids"""
+    if n_c < 1 or dim < 1:
+        raise ValueError("at least one member and one word")
+    lay = _ann_cluster_layout(K, n_c, dim)
+    u = lay["units"] = nearest_units(metric, K, dim, 1, P, L)
     lay["routed"] = lay["members"] + n_c * dim
     lay["chain_off"] = K * u["db"].n
     lay["pick_off"] = lay["chain_off"] + (K - 1) * u["qm"].n
     lay["per_member"] = lay["pick_off"] + u["sb"].n
     lay["per_member_l"] = K * u["db"].n_lk + (K - 1) * u["qm"].n_lk
-    lay["merkle_c"] = lay["routed"] + n_c * lay["per_member"]
-    lay["merkle_m"] = lay["merkle_c"] + merkle_cells(K, dim)
-    lay["total"] = lay["merkle_m"] + merkle_cells(n_c, dim, zero_c)
     lay["total_l"] = n_c * lay["per_member_l"]
-    return lay
+    return _ann_cluster_close(lay, K, n_c, dim, lay["routed"] + n_c * lay["per_member"])
 
 
 def place_routed(B, u, members, centroids, ind, base, lbase):
@@ -1665,38 +1712,17 @@ def place_routed(B, u, members, centroids, ind, base, lbase):
     return own, acc[:, K - 1].copy()
 
 
-def ann_audit_instances(index_root, c):
-    """the public cells in make_public order: [index_root | c]"""
-    return [int(index_root), int(c)]
-
-
 def build_ann_audit(metric, K, n_c, dim, P, L, fetch_flags, fetch_values, builder=None):
-    """The audit of one cluster's routing in one circuit (pipeline.AnnAuditHotPath): the frame's head (_build_ann_head: the header
-    [c | centroids_root | cluster roots], idx_to_indicator(c, K), select_by_indicator(cluster roots, ind) -> picked, the sponge ->
-    index_root), [centroids | members] assigned, the routed block (place_routed) with every own_i TIED to m_i — centroid c attains the
-    minimum of member i's K distances — then merkle_commitment(centroids), tied to the header's centroids_root, and
-    merkle_commitment(members), tied to picked.  fetch_flags / fetch_values: as place_merkle; `builder`: as build_kmeans.
+    """The audit of one cluster's routing in one circuit (pipeline.AnnAuditHotPath): the cluster frame (_build_ann_cluster) around the
+    routed block (place_routed) with every own_i TIED to m_i — centroid c attains the minimum of member i's K distances.
+    fetch_flags / fetch_values: as place_merkle; `builder`: as build_kmeans.
     -> (CopyMap, public cells [index_root, c], dict(indicators, picked, own, m, centroids_root, members_root, index_root, layout))"""
     lay = ann_audit_layout(metric, K, n_c, dim, P, L)
-    B, inds, picked, index_root = _build_ann_head(lay, fetch_flags, fetch_values, builder)
-    if np.asarray(fetch_flags(lay["centroids"], lay["routed"])).any():
-        raise ValueError("the assigned centroids and members carry no gate or constant flag")
-    cent = lay["centroids"] + np.arange(K * dim, dtype=np.int64).reshape(K, dim)
-    mem = lay["members"] + np.arange(n_c * dim, dtype=np.int64).reshape(n_c, dim)
-    own, m = place_routed(B, lay["units"], mem, cent, inds, lay["routed"], 0)
-    for o, x in zip(own.tolist(), m.tolist()):
-        B.tie(o, x)                                          # ctx.constrain_equal(m_i, own_i)
-    croot, end = place_merkle(B, K, dim, lay["merkle_c"], lay["centroids"], fetch_flags, fetch_values)
-    assert end == lay["merkle_m"]
-    B.tie(croot, lay["centroids_root"])                      # ctx.constrain_equal(centroids_root, croot)
-    zero = lay["merkle_c"] + K * merkle_leaf_layout(dim)["leaf_cells"] if lay["zero_c"] else None
-    mroot, end = place_merkle(B, n_c, dim, lay["merkle_m"], lay["members"], fetch_flags, fetch_values, zero_cell=zero)
-    if end != lay["total"]:
-        raise ValueError("the trace does not end where the circuit does")
-    B.tie(mroot, picked)                                     # ctx.constrain_equal(picked, mroot)
-    info = dict(indicators=[int(i) for i in inds], picked=picked, own=[int(o) for o in own], m=[int(x) for x in m], centroids_root=croot,
-                members_root=mroot, index_root=index_root, layout=lay)
-    return B.finish(), ann_audit_instances(index_root, lay["c"]), info
+
+    def own_block(B, mem, cent, inds):
+        own, m = (x.tolist() for x in place_routed(B, lay["units"], mem, cent, inds, lay["routed"], 0))
+        return zip(own, m), dict(own=own, m=m)               # ctx.constrain_equal(m_i, own_i)
+    return _build_ann_cluster(lay, K, n_c, dim, fetch_flags, fetch_values, builder, own_block)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -1713,28 +1739,21 @@ def mean_units(K, P, L):
 
 
 def ann_mean_layout(K, n_c, dim, P, L):
-    """where the blocks of the mean audit circuit start: the head's keys of _ann_frame_layout (c, centroids_root, roots, n_in, indicator,
-    select, sponge_old, sponge) and centroids, members: the assigned block I (`update`: its first cell, where the head ends); own: block
-    S (dim select_by_indicator over K cells); len: the constant quantization(n_c), block M's first cell; chain: the qadd cells; div: the
-    dim qdiv blocks; merkle_c, merkle_m; total, total_l; units: mean_units; zero_c: the centroids' padding loads the zero cell"""
+    """where the blocks of the mean audit circuit start: _ann_cluster_layout's keys; own: block S (dim select_by_indicator over K
+    cells); len: the constant quantization(n_c), block M's first cell; chain: the qadd cells; div: the dim qdiv blocks; merkle_c,
+    merkle_m; total, total_l; units: mean_units"""
     if n_c < 1 or dim < 1:
         raise ValueError("at least one member and one word")
     if n_c >= 1 << P:
         raise ValueError("quantization(n_c) must stay below qdiv's divisor bound 2^(2P)")
-    head = _ann_frame_layout(K, merkle_leaf_layout(K + 1), 0)
-    lay = {k: head[k] for k in ("c", "centroids_root", "roots", "n_in", "indicator", "sponge", "select", "sponge_old", "update")}
-    u = mean_units(K, P, L)
-    zero_c = (1 << (K - 1).bit_length()) > K
-    lay.update(units=u, zero_c=zero_c, centroids=lay["update"], members=lay["update"] + K * dim)
+    lay = _ann_cluster_layout(K, n_c, dim)
+    u = lay["units"] = mean_units(K, P, L)
     lay["own"] = lay["members"] + n_c * dim
     lay["len"] = lay["own"] + dim * u["sb"].n
     lay["chain"] = lay["len"] + 1
     lay["div"] = lay["chain"] + (n_c - 1) * dim * u["add"].n
-    lay["merkle_c"] = lay["div"] + dim * u["qd"].n
-    lay["merkle_m"] = lay["merkle_c"] + merkle_cells(K, dim)
-    lay["total"] = lay["merkle_m"] + merkle_cells(n_c, dim, zero_c)
     lay["total_l"] = dim * u["qd"].n_lk
-    return lay
+    return _ann_cluster_close(lay, K, n_c, dim, lay["div"] + dim * u["qd"].n)
 
 
 def place_mean(B, u, members, centroids, ind, n_c_quantized, own_base, len_cell, lbase):
@@ -1764,38 +1783,17 @@ def place_mean(B, u, members, centroids, ind, n_c_quantized, own_base, len_cell,
     return own, mean
 
 
-def ann_mean_instances(index_root, c):
-    """the public cells in make_public order: [index_root | c]"""
-    return [int(index_root), int(c)]
-
-
 def build_ann_mean(K, n_c, dim, P, L, fetch_flags, fetch_values, builder=None):
-    """The mean audit of one cluster in one circuit (pipeline.AnnMeanHotPath): the frame's head (_build_ann_head: the header
-    [c | centroids_root | cluster roots], idx_to_indicator(c, K), select_by_indicator(cluster roots, ind) -> picked, the sponge ->
-    index_root), [centroids | members] assigned, blocks S and M (place_mean) with every quotient mean_j TIED to own_j — word j of centroid
-    c is the mean of the members' words j — then merkle_commitment(centroids), tied to the header's centroids_root, and
-    merkle_commitment(members), tied to picked.  fetch_flags / fetch_values: as place_merkle; `builder`: as build_kmeans.
+    """The mean audit of one cluster in one circuit (pipeline.AnnMeanHotPath): the cluster frame (_build_ann_cluster) around blocks S and
+    M (place_mean) with every quotient mean_j TIED to own_j — word j of centroid c is the mean of the members' words j.
+    fetch_flags / fetch_values: as place_merkle; `builder`: as build_kmeans.
     -> (CopyMap, public cells [index_root, c], dict(indicators, picked, own, mean, len, centroids_root, members_root, index_root, layout))"""
     lay = ann_mean_layout(K, n_c, dim, P, L)
-    B, inds, picked, index_root = _build_ann_head(lay, fetch_flags, fetch_values, builder)
-    if np.asarray(fetch_flags(lay["centroids"], lay["own"])).any():
-        raise ValueError("the assigned centroids and members carry no gate or constant flag")
-    cent = lay["centroids"] + np.arange(K * dim, dtype=np.int64).reshape(K, dim)
-    mem = lay["members"] + np.arange(n_c * dim, dtype=np.int64).reshape(n_c, dim)
-    own, mean = place_mean(B, lay["units"], mem, cent, inds, n_c << P, lay["own"], lay["len"], 0)
-    for o, x in zip(own.tolist(), mean.tolist()):
-        B.tie(x, o)                                          # ctx.constrain_equal(own_j, mean_j)
-    croot, end = place_merkle(B, K, dim, lay["merkle_c"], lay["centroids"], fetch_flags, fetch_values)
-    assert end == lay["merkle_m"]
-    B.tie(croot, lay["centroids_root"])                      # ctx.constrain_equal(centroids_root, croot)
-    zero = lay["merkle_c"] + K * merkle_leaf_layout(dim)["leaf_cells"] if lay["zero_c"] else None
-    mroot, end = place_merkle(B, n_c, dim, lay["merkle_m"], lay["members"], fetch_flags, fetch_values, zero_cell=zero)
-    if end != lay["total"]:
-        raise ValueError("the trace does not end where the circuit does")
-    B.tie(mroot, picked)                                     # ctx.constrain_equal(picked, mroot)
-    info = dict(indicators=[int(i) for i in inds], picked=picked, own=[int(o) for o in own], mean=[int(x) for x in mean], len=lay["len"],
-                centroids_root=croot, members_root=mroot, index_root=index_root, layout=lay)
-    return B.finish(), ann_mean_instances(index_root, lay["c"]), info
+
+    def own_block(B, mem, cent, inds):
+        own, mean = (x.tolist() for x in place_mean(B, lay["units"], mem, cent, inds, n_c << P, lay["own"], lay["len"], 0))
+        return zip(mean, own), dict(own=own, mean=mean, len=lay["len"])    # ctx.constrain_equal(own_j, mean_j)
+    return _build_ann_cluster(lay, K, n_c, dim, fetch_flags, fetch_values, builder, own_block)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -19,19 +19,25 @@ static inline void tree_shape(uint64_t n, uint64_t* lp, uint32_t* depth) {
   for (*lp = 1, *depth = 0; *lp < n; *lp <<= 1) ++*depth;
 }
 
-// first stream cell of every block of a circuit against the index root over K clusters (the update's and the delete's): A the header
-// [c | centroids_root | cluster roots], B the indicators, C select_by_indicator, D the old sponge, E the update block, S the delete's
-// proof that the dropped half is empty (b_shr; no cells in the update and when the tree keeps its size), F the K selects, G the new sponge
+// The head of every circuit against the index root over K clusters, first stream cell of each block: A the header [c | centroids_root |
+// cluster roots] (n_in cells from 0), B the indicators, C select_by_indicator, D the sponge over the header's roots; `end`: behind D
+struct AnnHead {
+  uint64_t n_in, b_ind, b_sel, b_old, end;
+};
+static inline AnnHead ann_head(uint64_t K, uint64_t sponge_cells) {
+  const uint64_t b_ind = K + 2, b_sel = b_ind + 8 + 12 * (K - 1), b_old = b_sel + 1 + 3 * K;
+  return AnnHead{K + 2, b_ind, b_sel, b_old, b_old + sponge_cells};
+}
+// a batch against the index root (the update's and the delete's), behind the head: E the update block, S the delete's proof that the
+// dropped half is empty (b_shr; no cells in the update and when the tree keeps its size), F the K selects, G the new sponge
 struct AnnuBlocks {
-  uint64_t n_in, b_ind, b_sel, b_old, b_upd, b_shr, b_new, b_root, total;
+  AnnHead h;
+  uint64_t b_upd, b_shr, b_new, b_root, total;
 };
 static inline AnnuBlocks annu_blocks(uint64_t K, uint64_t sponge_cells, uint64_t update_cells, uint64_t shrink_cells = 0) {
   AnnuBlocks o;
-  o.n_in = K + 2;
-  o.b_ind = o.n_in;
-  o.b_sel = o.b_ind + 8 + 12 * (K - 1);
-  o.b_old = o.b_sel + 1 + 3 * K;
-  o.b_upd = o.b_old + sponge_cells;
+  o.h = ann_head(K, sponge_cells);
+  o.b_upd = o.h.end;
   o.b_shr = o.b_upd + update_cells;
   o.b_new = o.b_shr + shrink_cells;
   o.b_root = o.b_new + 8 * K;
@@ -41,59 +47,55 @@ static inline AnnuBlocks annu_blocks(uint64_t K, uint64_t sponge_cells, uint64_t
 // where lane j's indicator starts inside block B: is_zero (8 cells) for j = 0, then is_equal (12 cells) each
 ANNU_HD static inline uint64_t annu_indicator_off(uint64_t j) { return j ? 8 + 12 * (j - 1) : 0; }
 
+// an audit of one cluster (the routing audit and the mean audit), behind the head: I the assigned [centroids K x dim | members n_c x dim],
+// the audit's own blocks (own_cells of them from b_own), MC and MM the merkle_commitments of the centroids and of the members
+struct AnnCluster {
+  AnnHead h;
+  uint64_t b_in, b_own, b_mc, b_mm, total;
+};
+static inline AnnCluster ann_cluster(const AnnHead& h, uint64_t K, uint64_t n_c, uint64_t dim, uint64_t own_cells, uint64_t mc_cells, uint64_t mm_cells) {
+  const uint64_t b_own = h.end + (K + n_c) * dim, b_mc = b_own + own_cells, b_mm = b_mc + mc_cells;
+  return AnnCluster{h, h.end, b_own, b_mc, b_mm, b_mm + mm_cells};
+}
+
 // ------------------------------------------------------------------ the audit of one cluster's routing (include/vdb.h vdb_wit_ann_audit)
-// first stream cell of every block: A - D the frame's head as above (b_ind, b_sel, b_old), I the assigned [centroids K x dim | members
-// n_c x dim], R the routed block, one sub-block of per_member cells per member: K distances, the K - 1 qmin of the chain, then
-// select_by_indicator over the K distances (1 + 3 K cells, at pick_off inside the sub-block); MC and MM the two merkle_commitments.
-// Lookup cells are R's alone, per_member_l per member: the distance runs, then the qmin runs.
+// its own block R in the cluster frame f: one sub-block of per_member cells per member from f.b_own on: K distances, the K - 1 qmin of
+// the chain (at chain_off), then select_by_indicator over the K distances (1 + 3 K cells, at pick_off inside the sub-block).
+// Lookup cells are R's alone, per_member_l per member: the distance runs, then the qmin runs (at chain_loff).
 struct AnnaBlocks {
-  uint64_t n_in, b_ind, b_sel, b_old, b_in, b_r, b_mc, b_mm, total;
+  AnnCluster f;
   uint64_t per_member, per_member_l, chain_off, chain_loff, pick_off, total_l;
 };
 static inline AnnaBlocks anna_blocks(uint64_t K, uint64_t n_c, uint64_t dim, uint64_t sponge_cells, uint64_t dist_cells, uint64_t dist_lk,
                                      uint64_t qmin_cells, uint64_t qmin_lk, uint64_t mc_cells, uint64_t mm_cells) {
   AnnaBlocks o;
-  o.n_in = K + 2;
-  o.b_ind = o.n_in;
-  o.b_sel = o.b_ind + 8 + 12 * (K - 1);
-  o.b_old = o.b_sel + 1 + 3 * K;
-  o.b_in = o.b_old + sponge_cells;
-  o.b_r = o.b_in + (K + n_c) * dim;
   o.chain_off = K * dist_cells;
   o.chain_loff = K * dist_lk;
   o.pick_off = o.chain_off + (K - 1) * qmin_cells;
   o.per_member = o.pick_off + 1 + 3 * K;
   o.per_member_l = o.chain_loff + (K - 1) * qmin_lk;
-  o.b_mc = o.b_r + n_c * o.per_member;
-  o.b_mm = o.b_mc + mc_cells;
-  o.total = o.b_mm + mm_cells;
   o.total_l = n_c * o.per_member_l;
+  o.f = ann_cluster(ann_head(K, sponge_cells), K, n_c, dim, n_c * o.per_member, mc_cells, mm_cells);
   return o;
 }
 
 // ------------------------------------------------------------------ the mean audit of one cluster (include/vdb.h vdb_wit_ann_mean)
-// first stream cell of every block: A - D the frame's head as above (b_ind, b_sel, b_old), I the assigned [centroids K x dim | members
-// n_c x dim], S select_by_indicator(centroids, ind) word by word (1 + 3 K cells each) -> own, M: the constant len = quantization(n_c) at
-// b_m, the qadd chain from b_chain on (4 cells per member after the first and word, member-major), the dim qdiv blocks from b_div on; MC
-// and MM the two merkle_commitments.  Lookup cells are the qdiv blocks' alone, word j's from j * qdiv_lk on.
+// its own blocks in the cluster frame f, first stream cell of each: S select_by_indicator(centroids, ind) word by word (1 + 3 K cells each,
+// from b_s = f.b_own) -> own, M: the constant len = quantization(n_c) at b_m, the qadd chain from b_chain on (4 cells per member after the
+// first and word, member-major), the dim qdiv blocks from b_div on.  Lookup cells are the qdiv blocks' alone, word j's from j * qdiv_lk on.
 struct AnnmBlocks {
-  uint64_t n_in, b_ind, b_sel, b_old, b_in, b_s, b_m, b_chain, b_div, b_mc, b_mm, total, total_l;
+  AnnCluster f;
+  uint64_t b_s, b_m, b_chain, b_div, total_l;
 };
 static inline AnnmBlocks annm_blocks(uint64_t K, uint64_t n_c, uint64_t dim, uint64_t sponge_cells, uint64_t qdiv_cells, uint64_t qdiv_lk,
                                      uint64_t mc_cells, uint64_t mm_cells) {
   AnnmBlocks o;
-  o.n_in = K + 2;
-  o.b_ind = o.n_in;
-  o.b_sel = o.b_ind + 8 + 12 * (K - 1);
-  o.b_old = o.b_sel + 1 + 3 * K;
-  o.b_in = o.b_old + sponge_cells;
-  o.b_s = o.b_in + (K + n_c) * dim;
-  o.b_m = o.b_s + dim * (1 + 3 * K);
+  const uint64_t s_cells = dim * (1 + 3 * K), chain_cells = (n_c - 1) * dim * 4;
+  o.f = ann_cluster(ann_head(K, sponge_cells), K, n_c, dim, s_cells + 1 + chain_cells + dim * qdiv_cells, mc_cells, mm_cells);
+  o.b_s = o.f.b_own;
+  o.b_m = o.b_s + s_cells;
   o.b_chain = o.b_m + 1;
-  o.b_div = o.b_chain + (n_c - 1) * dim * 4;
-  o.b_mc = o.b_div + dim * qdiv_cells;
-  o.b_mm = o.b_mc + mc_cells;
-  o.total = o.b_mm + mm_cells;
+  o.b_div = o.b_chain + chain_cells;
   o.total_l = dim * qdiv_lk;
   return o;
 }

@@ -1659,6 +1659,12 @@ static void mk_layout(size_t n, size_t dim, int zero_cached, MkLayout* o) {
   o->zero_cell = (lp > n && !zero_cached) ? 1 : 0;
   o->total = o->leaves + o->zero_cell + (lp - 1) * (uint64_t)NODE_CELLS;
 }
+// the centroids' tree, then the members' tree behind it in the same context: Context::load_zero caches its cell, so where the centroids'
+// padding has loaded it the members' padding does not load it again
+static void mk_layout_pair(size_t K, size_t n_c, size_t dim, MkLayout* mc, MkLayout* mm) {
+  mk_layout(K, dim, 0, mc);
+  mk_layout(n_c, dim, (int)mc->zero_cell, mm);
+}
 // merkle_commitment's cells from stream cell `base` on (the caller has published the call's context).  `resident`: the tree's digests
 // where they already lie on the device (vdb_merkle_tree_build_dev's layout, only read) — then only the leaves' sponge states are computed,
 // and the launch count does not depend on n (the zero cell and the tree trace are launched where they have nothing to store, too);
@@ -1930,8 +1936,7 @@ static int ann_layout(FpEntry* fp, int metric, size_t K, size_t n_c, size_t dim,
   TRY(nv_fits(1, K, dim, 1, o->nc));
   TRY(nv_layout(fp, metric, n_c, dim, 1, &o->dl, &o->nm));
   TRY(nv_fits(1, n_c, dim, 1, o->nm));
-  mk_layout(K, dim, 0, &o->mc);
-  mk_layout(n_c, dim, (int)o->mc.zero_cell, &o->mm);   // Context::load_zero caches its cell: the centroids' padding has loaded it
+  mk_layout_pair(K, n_c, dim, &o->mc, &o->mm);
   mk_layout(1, K + 1, 1, &o->mw);
   o->n_in = dim + K * dim + n_c * dim + K;
   o->b_nc = o->n_in;
@@ -2041,22 +2046,27 @@ __global__ __launch_bounds__(256) void k_annu_public(const u256* __restrict__ up
   if (i >= 3 * m + 3) return;
   pub[i] = i == 0 ? iroot[0] : i == 1 ? hdr[0] : i == 3 * m + 2 ? iroot[1] : upub[i - 1];
 }
-// The refusals and the blocks every circuit against the index root shares.  inner(&shrink_cells) lays out the circuit's own blocks
-// into *ml, with its own refusals, which come between the frame's: after the arguments', before the cell limit.
+// The refusals and the blocks every circuit against the index root shares.  inner(&update_cells, &shrink_cells) lays out the circuit's
+// own blocks, with its own refusals, which come between the frame's: after the arguments', before the cell limit.  An audit has no block
+// between the head and F: both counts stay 0, and the limit of its own cells is its own.
 template <class Inner>
-static int ann_frame_layout(size_t K, size_t cluster, size_t n_c, AnnuLayout* o, MkuLayout* ml, Inner inner) {
+static int ann_frame_layout(size_t K, size_t cluster, size_t n_c, MkLayout* mw, AnnuBlocks* b, Inner inner) {
   VDB_ARG(K > 0 && K <= VDB_ANN_MAX_CLUSTERS, "K = 0 or K above VDB_ANN_MAX_CLUSTERS");
   VDB_ARG(cluster < K, "cluster >= K");
   VDB_ARG(n_c <= VDB_ANN_MAX_VECTORS, "cluster larger than VDB_ANN_MAX_VECTORS");
-  uint64_t shrink_cells = 0;
-  TRY(inner(&shrink_cells));
-  mk_layout(1, K + 1, 1, &o->mw);
-  o->b = annu_blocks(K, o->mw.total, ml->total, shrink_cells);
-  VDB_ARG(o->b.total <= ((uint64_t)1 << 34), "more than VDB_MERKLE_UPDATE_MAX_CELLS cells in one call");
+  uint64_t update_cells = 0, shrink_cells = 0;
+  TRY(inner(&update_cells, &shrink_cells));
+  mk_layout(1, K + 1, 1, mw);
+  *b = annu_blocks(K, mw->total, update_cells, shrink_cells);
+  VDB_ARG(b->total <= ((uint64_t)1 << 34), "more than VDB_MERKLE_UPDATE_MAX_CELLS cells in one call");
   return VDB_OK;
 }
 static int annu_layout(size_t K, size_t cluster, size_t n_c, size_t dim, size_t m, unsigned grow, AnnuLayout* o, MkuLayout* ml) {
-  return ann_frame_layout(K, cluster, n_c, o, ml, [&](uint64_t*) { return mku_layout(n_c, dim, m, nullptr, grow, ml, nullptr, nullptr, nullptr); });
+  return ann_frame_layout(K, cluster, n_c, &o->mw, &o->b, [&](uint64_t* update_cells, uint64_t*) -> int {
+    TRY(mku_layout(n_c, dim, m, nullptr, grow, ml, nullptr, nullptr, nullptr));
+    *update_cells = ml->total;
+    return VDB_OK;
+  });
 }
 // The frame of one call: its work space in scratch slot 7, in u256: [c | words_old K + 1] (the header as it is assigned) | ind K |
 // picked | words_new K + 1 | index_root_old, index_root_new | the inner block's public values n_upub | n_extra for the caller | the
@@ -2066,12 +2076,13 @@ struct AnnFrame {
   Streams st;
   FpEntry* fp;
   const PoseidonSpec* sp;
-  const AnnuLayout* a;
+  const MkLayout* mw;   // the sponge over K + 1 words, blocks D and G
   uint32_t K;
   u256 *hdr, *ind, *picked, *words_new, *iroot, *upub, *extra, *st_old, *st_new;
-  int open(Streams streams, const u256* roots, size_t K_, size_t cluster, const AnnuLayout& lay, size_t n_upub, size_t n_extra) {
-    st = streams, a = &lay, K = (uint32_t)K_;
-    const size_t n_st = (size_t)lay.mw.nperm * PSD_T;
+  // h: where the head's blocks start; total: the cells of the whole circuit
+  int open(Streams streams, const u256* roots, size_t K_, size_t cluster, const AnnHead& h, const MkLayout& mw_, uint64_t total, size_t n_upub, size_t n_extra) {
+    st = streams, mw = &mw_, K = (uint32_t)K_;
+    const size_t n_st = (size_t)mw->nperm * PSD_T;
     hdr = (u256*)scratch_get(7, (2 * (K_ + 2) + K_ + 1 + 2 + n_upub + n_extra + 2 * n_st + 8) * sizeof(u256));
     if (!hdr) return VDB_ERR_OOM;
     ind = hdr + K_ + 2;
@@ -2082,24 +2093,24 @@ struct AnnFrame {
     extra = upub + n_upub;
     st_old = extra + n_extra;
     st_new = st_old + n_st;
-    TRY(inv_list_attach(st, lay.b.total));
+    TRY(inv_list_attach(st, total));
     TRY(mk_begin(st, &fp, &sp));
     const uint32_t cu = (uint32_t)cluster;
     VDB_LAUNCH(k_annu_header, dim3((unsigned)((K_ + 2 + 255) / 256)), dim3(256), st, 0, cu, roots, K, hdr);
-    VDB_LAUNCH(k_annu_indicator, dim3((unsigned)((K_ + 63) / 64)), dim3(64), st, fp->dev, lay.b.b_ind, cu, K, ind);
-    const NvMap sm{lay.b.b_sel, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, K, 1u, 1u};
+    VDB_LAUNCH(k_annu_indicator, dim3((unsigned)((K_ + 63) / 64)), dim3(64), st, fp->dev, h.b_ind, cu, K, ind);
+    const NvMap sm{h.b_sel, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, K, 1u, 1u};
     VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), st, fp->dev, sm, 1u, hdr + 2, ind, picked);
-    return sponge(hdr + 1, lay.b.b_old, st_old, iroot);
+    return sponge(hdr + 1, h.b_old, st_old, iroot);
   }
-  int close(const u256* new_root) {
-    VDB_LAUNCH(k_annu_new_roots, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, a->b.b_new, K, new_root, hdr + 1, ind, words_new);
-    return sponge(words_new, a->b.b_root, st_new, iroot + 1);
+  int close(const AnnuBlocks& b, const u256* new_root) {
+    VDB_LAUNCH(k_annu_new_roots, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, b.b_new, K, new_root, hdr + 1, ind, words_new);
+    return sponge(words_new, b.b_root, st_new, iroot + 1);
   }
   // blocks D and G: the sponge over K + 1 words at `base`, its digest to *root
   int sponge(const u256* words, uint64_t base, u256* states, u256* root) {
-    const uint32_t nperm = a->mw.nperm;
+    const uint32_t nperm = mw->nperm;
     TRY(mk_leaf_states(sp, words, 1u, K + 1, nperm, states, root, nullptr));
-    VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((nperm + 63) / 64)), dim3(64), st, fp->dev, sp, words, 1u, K + 1, nperm, base, a->mw.leaf_cells, states,
+    VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((nperm + 63) / 64)), dim3(64), st, fp->dev, sp, words, 1u, K + 1, nperm, base, mw->leaf_cells, states,
                nullptr);
     return VDB_OK;
   }
@@ -2115,9 +2126,9 @@ int wit_ann_update_dev(u256* levels, const u256* roots, size_t K, size_t cluster
   TRY(mku_plan(n_c, dim, grow, new_vectors, indices, nullptr, m, &pl));
   VDB_ARG(annu_track_fill(indices, m, n_c, pl.lp, nullptr, nullptr) == 0, "a write above the cluster's fill at its turn: the members of a cluster stay dense (append at the fill, or replace below it)");
   AnnFrame f;
-  TRY(f.open(st, roots, K, cluster, a, 3 * m + 2, 0));
+  TRY(f.open(st, roots, K, cluster, a.b.h, a.mw, a.b.total, 3 * m + 2, 0));
   TRY(mku_emit(f.fp, f.sp, pl, levels, dim, new_vectors, f.st, a.b.b_upd, f.upub));
-  TRY(f.close(f.upub + 3 * m + 1));
+  TRY(f.close(a.b, f.upub + 3 * m + 1));
   VDB_LAUNCH(k_annu_public, dim3((unsigned)((3 * m + 3 + 255) / 256)), dim3(256), f.upub, f.hdr, f.iroot, (uint32_t)m, pub);
   return inv_list_fixup(f.st);
 }
@@ -2162,7 +2173,7 @@ __global__ __launch_bounds__(256) void k_annd_public(const u256* __restrict__ up
 }
 // the host side of a delete batch, before anything is launched: the expansion to 2 m path updates and every refusal
 static int annd_layout(size_t K, size_t cluster, size_t n_c, size_t dim, const uint64_t* slots, size_t m, AnnuLayout* o, MkuLayout* ml, AnndPlan* dp) {
-  return ann_frame_layout(K, cluster, n_c, o, ml, [&](uint64_t* shrink_cells) -> int {
+  return ann_frame_layout(K, cluster, n_c, &o->mw, &o->b, [&](uint64_t* update_cells, uint64_t* shrink_cells) -> int {
     VDB_ARG(m > 0 && m <= MKU_MAX_UPDATES / 2, "a batch holds 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES / 2 deletes (two path updates each)");
     VDB_ARG(m < n_c, "the batch would empty the cluster");
     static thread_local std::vector<uint64_t> none;
@@ -2174,7 +2185,9 @@ static int annd_layout(size_t K, size_t cluster, size_t n_c, size_t dim, const u
     VDB_ARG(rc != 3, "a slot at or above the cluster's fill at its turn (every delete lowers the fill by one)");
     VDB_ARG(rc == 0, "a batch holds at least one delete and leaves at least one member");
     *shrink_cells = annd_shrink_cells(dp->depth, dp->shrink, NODE_CELLS);
-    return mku_layout(n_c, dim, 2 * m, dp->kinds.data(), 0, ml, nullptr, nullptr, nullptr, true);
+    TRY(mku_layout(n_c, dim, 2 * m, dp->kinds.data(), 0, ml, nullptr, nullptr, nullptr, true));
+    *update_cells = ml->total;
+    return VDB_OK;
   });
 }
 // roots: [centroids_root | the K cluster roots] of the index before the batch; levels: cluster c's tree over its n_c members, left in
@@ -2192,26 +2205,67 @@ int wit_ann_delete_dev(u256* levels, const u256* roots, size_t K, size_t cluster
   if (dp.shrink) TRY(poseidon_empty_subtrees_dev(&empty));
   const size_t n_up = 6 * m + 2;
   AnnFrame f;
-  TRY(f.open(st, roots, K, cluster, a, n_up, 1));
+  TRY(f.open(st, roots, K, cluster, a.b.h, a.mw, a.b.total, n_up, 1));
   u256* s0 = f.extra;
   TRY(mku_emit(f.fp, f.sp, pl, levels, dim, nullptr, f.st, a.b.b_upd, f.upub));
   if (dp.shrink)  // S_i are the halved tree's top digests as the write-back left them
     VDB_LAUNCH(k_annd_shrink_trace, dim3((unsigned)((2 * (dp.depth - 1 + dp.shrink) + 63) / 64)), dim3(64), f.st, f.fp->dev, f.sp, a.b.b_shr, dp.depth, dp.shrink,
                pl.lp, levels, empty, s0);
-  TRY(f.close(dp.shrink ? s0 : f.upub + n_up - 1));
+  TRY(f.close(a.b, dp.shrink ? s0 : f.upub + n_up - 1));
   VDB_LAUNCH(k_annd_public, dim3((unsigned)((4 * m + 3 + 255) / 256)), dim3(256), f.upub, f.hdr, f.iroot, (uint32_t)m, pub);
   return inv_list_fixup(f.st);
 }
 
+// ------------------------------------------------------------------ the cluster frame of the routing audit and the mean audit below: blocks
+// A - D are the frame's head; I [centroids | members] assigned; the audit's own blocks; MC, MM the two merkle_commitments, whose roots the
+// map ties to the header's centroids_root and to picked.  pub: [index_root | c].  Nothing after the head is AnnFrame's: close() is not called.
+struct AnnClusterLayout { MkLayout mw, mc, mm; };
+// the refusals, in the frame's order: the arguments', own() with the audit's, the frame's cell limit; the audit's own limit comes behind them
+template <class Own>
+static int ann_cluster_layout(size_t K, size_t cluster, size_t n_c, size_t dim, AnnClusterLayout* t, Own own) {
+  AnnuBlocks frame;   // F and G over no block at all: asked for the cell limit alone
+  TRY(ann_frame_layout(K, cluster, n_c, &t->mw, &frame, [&](uint64_t*, uint64_t*) -> int {
+    VDB_ARG(n_c > 0 && dim > 0 && dim <= ((size_t)1 << 20), "empty cluster, dim = 0 or dim above 2^20");
+    return own();
+  }));
+  mk_layout_pair(K, n_c, dim, &t->mc, &t->mm);
+  return VDB_OK;
+}
+// One call's frame: open() emits the head and block I, the audit emits its own blocks through f.st, finish() emits MC and MM and the
+// public values.  levels_c / levels_m: the two trees where they are resident (forest segments K and c), or both null.
+struct AnnClusterFrame {
+  AnnFrame f;
+  FpEntry* fp;   // the tables of (P, L); f.fp is the head's
+  const AnnClusterLayout* t;
+  const AnnCluster* b;
+  const u256 *centroids, *members;
+  size_t K, n_c, dim;
+  int open(Streams st, FpEntry* fp_, const u256* centroids_, const u256* members_, const u256* roots, size_t K_, size_t cluster, size_t n_c_, size_t dim_,
+           const AnnClusterLayout& lay, const AnnCluster& blocks, size_t n_extra) {
+    fp = fp_, t = &lay, b = &blocks, centroids = centroids_, members = members_, K = K_, n_c = n_c_, dim = dim_;
+    TRY(f.open(st, roots, K, cluster, b->h, t->mw, b->total, 0, n_extra));
+    TRY(set_winv(f.st, fp->dev));   // the head's gadgets are GateChip's alone; the audit's own read the tables of (P, L)
+    VDB_LAUNCH(k_mku_inputs, dim3((unsigned)(((K + n_c) * dim + 255) / 256)), dim3(256), f.st, b->b_in, centroids, members, (uint64_t)(K * dim),
+               (uint64_t)((K + n_c) * dim));
+    return VDB_OK;
+  }
+  int finish(const u256* levels_c, const u256* levels_m, u256* pub) {
+    const bool resident = levels_c && levels_m;
+    TRY(mk_emit(fp, f.sp, centroids, K, dim, t->mc, f.st, b->b_mc, resident ? levels_c : nullptr, nullptr));
+    TRY(mk_emit(fp, f.sp, members, n_c, dim, t->mm, f.st, b->b_mm, resident ? levels_m : nullptr, nullptr));
+    VDB_HIP(hipMemcpyAsync(pub, f.iroot, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
+    VDB_HIP(hipMemcpyAsync(pub + 1, f.hdr, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
+    return inv_list_fixup(f.st);
+  }
+};
+
 // ------------------------------------------------------------------ the audit of one cluster's routing (include/vdb.h vdb_wit_ann_audit):
-// every member committed under cluster_root_c is at least as close to centroid c as to any other committed centroid.  Blocks A - D are
-// the frame's head; I [centroids | members] assigned; R per member i the K distance(centroid_j, member_i), the qmin chain -> m_i and
-// select_by_indicator(d_i0 .., ind) -> own_i, which the map ties to m_i; MC, MM the two merkle_commitments, whose roots the map ties to
-// the header's centroids_root and to picked.  Nothing after the head is the frame's: close() is not called.
+// every member committed under cluster_root_c is at least as close to centroid c as to any other committed centroid.  Its own block in
+// the cluster frame: R per member i the K distance(centroid_j, member_i), the qmin chain -> m_i and select_by_indicator(d_i0 .., ind) ->
+// own_i, which the map ties to m_i.
 struct AnnaLayout {
-  AnnuLayout fr;     // what AnnFrame::open reads: b_ind, b_sel, b_old, total, mw
+  AnnClusterLayout t;
   DistLayout dl;
-  MkLayout mc, mm;
   AnnaBlocks b;
 };
 // select_by_indicator([d_i0 .. d_i,K-1], ind) per member, lanes = (member i, j), j fastest.  ind is one-hot at c, so the running value
@@ -2235,27 +2289,18 @@ __global__ __launch_bounds__(64) void k_anna_pick(Streams st, const FpTables* __
 }
 // the refusals, in the frame's order, and where the blocks start
 static int anna_layout(FpEntry* fp, int metric, size_t K, size_t cluster, size_t n_c, size_t dim, AnnaLayout* o) {
-  MkuLayout none{};
-  TRY(ann_frame_layout(K, cluster, n_c, &o->fr, &none, [&](uint64_t*) -> int {
-    VDB_ARG(n_c > 0 && dim > 0 && dim <= ((size_t)1 << 20), "empty cluster, dim = 0 or dim above 2^20");
+  TRY(ann_cluster_layout(K, cluster, n_c, dim, &o->t, [&]() -> int {
     const size_t cap = VDB_NEAREST_TOPK_MAX_INSTANCES;
     VDB_ARG(K <= cap / n_c && dim <= cap / n_c, "audit too large: n_c * K and n_c * dim at most VDB_NEAREST_TOPK_MAX_INSTANCES");
     return dist_layout(fp->host, metric, dim, &o->dl);
   }));
-  mk_layout(K, dim, 0, &o->mc);
-  mk_layout(n_c, dim, (int)o->mc.zero_cell, &o->mm);   // Context::load_zero caches its cell: the centroids' padding has loaded it
-  o->b = anna_blocks(K, n_c, dim, o->fr.mw.total, o->dl.total_cells, o->dl.total_lk, fp->host.sz.qmin[0], fp->host.sz.qmin[1], o->mc.total, o->mm.total);
-  VDB_ARG(o->b.total <= VDB_NEAREST_TOPK_MAX_CELLS, "audit circuit above 2^34 cells");
-  o->fr.b.n_in = o->b.n_in;
-  o->fr.b.b_ind = o->b.b_ind;
-  o->fr.b.b_sel = o->b.b_sel;
-  o->fr.b.b_old = o->b.b_old;
-  o->fr.b.total = o->b.total;
+  o->b = anna_blocks(K, n_c, dim, o->t.mw.total, o->dl.total_cells, o->dl.total_lk, fp->host.sz.qmin[0], fp->host.sz.qmin[1], o->t.mc.total, o->t.mm.total);
+  VDB_ARG(o->b.f.total <= VDB_NEAREST_TOPK_MAX_CELLS, "audit circuit above 2^34 cells");
   return VDB_OK;
 }
-// roots: [centroids_root | the K cluster roots]; levels_c / levels_m: the two trees where they are resident (forest segments K and c),
-// or both null; routed: n_c bytes; pub: [index_root | c].  Scratch slot 0 holds the distances and the prefix minima until k_anna_pick
-// has read them, and mk_emit asks for the slot again: every launch of R is enqueued before the first mk_emit (the stream orders them).
+// roots: [centroids_root | the K cluster roots]; routed: n_c bytes; the rest as AnnClusterFrame has it.  Scratch slot 0 holds the distances
+// and the prefix minima until k_anna_pick has read them, and mk_emit asks for the slot again: every launch of R is enqueued before
+// finish(), whose first mk_emit is the next to take the slot (the stream orders them).
 int wit_ann_audit_dev(FpEntry* fp, int metric, const u256* centroids, const u256* members, const u256* roots, const u256* levels_c, const u256* levels_m,
                       size_t K, size_t cluster, size_t n_c, size_t dim, Streams st, uint8_t* routed, u256* pub) {
   AnnaLayout a;
@@ -2266,84 +2311,58 @@ int wit_ann_audit_dev(FpEntry* fp, int metric, const u256* centroids, const u256
   if (!mid) return VDB_ERR_OOM;
   u256 *dist = mid + 3 * inst, *pm = dist + inst;
   uint32_t* rnd = (uint32_t*)(pm + inst + 8);
-  AnnFrame f;
-  TRY(f.open(st, roots, K, cluster, a.fr, 0, 0));
-  TRY(set_winv(f.st, fp->dev));   // the head's gadgets are GateChip's alone; R's read the tables of (P, L)
-  const bool resident = levels_c && levels_m;
-  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)(((K + n_c) * dim + 255) / 256)), dim3(256), f.st, b.b_in, centroids, members, (uint64_t)(K * dim),
-             (uint64_t)((K + n_c) * dim));
-  const InstMap im{b.b_r, 0, (uint32_t)K, b.per_member, b.per_member_l, (uint32_t)K, (uint32_t)K};   // t = i K + j: (centroid_j, member_i)
-  TRY(run_distances(f.st, fp, a.dl, im, (uint32_t)inst, centroids, members, mid, dist));
+  AnnClusterFrame cf;
+  TRY(cf.open(st, fp, centroids, members, roots, K, cluster, n_c, dim, a.t, b.f, 0));
+  const InstMap im{b.f.b_own, 0, (uint32_t)K, b.per_member, b.per_member_l, (uint32_t)K, (uint32_t)K};   // t = i K + j: (centroid_j, member_i)
+  TRY(run_distances(cf.f.st, fp, a.dl, im, (uint32_t)inst, centroids, members, mid, dist));
   VDB_LAUNCH(k_nv_rounds, dim3((unsigned)n_c), dim3(64), fp->dev, dist, (uint32_t)K, 1u, pm, rnd);
-  const NvMap nm{b.b_r, 0, b.per_member, b.per_member_l, b.chain_off, b.chain_loff, 0, 0, 0, 0, 0, (uint32_t)n_c, (uint32_t)K, (uint32_t)dim, 1u};
-  VDB_LAUNCH(k_nv_qmin, dim3((unsigned)((n_c * (K - 1) + 63) / 64 + (K == 1))), dim3(64), f.st, fp->dev, nm, dist, pm, rnd);
-  VDB_LAUNCH(k_anna_pick, dim3((unsigned)((inst + 63) / 64)), dim3(64), f.st, fp->dev, b.b_r + b.pick_off, b.per_member, (uint32_t)cluster, (uint32_t)K,
+  const NvMap nm{b.f.b_own, 0, b.per_member, b.per_member_l, b.chain_off, b.chain_loff, 0, 0, 0, 0, 0, (uint32_t)n_c, (uint32_t)K, (uint32_t)dim, 1u};
+  VDB_LAUNCH(k_nv_qmin, dim3((unsigned)((n_c * (K - 1) + 63) / 64 + (K == 1))), dim3(64), cf.f.st, fp->dev, nm, dist, pm, rnd);
+  VDB_LAUNCH(k_anna_pick, dim3((unsigned)((inst + 63) / 64)), dim3(64), cf.f.st, fp->dev, b.f.b_own + b.pick_off, b.per_member, (uint32_t)cluster, (uint32_t)K,
              (uint32_t)n_c, dist, pm, routed);
-  TRY(mk_emit(fp, f.sp, centroids, K, dim, a.mc, f.st, b.b_mc, resident ? levels_c : nullptr, nullptr));
-  TRY(mk_emit(fp, f.sp, members, n_c, dim, a.mm, f.st, b.b_mm, resident ? levels_m : nullptr, nullptr));
-  VDB_HIP(hipMemcpyAsync(pub, f.iroot, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
-  VDB_HIP(hipMemcpyAsync(pub + 1, f.hdr, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
-  return inv_list_fixup(f.st);
+  return cf.finish(levels_c, levels_m, pub);
 }
 
 // ------------------------------------------------------------------ the mean audit of one cluster (include/vdb.h vdb_wit_ann_mean):
-// word for word, centroid c is qdiv(sum of the members committed under cluster_root_c, quantization(n_c)).  Blocks A - D are the frame's
-// head; I [centroids | members] assigned; S select_by_indicator(centroids, ind) -> own (k_nv_select over the K centroids, a lane per
-// word); M the constant len, the qadd chains and the dim qdiv, whose outputs the map ties to own; MC, MM the two merkle_commitments,
-// whose roots the map ties to the header's centroids_root and to picked.  Nothing after the head is the frame's: close() is not called.
+// word for word, centroid c is qdiv(sum of the members committed under cluster_root_c, quantization(n_c)).  Its own blocks in the cluster
+// frame: S select_by_indicator(centroids, ind) -> own (k_nv_select over the K centroids, a lane per word); M the constant len, the qadd
+// chains and the dim qdiv, whose outputs the map ties to own.
 struct AnnmLayout {
-  AnnuLayout fr;     // what AnnFrame::open reads: b_ind, b_sel, b_old, total, mw
-  MkLayout mc, mm;
+  AnnClusterLayout t;
   AnnmBlocks b;
 };
 // the refusals, in the frame's order, and where the blocks start
 static int annm_layout(FpEntry* fp, size_t K, size_t cluster, size_t n_c, size_t dim, AnnmLayout* o) {
-  MkuLayout none{};
-  TRY(ann_frame_layout(K, cluster, n_c, &o->fr, &none, [&](uint64_t*) -> int {
-    VDB_ARG(n_c > 0 && dim > 0 && dim <= ((size_t)1 << 20), "empty cluster, dim = 0 or dim above 2^20");
+  TRY(ann_cluster_layout(K, cluster, n_c, dim, &o->t, [&]() -> int {
     const size_t cap = VDB_NEAREST_TOPK_MAX_INSTANCES;
     VDB_ARG(K <= cap / dim && n_c <= cap / dim, "mean audit too large: K * dim and n_c * dim at most VDB_NEAREST_TOPK_MAX_INSTANCES");
     // qdiv's divisor is asserted below 2^(2P) (r_div_mod_var(ar, ba, 4P, 2P, ..) in fp_qdiv_emit__body): quantization(n_c) = n_c 2^P
     VDB_ARG(fp->host.P >= 63 || n_c < ((uint64_t)1 << fp->host.P), "n_c not below 2^P: quantization(n_c) would not pass qdiv's divisor bound 2^(2P)");
     return VDB_OK;
   }));
-  mk_layout(K, dim, 0, &o->mc);
-  mk_layout(n_c, dim, (int)o->mc.zero_cell, &o->mm);   // Context::load_zero caches its cell: the centroids' padding has loaded it
-  o->b = annm_blocks(K, n_c, dim, o->fr.mw.total, fp->host.sz.qdiv[0], fp->host.sz.qdiv[1], o->mc.total, o->mm.total);
-  VDB_ARG(o->b.total <= VDB_NEAREST_TOPK_MAX_CELLS, "mean audit circuit above 2^34 cells");
-  o->fr.b.n_in = o->b.n_in;
-  o->fr.b.b_ind = o->b.b_ind;
-  o->fr.b.b_sel = o->b.b_sel;
-  o->fr.b.b_old = o->b.b_old;
-  o->fr.b.total = o->b.total;
+  o->b = annm_blocks(K, n_c, dim, o->t.mw.total, fp->host.sz.qdiv[0], fp->host.sz.qdiv[1], o->t.mc.total, o->t.mm.total);
+  VDB_ARG(o->b.f.total <= VDB_NEAREST_TOPK_MAX_CELLS, "mean audit circuit above 2^34 cells");
   return VDB_OK;
 }
-// roots: [centroids_root | the K cluster roots]; levels_c / levels_m: the two trees where they are resident (forest segments K and c),
-// or both null; mean_ok: dim bytes; pub: [index_root | c].  own and the chain totals live in the frame's work space (scratch slot 7),
-// not in slot 0, which mk_emit asks for: S and M are still enqueued before the first mk_emit, the order the audit documents.
+// roots: [centroids_root | the K cluster roots]; mean_ok: dim bytes; the rest as AnnClusterFrame has it.  own and the chain totals live in
+// the frame's work space (`extra`, scratch slot 7), not in slot 0, which mk_emit asks for: S and M are still enqueued before finish() and
+// its first mk_emit, the order the audit documents.
 int wit_ann_mean_dev(FpEntry* fp, const u256* centroids, const u256* members, const u256* roots, const u256* levels_c, const u256* levels_m, size_t K,
                      size_t cluster, size_t n_c, size_t dim, Streams st, uint8_t* mean_ok, u256* pub) {
   AnnmLayout a;
   TRY(annm_layout(fp, K, cluster, n_c, dim, &a));
   const AnnmBlocks& b = a.b;
-  AnnFrame f;
-  TRY(f.open(st, roots, K, cluster, a.fr, 0, 2 * dim));
-  TRY(set_winv(f.st, fp->dev));   // the head's gadgets are GateChip's alone; M's qdiv reads the tables of (P, L)
+  AnnClusterFrame cf;
+  TRY(cf.open(st, fp, centroids, members, roots, K, cluster, n_c, dim, a.t, b.f, 2 * dim));
+  const AnnFrame& f = cf.f;
   u256 *own = f.extra, *sums = own + dim;
-  const bool resident = levels_c && levels_m;
-  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)(((K + n_c) * dim + 255) / 256)), dim3(256), f.st, b.b_in, centroids, members, (uint64_t)(K * dim),
-             (uint64_t)((K + n_c) * dim));
   const NvMap sm{b.b_s, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, (uint32_t)K, (uint32_t)dim, 1u};
   VDB_LAUNCH(k_nv_select, dim3((unsigned)((dim + 63) / 64)), dim3(64), f.st, fp->dev, sm, 1u, centroids, f.ind, own);
   const u256 len = fr_mul(to_mont<Fr>(u256_from_u64(n_c)), fp->host.scale);   // load_constant(quantization(n_c))
   VDB_LAUNCH(k_push_cells, dim3(1), dim3(1), f.st, b.b_m, len, len, 1u);
   VDB_LAUNCH(k_annm_sum, dim3((unsigned)dim), dim3(64), f.st, fp->dev, b.b_chain, (uint32_t)n_c, (uint32_t)dim, members, sums);
   VDB_LAUNCH(k_annm_div, dim3((unsigned)((dim + 63) / 64), 8), dim3(64), f.st, fp->dev, b.b_div, (uint32_t)dim, sums, len, own, mean_ok);
-  TRY(mk_emit(fp, f.sp, centroids, K, dim, a.mc, f.st, b.b_mc, resident ? levels_c : nullptr, nullptr));
-  TRY(mk_emit(fp, f.sp, members, n_c, dim, a.mm, f.st, b.b_mm, resident ? levels_m : nullptr, nullptr));
-  VDB_HIP(hipMemcpyAsync(pub, f.iroot, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
-  VDB_HIP(hipMemcpyAsync(pub + 1, f.hdr, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
-  return inv_list_fixup(f.st);
+  return cf.finish(levels_c, levels_m, pub);
 }
 
 // the means of all K clusters as values alone (include/vdb.h vdb_ann_cluster_means_dev); `offsets`: the host's copy, already checked
@@ -2368,6 +2387,13 @@ using namespace vdb;
 // rank window applied by the *_dev witness entry points (vdb_wit_set_window); full range by default; per device context
 #define g_win (vdb::ctx().win)
 
+// the error word of a call on the caller's own buffers: scratch slot 1, cleared on the stream
+static int err_word(int** derr) {
+  *derr = (int*)scratch_get(1, 64);
+  if (!*derr) return VDB_ERR_OOM;
+  VDB_HIP(hipMemsetAsync(*derr, 0, sizeof(int), ctx().stream));
+  return VDB_OK;
+}
 struct HostStreams {
   DevBuf adv, sel, lk, err;
   Streams st;
@@ -2403,9 +2429,8 @@ struct DevStreams {
   Streams st;
   // with the error word (distance, fp_op, nearest, kmeans)
   int init(vdb_fr* stream_dev, uint8_t* selector_dev, vdb_fr* lookup_dev) {
-    int* derr = (int*)scratch_get(1, 64);
-    if (!derr) return VDB_ERR_OOM;
-    VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
+    int* derr;
+    TRY(err_word(&derr));
     st = Streams{as_u256(stream_dev), selector_dev, as_u256(lookup_dev), derr, nullptr, nullptr, nullptr, 0, g_win[0], g_win[1], g_win[2], g_win[3]};
     return VDB_OK;
   }
@@ -2431,6 +2456,38 @@ static int ann_batch_host(vdb_fr* levels, uint64_t lp, const vdb_fr* roots, size
   TRY(download(public_out, dpub.p, n_pub * sizeof(u256)));
   TRY(download(levels, dl.p, 2 * lp * sizeof(u256)));
   return hs.finish(stream_out, nullptr, selector_out, cells, 0);
+}
+// What the host-array entry points of the two audits share: centroids, members and the K + 1 roots go up, run(centroids, members, roots,
+// streams, flags, public) emits the circuit, the n_flags flag bytes and the public row [index_root | c] come back.
+template <class Run>
+static int ann_cluster_host(const vdb_fr* centroids, const vdb_fr* members, const vdb_fr* roots, size_t K, size_t n_c, size_t dim, uint64_t cells, uint64_t lookups,
+                            size_t n_flags, vdb_fr* stream_out, vdb_fr* lookup_out, uint8_t* selector_out, uint8_t* flags_out, vdb_fr* public_out, Run run) {
+  DevBuf dc, dm, dr, dfl, dpub;
+  HostStreams hs;
+  TRY(upload(dc, centroids, K * dim * sizeof(u256)));
+  TRY(upload(dm, members, n_c * dim * sizeof(u256)));
+  TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
+  TRY(dfl.alloc(n_flags));
+  TRY(dpub.alloc(2 * sizeof(u256)));
+  TRY(hs.init(cells, lookups, selector_out != nullptr));
+  TRY(run(dc.as<u256>(), dm.as<u256>(), dr.as<u256>(), hs.st, dfl.as<uint8_t>(), dpub.as<u256>()));
+  TRY(download(flags_out, dfl.p, n_flags));
+  TRY(download(public_out, dpub.p, 2 * sizeof(u256)));
+  return hs.finish(stream_out, lookup_out, selector_out, cells, lookups);
+}
+// and their _dev forms: the pointer refusals, the tables of (P, L), the caller's buffers under the rank window; run(fp, levels_c, levels_m, streams) emits
+template <class Run>
+static int ann_cluster_dev(uint32_t P, uint32_t L, const vdb_fr* centroids_dev, const vdb_fr* members_dev, const vdb_fr* roots_dev, const vdb_fr* centroid_levels_dev,
+                           const vdb_fr* member_levels_dev, vdb_fr* stream_dev, vdb_fr* lookup_dev, uint8_t* selector_dev, const uint8_t* flags_dev, const vdb_fr* public_dev, Run run) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(centroids_dev && members_dev && roots_dev && stream_dev && lookup_dev && flags_dev && public_dev, "null pointer");
+  VDB_ARG(!centroid_levels_dev == !member_levels_dev, "the two resident trees are given together or not at all");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  DevStreams ds;
+  TRY(ds.init(stream_dev, selector_dev, lookup_dev));
+  TRY(run(fp, centroid_levels_dev ? as_u256(centroid_levels_dev) : nullptr, member_levels_dev ? as_u256(member_levels_dev) : nullptr, ds.st));
+  return ds.finish();
 }
 
 extern "C" {
@@ -2600,9 +2657,8 @@ int vdb_nearest_values_dev(uint32_t P, uint32_t L, int metric, const vdb_fr* que
   VDB_ARG(queries_dev && vectors_dev && idx_out_dev && n_queries > 0 && n > 0 && dim > 0, "null pointer or empty input");
   FpEntry* fp;
   TRY(get_fp(P, L, &fp));
-  int* derr = (int*)scratch_get(1, 64);
-  if (!derr) return VDB_ERR_OOM;
-  VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
+  int* derr;
+  TRY(err_word(&derr));
   TRY(nearest_values_dev(fp, metric, as_u256(queries_dev), as_u256(vectors_dev), n_queries, n, dim, derr, idx_out_dev, as_u256(dist_out_dev)));
   return check_err_flag(derr);
 }
@@ -2893,7 +2949,7 @@ int vdb_wit_ann_update_size(size_t K, size_t n_c, size_t dim, size_t m, unsigned
   MkuLayout ml;
   TRY(annu_layout(K, 0, n_c, dim, m, grow, &a, &ml));
   if (cells) *cells = a.b.total;
-  if (input_cells) *input_cells = a.b.n_in;
+  if (input_cells) *input_cells = a.b.h.n_in;
   if (update_base) *update_base = a.b.b_upd;
   return VDB_OK;
 }
@@ -2935,7 +2991,7 @@ int vdb_wit_ann_delete_size(size_t K, size_t n_c, size_t dim, size_t m, uint64_t
   AnndPlan dp;
   TRY(annd_layout(K, 0, n_c, dim, nullptr, m, &a, &ml, &dp));
   if (cells) *cells = a.b.total;
-  if (input_cells) *input_cells = a.b.n_in;
+  if (input_cells) *input_cells = a.b.h.n_in;
   if (update_base) *update_base = a.b.b_upd;
   if (shrink_base) *shrink_base = a.b.b_shr;
   if (shrink) *shrink = dp.shrink;
@@ -2970,25 +3026,18 @@ int vdb_wit_ann_audit_size(int metric, uint32_t P, uint32_t L, size_t K, size_t 
   TRY(get_fp(P, L, &fp));
   AnnaLayout a;
   TRY(anna_layout(fp, metric, K, 0, n_c, dim, &a));
-  if (cells) *cells = a.b.total;
+  if (cells) *cells = a.b.f.total;
   if (lookups) *lookups = a.b.total_l;
-  if (input_cells) *input_cells = a.b.n_in;
+  if (input_cells) *input_cells = a.b.f.h.n_in;
   return VDB_OK;
 }
 int vdb_wit_ann_audit_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* centroids_dev, const vdb_fr* members_dev, const vdb_fr* roots_dev,
                           const vdb_fr* centroid_levels_dev, const vdb_fr* member_levels_dev, size_t K, size_t cluster, size_t n_c, size_t dim,
                           vdb_fr* stream_dev, vdb_fr* lookup_dev, uint8_t* selector_dev, uint8_t* routed_dev, vdb_fr* public_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(centroids_dev && members_dev && roots_dev && stream_dev && lookup_dev && routed_dev && public_dev, "null pointer");
-  VDB_ARG(!centroid_levels_dev == !member_levels_dev, "the two resident trees are given together or not at all");
-  FpEntry* fp;
-  TRY(get_fp(P, L, &fp));
-  DevStreams ds;
-  TRY(ds.init(stream_dev, selector_dev, lookup_dev));
-  TRY(wit_ann_audit_dev(fp, metric, as_u256(centroids_dev), as_u256(members_dev), as_u256(roots_dev),
-                        centroid_levels_dev ? as_u256(centroid_levels_dev) : nullptr, member_levels_dev ? as_u256(member_levels_dev) : nullptr, K, cluster,
-                        n_c, dim, ds.st, routed_dev, as_u256(public_dev)));
-  return ds.finish();
+  const auto run = [&](FpEntry* fp, const u256* levels_c, const u256* levels_m, Streams st) {
+    return wit_ann_audit_dev(fp, metric, as_u256(centroids_dev), as_u256(members_dev), as_u256(roots_dev), levels_c, levels_m, K, cluster, n_c, dim, st, routed_dev, as_u256(public_dev));
+  };
+  return ann_cluster_dev(P, L, centroids_dev, members_dev, roots_dev, centroid_levels_dev, member_levels_dev, stream_dev, lookup_dev, selector_dev, routed_dev, public_dev, run);
 }
 int vdb_wit_ann_audit(int metric, uint32_t P, uint32_t L, const vdb_fr* centroids, const vdb_fr* members, const vdb_fr* roots, size_t K, size_t cluster,
                       size_t n_c, size_t dim, vdb_fr* stream_out, vdb_fr* lookup_out, uint8_t* selector_out, uint8_t* routed_out, vdb_fr* public_out) {
@@ -2998,19 +3047,10 @@ int vdb_wit_ann_audit(int metric, uint32_t P, uint32_t L, const vdb_fr* centroid
   TRY(get_fp(P, L, &fp));
   AnnaLayout a;
   TRY(anna_layout(fp, metric, K, cluster, n_c, dim, &a));
-  DevBuf dc, dm, dr, drt, dpub;
-  HostStreams hs;
-  TRY(upload(dc, centroids, K * dim * sizeof(u256)));
-  TRY(upload(dm, members, n_c * dim * sizeof(u256)));
-  TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
-  TRY(drt.alloc(n_c));
-  TRY(dpub.alloc(2 * sizeof(u256)));
-  TRY(hs.init(a.b.total, a.b.total_l, selector_out != nullptr));
-  TRY(wit_ann_audit_dev(fp, metric, dc.as<u256>(), dm.as<u256>(), dr.as<u256>(), nullptr, nullptr, K, cluster, n_c, dim, hs.st, drt.as<uint8_t>(),
-                        dpub.as<u256>()));
-  TRY(download(routed_out, drt.p, n_c));
-  TRY(download(public_out, dpub.p, 2 * sizeof(u256)));
-  return hs.finish(stream_out, lookup_out, selector_out, a.b.total, a.b.total_l);
+  const auto run = [&](const u256* dc, const u256* dm, const u256* dr, Streams st, uint8_t* routed, u256* dpub) {
+    return wit_ann_audit_dev(fp, metric, dc, dm, dr, nullptr, nullptr, K, cluster, n_c, dim, st, routed, dpub);
+  };
+  return ann_cluster_host(centroids, members, roots, K, n_c, dim, a.b.f.total, a.b.total_l, n_c, stream_out, lookup_out, selector_out, routed_out, public_out, run);
 }
 
 // the mean audit of one cluster (include/vdb.h)
@@ -3020,24 +3060,18 @@ int vdb_wit_ann_mean_size(uint32_t P, uint32_t L, size_t K, size_t n_c, size_t d
   TRY(get_fp(P, L, &fp));
   AnnmLayout a;
   TRY(annm_layout(fp, K, 0, n_c, dim, &a));
-  if (cells) *cells = a.b.total;
+  if (cells) *cells = a.b.f.total;
   if (lookups) *lookups = a.b.total_l;
-  if (input_cells) *input_cells = a.b.n_in;
+  if (input_cells) *input_cells = a.b.f.h.n_in;
   return VDB_OK;
 }
 int vdb_wit_ann_mean_dev(uint32_t P, uint32_t L, const vdb_fr* centroids_dev, const vdb_fr* members_dev, const vdb_fr* roots_dev,
                          const vdb_fr* centroid_levels_dev, const vdb_fr* member_levels_dev, size_t K, size_t cluster, size_t n_c, size_t dim,
                          vdb_fr* stream_dev, vdb_fr* lookup_dev, uint8_t* selector_dev, uint8_t* mean_ok_dev, vdb_fr* public_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(centroids_dev && members_dev && roots_dev && stream_dev && lookup_dev && mean_ok_dev && public_dev, "null pointer");
-  VDB_ARG(!centroid_levels_dev == !member_levels_dev, "the two resident trees are given together or not at all");
-  FpEntry* fp;
-  TRY(get_fp(P, L, &fp));
-  DevStreams ds;
-  TRY(ds.init(stream_dev, selector_dev, lookup_dev));
-  TRY(wit_ann_mean_dev(fp, as_u256(centroids_dev), as_u256(members_dev), as_u256(roots_dev), centroid_levels_dev ? as_u256(centroid_levels_dev) : nullptr,
-                       member_levels_dev ? as_u256(member_levels_dev) : nullptr, K, cluster, n_c, dim, ds.st, mean_ok_dev, as_u256(public_dev)));
-  return ds.finish();
+  const auto run = [&](FpEntry* fp, const u256* levels_c, const u256* levels_m, Streams st) {
+    return wit_ann_mean_dev(fp, as_u256(centroids_dev), as_u256(members_dev), as_u256(roots_dev), levels_c, levels_m, K, cluster, n_c, dim, st, mean_ok_dev, as_u256(public_dev));
+  };
+  return ann_cluster_dev(P, L, centroids_dev, members_dev, roots_dev, centroid_levels_dev, member_levels_dev, stream_dev, lookup_dev, selector_dev, mean_ok_dev, public_dev, run);
 }
 int vdb_wit_ann_mean(uint32_t P, uint32_t L, const vdb_fr* centroids, const vdb_fr* members, const vdb_fr* roots, size_t K, size_t cluster, size_t n_c,
                      size_t dim, vdb_fr* stream_out, vdb_fr* lookup_out, uint8_t* selector_out, uint8_t* mean_ok_out, vdb_fr* public_out) {
@@ -3047,18 +3081,10 @@ int vdb_wit_ann_mean(uint32_t P, uint32_t L, const vdb_fr* centroids, const vdb_
   TRY(get_fp(P, L, &fp));
   AnnmLayout a;
   TRY(annm_layout(fp, K, cluster, n_c, dim, &a));
-  DevBuf dc, dm, dr, dok, dpub;
-  HostStreams hs;
-  TRY(upload(dc, centroids, K * dim * sizeof(u256)));
-  TRY(upload(dm, members, n_c * dim * sizeof(u256)));
-  TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
-  TRY(dok.alloc(dim));
-  TRY(dpub.alloc(2 * sizeof(u256)));
-  TRY(hs.init(a.b.total, a.b.total_l, selector_out != nullptr));
-  TRY(wit_ann_mean_dev(fp, dc.as<u256>(), dm.as<u256>(), dr.as<u256>(), nullptr, nullptr, K, cluster, n_c, dim, hs.st, dok.as<uint8_t>(), dpub.as<u256>()));
-  TRY(download(mean_ok_out, dok.p, dim));
-  TRY(download(public_out, dpub.p, 2 * sizeof(u256)));
-  return hs.finish(stream_out, lookup_out, selector_out, a.b.total, a.b.total_l);
+  const auto run = [&](const u256* dc, const u256* dm, const u256* dr, Streams st, uint8_t* mean_ok, u256* dpub) {
+    return wit_ann_mean_dev(fp, dc, dm, dr, nullptr, nullptr, K, cluster, n_c, dim, st, mean_ok, dpub);
+  };
+  return ann_cluster_host(centroids, members, roots, K, n_c, dim, a.b.f.total, a.b.total_l, dim, stream_out, lookup_out, selector_out, mean_ok_out, public_out, run);
 }
 
 // the means of all K clusters of a resident index, values only (include/vdb.h): no stream, no window
@@ -3073,9 +3099,8 @@ int vdb_ann_cluster_means_dev(uint32_t P, uint32_t L, const vdb_fr* grouped_dev,
   TRY(download(off.data(), offsets_dev, (K + 1) * sizeof(uint64_t)));
   VDB_HIP(hipStreamSynchronize(ctx().stream));
   TRY(ann_means_check(off.data(), n, K, dim));
-  int* derr = (int*)scratch_get(1, 64);
-  if (!derr) return VDB_ERR_OOM;
-  VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
+  int* derr;
+  TRY(err_word(&derr));
   TRY(ann_means_dev(fp, as_u256(grouped_dev), offsets_dev, K, dim, derr, as_u256(means_dev)));
   return check_err_flag(derr);
 }
@@ -3090,9 +3115,8 @@ int vdb_ann_cluster_means(uint32_t P, uint32_t L, const vdb_fr* grouped, const u
   TRY(upload(dg, grouped, n * dim * sizeof(u256)));
   TRY(upload(doff, offsets, (K + 1) * sizeof(uint64_t)));
   TRY(dmeans.alloc(K * dim * sizeof(u256)));
-  int* derr = (int*)scratch_get(1, 64);
-  if (!derr) return VDB_ERR_OOM;
-  VDB_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx().stream));
+  int* derr;
+  TRY(err_word(&derr));
   TRY(ann_means_dev(fp, dg.as<u256>(), doff.as<uint64_t>(), K, dim, derr, dmeans.as<u256>()));
   TRY(check_err_flag(derr));
   TRY(download(means_out, dmeans.p, K * dim * sizeof(u256)));

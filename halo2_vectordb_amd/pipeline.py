@@ -1372,6 +1372,25 @@ class AnnIndex:
         self._bufs = []
 
 
+def _bind_cluster(hp, index, cluster):
+    """binds hot path `hp` to cluster c of the index -> n_c"""
+    hp.index, hp.K, hp.cluster = index, index.K, int(cluster)
+    if not 0 <= hp.cluster < hp.K:
+        raise ValueError("cluster outside the index")
+    return int(index.sizes[hp.cluster])
+
+
+def _given_ptr(hp, given, shape, resident_ptr):
+    """where a call reads what the index holds: `resident_ptr`, or the quantized override `given`, uploaded"""
+    if given is None:
+        return resident_ptr
+    a = np.ascontiguousarray(given, dtype=np.uint64)
+    assert a.shape == shape
+    d = hp._output(a.nbytes)
+    d.upload(a)
+    return d.ptr
+
+
 class AnnQueryHotPath(HotPath):
     """An approximate-nearest-neighbour query against a committed AnnIndex in ONE proof (include/vdb.h vdb_wit_ann_query): assign the
     query, the centroids, the members of the cluster searched and the K cluster roots; nearest_vector(query, centroids),
@@ -1399,19 +1418,8 @@ class AnnQueryHotPath(HotPath):
     def _load_inputs(self):
         super()._load_inputs()
         ix, self.resident = self.index, self.given_roots is None and self.given_cent is None
-        self.p_cent, self.p_roots = ix.d_cent.ptr, ix.d_roots.at(B)
-        if self.given_roots is not None:
-            r = np.ascontiguousarray(self.given_roots, dtype=np.uint64)
-            assert r.shape == (self.K, 4)
-            d = self._output(r.nbytes)
-            d.upload(r)
-            self.p_roots = d.ptr
-        if self.given_cent is not None:
-            c = np.ascontiguousarray(self.given_cent, dtype=np.uint64)
-            assert c.shape == (self.K, self.dim, 4)
-            d = self._output(c.nbytes)
-            d.upload(c)
-            self.p_cent = d.ptr
+        self.p_roots = _given_ptr(self, self.given_roots, (self.K, 4), ix.d_roots.at(B))
+        self.p_cent = _given_ptr(self, self.given_cent, (self.K, self.dim, 4), ix.d_cent.ptr)
 
     def _circuit_size(self):
         cells, lk, n_in = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
@@ -1453,13 +1461,6 @@ class _AnnBatchHotPath(PoseidonHotPath):
     AnnIndex, its tree before the batch (`d_levels0`) and the copy every witness run works on (`d_levels`), the public row `d_pub` of
     `n_public` values, the map.  A subclass sets lp, depth, m, n_public and given_levels, and gives _circuit_size, _call(sel): the
     library's witness call on these buffers -> its return code, and _builder(CS): (circuit_sym's build function, its own keywords)."""
-
-    def _cluster_size(self, index, cluster):
-        """binds the hot path to cluster c of the index -> n_c"""
-        self.index, self.K, self.cluster = index, index.K, int(cluster)
-        if not 0 <= self.cluster < self.K:
-            raise ValueError("cluster outside the index")
-        return int(index.sizes[self.cluster])
 
     def _load_inputs(self, grow=0):
         super()._load_inputs()
@@ -1509,7 +1510,7 @@ class AnnUpdateHotPath(_AnnBatchHotPath):
         m = self.indices.shape[0]
         if m < 1:
             raise ValueError("a batch holds at least one write")
-        n_c = self._cluster_size(index, cluster)
+        n_c = _bind_cluster(self, index, cluster)
         fill = n_c
         for s in self.indices.tolist():
             if s > fill:
@@ -1573,7 +1574,7 @@ class AnnDeleteHotPath(_AnnBatchHotPath):
         place of the index's segment c (tests of the binding)."""
         self.slots = np.ascontiguousarray(slots, dtype=np.uint64)
         m = self.slots.shape[0]
-        n_c = self._cluster_size(index, cluster)
+        n_c = _bind_cluster(self, index, cluster)
         if m < 1 or m >= n_c:
             raise ValueError("a batch holds at least one delete and leaves at least one member")
         origin = list(range(n_c))
@@ -1611,7 +1612,64 @@ class AnnDeleteHotPath(_AnnBatchHotPath):
         return CS.build_ann_delete, dict(shrink=self.shrink)
 
 
-class AnnAuditHotPath(HotPath):
+class _AnnClusterHotPath(HotPath):
+    """What the audits of one cluster c of a committed AnnIndex share (AnnAuditHotPath, AnnMeanHotPath): the binding to (index, cluster),
+    where the call reads the centroids and the members (`p_cent`, `p_members`: the resident index, or the overrides given; `resident`),
+    no input rows, the flag bytes and the public row [index_root | c] (`d_pub`), the map.  A subclass gives _size(*outputs) and
+    _call(*shared arguments): the library's size and witness calls -> their return codes, _n_flags(): the length of its flag bytes, and
+    _builder(CS): (circuit_sym's build function, the arguments ahead of K)."""
+
+    def __init__(self, index, cluster, k=13, P=48, L=12, tau=None, col_shard=(0, 1), blind_seed=None, params=None, centroids=None, members=None):
+        n_c = _bind_cluster(self, index, cluster)
+        super().__init__(n_c, index.dim, k, P, L, seed=None, tau=tau, col_shard=col_shard, vectors=np.zeros((0, index.dim)), blind_seed=blind_seed,
+                         params=params)
+        self.given_cent, self.given_members = centroids, members
+
+    def n_input_rows(self):
+        return 0
+
+    def _load_inputs(self):
+        super()._load_inputs()
+        ix, self.resident = self.index, self.given_cent is None and self.given_members is None
+        self.p_cent = _given_ptr(self, self.given_cent, (self.K, self.dim, 4), ix.d_cent.ptr)
+        self.p_members = _given_ptr(self, self.given_members, (self.n, self.dim, 4), ix.members_ptr(self.cluster))
+
+    def _circuit_size(self):
+        cells, lk, n_in = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(self._size(ctypes.byref(cells), ctypes.byref(lk), ctypes.byref(n_in)))
+        return n_in.value, cells.value - n_in.value, lk.value
+
+    def _alloc_outputs(self):
+        self.d_flag_bytes, self.d_pub = self._output(max(self._n_flags(), 32)), self._output(2 * B)
+
+    def _witness(self, sel=None):
+        # the call writes the assigned header, centroids and members too
+        ix = self.index
+        with self._window(sel, 0):
+            check(self._call(self.p_cent, self.p_members, ix.d_roots.ptr, ix.levels_ptr(self.K) if self.resident else None,
+                             ix.levels_ptr(self.cluster) if self.resident else None, self.K, self.cluster, self.n, self.dim, self.d_stream.ptr,
+                             self.d_lookup.ptr, self._sel_at(sel, 0), self.d_flag_bytes.ptr, self.d_pub.ptr))
+
+    def public_values_dev(self):
+        return self.d_pub.ptr, 2
+
+    def results(self):
+        """(index_root (4,), c (4,), the flag bytes, uint8: the audit's routed (n_c,), member i's own centroid attains the minimum of its K
+        distances; the mean's mean_ok (dim,), word j of centroid c is the mean of the members' words j)"""
+        pub = self.d_pub.download((2, 4))
+        return pub[0], pub[1], self.d_flag_bytes.download((self._n_flags(),), dtype=np.uint8)
+
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        build, ahead = self._builder(CS)
+        cm, public, _ = build(*ahead, self.K, self.n, self.dim, self.P, self.L, functools.partial(self._fetch_flags, d_flags), self._fetch,
+                              builder=DeviceBuilder if on_device else None)
+        assert cm.n_cells == self.n_cells
+        return cm, public, None
+
+
+class AnnAuditHotPath(_AnnClusterHotPath):
     """The routing of ONE cluster c of a committed AnnIndex proved in one proof (include/vdb.h vdb_wit_ann_audit): every member committed
     under cluster_root_c is at least as close to centroid c as to any other committed centroid, in the circuit's fixed-point distance.
     Assigned: the header [c | centroids' root | cluster roots]; then idx_to_indicator(c, K), select_by_indicator(cluster roots, indicators)
@@ -1626,68 +1684,25 @@ class AnnAuditHotPath(HotPath):
 
     def __init__(self, index, cluster, k=13, P=48, L=12, metric="euclidean", tau=None, col_shard=(0, 1), blind_seed=None, params=None, centroids=None,
                  members=None):
-        self.index, self.K, self.cluster = index, index.K, int(cluster)
-        if not 0 <= self.cluster < self.K:
-            raise ValueError("cluster outside the index")
-        super().__init__(int(index.sizes[self.cluster]), index.dim, k, P, L, seed=None, tau=tau, col_shard=col_shard, vectors=np.zeros((0, index.dim)),
-                         blind_seed=blind_seed, params=params)
+        super().__init__(index, cluster, k, P, L, tau, col_shard, blind_seed, params, centroids, members)
         self.metric, self.metric_name = api.METRICS[metric], metric
-        self.given_cent, self.given_members = centroids, members
 
-    def n_input_rows(self):
-        return 0
+    d_routed = property(lambda self: self.d_flag_bytes)
 
-    def _load_inputs(self):
-        super()._load_inputs()
-        self._cluster_inputs()
+    def _n_flags(self):
+        return self.n
 
-    def _cluster_inputs(self):
-        """where the call reads the centroids and the cluster's members: the resident index, or the overrides given (AnnMeanHotPath's too)"""
-        ix, self.resident = self.index, self.given_cent is None and self.given_members is None
-        self.p_cent, self.p_members = ix.d_cent.ptr, ix.members_ptr(self.cluster)
-        for given, shape, name in ((self.given_cent, (self.K, self.dim, 4), "p_cent"), (self.given_members, (self.n, self.dim, 4), "p_members")):
-            if given is not None:
-                a = np.ascontiguousarray(given, dtype=np.uint64)
-                assert a.shape == shape
-                d = self._output(a.nbytes)
-                d.upload(a)
-                setattr(self, name, d.ptr)
+    def _size(self, *out):
+        return self.lib.vdb_wit_ann_audit_size(self.metric, self.P, self.L, self.K, self.n, self.dim, *out)
 
-    def _circuit_size(self):
-        cells, lk, n_in = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-        check(self.lib.vdb_wit_ann_audit_size(self.metric, self.P, self.L, self.K, self.n, self.dim, ctypes.byref(cells), ctypes.byref(lk), ctypes.byref(n_in)))
-        return n_in.value, cells.value - n_in.value, lk.value
+    def _call(self, *shared):
+        return self.lib.vdb_wit_ann_audit_dev(self.metric, self.P, self.L, *shared)
 
-    def _alloc_outputs(self):
-        self.d_routed, self.d_pub = self._output(max(self.n, 32)), self._output(2 * B)
-
-    def _witness(self, sel=None):
-        # the call writes the assigned header, centroids and members too
-        ix = self.index
-        with self._window(sel, 0):
-            check(self.lib.vdb_wit_ann_audit_dev(self.metric, self.P, self.L, self.p_cent, self.p_members, ix.d_roots.ptr,
-                                                 ix.levels_ptr(self.K) if self.resident else None, ix.levels_ptr(self.cluster) if self.resident else None,
-                                                 self.K, self.cluster, self.n, self.dim, self.d_stream.ptr, self.d_lookup.ptr, self._sel_at(sel, 0),
-                                                 self.d_routed.ptr, self.d_pub.ptr))
-
-    def public_values_dev(self):
-        return self.d_pub.ptr, 2
-
-    def results(self):
-        """(index_root (4,), c (4,), routed (n_c,) uint8: member i's own centroid attains the minimum of its K distances)"""
-        pub = self.d_pub.download((2, 4))
-        return pub[0], pub[1], self.d_routed.download((self.n,), dtype=np.uint8)
-
-    def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        cm, public, _ = CS.build_ann_audit(self.metric_name, self.K, self.n, self.dim, self.P, self.L, functools.partial(self._fetch_flags, d_flags),
-                                           self._fetch, builder=DeviceBuilder if on_device else None)
-        assert cm.n_cells == self.n_cells
-        return cm, public, None
+    def _builder(self, CS):
+        return CS.build_ann_audit, (self.metric_name,)
 
 
-class AnnMeanHotPath(HotPath):
+class AnnMeanHotPath(_AnnClusterHotPath):
     """That centroid c of a committed AnnIndex is the mean of its cluster, proved in one proof (include/vdb.h vdb_wit_ann_mean): word for
     word, centroid c equals qdiv(sum of the members committed under cluster_root_c, quantization(n_c)) in the circuit's fixed-point
     arithmetic.  Assigned: the header [c | centroids' root | cluster roots]; then idx_to_indicator(c, K), select_by_indicator(cluster
@@ -1701,52 +1716,16 @@ class AnnMeanHotPath(HotPath):
     overrides of what the index holds (tests of the binding); with them the two trees are hashed by the call instead of read from the
     forest."""
 
-    def __init__(self, index, cluster, k=13, P=48, L=12, tau=None, col_shard=(0, 1), blind_seed=None, params=None, centroids=None, members=None):
-        self.index, self.K, self.cluster = index, index.K, int(cluster)
-        if not 0 <= self.cluster < self.K:
-            raise ValueError("cluster outside the index")
-        super().__init__(int(index.sizes[self.cluster]), index.dim, k, P, L, seed=None, tau=tau, col_shard=col_shard, vectors=np.zeros((0, index.dim)),
-                         blind_seed=blind_seed, params=params)
-        self.given_cent, self.given_members = centroids, members
+    d_ok = property(lambda self: self.d_flag_bytes)
 
-    def n_input_rows(self):
-        return 0
+    def _n_flags(self):
+        return self.dim
 
-    _cluster_inputs = AnnAuditHotPath._cluster_inputs
+    def _size(self, *out):
+        return self.lib.vdb_wit_ann_mean_size(self.P, self.L, self.K, self.n, self.dim, *out)
 
-    def _load_inputs(self):
-        super()._load_inputs()
-        self._cluster_inputs()
+    def _call(self, *shared):
+        return self.lib.vdb_wit_ann_mean_dev(self.P, self.L, *shared)
 
-    def _circuit_size(self):
-        cells, lk, n_in = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-        check(self.lib.vdb_wit_ann_mean_size(self.P, self.L, self.K, self.n, self.dim, ctypes.byref(cells), ctypes.byref(lk), ctypes.byref(n_in)))
-        return n_in.value, cells.value - n_in.value, lk.value
-
-    def _alloc_outputs(self):
-        self.d_ok, self.d_pub = self._output(max(self.dim, 32)), self._output(2 * B)
-
-    def _witness(self, sel=None):
-        # the call writes the assigned header, centroids and members too
-        ix = self.index
-        with self._window(sel, 0):
-            check(self.lib.vdb_wit_ann_mean_dev(self.P, self.L, self.p_cent, self.p_members, ix.d_roots.ptr,
-                                                ix.levels_ptr(self.K) if self.resident else None, ix.levels_ptr(self.cluster) if self.resident else None,
-                                                self.K, self.cluster, self.n, self.dim, self.d_stream.ptr, self.d_lookup.ptr, self._sel_at(sel, 0),
-                                                self.d_ok.ptr, self.d_pub.ptr))
-
-    def public_values_dev(self):
-        return self.d_pub.ptr, 2
-
-    def results(self):
-        """(index_root (4,), c (4,), mean_ok (dim,) uint8: word j of centroid c is the mean of the members' words j)"""
-        pub = self.d_pub.download((2, 4))
-        return pub[0], pub[1], self.d_ok.download((self.dim,), dtype=np.uint8)
-
-    def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        cm, public, _ = CS.build_ann_mean(self.K, self.n, self.dim, self.P, self.L, functools.partial(self._fetch_flags, d_flags), self._fetch,
-                                          builder=DeviceBuilder if on_device else None)
-        assert cm.n_cells == self.n_cells
-        return cm, public, None
+    def _builder(self, CS):
+        return CS.build_ann_mean, ()

@@ -217,3 +217,24 @@ def test_layout_refusals_and_exports():
         CS.ann_mean_layout(1, 1 << 8, 1, 8, 4)              # quantization(n_c) = 2^16 is not below 2^(2 P)
     assert CS.ann_mean_layout(1, (1 << 8) - 1, 1, 8, 4)["total_l"] > 0
     assert CS.ann_mean_instances(7, 0) == [7, 0]
+
+
+@pytest.mark.parametrize("K,n_c,dim", [(1, 1, 1), (2, 3, 2), (3, 5, 4), (65, 2, 1)])
+def test_the_two_audits_share_one_cluster_frame(K, n_c, dim):
+    """K = 65: the first K above one 64-lane block of indicators; K = 1: no is_equal block; (2, 3, 2): a padded centroid tree that is
+    full (zero_c false) beside a padded member tree"""
+    audit, mean = CS.ann_audit_layout("euclidean", K, n_c, dim, P, L), CS.ann_mean_layout(K, n_c, dim, P, L)
+    head = ("c", "centroids_root", "roots", "n_in", "indicator", "sponge", "select", "sponge_old", "update")
+    frame = head + ("centroids", "members", "zero_c")     # every key the two share up to and including `members`
+    assert {k for k in audit if k in mean} - set(frame) == {"units", "merkle_c", "merkle_m", "total", "total_l"}
+    for k in frame:
+        assert audit[k] == mean[k], k
+    update = CS.ann_update_layout(K, 1, dim, 1)
+    for k in head:
+        assert audit[k] == update[k], k
+    assert audit["centroids"] == audit["update"] and audit["members"] == audit["centroids"] + K * dim
+    assert audit["routed"] == mean["own"] == audit["members"] + n_c * dim
+    for lay in (audit, mean):
+        assert lay["merkle_m"] - lay["merkle_c"] == CS.merkle_cells(K, dim)
+        assert lay["total"] - lay["merkle_m"] == CS.merkle_cells(n_c, dim, lay["zero_c"])
+    assert audit["zero_c"] == (K not in (1, 2))

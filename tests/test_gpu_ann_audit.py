@@ -175,6 +175,9 @@ def test_two_windowed_calls_write_the_bytes_of_one(api, O):
         # runs and the qmin runs); inside a pick block; inside MC; inside the assigned members
         cuts = [(2, 0), (r["indicator"] + 8 + 5, 0), (m1 + m["chain_off"], per_l + K * d_lk), (m1 + m["pick_off"] + 5, 2 * per_l),
                 (r["merkle_c"] + 1000, len(lk)), (r["members"] + 3, 0)]
+        # the seams of the cluster frame the audits share: where the head ends, between the centroids and the members (inside the one
+        # launch that assigns both), where MC and MM start, one cell into MM
+        cuts += [(r["centroids"], 0), (r["members"], 0), (r["merkle_c"], len(lk)), (r["merkle_m"], len(lk)), (r["merkle_m"] + 1, len(lk))]
         for cut, lcut in cuts:
             halves = []
             for window in ((0, cut, 0, lcut), (cut, cells, lcut, len(lk))):

@@ -274,6 +274,9 @@ def test_windowed_calls_write_the_bytes_of_one(api, O):
         cuts = [(2, 0), (r["indicator"] + 8 + 5, 0), (r["members"] + 3, 0), (r["own"] + 5, 0), (r["len"], 0), (r["len"] + 1, 0), (r["chain"] + 6, 0),
                 (r["div"] + q_n, q_lk), (r["div"] + 2 * q_n, 2 * q_lk), (r["merkle_c"] + 1000, len(lk))]
         splits = [[x] for x in cuts] + [[cuts[3], cuts[7]], [cuts[6], cuts[8]]]          # two windows each, then three
+        # the seams of the cluster frame the audits share: where the head ends, between the centroids and the members (inside the one
+        # launch that assigns both), where MC and MM start, one cell into MM
+        splits += [[x] for x in ((r["centroids"], 0), (r["members"], 0), (r["merkle_c"], len(lk)), (r["merkle_m"], len(lk)), (r["merkle_m"] + 1, len(lk)))]
         for split in splits:
             edges = [(0, 0)] + split + [(cells, len(lk))]
             parts = []

@@ -35,16 +35,16 @@ int main() {
   // the blocks: sizes add up, the indicator offsets tile block B
   for (uint64_t K : {1ull, 2ull, 3ull, 64ull, 4096ull}) {
     const AnnuBlocks b = annu_blocks(K, 1000, 77);
-    CHECK(b.n_in == K + 2 && b.b_ind == K + 2);
-    CHECK(b.b_sel - b.b_ind == 8 + 12 * (K - 1));
-    CHECK(b.b_old - b.b_sel == 1 + 3 * K && b.b_upd - b.b_old == 1000 && b.b_new - b.b_upd == 77 && b.b_shr == b.b_new);
+    CHECK(b.h.n_in == K + 2 && b.h.b_ind == K + 2);
+    CHECK(b.h.b_sel - b.h.b_ind == 8 + 12 * (K - 1));
+    CHECK(b.h.b_old - b.h.b_sel == 1 + 3 * K && b.b_upd - b.h.b_old == 1000 && b.b_upd == b.h.end && b.b_new - b.b_upd == 77 && b.b_shr == b.b_new);
     CHECK(b.b_root - b.b_new == 8 * K && b.total - b.b_root == 1000);
     uint64_t at = 0;
     for (uint64_t j = 0; j < K; j++) {
       CHECK(annu_indicator_off(j) == at);
       at += j ? 12 : 8;
     }
-    CHECK(at == b.b_sel - b.b_ind);
+    CHECK(at == b.h.b_sel - b.h.b_ind);
   }
   // fill tracking against a set of occupied slots
   std::mt19937_64 rng(7);
