@@ -578,6 +578,27 @@ def wit_ann_mean(centroids, members, roots, cluster, P=48, L=13, selectors=False
     return _wit_ann_cluster(lib.vdb_wit_ann_mean_size, lib.vdb_wit_ann_mean, None, centroids, members, roots, cluster, P, L, selectors, "mean_ok", False)
 
 
+def wit_ann_recentre(centroid_levels, members, roots, c, P=48, L=13, selectors=False):
+    """the recentre of cluster `c` (vdb_wit_ann_recentre), the streams alone: `centroid_levels` the centroids' tree (2 lp_K, 4)
+    (merkle_tree_build's array over the K centroids), the members of the cluster (n_c, dim, 4) and roots (K + 1, 4): [centroids' root |
+    cluster roots]: dict(stream, lookup, selectors, flags, n_in, update_base, public (3, 4): [index_root_old | c | index_root_new],
+    new_centroid (dim, 4): qdiv(sum of the members' words, quantization(n_c)), levels: the centroids' tree after the write)"""
+    lib = _lib.init()
+    members, roots = _fr(members), _fr(roots)
+    n_c, dim, K = members.shape[0], members.shape[1], roots.shape[0] - 1
+    levels = np.array(centroid_levels, dtype=np.uint64, copy=True)
+    assert roots.shape == (K + 1, 4) and levels.shape == (2 * merkle_levels(max(K, 1))[0], 4)
+    cells, lk, n_in, ub = _u64(), _u64(), _u64(), _u64()
+    check(lib.vdb_wit_ann_recentre_size(ctypes.c_uint32(P), ctypes.c_uint32(L), _sz(K), _sz(n_c), _sz(dim), ctypes.byref(cells), ctypes.byref(lk),
+                                        ctypes.byref(n_in), ctypes.byref(ub)))
+    stream, lookup = np.zeros((cells.value, 4), dtype=np.uint64), np.zeros((lk.value, 4), dtype=np.uint64)
+    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
+    new, pub = np.zeros((dim, 4), dtype=np.uint64), np.zeros((3, 4), dtype=np.uint64)
+    check(lib.vdb_wit_ann_recentre(ctypes.c_uint32(P), ctypes.c_uint32(L), _p(levels), _p(members), _p(roots), _sz(K), _sz(c), _sz(n_c), _sz(dim), _p(stream),
+                                   _p(lookup), _p(sel) if selectors else None, _p(new), _p(pub)))
+    return dict(stream=stream, lookup=lookup, **_split_flags(sel), n_in=n_in.value, update_base=ub.value, public=pub, new_centroid=new, levels=levels)
+
+
 def ann_cluster_means(grouped, offsets, P=48, L=13):
     """the means of all K clusters of grouped rows (n, dim, 4), cluster k the rows [offsets[k], offsets[k + 1]) (vdb_ann_cluster_means: values
     only): (K, dim, 4), means[k][j] = qdiv(sum of the cluster's words j, quantization(n_k)) bit for bit as vdb_wit_ann_mean constrains it"""

@@ -1762,12 +1762,22 @@ def place_mean(B, u, members, centroids, ind, n_c_quantized, own_base, len_cell,
     members i = 1 .. n_c - 1, member-major (kmeans' order and stride), then per word qdiv(sum_j, len), its lookup cells from lbase +
     j qd.n_lk on.  `members` (n_c, dim) / `centroids` (K, dim) / `ind` (K,): stream cells.  -> (own (dim,), mean (dim,)): the selection's
     outputs and the quotients; the caller ties them."""
-    sb, add, qd = u["sb"], u["add"], u["qd"]
+    sb = u["sb"]
     members, centroids = np.asarray(members, dtype=np.int64), np.asarray(centroids, dtype=np.int64)
     (n_c, dim), K = members.shape, centroids.shape[0]
     ind = np.asarray(ind, dtype=np.int64).reshape(K)
     j = np.arange(dim, dtype=np.int64)
     own = B.place(sb, own_base + j * sb.n, np.zeros(dim, dtype=np.int64), np.concatenate([centroids.T, np.broadcast_to(ind[None, :], (dim, K))], axis=1))[:, 0]
+    return own, place_mean_quotients(B, u, members, n_c_quantized, len_cell, lbase)
+
+
+def place_mean_quotients(B, u, members, n_c_quantized, len_cell, lbase):
+    """Block M alone (place_mean's second half; the recentre has no block S): the constant `n_c_quantized` at `len_cell`, the qadd chain
+    from len_cell + 1 on, then per word qdiv(sum_j, len).  `u` needs add and qd.  -> mean (dim,): the quotients' cells"""
+    add, qd = u["add"], u["qd"]
+    members = np.asarray(members, dtype=np.int64)
+    n_c, dim = members.shape
+    j = np.arange(dim, dtype=np.int64)
     B.constant_cell(len_cell, n_c_quantized)                 # ctx.load_constant(quantization(n_c))
     chain = len_cell + 1
     sum_cells = members[0].copy()
@@ -1779,8 +1789,7 @@ def place_mean(B, u, members, centroids, ind, n_c_quantized, own_base, len_cell,
         B.place(add, bases, np.zeros_like(bases), np.stack([members[vv, jj], prev], axis=1))    # qadd(member's word, running sum)
         sum_cells = outs.reshape(n_c - 1, dim)[-1]
     div = chain + (n_c - 1) * dim * add.n
-    mean = B.place(qd, div + j * qd.n, lbase + j * qd.n_lk, np.stack([sum_cells, np.full(dim, len_cell)], axis=1))[:, 0]
-    return own, mean
+    return B.place(qd, div + j * qd.n, lbase + j * qd.n_lk, np.stack([sum_cells, np.full(dim, len_cell)], axis=1))[:, 0]
 
 
 def build_ann_mean(K, n_c, dim, P, L, fetch_flags, fetch_values, builder=None):
@@ -1794,6 +1803,75 @@ def build_ann_mean(K, n_c, dim, P, L, fetch_flags, fetch_values, builder=None):
         own, mean = (x.tolist() for x in place_mean(B, lay["units"], mem, cent, inds, n_c << P, lay["own"], lay["len"], 0))
         return zip(mean, own), dict(own=own, mean=mean, len=lay["len"])    # ctx.constrain_equal(own_j, mean_j)
     return _build_ann_cluster(lay, K, n_c, dim, fetch_flags, fetch_values, builder, own_block)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The recentre of one cluster, old index root to new (include/vdb.h vdb_wit_ann_recentre; pipeline.AnnRecentreHotPath)
+def ann_recentre_layout(K, n_c, dim, P, L):
+    """where the blocks of the recentre circuit start: the head's keys of _ann_frame_layout (c, centroids_root, roots, n_in, indicator,
+    select, sponge_old, sponge; `update`: where the head ends); members: the assigned block I; len, chain, div: block M as
+    ann_mean_layout has it; merkle_m: MM; centroid_update: block U, update_layout: its merkle_update_layout (relative to it), depth;
+    sponge_new: G; total, total_l; units: dict(add, qd)"""
+    if n_c < 1 or dim < 1:
+        raise ValueError("at least one member and one word")
+    if n_c >= 1 << P:
+        raise ValueError("quantization(n_c) must stay below qdiv's divisor bound 2^(2P)")
+    if K == 1:
+        raise ValueError("a tree of one leaf has no path (depth 0)")
+    sp = merkle_leaf_layout(K + 1)
+    head = _ann_frame_layout(K, sp, 0)
+    lay = {k: head[k] for k in ("c", "centroids_root", "roots", "n_in", "indicator", "sponge", "select", "sponge_old", "update")}
+    mu = mean_units(1, P, L)
+    u = lay["units"] = dict(add=mu["add"], qd=mu["qd"])
+    depth = (K - 1).bit_length()
+    upd = merkle_update_layout(1, dim, depth)
+    lay.update(members=lay["update"], depth=depth, update_layout=upd)
+    lay["len"] = lay["members"] + n_c * dim
+    lay["chain"] = lay["len"] + 1
+    lay["div"] = lay["chain"] + (n_c - 1) * dim * u["add"].n
+    lay["merkle_m"] = lay["div"] + dim * u["qd"].n
+    lay["centroid_update"] = lay["merkle_m"] + merkle_cells(n_c, dim)
+    lay["sponge_new"] = lay["centroid_update"] + upd["total"]
+    lay["total"] = lay["sponge_new"] + sp["leaf_cells"]
+    lay["total_l"] = dim * u["qd"].n_lk
+    return lay
+
+
+def ann_recentre_instances(index_root_old, c, index_root_new):
+    """the public cells in make_public order: [index_root_old | c | index_root_new]"""
+    return [int(index_root_old), int(c), int(index_root_new)]
+
+
+def build_ann_recentre(K, n_c, dim, P, L, fetch_flags, fetch_values, builder=None):
+    """The recentre of one cluster in one circuit (pipeline.AnnRecentreHotPath), from the pieces the other circuits have: the frame's head
+    (_build_ann_head), the members assigned, block M (place_mean_quotients), merkle_commitment(members) TIED to picked (place_merkle),
+    the update block of the centroids' tree with one write (place_merkle_update at its base) — its old root TIED to the header's
+    centroids_root, its idx to c, its assigned new-vector word j to mean_j — and the sponge over [the block's new root | the header's
+    cluster roots] (place_sponge).  fetch_flags / fetch_values: as place_merkle; `builder`: as build_kmeans.
+    -> (CopyMap, public cells [index_root_old, c, index_root_new], dict(indicators, picked, mean, len, members_root, update_public,
+    new_vector, index_root_old, index_root_new, layout))"""
+    lay = ann_recentre_layout(K, n_c, dim, P, L)
+    B, inds, picked, root_old = _build_ann_head(lay, fetch_flags, fetch_values, builder)
+    if np.asarray(fetch_flags(lay["members"], lay["members"] + n_c * dim)).any():
+        raise ValueError("the assigned members carry no gate or constant flag")
+    mem = lay["members"] + np.arange(n_c * dim, dtype=np.int64).reshape(n_c, dim)
+    mean = [int(x) for x in place_mean_quotients(B, lay["units"], mem, n_c << P, lay["len"], 0)]
+    mroot, end = place_merkle(B, n_c, dim, lay["merkle_m"], lay["members"], fetch_flags, fetch_values)
+    assert end == lay["centroid_update"]
+    B.tie(mroot, picked)                                     # ctx.constrain_equal(picked, mroot)
+    ub = lay["centroid_update"]
+    upub = place_merkle_update(B, 1, dim, lay["depth"], fetch_flags, fetch_values, ub)
+    new_vector = [ub + j for j in range(dim)]
+    for j in range(dim):
+        B.tie(new_vector[j], mean[j])                        # ctx.constrain_equal(mean_j, the block's new-vector word j)
+    B.tie(upub[0], lay["centroids_root"])                    # ctx.constrain_equal(centroids_root, the block's old root)
+    B.tie(upub[1], lay["c"])                                 # ctx.constrain_equal(c, the block's idx)
+    root_new, end = place_sponge(B, lay["sponge_new"], [upub[-1]] + [lay["roots"] + j for j in range(K)], fetch_flags, fetch_values)
+    if end != lay["total"]:
+        raise ValueError("the trace does not end where the circuit does")
+    info = dict(indicators=[int(i) for i in inds], picked=picked, mean=mean, len=lay["len"], members_root=mroot, update_public=upub, new_vector=new_vector,
+                index_root_old=root_old, index_root_new=root_new, layout=lay)
+    return B.finish(), ann_recentre_instances(root_old, lay["c"], root_new), info
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

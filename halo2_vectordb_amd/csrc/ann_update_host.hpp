@@ -100,6 +100,31 @@ static inline AnnmBlocks annm_blocks(uint64_t K, uint64_t n_c, uint64_t dim, uin
   return o;
 }
 
+// ------------------------------------------------------------------ the recentre of one cluster (include/vdb.h vdb_wit_ann_recentre)
+// behind the head, first stream cell of each block: I the assigned members n_c x dim (b_in), M as the mean audit has it (the constant
+// len at b_m, the qadd chain from b_chain, the dim qdiv blocks from b_div), MM merkle_commitment(members) (b_mm), U the update block
+// of the centroids' tree with one write (b_upd), G the sponge over [new centroids' root | cluster roots] (b_root).  Lookup cells are the
+// qdiv blocks' alone, word j's from j * qdiv_lk on.
+struct AnnrBlocks {
+  AnnHead h;
+  uint64_t b_in, b_m, b_chain, b_div, b_mm, b_upd, b_root, total, total_l;
+};
+static inline AnnrBlocks annr_blocks(uint64_t K, uint64_t n_c, uint64_t dim, uint64_t sponge_cells, uint64_t qdiv_cells, uint64_t qdiv_lk,
+                                     uint64_t mm_cells, uint64_t update_cells) {
+  AnnrBlocks o;
+  o.h = ann_head(K, sponge_cells);
+  o.b_in = o.h.end;
+  o.b_m = o.b_in + n_c * dim;
+  o.b_chain = o.b_m + 1;
+  o.b_div = o.b_chain + (n_c - 1) * dim * 4;
+  o.b_mm = o.b_div + dim * qdiv_cells;
+  o.b_upd = o.b_mm + mm_cells;
+  o.b_root = o.b_upd + update_cells;
+  o.total = o.b_root + sponge_cells;
+  o.total_l = dim * qdiv_lk;
+  return o;
+}
+
 // The members of a cluster stay dense: write j goes to a slot below the fill at its turn (a replacement) or exactly at it (an append,
 // which raises the fill by one).  n_c: the fill before the batch, glp: the padded leaf count of the grown tree.
 // -> 0 and *appends; 1: indices[*bad] lies above the fill at its turn; 2: it lies outside the grown tree

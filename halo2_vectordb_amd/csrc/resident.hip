@@ -378,6 +378,50 @@ int ann_index_apply_dev(const u256* grouped, const uint32_t* slots, const u256* 
   return VDB_OK;
 }
 
+// ------------------------------------------------------------------ the index after the recentre of one cluster (include/vdb.h
+// vdb_ann_index_recentre_dev; the circuit is witness.hip's).  Values only; the old buffers are only read.  Nothing of the members
+// changes: the grouped rows, the slots, the offsets and forest segments 0 .. K - 1 are copied device to device; segment K is the
+// centroids' tree as the witness call left it (`updated`), row c of the centroids is the new centroid, the centroids' root is
+// `updated`'s and the index root is hashed again: one launch (the sponge), no grouping, no forest level, no member leaf.
+int ann_index_recentre_dev(const u256* grouped, const uint32_t* slots, const uint64_t* offsets, const u256* forest, const u256* roots, const u256* centroids,
+                           const uint64_t* sizes, size_t K, size_t dim, size_t cluster, const u256* updated, const u256* new_centroid, u256* grouped_out,
+                           uint32_t* slots_out, uint64_t* offsets_out, u256* forest_out, u256* roots_out, u256* centroids_out) {
+  VDB_ARG(sizes, "null pointer");
+  VDB_ARG(K > 1 && K <= VDB_ANN_MAX_CLUSTERS && cluster < K, "K below 2 (a centroids' tree of one leaf has no path), K above VDB_ANN_MAX_CLUSTERS or cluster >= K");
+  VDB_ARG(dim > 0 && dim <= ((size_t)1 << 20), "dim outside [1, 2^20]");
+  uint64_t n = 0, seg_k = 0, lp_k;
+  uint32_t d;
+  for (size_t s = 0; s < K; s++) {
+    VDB_ARG(sizes[s] > 0 && sizes[s] <= VDB_ANN_MAX_VECTORS, "empty cluster or cluster too large");
+    uint64_t lp;
+    tree_shape(sizes[s], &lp, &d);
+    n += sizes[s];
+    seg_k += 2 * lp;
+  }
+  VDB_ARG(n <= VDB_ANN_MAX_VECTORS, "index too large: n at most VDB_ANN_MAX_VECTORS");
+  tree_shape(K, &lp_k, &d);
+  const PoseidonSpec* sp;
+  TRY(poseidon_spec_dev(&sp, nullptr));
+  hipStream_t s = ctx().stream;
+  MkShape mw;
+  mk_shape(1, K + 1, &mw);
+  u256* states = (u256*)scratch_get(0, ((size_t)mw.nperm * PSD_T + 8) * sizeof(u256));
+  if (!states) return VDB_ERR_OOM;
+  const auto d2d = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s); };
+  VDB_HIP(d2d(grouped_out, grouped, n * dim * sizeof(u256)));
+  VDB_HIP(d2d(slots_out, slots, n * sizeof(uint32_t)));
+  VDB_HIP(d2d(offsets_out, offsets, (K + 1) * sizeof(uint64_t)));
+  VDB_HIP(d2d(forest_out, forest, seg_k * sizeof(u256)));
+  VDB_HIP(d2d(forest_out + seg_k, updated, 2 * lp_k * sizeof(u256)));
+  VDB_HIP(d2d(centroids_out, centroids, K * dim * sizeof(u256)));
+  VDB_HIP(d2d(centroids_out + cluster * dim, new_centroid, dim * sizeof(u256)));
+  VDB_HIP(d2d(roots_out, updated + 2 * lp_k - 2, sizeof(u256)));
+  VDB_HIP(d2d(roots_out + 1, roots + 1, K * sizeof(u256)));
+  TRY(mk_leaf_states(sp, roots_out, 1u, (uint32_t)(K + 1), mw.nperm, states, roots_out + K + 1, nullptr));
+  VDB_HIP(hipStreamSynchronize(s));
+  return VDB_OK;
+}
+
 // ------------------------------------------------------------------ the index after a batch of deletes (include/vdb.h
 // vdb_ann_index_remove_dev; the batch's circuit is witness.hip's).  Values only; the old buffers are only read.
 // A removal compacts the database: the result is the fresh build over its own grouped rows taken as the database, so every grouped
@@ -562,6 +606,19 @@ int vdb_ann_index_apply_dev(const vdb_fr* grouped_dev, const uint32_t* slots_dev
   return ann_index_apply_dev(as_u256(grouped_dev), slots_dev, as_u256(forest_dev), as_u256(roots_dev), cluster_sizes, K, dim, cluster, grow,
                              as_u256(updated_levels_dev), as_u256(new_vectors_dev), indices, db_slots, m, as_u256(grouped_out_dev), slots_out_dev,
                              offsets_out_dev, as_u256(forest_out_dev), as_u256(roots_out_dev));
+}
+
+int vdb_ann_index_recentre_dev(const vdb_fr* grouped_dev, const uint32_t* slots_dev, const uint64_t* offsets_dev, const vdb_fr* forest_dev,
+                               const vdb_fr* roots_dev, const vdb_fr* centroids_dev, const uint64_t* cluster_sizes, size_t K, size_t dim, size_t cluster,
+                               const vdb_fr* updated_levels_dev, const vdb_fr* new_centroid_dev, vdb_fr* grouped_out_dev, uint32_t* slots_out_dev,
+                               uint64_t* offsets_out_dev, vdb_fr* forest_out_dev, vdb_fr* roots_out_dev, vdb_fr* centroids_out_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(grouped_dev && slots_dev && offsets_dev && forest_dev && roots_dev && centroids_dev && updated_levels_dev && new_centroid_dev && grouped_out_dev &&
+              slots_out_dev && offsets_out_dev && forest_out_dev && roots_out_dev && centroids_out_dev,
+          "null pointer");
+  return ann_index_recentre_dev(as_u256(grouped_dev), slots_dev, offsets_dev, as_u256(forest_dev), as_u256(roots_dev), as_u256(centroids_dev), cluster_sizes, K,
+                                dim, cluster, as_u256(updated_levels_dev), as_u256(new_centroid_dev), as_u256(grouped_out_dev), slots_out_dev, offsets_out_dev,
+                                as_u256(forest_out_dev), as_u256(roots_out_dev), as_u256(centroids_out_dev));
 }
 
 int vdb_ann_index_remove_size(const uint64_t* cluster_sizes, size_t K, size_t cluster, const uint64_t* slots, size_t m, unsigned* shrink, uint64_t* digests,

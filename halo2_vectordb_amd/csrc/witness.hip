@@ -987,6 +987,16 @@ __global__ __launch_bounds__(64) void k_annm_div(Streams st, const FpTables* __r
   qdiv_sliced(st, T, div + (uint64_t)j * T->sz.qdiv[0], (uint64_t)j * T->sz.qdiv[1], live, [&] { return sums[j]; }, [&] { return len; },
               [&](const u256& r) { mean_ok[j] = u256_eq(r, own[j]) ? 1 : 0; });
 }
+// k_annm_div's sibling of the recentre (include/vdb.h vdb_wit_ann_recentre): the same cells, and the quotient itself kept as a value in
+// mean[j] — the new centroid's word j, which the update block of the centroids' tree absorbs — where the audit compares it with own_j
+__global__ __launch_bounds__(64) void k_annr_div(Streams st, const FpTables* __restrict__ T, uint64_t div, uint32_t dim, const u256* __restrict__ sums,
+                                                 u256 len, u256* __restrict__ mean) {
+  uint32_t j = blockIdx.x * 64 + threadIdx.x;
+  const bool live = j < dim;
+  if (!live) j = dim - 1;
+  qdiv_sliced(st, T, div + (uint64_t)j * T->sz.qdiv[0], (uint64_t)j * T->sz.qdiv[1], live, [&] { return sums[j]; }, [&] { return len; },
+              [&](const u256& r) { mean[j] = r; });
+}
 // The means of all K clusters of a resident index as values alone (include/vdb.h vdb_ann_cluster_means_dev): per cluster k and word j
 // qdiv(sum_i member_i[j], quantization(n_k)), the k-means tail's arithmetic with no filter in front.  fr_add is exact and associative, so
 // the serial walk gives the bits of the circuit's qadd chain; the quotient is the value form fp_qdiv takes under an empty window.  Grid
@@ -2106,6 +2116,13 @@ struct AnnFrame {
     VDB_LAUNCH(k_annu_new_roots, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, b.b_new, K, new_root, hdr + 1, ind, words_new);
     return sponge(words_new, b.b_root, st_new, iroot + 1);
   }
+  // the closing of a circuit that replaces word 0 and carries the K cluster roots over (the recentre): no block F, words_new =
+  // [new centroids' root | the header's cluster roots], then G at b_root
+  int close_word0(uint64_t b_root, const u256* new_croot) {
+    VDB_HIP(hipMemcpyAsync(words_new, new_croot, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
+    VDB_HIP(hipMemcpyAsync(words_new + 1, hdr + 2, K * sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
+    return sponge(words_new, b_root, st_new, iroot + 1);
+  }
   // blocks D and G: the sponge over K + 1 words at `base`, its digest to *root
   int sponge(const u256* words, uint64_t base, u256* states, u256* root) {
     const uint32_t nperm = mw->nperm;
@@ -2363,6 +2380,61 @@ int wit_ann_mean_dev(FpEntry* fp, const u256* centroids, const u256* members, co
   VDB_LAUNCH(k_annm_sum, dim3((unsigned)dim), dim3(64), f.st, fp->dev, b.b_chain, (uint32_t)n_c, (uint32_t)dim, members, sums);
   VDB_LAUNCH(k_annm_div, dim3((unsigned)((dim + 63) / 64), 8), dim3(64), f.st, fp->dev, b.b_div, (uint32_t)dim, sums, len, own, mean_ok);
   return cf.finish(levels_c, levels_m, pub);
+}
+
+// ------------------------------------------------------------------ the recentre of one cluster (include/vdb.h vdb_wit_ann_recentre):
+// the index under index_root_new has the K cluster roots of the index under index_root_old, and its centroids' tree is the old one with
+// leaf c replaced by the leaf of qdiv(sum of the members committed under cluster_root_c, quantization(n_c)).  Blocks: A - D the frame's
+// head; I the members assigned; M the mean audit's (len, the qadd chains, one qdiv per word -> mean_j); MM merkle_commitment(members),
+// tied to picked; U the update block of the centroids' tree with the one write (idx tied to c, its new vector to mean_j, its old root
+// to the header's centroids_root); G the sponge over [U's new root | the header's cluster roots].  The old centroid is never assigned.
+struct AnnrLayout {
+  MkLayout mw, mm;
+  MkuLayout mu;
+  AnnrBlocks b;
+};
+// the refusals, in the frame's order (the mean audit's and mku_layout's between the frame's), and where the blocks start
+static int annr_layout(FpEntry* fp, size_t K, size_t cluster, size_t n_c, size_t dim, AnnrLayout* o) {
+  AnnuBlocks frame;   // F and G over no block at all: asked for the cell limit alone
+  TRY(ann_frame_layout(K, cluster, n_c, &o->mw, &frame, [&](uint64_t*, uint64_t*) -> int {
+    VDB_ARG(n_c > 0 && dim > 0 && dim <= ((size_t)1 << 20), "empty cluster, dim = 0 or dim above 2^20");
+    VDB_ARG(n_c <= (size_t)VDB_NEAREST_TOPK_MAX_INSTANCES / dim, "recentre too large: n_c * dim at most VDB_NEAREST_TOPK_MAX_INSTANCES");
+    VDB_ARG(fp->host.P >= 63 || n_c < ((uint64_t)1 << fp->host.P), "n_c not below 2^P: quantization(n_c) would not pass qdiv's divisor bound 2^(2P)");
+    return mku_layout(K, dim, 1, nullptr, 0, &o->mu, nullptr, nullptr, nullptr);   // K = 1: a centroids' tree of one leaf has no path
+  }));
+  mk_layout(n_c, dim, 0, &o->mm);
+  o->b = annr_blocks(K, n_c, dim, o->mw.total, fp->host.sz.qdiv[0], fp->host.sz.qdiv[1], o->mm.total, o->mu.total);
+  VDB_ARG(o->b.total <= VDB_NEAREST_TOPK_MAX_CELLS, "recentre circuit above 2^34 cells");
+  return VDB_OK;
+}
+// levels: the centroids' tree (2 lp_K digests, a copy the caller owns), left in the state after the write; roots: [centroids_root | the K
+// cluster roots]; levels_m: cluster c's tree where it is resident, or null; new_centroid: dim words out; pub: [index_root_old | c |
+// index_root_new].  The quotients and the chain totals live in the frame's work space (`extra`, scratch slot 7).  Scratch slot 0 has
+// one user at a time: M asks for nothing there; mk_emit (MM) takes it first and every launch that reads what it put there is enqueued
+// before mku_emit (U) takes it again (the stream orders them); G's states are the frame's own.
+int wit_ann_recentre_dev(FpEntry* fp, u256* levels, const u256* members, const u256* roots, const u256* levels_m, size_t K, size_t cluster, size_t n_c,
+                         size_t dim, Streams st, u256* new_centroid, u256* pub) {
+  static thread_local MkuPlan pl;
+  AnnrLayout a;
+  TRY(annr_layout(fp, K, cluster, n_c, dim, &a));
+  const AnnrBlocks& b = a.b;
+  const uint64_t slot = cluster;
+  TRY(mku_plan(K, dim, 0, new_centroid, &slot, nullptr, 1, &pl));   // (the plan only asks that a write has a vector: the quotients, below)
+  AnnFrame f;
+  TRY(f.open(st, roots, K, cluster, b.h, a.mw, b.total, 5, 2 * dim));
+  TRY(set_winv(f.st, fp->dev));   // the head's gadgets are GateChip's alone; M reads the tables of (P, L)
+  u256 *mean = f.extra, *sums = mean + dim;
+  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)((n_c * dim + 255) / 256)), dim3(256), f.st, b.b_in, members, members, (uint64_t)(n_c * dim), (uint64_t)(n_c * dim));
+  const u256 len = fr_mul(to_mont<Fr>(u256_from_u64(n_c)), fp->host.scale);   // load_constant(quantization(n_c))
+  VDB_LAUNCH(k_push_cells, dim3(1), dim3(1), f.st, b.b_m, len, len, 1u);
+  VDB_LAUNCH(k_annm_sum, dim3((unsigned)dim), dim3(64), f.st, fp->dev, b.b_chain, (uint32_t)n_c, (uint32_t)dim, members, sums);
+  VDB_LAUNCH(k_annr_div, dim3((unsigned)((dim + 63) / 64), 8), dim3(64), f.st, fp->dev, b.b_div, (uint32_t)dim, sums, len, mean);
+  TRY(mk_emit(fp, f.sp, members, n_c, dim, a.mm, f.st, b.b_mm, levels_m, nullptr));
+  TRY(mku_emit(fp, f.sp, pl, levels, dim, mean, f.st, b.b_upd, f.upub));
+  TRY(f.close_word0(b.b_root, f.upub + 4));
+  VDB_LAUNCH(k_annu_public, dim3(1), dim3(256), f.upub, f.hdr, f.iroot, 0u, pub);
+  VDB_HIP(hipMemcpyAsync(new_centroid, mean, dim * sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
+  return inv_list_fixup(f.st);
 }
 
 // the means of all K clusters as values alone (include/vdb.h vdb_ann_cluster_means_dev); `offsets`: the host's copy, already checked
@@ -3085,6 +3157,59 @@ int vdb_wit_ann_mean(uint32_t P, uint32_t L, const vdb_fr* centroids, const vdb_
     return wit_ann_mean_dev(fp, dc, dm, dr, nullptr, nullptr, K, cluster, n_c, dim, st, mean_ok, dpub);
   };
   return ann_cluster_host(centroids, members, roots, K, n_c, dim, a.b.f.total, a.b.total_l, dim, stream_out, lookup_out, selector_out, mean_ok_out, public_out, run);
+}
+
+// the recentre of one cluster (include/vdb.h)
+int vdb_wit_ann_recentre_size(uint32_t P, uint32_t L, size_t K, size_t n_c, size_t dim, uint64_t* cells, uint64_t* lookups, uint64_t* input_cells,
+                              uint64_t* update_base) {
+  VDB_REQUIRE_INIT();
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  AnnrLayout a;
+  TRY(annr_layout(fp, K, 0, n_c, dim, &a));
+  if (cells) *cells = a.b.total;
+  if (lookups) *lookups = a.b.total_l;
+  if (input_cells) *input_cells = a.b.h.n_in;
+  if (update_base) *update_base = a.b.b_upd;
+  return VDB_OK;
+}
+int vdb_wit_ann_recentre_dev(uint32_t P, uint32_t L, vdb_fr* centroid_levels_dev, const vdb_fr* members_dev, const vdb_fr* roots_dev,
+                             const vdb_fr* member_levels_dev, size_t K, size_t cluster, size_t n_c, size_t dim, vdb_fr* stream_dev, vdb_fr* lookup_dev,
+                             uint8_t* selector_dev, vdb_fr* new_centroid_dev, vdb_fr* public_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(centroid_levels_dev && members_dev && roots_dev && stream_dev && lookup_dev && new_centroid_dev && public_dev, "null pointer");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  DevStreams ds;
+  TRY(ds.init(stream_dev, selector_dev, lookup_dev));
+  TRY(wit_ann_recentre_dev(fp, as_u256(centroid_levels_dev), as_u256(members_dev), as_u256(roots_dev), member_levels_dev ? as_u256(member_levels_dev) : nullptr, K,
+                           cluster, n_c, dim, ds.st, as_u256(new_centroid_dev), as_u256(public_dev)));
+  return ds.finish();
+}
+int vdb_wit_ann_recentre(uint32_t P, uint32_t L, vdb_fr* centroid_levels, const vdb_fr* members, const vdb_fr* roots, size_t K, size_t cluster, size_t n_c,
+                         size_t dim, vdb_fr* stream_out, vdb_fr* lookup_out, uint8_t* selector_out, vdb_fr* new_centroid_out, vdb_fr* public_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(centroid_levels && members && roots && new_centroid_out && public_out, "null pointer");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  AnnrLayout a;
+  TRY(annr_layout(fp, K, cluster, n_c, dim, &a));
+  uint64_t lp;
+  uint32_t d;
+  tree_shape(K, &lp, &d);
+  DevBuf dl, dm, dr, dnew, dpub;
+  HostStreams hs;
+  TRY(upload(dl, centroid_levels, 2 * lp * sizeof(u256)));
+  TRY(upload(dm, members, n_c * dim * sizeof(u256)));
+  TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
+  TRY(dnew.alloc(dim * sizeof(u256)));
+  TRY(dpub.alloc(3 * sizeof(u256)));
+  TRY(hs.init(a.b.total, a.b.total_l, selector_out != nullptr));
+  TRY(wit_ann_recentre_dev(fp, dl.as<u256>(), dm.as<u256>(), dr.as<u256>(), nullptr, K, cluster, n_c, dim, hs.st, dnew.as<u256>(), dpub.as<u256>()));
+  TRY(download(new_centroid_out, dnew.p, dim * sizeof(u256)));
+  TRY(download(public_out, dpub.p, 3 * sizeof(u256)));
+  TRY(download(centroid_levels, dl.p, 2 * lp * sizeof(u256)));
+  return hs.finish(stream_out, lookup_out, selector_out, a.b.total, a.b.total_l);
 }
 
 // the means of all K clusters of a resident index, values only (include/vdb.h): no stream, no window

@@ -1360,11 +1360,33 @@ class AnnIndex:
     def recentred(self):
         """a new AnnIndex over the same rows and cluster ids whose centroids are means(): built from scratch by the index build, on
         buffers of its own; this index stays valid.  After writes and deletes have moved the members, the mean audit of every cluster
-        of the result is clean.  NOT proved: that the result's root descends from this index's — nothing links the two roots; a
-        verifier of a recentred index checks its K mean audits (and K routing audits) against the new root alone."""
+        of the result is clean.  This call proves nothing; that the result's root descends from this index's is proved one centroid at a
+        time: K proofs of AnnRecentreHotPath, c = 0 .. K - 1, each on recentred_with of the one before, move this index's root to the
+        result's root bit for bit."""
         if self.qvec.shape[0] != self.n:
             raise ValueError("the database has slots no cluster holds: recentre an index whose rows are dense")
         return AnnIndex(self.n, self.dim, self.K, self.qvec, self.cluster_ids, self.means(), P=self.P, L=self.L, metric=self.metric_name)
+
+    def recentred_with(self, hp):
+        """the index after the recentre of AnnRecentreHotPath `hp` (its witness has run: hp.d_levels holds the centroids' tree after the
+        write, hp.d_new the new centroid), as a new AnnIndex on buffers of its own (vdb_ann_index_recentre_dev: copies and one sponge, no
+        rebuild); this index stays valid.  Its index root is the proof's index_root_new."""
+        if hp.index is not self:
+            raise ValueError("the proof is of another index")
+        c, sizes64 = hp.cluster, np.ascontiguousarray(self.sizes, dtype=np.uint64)
+        qcent = self.qcent.copy()
+        qcent[c] = hp.d_new.download((self.dim, 4))
+        ix = AnnIndex.from_resident(self.dim, self.K, self.sizes, self.n_digests, self.segments, qcent, self.qvec, self.cluster_ids, P=self.P, L=self.L,
+                                    metric=self.metric_name)
+        try:
+            check(self.lib.vdb_ann_index_recentre_dev(self.d_grouped.ptr, self.d_slots.ptr, self.d_offsets.ptr, self.d_forest.ptr, self.d_roots.ptr,
+                                                      self.d_cent.ptr, api._p(sizes64), self.K, self.dim, c,
+                                                      hp.d_levels.ptr, hp.d_new.ptr, ix.d_grouped.ptr, ix.d_slots.ptr, ix.d_offsets.ptr, ix.d_forest.ptr,
+                                                      ix.d_roots.ptr, ix.d_cent.ptr))
+        except Exception:
+            ix.free()
+            raise
+        return ix
 
     def free(self):
         for b in self._bufs:
@@ -1710,8 +1732,8 @@ class AnnMeanHotPath(_AnnClusterHotPath):
     indicators) -> own word by word, the constant quantization(n_c), the qadd chain over the members and one qdiv per word tied to own,
     merkle_commitment(centroids) tied to the header's centroids' root and merkle_commitment(members) tied to picked.  Public:
     [index_root | c].  K mean proofs and K routing audits (AnnAuditHotPath) state that the index is a fixed point of one Lloyd step over
-    the committed members.  Not proved: that the database is complete; that a recentred index (AnnIndex.recentred) descends from its
-    predecessor.  The shape depends on (K, n_c, dim): one proving key per cluster size.  A centroid that is not the mean still gives a
+    the committed members.  Not proved: that the database is complete.  That a recentred index descends from its predecessor is a
+    proof of its own, one centroid at a time (AnnRecentreHotPath).  The shape depends on (K, n_c, dim): one proving key per cluster size.  A centroid that is not the mean still gives a
     witness; results()[2] flags the words that differ and their copies fail in the Mock report.  `centroids` / `members`: quantized
     overrides of what the index holds (tests of the binding); with them the two trees are hashed by the call instead of read from the
     forest."""
@@ -1729,3 +1751,80 @@ class AnnMeanHotPath(_AnnClusterHotPath):
 
     def _builder(self, CS):
         return CS.build_ann_mean, ()
+
+
+class AnnRecentreHotPath(HotPath):
+    """The recentre of ONE cluster c of a committed AnnIndex proved from the old index root to the new one (include/vdb.h
+    vdb_wit_ann_recentre): the index under index_root_new has the K cluster roots of the index under index_root_old, and its centroids'
+    tree is the old one with leaf c replaced by the leaf of qdiv(sum of the members committed under cluster_root_c, quantization(n_c)),
+    word for word the quotient AnnMeanHotPath accepts.  Assigned: the header [c | centroids' root | cluster roots]; then
+    idx_to_indicator(c, K), select_by_indicator(cluster roots, indicators) -> picked, the sponge over the roots (index_root_old), the
+    members assigned, the constant quantization(n_c), the qadd chain over the members and one qdiv per word, merkle_commitment(members)
+    tied to picked, UpdateHotPath's circuit with one write on the centroids' tree — its old root tied to the header's centroids' root,
+    its index to c, its new vector to the quotients — and the sponge over [the new centroids' root | cluster roots] (index_root_new).
+    Public: [index_root_old | c | index_root_new].  K such proofs, one per cluster, recentre an index: the memberships do not change
+    between them, so the chain ends on the root of AnnIndex.recentred().  The old centroid is never assigned.  Not proved: that the
+    database is complete; that the members are still routed to their cluster after the recentre (the routing audits of the new root say
+    which are not; a delete from one cluster and a write into another moves them).  The shape depends on (K, n_c, dim): one proving key
+    per cluster size.  `d_levels` holds the centroids' tree after the write and `d_new` the new centroid; AnnIndex.recentred_with(hp)
+    gives the next index.  `members` / `levels`: quantized overrides of the cluster's members and of the centroids' tree (tests of the
+    binding); with `members` the cluster's tree is hashed by the call instead of read from the forest."""
+
+    def __init__(self, index, cluster, k=13, P=48, L=12, tau=None, col_shard=(0, 1), blind_seed=None, params=None, members=None, levels=None):
+        n_c = _bind_cluster(self, index, cluster)
+        if self.K < 2:
+            raise ValueError("a tree of one leaf has no path: an index of one cluster has no centroid to open")
+        super().__init__(n_c, index.dim, k, P, L, seed=None, tau=tau, col_shard=col_shard, vectors=np.zeros((0, index.dim)), blind_seed=blind_seed,
+                         params=params)
+        self.lp, self.depth = api.merkle_levels(self.K)
+        self.given_members, self.given_levels = members, levels
+
+    def n_input_rows(self):
+        return 0
+
+    def _load_inputs(self):
+        super()._load_inputs()
+        ix, self.resident = self.index, self.given_members is None
+        self.p_members = _given_ptr(self, self.given_members, (self.n, self.dim, 4), ix.members_ptr(self.cluster))
+        self.d_levels0, self.d_levels = self._output(2 * self.lp * B), self._output(2 * self.lp * B)
+        if self.given_levels is None:
+            check(self.lib.vdb_memcpy_d2d(self.d_levels0.ptr, ix.levels_ptr(self.K), ctypes.c_size_t(2 * self.lp * B)))
+        else:
+            lv = np.ascontiguousarray(self.given_levels, dtype=np.uint64)
+            assert lv.shape == (2 * self.lp, 4), "the tree does not belong to this shape"
+            self.d_levels0.upload(lv)
+
+    def _circuit_size(self):
+        cells, lk, n_in, ub = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(self.lib.vdb_wit_ann_recentre_size(self.P, self.L, self.K, self.n, self.dim, ctypes.byref(cells), ctypes.byref(lk), ctypes.byref(n_in),
+                                                 ctypes.byref(ub)))
+        self.update_base = ub.value
+        return n_in.value, cells.value - n_in.value, lk.value
+
+    def _alloc_outputs(self):
+        self.d_new, self.d_pub = self._output(max(self.dim * B, 32)), self._output(3 * B)
+
+    def _witness(self, sel=None):
+        # the call writes the assigned header and members too; every run starts from the centroids' tree before the write
+        ix = self.index
+        check(self.lib.vdb_memcpy_d2d(self.d_levels.ptr, self.d_levels0.ptr, ctypes.c_size_t(2 * self.lp * B)))
+        with self._window(sel, 0):
+            check(self.lib.vdb_wit_ann_recentre_dev(self.P, self.L, self.d_levels.ptr, self.p_members, ix.d_roots.ptr,
+                                                    ix.levels_ptr(self.cluster) if self.resident else None, self.K, self.cluster, self.n, self.dim,
+                                                    self.d_stream.ptr, self.d_lookup.ptr, self._sel_at(sel, 0), self.d_new.ptr, self.d_pub.ptr))
+
+    def public_values_dev(self):
+        return self.d_pub.ptr, 3
+
+    def results(self):
+        """(index_root_old (4,), c (4,), index_root_new (4,), the new centroid (dim, 4))"""
+        pub = self.d_pub.download((3, 4))
+        return pub[0], pub[1], pub[2], self.d_new.download((self.dim, 4))
+
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        cm, public, _ = CS.build_ann_recentre(self.K, self.n, self.dim, self.P, self.L, functools.partial(self._fetch_flags, d_flags), self._fetch,
+                                              builder=DeviceBuilder if on_device else None)
+        assert cm.n_cells == self.n_cells
+        return cm, public, None

@@ -574,6 +574,50 @@ int vdb_wit_ann_mean_dev(uint32_t precision_bits, uint32_t lookup_bits, const vd
                          size_t n_c, size_t dim, vdb_fr *stream_dev, vdb_fr *lookup_dev, uint8_t *selector_dev, uint8_t *mean_ok_dev,
                          vdb_fr *public_dev);
 
+/* The recentre of ONE cluster c, proved from the old index root to the new one (pipeline.AnnRecentreHotPath): the index under
+ * index_root_new has the K cluster roots of the index under index_root_old, and its centroids' tree is the old one with leaf c replaced
+ * by the leaf of the vector qdiv(sum of the members committed under cluster_root_c, quantization(n_c)), word for word the quotient
+ * vdb_wit_ann_mean accepts.  K such proofs, c = 0 .. K - 1, recentre an index: the memberships do not change between them, so the chain
+ * ends on the root of the index built on vdb_ann_cluster_means.  The old centroid c is never assigned: it is the opaque old leaf of
+ * the path.  Blocks in stream order:
+ *   A - D  the head of vdb_wit_ann_update: header [c | centroids_root | cluster roots], indicators, picked, sponge -> index_root_old
+ *   I      assigned members n_c x dim
+ *   M      vdb_wit_ann_mean's block M cell for cell: len = load_constant(quantization(n_c)), the qadd chains, one qdiv per word -> mean_j
+ *   MM     mroot = merkle_commitment(members) (its padding loads the zero cell: nothing before it has)
+ *   U      vdb_wit_merkle_update_ops' block at its base over the centroids' tree (n = K, depth = ceil(log2 K)): one write, no growth
+ *   G      the sponge over [U's new root | the header's cluster roots] -> index_root_new
+ * Copies (no cell): U's old root copies the header's centroids_root, U's idx copies c, U's assigned new-vector word j copies mean_j
+ * (the last cell of quotient j), mroot copies picked, G's word 0 copies U's new root and its words 1 .. K the header's cluster roots.
+ * Lookup cells are the qdiv blocks' alone, word j's from j * (qdiv's lookup cells) on.  public, 3 values:
+ * [index_root_old | c | index_root_new].  The shape depends on (K, n_c, dim): n_c enters as a constant; c is a witness.
+ * centroid_levels: the centroids' tree, 2 lp_K digests (vdb_merkle_tree_build_dev's layout, forest segment K), a copy the caller owns:
+ * the call leaves it in the state after the write.  roots: [centroids_root | K cluster roots].  member_levels_dev: cluster c's tree where
+ * it is resident (then the launch list does not depend on n_c, and on K only through one kernel per level of U), or NULL.
+ * new_centroid: dim words out.  The _dev form honours vdb_wit_set_window; new_centroid, centroid_levels and public are whole in every
+ * window.  VDB_ERR_ARG before anything is launched: K == 1 (a centroids' tree of one leaf has no path), K == 0,
+ * K > VDB_ANN_MAX_CLUSTERS, cluster >= K, n_c > VDB_ANN_MAX_VECTORS, n_c == 0, dim == 0, dim > 2^20, n_c * dim above
+ * VDB_NEAREST_TOPK_MAX_INSTANCES, n_c >= 2^precision_bits, more than 2^34 cells.  _size takes no cluster; each of its outputs may be
+ * NULL (update_base: the first cell of U). */
+int vdb_wit_ann_recentre_size(uint32_t precision_bits, uint32_t lookup_bits, size_t K, size_t n_c, size_t dim, uint64_t *cells, uint64_t *lookups,
+                              uint64_t *input_cells, uint64_t *update_base);
+int vdb_wit_ann_recentre(uint32_t precision_bits, uint32_t lookup_bits, vdb_fr *centroid_levels, const vdb_fr *members, const vdb_fr *roots, size_t K,
+                         size_t cluster, size_t n_c, size_t dim, vdb_fr *stream_out, vdb_fr *lookup_out, uint8_t *selector_out,
+                         vdb_fr *new_centroid_out, vdb_fr *public_out);
+int vdb_wit_ann_recentre_dev(uint32_t precision_bits, uint32_t lookup_bits, vdb_fr *centroid_levels_dev, const vdb_fr *members_dev,
+                             const vdb_fr *roots_dev, const vdb_fr *member_levels_dev, size_t K, size_t cluster, size_t n_c, size_t dim,
+                             vdb_fr *stream_dev, vdb_fr *lookup_dev, uint8_t *selector_dev, vdb_fr *new_centroid_dev, vdb_fr *public_dev);
+/* The index after that proof (values only, functional; the old buffers are only read), on buffers of its own and with no rebuild: the
+ * grouped rows, slots, offsets and forest segments 0 .. K - 1 are copied device to device, forest segment K is updated_levels_dev (what
+ * the witness call left in centroid_levels_dev), row c of the centroids is new_centroid_dev, the K + 2 roots are rewritten and the index
+ * root is hashed by one sponge launch.  cluster_sizes: K x uint64, a HOST array.  The result equals vdb_ann_index_build_dev over the
+ * same rows with row c of the centroids replaced, buffer for buffer.  VDB_ERR_ARG: K < 2, K > VDB_ANN_MAX_CLUSTERS, cluster >= K, dim
+ * outside [1, 2^20], an empty cluster, n above VDB_ANN_MAX_VECTORS. */
+int vdb_ann_index_recentre_dev(const vdb_fr *grouped_dev, const uint32_t *slots_dev, const uint64_t *offsets_dev, const vdb_fr *forest_dev,
+                               const vdb_fr *roots_dev, const vdb_fr *centroids_dev, const uint64_t *cluster_sizes, size_t K, size_t dim,
+                               size_t cluster, const vdb_fr *updated_levels_dev, const vdb_fr *new_centroid_dev, vdb_fr *grouped_out_dev,
+                               uint32_t *slots_out_dev, uint64_t *offsets_out_dev, vdb_fr *forest_out_dev, vdb_fr *roots_out_dev,
+                               vdb_fr *centroids_out_dev);
+
 /* The means of all K clusters of an index as vdb_ann_index_build_dev leaves it, values only: means[k][j] =
  * qdiv(sum_i member_i[j], quantization(n_k)) over the rows [offsets[k], offsets[k + 1]) of the grouped rows, bit for bit what
  * vdb_wit_ann_mean constrains (the sum is exact in the field, so its order does not matter; the quotient is qdiv's value).  A server

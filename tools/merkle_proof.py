@@ -34,7 +34,11 @@ with AnnIndex.assign, the circuit's own fixed-point rule; every member of cluste
 centroid c as to any other centroid; [index_root | c] public) and has the verifier check the proof.  Exit status 0 when it is accepted.
 `--circuit ann-mean --K C [--cluster c]` proves that centroid c of that index, recentred with AnnIndex.recentred (its centroids are then
 AnnIndex.means(), the circuit's own fixed-point means), is the mean of cluster c — default: the largest — (pipeline.AnnMeanHotPath;
-[index_root | c] public) and has the verifier check the proof.  Exit status 0 when it is accepted."""
+[index_root | c] public) and has the verifier check the proof.  Exit status 0 when it is accepted.
+`--circuit ann-recentre --K C [--cluster c]` proves the recentre of cluster c of that index — default: the largest — from the old index
+root to the new one (pipeline.AnnRecentreHotPath: the centroids' tree with leaf c replaced by the leaf of the members' mean, the cluster
+roots carried over; [index_root_old | c | index_root_new] public), has the verifier check the proof and recentres the resident index
+(AnnIndex.recentred_with), whose root must be the public index_root_new.  Exit status 0 when both hold."""
 import argparse
 import json
 import os
@@ -45,7 +49,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from halo2_vectordb_amd import api  # noqa: E402
-from halo2_vectordb_amd.pipeline import AnnAuditHotPath, AnnDeleteHotPath, AnnMeanHotPath, AnnIndex, AnnQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
+from halo2_vectordb_amd.pipeline import AnnAuditHotPath, AnnDeleteHotPath, AnnMeanHotPath, AnnRecentreHotPath, AnnIndex, AnnQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
 from halo2_vectordb_amd.rounds import ProverRounds, quotient_identity_holds  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -56,7 +60,7 @@ ap.add_argument("--seed", type=int, default=20260003)
 ap.add_argument("--block-cols", type=int, default=510)
 ap.add_argument("--ext-block-cols", type=int, default=None)
 ap.add_argument("--proofs", type=int, default=2)
-ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read", "ann", "ann-update", "ann-delete", "ann-audit", "ann-mean"])
+ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read", "ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre"])
 ap.add_argument("--lookup-bits", type=int, default=13)
 ap.add_argument("--metric", default="euclidean")
 ap.add_argument("--queries", type=int, default=1, help="--circuit query: queries proved against the one database in this proof")
@@ -67,7 +71,7 @@ ap.add_argument("--grow", type=int, default=None, help="--circuit update / ann-u
 ap.add_argument("--reads", type=int, default=8, help="--circuit read: slots opened in this proof")
 ap.add_argument("--leaf-only", action="store_true", help="--circuit read: reveal the leaf digests, not the vectors")
 ap.add_argument("--K", type=int, default=32, help="--circuit ann: clusters of the index")
-ap.add_argument("--cluster", type=int, default=None, help="--circuit ann-audit / ann-mean: the cluster audited (default: the largest)")
+ap.add_argument("--cluster", type=int, default=None, help="--circuit ann-audit / ann-mean / ann-recentre: the cluster audited or recentred (default: the largest)")
 ap.add_argument("--out", default=None, help="write the proof (io.write_snark) and the verifying key beside it")
 args = ap.parse_args()
 
@@ -89,7 +93,7 @@ elif args.circuit == "update":
         raise SystemExit("--deletes is between 0 and --updates, --grow is not negative")
     kinds = [0] * (args.updates - args.deletes) + [1] * args.deletes
     hp = UpdateHotPath(n=args.n, dim=args.dim, m=args.updates, k=args.k, seed=args.seed, kinds=kinds, grow=args.grow)
-elif args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit", "ann-mean"):
+elif args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre"):
     from halo2_vectordb_amd.pipeline import sift_like_vectors
     if not 1 <= args.K <= args.n:
         raise SystemExit("--K is between 1 and --n")
@@ -116,6 +120,11 @@ elif args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit", "ann-mean"
         built.free()
         c = int(np.argmax(index.sizes)) if args.cluster is None else args.cluster
         hp = AnnMeanHotPath(index, c, k=args.k, L=args.lookup_bits)
+    elif args.circuit == "ann-recentre":
+        if args.K < 2:
+            raise SystemExit("--K is at least 2: a centroids' tree of one leaf has no path")
+        c = int(np.argmax(index.sizes)) if args.cluster is None else args.cluster
+        hp = AnnRecentreHotPath(index, c, k=args.k, L=args.lookup_bits)
     elif args.circuit == "ann":
         hp = AnnQueryHotPath(index, query, k=args.k, L=args.lookup_bits, metric=args.metric)
     elif args.circuit == "ann-delete":
@@ -153,7 +162,8 @@ wall, host_ms, out = best
 T = {}
 pr.prove(None, timings=T)
 ok = quotient_identity_holds(pr, out["challenges"], out["evals"], out["instances"])
-root_at = 0 if args.circuit in ("read", "ann-audit", "ann-mean") else -1  # a read and the audits state the root first, the other circuits last
+# a read and the audits state the root first, the recentre its new root third, the other circuits last
+root_at = 0 if args.circuit in ("read", "ann-audit", "ann-mean") else 2 if args.circuit == "ann-recentre" else -1
 root = api.fr_to_canonical(np.asarray(hp.results() if args.circuit == "merkle" else hp.results()[root_at]).reshape(1, 4))[0]
 root_int = int(root[0]) | int(root[1]) << 64 | int(root[2]) << 128 | int(root[3]) << 192
 if args.out:
@@ -161,7 +171,7 @@ if args.out:
     write_snark(args.out, out["proof"], out["instances"])
     pr.save_verifying_key(args.out + ".vk.npz", opened=out["opened"])
 accepted = {}
-if args.circuit in ("read", "ann", "ann-update", "ann-delete", "ann-audit", "ann-mean"):
+if args.circuit in ("read", "ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre"):
     from halo2_vectordb_amd import verifier
     accepted = {"proof_accepted": bool(verifier.verify(out["proof"], out["instances"], verifier.VerifyingKey.from_prover(pr, out["opened"])))}
 if args.circuit == "ann-update":
@@ -172,6 +182,11 @@ if args.circuit == "ann-audit":
     accepted["members_routed"] = int(hp.results()[2].sum())
 if args.circuit == "ann-mean":
     accepted["words_at_the_mean"] = int(hp.results()[2].sum())
+if args.circuit == "ann-recentre":
+    index2 = index.recentred_with(hp)
+    accepted["recentred_root_is_public_root"] = bool(np.array_equal(index2.roots()[-1], hp.results()[2]))
+    accepted["root_moved"] = not np.array_equal(hp.results()[0], hp.results()[2])
+    index2.free()
 if args.circuit == "ann-delete":
     index2 = index.removed(hp)
     accepted["removed_index_root_is_the_public_new_root"] = bool(np.array_equal(index2.roots()[-1], hp.results()[-1]))
@@ -182,6 +197,7 @@ what = f"merkle_commitment {args.n}x{args.dim} k={args.k}" if args.circuit == "m
     f"ann query (K={args.K}, cluster {hp.cluster} of {hp.n} vectors, {args.metric}) against the index of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann" else \
     f"{args.updates} writes into cluster {hp.cluster} ({hp.n} members, tree grown {hp.grow} times) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-update" else \
     f"routing audit of cluster {hp.cluster} ({hp.n} members, {args.metric}) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann-audit" else \
+    f"recentre of cluster {hp.cluster} ({hp.n} members) from the old index root to the new (K={args.K}) of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann-recentre" else \
     f"mean audit of cluster {hp.cluster} ({hp.n} members) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann-mean" else \
     f"{args.deletes} deletes from cluster {hp.cluster} ({hp.n} members, tree halved {hp.shrink} times) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-delete" else \
     f"query circuit ({str(args.queries) + ' x ' if args.queries > 1 else ''}{'top-' + str(args.topk) + ' ' if args.topk > 1 else ''}nearest_vector {args.metric} + merkle_commitment) over {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}"
@@ -194,7 +210,9 @@ print(json.dumps({"workload": what + ": whole constraint map, public outputs in 
                   "block_cols": args.block_cols, "ext_cols_held": hp.ext_cols}))
 pr.free()
 hp.free()
-if args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit", "ann-mean"):
+if args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre"):
     index.free()
-if args.circuit in ("ann-audit", "ann-mean") and not accepted["proof_accepted"]:
+if args.circuit in ("ann-audit", "ann-mean", "ann-recentre") and not accepted["proof_accepted"]:
+    sys.exit(1)
+if args.circuit == "ann-recentre" and not accepted["recentred_root_is_public_root"]:
     sys.exit(1)
