@@ -14,6 +14,9 @@
 //  * k_msm_sort: one workgroup per column does a counting sort of the (digit -> table index) pairs
 //    entirely in LDS (histogram, scan, scatter) and cuts the sorted list into ranges of LCAP entries; bucket
 //    changes inside a range open new segments (one partial sum each), which removes the skew of witness columns.
+//    A scalar whose magnitude is a 32-bit value times 2^(c j0) — bits, limbs, and the fixed-point values of the circuits, small integers
+//    times 2^48, 2^96, ... — is decomposed once and revisited through an 8-byte record (msm_digits.hpp); only the rest are reduced again.
+//    Two workgroups share a CU (eight waves per SIMD).
 //    With wide windows (thousands of buckets, dense scalars) the scatter goes in two phases: entries to the 256 runs of coarse bins
 //    here, k_msm_scatter2 orders each bin in place through LDS — four-byte stores to 8,192 open runs per column do not merge in L2.
 //  * k_msm_accum: one thread per range (every lane does exactly LCAP mixed additions), XYZZ accumulator in VGPRs.
@@ -27,6 +30,7 @@
 #include "ec.hpp"
 #include "ec_l9.hpp"
 #include "limb9.hpp"
+#include "msm_digits.hpp"
 
 struct vdb_srs {
   uint32_t k;
@@ -79,45 +83,7 @@ __global__ __launch_bounds__(256) void k_srs_table(const Affine* __restrict__ ba
 }
 
 // ---------------------------------------------------------------- digit decomposition
-// canonical scalar -> (folded magnitude, sign)
-__device__ __forceinline__ bool fold_scalar(u256& s) {
-  // (r-1)/2
-  const uint32_t H[8] = {0xf8000000u, 0xa1f0fac9u, 0x3cdcb848u, 0x9419f424u, 0x40c0ac2eu, 0xdc2822dbu, 0x7098d014u, 0x18322739u};
-  u256 half;
-#pragma unroll
-  for (int i = 0; i < 8; i++) half.w[i] = H[i];
-  // s > half  <=>  !(half >= s)
-  if (!u256_geq(half, s)) {
-    u256 r = mod_p<Fr>(), t;
-    u256_sub(t, r, s);
-    s = t;
-    return true;
-  }
-  return false;
-}
-
-// signed window digits of a folded magnitude s (nb = its bit length): f(window, |digit|, negative)
-template <class F>
-__device__ __forceinline__ void emit_digits(u256 s, bool neg, uint32_t nb, uint32_t c, uint32_t W, F&& f, size_t idx = 0) {
-  uint32_t carry = 0;
-  const uint32_t half = 1u << (c - 1), full = 1u << c;
-  // witness scalars are mostly short: stop after the window that can still receive a carry
-  uint32_t wend = nb / c + 2;
-  if (wend > W) wend = W;
-  for (uint32_t j = 0; j < wend; j++) {
-    uint32_t d = (s.w[0] & (full - 1)) + carry;
-    s = u256_shr_small(s, c);
-    bool dneg = false;
-    if (d > half) {
-      d = full - d;
-      dneg = true;
-      carry = 1;
-    } else {
-      carry = 0;
-    }
-    if (d) f(j, d, neg != dneg, idx);
-  }
-}
+// fold_scalar, emit_digits, emit_digits32 and the short-scalar record: msm_digits.hpp
 template <class F>
 __device__ __forceinline__ void for_each_digit(const u256& mont_scalar, uint32_t c, uint32_t W, F&& f) {
   if (u256_is_zero(mont_scalar)) return;  // Montgomery form of zero is zero: skip the product for the ~1/3 zero cells
@@ -125,36 +91,19 @@ __device__ __forceinline__ void for_each_digit(const u256& mont_scalar, uint32_t
   bool neg = fold_scalar(s);
   emit_digits(s, neg, u256_bits(s), c, W, [&](uint32_t j, uint32_t d, bool ng, size_t) { f(j, d, ng); });
 }
-// same for a magnitude below 2^32
-template <class F>
-__device__ __forceinline__ void emit_digits32(uint32_t mag, bool neg, uint32_t nb, uint32_t c, uint32_t W, F&& f, size_t idx) {
-  uint32_t carry = 0;
-  const uint32_t half = 1u << (c - 1), full = 1u << c;
-  uint32_t wend = nb / c + 2;
-  if (wend > W) wend = W;
-  for (uint32_t j = 0; j < wend; j++) {
-    uint32_t d = (mag & (full - 1)) + carry;
-    mag >>= c;
-    bool dneg = false;
-    if (d > half) {
-      d = full - d;
-      dneg = true;
-      carry = 1;
-    } else {
-      carry = 0;
-    }
-    if (d) f(j, d, neg != dneg, idx);
-  }
-}
 // Two-speed, two-pass walk over a column's scalars (the counting sort visits them twice: histogram, then scatter).
-// Every lane of a wavefront pays for the longest path among its 64 scalars, and witness columns mix a majority of short
-// values (bits, 15-bit limbs) with ~100-bit fixed-point values.  First visit (`first`): the Montgomery reduction, sign
-// fold and bit length are computed once; a short scalar (magnitude below 2^32 and at most three windows) leaves an
-// 8-byte record {magnitude, sign, length} and is processed from registers; a long one is appended to a queue
-// (wavefront-aggregated) and all long ones are then processed densely, every lane holding one.  Second visit: the short
-// scalars come straight from their records (no 32-byte load, no field arithmetic), the long ones from the queue.
-// `queue`, `rec`: n entries of this column each.
-#define MSM_REC_VALID (1ull << 63)
+// Every lane of a wavefront pays for the longest path among its 64 scalars, and witness columns mix bits and 15-bit limbs with
+// fixed-point values: small integers times 2^48, 2^96, ..., long by bit length but two or three windows wide.  First visit
+// (`first`): the Montgomery reduction, the sign fold, the bit length and the first window j0 that holds a bit are computed once.
+// A scalar whose magnitude is s' * 2^(c * j0) with s' below 2^32 and at most three windows wide is short: it leaves an 8-byte record
+// {s', sign, j0, length of s'} (msm_digits.hpp) and is processed from registers.  Any other is long: it is appended to a queue
+// (wavefront-aggregated), and all long ones are then processed densely, every lane holding one, with the full 256-bit walk.
+// Second visit: the short scalars come straight from their records (no 32-byte load, no field arithmetic), the long ones from the
+// queue.  `queue`, `rec`: n entries of this column each.
+// The digits of a short scalar are those of the full walk over s: the windows below j0 are all zero and send no carry up; from
+// window j0 on the signed recoding reads s' alone; and the full walk stops at min(nb / c + 2, W), which is
+// j0 + min(nb' / c + 2, W - j0) because nb = nb' + c * j0.  So emit_digits32(s', ..., W - j0) with its window j handed on as j + j0
+// meets the same (window, digit, sign) triples (tests/test_msm_digits_cpu.py holds both walks to big integers).
 // `sc` (a materialised column) or `cs` (a column still lying in the witness stream, see ColSrc) supplies the scalars.
 template <class F>
 __device__ __forceinline__ void walk_scalars(const u256* __restrict__ sc, const ColSrc* __restrict__ cs, uint32_t n_blind, const uint8_t* __restrict__ mk,
@@ -177,7 +126,7 @@ __device__ __forceinline__ void walk_scalars(const u256* __restrict__ sc, const 
     }
     return;
   }
-  const uint32_t short_bits = 3 * c - 1 < 32 ? 3 * c - 1 : 32;
+  const uint32_t short_bits = msm_short_bits(c), inv_c = msm_recip16(c);
   if (first) {
     if (tid == 0) *s_qcnt = 0;
     __syncthreads();
@@ -196,7 +145,8 @@ __device__ __forceinline__ void walk_scalars(const u256* __restrict__ sc, const 
         neg = fold_scalar(s);
         nb = u256_bits(s);
       }
-      const bool is_long = live && nb > short_bits;
+      uint32_t mag = 0, nbs = 0, j0 = 0;
+      const bool is_long = live && !msm_classify(s, nb, c, inv_c, short_bits, mag, nbs, j0);
       const unsigned long long m = __ballot(is_long);
       if (m) {
         uint32_t base = 0;
@@ -205,14 +155,17 @@ __device__ __forceinline__ void walk_scalars(const u256* __restrict__ sc, const 
         if (is_long) queue[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)i;
       }
       const bool is_short = live && !is_long;
-      if (i < n) rec[i] = is_short ? (MSM_REC_VALID | ((unsigned long long)nb << 40) | ((unsigned long long)(neg ? 1 : 0) << 32) | s.w[0]) : 0ull;
-      if (is_short) emit_digits32(s.w[0], neg, nb, c, W, f, i);
+      if (i < n) rec[i] = is_short ? msm_rec_encode(mag, neg, nbs, j0) : 0ull;
+      if (is_short) emit_digits_short(mag, neg, nbs, j0, c, W, f, i);
     }
   } else {
     for (size_t i0 = 0; i0 < n; i0 += MSM_SORT_THREADS) {
       const size_t i = i0 + tid;
       const unsigned long long r = i < n ? rec[i] : 0ull;
-      if (r & MSM_REC_VALID) emit_digits32((uint32_t)r, ((r >> 32) & 1) != 0, (uint32_t)(r >> 40) & 0xffu, c, W, f, i);
+      if (r & MSM_REC_VALID) {
+        const MsmRec sr = msm_rec_decode(r);
+        emit_digits_short(sr.mag, sr.neg, sr.nbs, sr.j0, c, W, f, i);
+      }
     }
   }
   __syncthreads();  // queue complete (written and read by this workgroup only)
@@ -271,7 +224,12 @@ __global__ __launch_bounds__(256) void k_msm_count_entries(const u256* __restric
 }
 
 // One workgroup per column: counting sort of (bucket -> table index|sign), segment numbering and range cutting.
-__global__ __launch_bounds__(MSM_SORT_THREADS) void k_msm_sort(const u256* __restrict__ scalars, const ColSrc* __restrict__ srcs, uint32_t n_blind, size_t n,
+// Eight waves per SIMD (the second launch bound): the kernel waits — on its loads, its LDS atomics and its barriers — far more
+// than it issues, and a 1,024-thread workgroup is four waves on every SIMD, so a CU takes a second workgroup only when all eight wave
+// slots are usable.  Left alone the compiler took 106 scalar registers, which allows seven; held to eight it keeps 78 and parks 24 in
+// vector lanes, no scratch.  With the 11-bit windows' 12 KB of LDS two columns then share a CU and fill each other's waits
+// (15.3 -> 12.8 ms per k = 16 step, profiles/NOTES.md); the wide windows' histograms leave room for one workgroup as before.
+__global__ __launch_bounds__(MSM_SORT_THREADS, 8) void k_msm_sort(const u256* __restrict__ scalars, const ColSrc* __restrict__ srcs, uint32_t n_blind, size_t n,
                                                                size_t table_n, uint32_t c, uint32_t W,
                                                                uint32_t* __restrict__ entries, size_t ent_cap,
                                                                uint32_t* __restrict__ seg_off, uint32_t* __restrict__ bucket_off, MsmRange* __restrict__ ranges,
