@@ -50,7 +50,6 @@ struct Context {
   std::map<uint64_t, void*> fp_tables;   // witness.hip: FixedPointChip tables keyed by (P, L)
   void* poseidon_spec = nullptr;          // poseidon.hip: device copy of the Poseidon spec
   void* poseidon_empty = nullptr;         // poseidon.hip: digests of the empty subtrees of every height (poseidon_empty_subtrees_dev)
-  bool ntt_lds_raised = false;            // ntt.hip: hipFuncAttributeMaxDynamicSharedMemorySize raised on this device
   uint64_t win[4] = {0, ~0ull, 0, ~0ull}; // witness.hip: rank window of the *_dev witness entry points (vdb_wit_set_window)
 };
 
@@ -173,10 +172,5 @@ u256 host_root_of_unity(uint32_t k);  // ROOT_OF_UNITY^(2^(28-k)), Montgomery
 u256 host_zeta();                     // halo2curves bn256 Fr::ZETA, Montgomery
 u256 host_fr_from_u64(uint64_t v);
 u256 host_coset_shift(uint32_t k, uint32_t t);  // g_t = zeta w_{4n}^(bitrev2(t)): the shift of slot t of the extended domain taken coset by coset (ntt.hip)
-
-// internal device-level entry points shared between translation units (all on ctx().stream)
-int ntt_dev(u256* data, u256* out_or_null, size_t n_cols, uint32_t log_n, const u256& omega, bool scale_ninv,
-            bool coset_in, size_t in_len, const ColSrc* srcs, uint32_t n_blind, bool coset_out, const u256* in_scale = nullptr,
-            const u256* const* in_tabs = nullptr, uint32_t vslots = 0);
 
 }  // namespace vdb

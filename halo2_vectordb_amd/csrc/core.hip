@@ -245,7 +245,6 @@ static void shutdown_context(int device) {
   c.msm_out_bytes = 0;
   witness_release(c);
   poseidon_release(c);
-  c.ntt_lds_raised = false;
   c.win[0] = 0, c.win[1] = ~0ull, c.win[2] = 0, c.win[3] = ~0ull;
   (void)hipEventDestroy(c.ev0);
   (void)hipEventDestroy(c.ev1);

@@ -20,14 +20,13 @@
 
 #include "common.hpp"
 #include "limb9.hpp"
+#include "ntt_plan.hpp"
 #include "shoup_tables.hpp"
 
 namespace vdb {
 
 #define NTT_THREADS 256
 #define NTT_TILE 1024
-#define NTT_MAX_PASSES 4
-#define NTT_DEFAULT_COLGROUP 0x7fffffffu  // tile-major over all columns of a launch (measured equal to column-major within noise; 4x less twiddle refetch)
 
 struct NttPass {
   uint32_t log_n, S, log_inner, logG;
@@ -134,9 +133,6 @@ __device__ __forceinline__ void ntt_static_steps(F&& f) {
     ntt_static_steps<CS, (s + 1 < CS ? s + 2 : s + 1), step + 1>(f);
   }
 }
-// what ntt_dev's LDS budget gives 256- / 512-point passes: the 512-point passes' table at half resolution once the Montgomery-form table
-// is gone (SA), which then holds both twiddles of the step at stage 6 too
-constexpr uint32_t ntt_spec_sh_res_log(uint32_t cs, bool sa) { return cs == 8 ? 0u : (sa ? 1u : 2u); }
 // `SA` (specialised instantiations only): every product by a constant is a Shoup product (NttPass::sh_tab, sh2_tab, tw_rec, zsh).  A
 // Shoup product of v (limbs below 6.1 * 2^29, the bound every Montgomery operand here already keeps) is below (1 + v / 2^261 + 2^-23) r
 // with exactly normalised limbs (shoup_core29) — below 1.14 r for the v < 22 r of these passes, as a Montgomery product by a normalised
@@ -613,284 +609,185 @@ static const uint4* get_shoup_records(uint32_t log_n, const u256& omega, bool sc
   return d;
 }
 
-// Plans and runs the passes.  data: n_cols columns (stride in_len when in_len != 0, else n);
-// result goes to out (stride n) or back into data when out == nullptr.
-int ntt_dev(u256* data, u256* out_or_null, size_t n_cols, uint32_t log_n, const u256& omega, bool scale_ninv,
-            bool coset_in, size_t in_len, const ColSrc* srcs, uint32_t n_blind, bool coset_out, const u256* in_scale, const u256* const* in_tabs,
-            uint32_t vslots) {
-  // `in_tabs` / `vslots`: n_cols counts virtual columns — column c is input column c / vslots multiplied element by element by
-  // in_tabs[c % vslots] (the cosets of one polynomial, one after the other in the output)
+static_assert(NTT_PLAN_OK == VDB_OK && NTT_PLAN_REFUSED == VDB_ERR_ARG, "ntt_plan.hpp returns the C ABI's codes");
+
+// The process's settings, read from the environment once
+static const NttKnobs& ntt_knobs() {
+  static const NttKnobs knobs = [] {
+    const auto off = [](const char* name) {
+      const char* e = getenv(name);
+      return e && e[0] == '0';
+    };
+    NttKnobs k;
+    if (const char* e = getenv("VDB_NTT_MAX_S")) k.max_s = (uint32_t)atoi(e);
+    k.shoup = !off("VDB_NTT_SHOUP");
+    k.spec = !off("VDB_NTT_SPEC");
+    k.shoup_all = !off("VDB_NTT_SHOUP_ALL");
+    k.blk0 = !off("VDB_NTT_BLK0");
+    return k;
+  }();
+  return knobs;
+}
+
+// One batched transform: the job (ntt_plan.hpp; a caller sets what it asks for by name) with the pointers.  has_in_scale, has_in_tabs,
+// has_srcs and in_place are not a caller's to set: ntt_dev derives them from in_scale, in_tabs, srcs and out.
+struct NttRun : NttJob {
+  u256* data;                            // n_cols columns of in_len elements (n when in_len == 0); null with `srcs`
+  u256* out;                             // n_cols columns of n elements; null: the result goes back into data
+  u256 omega;
+  const ColSrc* srcs = nullptr;          // per column: where it still lies in a witness stream
+  uint32_t n_blind = 0;
+  const u256* in_scale = nullptr;        // coset_in: the polynomial s p(X) on the coset
+  // n_cols counts virtual columns — column c is input column c / vslots multiplied element by element by in_tabs[c % vslots] (the
+  // cosets of one polynomial, one after the other in the output)
+  const u256* const* in_tabs = nullptr;
+  NttRun(u256* data_, u256* out_, size_t n_cols_, uint32_t log_n_, const u256& omega_) : data(data_), out(out_), omega(omega_) {
+    n_cols = n_cols_;
+    log_n = log_n_;
+  }
+};
+
+// The kernel argument of a pass as far as its plan fills it; ntt_dev adds the pointers, strides and constants
+static NttPass ntt_pass_arg(uint32_t log_n, const NttPassPlan& q) {
+  NttPass p;
+  memset(&p, 0, sizeof(p));
+  p.log_n = log_n;
+  p.S = q.S;
+  p.log_inner = q.log_inner;
+  p.logG = q.logG;
+  p.nprev = q.nprev;
+  memcpy(p.prevS, q.prevS, sizeof(p.prevS));
+  p.first = q.first;
+  p.coset = q.coset;
+  p.coset_out = q.coset_out;
+  p.scale = q.scale;
+  p.s0 = q.s0;
+  p.ren_mask = q.ren_mask;
+  p.ren_out = q.ren_out;
+  p.blk0 = q.blk0;
+  p.sh_res_log = q.sh_res_log;
+  p.sh_ns = q.sh_ns;
+  p.sh_max_s = q.sh_max_s;
+  return p;
+}
+
+// Plans the passes (ntt_plan.hpp), fetches what the plan asks for, and launches them chunk by chunk.
+static int ntt_dev(const NttRun& t) {
+  if (t.n_cols == 0) return VDB_OK;
+  NttJob job = t;
+  job.has_in_scale = t.in_scale != nullptr;
+  job.has_in_tabs = t.in_tabs != nullptr;
+  job.has_srcs = t.srcs != nullptr;
+  job.in_place = t.out == nullptr;
+  NttPlan plan;
+  const char* why = nullptr;
+  if (int rc = ntt_plan(job, ntt_knobs(), &plan, &why)) {
+    set_error("%s", why);
+    return rc;
+  }
   Context& c = ctx();
-  if (n_cols == 0) return VDB_OK;
-  if (log_n > 26) {
-    set_error("ntt: log_n > 26 unsupported");
-    return VDB_ERR_ARG;
-  }
-  const uint64_t n = 1ull << log_n;
-  const uint64_t in_stride = in_len ? in_len : n;
-  if (!in_len) in_len = n;
-  u256* dst = out_or_null ? out_or_null : data;
-  if (!out_or_null && in_stride != n) {
-    set_error("ntt: in-place transform needs in_len == n");
-    return VDB_ERR_ARG;
-  }
-  if (vslots && (!out_or_null || !in_tabs || vslots > 4 || srcs || coset_in || n_cols % vslots)) {
-    set_error("ntt: virtual columns need an output buffer and their input tables");
-    return VDB_ERR_ARG;
-  }
-  if (srcs && (!out_or_null || in_len != n || log_n <= 10)) {
-    set_error("ntt: column sources need an output buffer and a multi-pass size");
-    return VDB_ERR_ARG;
-  }
+  const uint32_t log_n = t.log_n, L = plan.L;
+  const uint64_t n = 1ull << log_n, in_len = t.in_len ? t.in_len : n;
   int err = VDB_OK;
   const u256 m32 = host_fr_from_u64(32);
-  const u256* tw = get_twiddles(log_n, omega, m32, false, &err);
+  const u256* tw = get_twiddles(log_n, t.omega, m32, false, &err);
   if (!tw) return err;
-
-  // pass sizes
-  uint32_t L, S[NTT_MAX_PASSES];
-  if (log_n <= 10) {
-    L = 1;
-    S[0] = log_n;
-  } else {
-    static const uint32_t max_s = getenv("VDB_NTT_MAX_S") ? (uint32_t)atoi(getenv("VDB_NTT_MAX_S")) : 9u;
-    uint32_t ms = max_s >= 4 && max_s <= 9 ? max_s : 9u;
-    while ((log_n + ms - 1) / ms > NTT_MAX_PASSES) ms++;  // at most NTT_MAX_PASSES digits
-    L = (log_n + ms - 1) / ms;  // passes of up to 512 points: 2^16 = 256 x 256, 2^18 = 512 x 512
-    for (uint32_t l = 0; l < L; l++) S[l] = log_n / L + (l < log_n % L ? 1 : 0);
-  }
-  const u256 fin = scale_ninv ? fr_mul(mont_inv<Fr>(host_fr_from_u64(n)), m32) : m32;
+  const u256 fin = t.scale_ninv ? fr_mul(mont_inv<Fr>(host_fr_from_u64(n)), m32) : m32;
   // multi-pass inverse transforms take 1/n with the inter-pass twiddles of pass 0; their last pass then ends like a
   // forward transform's, without a product
   const u256* tw_scaled = tw;
-  if (scale_ninv && L > 1) {
-    tw_scaled = get_twiddles(log_n, omega, fin, true, &err);
+  if (plan.needs_scaled_twiddles) {
+    tw_scaled = get_twiddles(log_n, t.omega, fin, true, &err);
     if (!tw_scaled) return err;
   }
-  u256 z1 = host_zeta(), z2 = fr_mul(z1, z1);
-  z1 = fr_mul(z1, m32);
-  z2 = fr_mul(z2, m32);
-  u256 z0 = m32;
-  // SA: the same three factors without the 32, as Shoup constants (zsh)
-  u256 zc[3] = {mont_one<Fr>(), host_zeta(), fr_mul(host_zeta(), host_zeta())};
-  if (in_scale) {  // the polynomial s p(X) on the coset: the scalar rides on the coset factors (one more product on a third of the inputs)
-    z0 = fr_mul(z0, *in_scale);
-    z1 = fr_mul(z1, *in_scale);
-    z2 = fr_mul(z2, *in_scale);
-    for (int t = 0; t < 3; t++) zc[t] = fr_mul(zc[t], *in_scale);
+  // the coset factors 1, zeta, zeta^2 — for the polynomial s p(X) the scalar rides on them (one more product on a third of the inputs) —
+  // as Shoup constants for SA (zsh) and times 32 for the Montgomery products
+  u256 zc[3] = {mont_one<Fr>(), host_zeta(), fr_mul(host_zeta(), host_zeta())}, z[3];
+  for (int i = 0; i < 3; i++) {
+    if (t.in_scale) zc[i] = fr_mul(zc[i], *t.in_scale);
+    z[i] = fr_mul(zc[i], m32);
   }
-  static const bool shoup_on = !(getenv("VDB_NTT_SHOUP") && getenv("VDB_NTT_SHOUP")[0] == '0');
-  // 14 r with limbs that dominate a normalised subtrahend (l9_sub)
-  uint32_t ckp[9];
-  const double cmax = l9_offset_limbs<FrParams>(14, ckp);
 
-  // column chunking bounds the scratch buffer (<= ~2 GiB)
-  size_t chunk_cols = n_cols;
+  // the passes' kernel arguments, but for what changes from chunk to chunk
+  NttPass args[NTT_MAX_PASSES];
+  const u256* twi[NTT_MAX_PASSES];
+  for (uint32_t l = 0; l < L; l++) {
+    const NttPassPlan& q = plan.passes[l];
+    NttPass& p = args[l] = ntt_pass_arg(log_n, q);
+    p.vslots = t.vslots;
+    for (uint32_t s = 0; s < t.vslots; s++) p.in_tab[s] = t.in_tabs[s];
+    p.in_len = in_len;
+    p.in_stride = l == 0 ? in_len : n;
+    p.out_stride = n;
+    p.n_blind = t.n_blind;
+    p.zeta0 = z[0];
+    p.zeta1 = z[1];
+    p.zeta2 = z[2];
+    p.fin = fin;
+    memcpy(p.ckp, plan.ckp, sizeof(p.ckp));
+    twi[l] = (l == 0 && !q.last) ? tw_scaled : tw;
+    if (q.has_sh_tab) {
+      p.sh_tab = get_shoup_table(log_n, t.omega, q.S, q.sh_res_log, &err);
+      if (!p.sh_tab) return err;
+    }
+    if (q.needs_sh2_tab) {
+      p.sh2_tab = get_shoup_table(log_n, t.omega, q.S, 0, &err);
+      if (!p.sh2_tab) return err;
+    }
+    if (q.needs_tw_rec) {
+      p.tw_rec = get_shoup_records(log_n, t.omega, twi[l] != tw, twi[l], &err);
+      if (!p.tw_rec) return err;
+    }
+    if (q.sa)
+      for (int i = 0; i < 3; i++) shoup_const_of_mont(zc[i], p.zsh[i]);
+  }
+
+  const size_t chunk_cols = plan.chunk_cols(t.n_cols);
   u256* scratch = nullptr;
   if (L > 1) {
-    size_t max_cols = ((size_t)2 << 30) / (n * sizeof(u256));
-    if (max_cols < 1) max_cols = 1;
-    if (chunk_cols > max_cols) chunk_cols = max_cols;
-    if (vslots) chunk_cols = chunk_cols / vslots * vslots ? chunk_cols / vslots * vslots : vslots;
     scratch = (u256*)scratch_get(3, chunk_cols * n * sizeof(u256));
     if (!scratch) return VDB_ERR_OOM;
   }
-  // launch order of the non-last passes (VDB_NTT_COLGROUP: 0 = column after column)
-  static const uint32_t col_group = getenv("VDB_NTT_COLGROUP") ? (uint32_t)strtoul(getenv("VDB_NTT_COLGROUP"), nullptr, 10) : NTT_DEFAULT_COLGROUP;
-  for (size_t c0 = 0; c0 < n_cols; c0 += chunk_cols) {
-    size_t nc = n_cols - c0 < chunk_cols ? n_cols - c0 : chunk_cols;
-    uint32_t done_bits = 0;
+  u256* dst = t.out ? t.out : t.data;
+  for (size_t c0 = 0; c0 < t.n_cols; c0 += chunk_cols) {
+    const size_t nc = t.n_cols - c0 < chunk_cols ? t.n_cols - c0 : chunk_cols;
     for (uint32_t l = 0; l < L; l++) {
-      NttPass p;
-      memset(&p, 0, sizeof(p));
-      p.log_n = log_n;
-      p.S = S[l];
-      p.log_inner = log_n - done_bits - S[l];
-      p.first = (l == 0);
-      const bool last = (l == L - 1);
-      p.coset = (l == 0 && coset_in) ? (in_scale ? 2u : 1u) : ((l == 0 && vslots) ? 3u : 0u);
-      p.vslots = vslots;
-      for (uint32_t t = 0; t < vslots; t++) p.in_tab[t] = in_tabs[t];
-      p.zeta0 = z0;
-      p.in_len = in_len;
-      p.srcs = (l == 0 && srcs) ? srcs + c0 : nullptr;
-      p.n_blind = n_blind;
+      const NttPassPlan& q = plan.passes[l];
+      NttPass& p = args[l];
+      p.srcs = (l == 0 && t.srcs) ? t.srcs + c0 : nullptr;
       p.n_cols = (uint32_t)nc;
-      p.col_group = last ? 0u : (col_group < nc ? col_group : (uint32_t)nc);  // the last pass reads no inter-pass twiddles
-      p.zeta1 = z1;
-      p.zeta2 = z2;
-      p.fin = fin;
-      memcpy(p.ckp, ckp, sizeof(ckp));
-      p.scale = last && scale_ninv && L == 1;
-      p.coset_out = last && coset_out;
-      // zero-padded input (coeff_to_extended): when rows of pass 0 run along the top digit and only their first
-      // quarter is data, stages 0 and 1 are pure replication
-      p.s0 = (l == 0 && !last && S[0] >= 3 && in_len * 4 <= n) ? 2 : 0;
-      // carry-pass schedule: limb bounds in units of 2^29 (a sum adds the operands' bounds, a difference adds cmax);
-      // products need operands below 6.1, nothing may reach 8
-      {
-        double b = 1.0001;
-        uint32_t step = 0;
-        for (uint32_t st = p.s0; st < S[l]; step++) {
-          if (st + 1 < S[l]) {
-            if (st == 0) {
-              b = 1.0 + 2.0 * cmax;
-            } else {
-              if (b + cmax >= 6.1 || b + 2.0 * cmax >= 7.95) {
-                p.ren_mask |= 1u << step;
-                b = 1.0001;
-              }
-              b += 2.0 * cmax;
-            }
-            st += 2;
-          } else {
-            if (st == 0) {
-              b = 1.0 + cmax;
-            } else {
-              if (b >= 6.1 || b + cmax >= 7.95) {
-                p.ren_mask |= 1u << step;
-                b = 1.0001;
-              }
-              b += cmax;
-            }
-            st += 1;
-          }
-        }
-        // the step that starts at stage 0 subtracts its operands as loaded (k_ntt_pass, the FIRST branch and the radix-2 stage of a
-        // one-stage pass) and its limb bounds above assume exactly normalised input.  The loop above never puts a carry pass in front
-        // of it; keep it so.  (Limbs of 2^29 + 7 would still be inside l9_sub's domain for the 14 r offset, but not for every offset:
-        // tests/test_l9_cpu.py::test_sub_renormalised_subtrahend)
-        if (p.s0 == 0 && (p.ren_mask & 1u)) {
-          set_error("ntt: the carry schedule put a carry pass in front of the step at stage 0");
-          return VDB_ERR_ARG;
-        }
-        // the write-out multiplies (inter-pass twiddle, 1/n, zeta) unless it is a forward transform's last pass, whose reduction
-        // carries on its own (l9_canon_wide): a carry pass only when the last step left limbs above what a product takes
-        const bool out_mul = !last || p.scale || p.coset_out;
-        static const bool blk0_on = !(getenv("VDB_NTT_BLK0") && getenv("VDB_NTT_BLK0")[0] == '0');
-        p.blk0 = blk0_on ? 1u : 0u;
-        static const bool always = getenv("VDB_NTT_REN_OUT") && getenv("VDB_NTT_REN_OUT")[0] == '1';   // A/B: the unconditional pass of rounds 1-2
-        p.ren_out = (always || (out_mul && b >= 6.1)) ? 1u : 0u;
-      }
-      const u256* src;
-      u256* out;
-      if (l == 0) {
-        src = srcs ? scratch : data + (vslots ? c0 / vslots : c0) * in_stride;  // with column sources `in` is not read
-        p.in_stride = in_stride;
-      } else {
-        src = scratch;
-        p.in_stride = n;
-      }
-      if (last) {
-        out = dst + c0 * n;
-        p.out_stride = n;
-      } else {
-        out = scratch;
-        p.out_stride = n;
-      }
-      uint32_t m = 1u << S[l];
-      if (L == 1) {
-        p.logG = 0;
-        p.nprev = 0;
-      } else {
-        p.logG = 10 - S[l];  // 1024-element tiles: G = 4 for 256-point, G = 2 for 512-point DFTs
-        // a tile cannot be wider than the digit it is cut from: the inner index of a non-last pass, the first digit of the last
-        const uint32_t room = last ? S[0] : p.log_inner;
-        if (p.logG > room) p.logG = room;
-        p.nprev = l;  // only read when last
-        for (uint32_t q = 0; q < l && q < NTT_MAX_PASSES; q++) p.prevS[q] = S[q];
-      }
-      uint32_t G = 1u << p.logG;
-      uint32_t tiles = (uint32_t)(n / ((uint64_t)m * G));
-      // the instantiation with this pass's size, first stage, carry schedule and Shoup resolution as compile-time constants when there is
-      // one (the 256- and 512-point passes of the prover's transforms), the generic kernel otherwise (VDB_NTT_SPEC=0: always)
-      static const bool spec_on = !(getenv("VDB_NTT_SPEC") && getenv("VDB_NTT_SPEC")[0] == '0');
-      const bool vs = (l == 0 && vslots);
-      auto spec_shape = [&](uint32_t cs, uint32_t cs0, uint32_t cren) {
-        return spec_on && L > 1 && p.S == cs && p.s0 == cs0 && p.ren_mask == cren && p.logG == 10 - cs && p.blk0;
-      };
-      // SA instantiation (VDB_NTT_SHOUP_ALL=0: the Montgomery products of before, the same instantiations otherwise): a specialised,
-      // non-virtual pass, with the 80-B inter-pass records bounded to n <= 2^22 (335 MB)
-      static const bool shoup_all = !(getenv("VDB_NTT_SHOUP_ALL") && getenv("VDB_NTT_SHOUP_ALL")[0] == '0');
-      const bool sa = shoup_all && shoup_on && !vs && log_n <= 22 &&
-                      (spec_shape(8, 0, 4) || spec_shape(9, 0, 20) || (!last && spec_shape(9, 2, 4)));
-      // (SA holds no Montgomery-form stage twiddles in LDS)
-      size_t lds = (size_t)(G * (m + 1) + (sa ? 0 : (m / 2 ? m / 2 : 1))) * (2 * sizeof(uint4) + sizeof(uint32_t));
-      // Shoup table in what is left of a third of the CU's LDS (three workgroups per CU stay resident): full resolution for the
-      // 256-point passes, a quarter for the 512-point ones (a half under SA); passes too small to have a general radix-4 step do without
-      p.sh_tab = nullptr;
-      p.sh_res_log = p.sh_ns = 0;
-      p.sh_max_s = -1;
-      if (shoup_on && S[l] >= 4) {
-        const size_t room = (160 * 1024) / 3;
-        uint32_t rl = 0;
-        while (rl + 2 < S[l] && lds + (size_t)((m / 2) >> rl) * 72 > room) rl++;
-        const int32_t max_s = (int32_t)S[l] - 2 - (int32_t)rl;
-        if (lds + (size_t)((m / 2) >> rl) * 72 <= room && max_s >= 1) {
-          p.sh_tab = get_shoup_table(log_n, omega, S[l], rl, &err);
-          if (!p.sh_tab) return err;
-          p.sh_res_log = rl;
-          p.sh_ns = (m / 2) >> rl;
-          p.sh_max_s = max_s;
-          lds += (size_t)p.sh_ns * 72;
-        }
-      }
-      dim3 grid((unsigned)(nc * tiles));
-      if (lds > 64 * 1024) {
-        bool& raised = c.ntt_lds_raised;  // per device: the attribute belongs to the device's code object
-        if (!raised) {
-          VDB_HIP(hipFuncSetAttribute((const void*)k_ntt_pass<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-          VDB_HIP(hipFuncSetAttribute((const void*)k_ntt_pass<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-          VDB_HIP(hipFuncSetAttribute((const void*)k_ntt_pass<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-          VDB_HIP(hipFuncSetAttribute((const void*)k_ntt_pass<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-          raised = true;
-        }
-      }
-      const u256* twi = last ? tw : (l == 0 ? tw_scaled : tw);
-      auto spec = [&](uint32_t cs, uint32_t cs0, uint32_t cren, bool sa_) {
-        const uint32_t rl = ntt_spec_sh_res_log(cs, sa_);
-        return spec_shape(cs, cs0, cren) && p.sh_tab && p.sh_res_log == rl && p.sh_ns == ((1u << (cs - 1)) >> rl) && p.sh_max_s == (int32_t)cs - 2 - (int32_t)rl;
-      };
-      if (sa) {
-        if (!spec(p.S, p.s0, p.ren_mask, true)) {  // (cannot happen: the LDS plan above gives the SA resolution to these shapes)
-          set_error("ntt: SA plan does not match its instantiation");
-          return VDB_ERR_ARG;
-        }
-        if (S[l] & 1) {
-          p.sh2_tab = get_shoup_table(log_n, omega, S[l], 0, &err);
-          if (!p.sh2_tab) return err;
-        }
-        if (!last) {
-          p.tw_rec = get_shoup_records(log_n, omega, twi != tw, twi, &err);
-          if (!p.tw_rec) return err;
-        }
-        for (int t = 0; t < 3; t++) shoup_const_of_mont(zc[t], p.zsh[t]);
-      }
-#define NTT_LAUNCH(...) hipLaunchKernelGGL((k_ntt_pass<__VA_ARGS__>), grid, dim3(NTT_THREADS), lds, c.stream, src, out, tw, twi, p, tiles)
+      // non-last passes run tile-major over all columns of the launch: a tile's inter-pass and stage twiddles are L2 hits for every
+      // column after the first (measured equal to column-major within noise; 4x less twiddle refetch).  The last pass reads none
+      p.col_group = q.last ? 0u : (uint32_t)nc;
+      // (with column sources `in` is not read)
+      const u256* src = (l > 0 || t.srcs) ? scratch : t.data + (t.vslots ? c0 / t.vslots : c0) * in_len;
+      u256* out = q.last ? dst + c0 * n : scratch;
+      const dim3 grid((unsigned)(nc * q.tiles));
+#define NTT_LAUNCH(...) \
+  hipLaunchKernelGGL((k_ntt_pass<__VA_ARGS__>), grid, dim3(NTT_THREADS), q.lds_bytes, c.stream, src, out, tw, twi[l], p, q.tiles)
       {
         VDB_PROF("k_ntt_pass");
-        if (last) {
-          if (vs) NTT_LAUNCH(true, true);
-          else if (sa && p.S == 8) NTT_LAUNCH(true, false, 8, 0, 4, true);
-          else if (sa) NTT_LAUNCH(true, false, 9, 0, 20, true);
-          else if (spec(8, 0, 4, false)) NTT_LAUNCH(true, false, 8, 0, 4);
-          else if (spec(9, 0, 20, false)) NTT_LAUNCH(true, false, 9, 0, 20);
-          else NTT_LAUNCH(true, false);
-        } else {
-          if (vs && spec(8, 0, 4, false)) NTT_LAUNCH(false, true, 8, 0, 4);
-          else if (vs) NTT_LAUNCH(false, true);
-          else if (sa && p.S == 8) NTT_LAUNCH(false, false, 8, 0, 4, true);
-          else if (sa && p.s0 == 2) NTT_LAUNCH(false, false, 9, 2, 4, true);
-          else if (sa) NTT_LAUNCH(false, false, 9, 0, 20, true);
-          else if (spec(8, 0, 4, false)) NTT_LAUNCH(false, false, 8, 0, 4);
-          else if (spec(9, 2, 4, false)) NTT_LAUNCH(false, false, 9, 2, 4);
-          else if (spec(9, 0, 20, false)) NTT_LAUNCH(false, false, 9, 0, 20);
-          else NTT_LAUNCH(false, false);
+        switch (q.kernel) {
+          case NTT_K_LAST: NTT_LAUNCH(true, false); break;
+          case NTT_K_GENERIC: NTT_LAUNCH(false, false); break;
+          case NTT_K_LAST_VS: NTT_LAUNCH(true, true); break;
+          case NTT_K_VS: NTT_LAUNCH(false, true); break;
+          case NTT_K_LAST_256_SA: NTT_LAUNCH(true, false, 8, 0, 4, true); break;
+          case NTT_K_LAST_512_SA: NTT_LAUNCH(true, false, 9, 0, 20, true); break;
+          case NTT_K_LAST_256: NTT_LAUNCH(true, false, 8, 0, 4); break;
+          case NTT_K_LAST_512: NTT_LAUNCH(true, false, 9, 0, 20); break;
+          case NTT_K_VS_256: NTT_LAUNCH(false, true, 8, 0, 4); break;
+          case NTT_K_256_SA: NTT_LAUNCH(false, false, 8, 0, 4, true); break;
+          case NTT_K_512_PAD_SA: NTT_LAUNCH(false, false, 9, 2, 4, true); break;
+          case NTT_K_512_SA: NTT_LAUNCH(false, false, 9, 0, 20, true); break;
+          case NTT_K_256: NTT_LAUNCH(false, false, 8, 0, 4); break;
+          case NTT_K_512_PAD: NTT_LAUNCH(false, false, 9, 2, 4); break;
+          case NTT_K_512: NTT_LAUNCH(false, false, 9, 0, 20); break;
+          case NTT_K_COUNT: break;
         }
       }
 #undef NTT_LAUNCH
       VDB_LAUNCH_CHECK();
-      done_bits += S[l];
     }
   }
   return VDB_OK;
@@ -950,7 +847,9 @@ int vdb_ntt_batch_dev(vdb_fr* cols_dev, size_t n_cols, uint32_t log_n, const vdb
   VDB_ARG(cols_dev && omega, "null pointer");
   u256 w;
   memcpy(&w, omega, 32);
-  return ntt_dev(as_u256(cols_dev), nullptr, n_cols, log_n, w, (flags & VDB_NTT_INVERSE_SCALE) != 0, false, 0, nullptr, 0, false, nullptr);
+  NttRun t(as_u256(cols_dev), nullptr, n_cols, log_n, w);
+  t.scale_ninv = (flags & VDB_NTT_INVERSE_SCALE) != 0;
+  return ntt_dev(t);
 }
 int vdb_ntt_batch(vdb_fr* const* cols, size_t n_cols, uint32_t log_n, const vdb_fr* omega, int flags) {
   VDB_REQUIRE_INIT();
@@ -966,14 +865,18 @@ int vdb_ntt_batch(vdb_fr* const* cols, size_t n_cols, uint32_t log_n, const vdb_
 int vdb_lagrange_to_coeff_dev(vdb_fr* cols_dev, size_t n_cols, uint32_t k) {
   VDB_REQUIRE_INIT();
   VDB_ARG(cols_dev && k <= 26, "bad argument");
-  u256 w = mont_inv<Fr>(host_root_of_unity(k));
-  return ntt_dev(as_u256(cols_dev), nullptr, n_cols, k, w, true, false, 0, nullptr, 0, false, nullptr);
+  NttRun t(as_u256(cols_dev), nullptr, n_cols, k, mont_inv<Fr>(host_root_of_unity(k)));
+  t.scale_ninv = true;
+  return ntt_dev(t);
 }
 int vdb_lagrange_to_coeff_src_dev(const vdb_colsrc* src_dev, vdb_fr* coeff_dev, size_t n_cols, uint32_t k, uint32_t n_blind) {
   VDB_REQUIRE_INIT();
   VDB_ARG(src_dev && coeff_dev && k <= 26 && k > 10, "bad argument (column sources are supported for k > 10)");
-  u256 w = mont_inv<Fr>(host_root_of_unity(k));
-  return ntt_dev(nullptr, as_u256(coeff_dev), n_cols, k, w, true, false, 0, reinterpret_cast<const ColSrc*>(src_dev), n_blind, false, nullptr);
+  NttRun t(nullptr, as_u256(coeff_dev), n_cols, k, mont_inv<Fr>(host_root_of_unity(k)));
+  t.srcs = reinterpret_cast<const ColSrc*>(src_dev);
+  t.n_blind = n_blind;
+  t.scale_ninv = true;
+  return ntt_dev(t);
 }
 int vdb_lagrange_to_coeff(vdb_fr* const* cols, size_t n_cols, uint32_t k) {
   VDB_REQUIRE_INIT();
@@ -989,21 +892,29 @@ int vdb_lagrange_to_coeff(vdb_fr* const* cols, size_t n_cols, uint32_t k) {
 int vdb_coeff_to_extended_dev(const vdb_fr* coeff_dev, vdb_fr* ext_dev, size_t n_cols, uint32_t k, uint32_t ext_k) {
   VDB_REQUIRE_INIT();
   VDB_ARG(coeff_dev && ext_dev && k + ext_k <= 26, "bad argument");
-  u256 w = host_root_of_unity(k + ext_k);
-  return ntt_dev(const_cast<u256*>(as_u256(coeff_dev)), as_u256(ext_dev), n_cols, k + ext_k, w, false, true, (size_t)1 << k, nullptr, 0, false, nullptr);
+  NttRun t(const_cast<u256*>(as_u256(coeff_dev)), as_u256(ext_dev), n_cols, k + ext_k, host_root_of_unity(k + ext_k));
+  t.in_len = (size_t)1 << k;
+  t.coset_in = true;
+  return ntt_dev(t);
 }
 int vdb_coeff_to_extended_scaled_dev(const vdb_fr* coeff_dev, vdb_fr* ext_dev, size_t n_cols, uint32_t k, uint32_t ext_k, const vdb_fr* scale) {
   VDB_REQUIRE_INIT();
   VDB_ARG(coeff_dev && ext_dev && scale && k + ext_k <= 26, "bad argument");
-  u256 w = host_root_of_unity(k + ext_k), sv;
+  u256 sv;
   memcpy(&sv, scale, 32);
-  return ntt_dev(const_cast<u256*>(as_u256(coeff_dev)), as_u256(ext_dev), n_cols, k + ext_k, w, false, true, (size_t)1 << k, nullptr, 0, false, &sv);
+  NttRun t(const_cast<u256*>(as_u256(coeff_dev)), as_u256(ext_dev), n_cols, k + ext_k, host_root_of_unity(k + ext_k));
+  t.in_len = (size_t)1 << k;
+  t.coset_in = true;
+  t.in_scale = &sv;
+  return ntt_dev(t);
 }
 int vdb_extended_to_coeff_dev(vdb_fr* ext_dev, size_t n_cols, uint32_t k, uint32_t ext_k) {
   VDB_REQUIRE_INIT();
   VDB_ARG(ext_dev && k + ext_k <= 26, "bad argument");
-  u256 w = mont_inv<Fr>(host_root_of_unity(k + ext_k));
-  return ntt_dev(as_u256(ext_dev), nullptr, n_cols, k + ext_k, w, true, false, 0, nullptr, 0, true, nullptr);
+  NttRun t(as_u256(ext_dev), nullptr, n_cols, k + ext_k, mont_inv<Fr>(host_root_of_unity(k + ext_k)));
+  t.scale_ninv = true;
+  t.coset_out = true;
+  return ntt_dev(t);
 }
 // The cosets of the extended domain one by one ("slots"): slot t of a column is the polynomial on g_t H, H the 2^k-th roots of unity,
 // g_t = zeta w_{4n}^(bitrev2(t)) — g_0 = zeta, g_1 = zeta w_{2n}, g_2 = zeta w_{4n}, g_3 = zeta w_{4n}^3: together the 4 n points of
@@ -1037,8 +948,10 @@ int vdb_coeff_to_cosets_dev(const vdb_fr* coeff_dev, vdb_fr* cosets_dev, size_t 
       if (!tabs[t]) return err;
     }
   }
-  return ntt_dev(const_cast<u256*>(as_u256(coeff_dev)), as_u256(cosets_dev), n_cols * n_slots, k, host_root_of_unity(k), false, false, 0, nullptr, 0, false, nullptr,
-                 tabs, n_slots);
+  NttRun t(const_cast<u256*>(as_u256(coeff_dev)), as_u256(cosets_dev), n_cols * n_slots, k, host_root_of_unity(k));
+  t.in_tabs = tabs;
+  t.vslots = n_slots;
+  return ntt_dev(t);
 }
 // The way back for ONE polynomial, the quotient: `cosets_dev` holds the numerator's values on the first n_slots cosets ([slot][row];
 // overwritten); they are divided by X^n - 1 (a constant per coset), brought back to the residues modulo X^n - g_t^n, and the n_slots
@@ -1049,8 +962,9 @@ int vdb_cosets_to_coeff_dev(vdb_fr* cosets_dev, vdb_fr* coeff_dev, uint32_t k, u
   VDB_ARG(cosets_dev && coeff_dev && k + 2 <= 26 && n_slots >= 1 && n_slots <= 4, "bad argument");
   Context& c = ctx();
   const uint64_t n = 1ull << k;
-  int rc = ntt_dev(as_u256(cosets_dev), nullptr, n_slots, k, mont_inv<Fr>(host_root_of_unity(k)), true, false, 0, nullptr, 0, false, nullptr);
-  if (rc) return rc;
+  NttRun back(as_u256(cosets_dev), nullptr, n_slots, k, mont_inv<Fr>(host_root_of_unity(k)));
+  back.scale_ninv = true;
+  if (int rc = ntt_dev(back)) return rc;
   CosetMix mx;
   memset(&mx, 0, sizeof(mx));
   u256 u[4];
