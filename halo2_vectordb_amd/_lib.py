@@ -78,6 +78,9 @@ _SIGNATURES = {
     "vdb_wit_ann_query_size": [_I, _U32, _U32, _SZ, _SZ, _SZ, _P, _P, _P],
     "vdb_wit_ann_query": [_I, _U32, _U32, _P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _P],
     "vdb_wit_ann_query_dev": [_I, _U32, _U32, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _P],
+    "vdb_wit_ann_probe_size": [_I, _U32, _U32, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P],
+    "vdb_wit_ann_probe": [_I, _U32, _U32, _P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P],
+    "vdb_wit_ann_probe_dev": [_I, _U32, _U32, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P],
     "vdb_wit_ann_update_size": [_SZ, _SZ, _SZ, _SZ, _U32, _P, _P, _P],
     "vdb_wit_ann_update": [_P, _P, _SZ, _SZ, _SZ, _SZ, _U32, _P, _P, _SZ, _P, _P, _P],
     "vdb_wit_ann_update_dev": [_P, _P, _SZ, _SZ, _SZ, _SZ, _U32, _P, _P, _SZ, _P, _P, _P],
@@ -108,6 +111,8 @@ _SIGNATURES = {
     "vdb_wit_nearest_topk_dev": [_I, _U32, _U32, _P, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],
     "vdb_nearest_values": [_U32, _U32, _I, _P, _P, _SZ, _SZ, _SZ, _P, _P],
     "vdb_nearest_values_dev": [_U32, _U32, _I, _P, _P, _SZ, _SZ, _SZ, _P, _P],
+    "vdb_nearest_topk_values": [_U32, _U32, _I, _P, _P, _SZ, _SZ, _SZ, _SZ, _P, _P],
+    "vdb_nearest_topk_values_dev": [_U32, _U32, _I, _P, _P, _SZ, _SZ, _SZ, _SZ, _P, _P],
     "vdb_layout_plan": [_P, _U64, _U32, _U32, _P, _U64, _P], "vdb_layout_plan_dev": [_P, _U64, _U32, _U32, _P, _U64, _P],
     "vdb_layout_columns": [_P, _U64, _P, _U64, _P, _U64, _U32, _U32, _P, _P, _U64],
     "vdb_layout_columns_dev": [_P, _U64, _P, _U64, _U32, _P, _P, _U32],

@@ -392,6 +392,21 @@ def nearest_values(metric, queries, vectors, P=48, L=13):
     return idx, dist
 
 
+def nearest_topk_values(metric, queries, vectors, p, P=48, L=13):
+    """the winners of p rounds of top-k for every row of `queries` (q, dim, 4) over `vectors` (n, dim, 4) as values alone
+    (vdb_nearest_topk_values: no stream is emitted): (idx (q, p) uint32, dist (q, p, 4)), dist[., r] the minimum round r's qmin chain ends
+    in, idx[., r] the last i at it — the vector the round's select_by_indicator states"""
+    lib = _lib.init()
+    queries, vectors = _fr(queries), _fr(vectors)
+    q, n, dim, p = queries.shape[0], vectors.shape[0], vectors.shape[1], int(p)
+    assert queries.ndim == 3 and vectors.ndim == 3 and queries.shape[1] == dim
+    idx = np.zeros((q, max(p, 0)), dtype=np.uint32)
+    dist = np.zeros((q, max(p, 0), 4), dtype=np.uint64)
+    check(lib.vdb_nearest_topk_values(ctypes.c_uint32(P), ctypes.c_uint32(L), METRICS[metric], _p(queries), _p(vectors), _sz(q), _sz(n), _sz(dim), _sz(p),
+                                      _p(idx), _p(dist)))
+    return idx, dist
+
+
 def wit_kmeans(metric, vectors, K, I, P=48, L=13, zero_cached=False, selectors=False):
     lib = _lib.init()
     vectors = _fr(vectors)
@@ -541,6 +556,33 @@ def wit_ann_query(metric, query, centroids, members, cluster_roots, P=48, L=13, 
                                 _sz(dim), _p(stream), _p(lookup), _p(sel) if selectors else None, _p(ind_c), _p(ind_m), _p(pub)))
     return dict(stream=stream, lookup=lookup, **_split_flags(sel), n_in=n_in.value, centroid_indicator=ind_c, member_indicator=ind_m, result=pub[:dim],
                 index_root=pub[dim], public=pub)
+
+
+def wit_ann_probe(metric, query, centroids, members_list, cluster_roots, topk=1, P=48, L=13, selectors=False):
+    """the circuit of one query over the p nearest clusters that returns the `topk` nearest candidates (vdb_wit_ann_probe) on query
+    (dim, 4), centroids (K, dim, 4), members_list: the rows (n_r, dim, 4) of the p clusters the centroid rounds state, in round order, and
+    the K cluster roots (K, 4): dict(stream, lookup, selectors, n_in, centroid_indicators (p, K, 4), candidate_indicators (topk, N, 4),
+    results (topk, dim, 4), index_root (4,), public (topk dim + 1, 4))"""
+    lib = _lib.init()
+    query, centroids, cluster_roots = _fr(query), _fr(centroids), _fr(cluster_roots)
+    members_list = [_fr(m) for m in members_list]
+    K, dim, p, t = centroids.shape[0], centroids.shape[1], len(members_list), int(topk)
+    assert query.shape == (dim, 4) and cluster_roots.shape == (K, 4) and all(m.ndim == 3 and m.shape[1:] == (dim, 4) for m in members_list)
+    sizes = np.ascontiguousarray([m.shape[0] for m in members_list], dtype=np.uint64)
+    cand = np.ascontiguousarray(np.concatenate(members_list)) if p else np.zeros((0, dim, 4), dtype=np.uint64)
+    N = cand.shape[0]
+    cells, lk, n_in = _u64(), _u64(), _u64()
+    m = METRICS[metric]
+    check(lib.vdb_wit_ann_probe_size(m, ctypes.c_uint32(P), ctypes.c_uint32(L), _sz(K), _sz(dim), _sz(p), _p(sizes), _sz(t), ctypes.byref(cells),
+                                     ctypes.byref(lk), ctypes.byref(n_in)))
+    stream = np.zeros((cells.value, 4), dtype=np.uint64)
+    lookup = np.zeros((lk.value, 4), dtype=np.uint64)
+    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
+    ind_c, ind_m, pub = np.zeros((p, K, 4), dtype=np.uint64), np.zeros((t, N, 4), dtype=np.uint64), np.zeros((t * dim + 1, 4), dtype=np.uint64)
+    check(lib.vdb_wit_ann_probe(m, ctypes.c_uint32(P), ctypes.c_uint32(L), _p(query), _p(centroids), _p(cand), _p(cluster_roots), _sz(K), _sz(dim), _sz(p),
+                                _p(sizes), _sz(t), _p(stream), _p(lookup), _p(sel) if selectors else None, _p(ind_c), _p(ind_m), _p(pub)))
+    return dict(stream=stream, lookup=lookup, **_split_flags(sel), n_in=n_in.value, centroid_indicators=ind_c, candidate_indicators=ind_m,
+                results=pub[:t * dim].reshape(t, dim, 4), index_root=pub[t * dim], public=pub)
 
 
 def _wit_ann_cluster(size, call, metric, centroids, members, roots, cluster, P, L, selectors, flag, per_member):

@@ -1076,6 +1076,81 @@ def build_ann_query(metric, K, n_c, dim, P, L, fetch_flags, fetch_values, builde
                                     index_root=index_root, layout=lay)
 
 
+def ann_probe_layout(metric, K, sizes, dim, p, t, P, L):
+    """where the blocks of the query over the p nearest clusters start (include/vdb.h vdb_wit_ann_probe); `sizes`: the size of the cluster
+    round r of the centroid search states, r < p.  dict(query, centroids, candidates, roots: the assigned inputs; n_in; N; offsets (p + 1):
+    candidate rows [offsets[r], offsets[r + 1]) are round r's cluster; nearest_c, merkle_c, nearest_m, merkle_m (p), select (p), sponge:
+    the blocks; total; lk_m, total_l; units_c, units_m: nearest_units of the two searches at p and t rounds; zero_cell: the load_zero cell
+    of the first padded tree among [centroids, members_0 ..] (None: none is padded); zero_cached (p): the members' tree copies it)"""
+    sizes = [int(x) for x in sizes]
+    if len(sizes) != p or not 1 <= p <= K or min(sizes) < 1:
+        raise ValueError("one non-empty cluster per probe, at least 1 and at most K probes")
+    N = sum(sizes)
+    uc, um = nearest_units(metric, K, dim, p, P, L), nearest_units(metric, N, dim, t, P, L)
+    leaf = merkle_leaf_layout(dim)["leaf_cells"]
+    padded = lambda n: (1 << (n - 1).bit_length()) > n
+    lay = dict(query=0, centroids=dim, candidates=dim + K * dim, roots=dim + K * dim + N * dim, N=N, units_c=uc, units_m=um,
+               offsets=[sum(sizes[:r]) for r in range(p + 1)], sizes=sizes)
+    lay["n_in"] = lay["nearest_c"] = lay["roots"] + K
+    lay["merkle_c"] = lay["nearest_c"] + uc["per_q"]
+    lay["nearest_m"] = lay["merkle_c"] + merkle_cells(K, dim)
+    zero = lay["merkle_c"] + K * leaf if padded(K) else None
+    at, lay["merkle_m"], lay["zero_cached"] = lay["nearest_m"] + um["per_q"], [], []
+    for n_r in sizes:
+        lay["merkle_m"].append(at)
+        lay["zero_cached"].append(zero is not None)
+        if padded(n_r) and zero is None:
+            zero = at + n_r * leaf
+        at += merkle_cells(n_r, dim, lay["zero_cached"][-1])
+    lay["zero_cell"] = zero
+    lay["select"] = [at + r * (1 + 3 * K) for r in range(p)]
+    lay["sponge"] = at + p * (1 + 3 * K)
+    lay["total"] = lay["sponge"] + merkle_leaf_layout(K + 1)["leaf_cells"]
+    lay["lk_m"], lay["total_l"] = uc["per_q_l"], uc["per_q_l"] + um["per_q_l"]
+    return lay
+
+
+def build_ann_probe(metric, K, sizes, dim, p, t, P, L, fetch_flags, fetch_values, builder=None):
+    """The query over the p nearest clusters that returns the t nearest candidates, in one circuit (pipeline.AnnProbeQueryHotPath):
+    [query | centroids | candidates | cluster roots] assigned, then nearest_topk(query, centroids, p), merkle_commitment(centroids),
+    nearest_topk(query, candidates, t), merkle_commitment(members_r) over the candidate rows of every round r — the padded trees sharing one
+    zero cell, as Context::load_zero caches it —, p select_by_indicator(cluster roots, centroid indicators of round r), each TIED to the
+    root of the members' tree of its round, and the sponge over [centroids' root | cluster roots].  build_ann_query is this at p = t = 1.
+    -> (CopyMap, public cells: the t x dim result cells nearest first, then the index root, dict(centroid_indicators (p, K),
+    candidate_indicators (t, N), results (t, dim), centroids_root, members_roots (p), selected (p), index_root, layout))"""
+    if K < 1 or dim < 1:
+        raise ValueError("at least one centroid and one word")
+    lay = ann_probe_layout(metric, K, sizes, dim, p, t, P, L)
+    if np.asarray(fetch_flags(0, lay["n_in"])).any():
+        raise ValueError("the assigned inputs carry no gate or constant flag")
+    N = lay["N"]
+    B = (builder or _Builder)(lay["total"], lay["total_l"])
+    query = np.arange(dim, dtype=np.int64).reshape(1, dim)
+    cent = lay["centroids"] + np.arange(K * dim, dtype=np.int64).reshape(K, dim)
+    cand = lay["candidates"] + np.arange(N * dim, dtype=np.int64).reshape(N, dim)
+    roots = lay["roots"] + np.arange(K, dtype=np.int64)
+    ind_c, _ = place_nearest(B, lay["units_c"], query, cent, lay["nearest_c"], 0)
+    croot, end = place_merkle(B, K, dim, lay["merkle_c"], lay["centroids"], fetch_flags, fetch_values)
+    assert end == lay["nearest_m"]
+    ind_m, res = place_nearest(B, lay["units_m"], query, cand, lay["nearest_m"], lay["lk_m"])
+    mroots = []
+    for r in range(p):
+        mroot, end = place_merkle(B, lay["sizes"][r], dim, lay["merkle_m"][r], lay["candidates"] + lay["offsets"][r] * dim, fetch_flags, fetch_values,
+                                  zero_cell=lay["zero_cell"] if lay["zero_cached"][r] else None)
+        assert end == (lay["merkle_m"][r + 1] if r + 1 < p else lay["select"][0])
+        mroots.append(mroot)
+    ind_c, ind_m, res = ind_c.reshape(p, K), ind_m.reshape(t, N), res.reshape(t, dim)
+    sel = B.place(lay["units_c"]["sb"], lay["select"], np.zeros(p, dtype=np.int64), np.concatenate([np.broadcast_to(roots, (p, K)), ind_c], axis=1))[:, 0]
+    for r in range(p):
+        B.tie(int(sel[r]), mroots[r])                        # constrain_equal(sel_r, mroot_r)
+    index_root, end = place_sponge(B, lay["sponge"], [croot] + [int(c) for c in roots], fetch_flags, fetch_values)
+    if end != lay["total"]:
+        raise ValueError("the trace does not end where the circuit does")
+    public = [int(c) for c in res.reshape(-1)] + [index_root]
+    return B.finish(), public, dict(centroid_indicators=ind_c, candidate_indicators=ind_m, results=res, centroids_root=croot, members_roots=mroots,
+                                    selected=[int(c) for c in sel], index_root=index_root, layout=lay)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # The Merkle path that updates and openings share: per level [assert_bit 4 | select 8 | select 8 | H] for the first running digest and
 # [select 8 | select 8 | H] for a second one (an update's new path), then the index inner product over the bits

@@ -747,6 +747,31 @@ __global__ __launch_bounds__(64) void k_nv_argmin(const u256* __restrict__ d, ui
     if (dist_out) dist_out[q] = best;
   }
 }
+// The winner of every round of k_nv_rounds as a value (vdb_nearest_topk_values_dev), one wavefront per (query, round): the LAST entry the
+// round works on whose bits equal the round's minimum pm[.. n - 1] — the last set indicator of the round's is_equal(min, cur_i), which
+// is what its select_by_indicator states.  The round's entries are read through nv_cur, so the last round needs no mark of its own.
+// A lane keeps the last hit of its stride (rising i), a butterfly of maxima joins the 64; every round has a hit (the minimum is one of
+// its entries), a round with nothing left unmasked works on M everywhere and states n - 1.  No LDS, no scratch.
+__global__ __launch_bounds__(64) void k_nv_round_winners(const FpTables* __restrict__ T, const u256* __restrict__ d, const u256* __restrict__ pm,
+                                                          const uint32_t* __restrict__ rnd, uint32_t n, uint32_t t, uint32_t* __restrict__ idx_out,
+                                                          u256* __restrict__ dist_out) {
+  const uint32_t qr = blockIdx.x, q = qr / t, r = qr % t, lane = threadIdx.x;
+  const u256* dq = d + (size_t)q * n;
+  const uint32_t* rq = rnd + (size_t)q * n;
+  const u256 M = nv_mask_value(T), m = pm[(size_t)qr * n + n - 1];
+  int best = -1;
+  for (uint32_t i = lane; i < n; i += 64)
+    if (u256_eq(nv_cur(dq, rq, i, r, M), m)) best = (int)i;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const int o = __shfl_xor(best, off, 64);
+    best = o > best ? o : best;
+  }
+  if (lane == 0) {
+    idx_out[qr] = (uint32_t)best;
+    if (dist_out) dist_out[qr] = m;
+  }
+}
 // lanes = (query, round, link of the round's chain): qmin(pm[i - 1], cur_i), i = 1 .. n - 1
 __global__ __launch_bounds__(64) void k_nv_qmin(Streams st, const FpTables* __restrict__ T, NvMap nm, const u256* __restrict__ d,
                                                  const u256* __restrict__ pm, const uint32_t* __restrict__ rnd) {
@@ -1599,6 +1624,29 @@ int nearest_values_dev(FpEntry* fp, int metric, const u256* queries, const u256*
   VDB_LAUNCH(k_nv_argmin, dim3((unsigned)Q), dim3(64), dist, (uint32_t)n, idx, dist_out);
   return VDB_OK;
 }
+// the same at p rounds (include/vdb.h vdb_nearest_topk_values_dev): the distances as above, every round's prefix minima and masks by the
+// witness call's own k_nv_rounds, then one wavefront per (query, round) for the round's winner.  idx / dist_out: (Q, p)
+int nearest_topk_values_dev(FpEntry* fp, int metric, const u256* queries, const u256* vectors, size_t Q, size_t n, size_t dim, size_t p, int* err,
+                            uint32_t* idx, u256* dist_out) {
+  DistLayout dl;
+  NvLayout nl;
+  TRY(nv_layout(fp, metric, n, dim, p, &dl, &nl));
+  TRY(nv_fits(Q, n, dim, p, nl));
+  Streams st{nullptr, nullptr, nullptr, err, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};   // the empty rank window
+  TRY(inv_list_attach(st, 0));
+  TRY(set_winv(st, fp->dev));
+  const size_t inst = Q * n, rinst = inst * p;
+  u256* mid = (u256*)scratch_get(0, (inst * 4 + rinst + 8) * sizeof(u256) + inst * sizeof(uint32_t));
+  if (!mid) return VDB_ERR_OOM;
+  u256* dist = mid + 3 * inst;
+  u256* pm = dist + inst;
+  uint32_t* rnd = (uint32_t*)(pm + rinst + 8);
+  InstMap im{0, 0, (uint32_t)n, nl.total, nl.total_l, (uint32_t)n, (uint32_t)n};  // (vector_{t % n}, query_{t / n})
+  TRY(run_distances(st, fp, dl, im, (uint32_t)inst, vectors, queries, mid, dist));
+  VDB_LAUNCH(k_nv_rounds, dim3((unsigned)Q), dim3(64), fp->dev, dist, (uint32_t)n, (uint32_t)p, pm, rnd);
+  VDB_LAUNCH(k_nv_round_winners, dim3((unsigned)(Q * p)), dim3(64), fp->dev, dist, pm, rnd, (uint32_t)n, (uint32_t)p, idx, dist_out);
+  return VDB_OK;
+}
 
 static int km_layout(FpEntry* fp, int metric, size_t n, size_t dim, size_t K, DistLayout* dl, KmLayout* kl) {
   TRY(dist_layout(fp->host, metric, dim, dl));
@@ -1990,6 +2038,127 @@ int wit_ann_query_dev(FpEntry* fp, int metric, const u256* query, const u256* ce
   const NvMap sm{a.b_sel, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, (uint32_t)K, 1u, 1u};
   VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), st, fp->dev, sm, 1u, cluster_roots, ind_c, picked);
   TRY(mk_leaf_states(sp, words, 1u, (uint32_t)(K + 1), a.mw.nperm, wstates, pub + dim, nullptr));
+  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((a.mw.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, words, 1u, (uint32_t)(K + 1), a.mw.nperm, a.b_root,
+             a.mw.leaf_cells, wstates, nullptr);
+  return inv_list_fixup(st);
+}
+
+// ------------------------------------------------------------------ the query over the p nearest clusters that returns the t nearest
+// candidates (include/vdb.h vdb_wit_ann_probe): the blocks of the query above, the two searches with p and t rounds, one members' tree
+// and one selection per probed cluster
+struct AnnpLayout {
+  DistLayout dl;
+  NvLayout nc, nm;
+  MkLayout mc, mw, mm[VDB_ANN_PROBE_MAX];
+  uint64_t off[VDB_ANN_PROBE_MAX + 1];   // candidate rows [off[r], off[r + 1]) are the cluster of round r
+  uint64_t b_mm[VDB_ANN_PROBE_MAX];
+  uint64_t N, n_in, b_nc, b_mc, b_nm, b_sel, b_root, total, l_nm, total_l;
+};
+static int annp_layout(FpEntry* fp, int metric, size_t K, size_t dim, size_t p, const size_t* n_c, size_t t, AnnpLayout* o) {
+  VDB_ARG(K > 0 && dim > 0, "K = 0 or dim = 0");
+  VDB_ARG(K <= VDB_ANN_MAX_CLUSTERS && dim <= ((size_t)1 << 20), "query too large (include/vdb.h)");
+  VDB_ARG(p >= 1 && p <= K, "probes: at least 1 and at most K");
+  VDB_ARG(p <= VDB_ANN_PROBE_MAX, "probes above VDB_ANN_PROBE_MAX");
+  VDB_ARG(n_c != nullptr, "null pointer");
+  o->off[0] = 0;
+  for (size_t r = 0; r < p; r++) {
+    VDB_ARG(n_c[r] > 0, "empty cluster");
+    VDB_ARG(n_c[r] <= VDB_ANN_MAX_VECTORS, "candidates above VDB_ANN_MAX_VECTORS");
+    o->off[r + 1] = o->off[r] + n_c[r];
+  }
+  const size_t N = o->N = o->off[p];
+  VDB_ARG(N <= VDB_ANN_MAX_VECTORS, "candidates above VDB_ANN_MAX_VECTORS");
+  VDB_ARG(t >= 1 && t <= N, "topk: at least 1 and at most the number of candidates");
+  TRY(nv_layout(fp, metric, K, dim, p, &o->dl, &o->nc));
+  TRY(nv_fits(1, K, dim, p, o->nc));
+  TRY(nv_layout(fp, metric, N, dim, t, &o->dl, &o->nm));
+  TRY(nv_fits(1, N, dim, t, o->nm));
+  // the chain of p + 1 trees in one context: the first padded one loads the zero cell, every later padded one copies it
+  mk_layout(K, dim, 0, &o->mc);
+  int zero = (int)o->mc.zero_cell;
+  mk_layout(1, K + 1, 1, &o->mw);
+  o->n_in = dim + K * dim + N * dim + K;
+  o->b_nc = o->n_in;
+  o->b_mc = o->b_nc + o->nc.total;
+  o->b_nm = o->b_mc + o->mc.total;
+  uint64_t at = o->b_nm + o->nm.total;
+  for (size_t r = 0; r < p; r++) {
+    mk_layout(n_c[r], dim, zero, &o->mm[r]);
+    zero |= (int)o->mm[r].zero_cell;
+    o->b_mm[r] = at;
+    at += o->mm[r].total;
+  }
+  o->b_sel = at;
+  o->b_root = o->b_sel + p * (1 + 3 * (uint64_t)K);
+  o->total = o->b_root + o->mw.total;
+  o->l_nm = o->nc.total_l;
+  o->total_l = o->nc.total_l + o->nm.total_l;
+  VDB_ARG(o->total <= VDB_NEAREST_TOPK_MAX_CELLS, "query circuit above 2^34 cells");
+  return VDB_OK;
+}
+// where the candidates lie: the p clusters' rows and the prefix sums of their sizes
+struct AnnpSegments {
+  const u256* rows[VDB_ANN_PROBE_MAX];
+  uint32_t pre[VDB_ANN_PROBE_MAX + 1];
+};
+// The candidates in one pass: lane i is word i of the N x dim candidates — consecutive lanes, consecutive words of one row — read from
+// the cluster whose prefix sums hold its row (bisection, as k_ann_forest_level finds its segment), written to the contiguous buffer the
+// second search reads and, inside the rank window, to its assigned cell (ctx.assign_witnesses: no gate, no constant flag).
+__global__ __launch_bounds__(256) void k_annp_gather(Streams st, uint64_t base, const AnnpSegments* __restrict__ sg, uint32_t p, uint32_t D,
+                                                     u256* __restrict__ cand) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (uint64_t)sg->pre[p] * D) return;
+  const uint32_t row = (uint32_t)(i / D), j = (uint32_t)(i % D);
+  uint32_t lo = 0, hi = p;   // the last segment s with pre[s] <= row (no segment is empty)
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (sg->pre[mid] <= row) lo = mid; else hi = mid;
+  }
+  const u256 v = sg->rows[lo][(uint64_t)(row - sg->pre[lo]) * D + j];
+  cand[i] = v;
+  const uint64_t pos = base + i;
+  if (pos < st.rlo || pos >= st.rhi) return;
+  st.adv[pos] = v;
+  if (st.sel) st.sel[pos] = 0;
+}
+// members: HOST array of the p clusters' rows on the device; levels_c / levels_m (HOST array of p): the p + 1 trees where they are
+// resident, or null.  pub: the t x dim result words, nearest first, then the index root.
+int wit_ann_probe_dev(FpEntry* fp, int metric, const u256* query, const u256* centroids, const u256* const* members, const u256* cluster_roots,
+                      const u256* levels_c, const u256* const* levels_m, size_t K, size_t dim, size_t p, const size_t* n_c, size_t t, Streams st,
+                      u256* ind_c, u256* ind_m, u256* pub) {
+  AnnpLayout a;
+  static thread_local AnnpSegments hseg;   // pageable source of an asynchronous upload: it outlives the call
+  TRY(annp_layout(fp, metric, K, dim, p, n_c, t, &a));
+  const PoseidonSpec* sp;
+  TRY(poseidon_spec_dev(&sp, nullptr));
+  const size_t N = a.N;
+  // work space of the call: [centroids' root | cluster roots], the p selected roots, the first search's results, the sponge's states,
+  // the candidates, the segment table
+  const size_t n_words = K + 1 + p + p * dim + 8 + (size_t)a.mw.nperm * PSD_T + N * dim;
+  u256* words = (u256*)scratch_get(7, n_words * sizeof(u256) + sizeof(AnnpSegments));
+  if (!words) return VDB_ERR_OOM;
+  u256 *picked = words + K + 1, *res_c = picked + p, *wstates = res_c + p * dim + 8, *cand = wstates + (size_t)a.mw.nperm * PSD_T;
+  AnnpSegments* dseg = (AnnpSegments*)(cand + N * dim);
+  TRY(inv_list_attach(st, a.total));
+  TRY(set_winv(st, fp->dev));
+  hipStream_t s = ctx().stream;
+  for (size_t r = 0; r < VDB_ANN_PROBE_MAX; r++) hseg.rows[r] = r < p ? members[r] : nullptr;
+  for (size_t r = 0; r <= VDB_ANN_PROBE_MAX; r++) hseg.pre[r] = (uint32_t)a.off[r < p ? r : p];
+  VDB_HIP(hipMemcpyAsync(dseg, &hseg, sizeof(AnnpSegments), hipMemcpyHostToDevice, s));
+  const uint64_t b_cand = dim + K * dim, b_roots = b_cand + N * dim;
+  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)((dim + K * dim + 255) / 256)), dim3(256), st, 0, query, centroids, (uint64_t)dim, (uint64_t)(dim + K * dim));
+  VDB_LAUNCH(k_annp_gather, dim3((unsigned)((N * dim + 255) / 256)), dim3(256), st, b_cand, dseg, (uint32_t)p, (uint32_t)dim, cand);
+  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)((K + 255) / 256)), dim3(256), st, b_roots, cluster_roots, cluster_roots, (uint64_t)K, (uint64_t)K);
+  TRY(nv_emit(fp, a.dl, a.nc, query, centroids, 1, K, dim, p, st, a.b_nc, 0, true, ind_c, res_c));
+  TRY(mk_emit(fp, sp, centroids, K, dim, a.mc, st, a.b_mc, levels_c, words));
+  TRY(nv_emit(fp, a.dl, a.nm, query, cand, 1, N, dim, t, st, a.b_nm, a.l_nm, true, ind_m, pub));
+  for (size_t r = 0; r < p; r++)
+    TRY(mk_emit(fp, sp, cand + a.off[r] * dim, n_c[r], dim, a.mm[r], st, a.b_mm[r], levels_m ? levels_m[r] : nullptr, nullptr));
+  VDB_HIP(hipMemcpyAsync(words + 1, cluster_roots, K * sizeof(u256), hipMemcpyDeviceToDevice, s));
+  // the p selections end to end: rounds of 1 + 3 K cells, one dimension, over the cluster roots
+  const NvMap sm{a.b_sel, 0, 0, 0, 0, 0, 1 + 3 * (uint64_t)K, 0, 0, 0, 0, 1u, (uint32_t)K, 1u, (uint32_t)p};
+  VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), st, fp->dev, sm, 1u, cluster_roots, ind_c, picked);
+  TRY(mk_leaf_states(sp, words, 1u, (uint32_t)(K + 1), a.mw.nperm, wstates, pub + t * dim, nullptr));
   VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((a.mw.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, words, 1u, (uint32_t)(K + 1), a.mw.nperm, a.b_root,
              a.mw.leaf_cells, wstates, nullptr);
   return inv_list_fixup(st);
@@ -2755,6 +2924,39 @@ int vdb_nearest_values(uint32_t P, uint32_t L, int metric, const vdb_fr* queries
   VDB_HIP(hipStreamSynchronize(ctx().stream));
   return VDB_OK;
 }
+// every round's minimum and the last entry at it, values only (include/vdb.h): no stream, no window
+int vdb_nearest_topk_values_dev(uint32_t P, uint32_t L, int metric, const vdb_fr* queries_dev, const vdb_fr* vectors_dev, size_t n_queries, size_t n,
+                                size_t dim, size_t p, uint32_t* idx_out_dev, vdb_fr* dist_out_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(queries_dev && vectors_dev && idx_out_dev && n_queries > 0 && n > 0 && dim > 0, "null pointer or empty input");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  int* derr;
+  TRY(err_word(&derr));
+  TRY(nearest_topk_values_dev(fp, metric, as_u256(queries_dev), as_u256(vectors_dev), n_queries, n, dim, p, derr, idx_out_dev, as_u256(dist_out_dev)));
+  return check_err_flag(derr);
+}
+int vdb_nearest_topk_values(uint32_t P, uint32_t L, int metric, const vdb_fr* queries, const vdb_fr* vectors, size_t n_queries, size_t n, size_t dim,
+                            size_t p, uint32_t* idx_out, vdb_fr* dist_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(queries && vectors && idx_out && n_queries > 0 && n > 0 && dim > 0, "null pointer or empty input");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  DistLayout dl;
+  NvLayout nl;
+  TRY(nv_layout(fp, metric, n, dim, p, &dl, &nl));
+  TRY(nv_fits(n_queries, n, dim, p, nl));   // before anything is uploaded
+  DevBuf dq, dv, didx, ddist;
+  TRY(upload(dq, queries, n_queries * dim * sizeof(u256)));
+  TRY(upload(dv, vectors, n * dim * sizeof(u256)));
+  TRY(didx.alloc(n_queries * p * sizeof(uint32_t)));
+  TRY(ddist.alloc(n_queries * p * sizeof(u256)));
+  TRY(vdb_nearest_topk_values_dev(P, L, metric, dq.as<vdb_fr>(), dv.as<vdb_fr>(), n_queries, n, dim, p, didx.as<uint32_t>(), ddist.as<vdb_fr>()));
+  TRY(download(idx_out, didx.p, n_queries * p * sizeof(uint32_t)));
+  TRY(download(dist_out, ddist.p, n_queries * p * sizeof(u256)));
+  VDB_HIP(hipStreamSynchronize(ctx().stream));
+  return VDB_OK;
+}
 
 // nearest_vector (vectordb.rs:122-163) for n_queries queries over one database, the calls end to end in the streams
 int vdb_wit_nearest_batch_size(int metric, uint32_t P, uint32_t L, size_t n_queries, size_t n, size_t dim, uint64_t* cells, uint64_t* lookups) {
@@ -3013,6 +3215,74 @@ int vdb_wit_ann_query(int metric, uint32_t P, uint32_t L, const vdb_fr* query, c
   TRY(download(member_indicator_out, dim_.p, n_c * sizeof(u256)));
   TRY(download(public_out, dpub.p, (dim + 1) * sizeof(u256)));
   return hs.finish(stream_out, lookup_out, selector_out, a.total, a.total_l);
+}
+
+// the query over the p nearest clusters (include/vdb.h)
+int vdb_wit_ann_probe_size(int metric, uint32_t P, uint32_t L, size_t K, size_t dim, size_t p, const size_t* n_c, size_t t, uint64_t* cells,
+                           uint64_t* lookups, uint64_t* input_cells) {
+  VDB_REQUIRE_INIT();
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  AnnpLayout a;
+  TRY(annp_layout(fp, metric, K, dim, p, n_c, t, &a));
+  if (cells) *cells = a.total;
+  if (lookups) *lookups = a.total_l;
+  if (input_cells) *input_cells = a.n_in;
+  return VDB_OK;
+}
+int vdb_wit_ann_probe_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* query_dev, const vdb_fr* centroids_dev, const vdb_fr* const* members_dev,
+                          const vdb_fr* cluster_roots_dev, const vdb_fr* centroid_levels_dev, const vdb_fr* const* member_levels_dev, size_t K, size_t dim,
+                          size_t p, const size_t* n_c, size_t t, vdb_fr* stream_dev, vdb_fr* lookup_dev, uint8_t* selector_dev,
+                          vdb_fr* centroid_indicators_dev, vdb_fr* candidate_indicators_dev, vdb_fr* public_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(query_dev && centroids_dev && members_dev && cluster_roots_dev && n_c && stream_dev && lookup_dev && centroid_indicators_dev &&
+              candidate_indicators_dev && public_dev,
+          "null pointer");
+  VDB_ARG(p >= 1 && p <= VDB_ANN_PROBE_MAX, "probes: at least 1 and at most VDB_ANN_PROBE_MAX");
+  size_t n_resident = centroid_levels_dev ? 1 : 0;
+  for (size_t r = 0; r < p; r++) {
+    VDB_ARG(members_dev[r], "null pointer");
+    if (member_levels_dev && member_levels_dev[r]) n_resident++;
+  }
+  VDB_ARG(n_resident == 0 || n_resident == p + 1, "the resident trees are given all together or not at all");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  DevStreams ds;
+  TRY(ds.init(stream_dev, selector_dev, lookup_dev));
+  TRY(wit_ann_probe_dev(fp, metric, as_u256(query_dev), as_u256(centroids_dev), (const u256* const*)members_dev, as_u256(cluster_roots_dev),
+                        n_resident ? as_u256(centroid_levels_dev) : nullptr, n_resident ? (const u256* const*)member_levels_dev : nullptr, K, dim, p, n_c, t,
+                        ds.st, as_u256(centroid_indicators_dev), as_u256(candidate_indicators_dev), as_u256(public_dev)));
+  return ds.finish();
+}
+int vdb_wit_ann_probe(int metric, uint32_t P, uint32_t L, const vdb_fr* query, const vdb_fr* centroids, const vdb_fr* candidates,
+                      const vdb_fr* cluster_roots, size_t K, size_t dim, size_t p, const size_t* n_c, size_t t, vdb_fr* stream_out, vdb_fr* lookup_out,
+                      uint8_t* selector_out, vdb_fr* centroid_indicators_out, vdb_fr* candidate_indicators_out, vdb_fr* public_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(query && centroids && candidates && cluster_roots && n_c, "null pointer");
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  AnnpLayout a;
+  TRY(annp_layout(fp, metric, K, dim, p, n_c, t, &a));
+  const uint64_t total = a.total, total_l = a.total_l;
+  const size_t N = a.N;
+  DevBuf dq, dc, dm, dr, dic, dim_, dpub;
+  HostStreams hs;
+  TRY(upload(dq, query, dim * sizeof(u256)));
+  TRY(upload(dc, centroids, K * dim * sizeof(u256)));
+  TRY(upload(dm, candidates, N * dim * sizeof(u256)));
+  TRY(upload(dr, cluster_roots, K * sizeof(u256)));
+  TRY(dic.alloc(p * K * sizeof(u256)));
+  TRY(dim_.alloc(t * N * sizeof(u256)));
+  TRY(dpub.alloc((t * dim + 1) * sizeof(u256)));
+  const u256* rows[VDB_ANN_PROBE_MAX];
+  for (size_t r = 0; r < p; r++) rows[r] = dm.as<u256>() + a.off[r] * dim;
+  TRY(hs.init(total, total_l, selector_out != nullptr));
+  TRY(wit_ann_probe_dev(fp, metric, dq.as<u256>(), dc.as<u256>(), rows, dr.as<u256>(), nullptr, nullptr, K, dim, p, n_c, t, hs.st, dic.as<u256>(),
+                        dim_.as<u256>(), dpub.as<u256>()));
+  TRY(download(centroid_indicators_out, dic.p, p * K * sizeof(u256)));
+  TRY(download(candidate_indicators_out, dim_.p, t * N * sizeof(u256)));
+  TRY(download(public_out, dpub.p, (t * dim + 1) * sizeof(u256)));
+  return hs.finish(stream_out, lookup_out, selector_out, total, total_l);
 }
 
 // inserts and replacements against the index root, and the index after them (include/vdb.h)

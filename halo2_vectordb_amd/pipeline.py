@@ -1327,6 +1327,21 @@ class AnnIndex:
         ind = api.wit_nearest(self.metric_name, q, self.qcent, self.P, self.L)["indicator"]
         return int(np.flatnonzero(ind.any(axis=1))[-1])
 
+    def probe_many(self, query, p):
+        """the clusters p rounds of top-k over the centroids state for `query` ((dim,) f64), in round order, (p,) int64: round r's entry
+        is the last centroid at the minimum of what the earlier rounds left — probe's rule round by round, so probe_many(q, 1)[0] ==
+        probe(q) — in one values-only call against the resident centroids (vdb_nearest_topk_values_dev).  Centroids at equal distance
+        leave in one round, which states the last of them: with fewer than p distance classes the entries are not pairwise distinct."""
+        d_q, d_idx = api.DeviceBuffer(self.dim * B), api.DeviceBuffer(max(int(p), 1) * 4)
+        try:
+            d_q.upload(api.quantize(np.ascontiguousarray(query, dtype=np.float64).reshape(1, self.dim), self.P))
+            check(self.lib.vdb_nearest_topk_values_dev(self.P, self.L, api.METRICS[self.metric_name], d_q.ptr, self.d_cent.ptr, 1, self.K, self.dim, int(p),
+                                                       d_idx.ptr, None))
+            return d_idx.download((int(p),), dtype=np.uint32).astype(np.int64)
+        finally:
+            d_q.free()
+            d_idx.free()
+
     def assign(self, rows, distances=False):
         """the cluster of every row of `rows` ((m, dim) f64): probe's answer for each — the last centroid at the minimum of the
         circuit's fixed-point distance — in one values-only call against the resident centroids (vdb_nearest_values_dev: nothing is
@@ -1474,6 +1489,97 @@ class AnnQueryHotPath(HotPath):
         from .circuit_dev import DeviceBuilder
         cm, public, _ = CS.build_ann_query(self.metric_name, self.K, self.n, self.dim, self.P, self.L, functools.partial(self._fetch_flags, d_flags),
                                            self._fetch, builder=DeviceBuilder if on_device else None)
+        assert cm.n_cells == self.n_cells
+        return cm, public, None
+
+
+class AnnProbeQueryHotPath(HotPath):
+    """The approximate-nearest-neighbour query with the two knobs of an IVF-style index, in ONE proof (include/vdb.h vdb_wit_ann_probe):
+    the `topk` nearest candidates over the members of the `probes` clusters whose centroids `probes` rounds of top-k over the committed
+    centroids state.  Assigned: the query, the centroids, the candidates (the probed clusters' members end to end in round order), the
+    K cluster roots; then nearest_topk(query, centroids, probes), merkle_commitment(centroids), nearest_topk(query, candidates, topk),
+    one merkle_commitment per probed cluster, one select_by_indicator(cluster roots, centroid indicators of round r) per round, tied
+    to that cluster's root, and the sponge over [centroids' root | cluster roots].  Public: the topk results nearest first, then the
+    index root; the query, the clusters probed and their sizes stay private (the sizes shape the proving key).  Not proved: that no
+    vector outside the probed clusters is nearer — that is what approximate means here.  `clusters`: the clusters probed, in round
+    order (None: index.probe_many(query, probes)); a list other than the rounds' breaks a copy constraint.  Centroids at equal distance
+    leave in one round, which states the last of them: a query with fewer than `probes` distance classes among the centroids probes
+    some cluster twice and is refused (ValueError).  `cluster_roots` / `centroids`: quantized overrides of what the index holds (tests
+    of the binding); with them the trees are hashed by the call instead of read from the forest."""
+
+    def __init__(self, index, query, probes=1, topk=1, clusters=None, k=13, P=48, L=12, metric="euclidean", tau=None, col_shard=(0, 1), blind_seed=None,
+                 params=None, cluster_roots=None, centroids=None):
+        query = np.ascontiguousarray(query, dtype=np.float64).reshape(1, index.dim)
+        self.index, self.K, self.probes, self.topk = index, index.K, int(probes), int(topk)
+        if not 1 <= self.probes <= self.K:
+            raise ValueError("probes: at least 1 and at most K")
+        self.clusters = [int(c) for c in (index.probe_many(query[0], self.probes) if clusters is None else clusters)]
+        if len(self.clusters) != self.probes or not all(0 <= c < self.K for c in self.clusters):
+            raise ValueError("one cluster of the index per probe")
+        if len(set(self.clusters)) != self.probes:
+            raise ValueError("the clusters probed are not pairwise distinct: fewer than `probes` distance classes among the centroids")
+        self.sizes = np.ascontiguousarray([index.sizes[c] for c in self.clusters], dtype=np.uint64)
+        self.cand_offsets = np.concatenate([[0], np.cumsum(self.sizes.astype(np.int64))])
+        super().__init__(int(self.sizes.sum()), index.dim, k, P, L, seed=None, tau=tau, col_shard=col_shard, vectors=query, blind_seed=blind_seed,
+                         params=params)
+        self.metric, self.metric_name = api.METRICS[metric], metric
+        self.given_roots, self.given_cent = cluster_roots, centroids
+
+    def n_input_rows(self):
+        return 1
+
+    def _load_inputs(self):
+        super()._load_inputs()
+        ix, self.resident = self.index, self.given_roots is None and self.given_cent is None
+        self.p_roots = _given_ptr(self, self.given_roots, (self.K, 4), ix.d_roots.at(B))
+        self.p_cent = _given_ptr(self, self.given_cent, (self.K, self.dim, 4), ix.d_cent.ptr)
+        as_ptrs = lambda ptrs: (ctypes.c_void_p * self.probes)(*[p.value for p in ptrs])
+        self.p_members = as_ptrs([ix.members_ptr(c) for c in self.clusters])
+        self.p_levels = as_ptrs([ix.levels_ptr(c) for c in self.clusters]) if self.resident else None
+
+    def _circuit_size(self):
+        cells, lk, n_in = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(self.lib.vdb_wit_ann_probe_size(self.metric, self.P, self.L, self.K, self.dim, self.probes, api._p(self.sizes), self.topk, ctypes.byref(cells),
+                                              ctypes.byref(lk), ctypes.byref(n_in)))
+        return n_in.value, cells.value - n_in.value, lk.value
+
+    def _alloc_outputs(self):
+        self.d_ind_c, self.d_ind_m = self._output(self.probes * self.K * B), self._output(self.topk * self.n * B)
+        self.d_pub = self._output((self.topk * self.dim + 1) * B)
+
+    def _witness(self, sel=None):
+        # the call writes the assigned witnesses too (centroids, candidates and roots where the index holds them)
+        ix = self.index
+        with self._window(sel, 0):
+            check(self.lib.vdb_wit_ann_probe_dev(self.metric, self.P, self.L, self.d_vec.ptr, self.p_cent, self.p_members, self.p_roots,
+                                                 ix.levels_ptr(self.K) if self.resident else None, self.p_levels, self.K, self.dim, self.probes,
+                                                 api._p(self.sizes), self.topk, self.d_stream.ptr, self.d_lookup.ptr, self._sel_at(sel, 0),
+                                                 self.d_ind_c.ptr, self.d_ind_m.ptr, self.d_pub.ptr))
+
+    def public_values_dev(self):
+        return self.d_pub.ptr, self.topk * self.dim + 1
+
+    def results(self):
+        """(centroid indicators (p, K, 4), candidate indicators (t, N, 4), results (t, dim, 4) nearest first, index root (4,))"""
+        t, pub = self.topk, self.d_pub.download((self.topk * self.dim + 1, 4))
+        return (self.d_ind_c.download((self.probes, self.K, 4)), self.d_ind_m.download((t, self.n, 4)), pub[:t * self.dim].reshape(t, self.dim, 4),
+                pub[t * self.dim])
+
+    def neighbours(self):
+        """(t,) int64: the database slots of the results, nearest first — the last set indicator of every round of the candidate
+        search, through the candidates' place in their cluster's grouped rows, to index.d_slots"""
+        ind = self.d_ind_m.download((self.topk, self.n, 4)).any(axis=2)
+        cand = np.asarray([int(np.flatnonzero(row)[-1]) for row in ind], dtype=np.int64)
+        r = np.searchsorted(self.cand_offsets, cand, side="right") - 1
+        grouped = np.asarray([self.index.offsets[self.clusters[j]] for j in r], dtype=np.int64) + cand - self.cand_offsets[r]
+        slots = self.index.d_slots.download((self.index.n,), dtype=np.uint32).astype(np.int64)
+        return slots[grouped]
+
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        cm, public, _ = CS.build_ann_probe(self.metric_name, self.K, [int(x) for x in self.sizes], self.dim, self.probes, self.topk, self.P, self.L,
+                                           functools.partial(self._fetch_flags, d_flags), self._fetch, builder=DeviceBuilder if on_device else None)
         assert cm.n_cells == self.n_cells
         return cm, public, None
 

@@ -388,6 +388,54 @@ int vdb_wit_ann_query_dev(int metric, uint32_t precision_bits, uint32_t lookup_b
                           size_t K, size_t n_c, size_t dim, vdb_fr *stream_dev, vdb_fr *lookup_dev, uint8_t *selector_dev,
                           vdb_fr *centroid_indicator_dev, vdb_fr *member_indicator_dev, vdb_fr *public_dev);
 
+/* The query over the p nearest clusters that returns the t nearest candidates, in one circuit bound to one index root: the two knobs of
+ * an IVF-style index.  The reference's demo (tests/demo/mod.rs:47-90) searches one cluster for one vector, in two circuits; this is the
+ * closure a user of its chips writes for p probes and t neighbours, every block one of the gadgets above.  n_c[r]: the size of the
+ * cluster that round r of the centroid search states, N = sum n_c[r].  Assigned, from cell 0: the query (dim), the centroids (K x dim),
+ * the candidates (N x dim: the members of the p probed clusters end to end in round order), the K cluster roots: input_cells of them.
+ *   ind_c (p x K), _      = nearest_topk(query, centroids, p)        croot   = merkle_commitment(centroids)
+ *   ind_m (t x N), result = nearest_topk(query, candidates, t)       mroot_r = merkle_commitment(candidates[o_r, o_r + n_c[r]))  r < p
+ *   sel_r = gate.select_by_indicator(cluster_roots, ind_c[r])        (1 + 3 K cells each, the p of them end to end)
+ *   index_root = the sponge over [croot, cluster_roots ..]
+ * and the circuit ties sel_r to mroot_r for every r (copies, no cell): the candidates are exactly the members committed under the roots
+ * of the centroids the p rounds state.  Context::load_zero caches its cell: among the trees [centroids, members_0 .. members_{p-1}] the
+ * first padded one emits the zero cell, every later padded one copies it.  Lookup cells: the two searches', in block order.  public
+ * t x dim + 1 values: the t results nearest first, then index_root; the query, the clusters probed and their sizes stay private (the
+ * sizes shape the verifying key).  NOT stated: that no vector outside the probed clusters is nearer — the answer is approximate.
+ * Ties are vdb_wit_nearest_topk's: centroids at equal distance leave in the same round, which states the LAST of them — two centroids
+ * tied nearest cost one probe and the earlier one is never searched; a round with nothing left unmasked states centroid K - 1 again.
+ * The entry points take whatever cluster list they are given: candidates of other clusters still give a stream, which breaks a
+ * sel_r = mroot_r copy.  At p == t == 1 the streams, flags and public values are vdb_wit_ann_query's byte for byte.
+ * vdb_wit_ann_probe: candidates is one flat N x dim host array; the call hashes the trees itself.  vdb_wit_ann_probe_dev: members_dev is a
+ * HOST array of p device pointers to the clusters' rows, member_levels_dev a HOST array of p device pointers to their trees (forest
+ * segments) or NULL, centroid_levels_dev the centroids' tree or NULL: the p + 1 resident trees come all together or not at all
+ * (VDB_ERR_ARG otherwise), and the caller answers for their being the trees of these rows, as above.  With them the launch count depends
+ * on p (one tree trace per probed cluster) and on neither K, any n_c[r] nor t.  One gather pass writes the candidates' assigned cells and
+ * the contiguous buffer the second search reads.  centroid_indicators p x K, candidate_indicators t x N raw 0/1 bits.  The _dev form
+ * honours vdb_wit_set_window.  VDB_ERR_ARG before anything is launched: K == 0, dim == 0, dim > 2^20, K > VDB_ANN_MAX_CLUSTERS, p == 0,
+ * p > K, p > VDB_ANN_PROBE_MAX, an empty cluster, N > VDB_ANN_MAX_VECTORS, t == 0, t > N, the limits of vdb_wit_nearest_topk for each of
+ * the two searches, more than 2^34 cells. */
+#define VDB_ANN_PROBE_MAX 16
+int vdb_wit_ann_probe_size(int metric, uint32_t precision_bits, uint32_t lookup_bits, size_t K, size_t dim, size_t p, const size_t *n_c, size_t t,
+                           uint64_t *cells, uint64_t *lookups, uint64_t *input_cells);
+int vdb_wit_ann_probe(int metric, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *query, const vdb_fr *centroids, const vdb_fr *candidates,
+                      const vdb_fr *cluster_roots, size_t K, size_t dim, size_t p, const size_t *n_c, size_t t, vdb_fr *stream_out, vdb_fr *lookup_out,
+                      uint8_t *selector_out, vdb_fr *centroid_indicators_out, vdb_fr *candidate_indicators_out, vdb_fr *public_out);
+int vdb_wit_ann_probe_dev(int metric, uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *query_dev, const vdb_fr *centroids_dev,
+                          const vdb_fr *const *members_dev /* host array */, const vdb_fr *cluster_roots_dev, const vdb_fr *centroid_levels_dev,
+                          const vdb_fr *const *member_levels_dev /* host array or NULL */, size_t K, size_t dim, size_t p, const size_t *n_c, size_t t,
+                          vdb_fr *stream_dev, vdb_fr *lookup_dev, uint8_t *selector_dev, vdb_fr *centroid_indicators_dev,
+                          vdb_fr *candidate_indicators_dev, vdb_fr *public_dev);
+/* The winners of p rounds of top-k as VALUES alone (vdb_nearest_values at p rounds): for every query q and round r < p the minimum of
+ * the entries the earlier rounds left and the LAST i at it — the index vdb_wit_nearest_topk's select_by_indicator states for that round,
+ * ties and exhausted rounds as there.  idx_out n_queries x p uint32, dist_out n_queries x p values or NULL.  The launch count depends on
+ * neither n_queries, n nor p.  Work space: vdb_wit_nearest_topk's.  VDB_ERR_ARG before anything is launched: n_queries, n or dim == 0 and
+ * vdb_wit_nearest_topk's limits at topk == p; VDB_ERR_DOMAIN as for the witness call. */
+int vdb_nearest_topk_values_dev(uint32_t precision_bits, uint32_t lookup_bits, int metric, const vdb_fr *queries_dev, const vdb_fr *vectors_dev,
+                                size_t n_queries, size_t n, size_t dim, size_t p, uint32_t *idx_out_dev, vdb_fr *dist_out_dev);
+int vdb_nearest_topk_values(uint32_t precision_bits, uint32_t lookup_bits, int metric, const vdb_fr *queries, const vdb_fr *vectors, size_t n_queries,
+                            size_t n, size_t dim, size_t p, uint32_t *idx_out, vdb_fr *dist_out);
+
 /* Inserts and replacements proved against the committed index root: m writes into ONE cluster c of an index of K clusters move
  * index_root_old to index_root_new in one circuit.  The reference has no such gadget; the cells are those of the closure a user of its
  * chips writes.  n_c = |members(c)| before the batch, lp the power of two >= n_c, depth = log2(lp) + grow >= 1; the cluster's tree may

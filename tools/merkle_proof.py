@@ -20,6 +20,9 @@ the verifier check the proof.
 (pipeline.AnnIndex, AnnQueryHotPath: the first C vectors are the centroids, every vector belongs to its nearest one; nearest_vector over
 the centroids and over the winning cluster, both commitments, the selected cluster root tied to the members' root, [result | index_root]
 public), and has the verifier check the proof.  The circuit's size follows the cluster searched, not n.
+With `--probes p` and / or `--topk t` above 1 it proves the t nearest vectors over the p nearest clusters in one proof instead
+(pipeline.AnnProbeQueryHotPath: top-k with p rounds over the centroids, with t rounds over the probed clusters' members, one commitment
+and one tied root selection per probed cluster, [t results nearest first | index_root] public); the defaults, 1 and 1, keep the path above.
 `--circuit ann-update --K C --updates M [--grow G]` proves M writes into one cluster of that index against its root
 (pipeline.AnnUpdateHotPath: the first write replaces member 0 of the largest cluster, the others append to it; [index_root_old | c | idx, old
 leaf, new leaf per write | index_root_new] public; `--grow` defaults to the smallest number of doublings that fits the appends), has the
@@ -49,7 +52,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from halo2_vectordb_amd import api  # noqa: E402
-from halo2_vectordb_amd.pipeline import AnnAuditHotPath, AnnDeleteHotPath, AnnMeanHotPath, AnnRecentreHotPath, AnnIndex, AnnQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
+from halo2_vectordb_amd.pipeline import AnnAuditHotPath, AnnDeleteHotPath, AnnMeanHotPath, AnnRecentreHotPath, AnnIndex, AnnProbeQueryHotPath, AnnQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
 from halo2_vectordb_amd.rounds import ProverRounds, quotient_identity_holds  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -64,7 +67,8 @@ ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "upda
 ap.add_argument("--lookup-bits", type=int, default=13)
 ap.add_argument("--metric", default="euclidean")
 ap.add_argument("--queries", type=int, default=1, help="--circuit query: queries proved against the one database in this proof")
-ap.add_argument("--topk", type=int, default=1, help="--circuit query: nearest vectors proved per query, nearest first")
+ap.add_argument("--topk", type=int, default=1, help="--circuit query / ann: nearest vectors proved per query, nearest first")
+ap.add_argument("--probes", type=int, default=1, help="--circuit ann: clusters searched, the nearest centroids' in the order the top-k rounds state them")
 ap.add_argument("--updates", type=int, default=8, help="--circuit update: inserts / replacements proved in this proof")
 ap.add_argument("--deletes", type=int, default=0, help="--circuit update: the last K updates empty their slot instead of writing it; --circuit ann-delete: deletes proved")
 ap.add_argument("--grow", type=int, default=None, help="--circuit update / ann-update: doublings of the padded leaf count before the first update")
@@ -82,8 +86,11 @@ if args.queries < 1 or (args.queries > 1 and args.circuit != "query"):
 if args.deletes and args.circuit not in ("update", "ann-delete") or args.grow is not None and args.circuit not in ("update", "ann-update"):
     raise SystemExit("--deletes needs --circuit update or ann-delete, --grow --circuit update or ann-update")
 ann_grow, args.grow = args.grow, args.grow or 0
-if args.topk < 1 or (args.topk > 1 and args.circuit != "query"):
-    raise SystemExit("--topk needs --circuit query and at least one neighbour")
+if args.topk < 1 or (args.topk > 1 and args.circuit not in ("query", "ann")):
+    raise SystemExit("--topk needs --circuit query or ann and at least one neighbour")
+if args.probes < 1 or (args.probes > 1 and args.circuit != "ann"):
+    raise SystemExit("--probes needs --circuit ann and at least one cluster")
+multi_probe = args.circuit == "ann" and (args.probes > 1 or args.topk > 1)
 if args.circuit == "query" and args.topk > 1:
     hp = TopKQueryHotPath(topk=args.topk, q=args.queries, n=args.n, dim=args.dim, k=args.k, L=args.lookup_bits, metric=args.metric, seed=args.seed)
 elif args.circuit == "query" and args.queries > 1:
@@ -125,6 +132,8 @@ elif args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit", "ann-mean"
             raise SystemExit("--K is at least 2: a centroids' tree of one leaf has no path")
         c = int(np.argmax(index.sizes)) if args.cluster is None else args.cluster
         hp = AnnRecentreHotPath(index, c, k=args.k, L=args.lookup_bits)
+    elif multi_probe:
+        hp = AnnProbeQueryHotPath(index, query, probes=args.probes, topk=args.topk, k=args.k, L=args.lookup_bits, metric=args.metric)
     elif args.circuit == "ann":
         hp = AnnQueryHotPath(index, query, k=args.k, L=args.lookup_bits, metric=args.metric)
     elif args.circuit == "ann-delete":
@@ -178,6 +187,8 @@ if args.circuit == "ann-update":
     index2 = index.updated(hp)
     accepted["applied_index_root_is_the_public_new_root"] = bool(np.array_equal(index2.roots()[-1], hp.results()[-1]))
     index2.free()
+if multi_probe:
+    accepted["neighbours"] = hp.neighbours().tolist()
 if args.circuit == "ann-audit":
     accepted["members_routed"] = int(hp.results()[2].sum())
 if args.circuit == "ann-mean":
@@ -194,6 +205,7 @@ if args.circuit == "ann-delete":
 what = f"merkle_commitment {args.n}x{args.dim} k={args.k}" if args.circuit == "merkle" else \
     f"{args.updates} Merkle path updates ({args.deletes} deletes, tree grown {args.grow} times) against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "update" else \
     f"{args.reads} Merkle openings ({'leaves' if args.leaf_only else 'vectors'} public) against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "read" else \
+    f"ann query (K={args.K}, the {args.topk} nearest of the {hp.n} vectors of clusters {hp.clusters}, {args.metric}) against the index of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if multi_probe else \
     f"ann query (K={args.K}, cluster {hp.cluster} of {hp.n} vectors, {args.metric}) against the index of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann" else \
     f"{args.updates} writes into cluster {hp.cluster} ({hp.n} members, tree grown {hp.grow} times) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-update" else \
     f"routing audit of cluster {hp.cluster} ({hp.n} members, {args.metric}) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann-audit" else \
