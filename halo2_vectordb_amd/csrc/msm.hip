@@ -24,6 +24,10 @@
 //  * k_msm_reduce: one wavefront per column; each lane folds its slice of buckets with the running-sum
 //    trick, lanes are combined with wavefront shuffles (nine-limb form throughout: ec_l9.hpp).
 //  * k_msm_normalise: one lane per column brings the column's sum to canonical affine (the inversion).
+//  * The driver, msm_batch_dev, decides nothing between its launches: the window of a table, the range length, the capacities, the
+//    scatter's bit split, LDS sizes, the batch size under the memory budget and the layout of the work space are msm_plan.hpp's
+//    (host-only; tools/msm_plan_probe.hip and tests/test_msm_plan_cpu.py hold it to a model on the CPU).  The entry points fill an
+//    MsmCall by name and share one argument check, one deferred prologue and one copy-out.
 // Roofline: algorithmic HBM traffic is 32 B per scalar (+ bases once); the kernels are bound by 32-bit
 // integer multiply-add throughput (v_mad_u64_u32), see DESIGN.md.
 #include "common.hpp"
@@ -31,6 +35,7 @@
 #include "ec_l9.hpp"
 #include "limb9.hpp"
 #include "msm_digits.hpp"
+#include "msm_plan.hpp"
 
 struct vdb_srs {
   uint32_t k;
@@ -44,22 +49,7 @@ struct vdb_srs {
 
 namespace vdb {
 
-#define MSM_SORT_THREADS 1024
-// Range length (entries one thread of k_msm_accum adds up) is chosen per batch: long ranges mean fewer segments, i.e.
-// less work for k_msm_combine (256: 4 ms of combine on the k = 16 kmeans workload against 20 ms at 32, measured on the
-// eight-word folding), short ranges keep small jobs parallel (a single 2^16 column has only ~130 k entries).
-#define MSM_LCAP_MIN 32
-#define MSM_LCAP_MAX 256
-
-// A range is `lcap` consecutive entries of one column's bucket-sorted entry list.  Inside a range every change of
-// bucket starts a new *segment*; each segment produces one partial sum.  Segment numbering follows the sorted order,
-// so the partials of one bucket are contiguous: [seg_off[b], seg_off[b + 1]).
-struct MsmRange {
-  uint32_t col, bucket, start, len, seg0, pad;
-};
-struct MsmSegInfo {
-  uint32_t idx, len;  // position of the segment among its bucket's segments, and how many the bucket has
-};
+// MSM_SORT_THREADS, the range length bounds, MsmRange and MsmSegInfo: msm_plan.hpp
 
 // ---------------------------------------------------------------- table precompute
 __global__ __launch_bounds__(256) void k_srs_table(const Affine* __restrict__ bases, Affine* __restrict__ table, size_t n, uint32_t c, uint32_t W) {
@@ -379,8 +369,7 @@ __global__ __launch_bounds__(MSM_SORT_THREADS, 8) void k_msm_sort(const u256* __
 
 // second phase of the two-phase scatter: one workgroup per (bin, column) loads the bin's entries (coarse order) into LDS and writes
 // them back bucket by bucket — 2^fine_bits open runs per workgroup, which L2 merges into whole lines
-#define MSM_SCATTER2_THREADS 256
-#define MSM_BIN_CAP (6 * 1024)   // entries of a bin a workgroup holds (24 registers per thread, 24 KB of LDS)
+// (MSM_SCATTER2_THREADS threads; MSM_BIN_CAP, the entries of a bin a workgroup holds: msm_plan.hpp)
 __global__ __launch_bounds__(MSM_SCATTER2_THREADS) void k_msm_scatter2(uint32_t* __restrict__ entries, size_t ent_cap, const uint32_t* __restrict__ bucket_off,
                                                                        uint32_t B, uint32_t fine_bits, uint32_t idx_bits, uint32_t bin_cap,
                                                                        const uint32_t* __restrict__ counters) {
@@ -440,8 +429,7 @@ __global__ __launch_bounds__(MSM_SCATTER2_THREADS) void k_msm_scatter2(uint32_t*
 // folding works on these records as they are (xyzz_add_l9 takes and leaves the accumulator's form): k_msm_combine folds them
 // in place, k_msm_reduce reads them and leaves one such record per column, and only k_msm_normalise converts — one column's
 // sum, not every segment (a conversion kernel used to bring all segments to eight-word XYZZ: four products and a canonical
-// form each, which the folding then split into limbs again).
-#define MSM_RAW_WORDS 36
+// form each, which the folding then split into limbs again).  MSM_RAW_WORDS: msm_plan.hpp
 __device__ __forceinline__ void flush_l9(uint4* dst, const AccL9& acc, bool ident) {
   const uint32_t z = ident ? 0u : 0xffffffffu;
   dst[0] = make_uint4(acc.x.l[0], acc.x.l[1], acc.x.l[2], acc.x.l[3]);
@@ -687,124 +675,121 @@ __global__ __launch_bounds__(64) void k_g1_sum(const Affine* __restrict__ parts,
   st_affine(out + c, xyzz_to_affine(acc));
 }
 
-static uint32_t pick_window(uint32_t k) {
-  const char* env = getenv("VDB_MSM_C");
-  if (env) {
-    int v = atoi(env);
-    if (v >= 2 && v <= 14) return (uint32_t)v;
-  }
-  // measured on the C4 witness columns (profiles/): per-task overhead of the many light buckets outweighs the
-  // extra digits of a smaller window; c = 11 is the optimum for k = 16
-  if (k <= 8) return 8;
-  return 11;
+static_assert(MSM_PLAN_OK == VDB_OK && MSM_PLAN_REFUSED == VDB_ERR_ARG, "msm_plan.hpp returns the C ABI's codes");
+
+// the process's knobs, read from the environment once
+static const MsmKnobs& msm_knobs() {
+  static const MsmKnobs knobs = [] {
+    MsmKnobs k;
+    if (const char* e = getenv("VDB_MSM_C")) k.window = (uint32_t)atoi(e);
+    return k;
+  }();
+  return knobs;
 }
 
-// device-level batched MSM: scalars_dev = n_cols x n (contiguous), out_dev = n_cols affine points
-// `defer_tail`: the bucket folding of the LAST batch (k_msm_combine, k_msm_reduce, k_msm_normalise) goes to the context's
-// auxiliary stream and the function returns without waiting; msm_collect() joins.  The scalars are no longer read at that
-// point, so the caller may overwrite them (NTT in place).  The folding is not free there: it fills the chip's issue slots
+// One batched MSM: n_cols columns of n scalars against the tables of `srs`, one affine point per column.  A caller sets what it asks
+// for by name.
+struct MsmCall {
+  const vdb_srs* srs = nullptr;
+  int basis = 0;
+  const u256* scalars = nullptr;       // n_cols x n, contiguous; null with `srcs`
+  const ColSrc* srcs = nullptr;        // per column: where it still lies in a witness stream
+  uint32_t n_blind = 0;
+  size_t n_cols = 0, n = 0;
+  Affine* out = nullptr;               // device: n_cols points
+  const uint8_t* skip_mask = nullptr;  // n per column: cells left out (their terms are part of add_points)
+  const Affine* add_points = nullptr;  // per column: added to its sum
+  // the bucket folding of the LAST batch (k_msm_combine, k_msm_reduce, k_msm_normalise) goes to the context's auxiliary stream and
+  // the driver returns without waiting; msm_collect() joins
+  bool defer_tail = false;
+};
+
+// the work space of a batch: the plan's regions as pointers
+struct MsmWork {
+  uint32_t* entries;
+  uint4 *raw, *sums;
+  MsmRange* ranges;
+  MsmSegInfo* seginfo;
+  uint32_t *seg_off, *bucket_off, *counters;
+  unsigned long long* recs;
+  uint32_t* longq;
+  template <class T>
+  static T* at(uint8_t* buf, const MsmPlan& P, MsmRegion r) {
+    return reinterpret_cast<T*>(buf + P.off[r]);
+  }
+  MsmWork(uint8_t* buf, const MsmPlan& P)
+      : entries(at<uint32_t>(buf, P, MSM_ENTRIES)), raw(at<uint4>(buf, P, MSM_RAW)), sums(at<uint4>(buf, P, MSM_SUMS)),
+        ranges(at<MsmRange>(buf, P, MSM_RANGES)), seginfo(at<MsmSegInfo>(buf, P, MSM_SEGINFO)), seg_off(at<uint32_t>(buf, P, MSM_SEG_OFF)),
+        bucket_off(at<uint32_t>(buf, P, MSM_BUCKET_OFF)), counters(at<uint32_t>(buf, P, MSM_COUNTERS)),
+        recs(at<unsigned long long>(buf, P, MSM_RECS)), longq(at<uint32_t>(buf, P, MSM_LONGQ)) {}
+};
+
+// Device-level batched MSM.  Plans the job (msm_plan.hpp: range length, capacities, scatter, batch size under the memory budget, the
+// layout of the work space), fetches the work space and runs the batches.
+// With `defer_tail` the scalars are no longer read when the function returns, so the caller may overwrite them (NTT in place).  The
+// folding is not free on the auxiliary stream: it fills the chip's issue slots
 // and registers like any other kernel, and the transform launches that run beside it take longer by most of what it costs
 // alone (profiles/NOTES.md, "bucket folding beside the transforms": the first two launches of lagrange_to_coeff, 2.3 and
 // 2.1 ms alone, took 4.9 and 6.5 ms beside the eight-word folding and its 213-register k_msm_reduce, 5.1 and 3.4 ms beside
 // this one).  What it saves is the dependency: the transforms need not wait for the commitments.
-int msm_batch_dev(const vdb_srs* srs, int basis, const u256* scalars_dev, size_t n_cols, size_t n, Affine* out_dev, const uint8_t* skip_mask = nullptr,
-                  const Affine* add_points = nullptr, bool defer_tail = false, const ColSrc* srcs = nullptr, uint32_t n_blind = 0) {
+static int msm_batch_dev(const MsmCall& m) {
   Context& cx = ctx();
-  if (g_prof_mode == 1) defer_tail = false;  // per-kernel timing serialises on the main stream
+  const bool defer_tail = m.defer_tail && g_prof_mode != 1;  // per-kernel timing serialises on the main stream
   if (cx.msm_pending) {
     set_error("msm: a deferred batch has not been collected (vdb_msm_batch_end)");
     return VDB_ERR_ARG;
   }
+  const size_t n_cols = m.n_cols, n = m.n;
   if (n_cols == 0) return VDB_OK;
-  const Affine* table = srs->table[basis];
+  const vdb_srs* srs = m.srs;
+  const Affine* table = srs->table[m.basis];
   const uint32_t c = srs->c, W = srs->W, B = srs->B;
-  const size_t ent_cap = n * W;
-  uint32_t lcap = MSM_LCAP_MIN;
-  while (lcap < MSM_LCAP_MAX && (n_cols * n) / lcap >= ((size_t)1 << 19)) lcap <<= 1;  // keep >= ~2^20 ranges in a large job
-  const size_t range_cap_col = (ent_cap + lcap - 1) / lcap;  // worst case: every digit non-zero
-  const size_t seg_cap_col = B + range_cap_col;
-  // large batches keep thousands of independent column reductions in flight
-  size_t per_col = ent_cap * 4 + range_cap_col * sizeof(MsmRange) + seg_cap_col * (sizeof(MsmSegInfo) + MSM_RAW_WORDS * 4) + MSM_RAW_WORDS * 4 + 2 * (B + 1) * 4 +
-                   n * 12;
-  // two-phase scatter of the sort: bins of 2^fine_bits buckets; the table index and the fine bucket number share an entry's 31 bits
-  static const bool two_phase_on = !(getenv("VDB_MSM_TWO_PHASE") && getenv("VDB_MSM_TWO_PHASE")[0] == '0');
-  uint32_t idx_bits = 1;
-  while (((uint64_t)1 << idx_bits) < (uint64_t)W * srs->n) idx_bits++;
-  uint32_t fine_bits = 0;
-  const uint32_t bin_cap = MSM_BIN_CAP;
-  // (only where the direct scatter is what the sort waits for: thousands of buckets per column and dense scalars — the 14-bit windows
-  //  of the product / quotient / fixed columns; with the 11-bit windows of the witness columns, 1,024 buckets and mostly short scalars,
-  //  the second phase costs more than it saves: 15.4 + 4.2 against 15.2 ms per C4 step)
-  if (two_phase_on && c >= 13) {
-    fine_bits = c - 1 - 8;              // 256 bins
-    if (fine_bits + idx_bits > 31) fine_bits = idx_bits < 31 ? 31 - idx_bits : 0;
-    if (fine_bits < 2) fine_bits = 0;
+  MsmMem mem = {0, cx.scratch_bytes[2], cx.msm_scratch_cap};
+  size_t total_b = 0;
+  if (hipMemGetInfo(&mem.free_bytes, &total_b) != hipSuccess) mem.free_bytes = (size_t)80 << 30;
+  MsmPlan P;
+  const char* why = nullptr;
+  if (int rc = msm_plan(MsmShape{c, W, B, srs->n}, MsmJob{n_cols, n}, mem, &P, &why)) {
+    set_error("%s", why);
+    return rc;
   }
-  // budget: half of what is free on the card (counting the slot this buffer already holds), between 8 and 96 GiB —
-  // on a 288 GB MI355X the 8,146 columns of the kmeans k = 16 job go through in ONE batch (76 GB), so the whole
-  // bucket-folding tail can run beside the NTTs (defer_tail)
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)80 << 30;
-  size_t budget = (free_b + cx.scratch_bytes[2]) / 2;
-  if (budget < ((size_t)8 << 30)) budget = (size_t)8 << 30;
-  if (budget > ((size_t)96 << 30)) budget = (size_t)96 << 30;
-  // a caller that is about to allocate tens of GB of its own (keygen) bounds the work space: growing it to half of a still empty
-  // card and releasing it again costs seconds of page mapping (vdb_msm_set_scratch_cap)
-  if (cx.msm_scratch_cap && budget > cx.msm_scratch_cap) budget = cx.msm_scratch_cap > cx.scratch_bytes[2] ? cx.msm_scratch_cap : cx.scratch_bytes[2];
-  size_t nb = budget / per_col;
-  if (nb < 1) nb = 1;
-  if (nb > n_cols) nb = n_cols;
-  if (nb > 16384) nb = 16384;
-  if (nb * seg_cap_col > 0x7fffffffull) nb = 0x7fffffffull / seg_cap_col;
-  uint8_t* buf = (uint8_t*)scratch_get(2, nb * per_col + 512);
+  uint8_t* buf = (uint8_t*)scratch_get(2, P.bytes);
   if (!buf) return VDB_ERR_OOM;
-  uint32_t* entries = (uint32_t*)buf;
-  uint4* raw = (uint4*)(buf + nb * ent_cap * 4);                                 // one record per segment, folded in place
-  uint4* sums = (uint4*)((uint8_t*)raw + nb * seg_cap_col * MSM_RAW_WORDS * 4);  // one record per column: what k_msm_reduce leaves
-  MsmRange* ranges = (MsmRange*)((uint8_t*)sums + nb * MSM_RAW_WORDS * 4);
-  MsmSegInfo* seginfo = (MsmSegInfo*)((uint8_t*)ranges + nb * range_cap_col * sizeof(MsmRange));
-  uint32_t* seg_off = (uint32_t*)((uint8_t*)seginfo + nb * seg_cap_col * sizeof(MsmSegInfo));
-  uint32_t* bucket_off = seg_off + nb * (B + 1);
-  uint32_t* counters = bucket_off + nb * (B + 1);
-  unsigned long long* recs = (unsigned long long*)(((uintptr_t)(counters + 64) + 7) & ~(uintptr_t)7);  // n records per column
-  uint32_t* longq = (uint32_t*)(recs + nb * n);                       // then n queue entries per column
-  const uint32_t seg_cap = (uint32_t)(nb * seg_cap_col), range_cap = (uint32_t)(nb * range_cap_col);
-  size_t lds = (3 * (size_t)B + 32) * sizeof(uint32_t);
+  const MsmWork w(buf, P);
   MsmL9Consts l9k;
   l9_offset_limbs<FqParams>(2, l9k.c2);
   l9_offset_limbs<FqParams>(8, l9k.c8);
   l9k.one_rp = to_mont<Fq>(u256_from_u64(32));
   l9k.to_std = mont_one<Fq>();
   l9k.to_rp = to_mont<Fq>(u256_from_u64(1024));
-  for (size_t c0 = 0; c0 < n_cols; c0 += nb) {
-    size_t nc = n_cols - c0 < nb ? n_cols - c0 : nb;
+  for (size_t c0 = 0; c0 < n_cols; c0 += P.nb) {
+    size_t nc = n_cols - c0 < P.nb ? n_cols - c0 : P.nb;
     // counters[1], the overflow flag, is read once after the last batch: cleared before the first batch only, so that an overflow
     // in any batch (whose k_msm_reduce leaves its points unwritten) still fails the call; the other three words are per batch
     if (c0 == 0) {
-      VDB_HIP(hipMemsetAsync(counters, 0, 4 * sizeof(uint32_t), cx.stream));
+      VDB_HIP(hipMemsetAsync(w.counters, 0, 4 * sizeof(uint32_t), cx.stream));
     } else {
-      VDB_HIP(hipMemsetAsync(counters, 0, sizeof(uint32_t), cx.stream));
-      VDB_HIP(hipMemsetAsync(counters + 2, 0, 2 * sizeof(uint32_t), cx.stream));
+      VDB_HIP(hipMemsetAsync(w.counters, 0, sizeof(uint32_t), cx.stream));
+      VDB_HIP(hipMemsetAsync(w.counters + 2, 0, 2 * sizeof(uint32_t), cx.stream));
     }
     {
       VDB_PROF("k_msm_sort");
-      hipLaunchKernelGGL(k_msm_sort, dim3((unsigned)nc), dim3(MSM_SORT_THREADS), lds, cx.stream, scalars_dev ? scalars_dev + c0 * n : nullptr, srcs ? srcs + c0 : nullptr,
-                       n_blind, n, srs->n, c, W, entries,
-                       ent_cap, seg_off, bucket_off, ranges, counters, seg_cap, range_cap, skip_mask ? skip_mask + c0 * n : nullptr,
-                       lcap, longq, recs, fine_bits, idx_bits, bin_cap);
+      hipLaunchKernelGGL(k_msm_sort, dim3((unsigned)nc), dim3(MSM_SORT_THREADS), P.sort_lds, cx.stream, m.scalars ? m.scalars + c0 * n : nullptr,
+                       m.srcs ? m.srcs + c0 : nullptr, m.n_blind, n, srs->n, c, W, w.entries,
+                       P.ent_cap, w.seg_off, w.bucket_off, w.ranges, w.counters, P.seg_cap, P.range_cap, m.skip_mask ? m.skip_mask + c0 * n : nullptr,
+                       P.lcap, w.longq, w.recs, P.fine_bits, P.idx_bits, P.bin_cap);
     }
     VDB_LAUNCH_CHECK();
-    if (fine_bits) {
+    if (P.fine_bits) {
       VDB_PROF("k_msm_scatter2");
-      const unsigned bins_x = (B >> fine_bits) < 64u ? (B >> fine_bits) : 64u;   // (16 .. 256 workgroups per column measure the same)
-      hipLaunchKernelGGL(k_msm_scatter2, dim3(bins_x, (unsigned)nc), dim3(MSM_SCATTER2_THREADS), (bin_cap + (1u << fine_bits)) * sizeof(uint32_t), cx.stream,
-                       entries, ent_cap, bucket_off, B, fine_bits, idx_bits, bin_cap, counters);
+      hipLaunchKernelGGL(k_msm_scatter2, dim3(P.scatter2_bins_x, (unsigned)nc), dim3(MSM_SCATTER2_THREADS), P.scatter2_lds, cx.stream,
+                       w.entries, P.ent_cap, w.bucket_off, B, P.fine_bits, P.idx_bits, P.bin_cap, w.counters);
     }
     VDB_LAUNCH_CHECK();
     {
       VDB_PROF("k_msm_accum");
-      hipLaunchKernelGGL(k_msm_accum, dim3((unsigned)(cx.cu_count * 8)), dim3(256), 0, cx.stream, table, entries, ent_cap, ranges, bucket_off, B,
-                       seg_off, counters, raw, seginfo, range_cap, l9k);
+      hipLaunchKernelGGL(k_msm_accum, dim3((unsigned)(cx.cu_count * 8)), dim3(256), 0, cx.stream, table, w.entries, P.ent_cap, w.ranges, w.bucket_off, B,
+                       w.seg_off, w.counters, w.raw, w.seginfo, P.range_cap, l9k);
     }
     VDB_LAUNCH_CHECK();
     hipStream_t ts = cx.stream;
@@ -813,34 +798,29 @@ int msm_batch_dev(const vdb_srs* srs, int basis, const u256* scalars_dev, size_t
       VDB_HIP(hipStreamWaitEvent(cx.aux, cx.ev_tail, 0));
       ts = cx.aux;
     }
-    {
-      // at most ceil(log2(max segments per bucket)) passes do work; the rest exit on the device-side maximum
-      uint32_t max_nt = (uint32_t)range_cap_col + 1, passes = 0;
-      while ((1u << passes) < max_nt) passes++;
-      for (uint32_t ps = 0; ps < passes; ps++) {
-        VDB_PROF_ON("k_msm_combine", ts);
-        hipLaunchKernelGGL(k_msm_combine, dim3((unsigned)(cx.cu_count * 8)), dim3(256), 0, ts, raw, seginfo, counters, ps, seg_cap, l9k);
-      }
-      VDB_LAUNCH_CHECK();
+    for (uint32_t ps = 0; ps < P.combine_passes; ps++) {
+      VDB_PROF_ON("k_msm_combine", ts);
+      hipLaunchKernelGGL(k_msm_combine, dim3((unsigned)(cx.cu_count * 8)), dim3(256), 0, ts, w.raw, w.seginfo, w.counters, ps, P.seg_cap, l9k);
     }
+    VDB_LAUNCH_CHECK();
     {
       VDB_PROF_ON("k_msm_reduce", ts);
-      hipLaunchKernelGGL(k_msm_reduce, dim3((unsigned)nc), dim3(64), 0, ts, raw, seg_off, c, counters, add_points ? add_points + c0 : nullptr, sums, l9k);
+      hipLaunchKernelGGL(k_msm_reduce, dim3((unsigned)nc), dim3(64), 0, ts, w.raw, w.seg_off, c, w.counters, m.add_points ? m.add_points + c0 : nullptr, w.sums, l9k);
     }
     VDB_LAUNCH_CHECK();
     {
       VDB_PROF_ON("k_msm_normalise", ts);
-      hipLaunchKernelGGL(k_msm_normalise, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, ts, sums, (uint32_t)nc, counters, l9k.to_std, out_dev + c0);
+      hipLaunchKernelGGL(k_msm_normalise, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, ts, w.sums, (uint32_t)nc, w.counters, l9k.to_std, m.out + c0);
     }
     VDB_LAUNCH_CHECK();
   }
   if (defer_tail) {
     cx.msm_pending = true;
-    cx.msm_counters = counters;
+    cx.msm_counters = w.counters;
     return VDB_OK;
   }
   uint32_t h_counters[2] = {0, 0};
-  VDB_HIP(hipMemcpyAsync(h_counters, counters, sizeof(h_counters), hipMemcpyDeviceToHost, cx.stream));
+  VDB_HIP(hipMemcpyAsync(h_counters, w.counters, sizeof(h_counters), hipMemcpyDeviceToHost, cx.stream));
   VDB_HIP(hipStreamSynchronize(cx.stream));
   if (h_counters[1]) {
     set_error("msm: internal task buffer overflow");
@@ -850,7 +830,7 @@ int msm_batch_dev(const vdb_srs* srs, int basis, const u256* scalars_dev, size_t
 }
 
 // joins a deferred batch: both streams drained, overflow flag checked
-int msm_collect() {
+static int msm_collect() {
   Context& cx = ctx();
   if (!cx.msm_pending) return VDB_OK;
   cx.msm_pending = false;
@@ -905,22 +885,21 @@ int vdb_srs_load(uint32_t k, const vdb_g1* g, const vdb_g1* g_lagrange, vdb_srs*
 int vdb_srs_load_window(uint32_t k, const vdb_g1* g, const vdb_g1* g_lagrange, uint32_t window_bits, vdb_srs** out) {
   VDB_REQUIRE_INIT();
   VDB_ARG(out && (g || g_lagrange) && k >= 1 && k <= 24, "bad argument");
-  // the counting sort keeps three counters per bucket in LDS: 2^(c-1) buckets must fit 160 KB
-  VDB_ARG(window_bits == 0 || (window_bits >= 2 && window_bits <= 14), "window_bits must be 0 (default) or 2..14");
+  MsmShape shape;
+  const char* why = nullptr;
+  if (int rc = msm_window(k, window_bits, msm_knobs(), &shape, &why)) {
+    set_error("%s", why);
+    return rc;
+  }
   Context& cx = ctx();
   vdb_srs* s = new vdb_srs();
   s->device = cx.device;
   s->k = k;
-  s->n = (size_t)1 << k;
-  s->c = window_bits ? window_bits : pick_window(k);
-  s->W = (254 + s->c - 1) / s->c;
-  s->B = 1u << (s->c - 1);
+  s->n = shape.table_n;
+  s->c = shape.c;
+  s->W = shape.W;
+  s->B = shape.B;
   s->table[0] = s->table[1] = nullptr;
-  if ((size_t)s->W * s->n > 0x7fffffffull) {
-    delete s;
-    set_error("srs: table index does not fit 31 bits");
-    return VDB_ERR_ARG;
-  }
   const vdb_g1* src[2] = {g, g_lagrange};
   for (int b = 0; b < 2; b++) {
     if (!src[b]) continue;
@@ -1001,20 +980,56 @@ static void* deferred_out(size_t bytes) {
   c.msm_out_bytes = bytes + bytes / 8 + 64;
   return c.msm_out_buf;
 }
-int vdb_msm_batch_dev(const vdb_srs* srs, int basis, const vdb_fr* scalars_dev, size_t n_cols, size_t n, vdb_g1* out_host) {
+// What the device entry points refuse, in this order.  `ptrs_ok`: the entry point's own pointers are given; `n_msg`: its words for a bad n.
+static int msm_check_call(const MsmCall& m, bool ptrs_ok, const char* n_msg = "n exceeds the loaded SRS size") {
   VDB_REQUIRE_INIT();
-  VDB_ARG(srs && scalars_dev && out_host && (basis == 0 || basis == 1), "bad argument");
-  VDB_SRS_HERE(srs);
-  VDB_ARG(srs->table[basis], "srs was loaded without this basis");
-  VDB_ARG(n <= srs->n && n > 0, "n exceeds the loaded SRS size (shorter columns are allowed)");
-  if (n_cols == 0) return VDB_OK;
-  Affine* dout = (Affine*)scratch_get(1, n_cols * sizeof(Affine));
-  if (!dout) return VDB_ERR_OOM;
-  int rc = msm_batch_dev(srs, basis, as_u256(scalars_dev), n_cols, n, dout);
+  VDB_ARG(m.srs && ptrs_ok && (m.basis == 0 || m.basis == 1), "bad argument");
+  VDB_SRS_HERE(m.srs);
+  VDB_ARG(m.srs->table[m.basis], "srs was loaded without this basis");
+  VDB_ARG(m.n <= m.srs->n && m.n > 0 && m.n_blind <= m.n, n_msg);
+  VDB_ARG((m.skip_mask == nullptr) == (m.add_points == nullptr), "mask and constant points go together");
+  return VDB_OK;
+}
+// the synchronous forms: the points go through scratch slot 1 to the host
+static int msm_to_host(MsmCall m, vdb_g1* out_host) {
+  if (m.n_cols == 0) return VDB_OK;
+  m.out = (Affine*)scratch_get(1, m.n_cols * sizeof(Affine));
+  if (!m.out) return VDB_ERR_OOM;
+  int rc = msm_batch_dev(m);
   if (rc) return rc;
-  VDB_HIP(hipMemcpyAsync(out_host, dout, n_cols * sizeof(Affine), hipMemcpyDeviceToHost, ctx().stream));
+  VDB_HIP(hipMemcpyAsync(out_host, m.out, m.n_cols * sizeof(Affine), hipMemcpyDeviceToHost, ctx().stream));
   VDB_HIP(hipStreamSynchronize(ctx().stream));
   return VDB_OK;
+}
+// the _begin forms: the points go to the deferred batch's own buffer, the tail of the last batch to the auxiliary stream
+static int msm_begin(MsmCall m) {
+  if (m.n_cols == 0) return VDB_OK;
+  // refused before the output buffer is touched: a wider second batch would re-allocate it under the batch that is still open
+  VDB_ARG(!ctx().msm_pending, "msm: a deferred batch has not been collected (vdb_msm_batch_end)");
+  m.out = (Affine*)deferred_out(m.n_cols * sizeof(Affine));
+  if (!m.out) return VDB_ERR_OOM;
+  ctx().msm_out = m.out;
+  m.defer_tail = true;
+  int rc = msm_batch_dev(m);
+  if (rc == VDB_OK && !ctx().msm_pending) ctx().msm_pending = true;  // profiling mode ran it synchronously: _end still copies out
+  return rc;
+}
+static MsmCall msm_call(const vdb_srs* srs, int basis, const vdb_fr* scalars_dev, size_t n_cols, size_t n, const uint8_t* skip_mask_dev = nullptr,
+                        const vdb_g1* const_points_dev = nullptr) {
+  MsmCall m;
+  m.srs = srs;
+  m.basis = basis;
+  m.scalars = as_u256(scalars_dev);
+  m.n_cols = n_cols;
+  m.n = n;
+  m.skip_mask = skip_mask_dev;
+  m.add_points = reinterpret_cast<const Affine*>(const_points_dev);
+  return m;
+}
+int vdb_msm_batch_dev(const vdb_srs* srs, int basis, const vdb_fr* scalars_dev, size_t n_cols, size_t n, vdb_g1* out_host) {
+  const MsmCall m = msm_call(srs, basis, scalars_dev, n_cols, n);
+  if (int rc = msm_check_call(m, scalars_dev && out_host, "n exceeds the loaded SRS size (shorter columns are allowed)")) return rc;
+  return msm_to_host(m, out_host);
 }
 int vdb_msm_count_entries_dev(const vdb_srs* srs, const vdb_fr* scalars_dev, size_t n_cols, size_t n, const uint8_t* skip_mask_dev, uint64_t* counts_out) {
   VDB_REQUIRE_INIT();
@@ -1036,40 +1051,17 @@ int vdb_msm_count_entries_dev(const vdb_srs* srs, const vdb_fr* scalars_dev, siz
 }
 int vdb_msm_batch_masked_dev_begin(const vdb_srs* srs, int basis, const vdb_fr* scalars_dev, size_t n_cols, size_t n, const uint8_t* skip_mask_dev,
                                    const vdb_g1* const_points_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(srs && scalars_dev && (basis == 0 || basis == 1), "bad argument");
-  VDB_SRS_HERE(srs);
-  VDB_ARG(srs->table[basis], "srs was loaded without this basis");
-  VDB_ARG(n <= srs->n && n > 0, "n exceeds the loaded SRS size");
-  VDB_ARG((skip_mask_dev == nullptr) == (const_points_dev == nullptr), "mask and constant points go together");
-  if (n_cols == 0) return VDB_OK;
-  // refused before the output buffer is touched: a wider second batch would re-allocate it under the batch that is still open
-  VDB_ARG(!ctx().msm_pending, "msm: a deferred batch has not been collected (vdb_msm_batch_end)");
-  Affine* dout = (Affine*)deferred_out(n_cols * sizeof(Affine));
-  if (!dout) return VDB_ERR_OOM;
-  ctx().msm_out = dout;
-  int rc = msm_batch_dev(srs, basis, as_u256(scalars_dev), n_cols, n, dout, skip_mask_dev, reinterpret_cast<const Affine*>(const_points_dev), true);
-  if (rc == VDB_OK && !ctx().msm_pending) ctx().msm_pending = true;  // profiling mode ran it synchronously: _end still copies out
-  return rc;
+  const MsmCall m = msm_call(srs, basis, scalars_dev, n_cols, n, skip_mask_dev, const_points_dev);
+  if (int rc = msm_check_call(m, scalars_dev)) return rc;
+  return msm_begin(m);
 }
 int vdb_msm_batch_src_dev_begin(const vdb_srs* srs, int basis, const vdb_colsrc* src_dev, size_t n_cols, size_t n, uint32_t n_blind,
                                 const uint8_t* skip_mask_dev, const vdb_g1* const_points_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(srs && src_dev && (basis == 0 || basis == 1), "bad argument");
-  VDB_SRS_HERE(srs);
-  VDB_ARG(srs->table[basis], "srs was loaded without this basis");
-  VDB_ARG(n <= srs->n && n > 0 && n_blind <= n, "n exceeds the loaded SRS size");
-  VDB_ARG((skip_mask_dev == nullptr) == (const_points_dev == nullptr), "mask and constant points go together");
-  if (n_cols == 0) return VDB_OK;
-  // refused before the output buffer is touched: a wider second batch would re-allocate it under the batch that is still open
-  VDB_ARG(!ctx().msm_pending, "msm: a deferred batch has not been collected (vdb_msm_batch_end)");
-  Affine* dout = (Affine*)deferred_out(n_cols * sizeof(Affine));
-  if (!dout) return VDB_ERR_OOM;
-  ctx().msm_out = dout;
-  int rc = msm_batch_dev(srs, basis, nullptr, n_cols, n, dout, skip_mask_dev, reinterpret_cast<const Affine*>(const_points_dev), true,
-                         reinterpret_cast<const ColSrc*>(src_dev), n_blind);
-  if (rc == VDB_OK && !ctx().msm_pending) ctx().msm_pending = true;
-  return rc;
+  MsmCall m = msm_call(srs, basis, nullptr, n_cols, n, skip_mask_dev, const_points_dev);
+  m.srcs = reinterpret_cast<const ColSrc*>(src_dev);
+  m.n_blind = n_blind;
+  if (int rc = msm_check_call(m, src_dev)) return rc;
+  return msm_begin(m);
 }
 int vdb_msm_batch_end(vdb_g1* out_host, size_t n_cols) {
   VDB_REQUIRE_INIT();
@@ -1086,19 +1078,9 @@ int vdb_msm_batch_end(vdb_g1* out_host, size_t n_cols) {
 }
 int vdb_msm_batch_masked_dev(const vdb_srs* srs, int basis, const vdb_fr* scalars_dev, size_t n_cols, size_t n, const uint8_t* skip_mask_dev,
                              const vdb_g1* const_points_dev, vdb_g1* out_host) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(srs && scalars_dev && out_host && (basis == 0 || basis == 1) && skip_mask_dev && const_points_dev, "bad argument");
-  VDB_SRS_HERE(srs);
-  VDB_ARG(srs->table[basis], "srs was loaded without this basis");
-  VDB_ARG(n <= srs->n && n > 0, "n exceeds the loaded SRS size");
-  if (n_cols == 0) return VDB_OK;
-  Affine* dout = (Affine*)scratch_get(1, n_cols * sizeof(Affine));
-  if (!dout) return VDB_ERR_OOM;
-  int rc = msm_batch_dev(srs, basis, as_u256(scalars_dev), n_cols, n, dout, skip_mask_dev, reinterpret_cast<const Affine*>(const_points_dev));
-  if (rc) return rc;
-  VDB_HIP(hipMemcpyAsync(out_host, dout, n_cols * sizeof(Affine), hipMemcpyDeviceToHost, ctx().stream));
-  VDB_HIP(hipStreamSynchronize(ctx().stream));
-  return VDB_OK;
+  const MsmCall m = msm_call(srs, basis, scalars_dev, n_cols, n, skip_mask_dev, const_points_dev);
+  if (int rc = msm_check_call(m, scalars_dev && out_host && skip_mask_dev && const_points_dev)) return rc;
+  return msm_to_host(m, out_host);
 }
 int vdb_msm_batch(const vdb_srs* srs, int basis, const vdb_fr* const* cols, size_t n_cols, size_t n, vdb_g1* out) {
   VDB_REQUIRE_INIT();
