@@ -101,6 +101,10 @@ _SIGNATURES = {
     "vdb_wit_ann_recentre": [_U32, _U32, _P, _P, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],
     "vdb_wit_ann_recentre_dev": [_U32, _U32, _P, _P, _P, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],
     "vdb_ann_index_recentre_dev": [_P, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _P, _P, _P],
+    "vdb_wit_ann_cover_size": [_P, _SZ, _SZ, _P, _P],
+    "vdb_wit_ann_cover": [_P, _P, _P, _P, _SZ, _SZ, _P, _P, _P],
+    "vdb_wit_ann_cover_dev": [_P, _P, _P, _P, _SZ, _SZ, _P, _P, _P, _P, _P],
+    "vdb_ann_index_db_tree_dev": [_P, _P, _P, _SZ, _SZ, _P],
     "vdb_ann_cluster_means_dev": [_U32, _U32, _P, _P, _SZ, _SZ, _SZ, _P],
     "vdb_ann_cluster_means": [_U32, _U32, _P, _P, _SZ, _SZ, _SZ, _P],
     "vdb_wit_nearest_batch_size": [_I, _U32, _U32, _SZ, _SZ, _SZ, _P, _P],

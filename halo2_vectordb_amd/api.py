@@ -641,6 +641,46 @@ def wit_ann_recentre(centroid_levels, members, roots, c, P=48, L=13, selectors=F
     return dict(stream=stream, lookup=lookup, **_split_flags(sel), n_in=n_in.value, update_base=ub.value, public=pub, new_centroid=new, levels=levels)
 
 
+def wit_ann_cover(db_leaves, cluster_leaves, sizes, centroids_root, selectors=False):
+    """the cover of the database by the index (vdb_wit_ann_cover), the streams alone: `db_leaves` (n, 4) the database's leaf digests in
+    slot order, `cluster_leaves` (n, 4) the clusters' leaf digests in grouped order, `sizes` the K cluster sizes (they sum to n) and the
+    centroids' root (4,).  The K + 1 trees are hashed over what is given: dict(stream, selectors, flags, n_in, public (2, 4):
+    [database_root | index_root])"""
+    lib = _lib.init()
+    a, b, croot = _fr(db_leaves), _fr(cluster_leaves), _fr(centroids_root).reshape(4)
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
+    K, n = sizes.size, a.shape[0]
+    assert a.shape == (n, 4) and b.shape == (n, 4)
+    cells, n_in = _u64(), _u64()
+    check(lib.vdb_wit_ann_cover_size(_p(sizes), _sz(K), _sz(n), ctypes.byref(cells), ctypes.byref(n_in)))
+    stream = np.zeros((cells.value, 4), dtype=np.uint64)
+    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
+    pub = np.zeros((2, 4), dtype=np.uint64)
+    check(lib.vdb_wit_ann_cover(_p(a), _p(b), _p(croot), _p(sizes), _sz(K), _sz(n), _p(stream), _p(sel) if selectors else None, _p(pub)))
+    return dict(stream=stream, **_split_flags(sel), n_in=n_in.value, public=pub)
+
+
+def ann_index_db_tree(forest, sizes, slots):
+    """the database tree of an index (vdb_ann_index_db_tree_dev) from its downloaded `forest` (digests, 4), the K cluster `sizes` and the
+    `slots` (n,) of ann_index_build: (2 lp, 4), bit for bit merkle_tree_build over the rows in slot order; VdbError where `slots` is no
+    permutation of 0 .. n - 1"""
+    lib = _lib.init()
+    forest, sizes = _fr(forest), np.ascontiguousarray(sizes, dtype=np.uint64)
+    slots = np.ascontiguousarray(slots, dtype=np.uint32)
+    K, n = sizes.size, slots.size
+    lp, _ = merkle_levels(max(n, 1))
+    assert forest.shape[0] >= sum(2 * merkle_levels(int(x))[0] for x in sizes), "the forest does not hold the K cluster trees"
+    d_f, d_s, d_lv = DeviceBuffer(max(forest.nbytes, 32)), DeviceBuffer(max(slots.nbytes, 32)), DeviceBuffer(2 * lp * 32)
+    try:
+        d_f.upload(forest)
+        d_s.upload(slots)
+        check(lib.vdb_ann_index_db_tree_dev(d_f.ptr, _p(sizes), d_s.ptr, _sz(K), _sz(n), d_lv.ptr))
+        return d_lv.download((2 * lp, 4))
+    finally:
+        for d in (d_f, d_s, d_lv):
+            d.free()
+
+
 def ann_cluster_means(grouped, offsets, P=48, L=13):
     """the means of all K clusters of grouped rows (n, dim, 4), cluster k the rows [offsets[k], offsets[k + 1]) (vdb_ann_cluster_means: values
     only): (K, dim, 4), means[k][j] = qdiv(sum of the cluster's words j, quantization(n_k)) bit for bit as vdb_wit_ann_mean constrains it"""

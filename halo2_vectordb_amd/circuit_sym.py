@@ -1950,6 +1950,112 @@ def build_ann_recentre(K, n_c, dim, P, L, fetch_flags, fetch_values, builder=Non
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# The cover of the database by the index (include/vdb.h vdb_wit_ann_cover; pipeline.AnnCoverHotPath)
+def place_tree(perm, digest, pos, node_cells):
+    """the nodes of a tree over the digest cells `digest` (a power of two of them: the padding already filled in) placed from stream
+    cell `pos` on, level-major (place_merkle's loop; perm: _perm_placer's) -> (the root's cell: the digest itself where there is one
+    leaf, the first cell after the nodes)"""
+    digest = np.asarray(digest, dtype=np.int64)
+    while digest.size > 1:
+        bases = pos + np.arange(digest.size // 2, dtype=np.int64) * node_cells
+        digest = _node(perm, bases, digest[0::2], digest[1::2])
+        pos += bases.size * node_cells
+    return int(digest[0]), pos
+
+
+def ann_cover_layout(sizes):
+    """where the blocks of the cover circuit start, for the K cluster sizes `sizes`: dict(K, n, lp, sizes, lps: the clusters' padded leaf
+    counts, header (0), a, b: the assigned digests, n_in, zero: the load_zero cell or None, tree_d, tree_c: the K + 1 trees' nodes,
+    tree_c_at: where cluster c's nodes start, sponge: D, gamma: G, sub_a, mul_a, sub_b, mul_b, total, total_l = 0, node_cells)"""
+    sizes = [int(x) for x in sizes]
+    K, n = len(sizes), sum(sizes)
+    if K < 1 or min(sizes) < 1:
+        raise ValueError("at least one cluster, and no empty one")
+    sp = merkle_leaf_layout(K + 1)
+    node = sp["node_cells"]
+    lp, lps = 1 << (n - 1).bit_length(), [1 << (x - 1).bit_length() for x in sizes]
+    lay = dict(K=K, n=n, lp=lp, sizes=sizes, lps=lps, header=0, a=K + 1, b=K + 1 + n, n_in=K + 1 + 2 * n, node_cells=node, total_l=0)
+    padded = lp > n or any(l > x for l, x in zip(lps, sizes))
+    lay["zero"] = lay["n_in"] if padded else None
+    lay["tree_d"] = lay["n_in"] + (1 if padded else 0)
+    lay["tree_c"] = lay["tree_d"] + (lp - 1) * node
+    at, lay["tree_c_at"] = lay["tree_c"], []
+    for l in lps:
+        lay["tree_c_at"].append(at)
+        at += (l - 1) * node
+    lay["sponge"] = at
+    lay["gamma"] = at + sp["leaf_cells"]
+    lay["sub_a"] = lay["gamma"] + node
+    lay["mul_a"] = lay["sub_a"] + 4 * n
+    lay["sub_b"] = lay["mul_a"] + 4 * (n - 1)
+    lay["mul_b"] = lay["sub_b"] + 4 * n
+    lay["total"] = lay["mul_b"] + 4 * (n - 1)
+    return lay
+
+
+def ann_cover_instances(database_root, index_root):
+    """the public cells in make_public order: [database_root | index_root]"""
+    return [int(database_root), int(index_root)]
+
+
+def build_ann_cover(sizes, fetch_flags, fetch_values, builder=None):
+    """The cover of the database by the index in one circuit (pipeline.AnnCoverHotPath): the header [centroids_root | cluster roots] and
+    the 2 n leaf digests assigned, the zero cell, the database tree over a and the K cluster trees over their stretches of b (place_tree;
+    root_c TIED to the header's cluster_root_c), the sponge over the header (index_root), the sponge over [droot, index_root] (gamma),
+    then per side g_sub(gamma, x_i) and the g_mul chain; the last accumulator of b TIED to the last of a.  fetch_flags / fetch_values:
+    as place_merkle; `builder`: as build_kmeans.
+    -> (CopyMap, public cells [database_root, index_root], dict(roots: the K root cells, gamma, last_a, last_b, layout))"""
+    lay = ann_cover_layout(sizes)
+    K, n, node = lay["K"], lay["n"], lay["node_cells"]
+    if np.asarray(fetch_flags(0, lay["n_in"])).any():
+        raise ValueError("the assigned header and digests carry no gate or constant flag")
+    B = (builder or _Builder)(lay["total"], 0)
+    if lay["zero"] is not None:
+        B.constant_cell(lay["zero"], 0)                      # ctx.load_zero(), once: every tree's padding copies it
+    perm = _perm_placer(B, fetch_flags, fetch_values)
+
+    def padded(first, count, lp):
+        d = np.full(lp, lay["zero"] if lay["zero"] is not None else -1, dtype=np.int64)
+        d[:count] = first + np.arange(count, dtype=np.int64)
+        return d
+
+    droot, at = place_tree(perm, padded(lay["a"], n, lay["lp"]), lay["tree_d"], node)
+    assert at == lay["tree_c"]
+    roots, off = [], 0
+    for c in range(K):
+        assert at == lay["tree_c_at"][c]
+        root, at = place_tree(perm, padded(lay["b"] + off, lay["sizes"][c], lay["lps"][c]), at, node)
+        B.tie(root, lay["header"] + 1 + c)                   # ctx.constrain_equal(cluster_root_c, root_c)
+        roots.append(root)
+        off += lay["sizes"][c]
+    assert at == lay["sponge"]
+    iroot, at = place_sponge(B, lay["sponge"], [lay["header"] + j for j in range(K + 1)], fetch_flags, fetch_values)
+    assert at == lay["gamma"]
+    gamma, at = place_sponge(B, lay["gamma"], [droot, iroot], fetch_flags, fetch_values)
+    assert at == lay["sub_a"]
+    s = Sym(0, 0)
+    sub = Block(s, [s.g_sub(ext(0), ext(1))])
+    s = Sym(0, 0)
+    mul = Block(s, [s.g_mul(ext(0), ext(1))])
+    i, last = np.arange(n, dtype=np.int64), []
+    for x, sb, mb in ((lay["a"], lay["sub_a"], lay["mul_a"]), (lay["b"], lay["sub_b"], lay["mul_b"])):
+        t = B.place(sub, sb + 4 * i, np.zeros(n, dtype=np.int64), np.stack([np.full(n, gamma, dtype=np.int64), x + i], axis=1))[:, 0]
+        if n > 1:
+            bases = mb + 4 * i[:-1]
+            outs = bases + int(mul.outs[0])
+            acc = np.concatenate([t[:1], outs[:-1]])         # acc_0 = t_0; acc_i = the product before it
+            B.place(mul, bases, np.zeros(n - 1, dtype=np.int64), np.stack([acc, t[1:]], axis=1))
+            last.append(int(outs[-1]))
+        else:
+            last.append(int(t[0]))
+    B.tie(last[1], last[0])                                  # ctx.constrain_equal(prod_a, prod_b)
+    if lay["mul_b"] + 4 * (n - 1) != lay["total"]:
+        raise ValueError("the trace does not end where the circuit does")
+    info = dict(roots=roots, gamma=gamma, droot=droot, index_root=iroot, last_a=last[0], last_b=last[1], layout=lay)
+    return B.finish(), ann_cover_instances(droot, iroot), info
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # Merkle openings (include/vdb.h vdb_wit_merkle_open; pipeline.ReadHotPath)
 def merkle_open_layout(m, dim, depth, with_vectors):
     """where the cells of m openings lie: dict(nperm, n_ins, sizes, leaf_cells, node_cells, level_cells, ip_cells, per_read, n_lead,

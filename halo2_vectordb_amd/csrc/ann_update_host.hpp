@@ -125,6 +125,51 @@ static inline AnnrBlocks annr_blocks(uint64_t K, uint64_t n_c, uint64_t dim, uin
   return o;
 }
 
+// ------------------------------------------------------------------ the cover of the database by the index (include/vdb.h vdb_wit_ann_cover)
+// first stream cell of each block: A the header [centroids_root | cluster roots] (from 0), I the assigned leaf digests a_0 .. a_{n-1}
+// (b_a, database slot order) and b_0 .. b_{n-1} (b_b, grouped order), Z the one load_zero cell (zero: 1 where the database tree or a
+// cluster tree is padded), TD the database tree's nodes (b_td), TC the K cluster trees' nodes one tree after the other (b_tc; tree c
+// from b_tc + node_pre[c] * node_cells; a cluster of one member has no node), D the sponge over the header (b_d), G the sponge over
+// [droot, index_root] (b_g: two words, the cells of a node), then the products: SA the n g_sub(gamma, a_i) (b_sa), MA the n - 1 g_mul
+// (b_ma), SB and MB the same over b.  No lookup cell.
+struct AnncBlocks {
+  uint64_t n, lp, zero, nodes_c, n_in, b_a, b_b, b_z, b_td, b_tc, b_d, b_g, b_sa, b_ma, b_sb, b_mb, total;
+};
+// sizes: the K cluster sizes.  -> 0; 1: K = 0 or an empty cluster; 2: n above max_n (the sum is cut off there: no overflow)
+static inline int annc_blocks(const uint64_t* sizes, uint64_t K, uint64_t max_n, uint64_t sponge_cells, uint64_t node_cells, AnncBlocks* o) {
+  if (K == 0) return 1;
+  uint64_t n = 0, nodes_c = 0, padded = 0;
+  for (uint64_t c = 0; c < K; c++) {
+    if (sizes[c] == 0) return 1;
+    if (sizes[c] > max_n || n + sizes[c] > max_n) return 2;
+    uint64_t lp_c;
+    uint32_t d;
+    tree_shape(sizes[c], &lp_c, &d);
+    n += sizes[c];
+    nodes_c += lp_c - 1;
+    padded |= lp_c > sizes[c];
+  }
+  uint32_t d;
+  o->n = n;
+  tree_shape(n, &o->lp, &d);
+  o->zero = (o->lp > n || padded) ? 1 : 0;
+  o->nodes_c = nodes_c;
+  o->n_in = K + 1 + 2 * n;
+  o->b_a = K + 1;
+  o->b_b = o->b_a + n;
+  o->b_z = o->b_b + n;
+  o->b_td = o->b_z + o->zero;
+  o->b_tc = o->b_td + (o->lp - 1) * node_cells;
+  o->b_d = o->b_tc + nodes_c * node_cells;
+  o->b_g = o->b_d + sponge_cells;
+  o->b_sa = o->b_g + node_cells;
+  o->b_ma = o->b_sa + 4 * n;
+  o->b_sb = o->b_ma + 4 * (n - 1);
+  o->b_mb = o->b_sb + 4 * n;
+  o->total = o->b_mb + 4 * (n - 1);
+  return 0;
+}
+
 // The members of a cluster stay dense: write j goes to a slot below the fill at its turn (a replacement) or exactly at it (an append,
 // which raises the fill by one).  n_c: the fill before the batch, glp: the padded leaf count of the grown tree.
 // -> 0 and *appends; 1: indices[*bad] lies above the fill at its turn; 2: it lies outside the grown tree

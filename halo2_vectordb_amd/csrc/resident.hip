@@ -46,6 +46,14 @@ __global__ __launch_bounds__(64) void k_mk_level_values(const PoseidonSpec* __re
   psd_permute_absorb(sp, st, in, 0);
   out_lv[t] = st[1];
 }
+// the levels above the lp leaf digests that `levels` holds (its layout: resident.hpp), a launch per level; the root is at *root_off
+int mk_levels_from_leaves(const PoseidonSpec* sp, u256* levels, uint64_t lp, uint64_t* root_off) {
+  uint64_t off = 0;
+  for (uint64_t lv = lp; lv > 1; off += lv, lv /= 2)
+    VDB_LAUNCH(k_mk_level_values, dim3((unsigned)((lv / 2 + 63) / 64)), dim3(64), sp, levels + off, (uint32_t)(lv / 2), levels + off + lv);
+  if (root_off) *root_off = off;
+  return VDB_OK;
+}
 // The digests of every level of merkle_commitment's tree, values only, into `levels` in the layout of resident.hpp: the lp padded leaf
 // digests, then the levels one after the other (lp + lp / 2 + ... + 1 of the 2 lp entries, the last unused); the root is at *root_off.
 // `states` receives the sponge state before every permutation of every leaf (n * nperm * PSD_T entries).
@@ -54,11 +62,7 @@ int mk_tree_values(const PoseidonSpec* sp, const u256* vectors, size_t n, size_t
   const uint64_t lp = ml.n_leaves_pow2;
   VDB_HIP(hipMemsetAsync(levels, 0, 2 * lp * sizeof(u256), ctx().stream));
   TRY(mk_leaf_states(sp, vectors, (uint32_t)n, (uint32_t)dim, ml.nperm, states, levels, nullptr));
-  uint64_t off = 0;
-  for (uint64_t lv = lp; lv > 1; off += lv, lv /= 2)
-    VDB_LAUNCH(k_mk_level_values, dim3((unsigned)((lv / 2 + 63) / 64)), dim3(64), sp, levels + off, (uint32_t)(lv / 2), levels + off + lv);
-  *root_off = off;
-  return VDB_OK;
+  return mk_levels_from_leaves(sp, levels, lp, root_off);
 }
 // the resident tree of the path updates: mk_tree_values into the caller's buffer
 int merkle_tree_build_dev(const u256* vectors, size_t n, size_t dim, u256* levels) {
@@ -422,6 +426,71 @@ int ann_index_recentre_dev(const u256* grouped, const uint32_t* slots, const uin
   return VDB_OK;
 }
 
+// ------------------------------------------------------------------ the database tree of an index (include/vdb.h
+// vdb_ann_index_db_tree_dev; the cover's circuit is witness.hip's).  Values only: no vector is hashed again, every leaf digest already
+// lies in level 0 of its cluster's forest segment.  Lane g (a grouped row) finds its cluster by bisection in the offsets, copies its
+// digest to levels_out[slots[g]] and counts the hit; a slot at or above n is skipped here and flagged by the second pass
+__global__ __launch_bounds__(256) void k_annc_scatter(const u256* __restrict__ forest, const uint64_t* __restrict__ seg_off, const uint64_t* __restrict__ offsets,
+                                                      const uint32_t* __restrict__ slots, uint32_t K, uint32_t n, u256* __restrict__ levels_out,
+                                                      uint32_t* __restrict__ count) {
+  const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= n) return;
+  uint32_t lo = 0, hi = K;   // the cluster c with offsets[c] <= g < offsets[c + 1] (no cluster is empty)
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (offsets[mid] <= g) lo = mid; else hi = mid;
+  }
+  const uint32_t slot = slots[g];
+  if (slot >= n) return;
+  levels_out[slot] = forest[seg_off[lo] + (g - offsets[lo])];
+  atomicAdd(count + slot, 1u);
+}
+// lane g: a slot entry at or above n, or a slot that was not hit exactly once: `slots` is no permutation of 0 .. n - 1
+__global__ __launch_bounds__(256) void k_annc_slots_check(const uint32_t* __restrict__ slots, const uint32_t* __restrict__ count, uint32_t n,
+                                                          uint32_t* __restrict__ flag) {
+  const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= n) return;
+  if (slots[g] >= n || count[g] != 1u) atomicOr(flag, 1u);
+}
+int ann_index_db_tree_dev(const u256* forest, const uint64_t* sizes, const uint32_t* slots, size_t K, size_t n, u256* levels_out) {
+  static thread_local std::vector<uint64_t> tab;   // [seg_off K + 1 | offsets K + 1] (pageable source of an asynchronous upload)
+  VDB_ARG(sizes, "null pointer");
+  VDB_ARG(K > 0 && K <= VDB_ANN_MAX_CLUSTERS, "K = 0 or K above VDB_ANN_MAX_CLUSTERS");
+  VDB_ARG(n > 0 && n <= VDB_ANN_MAX_VECTORS, "empty database or n above VDB_ANN_MAX_VECTORS");
+  tab.assign(2 * (K + 1), 0);
+  for (size_t c = 0; c < K; c++) {
+    VDB_ARG(sizes[c] > 0 && sizes[c] <= n, "empty cluster or cluster sizes that do not sum to n");
+    uint64_t lp_c;
+    uint32_t d;
+    tree_shape(sizes[c], &lp_c, &d);
+    tab[c + 1] = tab[c] + 2 * lp_c;
+    tab[K + 1 + c + 1] = tab[K + 1 + c] + sizes[c];
+  }
+  VDB_ARG(tab[2 * K + 1] == n, "cluster sizes that do not sum to n");
+  const PoseidonSpec* sp;
+  TRY(poseidon_spec_dev(&sp, nullptr));
+  hipStream_t s = ctx().stream;
+  uint64_t lp;
+  uint32_t d;
+  tree_shape(n, &lp, &d);
+  uint8_t* w = (uint8_t*)scratch_get(7, 2 * (K + 1) * 8 + (n + 16) * 4);
+  if (!w) return VDB_ERR_OOM;
+  uint64_t* d_tab = (uint64_t*)w;
+  uint32_t *d_count = (uint32_t*)(d_tab + 2 * (K + 1)), *d_flag = d_count + n;
+  VDB_HIP(hipMemcpyAsync(d_tab, tab.data(), 2 * (K + 1) * 8, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemsetAsync(d_count, 0, (n + 1) * 4, s));
+  VDB_HIP(hipMemsetAsync(levels_out, 0, 2 * lp * sizeof(u256), s));
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  VDB_LAUNCH(k_annc_scatter, dim3(grid), dim3(256), forest, d_tab, d_tab + K + 1, slots, (uint32_t)K, (uint32_t)n, levels_out, d_count);
+  VDB_LAUNCH(k_annc_slots_check, dim3(grid), dim3(256), slots, d_count, (uint32_t)n, d_flag);
+  TRY(mk_levels_from_leaves(sp, levels_out, lp, nullptr));
+  uint32_t flag = 0;
+  VDB_HIP(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s));
+  VDB_HIP(hipStreamSynchronize(s));
+  VDB_ARG(flag == 0, "slots is not a permutation of 0 .. n - 1: the database has slots no cluster holds, or one held twice");
+  return VDB_OK;
+}
+
 // ------------------------------------------------------------------ the index after a batch of deletes (include/vdb.h
 // vdb_ann_index_remove_dev; the batch's circuit is witness.hip's).  Values only; the old buffers are only read.
 // A removal compacts the database: the result is the fresh build over its own grouped rows taken as the database, so every grouped
@@ -619,6 +688,12 @@ int vdb_ann_index_recentre_dev(const vdb_fr* grouped_dev, const uint32_t* slots_
   return ann_index_recentre_dev(as_u256(grouped_dev), slots_dev, offsets_dev, as_u256(forest_dev), as_u256(roots_dev), as_u256(centroids_dev), cluster_sizes, K,
                                 dim, cluster, as_u256(updated_levels_dev), as_u256(new_centroid_dev), as_u256(grouped_out_dev), slots_out_dev, offsets_out_dev,
                                 as_u256(forest_out_dev), as_u256(roots_out_dev), as_u256(centroids_out_dev));
+}
+
+int vdb_ann_index_db_tree_dev(const vdb_fr* forest_dev, const uint64_t* cluster_sizes, const uint32_t* slots_dev, size_t K, size_t n, vdb_fr* levels_out_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(forest_dev && slots_dev && levels_out_dev, "null pointer");
+  return ann_index_db_tree_dev(as_u256(forest_dev), cluster_sizes, slots_dev, K, n, as_u256(levels_out_dev));
 }
 
 int vdb_ann_index_remove_size(const uint64_t* cluster_sizes, size_t K, size_t cluster, const uint64_t* slots, size_t m, unsigned* shrink, uint64_t* digests,

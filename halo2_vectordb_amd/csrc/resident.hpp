@@ -32,6 +32,7 @@ int mk_leaf_states(const PoseidonSpec* sp, const u256* vectors, uint32_t n, uint
                    const uint32_t* leaf_at);
 int mk_tree_values(const PoseidonSpec* sp, const u256* vectors, size_t n, size_t dim, const MkShape& ml, u256* states, u256* levels,
                    uint64_t* root_off);
+int mk_levels_from_leaves(const PoseidonSpec* sp, u256* levels, uint64_t lp, uint64_t* root_off);
 int merkle_tree_build_dev(const u256* vectors, size_t n, size_t dim, u256* levels);
 int merkle_tree_grow_dev(const u256* levels, size_t n, unsigned grow, u256* grown);
 int ann_index_build_dev(const u256* db, const uint32_t* ids, const u256* centroids, size_t n, size_t K, size_t dim, u256* grouped, uint32_t* slots,
@@ -42,5 +43,6 @@ int ann_index_apply_dev(const u256* grouped, const uint32_t* slots, const u256* 
 int ann_index_remove_dev(const u256* grouped, const u256* forest, const u256* roots, const uint64_t* sizes, size_t K, size_t dim, size_t cluster,
                          const u256* updated, const uint64_t* slots, size_t m, u256* grouped_out, uint32_t* slots_out, uint64_t* offsets_out,
                          u256* forest_out, u256* roots_out);
+int ann_index_db_tree_dev(const u256* forest, const uint64_t* sizes, const uint32_t* slots, size_t K, size_t n, u256* levels_out);
 
 }  // namespace vdb

@@ -2606,6 +2606,204 @@ int wit_ann_recentre_dev(FpEntry* fp, u256* levels, const u256* members, const u
   return inv_list_fixup(f.st);
 }
 
+// ------------------------------------------------------------------ the cover of the database by the index (include/vdb.h
+// vdb_wit_ann_cover): the multiset of the n leaf digests under database_root is the union of the multisets of the leaf digests under
+// the K cluster roots of index_root.  On leaf digests alone: no vector is hashed.  Blocks (AnncBlocks, ann_update_host.hpp): A the
+// header [centroids_root | cluster roots], I the digests a (slot order) and b (grouped order), Z the one zero cell, TD the database
+// tree over a, TC the K cluster trees over their stretches of b (each root tied to the header), D the sponge over the header ->
+// index_root, G the sponge over [droot, index_root] -> gamma, then prod (gamma - a_i) and prod (gamma - b_j), whose last cells are tied.
+// Every tree is read where it lies: tree 0 is `dbtree` (2 lp digests), tree 1 + c is segment c of `forest` (seg_off[c], 2 lp_c digests).
+struct AnncLayout {
+  MkLayout mw;
+  AnncBlocks b;
+};
+static int annc_layout(const uint64_t* sizes, size_t K, size_t n, AnncLayout* o) {
+  VDB_ARG(sizes, "null pointer");
+  VDB_ARG(K > 0 && K <= VDB_ANN_MAX_CLUSTERS, "K = 0 or K above VDB_ANN_MAX_CLUSTERS");
+  VDB_ARG(n <= VDB_ANN_MAX_VECTORS, "n above VDB_ANN_MAX_VECTORS");
+  mk_layout(1, K + 1, 1, &o->mw);
+  const int rc = annc_blocks(sizes, K, VDB_ANN_MAX_VECTORS, o->mw.total, NODE_CELLS, &o->b);
+  VDB_ARG(rc != 1, "empty cluster: merkle_commitment is undefined over zero vectors");
+  VDB_ARG(rc == 0 && o->b.n == n, "the cluster sizes do not sum to n");
+  VDB_ARG(o->b.total <= ((uint64_t)1 << 34), "cover circuit above 2^34 cells");
+  return VDB_OK;
+}
+// blocks A and I, a lane per cell: the header's word i (lane 0: the centroids' root, lane 1 + c: the root of forest segment c), then a_j
+// = level 0 of the database tree, then b_j = level 0 of its cluster's segment (the cluster by bisection in the offsets).  The values
+// stay in `words` (K + 1) and `ab` (2 n) for the sponge and the products; lane K + 1 leaves the database root in pubv[0]
+__global__ __launch_bounds__(256) void k_annc_inputs(Streams st, const u256* __restrict__ croot, const u256* __restrict__ dbtree, const u256* __restrict__ forest,
+                                                     const uint64_t* __restrict__ seg_off, const uint64_t* __restrict__ offsets,
+                                                     const uint32_t* __restrict__ lp_t, uint32_t K, uint32_t n, u256* __restrict__ words,
+                                                     u256* __restrict__ ab, u256* __restrict__ pubv) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (uint64_t)K + 1 + 2ull * n) return;
+  u256 v;
+  if (i <= K) {
+    v = i ? forest[seg_off[i - 1] + 2 * (uint64_t)lp_t[i] - 2] : *croot;
+    words[i] = v;
+  } else {
+    const uint32_t j = (uint32_t)(i - K - 1);
+    if (j < n) {
+      v = dbtree[j];
+      if (j == 0) pubv[0] = dbtree[2 * (uint64_t)lp_t[0] - 2];
+    } else {
+      const uint32_t g = j - n;
+      uint32_t lo = 0, hi = K;   // the cluster c with offsets[c] <= g < offsets[c + 1] (no cluster is empty)
+      while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) / 2;
+        if (offsets[mid] <= g) lo = mid; else hi = mid;
+      }
+      v = forest[seg_off[lo] + (g - offsets[lo])];
+    }
+    ab[j] = v;
+  }
+  if (i < st.rlo || i >= st.rhi) return;
+  st.adv[i] = v;
+  if (st.sel) st.sel[i] = 0;
+}
+// Blocks TD and TC in ONE launch: a thread per (node, permutation half) of the K + 1 trees.  The tree is found by bisection in the prefix
+// sums of the node counts (node_pre, n_tree + 1 entries; a tree of one leaf has no node and shares its successor's prefix), the level
+// inside the tree by k_mk_tree_trace's walk; the trees' cells follow each other, so node t of the launch has its cells at base + t NODE_CELLS
+__global__ __launch_bounds__(64) void k_annc_forest_trace(Streams stq, const FpTables* __restrict__ T, const PoseidonSpec* __restrict__ sp,
+                                                          const u256* __restrict__ dbtree, const u256* __restrict__ forest,
+                                                          const uint64_t* __restrict__ seg_off, const uint32_t* __restrict__ lp_t,
+                                                          const uint32_t* __restrict__ node_pre, uint32_t n_tree, uint64_t base) {
+  const uint32_t id = blockIdx.x * 64 + threadIdx.x;
+  const uint32_t t = id >> 1, j = id & 1u;
+  if (t >= node_pre[n_tree]) return;
+  uint32_t lo = 0, hi = n_tree;   // the last tree s with node_pre[s] <= t
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (node_pre[mid] <= t) lo = mid; else hi = mid;
+  }
+  const uint32_t g = t - node_pre[lo], lp = lp_t[lo];
+  const u256* levels = lo ? forest + seg_off[lo - 1] : dbtree;
+  uint32_t sz = lp >> 1, first = 0, in_off = 0, in_sz = lp;
+  while (g >= first + sz) {
+    first += sz;
+    in_off += in_sz;
+    in_sz = sz;
+    sz >>= 1;
+  }
+  const u256* in = levels + in_off + 2 * (g - first);
+  trace_node_half(stq, T, sp, base + (uint64_t)t * NODE_CELLS, in, in + 1, j);
+}
+// Blocks SA, MA (workgroup 0, over a) and SB, MB (workgroup 1, over b): t_i = g_sub(gamma, x_i) at sub + 4 i, acc_i = g_mul(acc_{i-1},
+// t_i) at mul + 4 (i - 1), acc_0 = t_0.  Each thread owns a contiguous stretch: its total of (gamma - x_i), an inclusive product scan
+// of the totals in LDS (block_scan_mul's scheme, polyops.hip), then the stretch again from the exclusive prefix, through the context's
+// own g_sub / g_mul: the flags are theirs and push() keeps to the rank window.  gamma is read where G's sponge left it.
+#define ANNC_THREADS 256
+__global__ __launch_bounds__(ANNC_THREADS) void k_annc_products(Streams st, const FpTables* __restrict__ T, const u256* __restrict__ ab,
+                                                                const u256* __restrict__ gamma_at, uint32_t n, uint64_t b_sa, uint64_t b_ma,
+                                                                uint64_t b_sb, uint64_t b_mb) {
+  __shared__ u256 sh[ANNC_THREADS];
+  const uint32_t tid = threadIdx.x, side = blockIdx.x;
+  const u256* x = ab + (size_t)side * n;
+  const uint64_t sub = side ? b_sb : b_sa, mul = side ? b_mb : b_ma;
+  const u256 gamma = *gamma_at, one = mont_one<Fr>();
+  const uint32_t E = (n + ANNC_THREADS - 1) / ANNC_THREADS;
+  const uint32_t lo = (uint64_t)tid * E < n ? tid * E : n, hi = lo + E < n ? lo + E : n;
+  u256 v = one;
+  for (uint32_t i = lo; i < hi; i++) v = fr_mul(v, fr_sub(gamma, x[i]));
+  sh[tid] = v;
+  __syncthreads();
+  for (uint32_t o = 1; o < ANNC_THREADS; o <<= 1) {
+    const u256 other = tid >= o ? sh[tid - o] : one;
+    __syncthreads();
+    if (tid >= o) {
+      v = fr_mul(v, other);
+      sh[tid] = v;
+    }
+    __syncthreads();
+  }
+  u256 acc = tid ? sh[tid - 1] : one;   // the product of every factor in front of the stretch
+  WCtx c = make_ctx(st, T, 0, 0);
+  Gadgets g(c);
+  for (uint32_t i = lo; i < hi; i++) {
+    c.pos = sub + 4ull * i;
+    const u256 t = g.g_sub(gamma, x[i]);
+    if (i == 0) {
+      acc = t;
+    } else {
+      c.pos = mul + 4ull * (i - 1);
+      acc = g.g_mul(acc, t);
+    }
+  }
+}
+// the tables of a call: [seg_off K + 1 | offsets K + 1] and [lp_t K + 1 | node_pre K + 2] (pageable sources of asynchronous uploads)
+struct AnncTables {
+  std::vector<uint64_t> u64;
+  std::vector<uint32_t> u32;
+};
+// a_leaves / b_leaves: the n database leaf digests in slot order and the n cluster leaf digests in grouped order, read only when the
+// trees are not resident (then they are hashed here, a launch per level and tree); dbtree / forest: the resident trees, both or neither;
+// croot: the centroids' root; pub: [database_root | index_root].  The work space is scratch slot 7 alone: scratch slot 0 is not touched.
+int wit_ann_cover_dev(const u256* a_leaves, const u256* b_leaves, const u256* croot, const uint64_t* sizes, size_t K, size_t n, const u256* dbtree,
+                      const u256* forest, Streams st, u256* pub) {
+  static thread_local AnncTables tb;
+  AnncLayout a;
+  TRY(annc_layout(sizes, K, n, &a));
+  const AnncBlocks& b = a.b;
+  const bool resident = dbtree != nullptr;
+  tb.u64.assign(2 * (K + 1), 0);
+  tb.u32.assign(2 * K + 3, 0);
+  uint64_t *seg_off = tb.u64.data(), *offsets = seg_off + K + 1;
+  uint32_t *lp_t = tb.u32.data(), *node_pre = lp_t + K + 1;
+  lp_t[0] = (uint32_t)b.lp;
+  node_pre[1] = (uint32_t)(b.lp - 1);
+  for (size_t c = 0; c < K; c++) {
+    uint64_t lp_c;
+    uint32_t d;
+    tree_shape(sizes[c], &lp_c, &d);
+    lp_t[1 + c] = (uint32_t)lp_c;
+    seg_off[c + 1] = seg_off[c] + 2 * lp_c;
+    offsets[c + 1] = offsets[c] + sizes[c];
+    node_pre[c + 2] = node_pre[c + 1] + (uint32_t)(lp_c - 1);
+  }
+  const uint64_t n_nodes = node_pre[K + 1], n_forest = seg_off[K];
+  const size_t n_st_d = (size_t)a.mw.nperm * PSD_T, n_st_g = 2 * PSD_T;
+  const size_t n_u256 = (K + 1) + 3 + n_st_d + n_st_g + 2 * n + (resident ? 0 : 2 * b.lp + n_forest) + 8;
+  u256* words = (u256*)scratch_get(7, n_u256 * sizeof(u256) + 2 * (K + 1) * 8 + (2 * K + 3 + 16) * 4);
+  if (!words) return VDB_ERR_OOM;
+  u256 *pubv = words + K + 1, *gamma = pubv + 2, *st_d = gamma + 1, *st_g = st_d + n_st_d, *ab = st_g + n_st_g, *own = ab + 2 * n;
+  uint64_t* d_u64 = (uint64_t*)(words + n_u256);
+  uint32_t* d_u32 = (uint32_t*)(d_u64 + 2 * (K + 1));
+  const uint64_t *d_seg = d_u64, *d_offsets = d_u64 + K + 1;
+  const uint32_t *d_lp = d_u32, *d_pre = d_u32 + K + 1;
+  hipStream_t s = ctx().stream;
+  FpEntry* fp;
+  const PoseidonSpec* sp;
+  TRY(mk_begin(st, &fp, &sp));
+  VDB_HIP(hipMemcpyAsync(d_u64, tb.u64.data(), 2 * (K + 1) * 8, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(d_u32, tb.u32.data(), (2 * K + 3) * 4, hipMemcpyHostToDevice, s));
+  if (!resident) {
+    u256 *own_db = own, *own_forest = own + 2 * b.lp;
+    VDB_HIP(hipMemsetAsync(own, 0, (2 * b.lp + n_forest) * sizeof(u256), s));
+    VDB_HIP(hipMemcpyAsync(own_db, a_leaves, n * sizeof(u256), hipMemcpyDeviceToDevice, s));
+    TRY(mk_levels_from_leaves(sp, own_db, b.lp, nullptr));
+    for (size_t c = 0; c < K; c++) {
+      VDB_HIP(hipMemcpyAsync(own_forest + seg_off[c], b_leaves + offsets[c], sizes[c] * sizeof(u256), hipMemcpyDeviceToDevice, s));
+      TRY(mk_levels_from_leaves(sp, own_forest + seg_off[c], lp_t[1 + c], nullptr));
+    }
+    dbtree = own_db;
+    forest = own_forest;
+  }
+  VDB_LAUNCH(k_annc_inputs, dim3((unsigned)((b.n_in + 255) / 256)), dim3(256), st, croot, dbtree, forest, d_seg, d_offsets, d_lp, (uint32_t)K, (uint32_t)n, words,
+             ab, pubv);
+  VDB_LAUNCH(k_push_cells, dim3(1), dim3(1), st, b.b_z, u256_zero(), u256_zero(), b.zero ? 1u : 0u);
+  VDB_LAUNCH(k_annc_forest_trace, dim3((unsigned)((2 * n_nodes + 63) / 64 + (n_nodes == 0))), dim3(64), st, fp->dev, sp, dbtree, forest, d_seg, d_lp, d_pre,
+             (uint32_t)(K + 1), b.b_td);
+  // D: the sponge over the header -> index_root; G: the sponge over [droot, index_root] -> gamma (two words: a node's cells)
+  TRY(mk_leaf_states(sp, words, 1u, (uint32_t)(K + 1), a.mw.nperm, st_d, pubv + 1, nullptr));
+  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((a.mw.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, words, 1u, (uint32_t)(K + 1), a.mw.nperm, b.b_d,
+             a.mw.leaf_cells, st_d, nullptr);
+  TRY(mk_leaf_states(sp, pubv, 1u, 2u, 2u, st_g, gamma, nullptr));
+  VDB_LAUNCH(k_mk_leaf_trace, dim3(1), dim3(64), st, fp->dev, sp, pubv, 1u, 2u, 2u, b.b_g, (uint64_t)NODE_CELLS, st_g, nullptr);
+  VDB_LAUNCH(k_annc_products, dim3(2), dim3(ANNC_THREADS), st, fp->dev, ab, gamma, (uint32_t)n, b.b_sa, b.b_ma, b.b_sb, b.b_mb);
+  VDB_HIP(hipMemcpyAsync(pub, pubv, 2 * sizeof(u256), hipMemcpyDeviceToDevice, s));
+  return VDB_OK;
+}
+
 // the means of all K clusters as values alone (include/vdb.h vdb_ann_cluster_means_dev); `offsets`: the host's copy, already checked
 static int ann_means_dev(FpEntry* fp, const u256* grouped, const uint64_t* offsets_dev, size_t K, size_t dim, int* err, u256* means) {
   Streams st{nullptr, nullptr, nullptr, err, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};   // the empty rank window: no stream is attached
@@ -3480,6 +3678,47 @@ int vdb_wit_ann_recentre(uint32_t P, uint32_t L, vdb_fr* centroid_levels, const 
   TRY(download(public_out, dpub.p, 3 * sizeof(u256)));
   TRY(download(centroid_levels, dl.p, 2 * lp * sizeof(u256)));
   return hs.finish(stream_out, lookup_out, selector_out, a.b.total, a.b.total_l);
+}
+
+// the cover of the database by the index (include/vdb.h)
+int vdb_wit_ann_cover_size(const uint64_t* cluster_sizes, size_t K, size_t n, uint64_t* cells, uint64_t* input_cells) {
+  VDB_REQUIRE_INIT();
+  AnncLayout a;
+  TRY(annc_layout(cluster_sizes, K, n, &a));
+  if (cells) *cells = a.b.total;
+  if (input_cells) *input_cells = a.b.n_in;
+  return VDB_OK;
+}
+int vdb_wit_ann_cover_dev(const vdb_fr* db_leaves_dev, const vdb_fr* cluster_leaves_dev, const vdb_fr* centroids_root_dev, const uint64_t* cluster_sizes,
+                          size_t K, size_t n, const vdb_fr* db_tree_dev, const vdb_fr* forest_dev, vdb_fr* stream_dev, uint8_t* selector_dev,
+                          vdb_fr* public_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(centroids_root_dev && stream_dev && public_dev, "null pointer");
+  VDB_ARG(!db_tree_dev == !forest_dev, "the resident database tree and the forest are given together or not at all");
+  VDB_ARG(db_tree_dev || (db_leaves_dev && cluster_leaves_dev), "null pointer: without the resident trees the call reads the two leaf arrays");
+  DevStreams ds;
+  ds.init(stream_dev, selector_dev);
+  TRY(wit_ann_cover_dev(db_leaves_dev ? as_u256(db_leaves_dev) : nullptr, cluster_leaves_dev ? as_u256(cluster_leaves_dev) : nullptr,
+                        as_u256(centroids_root_dev), cluster_sizes, K, n, db_tree_dev ? as_u256(db_tree_dev) : nullptr,
+                        forest_dev ? as_u256(forest_dev) : nullptr, ds.st, as_u256(public_dev)));
+  return ds.finish();
+}
+int vdb_wit_ann_cover(const vdb_fr* db_leaves, const vdb_fr* cluster_leaves, const vdb_fr* centroids_root, const uint64_t* cluster_sizes, size_t K, size_t n,
+                      vdb_fr* stream_out, uint8_t* selector_out, vdb_fr* public_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(db_leaves && cluster_leaves && centroids_root && public_out, "null pointer");
+  AnncLayout a;
+  TRY(annc_layout(cluster_sizes, K, n, &a));
+  DevBuf da, db, dc, dpub;
+  HostStreams hs;
+  TRY(upload(da, db_leaves, n * sizeof(u256)));
+  TRY(upload(db, cluster_leaves, n * sizeof(u256)));
+  TRY(upload(dc, centroids_root, sizeof(u256)));
+  TRY(dpub.alloc(2 * sizeof(u256)));
+  TRY(hs.init(a.b.total, 0, selector_out != nullptr));
+  TRY(wit_ann_cover_dev(da.as<u256>(), db.as<u256>(), dc.as<u256>(), cluster_sizes, K, n, nullptr, nullptr, hs.st, dpub.as<u256>()));
+  TRY(download(public_out, dpub.p, 2 * sizeof(u256)));
+  return hs.finish(stream_out, nullptr, selector_out, a.b.total, 0);
 }
 
 // the means of all K clusters of a resident index, values only (include/vdb.h): no stream, no window

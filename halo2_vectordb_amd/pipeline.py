@@ -1403,10 +1403,29 @@ class AnnIndex:
             raise
         return ix
 
+    def database_tree(self):
+        """the merkle_commitment tree over the database rows in slot order (2 lp digests, api.merkle_tree_build's layout) as a device
+        buffer this index owns, made once (vdb_ann_index_db_tree_dev): every leaf digest is copied from the forest to its row's slot,
+        no vector is hashed again.  Its root is the root QueryHotPath / MerkleHotPath publish for the same rows, and the database_root
+        of AnnCoverHotPath.  An index whose slots are no permutation of 0 .. n - 1 (a database with slots no cluster holds) is refused."""
+        if getattr(self, "d_db_tree", None) is None:
+            lp, _ = api.merkle_levels(self.n)
+            buf = api.DeviceBuffer(2 * lp * B)
+            try:
+                check(self.lib.vdb_ann_index_db_tree_dev(self.d_forest.ptr, api._p(np.ascontiguousarray(self.sizes, dtype=np.uint64)), self.d_slots.ptr, self.K,
+                                                         self.n, buf.ptr))
+            except Exception:
+                buf.free()
+                raise
+            self._bufs.append(buf)
+            self.d_db_tree = buf
+        return self.d_db_tree
+
     def free(self):
         for b in self._bufs:
             b.free()
         self._bufs = []
+        self.d_db_tree = None
 
 
 def _bind_cluster(hp, index, cluster):
@@ -1805,7 +1824,7 @@ class AnnAuditHotPath(_AnnClusterHotPath):
     select_by_indicator(distances, indicators) tied to the chain's minimum, merkle_commitment(centroids) tied to the header's centroids'
     root and merkle_commitment(members) tied to picked.  Public: [index_root | c].  It covers the build's cluster ids and the writes after
     them: audit cluster c of index.updated(hp) after a batch into c; K proofs cover an index.  That centroids are means is
-    proved per cluster by a proof of its own (AnnMeanHotPath).  Not proved: that the database is complete.  A member equidistant from two centroids is accepted under either.  The shape depends on (K, n_c, dim,
+    proved per cluster by a proof of its own (AnnMeanHotPath).  That the members are the database: AnnCoverHotPath.  A member equidistant from two centroids is accepted under either.  The shape depends on (K, n_c, dim,
     metric): one proving key per cluster size.  A misrouted member still gives a witness; results()[2] flags it and its copy fails in
     the Mock report.  `centroids` / `members`: quantized overrides of what the index holds (tests of the binding); with them the two
     trees are hashed by the call instead of read from the forest."""
@@ -1838,7 +1857,7 @@ class AnnMeanHotPath(_AnnClusterHotPath):
     indicators) -> own word by word, the constant quantization(n_c), the qadd chain over the members and one qdiv per word tied to own,
     merkle_commitment(centroids) tied to the header's centroids' root and merkle_commitment(members) tied to picked.  Public:
     [index_root | c].  K mean proofs and K routing audits (AnnAuditHotPath) state that the index is a fixed point of one Lloyd step over
-    the committed members.  Not proved: that the database is complete.  That a recentred index descends from its predecessor is a
+    the committed members.  That the members are the database: AnnCoverHotPath.  That a recentred index descends from its predecessor is a
     proof of its own, one centroid at a time (AnnRecentreHotPath).  The shape depends on (K, n_c, dim): one proving key per cluster size.  A centroid that is not the mean still gives a
     witness; results()[2] flags the words that differ and their copies fail in the Mock report.  `centroids` / `members`: quantized
     overrides of what the index holds (tests of the binding); with them the two trees are hashed by the call instead of read from the
@@ -1869,9 +1888,9 @@ class AnnRecentreHotPath(HotPath):
     tied to picked, UpdateHotPath's circuit with one write on the centroids' tree — its old root tied to the header's centroids' root,
     its index to c, its new vector to the quotients — and the sponge over [the new centroids' root | cluster roots] (index_root_new).
     Public: [index_root_old | c | index_root_new].  K such proofs, one per cluster, recentre an index: the memberships do not change
-    between them, so the chain ends on the root of AnnIndex.recentred().  The old centroid is never assigned.  Not proved: that the
-    database is complete; that the members are still routed to their cluster after the recentre (the routing audits of the new root say
-    which are not; a delete from one cluster and a write into another moves them).  The shape depends on (K, n_c, dim): one proving key
+    between them, so the chain ends on the root of AnnIndex.recentred().  The old centroid is never assigned.  Not proved: that
+    the members are still routed to their cluster after the recentre (the routing audits of the new root say which are not; a delete
+    from one cluster and a write into another moves them).  That the members are the database: AnnCoverHotPath.  The shape depends on (K, n_c, dim): one proving key
     per cluster size.  `d_levels` holds the centroids' tree after the write and `d_new` the new centroid; AnnIndex.recentred_with(hp)
     gives the next index.  `members` / `levels`: quantized overrides of the cluster's members and of the centroids' tree (tests of the
     binding); with `members` the cluster's tree is hashed by the call instead of read from the forest."""
@@ -1932,5 +1951,71 @@ class AnnRecentreHotPath(HotPath):
         from .circuit_dev import DeviceBuilder
         cm, public, _ = CS.build_ann_recentre(self.K, self.n, self.dim, self.P, self.L, functools.partial(self._fetch_flags, d_flags), self._fetch,
                                               builder=DeviceBuilder if on_device else None)
+        assert cm.n_cells == self.n_cells
+        return cm, public, None
+
+
+class AnnCoverHotPath(PoseidonHotPath):
+    """The index holds exactly the committed database (include/vdb.h vdb_wit_ann_cover): public [database_root | index_root], where
+    database_root is the merkle_commitment root QueryHotPath / MerkleHotPath / UpdateHotPath / ReadHotPath publish for the rows in slot
+    order and index_root the root every index proof is bound to.  Assigned: the header [centroids' root | cluster roots] and the 2 n leaf
+    digests, the database's in slot order and the clusters' in grouped order; then the database tree and the K cluster trees over them
+    (every root tied to the header), the sponge over the header (index_root), gamma = sponge([database_root, index_root]) and the two
+    products prod (gamma - a_i), prod (gamma - b_j), tied: the two multisets of leaf digests are equal, so the members of the index are
+    the database's vectors with their multiplicities (gamma is the circuit's own hash of the two roots, the one step argued in the model of an ideal hash).  No vector is hashed: the statement is on
+    leaf digests, which both commitments share.  The shape — and the verifying key — depends on n, K and the K cluster sizes, which are
+    therefore public.  Not covered: a database with emptied slots (after UpdateHotPath deletes; AnnIndex's own deletes compact).
+    `leaves`: (database leaf digests (n, 4), cluster leaf digests (n, 4)) in place of what the index holds (tests of the binding); the
+    K + 1 trees are then hashed by the call instead of read where they lie."""
+
+    def __init__(self, index, k=15, L=8, tau=None, col_shard=(0, 1), blind_seed=None, params=None, leaves=None):
+        self.index, self.K = index, index.K
+        self.sizes64 = np.ascontiguousarray(index.sizes, dtype=np.uint64)
+        super().__init__(index.n, index.dim, k, index.P, L, seed=None, tau=tau, col_shard=col_shard, vectors=np.zeros((0, index.dim)), blind_seed=blind_seed,
+                         params=params)
+        self.given_leaves = leaves
+
+    def n_input_rows(self):
+        return 0
+
+    def _load_inputs(self):
+        super()._load_inputs()
+        self.resident = self.given_leaves is None
+        if self.resident:
+            self.p_tree, self.p_a, self.p_b = self.index.database_tree().ptr, None, None
+        else:
+            a, b = (np.ascontiguousarray(x, dtype=np.uint64) for x in self.given_leaves)
+            assert a.shape == (self.n, 4) and b.shape == (self.n, 4), "n leaf digests a side"
+            self.p_tree = None
+            self.p_a, self.p_b = _given_ptr(self, a, a.shape, None), _given_ptr(self, b, b.shape, None)
+
+    def _circuit_size(self):
+        cells, n_in = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self.lib.vdb_wit_ann_cover_size(api._p(self.sizes64), self.K, self.n, ctypes.byref(cells), ctypes.byref(n_in)))
+        return n_in.value, cells.value - n_in.value, 0
+
+    def _alloc_outputs(self):
+        self.d_pub = self._output(2 * B)
+
+    def _witness(self, sel=None):
+        # the call writes the assigned header and digests too; the centroids' root is word 0 of the index's roots
+        ix = self.index
+        with self._window(sel, 0, lookup=False):
+            check(self.lib.vdb_wit_ann_cover_dev(self.p_a, self.p_b, ix.d_roots.ptr, api._p(self.sizes64), self.K, self.n, self.p_tree,
+                                                 ix.d_forest.ptr if self.resident else None, self.d_stream.ptr, self._sel_at(sel, 0), self.d_pub.ptr))
+
+    def public_values_dev(self):
+        return self.d_pub.ptr, 2
+
+    def results(self):
+        """(database_root (4,), index_root (4,))"""
+        pub = self.d_pub.download((2, 4))
+        return pub[0], pub[1]
+
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        cm, public, _ = CS.build_ann_cover(self.index.sizes, functools.partial(self._fetch_flags, d_flags), self._fetch,
+                                           builder=DeviceBuilder if on_device else None)
         assert cm.n_cells == self.n_cells
         return cm, public, None

@@ -666,6 +666,47 @@ int vdb_ann_index_recentre_dev(const vdb_fr *grouped_dev, const uint32_t *slots_
                                uint32_t *slots_out_dev, uint64_t *offsets_out_dev, vdb_fr *forest_out_dev, vdb_fr *roots_out_dev,
                                vdb_fr *centroids_out_dev);
 
+/* The cover of the database by the index (pipeline.AnnCoverHotPath): the index under index_root holds exactly the vectors under
+ * database_root, with their multiplicities.  The verifying key is fixed by n, K and the cluster sizes n_0 .. n_{K-1} (they sum to n, and
+ * are public with it).  Statement: database_root is the root of a merkle_commitment tree over n leaves, index_root is the sponge over
+ * [centroids_root | cluster_root_0 .. cluster_root_{K-1}], cluster_root_c is the root of a merkle_commitment tree over n_c leaves, both
+ * kinds padded with the zero cell, and the multiset of the n database leaf digests is the union of the multisets of the clusters' leaf
+ * digests.  Both commitments use one leaf hash (the sponge of a vector), so the statement is made on leaf digests: no vector is hashed.
+ * The multisets are compared by prod (gamma - a_i) = prod (gamma - b_j) at gamma = sponge([database_root, index_root]), a challenge the
+ * circuit derives itself (a random-oracle argument: DESIGN 4n).  Blocks in stream order:
+ *   A   assigned header [centroids_root | cluster_root_0 .. K-1]                                              K + 1 cells
+ *   I   assigned leaf digests a_0 .. a_{n-1} (database slot order), then b_0 .. b_{n-1} (grouped order)      2 n
+ *   Z   load_zero, once, where the database tree or a cluster tree is padded                                   0 or 1
+ *   TD  the database tree's nodes over a (level-major) -> droot                                                (lp - 1) NODE
+ *   TC  the K cluster trees' nodes over their stretches of b, c = 0 .. K - 1 -> root_c (n_c = 1: the leaf)     sum (lp_c - 1) NODE
+ *   D   the sponge over the header -> index_root
+ *   G   the sponge over [droot, index_root] -> gamma (two words: the cells of a node)
+ *   SA  g_sub(gamma, a_i) at SA + 4 i;  MA  g_mul(acc_{i-1}, t_i) at MA + 4 (i - 1), acc_0 = t_0             4 n + 4 (n - 1)
+ *   SB, MB  the same over b                                                                                    4 n + 4 (n - 1)
+ * NODE = 4,506 cells.  Copies (no cell): the trees' level-0 inputs copy I (padding copies Z), root_c copies the header's cluster_root_c,
+ * D's words copy A, G's words copy droot and D's digest, every gamma cell copies G's digest, the a_i / b_j cells of SA / SB copy I, the
+ * last accumulator of MA copies the last of MB.  No lookup cell.  public, 2 values: [database_root | index_root].
+ * db_leaves / cluster_leaves: n digests each; cluster_sizes: K x uint64, a HOST array; centroids_root: one digest.  The host-array form
+ * hashes the K + 1 trees itself (a launch per level and tree).  The _dev form takes the resident trees instead — db_tree_dev
+ * (vdb_ann_index_db_tree_dev, 2 lp digests) and forest_dev (vdb_ann_index_build_dev's), both or neither (one alone: VDB_ERR_ARG) — reads
+ * every digest where it lies (the two leaf arrays may then be NULL), and its launch list depends on neither K nor n.  It honours
+ * vdb_wit_set_window; public is whole in every window.  VDB_ERR_ARG before anything is launched: K == 0, K > VDB_ANN_MAX_CLUSTERS, an
+ * empty cluster, n > VDB_ANN_MAX_VECTORS, sizes that do not sum to n, more than 2^34 cells.  Each output of _size may be NULL. */
+int vdb_wit_ann_cover_size(const uint64_t *cluster_sizes, size_t K, size_t n, uint64_t *cells, uint64_t *input_cells);
+int vdb_wit_ann_cover(const vdb_fr *db_leaves, const vdb_fr *cluster_leaves, const vdb_fr *centroids_root, const uint64_t *cluster_sizes, size_t K,
+                      size_t n, vdb_fr *stream_out, uint8_t *selector_out, vdb_fr *public_out);
+int vdb_wit_ann_cover_dev(const vdb_fr *db_leaves_dev, const vdb_fr *cluster_leaves_dev, const vdb_fr *centroids_root_dev,
+                          const uint64_t *cluster_sizes, size_t K, size_t n, const vdb_fr *db_tree_dev, const vdb_fr *forest_dev,
+                          vdb_fr *stream_dev, uint8_t *selector_dev, vdb_fr *public_dev);
+/* The database tree of an index, values only: levels_out (2 lp digests, vdb_merkle_tree_build_dev's layout) is the tree over the n
+ * vectors in database slot order, bit for bit vdb_merkle_tree_build_dev over the same rows, without hashing a vector: grouped row g's
+ * leaf digest is copied from level 0 of its cluster's forest segment to slot slots[g], then the levels are hashed.  cluster_sizes:
+ * K x uint64, a HOST array; slots_dev: vdb_ann_index_build_dev's.  VDB_ERR_ARG before anything is launched: K == 0,
+ * K > VDB_ANN_MAX_CLUSTERS, n == 0, n > VDB_ANN_MAX_VECTORS, an empty cluster, sizes that do not sum to n; and after the call's one flag
+ * read: slots that are no permutation of 0 .. n - 1 (a database with slots no cluster holds; levels_out is then undefined). */
+int vdb_ann_index_db_tree_dev(const vdb_fr *forest_dev, const uint64_t *cluster_sizes, const uint32_t *slots_dev, size_t K, size_t n,
+                              vdb_fr *levels_out_dev);
+
 /* The means of all K clusters of an index as vdb_ann_index_build_dev leaves it, values only: means[k][j] =
  * qdiv(sum_i member_i[j], quantization(n_k)) over the rows [offsets[k], offsets[k + 1]) of the grouped rows, bit for bit what
  * vdb_wit_ann_mean constrains (the sum is exact in the field, so its order does not matter; the quotient is qdiv's value).  A server

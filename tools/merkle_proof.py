@@ -41,7 +41,11 @@ AnnIndex.means(), the circuit's own fixed-point means), is the mean of cluster c
 `--circuit ann-recentre --K C [--cluster c]` proves the recentre of cluster c of that index — default: the largest — from the old index
 root to the new one (pipeline.AnnRecentreHotPath: the centroids' tree with leaf c replaced by the leaf of the members' mean, the cluster
 roots carried over; [index_root_old | c | index_root_new] public), has the verifier check the proof and recentres the resident index
-(AnnIndex.recentred_with), whose root must be the public index_root_new.  Exit status 0 when both hold."""
+(AnnIndex.recentred_with), whose root must be the public index_root_new.  Exit status 0 when both hold.
+`--circuit ann-cover --K C` proves that that index holds exactly the committed database (pipeline.AnnCoverHotPath: the multiset of the
+database's leaf digests equals the union of the clusters'; [database_root | index_root] public; the cluster sizes are circuit shape),
+has the verifier check the proof and holds database_root against the root of the tree builder over the rows.  Exit status 0 when the
+proof is accepted and the roots agree."""
 import argparse
 import json
 import os
@@ -52,7 +56,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from halo2_vectordb_amd import api  # noqa: E402
-from halo2_vectordb_amd.pipeline import AnnAuditHotPath, AnnDeleteHotPath, AnnMeanHotPath, AnnRecentreHotPath, AnnIndex, AnnProbeQueryHotPath, AnnQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
+from halo2_vectordb_amd.pipeline import AnnAuditHotPath, AnnCoverHotPath, AnnDeleteHotPath, AnnMeanHotPath, AnnRecentreHotPath, AnnIndex, AnnProbeQueryHotPath, AnnQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
 from halo2_vectordb_amd.rounds import ProverRounds, quotient_identity_holds  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -63,7 +67,7 @@ ap.add_argument("--seed", type=int, default=20260003)
 ap.add_argument("--block-cols", type=int, default=510)
 ap.add_argument("--ext-block-cols", type=int, default=None)
 ap.add_argument("--proofs", type=int, default=2)
-ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read", "ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre"])
+ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read", "ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"])
 ap.add_argument("--lookup-bits", type=int, default=13)
 ap.add_argument("--metric", default="euclidean")
 ap.add_argument("--queries", type=int, default=1, help="--circuit query: queries proved against the one database in this proof")
@@ -100,7 +104,7 @@ elif args.circuit == "update":
         raise SystemExit("--deletes is between 0 and --updates, --grow is not negative")
     kinds = [0] * (args.updates - args.deletes) + [1] * args.deletes
     hp = UpdateHotPath(n=args.n, dim=args.dim, m=args.updates, k=args.k, seed=args.seed, kinds=kinds, grow=args.grow)
-elif args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre"):
+elif args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"):
     from halo2_vectordb_amd.pipeline import sift_like_vectors
     if not 1 <= args.K <= args.n:
         raise SystemExit("--K is between 1 and --n")
@@ -132,6 +136,8 @@ elif args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit", "ann-mean"
             raise SystemExit("--K is at least 2: a centroids' tree of one leaf has no path")
         c = int(np.argmax(index.sizes)) if args.cluster is None else args.cluster
         hp = AnnRecentreHotPath(index, c, k=args.k, L=args.lookup_bits)
+    elif args.circuit == "ann-cover":
+        hp = AnnCoverHotPath(index, k=args.k)
     elif multi_probe:
         hp = AnnProbeQueryHotPath(index, query, probes=args.probes, topk=args.topk, k=args.k, L=args.lookup_bits, metric=args.metric)
     elif args.circuit == "ann":
@@ -171,8 +177,8 @@ wall, host_ms, out = best
 T = {}
 pr.prove(None, timings=T)
 ok = quotient_identity_holds(pr, out["challenges"], out["evals"], out["instances"])
-# a read and the audits state the root first, the recentre its new root third, the other circuits last
-root_at = 0 if args.circuit in ("read", "ann-audit", "ann-mean") else 2 if args.circuit == "ann-recentre" else -1
+# a read, the audits and the cover (its database root) state the root first, the recentre its new root third, the other circuits last
+root_at = 0 if args.circuit in ("read", "ann-audit", "ann-mean", "ann-cover") else 2 if args.circuit == "ann-recentre" else -1
 root = api.fr_to_canonical(np.asarray(hp.results() if args.circuit == "merkle" else hp.results()[root_at]).reshape(1, 4))[0]
 root_int = int(root[0]) | int(root[1]) << 64 | int(root[2]) << 128 | int(root[3]) << 192
 if args.out:
@@ -180,7 +186,7 @@ if args.out:
     write_snark(args.out, out["proof"], out["instances"])
     pr.save_verifying_key(args.out + ".vk.npz", opened=out["opened"])
 accepted = {}
-if args.circuit in ("read", "ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre"):
+if args.circuit in ("read", "ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"):
     from halo2_vectordb_amd import verifier
     accepted = {"proof_accepted": bool(verifier.verify(out["proof"], out["instances"], verifier.VerifyingKey.from_prover(pr, out["opened"])))}
 if args.circuit == "ann-update":
@@ -198,6 +204,9 @@ if args.circuit == "ann-recentre":
     accepted["recentred_root_is_public_root"] = bool(np.array_equal(index2.roots()[-1], hp.results()[2]))
     accepted["root_moved"] = not np.array_equal(hp.results()[0], hp.results()[2])
     index2.free()
+if args.circuit == "ann-cover":
+    accepted["database_root_is_the_tree_builders"] = bool(np.array_equal(hp.results()[0], api.poseidon_merkle_root(index.qvec)))
+    accepted["index_root_is_the_indexs"] = bool(np.array_equal(hp.results()[1], index.roots()[-1]))
 if args.circuit == "ann-delete":
     index2 = index.removed(hp)
     accepted["removed_index_root_is_the_public_new_root"] = bool(np.array_equal(index2.roots()[-1], hp.results()[-1]))
@@ -210,6 +219,7 @@ what = f"merkle_commitment {args.n}x{args.dim} k={args.k}" if args.circuit == "m
     f"{args.updates} writes into cluster {hp.cluster} ({hp.n} members, tree grown {hp.grow} times) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-update" else \
     f"routing audit of cluster {hp.cluster} ({hp.n} members, {args.metric}) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann-audit" else \
     f"recentre of cluster {hp.cluster} ({hp.n} members) from the old index root to the new (K={args.K}) of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann-recentre" else \
+    f"cover of the database by the index (K={args.K}, cluster sizes {int(index.sizes.min())} .. {int(index.sizes.max())}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-cover" else \
     f"mean audit of cluster {hp.cluster} ({hp.n} members) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann-mean" else \
     f"{args.deletes} deletes from cluster {hp.cluster} ({hp.n} members, tree halved {hp.shrink} times) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-delete" else \
     f"query circuit ({str(args.queries) + ' x ' if args.queries > 1 else ''}{'top-' + str(args.topk) + ' ' if args.topk > 1 else ''}nearest_vector {args.metric} + merkle_commitment) over {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}"
@@ -222,9 +232,11 @@ print(json.dumps({"workload": what + ": whole constraint map, public outputs in 
                   "block_cols": args.block_cols, "ext_cols_held": hp.ext_cols}))
 pr.free()
 hp.free()
-if args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre"):
+if args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"):
     index.free()
-if args.circuit in ("ann-audit", "ann-mean", "ann-recentre") and not accepted["proof_accepted"]:
+if args.circuit == "ann-cover" and not (accepted["database_root_is_the_tree_builders"] and accepted["index_root_is_the_indexs"]):
+    sys.exit(1)
+if args.circuit in ("ann-audit", "ann-mean", "ann-recentre", "ann-cover") and not accepted["proof_accepted"]:
     sys.exit(1)
 if args.circuit == "ann-recentre" and not accepted["recentred_root_is_public_root"]:
     sys.exit(1)
