@@ -536,28 +536,6 @@ def ann_index_build(vectors, cluster_ids, centroids):
             b.free()
 
 
-def wit_ann_query(metric, query, centroids, members, cluster_roots, P=48, L=13, selectors=False):
-    """the circuit of one approximate-nearest-neighbour query (vdb_wit_ann_query) on query (dim, 4), centroids (K, dim, 4), the members of
-    the cluster searched (n_c, dim, 4) and the K cluster roots (K, 4): dict(stream, lookup, selectors, n_in, centroid_indicator (K, 4),
-    member_indicator (n_c, 4), result (dim, 4), index_root (4,), public (dim + 1, 4))"""
-    lib = _lib.init()
-    query, centroids, members, cluster_roots = _fr(query), _fr(centroids), _fr(members), _fr(cluster_roots)
-    K, dim, n_c = centroids.shape[0], centroids.shape[1], members.shape[0]
-    assert query.shape == (dim, 4) and members.shape[1] == dim and cluster_roots.shape == (K, 4)
-    cells, lk, n_in = _u64(), _u64(), _u64()
-    m = METRICS[metric]
-    check(lib.vdb_wit_ann_query_size(m, ctypes.c_uint32(P), ctypes.c_uint32(L), _sz(K), _sz(n_c), _sz(dim), ctypes.byref(cells), ctypes.byref(lk),
-                                     ctypes.byref(n_in)))
-    stream = np.zeros((cells.value, 4), dtype=np.uint64)
-    lookup = np.zeros((lk.value, 4), dtype=np.uint64)
-    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
-    ind_c, ind_m, pub = np.zeros((K, 4), dtype=np.uint64), np.zeros((n_c, 4), dtype=np.uint64), np.zeros((dim + 1, 4), dtype=np.uint64)
-    check(lib.vdb_wit_ann_query(m, ctypes.c_uint32(P), ctypes.c_uint32(L), _p(query), _p(centroids), _p(members), _p(cluster_roots), _sz(K), _sz(n_c),
-                                _sz(dim), _p(stream), _p(lookup), _p(sel) if selectors else None, _p(ind_c), _p(ind_m), _p(pub)))
-    return dict(stream=stream, lookup=lookup, **_split_flags(sel), n_in=n_in.value, centroid_indicator=ind_c, member_indicator=ind_m, result=pub[:dim],
-                index_root=pub[dim], public=pub)
-
-
 def wit_ann_probe(metric, query, centroids, members_list, cluster_roots, topk=1, P=48, L=13, selectors=False):
     """the circuit of one query over the p nearest clusters that returns the `topk` nearest candidates (vdb_wit_ann_probe) on query
     (dim, 4), centroids (K, dim, 4), members_list: the rows (n_r, dim, 4) of the p clusters the centroid rounds state, in round order, and
@@ -583,6 +561,16 @@ def wit_ann_probe(metric, query, centroids, members_list, cluster_roots, topk=1,
                                 _p(sizes), _sz(t), _p(stream), _p(lookup), _p(sel) if selectors else None, _p(ind_c), _p(ind_m), _p(pub)))
     return dict(stream=stream, lookup=lookup, **_split_flags(sel), n_in=n_in.value, centroid_indicators=ind_c, candidate_indicators=ind_m,
                 results=pub[:t * dim].reshape(t, dim, 4), index_root=pub[t * dim], public=pub)
+
+
+def wit_ann_query(metric, query, centroids, members, cluster_roots, P=48, L=13, selectors=False):
+    """the circuit of one query of the nearest cluster alone (vdb_wit_ann_query) on query (dim, 4), centroids (K, dim, 4), the members of
+    the cluster searched (n_c, dim, 4) and the K cluster roots (K, 4): wit_ann_probe of the one cluster at topk = 1; dict(stream, lookup,
+    selectors, n_in, centroid_indicator (K, 4), member_indicator (n_c, 4), result (dim, 4), index_root (4,), public (dim + 1, 4))"""
+    out = wit_ann_probe(metric, query, centroids, [members], cluster_roots, 1, P, L, selectors)
+    out["centroid_indicator"], out["member_indicator"] = out.pop("centroid_indicators")[0], out.pop("candidate_indicators")[0]
+    out["result"] = out.pop("results")[0]
+    return out
 
 
 def _wit_ann_cluster(size, call, metric, centroids, members, roots, cluster, P, L, selectors, flag, per_member):

@@ -1022,60 +1022,6 @@ def place_sponge(B, base, words, fetch_flags, fetch_values):
     return int(digest[0]), int(end[0])
 
 
-def ann_query_layout(metric, K, n_c, dim, P, L):
-    """where the blocks of the approximate-nearest-neighbour query circuit start (include/vdb.h vdb_wit_ann_query): dict(query, centroids,
-    members, roots: the assigned inputs; n_in; nearest_c, merkle_c, nearest_m, merkle_m, select, sponge: the blocks; total; lk_m: the
-    first lookup cell of the second search; total_l; units_c, units_m: nearest_units of the two searches; zero_c: the centroids' padding
-    loads the zero cell)"""
-    uc, um = nearest_units(metric, K, dim, 1, P, L), nearest_units(metric, n_c, dim, 1, P, L)
-    zero_c = (1 << (K - 1).bit_length()) > K
-    lay = dict(query=0, centroids=dim, members=dim + K * dim, roots=dim + K * dim + n_c * dim, units_c=uc, units_m=um, zero_c=zero_c)
-    lay["n_in"] = lay["nearest_c"] = lay["roots"] + K
-    lay["merkle_c"] = lay["nearest_c"] + uc["per_q"]
-    lay["nearest_m"] = lay["merkle_c"] + merkle_cells(K, dim)
-    lay["merkle_m"] = lay["nearest_m"] + um["per_q"]
-    lay["select"] = lay["merkle_m"] + merkle_cells(n_c, dim, zero_c)
-    lay["sponge"] = lay["select"] + 1 + 3 * K
-    lay["total"] = lay["sponge"] + merkle_leaf_layout(K + 1)["leaf_cells"]
-    lay["lk_m"], lay["total_l"] = uc["per_q_l"], uc["per_q_l"] + um["per_q_l"]
-    return lay
-
-
-def build_ann_query(metric, K, n_c, dim, P, L, fetch_flags, fetch_values, builder=None):
-    """The approximate-nearest-neighbour query against a committed index in one circuit (pipeline.AnnQueryHotPath): [query | centroids |
-    members | cluster roots] assigned, then nearest_vector(query, centroids), merkle_commitment(centroids), nearest_vector(query, members),
-    merkle_commitment(members), select_by_indicator(cluster roots, centroid indicator), whose output is TIED to the members' root — the
-    cluster searched is the winning centroid's — and the sponge over [centroids' root | cluster roots].  fetch_flags / fetch_values: as
-    place_merkle.  -> (CopyMap, public cells: the dim result cells then the index root, dict(centroid_indicator, member_indicator, result,
-    centroids_root, members_root, selected, index_root, layout))"""
-    if K < 1 or n_c < 1 or dim < 1:
-        raise ValueError("at least one centroid, one member and one word")
-    lay = ann_query_layout(metric, K, n_c, dim, P, L)
-    if np.asarray(fetch_flags(0, lay["n_in"])).any():
-        raise ValueError("the assigned inputs carry no gate or constant flag")
-    B = (builder or _Builder)(lay["total"], lay["total_l"])
-    query = np.arange(dim, dtype=np.int64).reshape(1, dim)
-    cent = lay["centroids"] + np.arange(K * dim, dtype=np.int64).reshape(K, dim)
-    mem = lay["members"] + np.arange(n_c * dim, dtype=np.int64).reshape(n_c, dim)
-    roots = lay["roots"] + np.arange(K, dtype=np.int64)
-    ind_c, _ = place_nearest(B, lay["units_c"], query, cent, lay["nearest_c"], 0)
-    croot, end = place_merkle(B, K, dim, lay["merkle_c"], lay["centroids"], fetch_flags, fetch_values)
-    assert end == lay["nearest_m"]
-    ind_m, res = place_nearest(B, lay["units_m"], query, mem, lay["nearest_m"], lay["lk_m"])
-    zero = lay["merkle_c"] + K * merkle_leaf_layout(dim)["leaf_cells"] if lay["zero_c"] else None
-    mroot, end = place_merkle(B, n_c, dim, lay["merkle_m"], lay["members"], fetch_flags, fetch_values, zero_cell=zero)
-    assert end == lay["select"]
-    ind_c, ind_m, res = ind_c.reshape(K), ind_m.reshape(n_c), res.reshape(dim)
-    sel = int(B.place(lay["units_c"]["sb"], [lay["select"]], [0], np.concatenate([roots, ind_c])[None, :])[0, 0])
-    B.tie(sel, mroot)                                        # constrain_equal(sel, mroot)
-    index_root, end = place_sponge(B, lay["sponge"], [croot] + [int(c) for c in roots], fetch_flags, fetch_values)
-    if end != lay["total"]:
-        raise ValueError("the trace does not end where the circuit does")
-    public = [int(c) for c in res] + [index_root]
-    return B.finish(), public, dict(centroid_indicator=ind_c, member_indicator=ind_m, result=res, centroids_root=croot, members_root=mroot, selected=sel,
-                                    index_root=index_root, layout=lay)
-
-
 def ann_probe_layout(metric, K, sizes, dim, p, t, P, L):
     """where the blocks of the query over the p nearest clusters start (include/vdb.h vdb_wit_ann_probe); `sizes`: the size of the cluster
     round r of the centroid search states, r < p.  dict(query, centroids, candidates, roots: the assigned inputs; n_in; N; offsets (p + 1):
@@ -1149,6 +1095,28 @@ def build_ann_probe(metric, K, sizes, dim, p, t, P, L, fetch_flags, fetch_values
     public = [int(c) for c in res.reshape(-1)] + [index_root]
     return B.finish(), public, dict(centroid_indicators=ind_c, candidate_indicators=ind_m, results=res, centroids_root=croot, members_roots=mroots,
                                     selected=[int(c) for c in sel], index_root=index_root, layout=lay)
+
+
+def _one_cluster(lay):
+    """an ann_probe_layout at p = 1 with the one cluster's entries as scalars: members (= candidates), merkle_m, select, and zero_c: the
+    centroids' padding loads the zero cell (the members' tree copies it)"""
+    return dict(lay, members=lay["candidates"], merkle_m=lay["merkle_m"][0], select=lay["select"][0], zero_c=lay["zero_cached"][0])
+
+
+def ann_query_layout(metric, K, n_c, dim, P, L):
+    """where the blocks of the single-cluster query start (include/vdb.h vdb_wit_ann_query): ann_probe_layout at sizes = [n_c], p = t = 1,
+    through _one_cluster"""
+    return _one_cluster(ann_probe_layout(metric, K, [n_c], dim, 1, 1, P, L))
+
+
+def build_ann_query(metric, K, n_c, dim, P, L, fetch_flags, fetch_values, builder=None):
+    """The query of the nearest cluster alone that returns its nearest member (pipeline.AnnQueryHotPath): build_ann_probe at sizes = [n_c],
+    p = t = 1.  -> (CopyMap, public cells: the dim result cells then the index root, dict(centroid_indicator (K,), member_indicator (n_c,),
+    result (dim,), centroids_root, members_root, selected, index_root, layout: ann_query_layout's))"""
+    cmap, public, info = build_ann_probe(metric, K, [n_c], dim, 1, 1, P, L, fetch_flags, fetch_values, builder=builder)
+    return cmap, public, dict(centroid_indicator=info["centroid_indicators"][0], member_indicator=info["candidate_indicators"][0], result=info["results"][0],
+                              centroids_root=info["centroids_root"], members_root=info["members_roots"][0], selected=info["selected"][0],
+                              index_root=info["index_root"], layout=_one_cluster(info["layout"]))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

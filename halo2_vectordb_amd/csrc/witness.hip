@@ -1978,74 +1978,13 @@ int wit_merkle_open_dev(const u256* levels, size_t n, size_t dim, const u256* ve
   return VDB_OK;
 }
 
-// ------------------------------------------------------------------ an approximate-nearest-neighbour query against the committed index
-// (include/vdb.h vdb_wit_ann_query; the index itself, its forest of K + 1 trees and their roots: resident.hip)
-// the circuit of one query (include/vdb.h vdb_wit_ann_query): where its blocks start
-struct AnnLayout {
-  DistLayout dl;
-  NvLayout nc, nm;
-  MkLayout mc, mm, mw;
-  uint64_t n_in, b_nc, b_mc, b_nm, b_mm, b_sel, b_root, total, l_nm, total_l;
-};
-static int ann_layout(FpEntry* fp, int metric, size_t K, size_t n_c, size_t dim, AnnLayout* o) {
-  VDB_ARG(K > 0 && n_c > 0 && dim > 0, "K = 0, empty cluster or dim = 0");
-  VDB_ARG(K <= VDB_ANN_MAX_CLUSTERS && n_c <= VDB_ANN_MAX_VECTORS && dim <= ((size_t)1 << 20), "query too large (include/vdb.h)");
-  TRY(nv_layout(fp, metric, K, dim, 1, &o->dl, &o->nc));
-  TRY(nv_fits(1, K, dim, 1, o->nc));
-  TRY(nv_layout(fp, metric, n_c, dim, 1, &o->dl, &o->nm));
-  TRY(nv_fits(1, n_c, dim, 1, o->nm));
-  mk_layout_pair(K, n_c, dim, &o->mc, &o->mm);
-  mk_layout(1, K + 1, 1, &o->mw);
-  o->n_in = dim + K * dim + n_c * dim + K;
-  o->b_nc = o->n_in;
-  o->b_mc = o->b_nc + o->nc.total;
-  o->b_nm = o->b_mc + o->mc.total;
-  o->b_mm = o->b_nm + o->nm.total;
-  o->b_sel = o->b_mm + o->mm.total;
-  o->b_root = o->b_sel + 1 + 3 * K;
-  o->total = o->b_root + o->mw.total;
-  o->l_nm = o->nc.total_l;
-  o->total_l = o->nc.total_l + o->nm.total_l;
-  VDB_ARG(o->total <= VDB_NEAREST_TOPK_MAX_CELLS, "query circuit above 2^34 cells");
-  return VDB_OK;
-}
-// [query | centroids | members | cluster roots] assigned, then nearest_vector(query, centroids), merkle_commitment(centroids),
-// nearest_vector(query, members), merkle_commitment(members), select_by_indicator(cluster roots, centroid indicator) — which the map ties
-// to the members' root — and the sponge over [centroids' root | cluster roots].  levels_c / levels_m: the two trees where they are
-// resident (forest segments), or null.  pub: the dim result words, then the index root.
-int wit_ann_query_dev(FpEntry* fp, int metric, const u256* query, const u256* centroids, const u256* members, const u256* cluster_roots,
-                      const u256* levels_c, const u256* levels_m, size_t K, size_t n_c, size_t dim, Streams st, u256* ind_c, u256* ind_m, u256* pub) {
-  AnnLayout a;
-  TRY(ann_layout(fp, metric, K, n_c, dim, &a));
-  const PoseidonSpec* sp;
-  TRY(poseidon_spec_dev(&sp, nullptr));
-  // work space of the call: [centroids' root | cluster roots] (the sponge's words), the selected root, the first search's result
-  u256* words = (u256*)scratch_get(7, (K + 1 + 1 + dim + 8 + (size_t)a.mw.nperm * PSD_T) * sizeof(u256));
-  if (!words) return VDB_ERR_OOM;
-  u256 *picked = words + K + 1, *res_c = picked + 1, *wstates = res_c + dim;
-  TRY(inv_list_attach(st, a.total));
-  TRY(set_winv(st, fp->dev));
-  hipStream_t s = ctx().stream;
-  const bool resident = levels_c && levels_m;
-  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)((dim + K * dim + 255) / 256)), dim3(256), st, 0, query, centroids, (uint64_t)dim, (uint64_t)(dim + K * dim));
-  VDB_LAUNCH(k_mku_inputs, dim3((unsigned)((n_c * dim + K + 255) / 256)), dim3(256), st, dim + K * dim, members, cluster_roots, (uint64_t)(n_c * dim),
-             (uint64_t)(n_c * dim + K));
-  TRY(nv_emit(fp, a.dl, a.nc, query, centroids, 1, K, dim, 1, st, a.b_nc, 0, true, ind_c, res_c));
-  TRY(mk_emit(fp, sp, centroids, K, dim, a.mc, st, a.b_mc, resident ? levels_c : nullptr, words));
-  TRY(nv_emit(fp, a.dl, a.nm, query, members, 1, n_c, dim, 1, st, a.b_nm, a.l_nm, true, ind_m, pub));
-  TRY(mk_emit(fp, sp, members, n_c, dim, a.mm, st, a.b_mm, resident ? levels_m : nullptr, nullptr));
-  VDB_HIP(hipMemcpyAsync(words + 1, cluster_roots, K * sizeof(u256), hipMemcpyDeviceToDevice, s));
-  const NvMap sm{a.b_sel, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, (uint32_t)K, 1u, 1u};
-  VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), st, fp->dev, sm, 1u, cluster_roots, ind_c, picked);
-  TRY(mk_leaf_states(sp, words, 1u, (uint32_t)(K + 1), a.mw.nperm, wstates, pub + dim, nullptr));
-  VDB_LAUNCH(k_mk_leaf_trace, dim3((unsigned)((a.mw.nperm + 63) / 64)), dim3(64), st, fp->dev, sp, words, 1u, (uint32_t)(K + 1), a.mw.nperm, a.b_root,
-             a.mw.leaf_cells, wstates, nullptr);
-  return inv_list_fixup(st);
-}
-
-// ------------------------------------------------------------------ the query over the p nearest clusters that returns the t nearest
-// candidates (include/vdb.h vdb_wit_ann_probe): the blocks of the query above, the two searches with p and t rounds, one members' tree
-// and one selection per probed cluster
+// ------------------------------------------------------------------ an approximate-nearest-neighbour query against the committed index:
+// over the p nearest clusters, the t nearest candidates (include/vdb.h vdb_wit_ann_probe; the single-cluster vdb_wit_ann_query is this at
+// p = t = 1; the index itself, its forest of K + 1 trees and their roots: resident.hip).
+// [query | centroids | candidates | cluster roots] assigned, then nearest_vector(query, centroids) with p rounds, merkle_commitment(centroids),
+// nearest_vector(query, candidates) with t rounds, one merkle_commitment per probed cluster, one select_by_indicator(cluster roots, centroid
+// indicator of the round) per probed cluster — which the map ties to that cluster's root — and the sponge over [centroids' root | cluster
+// roots].  Where its blocks start:
 struct AnnpLayout {
   DistLayout dl;
   NvLayout nc, nm;
@@ -3358,64 +3297,7 @@ int vdb_wit_merkle_open(const vdb_fr* levels, size_t n, size_t dim, const vdb_fr
   return hs.finish(stream_out, nullptr, selector_out, ml.total, 0);
 }
 
-// the circuit of one approximate-nearest-neighbour query (include/vdb.h)
-int vdb_wit_ann_query_size(int metric, uint32_t P, uint32_t L, size_t K, size_t n_c, size_t dim, uint64_t* cells, uint64_t* lookups, uint64_t* input_cells) {
-  VDB_REQUIRE_INIT();
-  FpEntry* fp;
-  TRY(get_fp(P, L, &fp));
-  AnnLayout a;
-  TRY(ann_layout(fp, metric, K, n_c, dim, &a));
-  if (cells) *cells = a.total;
-  if (lookups) *lookups = a.total_l;
-  if (input_cells) *input_cells = a.n_in;
-  return VDB_OK;
-}
-int vdb_wit_ann_query_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* query_dev, const vdb_fr* centroids_dev, const vdb_fr* members_dev,
-                          const vdb_fr* cluster_roots_dev, const vdb_fr* centroid_levels_dev, const vdb_fr* member_levels_dev, size_t K, size_t n_c,
-                          size_t dim, vdb_fr* stream_dev, vdb_fr* lookup_dev, uint8_t* selector_dev, vdb_fr* centroid_indicator_dev,
-                          vdb_fr* member_indicator_dev, vdb_fr* public_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(query_dev && centroids_dev && members_dev && cluster_roots_dev && stream_dev && lookup_dev && centroid_indicator_dev && member_indicator_dev &&
-              public_dev,
-          "null pointer");
-  VDB_ARG(!centroid_levels_dev == !member_levels_dev, "the two resident trees are given together or not at all");
-  FpEntry* fp;
-  TRY(get_fp(P, L, &fp));
-  DevStreams ds;
-  TRY(ds.init(stream_dev, selector_dev, lookup_dev));
-  TRY(wit_ann_query_dev(fp, metric, as_u256(query_dev), as_u256(centroids_dev), as_u256(members_dev), as_u256(cluster_roots_dev),
-                        centroid_levels_dev ? as_u256(centroid_levels_dev) : nullptr, member_levels_dev ? as_u256(member_levels_dev) : nullptr, K, n_c, dim,
-                        ds.st, as_u256(centroid_indicator_dev), as_u256(member_indicator_dev), as_u256(public_dev)));
-  return ds.finish();
-}
-int vdb_wit_ann_query(int metric, uint32_t P, uint32_t L, const vdb_fr* query, const vdb_fr* centroids, const vdb_fr* members, const vdb_fr* cluster_roots,
-                      size_t K, size_t n_c, size_t dim, vdb_fr* stream_out, vdb_fr* lookup_out, uint8_t* selector_out, vdb_fr* centroid_indicator_out,
-                      vdb_fr* member_indicator_out, vdb_fr* public_out) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(query && centroids && members && cluster_roots, "null pointer");
-  FpEntry* fp;
-  TRY(get_fp(P, L, &fp));
-  AnnLayout a;
-  TRY(ann_layout(fp, metric, K, n_c, dim, &a));
-  DevBuf dq, dc, dm, dr, dic, dim_, dpub;
-  HostStreams hs;
-  TRY(upload(dq, query, dim * sizeof(u256)));
-  TRY(upload(dc, centroids, K * dim * sizeof(u256)));
-  TRY(upload(dm, members, n_c * dim * sizeof(u256)));
-  TRY(upload(dr, cluster_roots, K * sizeof(u256)));
-  TRY(dic.alloc(K * sizeof(u256)));
-  TRY(dim_.alloc(n_c * sizeof(u256)));
-  TRY(dpub.alloc((dim + 1) * sizeof(u256)));
-  TRY(hs.init(a.total, a.total_l, selector_out != nullptr));
-  TRY(wit_ann_query_dev(fp, metric, dq.as<u256>(), dc.as<u256>(), dm.as<u256>(), dr.as<u256>(), nullptr, nullptr, K, n_c, dim, hs.st, dic.as<u256>(),
-                        dim_.as<u256>(), dpub.as<u256>()));
-  TRY(download(centroid_indicator_out, dic.p, K * sizeof(u256)));
-  TRY(download(member_indicator_out, dim_.p, n_c * sizeof(u256)));
-  TRY(download(public_out, dpub.p, (dim + 1) * sizeof(u256)));
-  return hs.finish(stream_out, lookup_out, selector_out, a.total, a.total_l);
-}
-
-// the query over the p nearest clusters (include/vdb.h)
+// the approximate-nearest-neighbour query over the p nearest clusters (include/vdb.h)
 int vdb_wit_ann_probe_size(int metric, uint32_t P, uint32_t L, size_t K, size_t dim, size_t p, const size_t* n_c, size_t t, uint64_t* cells,
                            uint64_t* lookups, uint64_t* input_cells) {
   VDB_REQUIRE_INIT();
@@ -3481,6 +3363,27 @@ int vdb_wit_ann_probe(int metric, uint32_t P, uint32_t L, const vdb_fr* query, c
   TRY(download(candidate_indicators_out, dim_.p, t * N * sizeof(u256)));
   TRY(download(public_out, dpub.p, (t * dim + 1) * sizeof(u256)));
   return hs.finish(stream_out, lookup_out, selector_out, total, total_l);
+}
+
+// the single-cluster query is the query over the p nearest clusters at p = t = 1 (include/vdb.h)
+int vdb_wit_ann_query_size(int metric, uint32_t P, uint32_t L, size_t K, size_t n_c, size_t dim, uint64_t* cells, uint64_t* lookups, uint64_t* input_cells) {
+  return vdb_wit_ann_probe_size(metric, P, L, K, dim, 1, &n_c, 1, cells, lookups, input_cells);
+}
+int vdb_wit_ann_query(int metric, uint32_t P, uint32_t L, const vdb_fr* query, const vdb_fr* centroids, const vdb_fr* members, const vdb_fr* cluster_roots,
+                      size_t K, size_t n_c, size_t dim, vdb_fr* stream_out, vdb_fr* lookup_out, uint8_t* selector_out, vdb_fr* centroid_indicator_out,
+                      vdb_fr* member_indicator_out, vdb_fr* public_out) {
+  return vdb_wit_ann_probe(metric, P, L, query, centroids, members, cluster_roots, K, dim, 1, &n_c, 1, stream_out, lookup_out, selector_out,
+                           centroid_indicator_out, member_indicator_out, public_out);
+}
+// the one cluster's rows and its resident tree as arrays of one
+int vdb_wit_ann_query_dev(int metric, uint32_t P, uint32_t L, const vdb_fr* query_dev, const vdb_fr* centroids_dev, const vdb_fr* members_dev,
+                          const vdb_fr* cluster_roots_dev, const vdb_fr* centroid_levels_dev, const vdb_fr* member_levels_dev, size_t K, size_t n_c,
+                          size_t dim, vdb_fr* stream_dev, vdb_fr* lookup_dev, uint8_t* selector_dev, vdb_fr* centroid_indicator_dev,
+                          vdb_fr* member_indicator_dev, vdb_fr* public_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(members_dev, "null pointer");
+  return vdb_wit_ann_probe_dev(metric, P, L, query_dev, centroids_dev, &members_dev, cluster_roots_dev, centroid_levels_dev, &member_levels_dev, K, dim, 1,
+                               &n_c, 1, stream_dev, lookup_dev, selector_dev, centroid_indicator_dev, member_indicator_dev, public_dev);
 }
 
 // inserts and replacements against the index root, and the index after them (include/vdb.h)

@@ -1447,71 +1447,6 @@ def _given_ptr(hp, given, shape, resident_ptr):
     return d.ptr
 
 
-class AnnQueryHotPath(HotPath):
-    """An approximate-nearest-neighbour query against a committed AnnIndex in ONE proof (include/vdb.h vdb_wit_ann_query): assign the
-    query, the centroids, the members of the cluster searched and the K cluster roots; nearest_vector(query, centroids),
-    merkle_commitment(centroids), nearest_vector(query, members), merkle_commitment(members), select_by_indicator(cluster roots,
-    centroid indicator) tied to the members' root, and the sponge over [centroids' root | cluster roots].  The reference runs the two
-    searches in two circuits and compares roots outside them (tests/demo/mod.rs:52 "FIXME: these should be done in the same circuit"):
-    this is that one circuit.  Public: the result vector, then the index root.  The circuit's shape depends on (K, n_c, dim, metric):
-    one proving key per cluster size.  `cluster`: the cluster searched (None: index.probe(query)); a cluster other than the winning
-    centroid's breaks the copy constraint.  `cluster_roots` / `centroids`: quantized overrides of what the index holds (tests of the
-    binding); with them the two trees are hashed by the call instead of read from the forest."""
-
-    def __init__(self, index, query, cluster=None, k=13, P=48, L=12, metric="euclidean", tau=None, col_shard=(0, 1), blind_seed=None, params=None,
-                 cluster_roots=None, centroids=None):
-        query = np.ascontiguousarray(query, dtype=np.float64).reshape(1, index.dim)
-        self.index, self.K = index, index.K
-        self.cluster = index.probe(query[0]) if cluster is None else int(cluster)
-        super().__init__(int(index.sizes[self.cluster]), index.dim, k, P, L, seed=None, tau=tau, col_shard=col_shard, vectors=query, blind_seed=blind_seed,
-                         params=params)
-        self.metric, self.metric_name = api.METRICS[metric], metric
-        self.given_roots, self.given_cent = cluster_roots, centroids
-
-    def n_input_rows(self):
-        return 1
-
-    def _load_inputs(self):
-        super()._load_inputs()
-        ix, self.resident = self.index, self.given_roots is None and self.given_cent is None
-        self.p_roots = _given_ptr(self, self.given_roots, (self.K, 4), ix.d_roots.at(B))
-        self.p_cent = _given_ptr(self, self.given_cent, (self.K, self.dim, 4), ix.d_cent.ptr)
-
-    def _circuit_size(self):
-        cells, lk, n_in = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-        check(self.lib.vdb_wit_ann_query_size(self.metric, self.P, self.L, self.K, self.n, self.dim, ctypes.byref(cells), ctypes.byref(lk), ctypes.byref(n_in)))
-        return n_in.value, cells.value - n_in.value, lk.value
-
-    def _alloc_outputs(self):
-        self.d_ind_c, self.d_ind_m = self._output(self.K * B), self._output(self.n * B)
-        self.d_pub = self._output((self.dim + 1) * B)
-
-    def _witness(self, sel=None):
-        # the call writes the assigned witnesses too (centroids, members and roots where the index holds them)
-        ix = self.index
-        with self._window(sel, 0):
-            check(self.lib.vdb_wit_ann_query_dev(self.metric, self.P, self.L, self.d_vec.ptr, self.p_cent, ix.members_ptr(self.cluster), self.p_roots,
-                                                 ix.levels_ptr(self.K) if self.resident else None, ix.levels_ptr(self.cluster) if self.resident else None,
-                                                 self.K, self.n, self.dim, self.d_stream.ptr, self.d_lookup.ptr, self._sel_at(sel, 0), self.d_ind_c.ptr,
-                                                 self.d_ind_m.ptr, self.d_pub.ptr))
-
-    def public_values_dev(self):
-        return self.d_pub.ptr, self.dim + 1
-
-    def results(self):
-        """(centroid indicator (K, 4), member indicator (n_c, 4), result (dim, 4), index root (4,))"""
-        pub = self.d_pub.download((self.dim + 1, 4))
-        return self.d_ind_c.download((self.K, 4)), self.d_ind_m.download((self.n, 4)), pub[:self.dim], pub[self.dim]
-
-    def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        cm, public, _ = CS.build_ann_query(self.metric_name, self.K, self.n, self.dim, self.P, self.L, functools.partial(self._fetch_flags, d_flags),
-                                           self._fetch, builder=DeviceBuilder if on_device else None)
-        assert cm.n_cells == self.n_cells
-        return cm, public, None
-
-
 class AnnProbeQueryHotPath(HotPath):
     """The approximate-nearest-neighbour query with the two knobs of an IVF-style index, in ONE proof (include/vdb.h vdb_wit_ann_probe):
     the `topk` nearest candidates over the members of the `probes` clusters whose centroids `probes` rounds of top-k over the committed
@@ -1601,6 +1536,26 @@ class AnnProbeQueryHotPath(HotPath):
                                            functools.partial(self._fetch_flags, d_flags), self._fetch, builder=DeviceBuilder if on_device else None)
         assert cm.n_cells == self.n_cells
         return cm, public, None
+
+
+class AnnQueryHotPath(AnnProbeQueryHotPath):
+    """The query of the nearest cluster alone (include/vdb.h vdb_wit_ann_query): nearest_vector(query, centroids), then
+    nearest_vector(query, members of the winning centroid's cluster), both trees and the index root in ONE proof.  The reference runs the
+    two searches in two circuits and compares roots outside them (tests/demo/mod.rs:52 "FIXME: these should be done in the same
+    circuit"): this is that one circuit.  Public: the result vector, then the index root.  The circuit's shape depends on (K, n_c, dim,
+    metric): one proving key per cluster size.  `cluster`: the cluster searched (None: index.probe(query)); a cluster other than the
+    winning centroid's breaks the copy constraint.  AnnProbeQueryHotPath at probes = topk = 1, its results without the round axes."""
+
+    def __init__(self, index, query, cluster=None, k=13, P=48, L=12, metric="euclidean", tau=None, col_shard=(0, 1), blind_seed=None, params=None,
+                 cluster_roots=None, centroids=None):
+        super().__init__(index, query, 1, 1, None if cluster is None else [cluster], k, P, L, metric, tau, col_shard, blind_seed, params, cluster_roots,
+                         centroids)
+        self.cluster = self.clusters[0]
+
+    def results(self):
+        """(centroid indicator (K, 4), member indicator (n_c, 4), result (dim, 4), index root (4,))"""
+        ind_c, ind_m, res, root = super().results()
+        return ind_c[0], ind_m[0], res[0], root
 
 
 class _AnnBatchHotPath(PoseidonHotPath):

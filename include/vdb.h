@@ -357,8 +357,10 @@ int vdb_wit_merkle_open_dev(const vdb_fr *levels_dev, size_t n, size_t dim, cons
  * Cost: the grouping kernel is a single wavefront that walks the n rows 64 at a time (a 64-step shuffle loop and two barriers a tile)
  * and writes every row's place itself: n / 64 serial tiles on one compute unit, 262,144 of them at n = VDB_ANN_MAX_VECTORS.
  *
- * vdb_wit_ann_query: assigned, from cell 0: the query (dim), the centroids (K x dim), the members of the cluster searched (n_c x dim),
- * the K cluster roots: input_cells of them.  Then
+ * vdb_wit_ann_query_size, vdb_wit_ann_query and vdb_wit_ann_query_dev are vdb_wit_ann_probe_size, vdb_wit_ann_probe and
+ * vdb_wit_ann_probe_dev (below) at p == t == 1, the cluster searched the one entry of their lists: they forward there.  Its stream at
+ * these values: assigned, from cell 0: the query (dim), the centroids (K x dim), the members of the cluster searched (n_c x dim), the K
+ * cluster roots: input_cells of them.  Then
  *   ind_c, _  = nearest_vector(query, centroids)            croot = merkle_commitment(centroids)
  *   _, result = nearest_vector(query, members)              mroot = merkle_commitment(members)
  *   sel       = gate.select_by_indicator(cluster_roots, ind_c)                  (1 + 3 K cells)
@@ -405,7 +407,7 @@ int vdb_wit_ann_query_dev(int metric, uint32_t precision_bits, uint32_t lookup_b
  * Ties are vdb_wit_nearest_topk's: centroids at equal distance leave in the same round, which states the LAST of them — two centroids
  * tied nearest cost one probe and the earlier one is never searched; a round with nothing left unmasked states centroid K - 1 again.
  * The entry points take whatever cluster list they are given: candidates of other clusters still give a stream, which breaks a
- * sel_r = mroot_r copy.  At p == t == 1 the streams, flags and public values are vdb_wit_ann_query's byte for byte.
+ * sel_r = mroot_r copy.  At p == t == 1 this is vdb_wit_ann_query: its entry points are these with lists of one.
  * vdb_wit_ann_probe: candidates is one flat N x dim host array; the call hashes the trees itself.  vdb_wit_ann_probe_dev: members_dev is a
  * HOST array of p device pointers to the clusters' rows, member_levels_dev a HOST array of p device pointers to their trees (forest
  * segments) or NULL, centroid_levels_dev the centroids' tree or NULL: the p + 1 resident trees come all together or not at all

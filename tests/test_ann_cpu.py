@@ -83,6 +83,24 @@ def test_map_counts_tie_and_public_cells(O, K, n, ids):
         assert ((cm.copy_of == lay["roots"] + k) & (np.arange(cm.n_cells) >= lay["sponge"])).sum() == 1
 
 
+@pytest.mark.parametrize("K,n,ids", [(3, 12, IDS), (2, 2, [1, 0]), (1, 5, [0] * 5), (4, 6, [0, 1, 2, 3, 3, 3])])
+def test_map_is_the_probe_maps_at_one_cluster_and_one_neighbour(O, K, n, ids):
+    """build_ann_query is a view of build_ann_probe at sizes = [n_c], p = t = 1: the same map and public cells, the info without the round axes"""
+    db, ids, cent, query = _setup(O, seed=9 + K, n=n, K=K, ids=ids)
+    members, _ = AN.select_cluster(db, ids, _winner(O, query, cent))
+    n_c = members.shape[0]
+    m = AN.query_model(O, "euclidean", query, cent, members, AN.index_model(O, db, ids, cent)["roots"][1:1 + K], P, L)
+    ff, fv, _ = fetchers(m)
+    cm, public, info = CS.build_ann_query("euclidean", K, n_c, 4, P, L, ff, fv)
+    pm, ppublic, pinfo = CS.build_ann_probe("euclidean", K, [n_c], 4, 1, 1, P, L, ff, fv)
+    for key in ("copy_of", "gate", "lookup_src"):
+        assert np.array_equal(np.asarray(getattr(cm, key)), np.asarray(getattr(pm, key))), key
+    assert public == ppublic
+    assert (info["centroid_indicator"].shape, info["member_indicator"].shape, info["result"].shape) == ((K,), (n_c,), (4,))
+    assert np.array_equal(info["centroid_indicator"], pinfo["centroid_indicators"][0]) and np.array_equal(info["result"], pinfo["results"][0])
+    assert np.array_equal(info["member_indicator"], pinfo["candidate_indicators"][0])
+
+
 def test_wrong_cluster_and_altered_root_break_the_map(O):
     db, ids, cent, query = _setup(O)
     ix = AN.index_model(O, db, ids, cent)

@@ -287,6 +287,98 @@ def test_query_launch_count_depends_on_neither_K_nor_the_cluster_size_and_one_re
     assert (K0, n0, K1, n1) == (3, 7, 5, 65) and c0 == c1 and sum(c0.values()) >= 1, counts
 
 
+def test_single_cluster_entry_points_refuse_what_they_refused_and_launch_nothing(api, O):
+    """vdb_wit_ann_query_size and vdb_wit_ann_query_dev forward to vdb_wit_ann_probe*: K = 0, an empty cluster, dim = 0, a cluster above
+    VDB_ANN_MAX_VECTORS and (the device call) null members are VDB_ERR_ARG as they were, before anything is launched"""
+    from halo2_vectordb_amd._lib import check
+    index, hp = _hot_path(O, "1-1")
+    try:
+        hp.setup()
+        hp._witness()
+        api.sync()
+        lc, lm, members = index.levels_ptr(hp.K), index.levels_ptr(hp.cluster), index.members_ptr(hp.cluster)
+        cells, lk, n_in = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        dev = lambda K, n_c, dim, mem: hp.lib.vdb_wit_ann_query_dev(hp.metric, P, L, hp.d_vec.ptr, hp.p_cent, mem, hp.p_roots, lc, lm, K, n_c, dim,
+                                                                    hp.d_stream.ptr, hp.d_lookup.ptr, None, hp.d_ind_c.ptr, hp.d_ind_m.ptr, hp.d_pub.ptr)
+        size = lambda K, n_c, dim: hp.lib.vdb_wit_ann_query_size(hp.metric, P, L, K, n_c, dim, ctypes.byref(cells), ctypes.byref(lk), ctypes.byref(n_in))
+        check(size(hp.K, hp.n, DIM))
+        assert (cells.value, lk.value, n_in.value) == (hp.n_cells, hp.n_lookup, hp.n_in)
+        api.profile_begin(deferred=True)
+        for K, n_c, dim in ((0, hp.n, DIM), (hp.K, 0, DIM), (hp.K, hp.n, 0), (hp.K, (1 << 24) + 1, DIM)):
+            for call in (lambda: size(K, n_c, dim), lambda: dev(K, n_c, dim, members)):
+                with pytest.raises(api.VdbError) as e:
+                    check(call())
+                assert e.value.code == -3, (K, n_c, dim)
+        with pytest.raises(api.VdbError) as e:
+            check(dev(hp.K, hp.n, DIM, None))
+        assert e.value.code == -3
+        api.sync()
+        assert api.profile_end() == {}
+    finally:
+        hp.free()
+        index.free()
+
+
+def test_single_cluster_hot_path_is_the_probe_at_one_cluster_and_one_neighbour(api, O):
+    from halo2_vectordb_amd.pipeline import AnnProbeQueryHotPath
+    n, K, ids, f, db, cent, query = _setup(O, "1-4-7")
+    index, hp = _hot_path(O, "1-4-7")
+    try:
+        assert isinstance(hp, AnnProbeQueryHotPath) and hp.probes == hp.topk == 1
+        assert hp.cluster == index.probe(f["query"]) == _winner(O, query, cent) and hp.clusters == [hp.cluster]
+        hp.setup()
+        hp._witness()
+        api.sync()
+        ind_c, ind_m, res, root = hp.results()
+        assert (ind_c.shape, ind_m.shape, res.shape, root.shape) == ((K, 4), (hp.n, 4), (DIM, 4), (4,)) and hp.n == 7
+        slots = np.flatnonzero((db == res[None]).all(axis=(1, 2)))
+        assert len(slots) == 1 and np.array_equal(hp.neighbours(), slots)
+    finally:
+        hp.free()
+        index.free()
+
+
+def test_single_cluster_c_entry_points_write_the_hot_paths_and_the_wrappers_bytes(api, O):
+    """vdb_wit_ann_query_dev and vdb_wit_ann_query called as vdb.h declares them: the device form, with the two resident trees and with
+    neither, fills fresh buffers with the hot path's stream, lookup stream, indicators and public values (which
+    test_hot_path_is_the_model_split_windows_and_resident_roots holds to the model); the host form gives api.wit_ann_query's arrays"""
+    from halo2_vectordb_amd._lib import check
+    query, cent, members, roots = (np.ascontiguousarray(a, dtype=np.uint64) for a in _witness_case(api, O, "1-4-7")[:4])
+    index, hp = _hot_path(O, "1-4-7")
+    K, n_c = hp.K, hp.n
+    bufs = []
+    try:
+        hp.setup()
+        hp._witness()
+        api.sync()
+        sizes = dict(stream=hp.n_cells, lookup=hp.n_lookup, ind_c=K, ind_m=n_c, pub=DIM + 1)
+        want = dict(stream=hp.d_stream.download((hp.n_cells, 4)), lookup=hp.d_lookup.download((hp.n_lookup, 4)), ind_c=hp.d_ind_c.download((K, 4)),
+                    ind_m=hp.d_ind_m.download((n_c, 4)), pub=hp.d_pub.download((DIM + 1, 4)))
+        for lc, lm in ((index.levels_ptr(K), index.levels_ptr(hp.cluster)), (None, None)):
+            d = {key: api.DeviceBuffer(rows * 32) for key, rows in sizes.items()}
+            bufs += list(d.values())
+            for b in d.values():
+                check(hp.lib.vdb_memset_dev(b.ptr, 0xA5, ctypes.c_size_t(b.nbytes)))
+            check(hp.lib.vdb_wit_ann_query_dev(hp.metric, P, L, hp.d_vec.ptr, hp.p_cent, index.members_ptr(hp.cluster), hp.p_roots, lc, lm, K, n_c, DIM,
+                                               d["stream"].ptr, d["lookup"].ptr, None, d["ind_c"].ptr, d["ind_m"].ptr, d["pub"].ptr))
+            api.sync()
+            for key, rows in sizes.items():
+                assert np.array_equal(d[key].download((rows, 4)), want[key]), (key, lc is None)
+        got = api.wit_ann_query("euclidean", query, cent, members, roots, P, L, selectors=True)
+        assert np.array_equal(got["stream"], want["stream"]) and np.array_equal(got["lookup"], want["lookup"])
+        h = dict(stream=np.zeros((hp.n_cells, 4), dtype=np.uint64), lookup=np.zeros((hp.n_lookup, 4), dtype=np.uint64), flags=np.zeros(hp.n_cells, dtype=np.uint8),
+                 centroid_indicator=np.zeros((K, 4), dtype=np.uint64), member_indicator=np.zeros((n_c, 4), dtype=np.uint64),
+                 public=np.zeros((DIM + 1, 4), dtype=np.uint64))
+        check(hp.lib.vdb_wit_ann_query(hp.metric, P, L, api._p(query), api._p(cent), api._p(members), api._p(roots), K, n_c, DIM, *[api._p(a) for a in h.values()]))
+        for key, a in h.items():
+            assert np.array_equal(a, got[key]), key
+    finally:
+        for b in bufs:
+            b.free()
+        hp.free()
+        index.free()
+
+
 @pytest.mark.parametrize("name", ["1-1", "5"])
 def test_single_cell_alteration_sweep(api, O, name):
     """tests/alteration_model.py's method on this circuit at its two smallest shapes, by the device sweep of tests/test_gpu_alteration.py: the

@@ -22,7 +22,8 @@ the centroids and over the winning cluster, both commitments, the selected clust
 public), and has the verifier check the proof.  The circuit's size follows the cluster searched, not n.
 With `--probes p` and / or `--topk t` above 1 it proves the t nearest vectors over the p nearest clusters in one proof instead
 (pipeline.AnnProbeQueryHotPath: top-k with p rounds over the centroids, with t rounds over the probed clusters' members, one commitment
-and one tied root selection per probed cluster, [t results nearest first | index_root] public); the defaults, 1 and 1, keep the path above.
+and one tied root selection per probed cluster, [t results nearest first | index_root] public); the defaults, 1 and 1, are the circuit
+above — AnnQueryHotPath is AnnProbeQueryHotPath at these.
 `--circuit ann-update --K C --updates M [--grow G]` proves M writes into one cluster of that index against its root
 (pipeline.AnnUpdateHotPath: the first write replaces member 0 of the largest cluster, the others append to it; [index_root_old | c | idx, old
 leaf, new leaf per write | index_root_new] public; `--grow` defaults to the smallest number of doublings that fits the appends), has the
@@ -56,7 +57,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from halo2_vectordb_amd import api  # noqa: E402
-from halo2_vectordb_amd.pipeline import AnnAuditHotPath, AnnCoverHotPath, AnnDeleteHotPath, AnnMeanHotPath, AnnRecentreHotPath, AnnIndex, AnnProbeQueryHotPath, AnnQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
+from halo2_vectordb_amd.pipeline import AnnAuditHotPath, AnnCoverHotPath, AnnDeleteHotPath, AnnMeanHotPath, AnnRecentreHotPath, AnnIndex, AnnProbeQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
 from halo2_vectordb_amd.rounds import ProverRounds, quotient_identity_holds  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -138,10 +139,8 @@ elif args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit", "ann-mean"
         hp = AnnRecentreHotPath(index, c, k=args.k, L=args.lookup_bits)
     elif args.circuit == "ann-cover":
         hp = AnnCoverHotPath(index, k=args.k)
-    elif multi_probe:
-        hp = AnnProbeQueryHotPath(index, query, probes=args.probes, topk=args.topk, k=args.k, L=args.lookup_bits, metric=args.metric)
     elif args.circuit == "ann":
-        hp = AnnQueryHotPath(index, query, k=args.k, L=args.lookup_bits, metric=args.metric)
+        hp = AnnProbeQueryHotPath(index, query, probes=args.probes, topk=args.topk, k=args.k, L=args.lookup_bits, metric=args.metric)
     elif args.circuit == "ann-delete":
         c = int(np.argmax(index.sizes))
         if not 1 <= args.deletes < int(index.sizes[c]):
@@ -215,7 +214,7 @@ what = f"merkle_commitment {args.n}x{args.dim} k={args.k}" if args.circuit == "m
     f"{args.updates} Merkle path updates ({args.deletes} deletes, tree grown {args.grow} times) against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "update" else \
     f"{args.reads} Merkle openings ({'leaves' if args.leaf_only else 'vectors'} public) against the root of {args.n}x{args.dim}, k={args.k}" if args.circuit == "read" else \
     f"ann query (K={args.K}, the {args.topk} nearest of the {hp.n} vectors of clusters {hp.clusters}, {args.metric}) against the index of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if multi_probe else \
-    f"ann query (K={args.K}, cluster {hp.cluster} of {hp.n} vectors, {args.metric}) against the index of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann" else \
+    f"ann query (K={args.K}, cluster {hp.clusters[0]} of {hp.n} vectors, {args.metric}) against the index of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann" else \
     f"{args.updates} writes into cluster {hp.cluster} ({hp.n} members, tree grown {hp.grow} times) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-update" else \
     f"routing audit of cluster {hp.cluster} ({hp.n} members, {args.metric}) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann-audit" else \
     f"recentre of cluster {hp.cluster} ({hp.n} members) from the old index root to the new (K={args.K}) of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann-recentre" else \
