@@ -250,7 +250,8 @@ def test_merkle_update(O):
 def test_a_dropped_tie_is_found_and_named(O, monkeypatch):
     """is_zero without the copy of its operand into the second gate [0, a', z, 0]: wherever a != 0, z = 0 and a' is bound by nothing —
     the honest witness still passes, and the sweep names such cells instead of passing.  (The copy of z into that gate, dropped alone,
-    is beyond a sweep of single cells: z' then sits beside a = 0 or is held by the cells that copy it.)"""
+    is beyond a sweep of single cells: z' then sits beside a = 0 or is held by the cells that copy it.  The splice sweep finds it:
+    tests/test_splice_cpu.py::test_a_dropped_copy_of_z_is_found_and_named.)"""
     def g_is_zero(self, a):
         z = self.push(None, True)
         self.push(a); self.push(None); self.push(CS.C(1))
