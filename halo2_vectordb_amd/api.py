@@ -803,6 +803,70 @@ def ann_index_remove(index, cluster, updated_levels, slots):
             b.free()
 
 
+def wit_ann_move(levels_src, levels_dst, roots, src, dst, n_a, n_b, slots, grow=None, selectors=False):
+    """m moves from cluster `src` to cluster `dst` of a committed index (vdb_wit_ann_move), the streams alone: levels_src a's tree over
+    its n_a members, levels_dst b's tree over its n_b members AFTER merkle_tree_grow when grow > 0 (grow None: the smallest number that
+    fits, which the shape of levels_dst must match), `roots` (K + 1, 4): [centroids' root | cluster roots], slots (m,): slot j of a is
+    below a's fill at its turn (n_a - j).  dict(stream, selectors, flags, input_cells, delete_base, shrink_base, append_base, shrink, grow,
+    public (6 m + 4, 4): [index_root_old | a | b | slot, leaf, last, moved leaf, dest, dest old leaf per move | index_root_new],
+    levels_src, levels_dst: the two trees after the batch, a's at its old size)"""
+    lib = _lib.init()
+    roots = _fr(roots)
+    idx = np.ascontiguousarray(slots, dtype=np.uint64)
+    m, K = idx.shape[0], roots.shape[0] - 1
+    cells, n_in, db, sb, ab, s, g = _u64(), _u64(), _u64(), _u64(), _u64(), ctypes.c_uint(), ctypes.c_uint()
+    check(lib.vdb_wit_ann_move_size(_sz(K), _sz(n_a), _sz(n_b), _sz(m), ctypes.byref(cells), ctypes.byref(n_in), ctypes.byref(db), ctypes.byref(sb),
+                                    ctypes.byref(ab), ctypes.byref(s), ctypes.byref(g)))
+    grow = g.value if grow is None else int(grow)
+    la, lb = np.array(levels_src, dtype=np.uint64, copy=True), np.array(levels_dst, dtype=np.uint64, copy=True)
+    assert idx.shape == (m,) and la.shape == (2 * merkle_levels(n_a)[0], 4) and lb.shape == (2 * (merkle_levels(n_b)[0] << grow), 4)
+    stream, pub = np.zeros((cells.value, 4), dtype=np.uint64), np.zeros((6 * m + 4, 4), dtype=np.uint64)
+    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
+    check(lib.vdb_wit_ann_move(_p(la), _p(lb), _p(roots), _sz(K), _sz(src), _sz(dst), _sz(n_a), _sz(n_b), grow, _p(idx), _sz(m), _p(stream),
+                               _p(sel) if selectors else None, _p(pub)))
+    return dict(stream=stream, **_split_flags(sel), input_cells=n_in.value, delete_base=db.value, shrink_base=sb.value, append_base=ab.value,
+                shrink=s.value, grow=g.value, public=pub, levels_src=la, levels_dst=lb)
+
+
+def ann_index_move_layout(sizes, src, dst, slots):
+    """(halvings of a's tree, doublings of b's, digests of the forest after the batch, its K + 2 segment offsets) of
+    vdb_ann_index_move_dev (vdb_ann_index_move_size; VdbError on src == dst, a slot at or above a's fill at its turn, or a batch that
+    would empty a)"""
+    lib = _lib.init()
+    sizes, idx = np.ascontiguousarray(sizes, dtype=np.uint64), np.ascontiguousarray(slots, dtype=np.uint64)
+    K = sizes.shape[0]
+    s, g, digests, seg = ctypes.c_uint(), ctypes.c_uint(), _u64(), np.zeros(K + 2, dtype=np.uint64)
+    check(lib.vdb_ann_index_move_size(_p(sizes), _sz(K), _sz(src), _sz(dst), _p(idx), _sz(idx.shape[0]), ctypes.byref(s), ctypes.byref(g),
+                                      ctypes.byref(digests), _p(seg)))
+    return s.value, g.value, digests.value, seg
+
+
+def ann_index_move(index, src, dst, updated_src, updated_dst, slots, grow=None):
+    """the index after a batch of moves from cluster src to cluster dst (vdb_ann_index_move_dev), host arrays in and out: `index` an
+    ann_index_build dict, updated_src / updated_dst the two trees the witness call left -> a dict of the same form over the SAME
+    database: the slots entries travel with their rows"""
+    lib = _lib.init()
+    ua, ub = _fr(updated_src), _fr(updated_dst)
+    idx = np.ascontiguousarray(slots, dtype=np.uint64)
+    sizes = np.diff(np.asarray(index["offsets"], dtype=np.uint64)).astype(np.uint64)
+    K, dim, n, m = sizes.shape[0], index["grouped"].shape[1], index["grouped"].shape[0], idx.shape[0]
+    _, g, digests, seg = ann_index_move_layout(sizes, src, dst, idx)
+    grow = g if grow is None else int(grow)
+    src_arrays = [index["grouped"], np.ascontiguousarray(index["slots"], dtype=np.uint32), index["forest"], index["roots"], ua, ub]
+    ins = [DeviceBuffer(max(a.nbytes, 32)) for a in src_arrays]
+    outs = [DeviceBuffer(max(b, 32)) for b in (n * dim * 32, n * 4, (K + 1) * 8, digests * 32, (K + 2) * 32)]
+    try:
+        for b, a in zip(ins, src_arrays):
+            b.upload(np.ascontiguousarray(a))
+        check(lib.vdb_ann_index_move_dev(ins[0].ptr, ins[1].ptr, ins[2].ptr, ins[3].ptr, _p(sizes), _sz(K), _sz(dim), _sz(src), _sz(dst), grow, ins[4].ptr,
+                                         ins[5].ptr, _p(idx), _sz(m), *[o.ptr for o in outs]))
+        return dict(grouped=outs[0].download((n, dim, 4)), slots=outs[1].download((n,), dtype=np.uint32), offsets=outs[2].download((K + 1,), dtype=np.uint64),
+                    forest=outs[3].download((digests, 4)), segments=seg, roots=outs[4].download((K + 2, 4)))
+    finally:
+        for b in ins + outs:
+            b.free()
+
+
 def wit_merkle_open(levels, n, indices, vectors=None, selectors=False):
     """m openings (vdb_wit_merkle_open) of the tree `levels` (merkle_tree_build's array over n vectors, or what a batch of updates left):
     slot indices[j] is read.  `vectors` (m, dim, 4): the vectors read (vector mode); None: leaf mode, any slot of the padded tree.

@@ -1654,6 +1654,217 @@ def build_ann_delete(K, m, dim, depth, fetch_flags, fetch_values, builder=None, 
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# Moves from one cluster to another against the index root (include/vdb.h vdb_wit_ann_move; pipeline.AnnMoveHotPath)
+def ann_move_shape(n_a, n_b, m):
+    """(d_a, s, d_b, g): the depth of a's tree and its halvings after m members left (ann_delete_shrink), the depth of b's GROWN tree
+    and the doublings after which it holds n_b + m members"""
+    d_a, s = ann_delete_shrink(n_a, m)
+    if n_b < 1:
+        raise ValueError("an empty destination cluster")
+    d_b = (n_b + m - 1).bit_length()
+    return d_a, s, d_b, d_b - (n_b - 1).bit_length()
+
+
+def ann_move_layout(K, m, depth_a, shrink, depth_b, grow):
+    """where the blocks of the index move circuit start: a, b, centroids_root, roots (the assigned header A, n_in = K + 3 cells);
+    indicator, select, sponge_old (B_a, C_a, D); update (E' on a's tree, update_layout: merkle_update_layout over [carried, delete] * m);
+    shrink (block S, shrink_cells, s); mid (F_a); indicator_b, select_b (B_b, C_b); update_b (E_b on b's grown tree, update_b_layout: m
+    carried appends, grow); new_roots (F_b); sponge_new (G); total.  No vector enters the circuit: the update layouts are taken at dim 1,
+    which no cell of theirs depends on."""
+    if K < 2:
+        raise ValueError("a move needs two clusters")
+    if m < 1 or not 0 <= shrink <= depth_a:
+        raise ValueError("at least one move, and no more halvings than the tree has levels")
+    upd_a = merkle_update_layout(2 * m, 1, depth_a, [2, 1] * m, 0, carried=True)
+    upd_b = merkle_update_layout(m, 1, depth_b, [2] * m, grow, carried=True)
+    sp = merkle_leaf_layout(K + 1)
+    ind_cells, sel_cells = 8 + 12 * (K - 1), 1 + 3 * K
+    lay = dict(K=K, a=0, b=1, c=0, centroids_root=2, roots=3, n_in=K + 3, sponge=sp, update_layout=upd_a, update_b_layout=upd_b, s=shrink, g=grow)
+    lay["indicator"] = K + 3
+    lay["select"] = lay["indicator"] + ind_cells
+    lay["sponge_old"] = lay["select"] + sel_cells
+    lay["update"] = lay["sponge_old"] + sp["leaf_cells"]
+    lay["shrink"] = lay["update"] + upd_a["total"]
+    lay["shrink_cells"] = 2 + (depth_a - 1 + shrink) * upd_a["node_cells"] if shrink else 0
+    lay["mid"] = lay["shrink"] + lay["shrink_cells"]
+    lay["indicator_b"] = lay["mid"] + 8 * K
+    lay["select_b"] = lay["indicator_b"] + ind_cells
+    lay["update_b"] = lay["select_b"] + sel_cells
+    lay["new_roots"] = lay["update_b"] + upd_b["total"]
+    lay["sponge_new"] = lay["new_roots"] + 8 * K
+    lay["total"] = lay["sponge_new"] + sp["leaf_cells"]
+    return lay
+
+
+def ann_move_instances(index_root_old, a, b, public_a, public_b, index_root_new):
+    """the public cells in make_public order: [index_root_old | a | b | slot, leaf, last, moved leaf, dest, dest old leaf per move |
+    index_root_new] from the two update blocks' [old root | idx, old leaf, new leaf per path update | new root]: move j is updates 2 j
+    and 2 j + 1 of a's block and update j of b's"""
+    ua, ub, out = public_a, public_b, [int(index_root_old), int(a), int(b)]
+    for j in range((len(ub) - 2) // 3):
+        out += [int(ua[1 + 6 * j]), int(ua[2 + 6 * j]), int(ua[4 + 6 * j]), int(ua[3 + 6 * j]), int(ub[1 + 3 * j]), int(ub[2 + 3 * j])]
+    return out + [int(index_root_new)]
+
+
+def _move_info(lay, m, upa, upb):
+    """what both forms report about E', S and E_b: carried / moved_old (the delete's own move copy inside a), removed (the assigned
+    old-leaf cell of E''s update 2 j: the removed leaf), arrived (the carried-leaf cell of E_b's update j, tied to it), z0, and each
+    block's own roots"""
+    u, base, ub, base_b = lay["update_layout"], lay["update"], lay["update_b_layout"], lay["update_b"]
+    return dict(carried=[base + u["block"][2 * j] for j in range(m)], moved_old=[base + u["old_leaf"] + 2 * j + 1 for j in range(m)],
+                removed=[base + u["old_leaf"] + 2 * j for j in range(m)], arrived=[base_b + ub["block"][j] for j in range(m)],
+                z0=lay["shrink"] + 1 if lay["s"] else None, old_root=upa[0], new_root=upa[-1], old_root_b=upb[0], new_root_b=upb[-1])
+
+
+def _indicator_b_lay(lay):
+    """the keys _trace_ann_head / _build_ann_head's indicator and select read, for blocks B_b and C_b"""
+    return dict(lay, c=lay["b"], indicator=lay["indicator_b"], select=lay["select_b"])
+
+
+def _trace_indicators(t, lay, roots):
+    """idx_to_indicator(lay.c, K) as select_from_idx unrolls it and select_by_indicator(roots, indicators) on a _CellTrace
+    -> (inds, picked)"""
+    c = lay["c"]
+    inds = [t.is_zero(lay["indicator"], c)]
+    for j in range(1, len(roots)):
+        at = _indicator_at(lay, j)
+        t.put(at, [None, ("k", j), ("k", 1), ("c", c)], [1, 0, 0, 0])      # is_equal(c, Constant(j)) = sub [d, j, 1, c] + is_zero(d)
+        inds.append(t.is_zero(at + 4, at))
+    cells, gates = [("k", 0)], [1]
+    for j in range(len(roots)):
+        cells += [("c", roots[j]), ("c", inds[j]), None]
+        gates += [0, 0, j + 1 < len(roots)]
+    return inds, t.put(lay["select"], cells, gates) - 1
+
+
+def trace_ann_move(K, m, depth_a, shrink, depth_b, grow, fetch_flags, fetch_values):
+    """The closure of m moves from cluster a to cluster b of a committed index cell by cell (the ground truth of build_ann_move): the
+    header, B_a, C_a, D, the delete's blocks E' and S on a's tree, F_a mid_j = select(a's new root, cluster_root_j, ind_a_j), B_b, C_b
+    over mid, E_b m carried appends on b's grown tree, F_b out_j = select(b's new root, mid_j, ind_b_j), G.  Ties: picked_a to E''s old
+    root, picked_b to E_b's, the carried leaf of E_b's update j to the removed leaf of E''s update 2 j.
+    -> (CopyMap, public cells, dict(indicators, indicators_b, picked, picked_b, mids, outs, index_root_old, index_root_new, s0,
+    shrink_top, layout and _move_info's keys))"""
+    lay = ann_move_layout(K, m, depth_a, shrink, depth_b, grow)
+    t = _CellTrace(lay["total"], fetch_flags, fetch_values)
+    roots = [lay["roots"] + j for j in range(K)]
+    inds, picked = _trace_indicators(t, lay, roots)
+    root_old, at = t.leaf(lay["sponge_old"], lay["sponge"], None, [lay["centroids_root"]] + roots)
+    assert at == lay["update"]
+    upa = _trace_update_block(t, lay["update_layout"], lay["update"])
+    t.copy_of[upa[0]] = picked                               # ctx.constrain_equal(picked_a, E''s old root)
+    info = _move_info(lay, m, upa, [None, None])
+    for x, y in zip(info["carried"], info["moved_old"]):
+        t.copy_of[x] = y                                     # the delete's move: what left the last slot is what arrived in slot_j
+    s0, top, new_root = None, None, upa[-1]
+    if shrink:
+        s0 = top = lay["shrink"]                             # S_0 = ctx.load_witness, Z_0 = ctx.load_constant(0)
+        at = t.put(s0 + 1, [("k", 0)], [0])
+        z = [s0 + 1]
+        for l in range(depth_a - 1):
+            z.append(t.node(at, z[l], z[l]))
+            at += lay["update_layout"]["node_cells"]
+        for i in range(shrink):
+            top = t.node(at, top, z[depth_a - shrink + i])
+            at += lay["update_layout"]["node_cells"]
+        assert at == lay["mid"]
+        t.copy_of[top] = upa[-1]                             # ctx.constrain_equal(S_s, E''s final root)
+        new_root = s0
+    mids = [t.select(lay["mid"] + 8 * j, new_root, roots[j], inds[j]) for j in range(K)]
+    inds_b, picked_b = _trace_indicators(t, _indicator_b_lay(lay), mids)
+    upb = _trace_update_block(t, lay["update_b_layout"], lay["update_b"])
+    t.copy_of[upb[0]] = picked_b                             # ctx.constrain_equal(picked_b, E_b's old root)
+    info = _move_info(lay, m, upa, upb)
+    for x, y in zip(info["arrived"], info["removed"]):
+        t.copy_of[x] = y                                     # THE MOVE: what arrived in b is what left a
+    outs = [t.select(lay["new_roots"] + 8 * j, upb[-1], mids[j], inds_b[j]) for j in range(K)]
+    root_new, at = t.leaf(lay["sponge_new"], lay["sponge"], None, [lay["centroids_root"]] + outs)
+    assert at == lay["total"]
+    info = dict(info, indicators=inds, indicators_b=inds_b, picked=picked, picked_b=picked_b, mids=mids, outs=outs, index_root_old=root_old,
+                index_root_new=root_new, s0=s0, shrink_top=top, layout=lay)
+    return t.finish(), ann_move_instances(root_old, lay["a"], lay["b"], upa, upb, root_new), info
+
+
+def _build_indicators(B, lay, roots):
+    """_trace_indicators from unit blocks on builder B (the blocks _build_ann_head places) -> (inds, picked)"""
+    K, c = len(roots), lay["c"]
+    s = Sym(0, 0)
+    iz = Block(s, [s.g_is_zero(ext(0))])
+    inds = [int(B.place(iz, [lay["indicator"]], [0], [[c]])[0, 0])]
+    if K > 1:
+        s = Sym(0, 0)
+        d = s.push(None, True)                               # is_equal(c, Constant(j)) = sub [d, j, 1, c] + is_zero(d)
+        s.push(None); s.push(C(1)); s.push(ext(0))
+        ie = Block(s, [s.g_is_zero(d)])
+        at = np.asarray([_indicator_at(lay, j) for j in range(1, K)], dtype=np.int64)
+        inds += [int(x) for x in B.place(ie, at, np.zeros(K - 1, dtype=np.int64), np.full((K - 1, 1), c, dtype=np.int64))[:, 0]]
+        for j in range(1, K):
+            B.constant_cell(int(at[j - 1]) + 1, j)
+    inds = np.asarray(inds, dtype=np.int64)
+    s = Sym(0, 0)
+    sb = Block(s, [s.g_select_by_indicator([ext(i) for i in range(K)], [ext(K + i) for i in range(K)])])
+    return inds, int(B.place(sb, [lay["select"]], [0], np.concatenate([np.asarray(roots, dtype=np.int64), inds])[None, :])[0, 0])
+
+
+def _build_selects(B, at, new_root, olds, inds):
+    """out_j = select(new_root, olds_j, inds_j) at at + 8 j, placed at once -> the out cells"""
+    K = len(inds)
+    s = Sym(0, 0)
+    sl = Block(s, [s.g_select(ext(0), ext(1), ext(2))])
+    return B.place(sl, at + 8 * np.arange(K, dtype=np.int64), np.zeros(K, dtype=np.int64),
+                   np.stack([np.full(K, new_root, dtype=np.int64), np.asarray(olds, dtype=np.int64), np.asarray(inds, dtype=np.int64)], axis=1))[:, 0]
+
+
+def build_ann_move(K, m, depth_a, shrink, depth_b, grow, fetch_flags, fetch_values, builder=None):
+    """trace_ann_move's map assembled from unit blocks, as build_ann_delete: the two update blocks are place_merkle_update at their bases
+    with the carried kind, block S's hashes are placed one after the other (`builder`: as build_kmeans).  -> as trace_ann_move"""
+    lay = ann_move_layout(K, m, depth_a, shrink, depth_b, grow)
+    if np.asarray(fetch_flags(0, lay["n_in"])).any():
+        raise ValueError("the assigned header carries no gate or constant flag")
+    B = (builder or _Builder)(lay["total"], 0)
+    roots = lay["roots"] + np.arange(K, dtype=np.int64)
+    inds, picked = _build_indicators(B, lay, roots)
+    root_old, end = place_sponge(B, lay["sponge_old"], [lay["centroids_root"]] + [int(r) for r in roots], fetch_flags, fetch_values)
+    assert end == lay["update"]
+    upa = place_merkle_update(B, 2 * m, 1, depth_a, fetch_flags, fetch_values, lay["update"], [2, 1] * m, 0, carried=True)
+    B.tie(upa[0], picked)                                    # ctx.constrain_equal(picked_a, E''s old root)
+    info = _move_info(lay, m, upa, [None, None])
+    for x, y in zip(info["carried"], info["moved_old"]):
+        B.tie(x, y)                                          # the delete's move
+    s0, top, new_root = None, None, upa[-1]
+    if shrink:
+        one = lambda x: np.asarray([x], dtype=np.int64)
+        perm = _perm_placer(B, fetch_flags, fetch_values)
+        s0 = lay["shrink"]
+        B.constant_cell(s0 + 1, 0)                           # Z_0 = ctx.load_constant(0)
+        z, top, at = [one(s0 + 1)], one(s0), s0 + 2
+        for l in range(depth_a - 1):
+            z.append(_node(perm, one(at), z[l], z[l]))
+            at += lay["update_layout"]["node_cells"]
+        for i in range(shrink):
+            top = _node(perm, one(at), top, z[depth_a - shrink + i])
+            at += lay["update_layout"]["node_cells"]
+        assert at == lay["mid"]
+        top = int(top[0])
+        B.tie(top, upa[-1])                                  # ctx.constrain_equal(S_s, E''s final root)
+        new_root = s0
+    mids = _build_selects(B, lay["mid"], new_root, roots, inds)
+    inds_b, picked_b = _build_indicators(B, _indicator_b_lay(lay), mids)
+    upb = place_merkle_update(B, m, 1, depth_b, fetch_flags, fetch_values, lay["update_b"], [2] * m, grow, carried=True)
+    B.tie(int(upb[0]), picked_b)                             # ctx.constrain_equal(picked_b, E_b's old root)
+    info = _move_info(lay, m, upa, upb)
+    for x, y in zip(info["arrived"], info["removed"]):
+        B.tie(x, y)                                          # THE MOVE: what arrived in b is what left a
+    outs = _build_selects(B, lay["new_roots"], upb[-1], mids, inds_b)
+    root_new, end = place_sponge(B, lay["sponge_new"], [lay["centroids_root"]] + [int(o) for o in outs], fetch_flags, fetch_values)
+    if end != lay["total"]:
+        raise ValueError("the trace does not end where the circuit does")
+    info = dict(info, indicators=[int(i) for i in inds], indicators_b=[int(i) for i in inds_b], picked=picked, picked_b=picked_b,
+                mids=[int(x) for x in mids], outs=[int(o) for o in outs], index_root_old=root_old, index_root_new=root_new, s0=s0, shrink_top=top,
+                layout=lay)
+    return B.finish(), ann_move_instances(root_old, lay["a"], lay["b"], upa, upb, root_new), info
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # The cluster frame of the routing audit and the mean audit below, one circuit around a block of their own: A - D the frame's head, I
 # [centroids | members] assigned, the own block, MC and MM the two merkle_commitments; public [index_root | c]
 def _ann_cluster_layout(K, n_c, dim):

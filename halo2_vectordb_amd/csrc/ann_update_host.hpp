@@ -232,6 +232,7 @@ struct AnndPlan {
   std::vector<uint8_t> kinds;         // 2 m: 2 (carried), 1 (delete), alternating
   std::vector<uint32_t> carry_src;    // 2 m: for update 2 j the slot whose leaf, as the tree stood before the batch, it carries
   std::vector<uint64_t> move_pos, move_src;   // the surviving positions p < n_c - m whose member is not the original one: p, origin[p]
+  std::vector<uint64_t> removed_src;  // m: the slot that held, before the batch, the member delete j removes (origin[slot_j] at its turn)
   uint64_t lp, lp_new;                // padded leaf counts before and after: lp_new = lp >> shrink is the power of two >= n_c - m
   uint32_t depth, shrink;
 };
@@ -247,6 +248,7 @@ static inline int annd_expand(const uint64_t* slots, size_t m, uint64_t n_c, siz
   p->indices.assign(2 * m, 0);
   p->kinds.assign(2 * m, 1);
   p->carry_src.assign(2 * m, 0);
+  p->removed_src.assign(m, 0);
   std::vector<uint64_t> w_pos, w_src;   // the writes so far, in order: position, origin
   auto origin = [&](uint64_t pos) {
     for (size_t i = w_pos.size(); i-- > 0;)
@@ -260,6 +262,7 @@ static inline int annd_expand(const uint64_t* slots, size_t m, uint64_t n_c, siz
       return 3;
     }
     const uint64_t src = origin(last);
+    p->removed_src[j] = origin(slots[j]);
     p->indices[2 * j] = slots[j];
     p->kinds[2 * j] = 2;
     p->carry_src[2 * j] = (uint32_t)src;
@@ -310,6 +313,96 @@ static inline int annd_remove_plan(const uint64_t* sizes, size_t K, size_t c, ui
   }
   p->n_new = p->offsets[K];
   p->delta = 2 * (lp - lp_new);
+  return 0;
+}
+
+// ------------------------------------------------------------------ moves (include/vdb.h vdb_wit_ann_move, vdb_ann_index_move_dev)
+// m members pass from cluster a to cluster b: move j is delete j of a (annd_expand: two path updates of a's tree, a's tree halved s
+// times) and an append to b at dest_j = n_b + j whose new leaf is CARRIED from a: the removed leaf of delete j, the digest slot
+// removed_src[j] of a's tree held before the batch.  b's tree is doubled g times before the first append: g is the smallest that fits.
+struct AnnMovePlan {
+  AnndPlan d;                  // a's side: 2 m path updates, origin tracking, s
+  std::vector<uint64_t> dest;  // m: n_b + j
+  std::vector<uint8_t> kinds;  // m: 2 (carried), b's side
+  uint64_t lp_b, glp_b;        // b's padded leaf counts before and after the growth
+  uint32_t depth_b, grow;      // depth_b: of the grown tree
+};
+// the doublings after which the tree over n_b members holds n_b + m
+static inline unsigned annmv_grow(uint64_t n_b, uint64_t m) {
+  uint64_t lp, glp;
+  uint32_t d, gd;
+  tree_shape(n_b, &lp, &d);
+  tree_shape(n_b + m, &glp, &gd);
+  return gd - d;
+}
+// -> 0; 1 .. 3: annd_expand's; 4: n_b == 0; 5: `grow` (< 0: not given) is not the smallest that fits
+static inline int annmv_expand(const uint64_t* slots, size_t m, uint64_t n_a, uint64_t n_b, int grow, size_t max_updates, AnnMovePlan* p, size_t* bad) {
+  const int rc = annd_expand(slots, m, n_a, max_updates, &p->d, bad);
+  if (rc) return rc;
+  if (n_b == 0) return 4;
+  uint32_t d;
+  tree_shape(n_b, &p->lp_b, &d);
+  tree_shape(n_b + m, &p->glp_b, &p->depth_b);
+  p->grow = p->depth_b - d;
+  if (grow >= 0 && (unsigned)grow != p->grow) return 5;
+  p->dest.resize(m);
+  for (size_t j = 0; j < m; j++) p->dest[j] = n_b + j;
+  p->kinds.assign(m, 2);
+  return 0;
+}
+// block offsets of the move circuit: A [a | b | centroids_root | cluster roots] (K + 3 cells), B_a, C_a, D, E' (b_upd_a), S (b_shr),
+// F_a (b_mid), B_b (b_ind_b), C_b (b_sel_b), E_b (b_upd_b), F_b (b_new), G (b_root)
+struct AnnMoveBlocks {
+  uint64_t n_in, b_ind_a, b_sel_a, b_old, b_upd_a, b_shr, b_mid, b_ind_b, b_sel_b, b_upd_b, b_new, b_root, total;
+};
+static inline AnnMoveBlocks annmv_blocks(uint64_t K, uint64_t sponge_cells, uint64_t update_a_cells, uint64_t shrink_cells, uint64_t update_b_cells) {
+  AnnMoveBlocks o;
+  const uint64_t ind_cells = 8 + 12 * (K - 1), sel_cells = 1 + 3 * K;
+  o.n_in = K + 3;
+  o.b_ind_a = o.n_in;
+  o.b_sel_a = o.b_ind_a + ind_cells;
+  o.b_old = o.b_sel_a + sel_cells;
+  o.b_upd_a = o.b_old + sponge_cells;
+  o.b_shr = o.b_upd_a + update_a_cells;
+  o.b_mid = o.b_shr + shrink_cells;
+  o.b_ind_b = o.b_mid + 8 * K;
+  o.b_sel_b = o.b_ind_b + ind_cells;
+  o.b_upd_b = o.b_sel_b + sel_cells;
+  o.b_new = o.b_upd_b + update_b_cells;
+  o.b_root = o.b_new + 8 * K;
+  o.total = o.b_root + sponge_cells;
+  return o;
+}
+// The index after the batch.  Rows: cluster a's surviving position p holds its original member origin_a[p] (annd_expand's move table),
+// the moved rows follow b's old rows in move order, every other row keeps its place in its cluster; a lane finds its cluster in the new
+// offsets and its source through the old ones, so the rows between a and b shift by m whichever of the two comes first.  Forest: segment
+// a is its updated tree cut to lp_a >> s, segment b its grown, updated tree, the others are copied from where the old forest holds them.
+struct AnnMoveIndexPlan {
+  std::vector<uint64_t> offsets, seg_off;          // new: K + 1 rows, K + 2 digests
+  std::vector<uint64_t> offsets_old, seg_off_old;  // old, the same shapes
+  uint64_t n;
+};
+// -> 0; 1: an empty cluster
+static inline int annmv_index_plan(const uint64_t* sizes, size_t K, size_t a, size_t b, uint64_t m, uint64_t lp_a_new, uint64_t glp_b, AnnMoveIndexPlan* p) {
+  p->offsets.assign(K + 1, 0);
+  p->seg_off.assign(K + 2, 0);
+  p->offsets_old.assign(K + 1, 0);
+  p->seg_off_old.assign(K + 2, 0);
+  for (size_t s = 0; s <= K; s++) {
+    const uint64_t old_sz = s < K ? sizes[s] : K;
+    if (old_sz == 0) return 1;
+    uint64_t l_old, l;
+    uint32_t d;
+    tree_shape(old_sz, &l_old, &d);
+    l = s == a ? lp_a_new : s == b ? glp_b : l_old;
+    if (s < K) {
+      p->offsets_old[s + 1] = p->offsets_old[s] + old_sz;
+      p->offsets[s + 1] = p->offsets[s] + (s == a ? old_sz - m : s == b ? old_sz + m : old_sz);
+    }
+    p->seg_off_old[s + 1] = p->seg_off_old[s] + 2 * l_old;
+    p->seg_off[s + 1] = p->seg_off[s] + 2 * l;
+  }
+  p->n = p->offsets[K];
   return 0;
 }
 

@@ -597,6 +597,142 @@ int ann_index_remove_dev(const u256* grouped, const u256* forest, const u256* ro
   return VDB_OK;
 }
 
+// ------------------------------------------------------------------ the index after a batch of moves (include/vdb.h
+// vdb_ann_index_move_dev; the batch's circuit is witness.hip's).  Values only; the old buffers are only read.  The database is not
+// renumbered: every row keeps its database slot, the `slots` entries travel with their rows.
+// One lane per word of the new grouped rows, then per slot entry: the lane finds its cluster s by bisection in the new offsets and its
+// place p in it; the source row lies in the OLD offsets: cluster a's surviving position p holds its original member origin[p] (p itself
+// unless the move table says otherwise, as k_ann_rows_remove), b's position n_b + j the member move j took out of a, every other row
+// position p of its own cluster: the rows between a and b shift by m whichever of the two comes first
+__global__ __launch_bounds__(256) void k_ann_rows_move(const u256* __restrict__ grouped, const uint32_t* __restrict__ slots, const uint64_t* __restrict__ off_new,
+                                                       const uint64_t* __restrict__ off_old, const uint32_t* __restrict__ move_pos,
+                                                       const uint32_t* __restrict__ move_src, uint32_t n_move, const uint32_t* __restrict__ removed_src,
+                                                       uint32_t K, uint32_t a, uint32_t b, uint64_t n_b, uint64_t n, uint32_t D,
+                                                       u256* __restrict__ grouped_out, uint32_t* __restrict__ slots_out) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x, n_words = n * D;
+  if (t >= n_words + n) return;
+  const bool is_slot = t >= n_words;
+  const uint64_t r = is_slot ? t - n_words : t / D;
+  uint32_t lo = 0, hi = K;   // the cluster s with off_new[s] <= r < off_new[s + 1] (no cluster is empty)
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (off_new[mid] <= r) lo = mid; else hi = mid;
+  }
+  const uint64_t p = r - off_new[lo];
+  uint64_t from = off_old[lo] + p;
+  if (lo == a) {
+    for (uint32_t i = 0; i < n_move; i++)
+      if (move_pos[i] == (uint32_t)p) {
+        from = off_old[a] + move_src[i];
+        break;
+      }
+  } else if (lo == b && p >= n_b) {
+    from = off_old[a] + removed_src[p - n_b];
+  }
+  if (is_slot)
+    slots_out[r] = slots[from];
+  else
+    grouped_out[t] = grouped[from * D + t % D];
+}
+// one lane per digest of the new forest: its segment by bisection in the new segment offsets; segment a is its updated tree cut to
+// lp_new leaves (as k_ann_forest_cut), segment b its grown, updated tree, every other one comes from where the old forest holds it
+__global__ __launch_bounds__(256) void k_ann_forest_splice(const u256* __restrict__ forest, const u256* __restrict__ updated_a, const u256* __restrict__ updated_b,
+                                                           const uint64_t* __restrict__ seg_new, const uint64_t* __restrict__ seg_old, uint32_t n_seg,
+                                                           uint32_t a, uint32_t b, uint64_t lp, uint64_t lp_new, u256* __restrict__ forest_out) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= seg_new[n_seg]) return;
+  uint32_t lo = 0, hi = n_seg;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (seg_new[mid] <= t) lo = mid; else hi = mid;
+  }
+  uint64_t e = t - seg_new[lo];
+  if (lo == b) {
+    forest_out[t] = updated_b[e];
+    return;
+  }
+  if (lo != a) {
+    forest_out[t] = forest[seg_old[lo] + e];
+    return;
+  }
+  uint64_t width = lp_new;
+  uint32_t l = 0;
+  while (width && e >= width) {
+    e -= width;
+    width >>= 1;
+    l++;
+  }
+  forest_out[t] = width ? updated_a[mku_level_off(lp, l) + e] : u256_zero();
+}
+// the K + 1 words of the index root: the old ones, words 1 + a and 1 + b the two new roots
+__global__ __launch_bounds__(64) void k_ann_roots_move(const u256* __restrict__ roots, const u256* __restrict__ root_a, const u256* __restrict__ root_b, uint32_t K,
+                                                       uint32_t a, uint32_t b, u256* __restrict__ roots_out) {
+  const uint32_t s = blockIdx.x * 64 + threadIdx.x;
+  if (s > K) return;
+  roots_out[s] = s == 1 + a ? *root_a : s == 1 + b ? *root_b : roots[s];
+}
+// what the two move entry points share: the batch against the two clusters and the offsets after it (VDB_ERR_ARG, nothing launched)
+static int ann_move_plan(const uint64_t* sizes, size_t K, size_t dim, size_t a, size_t b, int grow, const uint64_t* slots, size_t m, AnnMovePlan* mp,
+                         AnnMoveIndexPlan* p) {
+  VDB_ARG(sizes && slots, "null pointer");
+  VDB_ARG(K >= 2 && K <= VDB_ANN_MAX_CLUSTERS && a < K && b < K && a != b, "K below 2, K above VDB_ANN_MAX_CLUSTERS, a cluster >= K or src == dst");
+  VDB_ARG(dim > 0 && dim <= ((size_t)1 << 20), "dim outside [1, 2^20]");
+  VDB_ARG(sizes[a] <= VDB_ANN_MAX_VECTORS && sizes[b] <= VDB_ANN_MAX_VECTORS, "cluster too large");
+  const int rc = annmv_expand(slots, m, sizes[a], sizes[b], grow, MKU_MAX_UPDATES, mp, nullptr);
+  VDB_ARG(rc != 1, "a batch holds 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES / 2 moves");
+  VDB_ARG(rc != 2, "the batch would empty the source cluster");
+  VDB_ARG(rc != 3, "a slot at or above the source cluster's fill at its turn");
+  VDB_ARG(rc != 4, "empty destination cluster");
+  VDB_ARG(rc == 0, "grow is the smallest number of doublings after which the destination's tree holds its new members");
+  VDB_ARG(annmv_index_plan(sizes, K, a, b, m, mp->d.lp_new, mp->glp_b, p) == 0, "empty cluster");
+  VDB_ARG(p->n <= VDB_ANN_MAX_VECTORS, "index too large: n at most VDB_ANN_MAX_VECTORS");
+  return VDB_OK;
+}
+int ann_index_move_dev(const u256* grouped, const uint32_t* slots_in, const u256* forest, const u256* roots, const uint64_t* sizes, size_t K, size_t dim, size_t a,
+                       size_t b, unsigned grow, const u256* updated_a, const u256* updated_b, const uint64_t* slots, size_t m, u256* grouped_out,
+                       uint32_t* slots_out, uint64_t* offsets_out, u256* forest_out, u256* roots_out) {
+  static thread_local AnnMovePlan mp;                // (pageable sources of asynchronous uploads: they outlive the call)
+  static thread_local AnnMoveIndexPlan p;
+  static thread_local std::vector<uint64_t> tab64;   // [offsets K + 1 | old offsets K + 1 | seg_off K + 2 | old seg_off K + 2]
+  static thread_local std::vector<uint32_t> tab32;   // [move_pos | move_src | removed_src m]
+  VDB_ARG(grow <= 30, "more than 30 doublings");
+  TRY(ann_move_plan(sizes, K, dim, a, b, (int)grow, slots, m, &mp, &p));
+  const PoseidonSpec* sp;
+  TRY(poseidon_spec_dev(&sp, nullptr));
+  hipStream_t s = ctx().stream;
+  MkShape mw;
+  mk_shape(1, K + 1, &mw);
+  const size_t n_move = mp.d.move_pos.size(), n64 = 4 * K + 6, n32 = 2 * n_move + m;
+  tab64.clear();
+  tab64.insert(tab64.end(), p.offsets.begin(), p.offsets.end());
+  tab64.insert(tab64.end(), p.offsets_old.begin(), p.offsets_old.end());
+  tab64.insert(tab64.end(), p.seg_off.begin(), p.seg_off.end());
+  tab64.insert(tab64.end(), p.seg_off_old.begin(), p.seg_off_old.end());
+  tab32.resize(n32);
+  for (size_t i = 0; i < n_move; i++) tab32[i] = (uint32_t)mp.d.move_pos[i], tab32[n_move + i] = (uint32_t)mp.d.move_src[i];
+  for (size_t j = 0; j < m; j++) tab32[2 * n_move + j] = (uint32_t)mp.d.removed_src[j];
+  uint8_t* w = (uint8_t*)scratch_get(7, n64 * 8 + (n32 + 16) * 4);
+  if (!w) return VDB_ERR_OOM;
+  uint64_t *d_off = (uint64_t*)w, *d_off_old = d_off + K + 1, *d_seg = d_off_old + K + 1, *d_seg_old = d_seg + K + 2;
+  uint32_t* d_move = (uint32_t*)(d_seg_old + K + 2);
+  u256* states = (u256*)scratch_get(0, ((size_t)mw.nperm * PSD_T + 8) * sizeof(u256));
+  if (!states) return VDB_ERR_OOM;
+  VDB_HIP(hipMemcpyAsync(d_off, tab64.data(), n64 * 8, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(d_move, tab32.data(), n32 * 4, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(offsets_out, p.offsets.data(), (K + 1) * 8, hipMemcpyHostToDevice, s));
+  const uint64_t lanes = p.n * dim + p.n;
+  VDB_LAUNCH(k_ann_rows_move, dim3((unsigned)((lanes + 255) / 256)), dim3(256), grouped, slots_in, d_off, d_off_old, d_move, d_move + n_move, (uint32_t)n_move,
+             d_move + 2 * n_move, (uint32_t)K, (uint32_t)a, (uint32_t)b, sizes[b], p.n, (uint32_t)dim, grouped_out, slots_out);
+  VDB_LAUNCH(k_ann_forest_splice, dim3((unsigned)((p.seg_off[K + 1] + 255) / 256)), dim3(256), forest, updated_a, updated_b, d_seg, d_seg_old, (uint32_t)(K + 1),
+             (uint32_t)a, (uint32_t)b, mp.d.lp, mp.d.lp_new, forest_out);
+  // the cut tree's root lies where level d - s of a's old layout starts; b's at the end of its grown tree
+  VDB_LAUNCH(k_ann_roots_move, dim3((unsigned)(K / 64 + 1)), dim3(64), roots, updated_a + mku_level_off(mp.d.lp, mp.d.depth - mp.d.shrink),
+             updated_b + 2 * mp.glp_b - 2, (uint32_t)K, (uint32_t)a, (uint32_t)b, roots_out);
+  TRY(mk_leaf_states(sp, roots_out, 1u, (uint32_t)(K + 1), mw.nperm, states, roots_out + K + 1, nullptr));
+  VDB_HIP(hipStreamSynchronize(s));
+  return VDB_OK;
+}
+
 }  // namespace vdb
 
 using namespace vdb;
@@ -715,6 +851,30 @@ int vdb_ann_index_remove_dev(const vdb_fr* grouped_dev, const vdb_fr* forest_dev
           "null pointer");
   return ann_index_remove_dev(as_u256(grouped_dev), as_u256(forest_dev), as_u256(roots_dev), cluster_sizes, K, dim, cluster, as_u256(updated_levels_dev),
                               slots, m, as_u256(grouped_out_dev), slots_out_dev, offsets_out_dev, as_u256(forest_out_dev), as_u256(roots_out_dev));
+}
+
+int vdb_ann_index_move_size(const uint64_t* cluster_sizes, size_t K, size_t src, size_t dst, const uint64_t* slots, size_t m, unsigned* shrink, unsigned* grow,
+                            uint64_t* digests, uint64_t* segment_offsets) {
+  AnnMovePlan mp;
+  AnnMoveIndexPlan p;
+  TRY(ann_move_plan(cluster_sizes, K, 1, src, dst, -1, slots, m, &mp, &p));
+  if (shrink) *shrink = mp.d.shrink;
+  if (grow) *grow = mp.grow;
+  if (digests) *digests = p.seg_off[K + 1];
+  if (segment_offsets) memcpy(segment_offsets, p.seg_off.data(), (K + 2) * sizeof(uint64_t));
+  return VDB_OK;
+}
+int vdb_ann_index_move_dev(const vdb_fr* grouped_dev, const uint32_t* slots_dev, const vdb_fr* forest_dev, const vdb_fr* roots_dev, const uint64_t* cluster_sizes,
+                           size_t K, size_t dim, size_t src, size_t dst, unsigned grow, const vdb_fr* updated_src_dev, const vdb_fr* updated_dst_dev,
+                           const uint64_t* slots, size_t m, vdb_fr* grouped_out_dev, uint32_t* slots_out_dev, uint64_t* offsets_out_dev, vdb_fr* forest_out_dev,
+                           vdb_fr* roots_out_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(grouped_dev && slots_dev && forest_dev && roots_dev && updated_src_dev && updated_dst_dev && grouped_out_dev && slots_out_dev && offsets_out_dev &&
+              forest_out_dev && roots_out_dev,
+          "null pointer");
+  return ann_index_move_dev(as_u256(grouped_dev), slots_dev, as_u256(forest_dev), as_u256(roots_dev), cluster_sizes, K, dim, src, dst, grow,
+                            as_u256(updated_src_dev), as_u256(updated_dst_dev), slots, m, as_u256(grouped_out_dev), slots_out_dev, offsets_out_dev,
+                            as_u256(forest_out_dev), as_u256(roots_out_dev));
 }
 
 }  // extern "C"

@@ -1831,9 +1831,11 @@ struct MkuPlan {
   std::vector<uint64_t> level_at, tab;   // (tab: the pageable source of the upload; hipMemcpyAsync stages it before returning)
   std::vector<int32_t> write_no;
 };
-// carry_src (null: no kind 2 is admitted): for an update of kind 2 the slot whose resident digest is its new leaf
+// carry_src (null: no kind 2 is admitted): for an update of kind 2 the slot whose resident digest is its new leaf; carry_n > 0: the
+// digest is entry carry_src[j] of a second array of carry_n digests, which mku_emit is given (the index move's append: a leaf of the
+// OTHER cluster's tree)
 static int mku_plan(size_t n, size_t dim, unsigned grow, const u256* new_vectors, const uint64_t* indices, const uint8_t* kinds, size_t m, MkuPlan* p,
-                    const uint32_t* carry_src = nullptr) {
+                    const uint32_t* carry_src = nullptr, uint64_t carry_n = 0) {
   VDB_ARG(m > 0 && m <= MKU_MAX_UPDATES, "a batch holds 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES updates");
   p->level_at.resize(m);
   p->write_no.resize(m);
@@ -1853,7 +1855,7 @@ static int mku_plan(size_t n, size_t dim, unsigned grow, const u256* new_vectors
     p_level_at[j] = p->level_at[j];
     p_idx[j] = (uint32_t)indices[j];
     if (p->write_no[j] == -2) {
-      VDB_ARG(carry_src[j] < p->lp, "carried leaf outside the padded tree");
+      VDB_ARG(carry_src[j] < (carry_n ? carry_n : p->lp), "carried leaf outside the padded tree");
       p->write_no[j] = -2 - (int32_t)carry_src[j];
     }
     p_write_no[j] = p->write_no[j];
@@ -1866,9 +1868,9 @@ static int mku_plan(size_t n, size_t dim, unsigned grow, const u256* new_vectors
 }
 // The cells of a planned batch from stream cell `base` on, and its 3 m + 2 public values into `pub` (the caller has published the call's
 // context: mk_begin).  `levels`: the tree at depth d + grow (merkle_tree_grow_dev's when grow > 0), left in the state after the batch;
-// new_vectors: the rows of the writes in update order
+// new_vectors: the rows of the writes in update order; carry (null: `levels`): the array a carried leaf names its digest in
 static int mku_emit(FpEntry* fp, const PoseidonSpec* sp, const MkuPlan& pl, u256* levels, size_t dim, const u256* new_vectors, const Streams& st,
-                    uint64_t base, u256* pub) {
+                    uint64_t base, u256* pub, const u256* carry = nullptr) {
   const MkuLayout& ml = pl.ml;
   const uint64_t lp = pl.lp;
   const size_t m = ml.m, w = ml.w, n_tab = pl.n_tab;
@@ -1897,7 +1899,8 @@ static int mku_emit(FpEntry* fp, const PoseidonSpec* sp, const MkuPlan& pl, u256
   VDB_HIP(hipMemcpyAsync(level_at, pl.tab.data(), n_tab, hipMemcpyHostToDevice, s));
   const uint32_t mu = (uint32_t)m, wu = (uint32_t)w;
   // grids of at least one block: the launches of a call do not depend on how many of its updates are writes
-  VDB_LAUNCH(k_mku_touchers, dim3((unsigned)((m * depth + 255) / 256)), dim3(256), didx, mu, depth, sib_from, prev_same, last, write_no, levels, path_new);
+  VDB_LAUNCH(k_mku_touchers, dim3((unsigned)((m * depth + 255) / 256)), dim3(256), didx, mu, depth, sib_from, prev_same, last, write_no,
+             carry ? carry : levels, path_new);
   TRY(mk_leaf_states(sp, new_vectors, wu, (uint32_t)dim, ml.nperm, states, path_new, write_of));
   for (uint32_t l = 0; l < depth; l++)
     VDB_LAUNCH(k_mku_level, dim3((unsigned)((2 * m + 63) / 64)), dim3(64), sp, levels, lp, didx, mu, depth, l, sib_from, prev_same, wit, path_old, path_new);
@@ -2338,6 +2341,123 @@ int wit_ann_delete_dev(u256* levels, const u256* roots, size_t K, size_t cluster
                pl.lp, levels, empty, s0);
   TRY(f.close(a.b, dp.shrink ? s0 : f.upub + n_up - 1));
   VDB_LAUNCH(k_annd_public, dim3((unsigned)((4 * m + 3 + 255) / 256)), dim3(256), f.upub, f.hdr, f.iroot, (uint32_t)m, pub);
+  return inv_list_fixup(f.st);
+}
+
+// ------------------------------------------------------------------ moves from one cluster to another (include/vdb.h vdb_wit_ann_move,
+// vdb_ann_index_move_dev).  m members pass from cluster a to cluster b in one circuit, index_root_old to index_root_new:
+// A [a | b | centroids_root | cluster roots], B_a, C_a -> picked_a, D the old sponge, E' and S the delete's blocks on a's tree, F_a
+// mid_j = select(a's new root, cluster_root_j, ind_a_j), B_b, C_b over mid -> picked_b, E_b the update block on b's grown tree: m appends
+// whose new leaf is carried from a (the removed leaf of delete j), F_b out_j = select(b's new root, mid_j, ind_b_j), G the new sponge.
+// The composition is sequential: b's root is picked from mid, the roots after the removal.
+struct AnnMoveLayout {
+  MkLayout mw;
+  AnnMoveBlocks b;
+  MkuLayout ma, mb;
+};
+// the header: lane i < K + 3 assigns cell i and keeps the value for the blocks that read it
+__global__ __launch_bounds__(256) void k_annmv_header(Streams st, uint32_t a, uint32_t b, const u256* __restrict__ roots, uint32_t K,
+                                                      u256* __restrict__ hdr) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= K + 3) return;
+  const u256 v = i >= 2 ? roots[i - 2] : Gadgets::mont_small(i ? b : a);
+  hdr[i] = v;
+  if (i < st.rlo || i >= st.rhi) return;
+  st.adv[i] = v;
+  if (st.sel) st.sel[i] = 0;
+}
+// [index_root_old | a | b | slot_j, leaf_j, last_j, moved_leaf_j, dest_j, dest_old_leaf_j per move | index_root_new] from the two update
+// blocks' public rows [old root | idx, old leaf, new leaf per path update | new root]: move j is updates 2 j and 2 j + 1 of a's, update j of b's
+__global__ __launch_bounds__(256) void k_annmv_public(const u256* __restrict__ upa, const u256* __restrict__ upb, const u256* __restrict__ hdr,
+                                                      const u256* __restrict__ iroot, uint32_t m, u256* __restrict__ pub) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 6 * m + 4) return;
+  if (i < 3 || i == 6 * m + 3) {
+    pub[i] = i == 0 ? iroot[0] : i < 3 ? hdr[i - 1] : iroot[1];
+    return;
+  }
+  const uint32_t j = (i - 3) / 6, k = (i - 3) % 6;
+  pub[i] = k < 4 ? upa[1 + 6 * (size_t)j + (k == 0 ? 0 : k == 1 ? 1 : k == 2 ? 3 : 2)] : upb[1 + 3 * (size_t)j + (k - 4)];
+}
+// the host side of a move batch, before anything is launched: the expansion to 2 m + m path updates and every refusal.  grow < 0: the
+// call computes it; slots null (the size call): the shape does not depend on them
+static int annmv_layout(size_t K, size_t a, size_t b, size_t n_a, size_t n_b, int grow, const uint64_t* slots, size_t m, AnnMoveLayout* o, AnnMovePlan* mp) {
+  VDB_ARG(K >= 2 && K <= VDB_ANN_MAX_CLUSTERS, "K below 2 (a move needs two clusters) or K above VDB_ANN_MAX_CLUSTERS");
+  VDB_ARG(a < K && b < K, "cluster >= K");
+  VDB_ARG(a != b, "a move goes to another cluster: src == dst");
+  VDB_ARG(n_a <= VDB_ANN_MAX_VECTORS && n_b <= VDB_ANN_MAX_VECTORS, "cluster larger than VDB_ANN_MAX_VECTORS");
+  VDB_ARG(m > 0 && m <= MKU_MAX_UPDATES / 2, "a batch holds 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES / 2 moves (two path updates of the source each)");
+  VDB_ARG(m < n_a, "the batch would empty the source cluster");
+  static thread_local std::vector<uint64_t> none;
+  if (!slots) {
+    none.assign(m, 0);
+    slots = none.data();
+  }
+  const int rc = annmv_expand(slots, m, n_a, n_b, grow, MKU_MAX_UPDATES, mp, nullptr);
+  VDB_ARG(rc != 3, "a slot at or above the source cluster's fill at its turn (every move lowers the fill by one)");
+  VDB_ARG(rc != 4, "empty destination cluster");
+  VDB_ARG(rc != 5, "grow is the smallest number of doublings after which the destination's tree holds its new members");
+  VDB_ARG(rc == 0, "a batch holds at least one move and leaves at least one member");
+  TRY(mku_layout(n_a, 1, 2 * m, mp->d.kinds.data(), 0, &o->ma, nullptr, nullptr, nullptr, true));
+  TRY(mku_layout(n_b, 1, m, mp->kinds.data(), mp->grow, &o->mb, nullptr, nullptr, nullptr, true));
+  mk_layout(1, K + 1, 1, &o->mw);
+  o->b = annmv_blocks(K, o->mw.total, o->ma.total, annd_shrink_cells(mp->d.depth, mp->d.shrink, NODE_CELLS), o->mb.total);
+  VDB_ARG(o->b.total <= ((uint64_t)1 << 34), "more than VDB_MERKLE_UPDATE_MAX_CELLS cells in one call");
+  return VDB_OK;
+}
+// roots: [centroids_root | the K cluster roots] of the index before the batch; levels_a: a's tree over its n_a members, left in the
+// state after the batch at its old size; levels_b: b's tree at depth d_b + g, left in the state after the batch; pub: 6 m + 4.
+// The two update blocks take the plan's work space (scratch slot 0) and its one table upload one after the other in stream order: the
+// second block's upload and kernels are queued behind the first block's last kernel, which has read the first table by then.  What the
+// second block needs of the first, the removed leaves, lies in the first block's public row in the frame's own slot.
+int wit_ann_move_dev(u256* levels_a, u256* levels_b, const u256* roots, size_t K, size_t a, size_t b, size_t n_a, size_t n_b, int grow,
+                     const uint64_t* slots, size_t m, Streams st, u256* pub) {
+  static thread_local MkuPlan pa, pb;
+  static thread_local AnnMovePlan mp;
+  static thread_local std::vector<uint32_t> carry;
+  AnnMoveLayout L;
+  VDB_ARG(slots, "null pointer");
+  TRY(annmv_layout(K, a, b, n_a, n_b, grow, slots, m, &L, &mp));
+  const size_t n_upa = 6 * m + 2, n_upb = 3 * m + 2;
+  TRY(mku_plan(n_a, 1, 0, nullptr, mp.d.indices.data(), mp.d.kinds.data(), 2 * m, &pa, mp.d.carry_src.data()));
+  carry.resize(m);
+  for (size_t j = 0; j < m; j++) carry[j] = (uint32_t)(2 + 6 * j);   // the old leaf of a's update 2 j in a's public row: the removed leaf
+  TRY(mku_plan(n_b, 1, mp.grow, nullptr, mp.dest.data(), mp.kinds.data(), m, &pb, carry.data(), n_upa));
+  const u256* empty = nullptr;
+  if (mp.d.shrink) TRY(poseidon_empty_subtrees_dev(&empty));
+  const AnnMoveBlocks& B = L.b;
+  AnnFrame f;   // its sponge and its fields; the head is laid out here: two indicator blocks, K + 3 header cells
+  f.st = st, f.mw = &L.mw, f.K = (uint32_t)K;
+  const size_t n_st = (size_t)L.mw.nperm * PSD_T;
+  f.hdr = (u256*)scratch_get(7, (K + 3 + 2 * K + 2 + 2 * (K + 1) + 2 + n_upa + n_upb + 1 + 2 * n_st + 8) * sizeof(u256));
+  if (!f.hdr) return VDB_ERR_OOM;
+  u256 *ind_a = f.hdr + K + 3, *ind_b = ind_a + K, *picked = ind_b + K, *words_mid = picked + 2, *words_new = words_mid + K + 1;
+  f.iroot = words_new + K + 1;
+  u256 *upa = f.iroot + 2, *upb = upa + n_upa, *s0 = upb + n_upb;
+  f.st_old = s0 + 1;
+  f.st_new = f.st_old + n_st;
+  TRY(inv_list_attach(f.st, B.total));
+  TRY(mk_begin(f.st, &f.fp, &f.sp));
+  const uint32_t Ku = (uint32_t)K;
+  const u256* words_old = f.hdr + 2;
+  VDB_LAUNCH(k_annmv_header, dim3((unsigned)((K + 3 + 255) / 256)), dim3(256), f.st, (uint32_t)a, (uint32_t)b, roots, Ku, f.hdr);
+  VDB_LAUNCH(k_annu_indicator, dim3((unsigned)((K + 63) / 64)), dim3(64), f.st, f.fp->dev, B.b_ind_a, (uint32_t)a, Ku, ind_a);
+  const NvMap sa{B.b_sel_a, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, Ku, 1u, 1u};
+  VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), f.st, f.fp->dev, sa, 1u, words_old + 1, ind_a, picked);
+  TRY(f.sponge(words_old, B.b_old, f.st_old, f.iroot));
+  TRY(mku_emit(f.fp, f.sp, pa, levels_a, 1, nullptr, f.st, B.b_upd_a, upa));
+  if (mp.d.shrink)
+    VDB_LAUNCH(k_annd_shrink_trace, dim3((unsigned)((2 * (mp.d.depth - 1 + mp.d.shrink) + 63) / 64)), dim3(64), f.st, f.fp->dev, f.sp, B.b_shr, mp.d.depth,
+               mp.d.shrink, pa.lp, levels_a, empty, s0);
+  VDB_LAUNCH(k_annu_new_roots, dim3((unsigned)((K + 63) / 64)), dim3(64), f.st, f.fp->dev, B.b_mid, Ku, mp.d.shrink ? s0 : upa + n_upa - 1, words_old, ind_a,
+             words_mid);
+  VDB_LAUNCH(k_annu_indicator, dim3((unsigned)((K + 63) / 64)), dim3(64), f.st, f.fp->dev, B.b_ind_b, (uint32_t)b, Ku, ind_b);
+  const NvMap sb{B.b_sel_b, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, Ku, 1u, 1u};
+  VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), f.st, f.fp->dev, sb, 1u, words_mid + 1, ind_b, picked + 1);
+  TRY(mku_emit(f.fp, f.sp, pb, levels_b, 1, nullptr, f.st, B.b_upd_b, upb, upa));
+  VDB_LAUNCH(k_annu_new_roots, dim3((unsigned)((K + 63) / 64)), dim3(64), f.st, f.fp->dev, B.b_new, Ku, upb + n_upb - 1, words_mid, ind_b, words_new);
+  TRY(f.sponge(words_new, B.b_root, f.st_new, f.iroot + 1));
+  VDB_LAUNCH(k_annmv_public, dim3((unsigned)((6 * m + 4 + 255) / 256)), dim3(256), upa, upb, f.hdr, f.iroot, (uint32_t)m, pub);
   return inv_list_fixup(f.st);
 }
 
@@ -3460,6 +3580,55 @@ int vdb_wit_ann_delete(vdb_fr* levels, const vdb_fr* roots, size_t K, size_t clu
   return ann_batch_host(levels, dp.lp, roots, K, a.b.total, 4 * m + 3, stream_out, selector_out, public_out, [&](u256* dl, const u256* dr, Streams st, u256* dpub) {
     return wit_ann_delete_dev(dl, dr, K, cluster, n_c, dim, slots, m, st, dpub);
   });
+}
+
+// moves from one cluster to another against the index root (include/vdb.h); the index after them: resident.hip
+int vdb_wit_ann_move_size(size_t K, size_t n_a, size_t n_b, size_t m, uint64_t* cells, uint64_t* input_cells, uint64_t* delete_base, uint64_t* shrink_base,
+                          uint64_t* append_base, unsigned* shrink, unsigned* grow) {
+  AnnMoveLayout L;
+  AnnMovePlan mp;
+  TRY(annmv_layout(K, 0, 1, n_a, n_b, -1, nullptr, m, &L, &mp));
+  if (cells) *cells = L.b.total;
+  if (input_cells) *input_cells = L.b.n_in;
+  if (delete_base) *delete_base = L.b.b_upd_a;
+  if (shrink_base) *shrink_base = L.b.b_shr;
+  if (append_base) *append_base = L.b.b_upd_b;
+  if (shrink) *shrink = mp.d.shrink;
+  if (grow) *grow = mp.grow;
+  return VDB_OK;
+}
+int vdb_wit_ann_move_dev(vdb_fr* levels_src_dev, vdb_fr* levels_dst_dev, const vdb_fr* roots_dev, size_t K, size_t src, size_t dst, size_t n_a, size_t n_b,
+                         unsigned grow, const uint64_t* slots, size_t m, vdb_fr* stream_dev, uint8_t* selector_dev, vdb_fr* public_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(levels_src_dev && levels_dst_dev && roots_dev && slots && stream_dev && public_dev, "null pointer");
+  VDB_ARG(grow <= 30, "more than 30 doublings");
+  DevStreams ds;
+  ds.init(stream_dev, selector_dev);
+  TRY(wit_ann_move_dev(as_u256(levels_src_dev), as_u256(levels_dst_dev), as_u256(roots_dev), K, src, dst, n_a, n_b, (int)grow, slots, m, ds.st,
+                       as_u256(public_dev)));
+  return ds.finish();
+}
+int vdb_wit_ann_move(vdb_fr* levels_src, vdb_fr* levels_dst, const vdb_fr* roots, size_t K, size_t src, size_t dst, size_t n_a, size_t n_b, unsigned grow,
+                     const uint64_t* slots, size_t m, vdb_fr* stream_out, uint8_t* selector_out, vdb_fr* public_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(levels_src && levels_dst && roots && slots && stream_out && public_out, "null pointer");
+  VDB_ARG(grow <= 30, "more than 30 doublings");
+  AnnMoveLayout L;
+  AnnMovePlan mp;
+  TRY(annmv_layout(K, src, dst, n_a, n_b, (int)grow, slots, m, &L, &mp));
+  DevBuf da, db, dr, dpub;
+  HostStreams hs;
+  const size_t n_pub = 6 * m + 4;
+  TRY(upload(da, levels_src, 2 * mp.d.lp * sizeof(u256)));
+  TRY(upload(db, levels_dst, 2 * mp.glp_b * sizeof(u256)));
+  TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
+  TRY(dpub.alloc(n_pub * sizeof(u256)));
+  TRY(hs.init(L.b.total, 0, selector_out != nullptr));
+  TRY(wit_ann_move_dev(da.as<u256>(), db.as<u256>(), dr.as<u256>(), K, src, dst, n_a, n_b, (int)grow, slots, m, hs.st, dpub.as<u256>()));
+  TRY(download(public_out, dpub.p, n_pub * sizeof(u256)));
+  TRY(download(levels_src, da.p, 2 * mp.d.lp * sizeof(u256)));
+  TRY(download(levels_dst, db.p, 2 * mp.glp_b * sizeof(u256)));
+  return hs.finish(stream_out, nullptr, selector_out, L.b.total, 0);
 }
 
 // the audit of one cluster's routing (include/vdb.h)

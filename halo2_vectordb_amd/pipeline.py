@@ -1296,6 +1296,30 @@ class AnnIndex:
             raise
         return ix
 
+    def moved(self, hp):
+        """the index after the batch of AnnMoveHotPath `hp` (its witness has run: hp.d_levels_a and hp.d_levels_b hold the two trees
+        after the batch), as a new AnnIndex on buffers of its own (vdb_ann_index_move_dev); this index stays valid.  The database is not
+        renumbered: the result's host view is the same qvec with the moved rows' cluster_ids set to b, and its database tree is this
+        index's bit for bit.  Queries, reads, updates, deletes, audits and further moves run on the result unchanged."""
+        a, b, m = hp.src, hp.dst, hp.m
+        sizes64 = np.ascontiguousarray(self.sizes, dtype=np.uint64)
+        _, g, digests, seg = api.ann_index_move_layout(sizes64, a, b, hp.slots)
+        sizes = self.sizes.copy()
+        sizes[a] -= m
+        sizes[b] += m
+        old_slots = self.d_slots.download((int(self.sizes[a]),), dtype=np.uint32, offset=int(self.offsets[a]) * 4).astype(np.int64)
+        ids = self.cluster_ids.copy()
+        ids[old_slots[np.asarray(hp.moved_from, dtype=np.int64)]] = b
+        ix = AnnIndex.from_resident(self.dim, self.K, sizes, digests, seg, self.qcent, self.qvec, ids, P=self.P, L=self.L, metric=self.metric_name)
+        try:
+            check(self.lib.vdb_ann_index_move_dev(self.d_grouped.ptr, self.d_slots.ptr, self.d_forest.ptr, self.d_roots.ptr, api._p(sizes64), self.K, self.dim,
+                                                  a, b, g, hp.d_levels_a.ptr, hp.d_levels_b.ptr, api._p(hp.slots), m, ix.d_grouped.ptr, ix.d_slots.ptr,
+                                                  ix.d_offsets.ptr, ix.d_forest.ptr, ix.d_roots.ptr))
+        except Exception:
+            ix.free()
+            raise
+        return ix
+
     def _buf(self, nbytes):
         b = api.DeviceBuffer(max(int(nbytes), 32))
         self._bufs.append(b)
@@ -1712,6 +1736,95 @@ class AnnDeleteHotPath(_AnnBatchHotPath):
 
     def _builder(self, CS):
         return CS.build_ann_delete, dict(shrink=self.shrink)
+
+
+class AnnMoveHotPath(_AnnBatchHotPath):
+    """Moves proved against the committed index root: m members pass from cluster a = `src` to cluster b = `dst` of an AnnIndex in one
+    proof (include/vdb.h vdb_wit_ann_move), index_root_old to index_root_new.  Move j is delete j of a (AnnDeleteHotPath's blocks E' and S
+    on a's tree) and an append to b at dest_j = n_b + j whose new leaf is CARRIED: one witness cell tied to the removed leaf, so no vector
+    enters the circuit and the database, its slots and its root are untouched.  b's root is selected from the roots after the removal.
+    Public: [index_root_old | a | b | slot, leaf, last, moved leaf, dest, dest old leaf per move | index_root_new]; a verifier who tracks
+    n_a and n_b checks last_j = n_a - 1 - j, dest_j = n_b + j and dest old leaf = 0.  No input rows, no lookup cells.  (K, d_a, s, d_b, g,
+    m) are circuit shape; a, b and the slots are not.  `d_levels_a` and `d_levels_b` hold the two trees after the batch (a's at its old
+    size); AnnIndex.moved(hp) gives the next index.  `origin[p]`: the slot of a that held, before the batch, the member at surviving
+    position p; `moved_from[j]`: the slot of a that held the member move j takes to b."""
+
+    def __init__(self, index, src, dst, slots, grow=None, k=15, L=8, tau=None, col_shard=(0, 1), blind_seed=None, params=None, levels_src=None,
+                 levels_dst=None):
+        """`slots`: (m,) slots of cluster src, each below its fill at its turn (n_a - j); repeats are legal.  `grow`: doublings of b's
+        tree before the first append: None, or the smallest number that fits.  `levels_src` / `levels_dst`: trees to use in place of the
+        index's segments a and b, the latter not yet grown (tests of the binding)."""
+        self.slots = np.ascontiguousarray(slots, dtype=np.uint64)
+        m = self.slots.shape[0]
+        n_a = _bind_cluster(self, index, src)
+        self.src, self.dst = self.cluster, int(dst)
+        if not 0 <= self.dst < self.K or self.dst == self.src:
+            raise ValueError("the destination is another cluster of the index")
+        n_b = int(index.sizes[self.dst])
+        if m < 1 or m >= n_a:
+            raise ValueError("a batch holds at least one move and leaves at least one member")
+        origin, self.moved_from = list(range(n_a)), []
+        for j, s in enumerate(self.slots.tolist()):
+            if s >= n_a - j:
+                raise ValueError("a slot at or above the source cluster's fill at its turn")
+            self.moved_from.append(origin[s])
+            origin[s] = origin[n_a - j - 1]
+        self.origin = origin[:n_a - m]
+        self.lp, self.depth = api.merkle_levels(n_a)
+        self.lp_b0, depth_b0 = api.merkle_levels(n_b)
+        self.lp_b, self.depth_b = api.merkle_levels(n_b + m)
+        if grow is not None and int(grow) != self.depth_b - depth_b0:
+            raise ValueError("grow is the smallest number of doublings after which the destination's tree holds its new members")
+        self.grow = self.depth_b - depth_b0
+        super().__init__(n_a, index.dim, k, index.P, L, seed=None, tau=tau, col_shard=col_shard, vectors=np.zeros((0, index.dim)), blind_seed=blind_seed,
+                         params=params)
+        self.n_b, self.m, self.n_public, self.given_levels, self.given_levels_b = n_b, m, 6 * m + 4, levels_src, levels_dst
+
+    def n_input_rows(self):
+        return 0
+
+    def _load_inputs(self):
+        super()._load_inputs()
+        self.d_levels_a = self.d_levels
+        self.d_levels_b0 = self._output(2 * self.lp_b * B)       # b's grown tree before the batch
+        self.d_levels_b = self._output(2 * self.lp_b * B)
+        given = self.index.levels(self.dst) if self.given_levels_b is None else self.given_levels_b
+        self._load_tree(self.d_levels_b if self.grow else self.d_levels_b0, self.lp_b0, given)
+        if self.grow:
+            check(self.lib.vdb_merkle_tree_grow_dev(self.d_levels_b.ptr, self.n_b, self.grow, self.d_levels_b0.ptr))
+            api.sync()
+
+    def _witness(self, sel=None):
+        check(self.lib.vdb_memcpy_d2d(self.d_levels_b.ptr, self.d_levels_b0.ptr, ctypes.c_size_t(2 * self.lp_b * B)))
+        super()._witness(sel)
+
+    def _circuit_size(self):
+        cells, n_in, db, sb, ab = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        s, g = ctypes.c_uint(), ctypes.c_uint()
+        check(self.lib.vdb_wit_ann_move_size(self.K, self.n, self.n_b, self.m, ctypes.byref(cells), ctypes.byref(n_in), ctypes.byref(db), ctypes.byref(sb),
+                                             ctypes.byref(ab), ctypes.byref(s), ctypes.byref(g)))
+        assert g.value == self.grow
+        self.delete_base, self.shrink_base, self.append_base, self.shrink = db.value, sb.value, ab.value, s.value
+        return n_in.value, cells.value - n_in.value, 0
+
+    def _call(self, sel):
+        return self.lib.vdb_wit_ann_move_dev(self.d_levels.ptr, self.d_levels_b.ptr, self.index.d_roots.ptr, self.K, self.src, self.dst, self.n, self.n_b,
+                                             self.grow, api._p(self.slots), self.m, self.d_stream.ptr, sel, self.d_pub.ptr)
+
+    def results(self):
+        """(index_root_old (4,), a (4,), b (4,), slots (m, 4), leaves (m, 4), last (m, 4), moved leaves (m, 4), dest (m, 4), dest old
+        leaves (m, 4), index_root_new (4,))"""
+        pub = self.d_pub.download((6 * self.m + 4, 4))
+        per = pub[3:-1].reshape(self.m, 6, 4)
+        return (pub[0], pub[1], pub[2]) + tuple(per[:, i] for i in range(6)) + (pub[-1],)
+
+    def constraint_map(self, d_flags, on_device=True):
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        cm, pub, _ = CS.build_ann_move(self.K, self.m, self.depth, self.shrink, self.depth_b, self.grow, functools.partial(self._fetch_flags, d_flags),
+                                       self._fetch, builder=DeviceBuilder if on_device else None)
+        assert cm.n_cells == self.n_cells
+        return cm, pub, None
 
 
 class _AnnClusterHotPath(HotPath):

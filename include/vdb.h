@@ -539,6 +539,58 @@ int vdb_ann_index_remove_dev(const vdb_fr *grouped_dev, const vdb_fr *forest_dev
                              const uint64_t *slots /* host */, size_t m, vdb_fr *grouped_out_dev, uint32_t *slots_out_dev,
                              uint64_t *offsets_out_dev, vdb_fr *forest_out_dev, vdb_fr *roots_out_dev);
 
+/* Moves against the index root: m members pass from cluster a = src to cluster b = dst (a != b) in one circuit, index_root_old to
+ * index_root_new.  The database, its slots and its database_root are untouched: no vector enters the circuit, a leaf travels as one
+ * witness cell.  Move j is delete j of a as vdb_wit_ann_delete has it (swap-with-last; repeats and slot_j == last_j are legal) and an
+ * append to b at dest_j = n_b + j whose new leaf is the removed leaf.  s: a's halvings as in vdb_wit_ann_delete; g: the smallest number
+ * of doublings after which b's tree holds n_b + m leaves (both returned by _size).  Stream, from cell 0:
+ *   A      [a | b | centroids_root | cluster_root_0 .. cluster_root_{K-1}] assigned, K + 3 cells (input_cells)
+ *   B_a, C_a  idx_to_indicator(a, K), select_by_indicator(cluster roots, .) -> picked_a            (blocks B, C of vdb_wit_ann_update)
+ *   D      the sponge over [centroids_root | cluster roots] -> index_root_old
+ *   E'     the delete's update block on a's tree, from cell delete_base on: 2 m path updates, 2 j at slot_j with a carried leaf, 2 j + 1 at
+ *          last_j a delete; S from shrink_base on when s >= 1
+ *   F_a    mid_j = select(a's new root, cluster_root_j, ind_a_j), 8 K cells
+ *   B_b, C_b  idx_to_indicator(b, K), select_by_indicator(mid_0 .. mid_{K-1}, .) -> picked_b: over the roots AFTER the removal
+ *   E_b    the update block of vdb_wit_merkle_update_ops on b's tree with grow = g, from cell append_base on: m appends at dest_j, each
+ *          new leaf CARRIED: one ctx.load_witness(digest) cell where a write has its leaf sponge
+ *   F_b    out_j = select(b's new root, mid_j, ind_b_j)
+ *   G      the sponge over [centroids_root | out_0 ..] -> index_root_new
+ * Copies (no cell), beyond those of the blocks themselves: picked_a <-> the old root E' exposes; picked_b <-> the old root E_b exposes
+ * (R_0 when g >= 1, else cur_old at the top of its update 0); THE MOVE: the carried-leaf cell of E_b's update j <-> the assigned old-leaf
+ * cell of E''s update 2 j, the removed leaf; F_a's a <-> S_0 (E''s final root when s == 0); F_b's a <-> E_b's final root.  Because b's
+ * root is selected from mid, the circuit is sound whatever a and b are and holds no a != b gate; the library refuses a == b because the
+ * resident operation is not defined for it.
+ * public, 6 m + 4 values: [index_root_old | a | b | slot_j, leaf_j, last_j, moved_leaf_j, dest_j, dest_old_leaf_j per move |
+ * index_root_new].  The fills are not committed: a verifier who tracks n_a and n_b checks last_j == n_a - 1 - j, dest_j == n_b + j and
+ * dest_old_leaf_j == 0.  The shape depends on (K, d_a, s, d_b, g, m) only; no input row, no lookup cell; the launches depend on d_a, d_b,
+ * s > 0 and g > 0.
+ * levels_src: a's tree over its n_a members, left in the state after the batch at its old size; levels_dst: b's tree AFTER
+ * vdb_merkle_tree_grow_dev when g > 0, left in the state after the batch.  slots is a HOST array.  The _dev form honours
+ * vdb_wit_set_window.  VDB_ERR_ARG before anything is launched: m == 0, 2 m > VDB_MERKLE_UPDATE_MAX_UPDATES, m >= n_a, a slot >= a's
+ * fill at its turn, a == b, a >= K, b >= K, K < 2, K > VDB_ANN_MAX_CLUSTERS, n_b == 0, a grow that is not the smallest that fits, the cell
+ * limit.  _size takes no slots; each of its outputs may be NULL.
+ *
+ * vdb_ann_index_move_dev (values only, functional; the old buffers are only read): the index after the batch.  a's surviving position p
+ * holds its original member origin[p], the moved rows follow b's rows in move order, the rows between the two clusters shift by m; THE
+ * SLOTS ENTRIES TRAVEL WITH THEIR ROWS: the database is not renumbered.  Forest segment a is its updated tree cut to lp_a >> s, segment
+ * b the grown, updated tree; two roots are replaced and the index root is hashed once: four launches whatever the shape.
+ * vdb_ann_index_move_size: s, g, the digests of the new forest and its K + 2 segment offsets (each may be NULL).  Output sizes: grouped
+ * n x dim, slots n, offsets K + 1, forest `digests`, roots K + 2. */
+int vdb_wit_ann_move_size(size_t K, size_t n_a, size_t n_b, size_t m, uint64_t *cells, uint64_t *input_cells, uint64_t *delete_base,
+                          uint64_t *shrink_base, uint64_t *append_base, unsigned *shrink, unsigned *grow);
+int vdb_wit_ann_move(vdb_fr *levels_src, vdb_fr *levels_dst, const vdb_fr *roots, size_t K, size_t src, size_t dst, size_t n_a, size_t n_b,
+                     unsigned grow, const uint64_t *slots, size_t m, vdb_fr *stream_out, uint8_t *selector_out, vdb_fr *public_out);
+int vdb_wit_ann_move_dev(vdb_fr *levels_src_dev, vdb_fr *levels_dst_dev, const vdb_fr *roots_dev, size_t K, size_t src, size_t dst, size_t n_a,
+                         size_t n_b, unsigned grow, const uint64_t *slots /* host */, size_t m, vdb_fr *stream_dev, uint8_t *selector_dev,
+                         vdb_fr *public_dev);
+int vdb_ann_index_move_size(const uint64_t *cluster_sizes /* host */, size_t K, size_t src, size_t dst, const uint64_t *slots /* host */, size_t m,
+                            unsigned *shrink, unsigned *grow, uint64_t *digests, uint64_t *segment_offsets);
+int vdb_ann_index_move_dev(const vdb_fr *grouped_dev, const uint32_t *slots_dev, const vdb_fr *forest_dev, const vdb_fr *roots_dev,
+                           const uint64_t *cluster_sizes /* host */, size_t K, size_t dim, size_t src, size_t dst, unsigned grow,
+                           const vdb_fr *updated_src_dev, const vdb_fr *updated_dst_dev, const uint64_t *slots /* host */, size_t m,
+                           vdb_fr *grouped_out_dev, uint32_t *slots_out_dev, uint64_t *offsets_out_dev, vdb_fr *forest_out_dev,
+                           vdb_fr *roots_out_dev);
+
 /* The audit of one cluster's routing: in the index with root index_root, every member committed under cluster_root_c is at least as
  * close to centroid c as to any other committed centroid, in the circuit's fixed-point distance for `metric`.  It covers the build's
  * cluster ids and the writes after them alike (audit cluster c of the index a batch into c leaves); K such proofs cover an index.  It

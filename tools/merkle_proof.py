@@ -33,6 +33,10 @@ again, so every delete but the first removes the member the one before moved the
 tree halves when the fill drops to a power of two; [index_root_old | c | slot, removed leaf, last, moved leaf per delete | index_root_new]
 public), has the verifier check the proof and removes the batch from the resident index (AnnIndex.removed), whose root must be the
 public index_root_new.
+`--circuit ann-move --K C --moves M [--src a --dst b]` proves M moves from cluster a (default: the largest) to cluster b (default: the
+next one) of that index (pipeline.AnnMoveHotPath: slots 0, 1, .. of a; [index_root_old | a | b | slot, leaf, last, moved leaf, dest, dest old leaf per
+move | index_root_new] public; no vector enters the circuit), has the verifier check the proof and moves the batch in the resident
+index (AnnIndex.moved), whose root must be the public index_root_new and whose database tree must be the old one.
 `--circuit ann-audit --K C [--cluster c]` proves the routing of one cluster of that index (pipeline.AnnAuditHotPath: the database is routed
 with AnnIndex.assign, the circuit's own fixed-point rule; every member of cluster c — default: the largest — is at least as close to
 centroid c as to any other centroid; [index_root | c] public) and has the verifier check the proof.  Exit status 0 when it is accepted.
@@ -57,7 +61,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from halo2_vectordb_amd import api  # noqa: E402
-from halo2_vectordb_amd.pipeline import AnnAuditHotPath, AnnCoverHotPath, AnnDeleteHotPath, AnnMeanHotPath, AnnRecentreHotPath, AnnIndex, AnnProbeQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
+from halo2_vectordb_amd.pipeline import AnnAuditHotPath, AnnCoverHotPath, AnnDeleteHotPath, AnnMeanHotPath, AnnMoveHotPath, AnnRecentreHotPath, AnnIndex, AnnProbeQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
 from halo2_vectordb_amd.rounds import ProverRounds, quotient_identity_holds  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -68,7 +72,7 @@ ap.add_argument("--seed", type=int, default=20260003)
 ap.add_argument("--block-cols", type=int, default=510)
 ap.add_argument("--ext-block-cols", type=int, default=None)
 ap.add_argument("--proofs", type=int, default=2)
-ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read", "ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"])
+ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read", "ann", "ann-update", "ann-delete", "ann-move", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"])
 ap.add_argument("--lookup-bits", type=int, default=13)
 ap.add_argument("--metric", default="euclidean")
 ap.add_argument("--queries", type=int, default=1, help="--circuit query: queries proved against the one database in this proof")
@@ -76,6 +80,9 @@ ap.add_argument("--topk", type=int, default=1, help="--circuit query / ann: near
 ap.add_argument("--probes", type=int, default=1, help="--circuit ann: clusters searched, the nearest centroids' in the order the top-k rounds state them")
 ap.add_argument("--updates", type=int, default=8, help="--circuit update: inserts / replacements proved in this proof")
 ap.add_argument("--deletes", type=int, default=0, help="--circuit update: the last K updates empty their slot instead of writing it; --circuit ann-delete: deletes proved")
+ap.add_argument("--moves", type=int, default=8, help="--circuit ann-move: members moved in this proof")
+ap.add_argument("--src", type=int, default=None, help="--circuit ann-move: the cluster the members leave (default: the largest)")
+ap.add_argument("--dst", type=int, default=None, help="--circuit ann-move: the cluster they arrive in (default: the one after --src)")
 ap.add_argument("--grow", type=int, default=None, help="--circuit update / ann-update: doublings of the padded leaf count before the first update")
 ap.add_argument("--reads", type=int, default=8, help="--circuit read: slots opened in this proof")
 ap.add_argument("--leaf-only", action="store_true", help="--circuit read: reveal the leaf digests, not the vectors")
@@ -105,7 +112,7 @@ elif args.circuit == "update":
         raise SystemExit("--deletes is between 0 and --updates, --grow is not negative")
     kinds = [0] * (args.updates - args.deletes) + [1] * args.deletes
     hp = UpdateHotPath(n=args.n, dim=args.dim, m=args.updates, k=args.k, seed=args.seed, kinds=kinds, grow=args.grow)
-elif args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"):
+elif args.circuit in ("ann", "ann-update", "ann-delete", "ann-move", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"):
     from halo2_vectordb_amd.pipeline import sift_like_vectors
     if not 1 <= args.K <= args.n:
         raise SystemExit("--K is between 1 and --n")
@@ -141,6 +148,12 @@ elif args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit", "ann-mean"
         hp = AnnCoverHotPath(index, k=args.k)
     elif args.circuit == "ann":
         hp = AnnProbeQueryHotPath(index, query, probes=args.probes, topk=args.topk, k=args.k, L=args.lookup_bits, metric=args.metric)
+    elif args.circuit == "ann-move":
+        a = int(np.argmax(index.sizes)) if args.src is None else args.src
+        b = (a + 1) % args.K if args.dst is None else args.dst
+        if args.K < 2 or not (0 <= a < args.K and 0 <= b < args.K and a != b) or not 1 <= args.moves < int(index.sizes[a]):
+            raise SystemExit("--K is at least 2, --src and --dst are two clusters of the index, --moves is at least 1 and leaves --src a member")
+        hp = AnnMoveHotPath(index, a, b, list(range(args.moves)), k=args.k)
     elif args.circuit == "ann-delete":
         c = int(np.argmax(index.sizes))
         if not 1 <= args.deletes < int(index.sizes[c]):
@@ -185,7 +198,7 @@ if args.out:
     write_snark(args.out, out["proof"], out["instances"])
     pr.save_verifying_key(args.out + ".vk.npz", opened=out["opened"])
 accepted = {}
-if args.circuit in ("read", "ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"):
+if args.circuit in ("read", "ann", "ann-update", "ann-delete", "ann-move", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"):
     from halo2_vectordb_amd import verifier
     accepted = {"proof_accepted": bool(verifier.verify(out["proof"], out["instances"], verifier.VerifyingKey.from_prover(pr, out["opened"])))}
 if args.circuit == "ann-update":
@@ -206,6 +219,12 @@ if args.circuit == "ann-recentre":
 if args.circuit == "ann-cover":
     accepted["database_root_is_the_tree_builders"] = bool(np.array_equal(hp.results()[0], api.poseidon_merkle_root(index.qvec)))
     accepted["index_root_is_the_indexs"] = bool(np.array_equal(hp.results()[1], index.roots()[-1]))
+if args.circuit == "ann-move":
+    index2 = index.moved(hp)
+    lp2 = 2 * api.merkle_levels(index.n)[0]
+    accepted["moved_index_root_is_the_public_new_root"] = bool(np.array_equal(index2.roots()[-1], hp.results()[-1]))
+    accepted["database_tree_is_unchanged"] = bool(np.array_equal(index2.database_tree().download((lp2, 4)), index.database_tree().download((lp2, 4))))
+    index2.free()
 if args.circuit == "ann-delete":
     index2 = index.removed(hp)
     accepted["removed_index_root_is_the_public_new_root"] = bool(np.array_equal(index2.roots()[-1], hp.results()[-1]))
@@ -220,6 +239,7 @@ what = f"merkle_commitment {args.n}x{args.dim} k={args.k}" if args.circuit == "m
     f"recentre of cluster {hp.cluster} ({hp.n} members) from the old index root to the new (K={args.K}) of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann-recentre" else \
     f"cover of the database by the index (K={args.K}, cluster sizes {int(index.sizes.min())} .. {int(index.sizes.max())}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-cover" else \
     f"mean audit of cluster {hp.cluster} ({hp.n} members) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann-mean" else \
+    f"{args.moves} moves from cluster {hp.src} ({hp.n} members, tree halved {hp.shrink} times) to cluster {hp.dst} ({hp.n_b} members, tree grown {hp.grow} times) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-move" else \
     f"{args.deletes} deletes from cluster {hp.cluster} ({hp.n} members, tree halved {hp.shrink} times) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-delete" else \
     f"query circuit ({str(args.queries) + ' x ' if args.queries > 1 else ''}{'top-' + str(args.topk) + ' ' if args.topk > 1 else ''}nearest_vector {args.metric} + merkle_commitment) over {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}"
 print(json.dumps({"workload": what + ": whole constraint map, public outputs in the instance column, transcript, fresh blinds, SHPLONK", "lookup_cells": hp.n_lookup,
@@ -231,11 +251,13 @@ print(json.dumps({"workload": what + ": whole constraint map, public outputs in 
                   "block_cols": args.block_cols, "ext_cols_held": hp.ext_cols}))
 pr.free()
 hp.free()
-if args.circuit in ("ann", "ann-update", "ann-delete", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"):
+if args.circuit in ("ann", "ann-update", "ann-delete", "ann-move", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"):
     index.free()
 if args.circuit == "ann-cover" and not (accepted["database_root_is_the_tree_builders"] and accepted["index_root_is_the_indexs"]):
     sys.exit(1)
 if args.circuit in ("ann-audit", "ann-mean", "ann-recentre", "ann-cover") and not accepted["proof_accepted"]:
     sys.exit(1)
 if args.circuit == "ann-recentre" and not accepted["recentred_root_is_public_root"]:
+    sys.exit(1)
+if args.circuit == "ann-move" and not (accepted["proof_accepted"] and accepted["moved_index_root_is_the_public_new_root"] and accepted["database_tree_is_unchanged"]):
     sys.exit(1)
