@@ -96,6 +96,12 @@ _SIGNATURES = {
     "vdb_wit_ann_move_dev": [_P, _P, _P, _SZ, _SZ, _SZ, _SZ, _SZ, _U32, _P, _SZ, _P, _P, _P],
     "vdb_ann_index_move_size": [_P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P],
     "vdb_ann_index_move_dev": [_P, _P, _P, _P, _P, _SZ, _SZ, _SZ, _SZ, _U32, _P, _P, _P, _SZ, _P, _P, _P, _P, _P],
+    "vdb_wit_ann_write_size": [_SZ, _SZ, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _P],
+    "vdb_ann_write_db_indices": [_P, _SZ, _SZ, _P, _SZ, _P, _P, _P],
+    "vdb_wit_ann_write": [_P, _P, _P, _SZ, _SZ, _SZ, _SZ, _SZ, _U32, _U32, _P, _P, _P, _SZ, _P, _P, _P],
+    "vdb_wit_ann_write_dev": [_P, _P, _P, _SZ, _SZ, _SZ, _SZ, _SZ, _U32, _U32, _P, _P, _P, _SZ, _P, _P, _P],
+    "vdb_ann_index_write_size": [_P, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P],
+    "vdb_ann_index_write_dev": [_P, _P, _P, _P, _P, _SZ, _SZ, _SZ, _U32, _U32, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P, _P],
     "vdb_wit_ann_audit_size": [_I, _U32, _U32, _SZ, _SZ, _SZ, _P, _P, _P],
     "vdb_wit_ann_audit": [_I, _U32, _U32, _P, _P, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],
     "vdb_wit_ann_audit_dev": [_I, _U32, _U32, _P, _P, _P, _P, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],

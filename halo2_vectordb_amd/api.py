@@ -748,6 +748,87 @@ def ann_index_apply(index, cluster, grow, updated_levels, new_vectors, indices, 
             b.free()
 
 
+def ann_write_db_indices(cluster_slots, indices, n_db):
+    """the database slot of every write of a batch into one cluster (vdb_ann_write_db_indices: values only, no device call): a replacement
+    takes the slot `cluster_slots` records for its member, an append n_db + the appends so far, a write to a member the batch appended
+    that member's -> (db_idx (m,) uint64, appends); VdbError on a write above the fill or a recorded slot outside the database"""
+    lib = _lib.load()
+    slots, idx = np.ascontiguousarray(cluster_slots, dtype=np.uint64), np.ascontiguousarray(indices, dtype=np.uint64)
+    out, appends = np.zeros(max(idx.shape[0], 1), dtype=np.uint64), _u64()
+    check(lib.vdb_ann_write_db_indices(_p(slots), _sz(slots.shape[0]), _sz(n_db), _p(idx), _sz(idx.shape[0]), _p(out), ctypes.byref(appends), None))
+    return out[:idx.shape[0]], appends.value
+
+
+def wit_ann_write(levels_c, levels_db, roots, cluster, n_c, n_db, new_vectors, indices, db_indices, grow_c=None, grow_db=None, selectors=False):
+    """a linked write (vdb_wit_ann_write), the streams alone: m writes into cluster `cluster` of a committed index and the same m leaf
+    changes in the database tree.  levels_c: cluster c's tree over its n_c members, levels_db: the database tree over its n_db rows, each
+    AFTER merkle_tree_grow when its grow > 0 (None: the smallest number that fits, which the array's shape must match); `roots` (K + 1, 4):
+    [centroids' root | cluster roots]; new_vectors (m, dim, 4); indices (m,): slots of the cluster as wit_ann_update; db_indices (m,): the
+    database slots (ann_write_db_indices).  dict(stream, selectors, flags, input_cells, update_base, update_db_base, grow_c, grow_db,
+    public (4 m + 5, 4): [database_root_old | index_root_old | c | idx, db_idx, old leaf, new leaf per write | database_root_new |
+    index_root_new], levels_c, levels_db: the two trees after the batch)"""
+    lib = _lib.init()
+    new_vectors, roots = _fr(new_vectors), _fr(roots)
+    idx, dbi = np.ascontiguousarray(indices, dtype=np.uint64), np.ascontiguousarray(db_indices, dtype=np.uint64)
+    m, dim, K = idx.shape[0], new_vectors.shape[1], roots.shape[0] - 1
+    fill = n_c
+    for s in idx.tolist():
+        fill += s == fill
+    cells, n_in, ub, udb, gc, gdb = _u64(), _u64(), _u64(), _u64(), ctypes.c_uint(), ctypes.c_uint()
+    check(lib.vdb_wit_ann_write_size(_sz(K), _sz(n_c), _sz(n_db), _sz(dim), _sz(m), _sz(fill - n_c), ctypes.byref(cells), ctypes.byref(n_in), ctypes.byref(ub),
+                                     ctypes.byref(udb), ctypes.byref(gc), ctypes.byref(gdb)))
+    grow_c, grow_db = gc.value if grow_c is None else int(grow_c), gdb.value if grow_db is None else int(grow_db)
+    lc, ld = np.array(levels_c, dtype=np.uint64, copy=True), np.array(levels_db, dtype=np.uint64, copy=True)
+    assert idx.shape == (m,) and dbi.shape == (m,) and new_vectors.shape[0] == m
+    assert lc.shape == (2 * (merkle_levels(n_c)[0] << grow_c), 4) and ld.shape == (2 * (merkle_levels(n_db)[0] << grow_db), 4)
+    stream, pub = np.zeros((cells.value, 4), dtype=np.uint64), np.zeros((4 * m + 5, 4), dtype=np.uint64)
+    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
+    check(lib.vdb_wit_ann_write(_p(lc), _p(ld), _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(n_db), _sz(dim), grow_c, grow_db, _p(new_vectors), _p(idx),
+                                _p(dbi), _sz(m), _p(stream), _p(sel) if selectors else None, _p(pub)))
+    return dict(stream=stream, **_split_flags(sel), input_cells=n_in.value, update_base=ub.value, update_db_base=udb.value, grow_c=grow_c, grow_db=grow_db,
+                public=pub, levels_c=lc, levels_db=ld)
+
+
+def ann_index_write_layout(sizes, cluster, indices):
+    """(appends, g_c, g_db, digests of the forest after the batch, its K + 2 segment offsets, digests of the database tree after it) of
+    vdb_ann_index_write_dev (vdb_ann_index_write_size; VdbError on a write above the fill)"""
+    lib = _lib.init()
+    sizes, idx = np.ascontiguousarray(sizes, dtype=np.uint64), np.ascontiguousarray(indices, dtype=np.uint64)
+    K = sizes.shape[0]
+    appends, gc, gdb, digests, seg, dbd = _u64(), ctypes.c_uint(), ctypes.c_uint(), _u64(), np.zeros(K + 2, dtype=np.uint64), _u64()
+    check(lib.vdb_ann_index_write_size(_p(sizes), _sz(K), _sz(cluster), _p(idx), _sz(idx.shape[0]), ctypes.byref(appends), ctypes.byref(gc), ctypes.byref(gdb),
+                                       ctypes.byref(digests), _p(seg), ctypes.byref(dbd)))
+    return appends.value, gc.value, gdb.value, digests.value, seg, dbd.value
+
+
+def ann_index_write(index, cluster, updated_levels, updated_db_levels, new_vectors, indices, grow_c=None, grow_db=None):
+    """both resident objects after a linked write (vdb_ann_index_write_dev), host arrays in and out: `index` an ann_index_build dict,
+    updated_levels / updated_db_levels the two trees the witness call left -> a dict of the same form with db_tree: the database tree of
+    the new index; the appends take the database slots n, n + 1, ..."""
+    lib = _lib.init()
+    new_vectors, uc, ud = _fr(new_vectors), _fr(updated_levels), _fr(updated_db_levels)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64)
+    sizes = np.diff(np.asarray(index["offsets"], dtype=np.uint64)).astype(np.uint64)
+    K, dim, n = sizes.shape[0], new_vectors.shape[1], index["grouped"].shape[0]
+    appends, gc, gdb, digests, seg, dbd = ann_index_write_layout(sizes, cluster, idx)
+    grow_c, grow_db = gc if grow_c is None else int(grow_c), gdb if grow_db is None else int(grow_db)
+    assert idx.shape == (new_vectors.shape[0],)
+    n2 = n + appends
+    src = [index["grouped"], np.ascontiguousarray(index["slots"], dtype=np.uint32), index["forest"], index["roots"], uc, ud, new_vectors]
+    ins = [DeviceBuffer(max(a.nbytes, 32)) for a in src]
+    outs = [DeviceBuffer(max(b, 32)) for b in (n2 * dim * 32, n2 * 4, (K + 1) * 8, digests * 32, (K + 2) * 32, ud.nbytes)]
+    try:
+        for b, a in zip(ins, src):
+            b.upload(np.ascontiguousarray(a))
+        check(lib.vdb_ann_index_write_dev(ins[0].ptr, ins[1].ptr, ins[2].ptr, ins[3].ptr, _p(sizes), _sz(K), _sz(dim), _sz(cluster), grow_c, grow_db,
+                                          ins[4].ptr, ins[5].ptr, ins[6].ptr, _p(idx), _sz(idx.shape[0]), *[o.ptr for o in outs]))
+        return dict(grouped=outs[0].download((n2, dim, 4)), slots=outs[1].download((n2,), dtype=np.uint32), offsets=outs[2].download((K + 1,), dtype=np.uint64),
+                    forest=outs[3].download((digests, 4)), segments=seg, roots=outs[4].download((K + 2, 4)), db_tree=outs[5].download((ud.shape[0], 4)))
+    finally:
+        for b in ins + outs:
+            b.free()
+
+
 def wit_ann_delete(levels, roots, cluster, n_c, dim, slots, selectors=False):
     """m deletes from cluster `cluster` of a committed index (vdb_wit_ann_delete), the streams alone: `levels` cluster c's tree over its
     n_c members (merkle_tree_build's array), `roots` (K + 1, 4): [centroids' root | cluster roots], slots (m,): slot j is below the fill

@@ -1547,6 +1547,77 @@ def build_ann_update(K, m, dim, depth, fetch_flags, fetch_values, builder=None, 
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# Linked writes: one batch against the database root and the index root (include/vdb.h vdb_wit_ann_write; pipeline.AnnWriteHotPath)
+def ann_write_layout(K, m, dim, depth, grow, depth_db, grow_db):
+    """where the blocks of the linked write start: ann_update_layout's keys (A - D, E at `update`, F, G; update_layout) with block E_db
+    between E and F: update_db its first cell, update_db_layout merkle_update_layout of m carried updates at dim 1 on the database tree
+    (`depth_db` the grown one)"""
+    upd = merkle_update_layout(m, dim, depth, None, grow)
+    upd_db = merkle_update_layout(m, 1, depth_db, [2] * m, grow_db, carried=True)
+    lay = dict(_ann_frame_layout(K, merkle_leaf_layout(K + 1), upd["total"] + upd_db["total"]), update_layout=upd, update_db_layout=upd_db)
+    lay["update_db"] = lay["update"] + upd["total"]
+    return lay
+
+
+def ann_write_instances(index_root_old, c, update_public, update_db_public, index_root_new):
+    """the public cells in make_public order: [database_root_old | index_root_old | c | idx, db_idx, old leaf, new leaf per write |
+    database_root_new | index_root_new] from the two update blocks' [old root | idx, old leaf, new leaf per update | new root]"""
+    u, d = update_public, update_db_public
+    out = [int(d[0]), int(index_root_old), int(c)]
+    for j in range((len(u) - 2) // 3):
+        out += [int(u[1 + 3 * j]), int(d[1 + 3 * j]), int(u[2 + 3 * j]), int(u[3 + 3 * j])]
+    return out + [int(d[-1]), int(index_root_new)]
+
+
+def _write_info(lay, m, upub, updb):
+    """what both forms report about E and E_db: carried (the carried-leaf cell of E_db's update j), new_leaves (the squeeze of E's
+    leaf sponge j, tied to it), old_leaves / old_leaves_db (the assigned old-leaf cells of the two blocks, tied), each block's roots"""
+    u, db = lay["update_layout"], lay["update_db_layout"]
+    return dict(carried=[lay["update_db"] + db["block"][j] for j in range(m)], new_leaves=[int(upub[3 + 3 * j]) for j in range(m)],
+                old_leaves=[lay["update"] + u["old_leaf"] + j for j in range(m)], old_leaves_db=[lay["update_db"] + db["old_leaf"] + j for j in range(m)],
+                old_root=int(upub[0]), new_root=int(upub[-1]), old_root_db=int(updb[0]), new_root_db=int(updb[-1]))
+
+
+def trace_ann_write(K, m, dim, depth, fetch_flags, fetch_values, grow=0, depth_db=1, grow_db=0):
+    """The closure of a linked write cell by cell (the ground truth of build_ann_write): trace_ann_update's blocks A - D and E, then E_db
+    (the update block of the database tree, m carried updates), then F and G over E's final root.  Ties beyond trace_ann_update's: the
+    carried leaf of E_db's update j to the new leaf E's update j hashed, the old leaf of E_db's update j to the old leaf of E's.
+    -> (CopyMap, public cells, dict(trace_ann_update's keys and _write_info's))"""
+    lay = ann_write_layout(K, m, dim, depth, grow, depth_db, grow_db)
+    t = _CellTrace(lay["total"], fetch_flags, fetch_values)
+    inds, picked, root_old = _trace_ann_head(t, lay)
+    upub = _trace_update_block(t, lay["update_layout"], lay["update"])
+    t.copy_of[upub[0]] = picked                              # ctx.constrain_equal(picked, the update block's old root)
+    updb = _trace_update_block(t, lay["update_db_layout"], lay["update_db"])
+    info = _write_info(lay, m, upub, updb)
+    for x, y in zip(info["carried"], info["new_leaves"]):
+        t.copy_of[x] = y                                     # THE LINK: the database gains the digest the cluster gains
+    for x, y in zip(info["old_leaves_db"], info["old_leaves"]):
+        t.copy_of[x] = y                                     # and loses the digest the cluster loses
+    outs, root_new = _trace_ann_tail(t, lay, inds, upub[-1])
+    info = dict(info, indicators=inds, picked=picked, outs=outs, index_root_old=root_old, index_root_new=root_new, layout=lay)
+    return t.finish(), ann_write_instances(root_old, lay["c"], upub, updb, root_new), info
+
+
+def build_ann_write(K, m, dim, depth, fetch_flags, fetch_values, builder=None, grow=0, depth_db=1, grow_db=0):
+    """trace_ann_write's map assembled from unit blocks: build_ann_update's head and tail, place_merkle_update twice, the second with
+    the carried kind (`builder`: as build_kmeans).  -> as trace_ann_write"""
+    lay = ann_write_layout(K, m, dim, depth, grow, depth_db, grow_db)
+    B, inds, picked, root_old = _build_ann_head(lay, fetch_flags, fetch_values, builder)
+    upub = place_merkle_update(B, m, dim, depth, fetch_flags, fetch_values, lay["update"], None, grow)
+    B.tie(upub[0], picked)                                   # ctx.constrain_equal(picked, the update block's old root)
+    updb = place_merkle_update(B, m, 1, depth_db, fetch_flags, fetch_values, lay["update_db"], [2] * m, grow_db, carried=True)
+    info = _write_info(lay, m, upub, updb)
+    for x, y in zip(info["carried"], info["new_leaves"]):
+        B.tie(x, y)                                          # THE LINK: the database gains the digest the cluster gains
+    for x, y in zip(info["old_leaves_db"], info["old_leaves"]):
+        B.tie(x, y)                                          # and loses the digest the cluster loses
+    outs, root_new = _build_ann_tail(B, lay, inds, upub[-1], fetch_flags, fetch_values)
+    info = dict(info, indicators=[int(i) for i in inds], picked=picked, outs=outs, index_root_old=root_old, index_root_new=root_new, layout=lay)
+    return B.finish(), ann_write_instances(root_old, lay["c"], upub, updb, root_new), info
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # Deletes against the index root (include/vdb.h vdb_wit_ann_delete; pipeline.AnnDeleteHotPath)
 def ann_delete_shrink(n_c, m):
     """(depth of the cluster's tree over n_c members, the halvings s after m deletes: lp >> s is the power of two >= n_c - m)"""

@@ -406,4 +406,82 @@ static inline int annmv_index_plan(const uint64_t* sizes, size_t K, size_t a, si
   return 0;
 }
 
+// ------------------------------------------------------------------ linked writes (include/vdb.h vdb_wit_ann_write, vdb_ann_index_write_dev)
+// m inserts or replacements into cluster c run through TWO trees: write j is update j of the cluster's tree at indices[j] (the update's
+// block E, annu_track_fill's dense fill) and update j of the database tree at db_idx[j] with the CARRIED leaf E's update j hashed.  A
+// replacement takes the database slot recorded for its member (slots[indices[j]]: what the index's slots hold for cluster c); an append
+// takes n + the appends so far and records it, so a later write of the batch to the appended member finds it.  The database tree is
+// doubled g_db times before the first update: g_db is the smallest that fits n + appends.
+struct AnnwPlan {
+  std::vector<uint64_t> db_idx;   // m
+  uint64_t appends, lp_db, glp_db;   // the database's padded leaf counts before and after the growth
+  uint32_t depth_db, grow_db;        // depth_db: of the grown tree
+};
+// slots: the n_c database slots of the cluster's members (null: unknown to the caller; then `given` is checked as far as the fills
+// allow: an append's entry is n + the appends so far, a replacement's lies below that).  given (null: not given; it is required when slots
+// is null): the caller's own db_idx, which must be what the expansion yields.  grow_db < 0: not given.
+// -> 0; 1: indices[*bad] lies above the cluster's fill at its turn; 2: n == 0 or n_c > n; 3: slots[*bad] >= n; 4: given[*bad] is not what
+// the expansion yields; 5: grow_db is not the smallest that fits
+static inline int annw_expand(const uint64_t* slots, const uint64_t* indices, size_t m, uint64_t n_c, uint64_t n, const uint64_t* given, int grow_db,
+                              AnnwPlan* p, size_t* bad) {
+  if (n == 0 || n_c > n) return 2;
+  if (slots)
+    for (uint64_t i = 0; i < n_c; i++)
+      if (slots[i] >= n) {
+        if (bad) *bad = (size_t)i;
+        return 3;
+      }
+  p->db_idx.assign(m, 0);
+  p->appends = 0;
+  uint64_t fill = n_c;
+  for (size_t j = 0; j < m; j++) {
+    const uint64_t s = indices[j];
+    if (s > fill) {
+      if (bad) *bad = j;
+      return 1;
+    }
+    uint64_t d;
+    bool known = true;
+    if (s == fill) {
+      d = n + p->appends++;
+      fill++;
+    } else if (s >= n_c) {
+      d = n + (s - n_c);   // a member this batch appended: its slot was recorded at its append
+    } else if (slots) {
+      d = slots[s];
+    } else {
+      d = given ? given[j] : 0;
+      known = false;
+      if (!given || d >= n + p->appends) {
+        if (bad) *bad = j;
+        return 4;
+      }
+    }
+    if (known && given && given[j] != d) {
+      if (bad) *bad = j;
+      return 4;
+    }
+    p->db_idx[j] = d;
+  }
+  tree_shape(n, &p->lp_db, &p->depth_db);
+  uint32_t d0 = p->depth_db;
+  tree_shape(n + p->appends, &p->glp_db, &p->depth_db);
+  p->grow_db = p->depth_db - d0;
+  if (grow_db >= 0 && (unsigned)grow_db != p->grow_db) return 5;
+  return 0;
+}
+// block offsets of the linked write: the update's frame (annu_blocks: A - D, E at u.b_upd, F at u.b_new, G at u.b_root) with E_db, the
+// update block of the database tree, between E and F (b_upd_db); n_pub = 4 m + 5 public values
+struct AnnwBlocks {
+  AnnuBlocks u;
+  uint64_t b_upd_db, n_pub;
+};
+static inline AnnwBlocks annw_blocks(uint64_t K, uint64_t m, uint64_t sponge_cells, uint64_t update_cells, uint64_t update_db_cells) {
+  AnnwBlocks o;
+  o.u = annu_blocks(K, sponge_cells, update_cells, update_db_cells);   // (E_db lies where the delete has its block S)
+  o.b_upd_db = o.u.b_shr;
+  o.n_pub = 4 * m + 5;
+  return o;
+}
+
 }  // namespace vdb

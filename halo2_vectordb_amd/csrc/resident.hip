@@ -347,13 +347,12 @@ static int ann_apply_plan(const uint64_t* sizes, size_t K, size_t dim, size_t cl
   VDB_ARG(p->n_new <= VDB_ANN_MAX_VECTORS, "index too large: n at most VDB_ANN_MAX_VECTORS");
   return VDB_OK;
 }
-int ann_index_apply_dev(const u256* grouped, const uint32_t* slots, const u256* forest, const u256* roots, const uint64_t* sizes, size_t K, size_t dim,
-                        size_t cluster, unsigned grow, const u256* updated, const u256* new_vectors, const uint64_t* indices, const uint32_t* db_slots,
-                        size_t m, u256* grouped_out, uint32_t* slots_out, uint64_t* offsets_out, u256* forest_out, u256* roots_out) {
-  static thread_local AnnuApplyPlan p;            // (pageable sources of asynchronous uploads: they outlive the call)
+// the launches of a planned batch (`p` outlives the call: the pageable source of asynchronous uploads); db_slots null: the appends go to
+// the database slots n, n + 1, .. (the linked write's)
+static int ann_apply_run(const AnnuApplyPlan& p, const u256* grouped, const uint32_t* slots, const u256* forest, const u256* roots, size_t K, size_t dim,
+                         size_t cluster, const u256* updated, const u256* new_vectors, const uint64_t* indices, const uint32_t* db_slots, size_t m,
+                         u256* grouped_out, uint32_t* slots_out, uint64_t* offsets_out, u256* forest_out, u256* roots_out) {
   static thread_local std::vector<uint32_t> tab;  // [idx m | db_slots appends]
-  TRY(ann_apply_plan(sizes, K, dim, cluster, grow, indices, m, &p));
-  VDB_ARG(db_slots || p.appends == 0, "null pointer: an append needs its database slot");
   const PoseidonSpec* sp;
   TRY(poseidon_spec_dev(&sp, nullptr));
   hipStream_t s = ctx().stream;
@@ -361,7 +360,7 @@ int ann_index_apply_dev(const u256* grouped, const uint32_t* slots, const u256* 
   mk_shape(1, K + 1, &mw);
   tab.resize(m + p.appends + 1);
   for (size_t j = 0; j < m; j++) tab[j] = (uint32_t)indices[j];
-  for (size_t i = 0; i < p.appends; i++) tab[m + i] = db_slots[i];
+  for (size_t i = 0; i < p.appends; i++) tab[m + i] = db_slots ? db_slots[i] : (uint32_t)(p.n_old + i);
   uint8_t* w = (uint8_t*)scratch_get(7, (K + 2) * 8 + (m + p.appends + 16) * 4);
   if (!w) return VDB_ERR_OOM;
   uint64_t* d_off = (uint64_t*)w;
@@ -380,6 +379,15 @@ int ann_index_apply_dev(const u256* grouped, const uint32_t* slots, const u256* 
   TRY(mk_leaf_states(sp, roots_out, 1u, (uint32_t)(K + 1), mw.nperm, states, roots_out + K + 1, nullptr));
   VDB_HIP(hipStreamSynchronize(s));
   return VDB_OK;
+}
+int ann_index_apply_dev(const u256* grouped, const uint32_t* slots, const u256* forest, const u256* roots, const uint64_t* sizes, size_t K, size_t dim,
+                        size_t cluster, unsigned grow, const u256* updated, const u256* new_vectors, const uint64_t* indices, const uint32_t* db_slots,
+                        size_t m, u256* grouped_out, uint32_t* slots_out, uint64_t* offsets_out, u256* forest_out, u256* roots_out) {
+  static thread_local AnnuApplyPlan p;
+  TRY(ann_apply_plan(sizes, K, dim, cluster, grow, indices, m, &p));
+  VDB_ARG(db_slots || p.appends == 0, "null pointer: an append needs its database slot");
+  return ann_apply_run(p, grouped, slots, forest, roots, K, dim, cluster, updated, new_vectors, indices, db_slots, m, grouped_out, slots_out, offsets_out,
+                       forest_out, roots_out);
 }
 
 // ------------------------------------------------------------------ the index after the recentre of one cluster (include/vdb.h
@@ -733,6 +741,36 @@ int ann_index_move_dev(const u256* grouped, const uint32_t* slots_in, const u256
   return VDB_OK;
 }
 
+// ------------------------------------------------------------------ the index after a linked write (include/vdb.h vdb_ann_index_write_dev;
+// the batch's circuit is witness.hip's).  Both resident objects are kept: the index is ann_index_apply_dev's launches (ann_apply_run on the one plan), its appends at database
+// slots n, n + 1, ... in append order, and the database tree is the one the witness call wrote its carried leaves back into, copied
+// device to device as it stands: no vector and no node is hashed again.
+// what the two entry points share (VDB_ERR_ARG, nothing launched): ann_apply_plan's, then the database's own shape
+static int ann_write_plan(const uint64_t* sizes, size_t K, size_t dim, size_t cluster, unsigned grow_c, int grow_db, const uint64_t* indices, size_t m,
+                          AnnuApplyPlan* p, uint64_t* glp_db, unsigned* g_db) {
+  TRY(ann_apply_plan(sizes, K, dim, cluster, grow_c, indices, m, p));
+  uint64_t lp;
+  uint32_t d, gd;
+  tree_shape(p->n_old, &lp, &d);
+  tree_shape(p->n_new, glp_db, &gd);
+  *g_db = gd - d;
+  VDB_ARG(grow_db < 0 || (unsigned)grow_db == *g_db, "grow_db is the smallest number of doublings after which the database tree holds the appends");
+  return VDB_OK;
+}
+int ann_index_write_dev(const u256* grouped, const uint32_t* slots, const u256* forest, const u256* roots, const uint64_t* sizes, size_t K, size_t dim,
+                        size_t cluster, unsigned grow_c, unsigned grow_db, const u256* updated_c, const u256* updated_db, const u256* new_vectors,
+                        const uint64_t* indices, size_t m, u256* grouped_out, uint32_t* slots_out, uint64_t* offsets_out, u256* forest_out, u256* roots_out,
+                        u256* db_tree_out) {
+  static thread_local AnnuApplyPlan p;
+  uint64_t glp_db;
+  unsigned g_db;
+  VDB_ARG(grow_db <= 30, "more than 30 doublings");
+  TRY(ann_write_plan(sizes, K, dim, cluster, grow_c, (int)grow_db, indices, m, &p, &glp_db, &g_db));
+  VDB_HIP(hipMemcpyAsync(db_tree_out, updated_db, 2 * glp_db * sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
+  return ann_apply_run(p, grouped, slots, forest, roots, K, dim, cluster, updated_c, new_vectors, indices, nullptr, m, grouped_out, slots_out, offsets_out,
+                       forest_out, roots_out);
+}
+
 }  // namespace vdb
 
 using namespace vdb;
@@ -875,6 +913,43 @@ int vdb_ann_index_move_dev(const vdb_fr* grouped_dev, const uint32_t* slots_dev,
   return ann_index_move_dev(as_u256(grouped_dev), slots_dev, as_u256(forest_dev), as_u256(roots_dev), cluster_sizes, K, dim, src, dst, grow,
                             as_u256(updated_src_dev), as_u256(updated_dst_dev), slots, m, as_u256(grouped_out_dev), slots_out_dev, offsets_out_dev,
                             as_u256(forest_out_dev), as_u256(roots_out_dev));
+}
+
+int vdb_ann_index_write_size(const uint64_t* cluster_sizes, size_t K, size_t cluster, const uint64_t* indices, size_t m, uint64_t* appends, unsigned* grow_c,
+                             unsigned* grow_db, uint64_t* digests, uint64_t* segment_offsets, uint64_t* db_digests) {
+  AnnuApplyPlan p;
+  VDB_ARG(cluster_sizes && indices, "null pointer");
+  VDB_ARG(K > 0 && K <= VDB_ANN_MAX_CLUSTERS && cluster < K, "K = 0, K above VDB_ANN_MAX_CLUSTERS or cluster >= K");
+  VDB_ARG(cluster_sizes[cluster] > 0 && cluster_sizes[cluster] <= VDB_ANN_MAX_VECTORS && m > 0 && m <= MKU_MAX_UPDATES,
+          "empty cluster, cluster too large or a batch outside 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES");
+  // g_c: the smallest number of doublings after which the cluster's tree holds its appends
+  uint64_t lp, glp, app = 0, glp_db;
+  uint32_t d, gd;
+  unsigned g_db;
+  VDB_ARG(annu_track_fill(indices, m, cluster_sizes[cluster], ~(uint64_t)0, &app, nullptr) == 0, "a write above the cluster's fill at its turn");
+  tree_shape(cluster_sizes[cluster], &lp, &d);
+  tree_shape(cluster_sizes[cluster] + app, &glp, &gd);
+  TRY(ann_write_plan(cluster_sizes, K, 1, cluster, gd - d, -1, indices, m, &p, &glp_db, &g_db));
+  if (appends) *appends = p.appends;
+  if (grow_c) *grow_c = gd - d;
+  if (grow_db) *grow_db = g_db;
+  if (digests) *digests = p.seg_off[K + 1];
+  if (segment_offsets) memcpy(segment_offsets, p.seg_off.data(), (K + 2) * sizeof(uint64_t));
+  if (db_digests) *db_digests = 2 * glp_db;
+  return VDB_OK;
+}
+int vdb_ann_index_write_dev(const vdb_fr* grouped_dev, const uint32_t* slots_dev, const vdb_fr* forest_dev, const vdb_fr* roots_dev,
+                            const uint64_t* cluster_sizes, size_t K, size_t dim, size_t cluster, unsigned grow_c, unsigned grow_db,
+                            const vdb_fr* updated_levels_dev, const vdb_fr* updated_db_levels_dev, const vdb_fr* new_vectors_dev, const uint64_t* indices,
+                            size_t m, vdb_fr* grouped_out_dev, uint32_t* slots_out_dev, uint64_t* offsets_out_dev, vdb_fr* forest_out_dev,
+                            vdb_fr* roots_out_dev, vdb_fr* db_tree_out_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(grouped_dev && slots_dev && forest_dev && roots_dev && updated_levels_dev && updated_db_levels_dev && new_vectors_dev && grouped_out_dev &&
+              slots_out_dev && offsets_out_dev && forest_out_dev && roots_out_dev && db_tree_out_dev,
+          "null pointer");
+  return ann_index_write_dev(as_u256(grouped_dev), slots_dev, as_u256(forest_dev), as_u256(roots_dev), cluster_sizes, K, dim, cluster, grow_c, grow_db,
+                             as_u256(updated_levels_dev), as_u256(updated_db_levels_dev), as_u256(new_vectors_dev), indices, m, as_u256(grouped_out_dev),
+                             slots_out_dev, offsets_out_dev, as_u256(forest_out_dev), as_u256(roots_out_dev), as_u256(db_tree_out_dev));
 }
 
 }  // extern "C"

@@ -46,6 +46,10 @@ int ann_index_remove_dev(const u256* grouped, const u256* forest, const u256* ro
 int ann_index_move_dev(const u256* grouped, const uint32_t* slots_in, const u256* forest, const u256* roots, const uint64_t* sizes, size_t K, size_t dim, size_t a,
                        size_t b, unsigned grow, const u256* updated_a, const u256* updated_b, const uint64_t* slots, size_t m, u256* grouped_out,
                        uint32_t* slots_out, uint64_t* offsets_out, u256* forest_out, u256* roots_out);
+int ann_index_write_dev(const u256* grouped, const uint32_t* slots, const u256* forest, const u256* roots, const uint64_t* sizes, size_t K, size_t dim,
+                        size_t cluster, unsigned grow_c, unsigned grow_db, const u256* updated_c, const u256* updated_db, const u256* new_vectors,
+                        const uint64_t* indices, size_t m, u256* grouped_out, uint32_t* slots_out, uint64_t* offsets_out, u256* forest_out, u256* roots_out,
+                        u256* db_tree_out);
 int ann_index_db_tree_dev(const u256* forest, const uint64_t* sizes, const uint32_t* slots, size_t K, size_t n, u256* levels_out);
 
 }  // namespace vdb

@@ -2461,6 +2461,98 @@ int wit_ann_move_dev(u256* levels_a, u256* levels_b, const u256* roots, size_t K
   return inv_list_fixup(f.st);
 }
 
+// ------------------------------------------------------------------ linked writes: one batch through the cluster's tree and the database
+// tree (include/vdb.h vdb_wit_ann_write, vdb_ann_index_write_dev).  m inserts or replacements into cluster c in one circuit,
+// (database_root_old, index_root_old) to (database_root_new, index_root_new): blocks A - D, E, F, G are the update's above, cell for cell;
+// E_db between E and F is the update block on the database tree at dim 1 with grow g_db: update j at db_idx_j, its new leaf CARRIED from
+// E (the digest E's leaf sponge j squeezed, entry 3 + 3 j of E's public row), so every vector is hashed once.
+struct AnnwLayout {
+  MkLayout mw;
+  AnnwBlocks b;
+  MkuLayout me, mdb;
+};
+// [database_root_old | index_root_old | c | idx_j, db_idx_j, old_leaf_j, new_leaf_j per write | database_root_new | index_root_new] from
+// the two blocks' public rows [old root | idx, old leaf, new leaf per update | new root], the header and the two index roots
+__global__ __launch_bounds__(256) void k_annw_public(const u256* __restrict__ upub, const u256* __restrict__ updb, const u256* __restrict__ hdr,
+                                                     const u256* __restrict__ iroot, uint32_t m, u256* __restrict__ pub) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 4 * m + 5) return;
+  if (i < 3 || i >= 4 * m + 3) {
+    pub[i] = i == 0 ? updb[0] : i == 1 ? iroot[0] : i == 2 ? hdr[0] : i == 4 * m + 3 ? updb[3 * (size_t)m + 1] : iroot[1];
+    return;
+  }
+  const uint32_t j = (i - 3) / 4, k = (i - 3) % 4;
+  pub[i] = k == 1 ? updb[1 + 3 * (size_t)j] : upub[1 + 3 * (size_t)j + (k ? k - 1 : 0)];
+}
+// the host side of a linked write, before anything is launched: the layout of both blocks and every refusal.  indices null (the size
+// call): the batch is `appends` appends followed by replacements of slot 0, which has the shape of every batch with as many appends.
+// db_slots (null: unknown): the cluster's n_c database slots; db_indices (null: the expansion's own, which needs db_slots).  grow_db < 0:
+// the call computes it
+static int annw_layout(size_t K, size_t cluster, size_t n_c, size_t n_db, size_t dim, unsigned grow_c, int grow_db, const uint64_t* indices, uint64_t appends,
+                       const uint64_t* db_slots, const uint64_t* db_indices, size_t m, AnnwLayout* o, AnnwPlan* wp) {
+  static thread_local std::vector<uint64_t> shape_idx, shape_db;
+  static thread_local std::vector<uint8_t> kinds;
+  TRY(ann_frame_layout(K, cluster, n_c, &o->mw, &o->b.u, [&](uint64_t* update_cells, uint64_t* second_cells) -> int {
+    TRY(mku_layout(n_c, dim, m, nullptr, grow_c, &o->me, nullptr, nullptr, nullptr));
+    VDB_ARG(n_db > 0, "empty database");
+    VDB_ARG(n_c <= n_db && n_db <= VDB_ANN_MAX_VECTORS, "a cluster larger than its database, or n_db above VDB_ANN_MAX_VECTORS");
+    if (!indices) {
+      VDB_ARG(appends <= m, "more appends than writes");
+      shape_idx.resize(m);
+      shape_db.resize(m);
+      for (size_t j = 0; j < m; j++) shape_idx[j] = j < appends ? n_c + j : 0, shape_db[j] = j < appends ? n_db + j : 0;
+      indices = shape_idx.data(), db_indices = shape_db.data(), db_slots = nullptr;
+    }
+    uint64_t lp, track = 0;
+    uint32_t d;
+    tree_shape(n_c, &lp, &d);
+    VDB_ARG(annu_track_fill(indices, m, n_c, lp << grow_c, &track, nullptr) == 0,
+            "a write above the cluster's fill at its turn or outside the grown tree: the members of a cluster stay dense");
+    const int rc = annw_expand(db_slots, indices, m, n_c, n_db, db_indices, grow_db, wp, nullptr);
+    VDB_ARG(rc != 1, "a write above the cluster's fill at its turn");
+    VDB_ARG(rc != 2, "empty database, or a cluster larger than its database");
+    VDB_ARG(rc != 3, "a member's database slot at or above n_db");
+    VDB_ARG(rc != 4, "a database slot the batch does not yield: an append goes to the database's fill at its turn, a replacement below it");
+    VDB_ARG(rc == 0, "grow_db is the smallest number of doublings after which the database tree holds the appends");
+    kinds.assign(m, 2);
+    TRY(mku_layout(n_db, 1, m, kinds.data(), wp->grow_db, &o->mdb, nullptr, nullptr, nullptr, true));
+    *update_cells = o->me.total;
+    *second_cells = o->mdb.total;   // (E_db lies where the delete has its block S: annw_blocks)
+    return VDB_OK;
+  }));
+  o->b = annw_blocks(K, m, o->mw.total, o->me.total, o->mdb.total);
+  return VDB_OK;
+}
+// roots: [centroids_root | the K cluster roots] of the index before the batch; levels_c: cluster c's tree at depth d_c + g_c, levels_db:
+// the database tree at depth d_db + g_db (merkle_tree_grow_dev's when grown), both left in the state after the batch; pub: 4 m + 5.
+// The two update blocks take the plan's work space (scratch slot 0) and its one table upload one after the other in stream order, as
+// wit_ann_move_dev: E_db's upload and kernels are queued behind E's last kernel, which has read E's table by then and has written E's
+// public row, where E_db's carried leaves name their digests.
+int wit_ann_write_dev(u256* levels_c, u256* levels_db, const u256* roots, size_t K, size_t cluster, size_t n_c, size_t n_db, size_t dim, unsigned grow_c,
+                      int grow_db, const u256* new_vectors, const uint64_t* indices, const uint64_t* db_indices, size_t m, Streams st, u256* pub) {
+  static thread_local MkuPlan pe, pdb;
+  static thread_local AnnwPlan wp;
+  static thread_local std::vector<uint32_t> carry;
+  static thread_local std::vector<uint8_t> kinds;
+  AnnwLayout L;
+  VDB_ARG(indices && db_indices, "null pointer");
+  TRY(annw_layout(K, cluster, n_c, n_db, dim, grow_c, grow_db, indices, 0, nullptr, db_indices, m, &L, &wp));
+  const size_t n_up = 3 * m + 2;
+  TRY(mku_plan(n_c, dim, grow_c, new_vectors, indices, nullptr, m, &pe));
+  carry.resize(m);
+  kinds.assign(m, 2);
+  for (size_t j = 0; j < m; j++) carry[j] = (uint32_t)(3 + 3 * j);   // the new leaf of E's update j in E's public row
+  TRY(mku_plan(n_db, 1, wp.grow_db, nullptr, wp.db_idx.data(), kinds.data(), m, &pdb, carry.data(), n_up));
+  const AnnuBlocks& B = L.b.u;
+  AnnFrame f;
+  TRY(f.open(st, roots, K, cluster, B.h, L.mw, B.total, n_up, n_up));
+  TRY(mku_emit(f.fp, f.sp, pe, levels_c, dim, new_vectors, f.st, B.b_upd, f.upub));
+  TRY(mku_emit(f.fp, f.sp, pdb, levels_db, 1, nullptr, f.st, L.b.b_upd_db, f.extra, f.upub));
+  TRY(f.close(B, f.upub + n_up - 1));
+  VDB_LAUNCH(k_annw_public, dim3((unsigned)((4 * m + 5 + 255) / 256)), dim3(256), f.upub, f.extra, f.hdr, f.iroot, (uint32_t)m, pub);
+  return inv_list_fixup(f.st);
+}
+
 // ------------------------------------------------------------------ the cluster frame of the routing audit and the mean audit below: blocks
 // A - D are the frame's head; I [centroids | members] assigned; the audit's own blocks; MC, MM the two merkle_commitments, whose roots the
 // map ties to the header's centroids_root and to picked.  pub: [index_root | c].  Nothing after the head is AnnFrame's: close() is not called.
@@ -3629,6 +3721,83 @@ int vdb_wit_ann_move(vdb_fr* levels_src, vdb_fr* levels_dst, const vdb_fr* roots
   TRY(download(levels_src, da.p, 2 * mp.d.lp * sizeof(u256)));
   TRY(download(levels_dst, db.p, 2 * mp.glp_b * sizeof(u256)));
   return hs.finish(stream_out, nullptr, selector_out, L.b.total, 0);
+}
+
+// linked writes: one batch against the database root and the index root (include/vdb.h); the index after them: resident.hip
+int vdb_wit_ann_write_size(size_t K, size_t n_c, size_t n_db, size_t dim, size_t m, size_t appends, uint64_t* cells, uint64_t* input_cells,
+                           uint64_t* update_base, uint64_t* update_db_base, unsigned* grow_c, unsigned* grow_db) {
+  AnnwLayout L;
+  AnnwPlan wp;
+  VDB_ARG(n_c > 0 && n_c <= VDB_ANN_MAX_VECTORS && appends <= m, "empty cluster, cluster larger than VDB_ANN_MAX_VECTORS or more appends than writes");
+  uint64_t lp, glp;
+  uint32_t d, gd;
+  tree_shape(n_c, &lp, &d);
+  tree_shape(n_c + appends, &glp, &gd);
+  TRY(annw_layout(K, 0, n_c, n_db, dim, gd - d, -1, nullptr, appends, nullptr, nullptr, m, &L, &wp));
+  if (cells) *cells = L.b.u.total;
+  if (input_cells) *input_cells = L.b.u.h.n_in;
+  if (update_base) *update_base = L.b.u.b_upd;
+  if (update_db_base) *update_db_base = L.b.b_upd_db;
+  if (grow_c) *grow_c = gd - d;
+  if (grow_db) *grow_db = wp.grow_db;
+  return VDB_OK;
+}
+// the database slots of a batch from the cluster's recorded slots (annw_expand with the slots known): values only, host arrays, no device call
+int vdb_ann_write_db_indices(const uint64_t* cluster_slots, size_t n_c, size_t n_db, const uint64_t* indices, size_t m, uint64_t* db_indices, uint64_t* appends,
+                             unsigned* grow_db) {
+  AnnwPlan wp;
+  VDB_ARG(cluster_slots && indices && db_indices, "null pointer");
+  VDB_ARG(m > 0 && m <= MKU_MAX_UPDATES, "a batch holds 1 .. VDB_MERKLE_UPDATE_MAX_UPDATES updates");
+  VDB_ARG(n_c > 0 && n_db <= VDB_ANN_MAX_VECTORS, "empty cluster or n_db above VDB_ANN_MAX_VECTORS");
+  const int rc = annw_expand(cluster_slots, indices, m, n_c, n_db, nullptr, -1, &wp, nullptr);
+  VDB_ARG(rc != 1, "a write above the cluster's fill at its turn");
+  VDB_ARG(rc != 2, "empty database, or a cluster larger than its database");
+  VDB_ARG(rc == 0, "a member's database slot at or above n_db");
+  memcpy(db_indices, wp.db_idx.data(), m * sizeof(uint64_t));
+  if (appends) *appends = wp.appends;
+  if (grow_db) *grow_db = wp.grow_db;
+  return VDB_OK;
+}
+int vdb_wit_ann_write_dev(vdb_fr* levels_c_dev, vdb_fr* levels_db_dev, const vdb_fr* roots_dev, size_t K, size_t cluster, size_t n_c, size_t n_db, size_t dim,
+                          unsigned grow_c, unsigned grow_db, const vdb_fr* new_vectors_dev, const uint64_t* indices, const uint64_t* db_indices, size_t m,
+                          vdb_fr* stream_dev, uint8_t* selector_dev, vdb_fr* public_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(levels_c_dev && levels_db_dev && roots_dev && new_vectors_dev && indices && db_indices && stream_dev && public_dev, "null pointer");
+  VDB_ARG(grow_c <= 30 && grow_db <= 30, "more than 30 doublings");
+  DevStreams ds;
+  ds.init(stream_dev, selector_dev);
+  TRY(wit_ann_write_dev(as_u256(levels_c_dev), as_u256(levels_db_dev), as_u256(roots_dev), K, cluster, n_c, n_db, dim, grow_c, (int)grow_db,
+                        as_u256(new_vectors_dev), indices, db_indices, m, ds.st, as_u256(public_dev)));
+  return ds.finish();
+}
+int vdb_wit_ann_write(vdb_fr* levels_c, vdb_fr* levels_db, const vdb_fr* roots, size_t K, size_t cluster, size_t n_c, size_t n_db, size_t dim, unsigned grow_c,
+                      unsigned grow_db, const vdb_fr* new_vectors, const uint64_t* indices, const uint64_t* db_indices, size_t m, vdb_fr* stream_out,
+                      uint8_t* selector_out, vdb_fr* public_out) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(levels_c && levels_db && roots && new_vectors && indices && db_indices && stream_out && public_out, "null pointer");
+  VDB_ARG(grow_c <= 30 && grow_db <= 30, "more than 30 doublings");
+  AnnwLayout L;
+  AnnwPlan wp;
+  TRY(annw_layout(K, cluster, n_c, n_db, dim, grow_c, (int)grow_db, indices, 0, nullptr, db_indices, m, &L, &wp));
+  uint64_t lp_c;
+  uint32_t d;
+  tree_shape(n_c, &lp_c, &d);
+  lp_c <<= grow_c;
+  DevBuf dc, db, dr, dv, dpub;
+  HostStreams hs;
+  const size_t n_pub = L.b.n_pub;
+  TRY(upload(dc, levels_c, 2 * lp_c * sizeof(u256)));
+  TRY(upload(db, levels_db, 2 * wp.glp_db * sizeof(u256)));
+  TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
+  TRY(upload(dv, new_vectors, L.me.n_vec * sizeof(u256)));
+  TRY(dpub.alloc(n_pub * sizeof(u256)));
+  TRY(hs.init(L.b.u.total, 0, selector_out != nullptr));
+  TRY(wit_ann_write_dev(dc.as<u256>(), db.as<u256>(), dr.as<u256>(), K, cluster, n_c, n_db, dim, grow_c, (int)grow_db, dv.as<u256>(), indices, db_indices, m,
+                        hs.st, dpub.as<u256>()));
+  TRY(download(public_out, dpub.p, n_pub * sizeof(u256)));
+  TRY(download(levels_c, dc.p, 2 * lp_c * sizeof(u256)));
+  TRY(download(levels_db, db.p, 2 * wp.glp_db * sizeof(u256)));
+  return hs.finish(stream_out, nullptr, selector_out, L.b.u.total, 0);
 }
 
 // the audit of one cluster's routing (include/vdb.h)

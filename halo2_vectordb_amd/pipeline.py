@@ -1239,18 +1239,15 @@ class AnnIndex:
         ix.d_cent.upload(qcent)
         return ix
 
-    def updated(self, hp, db_slots=None):
-        """the index after the batch of AnnUpdateHotPath `hp` (its witness has run: hp.d_levels holds the cluster's tree after the
-        batch), as a new AnnIndex on buffers of its own (vdb_ann_index_apply_dev); this index stays valid.  `db_slots`: the database slot
-        of every append, in append order (None: n, n + 1, ..., which keeps the members in database order).  Queries, reads and further
-        updates run on the result unchanged."""
+    def _after_writes(self, hp, db_slots):
+        """the shape and the host view of the index after the writes of `hp` (AnnUpdateHotPath or AnnWriteHotPath) with its appends at
+        the database slots `db_slots`: replaced rows where the cluster's slots say, appended rows at db_slots -> (sizes before the batch
+        as uint64, the new AnnIndex on fresh, unfilled buffers)"""
         c, m, app = hp.cluster, hp.m, hp.appends
-        db_slots = np.arange(self.n, self.n + app, dtype=np.uint32) if db_slots is None else np.ascontiguousarray(db_slots, dtype=np.uint32)
         if db_slots.shape != (app,):
             raise ValueError("one database slot per append")
         sizes64 = np.ascontiguousarray(self.sizes, dtype=np.uint64)
         _, digests, seg = api.ann_index_apply_layout(sizes64, c, hp.grow, hp.indices)
-        # the host's view of the database: replaced rows where the cluster's slots say, appended rows at db_slots
         old_slots = self.d_slots.download((int(self.sizes[c]),), dtype=np.uint32, offset=int(self.offsets[c]) * 4)
         place = np.concatenate([old_slots, db_slots]).astype(np.int64)
         n2 = max(self.n, int(place.max()) + 1)
@@ -1260,11 +1257,39 @@ class AnnIndex:
             qvec[place[int(hp.indices[j])]], ids[place[int(hp.indices[j])]] = hp.qvec[j], c
         sizes = self.sizes.copy()
         sizes[c] += app
-        ix = AnnIndex.from_resident(self.dim, self.K, sizes, digests, seg, self.qcent, qvec, ids, P=self.P, L=self.L, metric=self.metric_name)
+        return sizes64, AnnIndex.from_resident(self.dim, self.K, sizes, digests, seg, self.qcent, qvec, ids, P=self.P, L=self.L, metric=self.metric_name)
+
+    def updated(self, hp, db_slots=None):
+        """the index after the batch of AnnUpdateHotPath `hp` (its witness has run: hp.d_levels holds the cluster's tree after the
+        batch), as a new AnnIndex on buffers of its own (vdb_ann_index_apply_dev); this index stays valid.  `db_slots`: the database slot
+        of every append, in append order (None: n, n + 1, ..., which keeps the members in database order).  Queries, reads and further
+        updates run on the result unchanged."""
+        c, m, app = hp.cluster, hp.m, hp.appends
+        db_slots = np.arange(self.n, self.n + app, dtype=np.uint32) if db_slots is None else np.ascontiguousarray(db_slots, dtype=np.uint32)
+        sizes64, ix = self._after_writes(hp, db_slots)
         try:
             check(self.lib.vdb_ann_index_apply_dev(self.d_grouped.ptr, self.d_slots.ptr, self.d_forest.ptr, self.d_roots.ptr, api._p(sizes64), self.K, self.dim,
                                                    c, hp.grow, hp.d_levels.ptr, hp.d_vec.ptr, api._p(hp.indices), api._p(db_slots) if app else None, m,
                                                    ix.d_grouped.ptr, ix.d_slots.ptr, ix.d_offsets.ptr, ix.d_forest.ptr, ix.d_roots.ptr))
+        except Exception:
+            ix.free()
+            raise
+        return ix
+
+    def written(self, hp):
+        """the index after the linked write of AnnWriteHotPath `hp` (its witness has run: hp.d_levels and hp.d_levels_db hold the two
+        trees after the batch), as a new AnnIndex on buffers of its own (vdb_ann_index_write_dev); this index stays valid.  The appends
+        take the database slots n, n + 1, ...; the host view is updated()'s.  The result's database tree is the one the proof wrote:
+        written(hp).database_tree() costs nothing and refuses nothing.  ValueError for a hot path built on another index or with one of
+        AnnWriteHotPath's overrides (levels, levels_db, db_indices): its trees are not this index's."""
+        if hp.index is not self or hp.given_levels is not None or hp.given_levels_db is not None or hp.given_db_indices is not None:
+            raise ValueError("the hot path was built on this index, with the index's own trees and database slots")
+        sizes64, ix = self._after_writes(hp, np.arange(self.n, self.n + hp.appends, dtype=np.uint32))
+        try:
+            ix.d_db_tree = ix._buf(2 * hp.lp_db * B)
+            check(self.lib.vdb_ann_index_write_dev(self.d_grouped.ptr, self.d_slots.ptr, self.d_forest.ptr, self.d_roots.ptr, api._p(sizes64), self.K, self.dim,
+                                                   hp.cluster, hp.grow, hp.grow_db, hp.d_levels.ptr, hp.d_levels_db.ptr, hp.d_vec.ptr, api._p(hp.indices), hp.m,
+                                                   ix.d_grouped.ptr, ix.d_slots.ptr, ix.d_offsets.ptr, ix.d_forest.ptr, ix.d_roots.ptr, ix.d_db_tree.ptr))
         except Exception:
             ix.free()
             raise
@@ -1683,6 +1708,71 @@ class AnnUpdateHotPath(_AnnBatchHotPath):
 
     def _builder(self, CS):
         return CS.build_ann_update, dict(grow=self.grow)
+
+
+class AnnWriteHotPath(AnnUpdateHotPath):
+    """Linked writes: m inserts or replacements into ONE cluster c of an AnnIndex and the same m leaf changes in the database tree, in one
+    proof (include/vdb.h vdb_wit_ann_write): (database_root_old, index_root_old) to (database_root_new, index_root_new).  The circuit is
+    AnnUpdateHotPath's, cell for cell, with one more block E_db between E and F: the update block of the database tree at dim 1 whose new
+    leaves are CARRIED: one witness cell each, tied to the digest E's leaf sponge squeezed, its old leaf tied to E's old leaf; every vector
+    is hashed once.  So a cover of the old pair of roots (AnnCoverHotPath) and this proof cover the new pair.  Public: [database_root_old |
+    index_root_old | c | idx, db_idx, old leaf, new leaf per write | database_root_new | index_root_new]; a verifier who tracks n_c and n
+    checks for an append idx = the cluster's fill, db_idx = the database's fill and old leaf = 0.  (K, d_c, g_c, d_db, g_db, m, dim) are
+    circuit shape; c, the slots and the values are not.  `d_levels` and `d_levels_db` hold the two trees after the batch;
+    AnnIndex.written(hp) gives the next index with its database tree."""
+
+    def __init__(self, index, cluster, updates, grow=None, k=15, L=8, tau=None, col_shard=(0, 1), blind_seed=None, params=None, levels=None, levels_db=None,
+                 db_indices=None):
+        """`updates`, `grow`, `levels`: as AnnUpdateHotPath (grow None: the smallest number that fits, which AnnIndex.written demands).
+        The database slots come from the index's own slots of cluster c; `db_indices` (m,) overrides them and `levels_db` the index's
+        database tree, not yet grown (tests of the binding)."""
+        super().__init__(index, cluster, updates, grow=grow, k=k, L=L, tau=tau, col_shard=col_shard, blind_seed=blind_seed, params=params, levels=levels)
+        slots = index.d_slots.download((self.n,), dtype=np.uint32, offset=int(index.offsets[self.cluster]) * 4)
+        own, _ = api.ann_write_db_indices(slots, self.indices, index.n)
+        self.db_indices = own if db_indices is None else np.ascontiguousarray(db_indices, dtype=np.uint64)
+        self.n_db = index.n
+        self.lp_db0, depth_db0 = api.merkle_levels(self.n_db)
+        self.lp_db, self.depth_db = api.merkle_levels(self.n_db + self.appends)
+        if self.depth_db < 1:
+            raise ValueError("a database tree of one leaf has no path")
+        self.grow_db = self.depth_db - depth_db0
+        self.n_public, self.given_levels_db, self.given_db_indices = 4 * self.m + 5, levels_db, db_indices
+
+    def _load_inputs(self):
+        super()._load_inputs()
+        self.d_levels_db0 = self._output(2 * self.lp_db * B)     # the grown database tree before the batch
+        self.d_levels_db = self._output(2 * self.lp_db * B)
+        given = self.index.database_tree() if self.given_levels_db is None else self.given_levels_db
+        self._load_tree(self.d_levels_db if self.grow_db else self.d_levels_db0, self.lp_db0, given)
+        if self.grow_db:
+            check(self.lib.vdb_merkle_tree_grow_dev(self.d_levels_db.ptr, self.n_db, self.grow_db, self.d_levels_db0.ptr))
+            api.sync()
+
+    def _witness(self, sel=None):
+        check(self.lib.vdb_memcpy_d2d(self.d_levels_db.ptr, self.d_levels_db0.ptr, ctypes.c_size_t(2 * self.lp_db * B)))
+        super()._witness(sel)
+
+    def _circuit_size(self):
+        cells, n_in, ub, udb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(self.lib.vdb_wit_ann_write_size(self.K, self.n, self.n_db, self.dim, self.m, self.appends, ctypes.byref(cells), ctypes.byref(n_in), ctypes.byref(ub),
+                                              ctypes.byref(udb), None, None))
+        self.update_base, self.update_db_base = ub.value, udb.value
+        return n_in.value, cells.value - n_in.value, 0
+
+    def _call(self, sel):
+        return self.lib.vdb_wit_ann_write_dev(self.d_levels.ptr, self.d_levels_db.ptr, self.index.d_roots.ptr, self.K, self.cluster, self.n, self.n_db, self.dim,
+                                              self.grow, self.grow_db, self.d_vec.ptr, api._p(self.indices), api._p(self.db_indices), self.m, self.d_stream.ptr,
+                                              sel, self.d_pub.ptr)
+
+    def results(self):
+        """(database_root_old (4,), index_root_old (4,), c (4,), indices (m, 4), database indices (m, 4), old leaves (m, 4), new leaves
+        (m, 4), database_root_new (4,), index_root_new (4,))"""
+        pub = self.d_pub.download((4 * self.m + 5, 4))
+        per = pub[3:-2].reshape(self.m, 4, 4)
+        return (pub[0], pub[1], pub[2]) + tuple(per[:, i] for i in range(4)) + (pub[-2], pub[-1])
+
+    def _builder(self, CS):
+        return CS.build_ann_write, dict(grow=self.grow, depth_db=self.depth_db, grow_db=self.grow_db)
 
 
 class AnnDeleteHotPath(_AnnBatchHotPath):

@@ -591,6 +591,57 @@ int vdb_ann_index_move_dev(const vdb_fr *grouped_dev, const uint32_t *slots_dev,
                            vdb_fr *grouped_out_dev, uint32_t *slots_out_dev, uint64_t *offsets_out_dev, vdb_fr *forest_out_dev,
                            vdb_fr *roots_out_dev);
 
+/* Linked writes: m inserts or replacements into ONE cluster c of the index and the same m leaf changes in the database tree, in one
+ * circuit: (database_root_old, index_root_old) to (database_root_new, index_root_new).  Every vector is hashed once.  Blocks A - D, E, F
+ * and G are vdb_wit_ann_update's, cell for cell (E from cell update_base on, grow = g_c); one block E_db lies between E and F, from cell
+ * update_db_base on: the update block of vdb_wit_merkle_update_ops on the database tree (n_db leaves, dim 1, grow = g_db) with m updates
+ * at the database slots db_idx_j, each new leaf CARRIED: one ctx.load_witness(digest) cell where a write has its leaf sponge.  A slot of
+ * E_db may be occupied (a replacement) or empty (an append: its old leaf is 0, the padding of the grown tree).
+ * Copies (no cell), beyond those of vdb_wit_ann_update: the carried-leaf cell of E_db's update j <-> the new-leaf digest cell of E's
+ * update j (the squeeze of its leaf sponge); the assigned old-leaf cell of E_db's update j <-> the assigned old-leaf cell of E's update j;
+ * the public database_root_old / database_root_new <-> the old root E_db exposes (R_0 when g_db >= 1, else cur_old at the top of its
+ * update 0) and its final root.
+ * public, 4 m + 5 values: [database_root_old | index_root_old | c | idx_j, db_idx_j, old_leaf_j, new_leaf_j per write |
+ * database_root_new | index_root_new].  The fills are not committed: a verifier who tracks n_c and n_db checks for an append idx_j ==
+ * the cluster's fill, db_idx_j == the database's fill and old_leaf_j == 0.  db_idx_j need not be "the" slot of the member: both trees
+ * lose the same digest and gain the same digest, and equal digests are interchangeable in a multiset.
+ * The shape depends on (K, d_c, g_c, d_db, g_db, m, dim) only; no input row, no lookup cell.
+ * levels_c: cluster c's tree AFTER vdb_merkle_tree_grow_dev when g_c > 0; levels_db: the database tree (vdb_ann_index_db_tree_dev's) AFTER
+ * vdb_merkle_tree_grow_dev when g_db > 0; both are left in the state after the batch.  indices and db_indices are HOST arrays.  The _dev
+ * form honours vdb_wit_set_window.  VDB_ERR_ARG before anything is launched: vdb_wit_ann_update's refusals; n_db == 0; n_c > n_db; a
+ * db_indices entry the batch does not yield (an append's is n_db + the appends so far, a write to a member this batch appended has that
+ * member's, a replacement's lies below n_db + the appends so far); a grow_db that is not the smallest that fits; the cell limit.
+ * vdb_ann_write_db_indices (values only, host arrays, no device call): db_indices from the cluster's n_c recorded database slots (what the
+ * index's slots hold for cluster c) and the batch's indices, with the appends and g_db (each may be NULL); VDB_ERR_ARG on a write above
+ * the fill, n_db == 0, n_c > n_db or a recorded slot >= n_db.
+ * _size takes the number of appends in place of the indices (the shape of every batch with as many) and returns the g_c and g_db it
+ * would pick; each of its outputs may be NULL.
+ *
+ * vdb_ann_index_write_dev (values only, functional; the old buffers are only read): both resident objects after the batch.  The index
+ * is vdb_ann_index_apply_dev's (its four launches), the appends at database slots n, n + 1, ... in append order; db_tree_out (2 * the
+ * grown padded leaf count digests, db_digests of _size) is updated_db_levels copied device to device: the new index's database tree, no
+ * vector or node hashed again.  Its refusals are vdb_ann_index_apply_dev's (n_db is the sum of the sizes) and a grow_db that is not the
+ * smallest that fits.  vdb_ann_index_write_size: the appends, g_c, g_db, the digests of the new forest, its K + 2 segment offsets and
+ * the digests of the database tree (each may be NULL). */
+int vdb_wit_ann_write_size(size_t K, size_t n_c, size_t n_db, size_t dim, size_t m, size_t appends, uint64_t *cells, uint64_t *input_cells,
+                           uint64_t *update_base, uint64_t *update_db_base, unsigned *grow_c, unsigned *grow_db);
+int vdb_ann_write_db_indices(const uint64_t *cluster_slots /* host */, size_t n_c, size_t n_db, const uint64_t *indices /* host */, size_t m,
+                             uint64_t *db_indices /* host, m */, uint64_t *appends, unsigned *grow_db);
+int vdb_wit_ann_write(vdb_fr *levels_c, vdb_fr *levels_db, const vdb_fr *roots, size_t K, size_t cluster, size_t n_c, size_t n_db, size_t dim,
+                      unsigned grow_c, unsigned grow_db, const vdb_fr *new_vectors, const uint64_t *indices, const uint64_t *db_indices, size_t m,
+                      vdb_fr *stream_out, uint8_t *selector_out, vdb_fr *public_out);
+int vdb_wit_ann_write_dev(vdb_fr *levels_c_dev, vdb_fr *levels_db_dev, const vdb_fr *roots_dev, size_t K, size_t cluster, size_t n_c, size_t n_db,
+                          size_t dim, unsigned grow_c, unsigned grow_db, const vdb_fr *new_vectors_dev, const uint64_t *indices /* host */,
+                          const uint64_t *db_indices /* host */, size_t m, vdb_fr *stream_dev, uint8_t *selector_dev, vdb_fr *public_dev);
+int vdb_ann_index_write_size(const uint64_t *cluster_sizes /* host */, size_t K, size_t cluster, const uint64_t *indices /* host */, size_t m,
+                             uint64_t *appends, unsigned *grow_c, unsigned *grow_db, uint64_t *digests, uint64_t *segment_offsets,
+                             uint64_t *db_digests);
+int vdb_ann_index_write_dev(const vdb_fr *grouped_dev, const uint32_t *slots_dev, const vdb_fr *forest_dev, const vdb_fr *roots_dev,
+                            const uint64_t *cluster_sizes /* host */, size_t K, size_t dim, size_t cluster, unsigned grow_c, unsigned grow_db,
+                            const vdb_fr *updated_levels_dev, const vdb_fr *updated_db_levels_dev, const vdb_fr *new_vectors_dev,
+                            const uint64_t *indices /* host */, size_t m, vdb_fr *grouped_out_dev, uint32_t *slots_out_dev,
+                            uint64_t *offsets_out_dev, vdb_fr *forest_out_dev, vdb_fr *roots_out_dev, vdb_fr *db_tree_out_dev);
+
 /* The audit of one cluster's routing: in the index with root index_root, every member committed under cluster_root_c is at least as
  * close to centroid c as to any other committed centroid, in the circuit's fixed-point distance for `metric`.  It covers the build's
  * cluster ids and the writes after them alike (audit cluster c of the index a batch into c leaves); K such proofs cover an index.  It

@@ -28,6 +28,12 @@ above — AnnQueryHotPath is AnnProbeQueryHotPath at these.
 (pipeline.AnnUpdateHotPath: the first write replaces member 0 of the largest cluster, the others append to it; [index_root_old | c | idx, old
 leaf, new leaf per write | index_root_new] public; `--grow` defaults to the smallest number of doublings that fits the appends), has the
 verifier check the proof and applies the batch to the resident index (AnnIndex.updated), whose root must be the public index_root_new.
+`--circuit ann-write --K C --updates M [--appends A]` proves a linked write: M writes into the largest cluster of that index AND the same
+M leaf changes in the database tree, in one proof (pipeline.AnnWriteHotPath: the first M - A writes replace members 0, 1, .., the last A
+append — default: all but the first; [database_root_old | index_root_old | c | idx, db idx, old leaf, new leaf per write |
+database_root_new | index_root_new] public), has the verifier check the proof and writes the batch to the resident index
+(AnnIndex.written), whose root must be the public index_root_new and whose database tree must be the tree builder's over the updated
+rows with the public database_root_new.  Exit status 0 when all of that holds.
 `--circuit ann-delete --K C --deletes M` proves M deletes from the largest cluster of that index (pipeline.AnnDeleteHotPath: slot 0 again and
 again, so every delete but the first removes the member the one before moved there; the last member moves into the slot and the cluster's
 tree halves when the fill drops to a power of two; [index_root_old | c | slot, removed leaf, last, moved leaf per delete | index_root_new]
@@ -61,7 +67,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from halo2_vectordb_amd import api  # noqa: E402
-from halo2_vectordb_amd.pipeline import AnnAuditHotPath, AnnCoverHotPath, AnnDeleteHotPath, AnnMeanHotPath, AnnMoveHotPath, AnnRecentreHotPath, AnnIndex, AnnProbeQueryHotPath, AnnUpdateHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
+from halo2_vectordb_amd.pipeline import AnnAuditHotPath, AnnCoverHotPath, AnnDeleteHotPath, AnnMeanHotPath, AnnMoveHotPath, AnnRecentreHotPath, AnnIndex, AnnProbeQueryHotPath, AnnUpdateHotPath, AnnWriteHotPath, BatchQueryHotPath, MerkleHotPath, QueryHotPath, ReadHotPath, TopKQueryHotPath, UpdateHotPath  # noqa: E402
 from halo2_vectordb_amd.rounds import ProverRounds, quotient_identity_holds  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -72,13 +78,14 @@ ap.add_argument("--seed", type=int, default=20260003)
 ap.add_argument("--block-cols", type=int, default=510)
 ap.add_argument("--ext-block-cols", type=int, default=None)
 ap.add_argument("--proofs", type=int, default=2)
-ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read", "ann", "ann-update", "ann-delete", "ann-move", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"])
+ap.add_argument("--circuit", default="merkle", choices=["merkle", "query", "update", "read", "ann", "ann-update", "ann-write", "ann-delete", "ann-move", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"])
 ap.add_argument("--lookup-bits", type=int, default=13)
 ap.add_argument("--metric", default="euclidean")
 ap.add_argument("--queries", type=int, default=1, help="--circuit query: queries proved against the one database in this proof")
 ap.add_argument("--topk", type=int, default=1, help="--circuit query / ann: nearest vectors proved per query, nearest first")
 ap.add_argument("--probes", type=int, default=1, help="--circuit ann: clusters searched, the nearest centroids' in the order the top-k rounds state them")
 ap.add_argument("--updates", type=int, default=8, help="--circuit update: inserts / replacements proved in this proof")
+ap.add_argument("--appends", type=int, default=None, help="--circuit ann-write: the last A writes append (default: all but the first)")
 ap.add_argument("--deletes", type=int, default=0, help="--circuit update: the last K updates empty their slot instead of writing it; --circuit ann-delete: deletes proved")
 ap.add_argument("--moves", type=int, default=8, help="--circuit ann-move: members moved in this proof")
 ap.add_argument("--src", type=int, default=None, help="--circuit ann-move: the cluster the members leave (default: the largest)")
@@ -112,7 +119,7 @@ elif args.circuit == "update":
         raise SystemExit("--deletes is between 0 and --updates, --grow is not negative")
     kinds = [0] * (args.updates - args.deletes) + [1] * args.deletes
     hp = UpdateHotPath(n=args.n, dim=args.dim, m=args.updates, k=args.k, seed=args.seed, kinds=kinds, grow=args.grow)
-elif args.circuit in ("ann", "ann-update", "ann-delete", "ann-move", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"):
+elif args.circuit in ("ann", "ann-update", "ann-write", "ann-delete", "ann-move", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"):
     from halo2_vectordb_amd.pipeline import sift_like_vectors
     if not 1 <= args.K <= args.n:
         raise SystemExit("--K is between 1 and --n")
@@ -159,6 +166,13 @@ elif args.circuit in ("ann", "ann-update", "ann-delete", "ann-move", "ann-audit"
         if not 1 <= args.deletes < int(index.sizes[c]):
             raise SystemExit("--deletes is at least 1 and leaves the largest cluster a member")
         hp = AnnDeleteHotPath(index, c, [0] * args.deletes, k=args.k)
+    elif args.circuit == "ann-write":
+        c = int(np.argmax(index.sizes))
+        app = args.updates - 1 if args.appends is None else args.appends
+        if not 0 <= app <= args.updates or args.updates - app > int(index.sizes[c]) or args.updates < 1:
+            raise SystemExit("--appends is between 0 and --updates, and the replacements fit the largest cluster")
+        slots = list(range(args.updates - app)) + [int(index.sizes[c]) + i for i in range(app)]
+        hp = AnnWriteHotPath(index, c, (slots, sift_like_vectors(seed + 2000, args.updates, args.dim)[0]), k=args.k)
     else:
         c = int(np.argmax(index.sizes))
         slots = [0] + [int(index.sizes[c]) + i for i in range(args.updates - 1)]
@@ -198,12 +212,21 @@ if args.out:
     write_snark(args.out, out["proof"], out["instances"])
     pr.save_verifying_key(args.out + ".vk.npz", opened=out["opened"])
 accepted = {}
-if args.circuit in ("read", "ann", "ann-update", "ann-delete", "ann-move", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"):
+if args.circuit in ("read", "ann", "ann-update", "ann-write", "ann-delete", "ann-move", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"):
     from halo2_vectordb_amd import verifier
     accepted = {"proof_accepted": bool(verifier.verify(out["proof"], out["instances"], verifier.VerifyingKey.from_prover(pr, out["opened"])))}
 if args.circuit == "ann-update":
     index2 = index.updated(hp)
     accepted["applied_index_root_is_the_public_new_root"] = bool(np.array_equal(index2.roots()[-1], hp.results()[-1]))
+    index2.free()
+if args.circuit == "ann-write":
+    index2 = index.written(hp)
+    tree2 = index2.database_tree().download((2 * api.merkle_levels(index2.n)[0], 4))
+    accepted["written_index_root_is_the_public_new_root"] = bool(np.array_equal(index2.roots()[-1], hp.results()[-1]))
+    accepted["database_tree_is_the_tree_builders"] = bool(np.array_equal(tree2, api.merkle_tree_build(index2.qvec)))
+    accepted["database_root_is_the_public_new_root"] = bool(np.array_equal(tree2[-2], hp.results()[-2]))
+    accepted["old_roots_are_the_indexs"] = bool(np.array_equal(hp.results()[1], index.roots()[-1]) and
+                                                np.array_equal(hp.results()[0], api.poseidon_merkle_root(index.qvec)))
     index2.free()
 if multi_probe:
     accepted["neighbours"] = hp.neighbours().tolist()
@@ -235,6 +258,7 @@ what = f"merkle_commitment {args.n}x{args.dim} k={args.k}" if args.circuit == "m
     f"ann query (K={args.K}, the {args.topk} nearest of the {hp.n} vectors of clusters {hp.clusters}, {args.metric}) against the index of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if multi_probe else \
     f"ann query (K={args.K}, cluster {hp.clusters[0]} of {hp.n} vectors, {args.metric}) against the index of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann" else \
     f"{args.updates} writes into cluster {hp.cluster} ({hp.n} members, tree grown {hp.grow} times) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-update" else \
+    f"{args.updates} linked writes ({hp.appends} appends) into cluster {hp.cluster} ({hp.n} members, tree grown {hp.grow} times) and the database tree (grown {hp.grow_db} times) against both roots (K={args.K}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-write" else \
     f"routing audit of cluster {hp.cluster} ({hp.n} members, {args.metric}) against the index root (K={args.K}) of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann-audit" else \
     f"recentre of cluster {hp.cluster} ({hp.n} members) from the old index root to the new (K={args.K}) of {args.n}x{args.dim}, k={args.k}, LOOKUP_BITS={args.lookup_bits}" if args.circuit == "ann-recentre" else \
     f"cover of the database by the index (K={args.K}, cluster sizes {int(index.sizes.min())} .. {int(index.sizes.max())}) of {args.n}x{args.dim}, k={args.k}" if args.circuit == "ann-cover" else \
@@ -251,13 +275,15 @@ print(json.dumps({"workload": what + ": whole constraint map, public outputs in 
                   "block_cols": args.block_cols, "ext_cols_held": hp.ext_cols}))
 pr.free()
 hp.free()
-if args.circuit in ("ann", "ann-update", "ann-delete", "ann-move", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"):
+if args.circuit in ("ann", "ann-update", "ann-write", "ann-delete", "ann-move", "ann-audit", "ann-mean", "ann-recentre", "ann-cover"):
     index.free()
 if args.circuit == "ann-cover" and not (accepted["database_root_is_the_tree_builders"] and accepted["index_root_is_the_indexs"]):
     sys.exit(1)
 if args.circuit in ("ann-audit", "ann-mean", "ann-recentre", "ann-cover") and not accepted["proof_accepted"]:
     sys.exit(1)
 if args.circuit == "ann-recentre" and not accepted["recentred_root_is_public_root"]:
+    sys.exit(1)
+if args.circuit == "ann-write" and not all(accepted.values()):
     sys.exit(1)
 if args.circuit == "ann-move" and not (accepted["proof_accepted"] and accepted["moved_index_root_is_the_public_new_root"] and accepted["database_tree_is_unchanged"]):
     sys.exit(1)
