@@ -682,13 +682,14 @@ def ann_cluster_means(grouped, offsets, P=48, L=13):
     return means
 
 
-def _wit_ann_batch(levels, cells, n_pub, selectors, call, **sizes):
-    """the buffers of a host-array call against the index root and its dict: call(levels, stream, selectors or None, public) -> its code"""
-    levels = np.array(levels, dtype=np.uint64, copy=True)
+def _wit_ann_batch(trees, cells, n_pub, selectors, call, **sizes):
+    """the buffers of a host-array call against the index root and its dict: `trees` the trees the call edits in place, by their key in
+    the dict (copied first); call(*trees, stream, selectors or None, public) -> its code"""
+    trees = {key: np.array(lv, dtype=np.uint64, copy=True) for key, lv in trees.items()}
     stream, pub = np.zeros((cells, 4), dtype=np.uint64), np.zeros((n_pub, 4), dtype=np.uint64)
     sel = np.zeros(cells, dtype=np.uint8) if selectors else None
-    check(call(_p(levels), _p(stream), _p(sel) if selectors else None, _p(pub)))
-    return dict(stream=stream, **_split_flags(sel), **sizes, public=pub, levels=levels)
+    check(call(*[_p(lv) for lv in trees.values()], _p(stream), _p(sel) if selectors else None, _p(pub)))
+    return dict(stream=stream, **_split_flags(sel), **sizes, public=pub, **trees)
 
 
 def wit_ann_update(levels, roots, cluster, n_c, new_vectors, indices, grow=0, selectors=False):
@@ -706,7 +707,7 @@ def wit_ann_update(levels, roots, cluster, n_c, new_vectors, indices, grow=0, se
     check(lib.vdb_wit_ann_update_size(_sz(K), _sz(n_c), _sz(dim), _sz(m), int(grow), ctypes.byref(cells), ctypes.byref(n_in), ctypes.byref(ub)))
     call = lambda lv, st, sl, pb: lib.vdb_wit_ann_update(lv, _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(dim), int(grow), _p(new_vectors), _p(idx),
                                                          _sz(m), st, sl, pb)
-    return _wit_ann_batch(levels, cells.value, 3 * m + 3, selectors, call, input_cells=n_in.value, update_base=ub.value)
+    return _wit_ann_batch(dict(levels=levels), cells.value, 3 * m + 3, selectors, call, input_cells=n_in.value, update_base=ub.value)
 
 
 def ann_index_apply_layout(sizes, cluster, grow, indices):
@@ -721,6 +722,27 @@ def ann_index_apply_layout(sizes, cluster, grow, indices):
     return appends.value, digests.value, seg
 
 
+def _ann_index_run(src, n2, dim, K, digests, seg, call, db_digests=0):
+    """the buffers of a host-array transition of the index and its dict: `src` the arrays the call reads, uploaded; n2 rows, `digests` and
+    `seg` the shape of the index after it; `db_digests`: digests of the database tree the call writes too (0: none, no db_tree in the
+    dict); call(ins, outs): the library call on the device pointers of `src` and of the outputs [grouped | slots | offsets | forest |
+    roots | database tree] -> its code"""
+    ins = [DeviceBuffer(max(a.nbytes, 32)) for a in src]
+    outs = [DeviceBuffer(max(b, 32)) for b in (n2 * dim * 32, n2 * 4, (K + 1) * 8, digests * 32, (K + 2) * 32) + ((db_digests * 32,) if db_digests else ())]
+    try:
+        for b, a in zip(ins, src):
+            b.upload(np.ascontiguousarray(a))
+        check(call([b.ptr for b in ins], [o.ptr for o in outs]))
+        out = dict(grouped=outs[0].download((n2, dim, 4)), slots=outs[1].download((n2,), dtype=np.uint32), offsets=outs[2].download((K + 1,), dtype=np.uint64),
+                   forest=outs[3].download((digests, 4)), segments=seg, roots=outs[4].download((K + 2, 4)))
+        if db_digests:
+            out["db_tree"] = outs[5].download((db_digests, 4))
+        return out
+    finally:
+        for b in ins + outs:
+            b.free()
+
+
 def ann_index_apply(index, cluster, grow, updated_levels, new_vectors, indices, db_slots):
     """the index after a batch of writes into one cluster (vdb_ann_index_apply_dev), host arrays in and out: `index` an ann_index_build
     dict, updated_levels the cluster's tree the witness call left, db_slots one database slot per append -> a dict of the same form"""
@@ -732,20 +754,10 @@ def ann_index_apply(index, cluster, grow, updated_levels, new_vectors, indices, 
     K, dim, n = sizes.shape[0], new_vectors.shape[1], index["grouped"].shape[0]
     appends, digests, seg = ann_index_apply_layout(sizes, cluster, grow, idx)
     assert slots_new.shape == (appends,) and idx.shape == (new_vectors.shape[0],)
-    n2 = n + appends
     src = [index["grouped"], np.ascontiguousarray(index["slots"], dtype=np.uint32), index["forest"], index["roots"], updated, new_vectors]
-    ins = [DeviceBuffer(max(a.nbytes, 32)) for a in src]
-    outs = [DeviceBuffer(max(b, 32)) for b in (n2 * dim * 32, n2 * 4, (K + 1) * 8, digests * 32, (K + 2) * 32)]
-    try:
-        for b, a in zip(ins, src):
-            b.upload(np.ascontiguousarray(a))
-        check(lib.vdb_ann_index_apply_dev(ins[0].ptr, ins[1].ptr, ins[2].ptr, ins[3].ptr, _p(sizes), _sz(K), _sz(dim), _sz(cluster), int(grow), ins[4].ptr,
-                                          ins[5].ptr, _p(idx), _p(slots_new) if appends else None, _sz(idx.shape[0]), *[o.ptr for o in outs]))
-        return dict(grouped=outs[0].download((n2, dim, 4)), slots=outs[1].download((n2,), dtype=np.uint32), offsets=outs[2].download((K + 1,), dtype=np.uint64),
-                    forest=outs[3].download((digests, 4)), segments=seg, roots=outs[4].download((K + 2, 4)))
-    finally:
-        for b in ins + outs:
-            b.free()
+    call = lambda ins, outs: lib.vdb_ann_index_apply_dev(*ins[:4], _p(sizes), _sz(K), _sz(dim), _sz(cluster), int(grow), ins[4], ins[5], _p(idx),
+                                                         _p(slots_new) if appends else None, _sz(idx.shape[0]), *outs)
+    return _ann_index_run(src, n + appends, dim, K, digests, seg, call)
 
 
 def ann_write_db_indices(cluster_slots, indices, n_db):
@@ -778,15 +790,12 @@ def wit_ann_write(levels_c, levels_db, roots, cluster, n_c, n_db, new_vectors, i
     check(lib.vdb_wit_ann_write_size(_sz(K), _sz(n_c), _sz(n_db), _sz(dim), _sz(m), _sz(fill - n_c), ctypes.byref(cells), ctypes.byref(n_in), ctypes.byref(ub),
                                      ctypes.byref(udb), ctypes.byref(gc), ctypes.byref(gdb)))
     grow_c, grow_db = gc.value if grow_c is None else int(grow_c), gdb.value if grow_db is None else int(grow_db)
-    lc, ld = np.array(levels_c, dtype=np.uint64, copy=True), np.array(levels_db, dtype=np.uint64, copy=True)
     assert idx.shape == (m,) and dbi.shape == (m,) and new_vectors.shape[0] == m
-    assert lc.shape == (2 * (merkle_levels(n_c)[0] << grow_c), 4) and ld.shape == (2 * (merkle_levels(n_db)[0] << grow_db), 4)
-    stream, pub = np.zeros((cells.value, 4), dtype=np.uint64), np.zeros((4 * m + 5, 4), dtype=np.uint64)
-    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
-    check(lib.vdb_wit_ann_write(_p(lc), _p(ld), _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(n_db), _sz(dim), grow_c, grow_db, _p(new_vectors), _p(idx),
-                                _p(dbi), _sz(m), _p(stream), _p(sel) if selectors else None, _p(pub)))
-    return dict(stream=stream, **_split_flags(sel), input_cells=n_in.value, update_base=ub.value, update_db_base=udb.value, grow_c=grow_c, grow_db=grow_db,
-                public=pub, levels_c=lc, levels_db=ld)
+    assert np.shape(levels_c) == (2 * (merkle_levels(n_c)[0] << grow_c), 4) and np.shape(levels_db) == (2 * (merkle_levels(n_db)[0] << grow_db), 4)
+    call = lambda lc, ld, st, sl, pb: lib.vdb_wit_ann_write(lc, ld, _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(n_db), _sz(dim), grow_c, grow_db,
+                                                            _p(new_vectors), _p(idx), _p(dbi), _sz(m), st, sl, pb)
+    return _wit_ann_batch(dict(levels_c=levels_c, levels_db=levels_db), cells.value, 4 * m + 5, selectors, call, input_cells=n_in.value,
+                          update_base=ub.value, update_db_base=udb.value, grow_c=grow_c, grow_db=grow_db)
 
 
 def ann_index_write_layout(sizes, cluster, indices):
@@ -813,20 +822,10 @@ def ann_index_write(index, cluster, updated_levels, updated_db_levels, new_vecto
     appends, gc, gdb, digests, seg, dbd = ann_index_write_layout(sizes, cluster, idx)
     grow_c, grow_db = gc if grow_c is None else int(grow_c), gdb if grow_db is None else int(grow_db)
     assert idx.shape == (new_vectors.shape[0],)
-    n2 = n + appends
     src = [index["grouped"], np.ascontiguousarray(index["slots"], dtype=np.uint32), index["forest"], index["roots"], uc, ud, new_vectors]
-    ins = [DeviceBuffer(max(a.nbytes, 32)) for a in src]
-    outs = [DeviceBuffer(max(b, 32)) for b in (n2 * dim * 32, n2 * 4, (K + 1) * 8, digests * 32, (K + 2) * 32, ud.nbytes)]
-    try:
-        for b, a in zip(ins, src):
-            b.upload(np.ascontiguousarray(a))
-        check(lib.vdb_ann_index_write_dev(ins[0].ptr, ins[1].ptr, ins[2].ptr, ins[3].ptr, _p(sizes), _sz(K), _sz(dim), _sz(cluster), grow_c, grow_db,
-                                          ins[4].ptr, ins[5].ptr, ins[6].ptr, _p(idx), _sz(idx.shape[0]), *[o.ptr for o in outs]))
-        return dict(grouped=outs[0].download((n2, dim, 4)), slots=outs[1].download((n2,), dtype=np.uint32), offsets=outs[2].download((K + 1,), dtype=np.uint64),
-                    forest=outs[3].download((digests, 4)), segments=seg, roots=outs[4].download((K + 2, 4)), db_tree=outs[5].download((ud.shape[0], 4)))
-    finally:
-        for b in ins + outs:
-            b.free()
+    call = lambda ins, outs: lib.vdb_ann_index_write_dev(*ins[:4], _p(sizes), _sz(K), _sz(dim), _sz(cluster), grow_c, grow_db, ins[4], ins[5], ins[6],
+                                                         _p(idx), _sz(idx.shape[0]), *outs)
+    return _ann_index_run(src, n + appends, dim, K, digests, seg, call, db_digests=ud.shape[0])
 
 
 def wit_ann_delete(levels, roots, cluster, n_c, dim, slots, selectors=False):
@@ -844,7 +843,7 @@ def wit_ann_delete(levels, roots, cluster, n_c, dim, slots, selectors=False):
     check(lib.vdb_wit_ann_delete_size(_sz(K), _sz(n_c), _sz(dim), _sz(m), ctypes.byref(cells), ctypes.byref(n_in), ctypes.byref(ub), ctypes.byref(sb),
                                       ctypes.byref(s)))
     call = lambda lv, st, sl, pb: lib.vdb_wit_ann_delete(lv, _p(roots), _sz(K), _sz(cluster), _sz(n_c), _sz(dim), _p(idx), _sz(m), st, sl, pb)
-    return _wit_ann_batch(levels, cells.value, 4 * m + 3, selectors, call, input_cells=n_in.value, update_base=ub.value, shrink_base=sb.value, shrink=s.value)
+    return _wit_ann_batch(dict(levels=levels), cells.value, 4 * m + 3, selectors, call, input_cells=n_in.value, update_base=ub.value, shrink_base=sb.value, shrink=s.value)
 
 
 def ann_index_remove_layout(sizes, cluster, slots):
@@ -868,20 +867,9 @@ def ann_index_remove(index, cluster, updated_levels, slots):
     sizes = np.diff(np.asarray(index["offsets"], dtype=np.uint64)).astype(np.uint64)
     K, dim, n, m = sizes.shape[0], index["grouped"].shape[1], index["grouped"].shape[0], idx.shape[0]
     _, digests, seg = ann_index_remove_layout(sizes, cluster, idx)
-    n2 = n - m
     src = [index["grouped"], index["forest"], index["roots"], updated]
-    ins = [DeviceBuffer(max(a.nbytes, 32)) for a in src]
-    outs = [DeviceBuffer(max(b, 32)) for b in (n2 * dim * 32, n2 * 4, (K + 1) * 8, digests * 32, (K + 2) * 32)]
-    try:
-        for b, a in zip(ins, src):
-            b.upload(np.ascontiguousarray(a))
-        check(lib.vdb_ann_index_remove_dev(ins[0].ptr, ins[1].ptr, ins[2].ptr, _p(sizes), _sz(K), _sz(dim), _sz(cluster), ins[3].ptr, _p(idx), _sz(m),
-                                           *[o.ptr for o in outs]))
-        return dict(grouped=outs[0].download((n2, dim, 4)), slots=outs[1].download((n2,), dtype=np.uint32), offsets=outs[2].download((K + 1,), dtype=np.uint64),
-                    forest=outs[3].download((digests, 4)), segments=seg, roots=outs[4].download((K + 2, 4)))
-    finally:
-        for b in ins + outs:
-            b.free()
+    call = lambda ins, outs: lib.vdb_ann_index_remove_dev(*ins[:3], _p(sizes), _sz(K), _sz(dim), _sz(cluster), ins[3], _p(idx), _sz(m), *outs)
+    return _ann_index_run(src, n - m, dim, K, digests, seg, call)
 
 
 def wit_ann_move(levels_src, levels_dst, roots, src, dst, n_a, n_b, slots, grow=None, selectors=False):
@@ -899,14 +887,10 @@ def wit_ann_move(levels_src, levels_dst, roots, src, dst, n_a, n_b, slots, grow=
     check(lib.vdb_wit_ann_move_size(_sz(K), _sz(n_a), _sz(n_b), _sz(m), ctypes.byref(cells), ctypes.byref(n_in), ctypes.byref(db), ctypes.byref(sb),
                                     ctypes.byref(ab), ctypes.byref(s), ctypes.byref(g)))
     grow = g.value if grow is None else int(grow)
-    la, lb = np.array(levels_src, dtype=np.uint64, copy=True), np.array(levels_dst, dtype=np.uint64, copy=True)
-    assert idx.shape == (m,) and la.shape == (2 * merkle_levels(n_a)[0], 4) and lb.shape == (2 * (merkle_levels(n_b)[0] << grow), 4)
-    stream, pub = np.zeros((cells.value, 4), dtype=np.uint64), np.zeros((6 * m + 4, 4), dtype=np.uint64)
-    sel = np.zeros(cells.value, dtype=np.uint8) if selectors else None
-    check(lib.vdb_wit_ann_move(_p(la), _p(lb), _p(roots), _sz(K), _sz(src), _sz(dst), _sz(n_a), _sz(n_b), grow, _p(idx), _sz(m), _p(stream),
-                               _p(sel) if selectors else None, _p(pub)))
-    return dict(stream=stream, **_split_flags(sel), input_cells=n_in.value, delete_base=db.value, shrink_base=sb.value, append_base=ab.value,
-                shrink=s.value, grow=g.value, public=pub, levels_src=la, levels_dst=lb)
+    assert idx.shape == (m,) and np.shape(levels_src) == (2 * merkle_levels(n_a)[0], 4) and np.shape(levels_dst) == (2 * (merkle_levels(n_b)[0] << grow), 4)
+    call = lambda la, lb, st, sl, pb: lib.vdb_wit_ann_move(la, lb, _p(roots), _sz(K), _sz(src), _sz(dst), _sz(n_a), _sz(n_b), grow, _p(idx), _sz(m), st, sl, pb)
+    return _wit_ann_batch(dict(levels_src=levels_src, levels_dst=levels_dst), cells.value, 6 * m + 4, selectors, call, input_cells=n_in.value,
+                          delete_base=db.value, shrink_base=sb.value, append_base=ab.value, shrink=s.value, grow=g.value)
 
 
 def ann_index_move_layout(sizes, src, dst, slots):
@@ -934,18 +918,9 @@ def ann_index_move(index, src, dst, updated_src, updated_dst, slots, grow=None):
     _, g, digests, seg = ann_index_move_layout(sizes, src, dst, idx)
     grow = g if grow is None else int(grow)
     src_arrays = [index["grouped"], np.ascontiguousarray(index["slots"], dtype=np.uint32), index["forest"], index["roots"], ua, ub]
-    ins = [DeviceBuffer(max(a.nbytes, 32)) for a in src_arrays]
-    outs = [DeviceBuffer(max(b, 32)) for b in (n * dim * 32, n * 4, (K + 1) * 8, digests * 32, (K + 2) * 32)]
-    try:
-        for b, a in zip(ins, src_arrays):
-            b.upload(np.ascontiguousarray(a))
-        check(lib.vdb_ann_index_move_dev(ins[0].ptr, ins[1].ptr, ins[2].ptr, ins[3].ptr, _p(sizes), _sz(K), _sz(dim), _sz(src), _sz(dst), grow, ins[4].ptr,
-                                         ins[5].ptr, _p(idx), _sz(m), *[o.ptr for o in outs]))
-        return dict(grouped=outs[0].download((n, dim, 4)), slots=outs[1].download((n,), dtype=np.uint32), offsets=outs[2].download((K + 1,), dtype=np.uint64),
-                    forest=outs[3].download((digests, 4)), segments=seg, roots=outs[4].download((K + 2, 4)))
-    finally:
-        for b in ins + outs:
-            b.free()
+    call = lambda ins, outs: lib.vdb_ann_index_move_dev(*ins[:4], _p(sizes), _sz(K), _sz(dim), _sz(src), _sz(dst), grow, ins[4], ins[5], _p(idx), _sz(m),
+                                                        *outs)
+    return _ann_index_run(src_arrays, n, dim, K, digests, seg, call)
 
 
 def wit_merkle_open(levels, n, indices, vectors=None, selectors=False):

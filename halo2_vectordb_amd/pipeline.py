@@ -198,7 +198,8 @@ class HotPath:
     """The HBM-resident driver of one circuit on one GPU (or one rank's block of its columns): witness -> layout -> commit -> NTT.
     Circuit neutral: a circuit class states its inputs and sizes (_input_vectors, n_input_rows, _circuit_size), its outputs
     (_alloc_outputs, registered with _output), the gadget calls that emit its cells after the input rows (_emit), what it makes
-    public (public_values_dev), what it returns (results) and its constraint map (constraint_map)."""
+    public (public_values_dev), what it returns (results) and its constraint map (_map_builder, or constraint_map itself where the
+    map is not one build_* call over the readers)."""
 
     def __init__(self, n, dim, k, P, L, seed=None, tau=None, col_shard=(0, 1), vectors=None, blind_seed=None, params=None):
         """`tau`: toxic-waste scalar of the "unsafe" SRS as a canonical integer; None = the scalar the reference's
@@ -449,17 +450,28 @@ class HotPath:
 
     def public_values_dev(self):
         """(device pointer, count) of the values the reference's example of this circuit makes public, in make_public order.  Every
-        rank computes them (value-only walk), whichever rank's columns hold the cells."""
-        raise NotImplementedError
+        rank computes them (value-only walk), whichever rank's columns hold the cells.  As it stands: the public row `d_pub` of
+        `n_public` values the witness call of the circuit fills."""
+        return self.d_pub.ptr, self.n_public
 
     def results(self):
+        raise NotImplementedError
+
+    def _map_builder(self, CS):
+        """(circuit_sym's build function of the circuit, its shape arguments ahead of the readers, its keywords behind the builder)"""
         raise NotImplementedError
 
     def constraint_map(self, d_flags, on_device=True):
         """(the circuit's constraint map (circuit_sym.CopyMap over the stream cells), the cells its example makes public in make_public
         order, the stream cell of its Merkle root or None).  d_flags: the flags of a keygen-style run (keygen_flags); on_device: let the
-        device place the map of a large circuit (circuit_dev.py) instead of the host."""
-        raise NotImplementedError
+        device place the map of a large circuit (circuit_dev.py) instead of the host.  As it stands: the map of _map_builder, which reads
+        the flags and the cells of the stream, over every cell, with no root cell."""
+        from . import circuit_sym as CS
+        from .circuit_dev import DeviceBuilder
+        build, shape, kw = self._map_builder(CS)
+        cm, public = build(*shape, functools.partial(self._fetch_flags, d_flags), self._fetch, builder=DeviceBuilder if on_device else None, **kw)[:2]
+        assert cm.n_cells == self.n_cells
+        return cm, public, None
 
     # ------------------------------------------------------------------ helpers of the circuits
     def _output(self, nbytes):
@@ -467,6 +479,26 @@ class HotPath:
         buf = api.DeviceBuffer(nbytes)
         self._outputs.append(buf)
         return buf
+
+    def _load_tree(self, d_out, lp, levels):
+        """The resident tree over the n database vectors (api.merkle_tree_build's layout, 2 lp digests) into d_out: `levels` a
+        DeviceBuffer (copied), a (2 lp, 4) array (uploaded), or None: built from self.database_f64."""
+        if isinstance(levels, api.DeviceBuffer):
+            check(self.lib.vdb_memcpy_d2d(d_out.ptr, levels.ptr, ctypes.c_size_t(2 * lp * B)))
+        elif levels is not None:
+            levels = np.ascontiguousarray(levels, dtype=np.uint64)
+            assert levels.shape == (2 * lp, 4), "the tree does not belong to this shape"
+            d_out.upload(levels)
+        else:
+            assert self.database_f64.shape == (self.n, self.dim), "database rows do not match the circuit's shape"
+            qdb = api.quantize(self.database_f64, self.P)
+            d_db = api.DeviceBuffer(qdb.nbytes)
+            try:
+                d_db.upload(qdb)
+                check(self.lib.vdb_merkle_tree_build_dev(d_db.ptr, self.n, self.dim, d_out.ptr))
+                api.sync()
+            finally:
+                d_db.free()
 
     @staticmethod
     def _sel_at(sel, at):
@@ -670,6 +702,41 @@ def _merkle_trace(hp, d_vectors, at, sel):
         check(hp.lib.vdb_wit_merkle_dev(d_vectors, hp.n, hp.dim, 0, hp.d_stream.at(at * B), hp._sel_at(sel, at), hp.d_root.ptr))
 
 
+class _EditedTree:
+    """A tree the witness call of hot path `hp` edits in place: `before`, the tree before the batch, grown `grow` doublings from its lp0
+    padded leaves over n vectors, and `working`, the copy every witness run works on; both outputs of `hp`.  `levels`: the tree not yet
+    grown, as HotPath._load_tree takes it."""
+
+    def __init__(self, hp, lp0, grow, n, levels):
+        self.lib, self.nbytes = hp.lib, 2 * (lp0 << grow) * B
+        self.before, self.working = hp._output(self.nbytes), hp._output(self.nbytes)
+        # a tree that has yet to be grown into `before` waits in `working`, which every run overwrites
+        hp._load_tree(self.working if grow else self.before, lp0, levels)
+        if grow:
+            check(self.lib.vdb_merkle_tree_grow_dev(self.working.ptr, n, grow, self.before.ptr))
+            api.sync()
+
+    def reset(self):
+        """every run starts from the tree before the batch, so that the keygen-style runs and the proof state the same batch"""
+        check(self.lib.vdb_memcpy_d2d(self.working.ptr, self.before.ptr, ctypes.c_size_t(self.nbytes)))
+
+
+def _swap_with_last(n, slots, what):
+    """Deletes from the dense members 0 .. n - 1 replayed: delete j moves the member at n - j - 1 into slots[j] and empties the last slot.
+    -> (origin (n - m,): the slot that held, before the batch, the member at surviving position p; moved_from (m,): the slot that held,
+    before the batch, the member delete j takes away).  `what`: the caller's words for (a delete, the members) in the refusals."""
+    kind, where = what
+    if not 1 <= len(slots) < n:
+        raise ValueError("a batch holds at least one " + kind + " and leaves at least one member")
+    origin, moved_from = list(range(n)), []
+    for j, s in enumerate(slots):
+        if s >= n - j:
+            raise ValueError("a slot at or above the " + where + "'s fill at its turn")
+        moved_from.append(origin[s])
+        origin[s] = origin[n - j - 1]
+    return origin[:n - len(slots)], moved_from
+
+
 class KmeansHotPath(HotPath):
     """kmeans::<K, I> over N x D vectors at 2^k rows: witness -> layout -> commit -> NTT, one GPU."""
 
@@ -724,26 +791,6 @@ class PoseidonHotPath(HotPath):
         self.balance_shards = False
         self.msm_window_bits = 14   # nearly every scalar is a full-width Poseidon state: 19 windows instead of 24
 
-    def _load_tree(self, d_out, lp, levels):
-        """The resident tree over the n database vectors (api.merkle_tree_build's layout, 2 lp digests) into d_out: `levels` a
-        DeviceBuffer (copied), a (2 lp, 4) array (uploaded), or None: built from self.database_f64."""
-        if isinstance(levels, api.DeviceBuffer):
-            check(self.lib.vdb_memcpy_d2d(d_out.ptr, levels.ptr, ctypes.c_size_t(2 * lp * B)))
-        elif levels is not None:
-            levels = np.ascontiguousarray(levels, dtype=np.uint64)
-            assert levels.shape == (2 * lp, 4), "the tree does not belong to this shape"
-            d_out.upload(levels)
-        else:
-            assert self.database_f64.shape == (self.n, self.dim), "database rows do not match the circuit's shape"
-            qdb = api.quantize(self.database_f64, self.P)
-            d_db = api.DeviceBuffer(qdb.nbytes)
-            try:
-                d_db.upload(qdb)
-                check(self.lib.vdb_merkle_tree_build_dev(d_db.ptr, self.n, self.dim, d_out.ptr))
-                api.sync()
-            finally:
-                d_db.free()
-
 
 class MerkleHotPath(PoseidonHotPath):
     """merkle_commitment over N x D vectors (src/gadget/vectordb.rs:165-223; examples/merkle.rs) through the same hot
@@ -771,11 +818,11 @@ class MerkleHotPath(PoseidonHotPath):
     def results(self):
         return self.d_root.download((4,))
 
+    def _map_builder(self, CS):
+        return CS.build_merkle, (self.n, self.dim), {}
+
     def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        cm, root = CS.build_merkle(self.n, self.dim, functools.partial(self._fetch_flags, d_flags), self._fetch, builder=DeviceBuilder if on_device else None)
-        assert cm.n_cells == self.n_cells
+        cm, root, _ = super().constraint_map(d_flags, on_device)      # build_merkle's second output is the root cell
         return cm, [root], root                    # examples/merkle.rs:47 make_public.push(root)
 
 
@@ -810,7 +857,7 @@ class UpdateHotPath(PoseidonHotPath):
         if self.depth > 30:
             raise ValueError("a tree of at most 30 levels")
         super().__init__(n, dim, k, P, L, seed=seed, tau=tau, col_shard=col_shard, vectors=None, blind_seed=blind_seed, params=params)
-        self.m = m
+        self.m, self.n_public = m, 3 * m + 2
         self.database_f64 = None if vectors is None else np.ascontiguousarray(vectors, dtype=np.float64)
         self.given_levels, self.given_updates = levels, updates
 
@@ -837,16 +884,10 @@ class UpdateHotPath(PoseidonHotPath):
 
     def _load_inputs(self):
         super()._load_inputs()
-        self.d_levels0 = self._output(2 * self.lp * B)
-        self.d_levels = self._output(2 * self.lp * B)
-        # the tree before the growth: straight into d_levels0 when it is not grown, else into d_levels, which every run overwrites
-        d_small = self.d_levels if self.grow else self.d_levels0
         if self.given_levels is None and self.database_f64 is None:
             self.database_f64, _ = sift_like_vectors(self.seed, self.n, self.dim)
-        self._load_tree(d_small, self.lp0, self.given_levels)
-        if self.grow:
-            check(self.lib.vdb_merkle_tree_grow_dev(d_small.ptr, self.n, self.grow, self.d_levels0.ptr))
-            api.sync()
+        self.tree = _EditedTree(self, self.lp0, self.grow, self.n, self.given_levels)
+        self.d_levels0, self.d_levels = self.tree.before, self.tree.working
 
     def _circuit_size(self):
         cells, n_in = ctypes.c_uint64(), ctypes.c_uint64()
@@ -854,19 +895,16 @@ class UpdateHotPath(PoseidonHotPath):
         return n_in.value, cells.value - n_in.value, 0
 
     def _alloc_outputs(self):
-        self.d_pub = self._output((3 * self.m + 2) * B)
+        self.d_pub = self._output(self.n_public * B)
 
     def _witness(self, sel=None):
         # the call writes the assigned witnesses too (old leaves and siblings come out of its value pass); every run starts from the
         # tree before the batch, so that the keygen-style runs and the proof state the same update
-        check(self.lib.vdb_memcpy_d2d(self.d_levels.ptr, self.d_levels0.ptr, ctypes.c_size_t(2 * self.lp * B)))
+        self.tree.reset()
         with self._window(sel, 0, lookup=False):
             check(self.lib.vdb_wit_merkle_update_ops_dev(self.d_levels.ptr, self.n, self.dim, self.grow, self.d_vec.ptr if self.w else None,
                                                          api._p(self.indices), api._p(self.kinds), self.m, self.d_stream.ptr, self._sel_at(sel, 0),
                                                          self.d_pub.ptr))
-
-    def public_values_dev(self):
-        return self.d_pub.ptr, 3 * self.m + 2
 
     def results(self):
         """(old root (4,), indices (m, 4), old leaves (m, 4), new leaves (m, 4), new root (4,))"""
@@ -874,13 +912,8 @@ class UpdateHotPath(PoseidonHotPath):
         per = pub[1:-1].reshape(self.m, 3, 4)
         return pub[0], per[:, 0], per[:, 1], per[:, 2], pub[-1]
 
-    def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        cm, pub = CS.build_merkle_update(self.m, self.dim, self.depth, functools.partial(self._fetch_flags, d_flags), self._fetch,
-                                         builder=DeviceBuilder if on_device else None, kinds=self.kinds.tolist(), grow=self.grow)
-        assert cm.n_cells == self.n_cells
-        return cm, pub, None
+    def _map_builder(self, CS):
+        return CS.build_merkle_update, (self.m, self.dim, self.depth), dict(kinds=self.kinds.tolist(), grow=self.grow)
 
 
 class ReadHotPath(PoseidonHotPath):
@@ -944,8 +977,8 @@ class ReadHotPath(PoseidonHotPath):
         return n_in.value, cells.value - n_in.value, 0
 
     def _alloc_outputs(self):
-        self.n_pub = 1 + 2 * self.m + (self.m * self.dim if self.with_vectors else 0)
-        self.d_pub = self._output(self.n_pub * B)
+        self.n_public = 1 + 2 * self.m + (self.m * self.dim if self.with_vectors else 0)
+        self.d_pub = self._output(self.n_public * B)
 
     def _witness(self, sel=None):
         # the call writes the assigned witnesses too (bits from the indices, siblings and leaves out of the tree)
@@ -953,23 +986,15 @@ class ReadHotPath(PoseidonHotPath):
             check(self.lib.vdb_wit_merkle_open_dev(self.d_levels.ptr, self.n, self.dim, self.d_vec.ptr if self.with_vectors else None, api._p(self.indices),
                                                    self.m, self.d_stream.ptr, self._sel_at(sel, 0), self.d_pub.ptr))
 
-    def public_values_dev(self):
-        return self.d_pub.ptr, self.n_pub
-
     def results(self):
         """(root (4,), indices (m, 4), leaves (m, 4)[, vectors (m, dim, 4) in vector mode])"""
-        pub = self.d_pub.download((self.n_pub, 4))
+        pub = self.d_pub.download((self.n_public, 4))
         per = pub[1:1 + 2 * self.m].reshape(self.m, 2, 4)
         out = (pub[0], per[:, 0], per[:, 1])
         return out + (pub[1 + 2 * self.m:].reshape(self.m, self.dim, 4),) if self.with_vectors else out
 
-    def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        cm, pub = CS.build_merkle_open(self.m, self.dim, self.depth, self.with_vectors, functools.partial(self._fetch_flags, d_flags), self._fetch,
-                                       builder=DeviceBuilder if on_device else None)
-        assert cm.n_cells == self.n_cells
-        return cm, pub, None
+    def _map_builder(self, CS):
+        return CS.build_merkle_open, (self.m, self.dim, self.depth, self.with_vectors), {}
 
 
 class TopKQueryHotPath(HotPath):
@@ -1000,6 +1025,7 @@ class TopKQueryHotPath(HotPath):
         super().__init__(n, dim, k, P, L, seed=seed, tau=tau, col_shard=col_shard, vectors=vectors, blind_seed=blind_seed, params=params)
         self.q, self.topk = q, topk
         self.n_results = q * topk * dim            # cells of the result vectors
+        self.n_public = self.n_results + self.commit
         self.metric = api.METRICS[metric]
         self.metric_name = metric
 
@@ -1020,7 +1046,7 @@ class TopKQueryHotPath(HotPath):
     def _alloc_outputs(self):
         self.d_ind = self._output(self.q * self.topk * self.n * 32)
         # [result vectors | root]: the public statement, in make_public order (examples/query.rs:58 make_public.extend(result), :69 push(root))
-        self.d_pub = self.d_res = self._output((self.n_results + self.commit) * 32)
+        self.d_pub = self.d_res = self._output(self.n_public * 32)
         if self.commit:
             self.d_root = self._output(32)
 
@@ -1032,9 +1058,6 @@ class TopKQueryHotPath(HotPath):
         if self.commit:
             _merkle_trace(self, d_db, at + self.nearest_cells, sel)
             check(self.lib.vdb_memcpy_d2d(self.d_pub.at(self.n_results * 32), self.d_root.ptr, ctypes.c_size_t(32)))
-
-    def public_values_dev(self):
-        return self.d_pub.ptr, self.n_results + self.commit
 
     def _result_axes(self):
         return self.q, self.topk
@@ -1239,10 +1262,21 @@ class AnnIndex:
         ix.d_cent.upload(qcent)
         return ix
 
+    def _successor(self, sizes, digests, segments, qcent, qvec, ids, fill):
+        """the index after a batch as a new AnnIndex on buffers of its own: its host-side shape and view (from_resident's), and
+        fill(ix): the device call that fills its buffers from this index's; the buffers are freed again when it fails"""
+        ix = AnnIndex.from_resident(self.dim, self.K, sizes, digests, segments, qcent, qvec, ids, P=self.P, L=self.L, metric=self.metric_name)
+        try:
+            fill(ix)
+        except Exception:
+            ix.free()
+            raise
+        return ix
+
     def _after_writes(self, hp, db_slots):
         """the shape and the host view of the index after the writes of `hp` (AnnUpdateHotPath or AnnWriteHotPath) with its appends at
         the database slots `db_slots`: replaced rows where the cluster's slots say, appended rows at db_slots -> (sizes before the batch
-        as uint64, the new AnnIndex on fresh, unfilled buffers)"""
+        as uint64, what _successor takes ahead of `fill`)"""
         c, m, app = hp.cluster, hp.m, hp.appends
         if db_slots.shape != (app,):
             raise ValueError("one database slot per append")
@@ -1257,7 +1291,7 @@ class AnnIndex:
             qvec[place[int(hp.indices[j])]], ids[place[int(hp.indices[j])]] = hp.qvec[j], c
         sizes = self.sizes.copy()
         sizes[c] += app
-        return sizes64, AnnIndex.from_resident(self.dim, self.K, sizes, digests, seg, self.qcent, qvec, ids, P=self.P, L=self.L, metric=self.metric_name)
+        return sizes64, (sizes, digests, seg, self.qcent, qvec, ids)
 
     def updated(self, hp, db_slots=None):
         """the index after the batch of AnnUpdateHotPath `hp` (its witness has run: hp.d_levels holds the cluster's tree after the
@@ -1266,15 +1300,11 @@ class AnnIndex:
         updates run on the result unchanged."""
         c, m, app = hp.cluster, hp.m, hp.appends
         db_slots = np.arange(self.n, self.n + app, dtype=np.uint32) if db_slots is None else np.ascontiguousarray(db_slots, dtype=np.uint32)
-        sizes64, ix = self._after_writes(hp, db_slots)
-        try:
-            check(self.lib.vdb_ann_index_apply_dev(self.d_grouped.ptr, self.d_slots.ptr, self.d_forest.ptr, self.d_roots.ptr, api._p(sizes64), self.K, self.dim,
-                                                   c, hp.grow, hp.d_levels.ptr, hp.d_vec.ptr, api._p(hp.indices), api._p(db_slots) if app else None, m,
-                                                   ix.d_grouped.ptr, ix.d_slots.ptr, ix.d_offsets.ptr, ix.d_forest.ptr, ix.d_roots.ptr))
-        except Exception:
-            ix.free()
-            raise
-        return ix
+        sizes64, after = self._after_writes(hp, db_slots)
+        return self._successor(*after, lambda ix: check(self.lib.vdb_ann_index_apply_dev(
+            self.d_grouped.ptr, self.d_slots.ptr, self.d_forest.ptr, self.d_roots.ptr, api._p(sizes64), self.K, self.dim, c, hp.grow, hp.d_levels.ptr,
+            hp.d_vec.ptr, api._p(hp.indices), api._p(db_slots) if app else None, m, ix.d_grouped.ptr, ix.d_slots.ptr, ix.d_offsets.ptr, ix.d_forest.ptr,
+            ix.d_roots.ptr)))
 
     def written(self, hp):
         """the index after the linked write of AnnWriteHotPath `hp` (its witness has run: hp.d_levels and hp.d_levels_db hold the two
@@ -1284,16 +1314,14 @@ class AnnIndex:
         AnnWriteHotPath's overrides (levels, levels_db, db_indices): its trees are not this index's."""
         if hp.index is not self or hp.given_levels is not None or hp.given_levels_db is not None or hp.given_db_indices is not None:
             raise ValueError("the hot path was built on this index, with the index's own trees and database slots")
-        sizes64, ix = self._after_writes(hp, np.arange(self.n, self.n + hp.appends, dtype=np.uint32))
-        try:
+        sizes64, after = self._after_writes(hp, np.arange(self.n, self.n + hp.appends, dtype=np.uint32))
+
+        def fill(ix):
             ix.d_db_tree = ix._buf(2 * hp.lp_db * B)
             check(self.lib.vdb_ann_index_write_dev(self.d_grouped.ptr, self.d_slots.ptr, self.d_forest.ptr, self.d_roots.ptr, api._p(sizes64), self.K, self.dim,
                                                    hp.cluster, hp.grow, hp.grow_db, hp.d_levels.ptr, hp.d_levels_db.ptr, hp.d_vec.ptr, api._p(hp.indices), hp.m,
                                                    ix.d_grouped.ptr, ix.d_slots.ptr, ix.d_offsets.ptr, ix.d_forest.ptr, ix.d_roots.ptr, ix.d_db_tree.ptr))
-        except Exception:
-            ix.free()
-            raise
-        return ix
+        return self._successor(*after, fill)
 
     def removed(self, hp):
         """the index after the batch of AnnDeleteHotPath `hp` (its witness has run: hp.d_levels holds the cluster's tree after the
@@ -1311,15 +1339,9 @@ class AnnIndex:
         keep = np.concatenate([np.arange(lo), lo + np.asarray(hp.origin, dtype=np.int64), np.arange(lo + int(self.sizes[c]), self.n)]).astype(np.int64)
         qvec = np.ascontiguousarray(self.qvec[old_slots[keep]])
         ids = np.repeat(np.arange(self.K, dtype=np.uint32), sizes)
-        ix = AnnIndex.from_resident(self.dim, self.K, sizes, digests, seg, self.qcent, qvec, ids, P=self.P, L=self.L, metric=self.metric_name)
-        try:
-            check(self.lib.vdb_ann_index_remove_dev(self.d_grouped.ptr, self.d_forest.ptr, self.d_roots.ptr, api._p(sizes64), self.K, self.dim, c,
-                                                    hp.d_levels.ptr, api._p(hp.slots), m, ix.d_grouped.ptr, ix.d_slots.ptr, ix.d_offsets.ptr,
-                                                    ix.d_forest.ptr, ix.d_roots.ptr))
-        except Exception:
-            ix.free()
-            raise
-        return ix
+        return self._successor(sizes, digests, seg, self.qcent, qvec, ids, lambda ix: check(self.lib.vdb_ann_index_remove_dev(
+            self.d_grouped.ptr, self.d_forest.ptr, self.d_roots.ptr, api._p(sizes64), self.K, self.dim, c, hp.d_levels.ptr, api._p(hp.slots), m,
+            ix.d_grouped.ptr, ix.d_slots.ptr, ix.d_offsets.ptr, ix.d_forest.ptr, ix.d_roots.ptr)))
 
     def moved(self, hp):
         """the index after the batch of AnnMoveHotPath `hp` (its witness has run: hp.d_levels_a and hp.d_levels_b hold the two trees
@@ -1335,15 +1357,9 @@ class AnnIndex:
         old_slots = self.d_slots.download((int(self.sizes[a]),), dtype=np.uint32, offset=int(self.offsets[a]) * 4).astype(np.int64)
         ids = self.cluster_ids.copy()
         ids[old_slots[np.asarray(hp.moved_from, dtype=np.int64)]] = b
-        ix = AnnIndex.from_resident(self.dim, self.K, sizes, digests, seg, self.qcent, self.qvec, ids, P=self.P, L=self.L, metric=self.metric_name)
-        try:
-            check(self.lib.vdb_ann_index_move_dev(self.d_grouped.ptr, self.d_slots.ptr, self.d_forest.ptr, self.d_roots.ptr, api._p(sizes64), self.K, self.dim,
-                                                  a, b, g, hp.d_levels_a.ptr, hp.d_levels_b.ptr, api._p(hp.slots), m, ix.d_grouped.ptr, ix.d_slots.ptr,
-                                                  ix.d_offsets.ptr, ix.d_forest.ptr, ix.d_roots.ptr))
-        except Exception:
-            ix.free()
-            raise
-        return ix
+        return self._successor(sizes, digests, seg, self.qcent, self.qvec, ids, lambda ix: check(self.lib.vdb_ann_index_move_dev(
+            self.d_grouped.ptr, self.d_slots.ptr, self.d_forest.ptr, self.d_roots.ptr, api._p(sizes64), self.K, self.dim, a, b, g, hp.d_levels_a.ptr,
+            hp.d_levels_b.ptr, api._p(hp.slots), m, ix.d_grouped.ptr, ix.d_slots.ptr, ix.d_offsets.ptr, ix.d_forest.ptr, ix.d_roots.ptr)))
 
     def _buf(self, nbytes):
         b = api.DeviceBuffer(max(int(nbytes), 32))
@@ -1440,17 +1456,10 @@ class AnnIndex:
         c, sizes64 = hp.cluster, np.ascontiguousarray(self.sizes, dtype=np.uint64)
         qcent = self.qcent.copy()
         qcent[c] = hp.d_new.download((self.dim, 4))
-        ix = AnnIndex.from_resident(self.dim, self.K, self.sizes, self.n_digests, self.segments, qcent, self.qvec, self.cluster_ids, P=self.P, L=self.L,
-                                    metric=self.metric_name)
-        try:
-            check(self.lib.vdb_ann_index_recentre_dev(self.d_grouped.ptr, self.d_slots.ptr, self.d_offsets.ptr, self.d_forest.ptr, self.d_roots.ptr,
-                                                      self.d_cent.ptr, api._p(sizes64), self.K, self.dim, c,
-                                                      hp.d_levels.ptr, hp.d_new.ptr, ix.d_grouped.ptr, ix.d_slots.ptr, ix.d_offsets.ptr, ix.d_forest.ptr,
-                                                      ix.d_roots.ptr, ix.d_cent.ptr))
-        except Exception:
-            ix.free()
-            raise
-        return ix
+        return self._successor(self.sizes, self.n_digests, self.segments, qcent, self.qvec, self.cluster_ids, lambda ix: check(
+            self.lib.vdb_ann_index_recentre_dev(self.d_grouped.ptr, self.d_slots.ptr, self.d_offsets.ptr, self.d_forest.ptr, self.d_roots.ptr, self.d_cent.ptr,
+                                                api._p(sizes64), self.K, self.dim, c, hp.d_levels.ptr, hp.d_new.ptr, ix.d_grouped.ptr, ix.d_slots.ptr,
+                                                ix.d_offsets.ptr, ix.d_forest.ptr, ix.d_roots.ptr, ix.d_cent.ptr)))
 
     def database_tree(self):
         """the merkle_commitment tree over the database rows in slot order (2 lp digests, api.merkle_tree_build's layout) as a device
@@ -1526,7 +1535,7 @@ class AnnProbeQueryHotPath(HotPath):
         super().__init__(int(self.sizes.sum()), index.dim, k, P, L, seed=None, tau=tau, col_shard=col_shard, vectors=query, blind_seed=blind_seed,
                          params=params)
         self.metric, self.metric_name = api.METRICS[metric], metric
-        self.given_roots, self.given_cent = cluster_roots, centroids
+        self.n_public, self.given_roots, self.given_cent = self.topk * self.dim + 1, cluster_roots, centroids
 
     def n_input_rows(self):
         return 1
@@ -1548,7 +1557,7 @@ class AnnProbeQueryHotPath(HotPath):
 
     def _alloc_outputs(self):
         self.d_ind_c, self.d_ind_m = self._output(self.probes * self.K * B), self._output(self.topk * self.n * B)
-        self.d_pub = self._output((self.topk * self.dim + 1) * B)
+        self.d_pub = self._output(self.n_public * B)
 
     def _witness(self, sel=None):
         # the call writes the assigned witnesses too (centroids, candidates and roots where the index holds them)
@@ -1559,12 +1568,9 @@ class AnnProbeQueryHotPath(HotPath):
                                                  api._p(self.sizes), self.topk, self.d_stream.ptr, self.d_lookup.ptr, self._sel_at(sel, 0),
                                                  self.d_ind_c.ptr, self.d_ind_m.ptr, self.d_pub.ptr))
 
-    def public_values_dev(self):
-        return self.d_pub.ptr, self.topk * self.dim + 1
-
     def results(self):
         """(centroid indicators (p, K, 4), candidate indicators (t, N, 4), results (t, dim, 4) nearest first, index root (4,))"""
-        t, pub = self.topk, self.d_pub.download((self.topk * self.dim + 1, 4))
+        t, pub = self.topk, self.d_pub.download((self.n_public, 4))
         return (self.d_ind_c.download((self.probes, self.K, 4)), self.d_ind_m.download((t, self.n, 4)), pub[:t * self.dim].reshape(t, self.dim, 4),
                 pub[t * self.dim])
 
@@ -1578,13 +1584,8 @@ class AnnProbeQueryHotPath(HotPath):
         slots = self.index.d_slots.download((self.index.n,), dtype=np.uint32).astype(np.int64)
         return slots[grouped]
 
-    def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        cm, public, _ = CS.build_ann_probe(self.metric_name, self.K, [int(x) for x in self.sizes], self.dim, self.probes, self.topk, self.P, self.L,
-                                           functools.partial(self._fetch_flags, d_flags), self._fetch, builder=DeviceBuilder if on_device else None)
-        assert cm.n_cells == self.n_cells
-        return cm, public, None
+    def _map_builder(self, CS):
+        return CS.build_ann_probe, (self.metric_name, self.K, [int(x) for x in self.sizes], self.dim, self.probes, self.topk, self.P, self.L), {}
 
 
 class AnnQueryHotPath(AnnProbeQueryHotPath):
@@ -1610,36 +1611,23 @@ class AnnQueryHotPath(AnnProbeQueryHotPath):
 class _AnnBatchHotPath(PoseidonHotPath):
     """What the proofs of a batch against the committed index root share (AnnUpdateHotPath, AnnDeleteHotPath): the cluster c of an
     AnnIndex, its tree before the batch (`d_levels0`) and the copy every witness run works on (`d_levels`), the public row `d_pub` of
-    `n_public` values, the map.  A subclass sets lp, depth, m, n_public and given_levels, and gives _circuit_size, _call(sel): the
-    library's witness call on these buffers -> its return code, and _builder(CS): (circuit_sym's build function, its own keywords)."""
+    `n_public` values.  A subclass sets lp, depth, m, n_public and given_levels, and gives _circuit_size, _call(sel): the library's
+    witness call on these buffers -> its return code, and _map_builder."""
 
     def _load_inputs(self, grow=0):
         super()._load_inputs()
-        self.d_levels0 = self._output(2 * self.lp * B)
-        self.d_levels = self._output(2 * self.lp * B)
-        d_given = self.d_levels if grow else self.d_levels0      # a tree that has yet to be grown into d_levels0 waits in d_levels
-        self._load_tree(d_given, self.lp >> grow, self.index.levels(self.cluster) if self.given_levels is None else self.given_levels)
+        given = self.index.levels(self.cluster) if self.given_levels is None else self.given_levels
+        self.tree = _EditedTree(self, self.lp >> grow, grow, self.n, given)
+        self.d_levels0, self.d_levels = self.tree.before, self.tree.working
 
     def _alloc_outputs(self):
         self.d_pub = self._output(self.n_public * B)
 
     def _witness(self, sel=None):
         # the call writes the assigned header too; every run starts from the cluster's tree before the batch
-        check(self.lib.vdb_memcpy_d2d(self.d_levels.ptr, self.d_levels0.ptr, ctypes.c_size_t(2 * self.lp * B)))
+        self.tree.reset()
         with self._window(sel, 0, lookup=False):
             check(self._call(self._sel_at(sel, 0)))
-
-    def public_values_dev(self):
-        return self.d_pub.ptr, self.n_public
-
-    def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        build, kw = self._builder(CS)
-        cm, pub, _ = build(self.K, self.m, self.dim, self.depth, functools.partial(self._fetch_flags, d_flags), self._fetch,
-                           builder=DeviceBuilder if on_device else None, **kw)
-        assert cm.n_cells == self.n_cells
-        return cm, pub, None
 
 
 class AnnUpdateHotPath(_AnnBatchHotPath):
@@ -1686,9 +1674,6 @@ class AnnUpdateHotPath(_AnnBatchHotPath):
 
     def _load_inputs(self):
         super()._load_inputs(self.grow)
-        if self.grow:
-            check(self.lib.vdb_merkle_tree_grow_dev(self.d_levels.ptr, self.n, self.grow, self.d_levels0.ptr))
-            api.sync()
 
     def _circuit_size(self):
         cells, n_in, ub = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
@@ -1706,8 +1691,8 @@ class AnnUpdateHotPath(_AnnBatchHotPath):
         per = pub[2:-1].reshape(self.m, 3, 4)
         return pub[0], pub[1], per[:, 0], per[:, 1], per[:, 2], pub[-1]
 
-    def _builder(self, CS):
-        return CS.build_ann_update, dict(grow=self.grow)
+    def _map_builder(self, CS):
+        return CS.build_ann_update, (self.K, self.m, self.dim, self.depth), dict(grow=self.grow)
 
 
 class AnnWriteHotPath(AnnUpdateHotPath):
@@ -1740,16 +1725,12 @@ class AnnWriteHotPath(AnnUpdateHotPath):
 
     def _load_inputs(self):
         super()._load_inputs()
-        self.d_levels_db0 = self._output(2 * self.lp_db * B)     # the grown database tree before the batch
-        self.d_levels_db = self._output(2 * self.lp_db * B)
         given = self.index.database_tree() if self.given_levels_db is None else self.given_levels_db
-        self._load_tree(self.d_levels_db if self.grow_db else self.d_levels_db0, self.lp_db0, given)
-        if self.grow_db:
-            check(self.lib.vdb_merkle_tree_grow_dev(self.d_levels_db.ptr, self.n_db, self.grow_db, self.d_levels_db0.ptr))
-            api.sync()
+        self.tree_db = _EditedTree(self, self.lp_db0, self.grow_db, self.n_db, given)
+        self.d_levels_db0, self.d_levels_db = self.tree_db.before, self.tree_db.working      # the grown database tree before the batch, and after
 
     def _witness(self, sel=None):
-        check(self.lib.vdb_memcpy_d2d(self.d_levels_db.ptr, self.d_levels_db0.ptr, ctypes.c_size_t(2 * self.lp_db * B)))
+        self.tree_db.reset()
         super()._witness(sel)
 
     def _circuit_size(self):
@@ -1771,8 +1752,8 @@ class AnnWriteHotPath(AnnUpdateHotPath):
         per = pub[3:-2].reshape(self.m, 4, 4)
         return (pub[0], pub[1], pub[2]) + tuple(per[:, i] for i in range(4)) + (pub[-2], pub[-1])
 
-    def _builder(self, CS):
-        return CS.build_ann_write, dict(grow=self.grow, depth_db=self.depth_db, grow_db=self.grow_db)
+    def _map_builder(self, CS):
+        return CS.build_ann_write, (self.K, self.m, self.dim, self.depth), dict(grow=self.grow, depth_db=self.depth_db, grow_db=self.grow_db)
 
 
 class AnnDeleteHotPath(_AnnBatchHotPath):
@@ -1791,14 +1772,7 @@ class AnnDeleteHotPath(_AnnBatchHotPath):
         self.slots = np.ascontiguousarray(slots, dtype=np.uint64)
         m = self.slots.shape[0]
         n_c = _bind_cluster(self, index, cluster)
-        if m < 1 or m >= n_c:
-            raise ValueError("a batch holds at least one delete and leaves at least one member")
-        origin = list(range(n_c))
-        for j, s in enumerate(self.slots.tolist()):
-            if s >= n_c - j:
-                raise ValueError("a slot at or above the cluster's fill at its turn")
-            origin[s] = origin[n_c - j - 1]
-        self.origin = origin[:n_c - m]
+        self.origin, _ = _swap_with_last(n_c, self.slots.tolist(), ("delete", "cluster"))
         self.lp, self.depth = api.merkle_levels(n_c)
         super().__init__(n_c, index.dim, k, index.P, L, seed=None, tau=tau, col_shard=col_shard, vectors=np.zeros((0, index.dim)), blind_seed=blind_seed,
                          params=params)
@@ -1824,8 +1798,8 @@ class AnnDeleteHotPath(_AnnBatchHotPath):
         per = pub[2:-1].reshape(self.m, 4, 4)
         return pub[0], pub[1], per[:, 0], per[:, 1], per[:, 2], per[:, 3], pub[-1]
 
-    def _builder(self, CS):
-        return CS.build_ann_delete, dict(shrink=self.shrink)
+    def _map_builder(self, CS):
+        return CS.build_ann_delete, (self.K, self.m, self.dim, self.depth), dict(shrink=self.shrink)
 
 
 class AnnMoveHotPath(_AnnBatchHotPath):
@@ -1851,15 +1825,7 @@ class AnnMoveHotPath(_AnnBatchHotPath):
         if not 0 <= self.dst < self.K or self.dst == self.src:
             raise ValueError("the destination is another cluster of the index")
         n_b = int(index.sizes[self.dst])
-        if m < 1 or m >= n_a:
-            raise ValueError("a batch holds at least one move and leaves at least one member")
-        origin, self.moved_from = list(range(n_a)), []
-        for j, s in enumerate(self.slots.tolist()):
-            if s >= n_a - j:
-                raise ValueError("a slot at or above the source cluster's fill at its turn")
-            self.moved_from.append(origin[s])
-            origin[s] = origin[n_a - j - 1]
-        self.origin = origin[:n_a - m]
+        self.origin, self.moved_from = _swap_with_last(n_a, self.slots.tolist(), ("move", "source cluster"))
         self.lp, self.depth = api.merkle_levels(n_a)
         self.lp_b0, depth_b0 = api.merkle_levels(n_b)
         self.lp_b, self.depth_b = api.merkle_levels(n_b + m)
@@ -1876,16 +1842,12 @@ class AnnMoveHotPath(_AnnBatchHotPath):
     def _load_inputs(self):
         super()._load_inputs()
         self.d_levels_a = self.d_levels
-        self.d_levels_b0 = self._output(2 * self.lp_b * B)       # b's grown tree before the batch
-        self.d_levels_b = self._output(2 * self.lp_b * B)
         given = self.index.levels(self.dst) if self.given_levels_b is None else self.given_levels_b
-        self._load_tree(self.d_levels_b if self.grow else self.d_levels_b0, self.lp_b0, given)
-        if self.grow:
-            check(self.lib.vdb_merkle_tree_grow_dev(self.d_levels_b.ptr, self.n_b, self.grow, self.d_levels_b0.ptr))
-            api.sync()
+        self.tree_b = _EditedTree(self, self.lp_b0, self.grow, self.n_b, given)
+        self.d_levels_b0, self.d_levels_b = self.tree_b.before, self.tree_b.working      # b's grown tree before the batch, and after
 
     def _witness(self, sel=None):
-        check(self.lib.vdb_memcpy_d2d(self.d_levels_b.ptr, self.d_levels_b0.ptr, ctypes.c_size_t(2 * self.lp_b * B)))
+        self.tree_b.reset()
         super()._witness(sel)
 
     def _circuit_size(self):
@@ -1908,21 +1870,18 @@ class AnnMoveHotPath(_AnnBatchHotPath):
         per = pub[3:-1].reshape(self.m, 6, 4)
         return (pub[0], pub[1], pub[2]) + tuple(per[:, i] for i in range(6)) + (pub[-1],)
 
-    def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        cm, pub, _ = CS.build_ann_move(self.K, self.m, self.depth, self.shrink, self.depth_b, self.grow, functools.partial(self._fetch_flags, d_flags),
-                                       self._fetch, builder=DeviceBuilder if on_device else None)
-        assert cm.n_cells == self.n_cells
-        return cm, pub, None
+    def _map_builder(self, CS):
+        return CS.build_ann_move, (self.K, self.m, self.depth, self.shrink, self.depth_b, self.grow), {}
 
 
 class _AnnClusterHotPath(HotPath):
     """What the audits of one cluster c of a committed AnnIndex share (AnnAuditHotPath, AnnMeanHotPath): the binding to (index, cluster),
     where the call reads the centroids and the members (`p_cent`, `p_members`: the resident index, or the overrides given; `resident`),
-    no input rows, the flag bytes and the public row [index_root | c] (`d_pub`), the map.  A subclass gives _size(*outputs) and
+    no input rows, the flag bytes and the public row [index_root | c] (`d_pub`).  A subclass gives _size(*outputs) and
     _call(*shared arguments): the library's size and witness calls -> their return codes, _n_flags(): the length of its flag bytes, and
-    _builder(CS): (circuit_sym's build function, the arguments ahead of K)."""
+    _map_builder."""
+
+    n_public = 2
 
     def __init__(self, index, cluster, k=13, P=48, L=12, tau=None, col_shard=(0, 1), blind_seed=None, params=None, centroids=None, members=None):
         n_c = _bind_cluster(self, index, cluster)
@@ -1955,23 +1914,11 @@ class _AnnClusterHotPath(HotPath):
                              ix.levels_ptr(self.cluster) if self.resident else None, self.K, self.cluster, self.n, self.dim, self.d_stream.ptr,
                              self.d_lookup.ptr, self._sel_at(sel, 0), self.d_flag_bytes.ptr, self.d_pub.ptr))
 
-    def public_values_dev(self):
-        return self.d_pub.ptr, 2
-
     def results(self):
         """(index_root (4,), c (4,), the flag bytes, uint8: the audit's routed (n_c,), member i's own centroid attains the minimum of its K
         distances; the mean's mean_ok (dim,), word j of centroid c is the mean of the members' words j)"""
         pub = self.d_pub.download((2, 4))
         return pub[0], pub[1], self.d_flag_bytes.download((self._n_flags(),), dtype=np.uint8)
-
-    def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        build, ahead = self._builder(CS)
-        cm, public, _ = build(*ahead, self.K, self.n, self.dim, self.P, self.L, functools.partial(self._fetch_flags, d_flags), self._fetch,
-                              builder=DeviceBuilder if on_device else None)
-        assert cm.n_cells == self.n_cells
-        return cm, public, None
 
 
 class AnnAuditHotPath(_AnnClusterHotPath):
@@ -2003,8 +1950,8 @@ class AnnAuditHotPath(_AnnClusterHotPath):
     def _call(self, *shared):
         return self.lib.vdb_wit_ann_audit_dev(self.metric, self.P, self.L, *shared)
 
-    def _builder(self, CS):
-        return CS.build_ann_audit, (self.metric_name,)
+    def _map_builder(self, CS):
+        return CS.build_ann_audit, (self.metric_name, self.K, self.n, self.dim, self.P, self.L), {}
 
 
 class AnnMeanHotPath(_AnnClusterHotPath):
@@ -2032,8 +1979,8 @@ class AnnMeanHotPath(_AnnClusterHotPath):
     def _call(self, *shared):
         return self.lib.vdb_wit_ann_mean_dev(self.P, self.L, *shared)
 
-    def _builder(self, CS):
-        return CS.build_ann_mean, ()
+    def _map_builder(self, CS):
+        return CS.build_ann_mean, (self.K, self.n, self.dim, self.P, self.L), {}
 
 
 class AnnRecentreHotPath(HotPath):
@@ -2053,6 +2000,8 @@ class AnnRecentreHotPath(HotPath):
     gives the next index.  `members` / `levels`: quantized overrides of the cluster's members and of the centroids' tree (tests of the
     binding); with `members` the cluster's tree is hashed by the call instead of read from the forest."""
 
+    n_public = 3
+
     def __init__(self, index, cluster, k=13, P=48, L=12, tau=None, col_shard=(0, 1), blind_seed=None, params=None, members=None, levels=None):
         n_c = _bind_cluster(self, index, cluster)
         if self.K < 2:
@@ -2069,13 +2018,8 @@ class AnnRecentreHotPath(HotPath):
         super()._load_inputs()
         ix, self.resident = self.index, self.given_members is None
         self.p_members = _given_ptr(self, self.given_members, (self.n, self.dim, 4), ix.members_ptr(self.cluster))
-        self.d_levels0, self.d_levels = self._output(2 * self.lp * B), self._output(2 * self.lp * B)
-        if self.given_levels is None:
-            check(self.lib.vdb_memcpy_d2d(self.d_levels0.ptr, ix.levels_ptr(self.K), ctypes.c_size_t(2 * self.lp * B)))
-        else:
-            lv = np.ascontiguousarray(self.given_levels, dtype=np.uint64)
-            assert lv.shape == (2 * self.lp, 4), "the tree does not belong to this shape"
-            self.d_levels0.upload(lv)
+        self.tree = _EditedTree(self, self.lp, 0, self.K, ix.levels(self.K) if self.given_levels is None else self.given_levels)
+        self.d_levels0, self.d_levels = self.tree.before, self.tree.working
 
     def _circuit_size(self):
         cells, lk, n_in, ub = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
@@ -2090,27 +2034,19 @@ class AnnRecentreHotPath(HotPath):
     def _witness(self, sel=None):
         # the call writes the assigned header and members too; every run starts from the centroids' tree before the write
         ix = self.index
-        check(self.lib.vdb_memcpy_d2d(self.d_levels.ptr, self.d_levels0.ptr, ctypes.c_size_t(2 * self.lp * B)))
+        self.tree.reset()
         with self._window(sel, 0):
             check(self.lib.vdb_wit_ann_recentre_dev(self.P, self.L, self.d_levels.ptr, self.p_members, ix.d_roots.ptr,
                                                     ix.levels_ptr(self.cluster) if self.resident else None, self.K, self.cluster, self.n, self.dim,
                                                     self.d_stream.ptr, self.d_lookup.ptr, self._sel_at(sel, 0), self.d_new.ptr, self.d_pub.ptr))
-
-    def public_values_dev(self):
-        return self.d_pub.ptr, 3
 
     def results(self):
         """(index_root_old (4,), c (4,), index_root_new (4,), the new centroid (dim, 4))"""
         pub = self.d_pub.download((3, 4))
         return pub[0], pub[1], pub[2], self.d_new.download((self.dim, 4))
 
-    def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        cm, public, _ = CS.build_ann_recentre(self.K, self.n, self.dim, self.P, self.L, functools.partial(self._fetch_flags, d_flags), self._fetch,
-                                              builder=DeviceBuilder if on_device else None)
-        assert cm.n_cells == self.n_cells
-        return cm, public, None
+    def _map_builder(self, CS):
+        return CS.build_ann_recentre, (self.K, self.n, self.dim, self.P, self.L), {}
 
 
 class AnnCoverHotPath(PoseidonHotPath):
@@ -2125,6 +2061,8 @@ class AnnCoverHotPath(PoseidonHotPath):
     therefore public.  Not covered: a database with emptied slots (after UpdateHotPath deletes; AnnIndex's own deletes compact).
     `leaves`: (database leaf digests (n, 4), cluster leaf digests (n, 4)) in place of what the index holds (tests of the binding); the
     K + 1 trees are then hashed by the call instead of read where they lie."""
+
+    n_public = 2
 
     def __init__(self, index, k=15, L=8, tau=None, col_shard=(0, 1), blind_seed=None, params=None, leaves=None):
         self.index, self.K = index, index.K
@@ -2162,18 +2100,10 @@ class AnnCoverHotPath(PoseidonHotPath):
             check(self.lib.vdb_wit_ann_cover_dev(self.p_a, self.p_b, ix.d_roots.ptr, api._p(self.sizes64), self.K, self.n, self.p_tree,
                                                  ix.d_forest.ptr if self.resident else None, self.d_stream.ptr, self._sel_at(sel, 0), self.d_pub.ptr))
 
-    def public_values_dev(self):
-        return self.d_pub.ptr, 2
-
     def results(self):
         """(database_root (4,), index_root (4,))"""
         pub = self.d_pub.download((2, 4))
         return pub[0], pub[1]
 
-    def constraint_map(self, d_flags, on_device=True):
-        from . import circuit_sym as CS
-        from .circuit_dev import DeviceBuilder
-        cm, public, _ = CS.build_ann_cover(self.index.sizes, functools.partial(self._fetch_flags, d_flags), self._fetch,
-                                           builder=DeviceBuilder if on_device else None)
-        assert cm.n_cells == self.n_cells
-        return cm, public, None
+    def _map_builder(self, CS):
+        return CS.build_ann_cover, (self.index.sizes,), {}
