@@ -2189,50 +2189,85 @@ static int annu_layout(size_t K, size_t cluster, size_t n_c, size_t dim, size_t 
     return VDB_OK;
   });
 }
-// The frame of one call: its work space in scratch slot 7, in u256: [c | words_old K + 1] (the header as it is assigned) | ind K |
-// picked | words_new K + 1 | index_root_old, index_root_new | the inner block's public values n_upub | n_extra for the caller | the
-// sponge states of D and of G.  open() attaches the inverse list to the streams and emits A - D; the caller emits its own blocks
-// through `st`, then close() emits F and G over the new cluster root.
+// two kernels the frame launches, defined with their circuits below
+__global__ __launch_bounds__(256) void k_annmv_header(Streams, uint32_t, uint32_t, const u256*, uint32_t, u256*);
+__global__ __launch_bounds__(64) void k_annd_shrink_trace(Streams, const FpTables*, const PoseidonSpec*, uint64_t, uint32_t, uint32_t, uint64_t,
+                                                          const u256*, const u256*, u256*);
+// The frame of one call.  Its circuit is a chain of root lists w_0 .. w_n, one step per cluster id: w_0 = [centroids_root | cluster roots]
+// as the header assigns it, step i picks cluster id_i's root out of w_i (pick: B, C) and, once the caller's blocks have moved that root,
+// replaces it (replace: F) to give w_i+1; D is the sponge over w_0, G the sponge over w_n.  n = 1 but for the move (n = 2: w_1 is `mid`).
+// The work space is one request for scratch slot 7, handed out in this order, in u256: hdr [the n ids | w_0 .. w_n, K + 1 each] | ind n K |
+// picked n | iroot: index_root_old, index_root_new | s0: the halved tree's root (shrink) | upub n_upub: the public row of the caller's
+// update block | extra n_extra: the caller's | the sponge states of D and of G.  Where a second update block carries leaves out of the
+// first (the move's E_b, the write's E_db), `extra` is its public row and it reads the first's as mku_emit's trailing argument (upub),
+// its plan's carry_src naming entries below carry_n = n_upub: nothing depends on where the two rows lie.
+// begin() attaches the inverse list to the streams and emits A; open() is begin, pick, D of a circuit on one cluster and close() its F
+// and G; the caller emits its own blocks through `st` in between.
 struct AnnFrame {
   Streams st;
   FpEntry* fp;
   const PoseidonSpec* sp;
   const MkLayout* mw;   // the sponge over K + 1 words, blocks D and G
-  uint32_t K;
-  u256 *hdr, *ind, *picked, *words_new, *iroot, *upub, *extra, *st_old, *st_new;
-  // h: where the head's blocks start; total: the cells of the whole circuit
-  int open(Streams streams, const u256* roots, size_t K_, size_t cluster, const AnnHead& h, const MkLayout& mw_, uint64_t total, size_t n_upub, size_t n_extra) {
-    st = streams, mw = &mw_, K = (uint32_t)K_;
-    const size_t n_st = (size_t)mw->nperm * PSD_T;
-    hdr = (u256*)scratch_get(7, (2 * (K_ + 2) + K_ + 1 + 2 + n_upub + n_extra + 2 * n_st + 8) * sizeof(u256));
-    if (!hdr) return VDB_ERR_OOM;
-    ind = hdr + K_ + 2;
-    picked = ind + K_;
-    words_new = picked + 1;
-    iroot = words_new + K_ + 1;
-    upub = iroot + 2;
-    extra = upub + n_upub;
-    st_old = extra + n_extra;
-    st_new = st_old + n_st;
+  uint32_t K, n, id[2];
+  u256 *hdr, *ind, *picked, *iroot, *s0, *upub, *extra, *st_old, *st_new, *ws;
+  u256* take(size_t k) { u256* p = ws; ws += k; return p; }
+  u256* w(uint32_t i) const { return hdr + n + (size_t)i * (K + 1); }
+  // total: the cells of the whole circuit
+  int begin(Streams streams, const u256* roots, size_t K_, std::initializer_list<size_t> ids, const MkLayout& mw_, uint64_t total, size_t n_upub, size_t n_extra) {
+    st = streams, mw = &mw_, K = (uint32_t)K_, n = (uint32_t)ids.size();
+    for (uint32_t i = 0; i < n; i++) id[i] = (uint32_t)ids.begin()[i];
+    const size_t n_hdr = n + (n + 1) * (K_ + 1), n_st = (size_t)mw->nperm * PSD_T;
+    ws = (u256*)scratch_get(7, (n_hdr + n * K_ + n + 3 + n_upub + n_extra + 2 * n_st + 8) * sizeof(u256));
+    if (!ws) return VDB_ERR_OOM;
+    hdr = take(n_hdr), ind = take(n * K_), picked = take(n), iroot = take(2), s0 = take(1);
+    upub = take(n_upub), extra = take(n_extra), st_old = take(n_st), st_new = take(n_st);
     TRY(inv_list_attach(st, total));
     TRY(mk_begin(st, &fp, &sp));
-    const uint32_t cu = (uint32_t)cluster;
-    VDB_LAUNCH(k_annu_header, dim3((unsigned)((K_ + 2 + 255) / 256)), dim3(256), st, 0, cu, roots, K, hdr);
-    VDB_LAUNCH(k_annu_indicator, dim3((unsigned)((K_ + 63) / 64)), dim3(64), st, fp->dev, h.b_ind, cu, K, ind);
-    const NvMap sm{h.b_sel, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, K, 1u, 1u};
-    VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), st, fp->dev, sm, 1u, hdr + 2, ind, picked);
-    return sponge(hdr + 1, h.b_old, st_old, iroot);
+    if (n == 1)
+      VDB_LAUNCH(k_annu_header, dim3((unsigned)((K_ + 2 + 255) / 256)), dim3(256), st, 0, id[0], roots, K, hdr);
+    else
+      VDB_LAUNCH(k_annmv_header, dim3((unsigned)((K_ + 3 + 255) / 256)), dim3(256), st, id[0], id[1], roots, K, hdr);
+    return VDB_OK;
+  }
+  // blocks B and C of step i: idx_to_indicator(id_i, K) -> ind_i, select_by_indicator(the cluster roots of w_i, ind_i) -> picked_i
+  int pick(uint32_t i, uint64_t b_ind, uint64_t b_sel) {
+    u256* ind_i = ind + (size_t)i * K;
+    VDB_LAUNCH(k_annu_indicator, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, b_ind, id[i], K, ind_i);
+    const NvMap sm{b_sel, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, K, 1u, 1u};
+    VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), st, fp->dev, sm, 1u, w(i) + 1, ind_i, picked + i);
+    return VDB_OK;
+  }
+  // block F of step i: w_i+1 = w_i with cluster id_i's root replaced by *new_root
+  int replace(uint32_t i, uint64_t b_new, const u256* new_root) {
+    VDB_LAUNCH(k_annu_new_roots, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, b_new, K, new_root, w(i), ind + (size_t)i * K, w(i + 1));
+    return VDB_OK;
+  }
+  // block S behind an update block of n_up public values on `levels` (no launch when the tree keeps its size), and the root that F
+  // reads: s0 when the tree shrinks (the S_i are the halved tree's top digests as the write-back left them), else the block's new root
+  int shrink(uint64_t b_shr, uint32_t depth, uint32_t shrink, uint64_t lp, const u256* levels, size_t n_up, const u256** new_root) {
+    *new_root = shrink ? s0 : upub + n_up - 1;
+    if (!shrink) return VDB_OK;
+    const u256* empty;
+    TRY(poseidon_empty_subtrees_dev(&empty));
+    VDB_LAUNCH(k_annd_shrink_trace, dim3((unsigned)((2 * (depth - 1 + shrink) + 63) / 64)), dim3(64), st, fp->dev, sp, b_shr, depth, shrink, lp, levels, empty, s0);
+    return VDB_OK;
+  }
+  // h: where the head's blocks start
+  int open(Streams streams, const u256* roots, size_t K_, size_t cluster, const AnnHead& h, const MkLayout& mw_, uint64_t total, size_t n_upub, size_t n_extra) {
+    TRY(begin(streams, roots, K_, {cluster}, mw_, total, n_upub, n_extra));
+    TRY(pick(0, h.b_ind, h.b_sel));
+    return sponge(w(0), h.b_old, st_old, iroot);
   }
   int close(const AnnuBlocks& b, const u256* new_root) {
-    VDB_LAUNCH(k_annu_new_roots, dim3((unsigned)((K + 63) / 64)), dim3(64), st, fp->dev, b.b_new, K, new_root, hdr + 1, ind, words_new);
-    return sponge(words_new, b.b_root, st_new, iroot + 1);
+    TRY(replace(0, b.b_new, new_root));
+    return sponge(w(1), b.b_root, st_new, iroot + 1);
   }
-  // the closing of a circuit that replaces word 0 and carries the K cluster roots over (the recentre): no block F, words_new =
+  // the closing of a circuit that replaces word 0 and carries the K cluster roots over (the recentre): no block F, w_1 =
   // [new centroids' root | the header's cluster roots], then G at b_root
   int close_word0(uint64_t b_root, const u256* new_croot) {
-    VDB_HIP(hipMemcpyAsync(words_new, new_croot, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
-    VDB_HIP(hipMemcpyAsync(words_new + 1, hdr + 2, K * sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
-    return sponge(words_new, b_root, st_new, iroot + 1);
+    VDB_HIP(hipMemcpyAsync(w(1), new_croot, sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
+    VDB_HIP(hipMemcpyAsync(w(1) + 1, w(0) + 1, K * sizeof(u256), hipMemcpyDeviceToDevice, ctx().stream));
+    return sponge(w(1), b_root, st_new, iroot + 1);
   }
   // blocks D and G: the sponge over K + 1 words at `base`, its digest to *root
   int sponge(const u256* words, uint64_t base, u256* states, u256* root) {
@@ -2329,17 +2364,13 @@ int wit_ann_delete_dev(u256* levels, const u256* roots, size_t K, size_t cluster
   VDB_ARG(slots, "null pointer");
   TRY(annd_layout(K, cluster, n_c, dim, slots, m, &a, &ml0, &dp));
   TRY(mku_plan(n_c, dim, 0, nullptr, dp.indices.data(), dp.kinds.data(), 2 * m, &pl, dp.carry_src.data()));
-  const u256* empty = nullptr;
-  if (dp.shrink) TRY(poseidon_empty_subtrees_dev(&empty));
   const size_t n_up = 6 * m + 2;
+  const u256* new_root;
   AnnFrame f;
-  TRY(f.open(st, roots, K, cluster, a.b.h, a.mw, a.b.total, n_up, 1));
-  u256* s0 = f.extra;
+  TRY(f.open(st, roots, K, cluster, a.b.h, a.mw, a.b.total, n_up, 0));
   TRY(mku_emit(f.fp, f.sp, pl, levels, dim, nullptr, f.st, a.b.b_upd, f.upub));
-  if (dp.shrink)  // S_i are the halved tree's top digests as the write-back left them
-    VDB_LAUNCH(k_annd_shrink_trace, dim3((unsigned)((2 * (dp.depth - 1 + dp.shrink) + 63) / 64)), dim3(64), f.st, f.fp->dev, f.sp, a.b.b_shr, dp.depth, dp.shrink,
-               pl.lp, levels, empty, s0);
-  TRY(f.close(a.b, dp.shrink ? s0 : f.upub + n_up - 1));
+  TRY(f.shrink(a.b.b_shr, dp.depth, dp.shrink, pl.lp, levels, n_up, &new_root));
+  TRY(f.close(a.b, new_root));
   VDB_LAUNCH(k_annd_public, dim3((unsigned)((4 * m + 3 + 255) / 256)), dim3(256), f.upub, f.hdr, f.iroot, (uint32_t)m, pub);
   return inv_list_fixup(f.st);
 }
@@ -2409,7 +2440,7 @@ static int annmv_layout(size_t K, size_t a, size_t b, size_t n_a, size_t n_b, in
 // state after the batch at its old size; levels_b: b's tree at depth d_b + g, left in the state after the batch; pub: 6 m + 4.
 // The two update blocks take the plan's work space (scratch slot 0) and its one table upload one after the other in stream order: the
 // second block's upload and kernels are queued behind the first block's last kernel, which has read the first table by then.  What the
-// second block needs of the first, the removed leaves, lies in the first block's public row in the frame's own slot.
+// second block needs of the first, the removed leaves, lies in the first block's public row (the frame's upub).
 int wit_ann_move_dev(u256* levels_a, u256* levels_b, const u256* roots, size_t K, size_t a, size_t b, size_t n_a, size_t n_b, int grow,
                      const uint64_t* slots, size_t m, Streams st, u256* pub) {
   static thread_local MkuPlan pa, pb;
@@ -2423,41 +2454,20 @@ int wit_ann_move_dev(u256* levels_a, u256* levels_b, const u256* roots, size_t K
   carry.resize(m);
   for (size_t j = 0; j < m; j++) carry[j] = (uint32_t)(2 + 6 * j);   // the old leaf of a's update 2 j in a's public row: the removed leaf
   TRY(mku_plan(n_b, 1, mp.grow, nullptr, mp.dest.data(), mp.kinds.data(), m, &pb, carry.data(), n_upa));
-  const u256* empty = nullptr;
-  if (mp.d.shrink) TRY(poseidon_empty_subtrees_dev(&empty));
   const AnnMoveBlocks& B = L.b;
-  AnnFrame f;   // its sponge and its fields; the head is laid out here: two indicator blocks, K + 3 header cells
-  f.st = st, f.mw = &L.mw, f.K = (uint32_t)K;
-  const size_t n_st = (size_t)L.mw.nperm * PSD_T;
-  f.hdr = (u256*)scratch_get(7, (K + 3 + 2 * K + 2 + 2 * (K + 1) + 2 + n_upa + n_upb + 1 + 2 * n_st + 8) * sizeof(u256));
-  if (!f.hdr) return VDB_ERR_OOM;
-  u256 *ind_a = f.hdr + K + 3, *ind_b = ind_a + K, *picked = ind_b + K, *words_mid = picked + 2, *words_new = words_mid + K + 1;
-  f.iroot = words_new + K + 1;
-  u256 *upa = f.iroot + 2, *upb = upa + n_upa, *s0 = upb + n_upb;
-  f.st_old = s0 + 1;
-  f.st_new = f.st_old + n_st;
-  TRY(inv_list_attach(f.st, B.total));
-  TRY(mk_begin(f.st, &f.fp, &f.sp));
-  const uint32_t Ku = (uint32_t)K;
-  const u256* words_old = f.hdr + 2;
-  VDB_LAUNCH(k_annmv_header, dim3((unsigned)((K + 3 + 255) / 256)), dim3(256), f.st, (uint32_t)a, (uint32_t)b, roots, Ku, f.hdr);
-  VDB_LAUNCH(k_annu_indicator, dim3((unsigned)((K + 63) / 64)), dim3(64), f.st, f.fp->dev, B.b_ind_a, (uint32_t)a, Ku, ind_a);
-  const NvMap sa{B.b_sel_a, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, Ku, 1u, 1u};
-  VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), f.st, f.fp->dev, sa, 1u, words_old + 1, ind_a, picked);
-  TRY(f.sponge(words_old, B.b_old, f.st_old, f.iroot));
-  TRY(mku_emit(f.fp, f.sp, pa, levels_a, 1, nullptr, f.st, B.b_upd_a, upa));
-  if (mp.d.shrink)
-    VDB_LAUNCH(k_annd_shrink_trace, dim3((unsigned)((2 * (mp.d.depth - 1 + mp.d.shrink) + 63) / 64)), dim3(64), f.st, f.fp->dev, f.sp, B.b_shr, mp.d.depth,
-               mp.d.shrink, pa.lp, levels_a, empty, s0);
-  VDB_LAUNCH(k_annu_new_roots, dim3((unsigned)((K + 63) / 64)), dim3(64), f.st, f.fp->dev, B.b_mid, Ku, mp.d.shrink ? s0 : upa + n_upa - 1, words_old, ind_a,
-             words_mid);
-  VDB_LAUNCH(k_annu_indicator, dim3((unsigned)((K + 63) / 64)), dim3(64), f.st, f.fp->dev, B.b_ind_b, (uint32_t)b, Ku, ind_b);
-  const NvMap sb{B.b_sel_b, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1u, Ku, 1u, 1u};
-  VDB_LAUNCH(k_nv_select, dim3(1), dim3(64), f.st, f.fp->dev, sb, 1u, words_mid + 1, ind_b, picked + 1);
-  TRY(mku_emit(f.fp, f.sp, pb, levels_b, 1, nullptr, f.st, B.b_upd_b, upb, upa));
-  VDB_LAUNCH(k_annu_new_roots, dim3((unsigned)((K + 63) / 64)), dim3(64), f.st, f.fp->dev, B.b_new, Ku, upb + n_upb - 1, words_mid, ind_b, words_new);
-  TRY(f.sponge(words_new, B.b_root, f.st_new, f.iroot + 1));
-  VDB_LAUNCH(k_annmv_public, dim3((unsigned)((6 * m + 4 + 255) / 256)), dim3(256), upa, upb, f.hdr, f.iroot, (uint32_t)m, pub);
+  const u256* root_a;
+  AnnFrame f;
+  TRY(f.begin(st, roots, K, {a, b}, L.mw, B.total, n_upa, n_upb));                                // A
+  TRY(f.pick(0, B.b_ind_a, B.b_sel_a));                                                           // B_a, C_a
+  TRY(f.sponge(f.w(0), B.b_old, f.st_old, f.iroot));                                              // D
+  TRY(mku_emit(f.fp, f.sp, pa, levels_a, 1, nullptr, f.st, B.b_upd_a, f.upub));                   // E'
+  TRY(f.shrink(B.b_shr, mp.d.depth, mp.d.shrink, pa.lp, levels_a, n_upa, &root_a));               // S
+  TRY(f.replace(0, B.b_mid, root_a));                                                             // F_a: w_1 = mid
+  TRY(f.pick(1, B.b_ind_b, B.b_sel_b));                                                           // B_b, C_b
+  TRY(mku_emit(f.fp, f.sp, pb, levels_b, 1, nullptr, f.st, B.b_upd_b, f.extra, f.upub));          // E_b
+  TRY(f.replace(1, B.b_new, f.extra + n_upb - 1));                                                // F_b
+  TRY(f.sponge(f.w(2), B.b_root, f.st_new, f.iroot + 1));                                         // G
+  VDB_LAUNCH(k_annmv_public, dim3((unsigned)((6 * m + 4 + 255) / 256)), dim3(256), f.upub, f.extra, f.hdr, f.iroot, (uint32_t)m, pub);
   return inv_list_fixup(f.st);
 }
 
@@ -3031,21 +3041,36 @@ struct DevStreams {
   int finish() { return st.err ? check_err_flag(st.err) : VDB_OK; }
 };
 
-// What the host-array entry points of the two circuits against the index root share: the cluster's 2 lp levels and the K + 1 roots go
-// up, run(levels, roots, streams, public) emits the circuit, the public row and the levels as the batch left them come back.
+// What the host-array entry points of the batch circuits against the index root share (update, delete, move, write): every tree
+// (levels, lp: its 2 lp digests), the K + 1 roots and the n_vec words of new vectors (none: null, 0) go up, run(levels of the first tree,
+// of the second or null, roots, new vectors, streams, public) emits the circuit, the public row and every tree as the batch left it come back.
 template <class Run>
-static int ann_batch_host(vdb_fr* levels, uint64_t lp, const vdb_fr* roots, size_t K, uint64_t cells, size_t n_pub, vdb_fr* stream_out, uint8_t* selector_out,
-                          vdb_fr* public_out, Run run) {
-  DevBuf dl, dr, dpub;
+static int ann_batch_host(std::initializer_list<std::pair<vdb_fr*, uint64_t>> trees, const vdb_fr* roots, size_t K, const vdb_fr* new_vectors, size_t n_vec,
+                          uint64_t cells, size_t n_pub, vdb_fr* stream_out, uint8_t* selector_out, vdb_fr* public_out, Run run) {
+  DevBuf dl[2], dr, dv, dpub;
   HostStreams hs;
-  TRY(upload(dl, levels, 2 * lp * sizeof(u256)));
+  size_t i = 0;
+  for (auto [levels, lp] : trees) TRY(upload(dl[i++], levels, 2 * lp * sizeof(u256)));
   TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
+  TRY(upload(dv, new_vectors, n_vec * sizeof(u256)));
   TRY(dpub.alloc(n_pub * sizeof(u256)));
   TRY(hs.init(cells, 0, selector_out != nullptr));
-  TRY(run(dl.as<u256>(), dr.as<u256>(), hs.st, dpub.as<u256>()));
+  TRY(run(dl[0].as<u256>(), dl[1].as<u256>(), dr.as<u256>(), dv.as<u256>(), hs.st, dpub.as<u256>()));
   TRY(download(public_out, dpub.p, n_pub * sizeof(u256)));
-  TRY(download(levels, dl.p, 2 * lp * sizeof(u256)));
+  i = 0;
+  for (auto [levels, lp] : trees) TRY(download(levels, dl[i++].p, 2 * lp * sizeof(u256)));
   return hs.finish(stream_out, nullptr, selector_out, cells, 0);
+}
+// and their _dev forms: the pointer refusal (pointers: the entry point's own are all there), the caller's buffers under the rank window,
+// without error word and lookups (GateChip primitives only); run(streams) emits
+template <class Run>
+static int ann_batch_dev(bool pointers, vdb_fr* stream_dev, uint8_t* selector_dev, Run run) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(pointers && stream_dev, "null pointer");
+  DevStreams ds;
+  ds.init(stream_dev, selector_dev);
+  TRY(run(ds.st));
+  return ds.finish();
 }
 // What the host-array entry points of the two audits share: centroids, members and the K + 1 roots go up, run(centroids, members, roots,
 // streams, flags, public) emits the circuit, the n_flags flag bytes and the public row [index_root | c] come back.
@@ -3611,13 +3636,9 @@ int vdb_wit_ann_update_size(size_t K, size_t n_c, size_t dim, size_t m, unsigned
 int vdb_wit_ann_update_dev(vdb_fr* levels_dev, const vdb_fr* roots_dev, size_t K, size_t cluster, size_t n_c, size_t dim, unsigned grow,
                            const vdb_fr* new_vectors_dev, const uint64_t* indices, size_t m, vdb_fr* stream_dev, uint8_t* selector_dev,
                            vdb_fr* public_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(levels_dev && roots_dev && new_vectors_dev && indices && stream_dev && public_dev, "null pointer");
-  DevStreams ds;
-  ds.init(stream_dev, selector_dev);
-  TRY(wit_ann_update_dev(as_u256(levels_dev), as_u256(roots_dev), K, cluster, n_c, dim, grow, as_u256(new_vectors_dev), indices, m, ds.st,
-                         as_u256(public_dev)));
-  return ds.finish();
+  return ann_batch_dev(levels_dev && roots_dev && new_vectors_dev && indices && public_dev, stream_dev, selector_dev, [&](Streams st) {
+    return wit_ann_update_dev(as_u256(levels_dev), as_u256(roots_dev), K, cluster, n_c, dim, grow, as_u256(new_vectors_dev), indices, m, st, as_u256(public_dev));
+  });
 }
 int vdb_wit_ann_update(vdb_fr* levels, const vdb_fr* roots, size_t K, size_t cluster, size_t n_c, size_t dim, unsigned grow, const vdb_fr* new_vectors,
                        const uint64_t* indices, size_t m, vdb_fr* stream_out, uint8_t* selector_out, vdb_fr* public_out) {
@@ -3631,11 +3652,10 @@ int vdb_wit_ann_update(vdb_fr* levels, const vdb_fr* roots, size_t K, size_t clu
   tree_shape(n_c, &lp, &d);
   lp <<= grow;
   VDB_ARG(annu_track_fill(indices, m, n_c, lp, nullptr, nullptr) == 0, "a write above the cluster's fill at its turn or outside the grown tree");
-  DevBuf dv;
-  TRY(upload(dv, new_vectors, ml.n_vec * sizeof(u256)));
-  return ann_batch_host(levels, lp, roots, K, a.b.total, 3 * m + 3, stream_out, selector_out, public_out, [&](u256* dl, const u256* dr, Streams st, u256* dpub) {
-    return wit_ann_update_dev(dl, dr, K, cluster, n_c, dim, grow, dv.as<u256>(), indices, m, st, dpub);
-  });
+  const auto run = [&](u256* dl, u256*, const u256* dr, const u256* dv, Streams st, u256* dpub) {
+    return wit_ann_update_dev(dl, dr, K, cluster, n_c, dim, grow, dv, indices, m, st, dpub);
+  };
+  return ann_batch_host({{levels, lp}}, roots, K, new_vectors, ml.n_vec, a.b.total, 3 * m + 3, stream_out, selector_out, public_out, run);
 }
 
 // deletes against the index root (include/vdb.h); the index after them: resident.hip
@@ -3654,12 +3674,9 @@ int vdb_wit_ann_delete_size(size_t K, size_t n_c, size_t dim, size_t m, uint64_t
 }
 int vdb_wit_ann_delete_dev(vdb_fr* levels_dev, const vdb_fr* roots_dev, size_t K, size_t cluster, size_t n_c, size_t dim, const uint64_t* slots, size_t m,
                            vdb_fr* stream_dev, uint8_t* selector_dev, vdb_fr* public_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(levels_dev && roots_dev && slots && stream_dev && public_dev, "null pointer");
-  DevStreams ds;
-  ds.init(stream_dev, selector_dev);
-  TRY(wit_ann_delete_dev(as_u256(levels_dev), as_u256(roots_dev), K, cluster, n_c, dim, slots, m, ds.st, as_u256(public_dev)));
-  return ds.finish();
+  return ann_batch_dev(levels_dev && roots_dev && slots && public_dev, stream_dev, selector_dev, [&](Streams st) {
+    return wit_ann_delete_dev(as_u256(levels_dev), as_u256(roots_dev), K, cluster, n_c, dim, slots, m, st, as_u256(public_dev));
+  });
 }
 int vdb_wit_ann_delete(vdb_fr* levels, const vdb_fr* roots, size_t K, size_t cluster, size_t n_c, size_t dim, const uint64_t* slots, size_t m,
                        vdb_fr* stream_out, uint8_t* selector_out, vdb_fr* public_out) {
@@ -3669,9 +3686,10 @@ int vdb_wit_ann_delete(vdb_fr* levels, const vdb_fr* roots, size_t K, size_t clu
   MkuLayout ml;
   AnndPlan dp;
   TRY(annd_layout(K, cluster, n_c, dim, slots, m, &a, &ml, &dp));
-  return ann_batch_host(levels, dp.lp, roots, K, a.b.total, 4 * m + 3, stream_out, selector_out, public_out, [&](u256* dl, const u256* dr, Streams st, u256* dpub) {
+  const auto run = [&](u256* dl, u256*, const u256* dr, const u256*, Streams st, u256* dpub) {
     return wit_ann_delete_dev(dl, dr, K, cluster, n_c, dim, slots, m, st, dpub);
-  });
+  };
+  return ann_batch_host({{levels, dp.lp}}, roots, K, nullptr, 0, a.b.total, 4 * m + 3, stream_out, selector_out, public_out, run);
 }
 
 // moves from one cluster to another against the index root (include/vdb.h); the index after them: resident.hip
@@ -3691,14 +3709,11 @@ int vdb_wit_ann_move_size(size_t K, size_t n_a, size_t n_b, size_t m, uint64_t* 
 }
 int vdb_wit_ann_move_dev(vdb_fr* levels_src_dev, vdb_fr* levels_dst_dev, const vdb_fr* roots_dev, size_t K, size_t src, size_t dst, size_t n_a, size_t n_b,
                          unsigned grow, const uint64_t* slots, size_t m, vdb_fr* stream_dev, uint8_t* selector_dev, vdb_fr* public_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(levels_src_dev && levels_dst_dev && roots_dev && slots && stream_dev && public_dev, "null pointer");
-  VDB_ARG(grow <= 30, "more than 30 doublings");
-  DevStreams ds;
-  ds.init(stream_dev, selector_dev);
-  TRY(wit_ann_move_dev(as_u256(levels_src_dev), as_u256(levels_dst_dev), as_u256(roots_dev), K, src, dst, n_a, n_b, (int)grow, slots, m, ds.st,
-                       as_u256(public_dev)));
-  return ds.finish();
+  return ann_batch_dev(levels_src_dev && levels_dst_dev && roots_dev && slots && public_dev, stream_dev, selector_dev, [&](Streams st) -> int {
+    VDB_ARG(grow <= 30, "more than 30 doublings");
+    return wit_ann_move_dev(as_u256(levels_src_dev), as_u256(levels_dst_dev), as_u256(roots_dev), K, src, dst, n_a, n_b, (int)grow, slots, m, st,
+                            as_u256(public_dev));
+  });
 }
 int vdb_wit_ann_move(vdb_fr* levels_src, vdb_fr* levels_dst, const vdb_fr* roots, size_t K, size_t src, size_t dst, size_t n_a, size_t n_b, unsigned grow,
                      const uint64_t* slots, size_t m, vdb_fr* stream_out, uint8_t* selector_out, vdb_fr* public_out) {
@@ -3708,19 +3723,10 @@ int vdb_wit_ann_move(vdb_fr* levels_src, vdb_fr* levels_dst, const vdb_fr* roots
   AnnMoveLayout L;
   AnnMovePlan mp;
   TRY(annmv_layout(K, src, dst, n_a, n_b, (int)grow, slots, m, &L, &mp));
-  DevBuf da, db, dr, dpub;
-  HostStreams hs;
-  const size_t n_pub = 6 * m + 4;
-  TRY(upload(da, levels_src, 2 * mp.d.lp * sizeof(u256)));
-  TRY(upload(db, levels_dst, 2 * mp.glp_b * sizeof(u256)));
-  TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
-  TRY(dpub.alloc(n_pub * sizeof(u256)));
-  TRY(hs.init(L.b.total, 0, selector_out != nullptr));
-  TRY(wit_ann_move_dev(da.as<u256>(), db.as<u256>(), dr.as<u256>(), K, src, dst, n_a, n_b, (int)grow, slots, m, hs.st, dpub.as<u256>()));
-  TRY(download(public_out, dpub.p, n_pub * sizeof(u256)));
-  TRY(download(levels_src, da.p, 2 * mp.d.lp * sizeof(u256)));
-  TRY(download(levels_dst, db.p, 2 * mp.glp_b * sizeof(u256)));
-  return hs.finish(stream_out, nullptr, selector_out, L.b.total, 0);
+  const auto run = [&](u256* da, u256* db, const u256* dr, const u256*, Streams st, u256* dpub) {
+    return wit_ann_move_dev(da, db, dr, K, src, dst, n_a, n_b, (int)grow, slots, m, st, dpub);
+  };
+  return ann_batch_host({{levels_src, mp.d.lp}, {levels_dst, mp.glp_b}}, roots, K, nullptr, 0, L.b.total, 6 * m + 4, stream_out, selector_out, public_out, run);
 }
 
 // linked writes: one batch against the database root and the index root (include/vdb.h); the index after them: resident.hip
@@ -3761,14 +3767,12 @@ int vdb_ann_write_db_indices(const uint64_t* cluster_slots, size_t n_c, size_t n
 int vdb_wit_ann_write_dev(vdb_fr* levels_c_dev, vdb_fr* levels_db_dev, const vdb_fr* roots_dev, size_t K, size_t cluster, size_t n_c, size_t n_db, size_t dim,
                           unsigned grow_c, unsigned grow_db, const vdb_fr* new_vectors_dev, const uint64_t* indices, const uint64_t* db_indices, size_t m,
                           vdb_fr* stream_dev, uint8_t* selector_dev, vdb_fr* public_dev) {
-  VDB_REQUIRE_INIT();
-  VDB_ARG(levels_c_dev && levels_db_dev && roots_dev && new_vectors_dev && indices && db_indices && stream_dev && public_dev, "null pointer");
-  VDB_ARG(grow_c <= 30 && grow_db <= 30, "more than 30 doublings");
-  DevStreams ds;
-  ds.init(stream_dev, selector_dev);
-  TRY(wit_ann_write_dev(as_u256(levels_c_dev), as_u256(levels_db_dev), as_u256(roots_dev), K, cluster, n_c, n_db, dim, grow_c, (int)grow_db,
-                        as_u256(new_vectors_dev), indices, db_indices, m, ds.st, as_u256(public_dev)));
-  return ds.finish();
+  const bool pointers = levels_c_dev && levels_db_dev && roots_dev && new_vectors_dev && indices && db_indices && public_dev;
+  return ann_batch_dev(pointers, stream_dev, selector_dev, [&](Streams st) -> int {
+    VDB_ARG(grow_c <= 30 && grow_db <= 30, "more than 30 doublings");
+    return wit_ann_write_dev(as_u256(levels_c_dev), as_u256(levels_db_dev), as_u256(roots_dev), K, cluster, n_c, n_db, dim, grow_c, (int)grow_db,
+                             as_u256(new_vectors_dev), indices, db_indices, m, st, as_u256(public_dev));
+  });
 }
 int vdb_wit_ann_write(vdb_fr* levels_c, vdb_fr* levels_db, const vdb_fr* roots, size_t K, size_t cluster, size_t n_c, size_t n_db, size_t dim, unsigned grow_c,
                       unsigned grow_db, const vdb_fr* new_vectors, const uint64_t* indices, const uint64_t* db_indices, size_t m, vdb_fr* stream_out,
@@ -3783,21 +3787,11 @@ int vdb_wit_ann_write(vdb_fr* levels_c, vdb_fr* levels_db, const vdb_fr* roots, 
   uint32_t d;
   tree_shape(n_c, &lp_c, &d);
   lp_c <<= grow_c;
-  DevBuf dc, db, dr, dv, dpub;
-  HostStreams hs;
-  const size_t n_pub = L.b.n_pub;
-  TRY(upload(dc, levels_c, 2 * lp_c * sizeof(u256)));
-  TRY(upload(db, levels_db, 2 * wp.glp_db * sizeof(u256)));
-  TRY(upload(dr, roots, (K + 1) * sizeof(u256)));
-  TRY(upload(dv, new_vectors, L.me.n_vec * sizeof(u256)));
-  TRY(dpub.alloc(n_pub * sizeof(u256)));
-  TRY(hs.init(L.b.u.total, 0, selector_out != nullptr));
-  TRY(wit_ann_write_dev(dc.as<u256>(), db.as<u256>(), dr.as<u256>(), K, cluster, n_c, n_db, dim, grow_c, (int)grow_db, dv.as<u256>(), indices, db_indices, m,
-                        hs.st, dpub.as<u256>()));
-  TRY(download(public_out, dpub.p, n_pub * sizeof(u256)));
-  TRY(download(levels_c, dc.p, 2 * lp_c * sizeof(u256)));
-  TRY(download(levels_db, db.p, 2 * wp.glp_db * sizeof(u256)));
-  return hs.finish(stream_out, nullptr, selector_out, L.b.u.total, 0);
+  const auto run = [&](u256* dc, u256* ddb, const u256* dr, const u256* dv, Streams st, u256* dpub) {
+    return wit_ann_write_dev(dc, ddb, dr, K, cluster, n_c, n_db, dim, grow_c, (int)grow_db, dv, indices, db_indices, m, st, dpub);
+  };
+  return ann_batch_host({{levels_c, lp_c}, {levels_db, wp.glp_db}}, roots, K, new_vectors, L.me.n_vec, L.b.u.total, L.b.n_pub, stream_out, selector_out,
+                        public_out, run);
 }
 
 // the audit of one cluster's routing (include/vdb.h)
@@ -3868,7 +3862,8 @@ int vdb_wit_ann_mean(uint32_t P, uint32_t L, const vdb_fr* centroids, const vdb_
   return ann_cluster_host(centroids, members, roots, K, n_c, dim, a.b.f.total, a.b.total_l, dim, stream_out, lookup_out, selector_out, mean_ok_out, public_out, run);
 }
 
-// the recentre of one cluster (include/vdb.h)
+// the recentre of one cluster (include/vdb.h).  Its two forms stand alone: beside the tree that ann_batch_host carries it has the
+// members, lookups under (P, L) and new_centroid, and of what ann_cluster_host carries it has no centroids and no flags
 int vdb_wit_ann_recentre_size(uint32_t P, uint32_t L, size_t K, size_t n_c, size_t dim, uint64_t* cells, uint64_t* lookups, uint64_t* input_cells,
                               uint64_t* update_base) {
   VDB_REQUIRE_INIT();
