@@ -1165,6 +1165,12 @@ def _place_path(B, perm, lay, levels_at, bits, sibs, curs):
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # Merkle path updates (include/vdb.h vdb_wit_merkle_update; pipeline.UpdateHotPath)
+def _ladder_cells(depth, count, node_cells):
+    """cells of the zero ladder of a tree of `depth` levels: Z_0, depth - 1 hashes Z_{l+1} = H(Z_l, Z_l), `count` folds of a running top
+    with Z_{depth - count + i} (an update's growth block; behind S_0, an index delete's block S)"""
+    return 1 + (depth - 1 + count) * node_cells
+
+
 def merkle_update_layout(m, dim, depth, kinds=None, grow=0, carried=False):
     """where the cells of a batch of m path updates lie: dict(nperm, n_ins, sizes, leaf_cells, node_cells, level_cells, ip_cells,
     per_update, n_vec, old_leaf, bits, sibs, n_in, total) — the last five stream cells: [new vectors | old leaves | bits | siblings],
@@ -1188,7 +1194,7 @@ def merkle_update_layout(m, dim, depth, kinds=None, grow=0, carried=False):
     lay["per_update"] = lay["leaf_cells"] + depth * lay["level_cells"] + lay["ip_cells"]
     lay["n_in"] = w * dim + m * (1 + 2 * depth) + (1 if grow else 0)
     lay["r0"], lay["z0"] = (lay["n_in"] - 1, lay["n_in"]) if grow else (None, None)
-    lay["grow_cells"] = 1 + (depth - 1 + grow) * lay["node_cells"] if grow else 0
+    lay["grow_cells"] = _ladder_cells(depth, grow, lay["node_cells"]) if grow else 0
     at, wn = lay["n_in"] + lay["grow_cells"], 0
     lay["block"], lay["levels_at"], lay["write_no"] = [], [], []
     for k in kinds:
@@ -1314,20 +1320,27 @@ class _CellTrace:
                        np.asarray(self.gate, dtype=bool), np.zeros(0, dtype=np.int64))
 
 
+def _trace_ladder(t, z0, top, depth, count, node_cells):
+    """the zero ladder (_ladder_cells) traced into `t`: Z_0 = ctx.load_constant(0) at cell `z0`, behind it the hashes of Z with itself,
+    then the folds of the running digest that starts at cell `top` -> (the last fold's digest, the first cell after the ladder)"""
+    at = t.put(z0, [("k", 0)], [0])
+    z = [z0]
+    for l in range(depth - 1):
+        z.append(t.node(at, z[l], z[l]))
+        at += node_cells
+    for i in range(count):
+        top = t.node(at, top, z[depth - count + i])
+        at += node_cells
+    return top, at
+
+
 def _trace_update_block(t, lay, base):
     """the cells of a batch of updates (lay: merkle_update_layout) traced into `t` from stream cell `base` on -> the public cells"""
     m, grow = len(lay["kinds"]), lay["grow"]
     dim, depth = lay["n_vec"] // max(lay["w"], 1), (lay["sibs"] - lay["bits"]) // m
     idx_cells, new_leaves, prev_top, top_old0 = [], [], None, None
     if grow:
-        at = t.put(base + lay["z0"], [("k", 0)], [0])         # Z_0 = ctx.load_constant(0)
-        z, prev_top = [base + lay["z0"]], base + lay["r0"]
-        for l in range(depth - 1):
-            z.append(t.node(at, z[l], z[l]))
-            at += lay["node_cells"]
-        for i in range(grow):
-            prev_top = t.node(at, prev_top, z[depth - grow + i])
-            at += lay["node_cells"]
+        prev_top, at = _trace_ladder(t, base + lay["z0"], base + lay["r0"], depth, grow, lay["node_cells"])
         assert at == base + lay["block"][0]
     for j in range(m):
         if lay["kinds"][j]:
@@ -1362,6 +1375,20 @@ def trace_merkle_update(m, dim, depth, fetch_flags, fetch_values, kinds=None, gr
     return t.finish(), public
 
 
+def _place_ladder(B, perm, z0, top, depth, count, node_cells):
+    """_trace_ladder's cells placed into builder `B`, the hashes one after the other (perm: _perm_placer's) -> as _trace_ladder"""
+    one = lambda c: np.asarray([c], dtype=np.int64)
+    B.constant_cell(z0, 0)                                   # Z_0 = ctx.load_constant(0)
+    z, top, at = [one(z0)], one(top), z0 + 1
+    for l in range(depth - 1):
+        z.append(_node(perm, one(at), z[l], z[l]))
+        at += node_cells
+    for i in range(count):
+        top = _node(perm, one(at), top, z[depth - count + i])
+        at += node_cells
+    return int(top[0]), at
+
+
 def place_merkle_update(B, m, dim, depth, fetch_flags, fetch_values, base=0, kinds=None, grow=0, carried=False):
     """trace_merkle_update's cells placed into builder `B` from stream cell `base` on, from unit blocks — one per kind of permutation,
     the bit with its two selects, the two selects of the new path, the index inner product — each placed for all m updates at once, level
@@ -1372,18 +1399,8 @@ def place_merkle_update(B, m, dim, depth, fetch_flags, fetch_values, base=0, kin
     j = np.arange(m, dtype=np.int64)
     blocks = base + np.asarray(lay["block"], dtype=np.int64)
     perm = _perm_placer(B, fetch_flags, fetch_values)
-    top = None
     if grow:
-        B.constant_cell(base + lay["z0"], 0)                 # Z_0 = ctx.load_constant(0)
-        one = lambda c: np.asarray([c], dtype=np.int64)
-        z, top, at = [one(base + lay["z0"])], one(base + lay["r0"]), base + lay["z0"] + 1
-        for l in range(depth - 1):
-            z.append(_node(perm, one(at), z[l], z[l]))
-            at += lay["node_cells"]
-        for i in range(grow):
-            top = _node(perm, one(at), top, z[depth - grow + i])
-            at += lay["node_cells"]
-
+        top, _ = _place_ladder(B, perm, base + lay["z0"], base + lay["r0"], depth, grow, lay["node_cells"])
     is_write = np.asarray(lay["kinds"], dtype=np.int64) == 0
     new_leaf = blocks.copy()                                 # a delete: its block starts with new_leaf = ctx.load_constant(0)
     for c in blocks[np.asarray(lay["kinds"], dtype=np.int64) == 1]:
@@ -1395,7 +1412,7 @@ def place_merkle_update(B, m, dim, depth, fetch_flags, fetch_values, base=0, kin
     (cur_old, cur_new), idx = _place_path(B, perm, lay, base + np.asarray(lay["levels_at"], dtype=np.int64), lay["bits"] + path, lay["sibs"] + path,
                                           [base + lay["old_leaf"] + j, new_leaf])
     if grow:
-        B.tie(int(cur_old[0]), int(top[0]))                  # ctx.constrain_equal(cur_old, R_grow)
+        B.tie(int(cur_old[0]), top)                          # ctx.constrain_equal(cur_old, R_grow)
     for k in range(1, m):
         B.tie(int(cur_old[k]), int(cur_new[k - 1]))          # ctx.constrain_equal(cur_old, root_{j-1})
     return merkle_update_instances(m, base + lay["r0"] if grow else cur_old[0], idx, base + lay["old_leaf"] + j, new_leaf, cur_new[m - 1])
@@ -1412,19 +1429,32 @@ def build_merkle_update(m, dim, depth, fetch_flags, fetch_values, builder=None, 
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # Inserts and replacements against the index root (include/vdb.h vdb_wit_ann_update; pipeline.AnnUpdateHotPath)
-def _ann_frame_layout(K, sp, inner_cells):
-    """The frame of a circuit against the index root (the update's and the delete's) around `inner_cells` cells of its own: dict(c,
-    centroids_root, roots: the assigned header A; n_in; indicator B, select C, sponge_old D, update: the inner block, new_roots F,
-    sponge_new G: the blocks; total; sponge: sp = merkle_leaf_layout(K + 1))"""
+def _frame_cells(K):
+    """(cells of an indicator block: is_zero 8, then sub 4 + is_zero 8 for every j >= 1; of select_by_indicator over K cells: the
+    leading zero, then [cell, indicator, sum] each; of K selects)"""
+    return 8 + 12 * (K - 1), 1 + 3 * K, 8 * K
+
+
+def _ann_head_layout(K, extra=0):
+    """The head of a circuit against the index root: dict(c, centroids_root, roots: the assigned header A [c | `extra` cells of the
+    circuit's own | centroids_root | K cluster roots]; n_in; indicator B, select C, sponge_old D: the blocks; update: where the head
+    ends; sponge: merkle_leaf_layout(K + 1))"""
     if K < 1:
         raise ValueError("an index has at least one cluster")
-    lay = dict(c=0, centroids_root=1, roots=2, n_in=K + 2, indicator=K + 2, sponge=sp)
-    lay["select"] = lay["indicator"] + 8 + 12 * (K - 1)
-    lay["sponge_old"] = lay["select"] + 1 + 3 * K
-    lay["update"] = lay["sponge_old"] + sp["leaf_cells"]
+    lay = dict(c=0, centroids_root=1 + extra, roots=2 + extra, n_in=K + 2 + extra, indicator=K + 2 + extra, sponge=merkle_leaf_layout(K + 1))
+    lay["select"] = lay["indicator"] + _frame_cells(K)[0]
+    lay["sponge_old"] = lay["select"] + _frame_cells(K)[1]
+    lay["update"] = lay["sponge_old"] + lay["sponge"]["leaf_cells"]
+    return lay
+
+
+def _ann_frame_layout(K, inner_cells, extra=0):
+    """The frame of a circuit against the index root around `inner_cells` cells of its own: _ann_head_layout's keys; new_roots F,
+    sponge_new G: the blocks behind the inner ones, which start at `update`; total"""
+    lay = _ann_head_layout(K, extra)
     lay["new_roots"] = lay["update"] + inner_cells
-    lay["sponge_new"] = lay["new_roots"] + 8 * K
-    lay["total"] = lay["sponge_new"] + sp["leaf_cells"]
+    lay["sponge_new"] = lay["new_roots"] + _frame_cells(K)[2]
+    lay["total"] = lay["sponge_new"] + lay["sponge"]["leaf_cells"]
     return lay
 
 
@@ -1432,11 +1462,16 @@ def ann_update_layout(K, m, dim, depth, grow=0):
     """where the blocks of the index update circuit start: _ann_frame_layout's keys and update_layout: merkle_update_layout of block E
     (relative to `update`)"""
     upd = merkle_update_layout(m, dim, depth, None, grow)
-    return dict(_ann_frame_layout(K, merkle_leaf_layout(K + 1), upd["total"]), update_layout=upd)
+    return dict(_ann_frame_layout(K, upd["total"]), update_layout=upd)
 
 
 def _indicator_at(lay, j):
-    return lay["indicator"] + (8 + 12 * (j - 1) if j else 0)
+    return lay["indicator"] + (_frame_cells(j)[0] if j else 0)
+
+
+def _frame_info(lay, inds, picked, root_old, root_new, **own):
+    """what both forms of every circuit of the frame report beside their `own` keys, cells as Python integers"""
+    return dict(own, indicators=[int(i) for i in inds], picked=picked, index_root_old=root_old, index_root_new=root_new, layout=lay)
 
 
 def ann_update_instances(index_root_old, c, update_public, index_root_new):
@@ -1445,30 +1480,41 @@ def ann_update_instances(index_root_old, c, update_public, index_root_new):
     return [int(index_root_old), int(c)] + [int(x) for x in update_public[1:-1]] + [int(index_root_new)]
 
 
-def _trace_ann_head(t, lay):
-    """blocks A - D of the frame on a _CellTrace: the header assigned, idx_to_indicator(c, K) as select_from_idx unrolls it,
-    select_by_indicator(cluster roots, indicators) -> picked, the sponge over the header's roots.  -> (inds, picked, root_old)"""
-    K = lay["n_in"] - 2
-    c, roots = lay["c"], [lay["roots"] + j for j in range(K)]
+def _trace_indicators(t, lay, roots):
+    """blocks B and C on a _CellTrace: idx_to_indicator(lay.c, K) as select_from_idx unrolls it and select_by_indicator(roots,
+    indicators) -> (inds, picked)"""
+    c = lay["c"]
     inds = [t.is_zero(lay["indicator"], c)]
-    for j in range(1, K):
+    for j in range(1, len(roots)):
         at = _indicator_at(lay, j)
         t.put(at, [None, ("k", j), ("k", 1), ("c", c)], [1, 0, 0, 0])      # is_equal(c, Constant(j)) = sub [d, j, 1, c] + is_zero(d)
         inds.append(t.is_zero(at + 4, at))
     cells, gates = [("k", 0)], [1]
-    for j in range(K):
+    for j in range(len(roots)):
         cells += [("c", roots[j]), ("c", inds[j]), None]
-        gates += [0, 0, j + 1 < K]
-    picked = t.put(lay["select"], cells, gates) - 1
+        gates += [0, 0, j + 1 < len(roots)]
+    return inds, t.put(lay["select"], cells, gates) - 1
+
+
+def _trace_ann_head(t, lay):
+    """blocks A - D of the frame on a _CellTrace: the header assigned, B and C over its cluster roots (_trace_indicators), the sponge
+    over the header's roots.  -> (inds, picked, root_old)"""
+    roots = list(range(lay["roots"], lay["n_in"]))
+    inds, picked = _trace_indicators(t, lay, roots)
     root_old, at = t.leaf(lay["sponge_old"], lay["sponge"], None, [lay["centroids_root"]] + roots)
     assert at == lay["update"]
     return inds, picked, root_old
 
 
-def _trace_ann_tail(t, lay, inds, new_root):
-    """blocks F and G: out_j = select(new_root, cluster_root_j, indicator_j), the sponge over [centroids_root | out_j].
-    -> (outs, root_new)"""
-    outs = [t.select(lay["new_roots"] + 8 * j, new_root, lay["roots"] + j, inds[j]) for j in range(len(inds))]
+def _trace_selects(t, at, new_root, olds, inds):
+    """out_j = select(new_root, olds_j, inds_j) at at + 8 j -> the out cells"""
+    return [t.select(at + 8 * j, new_root, olds[j], inds[j]) for j in range(len(inds))]
+
+
+def _trace_ann_tail(t, lay, inds, new_root, olds=None):
+    """blocks F and G: out_j = select(new_root, olds_j, indicator_j) (olds None: the header's cluster roots), the sponge over
+    [centroids_root | out_j].  -> (outs, root_new)"""
+    outs = _trace_selects(t, lay["new_roots"], new_root, range(lay["roots"], lay["n_in"]) if olds is None else olds, inds)
     root_new, at = t.leaf(lay["sponge_new"], lay["sponge"], None, [lay["centroids_root"]] + outs)
     assert at == lay["total"]
     return outs, root_new
@@ -1486,18 +1532,14 @@ def trace_ann_update(K, m, dim, depth, fetch_flags, fetch_values, grow=0):
     upub = _trace_update_block(t, lay["update_layout"], lay["update"])
     t.copy_of[upub[0]] = picked                              # ctx.constrain_equal(picked, the update block's old root)
     outs, root_new = _trace_ann_tail(t, lay, inds, upub[-1])
-    info = dict(indicators=inds, picked=picked, old_root=upub[0], new_root=upub[-1], outs=outs, index_root_old=root_old, index_root_new=root_new, layout=lay)
+    info = _frame_info(lay, inds, picked, root_old, root_new, old_root=upub[0], new_root=upub[-1], outs=outs)
     return t.finish(), ann_update_instances(root_old, lay["c"], upub, root_new), info
 
 
-def _build_ann_head(lay, fetch_flags, fetch_values, builder):
-    """blocks A - D of the frame from unit blocks on a new builder: is_equal(c, Constant(j)) placed for all j >= 1 at once (its
-    constant j set per instance), select_by_indicator over K cells, the sponge (place_sponge).  -> (B, inds, picked, root_old)"""
-    if np.asarray(fetch_flags(0, lay["n_in"])).any():
-        raise ValueError("the assigned header carries no gate or constant flag")
-    B = (builder or _Builder)(lay["total"], lay.get("total_l", 0))
-    K = lay["n_in"] - 2
-    c, roots = lay["c"], lay["roots"] + np.arange(K, dtype=np.int64)
+def _build_indicators(B, lay, roots):
+    """blocks B and C from unit blocks on builder B: is_equal(c, Constant(j)) placed for all j >= 1 at once (its constant j set per
+    instance), select_by_indicator over the K cells `roots` -> (inds, picked)"""
+    K, c = len(roots), lay["c"]
     s = Sym(0, 0)
     iz = Block(s, [s.g_is_zero(ext(0))])
     inds = [int(B.place(iz, [lay["indicator"]], [0], [[c]])[0, 0])]
@@ -1513,19 +1555,35 @@ def _build_ann_head(lay, fetch_flags, fetch_values, builder):
     inds = np.asarray(inds, dtype=np.int64)
     s = Sym(0, 0)
     sb = Block(s, [s.g_select_by_indicator([ext(i) for i in range(K)], [ext(K + i) for i in range(K)])])
-    picked = int(B.place(sb, [lay["select"]], [0], np.concatenate([roots, inds])[None, :])[0, 0])
+    return inds, int(B.place(sb, [lay["select"]], [0], np.concatenate([np.asarray(roots, dtype=np.int64), inds])[None, :])[0, 0])
+
+
+def _build_ann_head(lay, fetch_flags, fetch_values, builder):
+    """blocks A - D of the frame from unit blocks on a new builder: the header checked, B and C over its cluster roots
+    (_build_indicators), the sponge (place_sponge).  -> (B, inds, picked, root_old)"""
+    if np.asarray(fetch_flags(0, lay["n_in"])).any():
+        raise ValueError("the assigned header carries no gate or constant flag")
+    B = (builder or _Builder)(lay["total"], lay.get("total_l", 0))
+    roots = np.arange(lay["roots"], lay["n_in"], dtype=np.int64)
+    inds, picked = _build_indicators(B, lay, roots)
     root_old, end = place_sponge(B, lay["sponge_old"], [lay["centroids_root"]] + [int(r) for r in roots], fetch_flags, fetch_values)
     assert end == lay["update"]
     return B, inds, picked, root_old
 
 
-def _build_ann_tail(B, lay, inds, new_root, fetch_flags, fetch_values):
-    """blocks F and G: the K selects placed at once, the sponge over [centroids_root | out_j].  -> (outs, root_new)"""
+def _build_selects(B, at, new_root, olds, inds):
+    """out_j = select(new_root, olds_j, inds_j) at at + 8 j, placed at once -> the out cells"""
     K = len(inds)
     s = Sym(0, 0)
     sl = Block(s, [s.g_select(ext(0), ext(1), ext(2))])
-    outs = B.place(sl, lay["new_roots"] + 8 * np.arange(K, dtype=np.int64), np.zeros(K, dtype=np.int64),
-                   np.stack([np.full(K, new_root, dtype=np.int64), lay["roots"] + np.arange(K, dtype=np.int64), inds], axis=1))[:, 0]
+    return B.place(sl, at + 8 * np.arange(K, dtype=np.int64), np.zeros(K, dtype=np.int64),
+                   np.stack([np.full(K, new_root, dtype=np.int64), np.asarray(olds, dtype=np.int64), np.asarray(inds, dtype=np.int64)], axis=1))[:, 0]
+
+
+def _build_ann_tail(B, lay, inds, new_root, fetch_flags, fetch_values, olds=None):
+    """blocks F and G: the K selects placed at once (_build_selects; olds None: over the header's cluster roots), the sponge over
+    [centroids_root | out_j].  -> (outs, root_new)"""
+    outs = _build_selects(B, lay["new_roots"], new_root, np.arange(lay["roots"], lay["n_in"]) if olds is None else olds, inds)
     root_new, end = place_sponge(B, lay["sponge_new"], [lay["centroids_root"]] + [int(o) for o in outs], fetch_flags, fetch_values)
     if end != lay["total"]:
         raise ValueError("the trace does not end where the circuit does")
@@ -1541,8 +1599,7 @@ def build_ann_update(K, m, dim, depth, fetch_flags, fetch_values, builder=None, 
     upub = place_merkle_update(B, m, dim, depth, fetch_flags, fetch_values, lay["update"], None, grow)
     B.tie(upub[0], picked)                                   # ctx.constrain_equal(picked, the update block's old root)
     outs, root_new = _build_ann_tail(B, lay, inds, upub[-1], fetch_flags, fetch_values)
-    info = dict(indicators=[int(i) for i in inds], picked=picked, old_root=upub[0], new_root=upub[-1], outs=outs, index_root_old=root_old,
-                index_root_new=root_new, layout=lay)
+    info = _frame_info(lay, inds, picked, root_old, root_new, old_root=upub[0], new_root=upub[-1], outs=outs)
     return B.finish(), ann_update_instances(root_old, lay["c"], upub, root_new), info
 
 
@@ -1554,7 +1611,7 @@ def ann_write_layout(K, m, dim, depth, grow, depth_db, grow_db):
     (`depth_db` the grown one)"""
     upd = merkle_update_layout(m, dim, depth, None, grow)
     upd_db = merkle_update_layout(m, 1, depth_db, [2] * m, grow_db, carried=True)
-    lay = dict(_ann_frame_layout(K, merkle_leaf_layout(K + 1), upd["total"] + upd_db["total"]), update_layout=upd, update_db_layout=upd_db)
+    lay = dict(_ann_frame_layout(K, upd["total"] + upd_db["total"]), update_layout=upd, update_db_layout=upd_db)
     lay["update_db"] = lay["update"] + upd["total"]
     return lay
 
@@ -1595,7 +1652,7 @@ def trace_ann_write(K, m, dim, depth, fetch_flags, fetch_values, grow=0, depth_d
     for x, y in zip(info["old_leaves_db"], info["old_leaves"]):
         t.copy_of[x] = y                                     # and loses the digest the cluster loses
     outs, root_new = _trace_ann_tail(t, lay, inds, upub[-1])
-    info = dict(info, indicators=inds, picked=picked, outs=outs, index_root_old=root_old, index_root_new=root_new, layout=lay)
+    info = _frame_info(lay, inds, picked, root_old, root_new, outs=outs, **info)
     return t.finish(), ann_write_instances(root_old, lay["c"], upub, updb, root_new), info
 
 
@@ -1613,7 +1670,7 @@ def build_ann_write(K, m, dim, depth, fetch_flags, fetch_values, builder=None, g
     for x, y in zip(info["old_leaves_db"], info["old_leaves"]):
         B.tie(x, y)                                          # and loses the digest the cluster loses
     outs, root_new = _build_ann_tail(B, lay, inds, upub[-1], fetch_flags, fetch_values)
-    info = dict(info, indicators=[int(i) for i in inds], picked=picked, outs=outs, index_root_old=root_old, index_root_new=root_new, layout=lay)
+    info = _frame_info(lay, inds, picked, root_old, root_new, outs=outs, **info)
     return B.finish(), ann_write_instances(root_old, lay["c"], upub, updb, root_new), info
 
 
@@ -1627,6 +1684,11 @@ def ann_delete_shrink(n_c, m):
     return depth, depth - (n_c - m - 1).bit_length()
 
 
+def _shrink_cells(depth, shrink, node_cells):
+    """cells of block S [S_0 | the zero ladder with `shrink` folds from S_0 up]; 0 when the tree keeps its size"""
+    return 1 + _ladder_cells(depth, shrink, node_cells) if shrink else 0
+
+
 def ann_delete_layout(K, m, dim, depth, shrink=0):
     """where the blocks of the index delete circuit start: _ann_frame_layout's keys, update_layout (merkle_update_layout of block E' over
     the 2 m path updates [carried, delete] * m), `shrink`: the first cell of block S [S_0 | Z_0 | Z hashes depth - 1 | S hashes s]
@@ -1634,8 +1696,8 @@ def ann_delete_layout(K, m, dim, depth, shrink=0):
     if m < 1 or not 0 <= shrink <= depth:
         raise ValueError("at least one delete, and no more halvings than the tree has levels")
     upd = merkle_update_layout(2 * m, dim, depth, [2, 1] * m, 0, carried=True)
-    cells = 2 + (depth - 1 + shrink) * upd["node_cells"] if shrink else 0
-    lay = _ann_frame_layout(K, merkle_leaf_layout(K + 1), upd["total"] + cells)
+    cells = _shrink_cells(depth, shrink, upd["node_cells"])
+    lay = _ann_frame_layout(K, upd["total"] + cells)
     return dict(lay, update_layout=upd, shrink=lay["update"] + upd["total"], shrink_cells=cells, s=shrink)
 
 
@@ -1656,6 +1718,26 @@ def _delete_info(lay, m, upub, s0, top):
                 z0=lay["shrink"] + 1 if lay["s"] else None, old_root=upub[0], new_root=upub[-1])
 
 
+def _trace_delete_part(t, lay, m, depth, picked, end):
+    """blocks E' and S on a _CellTrace (lay: a layout with ann_delete_layout's update, update_layout, shrink and s): the update block over
+    [carried, delete] * m, its old root tied to `picked`, every carried cell tied to the old leaf of the update behind it; when the tree
+    halves, block S, which ends at cell `end`: S_0 = ctx.load_witness, the zero ladder with s folds from S_0 up, its top tied to the
+    update block's final root.  -> (the update block's public cells, s0, shrink_top, the new cluster root: S_0, or the final root when
+    nothing shrinks)"""
+    upub = _trace_update_block(t, lay["update_layout"], lay["update"])
+    t.copy_of[upub[0]] = picked                              # ctx.constrain_equal(picked, the update block's old root)
+    info = _delete_info(lay, m, upub, None, None)
+    for a, b in zip(info["carried"], info["moved_old"]):
+        t.copy_of[a] = b                                     # the move: what left the last slot is what arrived
+    if not lay["s"]:
+        return upub, None, None, upub[-1]
+    s0 = lay["shrink"]
+    top, at = _trace_ladder(t, s0 + 1, s0, depth, lay["s"], lay["update_layout"]["node_cells"])
+    assert at == end
+    t.copy_of[top] = upub[-1]                                # ctx.constrain_equal(S_s, the update block's final root)
+    return upub, s0, top, s0
+
+
 def trace_ann_delete(K, m, dim, depth, fetch_flags, fetch_values, shrink=0):
     """The closure of m deletes from one cluster of a committed index cell by cell (the ground truth of build_ann_delete): blocks A - D
     (_trace_ann_head), the update block over 2 m path updates (a carried leaf into slot_j, then the last slot emptied), the carried
@@ -1666,29 +1748,27 @@ def trace_ann_delete(K, m, dim, depth, fetch_flags, fetch_values, shrink=0):
     lay = ann_delete_layout(K, m, dim, depth, shrink)
     t = _CellTrace(lay["total"], fetch_flags, fetch_values)
     inds, picked, root_old = _trace_ann_head(t, lay)
-    upub = _trace_update_block(t, lay["update_layout"], lay["update"])
-    t.copy_of[upub[0]] = picked                              # ctx.constrain_equal(picked, the update block's old root)
-    s0, top = None, None
+    upub, s0, top, new_root = _trace_delete_part(t, lay, m, depth, picked, lay["new_roots"])
+    outs, root_new = _trace_ann_tail(t, lay, inds, new_root)
+    info = _frame_info(lay, inds, picked, root_old, root_new, outs=outs, **_delete_info(lay, m, upub, s0, top))
+    return t.finish(), ann_delete_instances(root_old, lay["c"], upub, root_new), info
+
+
+def _place_delete_part(B, lay, m, dim, depth, picked, end, fetch_flags, fetch_values):
+    """_trace_delete_part from unit blocks on builder `B`: the update block is place_merkle_update at its base with the carried kind,
+    block S's hashes are placed one after the other (_place_ladder).  -> as _trace_delete_part"""
+    upub = place_merkle_update(B, 2 * m, dim, depth, fetch_flags, fetch_values, lay["update"], [2, 1] * m, 0, carried=True)
+    B.tie(upub[0], picked)                                   # ctx.constrain_equal(picked, the update block's old root)
     info = _delete_info(lay, m, upub, None, None)
     for a, b in zip(info["carried"], info["moved_old"]):
-        t.copy_of[a] = b                                     # the move: what left the last slot is what arrived
-    new_root = upub[-1]
-    if shrink:
-        s0 = top = lay["shrink"]                             # S_0 = ctx.load_witness, Z_0 = ctx.load_constant(0)
-        at = t.put(s0 + 1, [("k", 0)], [0])
-        z = [s0 + 1]
-        for l in range(depth - 1):
-            z.append(t.node(at, z[l], z[l]))
-            at += lay["update_layout"]["node_cells"]
-        for i in range(shrink):
-            top = t.node(at, top, z[depth - shrink + i])
-            at += lay["update_layout"]["node_cells"]
-        assert at == lay["new_roots"]
-        t.copy_of[top] = upub[-1]                            # ctx.constrain_equal(S_s, the update block's final root)
-        new_root = s0
-    outs, root_new = _trace_ann_tail(t, lay, inds, new_root)
-    info = dict(_delete_info(lay, m, upub, s0, top), indicators=inds, picked=picked, outs=outs, index_root_old=root_old, index_root_new=root_new, layout=lay)
-    return t.finish(), ann_delete_instances(root_old, lay["c"], upub, root_new), info
+        B.tie(a, b)                                          # the move: what left the last slot is what arrived
+    if not lay["s"]:
+        return upub, None, None, upub[-1]
+    s0 = lay["shrink"]
+    top, at = _place_ladder(B, _perm_placer(B, fetch_flags, fetch_values), s0 + 1, s0, depth, lay["s"], lay["update_layout"]["node_cells"])
+    assert at == end
+    B.tie(top, upub[-1])                                     # ctx.constrain_equal(S_s, the update block's final root)
+    return upub, s0, top, s0
 
 
 def build_ann_delete(K, m, dim, depth, fetch_flags, fetch_values, builder=None, shrink=0):
@@ -1696,31 +1776,9 @@ def build_ann_delete(K, m, dim, depth, fetch_flags, fetch_values, builder=None, 
     the carried kind, block S's hashes are placed one after the other (`builder`: as build_kmeans).  -> as trace_ann_delete"""
     lay = ann_delete_layout(K, m, dim, depth, shrink)
     B, inds, picked, root_old = _build_ann_head(lay, fetch_flags, fetch_values, builder)
-    upub = place_merkle_update(B, 2 * m, dim, depth, fetch_flags, fetch_values, lay["update"], [2, 1] * m, 0, carried=True)
-    B.tie(upub[0], picked)                                   # ctx.constrain_equal(picked, the update block's old root)
-    info = _delete_info(lay, m, upub, None, None)
-    for a, b in zip(info["carried"], info["moved_old"]):
-        B.tie(a, b)                                          # the move: what left the last slot is what arrived
-    s0, top, new_root = None, None, upub[-1]
-    if shrink:
-        one = lambda x: np.asarray([x], dtype=np.int64)
-        perm = _perm_placer(B, fetch_flags, fetch_values)
-        s0 = lay["shrink"]
-        B.constant_cell(s0 + 1, 0)                           # Z_0 = ctx.load_constant(0)
-        z, top, at = [one(s0 + 1)], one(s0), s0 + 2
-        for l in range(depth - 1):
-            z.append(_node(perm, one(at), z[l], z[l]))
-            at += lay["update_layout"]["node_cells"]
-        for i in range(shrink):
-            top = _node(perm, one(at), top, z[depth - shrink + i])
-            at += lay["update_layout"]["node_cells"]
-        assert at == lay["new_roots"]
-        top = int(top[0])
-        B.tie(top, upub[-1])                                 # ctx.constrain_equal(S_s, the update block's final root)
-        new_root = s0
+    upub, s0, top, new_root = _place_delete_part(B, lay, m, dim, depth, picked, lay["new_roots"], fetch_flags, fetch_values)
     outs, root_new = _build_ann_tail(B, lay, inds, new_root, fetch_flags, fetch_values)
-    info = dict(_delete_info(lay, m, upub, s0, top), indicators=[int(i) for i in inds], picked=picked, outs=outs, index_root_old=root_old,
-                index_root_new=root_new, layout=lay)
+    info = _frame_info(lay, inds, picked, root_old, root_new, outs=outs, **_delete_info(lay, m, upub, s0, top))
     return B.finish(), ann_delete_instances(root_old, lay["c"], upub, root_new), info
 
 
@@ -1748,22 +1806,15 @@ def ann_move_layout(K, m, depth_a, shrink, depth_b, grow):
         raise ValueError("at least one move, and no more halvings than the tree has levels")
     upd_a = merkle_update_layout(2 * m, 1, depth_a, [2, 1] * m, 0, carried=True)
     upd_b = merkle_update_layout(m, 1, depth_b, [2] * m, grow, carried=True)
-    sp = merkle_leaf_layout(K + 1)
-    ind_cells, sel_cells = 8 + 12 * (K - 1), 1 + 3 * K
-    lay = dict(K=K, a=0, b=1, c=0, centroids_root=2, roots=3, n_in=K + 3, sponge=sp, update_layout=upd_a, update_b_layout=upd_b, s=shrink, g=grow)
-    lay["indicator"] = K + 3
-    lay["select"] = lay["indicator"] + ind_cells
-    lay["sponge_old"] = lay["select"] + sel_cells
-    lay["update"] = lay["sponge_old"] + sp["leaf_cells"]
+    cells = _shrink_cells(depth_a, shrink, upd_a["node_cells"])
+    ind_cells, sel_cells, f_cells = _frame_cells(K)
+    lay = _ann_frame_layout(K, upd_a["total"] + cells + f_cells + ind_cells + sel_cells + upd_b["total"], extra=1)
+    lay.update(K=K, a=0, b=1, update_layout=upd_a, update_b_layout=upd_b, s=shrink, g=grow, shrink_cells=cells)
     lay["shrink"] = lay["update"] + upd_a["total"]
-    lay["shrink_cells"] = 2 + (depth_a - 1 + shrink) * upd_a["node_cells"] if shrink else 0
-    lay["mid"] = lay["shrink"] + lay["shrink_cells"]
-    lay["indicator_b"] = lay["mid"] + 8 * K
+    lay["mid"] = lay["shrink"] + cells
+    lay["indicator_b"] = lay["mid"] + f_cells
     lay["select_b"] = lay["indicator_b"] + ind_cells
     lay["update_b"] = lay["select_b"] + sel_cells
-    lay["new_roots"] = lay["update_b"] + upd_b["total"]
-    lay["sponge_new"] = lay["new_roots"] + 8 * K
-    lay["total"] = lay["sponge_new"] + sp["leaf_cells"]
     return lay
 
 
@@ -1777,35 +1828,17 @@ def ann_move_instances(index_root_old, a, b, public_a, public_b, index_root_new)
     return out + [int(index_root_new)]
 
 
-def _move_info(lay, m, upa, upb):
-    """what both forms report about E', S and E_b: carried / moved_old (the delete's own move copy inside a), removed (the assigned
-    old-leaf cell of E''s update 2 j: the removed leaf), arrived (the carried-leaf cell of E_b's update j, tied to it), z0, and each
-    block's own roots"""
+def _move_info(lay, m, upa, upb, s0, top):
+    """what both forms report about E', S and E_b: _delete_info's keys of a's blocks, removed (the assigned old-leaf cell of E''s update
+    2 j: the removed leaf), arrived (the carried-leaf cell of E_b's update j, tied to it) and E_b's own roots"""
     u, base, ub, base_b = lay["update_layout"], lay["update"], lay["update_b_layout"], lay["update_b"]
-    return dict(carried=[base + u["block"][2 * j] for j in range(m)], moved_old=[base + u["old_leaf"] + 2 * j + 1 for j in range(m)],
-                removed=[base + u["old_leaf"] + 2 * j for j in range(m)], arrived=[base_b + ub["block"][j] for j in range(m)],
-                z0=lay["shrink"] + 1 if lay["s"] else None, old_root=upa[0], new_root=upa[-1], old_root_b=upb[0], new_root_b=upb[-1])
+    return dict(_delete_info(lay, m, upa, s0, top), removed=[base + u["old_leaf"] + 2 * j for j in range(m)],
+                arrived=[base_b + ub["block"][j] for j in range(m)], old_root_b=upb[0], new_root_b=upb[-1])
 
 
 def _indicator_b_lay(lay):
-    """the keys _trace_ann_head / _build_ann_head's indicator and select read, for blocks B_b and C_b"""
+    """the keys _trace_indicators / _build_indicators read, for blocks B_b and C_b"""
     return dict(lay, c=lay["b"], indicator=lay["indicator_b"], select=lay["select_b"])
-
-
-def _trace_indicators(t, lay, roots):
-    """idx_to_indicator(lay.c, K) as select_from_idx unrolls it and select_by_indicator(roots, indicators) on a _CellTrace
-    -> (inds, picked)"""
-    c = lay["c"]
-    inds = [t.is_zero(lay["indicator"], c)]
-    for j in range(1, len(roots)):
-        at = _indicator_at(lay, j)
-        t.put(at, [None, ("k", j), ("k", 1), ("c", c)], [1, 0, 0, 0])      # is_equal(c, Constant(j)) = sub [d, j, 1, c] + is_zero(d)
-        inds.append(t.is_zero(at + 4, at))
-    cells, gates = [("k", 0)], [1]
-    for j in range(len(roots)):
-        cells += [("c", roots[j]), ("c", inds[j]), None]
-        gates += [0, 0, j + 1 < len(roots)]
-    return inds, t.put(lay["select"], cells, gates) - 1
 
 
 def trace_ann_move(K, m, depth_a, shrink, depth_b, grow, fetch_flags, fetch_values):
@@ -1817,121 +1850,36 @@ def trace_ann_move(K, m, depth_a, shrink, depth_b, grow, fetch_flags, fetch_valu
     shrink_top, layout and _move_info's keys))"""
     lay = ann_move_layout(K, m, depth_a, shrink, depth_b, grow)
     t = _CellTrace(lay["total"], fetch_flags, fetch_values)
-    roots = [lay["roots"] + j for j in range(K)]
-    inds, picked = _trace_indicators(t, lay, roots)
-    root_old, at = t.leaf(lay["sponge_old"], lay["sponge"], None, [lay["centroids_root"]] + roots)
-    assert at == lay["update"]
-    upa = _trace_update_block(t, lay["update_layout"], lay["update"])
-    t.copy_of[upa[0]] = picked                               # ctx.constrain_equal(picked_a, E''s old root)
-    info = _move_info(lay, m, upa, [None, None])
-    for x, y in zip(info["carried"], info["moved_old"]):
-        t.copy_of[x] = y                                     # the delete's move: what left the last slot is what arrived in slot_j
-    s0, top, new_root = None, None, upa[-1]
-    if shrink:
-        s0 = top = lay["shrink"]                             # S_0 = ctx.load_witness, Z_0 = ctx.load_constant(0)
-        at = t.put(s0 + 1, [("k", 0)], [0])
-        z = [s0 + 1]
-        for l in range(depth_a - 1):
-            z.append(t.node(at, z[l], z[l]))
-            at += lay["update_layout"]["node_cells"]
-        for i in range(shrink):
-            top = t.node(at, top, z[depth_a - shrink + i])
-            at += lay["update_layout"]["node_cells"]
-        assert at == lay["mid"]
-        t.copy_of[top] = upa[-1]                             # ctx.constrain_equal(S_s, E''s final root)
-        new_root = s0
-    mids = [t.select(lay["mid"] + 8 * j, new_root, roots[j], inds[j]) for j in range(K)]
+    inds, picked, root_old = _trace_ann_head(t, lay)
+    upa, s0, top, new_root = _trace_delete_part(t, lay, m, depth_a, picked, lay["mid"])
+    mids = _trace_selects(t, lay["mid"], new_root, range(lay["roots"], lay["n_in"]), inds)
     inds_b, picked_b = _trace_indicators(t, _indicator_b_lay(lay), mids)
     upb = _trace_update_block(t, lay["update_b_layout"], lay["update_b"])
     t.copy_of[upb[0]] = picked_b                             # ctx.constrain_equal(picked_b, E_b's old root)
-    info = _move_info(lay, m, upa, upb)
+    info = _move_info(lay, m, upa, upb, s0, top)
     for x, y in zip(info["arrived"], info["removed"]):
         t.copy_of[x] = y                                     # THE MOVE: what arrived in b is what left a
-    outs = [t.select(lay["new_roots"] + 8 * j, upb[-1], mids[j], inds_b[j]) for j in range(K)]
-    root_new, at = t.leaf(lay["sponge_new"], lay["sponge"], None, [lay["centroids_root"]] + outs)
-    assert at == lay["total"]
-    info = dict(info, indicators=inds, indicators_b=inds_b, picked=picked, picked_b=picked_b, mids=mids, outs=outs, index_root_old=root_old,
-                index_root_new=root_new, s0=s0, shrink_top=top, layout=lay)
+    outs, root_new = _trace_ann_tail(t, lay, inds_b, upb[-1], mids)
+    info = _frame_info(lay, inds, picked, root_old, root_new, indicators_b=inds_b, picked_b=picked_b, mids=mids, outs=outs, **info)
     return t.finish(), ann_move_instances(root_old, lay["a"], lay["b"], upa, upb, root_new), info
-
-
-def _build_indicators(B, lay, roots):
-    """_trace_indicators from unit blocks on builder B (the blocks _build_ann_head places) -> (inds, picked)"""
-    K, c = len(roots), lay["c"]
-    s = Sym(0, 0)
-    iz = Block(s, [s.g_is_zero(ext(0))])
-    inds = [int(B.place(iz, [lay["indicator"]], [0], [[c]])[0, 0])]
-    if K > 1:
-        s = Sym(0, 0)
-        d = s.push(None, True)                               # is_equal(c, Constant(j)) = sub [d, j, 1, c] + is_zero(d)
-        s.push(None); s.push(C(1)); s.push(ext(0))
-        ie = Block(s, [s.g_is_zero(d)])
-        at = np.asarray([_indicator_at(lay, j) for j in range(1, K)], dtype=np.int64)
-        inds += [int(x) for x in B.place(ie, at, np.zeros(K - 1, dtype=np.int64), np.full((K - 1, 1), c, dtype=np.int64))[:, 0]]
-        for j in range(1, K):
-            B.constant_cell(int(at[j - 1]) + 1, j)
-    inds = np.asarray(inds, dtype=np.int64)
-    s = Sym(0, 0)
-    sb = Block(s, [s.g_select_by_indicator([ext(i) for i in range(K)], [ext(K + i) for i in range(K)])])
-    return inds, int(B.place(sb, [lay["select"]], [0], np.concatenate([np.asarray(roots, dtype=np.int64), inds])[None, :])[0, 0])
-
-
-def _build_selects(B, at, new_root, olds, inds):
-    """out_j = select(new_root, olds_j, inds_j) at at + 8 j, placed at once -> the out cells"""
-    K = len(inds)
-    s = Sym(0, 0)
-    sl = Block(s, [s.g_select(ext(0), ext(1), ext(2))])
-    return B.place(sl, at + 8 * np.arange(K, dtype=np.int64), np.zeros(K, dtype=np.int64),
-                   np.stack([np.full(K, new_root, dtype=np.int64), np.asarray(olds, dtype=np.int64), np.asarray(inds, dtype=np.int64)], axis=1))[:, 0]
 
 
 def build_ann_move(K, m, depth_a, shrink, depth_b, grow, fetch_flags, fetch_values, builder=None):
     """trace_ann_move's map assembled from unit blocks, as build_ann_delete: the two update blocks are place_merkle_update at their bases
     with the carried kind, block S's hashes are placed one after the other (`builder`: as build_kmeans).  -> as trace_ann_move"""
     lay = ann_move_layout(K, m, depth_a, shrink, depth_b, grow)
-    if np.asarray(fetch_flags(0, lay["n_in"])).any():
-        raise ValueError("the assigned header carries no gate or constant flag")
-    B = (builder or _Builder)(lay["total"], 0)
-    roots = lay["roots"] + np.arange(K, dtype=np.int64)
-    inds, picked = _build_indicators(B, lay, roots)
-    root_old, end = place_sponge(B, lay["sponge_old"], [lay["centroids_root"]] + [int(r) for r in roots], fetch_flags, fetch_values)
-    assert end == lay["update"]
-    upa = place_merkle_update(B, 2 * m, 1, depth_a, fetch_flags, fetch_values, lay["update"], [2, 1] * m, 0, carried=True)
-    B.tie(upa[0], picked)                                    # ctx.constrain_equal(picked_a, E''s old root)
-    info = _move_info(lay, m, upa, [None, None])
-    for x, y in zip(info["carried"], info["moved_old"]):
-        B.tie(x, y)                                          # the delete's move
-    s0, top, new_root = None, None, upa[-1]
-    if shrink:
-        one = lambda x: np.asarray([x], dtype=np.int64)
-        perm = _perm_placer(B, fetch_flags, fetch_values)
-        s0 = lay["shrink"]
-        B.constant_cell(s0 + 1, 0)                           # Z_0 = ctx.load_constant(0)
-        z, top, at = [one(s0 + 1)], one(s0), s0 + 2
-        for l in range(depth_a - 1):
-            z.append(_node(perm, one(at), z[l], z[l]))
-            at += lay["update_layout"]["node_cells"]
-        for i in range(shrink):
-            top = _node(perm, one(at), top, z[depth_a - shrink + i])
-            at += lay["update_layout"]["node_cells"]
-        assert at == lay["mid"]
-        top = int(top[0])
-        B.tie(top, upa[-1])                                  # ctx.constrain_equal(S_s, E''s final root)
-        new_root = s0
-    mids = _build_selects(B, lay["mid"], new_root, roots, inds)
+    B, inds, picked, root_old = _build_ann_head(lay, fetch_flags, fetch_values, builder)
+    upa, s0, top, new_root = _place_delete_part(B, lay, m, 1, depth_a, picked, lay["mid"], fetch_flags, fetch_values)
+    mids = _build_selects(B, lay["mid"], new_root, np.arange(lay["roots"], lay["n_in"]), inds)
     inds_b, picked_b = _build_indicators(B, _indicator_b_lay(lay), mids)
     upb = place_merkle_update(B, m, 1, depth_b, fetch_flags, fetch_values, lay["update_b"], [2] * m, grow, carried=True)
     B.tie(int(upb[0]), picked_b)                             # ctx.constrain_equal(picked_b, E_b's old root)
-    info = _move_info(lay, m, upa, upb)
+    info = _move_info(lay, m, upa, upb, s0, top)
     for x, y in zip(info["arrived"], info["removed"]):
         B.tie(x, y)                                          # THE MOVE: what arrived in b is what left a
-    outs = _build_selects(B, lay["new_roots"], upb[-1], mids, inds_b)
-    root_new, end = place_sponge(B, lay["sponge_new"], [lay["centroids_root"]] + [int(o) for o in outs], fetch_flags, fetch_values)
-    if end != lay["total"]:
-        raise ValueError("the trace does not end where the circuit does")
-    info = dict(info, indicators=[int(i) for i in inds], indicators_b=[int(i) for i in inds_b], picked=picked, picked_b=picked_b,
-                mids=[int(x) for x in mids], outs=[int(o) for o in outs], index_root_old=root_old, index_root_new=root_new, s0=s0, shrink_top=top,
-                layout=lay)
+    outs, root_new = _build_ann_tail(B, lay, inds_b, upb[-1], fetch_flags, fetch_values, mids)
+    info = _frame_info(lay, inds, picked, root_old, root_new, indicators_b=[int(i) for i in inds_b], picked_b=picked_b, mids=[int(x) for x in mids],
+                       outs=outs, **info)
     return B.finish(), ann_move_instances(root_old, lay["a"], lay["b"], upa, upb, root_new), info
 
 
@@ -1939,10 +1887,9 @@ def build_ann_move(K, m, depth_a, shrink, depth_b, grow, fetch_flags, fetch_valu
 # The cluster frame of the routing audit and the mean audit below, one circuit around a block of their own: A - D the frame's head, I
 # [centroids | members] assigned, the own block, MC and MM the two merkle_commitments; public [index_root | c]
 def _ann_cluster_layout(K, n_c, dim):
-    """the head's keys of _ann_frame_layout (c, centroids_root, roots, n_in, indicator, select, sponge_old, sponge; `update`: where the head
-    ends) and centroids, members: the assigned block I, the own block behind it; zero_c: the centroids' padding loads the zero cell"""
-    head = _ann_frame_layout(K, merkle_leaf_layout(K + 1), 0)
-    lay = {k: head[k] for k in ("c", "centroids_root", "roots", "n_in", "indicator", "sponge", "select", "sponge_old", "update")}
+    """_ann_head_layout's keys (c, centroids_root, roots, n_in, indicator, select, sponge_old, sponge; `update`: where the head ends) and
+    centroids, members: the assigned block I, the own block behind it; zero_c: the centroids' padding loads the zero cell"""
+    lay = _ann_head_layout(K)
     lay.update(zero_c=(1 << (K - 1).bit_length()) > K, centroids=lay["update"], members=lay["update"] + K * dim)
     return lay
 
@@ -2133,7 +2080,7 @@ def build_ann_mean(K, n_c, dim, P, L, fetch_flags, fetch_values, builder=None):
 # ---------------------------------------------------------------------------------------------------------------------------
 # The recentre of one cluster, old index root to new (include/vdb.h vdb_wit_ann_recentre; pipeline.AnnRecentreHotPath)
 def ann_recentre_layout(K, n_c, dim, P, L):
-    """where the blocks of the recentre circuit start: the head's keys of _ann_frame_layout (c, centroids_root, roots, n_in, indicator,
+    """where the blocks of the recentre circuit start: _ann_head_layout's keys (c, centroids_root, roots, n_in, indicator,
     select, sponge_old, sponge; `update`: where the head ends); members: the assigned block I; len, chain, div: block M as
     ann_mean_layout has it; merkle_m: MM; centroid_update: block U, update_layout: its merkle_update_layout (relative to it), depth;
     sponge_new: G; total, total_l; units: dict(add, qd)"""
@@ -2143,9 +2090,7 @@ def ann_recentre_layout(K, n_c, dim, P, L):
         raise ValueError("quantization(n_c) must stay below qdiv's divisor bound 2^(2P)")
     if K == 1:
         raise ValueError("a tree of one leaf has no path (depth 0)")
-    sp = merkle_leaf_layout(K + 1)
-    head = _ann_frame_layout(K, sp, 0)
-    lay = {k: head[k] for k in ("c", "centroids_root", "roots", "n_in", "indicator", "sponge", "select", "sponge_old", "update")}
+    lay = _ann_head_layout(K)
     mu = mean_units(1, P, L)
     u = lay["units"] = dict(add=mu["add"], qd=mu["qd"])
     depth = (K - 1).bit_length()
@@ -2157,7 +2102,7 @@ def ann_recentre_layout(K, n_c, dim, P, L):
     lay["merkle_m"] = lay["div"] + dim * u["qd"].n
     lay["centroid_update"] = lay["merkle_m"] + merkle_cells(n_c, dim)
     lay["sponge_new"] = lay["centroid_update"] + upd["total"]
-    lay["total"] = lay["sponge_new"] + sp["leaf_cells"]
+    lay["total"] = lay["sponge_new"] + lay["sponge"]["leaf_cells"]
     lay["total_l"] = dim * u["qd"].n_lk
     return lay
 
@@ -2194,8 +2139,7 @@ def build_ann_recentre(K, n_c, dim, P, L, fetch_flags, fetch_values, builder=Non
     root_new, end = place_sponge(B, lay["sponge_new"], [upub[-1]] + [lay["roots"] + j for j in range(K)], fetch_flags, fetch_values)
     if end != lay["total"]:
         raise ValueError("the trace does not end where the circuit does")
-    info = dict(indicators=[int(i) for i in inds], picked=picked, mean=mean, len=lay["len"], members_root=mroot, update_public=upub, new_vector=new_vector,
-                index_root_old=root_old, index_root_new=root_new, layout=lay)
+    info = _frame_info(lay, inds, picked, root_old, root_new, mean=mean, len=lay["len"], members_root=mroot, update_public=upub, new_vector=new_vector)
     return B.finish(), ann_recentre_instances(root_old, lay["c"], root_new), info
 
 
