@@ -30,12 +30,12 @@ MAGIC = 0x4C395042
 CHAIN = 64
 
 (MUL, MUL2, SQR, SHOUP, FROM_MONT, MONT_MUL, SPLIT, SPLIT32, PACK, RENORM, CARRY, ADD, SUB, NEG, CANON, IS_ZERO, CANON_WIDE, OFFSET,
- SHOUP_PAIR, MADD, MDBL, GATE, MADD_CHAIN) = range(23)
+ SHOUP_PAIR, MADD, MDBL, GATE, MADD_CHAIN, PERM_STEP, LOOKUP_STEP) = range(25)
 NAMES = ["mont_core29", "mont_core29_2", "mont_sqr_core29", "shoup_core29", "from_mont", "mont_mul", "l9_split", "l9_split32", "l9_pack",
          "l9_renorm", "l9_carry", "l9_add", "l9_sub", "l9_neg", "l9_canon", "l9_is_zero_mod", "l9_canon_wide", "l9_offset_limbs",
-         "shoup_pair29", "madd_l9", "mdbl_l9", "gate_step", "madd_l9_chain"]
-NIN = [18, 36, 9, 27, 8, 16, 8, 8, 9, 9, 9, 18, 27, 18, 9, 9, 9, 1, 8, 54, 18, 67, 37 + CHAIN * 17]
-NOUT = [9, 9, 9, 9, 8, 8, 9, 9, 8, 9, 9, 9, 9, 9, 8, 1, 8, 11, 18, 37, 37, 17, CHAIN * 37]
+         "shoup_pair29", "madd_l9", "mdbl_l9", "gate_step", "madd_l9_chain", "perm_step", "lookup_step"]
+NIN = [18, 36, 9, 27, 8, 16, 8, 8, 9, 9, 9, 18, 27, 18, 9, 9, 9, 1, 8, 54, 18, 67, 37 + CHAIN * 17, 173, 132]
+NOUT = [9, 9, 9, 9, 8, 8, 9, 9, 8, 9, 9, 9, 9, 9, 8, 1, 8, 11, 18, 37, 37, 17, CHAIN * 37, 17, 17]
 DEVICE_ONLY = {CANON_WIDE, MADD, MDBL, MADD_CHAIN}
 HOST_ONLY = {OFFSET, SHOUP_PAIR}
 OFFSETS_IN_USE = {0: (2, 9, 14, 34), 1: (2, 8)}
@@ -327,7 +327,134 @@ def expect(op, mod, tag, w):
             h = core_out(val(h) * y32 + val(g) * 32 * sel, p)
             assert val(h) < 2 * p     # the invariant l9_canon at the end of the kernel relies on
         return h + words8(val(h) % p)
+    if op == PERM_STEP:
+        return expect_perm_step(p, w)
+    if op == LOOKUP_STEP:
+        return expect_lookup_step(p, w)
     raise AssertionError(op)
+
+
+# ---- the loop bodies of k_perm_eval and k_lookup_eval (polyops.hip), primitive by primitive ------------------------------------------
+# A limb array V stands for the field element V / 2^261: a memory word (x 2^256, below p) enters as 32 times itself, a constant arrives
+# scaled (32 c 2^256 mod p), a product core divides by 2^261.  `Lazy` carries the limbs as 32-bit arithmetic gives them and, beside
+# them, the field element computed on integers mod p alone; every primitive asserts its operands' documented shape, that nothing
+# wrapped, that the value stays below the 70 p the kernels' comment states, and that the limbs still stand for the field element.
+VALUE_BOUND = 70
+
+
+class Lazy:
+    def __init__(self, p, limbs, fe):
+        self.p, self.l, self.fe = p, limbs, fe % p
+        v = val(limbs)
+        assert max(limbs) < U32 and v < VALUE_BOUND * p, v / p
+        assert v * pow(T261, -1, p) % p == self.fe
+
+    @staticmethod
+    def word(p, w):
+        """a memory word through l9_split32"""
+        assert w < p
+        return Lazy(p, norm(32 * w), w * pow(1 << 256, -1, p))
+
+    @staticmethod
+    def const(p, c):
+        """a scaled constant through l9_split"""
+        assert c < p
+        return Lazy(p, norm(c), c * pow(T261, -1, p))
+
+    def add(self, o):
+        return Lazy(self.p, [x + y for x, y in zip(self.l, o.l)], self.fe + o.fe)
+
+    def sub(self, t, c):
+        out, wrapped = sub_limbs(self.l, t.l, c)
+        assert not wrapped, "l9_sub wraps"
+        return Lazy(self.p, out, self.fe - t.fe)
+
+    def mul(self, o):
+        assert max(self.l) <= LIM61 and max(o.l) < B29, "operand shape of a product"
+        return Lazy(self.p, core_out(val(self.l) * val(o.l), self.p), self.fe * o.fe)
+
+    def mul2(self, b1, a2, b2):
+        assert all(x + y < 6 * B29 for x, y in zip(self.l, a2.l)) and max(b1.l) < B29 and max(b2.l) < B29, "operand shape of l9_mul2"
+        return Lazy(self.p, core_out(val(self.l) * val(b1.l) + val(a2.l) * val(b2.l), self.p), self.fe * b1.fe + a2.fe * b2.fe)
+
+
+def _finish(p, h):
+    """what the kernels store: l9_canon(l9_mul(h, l9_split(one))) — the memory word of h's field element"""
+    one = (1 << 256) % p
+    out = h.mul(Lazy(p, norm(one), one * pow(T261, -1, p)))
+    assert val(out.l) < 2 * p and is_norm(out.l)
+    word = val(out.l) % p
+    assert word == h.fe * (1 << 256) % p
+    return h.l + words8(word)
+
+
+def _step_head(p, w, c9_at, n_at):
+    h = w[0:9]
+    c9, c34, n = w[c9_at: c9_at + 9], w[c9_at + 9: c9_at + 18], w[n_at]
+    # the accumulator as l9_split32 of a stored word leaves it, or as a product left it
+    assert is_norm(h) and val(h) < 32 * p and c9 == offset_limbs(9, p) and c34 == offset_limbs(34, p) and 1 <= n <= 64
+    return Lazy(p, h, val(h) * pow(T261, -1, p)), c9, c34, n
+
+
+def expect_perm_step(p, w):
+    u = lambda at: from_words(w[at: at + 8])
+    h, c9, c34, n = _step_head(p, w, 154, 172)
+    Y, B, G, D, dstart = (Lazy.const(p, u(9 + 8 * i)) for i in range(5))
+    L0, LA, zc, zp, zl, zr, bx = (Lazy.word(p, u(49 + 8 * i)) for i in range(7))
+    adv, sig = [Lazy.word(p, u(105 + 8 * c)) for c in range(3)], [Lazy.word(p, u(129 + 8 * c)) for c in range(3)]
+    head = w[153]
+    assert head in (0, 2)
+    # the field value from the formula alone: l0 (z_i - z_{i-1}), l_active (z_i(wX) prod (a + beta sigma + gamma) - z_i prod (a + delta^c beta X + gamma))
+    left_f, right_f = zl.fe, zr.fe
+    for c in range(3):
+        left_f = left_f * (adv[c].fe + (sig[c].fe if head else B.fe * sig[c].fe) + G.fe) % p
+        right_f = right_f * (adv[c].fe + pow(D.fe, c, p) * dstart.fe * bx.fe + G.fe) % p
+    want = h.fe
+    for _ in range(n):
+        h = h.mul2(Y, zc.sub(zp, c34), L0)
+        cur = bx.mul(dstart)
+        left, right = zl, zr
+        for c in range(3):
+            v = adv[c].add(G)
+            left = v.add(sig[c] if head else sig[c].mul(B)).mul(left)
+            right = v.add(cur).mul(right)
+            cur = cur.mul(D)
+        h = h.mul2(Y, left.sub(right, c9), LA)
+        want = ((want * Y.fe + L0.fe * (zc.fe - zp.fe)) * Y.fe + LA.fe * (left_f - right_f)) % p
+        assert h.fe == want
+    return _finish(p, h)
+
+
+def expect_lookup_step(p, w):
+    u = lambda at: from_words(w[at: at + 8])
+    h, c9, c34, n = _step_head(p, w, 113, 131)
+    Y, B = Lazy.const(p, u(9)), Lazy.const(p, u(17))
+    gamma_m = u(25)
+    assert gamma_m < p
+    L0, LL, LA = (Lazy.word(p, u(33 + 8 * i)) for i in range(3))
+    tab_m, zc, zn, av, pav, ptv = u(57), *(Lazy.word(p, u(65 + 8 * i)) for i in range(5))
+    pav_m, ptv_m, prev_m = u(89), u(97), u(105)
+    assert max(tab_m, prev_m) < p
+    one = Lazy.word(p, (1 << 256) % p)
+    sg = Lazy.word(p, (tab_m + gamma_m) % p)            # sums that serve as a second factor are made in memory form
+    g_f, s_f, prev_f = (x * pow(1 << 256, -1, p) % p for x in (gamma_m, tab_m, prev_m))
+    terms = [L0.fe * (1 - zc.fe), LL.fe * (zc.fe * zc.fe - zc.fe),
+             LA.fe * (zn.fe * (pav.fe + B.fe) * (ptv.fe + g_f) - zc.fe * (av.fe + B.fe) * (s_f + g_f)),
+             L0.fe * (pav.fe - ptv.fe), LA.fe * (pav.fe - ptv.fe) * (pav.fe - prev_f)]
+    want = h.fe
+    for _ in range(n):
+        h = h.mul2(Y, one.sub(zc, c34), L0)
+        h = h.mul2(Y, zc.mul(zc).sub(zc, c34), LL)
+        left = pav.add(B).mul(Lazy.word(p, (ptv_m + gamma_m) % p)).mul(zn)
+        right = av.add(B).mul(sg).mul(zc)
+        h = h.mul2(Y, left.sub(right, c9), LA)
+        d = pav.sub(ptv, c34)
+        h = h.mul2(Y, d, L0)
+        h = h.mul2(Y, d.mul(Lazy.word(p, (pav_m - prev_m) % p)), LA)
+        for t in terms:
+            want = (want * Y.fe + t) % p
+        assert h.fe == want
+    return _finish(p, h)
 
 
 def expect_ec(op, tag, w):
@@ -562,6 +689,7 @@ SUB_SITES = [
     (1, 2, 11, 100, 300, "madd_l9 / mdbl_l9: a product (< 1.1 q) from a product"),
     (0, 34, 320, 100, 300, "polyops: 32 a for a canonical a (l9_split32) from a product or another such value"),
     (0, 9, 71, 100, 300, "polyops: a product of two loaded values (< 6.1 r + r) from another"),
+    (0, 9, 75, 100, 300, "k_perm_eval: `right` after one column ((a + gamma + cur) < 34.2 r times z < 32 r, / 2^261, + r) from `left`"),
     (0, 2, 10, 200, 410, "k_gate_eval: a canonical value from a + b c"),
     (0, 14, 130, None, 800, "k_ntt_pass: a value below 13 r from a minuend at the carry schedule's limit"),
     (0, 14, 30, None, 800, "k_ntt_pass: a Shoup product (< 3 r) from a minuend at the carry schedule's limit"),
@@ -640,6 +768,69 @@ def gen_gate(mod, rng):
     for _ in range(200):
         cs.append(("random", mk(rng.randrange(2 * p), *(rng.randrange(p) for _ in range(6)), rng.randint(1, 64))))
     return Block(GATE, mod, cs)
+
+
+def gen_perm_step(rng):
+    """k_perm_eval's loop body: words = h, y32 B G D dstart, l0 la zc zp zl zr bx, adv[3], sigma[3], head, c9, c34, n"""
+    p = R
+    one = (1 << 256) % p
+    c9, c34 = offset_limbs(9, p), offset_limbs(34, p)
+
+    def mk(h, consts, l, z, bx, adv, sig, head, n):
+        ws = []
+        for x in list(consts) + list(l) + list(z) + [bx] + list(adv) + list(sig):
+            ws += words8(x)
+        return norm(h) + ws + [head] + c9 + c34 + [n]
+    top, hmax = p - 1, 32 * (p - 1)
+    cs = []
+    for head in (0, 2):
+        for n in (1, 2, 64):
+            cs.append(("worst/all r-1", mk(hmax, [top] * 5, [top] * 2, [top] * 4, top, [top] * 3, [top] * 3, head, n)))
+            cs.append(("worst/all 0", mk(0, [0] * 5, [0] * 2, [0] * 4, 0, [0] * 3, [0] * 3, head, n)))
+            # `left` as large as it gets (z(wX), advice and sigma at r - 1) against a zero `right`, and the reverse
+            cs.append(("worst/left max right 0", mk(hmax, [top] * 5, [top] * 2, [top, 0, top, 0], 0, [top] * 3, [top] * 3, head, n)))
+            cs.append(("worst/left 0 right max", mk(hmax, [top] * 5, [top] * 2, [0, top, 0, top], top, [top] * 3, [0] * 3, head, n)))
+            cs.append(("worst/left 0 right max", mk(hmax, [top, 0, top, top, top], [top] * 2, [0, top, 0, top], top, [top] * 3, [top] * 3, head, n)))
+            # z = 1 everywhere: the satisfied case
+            cs.append(("worst/z one", mk(hmax, [top] * 5, [one] * 2, [one] * 4, top, [top] * 3, [top] * 3, head, n)))
+            cs.append(("worst/z one", mk(0, [rng.randrange(p) for _ in range(5)], [one, one], [one] * 4, rng.randrange(p), [0] * 3, [0] * 3, head, n)))
+            # the chaining term's subtrahend at 32 (r - 1) under a zero minuend
+            cs.append(("worst/subtrahend 32(r-1)", mk(hmax, [top] * 5, [top] * 2, [0, top, 0, top], 0, [0] * 3, [0] * 3, head, n)))
+        for _ in range(150):
+            r8 = lambda m: [rng.choice((0, 1, top, one, rng.randrange(p), rng.randrange(p))) for _ in range(m)]
+            cs.append(("random", mk(rng.randrange(32 * p), r8(5), r8(2), r8(4), r8(1)[0], r8(3), r8(3), head, rng.randint(1, 64))))
+    return Block(PERM_STEP, 0, cs)
+
+
+def gen_lookup_step(rng):
+    """k_lookup_eval's loop body: words = h, y32 B gamma, l0 ll la, tab zc zn a pa pt pa_prev, c9, c34, n"""
+    p = R
+    one = (1 << 256) % p
+    c9, c34 = offset_limbs(9, p), offset_limbs(34, p)
+
+    def mk(h, consts, l, cells, n):
+        ws = []
+        for x in list(consts) + list(l) + list(cells):
+            ws += words8(x)
+        return norm(h) + ws + c9 + c34 + [n]
+    top, hmax = p - 1, 32 * (p - 1)
+    cs = []
+    for n in (1, 2, 64):
+        cs.append(("worst/all r-1", mk(hmax, [top] * 3, [top] * 3, [top] * 7, n)))
+        cs.append(("worst/all 0", mk(0, [0] * 3, [0] * 3, [0] * 7, n)))
+        #                                                   tab  zc   zn   a    pa   pt  pa_prev
+        cs.append(("worst/left max right 0", mk(hmax, [top, top, 0], [top] * 3, [0, 0, top, 0, top, top, 0], n)))
+        cs.append(("worst/left max right 0", mk(hmax, [top, 0, top - 1], [top] * 3, [0, 0, top, 0, top, top, 0], n)))
+        cs.append(("worst/left 0 right max", mk(hmax, [top, top, 0], [top] * 3, [top, top, 0, top, 0, 0, top], n)))
+        cs.append(("worst/left 0 right max", mk(hmax, [top, 0, top - 1], [top] * 3, [top, top, 0, top - 1, 0, 0, top], n)))
+        cs.append(("worst/z one", mk(hmax, [top] * 3, [one] * 3, [top, one, one, top, top, top, top], n)))
+        cs.append(("worst/z one", mk(0, [rng.randrange(p) for _ in range(3)], [one] * 3, [5, one, one, 5, 5, 5, 5], n)))
+        # subtrahends at 32 (r - 1) under the smallest minuends: 1 - z, z^2 - z, a' - s' with a' = 0
+        cs.append(("worst/subtrahend 32(r-1)", mk(hmax, [top] * 3, [top] * 3, [0, top, 0, 0, 0, top, top], n)))
+    for _ in range(300):
+        r8 = lambda m: [rng.choice((0, 1, top, one, rng.randrange(p), rng.randrange(p))) for _ in range(m)]
+        cs.append(("random", mk(rng.randrange(32 * p), r8(3), r8(3), r8(7), rng.randint(1, 64))))
+    return Block(LOOKUP_STEP, 0, cs)
 
 
 def gen_host_only(mod, rng):
@@ -744,6 +935,9 @@ def build_blocks(host, seed=20261016):
         rng = random.Random(seed + mod)
         blocks += [gen_mul(mod, rng), gen_mul2(mod, rng), gen_sqr(mod, rng), gen_shoup(mod, rng)]
         blocks += gen_u256_ops(mod, rng) + gen_limb_ops(mod, rng) + gen_sub(mod, rng, host) + [gen_gate(mod, rng)]
+        if mod == 0:
+            rng_q = random.Random(seed + 3)     # (a stream of their own: the cases of the older blocks stay what they were)
+            blocks += [gen_perm_step(rng_q), gen_lookup_step(rng_q)]
         if host:
             blocks += gen_host_only(mod, rng)
     if not host:

@@ -52,11 +52,16 @@ def test_product_cores_device_host_model(probe, device_blocks, tmp_path):
 
 
 def test_limb_ops_device_host_model(probe, device_blocks, tmp_path):
-    """split / pack / renorm / carry / add / sub / neg / canon / is_zero_mod, one k_gate_eval step fed back up to 64 times, and
-    l9_canon_wide (Fr, device only)"""
+    """split / pack / renorm / carry / add / sub / neg / canon / is_zero_mod, one k_gate_eval step fed back up to 64 times, the loop
+    bodies of k_perm_eval and k_lookup_eval (Fr) the same way, and l9_canon_wide (Fr, device only)"""
     ops = (L.SPLIT, L.SPLIT32, L.PACK, L.RENORM, L.CARRY, L.ADD, L.SUB, L.NEG, L.CANON, L.IS_ZERO, L.GATE)
-    blocks = [b for b in device_blocks if b.op in ops or b.op == L.CANON_WIDE]
-    assert sorted((b.op, b.mod) for b in blocks) == sorted([(op, m) for op in ops for m in (0, 1)] + [(L.CANON_WIDE, 0)])
+    fr_only = (L.CANON_WIDE, L.PERM_STEP, L.LOOKUP_STEP)
+    blocks = [b for b in device_blocks if b.op in ops or b.op in fr_only]
+    assert sorted((b.op, b.mod) for b in blocks) == sorted([(op, m) for op in ops for m in (0, 1)] + [(op, 0) for op in fr_only])
+    for b in blocks:
+        if b.op in (L.PERM_STEP, L.LOOKUP_STEP):
+            have = b.classes()
+            assert have.get("worst", 0) > 0 and have.get("random", 0) > 0, have
     for b in blocks:
         if b.op in (L.SUB, L.NEG):
             have = b.classes()

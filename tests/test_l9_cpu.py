@@ -143,6 +143,32 @@ def test_gate_step_invariant(host_run, mod):
     assert max(w[66] for t, w in b.cases if t == "worst") == 64
 
 
+STEP_WORST = ["all r-1", "all 0", "left max right 0", "left 0 right max", "z one", "subtrahend 32(r-1)"]
+
+
+def check_step(run, op):
+    b, _ = run[(op, 0)]
+    worst = {t.split("/", 1)[1] for t, _ in b.cases if t.startswith("worst/")}
+    assert worst == set(STEP_WORST), worst
+    n_at = L.NIN[op] - 1
+    assert max(w[n_at] for t, w in b.cases if t.startswith("worst/")) == 64
+    check(run, op, 0, ["worst", "random"])
+
+
+def test_perm_step_bounds(host_run):
+    """one chaining term and one product term (three columns, with and without pre-scaled sigma) of k_perm_eval, fed back up to 64 times:
+    after every primitive the model asserts that no l9_sub wraps, every product's operands have their documented shape, every value
+    stays below 70 r, and the stored word is the field value of the formula"""
+    check_step(host_run, L.PERM_STEP)
+    b, _ = host_run[(L.PERM_STEP, 0)]
+    assert {w[153] for _, w in b.cases} == {0, 2}
+
+
+def test_lookup_step_bounds(host_run):
+    """the five terms of one column of k_lookup_eval, the same way"""
+    check_step(host_run, L.LOOKUP_STEP)
+
+
 def test_device_only_models_stand():
     """l9_canon_wide, madd_l9 and mdbl_l9 are device functions: their cases are generated and the model's own preconditions and
     contracts are asserted here, the comparison happens in tests/test_gpu_l9.py"""

@@ -29,6 +29,11 @@
 //   20  mdbl_l9           x y                   (Fq, device only)       x y zz zzz ident
 //   21  gate step x n     h, y32 a b c d sel (u256), C2, n              h after n steps of k_gate_eval's loop body (polyops.hip), l9_canon of it
 //   22  madd_l9 chain     x y zz zzz ident, 64 x (px py neg)   (Fq, device only)   64 x (x y zz zzz ident): the accumulator after every step
+//   23  perm step x n     h, y32 B G D dstart (scaled constants, u256), l0 la zc zp zl zr bx adv[3] sigma[3] (memory words), head, C9, C34, n   (Fr)
+//                         h after n times one chaining term and one product term of three columns of k_perm_eval (polyops.hip); head & 2: the
+//                         sigma words are those of beta sigma; then l9_canon of h times one, as the kernel stores it
+//   24  lookup step x n   h, y32 B (scaled), gamma (memory form), l0 ll la tab zc zn a pa pt pa_prev (memory words), C9, C34, n        (Fr)
+//                         h after n times the five terms of one column of k_lookup_eval, and l9_canon of h times one
 // l9_canon_wide, madd_l9 and mdbl_l9 are device functions (they are the kernels' own text), so only --device reaches them.
 #include <cstdint>
 #include <cstdio>
@@ -40,12 +45,12 @@
 using namespace vdb;
 
 #define L9P_MAGIC 0x4c395042u
-#define L9P_NOPS 23
+#define L9P_NOPS 25
 #define L9P_CHAIN 64
-static constexpr uint32_t NIN[L9P_NOPS] = {18, 36, 9, 27, 8, 16, 8, 8, 9, 9, 9, 18, 27, 18, 9, 9, 9, 1, 8, 54, 18, 67, 37 + L9P_CHAIN * 17};
-static constexpr uint32_t NOUT[L9P_NOPS] = {9, 9, 9, 9, 8, 8, 9, 9, 8, 9, 9, 9, 9, 9, 8, 1, 8, 11, 18, 37, 37, 17, L9P_CHAIN * 37};
+static constexpr uint32_t NIN[L9P_NOPS] = {18, 36, 9, 27, 8, 16, 8, 8, 9, 9, 9, 18, 27, 18, 9, 9, 9, 1, 8, 54, 18, 67, 37 + L9P_CHAIN * 17, 173, 132};
+static constexpr uint32_t NOUT[L9P_NOPS] = {9, 9, 9, 9, 8, 8, 9, 9, 8, 9, 9, 9, 9, 9, 8, 1, 8, 11, 18, 37, 37, 17, L9P_CHAIN * 37, 17, 17};
 // 0: host and device; 1: device only; 2: host only
-static constexpr int WHERE[L9P_NOPS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 2, 2, 1, 1, 0, 1};
+static constexpr int WHERE[L9P_NOPS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 2, 2, 1, 1, 0, 1, 0, 0};
 
 HD L9 get9(const uint32_t* p) {
   L9 r;
@@ -162,6 +167,67 @@ HD void eval_hd(const uint32_t* in, uint32_t* out) {
     }
     put9(out, h);
     put8(out + 9, l9_canon<M>(h));
+  } else if constexpr (OP == 23) {
+    // one chaining term and one product term (three columns) of k_perm_eval, from the same primitives in the same order
+    L9 h = get9(in);
+    const L9 Y = l9_split(get8(in + 9)), B = l9_split(get8(in + 17)), G = l9_split(get8(in + 25)), D = l9_split(get8(in + 33));
+    const u256 dstart = get8(in + 41);
+    const L9 L0 = l9_split32(get8(in + 49)), LA = l9_split32(get8(in + 57));
+    const u256 zc = get8(in + 65), zp = get8(in + 73), zl = get8(in + 81), zr = get8(in + 89), bx = get8(in + 97);
+    const uint32_t head = in[153];
+    uint32_t c9[9], c34[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+      c9[k] = in[154 + k];
+      c34[k] = in[163 + k];
+    }
+    const uint32_t n = in[172];
+    for (uint32_t it = 0; it < n; it++) {
+      h = l9_mul2<M>(h, Y, l9_sub(l9_split32(zc), l9_split32(zp), c34), L0);
+      L9 cur = l9_mul<M>(l9_split32(bx), l9_split(dstart));
+      L9 left = l9_split32(zl), right = l9_split32(zr);
+      for (int c = 0; c < 3; c++) {
+        const L9 v = l9_add(l9_split32(get8(in + 105 + 8 * c)), G);
+        const L9 sg = l9_split32(get8(in + 129 + 8 * c));
+        left = l9_mul<M>(l9_add(v, (head & 2) ? sg : l9_mul<M>(sg, B)), left);
+        right = l9_mul<M>(l9_add(v, cur), right);
+        cur = l9_mul<M>(cur, D);
+      }
+      h = l9_mul2<M>(h, Y, l9_sub(left, right, c9), LA);
+    }
+    put9(out, h);
+    put8(out + 9, l9_canon<M>(l9_mul<M>(h, l9_split(mont_one<M>()))));
+  } else if constexpr (OP == 24) {
+    // the five terms of one column of k_lookup_eval
+    L9 h = get9(in);
+    const L9 Y = l9_split(get8(in + 9)), B = l9_split(get8(in + 17));
+    const u256 gamma_m = get8(in + 25);
+    const L9 L0 = l9_split32(get8(in + 33)), LL = l9_split32(get8(in + 41)), LA = l9_split32(get8(in + 49));
+    const L9 ONE = l9_split32(mont_one<M>());
+    const L9 sg = l9_split32(mod_add<M>(get8(in + 57), gamma_m));
+    const u256 pav_m = get8(in + 89), ptv_m = get8(in + 97), prev_m = get8(in + 105);
+    uint32_t c9[9], c34[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+      c9[k] = in[113 + k];
+      c34[k] = in[122 + k];
+    }
+    const uint32_t n = in[131];
+    for (uint32_t it = 0; it < n; it++) {
+      const L9 zc = l9_split32(get8(in + 65)), zn = l9_split32(get8(in + 73));
+      const L9 av = l9_split32(get8(in + 81)), pav = l9_split32(pav_m), ptv = l9_split32(ptv_m);
+      h = l9_mul2<M>(h, Y, l9_sub(ONE, zc, c34), L0);
+      h = l9_mul2<M>(h, Y, l9_sub(l9_mul<M>(zc, zc), zc, c34), LL);
+      const L9 left = l9_mul<M>(l9_mul<M>(l9_add(pav, B), l9_split32(mod_add<M>(ptv_m, gamma_m))), zn);
+      const L9 right = l9_mul<M>(l9_mul<M>(l9_add(av, B), sg), zc);
+      h = l9_mul2<M>(h, Y, l9_sub(left, right, c9), LA);
+      const L9 d = l9_sub(pav, ptv, c34);
+      h = l9_mul2<M>(h, Y, d, L0);
+      const L9 e = l9_split32(mod_sub<M>(pav_m, prev_m));
+      h = l9_mul2<M>(h, Y, l9_mul<M>(d, e), LA);
+    }
+    put9(out, h);
+    put8(out + 9, l9_canon<M>(l9_mul<M>(h, l9_split(mont_one<M>()))));
   }
 }
 
@@ -267,7 +333,7 @@ static int run_op(int op, bool device, uint32_t mod, const uint32_t* in, uint32_
       fprintf(stderr, "l9_probe: op %d does not exist in this mode\n", op);
       return 1;
     }
-    if ((OP == 16 || OP == 18) && mod != 0) {
+    if ((OP == 16 || OP == 18 || OP == 23 || OP == 24) && mod != 0) {
       fprintf(stderr, "l9_probe: op %d is over Fr\n", op);
       return 1;
     }
