@@ -682,6 +682,62 @@ def ann_cluster_means(grouped, offsets, P=48, L=13):
     return means
 
 
+def ann_assign_plan(metric, n, K, dim):
+    """the tile plan of the fused assign for a call of this shape (vdb_ann_assign_plan; needs no device): dict of R, C, DC, chunks, dchunks,
+    grid, lds_bytes, work_bytes; VdbError -3 for a shape the call refuses"""
+    out = np.zeros(8, dtype=np.uint64)
+    check(_lib.load().vdb_ann_assign_plan(METRICS[metric], _sz(n), _sz(K), _sz(dim), _p(out)))
+    return dict(zip(("R", "C", "DC", "chunks", "dchunks", "grid", "lds_bytes", "work_bytes"), (int(v) for v in out)))
+
+
+def ann_assign(metric, rows, centroids, P=48, L=13):
+    """the nearest centroid of every row of `rows` (n, dim, 4) among `centroids` (K, dim, 4) by the fused kernel (vdb_ann_assign_dev):
+    nearest_values(metric, rows, centroids)'s (idx (n,) uint32, dist (n, 4)) bit for bit, with no limit on n * K"""
+    lib = _lib.init()
+    rows, centroids = _fr(rows), _fr(centroids)
+    n, K, dim = rows.shape[0], centroids.shape[0], centroids.shape[1]
+    assert rows.ndim == 3 and centroids.ndim == 3 and rows.shape[1] == dim
+    bufs = [DeviceBuffer(max(b, 32)) for b in (rows.nbytes, centroids.nbytes, n * 4, n * 32)]
+    try:
+        bufs[0].upload(rows)
+        bufs[1].upload(centroids)
+        check(lib.vdb_ann_assign_dev(ctypes.c_uint32(P), ctypes.c_uint32(L), METRICS[metric], bufs[0].ptr, bufs[1].ptr, _sz(n), _sz(K), _sz(dim),
+                                     bufs[2].ptr, bufs[3].ptr))
+        return bufs[2].download((n,), dtype=np.uint32), bufs[3].download((n, 4))
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def ann_train_dev(metric, d_rows, n, K, dim, d_centroids, d_ids, iterations, P=48, L=13):
+    """vdb_ann_train_dev over device buffers: the rows stay where they are, `d_centroids` (in: initial, out: final) and `d_ids` are
+    written -> (sizes (K,) int64, iterations_run)"""
+    lib = _lib.init()
+    sizes, it = np.zeros(K, dtype=np.uint64), ctypes.c_size_t()
+    check(lib.vdb_ann_train_dev(ctypes.c_uint32(P), ctypes.c_uint32(L), METRICS[metric], d_rows.ptr, _sz(n), _sz(K), _sz(dim), _sz(iterations),
+                                d_centroids.ptr, d_ids.ptr, _p(sizes), ctypes.byref(it)))
+    return sizes.astype(np.int64), int(it.value)
+
+
+def ann_train(metric, rows, centroids, iterations, P=48, L=13):
+    """at most `iterations` Lloyd iterations over `rows` (n, dim, 4) from `centroids` (K, dim, 4), all on the device in the circuit's
+    fixed-point arithmetic (vdb_ann_train_dev) -> (ids (n,) uint32, centroids (K, dim, 4), sizes (K,) int64, iterations_run).  The
+    centroids are the means of the ids; iterations_run < iterations: converged, the ids are every row's nearest centroid too."""
+    rows, centroids = _fr(rows), _fr(centroids)
+    n, K, dim = rows.shape[0], centroids.shape[0], centroids.shape[1]
+    assert rows.ndim == 3 and centroids.ndim == 3 and rows.shape[1] == dim
+    _lib.init()
+    bufs = [DeviceBuffer(max(b, 32)) for b in (rows.nbytes, centroids.nbytes, n * 4)]
+    try:
+        bufs[0].upload(rows)
+        bufs[1].upload(centroids)
+        sizes, it = ann_train_dev(metric, bufs[0], n, K, dim, bufs[1], bufs[2], iterations, P, L)
+        return bufs[2].download((n,), dtype=np.uint32), bufs[1].download((K, dim, 4)), sizes, it
+    finally:
+        for b in bufs:
+            b.free()
+
+
 def _wit_ann_batch(trees, cells, n_pub, selectors, call, **sizes):
     """the buffers of a host-array call against the index root and its dict: `trees` the trees the call edits in place, by their key in
     the dict (copied first); call(*trees, stream, selectors or None, public) -> its code"""

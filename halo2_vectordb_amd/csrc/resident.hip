@@ -771,6 +771,75 @@ int ann_index_write_dev(const u256* grouped, const uint32_t* slots, const u256* 
                        forest_out, roots_out);
 }
 
+// ------------------------------------------------------------------ the Lloyd step's grouping (vdb_ann_train_dev): ids that never
+// leave the device.  k_ann_group above is one wavefront over host-checked ids of an index of at most VDB_ANN_MAX_CLUSTERS; these are
+// a counting sort over any n < 2^32 and K <= 2^24: a histogram by atomics, a scan by one workgroup, a scatter through per-cluster
+// cursors.  The scatter is not stable — the order inside a cluster is whatever the atomics gave — and nothing needs it to be: the one
+// reader, k_ann_means_gather, adds the members up exactly.
+constexpr uint32_t ANN_SORT_THREADS = 256, ANN_SCAN_THREADS = 1024;
+static unsigned ann_sort_grid(size_t n) {
+  const size_t want = (n + ANN_SORT_THREADS - 1) / ANN_SORT_THREADS, cap = (size_t)ctx().cu_count * 16;
+  return (unsigned)(want < cap ? want : cap);
+}
+__global__ __launch_bounds__(ANN_SORT_THREADS) void k_ann_count_changes(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint64_t n,
+                                                                        uint32_t* __restrict__ count) {
+  uint32_t mine = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * ANN_SORT_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * ANN_SORT_THREADS) mine += a[i] != b[i];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off, 64);
+  if ((threadIdx.x & 63u) == 0 && mine) atomicAdd(count, mine);
+}
+__global__ __launch_bounds__(ANN_SORT_THREADS) void k_ann_id_hist(const uint32_t* __restrict__ ids, uint64_t n, uint32_t K, uint32_t* __restrict__ cursor) {
+  for (uint64_t i = (uint64_t)blockIdx.x * ANN_SORT_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * ANN_SORT_THREADS)
+    if (ids[i] < K) atomicAdd(&cursor[ids[i]], 1u);
+}
+// cursor[k] = offsets[k] = the counts before k, offsets[K] = their total: thread t owns the clusters [t per, (t + 1) per)
+__global__ __launch_bounds__(ANN_SCAN_THREADS) void k_ann_id_scan(uint32_t* __restrict__ cursor, uint32_t K, uint64_t* __restrict__ offsets) {
+  __shared__ uint64_t part[ANN_SCAN_THREADS];
+  const uint32_t t = threadIdx.x, per = (K + ANN_SCAN_THREADS - 1) / ANN_SCAN_THREADS;
+  const uint64_t lo = (uint64_t)t * per < K ? (uint64_t)t * per : K, hi = lo + per < K ? lo + per : K;
+  uint64_t s = 0;
+  for (uint64_t k = lo; k < hi; k++) s += cursor[k];
+  part[t] = s;
+  __syncthreads();
+  if (t == 0) {
+    uint64_t acc = 0;
+    for (uint32_t i = 0; i < ANN_SCAN_THREADS; i++) {
+      const uint64_t m = part[i];
+      part[i] = acc;
+      acc += m;
+    }
+    offsets[K] = acc;
+  }
+  __syncthreads();
+  uint64_t acc = part[t];
+  for (uint64_t k = lo; k < hi; k++) {
+    const uint32_t m = cursor[k];
+    offsets[k] = acc;
+    cursor[k] = (uint32_t)acc;   // n < 2^32
+    acc += m;
+  }
+}
+__global__ __launch_bounds__(ANN_SORT_THREADS) void k_ann_id_scatter(const uint32_t* __restrict__ ids, uint64_t n, uint32_t K, uint32_t* __restrict__ cursor,
+                                                                     uint32_t* __restrict__ order) {
+  for (uint64_t i = (uint64_t)blockIdx.x * ANN_SORT_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * ANN_SORT_THREADS)
+    if (ids[i] < K) order[atomicAdd(&cursor[ids[i]], 1u)] = (uint32_t)i;
+}
+int ann_count_changes_dev(const uint32_t* ids_new, const uint32_t* ids_old, size_t n, uint32_t* count_dev, uint32_t* count) {
+  VDB_HIP(hipMemsetAsync(count_dev, 0, sizeof(uint32_t), ctx().stream));
+  VDB_LAUNCH(k_ann_count_changes, dim3(ann_sort_grid(n)), dim3(ANN_SORT_THREADS), ids_new, ids_old, (uint64_t)n, count_dev);
+  VDB_HIP(hipMemcpyAsync(count, count_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx().stream));
+  VDB_HIP(hipStreamSynchronize(ctx().stream));
+  return VDB_OK;
+}
+int ann_group_ids_dev(const uint32_t* ids, size_t n, size_t K, uint32_t* cursor, uint64_t* offsets, uint32_t* order) {
+  VDB_HIP(hipMemsetAsync(cursor, 0, K * sizeof(uint32_t), ctx().stream));
+  VDB_LAUNCH(k_ann_id_hist, dim3(ann_sort_grid(n)), dim3(ANN_SORT_THREADS), ids, (uint64_t)n, (uint32_t)K, cursor);
+  VDB_LAUNCH(k_ann_id_scan, dim3(1), dim3(ANN_SCAN_THREADS), cursor, (uint32_t)K, offsets);
+  VDB_LAUNCH(k_ann_id_scatter, dim3(ann_sort_grid(n)), dim3(ANN_SORT_THREADS), ids, (uint64_t)n, (uint32_t)K, cursor, order);
+  return VDB_OK;
+}
+
 }  // namespace vdb
 
 using namespace vdb;

@@ -51,5 +51,11 @@ int ann_index_write_dev(const u256* grouped, const uint32_t* slots, const u256* 
                         const uint64_t* indices, size_t m, u256* grouped_out, uint32_t* slots_out, uint64_t* offsets_out, u256* forest_out, u256* roots_out,
                         u256* db_tree_out);
 int ann_index_db_tree_dev(const u256* forest, const uint64_t* sizes, const uint32_t* slots, size_t K, size_t n, u256* levels_out);
+// The steps of a Lloyd iteration that need no gadget (vdb_ann_train_dev, witness.hip), on device-resident ids.
+// how many i have ids_new[i] != ids_old[i]: counted into `count_dev`, read back (the iteration's one read-back)
+int ann_count_changes_dev(const uint32_t* ids_new, const uint32_t* ids_old, size_t n, uint32_t* count_dev, uint32_t* count);
+// counting sort of ids < K: order[offsets[k] .. offsets[k + 1]) = the rows of cluster k (in no particular order), offsets[K] = n;
+// `cursor`: K words of work space
+int ann_group_ids_dev(const uint32_t* ids, size_t n, size_t K, uint32_t* cursor, uint64_t* offsets, uint32_t* order);
 
 }  // namespace vdb

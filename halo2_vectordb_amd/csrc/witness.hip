@@ -18,6 +18,7 @@
 #include <cstring>
 #include <vector>
 
+#include "ann_assign_plan.hpp"
 #include "ann_update_host.hpp"
 #include "common.hpp"
 #include "gadgets.hpp"
@@ -1027,16 +1028,13 @@ __global__ __launch_bounds__(64) void k_annr_div(Streams st, const FpTables* __r
 // the serial walk gives the bits of the circuit's qadd chain; the quotient is the value form fp_qdiv takes under an empty window.  Grid
 // (ceil(dim / 64), K), one wavefront per block: lane l owns word 64 blockIdx.x + l, a member row is read as one contiguous run, KM_PF
 // loads are issued ahead of their adds as in chain_fold_wave.  The host has checked the offsets (rising, the last one the row count).
-__global__ __launch_bounds__(64) void k_ann_means(const u256* __restrict__ grouped, const uint64_t* __restrict__ offsets, uint32_t dim, int* __restrict__ err,
-                                                  u256* __restrict__ means) {
-  const uint32_t k = blockIdx.y, j = blockIdx.x * 64 + threadIdx.x;
-  if (j >= dim) return;
-  const uint64_t lo = offsets[k], hi = offsets[k + 1];
+template <class RowOf>
+__device__ __forceinline__ void ann_mean_word(RowOf row_of, uint64_t lo, uint64_t hi, uint32_t dim, uint32_t j, int* __restrict__ err, u256* __restrict__ out) {
   u256 tot = u256_zero();
   for (uint64_t v0 = lo; v0 < hi; v0 += KM_PF) {
     u256 xv[KM_PF];
 #pragma unroll
-    for (uint32_t q = 0; q < KM_PF; q++) xv[q] = grouped[(size_t)(v0 + q < hi ? v0 + q : hi - 1) * dim + j];
+    for (uint32_t q = 0; q < KM_PF; q++) xv[q] = row_of(v0 + q < hi ? v0 + q : hi - 1)[j];
 #pragma unroll
     for (uint32_t q = 0; q < KM_PF; q++)
       if (v0 + q < hi) tot = fr_add(tot, xv[q]);
@@ -1045,7 +1043,190 @@ __global__ __launch_bounds__(64) void k_ann_means(const u256* __restrict__ group
   Gadgets g(c);
   const u256 len = fr_mul(to_mont<Fr>(u256_from_u64(hi - lo)), g.T.scale);   // quantization(n_k) = n_k 2^P
   int e = 0;
-  means[(size_t)k * dim + j] = g.v_qdiv(tot, len, e);
+  *out = g.v_qdiv(tot, len, e);
+  if (e) atomicOr(err, e);
+}
+__global__ __launch_bounds__(64) void k_ann_means(const u256* __restrict__ grouped, const uint64_t* __restrict__ offsets, uint32_t dim, int* __restrict__ err,
+                                                  u256* __restrict__ means) {
+  const uint32_t k = blockIdx.y, j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= dim) return;
+  ann_mean_word([&](uint64_t v) { return grouped + (size_t)v * dim; }, offsets[k], offsets[k + 1], dim, j, err, &means[(size_t)k * dim + j]);
+}
+// The gather form (vdb_ann_train_dev): the same word of the same mean with member v of cluster k read in place, row order[v] of the
+// database, so that a Lloyd step moves no row; the order inside a cluster is free (fr_add is exact and commutative).  An empty cluster
+// keeps its centroid and raises no error (k_ann_means would divide by quantization(0); the index build refuses such an index later).
+// K up to 2^24 does not fit gridDim.y: a block takes clusters blockIdx.y, blockIdx.y + gridDim.y, ...
+__global__ __launch_bounds__(64) void k_ann_means_gather(const u256* __restrict__ rows, const uint32_t* __restrict__ order, const uint64_t* __restrict__ offsets,
+                                                         uint32_t K, uint32_t dim, int* __restrict__ err, u256* __restrict__ means) {
+  const uint32_t j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= dim) return;
+  for (uint32_t k = blockIdx.y; k < K; k += gridDim.y) {
+    const uint64_t lo = offsets[k], hi = offsets[k + 1];
+    if (lo == hi) continue;
+    ann_mean_word([&](uint64_t v) { return rows + (size_t)order[v] * dim; }, lo, hi, dim, j, err, &means[(size_t)k * dim + j]);
+  }
+}
+// ------------------------------------------------------------------ the fused assign (include/vdb.h vdb_ann_assign_dev):
+// values-only nearest at t = 1 for n rows against K centroids with no n x K matrix anywhere.  The structure is a GEMM's with "field
+// v_qmul and accumulate" where a GEMM has an FMA: a workgroup owns a tile of R rows and walks the K centroids in chunks of C
+// (ann_assign_plan.hpp); per chunk the dim axis passes through LDS ANN_ASSIGN_DC words at a time — the row tile as [row][word], so the C
+// lanes of a row read one broadcast address, the centroid chunk as [word][centroid], so consecutive lanes read consecutive 32-byte
+// words — and every staged word is used R or C times.  A lane keeps the head sums of its ANN_ASSIGN_PAIRS pairs in registers over the
+// dim chunks (no wavefront reduction: fr_add is exact and commutative, the order of a sum is free), then takes each sum through the
+// tail and the C lanes of a row fold (distance, index) in a butterfly — k_nv_argmin's rule: the earlier value in qmin's order, between
+// two of which neither comes before the other the later index — whose result lane 0 of the row folds into the row's running minimum
+// in LDS, the later chunk winning unless the running one comes strictly before it.  The arithmetic is the gadgets' value-only helpers
+// in k_dist_values' and k_dist_tail_values' order of operands (centroid first: distance(vector_i, query)).
+// One term of a head sum (x: the centroid's word, y: the row's).
+__device__ __forceinline__ u256 assign_term(const Gadgets& g, int metric, const u256& x, const u256& y) {
+  if (metric == M_HAMMING) return u256_eq(x, y) ? mont_one<Fr>() : u256_zero();
+  const u256 d = fr_sub(x, y);
+  if (metric == M_MANHATTAN) return g.v_qabs(d);
+  const bool eu = metric == M_EUCLID;   // one v_qmul site for both: (x - y)^2 or x y
+  return g.v_qmul(eu ? d : x, eu ? d : y);
+}
+// The tail of a distance from its head sum: k_dist_tail_values' steps under an emission window that holds no position (every
+// sub-gadget takes its value-only path, a zero denominator lands in c.err).  Cosine's two roots do not depend on the pair: they come
+// from the pre-pass (as: the centroid's, bs: the row's).
+__device__ __forceinline__ u256 assign_tail(WCtx& c, Gadgets& g, int metric, uint32_t D, const u256& s, const u256& as, const u256& bs) {
+  if (metric == M_MANHATTAN) return s;
+  if (metric == M_EUCLID) return g.fp_qsqrt(s);
+  u256 sim;
+  if (metric == M_HAMMING) {
+    const u256 len = fr_mul(to_mont<Fr>(u256_from_u64(D)), g.T.scale);
+    const u256 sq = fr_mul(s, g.T.scale);
+    c.push(len, false);
+    c.push(sq, false);
+    sim = g.fp_qdiv(sq, len);
+  } else {
+    const u256 den = g.fp_qmul(as, bs);
+    sim = g.fp_qdiv(s, den);
+  }
+  const u256 one = g.load_constant(g.T.c_one_q);
+  return g.g_sub(one, sim);
+}
+__device__ __forceinline__ WCtx assign_ctx() {   // k_dist_tail_values' context: position 1 of a window [0, 0)
+  WCtx c{};
+  c.pos = 1;
+  return c;
+}
+// Cosine's pre-pass, once per row and once per centroid instead of once per pair: norms[v] = sum_j v_qmul(x_j, x_j), a wavefront per
+// vector as in k_dist_values, then qsqrt of each in place, a lane per vector.  `count` may pass gridDim.x: a block strides.
+__global__ __launch_bounds__(64) void k_ann_norm_sums(const u256* __restrict__ vecs, uint64_t count, uint32_t dim, u256* __restrict__ norms) {
+  WCtx c{};
+  Gadgets g(c);
+  for (uint64_t v = blockIdx.x; v < count; v += gridDim.x) {
+    const u256* x = vecs + (size_t)v * dim;
+    u256 s = u256_zero();
+    for (uint32_t i = threadIdx.x; i < dim; i += 64) {
+      const u256 w = x[i];
+      s = fr_add(s, g.v_qmul(w, w));
+    }
+    s = wave_sum_fr(s);
+    if (threadIdx.x == 0) norms[v] = s;
+  }
+}
+__global__ __launch_bounds__(64) void k_ann_norm_roots(u256* __restrict__ norms, uint64_t count, int* __restrict__ err) {
+  int e = 0;
+  for (uint64_t v = (uint64_t)blockIdx.x * 64 + threadIdx.x; v < count; v += (uint64_t)gridDim.x * 64) {
+    WCtx c = assign_ctx();   // a context of its own per value: see k_ann_assign's tail
+    Gadgets g(c);
+    norms[v] = g.fp_qsqrt(norms[v]);
+    e |= c.err;
+  }
+  if (e) atomicOr(err, e);
+}
+__global__ __launch_bounds__(ANN_ASSIGN_THREADS) void k_ann_assign(int metric, const u256* __restrict__ rows, const u256* __restrict__ cents,
+                                                                   const u256* __restrict__ row_norms, const u256* __restrict__ cent_norms, uint32_t n,
+                                                                   uint32_t K, uint32_t dim, uint32_t C, int* __restrict__ err,
+                                                                   uint32_t* __restrict__ idx_out, u256* __restrict__ dist_out) {
+  __shared__ u256 stage[ANN_ASSIGN_STAGE_WORDS];
+  __shared__ u256 best_s[ANN_ASSIGN_R_MAX];
+  __shared__ uint32_t besti_s[ANN_ASSIGN_R_MAX];
+  constexpr uint32_t DC = ANN_ASSIGN_DC, TB = ANN_ASSIGN_THREADS, PP = ANN_ASSIGN_PAIRS;
+  const uint32_t t = threadIdx.x, RG = TB / C, R = RG * PP, cl = t & (C - 1), rg = t / C;
+  const uint64_t row0 = (uint64_t)blockIdx.x * R;
+  u256* row_s = stage;            // [R][DC]
+  u256* cent_s = stage + R * DC;  // [DC][C]
+  WCtx c{};
+  const Gadgets g(c);   // the value-only helpers: they leave the context alone
+  int e = 0;
+  for (uint32_t c0 = 0; c0 < K; c0 += C) {
+    u256 acc[PP];
+#pragma unroll
+    for (uint32_t p = 0; p < PP; p++) acc[p] = u256_zero();
+    for (uint32_t d0 = 0; d0 < dim; d0 += DC) {
+      const uint32_t dcur = dim - d0 < DC ? dim - d0 : DC;
+      __syncthreads();   // the readers of the stage before: the last dim chunk's, or the tail's of the chunk before
+      // rows past n and centroids past K are staged as the last real one: every pair a lane computes is a pair of the call, and raises
+      // the domain errors of one
+      for (uint32_t e = t; e < (R + C) * DC; e += TB) {
+        const uint32_t v = e / DC, d = e % DC;
+        if (d >= dcur) continue;
+        if (v < R) {
+          const uint64_t r = row0 + v < n ? row0 + v : n - 1;
+          row_s[v * DC + d] = rows[(size_t)r * dim + d0 + d];
+        } else {
+          const uint32_t cc = c0 + (v - R) < K ? c0 + (v - R) : K - 1;
+          cent_s[d * C + (v - R)] = cents[(size_t)cc * dim + d0 + d];
+        }
+      }
+      __syncthreads();
+      for (uint32_t d = 0; d < dcur; d++) {
+        const u256 x = cent_s[d * C + cl];
+#pragma unroll
+        for (uint32_t p = 0; p < PP; p++) acc[p] = fr_add(acc[p], assign_term(g, metric, x, row_s[(rg + RG * p) * DC + d]));
+      }
+    }
+    // the sums leave the registers for the lane's own PP slots of the stage: the tail below is one body walked PP times, not PP bodies
+    __syncthreads();
+#pragma unroll
+    for (uint32_t p = 0; p < PP; p++) stage[p * TB + t] = acc[p];
+#pragma unroll 1
+    for (uint32_t p = 0; p < PP; p++) {
+      const uint32_t r = rg + RG * p, cc = c0 + cl;
+      const uint64_t row = row0 + r < n ? row0 + r : n - 1;
+      u256 as = u256_zero(), bs = u256_zero();
+      if (metric == M_COSINE) {
+        as = cent_norms[cc < K ? cc : K - 1];
+        bs = row_norms[row];
+      }
+      // A context of its own per tail, at the constant position 1 of the window [0, 0): the compiler then sees every sub-gadget's
+      // window test fail (positions only grow from 1), as it does in k_dist_tail_values, and drops the emitting paths with their
+      // out-of-line calls; a context carried around the loop hides that and costs 256 VGPRs and 616 B of scratch a lane.
+      WCtx ct = assign_ctx();
+      Gadgets gt(ct);
+      u256 dv = assign_tail(ct, gt, metric, dim, stage[p * TB + t], as, bs);
+      e |= ct.err;
+      uint32_t di = cc;
+      // a lane past the last centroid holds the chunk's first entry instead: a real entry with the chunk's lowest index displaces no winner
+      const u256 first = wave_bcast(dv, (int)((t & 63u) & ~(C - 1)));
+      if (cc >= K) {
+        dv = first;
+        di = c0;
+      }
+      for (uint32_t off = C >> 1; off >= 1; off >>= 1) {
+        u256 o;
+#pragma unroll
+        for (int k = 0; k < 8; k++) o.w[k] = __shfl_xor(dv.w[k], (int)off, 64);
+        const uint32_t oi = __shfl_xor(di, (int)off, 64);
+        const bool o_first = g.v_is_neg(from_mont<Fr>(fr_sub(o, dv))), b_first = g.v_is_neg(from_mont<Fr>(fr_sub(dv, o)));
+        if (o_first || (!b_first && oi > di)) {
+          dv = o;
+          di = oi;
+        }
+      }
+      if (cl == 0 && (c0 == 0 || !g.v_is_neg(from_mont<Fr>(fr_sub(best_s[r], dv))))) {
+        best_s[r] = dv;
+        besti_s[r] = di;
+      }
+    }
+  }
+  __syncthreads();
+  if (t < R && row0 + t < n) {
+    idx_out[row0 + t] = besti_s[t];
+    if (dist_out) dist_out[row0 + t] = best_s[t];
+  }
   if (e) atomicOr(err, e);
 }
 __global__ void k_push_cells(Streams st, uint64_t pos, u256 a, u256 b, uint32_t n) {
@@ -2980,6 +3161,36 @@ static int ann_means_check(const uint64_t* offsets, size_t n, size_t K, size_t d
   return VDB_OK;
 }
 
+static_assert(ANN_ASSIGN_PLAN_OK == VDB_OK && ANN_ASSIGN_PLAN_REFUSED == VDB_ERR_ARG, "ann_assign_plan.hpp returns the C ABI's codes");
+static int ann_assign_planned(int metric, size_t n, size_t K, size_t dim, AnnAssignPlan* pl) {
+  VDB_ARG(metric >= M_EUCLID && metric <= M_HAMMING, "unknown metric");
+  const char* why = "";
+  if (int rc = ann_assign_plan(n, K, dim, metric == M_COSINE, pl, &why)) {
+    set_error("%s", why);
+    return rc;
+  }
+  return VDB_OK;
+}
+// the fused assign (include/vdb.h vdb_ann_assign_dev): cosine's pre-pass into work space of n + K words, then one launch whatever n and K
+static int ann_assign_dev(FpEntry* fp, int metric, const AnnAssignPlan& pl, const u256* rows, const u256* cents, size_t n, size_t K, size_t dim, int* err,
+                          uint32_t* idx, u256* dist_out) {
+  Streams st{nullptr, nullptr, nullptr, err, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};   // the empty rank window: no stream is attached
+  TRY(set_winv(st, fp->dev));
+  u256* norms = nullptr;
+  if (metric == M_COSINE) {
+    norms = (u256*)scratch_get(0, pl.work_bytes);
+    if (!norms) return VDB_ERR_OOM;
+    const size_t cap = (size_t)ctx().cu_count * 64;
+    VDB_LAUNCH(k_ann_norm_sums, dim3((unsigned)(n < cap ? n : cap)), dim3(64), rows, (uint64_t)n, (uint32_t)dim, norms);
+    VDB_LAUNCH(k_ann_norm_sums, dim3((unsigned)(K < cap ? K : cap)), dim3(64), cents, (uint64_t)K, (uint32_t)dim, norms + n);
+    const size_t groups = (n + K + 63) / 64;
+    VDB_LAUNCH(k_ann_norm_roots, dim3((unsigned)(groups < cap ? groups : cap)), dim3(64), norms, (uint64_t)(n + K), err);
+  }
+  VDB_LAUNCH(k_ann_assign, dim3(pl.grid), dim3(ANN_ASSIGN_THREADS), metric, rows, cents, norms, norms ? norms + n : nullptr, (uint32_t)n, (uint32_t)K,
+             (uint32_t)dim, pl.C, err, idx, dist_out);
+  return VDB_OK;
+}
+
 }  // namespace vdb
 
 using namespace vdb;
@@ -3991,6 +4202,73 @@ int vdb_ann_cluster_means(uint32_t P, uint32_t L, const vdb_fr* grouped, const u
   TRY(check_err_flag(derr));
   TRY(download(means_out, dmeans.p, K * dim * sizeof(u256)));
   VDB_HIP(hipStreamSynchronize(ctx().stream));
+  return VDB_OK;
+}
+
+// the tile plan of the fused assign as the driver takes it (ann_assign_plan.hpp), for a caller that sizes by it and for the tests; needs no
+// device.  out: R, C, DC, chunks, dchunks, grid, lds_bytes, work_bytes
+int vdb_ann_assign_plan(int metric, size_t n, size_t K, size_t dim, uint64_t* out) {
+  VDB_ARG(out, "null pointer");
+  AnnAssignPlan pl;
+  TRY(ann_assign_planned(metric, n, K, dim, &pl));
+  const uint64_t v[8] = {pl.R, pl.C, pl.DC, pl.chunks, pl.dchunks, pl.grid, pl.lds_bytes, pl.work_bytes};
+  memcpy(out, v, sizeof(v));
+  return VDB_OK;
+}
+// the nearest centroid of every row by the fused kernel, values only (include/vdb.h): no stream, no window, no n x K work space
+int vdb_ann_assign_dev(uint32_t P, uint32_t L, int metric, const vdb_fr* rows_dev, const vdb_fr* centroids_dev, size_t n, size_t K, size_t dim,
+                       uint32_t* idx_dev, vdb_fr* dist_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(rows_dev && centroids_dev && idx_dev, "null pointer");
+  AnnAssignPlan pl;
+  TRY(ann_assign_planned(metric, n, K, dim, &pl));
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  int* derr;
+  TRY(err_word(&derr));
+  TRY(ann_assign_dev(fp, metric, pl, as_u256(rows_dev), as_u256(centroids_dev), n, K, dim, derr, idx_dev, as_u256(dist_dev)));
+  return check_err_flag(derr);
+}
+// Lloyd iterations on the device (include/vdb.h): assign, count the changes, stop at none, group, means.  The ids alternate between
+// ids_dev and a buffer of the call's; `cur` is the assignment the centroids are the means of.
+int vdb_ann_train_dev(uint32_t P, uint32_t L, int metric, const vdb_fr* rows_dev, size_t n, size_t K, size_t dim, size_t max_iterations,
+                      vdb_fr* centroids_dev, uint32_t* ids_dev, uint64_t* sizes_host, size_t* iterations_run) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(rows_dev && centroids_dev && ids_dev && sizes_host && iterations_run, "null pointer");
+  VDB_ARG(max_iterations > 0, "max_iterations = 0");
+  AnnAssignPlan pl;
+  TRY(ann_assign_planned(metric, n, K, dim, &pl));
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_ids = up(n * sizeof(uint32_t)), b_cur = up(K * sizeof(uint32_t)), b_off = up((K + 1) * sizeof(uint64_t));
+  DevBuf work;
+  TRY(work.alloc(2 * b_ids + b_cur + b_off + 256));
+  uint8_t* w = work.as<uint8_t>();
+  uint32_t *nxt = (uint32_t*)w, *order = (uint32_t*)(w + b_ids), *cursor = (uint32_t*)(w + 2 * b_ids), *cur = ids_dev;
+  uint64_t* offsets = (uint64_t*)(w + 2 * b_ids + b_cur);
+  uint32_t* count = (uint32_t*)(w + 2 * b_ids + b_cur + b_off);
+  int* derr;
+  TRY(err_word(&derr));
+  VDB_HIP(hipMemsetAsync(cur, 0xff, n * sizeof(uint32_t), ctx().stream));   // no id: the first assignment changes every row
+  size_t it = 0;
+  while (it < max_iterations) {
+    TRY(ann_assign_dev(fp, metric, pl, as_u256(rows_dev), as_u256(centroids_dev), n, K, dim, derr, nxt, nullptr));
+    uint32_t changed = 0;
+    TRY(ann_count_changes_dev(nxt, cur, n, count, &changed));
+    if (!changed) break;   // converged: the centroids are the means of `cur`, and `cur` is routed to them
+    std::swap(cur, nxt);
+    TRY(ann_group_ids_dev(cur, n, K, cursor, offsets, order));
+    VDB_LAUNCH(k_ann_means_gather, dim3((unsigned)((dim + 63) / 64), (unsigned)(K < 65535 ? K : 65535)), dim3(64), as_u256(rows_dev), order, offsets,
+               (uint32_t)K, (uint32_t)dim, derr, as_u256(centroids_dev));
+    it++;
+  }
+  if (cur != ids_dev) VDB_HIP(hipMemcpyAsync(ids_dev, cur, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx().stream));
+  std::vector<uint64_t> off(K + 1);
+  TRY(download(off.data(), offsets, (K + 1) * sizeof(uint64_t)));
+  TRY(check_err_flag(derr));   // (synchronizes: `off` is here)
+  for (size_t k = 0; k < K; k++) sizes_host[k] = off[k + 1] - off[k];
+  *iterations_run = it;
   return VDB_OK;
 }
 

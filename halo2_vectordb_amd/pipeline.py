@@ -1244,6 +1244,27 @@ class AnnIndex:
                                                self.d_offsets.ptr, self.d_forest.ptr, self.d_roots.ptr))
 
     @classmethod
+    def train(cls, vectors, K, iterations=16, init=None, P=48, L=13, metric="euclidean"):
+        """an index trained on the device from the raw rows (vdb_ann_train_dev): `vectors` (n, dim) f64 are quantized once and uploaded
+        once for the whole run, at most `iterations` Lloyd iterations run from `init` ((K, dim) f64 or (K, dim, 4); by default the first K rows) in the circuit's
+        fixed-point arithmetic — the routing is probe's, the centroids are means()'s — and the index is built from the ids and
+        centroids they end in.  The result carries `iterations_run` and `converged`; a converged index passes AnnAuditHotPath and
+        AnnMeanHotPath for every cluster.  ValueError: a cluster that ends empty."""
+        vec = np.asarray(vectors)
+        qvec = np.ascontiguousarray(vec, dtype=np.uint64) if vec.ndim == 3 else api.quantize(np.ascontiguousarray(vec, dtype=np.float64), P)
+        n, dim = qvec.shape[0], qvec.shape[1]
+        cent = qvec[:K] if init is None else np.asarray(init)
+        qcent = np.ascontiguousarray(cent, dtype=np.uint64) if cent.ndim == 3 else api.quantize(np.ascontiguousarray(cent, dtype=np.float64), P)
+        if qcent.shape != (K, dim, 4):
+            raise ValueError("the initial centroids are not (K, dim)")
+        ids, qcent, sizes, run = api.ann_train(metric, qvec, qcent, iterations, P, L)
+        if (sizes == 0).any():
+            raise ValueError(f"cluster {int(np.argmin(sizes != 0))} ended empty: train with another init or a smaller K")
+        ix = cls(n, dim, K, qvec, ids, qcent, P=P, L=L, metric=metric)
+        ix.iterations_run, ix.converged = run, run < iterations
+        return ix
+
+    @classmethod
     def from_resident(cls, dim, K, sizes, n_digests, segments, qcent, qvec, cluster_ids, P=48, L=13, metric="euclidean"):
         """an index over buffers that are filled on the device (vdb_ann_index_apply_dev) instead of built here: the host-side shape
         (`sizes` of the K clusters, the forest's `n_digests` and `segments`), the quantized centroids and database, and fresh device

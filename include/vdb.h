@@ -824,6 +824,33 @@ int vdb_ann_cluster_means_dev(uint32_t precision_bits, uint32_t lookup_bits, con
 int vdb_ann_cluster_means(uint32_t precision_bits, uint32_t lookup_bits, const vdb_fr *grouped, const uint64_t *offsets, size_t n, size_t K,
                           size_t dim, vdb_fr *means_out);
 
+/* Training the index on the device in the circuit's own arithmetic.
+ *
+ * vdb_ann_assign_dev: vdb_nearest_values_dev's answer with the rows as queries and the centroids as the database — idx[i] the LAST
+ * centroid at the minimum of the circuit's fixed-point distance(centroid_c, row_i), dist[i] (may be NULL) that minimum, both bit for
+ * bit wherever that call runs — by one fused, tiled kernel that never holds the n x K distances: n up to 2^32 - 1, K and dim up to
+ * 2^24, no limit on n * K, work space (n + K) words under cosine and none otherwise.  rows: n x dim; centroids: K x dim; idx: n x
+ * uint32.  VDB_ERR_ARG before anything is launched (idx and dist untouched): a null pointer, an unknown metric, n, K or dim zero or
+ * above those limits.  VDB_ERR_DOMAIN: a zero denominator (a zero row under cosine), as vdb_nearest_values reports it.
+ * vdb_ann_assign_plan: the tile plan that call launches with (csrc/ann_assign_plan.hpp) and its refusals; needs no device.  out:
+ * 8 x uint64: R rows of a workgroup's tile, C centroids of a chunk, DC words of a dim chunk, ceil(K / C), ceil(dim / DC), the grid
+ * ceil(n / R), LDS bytes of a workgroup, bytes of work space.
+ *
+ * vdb_ann_train_dev: at most max_iterations Lloyd iterations from the centroids given, all on the device, one 4-byte read-back each:
+ * assign every row; count the rows whose id changed and stop if none did; group the ids (a counting sort); replace every centroid
+ * by vdb_ann_cluster_means' mean of its rows, read in place.  A cluster no row is assigned to keeps its centroid (sizes[k] = 0: the
+ * index build refuses such an index).  centroids: K x dim, in: the initial ones, out: the final ones; ids: n x uint32, out; sizes: K x
+ * uint64, a HOST array, out; iterations_run: how often the centroids were replaced.  The centroids returned are always the means of
+ * the ids returned.  iterations_run < max_iterations says the run converged: the ids are also every row's nearest centroid, so the
+ * index built from them passes vdb_wit_ann_audit and vdb_wit_ann_mean for every cluster.  At iterations_run == max_iterations the ids
+ * are the assignment the last means were taken from and need not be nearest to them.  VDB_ERR_ARG before anything is launched:
+ * vdb_ann_assign_dev's, and max_iterations == 0. */
+int vdb_ann_assign_plan(int metric, size_t n, size_t K, size_t dim, uint64_t *out);
+int vdb_ann_assign_dev(uint32_t precision_bits, uint32_t lookup_bits, int metric, const vdb_fr *rows_dev, const vdb_fr *centroids_dev, size_t n,
+                       size_t K, size_t dim, uint32_t *idx_dev, vdb_fr *dist_dev);
+int vdb_ann_train_dev(uint32_t precision_bits, uint32_t lookup_bits, int metric, const vdb_fr *rows_dev, size_t n, size_t K, size_t dim,
+                      size_t max_iterations, vdb_fr *centroids_dev, uint32_t *ids_dev, uint64_t *sizes_host, size_t *iterations_run);
+
 /* ---- b4 stream -> columns: replaces halo2-base GateThreadBuilder::assign_all (break points, keygen)
  *      and assign_threads_in (prover) as driven by RangeCircuitBuilder::prover(builder, break_points)
  *      (src/scaffold/mod.rs:393-396).  Columns are 2^k rows; the cell on a break row is duplicated at
