@@ -709,6 +709,61 @@ def ann_assign(metric, rows, centroids, P=48, L=13):
             b.free()
 
 
+def ann_search_plan(metric, Q, dim, topk, n=0, span=0, cus=0, offsets=None, clusters=None):
+    """the plan of a batch search (vdb_ann_search_plan; needs no device): the dense form over `n` rows, or with `offsets` (K + 1) and
+    `clusters` (Q, p) the index form.  dict of R, C, t, span, lds_bytes, work_bytes, norm_words, tasks (tasks, 6: q_start, q_count, v_lo,
+    v_hi, idx_base, slot0), order, list_off (Q + 1), list_slots, list_base, last (Q); VdbError -3 for a call the driver refuses"""
+    lib = _lib.load()
+    K = p = 0
+    if clusters is not None:
+        offsets, clusters = np.ascontiguousarray(offsets, dtype=np.uint64), np.ascontiguousarray(clusters, dtype=np.uint32).reshape(int(Q), -1)
+        K, p = offsets.size - 1, clusters.shape[1]
+    head = np.zeros(10, dtype=np.uint64)
+    args = (METRICS[metric], _sz(Q), _sz(n), _sz(K), _sz(dim), _sz(p), _sz(topk), _sz(span), ctypes.c_uint32(cus), None if clusters is None else _p(offsets),
+            None if clusters is None else _p(clusters), _p(head))
+    check(lib.vdb_ann_search_plan(*args, None, None, None, None, None, None))
+    R, C, t, span, lds, n_tasks, n_slots, n_ent, work, norm = (int(v) for v in head)
+    out = [np.zeros(s, dtype=np.uint32) for s in ((n_tasks, 6), n_ent, int(Q) + 1, n_slots, n_slots, int(Q))]
+    check(lib.vdb_ann_search_plan(*args, *[_p(a) for a in out]))
+    return dict(R=R, C=C, t=t, span=span, lds_bytes=lds, work_bytes=work, norm_words=norm,
+                **dict(zip(("tasks", "order", "list_off", "list_slots", "list_base", "last"), out)))
+
+
+def ann_search_dev(metric, d_queries, d_vectors, Q, n, dim, topk, d_idx, d_dist=None, span=0, P=48, L=13):
+    """vdb_ann_search_dev over device buffers: the dense form, every query against rows [0, n) of `d_vectors`"""
+    check(_lib.init().vdb_ann_search_dev(ctypes.c_uint32(P), ctypes.c_uint32(L), METRICS[metric], d_queries.ptr, d_vectors.ptr, _sz(Q), _sz(n), _sz(dim),
+                                         _sz(topk), _sz(span), d_idx.ptr, d_dist.ptr if d_dist is not None else None))
+
+
+def ann_search_probed_dev(metric, d_queries, d_grouped, offsets, clusters, dim, topk, d_idx, d_dist=None, span=0, P=48, L=13):
+    """vdb_ann_search_probed_dev over device buffers: query j against the members of clusters[j] ((Q, p), host) of the grouped rows,
+    cluster k being rows [offsets[k], offsets[k + 1]) (host)"""
+    offsets, clusters = np.ascontiguousarray(offsets, dtype=np.uint64), np.ascontiguousarray(clusters, dtype=np.uint32)
+    Q, p = clusters.shape
+    check(_lib.init().vdb_ann_search_probed_dev(ctypes.c_uint32(P), ctypes.c_uint32(L), METRICS[metric], d_queries.ptr, d_grouped.ptr, _p(offsets),
+                                                _p(clusters), _sz(Q), _sz(offsets.size - 1), _sz(dim), _sz(p), _sz(topk), _sz(span), d_idx.ptr,
+                                                d_dist.ptr if d_dist is not None else None))
+
+
+def ann_search(metric, queries, vectors, topk, P=48, L=13, span=0):
+    """the `topk` nearest of every row of `queries` (Q, dim, 4) among `vectors` (n, dim, 4) by the fused, tiled search
+    (vdb_ann_search_dev): nearest_topk_values(metric, queries, vectors, topk)'s (idx (Q, t) uint32, dist (Q, t, 4)) bit for bit, with
+    no limit on Q * n * t.  `span`: the rows a workgroup walks (0: the plan's); it never changes the result."""
+    _lib.init()
+    queries, vectors = _fr(queries), _fr(vectors)
+    Q, n, dim, t = queries.shape[0], vectors.shape[0], vectors.shape[1], int(topk)
+    assert queries.ndim == 3 and vectors.ndim == 3 and queries.shape[1] == dim
+    bufs = [DeviceBuffer(max(b, 32)) for b in (queries.nbytes, vectors.nbytes, Q * t * 4, Q * t * 32)]
+    try:
+        bufs[0].upload(queries)
+        bufs[1].upload(vectors)
+        ann_search_dev(metric, bufs[0], bufs[1], Q, n, dim, t, bufs[2], bufs[3], span, P, L)
+        return bufs[2].download((Q, t), dtype=np.uint32), bufs[3].download((Q, t, 4))
+    finally:
+        for b in bufs:
+            b.free()
+
+
 def ann_train_dev(metric, d_rows, n, K, dim, d_centroids, d_ids, iterations, P=48, L=13):
     """vdb_ann_train_dev over device buffers: the rows stay where they are, `d_centroids` (in: initial, out: final) and `d_ids` are
     written -> (sizes (K,) int64, iterations_run)"""

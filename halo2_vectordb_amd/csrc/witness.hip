@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "ann_assign_plan.hpp"
+#include "ann_search_plan.hpp"
 #include "ann_update_host.hpp"
 #include "common.hpp"
 #include "gadgets.hpp"
@@ -1228,6 +1229,226 @@ __global__ __launch_bounds__(ANN_ASSIGN_THREADS) void k_ann_assign(int metric, c
     if (dist_out) dist_out[row0 + t] = best_s[t];
   }
   if (e) atomicOr(err, e);
+}
+// ------------------------------------------------------------------ the batch search (include/vdb.h vdb_ann_search_dev and
+// vdb_ann_search_probed_dev): the t nearest of every query as values, the rounds of nearest_topk without a Q x n matrix.
+// What a query's result is: its distances' CLASSES are the distinct bit patterns strictly before M = nv_mask_value in qmin's order;
+// round r states the r-th class and the largest index at it, rounds past the last class state (M, last).  That is a function of the
+// SET of (value, index) pairs, so a query's candidates may be cut into pieces and the pieces' lists merged in any order.
+//
+// k_ann_search is k_ann_assign's tile with other roles: a workgroup takes one task (ann_search_plan.hpp) — the R rows are queries, read
+// through order[], the "centroids" are rows [v_lo, v_hi) of the vectors array walked in chunks of C — and the same head, stage and
+// tails.  In place of the row's running minimum stands the row's running LIST in LDS: up to t values ascending in qmin's order, each
+// with its index, and a fill count.  The C lanes of a row lie in one wavefront and a row belongs to one wavefront for the whole task, so
+// a list is wavefront-private: no barrier guards it, only the wavefront's own order of LDS operations (search_lds_order).
+__device__ __forceinline__ bool search_before(const Gadgets& g, const u256& a, const u256& b) { return g.v_is_neg(from_mont<Fr>(fr_sub(a, b))); }
+// the lanes of a wavefront run in lockstep, but the compiler orders one lane's accesses only: keep every LDS access before this point
+// before every one after it
+__device__ __forceinline__ void search_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// The candidates (dv, di) of the C lanes of a row, `live` where the lane holds one, into the row's list L / I / *cnt of capacity tk <= C.
+// Every lane of the wavefront calls it (the shuffles and ballots are the wavefront's; its 64 / C rows proceed side by side); `base` is
+// the row's first lane, `cl` the lane's place in the row.  First the filter: a candidate matters only if the list is not full or it
+// does not come after the last entry — after the first chunks almost none does.  The survivors are then taken one at a time from the
+// ballot, lowest lane (lowest index) first, and each is held against the list as it stands by then: lane l compares it with entry l,
+// the ballots give "equal to an entry" (the larger index stays) or the number of entries strictly before it, which is its place; the
+// lanes from there on move their entries up by one and the last falls off a full list.
+__device__ __forceinline__ void search_insert(const Gadgets& g, u256* L, uint32_t* I, uint32_t* cnt, uint32_t tk, uint32_t C, uint32_t base, uint32_t cl,
+                                              const u256& dv, uint32_t di, bool live) {
+  const uint64_t rowmask = C == 64 ? ~0ull : (1ull << C) - 1;
+  uint32_t fill = *cnt;
+  bool want = live;
+  if (want && fill == tk) want = !search_before(g, L[tk - 1], dv);
+  uint64_t m = (__ballot(want) >> base) & rowmask;
+  while (__any(m != 0)) {
+    const bool act = m != 0;
+    const int src = (int)base + (act ? __ffsll((long long)m) - 1 : 0);
+    u256 cv;
+#pragma unroll
+    for (int k = 0; k < 8; k++) cv.w[k] = __shfl(dv.w[k], src, 64);
+    const uint32_t ci = __shfl(di, src, 64);
+    m &= m - 1;
+    fill = *cnt;
+    const bool have = cl < fill;
+    const u256 ev = have ? L[cl] : cv;
+    const uint32_t ei = have ? I[cl] : 0;
+    const bool eq = act && have && u256_eq(ev, cv), lt = act && have && search_before(g, ev, cv);
+    const uint64_t eqm = (__ballot(eq) >> base) & rowmask, ltm = (__ballot(lt) >> base) & rowmask;
+    const uint32_t pos = (uint32_t)__popcll(ltm);
+    if (eqm) {
+      if (eq && ci > ei) I[cl] = ci;
+    } else if (act && pos < tk) {
+      if (have && cl >= pos && cl + 1 < tk) {
+        L[cl + 1] = ev;
+        I[cl + 1] = ei;
+      }
+      if (cl == pos) {
+        L[cl] = cv;
+        I[cl] = ci;
+      }
+      if (cl == 0 && fill < tk) *cnt = fill + 1;
+    }
+    search_lds_order();
+  }
+}
+__global__ __launch_bounds__(ANN_ASSIGN_THREADS) void k_ann_search(int metric, const u256* __restrict__ queries, const u256* __restrict__ vecs,
+                                                                   const u256* __restrict__ q_norms, const u256* __restrict__ v_norms,
+                                                                   const uint32_t* __restrict__ order, const AnnSearchTask* __restrict__ tasks,
+                                                                   uint32_t dim, uint32_t C, uint32_t tk, int* __restrict__ err,
+                                                                   u256* __restrict__ list_val, uint32_t* __restrict__ list_idx,
+                                                                   uint32_t* __restrict__ list_cnt) {
+  __shared__ u256 stage[ANN_ASSIGN_STAGE_WORDS];
+  __shared__ u256 lv[ANN_SEARCH_LIST_WORDS];        // [row][t]
+  __shared__ uint32_t li[ANN_SEARCH_LIST_WORDS];
+  __shared__ uint32_t lc[ANN_ASSIGN_R_MAX];         // entries of a row's list
+  __shared__ uint32_t qn[ANN_ASSIGN_R_MAX];         // the tile's query numbers
+  constexpr uint32_t DC = ANN_ASSIGN_DC, TB = ANN_ASSIGN_THREADS, PP = ANN_ASSIGN_PAIRS;
+  const uint32_t t = threadIdx.x, RG = TB / C, R = RG * PP, cl = t & (C - 1), rg = t / C, base = (t & 63u) & ~(C - 1);
+  const AnnSearchTask* tk_ = tasks + blockIdx.x;
+  const uint32_t q_start = tk_->q_start, qc = tk_->q_count, v_lo = tk_->v_lo, v_hi = tk_->v_hi, idx_base = tk_->idx_base, slot0 = tk_->slot0;
+  u256* row_s = stage;            // [R][DC]
+  u256* cent_s = stage + R * DC;  // [DC][C]
+  WCtx c{};
+  const Gadgets g(c);   // the value-only helpers: they leave the context alone
+  const u256 M = nv_mask_value(&g.T);
+  int e = 0;
+  // queries past the tile's last are staged as the last real one, rows past v_hi as row v_hi - 1 (every pair a lane computes is a pair
+  // of the call, and raises the domain errors of one); their candidates never reach a list
+  if (t < R) {
+    lc[t] = 0;
+    qn[t] = order[q_start + (t < qc ? t : qc - 1)];
+  }
+  for (uint64_t v0 = v_lo; v0 < v_hi; v0 += C) {
+    u256 acc[PP];
+#pragma unroll
+    for (uint32_t p = 0; p < PP; p++) acc[p] = u256_zero();
+    for (uint32_t d0 = 0; d0 < dim; d0 += DC) {
+      const uint32_t dcur = dim - d0 < DC ? dim - d0 : DC;
+      __syncthreads();   // qn; the readers of the stage before: the last dim chunk's, or the tail's of the chunk before
+      for (uint32_t e = t; e < (R + C) * DC; e += TB) {
+        const uint32_t v = e / DC, d = e % DC;
+        if (d >= dcur) continue;
+        if (v < R) {
+          row_s[v * DC + d] = queries[(size_t)qn[v] * dim + d0 + d];
+        } else {
+          const uint64_t vv = v0 + (v - R) < v_hi ? v0 + (v - R) : v_hi - 1;
+          cent_s[d * C + (v - R)] = vecs[(size_t)vv * dim + d0 + d];
+        }
+      }
+      __syncthreads();
+      for (uint32_t d = 0; d < dcur; d++) {
+        const u256 x = cent_s[d * C + cl];
+#pragma unroll
+        for (uint32_t p = 0; p < PP; p++) acc[p] = fr_add(acc[p], assign_term(g, metric, x, row_s[(rg + RG * p) * DC + d]));
+      }
+    }
+    // the sums leave the registers for the lane's own PP slots of the stage, as in k_ann_assign: one tail body walked PP times
+    __syncthreads();
+#pragma unroll
+    for (uint32_t p = 0; p < PP; p++) stage[p * TB + t] = acc[p];
+#pragma unroll 1
+    for (uint32_t p = 0; p < PP; p++) {
+      const uint32_t r = rg + RG * p;
+      const uint64_t vv = v0 + cl;
+      u256 as = u256_zero(), bs = u256_zero();
+      if (metric == M_COSINE) {
+        as = v_norms[vv < v_hi ? vv : v_hi - 1];
+        bs = q_norms[qn[r]];
+      }
+      WCtx ct = assign_ctx();   // a context of its own per tail: see k_ann_assign
+      Gadgets gt(ct);
+      const u256 dv = assign_tail(ct, gt, metric, dim, stage[p * TB + t], as, bs);
+      e |= ct.err;
+      // a padding lane — a row past v_hi, a query past the tile — is skipped outright: its value is a real pair's, its index is not;
+      // a value not strictly before M is no class
+      const bool live = vv < v_hi && r < qc && search_before(g, dv, M);
+      search_insert(g, lv + r * tk, li + r * tk, lc + r, tk, C, base, cl, dv, idx_base + (uint32_t)(vv - v_lo), live);
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = t; i < qc * tk; i += TB) {
+    const uint32_t r = i / tk, l = i % tk;
+    if (l < lc[r]) {
+      list_val[(size_t)(slot0 + r) * tk + l] = lv[i];
+      list_idx[(size_t)(slot0 + r) * tk + l] = li[i];
+    }
+  }
+  if (t < qc) list_cnt[slot0 + t] = lc[t];
+  if (e) atomicOr(err, e);
+}
+// entry `lane` of the partial list the CSR names at `s`, its index with the list's base added; live: the list holds such an entry
+__device__ __forceinline__ void search_fetch(const u256* __restrict__ list_val, const uint32_t* __restrict__ list_idx, const uint32_t* __restrict__ list_cnt,
+                                             const uint32_t* __restrict__ list_slots, const uint32_t* __restrict__ list_base, uint32_t s, uint32_t tk,
+                                             uint32_t lane, u256& v, uint32_t& i, bool& live) {
+  const uint32_t slot = list_slots[s];
+  live = lane < list_cnt[slot];
+  if (live) {
+    v = list_val[(size_t)slot * tk + lane];
+    i = list_idx[(size_t)slot * tk + lane] + list_base[s];
+  }
+}
+// One wavefront per query folds the query's partial lists (the CSR of ann_search_plan.hpp) by search_insert's rule, the running list in
+// registers: lane l holds entry l, an insertion is a shuffle up by one from its place.  A partial list is at most t <= 64 entries: one
+// load a lane, the next list's issued before this one is folded; the same filter first.  Then the t rounds: the list's entries, and
+// (M, last) for the rounds past them.  It runs for a single piece too: one path.
+__global__ __launch_bounds__(64) void k_ann_search_merge(const u256* __restrict__ list_val, const uint32_t* __restrict__ list_idx,
+                                                         const uint32_t* __restrict__ list_cnt, const uint32_t* __restrict__ list_off,
+                                                         const uint32_t* __restrict__ list_slots, const uint32_t* __restrict__ list_base,
+                                                         const uint32_t* __restrict__ last, uint32_t Q, uint32_t tk, uint32_t* __restrict__ idx_out,
+                                                         u256* __restrict__ dist_out) {
+  const uint32_t lane = threadIdx.x;
+  WCtx c{};
+  const Gadgets g(c);
+  const u256 M = nv_mask_value(&g.T);
+  for (uint32_t q = blockIdx.x; q < Q; q += gridDim.x) {
+    const uint32_t lo = list_off[q], hi = list_off[q + 1];
+    u256 ev = u256_zero(), nv = u256_zero();
+    uint32_t ei = 0, fill = 0, ni = 0;
+    bool nlive = false;
+    if (lo < hi) search_fetch(list_val, list_idx, list_cnt, list_slots, list_base, lo, tk, lane, nv, ni, nlive);
+    for (uint32_t s = lo; s < hi; s++) {
+      const u256 dv = nv;
+      const uint32_t di = ni;
+      bool want = nlive;
+      if (s + 1 < hi) search_fetch(list_val, list_idx, list_cnt, list_slots, list_base, s + 1, tk, lane, nv, ni, nlive);
+      if (fill == tk) {
+        const u256 tail = wave_bcast(ev, (int)tk - 1);
+        want = want && !search_before(g, tail, dv);
+      }
+      uint64_t m = __ballot(want);
+      while (m) {
+        const int src = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const u256 cv = wave_bcast(dv, src);
+        const uint32_t ci = __shfl(di, src, 64);
+        const bool have = lane < fill;
+        const bool eq = have && u256_eq(ev, cv), lt = have && search_before(g, ev, cv);
+        const uint64_t eqm = __ballot(eq);
+        const uint32_t pos = (uint32_t)__popcll(__ballot(lt));
+        const u256 uv = wave_shfl_up(ev, 1);
+        const uint32_t ui = __shfl_up(ei, 1, 64);
+        if (eqm) {
+          if (eq && ci > ei) ei = ci;
+        } else if (pos < tk) {
+          if (lane > pos) {
+            ev = uv;
+            ei = ui;
+          } else if (lane == pos) {
+            ev = cv;
+            ei = ci;
+          }
+          if (fill < tk) fill++;
+        }
+      }
+    }
+    if (lane < tk) {
+      idx_out[(size_t)q * tk + lane] = lane < fill ? ei : last[q];
+      if (dist_out) dist_out[(size_t)q * tk + lane] = lane < fill ? ev : M;
+    }
+  }
 }
 __global__ void k_push_cells(Streams st, uint64_t pos, u256 a, u256 b, uint32_t n) {
   if (blockIdx.x || threadIdx.x || n == 0) return;
@@ -3191,6 +3412,62 @@ static int ann_assign_dev(FpEntry* fp, int metric, const AnnAssignPlan& pl, cons
   return VDB_OK;
 }
 
+// The plan of a batch search (ann_search_plan.hpp): the dense form where `clusters` is null (every query against rows [0, n)), else the
+// index form (query j against clusters[j p ..] of the K ranges `offsets`).  cus: the CUs the span is sized for.
+static int ann_search_planned(int metric, size_t Q, size_t n, size_t K, size_t dim, size_t probes, size_t t, uint64_t span, uint32_t cus,
+                              const uint64_t* offsets, const uint32_t* clusters, AnnSearchPlan* pl) {
+  VDB_ARG(metric >= M_EUCLID && metric <= M_HAMMING, "unknown metric");
+  VDB_ARG(!clusters == !offsets, "offsets and clusters are given together (the index form) or not at all (the dense form)");
+  const char* why = "";
+  const int rc = clusters ? ann_search_plan_probed(offsets, clusters, Q, K, dim, probes, t, span, cus, metric == M_COSINE, pl, &why)
+                          : ann_search_plan_dense(Q, n, dim, t, span, cus, metric == M_COSINE, pl, &why);
+  if (rc) set_error("%s", why);
+  return rc;
+}
+// the batch search on a plan: the plan's lists to the device, cosine's pre-pass over the queries and the `vec_rows` rows of the vectors
+// array, one launch of k_ann_search over the tasks, one of k_ann_search_merge over the queries.  The plan outlives the call's
+// synchronisation (the caller's check_err_flag): its vectors are the source of the uploads.
+static int ann_search_dev(FpEntry* fp, int metric, const AnnSearchPlan& pl, const u256* queries, const u256* vecs, size_t Q, size_t vec_rows, size_t dim,
+                          int* err, uint32_t* idx, u256* dist_out) {
+  Streams st{nullptr, nullptr, nullptr, err, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};   // the empty rank window: no stream is attached
+  TRY(set_winv(st, fp->dev));
+  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t n_tasks = pl.tasks.size(), n_ent = pl.order.size(), n_slots = (size_t)pl.n_slots, t = pl.t;
+  const size_t b_val = up(n_slots * t * sizeof(u256)), b_norm = up((size_t)pl.norm_words * sizeof(u256)), b_idx = up(n_slots * t * 4),
+               b_slot = up(n_slots * 4), b_task = up(n_tasks * sizeof(AnnSearchTask)), b_ent = up(n_ent * 4), b_q = up((Q + 1) * 4);
+  uint8_t* w = (uint8_t*)scratch_get(0, b_val + b_norm + b_idx + 3 * b_slot + b_task + b_ent + 2 * b_q);
+  if (!w) return VDB_ERR_OOM;
+  u256 *list_val = (u256*)w, *norms = pl.norm_words ? (u256*)(w + b_val) : nullptr;
+  uint8_t* at = w + b_val + b_norm;
+  const auto take = [&](size_t b) {
+    uint8_t* r = at;
+    at += b;
+    return r;
+  };
+  uint32_t *list_idx = (uint32_t*)take(b_idx), *list_cnt = (uint32_t*)take(b_slot), *list_slots = (uint32_t*)take(b_slot), *list_base = (uint32_t*)take(b_slot);
+  AnnSearchTask* tasks = (AnnSearchTask*)take(b_task);
+  uint32_t *order = (uint32_t*)take(b_ent), *list_off = (uint32_t*)take(b_q), *last = (uint32_t*)take(b_q);
+  hipStream_t s = ctx().stream;
+  VDB_HIP(hipMemcpyAsync(tasks, pl.tasks.data(), n_tasks * sizeof(AnnSearchTask), hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(order, pl.order.data(), n_ent * 4, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(list_slots, pl.list_slots.data(), n_slots * 4, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(list_base, pl.list_base.data(), n_slots * 4, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(list_off, pl.list_off.data(), (Q + 1) * 4, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(last, pl.last.data(), Q * 4, hipMemcpyHostToDevice, s));
+  const size_t cap = (size_t)ctx().cu_count * 64;
+  if (norms) {
+    VDB_LAUNCH(k_ann_norm_sums, dim3((unsigned)(Q < cap ? Q : cap)), dim3(64), queries, (uint64_t)Q, (uint32_t)dim, norms);
+    VDB_LAUNCH(k_ann_norm_sums, dim3((unsigned)(vec_rows < cap ? vec_rows : cap)), dim3(64), vecs, (uint64_t)vec_rows, (uint32_t)dim, norms + Q);
+    const size_t groups = (Q + vec_rows + 63) / 64;
+    VDB_LAUNCH(k_ann_norm_roots, dim3((unsigned)(groups < cap ? groups : cap)), dim3(64), norms, (uint64_t)(Q + vec_rows), err);
+  }
+  VDB_LAUNCH(k_ann_search, dim3((unsigned)n_tasks), dim3(ANN_ASSIGN_THREADS), metric, queries, vecs, norms, norms ? norms + Q : nullptr, order, tasks,
+             (uint32_t)dim, pl.C, pl.t, err, list_val, list_idx, list_cnt);
+  VDB_LAUNCH(k_ann_search_merge, dim3((unsigned)(Q < cap ? Q : cap)), dim3(64), list_val, list_idx, list_cnt, list_off, list_slots, list_base, last,
+             (uint32_t)Q, pl.t, idx, dist_out);
+  return VDB_OK;
+}
+
 }  // namespace vdb
 
 using namespace vdb;
@@ -4228,6 +4505,53 @@ int vdb_ann_assign_dev(uint32_t P, uint32_t L, int metric, const vdb_fr* rows_de
   TRY(err_word(&derr));
   TRY(ann_assign_dev(fp, metric, pl, as_u256(rows_dev), as_u256(centroids_dev), n, K, dim, derr, idx_dev, as_u256(dist_dev)));
   return check_err_flag(derr);
+}
+// the plan of a batch search as the driver takes it (ann_search_plan.hpp), for a caller that sizes by it and for the tests; needs no
+// device.  header: R, C, t, span, lds_bytes, tasks, slots, entries of `order`, work_bytes, norm_words.  The arrays may be null (a first
+// call reads their lengths from the header): tasks (tasks, 6), order (entries), list_off (Q + 1), list_slots and list_base (slots),
+// last (Q).
+int vdb_ann_search_plan(int metric, size_t Q, size_t n, size_t K, size_t dim, size_t probes, size_t t, size_t span, uint32_t cus, const uint64_t* offsets,
+                        const uint32_t* clusters, uint64_t* header, uint32_t* tasks, uint32_t* order, uint32_t* list_off, uint32_t* list_slots,
+                        uint32_t* list_base, uint32_t* last) {
+  VDB_ARG(header, "null pointer");
+  AnnSearchPlan pl;
+  TRY(ann_search_planned(metric, Q, n, K, dim, probes, t, span, cus ? cus : 256, offsets, clusters, &pl));
+  const uint64_t v[10] = {pl.R, pl.C, pl.t, pl.span, pl.lds_bytes, pl.tasks.size(), pl.n_slots, pl.order.size(), pl.work_bytes, pl.norm_words};
+  memcpy(header, v, sizeof(v));
+  static_assert(sizeof(AnnSearchTask) == 6 * sizeof(uint32_t), "a task is six words");
+  if (tasks) memcpy(tasks, pl.tasks.data(), pl.tasks.size() * sizeof(AnnSearchTask));
+  if (order) memcpy(order, pl.order.data(), pl.order.size() * 4);
+  if (list_off) memcpy(list_off, pl.list_off.data(), pl.list_off.size() * 4);
+  if (list_slots) memcpy(list_slots, pl.list_slots.data(), pl.list_slots.size() * 4);
+  if (list_base) memcpy(list_base, pl.list_base.data(), pl.list_base.size() * 4);
+  if (last) memcpy(last, pl.last.data(), pl.last.size() * 4);
+  return VDB_OK;
+}
+// the t nearest of every query by the fused, tiled search, values only (include/vdb.h): no stream, no window, no Q x n work space
+static int ann_search_entry(uint32_t P, uint32_t L, int metric, const vdb_fr* queries_dev, const vdb_fr* vectors_dev, const uint64_t* offsets,
+                            const uint32_t* clusters, size_t Q, size_t n, size_t K, size_t dim, size_t probes, size_t t, size_t span, uint32_t* idx_out_dev,
+                            vdb_fr* dist_out_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(queries_dev && vectors_dev && idx_out_dev, "null pointer");
+  AnnSearchPlan pl;
+  TRY(ann_search_planned(metric, Q, n, K, dim, probes, t, span, (uint32_t)ctx().cu_count, offsets, clusters, &pl));
+  FpEntry* fp;
+  TRY(get_fp(P, L, &fp));
+  int* derr;
+  TRY(err_word(&derr));
+  TRY(ann_search_dev(fp, metric, pl, as_u256(queries_dev), as_u256(vectors_dev), Q, clusters ? (size_t)offsets[K] : n, dim, derr, idx_out_dev,
+                     as_u256(dist_out_dev)));
+  return check_err_flag(derr);   // (synchronizes: the plan's vectors may go)
+}
+int vdb_ann_search_dev(uint32_t P, uint32_t L, int metric, const vdb_fr* queries_dev, const vdb_fr* vectors_dev, size_t Q, size_t n, size_t dim, size_t t,
+                       size_t span, uint32_t* idx_out_dev, vdb_fr* dist_out_dev) {
+  return ann_search_entry(P, L, metric, queries_dev, vectors_dev, nullptr, nullptr, Q, n, 0, dim, 0, t, span, idx_out_dev, dist_out_dev);
+}
+int vdb_ann_search_probed_dev(uint32_t P, uint32_t L, int metric, const vdb_fr* queries_dev, const vdb_fr* grouped_dev, const uint64_t* offsets,
+                              const uint32_t* clusters, size_t Q, size_t K, size_t dim, size_t p, size_t t, size_t span, uint32_t* idx_out_dev,
+                              vdb_fr* dist_out_dev) {
+  VDB_ARG(offsets && clusters, "null pointer");
+  return ann_search_entry(P, L, metric, queries_dev, grouped_dev, offsets, clusters, Q, 0, K, dim, p, t, span, idx_out_dev, dist_out_dev);
 }
 // Lloyd iterations on the device (include/vdb.h): assign, count the changes, stop at none, group, means.  The ids alternate between
 // ids_dev and a buffer of the call's; `cur` is the assignment the centroids are the means of.

@@ -1447,6 +1447,70 @@ class AnnIndex:
             for b in (d_rows, d_idx, d_dist):
                 b.free()
 
+    def _search_call(self, queries, topk, call):
+        """upload the (Q, dim) f64 `queries` quantized, run call(d_queries, Q, d_idx, d_dist) and bring back (idx (Q, t) int64, dist (Q, t, 4))"""
+        rows = np.ascontiguousarray(queries, dtype=np.float64).reshape(-1, self.dim)
+        Q, t = rows.shape[0], int(topk)
+        bufs = [api.DeviceBuffer(max(b, 32)) for b in (Q * self.dim * B, Q * t * 4, Q * t * B)]
+        try:
+            bufs[0].upload(api.quantize(rows, self.P))
+            call(bufs[0], Q, bufs[1], bufs[2])
+            return bufs[1].download((Q, t), dtype=np.uint32).astype(np.int64), bufs[2].download((Q, t, 4))
+        finally:
+            for b in bufs:
+                b.free()
+
+    def search(self, queries, probes=1, topk=1, span=0):
+        """the `topk` nearest among the members of the `probes` clusters nearest to every row of `queries` ((Q, dim) f64), as values, in
+        two batch calls.  Stage 1: `probes` rounds over the resident centroids for all queries at once (vdb_ann_search_dev) and one
+        read-back of Q * probes ids; row j of `clusters` is probe_many(q_j, probes).  Stage 2: the (query, cluster) pairs grouped by
+        cluster, every cluster's members staged once for the queries that probe it (vdb_ann_search_probed_dev over d_grouped).
+        -> dict(clusters (Q, p), candidates (Q, t): places in the query's candidate list — the probed clusters' members end to end in
+        round order, AnnProbeQueryHotPath's —, slots (Q, t): database slots through d_slots, as AnnProbeQueryHotPath.neighbours(), dist
+        (Q, t, 4)), nearest first: the rounds vdb_wit_ann_probe states.  ValueError naming the first query whose probed clusters are
+        not pairwise distinct (fewer than `probes` distance classes among the centroids; AnnProbeQueryHotPath refuses it too), or the
+        first with fewer than `topk` candidates."""
+        p, t, name = int(probes), int(topk), self.metric_name
+        if not 1 <= p <= self.K:
+            raise ValueError("probes: at least 1 and at most K")
+        rows = np.ascontiguousarray(queries, dtype=np.float64).reshape(-1, self.dim)
+        out = {}
+
+        def call(d_q, Q, d_idx, d_dist):
+            d_cl = api.DeviceBuffer(max(Q * p * 4, 32))
+            try:
+                api.ann_search_dev(name, d_q, self.d_cent, Q, self.K, self.dim, p, d_cl, None, 0, self.P, self.L)
+                clusters = d_cl.download((Q, p), dtype=np.uint32)
+            finally:
+                d_cl.free()
+            out["clusters"] = clusters.astype(np.int64)
+            for j in range(Q):
+                if len(set(clusters[j].tolist())) != p:
+                    raise ValueError(f"query {j}: the clusters probed are not pairwise distinct: fewer than `probes` distance classes among the centroids")
+            sizes = self.sizes[out["clusters"]]
+            short = np.flatnonzero(sizes.sum(axis=1) < t)
+            if short.size:
+                raise ValueError(f"query {int(short[0])}: fewer than `topk` candidates in the clusters probed")
+            out["cand_offsets"] = np.concatenate([np.zeros((Q, 1), dtype=np.int64), np.cumsum(sizes, axis=1)], axis=1)
+            api.ann_search_probed_dev(name, d_q, self.d_grouped, self.offsets, clusters, self.dim, t, d_idx, d_dist, span, self.P, self.L)
+
+        cand, dist = self._search_call(rows, t, call)
+        off = out.pop("cand_offsets")
+        r = np.asarray([np.searchsorted(off[j], cand[j], side="right") - 1 for j in range(cand.shape[0])], dtype=np.int64).reshape(cand.shape)
+        grouped = self.offsets[np.take_along_axis(out["clusters"], r, axis=1)] + cand - np.take_along_axis(off, r, axis=1)
+        slots = self.d_slots.download((self.n,), dtype=np.uint32).astype(np.int64)
+        return dict(clusters=out["clusters"], candidates=cand, slots=slots[grouped], dist=dist)
+
+    def search_exact(self, queries, topk, span=0):
+        """the exact `topk` nearest of every row of `queries` ((Q, dim) f64) over ALL rows of the index (vdb_ann_search_dev over
+        d_grouped), for measuring search()'s recall -> (slots (Q, t) int64: database slots through d_slots, dist (Q, t, 4)), nearest
+        first.  The rows are searched in GROUPED order: among rows at equal distance a round states the last in grouped order, which
+        need not be the last in database order; the distances are the same either way."""
+        grouped, dist = self._search_call(queries, topk, lambda d_q, Q, d_idx, d_dist: api.ann_search_dev(
+            self.metric_name, d_q, self.d_grouped, Q, self.n, self.dim, int(topk), d_idx, d_dist, span, self.P, self.L))
+        slots = self.d_slots.download((self.n,), dtype=np.uint32).astype(np.int64)
+        return slots[grouped], dist
+
     def means(self):
         """(K, dim, 4): the mean of every cluster's members in the circuit's fixed-point arithmetic, qdiv(sum of the members' words,
         quantization(n_k)), in one values-only call over the resident grouped rows (vdb_ann_cluster_means_dev: nothing is emitted or

@@ -851,6 +851,43 @@ int vdb_ann_assign_dev(uint32_t precision_bits, uint32_t lookup_bits, int metric
 int vdb_ann_train_dev(uint32_t precision_bits, uint32_t lookup_bits, int metric, const vdb_fr *rows_dev, size_t n, size_t K, size_t dim,
                       size_t max_iterations, vdb_fr *centroids_dev, uint32_t *ids_dev, uint64_t *sizes_host, size_t *iterations_run);
 
+/* Batch search: the t nearest of Q queries as values, exact and over an index.
+ *
+ * The result, for one query over its candidates d_i = distance(candidate_i, query) (vdb_nearest_topk_values' operand order): the
+ * CLASSES are the distinct bit patterns among the d_i that come strictly before M = 2^(2P) - 1 in qmin's order; round r < t states
+ * the r-th class and the LARGEST index i at it; once the classes are used up every round states (M, last), last the query's largest
+ * candidate index.  Over the values the range checks admit this is vdb_nearest_topk_values_dev's (idx, dist) bit for bit, and at
+ * t = 1 vdb_ann_assign_dev's.  One fused, tiled kernel over a task list plus one merge kernel; no Q x n distances are held and Q n t
+ * has no limit.
+ *
+ * vdb_ann_search_dev: the dense form, every query against rows [0, n) of vectors.  queries: Q x dim; vectors: n x dim; idx_out:
+ * Q x t x uint32; dist_out: Q x t (may be NULL).  span: the database rows a workgroup walks (rounded up to the chunk); 0 lets the plan
+ * pick it so that few queries against a large database still fill the machine.  span changes the work split, never the result.
+ * vdb_ann_search_probed_dev: the index form.  grouped: the rows grouped by cluster, cluster k being rows [offsets[k], offsets[k + 1])
+ * (offsets: a HOST array of K + 1); clusters: a HOST array Q x p, the clusters query j probes in round order.  Query j's candidates
+ * are those clusters' members end to end in that order (vdb_wit_ann_probe's candidate list), idx_out indexes that list, last is
+ * N_j - 1.  The queries that probe a cluster share its staged members.
+ * Work space: t (32 + 4) + 4 bytes per (task, query) partial list, and under cosine one word per query and per row of the array.
+ * VDB_ERR_ARG before anything is launched (outputs untouched): a null pointer, an unknown metric, Q, n, dim or t zero, t > 64, t
+ * above a query's candidate count, Q or n above 2^32 - 1, dim above 2^24, more than 2^31 - 1 tasks or 2^32 - 1 partial lists; the
+ * index form also: K or p zero, p > K, a cluster >= K, offsets that do not rise from 0.  VDB_ERR_DOMAIN: a zero denominator (a zero
+ * query against a zero row under cosine), as vdb_ann_assign_dev reports it.
+ * vdb_ann_search_plan: the plan those calls launch with (csrc/ann_search_plan.hpp) and its refusals; needs no device.  The dense form
+ * where clusters is NULL (n counts, K and probes do not), else the index form.  cus: the compute units the span is sized for (0: 256).
+ * header: 10 x uint64: R queries of a tile, C rows of a chunk, t, span, LDS bytes, tasks, partial lists, entries of order, bytes of
+ * work space, words of norms.  Each array may be NULL (a first call reads the lengths): tasks: tasks x 6 x uint32 (q_start, q_count,
+ * v_lo, v_hi, idx_base, slot0: queries order[q_start ..] against rows [v_lo, v_hi), row v reported as idx_base + v - v_lo, query i of
+ * the tile writing list slot0 + i); order: the query numbers tile by tile; list_off (Q + 1), list_slots, list_base: query j merges
+ * the lists list_slots[list_off[j] .. list_off[j + 1]), adding list_base to their indices; last: Q. */
+int vdb_ann_search_plan(int metric, size_t Q, size_t n, size_t K, size_t dim, size_t probes, size_t t, size_t span, uint32_t cus,
+                        const uint64_t *offsets, const uint32_t *clusters, uint64_t *header, uint32_t *tasks, uint32_t *order, uint32_t *list_off,
+                        uint32_t *list_slots, uint32_t *list_base, uint32_t *last);
+int vdb_ann_search_dev(uint32_t precision_bits, uint32_t lookup_bits, int metric, const vdb_fr *queries_dev, const vdb_fr *vectors_dev, size_t Q,
+                       size_t n, size_t dim, size_t t, size_t span, uint32_t *idx_out_dev, vdb_fr *dist_out_dev);
+int vdb_ann_search_probed_dev(uint32_t precision_bits, uint32_t lookup_bits, int metric, const vdb_fr *queries_dev, const vdb_fr *grouped_dev,
+                              const uint64_t *offsets, const uint32_t *clusters, size_t Q, size_t K, size_t dim, size_t p, size_t t, size_t span,
+                              uint32_t *idx_out_dev, vdb_fr *dist_out_dev);
+
 /* ---- b4 stream -> columns: replaces halo2-base GateThreadBuilder::assign_all (break points, keygen)
  *      and assign_threads_in (prover) as driven by RangeCircuitBuilder::prover(builder, break_points)
  *      (src/scaffold/mod.rs:393-396).  Columns are 2^k rows; the cell on a break row is duplicated at
