@@ -124,6 +124,9 @@ _SIGNATURES = {
     "vdb_ann_search_plan": [_I, _SZ, _SZ, _SZ, _SZ, _SZ, _SZ, _SZ, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "vdb_ann_search_dev": [_U32, _U32, _I, _P, _P, _SZ, _SZ, _SZ, _SZ, _SZ, _P, _P],
     "vdb_ann_search_probed_dev": [_U32, _U32, _I, _P, _P, _P, _P, _SZ, _SZ, _SZ, _SZ, _SZ, _SZ, _P, _P],
+    "vdb_fp_pack_i64_dev": [_P, _SZ, _P],
+    "vdb_ann_search_i64_dev": [_U32, _U32, _I, _P, _P, _SZ, _SZ, _SZ, _SZ, _SZ, _P, _P],
+    "vdb_ann_search_probed_i64_dev": [_U32, _U32, _I, _P, _P, _P, _P, _SZ, _SZ, _SZ, _SZ, _SZ, _SZ, _P, _P],
     "vdb_wit_nearest_batch_size": [_I, _U32, _U32, _SZ, _SZ, _SZ, _P, _P],
     "vdb_wit_nearest_batch": [_I, _U32, _U32, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],
     "vdb_wit_nearest_batch_dev": [_I, _U32, _U32, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P],

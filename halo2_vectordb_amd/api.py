@@ -745,10 +745,47 @@ def ann_search_probed_dev(metric, d_queries, d_grouped, offsets, clusters, dim, 
                                                 d_dist.ptr if d_dist is not None else None))
 
 
-def ann_search(metric, queries, vectors, topk, P=48, L=13, span=0):
+def pack_i64_dev(d_words, count, d_out):
+    """vdb_fp_pack_i64_dev over device buffers: `count` field words of `d_words` as signed 64-bit integers into `d_out` (8 bytes a
+    word); VdbError -5 if a word is not packable (its signed value is outside -(2^63 - 1) .. 2^63 - 1)"""
+    check(_lib.init().vdb_fp_pack_i64_dev(d_words.ptr, _sz(count), d_out.ptr))
+
+
+def pack_i64(words):
+    """field words (..., 4) -> their packed values, an int64 array of the leading shape, through the device call"""
+    words = _fr(words)
+    count = words.size // 4
+    bufs = [DeviceBuffer(max(words.nbytes, 32)), DeviceBuffer(max(count * 8, 32))]
+    try:
+        bufs[0].upload(words)
+        pack_i64_dev(bufs[0], count, bufs[1])
+        return bufs[1].download(words.shape[:-1], dtype=np.int64)
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def ann_search_i64_dev(metric, d_queries, d_vectors, Q, n, dim, topk, d_idx, d_dist=None, span=0, P=48, L=13):
+    """vdb_ann_search_i64_dev over device buffers: ann_search_dev with packed (int64) queries and vectors"""
+    check(_lib.init().vdb_ann_search_i64_dev(ctypes.c_uint32(P), ctypes.c_uint32(L), METRICS[metric], d_queries.ptr, d_vectors.ptr, _sz(Q), _sz(n),
+                                             _sz(dim), _sz(topk), _sz(span), d_idx.ptr, d_dist.ptr if d_dist is not None else None))
+
+
+def ann_search_probed_i64_dev(metric, d_queries, d_grouped, offsets, clusters, dim, topk, d_idx, d_dist=None, span=0, P=48, L=13):
+    """vdb_ann_search_probed_i64_dev over device buffers: ann_search_probed_dev with packed (int64) queries and grouped rows"""
+    offsets, clusters = np.ascontiguousarray(offsets, dtype=np.uint64), np.ascontiguousarray(clusters, dtype=np.uint32)
+    Q, p = clusters.shape
+    check(_lib.init().vdb_ann_search_probed_i64_dev(ctypes.c_uint32(P), ctypes.c_uint32(L), METRICS[metric], d_queries.ptr, d_grouped.ptr, _p(offsets),
+                                                    _p(clusters), _sz(Q), _sz(offsets.size - 1), _sz(dim), _sz(p), _sz(topk), _sz(span), d_idx.ptr,
+                                                    d_dist.ptr if d_dist is not None else None))
+
+
+def ann_search(metric, queries, vectors, topk, P=48, L=13, span=0, packed=False):
     """the `topk` nearest of every row of `queries` (Q, dim, 4) among `vectors` (n, dim, 4) by the fused, tiled search
     (vdb_ann_search_dev): nearest_topk_values(metric, queries, vectors, topk)'s (idx (Q, t) uint32, dist (Q, t, 4)) bit for bit, with
-    no limit on Q * n * t.  `span`: the rows a workgroup walks (0: the plan's); it never changes the result."""
+    no limit on Q * n * t.  `span`: the rows a workgroup walks (0: the plan's); it never changes the result.  `packed`: both arrays
+    are packed to int64 on the device and searched by vdb_ann_search_i64_dev — the same result for packable words, VdbError -5 for
+    others."""
     _lib.init()
     queries, vectors = _fr(queries), _fr(vectors)
     Q, n, dim, t = queries.shape[0], vectors.shape[0], vectors.shape[1], int(topk)
@@ -757,7 +794,14 @@ def ann_search(metric, queries, vectors, topk, P=48, L=13, span=0):
     try:
         bufs[0].upload(queries)
         bufs[1].upload(vectors)
-        ann_search_dev(metric, bufs[0], bufs[1], Q, n, dim, t, bufs[2], bufs[3], span, P, L)
+        if packed:
+            bufs += [DeviceBuffer(max(Q * dim * 8, 32)), DeviceBuffer(max(n * dim * 8, 32))]
+            if Q * dim and n * dim:                                  # (an empty array goes to the search, which refuses it)
+                pack_i64_dev(bufs[0], Q * dim, bufs[4])
+                pack_i64_dev(bufs[1], n * dim, bufs[5])
+            ann_search_i64_dev(metric, bufs[4], bufs[5], Q, n, dim, t, bufs[2], bufs[3], span, P, L)
+        else:
+            ann_search_dev(metric, bufs[0], bufs[1], Q, n, dim, t, bufs[2], bufs[3], span, P, L)
         return bufs[2].download((Q, t), dtype=np.uint32), bufs[3].download((Q, t, 4))
     finally:
         for b in bufs:

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "ann_assign_plan.hpp"
+#include "ann_i64.hpp"
 #include "ann_search_plan.hpp"
 #include "ann_update_host.hpp"
 #include "common.hpp"
@@ -1449,6 +1450,153 @@ __global__ __launch_bounds__(64) void k_ann_search_merge(const u256* __restrict_
       if (dist_out) dist_out[(size_t)q * tk + lane] = lane < fill ? ev : M;
     }
   }
+}
+// ------------------------------------------------------------------ the batch search over PACKED rows (include/vdb.h
+// vdb_ann_search_i64_dev and vdb_ann_search_probed_i64_dev; ann_i64.hpp): k_ann_search with the head in native 64-bit
+// integers.  The tasks, the tile (R, C), order[], the lists, search_insert, the padding and `live` rules, the write-out and the merge are
+// k_ann_search's; the tail is assign_tail on the head sum converted to the field once a pair.  New are the stage and the head.
+//
+// The stage holds 8-byte words, ANN_I64_DC = 64 of the dim axis at a time.  LDS has 64 banks of 4 bytes: word w lies in the bank pair
+// w mod 32, and a wavefront's 8-byte access is free of conflicts when every 32 lanes touch 32 distinct pairs (or one address).
+//   queries [row][word], word d of row r at r 64 + ((d + r) mod 64): the C lanes of a row read one address (a broadcast); the 64 / C
+//     rows a wavefront reads at once are consecutive r, and the rotation by r puts them in the pairs (d + r) mod 32, all distinct —
+//     without it they would share one pair, their stride being 64 words.  A staging wavefront stores the 64 words of one row: a
+//     rotation of 64 consecutive words.
+//   vectors [word][row of the chunk] at d (C + 1) + j: consecutive lanes read consecutive words; the stride C + 1 is odd, so a
+//     staging wavefront — 64 consecutive d of one row j, read from 512 contiguous bytes of global memory — stores to distinct pairs.
+// (R + C + 1) 64 words are at most 41,472 B; with the lists 78,848 B a workgroup, two workgroups a CU as the field form.
+#define ANN_I64_STAGE_WORDS ((ANN_ASSIGN_R_MAX + ANN_ASSIGN_C_MIN + 1) * ANN_I64_DC)
+static_assert(ANN_I64_STAGE_WORDS >= 2 * ANN_ASSIGN_THREADS * ANN_ASSIGN_PAIRS, "the sums of a chunk (two words each) reuse the stage");
+static_assert(ANN_I64_EUCLID == M_EUCLID && ANN_I64_COSINE == M_COSINE && ANN_I64_MANHATTAN == M_MANHATTAN && ANN_I64_HAMMING == M_HAMMING,
+              "ann_i64.hpp names the metrics as this file does");
+// the head of one staged dim chunk for a lane's ANN_ASSIGN_PAIRS pairs: the vector's word once, the queries' words as broadcasts
+template <int METRIC>
+__device__ __forceinline__ void search_i64_head(ann_u128 (&acc)[ANN_ASSIGN_PAIRS], const int64_t* q_s, const int64_t* v_s, uint32_t dcur, uint32_t C,
+                                                uint32_t RG, uint32_t rg, uint32_t cl, uint32_t P) {
+  constexpr uint32_t DC = ANN_I64_DC;
+#pragma unroll 2
+  for (uint32_t d = 0; d < dcur; d++) {
+    const int64_t x = v_s[d * (C + 1) + cl];
+#pragma unroll
+    for (uint32_t p = 0; p < ANN_ASSIGN_PAIRS; p++) {
+      const uint32_t r = rg + RG * p;
+      acc[p] = ann_i64_accumulate<METRIC>(acc[p], x, q_s[r * DC + ((d + r) & (DC - 1))], P);
+    }
+  }
+}
+// Cosine's pre-pass over packed rows: norms[v] = sum_j (x_j x_j) >> P as a field word, a wavefront per vector; k_ann_norm_roots runs
+// on the result unchanged.
+__global__ __launch_bounds__(64) void k_ann_norm_sums_i64(const int64_t* __restrict__ vecs, uint64_t count, uint32_t dim, uint32_t P,
+                                                          u256* __restrict__ norms) {
+  for (uint64_t v = blockIdx.x; v < count; v += gridDim.x) {
+    const int64_t* x = vecs + (size_t)v * dim;
+    ann_u128 s = 0;
+    for (uint32_t i = threadIdx.x; i < dim; i += 64) s += ann_i64_norm_term(x[i], P);
+    for (int off = 32; off >= 1; off >>= 1) {
+      const unsigned long long lo = __shfl_xor((unsigned long long)s, off, 64), hi = __shfl_xor((unsigned long long)(s >> 64), off, 64);
+      s += ((ann_u128)hi << 64) | lo;
+    }
+    if (threadIdx.x == 0) norms[v] = ann_i64_sum_to_fr(s, false);
+  }
+}
+__global__ __launch_bounds__(ANN_ASSIGN_THREADS) void k_ann_search_i64(int metric, uint32_t P, const int64_t* __restrict__ queries,
+                                                                       const int64_t* __restrict__ vecs, const u256* __restrict__ q_norms,
+                                                                       const u256* __restrict__ v_norms, const uint32_t* __restrict__ order,
+                                                                       const AnnSearchTask* __restrict__ tasks, uint32_t dim, uint32_t C, uint32_t tk,
+                                                                       int* __restrict__ err, u256* __restrict__ list_val,
+                                                                       uint32_t* __restrict__ list_idx, uint32_t* __restrict__ list_cnt) {
+  __shared__ uint64_t stage[ANN_I64_STAGE_WORDS];
+  __shared__ u256 lv[ANN_SEARCH_LIST_WORDS];        // [row][t]
+  __shared__ uint32_t li[ANN_SEARCH_LIST_WORDS];
+  __shared__ uint32_t lc[ANN_ASSIGN_R_MAX];         // entries of a row's list
+  __shared__ uint32_t qn[ANN_ASSIGN_R_MAX];         // the tile's query numbers
+  constexpr uint32_t DC = ANN_I64_DC, TB = ANN_ASSIGN_THREADS, PP = ANN_ASSIGN_PAIRS;
+  const uint32_t t = threadIdx.x, RG = TB / C, R = RG * PP, cl = t & (C - 1), rg = t / C, base = (t & 63u) & ~(C - 1);
+  const AnnSearchTask* tk_ = tasks + blockIdx.x;
+  const uint32_t q_start = tk_->q_start, qc = tk_->q_count, v_lo = tk_->v_lo, v_hi = tk_->v_hi, idx_base = tk_->idx_base, slot0 = tk_->slot0;
+  int64_t* q_s = (int64_t*)stage;            // [R][DC], rotated by the row
+  int64_t* v_s = (int64_t*)stage + R * DC;   // [DC][C + 1]
+  WCtx c{};
+  const Gadgets g(c);   // the value-only helpers: they leave the context alone
+  const u256 M = nv_mask_value(&g.T);
+  int e = 0;
+  // padding as in k_ann_search: queries past the tile's last are staged as the last real one, rows past v_hi as row v_hi - 1
+  if (t < R) {
+    lc[t] = 0;
+    qn[t] = order[q_start + (t < qc ? t : qc - 1)];
+  }
+  for (uint64_t v0 = v_lo; v0 < v_hi; v0 += C) {
+    ann_u128 acc[PP];   // the lane's four head sums: registers across all dim chunks
+#pragma unroll
+    for (uint32_t p = 0; p < PP; p++) acc[p] = 0;
+    for (uint32_t d0 = 0; d0 < dim; d0 += DC) {
+      const uint32_t dcur = dim - d0 < DC ? dim - d0 : DC;
+      __syncthreads();   // qn; the readers of the stage before: the last dim chunk's, or the tail's of the chunk before
+      for (uint32_t e = t; e < (R + C) * DC; e += TB) {   // a wavefront takes the 64 words of one row: one 512-byte run of global memory
+        const uint32_t v = e / DC, d = e % DC;
+        if (d >= dcur) continue;
+        if (v < R) {
+          q_s[v * DC + ((d + v) & (DC - 1))] = queries[(size_t)qn[v] * dim + d0 + d];
+        } else {
+          const uint64_t vv = v0 + (v - R) < v_hi ? v0 + (v - R) : v_hi - 1;
+          v_s[d * (C + 1) + (v - R)] = vecs[(size_t)vv * dim + d0 + d];
+        }
+      }
+      __syncthreads();
+      switch (metric) {   // uniform: the test leaves the term loop
+        case M_EUCLID: search_i64_head<M_EUCLID>(acc, q_s, v_s, dcur, C, RG, rg, cl, P); break;
+        case M_COSINE: search_i64_head<M_COSINE>(acc, q_s, v_s, dcur, C, RG, rg, cl, P); break;
+        case M_MANHATTAN: search_i64_head<M_MANHATTAN>(acc, q_s, v_s, dcur, C, RG, rg, cl, P); break;
+        default: search_i64_head<M_HAMMING>(acc, q_s, v_s, dcur, C, RG, rg, cl, P); break;
+      }
+    }
+    // the sums leave the registers for the lane's own slots of the stage (low words, then high words), as in k_ann_search: one tail
+    // body walked PP times
+    __syncthreads();
+#pragma unroll
+    for (uint32_t p = 0; p < PP; p++) {
+      stage[p * TB + t] = (uint64_t)acc[p];
+      stage[(PP + p) * TB + t] = (uint64_t)(acc[p] >> 64);
+    }
+#pragma unroll 1
+    for (uint32_t p = 0; p < PP; p++) {
+      const uint32_t r = rg + RG * p;
+      const uint64_t vv = v0 + cl;
+      u256 as = u256_zero(), bs = u256_zero();
+      if (metric == M_COSINE) {
+        as = v_norms[vv < v_hi ? vv : v_hi - 1];
+        bs = q_norms[qn[r]];
+      }
+      // the integer sum is the field sum (ann_i64.hpp): once a pair to the field, then the field form's tail
+      const u256 s = ann_i64_sum_to_fr(((ann_u128)stage[(PP + p) * TB + t] << 64) | stage[p * TB + t], metric == M_COSINE);
+      WCtx ct = assign_ctx();   // a context of its own per tail: see k_ann_assign
+      Gadgets gt(ct);
+      const u256 dv = assign_tail(ct, gt, metric, dim, s, as, bs);
+      e |= ct.err;
+      const bool live = vv < v_hi && r < qc && search_before(g, dv, M);
+      search_insert(g, lv + r * tk, li + r * tk, lc + r, tk, C, base, cl, dv, idx_base + (uint32_t)(vv - v_lo), live);
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = t; i < qc * tk; i += TB) {
+    const uint32_t r = i / tk, l = i % tk;
+    if (l < lc[r]) {
+      list_val[(size_t)(slot0 + r) * tk + l] = lv[i];
+      list_idx[(size_t)(slot0 + r) * tk + l] = li[i];
+    }
+  }
+  if (t < qc) list_cnt[slot0 + t] = lc[t];
+  if (e) atomicOr(err, e);
+}
+// field words to packed words (include/vdb.h vdb_fp_pack_i64_dev), a lane a word; a word that is not packable raises the error word
+__global__ __launch_bounds__(256) void k_fp_pack_i64(const u256* __restrict__ words, uint64_t count, int64_t* __restrict__ out, int* __restrict__ err) {
+  int e = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (uint64_t)gridDim.x * 256) {
+    int64_t v;
+    if (!ann_i64_pack(words[i], &v)) e = 1;
+    out[i] = v;
+  }
+  if (e) atomicOr(err, e);
 }
 __global__ void k_push_cells(Streams st, uint64_t pos, u256 a, u256 b, uint32_t n) {
   if (blockIdx.x || threadIdx.x || n == 0) return;
@@ -3424,47 +3572,71 @@ static int ann_search_planned(int metric, size_t Q, size_t n, size_t K, size_t d
   if (rc) set_error("%s", why);
   return rc;
 }
-// the batch search on a plan: the plan's lists to the device, cosine's pre-pass over the queries and the `vec_rows` rows of the vectors
-// array, one launch of k_ann_search over the tasks, one of k_ann_search_merge over the queries.  The plan outlives the call's
+// the work space of a batch search on a plan, carved and filled: the plan's lists to the device.  The plan outlives the call's
 // synchronisation (the caller's check_err_flag): its vectors are the source of the uploads.
-static int ann_search_dev(FpEntry* fp, int metric, const AnnSearchPlan& pl, const u256* queries, const u256* vecs, size_t Q, size_t vec_rows, size_t dim,
-                          int* err, uint32_t* idx, u256* dist_out) {
-  Streams st{nullptr, nullptr, nullptr, err, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};   // the empty rank window: no stream is attached
-  TRY(set_winv(st, fp->dev));
+struct AnnSearchWork {
+  u256 *list_val, *norms;
+  uint32_t *list_idx, *list_cnt, *list_slots, *list_base, *order, *list_off, *last;
+  AnnSearchTask* tasks;
+};
+static int ann_search_work(const AnnSearchPlan& pl, size_t Q, AnnSearchWork* k) {
   const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t n_tasks = pl.tasks.size(), n_ent = pl.order.size(), n_slots = (size_t)pl.n_slots, t = pl.t;
   const size_t b_val = up(n_slots * t * sizeof(u256)), b_norm = up((size_t)pl.norm_words * sizeof(u256)), b_idx = up(n_slots * t * 4),
                b_slot = up(n_slots * 4), b_task = up(n_tasks * sizeof(AnnSearchTask)), b_ent = up(n_ent * 4), b_q = up((Q + 1) * 4);
   uint8_t* w = (uint8_t*)scratch_get(0, b_val + b_norm + b_idx + 3 * b_slot + b_task + b_ent + 2 * b_q);
   if (!w) return VDB_ERR_OOM;
-  u256 *list_val = (u256*)w, *norms = pl.norm_words ? (u256*)(w + b_val) : nullptr;
+  k->list_val = (u256*)w;
+  k->norms = pl.norm_words ? (u256*)(w + b_val) : nullptr;
   uint8_t* at = w + b_val + b_norm;
   const auto take = [&](size_t b) {
     uint8_t* r = at;
     at += b;
     return r;
   };
-  uint32_t *list_idx = (uint32_t*)take(b_idx), *list_cnt = (uint32_t*)take(b_slot), *list_slots = (uint32_t*)take(b_slot), *list_base = (uint32_t*)take(b_slot);
-  AnnSearchTask* tasks = (AnnSearchTask*)take(b_task);
-  uint32_t *order = (uint32_t*)take(b_ent), *list_off = (uint32_t*)take(b_q), *last = (uint32_t*)take(b_q);
+  k->list_idx = (uint32_t*)take(b_idx), k->list_cnt = (uint32_t*)take(b_slot), k->list_slots = (uint32_t*)take(b_slot), k->list_base = (uint32_t*)take(b_slot);
+  k->tasks = (AnnSearchTask*)take(b_task);
+  k->order = (uint32_t*)take(b_ent), k->list_off = (uint32_t*)take(b_q), k->last = (uint32_t*)take(b_q);
   hipStream_t s = ctx().stream;
-  VDB_HIP(hipMemcpyAsync(tasks, pl.tasks.data(), n_tasks * sizeof(AnnSearchTask), hipMemcpyHostToDevice, s));
-  VDB_HIP(hipMemcpyAsync(order, pl.order.data(), n_ent * 4, hipMemcpyHostToDevice, s));
-  VDB_HIP(hipMemcpyAsync(list_slots, pl.list_slots.data(), n_slots * 4, hipMemcpyHostToDevice, s));
-  VDB_HIP(hipMemcpyAsync(list_base, pl.list_base.data(), n_slots * 4, hipMemcpyHostToDevice, s));
-  VDB_HIP(hipMemcpyAsync(list_off, pl.list_off.data(), (Q + 1) * 4, hipMemcpyHostToDevice, s));
-  VDB_HIP(hipMemcpyAsync(last, pl.last.data(), Q * 4, hipMemcpyHostToDevice, s));
-  const size_t cap = (size_t)ctx().cu_count * 64;
+  VDB_HIP(hipMemcpyAsync(k->tasks, pl.tasks.data(), n_tasks * sizeof(AnnSearchTask), hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(k->order, pl.order.data(), n_ent * 4, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(k->list_slots, pl.list_slots.data(), n_slots * 4, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(k->list_base, pl.list_base.data(), n_slots * 4, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(k->list_off, pl.list_off.data(), (Q + 1) * 4, hipMemcpyHostToDevice, s));
+  VDB_HIP(hipMemcpyAsync(k->last, pl.last.data(), Q * 4, hipMemcpyHostToDevice, s));
+  return VDB_OK;
+}
+// the batch search on a plan: cosine's pre-pass over the queries and the `vec_rows` rows of the vectors array, one launch of the tile
+// kernel over the tasks, one of k_ann_search_merge over the queries.  `packed`: queries and vecs are int64 rows (ann_i64.hpp) and the
+// tile kernel is k_ann_search_i64, the norms' sums k_ann_norm_sums_i64; everything else is one path.
+static int ann_search_dev(FpEntry* fp, int metric, const AnnSearchPlan& pl, bool packed, const void* queries, const void* vecs, size_t Q, size_t vec_rows,
+                          size_t dim, int* err, uint32_t* idx, u256* dist_out) {
+  Streams st{nullptr, nullptr, nullptr, err, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};   // the empty rank window: no stream is attached
+  TRY(set_winv(st, fp->dev));
+  AnnSearchWork k;
+  TRY(ann_search_work(pl, Q, &k));
+  const size_t n_tasks = pl.tasks.size(), cap = (size_t)ctx().cu_count * 64;
+  const dim3 gq((unsigned)(Q < cap ? Q : cap)), gv((unsigned)(vec_rows < cap ? vec_rows : cap));
+  u256 *norms = k.norms, *v_norms = norms ? norms + Q : nullptr;
   if (norms) {
-    VDB_LAUNCH(k_ann_norm_sums, dim3((unsigned)(Q < cap ? Q : cap)), dim3(64), queries, (uint64_t)Q, (uint32_t)dim, norms);
-    VDB_LAUNCH(k_ann_norm_sums, dim3((unsigned)(vec_rows < cap ? vec_rows : cap)), dim3(64), vecs, (uint64_t)vec_rows, (uint32_t)dim, norms + Q);
+    if (packed) {
+      VDB_LAUNCH(k_ann_norm_sums_i64, gq, dim3(64), (const int64_t*)queries, (uint64_t)Q, (uint32_t)dim, fp->host.P, norms);
+      VDB_LAUNCH(k_ann_norm_sums_i64, gv, dim3(64), (const int64_t*)vecs, (uint64_t)vec_rows, (uint32_t)dim, fp->host.P, v_norms);
+    } else {
+      VDB_LAUNCH(k_ann_norm_sums, gq, dim3(64), (const u256*)queries, (uint64_t)Q, (uint32_t)dim, norms);
+      VDB_LAUNCH(k_ann_norm_sums, gv, dim3(64), (const u256*)vecs, (uint64_t)vec_rows, (uint32_t)dim, v_norms);
+    }
     const size_t groups = (Q + vec_rows + 63) / 64;
     VDB_LAUNCH(k_ann_norm_roots, dim3((unsigned)(groups < cap ? groups : cap)), dim3(64), norms, (uint64_t)(Q + vec_rows), err);
   }
-  VDB_LAUNCH(k_ann_search, dim3((unsigned)n_tasks), dim3(ANN_ASSIGN_THREADS), metric, queries, vecs, norms, norms ? norms + Q : nullptr, order, tasks,
-             (uint32_t)dim, pl.C, pl.t, err, list_val, list_idx, list_cnt);
-  VDB_LAUNCH(k_ann_search_merge, dim3((unsigned)(Q < cap ? Q : cap)), dim3(64), list_val, list_idx, list_cnt, list_off, list_slots, list_base, last,
-             (uint32_t)Q, pl.t, idx, dist_out);
+  if (packed)
+    VDB_LAUNCH(k_ann_search_i64, dim3((unsigned)n_tasks), dim3(ANN_ASSIGN_THREADS), metric, fp->host.P, (const int64_t*)queries, (const int64_t*)vecs, norms,
+               v_norms, k.order, k.tasks, (uint32_t)dim, pl.C, pl.t, err, k.list_val, k.list_idx, k.list_cnt);
+  else
+    VDB_LAUNCH(k_ann_search, dim3((unsigned)n_tasks), dim3(ANN_ASSIGN_THREADS), metric, (const u256*)queries, (const u256*)vecs, norms, v_norms, k.order,
+               k.tasks, (uint32_t)dim, pl.C, pl.t, err, k.list_val, k.list_idx, k.list_cnt);
+  VDB_LAUNCH(k_ann_search_merge, gq, dim3(64), k.list_val, k.list_idx, k.list_cnt, k.list_off, k.list_slots, k.list_base, k.last, (uint32_t)Q, pl.t, idx,
+             dist_out);
   return VDB_OK;
 }
 
@@ -4527,8 +4699,9 @@ int vdb_ann_search_plan(int metric, size_t Q, size_t n, size_t K, size_t dim, si
   if (last) memcpy(last, pl.last.data(), pl.last.size() * 4);
   return VDB_OK;
 }
-// the t nearest of every query by the fused, tiled search, values only (include/vdb.h): no stream, no window, no Q x n work space
-static int ann_search_entry(uint32_t P, uint32_t L, int metric, const vdb_fr* queries_dev, const vdb_fr* vectors_dev, const uint64_t* offsets,
+// the t nearest of every query by the fused, tiled search, values only (include/vdb.h): no stream, no window, no Q x n work space.
+// `packed`: the rows are int64 (the _i64 entries); the refusals, the plan and the outputs are the same
+static int ann_search_entry(uint32_t P, uint32_t L, int metric, bool packed, const void* queries_dev, const void* vectors_dev, const uint64_t* offsets,
                             const uint32_t* clusters, size_t Q, size_t n, size_t K, size_t dim, size_t probes, size_t t, size_t span, uint32_t* idx_out_dev,
                             vdb_fr* dist_out_dev) {
   VDB_REQUIRE_INIT();
@@ -4539,19 +4712,40 @@ static int ann_search_entry(uint32_t P, uint32_t L, int metric, const vdb_fr* qu
   TRY(get_fp(P, L, &fp));
   int* derr;
   TRY(err_word(&derr));
-  TRY(ann_search_dev(fp, metric, pl, as_u256(queries_dev), as_u256(vectors_dev), Q, clusters ? (size_t)offsets[K] : n, dim, derr, idx_out_dev,
-                     as_u256(dist_out_dev)));
+  TRY(ann_search_dev(fp, metric, pl, packed, queries_dev, vectors_dev, Q, clusters ? (size_t)offsets[K] : n, dim, derr, idx_out_dev, as_u256(dist_out_dev)));
   return check_err_flag(derr);   // (synchronizes: the plan's vectors may go)
 }
 int vdb_ann_search_dev(uint32_t P, uint32_t L, int metric, const vdb_fr* queries_dev, const vdb_fr* vectors_dev, size_t Q, size_t n, size_t dim, size_t t,
                        size_t span, uint32_t* idx_out_dev, vdb_fr* dist_out_dev) {
-  return ann_search_entry(P, L, metric, queries_dev, vectors_dev, nullptr, nullptr, Q, n, 0, dim, 0, t, span, idx_out_dev, dist_out_dev);
+  return ann_search_entry(P, L, metric, false, queries_dev, vectors_dev, nullptr, nullptr, Q, n, 0, dim, 0, t, span, idx_out_dev, dist_out_dev);
 }
 int vdb_ann_search_probed_dev(uint32_t P, uint32_t L, int metric, const vdb_fr* queries_dev, const vdb_fr* grouped_dev, const uint64_t* offsets,
                               const uint32_t* clusters, size_t Q, size_t K, size_t dim, size_t p, size_t t, size_t span, uint32_t* idx_out_dev,
                               vdb_fr* dist_out_dev) {
   VDB_ARG(offsets && clusters, "null pointer");
-  return ann_search_entry(P, L, metric, queries_dev, grouped_dev, offsets, clusters, Q, 0, K, dim, p, t, span, idx_out_dev, dist_out_dev);
+  return ann_search_entry(P, L, metric, false, queries_dev, grouped_dev, offsets, clusters, Q, 0, K, dim, p, t, span, idx_out_dev, dist_out_dev);
+}
+// the same two over packed rows (include/vdb.h; ann_i64.hpp)
+int vdb_ann_search_i64_dev(uint32_t P, uint32_t L, int metric, const int64_t* queries_dev, const int64_t* vectors_dev, size_t Q, size_t n, size_t dim,
+                           size_t t, size_t span, uint32_t* idx_out_dev, vdb_fr* dist_out_dev) {
+  return ann_search_entry(P, L, metric, true, queries_dev, vectors_dev, nullptr, nullptr, Q, n, 0, dim, 0, t, span, idx_out_dev, dist_out_dev);
+}
+int vdb_ann_search_probed_i64_dev(uint32_t P, uint32_t L, int metric, const int64_t* queries_dev, const int64_t* grouped_dev, const uint64_t* offsets,
+                                  const uint32_t* clusters, size_t Q, size_t K, size_t dim, size_t p, size_t t, size_t span, uint32_t* idx_out_dev,
+                                  vdb_fr* dist_out_dev) {
+  VDB_ARG(offsets && clusters, "null pointer");
+  return ann_search_entry(P, L, metric, true, queries_dev, grouped_dev, offsets, clusters, Q, 0, K, dim, p, t, span, idx_out_dev, dist_out_dev);
+}
+// field words to packed words, a lane a word (include/vdb.h): VDB_ERR_DOMAIN where a word is not packable
+int vdb_fp_pack_i64_dev(const vdb_fr* words_dev, size_t count, int64_t* out_dev) {
+  VDB_REQUIRE_INIT();
+  VDB_ARG(words_dev && out_dev, "null pointer");
+  VDB_ARG(count > 0, "count = 0");
+  int* derr;
+  TRY(err_word(&derr));
+  const size_t blocks = (count + 255) / 256, cap = (size_t)ctx().cu_count * 16;
+  VDB_LAUNCH(k_fp_pack_i64, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), as_u256(words_dev), (uint64_t)count, out_dev, derr);
+  return check_err_flag(derr);
 }
 // Lloyd iterations on the device (include/vdb.h): assign, count the changes, stop at none, group, means.  The ids alternate between
 // ids_dev and a buffer of the call's; `cur` is the assignment the centroids are the means of.

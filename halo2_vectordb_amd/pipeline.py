@@ -1447,20 +1447,50 @@ class AnnIndex:
             for b in (d_rows, d_idx, d_dist):
                 b.free()
 
-    def _search_call(self, queries, topk, call):
-        """upload the (Q, dim) f64 `queries` quantized, run call(d_queries, Q, d_idx, d_dist) and bring back (idx (Q, t) int64, dist (Q, t, 4))"""
+    def _packed(self):
+        """(d_grouped, d_cent) as packed int64 rows (vdb_fp_pack_i64_dev), a quarter of the size each: made at the first packed
+        search and kept until free().  ValueError: the index holds a word that is not packable."""
+        if getattr(self, "d_packed", None) is None:
+            bufs = [api.DeviceBuffer(max(m * self.dim * 8, 32)) for m in (self.n, self.K)]
+            try:
+                for what, src, m, dst in (("row", self.d_grouped, self.n, bufs[0]), ("centroid", self.d_cent, self.K, bufs[1])):
+                    try:
+                        api.pack_i64_dev(src, m * self.dim, dst)
+                    except api.VdbError as e:
+                        if e.code != -5:
+                            raise
+                        raise ValueError(f"the index holds a {what} word that is not packable: its signed value does not fit 64 bits") from e
+            except Exception:
+                for b in bufs:
+                    b.free()
+                raise
+            self._bufs += bufs
+            self.d_packed = tuple(bufs)
+        return self.d_packed
+
+    def _search_call(self, queries, topk, call, packed=False):
+        """upload the (Q, dim) f64 `queries` quantized (`packed`: and pack them), run call(d_queries, Q, d_idx, d_dist) and bring back
+        (idx (Q, t) int64, dist (Q, t, 4))"""
         rows = np.ascontiguousarray(queries, dtype=np.float64).reshape(-1, self.dim)
         Q, t = rows.shape[0], int(topk)
         bufs = [api.DeviceBuffer(max(b, 32)) for b in (Q * self.dim * B, Q * t * 4, Q * t * B)]
         try:
             bufs[0].upload(api.quantize(rows, self.P))
-            call(bufs[0], Q, bufs[1], bufs[2])
+            if packed and Q:
+                bufs.append(api.DeviceBuffer(max(Q * self.dim * 8, 32)))
+                try:
+                    api.pack_i64_dev(bufs[0], Q * self.dim, bufs[3])
+                except api.VdbError as e:
+                    if e.code != -5:
+                        raise
+                    raise ValueError("a query holds a word that is not packable: its signed value does not fit 64 bits") from e
+            call(bufs[3] if packed and Q else bufs[0], Q, bufs[1], bufs[2])
             return bufs[1].download((Q, t), dtype=np.uint32).astype(np.int64), bufs[2].download((Q, t, 4))
         finally:
             for b in bufs:
                 b.free()
 
-    def search(self, queries, probes=1, topk=1, span=0):
+    def search(self, queries, probes=1, topk=1, span=0, packed=False):
         """the `topk` nearest among the members of the `probes` clusters nearest to every row of `queries` ((Q, dim) f64), as values, in
         two batch calls.  Stage 1: `probes` rounds over the resident centroids for all queries at once (vdb_ann_search_dev) and one
         read-back of Q * probes ids; row j of `clusters` is probe_many(q_j, probes).  Stage 2: the (query, cluster) pairs grouped by
@@ -1469,8 +1499,11 @@ class AnnIndex:
         round order, AnnProbeQueryHotPath's —, slots (Q, t): database slots through d_slots, as AnnProbeQueryHotPath.neighbours(), dist
         (Q, t, 4)), nearest first: the rounds vdb_wit_ann_probe states.  ValueError naming the first query whose probed clusters are
         not pairwise distinct (fewer than `probes` distance classes among the centroids; AnnProbeQueryHotPath refuses it too), or the
-        first with fewer than `topk` candidates."""
+        first with fewer than `topk` candidates.  `packed`: both stages run over packed int64 rows (_packed(), the queries packed per
+        call; vdb_ann_search_i64_dev and vdb_ann_search_probed_i64_dev) — the same result; ValueError for a word that is not packable."""
         p, t, name = int(probes), int(topk), self.metric_name
+        dense, probed = (api.ann_search_i64_dev, api.ann_search_probed_i64_dev) if packed else (api.ann_search_dev, api.ann_search_probed_dev)
+        d_grouped, d_cent = self._packed() if packed else (self.d_grouped, self.d_cent)
         if not 1 <= p <= self.K:
             raise ValueError("probes: at least 1 and at most K")
         rows = np.ascontiguousarray(queries, dtype=np.float64).reshape(-1, self.dim)
@@ -1479,7 +1512,7 @@ class AnnIndex:
         def call(d_q, Q, d_idx, d_dist):
             d_cl = api.DeviceBuffer(max(Q * p * 4, 32))
             try:
-                api.ann_search_dev(name, d_q, self.d_cent, Q, self.K, self.dim, p, d_cl, None, 0, self.P, self.L)
+                dense(name, d_q, d_cent, Q, self.K, self.dim, p, d_cl, None, 0, self.P, self.L)
                 clusters = d_cl.download((Q, p), dtype=np.uint32)
             finally:
                 d_cl.free()
@@ -1492,22 +1525,23 @@ class AnnIndex:
             if short.size:
                 raise ValueError(f"query {int(short[0])}: fewer than `topk` candidates in the clusters probed")
             out["cand_offsets"] = np.concatenate([np.zeros((Q, 1), dtype=np.int64), np.cumsum(sizes, axis=1)], axis=1)
-            api.ann_search_probed_dev(name, d_q, self.d_grouped, self.offsets, clusters, self.dim, t, d_idx, d_dist, span, self.P, self.L)
+            probed(name, d_q, d_grouped, self.offsets, clusters, self.dim, t, d_idx, d_dist, span, self.P, self.L)
 
-        cand, dist = self._search_call(rows, t, call)
+        cand, dist = self._search_call(rows, t, call, packed)
         off = out.pop("cand_offsets")
         r = np.asarray([np.searchsorted(off[j], cand[j], side="right") - 1 for j in range(cand.shape[0])], dtype=np.int64).reshape(cand.shape)
         grouped = self.offsets[np.take_along_axis(out["clusters"], r, axis=1)] + cand - np.take_along_axis(off, r, axis=1)
         slots = self.d_slots.download((self.n,), dtype=np.uint32).astype(np.int64)
         return dict(clusters=out["clusters"], candidates=cand, slots=slots[grouped], dist=dist)
 
-    def search_exact(self, queries, topk, span=0):
+    def search_exact(self, queries, topk, span=0, packed=False):
         """the exact `topk` nearest of every row of `queries` ((Q, dim) f64) over ALL rows of the index (vdb_ann_search_dev over
         d_grouped), for measuring search()'s recall -> (slots (Q, t) int64: database slots through d_slots, dist (Q, t, 4)), nearest
         first.  The rows are searched in GROUPED order: among rows at equal distance a round states the last in grouped order, which
-        need not be the last in database order; the distances are the same either way."""
-        grouped, dist = self._search_call(queries, topk, lambda d_q, Q, d_idx, d_dist: api.ann_search_dev(
-            self.metric_name, d_q, self.d_grouped, Q, self.n, self.dim, int(topk), d_idx, d_dist, span, self.P, self.L))
+        need not be the last in database order; the distances are the same either way.  `packed`: as in search()."""
+        dense, d_grouped = (api.ann_search_i64_dev, self._packed()[0]) if packed else (api.ann_search_dev, self.d_grouped)
+        grouped, dist = self._search_call(queries, topk, lambda d_q, Q, d_idx, d_dist: dense(
+            self.metric_name, d_q, d_grouped, Q, self.n, self.dim, int(topk), d_idx, d_dist, span, self.P, self.L), packed)
         slots = self.d_slots.download((self.n,), dtype=np.uint32).astype(np.int64)
         return slots[grouped], dist
 
@@ -1568,7 +1602,7 @@ class AnnIndex:
         for b in self._bufs:
             b.free()
         self._bufs = []
-        self.d_db_tree = None
+        self.d_db_tree = self.d_packed = None
 
 
 def _bind_cluster(hp, index, cluster):

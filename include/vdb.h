@@ -888,6 +888,25 @@ int vdb_ann_search_probed_dev(uint32_t precision_bits, uint32_t lookup_bits, int
                               const uint64_t *offsets, const uint32_t *clusters, size_t Q, size_t K, size_t dim, size_t p, size_t t, size_t span,
                               uint32_t *idx_out_dev, vdb_fr *dist_out_dev);
 
+/* ---- Batch search over PACKED rows: one signed 64-bit integer a coordinate, the head of every distance in native integers.
+ * The packed word and its domain: the signed value of a field word a (canonical, 0 <= a < r) is a when a < 2^63 and -(r - a) when
+ * r - a < 2^63; every other word is NOT PACKABLE, so the value -2^63 is excluded.  The definition does not depend on P.
+ * vdb_fp_quantize of real data of magnitude below 2^(63 - P) lies in the domain.
+ * vdb_fp_pack_i64_dev: out_dev[i] = the packed value of words_dev[i] (Montgomery form, as everywhere), count words.  VDB_ERR_DOMAIN if
+ * any word is not packable (out_dev is then undefined); VDB_ERR_ARG for a null pointer or count == 0.
+ * vdb_ann_search_i64_dev / vdb_ann_search_probed_i64_dev: vdb_ann_search_dev / vdb_ann_search_probed_dev argument for argument with
+ * int64_t rows (queries: Q x dim, vectors / grouped: rows x dim, 8 bytes a coordinate).  For rows that are the packed values of field
+ * words they return exactly what the field forms return for those words, idx_out and dist_out (still vdb_fr) bit for bit: a term of a
+ * head sum is a 64 x 64 -> 128-bit integer product shifted right by P (the floor, which is what the field form's signed rescale takes),
+ * a sum stays below 2^120, and the tail of a distance runs in the field on the converted sum.  The same refusals before any launch,
+ * the same VDB_ERR_DOMAIN rule, the same work space. */
+int vdb_fp_pack_i64_dev(const vdb_fr *words_dev, size_t count, int64_t *out_dev);
+int vdb_ann_search_i64_dev(uint32_t precision_bits, uint32_t lookup_bits, int metric, const int64_t *queries_dev, const int64_t *vectors_dev, size_t Q,
+                           size_t n, size_t dim, size_t t, size_t span, uint32_t *idx_out_dev, vdb_fr *dist_out_dev);
+int vdb_ann_search_probed_i64_dev(uint32_t precision_bits, uint32_t lookup_bits, int metric, const int64_t *queries_dev, const int64_t *grouped_dev,
+                                  const uint64_t *offsets, const uint32_t *clusters, size_t Q, size_t K, size_t dim, size_t p, size_t t, size_t span,
+                                  uint32_t *idx_out_dev, vdb_fr *dist_out_dev);
+
 /* ---- b4 stream -> columns: replaces halo2-base GateThreadBuilder::assign_all (break points, keygen)
  *      and assign_threads_in (prover) as driven by RangeCircuitBuilder::prover(builder, break_points)
  *      (src/scaffold/mod.rs:393-396).  Columns are 2^k rows; the cell on a break row is duplicated at
